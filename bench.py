@@ -15,6 +15,9 @@ Extra objects in the line (DESIGN.md "Measurement"):
                 HIP events on its stream, single stream) vs 8 TB/s, PMC traffic beside it; the whole frame alone and pipelined; BVH bytes by
                 where they are served from; VALU issue against the chip's best and against the ceiling at the kernels' occupancy
   cpu_baseline  the CPU oracle (oracle/, OpenMP) timed on this host on a bounded row slab of the same frame
+
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs) as DIR/<name>.npy, so that two builds run with
+the same arguments can be compared output for output (a DIR under build/ stays out of git).
 """
 import argparse
 import json
@@ -30,6 +33,8 @@ import __graft_entry__ as ge  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: 8.0 TB/s spec
 BAND = 16
+DUMP_BYTES = 64_000_000         # --dump-outputs: at most this much in all, .npy headers included
+DUMP_SEED = 0                   # the pixel sample of a frame too large for DUMP_BYTES
 
 WORKLOADS = {
     # name: (scene factory kwargs, width, height, spp, bounces, description)
@@ -166,6 +171,42 @@ def self_launch(n):
     return rc
 
 
+def texture_values(a):
+    """A texture as textures_to_numpy returns it (raw DXGI format) -> the float32 values it stands for: RGBA/R 32F as they are,
+    16F bits decoded, 16-bit SNORM as max(v / 32767, -1), 8-bit UNORM as v / 255. Every decoding is exact and one-to-one."""
+    if a.dtype == np.float32:
+        return a
+    if a.dtype == np.uint16:
+        return a.view(np.float16).astype(np.float32)
+    if a.dtype == np.int16:
+        return np.maximum(a.astype(np.float32) / np.float32(32767.0), np.float32(-1.0))
+    if a.dtype == np.uint8:
+        return a.astype(np.float32) / np.float32(255.0)
+    raise TypeError(f"no float decoding for texture dtype {a.dtype}")
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: (rows, width, channels) float32} as out_dir/<name>.npy. A frame that fits DUMP_BYTES is written whole; a larger
+    one as the same fixed, seeded sample of pixels from every array, (n, channels) each, with the row-major pixel indices
+    (exact integers in float64) in out_dir/sample_pixels.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {a.shape[:2] for a in arrays.values()}
+    assert len(shapes) == 1, f"outputs of different frame sizes: {shapes}"
+    rows, width = shapes.pop()
+    pixels = rows * width
+    header = 4096 * (len(arrays) + 1)                             # generous bound on the .npy headers
+    per_pixel = sum(a.shape[2] * 4 for a in arrays.values())
+    if pixels * per_pixel + header <= DUMP_BYTES:
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        return
+    n = (DUMP_BYTES - header) // (per_pixel + 8)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(pixels, n, replace=False))
+    np.save(os.path.join(out_dir, "sample_pixels.npy"), idx.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a.reshape(pixels, -1)[idx], dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -191,7 +232,12 @@ def main():
                          "the frame's 68 bands travel by grouped ncclSend / ncclRecv to the rank itself (PT_DEBUG_GATHER_SELF_EXCHANGE)")
     ap.add_argument("--launch-check", action="store_true",
                     help="developer aid / CPU test: stop after the process group is up (gloo, no GPU touched) and print the world size")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): the frame's G-buffer and "
+                         "Radiance textures on one GPU, rank 0's gathered Radiance frame with N > 1; a fixed pixel sample when above 64 MB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # `python bench.py --gpus N` with N > 1 and no torchrun environment: start the N ranks ourselves, as a CHILD process
     # (never exec: nothing here has touched the GPU yet, and nothing may before this point), relay rank 0's one JSON line
@@ -327,6 +373,13 @@ def main():
     elapsed = time.perf_counter() - t0
     counters = [lane.ctx.counters() for lane in lanes]
     primary = sum(c.PrimaryRays for c in counters); secondary = sum(c.SecondaryRays for c in counters)
+    if args.dump_outputs and rank == 0:                         # after the clock stopped, before anything below renders again
+        last = lanes[(args.warmup + args.steps - 1) % len(lanes)]
+        if collective:                                          # what rank 0's caller receives: the gathered frame
+            outputs = {"Radiance": last.full.cpu().numpy().view(np.uint16)}
+        else:
+            outputs = P.textures_to_numpy(last.renderer.textures)
+        dump_outputs(args.dump_outputs, {k: texture_values(v) for k, v in outputs.items()})
 
     rays_local = float(primary + secondary)
     t = torch.tensor([elapsed, rays_local, float(secondary)], dtype=torch.float64, device=device)

@@ -58,3 +58,36 @@ def test_cpu_baseline_states_the_cores_it_really_uses():
     assert out["one_thread"]["cores"] == 1 and out["one_thread"]["value"] > 0
     assert 0 < out["parallel_efficiency"] <= 1.5 and out["host"]["sched_affinity"] == share["sched_affinity"]
     assert np.isfinite(out["value"])
+
+
+def test_dump_outputs_decodes_exactly_and_samples_large_frames_under_the_cap(tmp_path):
+    """--dump-outputs: texture formats decode to float32 one-to-one; a frame above the cap becomes the same seeded pixel sample of every
+    array, with its indices beside it, and stays under 64 MB on disk."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    h = np.array([0x3C00, 0xC000, 0x7C00, 0x0001], np.uint16)
+    assert bench.texture_values(h).tolist() == [1.0, -2.0, float("inf"), float(np.float16(2 ** -24))]
+    assert bench.texture_values(np.array([32767, -32768, 0], np.int16)).tolist() == [1.0, -1.0, 0.0]
+    assert bench.texture_values(np.array([255, 0], np.uint8)).tolist() == [1.0, 0.0]
+
+    rng = np.random.default_rng(5)
+    small = {"Radiance": rng.random((9, 16, 4), dtype=np.float32), "LinearDepth": rng.random((9, 16, 1), dtype=np.float32)}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    assert sorted(os.listdir(tmp_path / "small")) == ["LinearDepth.npy", "Radiance.npy"]
+    assert np.array_equal(np.load(tmp_path / "small" / "Radiance.npy"), small["Radiance"])
+
+    H, W = 2160, 3840                                               # C4's frame: 133 MB of Radiance alone
+    big = {"Radiance": np.arange(H * W * 4, dtype=np.float32).reshape(H, W, 4), "IOR": np.arange(H * W, dtype=np.float32).reshape(H, W, 1)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["IOR.npy", "Radiance.npy", "sample_pixels.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64_000_000
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    idx = np.load(tmp_path / "a" / "sample_pixels.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and idx.size > H * W // 4
+    rad = np.load(tmp_path / "a" / "Radiance.npy")
+    assert rad.dtype == np.float32 and rad.shape == (idx.size, 4)
+    assert np.array_equal(rad, big["Radiance"].reshape(-1, 4)[idx.astype(np.int64)])
