@@ -73,6 +73,69 @@ PT_DEV f4 texture_sample(const HeapEntry& t, const float* srgbLut, float u, floa
     return bilinear(t, srgbLut, 0, u * W - 0.5f, v * H - 0.5f, true);
 }
 
+// Seamless cube filtering (D3D10+ TextureCube sampling): a bilinear tap that leaves the face is fetched from the adjacent
+// face, and the one tap of a footprint that leaves through both coordinates (a cube corner) is the mean of the other three,
+// which are the three texels meeting at that corner. Integer lattice of the cube [-N, N]^3 in half-texel units: texel (x, y)
+// of a face sits at (M, S, T) = (N, 2x+1-N, 2y+1-N) in face-local axes; a tap one texel beyond an edge has |S| = N+1 (or
+// |T| = N+1), and its neighbour across the edge is (N-1, ±N, T): the adjacent face's edge texel. Exact in integers.
+PT_DEV void cube_across_edge(uint32_t& face, int N, int& x, int& y)
+{
+    int M = N, S = 2 * x + 1 - N, T = 2 * y + 1 - N;
+    if (S < -N || S > N) { S = S < 0 ? -N : N; M = N - 1; }
+    else { T = T < 0 ? -N : N; M = N - 1; }
+    int X, Y, Z;                                               // face-local -> world, the inverse of the face table in cube_sample
+    switch (face) {
+    case 0: X = M; Y = -T; Z = -S; break;
+    case 1: X = -M; Y = -T; Z = S; break;
+    case 2: X = S; Y = M; Z = T; break;
+    case 3: X = S; Y = -M; Z = -T; break;
+    case 4: X = S; Y = -T; Z = M; break;
+    default: X = -S; Y = -T; Z = -M; break;
+    }
+    const int ax = X < 0 ? -X : X, ay = Y < 0 ? -Y : Y;       // |major| = N, the other two <= N-1: no tie
+    int sc, tc;
+    if (ax == N) { if (X > 0) { face = 0; sc = -Z; tc = -Y; } else { face = 1; sc = Z; tc = -Y; } }
+    else if (ay == N) { if (Y > 0) { face = 2; sc = X; tc = Z; } else { face = 3; sc = X; tc = -Z; } }
+    else { if (Z > 0) { face = 4; sc = X; tc = -Y; } else { face = 5; sc = -X; tc = -Y; } }
+    x = (sc + N - 1) / 2; y = (tc + N - 1) / 2;
+}
+
+// Out of line: taken only when a tap of the footprint leaves the face (within half a texel of an edge). The texture goes by
+// value: a reference to the caller's HeapEntry would make the caller keep it in scratch memory.
+__device__ __attribute__((noinline)) f4 cube_bilinear_seam(const void* ptr, uint32_t N_, uint32_t fmt, const float* srgbLut, uint32_t face, float fx, float fy)
+{
+    const HeapEntry t{ ptr, (uint64_t)N_ | ((uint64_t)N_ << 32), fmt, kKindTextureCube };
+    const int N = (int)N_;
+    const float x0f = floorf(fx), y0f = floorf(fy);
+    const float wx = fx - x0f, wy = fy - y0f;
+    int x0 = (int)x0f, y0 = (int)y0f;
+    x0 = x0 < -1 ? -1 : (x0 > N - 1 ? N - 1 : x0); y0 = y0 < -1 ? -1 : (y0 > N - 1 ? N - 1 : y0);
+    f4 c[4];                                                   // (x0,y0) (x1,y0) (x0,y1) (x1,y1); unrolled: static indices, no scratch
+    int corner = -1;
+    #pragma unroll
+    for (int k = 0; k < 4; k++) {
+        int x = x0 + (k & 1), y = y0 + (k >> 1);
+        const bool outX = x < 0 || x >= N, outY = y < 0 || y >= N;
+        if (outX && outY) { corner = k; c[k] = f4{ 0.0f, 0.0f, 0.0f, 0.0f }; continue; }
+        uint32_t f = face;
+        if (outX || outY) cube_across_edge(f, N, x, y);
+        c[k] = texel_fetch(t, srgbLut, f, (uint32_t)x, (uint32_t)y);
+    }
+    #pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (corner != k) continue;
+        const f4 a = c[k ^ 3], b = c[k ^ 1], d = c[k ^ 2];      // diagonal, then the x- and y-neighbours
+        c[k].x = (a.x + b.x + d.x) / 3.0f; c[k].y = (a.y + b.y + d.y) / 3.0f;
+        c[k].z = (a.z + b.z + d.z) / 3.0f; c[k].w = (a.w + b.w + d.w) / 3.0f;
+    }
+    f4 o;
+    { float top = mad(c[1].x, wx, c[0].x * (1.0f - wx)), bot = mad(c[3].x, wx, c[2].x * (1.0f - wx)); o.x = mad(bot, wy, top * (1.0f - wy)); }
+    { float top = mad(c[1].y, wx, c[0].y * (1.0f - wx)), bot = mad(c[3].y, wx, c[2].y * (1.0f - wx)); o.y = mad(bot, wy, top * (1.0f - wy)); }
+    { float top = mad(c[1].z, wx, c[0].z * (1.0f - wx)), bot = mad(c[3].z, wx, c[2].z * (1.0f - wx)); o.z = mad(bot, wy, top * (1.0f - wy)); }
+    { float top = mad(c[1].w, wx, c[0].w * (1.0f - wx)), bot = mad(c[3].w, wx, c[2].w * (1.0f - wx)); o.w = mad(bot, wy, top * (1.0f - wy)); }
+    return o;
+}
+
 PT_DEV f4 cube_sample(const HeapEntry& t, const float* srgbLut, v3 d)
 {
     const float W = (float)(uint32_t)(t.bytes & 0xFFFFFFFFu), H = (float)(uint32_t)(t.bytes >> 32);
@@ -82,7 +145,12 @@ PT_DEV f4 cube_sample(const HeapEntry& t, const float* srgbLut, v3 d)
     else if (ay >= az) { ma = ay; if (d.y >= 0.0f) { face = 2; sc = d.x; tc = d.z; } else { face = 3; sc = d.x; tc = -d.z; } }
     else { ma = az; if (d.z >= 0.0f) { face = 4; sc = d.x; tc = -d.y; } else { face = 5; sc = -d.x; tc = -d.y; } }
     const float u = (sc / ma + 1.0f) * 0.5f, v = (tc / ma + 1.0f) * 0.5f;
-    return bilinear(t, srgbLut, face, u * W - 0.5f, v * H - 0.5f, false);
+    const float fx = u * W - 0.5f, fy = v * H - 0.5f;
+    const float x0f = floorf(fx), y0f = floorf(fy);
+    // u, v in [0, 1]: x0 in [-1, N-1]. A NaN direction fails every comparison and stays on the clamped in-face path.
+    if (__builtin_expect(x0f < 0.0f || y0f < 0.0f || x0f + 1.0f > W - 1.0f || y0f + 1.0f > H - 1.0f, 0))
+        return cube_bilinear_seam(t.ptr, (uint32_t)(t.bytes & 0xFFFFFFFFu), t.stride, srgbLut, face, fx, fy);
+    return bilinear(t, srgbLut, face, fx, fy, false);
 }
 
 struct TexCoords { float uv[2][2]; };

@@ -694,7 +694,60 @@ void or_texture_sample(const OrHeapEntry* t, float u, float v, float out[4])
     bilinear(t, 0, u * W - 0.5f, v * H - 0.5f, 1, out);
 }
 
-/* TextureCube.SampleLevel: D3D face selection (major axis), bilinear inside the face, clamped at its border */
+/* Seamless cube filtering (D3D10+ TextureCube sampling): a bilinear tap that leaves the face is fetched from the adjacent
+   face, and the one tap of a footprint that leaves through both coordinates (a cube corner) is the mean of the other three,
+   which are the three texels meeting at that corner. Integer lattice of the cube [-N, N]^3 in half-texel units: texel (x, y)
+   of a face sits at (M, S, T) = (N, 2x+1-N, 2y+1-N) in face-local axes; a tap one texel beyond an edge has |S| = N+1 (or
+   |T| = N+1), and its neighbour across the edge is (N-1, +-N, T): the adjacent face's edge texel. Exact in integers.
+   Same operations as pt_texture.hpp cube_across_edge / cube_bilinear_seam. */
+static void cube_across_edge(uint32_t* face, int N, int* x, int* y)
+{
+    int M = N, S = 2 * *x + 1 - N, T = 2 * *y + 1 - N;
+    if (S < -N || S > N) { S = S < 0 ? -N : N; M = N - 1; }
+    else { T = T < 0 ? -N : N; M = N - 1; }
+    int X, Y, Z;                                               /* face-local -> world, the inverse of the face table below */
+    switch (*face) {
+    case 0: X = M; Y = -T; Z = -S; break;
+    case 1: X = -M; Y = -T; Z = S; break;
+    case 2: X = S; Y = M; Z = T; break;
+    case 3: X = S; Y = -M; Z = -T; break;
+    case 4: X = S; Y = -T; Z = M; break;
+    default: X = -S; Y = -T; Z = -M; break;
+    }
+    int ax = X < 0 ? -X : X, ay = Y < 0 ? -Y : Y, sc, tc;      /* |major| = N, the other two <= N-1: no tie */
+    if (ax == N) { if (X > 0) { *face = 0; sc = -Z; tc = -Y; } else { *face = 1; sc = Z; tc = -Y; } }
+    else if (ay == N) { if (Y > 0) { *face = 2; sc = X; tc = Z; } else { *face = 3; sc = X; tc = -Z; } }
+    else { if (Z > 0) { *face = 4; sc = X; tc = -Y; } else { *face = 5; sc = -X; tc = -Y; } }
+    *x = (sc + N - 1) / 2; *y = (tc + N - 1) / 2;
+}
+
+static void cube_bilinear_seam(const OrHeapEntry* t, uint32_t face, float fx, float fy, float out[4])
+{
+    const int N = (int)(uint32_t)(t->Bytes & 0xFFFFFFFFu);
+    float x0f = floorf(fx), y0f = floorf(fy);
+    float wx = fx - x0f, wy = fy - y0f;
+    int x0 = (int)x0f, y0 = (int)y0f;
+    x0 = x0 < -1 ? -1 : (x0 > N - 1 ? N - 1 : x0); y0 = y0 < -1 ? -1 : (y0 > N - 1 ? N - 1 : y0);
+    float c[4][4] = { { 0 } };                                 /* (x0,y0) (x1,y0) (x0,y1) (x1,y1) */
+    int corner = -1;
+    for (int k = 0; k < 4; k++) {
+        int x = x0 + (k & 1), y = y0 + (k >> 1);
+        int outX = x < 0 || x >= N, outY = y < 0 || y >= N;
+        if (outX && outY) { corner = k; continue; }
+        uint32_t f = face;
+        if (outX || outY) cube_across_edge(&f, N, &x, &y);
+        texel_fetch(t, f, (uint32_t)x, (uint32_t)y, c[k]);
+    }
+    if (corner >= 0)                                           /* diagonal, then the x- and y-neighbours */
+        for (int q = 0; q < 4; q++) c[corner][q] = (c[corner ^ 3][q] + c[corner ^ 1][q] + c[corner ^ 2][q]) / 3.0f;
+    for (int q = 0; q < 4; q++) {
+        float top = mad(c[1][q], wx, c[0][q] * (1.0f - wx));
+        float bot = mad(c[3][q], wx, c[2][q] * (1.0f - wx));
+        out[q] = mad(bot, wy, top * (1.0f - wy));
+    }
+}
+
+/* TextureCube.SampleLevel: D3D face selection (major axis; ties go to X, then Y), bilinear, seamless across face edges */
 void or_cube_sample(const OrHeapEntry* t, const float d[3], float out[4])
 {
     const float W = (float)(uint32_t)(t->Bytes & 0xFFFFFFFFu), H = (float)(uint32_t)(t->Bytes >> 32);
@@ -703,7 +756,11 @@ void or_cube_sample(const OrHeapEntry* t, const float d[3], float out[4])
     else if (ay >= az) { ma = ay; if (d[1] >= 0.0f) { face = 2; sc = d[0]; tc = d[2]; } else { face = 3; sc = d[0]; tc = -d[2]; } }
     else { ma = az; if (d[2] >= 0.0f) { face = 4; sc = d[0]; tc = -d[1]; } else { face = 5; sc = -d[0]; tc = -d[1]; } }
     float u = (sc / ma + 1.0f) * 0.5f, v = (tc / ma + 1.0f) * 0.5f;
-    bilinear(t, face, u * W - 0.5f, v * H - 0.5f, 0, out);
+    float fx = u * W - 0.5f, fy = v * H - 0.5f;
+    float x0f = floorf(fx), y0f = floorf(fy);
+    /* u, v in [0, 1]: x0 in [-1, N-1]. A NaN direction fails every comparison and stays on the clamped in-face path. */
+    if (x0f < 0.0f || y0f < 0.0f || x0f + 1.0f > W - 1.0f || y0f + 1.0f > H - 1.0f) { cube_bilinear_seam(t, face, fx, fy, out); return; }
+    bilinear(t, face, fx, fy, 0, out);
 }
 
 /* Sample<T>(TextureMapInfo, textureCoordinates) ShadingHelpers.hlsli:53-59 */
