@@ -125,6 +125,7 @@ void pt_destroy(PtContext* ctx)
     for (hipEvent_t ev : c.chainJoin) if (ev) hipEventDestroy(ev);
     if (c.shadeRecA) hipFree(c.shadeRecA);
     if (c.shadeRecB) hipFree(c.shadeRecB);
+    release_direct_lighting(c);
     for (int k = 0; k < 2; k++) {
         PathQueue& q = c.queue[k];
         void* ptrs[6] = { q.s0, q.s1, q.s2, q.r0, q.r1, q.hit };
@@ -399,7 +400,7 @@ int pt_build_top_level(PtContext* ctx, const PtInstanceDesc* descs, uint32_t cou
     std::map<uint64_t, uint32_t> pieceOf;
     std::vector<BlasEntry> table;
     uint32_t blobNodes = tlasNodeCap, blobTris = 0;
-    uint64_t tris = 0, objectEnd = 0, bindingHash = 1469598103934665603ull;
+    uint64_t tris = 0, objectEnd = 0, bindingHash = 1469598103934665603ull, lightHash = 1469598103934665603ull ^ count;
     const size_t srcBytes = sizeof(InstanceSource) * (size_t)count;
     // staged in pinned host memory, two buffers taken in turn, each guarded by an event recorded behind the copy that read it: the host
     // may be a build ahead of the stream (a dynamic frame never synchronises) without rewriting bytes a copy has yet to read
@@ -425,6 +426,8 @@ int pt_build_top_level(PtContext* ctx, const PtInstanceDesc* descs, uint32_t cou
         tris += b.triCount;
         objectEnd = std::max<uint64_t>(objectEnd, (uint64_t)src.instanceID + b.geometryCount);
         bindingHash = (bindingHash ^ src.instanceID) * 1099511628211ull; bindingHash = (bindingHash ^ descs[i].AccelerationStructure) * 1099511628211ull;
+        lightHash = (lightHash ^ src.instanceID) * 1099511628211ull; lightHash = (lightHash ^ src.mask) * 1099511628211ull;
+        lightHash = (lightHash ^ descs[i].AccelerationStructure) * 1099511628211ull;
     }
     for (auto& kv : c.blas)                                        // adopted, not referenced: carried along
         if (kv.second.inBlob && !pieceOf.count(kv.first)) {
@@ -576,6 +579,8 @@ int pt_build_top_level(PtContext* ctx, const PtInstanceDesc* descs, uint32_t cou
     c.tlasBlasIds = pieceIds;
     if (objectEnd != c.tlasObjectEnd || count != c.tlasValidatedCount || bindingHash != c.tlasBindingHash) c.validated = false;     // same instances of the same bottom levels over the same objects: nothing new to check
     c.tlasObjectEnd = objectEnd; c.tlasValidatedCount = count; c.tlasBindingHash = bindingHash;
+    if (lightHash != c.tlasLightHash) c.lightListValid = false;
+    c.tlasLightHash = lightHash;
     // the same instances of the same bottom levels over the same objects (a dynamic frame's rebuild after a refit): the verdict of the
     // shared-geometry check still holds, and with it the frame's normal records (drop_tlas had put them aside with the old top level)
     c.normalsShared = c.validated && c.sharedVerdict;
@@ -664,6 +669,7 @@ int pt_invalidate_object_data(PtContext* ctx)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     ctx->c.validated = false; ctx->c.normalsShared = false; ctx->c.sharedVerdict = false;   // the next render resolves VertexDesc / MeshDescriptors again (validate_scene)
+    ctx->c.objectDataGen++;                                                                   // ... and pt_di_render lists the emissive triangles again
     return PT_OK;
 }
 int pt_set_instance_data(PtContext* ctx, const PtInstanceData* device_instances, uint32_t count)
@@ -811,7 +817,7 @@ int pt_raytrace_render(PtContext* ctx, const PtTextures* tx)
     API_ARG(&c, tx, "textures is NULL");
     if (!c.haveSettings) return fail(&c, PT_ERROR_NOT_READY, "call pt_raytrace_set_constants first");
     API_ARG(&c, c.settings.Denoiser <= PT_DENOISER_NRD_RELAX, "unknown Denoiser value");
-    API_ARG(&c, !c.settings.IsDIEnabled, "IsDIEnabled needs the RTXDI passes, which are out of scope");
+    API_ARG(&c, !c.settings.IsDIEnabled || (tx->Diffuse && tx->Specular), "IsDIEnabled reads the direct lighting from Textures.Diffuse / Textures.Specular (pt_di_render): not bound");
     API_ARG(&c, !(c.settings.Denoiser >= PT_DENOISER_NRD_REBLUR) || (tx->Diffuse && tx->Specular), "NRD modes write Textures.Diffuse / Textures.Specular: not bound");
     API_ARG(&c, c.settings.SamplesPerPixel < 65536 && c.settings.Bounces < 32768, "SamplesPerPixel / Bounces out of range");
     API_ARG(&c, tx->Position && tx->FlatNormal && tx->GeometricNormal && tx->BaseColorMetalness && tx->NormalRoughness && tx->IOR
@@ -972,3 +978,6 @@ int pt_get_round_timing(PtContext* ctx, float* round_ms, uint32_t* round_launche
 }
 
 } // extern "C"
+
+// the view set-up of the render operators, for the DI pass (pt_di.hip)
+namespace pt { int di_views(Context& c, uint32_t width, uint32_t height, SceneView& sv, FrameView& fv, bool needFrameInputs) { return make_views(c, width, height, sv, fv, needFrameInputs); } }

@@ -1,0 +1,466 @@
+// pt_di.hip -- direct lighting over emissive triangles (gfx950): light preparation and the DI pass.
+//
+//   k_light_count / k_light_fill   <- the task table of Shaders/LightPreparation.hlsl (FindTask) and Source/LightPreparation.ixx:
+//                                     the scene's emissive triangles, ordered by instance, geometry, triangle
+//   k_light_records                <- LightPreparation.hlsl main: TriangleLight::Initialize (Light.hlsli) on the world-space
+//                                     vertices, CalculatePower; run at every render (moving instances, refits)
+//   k_cdf_*                        <- the local-light pdf texture of the reference's Power_RIS mode, as a fixed-order prefix sum
+//   k_di                           <- DIInitialSampling (local lights only, streaming RIS) + DIFinalShading, no temporal /
+//                                     spatial reuse (RTXDIAppBridge.hlsli RAB_GetGBufferSurface, RAB_Surface::Shade, GetFinalVisibility)
+// DESIGN.md section 1 ("Direct lighting") is the arithmetic spec: seeding, draw order, triangle mapping.
+#include "pt_internal.hpp"
+
+#include <cstring>
+
+#include "pt_shade.hpp"
+
+namespace pt {
+
+constexpr uint32_t kDISalt = 0x44490001u;            // the DI pass's own stream: seed = ml_hash(rng_init(x, y, FrameIndex) ^ kDISalt)
+constexpr uint32_t kScanBlock = 1024u;               // lights per block of the prefix sum (256 threads x 4)
+constexpr uint32_t kLightRec16 = sizeof(PtTriangleLight) / 16u;
+static_assert(sizeof(PtTriangleLight) == 80, "layout");
+
+// ---- light list ------------------------------------------------------------------------------
+PT_DEV bool emissive(const PtMaterial& m) { const v3 e = material_emission(m); return e.x > 0.0f || e.y > 0.0f || e.z > 0.0f; }
+PT_DEV uint32_t geometry_triangles(const PtObjectData& od, const HeapEntry* heap)
+{
+    const HeapEntry ib = heap[od.MeshDescriptors.Indices];
+    return ib.stride ? (uint32_t)(ib.bytes / ib.stride / 3u) : 0u;
+}
+
+// one block: emissive triangles per instance (hidden instances: none), exclusive prefix sum in instance order; start[n] = total
+__global__ __launch_bounds__(1024) void k_light_count(const InstanceSource* __restrict__ src, const BlasEntry* __restrict__ table, uint32_t n,
+                                                      const PtObjectData* __restrict__ objects, const HeapEntry* __restrict__ heap, uint32_t* __restrict__ start)
+{
+    __shared__ uint32_t part[1024];
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < n; base += 1024u) {
+        const uint32_t i = base + threadIdx.x;
+        uint32_t cnt = 0;
+        if (i < n && src[i].mask != 0u) {
+            const BlasEntry b = table[src[i].blasSlot];
+            for (uint32_t g = 0; g < b.geometryCount; g++) {
+                const PtObjectData& od = objects[src[i].instanceID + g];
+                if (emissive(od.Material)) cnt += geometry_triangles(od, heap);
+            }
+        }
+        part[threadIdx.x] = cnt;
+        __syncthreads();
+        for (uint32_t off = 1; off < 1024u; off <<= 1) {            // inclusive scan (integers: exact in any order)
+            const uint32_t v = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
+            __syncthreads();
+            part[threadIdx.x] += v;
+            __syncthreads();
+        }
+        if (i < n) start[i] = carry + part[threadIdx.x] - cnt;
+        carry += part[1023];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) start[n] = carry;
+}
+
+// one block per instance: its emissive triangles in (geometry, triangle) order
+__global__ __launch_bounds__(256) void k_light_fill(const InstanceSource* __restrict__ src, const BlasEntry* __restrict__ table, const PtObjectData* __restrict__ objects,
+                                                    const HeapEntry* __restrict__ heap, const uint32_t* __restrict__ start, uint4* __restrict__ list)
+{
+    const uint32_t i = blockIdx.x;
+    if (src[i].mask == 0u) return;
+    const BlasEntry b = table[src[i].blasSlot];
+    uint32_t at = start[i];
+    for (uint32_t g = 0; g < b.geometryCount; g++) {
+        const uint32_t o = src[i].instanceID + g;
+        if (!emissive(objects[o].Material)) continue;
+        const uint32_t nt = geometry_triangles(objects[o], heap);
+        for (uint32_t t = threadIdx.x; t < nt; t += 256u) list[at + t] = make_uint4(i, g, t, o);
+        at += nt;
+    }
+}
+
+// ---- per-render records (PtTriangleLight, 5 x 16 B) -------------------------------------------
+PT_DEV v3 load_position(const HeapEntry& vb, uint32_t stride, uint32_t vi)
+{
+    const uint64_t at = (uint64_t)stride * vi;
+    if (at + 12u > vb.bytes) return V3(0.0f, 0.0f, 0.0f);             // an index beyond the vertex buffer reads nothing
+    const PT_GLOBAL_AS float* p = gptr<float>((const uint8_t*)vb.ptr + at);
+    return V3(p[0], p[1], p[2]);
+}
+PT_DEV v3 affine(const float* M, v3 p)                                  // Geometry::AffineTransform with a row-major 3x4
+{
+    return V3(M[0] * p.x + M[1] * p.y + M[2] * p.z + M[3], M[4] * p.x + M[5] * p.y + M[6] * p.z + M[7], M[8] * p.x + M[9] * p.y + M[10] * p.z + M[11]);
+}
+
+__global__ __launch_bounds__(256) void k_light_records(const uint4* __restrict__ list, uint32_t count, const InstanceSource* __restrict__ src, const PtObjectData* __restrict__ objects,
+                                                       const HeapEntry* __restrict__ heap, const HeapEntry* __restrict__ shadeTex, const float* __restrict__ srgbLut,
+                                                       float4* __restrict__ rec, float* __restrict__ power)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    const uint4 e = list[k];
+    const PtObjectData& od = objects[e.w];
+    const HeapEntry vb = heap[od.MeshDescriptors.Vertices], ib = heap[od.MeshDescriptors.Indices];
+    const uint32_t stride = od.VertexDesc.Stride;
+    uint32_t vi[3];
+    for (int j = 0; j < 3; j++) vi[j] = load_index_dev(ib.ptr, ib.stride, 3u * e.z + j);
+    float M[12];
+    for (int j = 0; j < 12; j++) M[j] = src[e.x].transform[j];
+    const v3 p0 = affine(M, load_position(vb, stride, vi[0])), p1 = affine(M, load_position(vb, stride, vi[1])), p2 = affine(M, load_position(vb, stride, vi[2]));
+    const v3 e0 = p1 - p0, e1 = p2 - p0;
+    const v3 nrm = cross(e0, e1);
+    const float len = sqrtf(dot(nrm, nrm));
+    v3 n = V3(0.0f, 0.0f, 0.0f); float area = 0.0f;
+    if (len > 0.0f) { n = V3(nrm.x / len, nrm.y / len, nrm.z / len); area = len / 2.0f; }
+    v3 L = material_emission(od.Material);
+    // the emissive texture at the UV centroid, bilinear mip 0 (the reference: SampleGrad over the triangle's UV footprint)
+    const HeapEntry t = shadeTex[(size_t)e.w * kTextureSlots + TEX_EmissiveColor];
+    if (t.ptr && (L.x > 0.0f || L.y > 0.0f || L.z > 0.0f)) {
+        const uint32_t off = od.VertexDesc.AttributeOffsets.TextureCoordinates[t.kind & 1u];
+        float uv[2] = { 0.0f, 0.0f };
+        if (off != ~0u) {
+            float a[3][2];
+            for (int j = 0; j < 3; j++) {
+                const uint64_t at = (uint64_t)stride * vi[j] + off;
+                a[j][0] = a[j][1] = 0.0f;
+                if (at + 4u <= vb.bytes) { const PT_GLOBAL_AS uint16_t* q = gptr<uint16_t>((const uint8_t*)vb.ptr + at); a[j][0] = f16_to_f32(q[0]); a[j][1] = f16_to_f32(q[1]); }
+            }
+            for (int c = 0; c < 2; c++) uv[c] = (a[0][c] + a[1][c] + a[2][c]) / 3.0f;
+        }
+        const f4 s = texture_sample(t, srgbLut, uv[0], uv[1]);
+        L = V3(L.x * s.x, L.y * s.y, L.z * s.z);
+    }
+    const float pw = area * kPi * ml_luminance(L);
+    float4* r = rec + kLightRec16 * (size_t)k;
+    r[0] = make_float4(p0.x, p0.y, p0.z, area);
+    r[1] = make_float4(e0.x, e0.y, e0.z, pw);
+    r[2] = make_float4(e1.x, e1.y, e1.z, __uint_as_float(e.x));
+    r[3] = make_float4(n.x, n.y, n.z, __uint_as_float(e.z));
+    r[4] = make_float4(L.x, L.y, L.z, __uint_as_float(e.y));
+    power[k] = pw;
+}
+
+// ---- sampling table: inclusive prefix sum of the powers in a fixed order (bit-identical from run to run) ----------------------
+// local: each block sums kScanBlock lights (4 per thread, sequentially, then a Hillis-Steele scan of the 256 thread sums)
+__global__ __launch_bounds__(256) void k_cdf_local(const float* __restrict__ power, uint32_t count, float* __restrict__ cdf, float* __restrict__ blockSums)
+{
+    __shared__ float part[256];
+    const uint32_t b0 = blockIdx.x * kScanBlock + threadIdx.x * 4u;
+    float v[4], s = 0.0f;
+    for (int j = 0; j < 4; j++) { v[j] = b0 + j < count ? power[b0 + j] : 0.0f; s += v[j]; v[j] = s; }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (uint32_t off = 1; off < 256u; off <<= 1) {
+        const float a = threadIdx.x >= off ? part[threadIdx.x - off] : 0.0f;
+        __syncthreads();
+        part[threadIdx.x] += a;
+        __syncthreads();
+    }
+    const float before = threadIdx.x ? part[threadIdx.x - 1] : 0.0f;
+    for (int j = 0; j < 4; j++) if (b0 + j < count) cdf[b0 + j] = before + v[j];
+    if (threadIdx.x == 255) blockSums[blockIdx.x] = part[255];
+}
+// one thread: running offsets of the blocks, in block order; blockSums[nb] = the total
+__global__ void k_cdf_blocks(float* __restrict__ blockSums, uint32_t nb)
+{
+    float s = 0.0f;
+    for (uint32_t b = 0; b < nb; b++) { const float t = blockSums[b]; blockSums[b] = s; s += t; }
+    blockSums[nb] = s;
+}
+// adds the block offsets; the last entry becomes the total itself (the order of the sums above can leave them an ulp apart, and the
+// selection rule needs cdf[count - 1] == total so that a light past the last positive power can never be returned)
+__global__ __launch_bounds__(256) void k_cdf_add(float* __restrict__ cdf, uint32_t count, const float* __restrict__ blockSums, uint32_t nb)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k + 1u == count) cdf[k] = blockSums[nb];
+    else if (k < count && k >= kScanBlock) cdf[k] = blockSums[k / kScanBlock] + cdf[k];
+}
+
+// ---- the DI pass ----------------------------------------------------------------------------------------------------------
+struct DICamera { float position[3], jitter[2]; float projectionToView[16], viewToWorld[16]; };
+struct DIArgs {
+    FrameView fv; DICamera cam; PtTextures tx;
+    const float4* lights; const float* cdf; const float* total; uint32_t count;
+    uint32_t frameIndex, samples, denoiser, lastPass, ext;
+};
+
+// first light whose inclusive prefix exceeds x: a light of zero power never qualifies. x >= total (rounding of u * total): the
+// first light that reaches the total, which has power > 0.
+PT_DEV uint32_t select_light(const float* __restrict__ cdf, uint32_t n, float x, float total)
+{
+    const float t = x < total ? x : total;
+    uint32_t lo = 0, hi = n - 1u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        const float c = cdf[mid];
+        if (x < total ? c > t : c >= t) hi = mid; else lo = mid + 1u;
+    }
+    return lo;
+}
+
+// Shade(lightSample) of RAB_Surface, RTXDIAppBridge.hlsli: all-lobe Evaluate times radiance / solid-angle pdf
+PT_DEV void shade_sample(const BSDFSample& bs, const SurfaceVectors& svec, const float w[3], uint32_t ext, v3 P, v3 V, v3 pos, v3 Le, float pdfSA, v3& dif, v3& spc)
+{
+    dif = V3(0.0f, 0.0f, 0.0f); spc = V3(0.0f, 0.0f, 0.0f);
+    if (!(pdfSA > 0.0f)) return;
+    float pdf;
+    bs.EvaluateAll(svec, normalize(pos - P), V, w, pdf, dif, spc, ext);
+    const float inv = 1.0f / pdfSA;
+    dif = V3(dif.x * Le.x * inv, dif.y * Le.y * inv, dif.z * Le.z * inv);
+    spc = V3(spc.x * Le.x * inv, spc.y * Le.y * inv, spc.z * Le.z * inv);
+}
+
+// One thread per local pixel; a wave covers an 8 x 8 square (as k_gbuffer), so the visibility rays of a wave stay together.
+__global__ __launch_bounds__(256) void k_di(DIArgs a, BlobView bv, AlphaContext ac, DeviceCounters* counters)
+{
+    const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63u;
+    const uint32_t x = blockIdx.x * 16 + (wv & 1u) * 8u + (ln & 7u), ly = blockIdx.y * 16 + (wv >> 1) * 8u + (ln >> 3);
+    if (x >= a.fv.width || ly >= a.fv.localRows) return;                 // no barrier below
+    const uint32_t y = global_row(a.fv, ly);
+    const size_t pi = (size_t)ly * a.fv.width + x;
+    const PtTextures& tx = a.tx;
+
+    // RAB_GetGBufferSurface (RTXDIAppBridge.hlsli:293-345)
+    const float depth = ((const float*)tx.LinearDepth)[pi];
+    if (!isfinite(depth)) return;
+    const short4 nr = ((const short4*)tx.NormalRoughness)[pi];
+    const float roughness = snorm16_to_f32(nr.w);
+    if (roughness < 0.05f) return;                                       // MinRoughness
+    const float u = ((float)x + 0.5f + a.cam.jitter[0]) / (float)a.fv.width, v = ((float)y + 0.5f + a.cam.jitter[1]) / (float)a.fv.height;
+    float q[4];
+    xform4(a.cam.projectionToView, V3(u * 2.0f + -1.0f, v * -2.0f + 1.0f, 0.5f), q);      // Camera::ReconstructWorldPosition
+    const v3 vp = V3(q[0] / q[2] * depth, q[1] / q[2] * depth, depth);
+    xform4(a.cam.viewToWorld, vp, q);
+    const v3 P = V3(q[0], q[1], q[2]);
+    const v3 V = normalize(V3(a.cam.position[0] - P.x, a.cam.position[1] - P.y, a.cam.position[2] - P.z));
+    const short2 ge = ((const short2*)tx.GeometricNormal)[pi];
+    const v3 gn = oct_decode(snorm16_to_f32(ge.x), snorm16_to_f32(ge.y));
+    const bool front = dot(gn, V) > 0.0f;
+    const SurfaceVectors svec = surface_vectors(front, gn, V3(snorm16_to_f32(nr.x), snorm16_to_f32(nr.y), snorm16_to_f32(nr.z)));
+    const uchar4 bcm = ((const uchar4*)tx.BaseColorMetalness)[pi];
+    const float metal = unorm8_to_f32(bcm.w);
+    const float tr = metal < 1.0f ? unorm8_to_f32(((const uint8_t*)tx.Transmission)[pi]) : 0.0f;
+    BSDFSample bs;
+    bs.Initialize(V3(unorm8_to_f32(bcm.x), unorm8_to_f32(bcm.y), unorm8_to_f32(bcm.z)), metal, roughness, f16_to_f32(((const uint16_t*)tx.IOR)[pi]), tr, front);
+    float w[3]; bs.ComputeLobeWeights(svec, V, a.ext, w);
+
+    // initial sampling: LocalLightSamples power-proportional candidates, streaming RIS (RTXDI_StreamSample); the selected sample's
+    // shaded terms stay in registers
+    const float total = *a.total;
+    if (!(total > 0.0f) || !isfinite(total)) return;
+    uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDISalt);
+    float wsum = 0.0f, pSel = 0.0f;
+    v3 difSel = V3(0, 0, 0), spcSel = V3(0, 0, 0), posSel = V3(0, 0, 0);
+    for (uint32_t k = 0; k < a.samples; k++) {
+        const float r0 = rng_float(rng), r1 = rng_float(rng), r2 = rng_float(rng), r3 = rng_float(rng);
+        const uint32_t li = select_light(a.cdf, a.count, r0 * total, total);
+        const float4* L = a.lights + kLightRec16 * (size_t)li;
+        const float4 l0 = L[0], l1 = L[1], l2 = L[2], l3 = L[3], l4 = L[4];
+        const float s = sqrtf(r1);                                          // Math::SampleTriangle
+        const float b0 = s * (1.0f - r2), b1 = s * r2;
+        const v3 pos = V3(l0.x + l1.x * b0 + l2.x * b1, l0.y + l1.y * b0 + l2.y * b1, l0.z + l1.z * b0 + l2.z * b1);
+        const v3 d = pos - P;
+        const float len = sqrtf(dot(d, d));
+        const v3 dn = V3(d.x / len, d.y / len, d.z / len);
+        const float cosL = fabsf(dot(dn, -V3(l3.x, l3.y, l3.z)));
+        const float pdfSA = (1.0f / l0.w) * len * len / cosL;              // CalculateSolidAnglePDF
+        v3 dif, spc;
+        shade_sample(bs, svec, w, a.ext, P, V, pos, V3(l4.x, l4.y, l4.z), pdfSA, dif, spc);
+        const float p = ml_luminance(dif + spc);                            // RAB_GetLightSampleTargetPdfForSurface
+        const float ris = p > 0.0f ? p / (l1.w / total) : 0.0f;          // target / source pdf (light selection; the point is uniform in uv)
+        wsum += ris;
+        if (r3 * wsum < ris) { pSel = p; difSel = dif; spcSel = spc; posSel = pos; }
+    }
+    if (!(pSel > 0.0f)) return;
+    const float W = wsum / (float)a.samples / pSel;                        // (sum w / M) / target(y)
+
+    // final shading (DIFinalShading.hlsl): one coloured visibility ray, CreateVisibilityRay with offset 1e-3
+    const v3 d = posSel - P;
+    const float dist = sqrtf(dot(d, d));
+    const v3 dir = V3(d.x / dist, d.y / dist, d.z / dist);
+    __shared__ uint2 ldsStack[kLdsStackDepth * 256];
+    uint2 spill[kStackSize - kLdsStackDepth];
+    GroupStack<kLdsStackDepth> stack; stack.init((PT_LDS_AS void*)ldsStack, spill);
+    BlobReader<false> blob; blob.p = bv.base;
+    TraceStats st; st.nodes = 0; st.tris = 0; st.overflow = 0;
+    v3 vis;
+    trace_single<false, false, true>(blob, bv, ac, P, dir, 1e-3f, fmaxf(0.0f, dist - 2e-3f), stack, &st, &vis);
+    if (st.overflow) atomicAdd(&counters->stackOverflows, st.overflow);
+    if (vis.x == 0.0f && vis.y == 0.0f && vis.z == 0.0f) return;
+    const v3 dif = V3(difSel.x * vis.x * W, difSel.y * vis.y * W, difSel.z * vis.z * W);
+    const v3 spc = V3(spcSel.x * vis.x * W, spcSel.y * vis.y * W, spcSel.z * vis.z * W);
+    const v3 rad = dif + spc;
+    if ((rad.x == 0.0f && rad.y == 0.0f && rad.z == 0.0f) || !finite3(rad)) return;
+
+    // outputs, DIFinalShading.hlsl:78-103
+    if (a.lastPass && a.denoiser <= PT_DENOISER_DLSS_RAY_RECONSTRUCTION) {
+        ushort4* R = (ushort4*)tx.Radiance;
+        const ushort4 o = R[pi];
+        const v3 sum = V3(f16_to_f32(o.x) + rad.x, f16_to_f32(o.y) + rad.y, f16_to_f32(o.z) + rad.z);
+        R[pi] = make_ushort4(f32_to_f16(sum.x), f32_to_f16(sum.y), f32_to_f16(sum.z), o.w);
+        if (tx.RadianceF32) ((float4*)tx.RadianceF32)[pi] = make_float4(sum.x, sum.y, sum.z, 0.0f);
+        if (a.denoiser == PT_DENOISER_DLSS_RAY_RECONSTRUCTION && tx.SpecularHitDistance && (spc.x > 0.0f || spc.y > 0.0f || spc.z > 0.0f))
+            ((uint16_t*)tx.SpecularHitDistance)[pi] = f32_to_f16(dist);
+        return;
+    }
+    ((ushort4*)tx.Diffuse)[pi] = make_ushort4(f32_to_f16(dif.x), f32_to_f16(dif.y), f32_to_f16(dif.z), f32_to_f16(dist));
+    ((ushort4*)tx.Specular)[pi] = make_ushort4(f32_to_f16(spc.x), f32_to_f16(spc.y), f32_to_f16(spc.z), f32_to_f16(dist));
+}
+
+// ---- host --------------------------------------------------------------------------------------------------------------------
+void release_direct_lighting(Context& c)
+{
+    if (c.lightList) hipFree(c.lightList);
+    if (c.lightInstStart) hipFree(c.lightInstStart);
+    if (c.lightRecords) hipFree(c.lightRecords);
+    if (c.lightCdf) hipFree(c.lightCdf);
+    if (c.lightBlockSums) hipFree(c.lightBlockSums);
+    c.lightList = nullptr; c.lightInstStart = nullptr; c.lightRecords = nullptr; c.lightCdf = nullptr; c.lightBlockSums = nullptr;
+    c.lightListCap = c.lightInstCap = c.lightRecordCap = 0; c.lightListValid = false;
+}
+
+// The scene's light list, one per context (a context that views another's scene lists the same triangles from the owner's read-only
+// top-level inputs, on its own stream; no context writes another's list). Rebuilt when the instances of the top level, the object-data
+// binding or pt_invalidate_object_data change it: two small kernels and one wait for the count. Nothing else waits.
+hipError_t ensure_light_list(Context& c, const SceneView& sv)
+{
+    const Context& s = c.sceneOwner ? *c.sceneOwner : c;            // who built the top level: the hash of its instances
+    uint64_t key = 1469598103934665603ull;
+    auto mix = [&](uint64_t v) { key = (key ^ v) * 1099511628211ull; };
+    mix(s.tlasLightHash); mix(s.tlas.instanceCount); mix((uint64_t)(uintptr_t)c.instSourceDev); mix((uint64_t)(uintptr_t)c.objects); mix(c.objectCount);
+    mix(c.objectDataGen);
+    if (c.lightListValid && c.lightListKey == key) return hipSuccess;
+    hipError_t e;
+    const uint32_t n = s.tlas.instanceCount;
+    c.lightCount = 0; c.lightListValid = false;
+    if (n && c.instSourceDev && c.blasTableDev && c.objectCount) {
+        if (n + 1u > c.lightInstCap) {
+            if ((e = hipStreamSynchronize(c.stream)) != hipSuccess) return e;
+            if (c.lightInstStart) hipFree(c.lightInstStart);
+            c.lightInstStart = nullptr; c.lightInstCap = 0;
+            if ((e = hipMalloc((void**)&c.lightInstStart, sizeof(uint32_t) * (n + 1u))) != hipSuccess) return e;
+            c.lightInstCap = n + 1u;
+        }
+        k_light_count<<<1, 1024, 0, c.stream>>>(c.instSourceDev, c.blasTableDev, n, sv.objects, sv.heap, c.lightInstStart);
+        uint32_t total = 0;
+        if ((e = hipMemcpyAsync(&total, c.lightInstStart + n, sizeof total, hipMemcpyDeviceToHost, c.stream)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(c.stream)) != hipSuccess) return e;
+        if (total > c.lightListCap) {
+            if (c.lightList) hipFree(c.lightList);
+            c.lightList = nullptr; c.lightListCap = 0;
+            if ((e = hipMalloc((void**)&c.lightList, sizeof(uint4) * total)) != hipSuccess) return e;
+            c.lightListCap = total;
+        }
+        if (total) k_light_fill<<<n, 256, 0, c.stream>>>(c.instSourceDev, c.blasTableDev, sv.objects, sv.heap, c.lightInstStart, c.lightList);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        c.lightCount = total;
+    }
+    c.lightListKey = key; c.lightListValid = true;
+    return hipSuccess;
+}
+
+} // namespace pt
+
+using namespace pt;
+
+static int di_fail(Context& c, int status, const std::string& msg) { c.lastError = msg; return status; }
+static int di_fail_hip(Context& c, hipError_t e, const char* what)
+{
+    return di_fail(c, e == hipErrorOutOfMemory ? PT_ERROR_OUT_OF_MEMORY : PT_ERROR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+#define DI_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return di_fail_hip(c, e_, #expr); } while (0)
+#define DI_ARG(cond, msg) do { if (!(cond)) return di_fail(c, PT_ERROR_INVALID_ARGUMENT, msg); } while (0)
+
+namespace pt { int di_views(Context& c, uint32_t width, uint32_t height, SceneView& sv, FrameView& fv, bool needFrameInputs); }   // pt_api.hip make_views
+
+extern "C" {
+
+int pt_di_set_constants(PtContext* ctx, const PtDISettings* s)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    DI_ARG(s, "settings is NULL");
+    DI_ARG(s->LocalLightSamples >= 1 && s->LocalLightSamples <= 32, "LocalLightSamples must be 1..32");
+    DI_ARG(s->Denoiser <= PT_DENOISER_NRD_RELAX, "unknown Denoiser value");
+    c.diSettings = *s; c.haveDISettings = true;
+    return PT_OK;
+}
+
+int pt_di_render(PtContext* ctx, const PtTextures* tx)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    DI_ARG(tx, "textures is NULL");
+    if (!c.haveDISettings) return di_fail(c, PT_ERROR_NOT_READY, "call pt_di_set_constants first");
+    const PtDISettings& s = c.diSettings;
+    DI_ARG(tx->LinearDepth && tx->GeometricNormal && tx->NormalRoughness && tx->BaseColorMetalness && tx->IOR && tx->Transmission,
+           "a G-buffer texture the DI pass reads is not bound (LinearDepth, GeometricNormal, NormalRoughness, BaseColorMetalness, IOR, Transmission)");
+    const bool toRadiance = s.IsLastRenderPass && s.Denoiser <= PT_DENOISER_DLSS_RAY_RECONSTRUCTION;
+    DI_ARG(toRadiance ? tx->Radiance != nullptr : (tx->Diffuse && tx->Specular),
+           toRadiance ? "IsLastRenderPass with Denoiser None / DLSS-RR adds to Textures.Radiance: not bound" : "the DI pass writes Textures.Diffuse / Textures.Specular: not bound");
+    DI_HIP(hipSetDevice(c.device));
+    SceneView sv; FrameView fv; memset(&sv, 0, sizeof sv); memset(&fv, 0, sizeof fv);
+    int st = di_views(c, s.RenderSize[0], s.RenderSize[1], sv, fv, true);
+    if (st != PT_OK) return st;
+    const size_t npix = (size_t)fv.width * fv.localRows;
+    if (tx->Diffuse) DI_HIP(hipMemsetAsync(tx->Diffuse, 0, npix * 8u, c.stream));                // App.cpp:1238-1239
+    if (tx->Specular) DI_HIP(hipMemsetAsync(tx->Specular, 0, npix * 8u, c.stream));
+    DI_HIP(ensure_light_list(c, sv));
+    const uint32_t n = c.lightCount;
+    c.lightRecordCount = n;
+    if (n == 0 || npix == 0) return PT_OK;
+    const uint32_t nb = (n + kScanBlock - 1u) / kScanBlock;
+    if (n > c.lightRecordCap) {
+        DI_HIP(hipStreamSynchronize(c.stream));
+        if (c.lightRecords) hipFree(c.lightRecords);
+        if (c.lightCdf) hipFree(c.lightCdf);
+        if (c.lightBlockSums) hipFree(c.lightBlockSums);
+        c.lightRecords = nullptr; c.lightCdf = nullptr; c.lightBlockSums = nullptr; c.lightRecordCap = 0;
+        DI_HIP(hipMalloc((void**)&c.lightRecords, sizeof(PtTriangleLight) * (size_t)n));
+        DI_HIP(hipMalloc((void**)&c.lightCdf, sizeof(float) * (size_t)n * 2u));              // cdf | powers
+        DI_HIP(hipMalloc((void**)&c.lightBlockSums, sizeof(float) * (nb + 1u)));
+        c.lightRecordCap = n;
+    }
+    float* power = c.lightCdf + c.lightRecordCap;
+    k_light_records<<<(n + 255u) / 256u, 256, 0, c.stream>>>(c.lightList, n, c.instSourceDev, sv.objects, sv.heap, sv.shadeTex, sv.srgbLut, c.lightRecords, power);
+    k_cdf_local<<<nb, 256, 0, c.stream>>>(power, n, c.lightCdf, c.lightBlockSums);
+    k_cdf_blocks<<<1, 1, 0, c.stream>>>(c.lightBlockSums, nb);
+    k_cdf_add<<<(n + 255u) / 256u, 256, 0, c.stream>>>(c.lightCdf, n, c.lightBlockSums, nb);
+    DIArgs a; memset(&a, 0, sizeof a);
+    a.fv = fv; a.tx = *tx;
+    memcpy(a.cam.position, c.camera.Position, sizeof a.cam.position); memcpy(a.cam.jitter, c.camera.Jitter, sizeof a.cam.jitter);
+    memcpy(a.cam.projectionToView, c.camera.ProjectionToView, sizeof a.cam.projectionToView); memcpy(a.cam.viewToWorld, c.camera.ViewToWorld, sizeof a.cam.viewToWorld);
+    a.lights = c.lightRecords; a.cdf = c.lightCdf; a.total = c.lightBlockSums + nb; a.count = n;
+    a.frameIndex = s.FrameIndex; a.samples = s.LocalLightSamples; a.denoiser = s.Denoiser; a.lastPass = s.IsLastRenderPass; a.ext = s.ExtFlags;
+    AlphaContext ac; ac.objects = sv.objects; ac.heap = sv.heap; ac.srgbLut = sv.srgbLut; ac.instances = sv.accel.instances; ac.shadeTex = sv.shadeTex;
+    k_di<<<dim3((fv.width + 15u) / 16u, (fv.localRows + 15u) / 16u), 256, 0, c.stream>>>(a, c.blob, ac, c.counters);
+    DI_HIP(hipGetLastError());
+    return PT_OK;
+}
+
+int pt_di_light_count(PtContext* ctx, uint32_t* out_count)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    DI_ARG(out_count, "out_count is NULL");
+    DI_HIP(hipSetDevice(c.device));
+    SceneView sv; FrameView fv; memset(&sv, 0, sizeof sv); memset(&fv, 0, sizeof fv);
+    int st = di_views(c, 1, 1, sv, fv, false);
+    if (st != PT_OK) return st;
+    DI_HIP(ensure_light_list(c, sv));
+    *out_count = c.lightCount;
+    return PT_OK;
+}
+
+int pt_di_download_lights(PtContext* ctx, PtTriangleLight* host_dst, uint32_t capacity, uint32_t* out_count)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    DI_ARG(out_count && (host_dst || capacity == 0), "out_count / host_dst is NULL");
+    DI_HIP(hipSetDevice(c.device));
+    DI_HIP(hipStreamSynchronize(c.stream));
+    *out_count = c.lightRecordCount;
+    const uint32_t k = std::min(capacity, c.lightRecordCount);
+    if (k) DI_HIP(hipMemcpy(host_dst, c.lightRecords, sizeof(PtTriangleLight) * (size_t)k, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+} // extern "C"

@@ -183,6 +183,16 @@ struct Context {
     bool timing = false;
     std::vector<hipEvent_t> evExtend, evShade, evRound;     // begin/end pairs since timing was enabled
     uint32_t nExtend = 0, nShade = 0, nRound = 0;
+
+    // direct lighting (pt_di.hip): per context. A context that views another's scene (pt_share_scene) lists its emissive triangles from the owner's
+    // read-only top-level inputs into a list of its own; the per-render records and the sampling table are the context's too.
+    PtDISettings diSettings{}; bool haveDISettings = false;
+    uint64_t tlasLightHash = 0;                       // over (InstanceID, InstanceMask, bottom-level id) of the top level's instances, in order
+    uint32_t objectDataGen = 0;                       // bumped by pt_invalidate_object_data
+    uint4* lightList = nullptr; uint32_t lightListCap = 0, lightCount = 0;   // (instance, geometry, primitive, object) per emissive triangle
+    uint32_t* lightInstStart = nullptr; uint32_t lightInstCap = 0;          // per instance: first list entry; [instanceCount]: the total
+    uint64_t lightListKey = 0; bool lightListValid = false;
+    float4* lightRecords = nullptr; float* lightCdf = nullptr; float* lightBlockSums = nullptr; uint32_t lightRecordCap = 0, lightRecordCount = 0;
 };
 
 std::string& create_error();             // pt_api.hip: the message pt_last_error(NULL) returns (errors of the context-free entry points)
@@ -217,6 +227,9 @@ uint32_t round_records_in_lds(const Context& c, uint32_t objectCount, bool haveS
 inline bool normal_records_usable(const Context& c) { return c.normalsShared && c.blasTableDev && c.blasTableCount <= 65535u /* grid.y of k_capture_normals */ && c.shadeRecA && c.blob.triCount && c.blob.triCount <= c.shadeRecCap; }
 hipError_t launch_check_shared_geometry(hipStream_t stream, const InstanceSource* src, const BlasEntry* table, uint32_t n, const ShadeGeom* shadeGeom, uint32_t* out);
 hipError_t launch_validate_objects(hipStream_t stream, const PtObjectData* objects, uint32_t count, const HeapEntry* heap, uint32_t heapCount, uint32_t* out, ShadeGeom* shadeGeom, HeapEntry* shadeTex);
+// pt_di.hip
+void release_direct_lighting(Context& c);
+
 hipError_t launch_deinterleave(hipStream_t stream, void* dst, const void* src, const uint64_t* rankOffsetsHost, uint32_t rankCount,
                                uint32_t bandHeight, uint32_t width, uint32_t height, uint32_t pixelBytes);
 

@@ -219,6 +219,7 @@ __global__ __launch_bounds__(256) void k_pt_init(FrameView fv, const FrameConsta
 // wrote them -- so the block that gathers a tile of pixels into primary-surface records shades their first bounce right away, out of
 // the registers that hold the record, and emits the survivors as round 0 would have. The fresh state (48 B written, 48 B read), the record
 // read-back (48 B) and one launch per frame go away; values and draws are those of k_pt_init + shade_fresh.
+template <bool DI>
 __global__ __launch_bounds__(256) void k_pt_first(FrameView fv, const FrameConstants* __restrict__ fc, PtTextures tx, PathQueue qout, float2* aux,
                                                                                              uint32_t segCap, uint32_t* countOut, uint4* __restrict__ primary, uint32_t sqShift)
 {
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(256) void k_pt_first(FrameView fv, const FrameConst
             const uint4 r2 = make_uint4(((const uint32_t*)tx.BaseColorMetalness)[pix], rad.x, rad.y,
                                         (uint32_t)((const uint16_t*)tx.IOR)[pix] | ((uint32_t)((const uint8_t*)tx.Transmission)[pix] << 16));
             primary[3 * (size_t)pix] = r0; primary[3 * (size_t)pix + 1] = r1; primary[3 * (size_t)pix + 2] = r2;
-            shade_fresh_record(fv, cam, gs, tx, aux, r0, r1, r2, p, toTraced, toFresh, newO, newD);
+            shade_fresh_record<DI>(fv, cam, gs, tx, aux, r0, r1, r2, p, toTraced, toFresh, newO, newD);
         }
         emit_tile(qout, seg, segCap, &countOut[sq], &countOut[nsq + sq], lds + ((emits++ & 1u) << 4), toTraced, toFresh, p, newO, newD);
     }
@@ -362,7 +363,7 @@ struct RoundArgs {
     const uint4* primary;
 };
 
-template <bool TEXTURED, bool LDS, bool FLAT>
+template <bool TEXTURED, bool LDS, bool FLAT, bool DI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_round(const RoundArgs* __restrict__ A, uint32_t sqBase, uint32_t sqCount)
 {
     const SceneView& sv = A->sv; const FrameView& fv = A->fv; const PtTextures& tx = A->tx; const BlobView& bv = A->bv;
@@ -438,7 +439,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             bool toTraced = false, toFresh = false;
             v3 newO = V3(0, 0, 0), newD = V3(0, 0, 1);
             if (valid) {
-                shade_traced<TEXTURED>(sv, GeometryFromBlob<LDS>{ blob, bv, tables }, sd, gs, tx, aux, p, make_uint4(h.inst, h.slot, __float_as_uint(h.u), __float_as_uint(h.v)), h.t,
+                shade_traced<TEXTURED, DI>(sv, GeometryFromBlob<LDS>{ blob, bv, tables }, sd, gs, tx, aux, p, make_uint4(h.inst, h.slot, __float_as_uint(h.u), __float_as_uint(h.v)), h.t,
                                        V3(d.x, d.y, d.z), toTraced, toFresh, newO, newD, prof);
             }
             PT_PROF_MARK(prof, 6);
@@ -457,7 +458,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         if (local < nF) {
             p = load_path(qin, seg + (segCap - 1u - local));
             PT_PROF_WAIT(); PT_PROF_MARK(prof, 12);
-            shade_fresh(fv, cam, gs, tx, aux, primary, p, toTraced, toFresh, newO, newD, prof);
+            shade_fresh<DI>(fv, cam, gs, tx, aux, primary, p, toTraced, toFresh, newO, newD, prof);
         }
         PT_PROF_MARK(prof, 14);
         emit_tile(qout, seg, segCap, &countOut[sq], &countOut[nsq + sq], lds + ((emits++ & 1u) << 4), toTraced, toFresh, p, newO, newD);
@@ -803,7 +804,10 @@ static hipError_t enqueue_preamble(Context& c, const SceneView& sv, const FrameV
     float2* aux = c.settings.Denoiser != PT_DENOISER_NONE ? c.pixelAux : nullptr;
     if (normal_records_usable(c))                          // the frame's normal records, from the vertex buffers as they are now
         k_capture_normals<<<dim3(std::min((c.blasTableMaxTris + 255u) / 256u, 64u), c.blasTableCount), 256, 0, c.stream>>>(c.blasTableDev, sv.shadeGeom, c.shadeRecA, c.shadeRecB);
-    if (frame_form(c).first) k_pt_first<<<grid, 256, 0, c.stream>>>(fv, c.frameConstants, tx, c.queue[1], aux, segCap, &c.queueCounts[cstride], c.primaryRecords, c.sqShift);
+    if (frame_form(c).first) {
+        if (c.settings.IsDIEnabled) k_pt_first<true><<<grid, 256, 0, c.stream>>>(fv, c.frameConstants, tx, c.queue[1], aux, segCap, &c.queueCounts[cstride], c.primaryRecords, c.sqShift);
+        else k_pt_first<false><<<grid, 256, 0, c.stream>>>(fv, c.frameConstants, tx, c.queue[1], aux, segCap, &c.queueCounts[cstride], c.primaryRecords, c.sqShift);
+    }
     else k_pt_init<<<grid, 256, 0, c.stream>>>(fv, c.frameConstants, tx, c.queue[0], aux, segCap, &c.queueCounts[nsq], c.primaryRecords, c.sqShift);
     return hipGetLastError();
 }
@@ -841,7 +845,8 @@ static hipError_t enqueue_chain(Context& c, const SceneView& sv, const FrameView
     const uint32_t smem = (flat ? kFlatLdsFixed : kExtendLdsFixed) + (lds ? c.blob.bytes : 0u) + round_objects_in_lds(c, sv) * kObjLds16 * 16u + lds_bytes_of_records(round_records_in_lds(c, sv));
     for (uint32_t r = 1; r <= rounds; r++) {                        // queues and counters of round r: in its argument block (launch_raytrace); round 0 ran inside k_pt_first
         timing_begin(c, c.evRound, c.nRound);
-        #define PT_ROUND(T, L, F) k_round<T, L, F><<<perSq * sqCount, 256, smem, s>>>(c.roundArgs + r, sqBase, sqCount)
+        #define PT_ROUND(T, L, F) do { if (c.settings.IsDIEnabled) k_round<T, L, F, true><<<perSq * sqCount, 256, smem, s>>>(c.roundArgs + r, sqBase, sqCount); \
+                                       else k_round<T, L, F, false><<<perSq * sqCount, 256, smem, s>>>(c.roundArgs + r, sqBase, sqCount); } while (0)
         #define PT_ROUND_F(T, L) do { if (flat) PT_ROUND(T, L, true); else PT_ROUND(T, L, false); } while (0)
         #define PT_ROUND_L(T) do { if (lds) PT_ROUND_F(T, true); else PT_ROUND_F(T, false); } while (0)
         if (c.heapHasTextures) PT_ROUND_L(true); else PT_ROUND_L(false);
@@ -947,7 +952,7 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
     std::string key;
     key_add(key, sv); key_add(key, fv); key_add(key, tx); key_add(key, rounds); key_add(key, segCap); key_add(key, grid);
     key_add(key, c.queue[0]); key_add(key, c.queue[1]); key_add(key, c.queueCounts); key_add(key, c.blob); key_add(key, c.heapHasTextures);
-    key_add(key, c.frameConstants); key_add(key, c.primaryRecords); key_add(key, c.stream); key_add(key, c.pixelAux); key_add(key, gs.Denoiser); key_add(key, c.debugFlags);
+    key_add(key, c.frameConstants); key_add(key, c.primaryRecords); key_add(key, c.stream); key_add(key, c.pixelAux); key_add(key, gs.Denoiser); key_add(key, c.debugFlags); key_add(key, gs.IsDIEnabled != 0u);
     key_add(key, c.framesInFlight); key_add(key, c.sqShift); key_add(key, c.chains);
     key_add(key, c.shadeRecA); key_add(key, c.blasTableDev); key_add(key, c.blasTableCount); key_add(key, c.blasTableMaxTris); key_add(key, normal_records_usable(c));
     if (key != c.roundArgsKey || !c.roundArgs) {                              // k_round's argument blocks, one per round (device memory)

@@ -381,15 +381,17 @@ struct BSDFSample {                           // BxDF.hlsli:36-44
     }
 
     // all-lobe EvaluatePDF :247-264 and Evaluate :266-285 (the RTXDI-facing overloads), built from the single-lobe forms
-    PT_DEV void EvaluateAll(const SurfaceVectors& sv, v3 L, v3 V, const float w[3], float& pdf, v3& diffuse, v3& specular) const
+    // ext: PT_EXT_* (the DI pass honours PT_EXT_LAMBERTIAN_ONLY; pt_bsdf_evaluate passes 0)
+    PT_DEV void EvaluateAll(const SurfaceVectors& sv, v3 L, v3 V, const float w[3], float& pdf, v3& diffuse, v3& specular, uint32_t ext = 0) const
     {
         const float tw = w[LOBE_TRANSMISSION];
         pdf = 0.0f; diffuse = V3(0.0f, 0.0f, 0.0f); specular = V3(0.0f, 0.0f, 0.0f);
         if (tw > 0.0f) { float p; v3 f; EvaluateLobe(sv, L, V, w, LOBE_TRANSMISSION, 0, p, f); pdf = p; specular = f; }
         if (tw < 1.0f && dot(sv.FrontGeometricNormal, L) > 0.0f) {
             float pd, ps; v3 fd, fs;
-            EvaluateLobe(sv, L, V, w, LOBE_DIFFUSE, 0, pd, fd);
-            EvaluateLobe(sv, L, V, w, LOBE_SPECULAR, 0, ps, fs);
+            EvaluateLobe(sv, L, V, w, LOBE_DIFFUSE, ext, pd, fd);
+            if (ext & kExtLambertianOnly) { ps = 0.0f; fs = V3(0.0f, 0.0f, 0.0f); }          // config C1: the diffuse lobe alone
+            else EvaluateLobe(sv, L, V, w, LOBE_SPECULAR, 0, ps, fs);
             pdf += pd + ps;
             diffuse = fd;
             specular = specular + fs;

@@ -339,7 +339,23 @@ PT_DEV bool scatter(const PtGraphicsSettings& gs, PathRegs& p, const SurfaceHit&
     return true;
 }
 
+// IsDIEnabled (template flag DI of the shading bodies and the kernels around them): the direct lighting the DI pass left in
+// Textures.Diffuse / Specular at the primary surface (Raytracing.hlsl:150-163). Read where it is used, never carried in the path state.
+PT_DEV void load_direct(const PtTextures& tx, uint32_t pixel, v3& directDiffuse, v3& directSpecular)
+{
+    const ushort4 d = ((const ushort4*)tx.Diffuse)[pixel], s = ((const ushort4*)tx.Specular)[pixel];
+    directDiffuse = V3(f16_to_f32(d.x), f16_to_f32(d.y), f16_to_f32(d.z));
+    directSpecular = V3(f16_to_f32(s.x), f16_to_f32(s.y), f16_to_f32(s.z));
+}
+PT_DEV bool direct_valid(const PtTextures& tx, uint32_t pixel)        // isDIValid = any(DI > 0)
+{
+    v3 dd, ds; load_direct(tx, pixel, dd, ds);
+    const v3 di = dd + ds;
+    return di.x > 0.0f || di.y > 0.0f || di.z > 0.0f;
+}
+
 // sample ended: accumulate, start the next sample of the pixel or finish the pixel (Raytracing.hlsl:372-413)
+template <bool DI = false>
 PT_DEV bool end_sample(const PtGraphicsSettings& gs, const PtTextures& tx, const float2* aux, PathRegs& p)
 {
     p.rsum = p.rsum + p.srad;                                    // :372
@@ -351,13 +367,22 @@ PT_DEV bool end_sample(const PtGraphicsSettings& gs, const PtTextures& tx, const
         const ushort4 rad = ((const ushort4*)tx.Radiance)[p.pixel];                          // primaryRadiance (G-buffer emission)
         const v3 ind = V3(fmaxf(out.x - f16_to_f32(rad.x), 0.0f), fmaxf(out.y - f16_to_f32(rad.y), 0.0f), fmaxf(out.z - f16_to_f32(rad.z), 0.0f));
         const float2 a = aux[p.pixel];
+        const bool isDiffuse = a.y != 0.0f;
+        if constexpr (DI) {                                                                   // direct + indirect, :405-412
+            v3 dd, ds; load_direct(tx, p.pixel, dd, ds);
+            const v3 id = isDiffuse ? ind : V3(0, 0, 0), is = isDiffuse ? V3(0, 0, 0) : ind;
+            const float hd = isDiffuse ? a.x : 0.0f, hs = isDiffuse ? 0.0f : a.x;
+            ((ushort4*)tx.Diffuse)[p.pixel] = make_ushort4(f32_to_f16(dd.x + id.x), f32_to_f16(dd.y + id.y), f32_to_f16(dd.z + id.z), f32_to_f16(hd));
+            ((ushort4*)tx.Specular)[p.pixel] = make_ushort4(f32_to_f16(ds.x + is.x), f32_to_f16(ds.y + is.y), f32_to_f16(ds.z + is.z), f32_to_f16(hs));
+            return false;
+        }
         const ushort4 packed = make_ushort4(f32_to_f16(ind.x), f32_to_f16(ind.y), f32_to_f16(ind.z), f32_to_f16(a.x));
         const ushort4 zero = make_ushort4(0, 0, 0, 0);
-        const bool isDiffuse = a.y != 0.0f;
         if (tx.Diffuse) ((ushort4*)tx.Diffuse)[p.pixel] = isDiffuse ? packed : zero;
         if (tx.Specular) ((ushort4*)tx.Specular)[p.pixel] = isDiffuse ? zero : packed;
         return false;
     }
+    if constexpr (DI) { v3 dd, ds; load_direct(tx, p.pixel, dd, ds); out = out + (dd + ds); }   // radiance += DI, after the division (:382, :390)
     if (gs.Denoiser == PT_DENOISER_DLSS_RAY_RECONSTRUCTION && tx.SpecularHitDistance) {      // :395-398
         const float2 a = aux[p.pixel];
         if (a.y == 0.0f && isfinite(a.x)) ((uint16_t*)tx.SpecularHitDistance)[p.pixel] = f32_to_f16(a.x);
@@ -374,7 +399,7 @@ template <bool LDS> struct GeometryFromBlob {                // ... out of the s
     PT_DEV HitGeometry load(uint32_t inst, uint32_t slot) const { return load_hit_geometry<LDS>(blob, bv, inst, slot); }
 };
 
-template <bool TEXTURED, typename GEOMETRY>
+template <bool TEXTURED, bool DI = false, typename GEOMETRY>
 PT_DEV void shade_traced(const SceneView& sv, const GEOMETRY& geometry, const PtSceneData& sd, const PtGraphicsSettings& gs, const PtTextures& tx, float2* aux,
                          PathRegs& p, uint4 hr, float hitT, v3 rayDir, bool& toTraced, bool& toFresh, v3& newO, v3& newD, RoundProf* prof = nullptr)
 {
@@ -389,14 +414,17 @@ PT_DEV void shade_traced(const SceneView& sv, const GEOMETRY& geometry, const Pt
         const PtMaterial m = surface_material<TEXTURED>(sv, h, geometry.tables.objects);
         BSDFSample bs;
         bs.Initialize(V3(m.BaseColor), m.Metallic, m.Roughness, m.IOR, m.Transmission, h.IsFrontFace);
-        goes = scatter(gs, p, h, bs, material_emission(m), rayDir, newO, newD, lobe);
+        v3 emission = material_emission(m);
+        if constexpr (DI) if (p.bounce == 1u && direct_valid(tx, p.pixel)) emission = V3(0, 0, 0);   // the DI pass lit this path's first hit, :302
+        goes = scatter(gs, p, h, bs, emission, rayDir, newO, newD, lobe);
     }
     if (goes) toTraced = true;
-    else toFresh = end_sample(gs, tx, aux, p);
+    else toFresh = end_sample<DI>(gs, tx, aux, p);
 }
 
 // A fresh path: bounce 0 on the primary surface rebuilt from the G-buffer, Raytracing.hlsl:118-148,193-198
 // (r0, r1, r2: the pixel's primary-surface record)
+template <bool DI = false>
 PT_DEV void shade_fresh_record(const FrameView& fv, const PtCamera& cam, const PtGraphicsSettings& gs, const PtTextures& tx, float2* aux, uint4 r0, uint4 r1, uint4 r2,
                                PathRegs& p, bool& toTraced, bool& toFresh, v3& newO, v3& newD)
 {
@@ -427,16 +455,17 @@ PT_DEV void shade_fresh_record(const FrameView& fv, const PtCamera& cam, const P
     if (scatter(gs, p, h, bs, emission, rayDir, newO, newD, lobe)) {
         toTraced = true;
         if (aux && first) aux[p.pixel].y = lobe == LOBE_DIFFUSE ? 1.0f : 0.0f;       // isDiffuse of the lobe sampled at bounce 0, :237
-    } else toFresh = end_sample(gs, tx, aux, p);
+    } else toFresh = end_sample<DI>(gs, tx, aux, p);
 }
 
+template <bool DI = false>
 PT_DEV void shade_fresh(const FrameView& fv, const PtCamera& cam, const PtGraphicsSettings& gs, const PtTextures& tx, float2* aux, const uint4* __restrict__ primary,
                         PathRegs& p, bool& toTraced, bool& toFresh, v3& newO, v3& newD, RoundProf* prof = nullptr)
 {
     const uint32_t pixel = p.pixel;
     const uint4 r0 = primary[3 * (size_t)pixel], r1 = primary[3 * (size_t)pixel + 1], r2 = primary[3 * (size_t)pixel + 2];
     PT_PROF_WAIT(); PT_PROF_MARK(prof, 13);
-    shade_fresh_record(fv, cam, gs, tx, aux, r0, r1, r2, p, toTraced, toFresh, newO, newD);
+    shade_fresh_record<DI>(fv, cam, gs, tx, aux, r0, r1, r2, p, toTraced, toFresh, newO, newD);
 }
 
 // compaction + stores of one tile: survivors to the traced region (state + ray), restarts to the fresh region (state).

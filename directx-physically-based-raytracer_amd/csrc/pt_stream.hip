@@ -9,7 +9,7 @@ namespace pt {
 // counts: [0..nsq) traced, [nsq..2*nsq) fresh (nsq = 1 << sqShift sub-queues)
 // k_shade<false> wants 132 VGPRs, one more than four waves per SIMD allow; held to 128 it spills nothing and the fourth wave is worth
 // +1.8 % on C3 and +0.7 % on C5 (the kernel waits on its 268 B per ray, not on issue slots)
-template <bool TEXTURED>
+template <bool TEXTURED, bool DI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_shade(SceneView sv, FrameView fv, const FrameConstants* __restrict__ fc, PtTextures tx,
                                                PathQueue qin, PathQueue qout, float2* aux, uint32_t segCap, const uint32_t* countIn, uint32_t* countOut,
                                                const uint4* __restrict__ primary, BlobView bv, const uint4* __restrict__ recA, const uint32_t* __restrict__ recB, uint32_t sqShift,
@@ -33,7 +33,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             p = load_path(qin, i);
             const uint4 hr = qin.hit[i];
             const float4 rd = qin.r1[i];                                     // k_extend left t in r1.w (denoiser modes)
-            shade_traced<TEXTURED>(sv, GeometryFromBlob<false>{ blob, bv, tables }, sd, gs, tx, aux, p, hr, rd.w, V3(rd.x, rd.y, rd.z), toTraced, toFresh, newO, newD);
+            shade_traced<TEXTURED, DI>(sv, GeometryFromBlob<false>{ blob, bv, tables }, sd, gs, tx, aux, p, hr, rd.w, V3(rd.x, rd.y, rd.z), toTraced, toFresh, newO, newD);
         }
         emit_tile(qout, seg, segCap, &countOut[sq], &countOut[nsq + sq], lds + ((emits++ & 1u) << 4), toTraced, toFresh, p, newO, newD);
     }
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         PathRegs p; v3 newO = V3(0, 0, 0), newD = V3(0, 0, 1);
         if (local < nF) {
             p = load_path(qin, seg + (segCap - 1u - local));
-            shade_fresh(fv, cam, gs, tx, aux, primary, p, toTraced, toFresh, newO, newD);
+            shade_fresh<DI>(fv, cam, gs, tx, aux, primary, p, toTraced, toFresh, newO, newD);
         }
         emit_tile(qout, seg, segCap, &countOut[sq], &countOut[nsq + sq], lds + ((emits++ & 1u) << 4), toTraced, toFresh, p, newO, newD);
     }
@@ -266,8 +266,10 @@ hipError_t launch_shade(Context& c, const SceneView& sv, const FrameView& fv, co
 {
     const bool rec = normal_records_usable(c);
     const uint4* recA = rec ? c.shadeRecA : nullptr; const uint32_t* recB = rec ? c.shadeRecB : nullptr;
-    if (c.heapHasTextures) k_shade<true><<<grid, 256, 0, stream>>>(sv, fv, c.frameConstants, tx, qin, qout, aux, segCap, countIn, countOut, c.primaryRecords, c.blob, recA, recB, c.sqShift, sqBase, sqCount);
-    else k_shade<false><<<grid, 256, 0, stream>>>(sv, fv, c.frameConstants, tx, qin, qout, aux, segCap, countIn, countOut, c.primaryRecords, c.blob, recA, recB, c.sqShift, sqBase, sqCount);
+    #define PT_SHADE(T, D) k_shade<T, D><<<grid, 256, 0, stream>>>(sv, fv, c.frameConstants, tx, qin, qout, aux, segCap, countIn, countOut, c.primaryRecords, c.blob, recA, recB, c.sqShift, sqBase, sqCount)
+    if (c.settings.IsDIEnabled) { if (c.heapHasTextures) PT_SHADE(true, true); else PT_SHADE(false, true); }
+    else { if (c.heapHasTextures) PT_SHADE(true, false); else PT_SHADE(false, false); }
+    #undef PT_SHADE
     return hipGetLastError();
 }
 

@@ -2,7 +2,10 @@
 // reference-shaped operators of ptamd.hpp (GBufferGeneration / Raytracing / RaytracingHelpers), times it and
 // optionally dumps the radiance for the parity test (tests/test_host_cpp.py compares it with the oracle).
 //
-//   pt_demo [--width W] [--height H] [--spp S] [--bounces B] [--frames N] [--out file.bin] [--ranks R]
+//   pt_demo [--width W] [--height H] [--spp S] [--bounces B] [--frames N] [--out file.bin] [--ranks R] [--di] [--di-samples N]
+//
+// --di: the direct-lighting pass between the G-buffer and the path tracer (App.cpp:1234-1308), LocalLightSamples = --di-samples (default 8);
+// the path tracer then runs with IsDIEnabled (with Bounces 0 the DI pass is the last render pass and adds to Radiance).
 //
 // --ranks R: one process per GPU. The parent (which never touches a GPU) starts R children `--rank r --world R --id-file F`; rank 0
 // makes the RCCL unique id and leaves it in F, the others pick it up; every rank renders its 16-row bands (BandSharding) and rank 0
@@ -219,6 +222,16 @@ static PtCamera make_camera(const HostScene& sc, double aspect)
         cam.WorldToProjection[4 * i + j] = cam.PreviousWorldToProjection[4 * i + j] = (float)w2p[i][j];
         cam.PreviousWorldToView[4 * i + j] = (float)w2v[i][j]; cam.PreviousViewToProjection[4 * i + j] = (float)v2p[i][j];
     }
+    // ProjectionToView = inverse(ViewToProjection) (its infinite-far form inverts in closed form), ViewToWorld = rows Right, Up, Forward,
+    // Position: what the direct-lighting pass reconstructs surface positions with (scenes.py:make_camera, Camera::ReconstructWorldPosition)
+    double p2v[4][4] = {}, v2w[4][4] = {};
+    p2v[0][0] = 1 / v2p[0][0]; p2v[1][1] = 1 / v2p[1][1]; p2v[2][3] = 1 / v2p[3][2]; p2v[3][2] = 1 / v2p[2][3];
+    for (int k = 0; k < 3; k++) { v2w[0][k] = r[k]; v2w[1][k] = u[k]; v2w[2][k] = f[k]; v2w[3][k] = pos[k]; }
+    v2w[3][3] = 1;
+    for (int i = 0; i < 16; i++) {
+        cam.ProjectionToView[i] = cam.PreviousProjectionToView[i] = (float)p2v[i / 4][i % 4];
+        cam.ViewToWorld[i] = cam.PreviousViewToWorld[i] = (float)v2w[i / 4][i % 4];
+    }
     return cam;
 }
 
@@ -323,15 +336,20 @@ static std::vector<uint8_t> exchange_unique_id(uint32_t rank, const std::string&
 int main(int argc, char** argv)
 {
     uint32_t W = 1920, H = 1080, spp = 4, bounces = 8, frames = 10, ranks = 0, rank = 0, world = 1;
+    uint32_t diSamples = 8; bool di = false;
     std::string out, idFile, scenePath, dumpPath;
-    for (int i = 1; i + 1 < argc; i += 2) {
+    for (int i = 1; i < argc; i++) {
         std::string k = argv[i];
-        if (k == "--width") W = atoi(argv[i + 1]); else if (k == "--height") H = atoi(argv[i + 1]);
-        else if (k == "--spp") spp = atoi(argv[i + 1]); else if (k == "--bounces") bounces = atoi(argv[i + 1]);
-        else if (k == "--frames") frames = atoi(argv[i + 1]); else if (k == "--out") out = argv[i + 1];
-        else if (k == "--ranks") ranks = atoi(argv[i + 1]); else if (k == "--rank") rank = atoi(argv[i + 1]);
-        else if (k == "--world") world = atoi(argv[i + 1]); else if (k == "--id-file") idFile = argv[i + 1];
-        else if (k == "--scene") scenePath = argv[i + 1]; else if (k == "--dump-scene") dumpPath = argv[i + 1];
+        if (k == "--di") { di = true; continue; }                  // the one flag without a value
+        if (i + 1 >= argc) break;
+        const char* v = argv[++i];
+        if (k == "--width") W = atoi(v); else if (k == "--height") H = atoi(v);
+        else if (k == "--spp") spp = atoi(v); else if (k == "--bounces") bounces = atoi(v);
+        else if (k == "--frames") frames = atoi(v); else if (k == "--out") out = v;
+        else if (k == "--ranks") ranks = atoi(v); else if (k == "--rank") rank = atoi(v);
+        else if (k == "--world") world = atoi(v); else if (k == "--id-file") idFile = v;
+        else if (k == "--di-samples") diSamples = atoi(v);
+        else if (k == "--scene") scenePath = v; else if (k == "--dump-scene") dumpPath = v;
     }
     const bool sharded = !idFile.empty();
     if (!dumpPath.empty()) {                                        // no GPU call on this path
@@ -435,6 +453,7 @@ int main(int argc, char** argv)
         tx.NormalizedDepth = alloc(px_ * 4); tx.MotionVector = alloc(px_ * 8); tx.BaseColorMetalness = alloc(px_ * 4); tx.NormalRoughness = alloc(px_ * 8);
         tx.IOR = alloc(px_ * 2); tx.Transmission = alloc(px_); tx.Radiance = alloc(px_ * 8);
         tx.RadianceF32 = radianceF32 = (float*)alloc(px_ * 16);
+        if (di) { tx.Diffuse = alloc(px_ * 8); tx.Specular = alloc(px_ * 8); }   // Raytracing::Textures Diffuse / Specular (App.cpp:475-482)
         void* fullRadiance = sharded && rank == 0 ? alloc(fullPx * 8) : nullptr;      // the assembled frame (R16G16B16A16_FLOAT), root only
         float* fullRadianceF32 = sharded && rank == 0 && !out.empty() ? (float*)alloc(fullPx * 16) : nullptr;
 
@@ -445,12 +464,22 @@ int main(int argc, char** argv)
         Raytracing raytracing(commandList);
         raytracing.GPUBuffers = { &sd, &cam, dObjects, n };
         raytracing.Textures = tx;
+        DirectLighting directLighting(commandList);
+        directLighting.GPUBuffers = { &sd, &cam, dObjects, n };
+        directLighting.Textures = tx;
         PtCounters counters{};
         double ms = 0;
         auto renderFrame = [&](uint32_t frameIndex) {
             gbuffer.Render(commandList, tlas, { { W, H }, ~0u & ~(uint32_t)GBufferGeneration::Flags::Albedo });     // App.cpp:1224
+            if (di) {                                               // App.cpp:1234-1308: RTXDI between the G-buffer and the path tracer
+                DirectLighting::Settings ds; ds.RenderSize[0] = W; ds.RenderSize[1] = H; ds.FrameIndex = frameIndex;
+                ds.LocalLightSamples = diSamples; ds.IsLastRenderPass = bounces == 0;
+                directLighting.SetConstants(ds);
+                directLighting.Render(commandList, tlas);
+            }
             Raytracing::GraphicsSettings gs; gs.RenderSize[0] = W; gs.RenderSize[1] = H;
             gs.FrameIndex = frameIndex; gs.Bounces = bounces; gs.SamplesPerPixel = spp; gs.IsRussianRouletteEnabled = true;
+            gs.IsDIEnabled = di;
             raytracing.SetConstants(gs);
             raytracing.Render(commandList, tlas);
             if (sharded) sharding.GatherBands(commandList, tx.Radiance, fullRadiance, W, H, 8);
@@ -465,6 +494,11 @@ int main(int argc, char** argv)
         ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         ThrowIfFailed(commandList.Context, pt_get_counters(commandList.Context, &counters));
         const double rays = (double)(counters.PrimaryRays + counters.SecondaryRays);
+        if (di) {                                                   // the direct-lighting pass's emissive triangles, on stderr
+            uint32_t lights = 0;
+            ThrowIfFailed(commandList.Context, pt_di_light_count(commandList.Context, &lights));
+            fprintf(stderr, "pt_demo: direct lighting over %u emissive triangles, %u candidates per pixel\n", lights, diSamples);
+        }
         if (!sharded)
             printf("{\"host\": \"c++\", \"width\": %u, \"height\": %u, \"spp\": %u, \"bounces\": %u, \"frames\": %u, \"rays\": %.0f, \"ms_per_frame\": %.4f, \"mrays_per_s\": %.1f}\n",
                    W, H, spp, bounces, frames, rays, ms / frames, rays / ms / 1e3);

@@ -174,18 +174,55 @@ struct SkeletalMeshSkinning {
     }
 };
 
-// The two calls the reference's direct-lighting bridge makes on the same scene data (Shaders/RTXDIAppBridge.hlsli:418-439,
-// Shaders/BxDF.hlsli:247-285), batched over device arrays.
-namespace DirectLighting {
-inline void TraceVisibility(CommandList& commandList, const PtRayDesc* deviceRays, uint32_t count, float* deviceVisibility)
-{
-    ThrowIfFailed(commandList.Context, pt_trace_visibility(commandList.Context, deviceRays, count, deviceVisibility));
-}
-inline void EvaluateBSDF(CommandList& commandList, const PtBsdfQuery* deviceQueries, uint32_t count, PtBsdfResult* deviceResults)
-{
-    ThrowIfFailed(commandList.Context, pt_bsdf_evaluate(commandList.Context, deviceQueries, count, deviceResults));
-}
-} // namespace DirectLighting
+// The RTXDI operator of the reference (Source/RTXDI.ixx: SetConstants + Render) as this library restates it: direct lighting from the
+// scene's emissive triangles, written to Textures.Diffuse / Specular for the path tracer (GraphicsSettings.IsDIEnabled), or added to
+// Textures.Radiance when it is the last render pass. Also the two calls the reference's direct-lighting bridge makes on the same scene
+// data (Shaders/RTXDIAppBridge.hlsli:418-439, Shaders/BxDF.hlsli:247-285), batched over device arrays.
+struct DirectLighting {
+    struct Settings {
+        uint32_t RenderSize[2]{};
+        uint32_t FrameIndex{}, LocalLightSamples = 8;        // 1..32
+        uint32_t Denoiser{};
+        bool IsLastRenderPass{};
+        uint32_t ExtFlags{};
+    };
+
+    struct { const PtSceneData* SceneData; const PtCamera* Camera; const PtObjectData* ObjectData; uint32_t ObjectCount; } GPUBuffers{};
+    PtTextures Textures{};                                  // the G-buffer it reads, Diffuse / Specular (or Radiance) it writes
+
+    explicit DirectLighting(CommandList& commandList) : m_context(commandList.Context) {}
+
+    void SetConstants(const Settings& settings)
+    {
+        PtDISettings s{};
+        s.RenderSize[0] = settings.RenderSize[0]; s.RenderSize[1] = settings.RenderSize[1];
+        s.FrameIndex = settings.FrameIndex; s.LocalLightSamples = settings.LocalLightSamples; s.Denoiser = settings.Denoiser;
+        s.IsLastRenderPass = settings.IsLastRenderPass ? 1u : 0u; s.ExtFlags = settings.ExtFlags;
+        ThrowIfFailed(m_context, pt_di_set_constants(m_context, &s));
+    }
+
+    void Render(CommandList& commandList, const RaytracingHelpers::TopLevelAccelerationStructure& topLevelAccelerationStructure)
+    {
+        if (!topLevelAccelerationStructure.Valid) throw std::invalid_argument("top-level acceleration structure has not been built");
+        PtContext* c = commandList.Context;
+        ThrowIfFailed(c, pt_set_scene_data(c, GPUBuffers.SceneData));
+        ThrowIfFailed(c, pt_set_camera(c, GPUBuffers.Camera));
+        ThrowIfFailed(c, pt_set_object_data(c, GPUBuffers.ObjectData, GPUBuffers.ObjectCount));
+        ThrowIfFailed(c, pt_di_render(c, &Textures));
+    }
+
+    static void TraceVisibility(CommandList& commandList, const PtRayDesc* deviceRays, uint32_t count, float* deviceVisibility)
+    {
+        ThrowIfFailed(commandList.Context, pt_trace_visibility(commandList.Context, deviceRays, count, deviceVisibility));
+    }
+    static void EvaluateBSDF(CommandList& commandList, const PtBsdfQuery* deviceQueries, uint32_t count, PtBsdfResult* deviceResults)
+    {
+        ThrowIfFailed(commandList.Context, pt_bsdf_evaluate(commandList.Context, deviceQueries, count, deviceResults));
+    }
+
+private:
+    PtContext* m_context;
+};
 
 struct GBufferGeneration {
     struct Flags {                                          // Source/GBufferGeneration.ixx:28-44

@@ -75,6 +75,28 @@ GRAPHICS_SETTINGS = np.dtype({
 
 EXT_LAMBERTIAN_ONLY = 0x1   # build-side switch living in the reference's padding word (config C1)
 
+DI_SETTINGS = np.dtype({  # PtDISettings (include/ptamd.h): RTXDI::SetConstants of this library's DI pass
+    "names": ["RenderSize", "FrameIndex", "LocalLightSamples", "Denoiser", "IsLastRenderPass", "ExtFlags"],
+    "formats": [("<u4", 2), "<u4", "<u4", "<u4", "<u4", "<u4"],
+    "offsets": [0, 8, 12, 16, 20, 24], "itemsize": 32})
+
+TRIANGLE_LIGHT = np.dtype({  # PtTriangleLight: one emissive triangle, world space (TriangleLight::Initialize, Light.hlsli)
+    "names": ["Base", "Area", "Edge0", "Power", "Edge1", "InstanceIndex", "Normal", "PrimitiveIndex", "Radiance", "GeometryIndex"],
+    "formats": [("<f4", 3), "<f4", ("<f4", 3), "<f4", ("<f4", 3), "<u4", ("<f4", 3), "<u4", ("<f4", 3), "<u4"],
+    "offsets": [0, 12, 16, 28, 32, 44, 48, 60, 64, 76], "itemsize": 80})
+
+
+def di_settings(width, height, frame_index=0, samples=8, denoiser=0, last_pass=False, ext_flags=0):
+    """PtDISettings with the reference's defaults (LocalLightSamples 8)."""
+    s = np.zeros((), DI_SETTINGS)
+    s["RenderSize"] = (width, height)
+    s["FrameIndex"] = frame_index
+    s["LocalLightSamples"] = samples
+    s["Denoiser"] = denoiser
+    s["IsLastRenderPass"] = 1 if last_pass else 0
+    s["ExtFlags"] = ext_flags
+    return s
+
 GBUFFER_CONSTANTS = np.dtype({
     "names": ["RenderSize", "Flags"], "formats": [("<u4", 2), "<u4"], "offsets": [0, 8], "itemsize": 12})
 

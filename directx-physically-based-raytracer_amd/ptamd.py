@@ -25,6 +25,7 @@ EXPORTS = [
     "pt_set_instance_data", "pt_set_sharding", "pt_local_rows", "pt_deinterleave_bands", "pt_gbuffer_render",
     "pt_comm_get_unique_id", "pt_comm_init", "pt_comm_adopt", "pt_comm_destroy", "pt_gather_bands", "pt_gather_plan",
     "pt_raytrace_set_constants", "pt_raytrace_render", "pt_trace_visibility", "pt_bsdf_evaluate", "pt_reset_counters", "pt_get_counters",
+    "pt_di_set_constants", "pt_di_render", "pt_di_light_count", "pt_di_download_lights",
     "pt_set_debug_flags", "pt_debug_read_mismatch", "pt_debug_download_blob", "pt_debug_trace_ray", "pt_enable_kernel_timing", "pt_get_kernel_timing", "pt_get_round_timing",
 ]
 
@@ -131,6 +132,10 @@ def load_library():
         lib.pt_trace_visibility.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.pt_bsdf_evaluate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.pt_reset_counters.argtypes = [C.c_void_p]
+        lib.pt_di_set_constants.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_di_render.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_di_light_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        lib.pt_di_download_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.pt_set_debug_flags.argtypes = [C.c_void_p, C.c_uint32]
         lib.pt_debug_read_mismatch.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_debug_download_blob.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -520,6 +525,47 @@ class Raytracing:
         ctx.check(lib.pt_raytrace_render(ctx.handle, C.addressof(t)))
 
 
+class DirectLighting:
+    """Mirror of the reference's RTXDI operator (Source/RTXDI.ixx: SetConstants + Render) for this library's DI pass: emissive-triangle
+    lights, LocalLightSamples power-proportional candidates, streaming RIS, one visibility ray. Writes Textures["Diffuse"] /
+    Textures["Specular"] (or adds to Textures["Radiance"] when it is the last render pass with Denoiser None / DLSS-RR)."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.GPUBuffers = {"SceneData": None, "Camera": None, "ObjectData": None}
+        self.Textures = {}
+        self._settings = None
+
+    def SetConstants(self, settings):
+        self._settings = np.array(settings).reshape(())
+        self.ctx.check(self.ctx.lib.pt_di_set_constants(self.ctx.handle, C.c_void_p(self._settings.ctypes.data)))
+
+    def Render(self, topLevelAccelerationStructure):
+        ctx, lib = self.ctx, self.ctx.lib
+        if self.GPUBuffers["Camera"] is not None:
+            cam = np.array(self.GPUBuffers["Camera"])
+            ctx.check(lib.pt_set_camera(ctx.handle, C.c_void_p(cam.ctypes.data)))
+        if self.GPUBuffers["SceneData"] is not None:
+            sd = np.array(self.GPUBuffers["SceneData"])
+            ctx.check(lib.pt_set_scene_data(ctx.handle, C.c_void_p(sd.ctypes.data)))
+        t = _pack_textures(self.Textures)
+        ctx.check(lib.pt_di_render(ctx.handle, C.addressof(t)))
+
+    def light_count(self):
+        n = C.c_uint32(0)
+        self.ctx.check(self.ctx.lib.pt_di_light_count(self.ctx.handle, C.byref(n)))
+        return n.value
+
+    def download_lights(self):
+        """The light records of the last Render (numpy layouts.TRIANGLE_LIGHT, list order)."""
+        n = C.c_uint32(0)
+        self.ctx.check(self.ctx.lib.pt_di_download_lights(self.ctx.handle, None, 0, C.byref(n)))
+        out = np.zeros(n.value, L.TRIANGLE_LIGHT)
+        if n.value:
+            self.ctx.check(self.ctx.lib.pt_di_download_lights(self.ctx.handle, C.c_void_p(out.ctypes.data), n.value, C.byref(n)))
+        return out
+
+
 class Renderer:
     """App::RenderScene for this path (Source/App.cpp:1157-1329): G-buffer pass, then the path tracer."""
 
@@ -530,8 +576,9 @@ class Renderer:
         self.textures = alloc_textures(width, self.local_rows, scene_gpu.device, with_f32, with_denoiser_outputs)
         self.gbuffer = GBufferGeneration(ctx)
         self.raytracing = Raytracing(ctx)
+        self.direct_lighting = DirectLighting(ctx)
         d = scene_gpu.desc
-        for op in (self.gbuffer, self.raytracing):
+        for op in (self.gbuffer, self.raytracing, self.direct_lighting):
             op.GPUBuffers["Camera"] = d.camera
             op.GPUBuffers["SceneData"] = d.scene_data
             op.Textures = self.textures
@@ -539,11 +586,18 @@ class Renderer:
         self.constants["RenderSize"] = (width, height)
         self.constants["Flags"] = L.GBufferFlags.DefaultNoDenoiser        # App.cpp:1224 with Denoiser::None
 
-    def render(self, settings):
+    def render(self, settings, di_samples=0):
+        """di_samples > 0: run the DI pass with that many candidates per pixel; set settings["IsDIEnabled"] to have the path tracer
+        consume it (the textures need Diffuse / Specular: with_denoiser_outputs=True)."""
         tlas = self.scene.GetTopLevelAccelerationStructure()
         denoiser = int(np.array(settings).reshape(())["Denoiser"])
         self.constants["Flags"] = 0xFFFFFFFF if denoiser != L.DENOISER_NONE else L.GBufferFlags.DefaultNoDenoiser   # App.cpp:1223
         self.gbuffer.Render(tlas, self.constants)
+        if di_samples:                                                    # App.cpp:1234-1308: the DI pass between the two
+            s = np.array(settings).reshape(())
+            self.direct_lighting.SetConstants(L.di_settings(self.width, self.height, int(s["FrameIndex"]), di_samples, denoiser,
+                                                            last_pass=int(s["Bounces"]) == 0, ext_flags=int(s["ExtFlags"])))
+            self.direct_lighting.Render(tlas)
         if int(np.array(settings).reshape(())["Bounces"]) > 0:            # App.cpp:1277
             self.raytracing.SetConstants(settings)
             self.raytracing.Render(tlas)

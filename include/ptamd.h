@@ -356,6 +356,44 @@ int  pt_raytrace_set_constants(PtContext* ctx, const PtGraphicsSettings* setting
 int  pt_raytrace_render(PtContext* ctx, const PtTextures* textures);
 
 /* ------------------------------------------------------------------------------------------
+ * direct lighting over emissive triangles (RTXDI::SetConstants + RTXDI::Render, Source/RTXDI.ixx; LightPreparation,
+ * DIInitialSampling, DIFinalShading) without temporal / spatial reuse: per pixel LocalLightSamples power-proportional
+ * candidates, streaming RIS, one coloured visibility ray. Writes Textures.Diffuse / Specular (R16G16B16A16_FLOAT:
+ * radiance.rgb, light distance), which pt_raytrace_render consumes when GraphicsSettings.IsDIEnabled is set; with
+ * IsLastRenderPass and Denoiser None / DLSS-RR the result is added to Textures.Radiance instead (DIFinalShading.hlsl:78-103).
+ * Reads the G-buffer (LinearDepth, GeometricNormal, NormalRoughness, BaseColorMetalness, IOR, Transmission) and the camera /
+ * object data bound for the G-buffer pass. Enqueued on the context's stream; the light list is rebuilt (one wait) only when
+ * the instances of the top level, the object-data binding or pt_invalidate_object_data change it.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct PtDISettings {
+    uint32_t RenderSize[2];
+    uint32_t FrameIndex;
+    uint32_t LocalLightSamples;           /* candidates per pixel, 1..32 (reference default 8) */
+    uint32_t Denoiser;                    /* PtDenoiser */
+    uint32_t IsLastRenderPass;            /* 1: no path-tracing pass follows (Bounces 0) */
+    uint32_t ExtFlags;                    /* PT_EXT_LAMBERTIAN_ONLY honoured */
+    uint32_t _pad;
+} PtDISettings;                           /* 32 B */
+
+/* One emissive triangle, world space, recomputed at every pt_di_render (TriangleLight::Initialize, Light.hlsli). 80 B. */
+typedef struct PtTriangleLight {
+    float Base[3], Area;                  /* Area = |Edge0 x Edge1| / 2 (0 for a degenerate triangle) */
+    float Edge0[3], Power;                /* Power = Area * pi * luminance(Radiance) (CalculatePower) */
+    float Edge1[3]; uint32_t InstanceIndex;
+    float Normal[3];                      /* unit (Edge0 x Edge1), 0 when degenerate */
+    uint32_t PrimitiveIndex;
+    float Radiance[3];                    /* EmissiveColor * EmissiveStrength, times the emissive texture at the UV centroid */
+    uint32_t GeometryIndex;
+} PtTriangleLight;                         /* 80 B */
+
+int  pt_di_set_constants(PtContext* ctx, const PtDISettings* settings);
+int  pt_di_render(PtContext* ctx, const PtTextures* textures);
+/* emissive triangles of the current light list (rebuilt first if it is stale); synchronises */
+int  pt_di_light_count(PtContext* ctx, uint32_t* out_count);
+/* the records of the last pt_di_render, list order (instance, geometry, triangle); synchronises */
+int  pt_di_download_lights(PtContext* ctx, PtTriangleLight* host_dst, uint32_t capacity, uint32_t* out_count);
+
+/* ------------------------------------------------------------------------------------------
  * building blocks the reference's direct-lighting bridge calls on the same data
  * ------------------------------------------------------------------------------------------ */
 typedef struct PtRayDesc { float Origin[3]; float TMin; float Direction[3]; float TMax; } PtRayDesc;   /* HLSL RayDesc, 32 B */

@@ -1,0 +1,62 @@
+"""Developer helper: time the direct-lighting pass (HIP events around N back-to-back pt_di_render calls) and one DI-on frame (G-buffer + DI +
+path tracer with IsDIEnabled) against the DI-off frame, per workload. Each workload runs in a child process of its own.
+usage: tools/di_time.py [--workloads c2,c3,c5] [--samples 8] [--n 20]"""
+import argparse, json, os, subprocess, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def child(w, samples, n):
+    sys.path.insert(0, ROOT)
+    import torch
+    import __graft_entry__ as ge
+    ge.load_package()
+    import dxpbrt_amd.layouts as L, dxpbrt_amd.ptamd as P, dxpbrt_amd.scenes as S
+    import bench
+    kind, W, H, spp, bounces, desc = bench.WORKLOADS[w]
+    scene, ext = bench.make_scene(kind, W / H, S)
+    ctx = P.DeviceContext(0)
+    ctx.set_frames_in_flight(1)
+    g = P.Scene(ctx, scene)
+    r = P.Renderer(ctx, g, W, H, with_denoiser_outputs=True)
+    tlas = g.GetTopLevelAccelerationStructure()
+    gs = S.graphics_settings(W, H, spp=spp, bounces=bounces, ext_flags=ext)
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+
+    def timed(fn, k):
+        a, b = ev(), ev()
+        a.record()
+        for i in range(k):
+            fn(i)
+        b.record(); torch.cuda.synchronize()
+        return a.elapsed_time(b) / k
+
+    r.render(gs)                                               # G-buffer + warm-up
+    ctx.sync()
+    r.direct_lighting.SetConstants(L.di_settings(W, H, 0, samples, ext_flags=ext))
+    lights = r.direct_lighting.light_count()
+    for _ in range(3):
+        r.direct_lighting.Render(tlas)
+    ctx.sync()
+    di_ms = timed(lambda i: r.direct_lighting.Render(tlas), n)
+    off_ms = timed(lambda i: r.render(gs), max(3, n // 4))
+    gs_on = gs.copy(); gs_on["IsDIEnabled"] = 1
+    r.render(gs_on, di_samples=samples); ctx.sync()
+    on_ms = timed(lambda i: r.render(gs_on, di_samples=samples), max(3, n // 4))
+    print(json.dumps({"workload": w, "size": [W, H], "lights": lights, "samples": samples, "di_ms": di_ms, "frame_di_off_ms": off_ms, "frame_di_on_ms": on_ms}))
+    ctx.close()
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--child", default=None); ap.add_argument("--workloads", default="c2,c3,c5")
+    ap.add_argument("--samples", type=int, default=8); ap.add_argument("--n", type=int, default=20)
+    a = ap.parse_args()
+    if a.child:
+        child(a.child, a.samples, a.n); sys.exit(0)
+    for w in a.workloads.split(","):
+        p = subprocess.run([sys.executable, __file__, "--child", w, "--samples", str(a.samples), "--n", str(a.n)], stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, text=True, timeout=600)
+        line = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        print(line[0] if line else "%s FAILED (exit %d) %s" % (w, p.returncode, p.stderr[-400:]), flush=True)
+        if p.returncode < 0:                                    # a child killed by a signal: start nothing more on the GPU
+            sys.exit(1)
