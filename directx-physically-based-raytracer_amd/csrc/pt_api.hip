@@ -854,6 +854,16 @@ int pt_bsdf_evaluate(PtContext* ctx, const PtBsdfQuery* device_queries, uint32_t
     return PT_OK;
 }
 
+int pt_bsdf_sample(PtContext* ctx, const PtBsdfSampleQuery* device_queries, uint32_t count, PtBsdfSampleResult* device_results)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    API_ARG(&c, count == 0 || (device_queries && device_results), "query / result buffer is NULL");
+    API_HIP(&c, hipSetDevice(c.device));
+    API_HIP(&c, launch_bsdf_sample(c.stream, (const float*)device_queries, count, (float*)device_results));
+    return PT_OK;
+}
+
 // ---- measurement ----------------------------------------------------------------------------
 int pt_reset_counters(PtContext* ctx)
 {

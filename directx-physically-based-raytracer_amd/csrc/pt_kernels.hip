@@ -639,6 +639,29 @@ __global__ __launch_bounds__(256) void k_bsdf_evaluate(const float* __restrict__
     o[0] = dif.x; o[1] = dif.y; o[2] = dif.z; o[3] = spc.x; o[4] = spc.y; o[5] = spc.z; o[6] = pdf; o[7] = 0.0f;
 }
 
+// one bounce's BSDF step as scatter() takes it: Initialize, ComputeLobeWeights, Sample, single-lobe EvaluateLobe (PtBsdfSampleQuery / Result)
+__global__ __launch_bounds__(256) void k_bsdf_sample(const float* __restrict__ q, uint32_t count, float* __restrict__ r)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const float* a = q + 24 * (size_t)i;
+    BSDFSample b;
+    const bool front = a[7] != 0.0f;
+    b.Initialize(V3(a), a[3], a[4], a[5], a[6], front);
+    const SurfaceVectors sv = surface_vectors(front, V3(a + 8), V3(a + 11));
+    const v3 V = V3(a + 14);
+    const float rnd[4] = { a[17], a[18], a[19], a[20] };
+    const uint32_t ext = __float_as_uint(a[21]);
+    float w[3]; b.ComputeLobeWeights(sv, V, ext, w);
+    v3 L = V3(0.0f, 0.0f, 0.0f); int lobe = 0;
+    const bool ok = b.Sample(sv, V, w, rnd, L, lobe);
+    float pdf = 0.0f; v3 f = V3(0.0f, 0.0f, 0.0f);
+    if (ok) b.EvaluateLobe(sv, L, V, w, lobe, ext, pdf, f);
+    float* o = r + 12 * (size_t)i;
+    o[0] = L.x; o[1] = L.y; o[2] = L.z; o[3] = pdf; o[4] = f.x; o[5] = f.y; o[6] = f.z; o[7] = w[0]; o[8] = w[1]; o[9] = w[2];
+    o[10] = __uint_as_float((uint32_t)lobe); o[11] = __uint_as_float(ok ? 1u : 0u);
+}
+
 hipError_t launch_visibility(Context& c, const SceneView& sv, const void* rays, uint32_t count, void* out)
 {
     if (!count) return hipSuccess;
@@ -651,6 +674,13 @@ hipError_t launch_bsdf_evaluate(hipStream_t stream, const float* q, uint32_t cou
 {
     if (!count) return hipSuccess;
     k_bsdf_evaluate<<<(count + 255) / 256, 256, 0, stream>>>(q, count, r);
+    return hipGetLastError();
+}
+
+hipError_t launch_bsdf_sample(hipStream_t stream, const float* q, uint32_t count, float* r)
+{
+    if (!count) return hipSuccess;
+    k_bsdf_sample<<<(count + 255) / 256, 256, 0, stream>>>(q, count, r);
     return hipGetLastError();
 }
 

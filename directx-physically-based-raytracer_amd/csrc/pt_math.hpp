@@ -188,7 +188,7 @@ PT_DEV float ml_distribution_ggx(float roughness, float NoH)
 {
     float m = roughness * roughness;
     float m2 = m * m;
-    float t = mad(mad(NoH, m2, -NoH), NoH, 1.0f);
+    float t = fmaxf(mad(mad(NoH, m2, -NoH), NoH, 1.0f), 0x1p-24f);    // floor: m2 - 1 rounds to -1 below roughness ~0.015, so NoH == 1 gave t = 0, D = inf
     float a = m / t;
     return PT_DIV_CONST(a * a, kPi);
 }

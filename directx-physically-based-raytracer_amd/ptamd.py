@@ -24,7 +24,7 @@ EXPORTS = [
     "pt_build_top_level", "pt_get_accel_stats", "pt_share_scene", "pt_set_camera", "pt_set_scene_data", "pt_set_object_data", "pt_invalidate_object_data",
     "pt_set_instance_data", "pt_set_sharding", "pt_local_rows", "pt_deinterleave_bands", "pt_gbuffer_render",
     "pt_comm_get_unique_id", "pt_comm_init", "pt_comm_adopt", "pt_comm_destroy", "pt_gather_bands", "pt_gather_plan",
-    "pt_raytrace_set_constants", "pt_raytrace_render", "pt_trace_visibility", "pt_bsdf_evaluate", "pt_reset_counters", "pt_get_counters",
+    "pt_raytrace_set_constants", "pt_raytrace_render", "pt_trace_visibility", "pt_bsdf_evaluate", "pt_bsdf_sample", "pt_reset_counters", "pt_get_counters",
     "pt_di_set_constants", "pt_di_render", "pt_di_light_count", "pt_di_download_lights",
     "pt_set_debug_flags", "pt_debug_read_mismatch", "pt_debug_download_blob", "pt_debug_trace_ray", "pt_enable_kernel_timing", "pt_get_kernel_timing", "pt_get_round_timing",
 ]
@@ -84,6 +84,28 @@ class AccelStats(C.Structure):
                 ("OwnedBottomLevelBytes", C.c_uint64), ("RoundObjectsInLds", C.c_uint32), ("RoundRecordsInLds", C.c_uint32)]
 
 
+_BSDF_MATERIAL = [("BaseColor", C.c_float * 3), ("Metallic", C.c_float), ("Roughness", C.c_float), ("IOR", C.c_float),
+                  ("Transmission", C.c_float), ("IsFrontFace", C.c_float),
+                  ("GeometricNormal", C.c_float * 3), ("ShadingNormal", C.c_float * 3), ("V", C.c_float * 3)]
+
+
+class BsdfQuery(C.Structure):
+    _fields_ = _BSDF_MATERIAL + [("L", C.c_float * 3)]
+
+
+class BsdfResult(C.Structure):
+    _fields_ = [("Diffuse", C.c_float * 3), ("Specular", C.c_float * 3), ("PDF", C.c_float), ("_pad", C.c_float)]
+
+
+class BsdfSampleQuery(C.Structure):
+    _fields_ = _BSDF_MATERIAL + [("Random", C.c_float * 4), ("ExtFlags", C.c_uint32), ("_pad", C.c_uint32 * 2)]
+
+
+class BsdfSampleResult(C.Structure):
+    _fields_ = [("L", C.c_float * 3), ("PDF", C.c_float), ("F", C.c_float * 3), ("Weights", C.c_float * 3),
+                ("Lobe", C.c_uint32), ("Ok", C.c_uint32)]
+
+
 def load_library():
     """Load libptamd.so; fail loudly when the HIP extension has not been built."""
     global _LIB
@@ -131,6 +153,7 @@ def load_library():
         lib.pt_gbuffer_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pt_trace_visibility.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.pt_bsdf_evaluate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.pt_bsdf_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.pt_reset_counters.argtypes = [C.c_void_p]
         lib.pt_di_set_constants.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_di_render.argtypes = [C.c_void_p, C.c_void_p]

@@ -411,6 +411,16 @@ typedef struct PtBsdfQuery {
 } PtBsdfQuery;                            /* 80 B */
 typedef struct PtBsdfResult { float Diffuse[3], Specular[3], PDF, _pad; } PtBsdfResult;   /* 32 B */
 int  pt_bsdf_evaluate(PtContext* ctx, const PtBsdfQuery* device_queries, uint32_t count, PtBsdfResult* device_results);
+/* One bounce's BSDF step (Shaders/Raytracing.hlsl:326-342): Initialize + ComputeLobeWeights + Sample(random) + the single-lobe
+ * EvaluatePDF / Evaluate of the sampled lobe, batched. The material part of the query is laid out as in PtBsdfQuery.
+ * Result: the sampled L, the lobe and Sample's return value (Ok); PDF and F are 0 when Ok is 0. */
+typedef struct PtBsdfSampleQuery {
+    float BaseColor[3], Metallic, Roughness, IOR, Transmission, IsFrontFace;     /* IsFrontFace: 0 or 1 */
+    float GeometricNormal[3], ShadingNormal[3], V[3], Random[4];
+    uint32_t ExtFlags, _pad[2];                                                  /* PT_EXT_* */
+} PtBsdfSampleQuery;                      /* 96 B */
+typedef struct PtBsdfSampleResult { float L[3], PDF, F[3], Weights[3]; uint32_t Lobe, Ok; } PtBsdfSampleResult;   /* 48 B */
+int  pt_bsdf_sample(PtContext* ctx, const PtBsdfSampleQuery* device_queries, uint32_t count, PtBsdfSampleResult* device_results);
 
 /* Measurement (no reference counterpart). Counters cover the work enqueued since the last reset;
  * reading them synchronises the stream. */

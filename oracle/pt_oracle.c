@@ -238,7 +238,7 @@ static float ml_distribution_ggx(float roughness, float NoH)
 {
     float m = roughness * roughness;
     float m2 = m * m;
-    float t = mad(mad(NoH, m2, -NoH), NoH, 1.0f);
+    float t = fmaxf(mad(mad(NoH, m2, -NoH), NoH, 1.0f), 0x1p-24f);   /* 2^-24: what 1 - NoH^2 (0.99999994 - m^2) gives at NoH = 1 */
     float a = m / t;
     return a * a / 3.14159265358979323846f;
 }
@@ -555,6 +555,18 @@ int or_bsdf_sample(const float mat[7], int front_face, const float Ng[3], const 
         f[0] = fv.x; f[1] = fv.y; f[2] = fv.z;
     }
     return ok;
+}
+
+void or_bsdf_sample_batch(const float* q, uint32_t count, float* r)
+{
+    for (uint32_t i = 0; i < count; i++, q += 24, r += 12) {
+        uint32_t ext, lobe_ok[2];
+        memcpy(&ext, q + 21, 4);
+        int lobe = 0;
+        lobe_ok[1] = (uint32_t)or_bsdf_sample(q, q[7] != 0.0f, q + 8, q + 11, q + 14, q + 17, ext, r, &lobe, r + 3, r + 4, r + 7);
+        lobe_ok[0] = (uint32_t)lobe;
+        memcpy(r + 10, lobe_ok, 8);
+    }
 }
 
 /* ======================================================================== */

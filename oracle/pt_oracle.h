@@ -218,6 +218,11 @@ void     or_invert_3x4(const float m[12], float out[12]);
  * q: 20 floats per query = base.rgb metallic roughness ior transmission frontFace(0/1) Ng.xyz Ns.xyz V.xyz L.xyz
  * r:  8 floats per query = diffuse.rgb specular.rgb pdf 0 */
 void     or_bsdf_evaluate(const float* q, uint32_t count, float* r);
+/* or_bsdf_sample over a batch: Initialize + ComputeLobeWeights + Sample + single-lobe EvaluatePDF / Evaluate, as one bounce does.
+ * q: 24 floats per query = base.rgb metallic roughness ior transmission frontFace(0/1) Ng.xyz Ns.xyz V.xyz rnd.xyzw
+ *    extFlags(uint32 bits) 0 0
+ * r: 12 floats per query = L.xyz pdf f.rgb weights[3] lobe(uint32 bits) ok(uint32 bits); pdf and f are 0 when ok is 0 */
+void     or_bsdf_sample_batch(const float* q, uint32_t count, float* r);
 /* TraceRay<FORCE_NON_OPAQUE | ACCEPT_FIRST_HIT_AND_END_SEARCH> with the coloured-visibility IsOpaque overload
  * (RaytracingHelpers.hlsli:7-55, ShadingHelpers.hlsli:117-159, RTXDIAppBridge.hlsli:418-439).
  * rays: 8 floats per ray = origin.xyz tmin dir.xyz tmax; out: 4 floats = visibility.rgb, 1 if nothing was committed else 0 */

@@ -36,6 +36,15 @@ def test_struct_sizes_match_reference_layouts(pkg, ptamd):
     assert L.INSTANCE_DATA.fields["ObjectToWorld"][1] == 64
     assert C.sizeof(ptamd.GeometryDesc) == 40 and C.sizeof(ptamd.InstanceDesc) == 64
     assert C.sizeof(ptamd.Textures) == 17 * 8 and C.sizeof(ptamd.Counters) == 64
+    # the BSDF building blocks: flat float arrays of 20 / 8 / 24 / 12 words in the tests and the oracle
+    assert C.sizeof(ptamd.BsdfQuery) == 80 and C.sizeof(ptamd.BsdfResult) == 32
+    assert C.sizeof(ptamd.BsdfSampleQuery) == 96 and C.sizeof(ptamd.BsdfSampleResult) == 48
+    for s, name, off in ((ptamd.BsdfQuery, "GeometricNormal", 32), (ptamd.BsdfQuery, "L", 68),
+                         (ptamd.BsdfResult, "PDF", 24), (ptamd.BsdfSampleQuery, "GeometricNormal", 32),(ptamd.BsdfSampleQuery, "V", 56),
+                         (ptamd.BsdfSampleQuery, "Random", 68), (ptamd.BsdfSampleQuery, "ExtFlags", 84),
+                         (ptamd.BsdfSampleResult, "F", 16), (ptamd.BsdfSampleResult, "Weights", 28),
+                         (ptamd.BsdfSampleResult, "Lobe", 40), (ptamd.BsdfSampleResult, "Ok", 44)):
+        assert getattr(s, name).offset == off, (s.__name__, name)
 
 
 def test_fails_loudly_without_gpu(ptamd):
