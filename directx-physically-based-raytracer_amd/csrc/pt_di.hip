@@ -7,9 +7,12 @@
 //   k_cdf_*                        <- the local-light pdf texture of the reference's Power_RIS mode, as a fixed-order prefix sum
 //   k_di                           <- DIInitialSampling (local lights only, streaming RIS) + DIFinalShading, no temporal /
 //                                     spatial reuse (RTXDIAppBridge.hlsli RAB_GetGBufferSurface, RAB_Surface::Shade, GetFinalVisibility)
+//   k_di_initial_temporal          <- DIInitialSampling + DITemporalResampling (boiling filter), with reservoir reuse on
+//   k_di_spatial_shade             <- DISpatialResampling + DIFinalShading
 // DESIGN.md section 1 ("Direct lighting") is the arithmetic spec: seeding, draw order, triangle mapping.
 #include "pt_internal.hpp"
 
+#include <cmath>
 #include <cstring>
 
 #include "pt_shade.hpp"
@@ -208,6 +211,114 @@ PT_DEV void shade_sample(const BSDFSample& bs, const SurfaceVectors& svec, const
     spc = V3(spc.x * Le.x * inv, spc.y * Le.y * inv, spc.z * Le.z * inv);
 }
 
+// G-buffer planes a surface is read from (the current frame's, or the Previous* textures)
+struct DIGBuffer { const void *depth, *normalRoughness, *geometricNormal, *baseColorMetalness, *ior, *transmission; };
+struct DISurface { v3 P, V; SurfaceVectors svec; BSDFSample bs; float w[3]; float depth; };
+
+// RAB_GetGBufferSurface (RTXDIAppBridge.hlsli:293-345) at pixel (x, y); false: the empty surface. The camera is the current one or,
+// for the previous frame, PreviousProjectionToView / PreviousViewToWorld / PreviousPosition -- with the current Jitter (:332).
+PT_DEV bool di_surface(const DIGBuffer& g, size_t pi, uint32_t x, uint32_t y, const FrameView& fv, const float jitter[2], const float* projectionToView,
+                       const float* viewToWorld, const float* position, uint32_t ext, DISurface& s)
+{
+    const float depth = ((const float*)g.depth)[pi];
+    if (!isfinite(depth)) return false;
+    const short4 nr = ((const short4*)g.normalRoughness)[pi];
+    const float roughness = snorm16_to_f32(nr.w);
+    if (roughness < 0.05f) return false;                                 // MinRoughness
+    const float u = ((float)x + 0.5f + jitter[0]) / (float)fv.width, v = ((float)y + 0.5f + jitter[1]) / (float)fv.height;
+    float q[4];
+    xform4(projectionToView, V3(u * 2.0f + -1.0f, v * -2.0f + 1.0f, 0.5f), q);          // Camera::ReconstructWorldPosition
+    const v3 vp = V3(q[0] / q[2] * depth, q[1] / q[2] * depth, depth);
+    xform4(viewToWorld, vp, q);
+    s.P = V3(q[0], q[1], q[2]);
+    s.V = normalize(V3(position[0] - s.P.x, position[1] - s.P.y, position[2] - s.P.z));
+    const short2 ge = ((const short2*)g.geometricNormal)[pi];
+    const v3 gn = oct_decode(snorm16_to_f32(ge.x), snorm16_to_f32(ge.y));
+    const bool front = dot(gn, s.V) > 0.0f;
+    s.svec = surface_vectors(front, gn, V3(snorm16_to_f32(nr.x), snorm16_to_f32(nr.y), snorm16_to_f32(nr.z)));
+    const uchar4 bcm = ((const uchar4*)g.baseColorMetalness)[pi];
+    const float metal = unorm8_to_f32(bcm.w);
+    const float tr = metal < 1.0f ? unorm8_to_f32(((const uint8_t*)g.transmission)[pi]) : 0.0f;
+    s.bs.Initialize(V3(unorm8_to_f32(bcm.x), unorm8_to_f32(bcm.y), unorm8_to_f32(bcm.z)), metal, roughness, f16_to_f32(((const uint16_t*)g.ior)[pi]), tr, front);
+    s.bs.ComputeLobeWeights(s.svec, s.V, ext, s.w);
+    s.depth = depth;
+    return true;
+}
+
+// p-hat of light sample (li, U, V) at surface s (RAB_GetLightSampleTargetPdfForSurface): the luminance of the all-lobe Shade. The
+// sample's point is re-derived from the light record: Math::SampleTriangle with r1 = U, r2 = V.
+PT_DEV float di_target(const DIArgs& a, const DISurface& s, uint32_t li, float U, float V, v3& pos, v3& dif, v3& spc)
+{
+    const float4* L = a.lights + kLightRec16 * (size_t)li;
+    const float4 l0 = L[0], l1 = L[1], l2 = L[2], l3 = L[3], l4 = L[4];
+    const float sq = sqrtf(U);                                          // Math::SampleTriangle
+    const float b0 = sq * (1.0f - V), b1 = sq * V;
+    pos = V3(l0.x + l1.x * b0 + l2.x * b1, l0.y + l1.y * b0 + l2.y * b1, l0.z + l1.z * b0 + l2.z * b1);
+    const v3 d = pos - s.P;
+    const float len = sqrtf(dot(d, d));
+    const v3 dn = V3(d.x / len, d.y / len, d.z / len);
+    const float cosL = fabsf(dot(dn, -V3(l3.x, l3.y, l3.z)));
+    const float pdfSA = (1.0f / l0.w) * len * len / cosL;              // CalculateSolidAnglePDF
+    shade_sample(s.bs, s.svec, s.w, a.ext, s.P, s.V, pos, V3(l4.x, l4.y, l4.z), pdfSA, dif, spc);
+    return ml_luminance(dif + spc);
+}
+
+// initial sampling: LocalLightSamples power-proportional candidates, streaming RIS (RTXDI_StreamSample); the selected sample's
+// shaded terms stay in registers
+struct DIInitial { float wsum, p; v3 dif, spc, pos; float u, v; uint32_t li; };
+PT_DEV void di_initial(const DIArgs& a, const DISurface& s, uint32_t x, uint32_t y, float total, DIInitial& o)
+{
+    uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDISalt);
+    o.wsum = 0.0f; o.p = 0.0f; o.u = 0.0f; o.v = 0.0f; o.li = ~0u;
+    o.dif = V3(0, 0, 0); o.spc = V3(0, 0, 0); o.pos = V3(0, 0, 0);
+    for (uint32_t k = 0; k < a.samples; k++) {
+        const float r0 = rng_float(rng), r1 = rng_float(rng), r2 = rng_float(rng), r3 = rng_float(rng);
+        const uint32_t li = select_light(a.cdf, a.count, r0 * total, total);
+        v3 pos, dif, spc;
+        const float p = di_target(a, s, li, r1, r2, pos, dif, spc);
+        const float ris = p > 0.0f ? p / (a.lights[kLightRec16 * (size_t)li + 1].w / total) : 0.0f;   // target / source pdf (light selection; the point is uniform in uv)
+        o.wsum += ris;
+        if (r3 * o.wsum < ris) { o.p = p; o.dif = dif; o.spc = spc; o.pos = pos; o.u = r1; o.v = r2; o.li = li; }
+    }
+}
+
+// final shading (DIFinalShading.hlsl): one coloured visibility ray, CreateVisibilityRay with offset 1e-3; outputs :78-103
+PT_DEV void di_final(const DIArgs& a, BlobView bv, const AlphaContext& ac, DeviceCounters* counters, uint2* ldsStack, size_t pi, v3 P, v3 posSel,
+                     v3 difSel, v3 spcSel, float W)
+{
+    const PtTextures& tx = a.tx;
+    const v3 d = posSel - P;
+    const float dist = sqrtf(dot(d, d));
+    const v3 dir = V3(d.x / dist, d.y / dist, d.z / dist);
+    uint2 spill[kStackSize - kLdsStackDepth];
+    GroupStack<kLdsStackDepth> stack; stack.init((PT_LDS_AS void*)ldsStack, spill);
+    BlobReader<false> blob; blob.p = bv.base;
+    TraceStats st; st.nodes = 0; st.tris = 0; st.overflow = 0;
+    v3 vis;
+    trace_single<false, false, true>(blob, bv, ac, P, dir, 1e-3f, fmaxf(0.0f, dist - 2e-3f), stack, &st, &vis);
+    if (st.overflow) atomicAdd(&counters->stackOverflows, st.overflow);
+    if (vis.x == 0.0f && vis.y == 0.0f && vis.z == 0.0f) return;
+    const v3 dif = V3(difSel.x * vis.x * W, difSel.y * vis.y * W, difSel.z * vis.z * W);
+    const v3 spc = V3(spcSel.x * vis.x * W, spcSel.y * vis.y * W, spcSel.z * vis.z * W);
+    const v3 rad = dif + spc;
+    if ((rad.x == 0.0f && rad.y == 0.0f && rad.z == 0.0f) || !finite3(rad)) return;
+
+    if (a.lastPass && a.denoiser <= PT_DENOISER_DLSS_RAY_RECONSTRUCTION) {
+        ushort4* R = (ushort4*)tx.Radiance;
+        const ushort4 o = R[pi];
+        const v3 sum = V3(f16_to_f32(o.x) + rad.x, f16_to_f32(o.y) + rad.y, f16_to_f32(o.z) + rad.z);
+        R[pi] = make_ushort4(f32_to_f16(sum.x), f32_to_f16(sum.y), f32_to_f16(sum.z), o.w);
+        if (tx.RadianceF32) ((float4*)tx.RadianceF32)[pi] = make_float4(sum.x, sum.y, sum.z, 0.0f);
+        if (a.denoiser == PT_DENOISER_DLSS_RAY_RECONSTRUCTION && tx.SpecularHitDistance && (spc.x > 0.0f || spc.y > 0.0f || spc.z > 0.0f))
+            ((uint16_t*)tx.SpecularHitDistance)[pi] = f32_to_f16(dist);
+        return;
+    }
+    ((ushort4*)tx.Diffuse)[pi] = make_ushort4(f32_to_f16(dif.x), f32_to_f16(dif.y), f32_to_f16(dif.z), f32_to_f16(dist));
+    ((ushort4*)tx.Specular)[pi] = make_ushort4(f32_to_f16(spc.x), f32_to_f16(spc.y), f32_to_f16(spc.z), f32_to_f16(dist));
+}
+
+PT_DEV DIGBuffer current_gbuffer(const PtTextures& tx) { return DIGBuffer{ tx.LinearDepth, tx.NormalRoughness, tx.GeometricNormal, tx.BaseColorMetalness, tx.IOR, tx.Transmission }; }
+
 // One thread per local pixel; a wave covers an 8 x 8 square (as k_gbuffer), so the visibility rays of a wave stay together.
 __global__ __launch_bounds__(256) void k_di(DIArgs a, BlobView bv, AlphaContext ac, DeviceCounters* counters)
 {
@@ -305,6 +416,211 @@ __global__ __launch_bounds__(256) void k_di(DIArgs a, BlobView bv, AlphaContext 
     ((ushort4*)tx.Specular)[pi] = make_ushort4(f32_to_f16(spc.x), f32_to_f16(spc.y), f32_to_f16(spc.z), f32_to_f16(dist));
 }
 
+// ---- reservoir reuse (DITemporalResampling / DISpatialResampling; DESIGN.md section 1, "Reservoir reuse") --------------------------------
+constexpr uint32_t kDITemporalSalt = 0x44490002u, kDISpatialSalt = 0x44490003u;
+constexpr uint32_t kDIOffsetCount = 8192u;          // neighbour-offset table entries (int8 x, y)
+static_assert(sizeof(PtDIReservoir) == 32 && sizeof(PtDIResamplingSettings) == 64 && sizeof(PtDIPreviousTextures) == 48, "layout");
+
+struct DIReuseArgs {
+    DIArgs d;
+    DIGBuffer prev; float prevPosition[3]; float prevProjectionToView[16], prevViewToWorld[16];
+    const PtDIReservoir* in; PtDIReservoir* out;  // temporal: last frame's final reservoirs -> A; spatial: A -> B
+    const char2* offsets;
+    uint32_t haveHistory, maxHistory, boiling, spatialSamples, boostSamples;
+    float boilingMul, tDepth, tNormal, radius, sDepth, sNormal;
+};
+
+PT_DEV PtDIReservoir di_empty(uint32_t M)
+{
+    PtDIReservoir r; r.LightIndex = ~0u; r.U = 0.0f; r.V = 0.0f; r.W = 0.0f; r.M = M; r.TargetPdf = 0.0f; r.Age = 0u; r._pad = 0u;
+    return r;
+}
+PT_DEV PtDIReservoir di_load(const PtDIReservoir* p, size_t i)
+{
+    const uint4 a = ((const uint4*)p)[2 * i], b = ((const uint4*)p)[2 * i + 1];
+    PtDIReservoir r; r.LightIndex = a.x; r.U = __uint_as_float(a.y); r.V = __uint_as_float(a.z); r.W = __uint_as_float(a.w);
+    r.M = b.x; r.TargetPdf = __uint_as_float(b.y); r.Age = b.z; r._pad = 0u;
+    return r;
+}
+PT_DEV void di_store(PtDIReservoir* p, size_t i, const PtDIReservoir& r)
+{
+    ((uint4*)p)[2 * i] = make_uint4(r.LightIndex, __float_as_uint(r.U), __float_as_uint(r.V), __float_as_uint(r.W));
+    ((uint4*)p)[2 * i + 1] = make_uint4(r.M, __float_as_uint(r.TargetPdf), r.Age, 0u);
+}
+// RAB_ClampSamplePositionIntoView: reflect across the screen edges (one reflection; a position still outside reads the empty surface)
+PT_DEV void di_reflect(int& x, int& y, int w, int h)
+{
+    if (x < 0) x = -x;
+    if (y < 0) y = -y;
+    if (x >= w) x = 2 * w - x - 1;
+    if (y >= h) y = 2 * h - y - 1;
+}
+// the neighbour test: shading normals, relative depth (RTXDI_CompareRelativeDifference) and RAB_AreMaterialsSimilar
+PT_DEV bool di_similar(const DISurface& a, const DISurface& b, float depthA, float normalThreshold, float depthThreshold)
+{
+    if (!(dot(a.svec.ShadingNormal, b.svec.ShadingNormal) >= normalThreshold)) return false;
+    if (!(fabsf(depthA - b.depth) <= depthThreshold * fmaxf(depthA, b.depth))) return false;
+    if (!(fabsf(a.bs.Roughness - b.bs.Roughness) <= 0.5f * fmaxf(a.bs.Roughness, b.bs.Roughness))) return false;
+    return fabsf(ml_luminance(a.bs.F0) - ml_luminance(b.bs.F0)) <= 0.25f && fabsf(ml_luminance(a.bs.Albedo) - ml_luminance(b.bs.Albedo)) <= 0.25f;
+}
+PT_DEV float di_target_of(const DIArgs& a, const DISurface& s, uint32_t li, float U, float V)
+{
+    if (li >= a.count) return 0.0f;
+    v3 pos, dif, spc;
+    return di_target(a, s, li, U, V, pos, dif, spc);
+}
+
+// Initial sampling fused with temporal reuse: the temporal step at a pixel reads only that pixel's fresh reservoir and last frame's data.
+// TEMPORAL = false writes the initial reservoirs (the spatial pass's input). The boiling filter is a 64-lane butterfly over the wave's
+// 8 x 8 tile, so every lane stays to the end.
+template <bool TEMPORAL, bool BASIC>
+__global__ __launch_bounds__(256) void k_di_initial_temporal(DIReuseArgs r)
+{
+    const DIArgs& a = r.d;
+    const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63u;
+    const uint32_t x = blockIdx.x * 16 + (wv & 1u) * 8u + (ln & 7u), y = blockIdx.y * 16 + (wv >> 1) * 8u + (ln >> 3);
+    const bool inside = x < a.fv.width && y < a.fv.localRows;             // unsharded: local row = global row
+    const size_t pi = (size_t)y * a.fv.width + x;
+    PtDIReservoir res = di_empty(0u);
+    DISurface s;
+    const bool valid = inside && di_surface(current_gbuffer(a.tx), pi, x, y, a.fv, a.cam.jitter, a.cam.projectionToView, a.cam.viewToWorld, a.cam.position, a.ext, s);
+    if (valid) {
+        res.M = a.samples;
+        const float total = *a.total;
+        if (total > 0.0f && isfinite(total)) {
+            DIInitial i0;
+            di_initial(a, s, x, y, total, i0);
+            if (i0.p > 0.0f) { res.LightIndex = i0.li; res.U = i0.u; res.V = i0.v; res.W = i0.wsum / (float)a.samples / i0.p; res.TargetPdf = i0.p; }
+        }
+        if (TEMPORAL) {
+            const int w = (int)a.fv.width, h = (int)a.fv.height;
+            uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDITemporalSalt);
+            DISurface sp;
+            int hx = -1, hy = -1;
+            if (r.haveHistory) {
+                const ushort4 mv = ((const ushort4*)a.tx.MotionVector)[pi];
+                const float expected = s.depth + f16_to_f32(mv.z);
+                const float fx = fminf(fmaxf((float)x + f16_to_f32(mv.x), -65536.0f), 65536.0f), fy = fminf(fmaxf((float)y + f16_to_f32(mv.y), -65536.0f), 65536.0f);
+                const int px = (int)rintf(fx), py = (int)rintf(fy);            // HLSL round: to nearest even
+                for (int i = 0; i < 9; i++) {
+                    int qx = px, qy = py;
+                    if (i) { const float rx = rng_float(rng), ry = rng_float(rng); qx += (int)((rx - 0.5f) * 6.0f); qy += (int)((ry - 0.5f) * 6.0f); }
+                    di_reflect(qx, qy, w, h);
+                    if (qx < 0 || qy < 0 || qx >= w || qy >= h) continue;
+                    if (!di_surface(r.prev, (size_t)qy * w + qx, qx, qy, a.fv, a.cam.jitter, r.prevProjectionToView, r.prevViewToWorld, r.prevPosition, a.ext, sp)) continue;
+                    if (!di_similar(s, sp, expected, r.tNormal, r.tDepth)) continue;
+                    hx = qx; hy = qy;
+                    break;
+                }
+            }
+            // combine(s, R0, 0.5, p(y0)) selects R0; then combine(s, H, rc, p(yH)) with the draw after every search draw
+            const uint32_t Mcur = res.M;
+            float wsum = res.TargetPdf * res.W * (float)res.M;
+            PtDIReservoir H = di_empty(0u);
+            bool fromH = false;
+            if (hx >= 0) {
+                H = di_load(r.in, (size_t)hy * w + hx);
+                H.M = min(H.M, r.maxHistory * Mcur);
+                const float pH = di_target_of(a, s, H.LightIndex, H.U, H.V);
+                const float rc = rng_float(rng);
+                const float wH = pH * H.W * (float)H.M;
+                wsum += wH;
+                if (rc * wsum < wH) { res.LightIndex = H.LightIndex; res.U = H.U; res.V = H.V; res.TargetPdf = pH; res.Age = H.Age == ~0u ? ~0u : H.Age + 1u; fromH = true; }
+                res.M = Mcur + H.M;
+            }
+            const float p = res.TargetPdf;
+            if (!(p > 0.0f)) {
+                res = di_empty(res.M);
+            } else if (BASIC) {                                             // p at the previous surface: no visibility
+                const float pPrev = hx >= 0 ? di_target_of(a, sp, res.LightIndex, res.U, res.V) : 0.0f;
+                const float den = p * ((float)Mcur * p + (float)H.M * pPrev);
+                res.W = den > 0.0f ? wsum * (fromH ? pPrev : p) / den : 0.0f;
+            } else {
+                res.W = wsum / (p * (float)res.M);
+            }
+        }
+    }
+    if (TEMPORAL && r.boiling) {                                           // boiling filter: the tile's mean of the nonzero weights
+        const bool nz = valid && res.W > 0.0f;
+        float sum = nz ? res.W : 0.0f, cnt = nz ? 1.0f : 0.0f;
+        for (int m = 1; m < 64; m <<= 1) { sum += __shfl_xor(sum, m); cnt += __shfl_xor(cnt, m); }
+        if (cnt > 0.0f && res.W > sum / cnt * r.boilingMul) res = di_empty(0u);
+    }
+    if (inside) di_store(r.out, pi, res);
+}
+
+// Spatial reuse, then final shading in the same thread. SPATIAL = false: the final reservoir is the input (temporal-only).
+template <bool SPATIAL, bool BASIC>
+__global__ __launch_bounds__(256) void k_di_spatial_shade(DIReuseArgs r, BlobView bv, AlphaContext ac, DeviceCounters* counters)
+{
+    const DIArgs& a = r.d;
+    const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63u;
+    const uint32_t x = blockIdx.x * 16 + (wv & 1u) * 8u + (ln & 7u), y = blockIdx.y * 16 + (wv >> 1) * 8u + (ln >> 3);
+    if (x >= a.fv.width || y >= a.fv.localRows) return;                 // no barrier below
+    const size_t pi = (size_t)y * a.fv.width + x;
+    const DIGBuffer g = current_gbuffer(a.tx);
+    PtDIReservoir c = di_load(r.in, pi);
+    DISurface s;
+    if (!di_surface(g, pi, x, y, a.fv, a.cam.jitter, a.cam.projectionToView, a.cam.viewToWorld, a.cam.position, a.ext, s)) { di_store(r.out, pi, c); return; }
+    if (SPATIAL) {
+        const int w = (int)a.fv.width, h = (int)a.fv.height;
+        uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDISpatialSalt);
+        const uint32_t start = (uint32_t)(rng_float(rng) * 8191.0f);
+        const uint32_t n = c.M < r.maxHistory ? max(r.spatialSamples, r.boostSamples) : r.spatialSamples;
+        float wsum = c.TargetPdf * c.W * (float)c.M;                       // combine(s, centre, 0.5, p(y_c)): selects the centre
+        uint32_t M = c.M, mask = 0u;
+        int sel = -1;
+        PtDIReservoir o = c;
+        for (uint32_t i = 0; i < n; i++) {
+            const char2 e = r.offsets[(start + i) & (kDIOffsetCount - 1u)];
+            int qx = (int)x + (int)((float)e.x / 127.0f * r.radius), qy = (int)y + (int)((float)e.y / 127.0f * r.radius);
+            di_reflect(qx, qy, w, h);
+            if (qx < 0 || qy < 0 || qx >= w || qy >= h) continue;
+            DISurface sn;
+            if (!di_surface(g, (size_t)qy * w + qx, qx, qy, a.fv, a.cam.jitter, a.cam.projectionToView, a.cam.viewToWorld, a.cam.position, a.ext, sn)) continue;
+            if (!di_similar(s, sn, s.depth, r.sNormal, r.sDepth)) continue;
+            mask |= 1u << i;
+            const PtDIReservoir rn = di_load(r.in, (size_t)qy * w + qx);
+            const float pn = di_target_of(a, s, rn.LightIndex, rn.U, rn.V);
+            const float rc = rng_float(rng);
+            const float wn = pn * rn.W * (float)rn.M;
+            wsum += wn; M += rn.M;
+            if (rc * wsum < wn) { o.LightIndex = rn.LightIndex; o.U = rn.U; o.V = rn.V; o.TargetPdf = pn; o.Age = rn.Age; sel = (int)i; }
+        }
+        const float p = o.TargetPdf;
+        o.M = M;
+        if (p > 0.0f) {
+            if (BASIC) {                                                     // sum over the centre and the contributing neighbours
+                float den = (float)c.M * p, pSrc = p;
+                for (uint32_t i = 0; i < n; i++) {
+                    if (!(mask & (1u << i))) continue;
+                    const char2 e = r.offsets[(start + i) & (kDIOffsetCount - 1u)];
+                    int qx = (int)x + (int)((float)e.x / 127.0f * r.radius), qy = (int)y + (int)((float)e.y / 127.0f * r.radius);
+                    di_reflect(qx, qy, w, h);
+                    DISurface sn;
+                    di_surface(g, (size_t)qy * w + qx, qx, qy, a.fv, a.cam.jitter, a.cam.projectionToView, a.cam.viewToWorld, a.cam.position, a.ext, sn);
+                    const float pn = di_target_of(a, sn, o.LightIndex, o.U, o.V);
+                    den += (float)r.in[(size_t)qy * w + qx].M * pn;
+                    if ((int)i == sel) pSrc = pn;
+                }
+                den *= p;
+                o.W = den > 0.0f ? wsum * pSrc / den : 0.0f;
+            } else {
+                o.W = wsum / (p * (float)M);
+            }
+        } else {
+            o = di_empty(M);
+        }
+        c = o;
+    }
+    di_store(r.out, pi, c);
+    if (c.LightIndex >= a.count || !(c.W > 0.0f)) return;
+    v3 pos, dif, spc;
+    di_target(a, s, c.LightIndex, c.U, c.V, pos, dif, spc);
+    __shared__ uint2 ldsStack[kLdsStackDepth * 256];
+    di_final(a, bv, ac, counters, ldsStack, pi, s.P, pos, dif, spc, c.W);
+}
+
 // ---- host --------------------------------------------------------------------------------------------------------------------
 void release_direct_lighting(Context& c)
 {
@@ -315,6 +631,27 @@ void release_direct_lighting(Context& c)
     if (c.lightBlockSums) hipFree(c.lightBlockSums);
     c.lightList = nullptr; c.lightInstStart = nullptr; c.lightRecords = nullptr; c.lightCdf = nullptr; c.lightBlockSums = nullptr;
     c.lightListCap = c.lightInstCap = c.lightRecordCap = 0; c.lightListValid = false;
+    if (c.diResA) hipFree(c.diResA);
+    if (c.diResB) hipFree(c.diResB);
+    if (c.diOffsets) hipFree(c.diOffsets);
+    c.diResA = c.diResB = nullptr; c.diOffsets = nullptr; c.diResCap = 0; c.diHistoryValid = false; c.diResCount = 0;
+}
+
+// The spatial neighbour-offset table: the R2 sequence from (0.5, 0.5), points outside the disc of radius 0.5
+// rejected, scaled to int8. Built in double on the host, the same on every machine.
+void build_di_offsets(int8_t* out)
+{
+    const double phi = 1.0 / 1.3247179572447, phi2 = phi * phi;
+    double u = 0.5, v = 0.5;
+    for (uint32_t k = 0; k < kDIOffsetCount;) {
+        u += phi; v += phi2;
+        if (u >= 1.0) u -= 1.0;
+        if (v >= 1.0) v -= 1.0;
+        if ((u - 0.5) * (u - 0.5) + (v - 0.5) * (v - 0.5) > 0.25) continue;
+        out[2 * k] = (int8_t)(int)((u - 0.5) * 254.0);
+        out[2 * k + 1] = (int8_t)(int)((v - 0.5) * 254.0);
+        k++;
+    }
 }
 
 // The scene's light list, one per context (a context that views another's scene lists the same triangles from the owner's read-only
@@ -330,7 +667,7 @@ hipError_t ensure_light_list(Context& c, const SceneView& sv)
     if (c.lightListValid && c.lightListKey == key) return hipSuccess;
     hipError_t e;
     const uint32_t n = s.tlas.instanceCount;
-    c.lightCount = 0; c.lightListValid = false;
+    c.lightCount = 0; c.lightListValid = false; c.diHistoryValid = false;       // light indices may move
     if (n && c.instSourceDev && c.blasTableDev && c.objectCount) {
         if (n + 1u > c.lightInstCap) {
             if ((e = hipStreamSynchronize(c.stream)) != hipSuccess) return e;
@@ -384,7 +721,7 @@ int pt_di_set_constants(PtContext* ctx, const PtDISettings* s)
     return PT_OK;
 }
 
-int pt_di_render(PtContext* ctx, const PtTextures* tx)
+int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPreviousTextures* prev)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
@@ -396,16 +733,24 @@ int pt_di_render(PtContext* ctx, const PtTextures* tx)
     const bool toRadiance = s.IsLastRenderPass && s.Denoiser <= PT_DENOISER_DLSS_RAY_RECONSTRUCTION;
     DI_ARG(toRadiance ? tx->Radiance != nullptr : (tx->Diffuse && tx->Specular),
            toRadiance ? "IsLastRenderPass with Denoiser None / DLSS-RR adds to Textures.Radiance: not bound" : "the DI pass writes Textures.Diffuse / Textures.Specular: not bound");
+    const PtDIResamplingSettings& rs = c.diReuse;
+    const bool reuse = c.diReuseOn, temporal = reuse && rs.TemporalResampling, spatial = reuse && rs.SpatialSamples > 0;
+    if (temporal)
+        DI_ARG(prev && prev->PreviousGeometricNormal && prev->PreviousLinearDepth && prev->PreviousBaseColorMetalness && prev->PreviousNormalRoughness &&
+               prev->PreviousIOR && prev->PreviousTransmission && tx->MotionVector,
+               "temporal resampling reads Textures.MotionVector and the six Previous* textures: not bound");
     DI_HIP(hipSetDevice(c.device));
     SceneView sv; FrameView fv; memset(&sv, 0, sizeof sv); memset(&fv, 0, sizeof fv);
     int st = di_views(c, s.RenderSize[0], s.RenderSize[1], sv, fv, true);
     if (st != PT_OK) return st;
+    DI_ARG(!reuse || fv.rankCount == 1, "reservoir reuse needs an unsharded context (RankCount 1)");
     const size_t npix = (size_t)fv.width * fv.localRows;
     if (tx->Diffuse) DI_HIP(hipMemsetAsync(tx->Diffuse, 0, npix * 8u, c.stream));                // App.cpp:1238-1239
     if (tx->Specular) DI_HIP(hipMemsetAsync(tx->Specular, 0, npix * 8u, c.stream));
     DI_HIP(ensure_light_list(c, sv));
     const uint32_t n = c.lightCount;
     c.lightRecordCount = n;
+    if (!reuse || n == 0 || npix == 0) { c.diHistoryValid = false; c.diResCount = 0; }
     if (n == 0 || npix == 0) return PT_OK;
     const uint32_t nb = (n + kScanBlock - 1u) / kScanBlock;
     if (n > c.lightRecordCap) {
@@ -431,10 +776,113 @@ int pt_di_render(PtContext* ctx, const PtTextures* tx)
     a.lights = c.lightRecords; a.cdf = c.lightCdf; a.total = c.lightBlockSums + nb; a.count = n;
     a.frameIndex = s.FrameIndex; a.samples = s.LocalLightSamples; a.denoiser = s.Denoiser; a.lastPass = s.IsLastRenderPass; a.ext = s.ExtFlags;
     AlphaContext ac; ac.objects = sv.objects; ac.heap = sv.heap; ac.srgbLut = sv.srgbLut; ac.instances = sv.accel.instances; ac.shadeTex = sv.shadeTex;
-    k_di<<<dim3((fv.width + 15u) / 16u, (fv.localRows + 15u) / 16u), 256, 0, c.stream>>>(a, c.blob, ac, c.counters);
+    const dim3 grid((fv.width + 15u) / 16u, (fv.localRows + 15u) / 16u);
+    if (!reuse) {
+        k_di<<<grid, 256, 0, c.stream>>>(a, c.blob, ac, c.counters);
+        DI_HIP(hipGetLastError());
+        return PT_OK;
+    }
+
+    // reservoir reuse: k_di_initial_temporal (last frame's B -> A), k_di_spatial_shade (A -> B); B is next frame's history
+    if (npix > c.diResCap || !c.diOffsets) {
+        DI_HIP(hipStreamSynchronize(c.stream));
+        if (npix > c.diResCap) {
+            if (c.diResA) hipFree(c.diResA);
+            if (c.diResB) hipFree(c.diResB);
+            c.diResA = c.diResB = nullptr; c.diResCap = 0; c.diHistoryValid = false;
+            DI_HIP(hipMalloc((void**)&c.diResA, sizeof(PtDIReservoir) * npix));
+            DI_HIP(hipMalloc((void**)&c.diResB, sizeof(PtDIReservoir) * npix));
+            c.diResCap = npix;
+        }
+        if (!c.diOffsets) {
+            int8_t host[2 * kDIOffsetCount];
+            build_di_offsets(host);
+            DI_HIP(hipMalloc((void**)&c.diOffsets, sizeof host));
+            DI_HIP(hipMemcpy(c.diOffsets, host, sizeof host, hipMemcpyHostToDevice));
+        }
+    }
+    if (c.diHistorySize[0] != fv.width || c.diHistorySize[1] != fv.height || c.diHistoryLightKey != c.lightListKey) c.diHistoryValid = false;
+    DIReuseArgs r; memset(&r, 0, sizeof r);
+    r.d = a;
+    if (temporal) {
+        r.prev = DIGBuffer{ prev->PreviousLinearDepth, prev->PreviousNormalRoughness, prev->PreviousGeometricNormal, prev->PreviousBaseColorMetalness,
+                            prev->PreviousIOR, prev->PreviousTransmission };
+        memcpy(r.prevPosition, c.camera.PreviousPosition, sizeof r.prevPosition);
+        memcpy(r.prevProjectionToView, c.camera.PreviousProjectionToView, sizeof r.prevProjectionToView);
+        memcpy(r.prevViewToWorld, c.camera.PreviousViewToWorld, sizeof r.prevViewToWorld);
+    }
+    r.offsets = (const char2*)c.diOffsets;
+    r.haveHistory = c.diHistoryValid ? 1u : 0u;
+    r.maxHistory = rs.MaxHistoryLength; r.boiling = rs.BoilingFilter; r.spatialSamples = rs.SpatialSamples; r.boostSamples = rs.DisocclusionBoostSamples;
+    r.boilingMul = 10.0f / std::min(std::max(rs.BoilingFilterStrength, 1e-6f), 1.0f) - 9.0f;
+    r.tDepth = rs.TemporalDepthThreshold; r.tNormal = rs.TemporalNormalThreshold;
+    r.radius = rs.SpatialSamplingRadius; r.sDepth = rs.SpatialDepthThreshold; r.sNormal = rs.SpatialNormalThreshold;
+    r.in = c.diResB; r.out = c.diResA;
+    const bool tb = rs.TemporalBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC, sb = rs.SpatialBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC;
+    if (!temporal) k_di_initial_temporal<false, false><<<grid, 256, 0, c.stream>>>(r);
+    else if (tb) k_di_initial_temporal<true, true><<<grid, 256, 0, c.stream>>>(r);
+    else k_di_initial_temporal<true, false><<<grid, 256, 0, c.stream>>>(r);
     DI_HIP(hipGetLastError());
+    r.in = c.diResA; r.out = c.diResB;
+    if (!spatial) k_di_spatial_shade<false, false><<<grid, 256, 0, c.stream>>>(r, c.blob, ac, c.counters);
+    else if (sb) k_di_spatial_shade<true, true><<<grid, 256, 0, c.stream>>>(r, c.blob, ac, c.counters);
+    else k_di_spatial_shade<true, false><<<grid, 256, 0, c.stream>>>(r, c.blob, ac, c.counters);
+    DI_HIP(hipGetLastError());
+    c.diHistoryValid = true; c.diHistorySize[0] = fv.width; c.diHistorySize[1] = fv.height; c.diHistoryLightKey = c.lightListKey;
+    c.diResCount = (uint32_t)npix;
     return PT_OK;
 }
+
+int pt_di_render(PtContext* ctx, const PtTextures* tx) { return pt_di_render_with_history(ctx, tx, nullptr); }
+
+int pt_di_set_resampling(PtContext* ctx, const PtDIResamplingSettings* s)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    PtDIResamplingSettings v; memset(&v, 0, sizeof v);
+    if (s) {
+        DI_ARG(s->TemporalResampling <= 1u && s->BoilingFilter <= 1u, "TemporalResampling / BoilingFilter must be 0 or 1");
+        DI_ARG(s->TemporalBiasCorrection != 2u && s->TemporalBiasCorrection != 3u && s->SpatialBiasCorrection != 2u && s->SpatialBiasCorrection != 3u,
+               "Pairwise and Raytraced bias correction are not supported (use PT_DI_BIAS_CORRECTION_OFF or _BASIC)");
+        DI_ARG(s->TemporalBiasCorrection <= 1u && s->SpatialBiasCorrection <= 1u, "unknown bias-correction mode");
+        DI_ARG(s->MaxHistoryLength >= 1u && s->MaxHistoryLength <= 64u, "MaxHistoryLength must be 1..64");
+        DI_ARG(s->BoilingFilterStrength >= 0.0f && s->BoilingFilterStrength <= 1.0f, "BoilingFilterStrength must be in [0, 1]");
+        DI_ARG(s->SpatialSamples <= 32u, "SpatialSamples must be 0..32");
+        DI_ARG(s->DisocclusionBoostSamples <= 32u, "DisocclusionBoostSamples must be 0..32");
+        DI_ARG(s->SpatialSamplingRadius > 0.0f && s->SpatialSamplingRadius <= 64.0f, "SpatialSamplingRadius must be in (0, 64]");
+        DI_ARG(s->TemporalDepthThreshold >= 0.0f && s->SpatialDepthThreshold >= 0.0f && std::isfinite(s->TemporalDepthThreshold) && std::isfinite(s->SpatialDepthThreshold),
+               "depth thresholds must be finite and >= 0");
+        DI_ARG(s->TemporalNormalThreshold >= -1.0f && s->TemporalNormalThreshold <= 1.0f && s->SpatialNormalThreshold >= -1.0f && s->SpatialNormalThreshold <= 1.0f,
+               "normal thresholds must be in [-1, 1]");
+        v = *s;
+        memset(v._pad, 0, sizeof v._pad);
+    }
+    const bool on = v.TemporalResampling || v.SpatialSamples;
+    if (on != c.diReuseOn || memcmp(&v, &c.diReuse, sizeof v) != 0) c.diHistoryValid = false;
+    c.diReuse = v; c.diReuseOn = on;
+    return PT_OK;
+}
+
+int pt_di_reset_history(PtContext* ctx)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    ctx->c.diHistoryValid = false;
+    return PT_OK;
+}
+
+int pt_di_download_reservoirs(PtContext* ctx, PtDIReservoir* host_dst, uint32_t capacity, uint32_t* out_count)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    DI_ARG(out_count && (host_dst || capacity == 0), "out_count / host_dst is NULL");
+    DI_HIP(hipSetDevice(c.device));
+    DI_HIP(hipStreamSynchronize(c.stream));
+    *out_count = c.diResCount;
+    const uint32_t k = std::min(capacity, c.diResCount);
+    if (k) DI_HIP(hipMemcpy(host_dst, c.diResB, sizeof(PtDIReservoir) * (size_t)k, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
 
 int pt_di_light_count(PtContext* ctx, uint32_t* out_count)
 {

@@ -193,6 +193,11 @@ struct Context {
     uint32_t* lightInstStart = nullptr; uint32_t lightInstCap = 0;          // per instance: first list entry; [instanceCount]: the total
     uint64_t lightListKey = 0; bool lightListValid = false;
     float4* lightRecords = nullptr; float* lightCdf = nullptr; float* lightBlockSums = nullptr; uint32_t lightRecordCap = 0, lightRecordCount = 0;
+    // reservoir reuse (pt_di_set_resampling): A = temporal output, B = final reservoirs = next frame's history
+    PtDIResamplingSettings diReuse{}; bool diReuseOn = false;
+    PtDIReservoir* diResA = nullptr; PtDIReservoir* diResB = nullptr; size_t diResCap = 0;
+    int8_t* diOffsets = nullptr;                      // the spatial neighbour-offset table, 8192 (x, y) pairs
+    bool diHistoryValid = false; uint32_t diHistorySize[2] = {0, 0}; uint64_t diHistoryLightKey = 0; uint32_t diResCount = 0;
 };
 
 std::string& create_error();             // pt_api.hip: the message pt_last_error(NULL) returns (errors of the context-free entry points)

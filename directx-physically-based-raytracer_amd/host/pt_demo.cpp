@@ -2,10 +2,12 @@
 // reference-shaped operators of ptamd.hpp (GBufferGeneration / Raytracing / RaytracingHelpers), times it and
 // optionally dumps the radiance for the parity test (tests/test_host_cpp.py compares it with the oracle).
 //
-//   pt_demo [--width W] [--height H] [--spp S] [--bounces B] [--frames N] [--out file.bin] [--ranks R] [--di] [--di-samples N]
+//   pt_demo [--width W] [--height H] [--spp S] [--bounces B] [--frames N] [--out file.bin] [--ranks R] [--di] [--di-samples N] [--restir]
 //
 // --di: the direct-lighting pass between the G-buffer and the path tracer (App.cpp:1234-1308), LocalLightSamples = --di-samples (default 8);
 // the path tracer then runs with IsDIEnabled (with Bounces 0 the DI pass is the last render pass and adds to Radiance).
+// --restir (with --di): temporal + spatial reservoir reuse at MyAppData's defaults; the Previous* G-buffer is swapped in before every
+// frame after the first (App.cpp:629-634). Unsharded only.
 //
 // --ranks R: one process per GPU. The parent (which never touches a GPU) starts R children `--rank r --world R --id-file F`; rank 0
 // makes the RCCL unique id and leaves it in F, the others pick it up; every rank renders its 16-row bands (BandSharding) and rank 0
@@ -336,11 +338,12 @@ static std::vector<uint8_t> exchange_unique_id(uint32_t rank, const std::string&
 int main(int argc, char** argv)
 {
     uint32_t W = 1920, H = 1080, spp = 4, bounces = 8, frames = 10, ranks = 0, rank = 0, world = 1;
-    uint32_t diSamples = 8; bool di = false;
+    uint32_t diSamples = 8; bool di = false, restir = false;
     std::string out, idFile, scenePath, dumpPath;
     for (int i = 1; i < argc; i++) {
         std::string k = argv[i];
-        if (k == "--di") { di = true; continue; }                  // the one flag without a value
+        if (k == "--di") { di = true; continue; }                  // the flags without a value
+        if (k == "--restir") { restir = true; continue; }
         if (i + 1 >= argc) break;
         const char* v = argv[++i];
         if (k == "--width") W = atoi(v); else if (k == "--height") H = atoi(v);
@@ -467,9 +470,26 @@ int main(int argc, char** argv)
         DirectLighting directLighting(commandList);
         directLighting.GPUBuffers = { &sd, &cam, dObjects, n };
         directLighting.Textures = tx;
+        if (restir && (!di || sharded)) throw std::invalid_argument("--restir needs --di and one unsharded process");
+        PtDIPreviousTextures& prev = directLighting.PreviousTextures;
+        if (restir) {
+            prev.PreviousGeometricNormal = alloc(px_ * 4); prev.PreviousLinearDepth = alloc(px_ * 4); prev.PreviousBaseColorMetalness = alloc(px_ * 4);
+            prev.PreviousNormalRoughness = alloc(px_ * 8); prev.PreviousIOR = alloc(px_ * 2); prev.PreviousTransmission = alloc(px_);
+            DirectLighting::ReSTIRDI r;
+            r.TemporalResampling.IsEnabled = true; r.SpatialResampling.IsEnabled = true;
+            directLighting.SetResampling(r);
+        }
+        bool firstFrame = true;
         PtCounters counters{};
         double ms = 0;
         auto renderFrame = [&](uint32_t frameIndex) {
+            if (restir && !firstFrame) {                            // App.cpp:629-634: this frame's G-buffer goes where last frame's was
+                std::swap(tx.GeometricNormal, prev.PreviousGeometricNormal); std::swap(tx.LinearDepth, prev.PreviousLinearDepth);
+                std::swap(tx.BaseColorMetalness, prev.PreviousBaseColorMetalness); std::swap(tx.NormalRoughness, prev.PreviousNormalRoughness);
+                std::swap(tx.IOR, prev.PreviousIOR); std::swap(tx.Transmission, prev.PreviousTransmission);
+                gbuffer.Textures = tx; raytracing.Textures = tx; directLighting.Textures = tx;
+            }
+            firstFrame = false;
             gbuffer.Render(commandList, tlas, { { W, H }, ~0u & ~(uint32_t)GBufferGeneration::Flags::Albedo });     // App.cpp:1224
             if (di) {                                               // App.cpp:1234-1308: RTXDI between the G-buffer and the path tracer
                 DirectLighting::Settings ds; ds.RenderSize[0] = W; ds.RenderSize[1] = H; ds.FrameIndex = frameIndex;

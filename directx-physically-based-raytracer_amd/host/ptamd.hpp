@@ -187,10 +187,49 @@ struct DirectLighting {
         uint32_t ExtFlags{};
     };
 
+    // MyAppData ReSTIRDI.TemporalResampling / SpatialResampling (Source/MyAppData.h:226-247); the thresholds, history length, radius and
+    // disocclusion boost are the RTXDI SDK's documented defaults. Both passes off by default: the plain pass.
+    enum class ReSTIRDIBiasCorrectionMode : uint32_t { Off = PT_DI_BIAS_CORRECTION_OFF, Basic = PT_DI_BIAS_CORRECTION_BASIC };
+    struct ReSTIRDI {
+        struct TemporalResampling {
+            bool IsEnabled{};
+            ReSTIRDIBiasCorrectionMode BiasCorrectionMode = ReSTIRDIBiasCorrectionMode::Basic;
+            struct BoilingFilter { bool IsEnabled = true; float Strength = 0.2f; } BoilingFilter;
+            uint32_t MaxHistoryLength = 20;
+            float DepthThreshold = 0.1f, NormalThreshold = 0.5f;
+        } TemporalResampling;
+        struct SpatialResampling {
+            bool IsEnabled{};
+            ReSTIRDIBiasCorrectionMode BiasCorrectionMode = ReSTIRDIBiasCorrectionMode::Basic;
+            uint32_t Samples = 1, DisocclusionBoostSamples = 8;
+            float SamplingRadius = 32.0f, DepthThreshold = 0.1f, NormalThreshold = 0.5f;
+        } SpatialResampling;
+    };
+
     struct { const PtSceneData* SceneData; const PtCamera* Camera; const PtObjectData* ObjectData; uint32_t ObjectCount; } GPUBuffers{};
     PtTextures Textures{};                                  // the G-buffer it reads, Diffuse / Specular (or Radiance) it writes
+    PtDIPreviousTextures PreviousTextures{};                // RTXDI::Textures Previous*: last frame's G-buffer (temporal resampling)
 
     explicit DirectLighting(CommandList& commandList) : m_context(commandList.Context) {}
+
+    void SetResampling(const ReSTIRDI& r)
+    {
+        PtDIResamplingSettings s{};
+        s.TemporalResampling = r.TemporalResampling.IsEnabled ? 1u : 0u;
+        s.TemporalBiasCorrection = (uint32_t)r.TemporalResampling.BiasCorrectionMode;
+        s.MaxHistoryLength = r.TemporalResampling.MaxHistoryLength;
+        s.BoilingFilter = r.TemporalResampling.BoilingFilter.IsEnabled ? 1u : 0u;
+        s.BoilingFilterStrength = r.TemporalResampling.BoilingFilter.Strength;
+        s.TemporalDepthThreshold = r.TemporalResampling.DepthThreshold; s.TemporalNormalThreshold = r.TemporalResampling.NormalThreshold;
+        s.SpatialSamples = r.SpatialResampling.IsEnabled ? r.SpatialResampling.Samples : 0u;
+        s.SpatialBiasCorrection = (uint32_t)r.SpatialResampling.BiasCorrectionMode;
+        s.DisocclusionBoostSamples = r.SpatialResampling.DisocclusionBoostSamples;
+        s.SpatialSamplingRadius = r.SpatialResampling.SamplingRadius;
+        s.SpatialDepthThreshold = r.SpatialResampling.DepthThreshold; s.SpatialNormalThreshold = r.SpatialResampling.NormalThreshold;
+        ThrowIfFailed(m_context, pt_di_set_resampling(m_context, &s));
+    }
+
+    void ResetHistory() { ThrowIfFailed(m_context, pt_di_reset_history(m_context)); }     // App::ResetHistory
 
     void SetConstants(const Settings& settings)
     {
@@ -208,7 +247,7 @@ struct DirectLighting {
         ThrowIfFailed(c, pt_set_scene_data(c, GPUBuffers.SceneData));
         ThrowIfFailed(c, pt_set_camera(c, GPUBuffers.Camera));
         ThrowIfFailed(c, pt_set_object_data(c, GPUBuffers.ObjectData, GPUBuffers.ObjectCount));
-        ThrowIfFailed(c, pt_di_render(c, &Textures));
+        ThrowIfFailed(c, pt_di_render_with_history(c, &Textures, PreviousTextures.PreviousLinearDepth ? &PreviousTextures : nullptr));
     }
 
     static void TraceVisibility(CommandList& commandList, const PtRayDesc* deviceRays, uint32_t count, float* deviceVisibility)

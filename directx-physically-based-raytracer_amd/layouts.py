@@ -97,6 +97,47 @@ def di_settings(width, height, frame_index=0, samples=8, denoiser=0, last_pass=F
     s["ExtFlags"] = ext_flags
     return s
 
+DI_BIAS_CORRECTION_OFF, DI_BIAS_CORRECTION_BASIC = 0, 1
+
+DI_RESAMPLING_SETTINGS = np.dtype({  # PtDIResamplingSettings: ReSTIRDI.TemporalResampling / SpatialResampling (Source/MyAppData.h:226-247)
+    "names": ["TemporalResampling", "TemporalBiasCorrection", "MaxHistoryLength", "BoilingFilter", "BoilingFilterStrength",
+              "TemporalDepthThreshold", "TemporalNormalThreshold", "SpatialSamples", "SpatialBiasCorrection", "DisocclusionBoostSamples",
+              "SpatialSamplingRadius", "SpatialDepthThreshold", "SpatialNormalThreshold"],
+    "formats": ["<u4", "<u4", "<u4", "<u4", "<f4", "<f4", "<f4", "<u4", "<u4", "<u4", "<f4", "<f4", "<f4"],
+    "offsets": [0, 4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 44, 48], "itemsize": 64})
+
+DI_RESERVOIR = np.dtype({  # PtDIReservoir: one per pixel, row-major
+    "names": ["LightIndex", "U", "V", "W", "M", "TargetPdf", "Age"],
+    "formats": ["<u4", "<f4", "<f4", "<f4", "<u4", "<f4", "<u4"],
+    "offsets": [0, 4, 8, 12, 16, 20, 24], "itemsize": 32})
+
+DI_PREVIOUS_TEXTURES = ["PreviousGeometricNormal", "PreviousLinearDepth", "PreviousBaseColorMetalness", "PreviousNormalRoughness",
+                        "PreviousIOR", "PreviousTransmission"]   # PtDIPreviousTextures member order
+
+
+def di_resampling_settings(temporal=True, spatial_samples=1, temporal_bias=DI_BIAS_CORRECTION_BASIC, spatial_bias=DI_BIAS_CORRECTION_BASIC,
+                           boiling_filter=True, boiling_strength=0.2, max_history=20, temporal_depth=0.1, temporal_normal=0.5,
+                           boost_samples=8, radius=32.0, spatial_depth=0.1, spatial_normal=0.5):
+    """PtDIResamplingSettings. From the reference (MyAppData.h): Basic bias correction for both passes, the boiling filter on at 0.2,
+    1 spatial sample. From the RTXDI SDK's documented defaults (not in the reference tree): max history 20, depth / normal thresholds
+    0.1 / 0.5, spatial radius 32 px, 8 disocclusion-boost samples."""
+    s = np.zeros((), DI_RESAMPLING_SETTINGS)
+    s["TemporalResampling"] = 1 if temporal else 0
+    s["TemporalBiasCorrection"] = temporal_bias
+    s["MaxHistoryLength"] = max_history
+    s["BoilingFilter"] = 1 if boiling_filter else 0
+    s["BoilingFilterStrength"] = boiling_strength
+    s["TemporalDepthThreshold"] = temporal_depth
+    s["TemporalNormalThreshold"] = temporal_normal
+    s["SpatialSamples"] = spatial_samples
+    s["SpatialBiasCorrection"] = spatial_bias
+    s["DisocclusionBoostSamples"] = boost_samples
+    s["SpatialSamplingRadius"] = radius
+    s["SpatialDepthThreshold"] = spatial_depth
+    s["SpatialNormalThreshold"] = spatial_normal
+    return s
+
+
 GBUFFER_CONSTANTS = np.dtype({
     "names": ["RenderSize", "Flags"], "formats": [("<u4", 2), "<u4"], "offsets": [0, 8], "itemsize": 12})
 

@@ -26,6 +26,7 @@ EXPORTS = [
     "pt_comm_get_unique_id", "pt_comm_init", "pt_comm_adopt", "pt_comm_destroy", "pt_gather_bands", "pt_gather_plan",
     "pt_raytrace_set_constants", "pt_raytrace_render", "pt_trace_visibility", "pt_bsdf_evaluate", "pt_bsdf_sample", "pt_reset_counters", "pt_get_counters",
     "pt_di_set_constants", "pt_di_render", "pt_di_light_count", "pt_di_download_lights",
+    "pt_di_set_resampling", "pt_di_render_with_history", "pt_di_reset_history", "pt_di_download_reservoirs",
     "pt_set_debug_flags", "pt_debug_read_mismatch", "pt_debug_download_blob", "pt_debug_trace_ray", "pt_enable_kernel_timing", "pt_get_kernel_timing", "pt_get_round_timing",
 ]
 
@@ -54,6 +55,10 @@ TEXTURE_NAMES = L.GBUFFER_ORDER + ["RadianceF32", "Diffuse", "Specular", "Specul
 
 class Textures(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in TEXTURE_NAMES]
+
+
+class PreviousTextures(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in L.DI_PREVIOUS_TEXTURES]
 
 
 class Sharding(C.Structure):
@@ -159,6 +164,10 @@ def load_library():
         lib.pt_di_render.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_di_light_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         lib.pt_di_download_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.pt_di_set_resampling.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_di_render_with_history.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pt_di_reset_history.argtypes = [C.c_void_p]
+        lib.pt_di_download_reservoirs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.pt_set_debug_flags.argtypes = [C.c_void_p, C.c_uint32]
         lib.pt_debug_read_mismatch.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_debug_download_blob.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -485,6 +494,10 @@ def alloc_textures(width, local_rows_, device, with_f32=False, with_denoiser_out
     return out
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 def _pack_textures(tex):
     t = Textures()
     for n in TEXTURE_NAMES:
@@ -497,8 +510,9 @@ def textures_to_numpy(tex):
     out = {}
     for name, t in tex.items():
         a = t.detach().cpu().numpy()
-        if name in L.GBUFFER_FORMATS:
-            a = a.view(np.dtype(L.GBUFFER_FORMATS[name][0]))
+        base = name[len("Previous"):] if name in L.DI_PREVIOUS_TEXTURES else name
+        if base in L.GBUFFER_FORMATS:
+            a = a.view(np.dtype(L.GBUFFER_FORMATS[base][0]))
         elif name in L.DENOISER_FORMATS:
             a = a.view(np.dtype(L.DENOISER_FORMATS[name][0]))
         out[name] = a
@@ -572,7 +586,31 @@ class DirectLighting:
             sd = np.array(self.GPUBuffers["SceneData"])
             ctx.check(lib.pt_set_scene_data(ctx.handle, C.c_void_p(sd.ctypes.data)))
         t = _pack_textures(self.Textures)
-        ctx.check(lib.pt_di_render(ctx.handle, C.addressof(t)))
+        if any(self.Textures.get(n) is not None for n in L.DI_PREVIOUS_TEXTURES):
+            p = PreviousTextures(*[_ptr(self.Textures.get(n)) for n in L.DI_PREVIOUS_TEXTURES])
+            ctx.check(lib.pt_di_render_with_history(ctx.handle, C.addressof(t), C.addressof(p)))
+        else:
+            ctx.check(lib.pt_di_render(ctx.handle, C.addressof(t)))
+
+    def SetResampling(self, settings):
+        """PtDIResamplingSettings (layouts.di_resampling_settings), or None: the plain pass. A changed value resets the history."""
+        if settings is None:
+            self.ctx.check(self.ctx.lib.pt_di_set_resampling(self.ctx.handle, None))
+            return
+        self._resampling = np.array(settings).reshape(())
+        self.ctx.check(self.ctx.lib.pt_di_set_resampling(self.ctx.handle, C.c_void_p(self._resampling.ctypes.data)))
+
+    def ResetHistory(self):
+        self.ctx.check(self.ctx.lib.pt_di_reset_history(self.ctx.handle))
+
+    def download_reservoirs(self):
+        """The final reservoirs of the last Render (numpy layouts.DI_RESERVOIR, row-major pixels; empty without reuse)."""
+        n = C.c_uint32(0)
+        self.ctx.check(self.ctx.lib.pt_di_download_reservoirs(self.ctx.handle, None, 0, C.byref(n)))
+        out = np.zeros(n.value, L.DI_RESERVOIR)
+        if n.value:
+            self.ctx.check(self.ctx.lib.pt_di_download_reservoirs(self.ctx.handle, C.c_void_p(out.ctypes.data), n.value, C.byref(n)))
+        return out
 
     def light_count(self):
         n = C.c_uint32(0)
@@ -592,11 +630,15 @@ class DirectLighting:
 class Renderer:
     """App::RenderScene for this path (Source/App.cpp:1157-1329): G-buffer pass, then the path tracer."""
 
-    def __init__(self, ctx, scene_gpu, width, height, with_f32=False, with_denoiser_outputs=False):
+    def __init__(self, ctx, scene_gpu, width, height, with_f32=False, with_denoiser_outputs=False, di_history=False):
         self.ctx, self.scene, self.width, self.height = ctx, scene_gpu, width, height
         rank, world, band = getattr(ctx, "sharding", (0, 1, 16))
         self.local_rows = local_rows(height, rank, world, band)
         self.textures = alloc_textures(width, self.local_rows, scene_gpu.device, with_f32, with_denoiser_outputs)
+        self.di_history, self._rendered = di_history, False
+        if di_history:                                                    # App.cpp:629-634: the DI pass's Previous* G-buffer
+            for n in L.DI_PREVIOUS_TEXTURES:
+                self.textures[n] = self.textures[n[len("Previous"):]].clone()
         self.gbuffer = GBufferGeneration(ctx)
         self.raytracing = Raytracing(ctx)
         self.direct_lighting = DirectLighting(ctx)
@@ -609,10 +651,17 @@ class Renderer:
         self.constants["RenderSize"] = (width, height)
         self.constants["Flags"] = L.GBufferFlags.DefaultNoDenoiser        # App.cpp:1224 with Denoiser::None
 
-    def render(self, settings, di_samples=0):
+    def render(self, settings, di_samples=0, di_reuse=None):
         """di_samples > 0: run the DI pass with that many candidates per pixel; set settings["IsDIEnabled"] to have the path tracer
-        consume it (the textures need Diffuse / Specular: with_denoiser_outputs=True)."""
+        consume it (the textures need Diffuse / Specular: with_denoiser_outputs=True). di_reuse: PtDIResamplingSettings
+        (layouts.di_resampling_settings) for reservoir reuse; temporal reuse needs di_history=True. With di_history the current and
+        Previous* G-buffer textures are swapped before each frame after the first, so that after render() the current ones hold this
+        frame's G-buffer and the Previous* ones the last frame's."""
         tlas = self.scene.GetTopLevelAccelerationStructure()
+        if self.di_history and self._rendered:
+            for n in L.DI_PREVIOUS_TEXTURES:
+                c = n[len("Previous"):]
+                self.textures[n], self.textures[c] = self.textures[c], self.textures[n]
         denoiser = int(np.array(settings).reshape(())["Denoiser"])
         self.constants["Flags"] = 0xFFFFFFFF if denoiser != L.DENOISER_NONE else L.GBufferFlags.DefaultNoDenoiser   # App.cpp:1223
         self.gbuffer.Render(tlas, self.constants)
@@ -620,7 +669,9 @@ class Renderer:
             s = np.array(settings).reshape(())
             self.direct_lighting.SetConstants(L.di_settings(self.width, self.height, int(s["FrameIndex"]), di_samples, denoiser,
                                                             last_pass=int(s["Bounces"]) == 0, ext_flags=int(s["ExtFlags"])))
+            self.direct_lighting.SetResampling(di_reuse)
             self.direct_lighting.Render(tlas)
         if int(np.array(settings).reshape(())["Bounces"]) > 0:            # App.cpp:1277
             self.raytracing.SetConstants(settings)
             self.raytracing.Render(tlas)
+        self._rendered = True

@@ -394,6 +394,54 @@ int  pt_di_light_count(PtContext* ctx, uint32_t* out_count);
 int  pt_di_download_lights(PtContext* ctx, PtTriangleLight* host_dst, uint32_t capacity, uint32_t* out_count);
 
 /* ------------------------------------------------------------------------------------------
+ * spatiotemporal reservoir reuse of the DI pass (RTXDI's DITemporalResampling / DISpatialResampling, Source/RTXDI.ixx:237-240;
+ * defaults of Source/MyAppData.h:226-247). DESIGN.md section 1 is the arithmetic spec; parity with the RTXDI SDK is unpinned.
+ * Off by default: pt_di_render is pt_di_render_with_history(ctx, tx, NULL) and, with both passes off, runs the plain pass.
+ * Unsharded contexts only. Each context keeps two reservoir buffers of RenderSize pixels x 32 B (ping-ponged per render).
+ * ------------------------------------------------------------------------------------------ */
+enum { PT_DI_BIAS_CORRECTION_OFF = 0, PT_DI_BIAS_CORRECTION_BASIC = 1 };   /* 2 Pairwise, 3 Raytraced: rejected */
+typedef struct PtDIResamplingSettings {
+    uint32_t TemporalResampling;          /* 0 / 1 */
+    uint32_t TemporalBiasCorrection;      /* OFF | BASIC (reference default BASIC) */
+    uint32_t MaxHistoryLength;            /* 1..64, default 20 */
+    uint32_t BoilingFilter;               /* 0 / 1, default 1 */
+    float    BoilingFilterStrength;       /* [0, 1], default 0.2 */
+    float    TemporalDepthThreshold;      /* default 0.1 */
+    float    TemporalNormalThreshold;     /* default 0.5 */
+    uint32_t SpatialSamples;              /* 0 = no spatial pass, 1..32 (reference default 1) */
+    uint32_t SpatialBiasCorrection;       /* OFF | BASIC */
+    uint32_t DisocclusionBoostSamples;    /* 0..32, default 8 */
+    float    SpatialSamplingRadius;       /* pixels, (0, 64], default 32 */
+    float    SpatialDepthThreshold;       /* default 0.1 */
+    float    SpatialNormalThreshold;      /* default 0.5 */
+    uint32_t _pad[3];
+} PtDIResamplingSettings;                 /* 64 B */
+
+typedef struct PtDIReservoir {            /* one per local pixel, row-major */
+    uint32_t LightIndex;                  /* into the light list; 0xFFFFFFFF = empty */
+    float    U, V;                        /* the two uniforms of Math::SampleTriangle (r1, r2 of the DI spec), unquantised */
+    float    W;                           /* unbiased contribution weight */
+    uint32_t M;                           /* confidence */
+    float    TargetPdf;                   /* p-hat of the sample at this pixel's surface */
+    uint32_t Age;                         /* frames since drawn, saturating; informational */
+    uint32_t _pad;
+} PtDIReservoir;                          /* 32 B */
+
+typedef struct PtDIPreviousTextures {     /* RTXDI::Textures Previous* members, Source/RTXDI.ixx:37-50: last frame's G-buffer, same formats */
+    void* PreviousGeometricNormal; void* PreviousLinearDepth; void* PreviousBaseColorMetalness;
+    void* PreviousNormalRoughness; void* PreviousIOR; void* PreviousTransmission;
+} PtDIPreviousTextures;
+
+/* NULL or both passes off: the plain pass. A changed value resets the history. */
+int  pt_di_set_resampling(PtContext* ctx, const PtDIResamplingSettings* settings);
+/* temporal reuse reads previous (not NULL) and Textures.MotionVector; the history is reset on the first render, a RenderSize change,
+ * a rebuilt light list and a settings change */
+int  pt_di_render_with_history(PtContext* ctx, const PtTextures* textures, const PtDIPreviousTextures* previous);
+int  pt_di_reset_history(PtContext* ctx);                                   /* App::ResetHistory */
+/* the final reservoirs of the last render (next frame's history), RenderSize pixels row-major; synchronises */
+int  pt_di_download_reservoirs(PtContext* ctx, PtDIReservoir* host_dst, uint32_t capacity, uint32_t* out_count);
+
+/* ------------------------------------------------------------------------------------------
  * building blocks the reference's direct-lighting bridge calls on the same data
  * ------------------------------------------------------------------------------------------ */
 typedef struct PtRayDesc { float Origin[3]; float TMin; float Direction[3]; float TMax; } PtRayDesc;   /* HLSL RayDesc, 32 B */

@@ -1,0 +1,256 @@
+"""Reservoir reuse pinned per pixel against the float64 restatement (tests/restirref.py), on a moving camera; unbiasedness of the Basic
+normalisation against a closed form and the no-reuse pass; a history reset by a hidden emitter instance; pt_demo --restir."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import __graft_entry__ as ge
+import bsdfref
+import restirref as R
+
+NEAR = 1e-5
+
+
+def _pin_scene(S, aspect):
+    """a GGX-ish floor, an opaque bar over it (parallax disocclusion as the camera moves), five emissive triangles on two instances"""
+    floor = S.quad_mesh((-2, 0, -2), (-2, 0, 2), (2, 0, 2), (2, 0, -2), (0, 1, 0), S.material((0.6, 0.5, 0.4), roughness=0.4, metallic=0.3))
+    bar = S.quad_mesh((-1.5, 0.7, -0.1), (1.5, 0.7, -0.1), (1.5, 0.7, 0.15), (-1.5, 0.7, 0.15), (0, -1, 0), S.material((0.9, 0.9, 0.9), roughness=0.8))
+
+    def tris(pts, strength, color):
+        pos = np.array(pts, np.float32)
+        return S.Mesh(S.make_vertices(pos, np.tile(np.float32([0, -1, 0]), (len(pos), 1))), S.make_indices(list(range(len(pos)))), True,
+                      S.material((0.5, 0.5, 0.5), emissive=color, strength=strength))
+    a = tris([(-0.6, 1.5, -0.3), (0.7, 1.6, 0.1), (0.0, 1.4, 0.8), (-1.5, 1.3, 0.5), (-1.2, 1.3, 0.6), (-1.3, 1.35, 0.9),
+              (1.0, 1.2, -0.8), (1.3, 1.2, -0.7), (1.1, 1.25, -0.4)], 6.0, (1.0, 0.8, 0.6))
+    b = tris([(0.2, 1.1, 1.2), (0.5, 1.1, 1.3), (0.3, 1.15, 1.6), (-0.9, 1.0, -1.2), (-0.6, 1.0, -1.1), (-0.8, 1.05, -0.8)], 20.0, (0.6, 0.8, 1.0))
+    nodes = [S.MeshNode([floor]), S.MeshNode([a]), S.MeshNode([bar]), S.MeshNode([b])]
+    objects = [S.RenderObject(i, S.trs()) for i in range(4)]
+    cam = S.make_camera((0, 2.2, -2.6), forward=(0, -0.6, 1), hfov_deg=70.0, aspect=aspect)
+    return S.Scene(nodes, objects, cam, S.make_scene_data((0, 0, 0, 1)), name="di_reuse_pin").finalize()
+
+
+def _move(S, cam, prev, dx):
+    """the camera shifted by dx along x, with Previous* from the last frame's camera (static geometry: IsStatic)"""
+    c = S.make_camera(cam["Position"].astype(np.float64) + (dx, 0, 0), forward=cam["ForwardDirection"].astype(np.float64), hfov_deg=70.0,
+                      aspect=float(np.linalg.norm(cam["RightDirection"]) / np.linalg.norm(cam["UpDirection"])))
+    c["PreviousPosition"] = prev["Position"]
+    for k in ("WorldToProjection", "ProjectionToView", "ViewToWorld"):
+        c["Previous" + k] = prev[k]
+    c["PreviousWorldToView"], c["PreviousViewToProjection"] = prev["PreviousWorldToView"], prev["PreviousViewToProjection"]
+    return c
+
+
+def _set_camera(r, cam):
+    for op in (r.gbuffer, r.raytracing, r.direct_lighting):
+        op.GPUBuffers["Camera"] = cam
+
+
+def _as_ref(res, H, W):
+    out = {k: res[k].reshape(H, W).astype(np.float64 if res.dtype[k].kind == "f" else np.int64) for k in res.dtype.names}
+    out["LightIndex"] = np.where(res["LightIndex"].reshape(H, W) == 0xFFFFFFFF, -1, out["LightIndex"])
+    return out
+
+
+CONFIGS = [  # (name, temporal, spatial samples, basic, boiling)
+    ("temporal-basic-boiling", True, 0, True, True),
+    ("temporal-off", True, 0, False, False),
+    ("spatial-basic", False, 1, True, False),
+    ("spatial-off", False, 2, False, False),
+    ("both-basic-boiling", True, 1, True, True),
+    ("both-off", True, 1, False, False),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,temporal,spatial,basic,boiling", CONFIGS, ids=[c[0] for c in CONFIGS])
+def test_gpu_reuse_pinned_per_pixel(gpu, ptamd, pkg, name, temporal, spatial, basic, boiling):
+    """3 frames of 48 x 32 with the camera moving ~2 px per frame. Each frame's final reservoirs match restirref, fed the downloaded
+    G-buffers, motion vectors, light records, last frame's final reservoirs and the frame's initial reservoirs: LightIndex, M, Age, U, V
+    exactly, W to 2e-5 relative (float32 against float64 p-hat; measured up to 1.3e-5). Pixels within 1e-5 of a decision (a coin, a
+    threshold, the boiling cut, the rounding of p + mv, a cosine where the BSDF or p-hat turns ill-conditioned) are left out and counted,
+    and so is every pixel that reused such a pixel's reservoir."""
+    S, L = pkg.scenes, pkg.layouts
+    W, H, n = 48, 32, 8
+    bsdf = bsdfref.Reference()
+    table = R.offset_table()
+    bias = L.DI_BIAS_CORRECTION_BASIC if basic else L.DI_BIAS_CORRECTION_OFF
+    reuse = L.di_resampling_settings(temporal=temporal, spatial_samples=spatial, temporal_bias=bias, spatial_bias=bias, boiling_filter=boiling)
+    # the initial reservoirs of each frame come from a second context: temporal-only, Off, no boiling, history reset before every frame
+    init = L.di_resampling_settings(temporal=True, spatial_samples=0, temporal_bias=L.DI_BIAS_CORRECTION_OFF, boiling_filter=False)
+    gpu.set_sharding(0, 1, 16)
+    scene = _pin_scene(S, W / H)
+    g = ptamd.Scene(gpu, scene)
+    ctx2 = ptamd.DeviceContext(0)
+    g2 = ptamd.Scene(ctx2, scene)
+    r = ptamd.Renderer(gpu, g, W, H, with_denoiser_outputs=True, di_history=True)
+    r2 = ptamd.Renderer(ctx2, g2, W, H, with_denoiser_outputs=True, di_history=True)
+    cam = scene.camera.copy()
+    history, excluded, compared, disoccluded = None, 0, 0, 0
+    for f in range(3):
+        if f:
+            cam = _move(S, cam, cam, 0.17)
+        _set_camera(r, cam); _set_camera(r2, cam)
+        gs = S.graphics_settings(W, H, spp=1, bounces=1, frame_index=40 + f)
+        r.render(gs, di_samples=n, di_reuse=reuse); gpu.sync()
+        r2.direct_lighting.ResetHistory()
+        r2.render(gs, di_samples=n, di_reuse=init); ctx2.sync()
+        out = ptamd.textures_to_numpy(r.textures)
+        got = _as_ref(r.direct_lighting.download_reservoirs(), H, W)
+        fresh = r2.direct_lighting.download_reservoirs().reshape(H, W)
+        lights = r.direct_lighting.download_lights()
+        cur = R.Surfaces(out, cam)
+        mv = out["MotionVector"].view(np.float16).astype(np.float32)
+        if temporal:
+            prev = R.Surfaces(out, cam, previous=True) if f else None
+            exp, margin = R.temporal_pass(cur, prev, mv, fresh, history if f else None, lights, None, 40 + f, bsdf, 20, basic, boiling, 0.2)
+            if f:
+                disoccluded += int((cur.valid & (exp["M"] == n)).sum())
+        else:
+            exp = _as_ref(fresh.reshape(-1), H, W)
+            exp["Age"][:] = 0
+            margin = np.full((H, W), np.inf)
+        if spatial:
+            exp, margin = R.spatial_pass(cur, exp, margin, lights, table, 40 + f, bsdf, spatial, 8, 20, 32.0, basic)
+        sel = cur.valid & (margin >= NEAR)
+        excluded += int((cur.valid & (margin < NEAR)).sum()); compared += int(sel.sum())
+        for k in ("LightIndex", "M", "Age"):
+            bad = sel & (got[k] != exp[k])
+            assert not bad.any(), (name, f, k, np.argwhere(bad)[:5].tolist(), got[k][bad][:5], exp[k][bad][:5], margin[bad][:5],
+                                   got["LightIndex"][bad][:5], exp["LightIndex"][bad][:5], got["W"][bad][:5], exp["W"][bad][:5])
+        for k in ("U", "V"):
+            assert np.array_equal(got[k][sel].astype(np.float32), exp[k][sel].astype(np.float32)), (name, f, k)
+        rel = np.abs(got["W"][sel] - exp["W"][sel]) / np.maximum(np.abs(exp["W"][sel]), 1e-30)
+        rel = np.where((got["W"][sel] == 0) & (exp["W"][sel] == 0), 0.0, rel)
+        print(f"{name} frame {f}: W rel err max {rel.max():.2e} p99 {np.quantile(rel, 0.99):.2e}")
+        worst = np.argwhere(sel)[np.argmax(rel)]
+        assert rel.max() <= 2e-5, (name, f, rel.max(), worst.tolist(), margin[tuple(worst)], got["W"][tuple(worst)], exp["W"][tuple(worst)],
+                                   got["M"][tuple(worst)])
+        history = r.direct_lighting.download_reservoirs().reshape(H, W)
+    print(f"{name}: {compared} pixels compared, {excluded} within {NEAR} of a decision ({excluded / max(1, compared + excluded):.3%}), "
+          f"{disoccluded} without history after motion")
+    assert compared > 0.3 * 3 * W * H
+    # the exclusion spreads: a spatial pixel that reused any uncertain neighbour (8 disocclusion-boost samples each) is left out too,
+    # and pixels on the emitters themselves see samples of their own triangle edge-on. Measured: 0.6 % (temporal) to 22 % (spatial).
+    assert excluded < 0.25 * (compared + excluded)
+    if temporal:
+        assert disoccluded > 0                                           # the motion disoccluded pixels
+    del r, r2
+    g2.close(); ctx2.close(); g.close()
+
+
+def _floor_mask(gb):
+    pos = gb["Position"][..., :3].astype(np.float64)
+    return np.isfinite(pos).all(-1) & (np.abs(pos[..., 1] + 1) < 1e-4) & (pos[..., 0] > -0.55) & (pos[..., 0] < -0.15) & \
+        (pos[..., 2] > -0.6) & (pos[..., 2] < -0.45), pos
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["diffuse", "ggx"])
+def test_gpu_basic_reuse_unbiased(gpu, ptamd, pkg, variant):
+    """Temporal + spatial reuse with Basic bias correction is unbiased on the unoccluded floor of the Cornell box: frame 4 of 48
+    independent sequences (history reset between them) against the polygon form-factor closed form (Lambertian) or the no-reuse pass's
+    256-frame mean (GGX), within 4 standard errors of the measured spread."""
+    S, L = pkg.scenes, pkg.layouts
+    W, H = 64, 48
+    ext = L.EXT_LAMBERTIAN_ONLY if variant == "diffuse" else 0
+    scene = S.cornell_box(aspect=W / H, variant=variant)
+    gpu.set_sharding(0, 1, 16)
+    g = ptamd.Scene(gpu, scene)
+    r = ptamd.Renderer(gpu, g, W, H, with_denoiser_outputs=True, di_history=True)
+    K, F = 48, 4
+    vals = []
+    for k in range(K):
+        r.direct_lighting.ResetHistory()
+        for f in range(F):
+            r.render(S.graphics_settings(W, H, spp=1, bounces=1, frame_index=2000 + k * F + f, ext_flags=ext), di_samples=4,
+                     di_reuse=L.di_resampling_settings())
+        gpu.sync()
+        o = ptamd.textures_to_numpy(r.textures)
+        vals.append(o["Diffuse"][..., :3].view(np.float16).astype(np.float64) + o["Specular"][..., :3].view(np.float16).astype(np.float64))
+    vals = np.stack(vals)
+    floor, pos = _floor_mask(o)
+    assert floor.sum() >= 3
+    if variant == "diffuse":
+        M = scene.instance_data["ObjectToWorld"][5].reshape(3, 4).astype(np.float64)
+        light = scene.nodes[scene.objects[5].node].meshes[0].vertices["Position"].astype(np.float64) @ M[:, :3].T + M[:, 3]
+        albedo = o["BaseColorMetalness"][..., :3].astype(np.float64) / 255.0
+        expect = np.zeros_like(vals[0]); ref_se = np.zeros_like(vals[0])
+        for y, x in zip(*np.nonzero(floor)):
+            ff = 0.0
+            for e in range(4):
+                a, b = light[e] - pos[y, x], light[(e + 1) % 4] - pos[y, x]
+                a /= np.linalg.norm(a); b /= np.linalg.norm(b)
+                c = np.cross(a, b)
+                ff += np.arccos(np.clip(a @ b, -1, 1)) * (c / np.linalg.norm(c)) @ np.array([0, 1.0, 0])
+            expect[y, x] = albedo[y, x] / np.pi * 15.0 * abs(ff) / 2
+    else:
+        plain = ptamd.Renderer(gpu, g, W, H, with_denoiser_outputs=True)
+        ref = []
+        for f in range(256):
+            plain.render(S.graphics_settings(W, H, spp=1, bounces=1, frame_index=9000 + f), di_samples=4); gpu.sync()
+            p = ptamd.textures_to_numpy(plain.textures)
+            ref.append(p["Diffuse"][..., :3].view(np.float16).astype(np.float64) + p["Specular"][..., :3].view(np.float16).astype(np.float64))
+        ref = np.stack(ref)
+        expect, ref_se = ref.mean(0), ref.std(0, ddof=1) / np.sqrt(len(ref))
+    mean, se = vals.mean(0), vals.std(0, ddof=1) / np.sqrt(K)
+    tol = 4 * np.sqrt(se ** 2 + ref_se ** 2) + 2e-3 * expect                  # + fp16 storage
+    z = np.abs(mean - expect)[floor] / np.maximum(tol[floor], 1e-12)
+    print(f"{variant}: {floor.sum()} floor pixels, max |mean - expected| / (4 sigma) = {z.max():.2f}")
+    assert (z <= 1).all(), z.max()
+    g.close()
+
+
+@pytest.mark.gpu
+def test_gpu_hidden_emitter_resets_history(gpu, ptamd, pkg):
+    """hiding an emitter instance rebuilds the light list (the top level's instance hash): the next temporal frame has no history"""
+    S, L = pkg.scenes, pkg.layouts
+    W, H, n = 48, 32, 8
+    scene = _pin_scene(S, W / H)
+    gpu.set_sharding(0, 1, 16)
+    g = ptamd.Scene(gpu, scene)
+    r = ptamd.Renderer(gpu, g, W, H, with_denoiser_outputs=True, di_history=True)
+    reuse = L.di_resampling_settings(temporal=True, spatial_samples=0, boiling_filter=False)
+    for f in range(2):
+        r.render(S.graphics_settings(W, H, spp=1, bounces=1, frame_index=f), di_samples=n, di_reuse=reuse)
+    gpu.sync()
+    res = r.direct_lighting.download_reservoirs()
+    assert (res["M"] > n).any() and r.direct_lighting.light_count() == 5
+    scene.instance_masks[3] = 0                                            # the second emitter instance
+    g._descs = None
+    g._build_top_level()
+    r.render(S.graphics_settings(W, H, spp=1, bounces=1, frame_index=2), di_samples=n, di_reuse=reuse); gpu.sync()
+    assert r.direct_lighting.light_count() == 3
+    out = ptamd.textures_to_numpy(r.textures)
+    res = r.direct_lighting.download_reservoirs()
+    valid = R.Surfaces(out, scene.camera).valid.reshape(-1)
+    assert valid.sum() > 0.5 * W * H
+    assert (res["M"][valid] == n).all() and (res["Age"] == 0).all()
+    assert (res["LightIndex"][res["LightIndex"] != 0xFFFFFFFF] < 3).all()
+    g.close()
+
+
+@pytest.mark.gpu
+def test_cpp_host_restir_matches_python(tmp_path, gpu, ptamd, pkg):
+    """pt_demo --di --restir --frames 4: the C++ host's DirectLighting with reuse and the Previous* swap, bit-identical to Python"""
+    demo = os.path.join(ge.PKG_DIR, "pt_demo")
+    S, L = pkg.scenes, pkg.layouts
+    W, H, spp, bounces, frames = 96, 64, 1, 2, 4
+    out = str(tmp_path / "radiance.bin")
+    subprocess.check_call([demo, "--di", "--restir", "--di-samples", "8", "--width", str(W), "--height", str(H), "--spp", str(spp),
+                           "--bounces", str(bounces), "--frames", str(frames), "--out", out], timeout=300)
+    got = np.fromfile(out, np.float32).reshape(H, W, 4)
+    gpu.set_sharding(0, 1, 16)
+    ctx = ptamd.DeviceContext(0)
+    g = ptamd.Scene(ctx, S.cornell_box(aspect=W / H, variant="ggx"))
+    r = ptamd.Renderer(ctx, g, W, H, with_f32=True, with_denoiser_outputs=True, di_history=True)
+    for fi in [12345] + list(range(frames - 1, -1, -1)):                    # pt_demo's warm-up frame, then N-1 .. 0
+        gs = S.graphics_settings(W, H, spp=spp, bounces=bounces, frame_index=fi)
+        gs["IsDIEnabled"] = 1
+        r.render(gs, di_samples=8, di_reuse=L.di_resampling_settings())
+    ctx.sync()
+    ref = ptamd.textures_to_numpy(r.textures)["RadianceF32"]
+    assert (r.direct_lighting.download_reservoirs()["M"] > 8).any()        # the history was used
+    g.close(); ctx.close()
+    assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))

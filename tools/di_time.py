@@ -1,11 +1,12 @@
 """Developer helper: time the direct-lighting pass (HIP events around N back-to-back pt_di_render calls) and one DI-on frame (G-buffer + DI +
-path tracer with IsDIEnabled) against the DI-off frame, per workload. Each workload runs in a child process of its own.
-usage: tools/di_time.py [--workloads c2,c3,c5] [--samples 8] [--n 20]"""
+path tracer with IsDIEnabled) against the DI-off frame, per workload. Each workload runs in a child process of its own. --reuse also times
+the pass with temporal + spatial reservoir reuse at the reference's defaults (layouts.di_resampling_settings), history carried over.
+usage: tools/di_time.py [--workloads c2,c3,c5] [--samples 8] [--n 20] [--reuse]"""
 import argparse, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def child(w, samples, n):
+def child(w, samples, n, reuse):
     sys.path.insert(0, ROOT)
     import torch
     import __graft_entry__ as ge
@@ -17,7 +18,7 @@ def child(w, samples, n):
     ctx = P.DeviceContext(0)
     ctx.set_frames_in_flight(1)
     g = P.Scene(ctx, scene)
-    r = P.Renderer(ctx, g, W, H, with_denoiser_outputs=True)
+    r = P.Renderer(ctx, g, W, H, with_denoiser_outputs=True, di_history=reuse)
     tlas = g.GetTopLevelAccelerationStructure()
     gs = S.graphics_settings(W, H, spp=spp, bounces=bounces, ext_flags=ext)
     ev = lambda: torch.cuda.Event(enable_timing=True)
@@ -42,19 +43,25 @@ def child(w, samples, n):
     gs_on = gs.copy(); gs_on["IsDIEnabled"] = 1
     r.render(gs_on, di_samples=samples); ctx.sync()
     on_ms = timed(lambda i: r.render(gs_on, di_samples=samples), max(3, n // 4))
-    print(json.dumps({"workload": w, "size": [W, H], "lights": lights, "samples": samples, "di_ms": di_ms, "frame_di_off_ms": off_ms, "frame_di_on_ms": on_ms}))
+    out = {"workload": w, "size": [W, H], "lights": lights, "samples": samples, "di_ms": di_ms, "frame_di_off_ms": off_ms, "frame_di_on_ms": on_ms}
+    if reuse:
+        r.render(gs, di_samples=samples, di_reuse=L.di_resampling_settings()); ctx.sync()     # Previous* G-buffer, first history
+        r.direct_lighting.Render(tlas); ctx.sync()
+        out["di_reuse_ms"] = timed(lambda i: r.direct_lighting.Render(tlas), n)
+        r.direct_lighting.SetResampling(None)
+    print(json.dumps(out))
     ctx.close()
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", default=None); ap.add_argument("--workloads", default="c2,c3,c5")
-    ap.add_argument("--samples", type=int, default=8); ap.add_argument("--n", type=int, default=20)
+    ap.add_argument("--samples", type=int, default=8); ap.add_argument("--n", type=int, default=20); ap.add_argument("--reuse", action="store_true")
     a = ap.parse_args()
     if a.child:
-        child(a.child, a.samples, a.n); sys.exit(0)
+        child(a.child, a.samples, a.n, a.reuse); sys.exit(0)
     for w in a.workloads.split(","):
-        p = subprocess.run([sys.executable, __file__, "--child", w, "--samples", str(a.samples), "--n", str(a.n)], stdout=subprocess.PIPE,
+        p = subprocess.run([sys.executable, __file__, "--child", w, "--samples", str(a.samples), "--n", str(a.n)] + (["--reuse"] if a.reuse else []), stdout=subprocess.PIPE,
                            stderr=subprocess.PIPE, text=True, timeout=600)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]
         print(line[0] if line else "%s FAILED (exit %d) %s" % (w, p.returncode, p.stderr[-400:]), flush=True)
