@@ -41,8 +41,8 @@ int pt_create(int device_ordinal, PtContext** out_ctx)
     PtContext* p = new (std::nothrow) PtContext();
     if (!p) return fail(nullptr, PT_ERROR_OUT_OF_MEMORY, "host allocation failed");
     p->c.device = device_ordinal;
-    if ((e = hipMalloc((void**)&p->c.counters, sizeof(DeviceCounters))) != hipSuccess) { delete p; return fail_hip(nullptr, e, "hipMalloc(counters)"); }
-    hipMemset(p->c.counters, 0, sizeof(DeviceCounters));
+    if ((e = p->c.counters.reserve(1)) != hipSuccess) { delete p; return fail_hip(nullptr, e, "hipMalloc(counters)"); }
+    hipMemset(p->c.counters.data(), 0, sizeof(DeviceCounters));
     *out_ctx = p;
     return PT_OK;
 }
@@ -51,40 +51,34 @@ static void detach_from_owner(Context& c)
 {
     Context* o = c.sceneOwner;
     if (!o) return;
-    o->borrowers--;
     for (size_t i = 0; i < o->viewers.size(); i++) if (o->viewers[i] == &c) { o->viewers.erase(o->viewers.begin() + i); break; }
     c.sceneOwner = nullptr;
 }
 
-static void free_blas(Blas& b) { if (b.nodes) hipFree(b.nodes); if (b.tris) hipFree(b.tris); if (b.idx) hipFree(b.idx); if (b.rootBounds) hipFree(b.rootBounds); b.tree.release(); b = Blas(); }
+static void drop_tlas(Context& c) { c.haveTlas = false; c.tlasBlasIds.clear(); c.scene = SceneRefs{}; c.normalsShared = false; }
+
 // The context is about to give up its traversal copy while it keeps its bottom levels (it becomes a view of another context's scene): the
-// adopted ones get arrays of their own again. Synchronous; a rare path.
+// adopted ones get arrays of their own again. Each is copied into new arrays first and only then stops living in the copy, so that a
+// failure leaves every bottom level whole. Synchronous; a rare path.
 static hipError_t materialise_adopted(Context& c)
 {
     if (!c.blobDev) return hipSuccess;
     hipError_t e = hipStreamSynchronize(c.stream);
+    const uint8_t* blob = c.blobDev.data();
     for (auto& kv : c.blas) {
         Blas& b = kv.second;
         if (!b.inBlob || e != hipSuccess) continue;
-        const uint8_t* blob = (const uint8_t*)c.blobDev;
-        const size_t nb = sizeof(WideNode) * (size_t)(b.nodeCount ? b.nodeCount : 1), tb = sizeof(TriPacket) * (size_t)(b.triCount ? b.triCount : 1), ib = 16 * (size_t)(b.triCount ? b.triCount : 1);
-        if ((e = hipMalloc((void**)&b.nodes, nb)) != hipSuccess) break;
-        if ((e = hipMalloc((void**)&b.tris, tb)) != hipSuccess) break;
-        if ((e = hipMalloc((void**)&b.idx, ib)) != hipSuccess) break;
-        if ((e = hipMemcpy(b.nodes, blob + b.blobNodeAt, sizeof(WideNode) * (size_t)b.nodeCount, hipMemcpyDeviceToDevice)) != hipSuccess) break;
-        if (b.triCount && (e = hipMemcpy(b.tris, blob + b.blobTriAt, sizeof(TriPacket) * (size_t)b.triCount, hipMemcpyDeviceToDevice)) != hipSuccess) break;
-        if (b.triCount && (e = hipMemcpy(b.idx, blob + b.blobIdxAt, 16 * (size_t)b.triCount, hipMemcpyDeviceToDevice)) != hipSuccess) break;
-        b.inBlob = false;
+        const size_t nt = b.triCount ? b.triCount : 1;
+        DeviceBuffer<WideNode> nodes; DeviceBuffer<TriPacket> tris; DeviceBuffer<uint4> idx;
+        if ((e = nodes.reserve(b.nodeCount ? b.nodeCount : 1)) != hipSuccess) break;
+        if ((e = tris.reserve(nt)) != hipSuccess) break;
+        if ((e = idx.reserve(nt)) != hipSuccess) break;
+        if ((e = hipMemcpy(nodes.data(), blob + b.blobNodeAt, sizeof(WideNode) * (size_t)b.nodeCount, hipMemcpyDeviceToDevice)) != hipSuccess) break;
+        if (b.triCount && (e = hipMemcpy(tris.data(), blob + b.blobTriAt, sizeof(TriPacket) * (size_t)b.triCount, hipMemcpyDeviceToDevice)) != hipSuccess) break;
+        if (b.triCount && (e = hipMemcpy(idx.data(), blob + b.blobIdxAt, 16 * (size_t)b.triCount, hipMemcpyDeviceToDevice)) != hipSuccess) break;
+        b.nodes = std::move(nodes); b.tris = std::move(tris); b.idx = std::move(idx); b.inBlob = false;
     }
     return e;
-}
-
-static void free_tlas(Tlas& t)
-{
-    void* ptrs[] = { t.nodes, t.rootBounds, t.instances, (void*)t.blasBounds };
-    for (void* p : ptrs) if (p) hipFree(p);
-    t.tree.release();
-    t = Tlas();
 }
 
 void pt_destroy(PtContext* ctx)
@@ -93,56 +87,20 @@ void pt_destroy(PtContext* ctx)
     Context& c = ctx->c;
     hipSetDevice(c.device);
     hipStreamSynchronize(c.stream);
-    for (hipStream_t st : c.chainStream) if (st) hipStreamSynchronize(st);       // (the context's stream has waited for them already: every frame joins its chains)
+    for (const Stream& st : c.chainStream) if (st) hipStreamSynchronize(st.get());   // (the context's stream has waited for them already: every frame joins its chains)
     pt_comm_destroy(ctx);
     // an owner that is still viewed (pt_share_scene): its viewers lose the scene -- their next render answers PT_ERROR_NOT_READY -- after
     // their streams have drained, and never touch this context again
     for (Context* v : c.viewers) {
         hipStreamSynchronize(v->stream);
-        v->sceneOwner = nullptr; v->tlas = Tlas(); v->blobDev = nullptr; v->blobCapacity = 0; v->blob = BlobView{}; v->haveTlas = false;
-        v->blasTableDev = nullptr; v->instSourceDev = nullptr; v->blasTableCount = 0; v->normalsShared = false;
+        v->sceneOwner = nullptr;
+        drop_tlas(*v);
         v->objects = nullptr; v->objectCount = 0; v->instanceData = nullptr; v->instanceDataCount = 0;
-        if (v->graphExec) { hipGraphExecDestroy(v->graphExec); v->graphExec = nullptr; }
-        v->graphKey.clear(); v->chainGraphKey.clear();
+        v->graphExec.reset(); v->graphKey.clear(); v->chainGraphKey.clear();
     }
-    c.viewers.clear(); c.borrowers = 0;
-    for (auto& kv : c.blas) free_blas(kv.second);
-    c.buildScratch.release();
-    if (c.sceneOwner) { detach_from_owner(c); c.tlas = Tlas(); c.blobDev = nullptr; }       // views: the owner frees them
-    free_tlas(c.tlas);
-    if (c.heapDev) hipFree(c.heapDev);
-    if (c.srgbLutDev) hipFree(c.srgbLutDev);
-    if (c.blobDev) hipFree(c.blobDev);
-    if (c.tlasUploadDev) hipFree(c.tlasUploadDev);
-    for (auto& st : c.tlasStage) { if (st.host) hipHostFree(st.host); if (st.event) hipEventDestroy(st.event); }
-    if (c.tlasHeaderHost) hipHostFree(c.tlasHeaderHost);
-    if (c.tlasHeaderEvent) hipEventDestroy(c.tlasHeaderEvent);
-    if (c.validateDev) hipFree(c.validateDev);
-    if (c.shadeGeomDev) hipFree(c.shadeGeomDev);
-    if (c.shadeTexDev) hipFree(c.shadeTexDev);
-    for (hipStream_t st : c.chainStream) if (st) hipStreamDestroy(st);
-    if (c.chainFork) hipEventDestroy(c.chainFork);
-    for (hipEvent_t ev : c.chainJoin) if (ev) hipEventDestroy(ev);
-    if (c.shadeRecA) hipFree(c.shadeRecA);
-    if (c.shadeRecB) hipFree(c.shadeRecB);
-    release_direct_lighting(c);
-    for (int k = 0; k < 2; k++) {
-        PathQueue& q = c.queue[k];
-        void* ptrs[6] = { q.s0, q.s1, q.s2, q.r0, q.r1, q.hit };
-        for (void* p : ptrs) if (p) hipFree(p);
-    }
-    if (c.graphExec) hipGraphExecDestroy(c.graphExec);
-    for (hipGraphExec_t ge : c.chainGraph) if (ge) hipGraphExecDestroy(ge);
-    if (c.frameConstants) hipFree(c.frameConstants);
-    if (c.primaryRecords) hipFree(c.primaryRecords);
-    if (c.pixelAux) hipFree(c.pixelAux);
-    if (c.queueCounts) hipFree(c.queueCounts);
-    if (c.roundArgs) hipFree(c.roundArgs);
-    if (c.counters) hipFree(c.counters);
-    for (auto e : c.evExtend) hipEventDestroy(e);
-    for (auto e : c.evRound) hipEventDestroy(e);
-    for (auto e : c.evShade) hipEventDestroy(e);
-    delete ctx;
+    c.viewers.clear();
+    detach_from_owner(c);
+    delete ctx;                                          // the owners in Context free the rest
 }
 
 const char* pt_last_error(const PtContext* ctx) { return ctx ? ctx->c.lastError.c_str() : g_createError.c_str(); }
@@ -218,20 +176,17 @@ static int upload_heap(Context& c)
     if (!c.srgbLutDev) {                                  // sRGB -> linear table, evaluated in double (arithmetic spec)
         float lut[256];
         for (int i = 0; i < 256; i++) { double v = i / 255.0; lut[i] = (float)(v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4)); }
-        API_HIP(&c, hipMalloc((void**)&c.srgbLutDev, sizeof lut));
-        API_HIP(&c, hipMemcpy(c.srgbLutDev, lut, sizeof lut, hipMemcpyHostToDevice));
+        DeviceBuffer<float> dev;
+        API_HIP(&c, dev.reserve(256));
+        API_HIP(&c, hipMemcpy(dev.data(), lut, sizeof lut, hipMemcpyHostToDevice));
+        c.srgbLutDev = std::move(dev);
     }
     if (!c.heapDirty) return PT_OK;
     uint32_t n = (uint32_t)c.heapHost.size();
     c.heapHasTextures = false;
     for (const HeapEntry& e : c.heapHost) if (e.kind != kKindBuffer) c.heapHasTextures = true;
-    if (n > c.heapDevCap) {
-        if (c.heapDev) hipFree(c.heapDev);
-        c.heapDev = nullptr; c.heapDevCap = 0;
-        API_HIP(&c, hipMalloc((void**)&c.heapDev, sizeof(HeapEntry) * n));
-        c.heapDevCap = n;
-    }
-    if (n) API_HIP(&c, hipMemcpyAsync(c.heapDev, c.heapHost.data(), sizeof(HeapEntry) * n, hipMemcpyHostToDevice, c.stream));
+    API_HIP(&c, c.heapDev.reserve(n));
+    if (n) API_HIP(&c, hipMemcpyAsync(c.heapDev.data(), c.heapHost.data(), sizeof(HeapEntry) * n, hipMemcpyHostToDevice, c.stream));
     API_HIP(&c, hipStreamSynchronize(c.stream));     // heapHost may change right after
     c.heapDirty = false; c.validated = false;
     return PT_OK;
@@ -251,8 +206,6 @@ static int check_geometries(Context& c, const PtGeometryDesc* geometries, uint32
     return PT_OK;
 }
 
-static void drop_tlas(Context& c) { c.haveTlas = false; c.tlasBlasIds.clear(); c.blasTableDev = nullptr; c.instSourceDev = nullptr; c.blasTableCount = 0; c.normalsShared = false; }
-
 // the traversal stack holds at most two entries per level of both trees (a node group and, in the streaming form, a postponed
 // leaf group) plus the three of an instance transition (pt_trace.hpp)
 static int check_depth(Context& c, uint32_t tlasDepth)
@@ -267,11 +220,11 @@ static int check_depth(Context& c, uint32_t tlasDepth)
 static int poll_tlas_header(Context& c, bool wait)
 {
     if (!c.tlasHeaderPending) return PT_OK;
-    if (wait) API_HIP(&c, hipEventSynchronize(c.tlasHeaderEvent));
-    else if (hipEventQuery(c.tlasHeaderEvent) != hipSuccess) { (void)hipGetLastError(); return PT_OK; }
+    if (wait) API_HIP(&c, hipEventSynchronize(c.tlasHeaderEvent.get()));
+    else if (hipEventQuery(c.tlasHeaderEvent.get()) != hipSuccess) { (void)hipGetLastError(); return PT_OK; }
     c.tlasHeaderPending = false;
-    if (c.tlasHeaderHost->error) { drop_tlas(c); return fail(&c, PT_ERROR_INVALID_ARGUMENT, "top-level build failed: tree deeper than the builder's level limit"); }
-    int s = check_depth(c, c.tlasHeaderHost->depth);
+    if (c.tlasHeaderHost.data()->error) { drop_tlas(c); return fail(&c, PT_ERROR_INVALID_ARGUMENT, "top-level build failed: tree deeper than the builder's level limit"); }
+    int s = check_depth(c, c.tlasHeaderHost.data()->depth);
     if (s != PT_OK) drop_tlas(c);
     return s;
 }
@@ -291,12 +244,12 @@ int pt_build_bottom_level(PtContext* ctx, const PtGeometryDesc* geometries, uint
     if (!updatable) std::swap(b.tree, c.buildScratch);
     hipError_t e = build_blas_device(geometries, geometry_count, updatable, c.stream, b);
     if (!updatable) std::swap(b.tree, c.buildScratch);
-    if (e != hipSuccess) { free_blas(b); return fail_hip(&c, e, "bottom-level build"); }
-    if (b.buildError || 2u * b.depth + 4u > (uint32_t)kStackSize) { free_blas(b); return fail(&c, PT_ERROR_INVALID_ARGUMENT, "bottom-level build failed: tree too deep for the traversal stack"); }
+    if (e != hipSuccess) return fail_hip(&c, e, "bottom-level build");
+    if (b.buildError || 2u * b.depth + 4u > (uint32_t)kStackSize) return fail(&c, PT_ERROR_INVALID_ARGUMENT, "bottom-level build failed: tree too deep for the traversal stack");
     b.geometryCount = geometry_count;
     uint64_t id = c.nextBlasId++;
-    c.blas[id] = b;
     c.maxBlasDepth = std::max(c.maxBlasDepth, b.depth);
+    c.blas[id] = std::move(b);
     *out_blas_id = id;
     return PT_OK;
 }
@@ -307,7 +260,7 @@ int pt_update_bottom_level(PtContext* ctx, uint64_t blas_id, const PtGeometryDes
     Context& c = ctx->c;
     auto it = c.blas.find(blas_id);
     API_ARG(&c, it != c.blas.end(), "unknown bottom-level id");
-    API_ARG(&c, c.borrowers == 0, "other contexts view this context's scene (pt_share_scene): destroy or re-point them before updating a bottom level");
+    API_ARG(&c, c.viewers.empty(), "other contexts view this context's scene (pt_share_scene): destroy or re-point them before updating a bottom level");
     int s = check_geometries(c, geometries, geometry_count);
     if (s != PT_OK) return s;
     API_HIP(&c, hipSetDevice(c.device));
@@ -330,12 +283,11 @@ int pt_update_bottom_level(PtContext* ctx, uint64_t blas_id, const PtGeometryDes
     if (!updatable) std::swap(nb.tree, c.buildScratch);
     hipError_t e = build_blas_device(geometries, geometry_count, updatable, c.stream, nb);
     if (!updatable) std::swap(nb.tree, c.buildScratch);
-    if (e != hipSuccess) { free_blas(nb); return fail_hip(&c, e, "bottom-level update"); }
-    if (nb.buildError || 2u * nb.depth + 4u > (uint32_t)kStackSize) { free_blas(nb); return fail(&c, PT_ERROR_INVALID_ARGUMENT, "bottom-level update failed: tree too deep for the traversal stack"); }
+    if (e != hipSuccess) return fail_hip(&c, e, "bottom-level update");
+    if (nb.buildError || 2u * nb.depth + 4u > (uint32_t)kStackSize) return fail(&c, PT_ERROR_INVALID_ARGUMENT, "bottom-level update failed: tree too deep for the traversal stack");
     nb.geometryCount = geometry_count;
-    free_blas(b);
-    b = nb;
     c.maxBlasDepth = std::max(c.maxBlasDepth, nb.depth);
+    b = std::move(nb);
     drop_tlas(c);                                        // instance records point at the freed arrays
     return PT_OK;
 }
@@ -356,15 +308,93 @@ int pt_release_bottom_level(PtContext* ctx, uint64_t blas_id)
     Context& c = ctx->c;
     auto it = c.blas.find(blas_id);
     API_ARG(&c, it != c.blas.end(), "unknown bottom-level id");
-    API_ARG(&c, c.borrowers == 0, "other contexts view this context's scene (pt_share_scene)");
+    API_ARG(&c, c.viewers.empty(), "other contexts view this context's scene (pt_share_scene)");
     hipStreamSynchronize(c.stream);
     // the live top level may refer to it (instance records hold its arrays): that top level dies with it, and a render
     // before the next pt_build_top_level answers PT_ERROR_NOT_READY instead of reading freed memory
     for (uint64_t id : c.tlasBlasIds) if (id == blas_id) { drop_tlas(c); break; }
-    free_blas(it->second);
     c.blas.erase(it);
     c.maxBlasDepth = 0;
     for (auto& kv : c.blas) c.maxBlasDepth = std::max(c.maxBlasDepth, kv.second.depth);
+    return PT_OK;
+}
+
+// ---- the top-level build, in phases: plan (host only) -> allocate -> upload -> launch -> commit. Nothing before the commit changes the
+// context's traversal copy, its capacity or where a bottom level lives in it: a build that fails leaves them as they were (drop_tlas has
+// put the top level aside, so a render answers PT_ERROR_NOT_READY until the next build succeeds).
+//
+// Layout of the traversal copy:
+//   [ nodes: top level (reserved) | one piece per bottom level ] [ triangle packets per piece ] [ vertex indices per packet ]
+//   [ InstanceT x count (API order) ] [ InstanceT x count (top-level leaf order) ] [ entry record x count ]
+// Everything that depends on the number of instances sits BEHIND the bottom-level data, and the top level's node reservation only moves
+// in steps, so that the pieces keep their places from build to build: a STATIC bottom level lives in the copy only (round 4, VERDICT r3
+// item 8). Its first top-level build copies its nodes, packets and indices in and frees the arrays the build left ("adoption"); later
+// builds find it in place and copy nothing; when the layout does change (another set of meshes, a top level beyond its reservation) a new
+// copy is allocated and the pieces move over from the old one. A bottom level built with ALLOW_UPDATE keeps its own arrays -- the refit
+// writes them -- and is copied in every build, as before. Bottom levels that were adopted but are not referenced by this top level ride
+// along, so that a later top level can still name them.
+namespace {
+struct TopLevelPlan {
+    struct Piece { uint64_t id; Blas* b; uint32_t nodeBase, triBase; bool referenced; };
+    std::vector<Piece> pieces;
+    std::vector<uint64_t> pieceIds;
+    std::map<uint64_t, uint32_t> pieceOf;
+    std::vector<BlasEntry> table;
+    uint32_t tlasNodeExact = 0, tlasNodeCap = 0, blobNodes = 0, blobTris = 0;
+    uint64_t tris = 0, objectEnd = 0, bindingHash = 1469598103934665603ull, lightHash = 1469598103934665603ull;
+    size_t srcBytes = 0, nodeAt = 0, triAt = 0, idxAt = 0, instAt = 0, leafAt = 0, enterAt = 0, total = 0;
+    size_t node_at(const Piece& p) const { return nodeAt + sizeof(WideNode) * (size_t)p.nodeBase; }
+    size_t tri_at(const Piece& p) const { return triAt + sizeof(TriPacket) * (size_t)p.triBase; }
+    size_t idx_at(const Piece& p) const { return idxAt + 16 * (size_t)p.triBase; }
+    bool in_place(const Piece& p) const { return p.b->blobNodeAt == node_at(p) && p.b->blobTriAt == tri_at(p) && p.b->blobIdxAt == idx_at(p); }
+};
+}
+
+// host only: resolve the ids, lay the copy out, write the instance sources into c.tlasUploadHost
+static int plan_top_level(Context& c, const PtInstanceDesc* descs, uint32_t count, TopLevelPlan& P)
+{
+    P.tlasNodeExact = wide_node_capacity(count);
+    P.tlasNodeCap = P.tlasNodeExact;
+    if (count >= 64u) { P.tlasNodeCap = 128u; while (P.tlasNodeCap < P.tlasNodeExact) P.tlasNodeCap <<= 1; }   // (small scenes stay exact: their copy is staged into LDS whole)
+    if (c.blobDev && c.tlasNodeReserve >= P.tlasNodeExact && c.tlasNodeReserve <= 2u * P.tlasNodeCap) P.tlasNodeCap = c.tlasNodeReserve;   // keep the reservation of the last build while it fits
+    P.blobNodes = P.tlasNodeCap;
+    P.lightHash ^= count;
+    P.srcBytes = sizeof(InstanceSource) * (size_t)count;
+    std::vector<uint8_t>& up = c.tlasUploadHost;
+    up.resize(P.srcBytes);
+    for (uint32_t i = 0; i < count; i++) {
+        auto it = c.blas.find(descs[i].AccelerationStructure);
+        API_ARG(&c, it != c.blas.end(), "instance refers to an unknown bottom-level id");
+        Blas& b = it->second;
+        auto pb = P.pieceOf.find(descs[i].AccelerationStructure);
+        if (pb == P.pieceOf.end()) {
+            P.pieces.push_back(TopLevelPlan::Piece{ descs[i].AccelerationStructure, &b, P.blobNodes, P.blobTris, true });
+            // (pointers of the row are filled in below, once the places are known)
+            P.table.push_back(BlasEntry{ nullptr, nullptr, b.rootBounds.data(), b.triCount, b.nodeCount, P.blobNodes, P.blobTris, nullptr, descs[i].InstanceID & 0xFFFFFFu, b.geometryCount });
+            P.blobNodes += b.nodeCount; P.blobTris += b.triCount;
+            P.pieceIds.push_back(descs[i].AccelerationStructure);
+            pb = P.pieceOf.emplace(descs[i].AccelerationStructure, (uint32_t)P.table.size() - 1).first;
+        }
+        InstanceSource src;
+        memcpy(src.transform, descs[i].Transform, sizeof(float) * 12);
+        src.instanceID = descs[i].InstanceID & 0xFFFFFFu; src.mask = descs[i].InstanceMask & 0xFFu; src.blasSlot = pb->second; src._pad = 0;
+        memcpy(up.data() + sizeof(InstanceSource) * (size_t)i, &src, sizeof src);
+        P.tris += b.triCount;
+        P.objectEnd = std::max<uint64_t>(P.objectEnd, (uint64_t)src.instanceID + b.geometryCount);
+        P.bindingHash = (P.bindingHash ^ src.instanceID) * 1099511628211ull; P.bindingHash = (P.bindingHash ^ descs[i].AccelerationStructure) * 1099511628211ull;
+        P.lightHash = (P.lightHash ^ src.instanceID) * 1099511628211ull; P.lightHash = (P.lightHash ^ src.mask) * 1099511628211ull;
+        P.lightHash = (P.lightHash ^ descs[i].AccelerationStructure) * 1099511628211ull;
+    }
+    for (auto& kv : c.blas)                                        // adopted, not referenced: carried along
+        if (kv.second.inBlob && !P.pieceOf.count(kv.first)) {
+            P.pieces.push_back(TopLevelPlan::Piece{ kv.first, &kv.second, P.blobNodes, P.blobTris, false });
+            P.blobNodes += kv.second.nodeCount; P.blobTris += kv.second.triCount;
+        }
+    const size_t instBytes = (size_t)count * sizeof(InstanceT), nodeBytes = (size_t)P.blobNodes * sizeof(WideNode), triBytes = (size_t)P.blobTris * sizeof(TriPacket);
+    const size_t idxBytes = (size_t)P.blobTris * 16;
+    P.nodeAt = 0; P.triAt = nodeBytes; P.idxAt = nodeBytes + triBytes; P.instAt = P.idxAt + idxBytes; P.leafAt = P.instAt + instBytes; P.enterAt = P.leafAt + instBytes;
+    P.total = P.enterAt + instBytes;
+    API_ARG(&c, P.total / 16 < 0xFFFFFFFFull, "scene too large for 32-bit blob addressing");
     return PT_OK;
 }
 
@@ -374,213 +404,138 @@ int pt_build_top_level(PtContext* ctx, const PtInstanceDesc* descs, uint32_t cou
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
     API_ARG(&c, descs || count == 0, "descs is NULL");
-    API_ARG(&c, c.borrowers == 0, "other contexts view this context's scene (pt_share_scene): destroy or re-point them before rebuilding");
+    API_ARG(&c, c.viewers.empty(), "other contexts view this context's scene (pt_share_scene): destroy or re-point them before rebuilding");
     API_HIP(&c, hipSetDevice(c.device));
-    if (c.sceneOwner) { detach_from_owner(c); c.tlas = Tlas(); c.blobDev = nullptr; c.blobCapacity = 0; c.blob = BlobView{}; drop_tlas(c); }
+    if (c.sceneOwner) { detach_from_owner(c); drop_tlas(c); }
     int st = poll_tlas_header(c, false);
     if (st != PT_OK) return st;
+    TopLevelPlan P;
+    st = plan_top_level(c, descs, count, P);
+    if (st != PT_OK) return st;
 
-    // ---- host side: resolve ids and lay the traversal copy out:
-    //   [ nodes: top level (reserved) | one piece per bottom level ] [ triangle packets per piece ] [ vertex indices per packet ]
-    //   [ InstanceT x count (API order) ] [ InstanceT x count (top-level leaf order) ] [ entry record x count ]
-    // Everything that depends on the number of instances sits BEHIND the bottom-level data, and the top level's node reservation only moves
-    // in steps, so that the pieces keep their places from build to build: a STATIC bottom level lives in the copy only (round 4, VERDICT r3
-    // item 8). Its first top-level build copies its nodes, packets and indices in and frees the arrays the build left ("adoption"); later
-    // builds find it in place and copy nothing; when the layout does change (another set of meshes, a top level beyond its reservation) a new
-    // copy is allocated and the pieces move over from the old one. A bottom level built with ALLOW_UPDATE keeps its own arrays -- the refit
-    // writes them -- and is copied in every build, as before. Bottom levels that were adopted but are not referenced by this top level ride
-    // along, so that a later top level can still name them.
-    const uint32_t tlasNodeExact = wide_node_capacity(count);
-    uint32_t tlasNodeCap = tlasNodeExact;
-    if (count >= 64u) { tlasNodeCap = 128u; while (tlasNodeCap < tlasNodeExact) tlasNodeCap <<= 1; }   // (small scenes stay exact: their copy is staged into LDS whole)
-    if (c.blob.base && c.tlasNodeReserve >= tlasNodeExact && c.tlasNodeReserve <= 2u * tlasNodeCap) tlasNodeCap = c.tlasNodeReserve;   // keep the reservation of the last build while it fits
-    struct Piece { uint64_t id; Blas* b; uint32_t nodeBase, triBase; bool referenced; };
-    std::vector<Piece> pieces;
-    std::vector<uint64_t> pieceIds;
-    std::map<uint64_t, uint32_t> pieceOf;
-    std::vector<BlasEntry> table;
-    uint32_t blobNodes = tlasNodeCap, blobTris = 0;
-    uint64_t tris = 0, objectEnd = 0, bindingHash = 1469598103934665603ull, lightHash = 1469598103934665603ull ^ count;
-    const size_t srcBytes = sizeof(InstanceSource) * (size_t)count;
-    // staged in pinned host memory, two buffers taken in turn, each guarded by an event recorded behind the copy that read it: the host
-    // may be a build ahead of the stream (a dynamic frame never synchronises) without rewriting bytes a copy has yet to read
-    std::vector<uint8_t>& up = c.tlasUploadHost;
-    up.resize(srcBytes);
-    for (uint32_t i = 0; i < count; i++) {
-        auto it = c.blas.find(descs[i].AccelerationStructure);
-        API_ARG(&c, it != c.blas.end(), "instance refers to an unknown bottom-level id");
-        Blas& b = it->second;
-        auto pb = pieceOf.find(descs[i].AccelerationStructure);
-        if (pb == pieceOf.end()) {
-            pieces.push_back(Piece{ descs[i].AccelerationStructure, &b, blobNodes, blobTris, true });
-            // (pointers of the row are filled in below, once the places are known)
-            table.push_back(BlasEntry{ nullptr, nullptr, b.rootBounds, b.triCount, b.nodeCount, blobNodes, blobTris, nullptr, descs[i].InstanceID & 0xFFFFFFu, b.geometryCount });
-            blobNodes += b.nodeCount; blobTris += b.triCount;
-            pieceIds.push_back(descs[i].AccelerationStructure);
-            pb = pieceOf.emplace(descs[i].AccelerationStructure, (uint32_t)table.size() - 1).first;
-        }
-        InstanceSource src;
-        memcpy(src.transform, descs[i].Transform, sizeof(float) * 12);
-        src.instanceID = descs[i].InstanceID & 0xFFFFFFu; src.mask = descs[i].InstanceMask & 0xFFu; src.blasSlot = pb->second; src._pad = 0;
-        memcpy(up.data() + sizeof(InstanceSource) * (size_t)i, &src, sizeof src);
-        tris += b.triCount;
-        objectEnd = std::max<uint64_t>(objectEnd, (uint64_t)src.instanceID + b.geometryCount);
-        bindingHash = (bindingHash ^ src.instanceID) * 1099511628211ull; bindingHash = (bindingHash ^ descs[i].AccelerationStructure) * 1099511628211ull;
-        lightHash = (lightHash ^ src.instanceID) * 1099511628211ull; lightHash = (lightHash ^ src.mask) * 1099511628211ull;
-        lightHash = (lightHash ^ descs[i].AccelerationStructure) * 1099511628211ull;
-    }
-    for (auto& kv : c.blas)                                        // adopted, not referenced: carried along
-        if (kv.second.inBlob && !pieceOf.count(kv.first)) {
-            pieces.push_back(Piece{ kv.first, &kv.second, blobNodes, blobTris, false });
-            blobNodes += kv.second.nodeCount; blobTris += kv.second.triCount;
-        }
-    const size_t instBytes = (size_t)count * sizeof(InstanceT), nodeBytes = (size_t)blobNodes * sizeof(WideNode), triBytes = (size_t)blobTris * sizeof(TriPacket);
-    const size_t idxBytes = (size_t)blobTris * 16;
-    const size_t nodeAt = 0, triAt = nodeBytes, idxAt = nodeBytes + triBytes, instAt = idxAt + idxBytes, leafAt = instAt + instBytes, enterAt = leafAt + instBytes;
-    const size_t total = enterAt + instBytes;
-    API_ARG(&c, total / 16 < 0xFFFFFFFFull, "scene too large for 32-bit blob addressing");
-    auto node_at = [&](const Piece& p) { return nodeAt + sizeof(WideNode) * (size_t)p.nodeBase; };
-    auto tri_at = [&](const Piece& p) { return triAt + sizeof(TriPacket) * (size_t)p.triBase; };
-    auto idx_at = [&](const Piece& p) { return idxAt + 16 * (size_t)p.triBase; };
-
-    // ---- capacities: everything is grow-only, so the rebuild of an unchanged scene layout (a dynamic frame) allocates nothing and
-    // waits for nothing; growth waits for the stream first (kernels in flight may still read the old buffers)
+    // ---- allocate: everything is grow-only, so the rebuild of an unchanged scene layout (a dynamic frame) allocates nothing and waits for
+    // nothing; growth waits for the stream first (kernels in flight may still read the old buffers). A new traversal copy stays local.
     bool moved = false;                                            // an adopted piece is not where the new layout wants it
-    for (const Piece& p : pieces) if (p.b->inBlob && (p.b->blobNodeAt != node_at(p) || p.b->blobTriAt != tri_at(p) || p.b->blobIdxAt != idx_at(p))) moved = true;
-    const bool newBlob = total > c.blobCapacity || !c.blobDev || moved;
-    const bool growth = count > c.tlas.capacity || !c.tlas.nodes || count > c.tlasInstanceCap || !c.tlas.instances || newBlob;
+    for (const auto& p : P.pieces) if (p.b->inBlob && !P.in_place(p)) moved = true;
+    const bool newBlob = P.total > c.blobDev.capacity() || moved;
+    const uint32_t instCap = count ? count : 1;
+    const bool growth = instCap > c.tlas.instances.capacity() || wide_node_capacity(instCap) > c.tlas.nodes.capacity() || newBlob;
     if (growth) API_HIP(&c, hipStreamSynchronize(c.stream));
     drop_tlas(c);
-    if (count > c.tlasInstanceCap || !c.tlas.instances) {
-        if (c.tlas.instances) hipFree(c.tlas.instances);
-        if (c.tlas.blasBounds) hipFree((void*)c.tlas.blasBounds);
-        c.tlas.instances = nullptr; c.tlas.blasBounds = nullptr; c.tlasInstanceCap = 0;
-        API_HIP(&c, hipMalloc((void**)&c.tlas.instances, sizeof(InstanceRecord) * (count ? count : 1)));
-        API_HIP(&c, hipMalloc((void**)&c.tlas.blasBounds, sizeof(float*) * (count ? count : 1)));
-        c.tlasInstanceCap = count ? count : 1;
+    if (instCap > c.tlas.instances.capacity()) {
+        c.tlas.instances.reset(); c.tlas.blasBounds.reset();
+        API_HIP(&c, c.tlas.blasBounds.reserve(instCap));
+        API_HIP(&c, c.tlas.instances.reserve(instCap));            // last: the grow decision reads its capacity
     }
-    void* oldBlob = nullptr;                                       // pieces move over from it; freed once the moves have run
+    DeviceBuffer<uint8_t> newCopy;                                 // pieces move over from the context's copy into it
     if (newBlob) {
-        oldBlob = c.blobDev;
-        const size_t oldCap = c.blobCapacity, cap = std::max<size_t>(total ? total : 16, moved ? c.blobCapacity : 0);
-        c.blobDev = nullptr; c.blobCapacity = 0; c.blob = BlobView{};
-        hipError_t ea = hipMalloc(&c.blobDev, cap);
-        if (ea != hipSuccess) { c.blobDev = oldBlob; c.blobCapacity = oldCap; return fail_hip(&c, ea, "hipMalloc(traversal copy)"); }   // (the adopted pieces stay where they were)
-        c.blobCapacity = cap;
+        const hipError_t ea = newCopy.reserve(std::max<size_t>(P.total ? P.total : 16, moved ? c.blobDev.capacity() : 0));
+        if (ea != hipSuccess) return fail_hip(&c, ea, "hipMalloc(traversal copy)");
     }
-    if (!c.tlasHeaderHost) {
-        API_HIP(&c, hipHostMalloc((void**)&c.tlasHeaderHost, sizeof(WideHeader)));
-        API_HIP(&c, hipEventCreateWithFlags(&c.tlasHeaderEvent, hipEventDisableTiming));
-    }
-    uint8_t* blob = (uint8_t*)c.blobDev;
+    if (!c.tlasHeaderEvent) API_HIP(&c, create_event(c.tlasHeaderEvent, hipEventDisableTiming));
+    API_HIP(&c, c.tlasHeaderHost.reserve(1));
+    const uint8_t* oldBlob = c.blobDev.data();
+    uint8_t* blob = newBlob ? newCopy.data() : c.blobDev.data();
 
-    // ---- one upload: instance sources | bottom-level table | copy jobs (first the moves / adoptions of static pieces, which run before
+    // ---- upload, one: instance sources | bottom-level table | copy jobs (first the moves / adoptions of static pieces, which run before
     // anything reads the table; then the per-build copies of updatable pieces and of the top level's nodes, inside the assembly launch)
     std::vector<BlobCopy> preJobs, jobs;
-    std::vector<Piece*> adopting;
-    for (Piece& p : pieces) {
+    std::vector<Blas*> adopting;
+    for (const auto& p : P.pieces) {
         Blas& b = *p.b;
-        uint8_t* dn = blob + node_at(p); uint8_t* dt = blob + tri_at(p); uint8_t* di = blob + idx_at(p);
+        uint8_t* dn = blob + P.node_at(p); uint8_t* dt = blob + P.tri_at(p); uint8_t* di = blob + P.idx_at(p);
         const uint64_t n16 = sizeof(WideNode) * (uint64_t)b.nodeCount / 16, t16 = sizeof(TriPacket) * (uint64_t)b.triCount / 16, i16 = b.triCount;
         const void *sn, *st_, *si;
         if (b.updatable) {                                         // own arrays stay the truth: copied in by the assembly launch, read in place by the build's kernels
-            jobs.push_back(BlobCopy{ b.nodes, dn, n16 });
-            if (b.triCount) { jobs.push_back(BlobCopy{ b.tris, dt, t16 }); jobs.push_back(BlobCopy{ b.idx, di, i16 }); }
-            sn = b.nodes; st_ = b.tris; si = b.idx;
+            jobs.push_back(BlobCopy{ b.nodes.data(), dn, n16 });
+            if (b.triCount) { jobs.push_back(BlobCopy{ b.tris.data(), dt, t16 }); jobs.push_back(BlobCopy{ b.idx.data(), di, i16 }); }
+            sn = b.nodes.data(); st_ = b.tris.data(); si = b.idx.data();
         } else {
             if (b.inBlob) {
                 if (newBlob) {                                     // moves over from the old copy
-                    const uint8_t* ob = (const uint8_t*)oldBlob;
-                    preJobs.push_back(BlobCopy{ ob + b.blobNodeAt, dn, n16 });
-                    if (b.triCount) { preJobs.push_back(BlobCopy{ ob + b.blobTriAt, dt, t16 }); preJobs.push_back(BlobCopy{ ob + b.blobIdxAt, di, i16 }); }
+                    preJobs.push_back(BlobCopy{ oldBlob + b.blobNodeAt, dn, n16 });
+                    if (b.triCount) { preJobs.push_back(BlobCopy{ oldBlob + b.blobTriAt, dt, t16 }); preJobs.push_back(BlobCopy{ oldBlob + b.blobIdxAt, di, i16 }); }
                 }                                                  // else: in place already
             } else {                                               // first top level that sees it: adopted
-                preJobs.push_back(BlobCopy{ b.nodes, dn, n16 });
-                if (b.triCount) { preJobs.push_back(BlobCopy{ b.tris, dt, t16 }); preJobs.push_back(BlobCopy{ b.idx, di, i16 }); }
-                adopting.push_back(&p);
+                preJobs.push_back(BlobCopy{ b.nodes.data(), dn, n16 });
+                if (b.triCount) { preJobs.push_back(BlobCopy{ b.tris.data(), dt, t16 }); preJobs.push_back(BlobCopy{ b.idx.data(), di, i16 }); }
+                adopting.push_back(&b);
             }
             sn = dn; st_ = dt; si = di;
         }
-        if (p.referenced) { BlasEntry& row = table[pieceOf[p.id]]; row.nodes = (const WideNode*)sn; row.tris = (const TriPacket*)st_; row.idx = (const uint4*)si; }
+        if (p.referenced) { BlasEntry& row = P.table[P.pieceOf[p.id]]; row.nodes = (const WideNode*)sn; row.tris = (const TriPacket*)st_; row.idx = (const uint4*)si; }
     }
-    const size_t tableOff = (srcBytes + 15) / 16 * 16, tableBytes = sizeof(BlasEntry) * table.size();
+    const size_t tableOff = (P.srcBytes + 15) / 16 * 16, tableBytes = sizeof(BlasEntry) * P.table.size();
     hipError_t e = build_tlas_prepare(c.tlas, count);          // node / order arrays of the TLAS (grow-only), known before the jobs that copy them
     if (e != hipSuccess) return fail_hip(&c, e, "top-level build");
-    jobs.push_back(BlobCopy{ c.tlas.nodes, blob + nodeAt, sizeof(WideNode) * (size_t)tlasNodeExact / 16 });
+    jobs.push_back(BlobCopy{ c.tlas.nodes.data(), blob + P.nodeAt, sizeof(WideNode) * (size_t)P.tlasNodeExact / 16 });
     const size_t preOff = (tableOff + tableBytes + 15) / 16 * 16, preBytes = sizeof(BlobCopy) * preJobs.size();
     const size_t jobsOff = (preOff + preBytes + 15) / 16 * 16, jobsBytes = sizeof(BlobCopy) * jobs.size();
+    std::vector<uint8_t>& up = c.tlasUploadHost;
     up.resize(jobsOff + jobsBytes);
-    if (tableBytes) memcpy(up.data() + tableOff, table.data(), tableBytes);
+    if (tableBytes) memcpy(up.data() + tableOff, P.table.data(), tableBytes);
     if (preBytes) memcpy(up.data() + preOff, preJobs.data(), preBytes);
     memcpy(up.data() + jobsOff, jobs.data(), jobsBytes);
-    if (up.size() > c.tlasUploadCap || !c.tlasUploadDev) {
+    if (up.size() > c.tlasUploadDev.capacity()) {
         if (!growth) API_HIP(&c, hipStreamSynchronize(c.stream));
-        if (c.tlasUploadDev) hipFree(c.tlasUploadDev);
-        c.tlasUploadDev = nullptr; c.tlasUploadCap = 0;
-        API_HIP(&c, hipMalloc(&c.tlasUploadDev, up.size() * 2));           // head room: a few more instances next frame do not reallocate
-        c.tlasUploadCap = up.size() * 2;
+        API_HIP(&c, c.tlasUploadDev.reserve(up.size() * 2));          // head room: a few more instances next frame do not reallocate
     }
     {
-        Context::UploadStage& st = c.tlasStage[c.tlasStageNext];
+        // staged in pinned host memory, two buffers taken in turn, each guarded by an event recorded behind the copy that read it: the host
+        // may be a build ahead of the stream (a dynamic frame never synchronises) without rewriting bytes a copy has yet to read
+        Context::UploadStage& sg = c.tlasStage[c.tlasStageNext];
         c.tlasStageNext ^= 1u;
-        if (st.event) API_HIP(&c, hipEventSynchronize(st.event));          // the copy that last read this buffer has run
-        else API_HIP(&c, hipEventCreateWithFlags(&st.event, hipEventDisableTiming));
-        if (up.size() > st.capacity) {
-            if (st.host) hipHostFree(st.host);
-            st.host = nullptr; st.capacity = 0;
-            API_HIP(&c, hipHostMalloc(&st.host, up.size() * 2));
-            st.capacity = up.size() * 2;
-        }
-        memcpy(st.host, up.data(), up.size());
-        API_HIP(&c, hipMemcpyAsync(c.tlasUploadDev, st.host, up.size(), hipMemcpyHostToDevice, c.stream));
-        API_HIP(&c, hipEventRecord(st.event, c.stream));
+        if (sg.event) API_HIP(&c, hipEventSynchronize(sg.event.get()));   // the copy that last read this buffer has run
+        else API_HIP(&c, create_event(sg.event, hipEventDisableTiming));
+        if (up.size() > sg.host.capacity()) API_HIP(&c, sg.host.reserve(up.size() * 2));
+        memcpy(sg.host.data(), up.data(), up.size());
+        API_HIP(&c, hipMemcpyAsync(c.tlasUploadDev.data(), sg.host.data(), up.size(), hipMemcpyHostToDevice, c.stream));
+        API_HIP(&c, hipEventRecord(sg.event.get(), c.stream));
     }
-    const InstanceSource* dSrc = (const InstanceSource*)c.tlasUploadDev;
-    const BlasEntry* dTable = (const BlasEntry*)((const uint8_t*)c.tlasUploadDev + tableOff);
-    c.blasTableDev = dTable; c.blasTableCount = (uint32_t)table.size(); c.instSourceDev = dSrc; c.blasTableMaxTris = 0;
-    for (const BlasEntry& te : table) c.blasTableMaxTris = std::max(c.blasTableMaxTris, te.triCount);
-    const BlobCopy* dPre = (const BlobCopy*)((const uint8_t*)c.tlasUploadDev + preOff);
-    const BlobCopy* dJobs = (const BlobCopy*)((const uint8_t*)c.tlasUploadDev + jobsOff);
+    const uint8_t* upDev = c.tlasUploadDev.data();
+    const InstanceSource* dSrc = (const InstanceSource*)upDev;
+    const BlasEntry* dTable = (const BlasEntry*)(upDev + tableOff);
+    const BlobCopy* dPre = (const BlobCopy*)(upDev + preOff);
+    const BlobCopy* dJobs = (const BlobCopy*)(upDev + jobsOff);
 
-    // ---- device side, all in stream order
-    e = hipSuccess;
+    // ---- launch, all in stream order
     if (!preJobs.empty()) e = launch_blob_assembly(nullptr, c.tlas, nullptr, 0, nullptr, nullptr, dPre, (uint32_t)preJobs.size(), nullptr, c.stream);   // static pieces into place first: the table points there
-    if (e == hipSuccess) e = launch_instance_records(dSrc, dTable, count, c.tlas.instances, c.tlas.blasBounds, c.tlas.tree.bounds, c.stream);
-    if (e == hipSuccess) e = build_tlas_device(c.tlas.instances, c.tlas.blasBounds, count, c.stream, c.tlas);
-    if (e == hipSuccess) e = launch_blob_assembly(c.tlas.instances, c.tlas, dTable, count, (InstanceT*)(blob + instAt), (InstanceT*)(blob + leafAt),
-                                                 dJobs, (uint32_t)jobs.size(), (f4v*)(blob + enterAt), c.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c.tlasHeaderHost, c.tlas.tree.header, sizeof(WideHeader), hipMemcpyDeviceToHost, c.stream);
-    if (e == hipSuccess) e = hipEventRecord(c.tlasHeaderEvent, c.stream);
-    // adoption and moves are load-time events (the first top level of a scene, a change of its meshes): wait for the copies, then let go of
-    // what they read. A frame of a dynamic scene over an unchanged set of meshes comes past here with nothing to do.
-    if (!adopting.empty() || oldBlob) {
+    if (e == hipSuccess) e = launch_instance_records(dSrc, dTable, count, c.tlas.instances.data(), c.tlas.blasBounds.data(), c.tlas.tree.bounds.data(), c.stream);
+    if (e == hipSuccess) e = build_tlas_device(c.tlas.instances.data(), c.tlas.blasBounds.data(), count, c.stream, c.tlas);
+    if (e == hipSuccess) e = launch_blob_assembly(c.tlas.instances.data(), c.tlas, dTable, count, (InstanceT*)(blob + P.instAt), (InstanceT*)(blob + P.leafAt),
+                                                 dJobs, (uint32_t)jobs.size(), (f4v*)(blob + P.enterAt), c.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c.tlasHeaderHost.data(), c.tlas.tree.header.data(), sizeof(WideHeader), hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipEventRecord(c.tlasHeaderEvent.get(), c.stream);
+    // adoption and moves are load-time events (the first top level of a scene, a change of its meshes): wait for the copies before letting
+    // go of what they read. A frame of a dynamic scene over an unchanged set of meshes comes past here with nothing to do.
+    if (!adopting.empty() || (newBlob && oldBlob)) {
         const hipError_t es = hipStreamSynchronize(c.stream);
         if (e == hipSuccess) e = es;
-        if (es == hipSuccess) {
-            for (Piece* p : adopting) {
-                Blas& b = *p->b;
-                if (b.nodes) hipFree(b.nodes);
-                if (b.tris) hipFree(b.tris);
-                if (b.idx) hipFree(b.idx);
-                b.nodes = nullptr; b.tris = nullptr; b.idx = nullptr; b.inBlob = true;
-            }
-            if (oldBlob) hipFree(oldBlob);
-        }
     }
-    for (Piece& p : pieces) if (p.b->inBlob) { p.b->blobNodeAt = node_at(p); p.b->blobTriAt = tri_at(p); p.b->blobIdxAt = idx_at(p); }
-    if (e != hipSuccess) return fail_hip(&c, e, "top-level build");
+    if (e != hipSuccess) {
+        if (newCopy) (void)hipStreamSynchronize(c.stream);         // (the launches may still write the new copy, freed on return)
+        return fail_hip(&c, e, "top-level build");
+    }
+
+    // ---- commit
+    if (newBlob) c.blobDev = std::move(newCopy);                   // (frees the old copy)
+    for (Blas* b : adopting) { b->nodes.reset(); b->tris.reset(); b->idx.reset(); b->inBlob = true; }
+    for (const auto& p : P.pieces) if (p.b->inBlob) { p.b->blobNodeAt = P.node_at(p); p.b->blobTriAt = P.tri_at(p); p.b->blobIdxAt = P.idx_at(p); }
     c.tlasHeaderPending = true;
-    c.tlasNodeReserve = tlasNodeCap;
-    c.blob.base = (const f4v*)blob;
-    c.blob.nodeOff16 = (uint32_t)(nodeAt / 16); c.blob.triOff16 = (uint32_t)(triAt / 16); c.blob.idxOff16 = (uint32_t)(idxAt / 16);
-    c.blob.instOff16 = (uint32_t)(instAt / 16); c.blob.leafInstOff16 = (uint32_t)(leafAt / 16); c.blob.enterOff16 = (uint32_t)(enterAt / 16);
-    c.blob.instCount = count; c.blob.nodeCount = blobNodes; c.blob.triCount = blobTris; c.blob.bytes = (uint32_t)total;
-    c.tlas.triangleCount = tris;
-    c.tlasBlasIds = pieceIds;
-    if (objectEnd != c.tlasObjectEnd || count != c.tlasValidatedCount || bindingHash != c.tlasBindingHash) c.validated = false;     // same instances of the same bottom levels over the same objects: nothing new to check
-    c.tlasObjectEnd = objectEnd; c.tlasValidatedCount = count; c.tlasBindingHash = bindingHash;
-    if (lightHash != c.tlasLightHash) c.lightListValid = false;
-    c.tlasLightHash = lightHash;
+    c.tlasNodeReserve = P.tlasNodeCap;
+    SceneRefs& r = c.scene;
+    r.instances = c.tlas.instances.data(); r.instanceCount = count; r.triangleCount = P.tris;
+    r.blob.base = (const f4v*)c.blobDev.data();
+    r.blob.nodeOff16 = (uint32_t)(P.nodeAt / 16); r.blob.triOff16 = (uint32_t)(P.triAt / 16); r.blob.idxOff16 = (uint32_t)(P.idxAt / 16);
+    r.blob.instOff16 = (uint32_t)(P.instAt / 16); r.blob.leafInstOff16 = (uint32_t)(P.leafAt / 16); r.blob.enterOff16 = (uint32_t)(P.enterAt / 16);
+    r.blob.instCount = count; r.blob.nodeCount = P.blobNodes; r.blob.triCount = P.blobTris; r.blob.bytes = (uint32_t)P.total;
+    r.blasTable = dTable; r.blasTableCount = (uint32_t)P.table.size(); r.instSource = dSrc; r.blasTableMaxTris = 0;
+    for (const BlasEntry& te : P.table) r.blasTableMaxTris = std::max(r.blasTableMaxTris, te.triCount);
+    c.tlasBlasIds = P.pieceIds;
+    if (P.objectEnd != c.tlasObjectEnd || count != c.tlasValidatedCount || P.bindingHash != c.tlasBindingHash) c.validated = false;     // same instances of the same bottom levels over the same objects: nothing new to check
+    c.tlasObjectEnd = P.objectEnd; c.tlasValidatedCount = count; c.tlasBindingHash = P.bindingHash;
+    if (P.lightHash != c.tlasLightHash) c.lightListValid = false;
+    c.tlasLightHash = P.lightHash;
     // the same instances of the same bottom levels over the same objects (a dynamic frame's rebuild after a refit): the verdict of the
     // shared-geometry check still holds, and with it the frame's normal records (drop_tlas had put them aside with the old top level)
     c.normalsShared = c.validated && c.sharedVerdict;
@@ -593,7 +548,7 @@ int pt_share_scene(PtContext* ctx, PtContext* source)
     if (!ctx || !source || ctx == source) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c; Context& s = source->c;
     API_ARG(&c, c.device == s.device, "both contexts must live on the same device");
-    API_ARG(&c, c.borrowers == 0, "other contexts view this context's scene");
+    API_ARG(&c, c.viewers.empty(), "other contexts view this context's scene");
     API_ARG(&c, !s.sceneOwner, "the source views another context's scene itself: share from the owner");
     API_HIP(&c, hipSetDevice(c.device));
     API_HIP(&c, hipStreamSynchronize(s.stream));
@@ -602,17 +557,14 @@ int pt_share_scene(PtContext* ctx, PtContext* source)
     if (st != PT_OK) return fail(&c, st, s.lastError);
     if (!s.haveTlas) return fail(&c, PT_ERROR_NOT_READY, "the source context has no top-level acceleration structure");
     if (c.sceneOwner) detach_from_owner(c);
-    else { API_HIP(&c, materialise_adopted(c)); free_tlas(c.tlas); if (c.blobDev) hipFree(c.blobDev); }
-    c.blobDev = nullptr; c.blobCapacity = 0;
-    c.tlas = Tlas();
-    c.tlas.instances = s.tlas.instances; c.tlas.instanceCount = s.tlas.instanceCount; c.tlas.triangleCount = s.tlas.triangleCount;   // views
-    c.blob = s.blob;
-    c.blasTableDev = s.blasTableDev; c.blasTableCount = s.blasTableCount; c.blasTableMaxTris = s.blasTableMaxTris; c.instSourceDev = s.instSourceDev; c.normalsShared = false;
+    else { API_HIP(&c, materialise_adopted(c)); c.tlas = Tlas(); c.blobDev.reset(); }
+    drop_tlas(c);
+    c.scene = s.scene;                                                      // views of the owner's
     c.tlasObjectEnd = s.tlasObjectEnd; c.maxBlasDepth = s.maxBlasDepth;
     c.heapHost = s.heapHost; c.heapDirty = true;                            // the descriptor table is copied (each context uploads its own)
     c.objects = s.objects; c.objectCount = s.objectCount; c.instanceData = s.instanceData; c.instanceDataCount = s.instanceDataCount;
-    c.sceneOwner = &s; s.borrowers++; s.viewers.push_back(&c);
-    c.tlasBlasIds.clear(); c.tlasHeaderPending = false; c.validated = false;
+    c.sceneOwner = &s; s.viewers.push_back(&c);
+    c.tlasHeaderPending = false; c.validated = false;
     c.haveTlas = true;
     return PT_OK;
 }
@@ -626,18 +578,18 @@ int pt_get_accel_stats(PtContext* ctx, PtAccelStats* out)
     int st = poll_tlas_header(c, true);
     if (st != PT_OK) return st;
     memset(out, 0, sizeof *out);
-    out->InstanceCount = c.tlas.instanceCount;
+    out->InstanceCount = c.scene.instanceCount;
     out->BottomLevelCount = (uint32_t)c.blas.size();
-    out->TriangleCount = c.tlas.triangleCount;
+    out->TriangleCount = c.scene.triangleCount;
     out->NodeSizeBytes = sizeof(WideNode); out->TriangleSizeBytes = sizeof(TriPacket);
-    uint64_t nb = (uint64_t)wide_node_capacity(c.tlas.instanceCount) * sizeof(WideNode), tb = 0;
+    uint64_t nb = (uint64_t)wide_node_capacity(c.scene.instanceCount) * sizeof(WideNode), tb = 0;
     for (auto& kv : c.blas) { nb += (uint64_t)kv.second.nodeCount * sizeof(WideNode); tb += (uint64_t)kv.second.triCount * sizeof(TriPacket); out->MaxBottomLevelDepth = std::max(out->MaxBottomLevelDepth, kv.second.depth); }
-    out->BlobBytes = c.sceneOwner ? 0 : c.blob.bytes;          // a view holds no memory of its own
+    out->BlobBytes = c.sceneOwner ? 0 : c.scene.blob.bytes;          // a view holds no memory of its own
     out->SharedScene = c.sceneOwner ? 1u : 0u;
     out->NormalRecords = c.normalsShared ? 1u : 0u;
-    out->RoundObjectsInLds = round_objects_in_lds(c, c.objectCount, c.shadeGeomDev != nullptr);
-    out->RoundRecordsInLds = round_records_in_lds(c, c.objectCount, c.shadeGeomDev != nullptr);
-    if (c.tlasHeaderHost && !c.tlasHeaderPending) out->TopLevelDepth = c.tlasHeaderHost->depth;
+    out->RoundObjectsInLds = round_objects_in_lds(c, c.objectCount, (bool)c.shadeGeomDev);
+    out->RoundRecordsInLds = round_records_in_lds(c, c.objectCount, (bool)c.shadeGeomDev);
+    if (c.tlasHeaderHost && !c.tlasHeaderPending) out->TopLevelDepth = c.tlasHeaderHost.data()->depth;
     out->NodeBytes = nb; out->TriangleBytes = tb;
     for (auto& kv : c.blas) if (!kv.second.inBlob) out->OwnedBottomLevelBytes += (uint64_t)kv.second.nodeCount * sizeof(WideNode) + (uint64_t)kv.second.triCount * (sizeof(TriPacket) + 16);
     return PT_OK;
@@ -723,27 +675,24 @@ static int validate_scene(Context& c)
     if (c.tlasObjectEnd > c.objectCount)
         return fail(&c, PT_ERROR_INVALID_ARGUMENT, "InstanceID + geometry count of an instance reaches ObjectData[" + std::to_string(c.tlasObjectEnd - 1)
                     + "] but only " + std::to_string(c.objectCount) + " objects are bound (pt_set_object_data)");
-    if (c.instanceData && c.instanceDataCount < c.tlas.instanceCount)
+    if (c.instanceData && c.instanceDataCount < c.scene.instanceCount)
         return fail(&c, PT_ERROR_INVALID_ARGUMENT, "InstanceData holds fewer records than the top level has instances");
     uint32_t sharedMismatch = 0;
     if (c.objectCount) {
-        if (!c.validateDev) API_HIP(&c, hipMalloc((void**)&c.validateDev, sizeof(uint32_t) * 8));
-        if (c.objectCount > c.shadeGeomCap) {                // the resolved-geometry table the same kernel fills (grow-only; kernels in flight may read the old one)
+        API_HIP(&c, c.validateDev.reserve(8));
+        if (c.objectCount > c.shadeGeomDev.capacity()) {    // the resolved-geometry table the same kernel fills (grow-only; kernels in flight may read the old one)
             API_HIP(&c, hipStreamSynchronize(c.stream));
-            if (c.shadeGeomDev) hipFree(c.shadeGeomDev);
-            if (c.shadeTexDev) hipFree(c.shadeTexDev);
-            c.shadeGeomDev = nullptr; c.shadeTexDev = nullptr; c.shadeGeomCap = 0;
-            API_HIP(&c, hipMalloc((void**)&c.shadeTexDev, sizeof(HeapEntry) * kTextureSlots * (size_t)c.objectCount));
-            API_HIP(&c, hipMalloc((void**)&c.shadeGeomDev, sizeof(ShadeGeom) * c.objectCount));
-            c.shadeGeomCap = c.objectCount;
+            c.shadeGeomDev.reset(); c.shadeTexDev.reset();
+            API_HIP(&c, c.shadeTexDev.reserve(kTextureSlots * (size_t)c.objectCount));
+            API_HIP(&c, c.shadeGeomDev.reserve(c.objectCount));     // last: the grow decision reads its capacity
         }
-        API_HIP(&c, hipMemsetAsync(c.validateDev, 0, sizeof(uint32_t) * 8, c.stream));
-        API_HIP(&c, launch_validate_objects(c.stream, c.objects, c.objectCount, c.heapDev, heapCount, c.validateDev, c.shadeGeomDev, c.shadeTexDev));
+        API_HIP(&c, hipMemsetAsync(c.validateDev.data(), 0, sizeof(uint32_t) * 8, c.stream));
+        API_HIP(&c, launch_validate_objects(c.stream, c.objects, c.objectCount, c.heapDev.data(), heapCount, c.validateDev.data(), c.shadeGeomDev.data(), c.shadeTexDev.data()));
         // do all instances of a bottom level name the same vertex data? (the frame's normal records are made from the first one's objects)
-        if (c.blasTableDev && c.instSourceDev)
-            API_HIP(&c, launch_check_shared_geometry(c.stream, c.instSourceDev, c.blasTableDev, c.blob.instCount, c.shadeGeomDev, c.validateDev));
+        if (c.scene.blasTable && c.scene.instSource)
+            API_HIP(&c, launch_check_shared_geometry(c.stream, c.scene.instSource, c.scene.blasTable, c.scene.blob.instCount, c.shadeGeomDev.data(), c.validateDev.data()));
         uint32_t r[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-        API_HIP(&c, hipMemcpyAsync(r, c.validateDev, sizeof r, hipMemcpyDeviceToHost, c.stream));
+        API_HIP(&c, hipMemcpyAsync(r, c.validateDev.data(), sizeof r, hipMemcpyDeviceToHost, c.stream));
         API_HIP(&c, hipStreamSynchronize(c.stream));
         sharedMismatch = r[4];
         if (r[0]) {
@@ -753,7 +702,7 @@ static int validate_scene(Context& c)
         }
     }
     c.validated = true; c.validatedObjects = c.objects; c.validatedObjectCount = c.objectCount;
-    c.sharedVerdict = c.objectCount != 0 && c.blasTableDev != nullptr && sharedMismatch == 0;
+    c.sharedVerdict = c.objectCount != 0 && c.scene.blasTable != nullptr && sharedMismatch == 0;
     c.normalsShared = c.sharedVerdict;
     return PT_OK;
 }
@@ -767,7 +716,7 @@ static int make_views(Context& c, uint32_t width, uint32_t height, SceneView& sv
     if (s != PT_OK) return s;
     if (!c.haveTlas) return fail(&c, PT_ERROR_NOT_READY, "no top-level acceleration structure: call pt_build_top_level first");
     if (needFrameInputs && (!c.haveCamera || !c.haveSceneData)) return fail(&c, PT_ERROR_NOT_READY, "camera / scene data not set");
-    if (!c.objects && c.tlas.instanceCount) return fail(&c, PT_ERROR_NOT_READY, "object data not set");
+    if (!c.objects && c.scene.instanceCount) return fail(&c, PT_ERROR_NOT_READY, "object data not set");
     s = upload_heap(c);
     if (s != PT_OK) return s;
     s = validate_scene(c);
@@ -778,11 +727,11 @@ static int make_views(Context& c, uint32_t width, uint32_t height, SceneView& sv
         API_ARG(&c, c.heapHost[d].kind == (c.sceneData.IsEnvironmentLightTextureCubeMap ? kKindTextureCube : kKindTexture2D),
                 "SceneData.EnvironmentLightTextureDescriptor is not the kind of texture IsEnvironmentLightTextureCubeMap says");
     }
-    sv.accel.instances = c.tlas.instances; sv.accel.instanceCount = c.tlas.instanceCount;
-    sv.objects = c.objects; sv.objectCount = c.objectCount; sv.shadeGeom = c.shadeGeomDev; sv.shadeTex = c.shadeTexDev;
+    sv.accel.instances = c.scene.instances; sv.accel.instanceCount = c.scene.instanceCount;
+    sv.objects = c.objects; sv.objectCount = c.objectCount; sv.shadeGeom = c.shadeGeomDev.data(); sv.shadeTex = c.shadeTexDev.data();
     sv.instanceData = c.instanceData;
-    sv.heap = c.heapDev; sv.heapCount = (uint32_t)c.heapHost.size();
-    sv.srgbLut = c.srgbLutDev;
+    sv.heap = c.heapDev.data(); sv.heapCount = (uint32_t)c.heapHost.size();
+    sv.srgbLut = c.srgbLutDev.data();
     fv.width = width; fv.height = height;
     fv.rankIndex = c.sharding.RankIndex; fv.rankCount = c.sharding.RankCount; fv.bandHeight = c.sharding.BandHeight;
     pt_local_rows(&c.sharding, height, &fv.localRows);
@@ -869,7 +818,7 @@ int pt_reset_counters(PtContext* ctx)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     API_HIP(&ctx->c, hipSetDevice(ctx->c.device));
-    API_HIP(&ctx->c, hipMemsetAsync(ctx->c.counters, 0, sizeof(DeviceCounters), ctx->c.stream));
+    API_HIP(&ctx->c, hipMemsetAsync(ctx->c.counters.data(), 0, sizeof(DeviceCounters), ctx->c.stream));
     return PT_OK;
 }
 
@@ -879,7 +828,7 @@ int pt_get_counters(PtContext* ctx, PtCounters* out)
     Context& c = ctx->c;
     API_HIP(&c, hipSetDevice(c.device));
     DeviceCounters d;
-    API_HIP(&c, hipMemcpyAsync(&d, c.counters, sizeof d, hipMemcpyDeviceToHost, c.stream));
+    API_HIP(&c, hipMemcpyAsync(&d, c.counters.data(), sizeof d, hipMemcpyDeviceToHost, c.stream));
     API_HIP(&c, hipStreamSynchronize(c.stream));
     memset(out, 0, sizeof *out);
     out->PrimaryRays = d.primaryRays; out->SecondaryRays = d.secondaryRays;
@@ -897,7 +846,7 @@ int pt_debug_read_mismatch(PtContext* ctx, float* out16)
     Context& c = ctx->c;
     API_HIP(&c, hipSetDevice(c.device));
     DeviceCounters d;
-    API_HIP(&c, hipMemcpyAsync(&d, c.counters, sizeof d, hipMemcpyDeviceToHost, c.stream));
+    API_HIP(&c, hipMemcpyAsync(&d, c.counters.data(), sizeof d, hipMemcpyDeviceToHost, c.stream));
     API_HIP(&c, hipStreamSynchronize(c.stream));
     memcpy(out16, d.mismatchRay, sizeof(float) * 16);
     return PT_OK;
@@ -912,7 +861,7 @@ int pt_debug_download_blob(PtContext* ctx, void* host_dst, uint64_t capacity_byt
     int st = poll_tlas_header(c, true);
     if (st != PT_OK) return st;
     if (!c.haveTlas) return fail(&c, PT_ERROR_NOT_READY, "no top-level acceleration structure");
-    const BlobView& b = c.blob;
+    const BlobView& b = c.scene.blob;
     *out_layout = PtBlobLayout{ b.instOff16, b.nodeOff16, b.triOff16, b.leafInstOff16, b.instCount, b.nodeCount, b.triCount, b.bytes };
     if (host_dst) {
         API_ARG(&c, capacity_bytes >= b.bytes, "host buffer smaller than the blob");
@@ -929,13 +878,12 @@ int pt_debug_trace_ray(PtContext* ctx, const PtRayDesc* host_ray, uint32_t* host
     SceneView sv; FrameView fv; memset(&sv, 0, sizeof sv); memset(&fv, 0, sizeof fv);
     int s = make_views(c, 1, 1, sv, fv, false);
     if (s != PT_OK) return s;
-    uint32_t* dev = nullptr;
-    API_HIP(&c, hipMalloc((void**)&dev, sizeof(uint32_t) * (log_words ? log_words : 4)));
-    hipError_t e = hipMemsetAsync(dev, 0, sizeof(uint32_t) * log_words, c.stream);
-    if (e == hipSuccess) e = launch_debug_trace(c, sv, (const float*)host_ray, dev, log_words);
-    if (e == hipSuccess) e = hipMemcpyAsync(host_log, dev, sizeof(uint32_t) * log_words, hipMemcpyDeviceToHost, c.stream);
+    DeviceBuffer<uint32_t> dev;
+    API_HIP(&c, dev.reserve(log_words ? log_words : 4));
+    hipError_t e = hipMemsetAsync(dev.data(), 0, sizeof(uint32_t) * log_words, c.stream);
+    if (e == hipSuccess) e = launch_debug_trace(c, sv, (const float*)host_ray, dev.data(), log_words);
+    if (e == hipSuccess) e = hipMemcpyAsync(host_log, dev.data(), sizeof(uint32_t) * log_words, hipMemcpyDeviceToHost, c.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    hipFree(dev);
     if (e != hipSuccess) return fail_hip(&c, e, "debug trace");
     return PT_OK;
 }
@@ -963,8 +911,8 @@ int pt_get_kernel_timing(PtContext* ctx, float* extend_ms, float* shade_ms, uint
     API_HIP(&c, hipStreamSynchronize(c.stream));
     float te = 0.0f, ts = 0.0f;
     if (c.timing) {
-        for (uint32_t k = 0; k < c.nExtend && 2 * k + 1 < c.evExtend.size(); k++) { float ms = 0; hipEventElapsedTime(&ms, c.evExtend[2 * k], c.evExtend[2 * k + 1]); te += ms; }
-        for (uint32_t k = 0; k < c.nShade && 2 * k + 1 < c.evShade.size(); k++) { float ms = 0; hipEventElapsedTime(&ms, c.evShade[2 * k], c.evShade[2 * k + 1]); ts += ms; }
+        for (uint32_t k = 0; k < c.nExtend && 2 * k + 1 < c.evExtend.size(); k++) { float ms = 0; hipEventElapsedTime(&ms, c.evExtend[2 * k].get(), c.evExtend[2 * k + 1].get()); te += ms; }
+        for (uint32_t k = 0; k < c.nShade && 2 * k + 1 < c.evShade.size(); k++) { float ms = 0; hipEventElapsedTime(&ms, c.evShade[2 * k].get(), c.evShade[2 * k + 1].get()); ts += ms; }
     }
     if (extend_ms) *extend_ms = te;
     if (shade_ms) *shade_ms = ts;
@@ -981,7 +929,7 @@ int pt_get_round_timing(PtContext* ctx, float* round_ms, uint32_t* round_launche
     API_HIP(&c, hipStreamSynchronize(c.stream));
     float t = 0.0f;
     if (c.timing)
-        for (uint32_t k = 0; k < c.nRound && 2 * k + 1 < c.evRound.size(); k++) { float ms = 0; hipEventElapsedTime(&ms, c.evRound[2 * k], c.evRound[2 * k + 1]); t += ms; }
+        for (uint32_t k = 0; k < c.nRound && 2 * k + 1 < c.evRound.size(); k++) { float ms = 0; hipEventElapsedTime(&ms, c.evRound[2 * k].get(), c.evRound[2 * k + 1].get()); t += ms; }
     if (round_ms) *round_ms = t;
     if (round_launches) *round_launches = c.nRound;
     return PT_OK;

@@ -851,140 +851,125 @@ __global__ void k_scatter_tris(const TriPacket* __restrict__ src, const uint32_t
 // ---------------------------------------------------------------------------------------------
 static inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
-#define BVH_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { err = e_; goto fail; } } while (0)
+#define BVH_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
 
-void TreeBuffers::release()
-{
-    void* ptrs[] = { boxLo, boxHi, bounds, keys, keysSorted, index, indexSorted, sortTemp, leafKeys, leafLo, leafHi, children, parentInternal,
-                     parentLeaf, nodeLo, nodeHi, arrival, binaryRootOf, slotRefs, leafDst, slotOfPrim, header, dp, collapseState };
-    for (void* p : ptrs) if (p) hipFree(p);
-    *this = TreeBuffers();
-}
-
-// (re)allocates the build buffers for nitems items in leaves of leafSize; grow-only, so a rebuild of the same size allocates nothing
+// (re)allocates the build buffers for nitems items in leaves of leafSize; grow-only, so a rebuild of the same size allocates nothing. The old
+// buffers are freed first; the new ones replace them only when all were allocated.
 static hipError_t ensure_tree_buffers(TreeBuffers& b, uint32_t nitems, uint32_t leafSize, bool withPrimSlots)
 {
     const uint32_t nleaves = cdiv(nitems, leafSize), nint = nleaves > 1 ? nleaves - 1 : 1, nwide = wide_node_capacity(nleaves);
-    if (b.header && nitems <= b.itemCapacity && nleaves <= b.leafCapacity && (!withPrimSlots || b.slotOfPrim)) return hipSuccess;
-    b.release();
-    hipError_t err = hipSuccess;
+    if (b.header && nitems <= b.boxLo.capacity() && nleaves <= b.leafLo.capacity() && (!withPrimSlots || b.slotOfPrim)) return hipSuccess;
+    b = TreeBuffers();
+    TreeBuffers t;
     const size_t ni = nitems ? nitems : 1, nl = nleaves ? nleaves : 1;
     size_t tmp = 0;
-    BVH_CHECK(hipMalloc((void**)&b.boxLo, sizeof(float4) * ni));
-    BVH_CHECK(hipMalloc((void**)&b.boxHi, sizeof(float4) * ni));
-    BVH_CHECK(hipMalloc((void**)&b.bounds, sizeof(uint32_t) * 8));
-    BVH_CHECK(hipMalloc((void**)&b.keys, sizeof(uint64_t) * ni));
-    BVH_CHECK(hipMalloc((void**)&b.keysSorted, sizeof(uint64_t) * ni));
-    BVH_CHECK(hipMalloc((void**)&b.index, sizeof(uint32_t) * ni));
-    BVH_CHECK(hipMalloc((void**)&b.indexSorted, sizeof(uint32_t) * ni));
-    BVH_CHECK(rocprim::radix_sort_pairs(nullptr, tmp, b.keys, b.keysSorted, b.index, b.indexSorted, ni, 0, 63, (hipStream_t)nullptr));
-    b.sortTempBytes = tmp;
-    BVH_CHECK(hipMalloc(&b.sortTemp, tmp ? tmp : 16));
-    BVH_CHECK(hipMalloc((void**)&b.leafKeys, sizeof(uint64_t) * nl));
-    BVH_CHECK(hipMalloc((void**)&b.leafLo, sizeof(float4) * nl));
-    BVH_CHECK(hipMalloc((void**)&b.leafHi, sizeof(float4) * nl));
-    BVH_CHECK(hipMalloc((void**)&b.children, sizeof(int2) * nint));
-    BVH_CHECK(hipMalloc((void**)&b.parentInternal, sizeof(int) * nint));
-    BVH_CHECK(hipMalloc((void**)&b.parentLeaf, sizeof(int) * nl));
-    BVH_CHECK(hipMalloc((void**)&b.nodeLo, sizeof(float4) * nint));
-    BVH_CHECK(hipMalloc((void**)&b.nodeHi, sizeof(float4) * nint));
-    BVH_CHECK(hipMalloc((void**)&b.arrival, sizeof(uint32_t) * nint));
-    BVH_CHECK(hipMemset(b.arrival, 0, sizeof(uint32_t) * nint));
-    BVH_CHECK(hipMalloc((void**)&b.binaryRootOf, sizeof(int) * nwide));
-    BVH_CHECK(hipMalloc((void**)&b.slotRefs, sizeof(int) * 8 * nwide));
-    BVH_CHECK(hipMalloc((void**)&b.leafDst, sizeof(uint32_t) * nl));
-    if (withPrimSlots) BVH_CHECK(hipMalloc((void**)&b.slotOfPrim, sizeof(uint32_t) * ni));
-    BVH_CHECK(hipMalloc((void**)&b.header, sizeof(WideHeader)));
-    BVH_CHECK(hipMalloc(&b.collapseState, 32));
-    BVH_CHECK(hipMalloc(&b.dp, sizeof(DpNode) * nint));
-    b.itemCapacity = (uint32_t)ni; b.leafCapacity = (uint32_t)nl;
+    BVH_CHECK(t.boxLo.reserve(ni));
+    BVH_CHECK(t.boxHi.reserve(ni));
+    BVH_CHECK(t.bounds.reserve(8));
+    BVH_CHECK(t.keys.reserve(ni));
+    BVH_CHECK(t.keysSorted.reserve(ni));
+    BVH_CHECK(t.index.reserve(ni));
+    BVH_CHECK(t.indexSorted.reserve(ni));
+    BVH_CHECK(rocprim::radix_sort_pairs(nullptr, tmp, t.keys.data(), t.keysSorted.data(), t.index.data(), t.indexSorted.data(), ni, 0, 63, (hipStream_t)nullptr));
+    t.sortTempBytes = tmp;
+    BVH_CHECK(t.sortTemp.reserve(tmp ? tmp : 16));
+    BVH_CHECK(t.leafKeys.reserve(nl));
+    BVH_CHECK(t.leafLo.reserve(nl));
+    BVH_CHECK(t.leafHi.reserve(nl));
+    BVH_CHECK(t.children.reserve(nint));
+    BVH_CHECK(t.parentInternal.reserve(nint));
+    BVH_CHECK(t.parentLeaf.reserve(nl));
+    BVH_CHECK(t.nodeLo.reserve(nint));
+    BVH_CHECK(t.nodeHi.reserve(nint));
+    BVH_CHECK(t.arrival.reserve(nint));
+    BVH_CHECK(hipMemset(t.arrival.data(), 0, sizeof(uint32_t) * nint));
+    BVH_CHECK(t.binaryRootOf.reserve(nwide));
+    BVH_CHECK(t.slotRefs.reserve(8 * (size_t)nwide));
+    BVH_CHECK(t.leafDst.reserve(nl));
+    if (withPrimSlots) BVH_CHECK(t.slotOfPrim.reserve(ni));
+    BVH_CHECK(t.header.reserve(1));
+    BVH_CHECK(t.collapseState.reserve(32));
+    BVH_CHECK(t.dp.reserve(sizeof(DpNode) * nint));
+    b = std::move(t);
     return hipSuccess;
-fail:
-    b.release();
-    return err;
 }
 
 // items in b.boxLo/boxHi/bounds -> sorted -> binary tree -> wide nodes in `nodes` (capacity: wide_node_capacity(nleaves)); no sync
 static hipError_t build_wide_tree(TreeBuffers& b, uint32_t nitems, uint32_t leafSize, uint32_t maxLeafItems, float costItem, bool cubicCells, bool largeFirst, WideNode* nodes, float* rootBounds, hipStream_t stream)
 {
-    hipError_t err = hipSuccess;
     const uint32_t nleaves = cdiv(nitems, leafSize);
     if (nitems) {
-        k_morton<<<cdiv(nitems, 256), 256, 0, stream>>>(b.boxLo, b.boxHi, nitems, b.bounds, b.keys, b.index, cubicCells, largeFirst);
+        k_morton<<<cdiv(nitems, 256), 256, 0, stream>>>(b.boxLo.data(), b.boxHi.data(), nitems, b.bounds.data(), b.keys.data(), b.index.data(), cubicCells, largeFirst);
         size_t tmp = b.sortTempBytes;
-        BVH_CHECK(rocprim::radix_sort_pairs(b.sortTemp, tmp, b.keys, b.keysSorted, b.index, b.indexSorted, nitems, 0, 63, stream));
-        k_leaves<<<cdiv(nleaves, 256), 256, 0, stream>>>(b.keysSorted, b.indexSorted, b.boxLo, b.boxHi, nitems, nleaves, leafSize, b.leafKeys, b.leafLo, b.leafHi);
-        if (nleaves > 1) k_karras<<<cdiv(nleaves - 1, 256), 256, 0, stream>>>(b.leafKeys, (int)nleaves, b.children, b.parentInternal, b.parentLeaf);
-        k_refit<<<cdiv(nleaves, 256), 256, 0, stream>>>((int)nleaves, b.leafLo, b.leafHi, b.children, b.parentInternal, b.parentLeaf, b.nodeLo, b.nodeHi, b.arrival, rootBounds,
-                                                     (DpNode*)b.dp, nitems, leafSize, maxLeafItems, costItem);
+        BVH_CHECK(rocprim::radix_sort_pairs(b.sortTemp.data(), tmp, b.keys.data(), b.keysSorted.data(), b.index.data(), b.indexSorted.data(), nitems, 0, 63, stream));
+        k_leaves<<<cdiv(nleaves, 256), 256, 0, stream>>>(b.keysSorted.data(), b.indexSorted.data(), b.boxLo.data(), b.boxHi.data(), nitems, nleaves, leafSize, b.leafKeys.data(), b.leafLo.data(), b.leafHi.data());
+        if (nleaves > 1) k_karras<<<cdiv(nleaves - 1, 256), 256, 0, stream>>>(b.leafKeys.data(), (int)nleaves, b.children.data(), b.parentInternal.data(), b.parentLeaf.data());
+        k_refit<<<cdiv(nleaves, 256), 256, 0, stream>>>((int)nleaves, b.leafLo.data(), b.leafHi.data(), b.children.data(), b.parentInternal.data(), b.parentLeaf.data(), b.nodeLo.data(), b.nodeHi.data(),
+                                                     b.arrival.data(), rootBounds, (DpNode*)b.dp.data(), nitems, leafSize, maxLeafItems, costItem);
     } else {
         k_empty_bounds<<<1, 64, 0, stream>>>(rootBounds);
     }
     {
         CollapseArgs A;
-        A.dp = (const DpNode*)b.dp;
-        A.children = b.children; A.nodeLo = b.nodeLo; A.nodeHi = b.nodeHi; A.leafLo = b.leafLo; A.leafHi = b.leafHi;
+        A.dp = (const DpNode*)b.dp.data();
+        A.children = b.children.data(); A.nodeLo = b.nodeLo.data(); A.nodeHi = b.nodeHi.data(); A.leafLo = b.leafLo.data(); A.leafHi = b.leafHi.data();
         A.nleaves = nleaves; A.nitems = nitems; A.leafSize = leafSize; A.nodes = nodes; A.nodeCapacity = wide_node_capacity(nleaves);
-        A.binaryRootOf = b.binaryRootOf; A.slotRefs = b.slotRefs; A.leafDst = b.leafDst; A.header = b.header;
+        A.binaryRootOf = b.binaryRootOf.data(); A.slotRefs = b.slotRefs.data(); A.leafDst = b.leafDst.data(); A.header = b.header.data();
         if (nleaves <= kSingleGroupCollapseLeaves) k_collapse<<<1, 1024, 0, stream>>>(A);
         else {
-            CollapseState* st = (CollapseState*)b.collapseState;
+            CollapseState* st = (CollapseState*)b.collapseState.data();
             k_collapse_begin<<<1, 1, 0, stream>>>(A, st);
             for (uint32_t level = 0; level < kLevelLaunches; level++) k_collapse_level<<<2048, 64, 0, stream>>>(A, st);
             k_collapse_end<<<1, 1, 0, stream>>>(A, st);
         }
     }
-    BVH_CHECK(hipGetLastError());
-fail:
-    return err;
+    return hipGetLastError();
 }
 
 hipError_t build_blas_device(const PtGeometryDesc* geoms, uint32_t ngeoms, bool allowUpdate, hipStream_t stream, Blas& out)
 {
-    hipError_t err = hipSuccess;
     uint32_t ntris = 0;
     for (uint32_t g = 0; g < ngeoms; g++) ntris += geoms[g].IndexCount / 3;
     const uint32_t leafSize = blas_leaf_tris(ntris);
     out.triCount = ntris;
     out.leafCount = cdiv(ntris, leafSize);
     const uint32_t capacity = wide_node_capacity(out.leafCount);
-    TriPacket* unsorted = nullptr; uint4* unsortedIdx = nullptr;
+    DeviceBuffer<TriPacket> unsorted; DeviceBuffer<uint4> unsortedIdx;
     WideHeader hdr{};
-    BVH_CHECK(ensure_tree_buffers(out.tree, ntris, leafSize, true));
-    BVH_CHECK(hipMalloc((void**)&out.nodes, sizeof(WideNode) * capacity));
-    BVH_CHECK(hipMalloc((void**)&out.tris, sizeof(TriPacket) * (ntris ? ntris : 1)));
-    BVH_CHECK(hipMalloc((void**)&out.idx, sizeof(uint4) * (ntris ? ntris : 1)));
-    BVH_CHECK(hipMalloc((void**)&out.rootBounds, sizeof(float) * 8));
+    TreeBuffers& t = out.tree;
+    BVH_CHECK(ensure_tree_buffers(t, ntris, leafSize, true));
+    BVH_CHECK(out.nodes.reserve(capacity));
+    BVH_CHECK(out.tris.reserve(ntris ? ntris : 1));
+    BVH_CHECK(out.idx.reserve(ntris ? ntris : 1));
+    BVH_CHECK(out.rootBounds.reserve(8));
     if (ntris) {
-        BVH_CHECK(hipMalloc((void**)&unsorted, sizeof(TriPacket) * ntris));
-        BVH_CHECK(hipMalloc((void**)&unsortedIdx, sizeof(uint4) * ntris));
-        k_init_bounds<<<1, 64, 0, stream>>>(out.tree.bounds);
+        BVH_CHECK(unsorted.reserve(ntris));
+        BVH_CHECK(unsortedIdx.reserve(ntris));
+        k_init_bounds<<<1, 64, 0, stream>>>(t.bounds.data());
         uint32_t off = 0;
         for (uint32_t g = 0; g < ngeoms; g++) {
             uint32_t np = geoms[g].IndexCount / 3;
             if (np) k_tri_setup<<<cdiv(np, 256), 256, 0, stream>>>((const uint8_t*)geoms[g].VertexBuffer, geoms[g].VertexStride,
                                                                    geoms[g].IndexBuffer, geoms[g].IndexStride, np, off, g, geoms[g].Flags,
-                                                                   unsorted, nullptr, out.tree.boxLo, out.tree.boxHi, out.tree.bounds, unsortedIdx);
+                                                                   unsorted.data(), nullptr, t.boxLo.data(), t.boxHi.data(), t.bounds.data(), unsortedIdx.data());
             off += np;
         }
         BVH_CHECK(hipGetLastError());
     }
-    BVH_CHECK(build_wide_tree(out.tree, ntris, leafSize, kMaxLeafTris, kCostTriangle, true, false, out.nodes, out.rootBounds, stream));
-    if (ntris) k_scatter_tris<<<cdiv(ntris, 256), 256, 0, stream>>>(unsorted, out.tree.indexSorted, out.tree.leafDst, ntris, leafSize, out.tris, out.tree.slotOfPrim, unsortedIdx, out.idx);
-    BVH_CHECK(hipMemcpyAsync(&hdr, out.tree.header, sizeof hdr, hipMemcpyDeviceToHost, stream));
+    BVH_CHECK(build_wide_tree(t, ntris, leafSize, kMaxLeafTris, kCostTriangle, true, false, out.nodes.data(), out.rootBounds.data(), stream));
+    if (ntris) k_scatter_tris<<<cdiv(ntris, 256), 256, 0, stream>>>(unsorted.data(), t.indexSorted.data(), t.leafDst.data(), ntris, leafSize, out.tris.data(), t.slotOfPrim.data(),
+                                                                    unsortedIdx.data(), out.idx.data());
+    BVH_CHECK(hipMemcpyAsync(&hdr, t.header.data(), sizeof hdr, hipMemcpyDeviceToHost, stream));
     BVH_CHECK(hipStreamSynchronize(stream));     // build is a load-time operation (reference: CommandList::End after the BLAS build, Scene.ixx:184-188)
     out.nodeCount = hdr.nodeCount; out.depth = hdr.depth; out.buildError = hdr.error != 0;
     if (hdr.nodeCount < capacity && !hdr.error) {  // the collapse needed fewer nodes than the worst case (it always does): give the rest back
-        WideNode* exact = nullptr;
-        BVH_CHECK(hipMalloc((void**)&exact, sizeof(WideNode) * hdr.nodeCount));
-        BVH_CHECK(hipMemcpy(exact, out.nodes, sizeof(WideNode) * hdr.nodeCount, hipMemcpyDeviceToDevice));
-        hipFree(out.nodes); out.nodes = exact;
+        DeviceBuffer<WideNode> exact;
+        BVH_CHECK(exact.reserve(hdr.nodeCount));
+        BVH_CHECK(hipMemcpy(exact.data(), out.nodes.data(), sizeof(WideNode) * hdr.nodeCount, hipMemcpyDeviceToDevice));
+        out.nodes = std::move(exact);
     }
     out.updatable = allowUpdate;                   // a static mesh never refits (Scene.ixx:329: no ALLOW_UPDATE): its build buffers are the caller's scratch
-fail:
-    if (unsorted) hipFree(unsorted);
-    if (unsortedIdx) hipFree(unsortedIdx);
-    return err;
+    return hipSuccess;
 }
 
 // PERFORM_UPDATE: same topology, same Morton order, same slots -- packets and boxes only. Nothing is allocated and nothing waits.
@@ -992,21 +977,22 @@ hipError_t refit_blas_device(const PtGeometryDesc* geoms, uint32_t ngeoms, hipSt
 {
     if (!b.triCount) return hipSuccess;
     const uint32_t leafSize = blas_leaf_tris(b.triCount);
+    const TreeBuffers& t = b.tree;
     uint32_t off = 0;
     for (uint32_t g = 0; g < ngeoms; g++) {
         uint32_t np = geoms[g].IndexCount / 3;
         if (np) k_tri_setup<<<cdiv(np, 256), 256, 0, stream>>>((const uint8_t*)geoms[g].VertexBuffer, geoms[g].VertexStride,
                                                                geoms[g].IndexBuffer, geoms[g].IndexStride, np, off, g, geoms[g].Flags,
-                                                               b.tris, b.tree.slotOfPrim, b.tree.boxLo, b.tree.boxHi, nullptr, nullptr);
+                                                               b.tris.data(), t.slotOfPrim.data(), t.boxLo.data(), t.boxHi.data(), nullptr, nullptr);
         off += np;
     }
-    k_leaves<<<cdiv(b.leafCount, 256), 256, 0, stream>>>(nullptr, b.tree.indexSorted, b.tree.boxLo, b.tree.boxHi, b.triCount, b.leafCount, leafSize,
-                                                         nullptr, b.tree.leafLo, b.tree.leafHi);
-    k_refit<<<cdiv(b.leafCount, 256), 256, 0, stream>>>((int)b.leafCount, b.tree.leafLo, b.tree.leafHi, b.tree.children, b.tree.parentInternal,
-                                                        b.tree.parentLeaf, b.tree.nodeLo, b.tree.nodeHi, b.tree.arrival, b.rootBounds, nullptr, b.triCount, leafSize, 0, 0.0f);
+    k_leaves<<<cdiv(b.leafCount, 256), 256, 0, stream>>>(nullptr, t.indexSorted.data(), t.boxLo.data(), t.boxHi.data(), b.triCount, b.leafCount, leafSize,
+                                                         nullptr, t.leafLo.data(), t.leafHi.data());
+    k_refit<<<cdiv(b.leafCount, 256), 256, 0, stream>>>((int)b.leafCount, t.leafLo.data(), t.leafHi.data(), t.children.data(), t.parentInternal.data(),
+                                                        t.parentLeaf.data(), t.nodeLo.data(), t.nodeHi.data(), t.arrival.data(), b.rootBounds.data(), nullptr, b.triCount, leafSize, 0, 0.0f);
     if (b.leafCount > 1)
-        k_requantise<<<cdiv(b.nodeCount, 256), 256, 0, stream>>>(b.nodeCount, b.nodes, b.tree.binaryRootOf, b.tree.slotRefs, b.tree.leafLo, b.tree.leafHi,
-                                                                 b.tree.nodeLo, b.tree.nodeHi);
+        k_requantise<<<cdiv(b.nodeCount, 256), 256, 0, stream>>>(b.nodeCount, b.nodes.data(), t.binaryRootOf.data(), t.slotRefs.data(), t.leafLo.data(), t.leafHi.data(),
+                                                                 t.nodeLo.data(), t.nodeHi.data());
     return hipGetLastError();
 }
 
@@ -1015,32 +1001,23 @@ hipError_t refit_blas_device(const PtGeometryDesc* geoms, uint32_t ngeoms, hipSt
 // allocation; the header (node count, depth) stays on the device until the caller reads it.
 hipError_t build_tlas_prepare(Tlas& out, uint32_t n)
 {
-    hipError_t err = hipSuccess;
     BVH_CHECK(ensure_tree_buffers(out.tree, n, 1, false));
-    if (n > out.capacity || !out.nodes) {
-        if (out.nodes) hipFree(out.nodes);
-        if (out.rootBounds) hipFree(out.rootBounds);
-        out.nodes = nullptr; out.rootBounds = nullptr; out.capacity = 0;
-        const uint32_t cap = n ? n : 1;
-        BVH_CHECK(hipMalloc((void**)&out.nodes, sizeof(WideNode) * wide_node_capacity(cap)));
-        BVH_CHECK(hipMalloc((void**)&out.rootBounds, sizeof(float) * 8));
-        out.capacity = cap;
+    const uint32_t nodes = wide_node_capacity(n ? n : 1);
+    if (nodes > out.nodes.capacity()) {
+        out.nodes.reset(); out.rootBounds.reset();
+        BVH_CHECK(out.rootBounds.reserve(8));
+        BVH_CHECK(out.nodes.reserve(nodes));                // last: the grow decision reads its capacity
     }
-fail:
-    return err;
+    return hipSuccess;
 }
 
 hipError_t build_tlas_device(const InstanceRecord* dInstances, const float* const* dBlasBounds, uint32_t n, hipStream_t stream, Tlas& out)
 {
-    hipError_t err = hipSuccess;
-    out.instanceCount = n;
     if (n) {                                                 // (launch_instance_records has reset out.tree.bounds)
-        k_instance_boxes<<<std::min(cdiv(n, 4), 256u), 256, 0, stream>>>(dInstances, dBlasBounds, n, out.tree.boxLo, out.tree.boxHi, out.tree.bounds);
+        k_instance_boxes<<<std::min(cdiv(n, 4), 256u), 256, 0, stream>>>(dInstances, dBlasBounds, n, out.tree.boxLo.data(), out.tree.boxHi.data(), out.tree.bounds.data());
     }
-    BVH_CHECK(build_wide_tree(out.tree, n, 1, 1, kCostInstance, kTlasCubicCells, true, out.nodes, out.rootBounds, stream));
-    BVH_CHECK(hipGetLastError());
-fail:
-    return err;
+    BVH_CHECK(build_wide_tree(out.tree, n, 1, 1, kCostInstance, kTlasCubicCells, true, out.nodes.data(), out.rootBounds.data(), stream));
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1136,7 +1113,7 @@ hipError_t launch_blob_assembly(const InstanceRecord* inst, const Tlas& tlas, co
 {
     const uint32_t instBlocks = cdiv(n, 256), copyBlocks = 64u * (njobs < 1024u ? njobs : 1024u);
     if (instBlocks + copyBlocks)
-        k_blob_assemble<<<instBlocks + copyBlocks, 256, 0, stream>>>(inst, tlas.tree.boxLo, tlas.tree.boxHi, table, n, tlas.tree.indexSorted, tlas.tree.leafDst,
+        k_blob_assemble<<<instBlocks + copyBlocks, 256, 0, stream>>>(inst, tlas.tree.boxLo.data(), tlas.tree.boxHi.data(), table, n, tlas.tree.indexSorted.data(), tlas.tree.leafDst.data(),
                                                                      outInst, outLeafInst, (uint4*)outEnter, jobs, njobs, instBlocks);
     return hipGetLastError();
 }

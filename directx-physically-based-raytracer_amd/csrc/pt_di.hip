@@ -622,21 +622,6 @@ __global__ __launch_bounds__(256) void k_di_spatial_shade(DIReuseArgs r, BlobVie
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
-void release_direct_lighting(Context& c)
-{
-    if (c.lightList) hipFree(c.lightList);
-    if (c.lightInstStart) hipFree(c.lightInstStart);
-    if (c.lightRecords) hipFree(c.lightRecords);
-    if (c.lightCdf) hipFree(c.lightCdf);
-    if (c.lightBlockSums) hipFree(c.lightBlockSums);
-    c.lightList = nullptr; c.lightInstStart = nullptr; c.lightRecords = nullptr; c.lightCdf = nullptr; c.lightBlockSums = nullptr;
-    c.lightListCap = c.lightInstCap = c.lightRecordCap = 0; c.lightListValid = false;
-    if (c.diResA) hipFree(c.diResA);
-    if (c.diResB) hipFree(c.diResB);
-    if (c.diOffsets) hipFree(c.diOffsets);
-    c.diResA = c.diResB = nullptr; c.diOffsets = nullptr; c.diResCap = 0; c.diHistoryValid = false; c.diResCount = 0;
-}
-
 // The spatial neighbour-offset table: the R2 sequence from (0.5, 0.5), points outside the disc of radius 0.5
 // rejected, scaled to int8. Built in double on the host, the same on every machine.
 void build_di_offsets(int8_t* out)
@@ -662,31 +647,23 @@ hipError_t ensure_light_list(Context& c, const SceneView& sv)
     const Context& s = c.sceneOwner ? *c.sceneOwner : c;            // who built the top level: the hash of its instances
     uint64_t key = 1469598103934665603ull;
     auto mix = [&](uint64_t v) { key = (key ^ v) * 1099511628211ull; };
-    mix(s.tlasLightHash); mix(s.tlas.instanceCount); mix((uint64_t)(uintptr_t)c.instSourceDev); mix((uint64_t)(uintptr_t)c.objects); mix(c.objectCount);
+    mix(s.tlasLightHash); mix(c.scene.instanceCount); mix((uint64_t)(uintptr_t)c.scene.instSource); mix((uint64_t)(uintptr_t)c.objects); mix(c.objectCount);
     mix(c.objectDataGen);
     if (c.lightListValid && c.lightListKey == key) return hipSuccess;
     hipError_t e;
-    const uint32_t n = s.tlas.instanceCount;
+    const uint32_t n = c.scene.instanceCount;
     c.lightCount = 0; c.lightListValid = false; c.diHistoryValid = false;       // light indices may move
-    if (n && c.instSourceDev && c.blasTableDev && c.objectCount) {
-        if (n + 1u > c.lightInstCap) {
+    if (n && c.scene.instSource && c.scene.blasTable && c.objectCount) {
+        if (n + 1u > c.lightInstStart.capacity()) {
             if ((e = hipStreamSynchronize(c.stream)) != hipSuccess) return e;
-            if (c.lightInstStart) hipFree(c.lightInstStart);
-            c.lightInstStart = nullptr; c.lightInstCap = 0;
-            if ((e = hipMalloc((void**)&c.lightInstStart, sizeof(uint32_t) * (n + 1u))) != hipSuccess) return e;
-            c.lightInstCap = n + 1u;
+            if ((e = c.lightInstStart.reserve(n + 1u)) != hipSuccess) return e;
         }
-        k_light_count<<<1, 1024, 0, c.stream>>>(c.instSourceDev, c.blasTableDev, n, sv.objects, sv.heap, c.lightInstStart);
+        k_light_count<<<1, 1024, 0, c.stream>>>(c.scene.instSource, c.scene.blasTable, n, sv.objects, sv.heap, c.lightInstStart.data());
         uint32_t total = 0;
-        if ((e = hipMemcpyAsync(&total, c.lightInstStart + n, sizeof total, hipMemcpyDeviceToHost, c.stream)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(&total, c.lightInstStart.data() + n, sizeof total, hipMemcpyDeviceToHost, c.stream)) != hipSuccess) return e;
         if ((e = hipStreamSynchronize(c.stream)) != hipSuccess) return e;
-        if (total > c.lightListCap) {
-            if (c.lightList) hipFree(c.lightList);
-            c.lightList = nullptr; c.lightListCap = 0;
-            if ((e = hipMalloc((void**)&c.lightList, sizeof(uint4) * total)) != hipSuccess) return e;
-            c.lightListCap = total;
-        }
-        if (total) k_light_fill<<<n, 256, 0, c.stream>>>(c.instSourceDev, c.blasTableDev, sv.objects, sv.heap, c.lightInstStart, c.lightList);
+        if ((e = c.lightList.reserve(total)) != hipSuccess) return e;
+        if (total) k_light_fill<<<n, 256, 0, c.stream>>>(c.scene.instSource, c.scene.blasTable, sv.objects, sv.heap, c.lightInstStart.data(), c.lightList.data());
         if ((e = hipGetLastError()) != hipSuccess) return e;
         c.lightCount = total;
     }
@@ -753,52 +730,47 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
     if (!reuse || n == 0 || npix == 0) { c.diHistoryValid = false; c.diResCount = 0; }
     if (n == 0 || npix == 0) return PT_OK;
     const uint32_t nb = (n + kScanBlock - 1u) / kScanBlock;
-    if (n > c.lightRecordCap) {
+    if (n > c.lightRecords.capacity()) {
         DI_HIP(hipStreamSynchronize(c.stream));
-        if (c.lightRecords) hipFree(c.lightRecords);
-        if (c.lightCdf) hipFree(c.lightCdf);
-        if (c.lightBlockSums) hipFree(c.lightBlockSums);
-        c.lightRecords = nullptr; c.lightCdf = nullptr; c.lightBlockSums = nullptr; c.lightRecordCap = 0;
-        DI_HIP(hipMalloc((void**)&c.lightRecords, sizeof(PtTriangleLight) * (size_t)n));
-        DI_HIP(hipMalloc((void**)&c.lightCdf, sizeof(float) * (size_t)n * 2u));              // cdf | powers
-        DI_HIP(hipMalloc((void**)&c.lightBlockSums, sizeof(float) * (nb + 1u)));
-        c.lightRecordCap = n;
+        c.lightRecords.reset(); c.lightCdf.reset(); c.lightBlockSums.reset();
+        DI_HIP(c.lightCdf.reserve((size_t)n * 2u));                  // cdf | powers
+        DI_HIP(c.lightBlockSums.reserve(nb + 1u));
+        DI_HIP(c.lightRecords.reserve(n));   // last: the grow decision reads its capacity
     }
-    float* power = c.lightCdf + c.lightRecordCap;
-    k_light_records<<<(n + 255u) / 256u, 256, 0, c.stream>>>(c.lightList, n, c.instSourceDev, sv.objects, sv.heap, sv.shadeTex, sv.srgbLut, c.lightRecords, power);
-    k_cdf_local<<<nb, 256, 0, c.stream>>>(power, n, c.lightCdf, c.lightBlockSums);
-    k_cdf_blocks<<<1, 1, 0, c.stream>>>(c.lightBlockSums, nb);
-    k_cdf_add<<<(n + 255u) / 256u, 256, 0, c.stream>>>(c.lightCdf, n, c.lightBlockSums, nb);
+    float* power = c.lightCdf.data() + c.lightRecords.capacity();
+    k_light_records<<<(n + 255u) / 256u, 256, 0, c.stream>>>(c.lightList.data(), n, c.scene.instSource, sv.objects, sv.heap, sv.shadeTex, sv.srgbLut, (float4*)c.lightRecords.data(), power);
+    k_cdf_local<<<nb, 256, 0, c.stream>>>(power, n, c.lightCdf.data(), c.lightBlockSums.data());
+    k_cdf_blocks<<<1, 1, 0, c.stream>>>(c.lightBlockSums.data(), nb);
+    k_cdf_add<<<(n + 255u) / 256u, 256, 0, c.stream>>>(c.lightCdf.data(), n, c.lightBlockSums.data(), nb);
     DIArgs a; memset(&a, 0, sizeof a);
     a.fv = fv; a.tx = *tx;
     memcpy(a.cam.position, c.camera.Position, sizeof a.cam.position); memcpy(a.cam.jitter, c.camera.Jitter, sizeof a.cam.jitter);
     memcpy(a.cam.projectionToView, c.camera.ProjectionToView, sizeof a.cam.projectionToView); memcpy(a.cam.viewToWorld, c.camera.ViewToWorld, sizeof a.cam.viewToWorld);
-    a.lights = c.lightRecords; a.cdf = c.lightCdf; a.total = c.lightBlockSums + nb; a.count = n;
+    a.lights = (const float4*)c.lightRecords.data(); a.cdf = c.lightCdf.data(); a.total = c.lightBlockSums.data() + nb; a.count = n;
     a.frameIndex = s.FrameIndex; a.samples = s.LocalLightSamples; a.denoiser = s.Denoiser; a.lastPass = s.IsLastRenderPass; a.ext = s.ExtFlags;
     AlphaContext ac; ac.objects = sv.objects; ac.heap = sv.heap; ac.srgbLut = sv.srgbLut; ac.instances = sv.accel.instances; ac.shadeTex = sv.shadeTex;
     const dim3 grid((fv.width + 15u) / 16u, (fv.localRows + 15u) / 16u);
     if (!reuse) {
-        k_di<<<grid, 256, 0, c.stream>>>(a, c.blob, ac, c.counters);
+        k_di<<<grid, 256, 0, c.stream>>>(a, c.scene.blob, ac, c.counters.data());
         DI_HIP(hipGetLastError());
         return PT_OK;
     }
 
     // reservoir reuse: k_di_initial_temporal (last frame's B -> A), k_di_spatial_shade (A -> B); B is next frame's history
-    if (npix > c.diResCap || !c.diOffsets) {
+    if (npix > c.diResB.capacity() || !c.diOffsets) {
         DI_HIP(hipStreamSynchronize(c.stream));
-        if (npix > c.diResCap) {
-            if (c.diResA) hipFree(c.diResA);
-            if (c.diResB) hipFree(c.diResB);
-            c.diResA = c.diResB = nullptr; c.diResCap = 0; c.diHistoryValid = false;
-            DI_HIP(hipMalloc((void**)&c.diResA, sizeof(PtDIReservoir) * npix));
-            DI_HIP(hipMalloc((void**)&c.diResB, sizeof(PtDIReservoir) * npix));
-            c.diResCap = npix;
+        if (npix > c.diResB.capacity()) {
+            c.diResA.reset(); c.diResB.reset(); c.diHistoryValid = false;
+            DI_HIP(c.diResA.reserve(npix));
+            DI_HIP(c.diResB.reserve(npix));                          // last: the grow decision reads its capacity
         }
         if (!c.diOffsets) {
             int8_t host[2 * kDIOffsetCount];
             build_di_offsets(host);
-            DI_HIP(hipMalloc((void**)&c.diOffsets, sizeof host));
-            DI_HIP(hipMemcpy(c.diOffsets, host, sizeof host, hipMemcpyHostToDevice));
+            DeviceBuffer<int8_t> dev;
+            DI_HIP(dev.reserve(sizeof host));
+            DI_HIP(hipMemcpy(dev.data(), host, sizeof host, hipMemcpyHostToDevice));
+            c.diOffsets = std::move(dev);
         }
     }
     if (c.diHistorySize[0] != fv.width || c.diHistorySize[1] != fv.height || c.diHistoryLightKey != c.lightListKey) c.diHistoryValid = false;
@@ -811,22 +783,22 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
         memcpy(r.prevProjectionToView, c.camera.PreviousProjectionToView, sizeof r.prevProjectionToView);
         memcpy(r.prevViewToWorld, c.camera.PreviousViewToWorld, sizeof r.prevViewToWorld);
     }
-    r.offsets = (const char2*)c.diOffsets;
+    r.offsets = (const char2*)c.diOffsets.data();
     r.haveHistory = c.diHistoryValid ? 1u : 0u;
     r.maxHistory = rs.MaxHistoryLength; r.boiling = rs.BoilingFilter; r.spatialSamples = rs.SpatialSamples; r.boostSamples = rs.DisocclusionBoostSamples;
     r.boilingMul = 10.0f / std::min(std::max(rs.BoilingFilterStrength, 1e-6f), 1.0f) - 9.0f;
     r.tDepth = rs.TemporalDepthThreshold; r.tNormal = rs.TemporalNormalThreshold;
     r.radius = rs.SpatialSamplingRadius; r.sDepth = rs.SpatialDepthThreshold; r.sNormal = rs.SpatialNormalThreshold;
-    r.in = c.diResB; r.out = c.diResA;
+    r.in = c.diResB.data(); r.out = c.diResA.data();
     const bool tb = rs.TemporalBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC, sb = rs.SpatialBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC;
     if (!temporal) k_di_initial_temporal<false, false><<<grid, 256, 0, c.stream>>>(r);
     else if (tb) k_di_initial_temporal<true, true><<<grid, 256, 0, c.stream>>>(r);
     else k_di_initial_temporal<true, false><<<grid, 256, 0, c.stream>>>(r);
     DI_HIP(hipGetLastError());
-    r.in = c.diResA; r.out = c.diResB;
-    if (!spatial) k_di_spatial_shade<false, false><<<grid, 256, 0, c.stream>>>(r, c.blob, ac, c.counters);
-    else if (sb) k_di_spatial_shade<true, true><<<grid, 256, 0, c.stream>>>(r, c.blob, ac, c.counters);
-    else k_di_spatial_shade<true, false><<<grid, 256, 0, c.stream>>>(r, c.blob, ac, c.counters);
+    r.in = c.diResA.data(); r.out = c.diResB.data();
+    if (!spatial) k_di_spatial_shade<false, false><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data());
+    else if (sb) k_di_spatial_shade<true, true><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data());
+    else k_di_spatial_shade<true, false><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data());
     DI_HIP(hipGetLastError());
     c.diHistoryValid = true; c.diHistorySize[0] = fv.width; c.diHistorySize[1] = fv.height; c.diHistoryLightKey = c.lightListKey;
     c.diResCount = (uint32_t)npix;
@@ -879,7 +851,7 @@ int pt_di_download_reservoirs(PtContext* ctx, PtDIReservoir* host_dst, uint32_t 
     DI_HIP(hipStreamSynchronize(c.stream));
     *out_count = c.diResCount;
     const uint32_t k = std::min(capacity, c.diResCount);
-    if (k) DI_HIP(hipMemcpy(host_dst, c.diResB, sizeof(PtDIReservoir) * (size_t)k, hipMemcpyDeviceToHost));
+    if (k) DI_HIP(hipMemcpy(host_dst, c.diResB.data(), sizeof(PtDIReservoir) * (size_t)k, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
@@ -907,7 +879,7 @@ int pt_di_download_lights(PtContext* ctx, PtTriangleLight* host_dst, uint32_t ca
     DI_HIP(hipStreamSynchronize(c.stream));
     *out_count = c.lightRecordCount;
     const uint32_t k = std::min(capacity, c.lightRecordCount);
-    if (k) DI_HIP(hipMemcpy(host_dst, c.lightRecords, sizeof(PtTriangleLight) * (size_t)k, hipMemcpyDeviceToHost));
+    if (k) DI_HIP(hipMemcpy(host_dst, c.lightRecords.data(), sizeof(PtTriangleLight) * (size_t)k, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

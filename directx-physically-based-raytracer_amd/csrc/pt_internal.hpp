@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/ptamd.h"
+#include "pt_memory.hpp"
 #include "pt_trace2.hpp"
 
 namespace pt {
@@ -16,17 +17,15 @@ struct WideHeader { uint32_t nodeCount, itemCount, depth, error; };      // writ
 // Device buffers of one tree build. A bottom level built with PT_BUILD_FLAG_ALLOW_UPDATE and the top level keep them, so that a
 // refit / rebuild allocates nothing; a static bottom level frees them after the build.
 struct TreeBuffers {
-    float4* boxLo = nullptr; float4* boxHi = nullptr; uint32_t* bounds = nullptr;
-    uint64_t* keys = nullptr; uint64_t* keysSorted = nullptr; uint32_t* index = nullptr; uint32_t* indexSorted = nullptr;
-    void* sortTemp = nullptr; size_t sortTempBytes = 0;
-    uint64_t* leafKeys = nullptr; float4* leafLo = nullptr; float4* leafHi = nullptr;
-    int2* children = nullptr; int* parentInternal = nullptr; int* parentLeaf = nullptr;
-    float4* nodeLo = nullptr; float4* nodeHi = nullptr; uint32_t* arrival = nullptr;
-    int* binaryRootOf = nullptr; int* slotRefs = nullptr; uint32_t* leafDst = nullptr; uint32_t* slotOfPrim = nullptr;
-    WideHeader* header = nullptr; void* collapseState = nullptr;
-    void* dp = nullptr;                             // collapse cost tables per binary node
-    uint32_t itemCapacity = 0, leafCapacity = 0;
-    void release();
+    DeviceBuffer<float4> boxLo, boxHi; DeviceBuffer<uint32_t> bounds;
+    DeviceBuffer<uint64_t> keys, keysSorted; DeviceBuffer<uint32_t> index, indexSorted;
+    DeviceBuffer<uint8_t> sortTemp; size_t sortTempBytes = 0;
+    DeviceBuffer<uint64_t> leafKeys; DeviceBuffer<float4> leafLo, leafHi;
+    DeviceBuffer<int2> children; DeviceBuffer<int> parentInternal, parentLeaf;
+    DeviceBuffer<float4> nodeLo, nodeHi; DeviceBuffer<uint32_t> arrival;
+    DeviceBuffer<int> binaryRootOf, slotRefs; DeviceBuffer<uint32_t> leafDst, slotOfPrim;
+    DeviceBuffer<WideHeader> header; DeviceBuffer<uint8_t> collapseState;
+    DeviceBuffer<uint8_t> dp;                       // collapse cost tables per binary node
 };
 
 // wide nodes a tree of nleaves leaves can need. A wide node absorbs at least one binary internal node (nleaves - 1 of them), and no more
@@ -35,25 +34,24 @@ struct TreeBuffers {
 inline uint32_t wide_node_capacity(uint32_t nleaves) { return nleaves + 1u; }
 
 struct Blas {
-    WideNode* nodes = nullptr;
-    TriPacket* tris = nullptr;               // node order: the triangles of a node's leaf slots are contiguous
-    uint4* idx = nullptr;                    // the three vertex indices of every triangle, same order (hit reconstruction: no index-buffer hop)
-    float* rootBounds = nullptr;             // device: lo.xyz hi.xyz
+    DeviceBuffer<WideNode> nodes;
+    DeviceBuffer<TriPacket> tris;            // node order: the triangles of a node's leaf slots are contiguous
+    DeviceBuffer<uint4> idx;                 // the three vertex indices of every triangle, same order (hit reconstruction: no index-buffer hop)
+    DeviceBuffer<float> rootBounds;          // lo.xyz hi.xyz
     uint32_t triCount = 0, leafCount = 0, nodeCount = 0, depth = 0, geometryCount = 0;
     bool buildError = false, updatable = false;
     // a static bottom level lives in the context's traversal copy only, once a top-level build has seen it (pt_api.hip pt_build_top_level):
-    // nodes / tris / idx above are null then, and these are the byte offsets of its three pieces in that copy
+    // nodes / tris / idx above are empty then, and these are the byte offsets of its three pieces in that copy
     bool inBlob = false; uint64_t blobNodeAt = 0, blobTriAt = 0, blobIdxAt = 0;
     TreeBuffers tree;                        // kept only when updatable
 };
 
+// the top level a context builds (its buffers are grow-only)
 struct Tlas {
-    WideNode* nodes = nullptr;               // capacity wide_node_capacity(capacity)
-    float* rootBounds = nullptr;
-    InstanceRecord* instances = nullptr;     // device, indexed by InstanceIndex
-    const float** blasBounds = nullptr;      // device, per instance: root bounds of its BLAS
-    uint32_t instanceCount = 0, capacity = 0;
-    uint64_t triangleCount = 0;              // sum over instances
+    DeviceBuffer<WideNode> nodes;            // capacity wide_node_capacity(instance capacity)
+    DeviceBuffer<float> rootBounds;
+    DeviceBuffer<InstanceRecord> instances;  // indexed by InstanceIndex
+    DeviceBuffer<const float*> blasBounds;   // per instance: root bounds of its BLAS
     TreeBuffers tree;
 };
 
@@ -62,6 +60,17 @@ struct InstanceSource { float transform[12]; uint32_t instanceID, mask, blasSlot
 struct BlasEntry { const WideNode* nodes; const TriPacket* tris; const float* rootBounds; uint32_t triCount, nodeCount, nodeBase, triBase; const uint4* idx;
                    uint32_t objectBase, geometryCount; };   // InstanceID of the first instance that refers to the bottom level: ObjectData[objectBase + geometry] describes its meshes
 struct BlobCopy { const void* src; void* dst; uint64_t n16; };
+
+// What a render reads of the scene: views of the storage of the context that built the top level -- this one, or the one it views
+// (pt_share_scene). Written when a top-level build commits, copied by pt_share_scene, cleared by drop_tlas and by the destruction of a viewed
+// owner. Nothing here is freed through these pointers.
+struct SceneRefs {
+    const InstanceRecord* instances = nullptr; uint32_t instanceCount = 0;
+    uint64_t triangleCount = 0;              // sum over instances
+    BlobView blob{};                         // compact traversal copy of TLAS + instances + every referenced BLAS
+    const BlasEntry* blasTable = nullptr; uint32_t blasTableCount = 0, blasTableMaxTris = 0;   // the top-level build's table of bottom levels
+    const InstanceSource* instSource = nullptr;
+};
 
 // What hit reconstruction needs of an object's geometry, resolved once per change of (ObjectData, heap) by the validation kernel: the
 // object record -> descriptor table -> buffer chain of the reference (RaytracingHelpers.hlsli:82-85) is one fetch here.
@@ -120,37 +129,35 @@ struct Context {
     std::string lastError;
 
     std::vector<HeapEntry> heapHost;
-    HeapEntry* heapDev = nullptr; uint32_t heapDevCap = 0; bool heapDirty = true;
-    float* srgbLutDev = nullptr;
+    DeviceBuffer<HeapEntry> heapDev; bool heapDirty = true;
+    DeviceBuffer<float> srgbLutDev;
     bool heapHasTextures = false;             // any Texture2D / TextureCube descriptor: selects the TEXTURED kernel variants
 
     std::map<uint64_t, Blas> blas; uint64_t nextBlasId = 1;
     TreeBuffers buildScratch;                         // build buffers of static bottom levels, reused from build to build (grow-only)
     Tlas tlas; bool haveTlas = false;
-    Context* sceneOwner = nullptr;                    // pt_share_scene: tlas / blob below are views of that context's, never freed here
-    int borrowers = 0;                                // contexts viewing THIS context's scene
-    std::vector<Context*> viewers;                    // ... and who they are (pt_destroy of a viewed owner detaches them)
+    DeviceBuffer<uint8_t> blobDev;                    // this context's traversal copy (SceneRefs::blob views it once a top-level build commits)
+    SceneRefs scene;                                  // what renders read: views of this context's top level, or of sceneOwner's
+    Context* sceneOwner = nullptr;                    // pt_share_scene: the context whose scene `scene` views
+    std::vector<Context*> viewers;                    // contexts viewing THIS context's scene (pt_destroy of a viewed owner detaches them)
     uint32_t framesInFlight = 1;                      // pt_set_frames_in_flight: how many contexts render concurrently on this GPU (grid sizing)
     std::vector<uint64_t> tlasBlasIds;                // bottom levels the live TLAS refers to (pt_release_bottom_level checks)
-    std::vector<uint8_t> tlasUploadHost; void* tlasUploadDev = nullptr; size_t tlasUploadCap = 0;   // InstanceSource | BlasEntry | BlobCopy
-    struct UploadStage { void* host = nullptr; size_t capacity = 0; hipEvent_t event = nullptr; };  // pinned staging of that upload, two in turn
+    std::vector<uint8_t> tlasUploadHost; DeviceBuffer<uint8_t> tlasUploadDev;   // InstanceSource | BlasEntry | BlobCopy
+    struct UploadStage { PinnedBuffer<uint8_t> host; Event event; };  // pinned staging of that upload, two in turn
     UploadStage tlasStage[2]; uint32_t tlasStageNext = 0;
-    WideHeader* tlasHeaderHost = nullptr; hipEvent_t tlasHeaderEvent = nullptr; bool tlasHeaderPending = false;   // lazy depth / error check
-    uint32_t maxBlasDepth = 0, tlasInstanceCap = 0, tlasNodeReserve = 0;   // tlasNodeReserve: top-level nodes reserved at the head of the traversal copy by the last build
-    size_t blobCapacity = 0;
+    PinnedBuffer<WideHeader> tlasHeaderHost; Event tlasHeaderEvent; bool tlasHeaderPending = false;   // lazy depth / error check
+    uint32_t maxBlasDepth = 0, tlasNodeReserve = 0;   // tlasNodeReserve: top-level nodes reserved at the head of the traversal copy by the last build
     uint32_t tlasValidatedCount = ~0u, persistentGrid = 0;
     uint64_t tlasBindingHash = 0;                     // over (InstanceID, bottom-level id) of the instances, in order: what the shared-geometry check depends on
     uint64_t tlasObjectEnd = 0;                       // max over instances of InstanceID + geometry count: ObjectData must reach that far
     uint32_t sqShift = kSubQueueShiftFused;   // log2 of the number of sub-queues of the frame being enqueued (launch_raytrace)
-    ShadeGeom* shadeGeomDev = nullptr; uint32_t shadeGeomCap = 0;
-    HeapEntry* shadeTexDev = nullptr;                 // same capacity: 7 resolved texture slots per object
+    DeviceBuffer<ShadeGeom> shadeGeomDev;             // per object
+    DeviceBuffer<HeapEntry> shadeTexDev;              // 7 resolved texture slots per object
     // per-frame copy of the vertex normals, one record per triangle packet of the traversal copy (pt_shade.hpp ShadeTables)
-    uint4* shadeRecA = nullptr; uint32_t* shadeRecB = nullptr; uint32_t shadeRecCap = 0;
-    const BlasEntry* blasTableDev = nullptr; uint32_t blasTableCount = 0; uint32_t blasTableMaxTris = 0;    // the top-level build's table of bottom levels (device; a viewer: the owner's)
-    const InstanceSource* instSourceDev = nullptr;
+    DeviceBuffer<uint4> shadeRecA; DeviceBuffer<uint32_t> shadeRecB;
     bool normalsShared = false;              // every instance of a bottom level resolves to the same vertex buffer / stride / normal offset (checked with the objects)
     bool sharedVerdict = false;              // what the last shared-geometry check said (normalsShared is put aside while there is no top level)
-    bool validated = false; uint32_t* validateDev = nullptr;   // descriptor / index validation of the scene inputs (pt_api.hip make_views)
+    bool validated = false; DeviceBuffer<uint32_t> validateDev;   // descriptor / index validation of the scene inputs (pt_api.hip make_views)
     const void* validatedObjects = nullptr; uint32_t validatedObjectCount = 0;
 
     PtCamera camera{}; PtSceneData sceneData{}; PtGraphicsSettings settings{};
@@ -159,29 +166,28 @@ struct Context {
     const PtInstanceData* instanceData = nullptr; uint32_t instanceDataCount = 0;
     PtSharding sharding{0, 1, 16, 0};
 
-    void* blobDev = nullptr; BlobView blob{};        // compact traversal copy of TLAS + instances + every referenced BLAS
-
-    PathQueue queue[2]{}; uint32_t queueCapacity = 0;
-    uint4* primaryRecords = nullptr; uint32_t primaryCapacity = 0;   // 48 B per local pixel: the primary surface as bounce 0 reads it (k_pt_init)
-    float2* pixelAux = nullptr; uint32_t pixelAuxCapacity = 0;   // denoiser modes: first-bounce hit distance | isDiffuse per pixel
-    FrameConstants* frameConstants = nullptr;
-    hipGraphExec_t graphExec = nullptr; std::string graphKey; bool disableGraphs = false;
+    DeviceBuffer<uint4> queueArrays[2][6];            // s0 s1 s2 r0 r1 hit of each path queue, 16 B per entry
+    PathQueue queue[2]{};                             // ... as the kernels take them
+    DeviceBuffer<uint4> primaryRecords;               // 48 B per local pixel: the primary surface as bounce 0 reads it (k_pt_init)
+    DeviceBuffer<float2> pixelAux;                    // denoiser modes: first-bounce hit distance | isDiffuse per pixel
+    DeviceBuffer<FrameConstants> frameConstants;
+    GraphExec graphExec; std::string graphKey; bool disableGraphs = false;
     // chains of a frame (pt_kernels.hip launch_raytrace): the rounds of a group of sub-queues need nothing from the other groups, so each group's
     // chain of launches is a linear graph replayed on a stream of its own, behind the frame's preamble and joined to the context's stream.
     static constexpr uint32_t kMaxChains = 4;
     uint32_t chains = 0;                              // 0: the library chooses (pt_set_round_chains)
-    hipStream_t chainStream[kMaxChains - 1] = { nullptr, nullptr, nullptr }; hipEvent_t chainFork = nullptr, chainJoin[kMaxChains - 1] = { nullptr, nullptr, nullptr };
-    hipGraphExec_t chainGraph[kMaxChains] = { nullptr, nullptr, nullptr, nullptr }; std::string chainGraphKey;
-    uint32_t* queueCounts = nullptr; uint32_t queueCountsCap = 0;
-    struct RoundArgs* roundArgs = nullptr; uint32_t roundArgsCap = 0; std::string roundArgsKey;   // per-round argument blocks of k_round (device)
-    DeviceCounters* counters = nullptr;
+    Stream chainStream[kMaxChains - 1]; Event chainFork, chainJoin[kMaxChains - 1];
+    GraphExec chainGraph[kMaxChains]; std::string chainGraphKey;
+    DeviceBuffer<uint32_t> queueCounts;
+    DeviceBuffer<RoundArgs> roundArgs; std::string roundArgsKey;   // per-round argument blocks of k_round
+    DeviceBuffer<DeviceCounters> counters;
     uint64_t lastIterations = 0;
     uint32_t debugFlags = 0;
 
     void* comm = nullptr; bool commOwned = false; uint32_t commRank = 0, commWorld = 1;   // ncclComm_t of pt_gather_bands (pt_comm.hip)
 
     bool timing = false;
-    std::vector<hipEvent_t> evExtend, evShade, evRound;     // begin/end pairs since timing was enabled
+    std::vector<Event> evExtend, evShade, evRound;     // begin/end pairs since timing was enabled
     uint32_t nExtend = 0, nShade = 0, nRound = 0;
 
     // direct lighting (pt_di.hip): per context. A context that views another's scene (pt_share_scene) lists its emissive triangles from the owner's
@@ -189,14 +195,14 @@ struct Context {
     PtDISettings diSettings{}; bool haveDISettings = false;
     uint64_t tlasLightHash = 0;                       // over (InstanceID, InstanceMask, bottom-level id) of the top level's instances, in order
     uint32_t objectDataGen = 0;                       // bumped by pt_invalidate_object_data
-    uint4* lightList = nullptr; uint32_t lightListCap = 0, lightCount = 0;   // (instance, geometry, primitive, object) per emissive triangle
-    uint32_t* lightInstStart = nullptr; uint32_t lightInstCap = 0;          // per instance: first list entry; [instanceCount]: the total
+    DeviceBuffer<uint4> lightList; uint32_t lightCount = 0;     // (instance, geometry, primitive, object) per emissive triangle
+    DeviceBuffer<uint32_t> lightInstStart;                      // per instance: first list entry; [instanceCount]: the total
     uint64_t lightListKey = 0; bool lightListValid = false;
-    float4* lightRecords = nullptr; float* lightCdf = nullptr; float* lightBlockSums = nullptr; uint32_t lightRecordCap = 0, lightRecordCount = 0;
+    DeviceBuffer<PtTriangleLight> lightRecords; DeviceBuffer<float> lightCdf, lightBlockSums; uint32_t lightRecordCount = 0;   // lightCdf: cdf | powers
     // reservoir reuse (pt_di_set_resampling): A = temporal output, B = final reservoirs = next frame's history
     PtDIResamplingSettings diReuse{}; bool diReuseOn = false;
-    PtDIReservoir* diResA = nullptr; PtDIReservoir* diResB = nullptr; size_t diResCap = 0;
-    int8_t* diOffsets = nullptr;                      // the spatial neighbour-offset table, 8192 (x, y) pairs
+    DeviceBuffer<PtDIReservoir> diResA, diResB;
+    DeviceBuffer<int8_t> diOffsets;                   // the spatial neighbour-offset table, 8192 (x, y) pairs
     bool diHistoryValid = false; uint32_t diHistorySize[2] = {0, 0}; uint64_t diHistoryLightKey = 0; uint32_t diResCount = 0;
 };
 
@@ -230,12 +236,9 @@ hipError_t launch_bsdf_sample(hipStream_t stream, const float* q, uint32_t count
 hipError_t launch_debug_trace(Context& c, const SceneView& sv, const float* ray8, uint32_t* devLog, uint32_t logCap);
 uint32_t round_objects_in_lds(const Context& c, uint32_t objectCount, bool haveShadeGeom);   // the fused round kernel's LDS tables (PtAccelStats)
 uint32_t round_records_in_lds(const Context& c, uint32_t objectCount, bool haveShadeGeom);
-inline bool normal_records_usable(const Context& c) { return c.normalsShared && c.blasTableDev && c.blasTableCount <= 65535u /* grid.y of k_capture_normals */ && c.shadeRecA && c.blob.triCount && c.blob.triCount <= c.shadeRecCap; }
+inline bool normal_records_usable(const Context& c) { return c.normalsShared && c.scene.blasTable && c.scene.blasTableCount <= 65535u /* grid.y of k_capture_normals */ && c.shadeRecB && c.scene.blob.triCount && c.scene.blob.triCount <= c.shadeRecB.capacity(); }
 hipError_t launch_check_shared_geometry(hipStream_t stream, const InstanceSource* src, const BlasEntry* table, uint32_t n, const ShadeGeom* shadeGeom, uint32_t* out);
 hipError_t launch_validate_objects(hipStream_t stream, const PtObjectData* objects, uint32_t count, const HeapEntry* heap, uint32_t heapCount, uint32_t* out, ShadeGeom* shadeGeom, HeapEntry* shadeTex);
-// pt_di.hip
-void release_direct_lighting(Context& c);
-
 hipError_t launch_deinterleave(hipStream_t stream, void* dst, const void* src, const uint64_t* rankOffsetsHost, uint32_t rankCount,
                                uint32_t bandHeight, uint32_t width, uint32_t height, uint32_t pixelBytes);
 

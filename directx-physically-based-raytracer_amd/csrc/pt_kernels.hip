@@ -530,7 +530,7 @@ __global__ __launch_bounds__(256) void k_debug_trace(BlobView bv, AlphaContext a
 hipError_t launch_debug_trace(Context& c, const SceneView& sv, const float* ray8, uint32_t* devLog, uint32_t logCap)
 {
     AlphaContext ac; ac.objects = sv.objects; ac.heap = sv.heap; ac.srgbLut = sv.srgbLut; ac.instances = sv.accel.instances; ac.shadeTex = sv.shadeTex;
-    k_debug_trace<<<1, 256, 0, c.stream>>>(c.blob, ac, make_float4(ray8[0], ray8[1], ray8[2], ray8[3]), make_float4(ray8[4], ray8[5], ray8[6], ray8[7]), devLog, logCap);
+    k_debug_trace<<<1, 256, 0, c.stream>>>(c.scene.blob, ac, make_float4(ray8[0], ray8[1], ray8[2], ray8[3]), make_float4(ray8[4], ray8[5], ray8[6], ray8[7]), devLog, logCap);
     return hipGetLastError();
 }
 
@@ -666,7 +666,7 @@ hipError_t launch_visibility(Context& c, const SceneView& sv, const void* rays, 
 {
     if (!count) return hipSuccess;
     AlphaContext ac; ac.objects = sv.objects; ac.heap = sv.heap; ac.srgbLut = sv.srgbLut; ac.instances = sv.accel.instances; ac.shadeTex = sv.shadeTex;
-    k_visibility<<<persistent_grid(c), 256, 0, c.stream>>>(c.blob, ac, (const float4*)rays, count, (float4*)out, c.counters);
+    k_visibility<<<persistent_grid(c), 256, 0, c.stream>>>(c.scene.blob, ac, (const float4*)rays, count, (float4*)out, c.counters.data());
     return hipGetLastError();
 }
 
@@ -718,11 +718,11 @@ hipError_t launch_gbuffer(Context& c, const SceneView& sv, const FrameView& fv, 
     if (fv.localRows == 0 || fv.width == 0) return hipSuccess;
     dim3 grid((fv.width + 15) / 16, (fv.localRows + 15) / 16);
     const bool stats = (c.debugFlags & PT_DEBUG_TRAVERSAL_STATS) != 0;
-    const bool flat = c.blob.base && c.blob.instCount <= kFlatInstances &&
+    const bool flat = c.scene.blob.base && c.scene.blob.instCount <= kFlatInstances &&
                       !(c.debugFlags & (PT_DEBUG_TRAVERSAL_V1 | PT_DEBUG_TRAVERSAL_PHASED | PT_DEBUG_BRUTE_FORCE));
-    const int mode = !flat ? 0 : (c.blob.bytes <= kBlobLdsMax ? 1 : 2);
-    const uint32_t smem = mode == 0 ? 0u : kFlatLdsFixed + (mode == 1 ? c.blob.bytes : 0u);
-    #define PT_GB(S, T, M) k_gbuffer<S, T, M><<<grid, 256, smem, c.stream>>>(sv, fv, c.camera, c.sceneData, flags, tx, c.blob, c.counters)
+    const int mode = !flat ? 0 : (c.scene.blob.bytes <= kBlobLdsMax ? 1 : 2);
+    const uint32_t smem = mode == 0 ? 0u : kFlatLdsFixed + (mode == 1 ? c.scene.blob.bytes : 0u);
+    #define PT_GB(S, T, M) k_gbuffer<S, T, M><<<grid, 256, smem, c.stream>>>(sv, fv, c.camera, c.sceneData, flags, tx, c.scene.blob, c.counters.data())
     #define PT_GB_M(S, T) do { if (mode == 0) PT_GB(S, T, 0); else if (mode == 1) PT_GB(S, T, 1); else PT_GB(S, T, 2); } while (0)
     #define PT_GB_T(S) do { if (c.heapHasTextures) PT_GB_M(S, true); else PT_GB_M(S, false); } while (0)
     if (stats) PT_GB_T(true); else PT_GB_T(false);
@@ -734,45 +734,33 @@ hipError_t launch_gbuffer(Context& c, const SceneView& sv, const FrameView& fv, 
 
 static hipError_t ensure_queues(Context& c, uint32_t capacity, uint32_t iterations)
 {
-    hipError_t e;
-    if (capacity > c.queueCapacity) {
-        for (int k = 0; k < 2; k++) {
-            PathQueue& q = c.queue[k];
-            void** ptrs[6] = { (void**)&q.s0, (void**)&q.s1, (void**)&q.s2, (void**)&q.r0, (void**)&q.r1, (void**)&q.hit };
-            for (auto pp : ptrs) { if (*pp) hipFree(*pp); *pp = nullptr; if ((e = hipMalloc(pp, (size_t)capacity * 16)) != hipSuccess) return e; }
-        }
-        c.queueCapacity = capacity;
+    hipError_t e = hipSuccess;
+    for (auto& arrays : c.queueArrays) for (auto& a : arrays) if (e == hipSuccess) e = a.reserve(capacity);   // each array freed, then allocated, in turn
+    for (int k = 0; k < 2; k++) {
+        DeviceBuffer<uint4>* a = c.queueArrays[k];
+        c.queue[k] = PathQueue{ (float4*)a[0].data(), (float4*)a[1].data(), (float4*)a[2].data(), (float4*)a[3].data(), (float4*)a[4].data(), a[5].data() };
     }
-    if (capacity > c.primaryCapacity) {                             // 48 bytes per local pixel (capacity >= pixels)
-        if (c.primaryRecords) hipFree(c.primaryRecords);
-        c.primaryRecords = nullptr; c.primaryCapacity = 0;
-        if ((e = hipMalloc((void**)&c.primaryRecords, (size_t)capacity * 48)) != hipSuccess) return e;
-        c.primaryCapacity = capacity;
-    }
-    if (iterations > c.queueCountsCap) {
-        if (c.queueCounts) hipFree(c.queueCounts);
-        c.queueCountsCap = iterations;
-        if ((e = hipMalloc((void**)&c.queueCounts, sizeof(uint32_t) * c.queueCountsCap)) != hipSuccess) return e;
-    }
-    return hipSuccess;
+    if (e != hipSuccess) return e;
+    if ((e = c.primaryRecords.reserve(3 * (size_t)capacity)) != hipSuccess) return e;   // 48 bytes per local pixel (capacity >= pixels)
+    return c.queueCounts.reserve(iterations);
 }
 
-static void timing_begin(Context& c, std::vector<hipEvent_t>& ev, uint32_t k)
+static void timing_begin(Context& c, std::vector<Event>& ev, uint32_t k)
 {
     if (!c.timing) return;
-    while (ev.size() < 2 * (size_t)(k + 1)) { hipEvent_t e; hipEventCreate(&e); ev.push_back(e); }
-    hipEventRecord(ev[2 * k], c.stream);
+    while (ev.size() < 2 * (size_t)(k + 1)) { hipEvent_t e; hipEventCreate(&e); ev.emplace_back(e); }
+    hipEventRecord(ev[2 * k].get(), c.stream);
 }
-static void timing_end(Context& c, std::vector<hipEvent_t>& ev, uint32_t k) { if (c.timing) hipEventRecord(ev[2 * k + 1], c.stream); }
+static void timing_end(Context& c, std::vector<Event>& ev, uint32_t k) { if (c.timing) hipEventRecord(ev[2 * k + 1].get(), c.stream); }
 
 // Objects whose resolved geometry + material k_round stages in LDS behind the blob: all of them, if that does not cost the kernel its fourth
 // workgroup per CU (160 KB / 4, the kernel's static words and the 512-byte allocation granule counted); otherwise none.
 static uint32_t lds_bytes_of_records(uint32_t n) { return (n * 20u + 15u) / 16u * 16u; }
 uint32_t round_objects_in_lds(const Context& c, uint32_t objectCount, bool haveShadeGeom)
 {
-    if (c.blob.bytes > kBlobLdsMax || !objectCount || !haveShadeGeom) return 0u;
-    const bool flat = c.blob.instCount <= kFlatInstances && !(c.debugFlags & PT_DEBUG_TRAVERSAL_PHASED);
-    const uint32_t bytes = (flat ? kFlatLdsFixed : kExtendLdsFixed) + c.blob.bytes + objectCount * kObjLds16 * 16u + 128u;
+    if (c.scene.blob.bytes > kBlobLdsMax || !objectCount || !haveShadeGeom) return 0u;
+    const bool flat = c.scene.blob.instCount <= kFlatInstances && !(c.debugFlags & PT_DEBUG_TRAVERSAL_PHASED);
+    const uint32_t bytes = (flat ? kFlatLdsFixed : kExtendLdsFixed) + c.scene.blob.bytes + objectCount * kObjLds16 * 16u + 128u;
     return (bytes + 511u) / 512u * 512u <= 160u * 1024u / 4u ? objectCount : 0u;
 }
 static uint32_t round_objects_in_lds(const Context& c, const SceneView& sv) { return round_objects_in_lds(c, sv.objectCount, sv.shadeGeom != nullptr); }
@@ -781,9 +769,9 @@ uint32_t round_records_in_lds(const Context& c, uint32_t objectCount, bool haveS
 {
     const uint32_t nobj = round_objects_in_lds(c, objectCount, haveShadeGeom);
     if (!nobj || !normal_records_usable(c)) return 0u;
-    const bool flat = c.blob.instCount <= kFlatInstances && !(c.debugFlags & PT_DEBUG_TRAVERSAL_PHASED);
-    const uint32_t bytes = (flat ? kFlatLdsFixed : kExtendLdsFixed) + c.blob.bytes + nobj * kObjLds16 * 16u + lds_bytes_of_records(c.blob.triCount) + 128u;
-    return (bytes + 511u) / 512u * 512u <= 160u * 1024u / 4u ? c.blob.triCount : 0u;
+    const bool flat = c.scene.blob.instCount <= kFlatInstances && !(c.debugFlags & PT_DEBUG_TRAVERSAL_PHASED);
+    const uint32_t bytes = (flat ? kFlatLdsFixed : kExtendLdsFixed) + c.scene.blob.bytes + nobj * kObjLds16 * 16u + lds_bytes_of_records(c.scene.blob.triCount) + 128u;
+    return (bytes + 511u) / 512u * 512u <= 160u * 1024u / 4u ? c.scene.blob.triCount : 0u;
 }
 static uint32_t round_records_in_lds(const Context& c, const SceneView& sv) { return round_records_in_lds(c, sv.objectCount, sv.shadeGeom != nullptr); }
 
@@ -807,7 +795,7 @@ static FrameForm frame_form(const Context& c)
     const uint32_t lockStepFlags = PT_DEBUG_LOCKSTEP | PT_DEBUG_TRAVERSAL_PHASED | PT_DEBUG_BRUTE_FORCE | PT_DEBUG_TRAVERSAL_V1 | PT_DEBUG_UNFUSED_ROUNDS;
     const uint32_t pairOnlyFlags = PT_DEBUG_TRAVERSAL_STATS | PT_DEBUG_BRUTE_FORCE | PT_DEBUG_TRAVERSAL_V1 | PT_DEBUG_UNFUSED_ROUNDS;
     FrameForm f;
-    f.streaming = c.blob.bytes > kBlobLdsMax && !(c.debugFlags & lockStepFlags);   // a scene that does not fit LDS: persistent traversal lanes with ray replacement
+    f.streaming = c.scene.blob.bytes > kBlobLdsMax && !(c.debugFlags & lockStepFlags);   // a scene that does not fit LDS: persistent traversal lanes with ray replacement
     f.fused = !f.streaming && !(c.debugFlags & pairOnlyFlags);                     // fused rounds: everything except the validation / statistics variants
     f.first = f.streaming || f.fused;                                              // the product paths start with k_pt_first; the validation variants keep k_pt_init and round 0 apart
     return f;
@@ -831,14 +819,14 @@ static uint32_t frame_chains(const Context& c, bool ownStreams)
 static hipError_t enqueue_preamble(Context& c, const SceneView& sv, const FrameView& fv, const PtTextures& tx, uint32_t segCap, uint32_t grid)
 {
     const uint32_t nsq = 1u << c.sqShift, cstride = 3u * nsq;                  // traced + fresh counters + the streaming form's cursor, per round
-    float2* aux = c.settings.Denoiser != PT_DENOISER_NONE ? c.pixelAux : nullptr;
+    float2* aux = c.settings.Denoiser != PT_DENOISER_NONE ? c.pixelAux.data() : nullptr;
     if (normal_records_usable(c))                          // the frame's normal records, from the vertex buffers as they are now
-        k_capture_normals<<<dim3(std::min((c.blasTableMaxTris + 255u) / 256u, 64u), c.blasTableCount), 256, 0, c.stream>>>(c.blasTableDev, sv.shadeGeom, c.shadeRecA, c.shadeRecB);
+        k_capture_normals<<<dim3(std::min((c.scene.blasTableMaxTris + 255u) / 256u, 64u), c.scene.blasTableCount), 256, 0, c.stream>>>(c.scene.blasTable, sv.shadeGeom, c.shadeRecA.data(), c.shadeRecB.data());
     if (frame_form(c).first) {
-        if (c.settings.IsDIEnabled) k_pt_first<true><<<grid, 256, 0, c.stream>>>(fv, c.frameConstants, tx, c.queue[1], aux, segCap, &c.queueCounts[cstride], c.primaryRecords, c.sqShift);
-        else k_pt_first<false><<<grid, 256, 0, c.stream>>>(fv, c.frameConstants, tx, c.queue[1], aux, segCap, &c.queueCounts[cstride], c.primaryRecords, c.sqShift);
+        if (c.settings.IsDIEnabled) k_pt_first<true><<<grid, 256, 0, c.stream>>>(fv, c.frameConstants.data(), tx, c.queue[1], aux, segCap, &c.queueCounts.data()[cstride], c.primaryRecords.data(), c.sqShift);
+        else k_pt_first<false><<<grid, 256, 0, c.stream>>>(fv, c.frameConstants.data(), tx, c.queue[1], aux, segCap, &c.queueCounts.data()[cstride], c.primaryRecords.data(), c.sqShift);
     }
-    else k_pt_init<<<grid, 256, 0, c.stream>>>(fv, c.frameConstants, tx, c.queue[0], aux, segCap, &c.queueCounts[nsq], c.primaryRecords, c.sqShift);
+    else k_pt_init<<<grid, 256, 0, c.stream>>>(fv, c.frameConstants.data(), tx, c.queue[0], aux, segCap, &c.queueCounts.data()[nsq], c.primaryRecords.data(), c.sqShift);
     return hipGetLastError();
 }
 
@@ -847,7 +835,7 @@ static hipError_t enqueue_chain(Context& c, const SceneView& sv, const FrameView
                                 uint32_t g, uint32_t chains, hipStream_t s)
 {
     const uint32_t nsq = 1u << c.sqShift, cstride = 3u * nsq;
-    float2* aux = c.settings.Denoiser != PT_DENOISER_NONE ? c.pixelAux : nullptr;
+    float2* aux = c.settings.Denoiser != PT_DENOISER_NONE ? c.pixelAux.data() : nullptr;
     const FrameForm form = frame_form(c);
     const bool stats = (c.debugFlags & PT_DEBUG_TRAVERSAL_STATS) != 0;
     AlphaContext ac; ac.objects = sv.objects; ac.heap = sv.heap; ac.srgbLut = sv.srgbLut; ac.instances = sv.accel.instances; ac.shadeTex = sv.shadeTex;
@@ -857,7 +845,7 @@ static hipError_t enqueue_chain(Context& c, const SceneView& sv, const FrameView
         const bool wt = aux != nullptr;
         for (uint32_t r = 0; r <= rounds; r++) {
             PathQueue& qin = c.queue[r & 1]; PathQueue& qout = c.queue[(r + 1) & 1];
-            uint32_t* cin = &c.queueCounts[r * cstride]; uint32_t* cout = &c.queueCounts[(r + 1) * cstride];
+            uint32_t* cin = &c.queueCounts.data()[r * cstride]; uint32_t* cout = &c.queueCounts.data()[(r + 1) * cstride];
             if (r > 0) {
                 timing_begin(c, c.evShade, c.nShade);
                 launch_shade(c, sv, fv, tx, qin, qout, aux, segCap, cin, cout, perSq * sqCount, s, sqBase, sqCount);
@@ -870,13 +858,13 @@ static hipError_t enqueue_chain(Context& c, const SceneView& sv, const FrameView
         }
         return hipGetLastError();
     }
-    const bool lds = c.blob.bytes <= kBlobLdsMax;
-    const bool flat = c.blob.instCount <= kFlatInstances && !(c.debugFlags & PT_DEBUG_TRAVERSAL_PHASED);
-    const uint32_t smem = (flat ? kFlatLdsFixed : kExtendLdsFixed) + (lds ? c.blob.bytes : 0u) + round_objects_in_lds(c, sv) * kObjLds16 * 16u + lds_bytes_of_records(round_records_in_lds(c, sv));
+    const bool lds = c.scene.blob.bytes <= kBlobLdsMax;
+    const bool flat = c.scene.blob.instCount <= kFlatInstances && !(c.debugFlags & PT_DEBUG_TRAVERSAL_PHASED);
+    const uint32_t smem = (flat ? kFlatLdsFixed : kExtendLdsFixed) + (lds ? c.scene.blob.bytes : 0u) + round_objects_in_lds(c, sv) * kObjLds16 * 16u + lds_bytes_of_records(round_records_in_lds(c, sv));
     for (uint32_t r = 1; r <= rounds; r++) {                        // queues and counters of round r: in its argument block (launch_raytrace); round 0 ran inside k_pt_first
         timing_begin(c, c.evRound, c.nRound);
-        #define PT_ROUND(T, L, F) do { if (c.settings.IsDIEnabled) k_round<T, L, F, true><<<perSq * sqCount, 256, smem, s>>>(c.roundArgs + r, sqBase, sqCount); \
-                                       else k_round<T, L, F, false><<<perSq * sqCount, 256, smem, s>>>(c.roundArgs + r, sqBase, sqCount); } while (0)
+        #define PT_ROUND(T, L, F) do { if (c.settings.IsDIEnabled) k_round<T, L, F, true><<<perSq * sqCount, 256, smem, s>>>(c.roundArgs.data() + r, sqBase, sqCount); \
+                                       else k_round<T, L, F, false><<<perSq * sqCount, 256, smem, s>>>(c.roundArgs.data() + r, sqBase, sqCount); } while (0)
         #define PT_ROUND_F(T, L) do { if (flat) PT_ROUND(T, L, true); else PT_ROUND(T, L, false); } while (0)
         #define PT_ROUND_L(T) do { if (lds) PT_ROUND_F(T, true); else PT_ROUND_F(T, false); } while (0)
         if (c.heapHasTextures) PT_ROUND_L(true); else PT_ROUND_L(false);
@@ -892,27 +880,27 @@ static hipError_t enqueue_chain(Context& c, const SceneView& sv, const FrameView
 static hipError_t enqueue_validation_rounds(Context& c, const SceneView& sv, const FrameView& fv, const PtTextures& tx, uint32_t rounds, uint32_t segCap, uint32_t grid)
 {
     const uint32_t nsq = 1u << c.sqShift, cstride = 3u * nsq;
-    float2* aux = c.settings.Denoiser != PT_DENOISER_NONE ? c.pixelAux : nullptr;
+    float2* aux = c.settings.Denoiser != PT_DENOISER_NONE ? c.pixelAux.data() : nullptr;
     const bool stats = (c.debugFlags & PT_DEBUG_TRAVERSAL_STATS) != 0;
     AlphaContext ac; ac.objects = sv.objects; ac.heap = sv.heap; ac.srgbLut = sv.srgbLut; ac.instances = sv.accel.instances; ac.shadeTex = sv.shadeTex;
     for (uint32_t r = 0; r <= rounds; r++) {
         PathQueue& qin = c.queue[r & 1]; PathQueue& qout = c.queue[(r + 1) & 1];
-        uint32_t* cin = &c.queueCounts[r * cstride]; uint32_t* cout = &c.queueCounts[(r + 1) * cstride];
+        uint32_t* cin = &c.queueCounts.data()[r * cstride]; uint32_t* cout = &c.queueCounts.data()[(r + 1) * cstride];
         timing_begin(c, c.evShade, c.nShade);
         launch_shade(c, sv, fv, tx, qin, qout, aux, segCap, cin, cout, grid, c.stream, 0u, nsq);
         timing_end(c, c.evShade, c.nShade); c.nShade++;
         if (r == rounds) break;
         timing_begin(c, c.evExtend, c.nExtend);
-        const bool lds = c.blob.bytes <= kBlobLdsMax;
-        const bool flat = c.blob.instCount <= kFlatInstances && !(c.debugFlags & PT_DEBUG_TRAVERSAL_PHASED);
-        const uint32_t smem = (flat ? kFlatLdsFixed : kExtendLdsFixed) + (lds ? c.blob.bytes : 0u);
-        if (c.debugFlags & PT_DEBUG_BRUTE_FORCE) k_extend_brute<<<grid, 256, 0, c.stream>>>(sv.accel, c.blob, ac, qout, segCap, cout, c.counters, c.sqShift);
+        const bool lds = c.scene.blob.bytes <= kBlobLdsMax;
+        const bool flat = c.scene.blob.instCount <= kFlatInstances && !(c.debugFlags & PT_DEBUG_TRAVERSAL_PHASED);
+        const uint32_t smem = (flat ? kFlatLdsFixed : kExtendLdsFixed) + (lds ? c.scene.blob.bytes : 0u);
+        if (c.debugFlags & PT_DEBUG_BRUTE_FORCE) k_extend_brute<<<grid, 256, 0, c.stream>>>(sv.accel, c.scene.blob, ac, qout, segCap, cout, c.counters.data(), c.sqShift);
         else if (c.debugFlags & PT_DEBUG_TRAVERSAL_V1) {
-            if (stats) k_extend<true><<<grid, 256, 0, c.stream>>>(c.blob, ac, qout, segCap, cout, c.counters, c.sqShift);
-            else k_extend<false><<<grid, 256, 0, c.stream>>>(c.blob, ac, qout, segCap, cout, c.counters, c.sqShift);
+            if (stats) k_extend<true><<<grid, 256, 0, c.stream>>>(c.scene.blob, ac, qout, segCap, cout, c.counters.data(), c.sqShift);
+            else k_extend<false><<<grid, 256, 0, c.stream>>>(c.scene.blob, ac, qout, segCap, cout, c.counters.data(), c.sqShift);
         } else {
             const bool wt = aux != nullptr;                            // denoiser modes need CommittedRayT
-            #define PT_EXT2(S, L, W, F) k_extend2<S, L, W, F><<<grid, 256, smem, c.stream>>>(c.blob, ac, qout, segCap, cout, c.counters, c.sqShift)
+            #define PT_EXT2(S, L, W, F) k_extend2<S, L, W, F><<<grid, 256, smem, c.stream>>>(c.scene.blob, ac, qout, segCap, cout, c.counters.data(), c.sqShift)
             #define PT_EXT2_F(S, L, W) do { if (flat) PT_EXT2(S, L, W, true); else PT_EXT2(S, L, W, false); } while (0)
             #define PT_EXT2_W(S, L) do { if (wt) PT_EXT2_F(S, L, true); else PT_EXT2_F(S, L, false); } while (0)
             #define PT_EXT2_L(S) do { if (lds) PT_EXT2_W(S, true); else PT_EXT2_W(S, false); } while (0)
@@ -944,35 +932,27 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
     const PtGraphicsSettings& gs = c.settings;
     const uint32_t npix = fv.width * fv.localRows;
     c.lastIterations = 0;
-    if (c.normalsShared && c.blasTableDev && c.blob.triCount > c.shadeRecCap) {       // the frame's normal records: 20 B per triangle packet (grow-only)
+    if (c.normalsShared && c.scene.blasTable && c.scene.blob.triCount > c.shadeRecB.capacity()) {       // the frame's normal records: 20 B per triangle packet (grow-only)
         hipError_t ea = hipStreamSynchronize(c.stream);
         if (ea != hipSuccess) return ea;
-        if (c.shadeRecA) hipFree(c.shadeRecA);
-        if (c.shadeRecB) hipFree(c.shadeRecB);
-        c.shadeRecA = nullptr; c.shadeRecB = nullptr; c.shadeRecCap = 0;
-        if ((ea = hipMalloc((void**)&c.shadeRecA, sizeof(uint4) * (size_t)c.blob.triCount)) != hipSuccess) return ea;
-        if ((ea = hipMalloc((void**)&c.shadeRecB, sizeof(uint32_t) * (size_t)c.blob.triCount)) != hipSuccess) return ea;
-        c.shadeRecCap = c.blob.triCount;
+        c.shadeRecA.reset(); c.shadeRecB.reset();
+        if ((ea = c.shadeRecA.reserve(c.scene.blob.triCount)) != hipSuccess) return ea;
+        if ((ea = c.shadeRecB.reserve(c.scene.blob.triCount)) != hipSuccess) return ea;   // last: the grow decision reads its capacity
     }
     if (npix == 0 || gs.SamplesPerPixel == 0) return hipSuccess;
     // a round = one k_shade + one k_extend. Per sample a path spends one round as "fresh" (bounce 0, no ray) and at
     // most Bounces rounds as "traced": spp * (Bounces + 1) rounds empty every queue.
     const uint32_t rounds = gs.SamplesPerPixel * (gs.Bounces + 1u);
     const uint32_t tiles = (npix + 255u) / 256u;
-    c.sqShift = c.blob.bytes <= kBlobLdsMax ? kSubQueueShiftFused : kSubQueueShiftStream;          // (pt_internal.hpp: who likes how many sub-queues)
+    c.sqShift = c.scene.blob.bytes <= kBlobLdsMax ? kSubQueueShiftFused : kSubQueueShiftStream;          // (pt_internal.hpp: who likes how many sub-queues)
     const uint32_t nsq = 1u << c.sqShift, cstride = 3u * nsq;
     const uint32_t segCap = (tiles + nsq - 1) / nsq * 256u;                   // entries per sub-queue segment
     hipError_t e = ensure_queues(c, segCap * nsq, (rounds + 2) * cstride);
     if (e != hipSuccess) return e;
-    if (!c.frameConstants && (e = hipMalloc((void**)&c.frameConstants, sizeof(FrameConstants))) != hipSuccess) return e;
-    if (gs.Denoiser != PT_DENOISER_NONE && npix > c.pixelAuxCapacity) {
-        if (c.pixelAux) hipFree(c.pixelAux);
-        c.pixelAux = nullptr; c.pixelAuxCapacity = 0;
-        if ((e = hipMalloc((void**)&c.pixelAux, (size_t)npix * sizeof(float2))) != hipSuccess) return e;
-        c.pixelAuxCapacity = npix;
-    }
+    if ((e = c.frameConstants.reserve(1)) != hipSuccess) return e;
+    if (gs.Denoiser != PT_DENOISER_NONE && (e = c.pixelAux.reserve(npix)) != hipSuccess) return e;
     FrameConstants fc; fc.cam = c.camera; fc.sd = c.sceneData; fc.gs = c.settings;
-    k_set_constants<<<1, 256, 0, c.stream>>>(fc, c.frameConstants, c.queueCounts, (rounds + 2u) * cstride);
+    k_set_constants<<<1, 256, 0, c.stream>>>(fc, c.frameConstants.data(), c.queueCounts.data(), (rounds + 2u) * cstride);
     // persistent grid, but never more blocks than the queue has tiles: surplus blocks only cost dispatch slots and LDS that
     // a concurrent frame's kernels (other streams) could use -- this matters for small shards (1/8 of a 1080p frame = 1013 tiles)
     const uint32_t grid = std::min(persistent_grid(c), (tiles + nsq - 1) / nsq * nsq);
@@ -981,28 +961,23 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
     // everything the launch sequence depends on: the key of the per-round argument blocks and of the captured graph
     std::string key;
     key_add(key, sv); key_add(key, fv); key_add(key, tx); key_add(key, rounds); key_add(key, segCap); key_add(key, grid);
-    key_add(key, c.queue[0]); key_add(key, c.queue[1]); key_add(key, c.queueCounts); key_add(key, c.blob); key_add(key, c.heapHasTextures);
-    key_add(key, c.frameConstants); key_add(key, c.primaryRecords); key_add(key, c.stream); key_add(key, c.pixelAux); key_add(key, gs.Denoiser); key_add(key, c.debugFlags); key_add(key, gs.IsDIEnabled != 0u);
+    key_add(key, c.queue[0]); key_add(key, c.queue[1]); key_add(key, c.queueCounts.data()); key_add(key, c.scene.blob); key_add(key, c.heapHasTextures);
+    key_add(key, c.frameConstants.data()); key_add(key, c.primaryRecords.data()); key_add(key, c.stream); key_add(key, c.pixelAux.data()); key_add(key, gs.Denoiser); key_add(key, c.debugFlags); key_add(key, gs.IsDIEnabled != 0u);
     key_add(key, c.framesInFlight); key_add(key, c.sqShift); key_add(key, c.chains);
-    key_add(key, c.shadeRecA); key_add(key, c.blasTableDev); key_add(key, c.blasTableCount); key_add(key, c.blasTableMaxTris); key_add(key, normal_records_usable(c));
-    if (key != c.roundArgsKey || !c.roundArgs) {                              // k_round's argument blocks, one per round (device memory)
-        if (rounds + 1 > c.roundArgsCap) {
-            if (c.roundArgs) hipFree(c.roundArgs);
-            c.roundArgs = nullptr; c.roundArgsCap = 0;
-            if ((e = hipMalloc((void**)&c.roundArgs, sizeof(RoundArgs) * (rounds + 1))) != hipSuccess) return e;
-            c.roundArgsCap = rounds + 1;
-        }
+    key_add(key, c.shadeRecA.data()); key_add(key, c.scene.blasTable); key_add(key, c.scene.blasTableCount); key_add(key, c.scene.blasTableMaxTris); key_add(key, normal_records_usable(c));
+    if (key != c.roundArgsKey || !c.roundArgs.data()) {                              // k_round's argument blocks, one per round (device memory)
+        if ((e = c.roundArgs.reserve(rounds + 1)) != hipSuccess) return e;
         std::vector<RoundArgs> host(rounds + 1);
-        float2* aux = gs.Denoiser != PT_DENOISER_NONE ? c.pixelAux : nullptr;
+        float2* aux = gs.Denoiser != PT_DENOISER_NONE ? c.pixelAux.data() : nullptr;
         for (uint32_t r = 0; r <= rounds; r++) {
             RoundArgs& a = host[r];
             std::memset(&a, 0, sizeof a);
-            a.sv = sv; a.fv = fv; a.tx = tx; a.bv = c.blob; a.qin = c.queue[r & 1]; a.qout = c.queue[(r + 1) & 1];
-            a.fc = c.frameConstants; a.aux = aux; a.countIn = &c.queueCounts[r * cstride]; a.countOut = &c.queueCounts[(r + 1) * cstride]; a.sqShift = c.sqShift;
-            a.counters = c.counters; a.segCap = segCap; a.primary = c.primaryRecords; a.objectsInLds = round_objects_in_lds(c, sv);
-            if (normal_records_usable(c)) { a.recA = c.shadeRecA; a.recB = c.shadeRecB; a.recordsInLds = round_records_in_lds(c, sv); }
+            a.sv = sv; a.fv = fv; a.tx = tx; a.bv = c.scene.blob; a.qin = c.queue[r & 1]; a.qout = c.queue[(r + 1) & 1];
+            a.fc = c.frameConstants.data(); a.aux = aux; a.countIn = &c.queueCounts.data()[r * cstride]; a.countOut = &c.queueCounts.data()[(r + 1) * cstride]; a.sqShift = c.sqShift;
+            a.counters = c.counters.data(); a.segCap = segCap; a.primary = c.primaryRecords.data(); a.objectsInLds = round_objects_in_lds(c, sv);
+            if (normal_records_usable(c)) { a.recA = c.shadeRecA.data(); a.recB = c.shadeRecB.data(); a.recordsInLds = round_records_in_lds(c, sv); }
         }
-        if ((e = hipMemcpyAsync(c.roundArgs, host.data(), sizeof(RoundArgs) * (rounds + 1), hipMemcpyHostToDevice, c.stream)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(c.roundArgs.data(), host.data(), sizeof(RoundArgs) * (rounds + 1), hipMemcpyHostToDevice, c.stream)) != hipSuccess) return e;
         if ((e = hipStreamSynchronize(c.stream)) != hipSuccess) return e;    // once per change of the scene / frame geometry, never per frame
         c.roundArgsKey = key;
     }
@@ -1010,8 +985,8 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
     // hipGraph replay: launch-bound frames (small shards, tail rounds) cost ~75 launches; a replay is one submission.
     const bool graphable = c.stream != nullptr && !c.timing && !c.disableGraphs &&
                            (c.debugFlags & ~(PT_DEBUG_UNFUSED_ROUNDS | PT_DEBUG_TRAVERSAL_PHASED | PT_DEBUG_LOCKSTEP | PT_DEBUG_GATHER_LOCAL_ONLY | PT_DEBUG_GATHER_SELF_EXCHANGE)) == 0;   // counters / validation variants launch directly
-    auto capture = [&](hipStream_t s, hipGraphExec_t& exec, auto&& body) -> hipError_t {          // one linear graph from what `body` enqueues on s
-        if (exec) { hipStreamSynchronize(c.stream); hipGraphExecDestroy(exec); exec = nullptr; }   // its last replay may still be running (once per change of scene / frame geometry)
+    auto capture = [&](hipStream_t s, GraphExec& exec, auto&& body) -> hipError_t {               // one linear graph from what `body` enqueues on s
+        if (exec) { hipStreamSynchronize(c.stream); exec.reset(); }                                 // its last replay may still be running (once per change of scene / frame geometry)
         hipGraph_t graph = nullptr;
         hipError_t ce = hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed);
         if (ce == hipSuccess) {
@@ -1019,38 +994,39 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
             ce = hipStreamEndCapture(s, &graph);
             if (ce == hipSuccess) ce = e2;
         }
-        if (ce == hipSuccess) ce = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        hipGraphExec_t ge = nullptr;
+        if (ce == hipSuccess) ce = hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0);
         if (graph) hipGraphDestroy(graph);
-        if (ce != hipSuccess) { exec = nullptr; (void)hipGetLastError(); }
+        if (ce == hipSuccess) exec.reset(ge); else (void)hipGetLastError();
         return ce;
     };
     const uint32_t chains = frame_form(c).first ? frame_chains(c, graphable) : 1u;
     if (graphable && chains > 1) {
         // every chain a linear graph on a stream of its own; the preamble is launched directly (two kernels)
-        if (!c.chainFork && (e = hipEventCreateWithFlags(&c.chainFork, hipEventDisableTiming)) != hipSuccess) return e;
+        if (!c.chainFork && (e = create_event(c.chainFork, hipEventDisableTiming)) != hipSuccess) return e;
         for (uint32_t g = 1; g < chains; g++) {
-            if (!c.chainStream[g - 1] && (e = hipStreamCreateWithFlags(&c.chainStream[g - 1], hipStreamNonBlocking)) != hipSuccess) return e;
-            if (!c.chainJoin[g - 1] && (e = hipEventCreateWithFlags(&c.chainJoin[g - 1], hipEventDisableTiming)) != hipSuccess) return e;
+            if (!c.chainStream[g - 1] && (e = create_stream(c.chainStream[g - 1], hipStreamNonBlocking)) != hipSuccess) return e;
+            if (!c.chainJoin[g - 1] && (e = create_event(c.chainJoin[g - 1], hipEventDisableTiming)) != hipSuccess) return e;
         }
         if (key != c.chainGraphKey) {
             c.chainGraphKey.clear();
             for (uint32_t g = 0; g < chains; g++) {
-                hipStream_t s = g == 0 ? c.stream : c.chainStream[g - 1];
+                hipStream_t s = g == 0 ? c.stream : c.chainStream[g - 1].get();
                 if (capture(s, c.chainGraph[g], [&] { return enqueue_chain(c, sv, fv, tx, rounds, segCap, grid, g, chains, s); }) != hipSuccess) { c.disableGraphs = true; break; }
             }
             if (!c.disableGraphs) c.chainGraphKey = key;
         }
         if (!c.disableGraphs) {
             if ((e = enqueue_preamble(c, sv, fv, tx, segCap, grid)) != hipSuccess) return e;
-            if ((e = hipEventRecord(c.chainFork, c.stream)) != hipSuccess) return e;
+            if ((e = hipEventRecord(c.chainFork.get(), c.stream)) != hipSuccess) return e;
             for (uint32_t g = 1; g < chains; g++) {
-                hipStream_t s = c.chainStream[g - 1];
-                if ((e = hipStreamWaitEvent(s, c.chainFork, 0)) != hipSuccess) return e;
-                if ((e = hipGraphLaunch(c.chainGraph[g], s)) != hipSuccess) return e;
-                if ((e = hipEventRecord(c.chainJoin[g - 1], s)) != hipSuccess) return e;
+                hipStream_t s = c.chainStream[g - 1].get();
+                if ((e = hipStreamWaitEvent(s, c.chainFork.get(), 0)) != hipSuccess) return e;
+                if ((e = hipGraphLaunch(c.chainGraph[g].get(), s)) != hipSuccess) return e;
+                if ((e = hipEventRecord(c.chainJoin[g - 1].get(), s)) != hipSuccess) return e;
             }
-            if ((e = hipGraphLaunch(c.chainGraph[0], c.stream)) != hipSuccess) return e;
-            for (uint32_t g = 1; g < chains; g++) if ((e = hipStreamWaitEvent(c.stream, c.chainJoin[g - 1], 0)) != hipSuccess) return e;
+            if ((e = hipGraphLaunch(c.chainGraph[0].get(), c.stream)) != hipSuccess) return e;
+            for (uint32_t g = 1; g < chains; g++) if ((e = hipStreamWaitEvent(c.stream, c.chainJoin[g - 1].get(), 0)) != hipSuccess) return e;
             return hipSuccess;
         }
     } else if (graphable) {
@@ -1059,7 +1035,7 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
             if (capture(c.stream, c.graphExec, [&] { return enqueue_frame(c, sv, fv, tx, rounds, segCap, grid, 1u); }) != hipSuccess) c.disableGraphs = true;
             else c.graphKey = key;
         }
-        if (c.graphExec) return hipGraphLaunch(c.graphExec, c.stream);
+        if (c.graphExec) return hipGraphLaunch(c.graphExec.get(), c.stream);
     }
     return enqueue_frame(c, sv, fv, tx, rounds, segCap, grid, frame_form(c).first ? frame_chains(c, false) : 1u);
 }

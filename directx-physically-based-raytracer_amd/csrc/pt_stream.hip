@@ -265,8 +265,8 @@ hipError_t launch_shade(Context& c, const SceneView& sv, const FrameView& fv, co
                         uint32_t segCap, const uint32_t* countIn, uint32_t* countOut, uint32_t grid, hipStream_t stream, uint32_t sqBase, uint32_t sqCount)
 {
     const bool rec = normal_records_usable(c);
-    const uint4* recA = rec ? c.shadeRecA : nullptr; const uint32_t* recB = rec ? c.shadeRecB : nullptr;
-    #define PT_SHADE(T, D) k_shade<T, D><<<grid, 256, 0, stream>>>(sv, fv, c.frameConstants, tx, qin, qout, aux, segCap, countIn, countOut, c.primaryRecords, c.blob, recA, recB, c.sqShift, sqBase, sqCount)
+    const uint4* recA = rec ? c.shadeRecA.data() : nullptr; const uint32_t* recB = rec ? c.shadeRecB.data() : nullptr;
+    #define PT_SHADE(T, D) k_shade<T, D><<<grid, 256, 0, stream>>>(sv, fv, c.frameConstants.data(), tx, qin, qout, aux, segCap, countIn, countOut, c.primaryRecords.data(), c.scene.blob, recA, recB, c.sqShift, sqBase, sqCount)
     if (c.settings.IsDIEnabled) { if (c.heapHasTextures) PT_SHADE(true, true); else PT_SHADE(false, true); }
     else { if (c.heapHasTextures) PT_SHADE(true, false); else PT_SHADE(false, false); }
     #undef PT_SHADE
@@ -284,7 +284,7 @@ hipError_t launch_extend_stream(Context& c, const AlphaContext& ac, const PathQu
     const uint32_t nsq = 1u << c.sqShift;
     const uint32_t whole = std::max(nsq, std::min(grid, c.framesInFlight > 1 ? kStreamGridShared : kStreamGridAlone));
     const uint32_t sgrid = std::max(1u, whole / nsq) * sqCount;
-    #define PT_XS(S, W) k_extend_stream<S, W><<<sgrid, 256, kStreamLdsStack, stream>>>(c.blob, ac, q, segCap, count, cursor, c.counters, sqBase, sqCount)
+    #define PT_XS(S, W) k_extend_stream<S, W><<<sgrid, 256, kStreamLdsStack, stream>>>(c.scene.blob, ac, q, segCap, count, cursor, c.counters.data(), sqBase, sqCount)
     if (stats) { if (writeT) PT_XS(true, true); else PT_XS(true, false); } else { if (writeT) PT_XS(false, true); else PT_XS(false, false); }
     #undef PT_XS
     return hipGetLastError();

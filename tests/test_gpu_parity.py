@@ -920,6 +920,71 @@ def test_static_bottom_levels_live_in_the_traversal_copy_only(ptamd, oracle, pkg
         ctx.close()
 
 
+def test_viewer_outlives_its_owner(ptamd, pkg):
+    """pt_destroy of a context that another still views (pt_share_scene): the viewer's render answers PT_ERROR_NOT_READY (status -4); the
+    viewer can then build a scene of its own on the same context and renders the same bits as a fresh context; closing it is clean."""
+    S = pkg.scenes
+    W, H = 64, 36
+    gs = S.graphics_settings(W, H, spp=1, bounces=2)
+    scene = S.cornell_box(aspect=W / H)
+    fresh = ptamd.DeviceContext(0)
+    try:
+        rf = ptamd.Renderer(fresh, ptamd.Scene(fresh, scene), W, H, with_f32=True)
+        rf.render(gs); fresh.sync()
+        want = ptamd.textures_to_numpy(rf.textures)["RadianceF32"]
+    finally:
+        fresh.close()
+    owner, viewer = ptamd.DeviceContext(0), ptamd.DeviceContext(0)
+    try:
+        so = ptamd.Scene(owner, scene)
+        rv = ptamd.Renderer(viewer, ptamd.SharedScene(viewer, so), W, H, with_f32=True)
+        rv.render(gs); viewer.sync()
+        owner.close()                                             # the owner goes first
+        with pytest.raises(ptamd.PtError, match="status -4"):
+            rv.render(gs)
+        own = ptamd.Renderer(viewer, ptamd.Scene(viewer, scene), W, H, with_f32=True)
+        own.render(gs); viewer.sync()
+        assert np.array_equal(ptamd.textures_to_numpy(own.textures)["RadianceF32"].view(np.uint32), want.view(np.uint32))
+    finally:
+        viewer.close()
+        owner.close()
+
+
+def test_sharing_gives_adopted_bottom_levels_their_arrays_back(ptamd, pkg):
+    """pt_share_scene on a context whose static bottom levels live in its traversal copy: they get arrays of their own again before the copy
+    goes (OwnedBottomLevelBytes > 0). Rebinding its own scene and rebuilding its own top level adopts them again (OwnedBottomLevelBytes 0) and
+    renders the frame it rendered before sharing, bit for bit."""
+    import ctypes as C
+    S = pkg.scenes
+    W, H = 64, 36
+    gs = S.graphics_settings(W, H, spp=2, bounces=3)
+    a, b = S.cornell_box(aspect=W / H), S.instanced_grid(n=4, aspect=W / H)
+    ctx, other = ptamd.DeviceContext(0), ptamd.DeviceContext(0)
+    try:
+        ga = ptamd.Scene(ctx, a)
+        assert ctx.accel_stats().OwnedBottomLevelBytes == 0
+        ra = ptamd.Renderer(ctx, ga, W, H, with_f32=True)
+        ra.render(gs); ctx.sync()
+        before = ptamd.textures_to_numpy(ra.textures)["RadianceF32"]
+        gb = ptamd.Scene(other, b)
+        ptamd.SharedScene(ctx, gb)                                # materialises ctx's adopted bottom levels
+        st = ctx.accel_stats()
+        assert st.SharedScene == 1 and st.OwnedBottomLevelBytes > 0
+        ctx.check(ctx.lib.pt_heap_resize(ctx.handle, len(a.heap)))                  # the view had copied the other context's descriptor table
+        for i, (item, t) in enumerate(zip(a.heap, ga._heap_dev)):
+            ctx.check(ctx.lib.pt_heap_set_buffer(ctx.handle, i, C.c_void_p(t.data_ptr()), item.array.nbytes, item.stride))
+        ctx.check(ctx.lib.pt_set_object_data(ctx.handle, ga.object_data.data_ptr(), len(a.object_data)))
+        ctx.check(ctx.lib.pt_set_instance_data(ctx.handle, ga.instance_data.data_ptr(), len(a.instance_data)))
+        ga._build_top_level()
+        st = ctx.accel_stats()
+        assert st.SharedScene == 0 and st.OwnedBottomLevelBytes == 0
+        ra.render(gs); ctx.sync()
+        assert np.array_equal(ptamd.textures_to_numpy(ra.textures)["RadianceF32"].view(np.uint32), before.view(np.uint32))
+    finally:
+        ctx.close()
+        other.close()
+
+
 def test_scene_inputs_are_validated(ptamd, pkg):
     """indices the kernels dereference are checked once per scene change, with a message naming the culprit."""
     import torch
