@@ -14,6 +14,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "pt_shade.hpp"
 
@@ -282,6 +283,120 @@ PT_DEV void di_initial(const DIArgs& a, const DISurface& s, uint32_t x, uint32_t
     }
 }
 
+// ---- local-light sampling (pt_di_set_light_sampling; DESIGN.md section 1, "Local-light sampling") ------------------------------------
+// The RTXDI SDK's static parameters. The SDK is not in the reference tree: these are its defaults from memory, unpinned.
+constexpr uint32_t kDITileCount = 128u, kDITileSize = 1024u;       // Power_RIS: light tiles x entries
+constexpr uint32_t kDIScreenTile = 16u;                            // pixels per side of the screen tile that shares one light tile
+constexpr uint32_t kDIGrid = 16u, kDICellLights = 512u;            // ReGIR Grid mode: cells per axis, lights per cell
+constexpr float kDIJitterScale = 2.0f;                             // max(0, 2 * samplingJitter) with jitter 1 (RTXDI.ixx:93)
+constexpr uint32_t kDITileEntries = kDITileCount * kDITileSize, kDICellEntries = kDIGrid * kDIGrid * kDIGrid * kDICellLights;
+constexpr uint32_t kDIPresampleSalt = 0x44490004u, kDIReGIRSalt = 0x44490005u, kDIReGIRCoherentSalt = 0x44490006u, kDIScreenTileSalt = 0x44490007u;
+static_assert(sizeof(PtDILightSamplingSettings) == 16 && sizeof(PtDIPresampledLight) == 8, "layout");
+
+struct DISampling { uint32_t mode; const uint2* tiles; const uint2* cells; float centre[3], cellSize; };
+
+// Power_RIS presampling (LocalLightPresampling.hlsl): one entry per thread, a power-proportional light from the prefix sum and its
+// inverse selection pdf. Seeded as ReGIRPresampling.hlsl splits its index: (g & 0xfff, g >> 12).
+__global__ __launch_bounds__(256) void k_di_presample_tiles(const float4* __restrict__ lights, const float* __restrict__ cdf, const float* __restrict__ total,
+                                                            uint32_t count, uint32_t frameIndex, uint2* __restrict__ tiles)
+{
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= kDITileEntries) return;
+    const float t = *total;
+    uint2 e = make_uint2(~0u, 0u);
+    if (t > 0.0f && isfinite(t)) {
+        uint32_t rng = ml_hash(rng_init(g & 0xFFFu, g >> 12, frameIndex) ^ kDIPresampleSalt);
+        const uint32_t li = select_light(cdf, count, rng_float(rng) * t, t);
+        e = make_uint2(li, __float_as_uint(t / lights[kLightRec16 * (size_t)li + 1].w));
+    }
+    tiles[g] = e;
+}
+
+// TriangleLight::CalculateWeightForVolume with CalculateAverageDistanceToVolume (Light.hlsli:16-24, 84-95)
+PT_DEV float di_volume_weight(const float4* L, v3 c, float radius)
+{
+    const float4 l0 = L[0], l1 = L[1], l2 = L[2], l3 = L[3], l4 = L[4];
+    const v3 base = V3(l0.x, l0.y, l0.z);
+    if (dot(c - base, V3(l3.x, l3.y, l3.z)) < -radius) return 0.0f;
+    const v3 d = V3(base.x + (l1.x + l2.x) / 3.0f, base.y + (l1.y + l2.y) / 3.0f, base.z + (l1.z + l2.z) / 3.0f) - c;
+    const float dc = sqrtf(dot(d, d));
+    const float value = dc + radius * 1.1547f;
+    const float dist = dc + radius * radius * radius / (value * value);
+    return fminf(l0.w / (dist * dist), 2.0f * kPi) * ml_luminance(V3(l4.x, l4.y, l4.z));
+}
+
+// ReGIR build (ReGIRPresampling.hlsl, Grid mode): one thread per slot, BuildSamples candidates from one Power_RIS tile (chosen by a
+// stream shared by 256 slots), streaming RIS against the cell's sphere (the cell centre, half its diagonal); the slot keeps the light and
+// its contribution weight sum(w) / (p(sel) * BuildSamples), or is empty.
+__global__ __launch_bounds__(256) void k_di_regir_build(const float4* __restrict__ lights, uint32_t count, const uint2* __restrict__ tiles, float cx0, float cy0, float cz0,
+                                                        float cellSize, uint32_t buildSamples, uint32_t frameIndex, uint2* __restrict__ cells)
+{
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= kDICellEntries) return;
+    const uint32_t cell = g / kDICellLights;
+    const uint32_t ix = cell % kDIGrid, iy = (cell / kDIGrid) % kDIGrid, iz = cell / (kDIGrid * kDIGrid);
+    const float h = (float)(kDIGrid / 2u) - 0.5f;
+    const v3 c = V3(cx0 + ((float)ix - h) * cellSize, cy0 + ((float)iy - h) * cellSize, cz0 + ((float)iz - h) * cellSize);
+    const float radius = 0.5f * sqrtf(3.0f) * cellSize;
+    uint32_t rng = ml_hash(rng_init(g & 0xFFFu, g >> 12, frameIndex) ^ kDIReGIRSalt);
+    uint32_t coherent = ml_hash(rng_init(g >> 8, 0u, frameIndex) ^ kDIReGIRCoherentSalt);
+    const uint2* tile = tiles + min((uint32_t)(rng_float(coherent) * (float)kDITileCount), kDITileCount - 1u) * kDITileSize;
+    float wsum = 0.0f, pSel = 0.0f;
+    uint32_t sel = ~0u;
+    for (uint32_t k = 0; k < buildSamples; k++) {
+        const float u = rng_float(rng), r = rng_float(rng);
+        const uint2 e = tile[min((uint32_t)(u * (float)kDITileSize), kDITileSize - 1u)];
+        const float p = e.x < count ? di_volume_weight(lights + kLightRec16 * (size_t)e.x, c, radius) : 0.0f;
+        const float w = p > 0.0f ? p / (1.0f / __uint_as_float(e.y)) : 0.0f;      // target / source pdf
+        wsum += w;
+        if (r * wsum < w) { sel = e.x; pSel = p; }
+    }
+    cells[g] = pSel > 0.0f ? make_uint2(sel, __float_as_uint(wsum / (pSel * (float)buildSamples))) : make_uint2(~0u, 0u);
+}
+
+// initial sampling with the Uniform, Power_RIS or ReGIR candidates: di_initial with another source of (light, source pdf). Power_RIS: the
+// pixel's screen tile picks a light tile. ReGIR: three jitter draws from the pixel stream pick the cell; outside the grid, Power_RIS.
+PT_DEV void di_initial_ls(const DIArgs& a, const DISampling& ls, const DISurface& s, uint32_t x, uint32_t y, float total, DIInitial& o)
+{
+    uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDISalt);
+    o.wsum = 0.0f; o.p = 0.0f; o.u = 0.0f; o.v = 0.0f; o.li = ~0u;
+    o.dif = V3(0, 0, 0); o.spc = V3(0, 0, 0); o.pos = V3(0, 0, 0);
+    const uint2* src = nullptr;
+    uint32_t span = 0;
+    if (ls.mode != PT_DI_LOCAL_LIGHT_UNIFORM) {
+        uint32_t ts = ml_hash(rng_init(x / kDIScreenTile, y / kDIScreenTile, a.frameIndex) ^ kDIScreenTileSalt);
+        src = ls.tiles + min((uint32_t)(rng_float(ts) * (float)kDITileCount), kDITileCount - 1u) * kDITileSize;
+        span = kDITileSize;
+    }
+    if (ls.mode == PT_DI_LOCAL_LIGHT_REGIR_RIS) {
+        const float jx = (rng_float(rng) - 0.5f) * kDIJitterScale, jy = (rng_float(rng) - 0.5f) * kDIJitterScale, jz = (rng_float(rng) - 0.5f) * kDIJitterScale;
+        const float fx = floorf((s.P.x + jx * ls.cellSize - ls.centre[0]) / ls.cellSize), fy = floorf((s.P.y + jy * ls.cellSize - ls.centre[1]) / ls.cellSize),
+                    fz = floorf((s.P.z + jz * ls.cellSize - ls.centre[2]) / ls.cellSize);
+        const float lim = (float)(kDIGrid / 2u);
+        if (fx >= -lim && fx < lim && fy >= -lim && fy < lim && fz >= -lim && fz < lim) {
+            const uint32_t cell = (((uint32_t)((int)fz + (int)(kDIGrid / 2u)) * kDIGrid) + (uint32_t)((int)fy + (int)(kDIGrid / 2u))) * kDIGrid + (uint32_t)((int)fx + (int)(kDIGrid / 2u));
+            src = ls.cells + (size_t)cell * kDICellLights;
+            span = kDICellLights;
+        }
+    }
+    for (uint32_t k = 0; k < a.samples; k++) {
+        const float r0 = rng_float(rng), r1 = rng_float(rng), r2 = rng_float(rng), r3 = rng_float(rng);
+        uint32_t li;
+        float pdf;                                                          // source pdf of the light
+        if (src) {
+            const uint2 e = src[min((uint32_t)(r0 * (float)span), span - 1u)];
+            li = e.x; pdf = 1.0f / __uint_as_float(e.y);
+        } else {
+            li = min((uint32_t)(r0 * (float)a.count), a.count - 1u); pdf = 1.0f / (float)a.count;
+        }
+        v3 pos = V3(0, 0, 0), dif = V3(0, 0, 0), spc = V3(0, 0, 0);
+        const float p = li < a.count ? di_target(a, s, li, r1, r2, pos, dif, spc) : 0.0f;    // an empty slot: weight 0, still counted in M
+        const float ris = p > 0.0f ? p / pdf : 0.0f;
+        o.wsum += ris;
+        if (r3 * o.wsum < ris) { o.p = p; o.dif = dif; o.spc = spc; o.pos = pos; o.u = r1; o.v = r2; o.li = li; }
+    }
+}
+
 // final shading (DIFinalShading.hlsl): one coloured visibility ray, CreateVisibilityRay with offset 1e-3; outputs :78-103
 PT_DEV void di_final(const DIArgs& a, BlobView bv, const AlphaContext& ac, DeviceCounters* counters, uint2* ldsStack, size_t pi, v3 P, v3 posSel,
                      v3 difSel, v3 spcSel, float W)
@@ -416,6 +531,25 @@ __global__ __launch_bounds__(256) void k_di(DIArgs a, BlobView bv, AlphaContext 
     ((ushort4*)tx.Specular)[pi] = make_ushort4(f32_to_f16(spc.x), f32_to_f16(spc.y), f32_to_f16(spc.z), f32_to_f16(dist));
 }
 
+// k_di with the Uniform, Power_RIS or ReGIR candidates (the mode is uniform over the grid); the same pixel mapping, surface and final shading.
+__global__ __launch_bounds__(256) void k_di_ls(DIArgs a, DISampling ls, BlobView bv, AlphaContext ac, DeviceCounters* counters)
+{
+    const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63u;
+    const uint32_t x = blockIdx.x * 16 + (wv & 1u) * 8u + (ln & 7u), ly = blockIdx.y * 16 + (wv >> 1) * 8u + (ln >> 3);
+    if (x >= a.fv.width || ly >= a.fv.localRows) return;                 // no barrier below
+    const uint32_t y = global_row(a.fv, ly);
+    const size_t pi = (size_t)ly * a.fv.width + x;
+    DISurface s;
+    if (!di_surface(current_gbuffer(a.tx), pi, x, y, a.fv, a.cam.jitter, a.cam.projectionToView, a.cam.viewToWorld, a.cam.position, a.ext, s)) return;
+    const float total = *a.total;
+    if (!(total > 0.0f) || !isfinite(total)) return;
+    DIInitial i0;
+    di_initial_ls(a, ls, s, x, y, total, i0);
+    if (!(i0.p > 0.0f)) return;
+    __shared__ uint2 ldsStack[kLdsStackDepth * 256];
+    di_final(a, bv, ac, counters, ldsStack, pi, s.P, i0.pos, i0.dif, i0.spc, i0.wsum / (float)a.samples / i0.p);
+}
+
 // ---- reservoir reuse (DITemporalResampling / DISpatialResampling; DESIGN.md section 1, "Reservoir reuse") --------------------------------
 constexpr uint32_t kDITemporalSalt = 0x44490002u, kDISpatialSalt = 0x44490003u;
 constexpr uint32_t kDIOffsetCount = 8192u;          // neighbour-offset table entries (int8 x, y)
@@ -429,6 +563,7 @@ struct DIReuseArgs {
     uint32_t haveHistory, maxHistory, boiling, spatialSamples, boostSamples;
     float boilingMul, tDepth, tNormal, radius, sDepth, sNormal;
 };
+struct DIReuseLSArgs : DIReuseArgs { DISampling ls; };   // k_di_initial_temporal with the candidates of di_initial_ls
 
 PT_DEV PtDIReservoir di_empty(uint32_t M)
 {
@@ -472,9 +607,9 @@ PT_DEV float di_target_of(const DIArgs& a, const DISurface& s, uint32_t li, floa
 
 // Initial sampling fused with temporal reuse: the temporal step at a pixel reads only that pixel's fresh reservoir and last frame's data.
 // TEMPORAL = false writes the initial reservoirs (the spatial pass's input). The boiling filter is a 64-lane butterfly over the wave's
-// 8 x 8 tile, so every lane stays to the end.
-template <bool TEMPORAL, bool BASIC>
-__global__ __launch_bounds__(256) void k_di_initial_temporal(DIReuseArgs r)
+// 8 x 8 tile, so every lane stays to the end. ARGS = DIReuseLSArgs: the candidates of di_initial_ls instead of di_initial.
+template <bool TEMPORAL, bool BASIC, typename ARGS = DIReuseArgs>
+__global__ __launch_bounds__(256) void k_di_initial_temporal(ARGS r)
 {
     const DIArgs& a = r.d;
     const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63u;
@@ -489,7 +624,8 @@ __global__ __launch_bounds__(256) void k_di_initial_temporal(DIReuseArgs r)
         const float total = *a.total;
         if (total > 0.0f && isfinite(total)) {
             DIInitial i0;
-            di_initial(a, s, x, y, total, i0);
+            if constexpr (std::is_same<ARGS, DIReuseLSArgs>::value) di_initial_ls(a, r.ls, s, x, y, total, i0);
+            else di_initial(a, s, x, y, total, i0);
             if (i0.p > 0.0f) { res.LightIndex = i0.li; res.U = i0.u; res.V = i0.v; res.W = i0.wsum / (float)a.samples / i0.p; res.TargetPdf = i0.p; }
         }
         if (TEMPORAL) {
@@ -727,6 +863,7 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
     DI_HIP(ensure_light_list(c, sv));
     const uint32_t n = c.lightCount;
     c.lightRecordCount = n;
+    c.diTileCount = 0; c.diCellCount = 0;
     if (!reuse || n == 0 || npix == 0) { c.diHistoryValid = false; c.diResCount = 0; }
     if (n == 0 || npix == 0) return PT_OK;
     const uint32_t nb = (n + kScanBlock - 1u) / kScanBlock;
@@ -742,6 +879,32 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
     k_cdf_local<<<nb, 256, 0, c.stream>>>(power, n, c.lightCdf.data(), c.lightBlockSums.data());
     k_cdf_blocks<<<1, 1, 0, c.stream>>>(c.lightBlockSums.data(), nb);
     k_cdf_add<<<(n + 255u) / 256u, 256, 0, c.stream>>>(c.lightCdf.data(), n, c.lightBlockSums.data(), nb);
+    // local-light sampling: Power_RIS tiles (POWER_RIS, REGIR_RIS), then the ReGIR cells around this render's camera (REGIR_RIS)
+    const PtDILightSamplingSettings& lss = c.diSampling;
+    DISampling ls; memset(&ls, 0, sizeof ls);
+    ls.mode = lss.Mode;
+    if (lss.Mode == PT_DI_LOCAL_LIGHT_POWER_RIS || lss.Mode == PT_DI_LOCAL_LIGHT_REGIR_RIS) {
+        const bool regir = lss.Mode == PT_DI_LOCAL_LIGHT_REGIR_RIS;
+        if (c.diTiles.capacity() < kDITileEntries || (regir && c.diCells.capacity() < kDICellEntries)) {
+            DI_HIP(hipStreamSynchronize(c.stream));
+            DI_HIP(c.diTiles.reserve(kDITileEntries));
+            if (regir) DI_HIP(c.diCells.reserve(kDICellEntries));    // 16 MB, only in ReGIR mode
+        }
+        k_di_presample_tiles<<<kDITileEntries / 256u, 256, 0, c.stream>>>((const float4*)c.lightRecords.data(), c.lightCdf.data(), c.lightBlockSums.data() + nb, n,
+                                                                         s.FrameIndex, (uint2*)c.diTiles.data());
+        DI_HIP(hipGetLastError());
+        c.diTileCount = kDITileEntries;
+        ls.tiles = (const uint2*)c.diTiles.data();
+        if (regir) {
+            memcpy(ls.centre, c.camera.Position, sizeof ls.centre);
+            ls.cellSize = lss.ReGIRCellSize;
+            k_di_regir_build<<<kDICellEntries / 256u, 256, 0, c.stream>>>((const float4*)c.lightRecords.data(), n, ls.tiles, ls.centre[0], ls.centre[1], ls.centre[2],
+                                                                          ls.cellSize, lss.ReGIRBuildSamples, s.FrameIndex, (uint2*)c.diCells.data());
+            DI_HIP(hipGetLastError());
+            c.diCellCount = kDICellEntries;
+            ls.cells = (const uint2*)c.diCells.data();
+        }
+    }
     DIArgs a; memset(&a, 0, sizeof a);
     a.fv = fv; a.tx = *tx;
     memcpy(a.cam.position, c.camera.Position, sizeof a.cam.position); memcpy(a.cam.jitter, c.camera.Jitter, sizeof a.cam.jitter);
@@ -751,7 +914,8 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
     AlphaContext ac; ac.objects = sv.objects; ac.heap = sv.heap; ac.srgbLut = sv.srgbLut; ac.instances = sv.accel.instances; ac.shadeTex = sv.shadeTex;
     const dim3 grid((fv.width + 15u) / 16u, (fv.localRows + 15u) / 16u);
     if (!reuse) {
-        k_di<<<grid, 256, 0, c.stream>>>(a, c.scene.blob, ac, c.counters.data());
+        if (lss.Mode == PT_DI_LOCAL_LIGHT_POWER_CDF) k_di<<<grid, 256, 0, c.stream>>>(a, c.scene.blob, ac, c.counters.data());
+        else k_di_ls<<<grid, 256, 0, c.stream>>>(a, ls, c.scene.blob, ac, c.counters.data());
         DI_HIP(hipGetLastError());
         return PT_OK;
     }
@@ -791,7 +955,14 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
     r.radius = rs.SpatialSamplingRadius; r.sDepth = rs.SpatialDepthThreshold; r.sNormal = rs.SpatialNormalThreshold;
     r.in = c.diResB.data(); r.out = c.diResA.data();
     const bool tb = rs.TemporalBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC, sb = rs.SpatialBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC;
-    if (!temporal) k_di_initial_temporal<false, false><<<grid, 256, 0, c.stream>>>(r);
+    if (lss.Mode != PT_DI_LOCAL_LIGHT_POWER_CDF) {
+        DIReuseLSArgs rl; memset(&rl, 0, sizeof rl);
+        static_cast<DIReuseArgs&>(rl) = r; rl.ls = ls;
+        if (!temporal) k_di_initial_temporal<false, false, DIReuseLSArgs><<<grid, 256, 0, c.stream>>>(rl);
+        else if (tb) k_di_initial_temporal<true, true, DIReuseLSArgs><<<grid, 256, 0, c.stream>>>(rl);
+        else k_di_initial_temporal<true, false, DIReuseLSArgs><<<grid, 256, 0, c.stream>>>(rl);
+    }
+    else if (!temporal) k_di_initial_temporal<false, false><<<grid, 256, 0, c.stream>>>(r);
     else if (tb) k_di_initial_temporal<true, true><<<grid, 256, 0, c.stream>>>(r);
     else k_di_initial_temporal<true, false><<<grid, 256, 0, c.stream>>>(r);
     DI_HIP(hipGetLastError());
@@ -832,6 +1003,38 @@ int pt_di_set_resampling(PtContext* ctx, const PtDIResamplingSettings* s)
     const bool on = v.TemporalResampling || v.SpatialSamples;
     if (on != c.diReuseOn || memcmp(&v, &c.diReuse, sizeof v) != 0) c.diHistoryValid = false;
     c.diReuse = v; c.diReuseOn = on;
+    return PT_OK;
+}
+
+int pt_di_set_light_sampling(PtContext* ctx, const PtDILightSamplingSettings* s)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    PtDILightSamplingSettings v; memset(&v, 0, sizeof v);
+    if (s) {
+        DI_ARG(s->Mode <= PT_DI_LOCAL_LIGHT_REGIR_RIS, "unknown local-light sampling Mode");
+        DI_ARG(std::isfinite(s->ReGIRCellSize) && s->ReGIRCellSize >= 0.1f && s->ReGIRCellSize <= 10.0f, "ReGIRCellSize must be finite and in [0.1, 10]");
+        DI_ARG(s->ReGIRBuildSamples >= 1u && s->ReGIRBuildSamples <= 32u, "ReGIRBuildSamples must be 1..32");
+        v = *s;
+        v._pad = 0;
+    }
+    if (memcmp(&v, &c.diSampling, sizeof v) != 0) c.diHistoryValid = false;
+    c.diSampling = v;
+    return PT_OK;
+}
+
+int pt_di_download_presampled(PtContext* ctx, uint32_t which, PtDIPresampledLight* host_dst, uint32_t capacity, uint32_t* out_count)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    DI_ARG(out_count && (host_dst || capacity == 0), "out_count / host_dst is NULL");
+    DI_ARG(which <= 1u, "which must be 0 (Power_RIS tiles) or 1 (ReGIR cells)");
+    DI_HIP(hipSetDevice(c.device));
+    DI_HIP(hipStreamSynchronize(c.stream));
+    const uint32_t n = which ? c.diCellCount : c.diTileCount;
+    *out_count = n;
+    const uint32_t k = std::min(capacity, n);
+    if (k) DI_HIP(hipMemcpy(host_dst, which ? c.diCells.data() : c.diTiles.data(), sizeof(PtDIPresampledLight) * (size_t)k, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

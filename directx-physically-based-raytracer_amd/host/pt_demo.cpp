@@ -3,11 +3,14 @@
 // optionally dumps the radiance for the parity test (tests/test_host_cpp.py compares it with the oracle).
 //
 //   pt_demo [--width W] [--height H] [--spp S] [--bounces B] [--frames N] [--out file.bin] [--ranks R] [--di] [--di-samples N] [--restir]
+//           [--light-sampling cdf|uniform|power_ris|regir]
 //
 // --di: the direct-lighting pass between the G-buffer and the path tracer (App.cpp:1234-1308), LocalLightSamples = --di-samples (default 8);
 // the path tracer then runs with IsDIEnabled (with Bounces 0 the DI pass is the last render pass and adds to Radiance).
 // --restir (with --di): temporal + spatial reservoir reuse at MyAppData's defaults; the Previous* G-buffer is swapped in before every
 // frame after the first (App.cpp:629-634). Unsharded only.
+// --light-sampling (with --di): how the DI pass draws its candidates (ReSTIRDI.InitialSampling.LocalLight.Mode; default cdf, the power
+// prefix sum); ReGIR at MyAppData's cell size 1 and 8 build samples.
 //
 // --ranks R: one process per GPU. The parent (which never touches a GPU) starts R children `--rank r --world R --id-file F`; rank 0
 // makes the RCCL unique id and leaves it in F, the others pick it up; every rank renders its 16-row bands (BandSharding) and rank 0
@@ -339,7 +342,7 @@ int main(int argc, char** argv)
 {
     uint32_t W = 1920, H = 1080, spp = 4, bounces = 8, frames = 10, ranks = 0, rank = 0, world = 1;
     uint32_t diSamples = 8; bool di = false, restir = false;
-    std::string out, idFile, scenePath, dumpPath;
+    std::string out, idFile, scenePath, dumpPath, lightSampling = "cdf";
     for (int i = 1; i < argc; i++) {
         std::string k = argv[i];
         if (k == "--di") { di = true; continue; }                  // the flags without a value
@@ -352,6 +355,7 @@ int main(int argc, char** argv)
         else if (k == "--ranks") ranks = atoi(v); else if (k == "--rank") rank = atoi(v);
         else if (k == "--world") world = atoi(v); else if (k == "--id-file") idFile = v;
         else if (k == "--di-samples") diSamples = atoi(v);
+        else if (k == "--light-sampling") lightSampling = v;
         else if (k == "--scene") scenePath = v; else if (k == "--dump-scene") dumpPath = v;
     }
     const bool sharded = !idFile.empty();
@@ -471,6 +475,16 @@ int main(int argc, char** argv)
         directLighting.GPUBuffers = { &sd, &cam, dObjects, n };
         directLighting.Textures = tx;
         if (restir && (!di || sharded)) throw std::invalid_argument("--restir needs --di and one unsharded process");
+        if (lightSampling != "cdf") {
+            using Mode = DirectLighting::ReSTIRDILocalLightSamplingMode;
+            DirectLighting::LightSampling l;
+            if (lightSampling == "uniform") l.InitialSampling.LocalLight.Mode = Mode::Uniform;
+            else if (lightSampling == "power_ris") l.InitialSampling.LocalLight.Mode = Mode::Power_RIS;
+            else if (lightSampling == "regir") l.InitialSampling.LocalLight.Mode = Mode::ReGIR_RIS;
+            else throw std::invalid_argument("--light-sampling: cdf, uniform, power_ris or regir");
+            if (!di) throw std::invalid_argument("--light-sampling needs --di");
+            directLighting.SetLightSampling(l);
+        }
         PtDIPreviousTextures& prev = directLighting.PreviousTextures;
         if (restir) {
             prev.PreviousGeometricNormal = alloc(px_ * 4); prev.PreviousLinearDepth = alloc(px_ * 4); prev.PreviousBaseColorMetalness = alloc(px_ * 4);

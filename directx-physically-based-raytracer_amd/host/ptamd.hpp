@@ -206,6 +206,19 @@ struct DirectLighting {
         } SpatialResampling;
     };
 
+    // MyAppData ReSTIRDI.InitialSampling.LocalLight.Mode and ReSTIRDI.ReGIR.{Cell.Size, BuildSamples} (Source/MyAppData.h:200-215).
+    // PowerCDF, this library's default, is not a reference mode; the reference's default is ReGIR_RIS.
+    enum class ReSTIRDILocalLightSamplingMode : uint32_t {
+        PowerCDF = PT_DI_LOCAL_LIGHT_POWER_CDF, Uniform = PT_DI_LOCAL_LIGHT_UNIFORM, Power_RIS = PT_DI_LOCAL_LIGHT_POWER_RIS, ReGIR_RIS = PT_DI_LOCAL_LIGHT_REGIR_RIS
+    };
+    struct LightSampling {
+        struct InitialSampling { struct LocalLight { ReSTIRDILocalLightSamplingMode Mode = ReSTIRDILocalLightSamplingMode::ReGIR_RIS; } LocalLight; } InitialSampling;
+        struct ReGIR {
+            struct Cell { float Size = 1.0f; } Cell;       // [0.1, 10]
+            uint32_t BuildSamples = 8;                      // 1..32
+        } ReGIR;
+    };
+
     struct { const PtSceneData* SceneData; const PtCamera* Camera; const PtObjectData* ObjectData; uint32_t ObjectCount; } GPUBuffers{};
     PtTextures Textures{};                                  // the G-buffer it reads, Diffuse / Specular (or Radiance) it writes
     PtDIPreviousTextures PreviousTextures{};                // RTXDI::Textures Previous*: last frame's G-buffer (temporal resampling)
@@ -230,6 +243,14 @@ struct DirectLighting {
     }
 
     void ResetHistory() { ThrowIfFailed(m_context, pt_di_reset_history(m_context)); }     // App::ResetHistory
+
+    void SetLightSampling(const LightSampling& l)
+    {
+        PtDILightSamplingSettings s{};
+        s.Mode = (uint32_t)l.InitialSampling.LocalLight.Mode;
+        s.ReGIRCellSize = l.ReGIR.Cell.Size; s.ReGIRBuildSamples = l.ReGIR.BuildSamples;
+        ThrowIfFailed(m_context, pt_di_set_light_sampling(m_context, &s));
+    }
 
     void SetConstants(const Settings& settings)
     {

@@ -111,6 +111,27 @@ DI_RESERVOIR = np.dtype({  # PtDIReservoir: one per pixel, row-major
     "formats": ["<u4", "<f4", "<f4", "<f4", "<u4", "<f4", "<u4"],
     "offsets": [0, 4, 8, 12, 16, 20, 24], "itemsize": 32})
 
+DI_LOCAL_LIGHT_POWER_CDF, DI_LOCAL_LIGHT_UNIFORM, DI_LOCAL_LIGHT_POWER_RIS, DI_LOCAL_LIGHT_REGIR_RIS = 0, 1, 2, 3
+DI_LOCAL_LIGHT_MODES = {"cdf": DI_LOCAL_LIGHT_POWER_CDF, "uniform": DI_LOCAL_LIGHT_UNIFORM, "power_ris": DI_LOCAL_LIGHT_POWER_RIS,
+                        "regir": DI_LOCAL_LIGHT_REGIR_RIS}
+
+DI_LIGHT_SAMPLING_SETTINGS = np.dtype({  # PtDILightSamplingSettings: ReSTIRDI.InitialSampling.LocalLight.Mode, ReGIR.{Cell.Size, BuildSamples}
+    "names": ["Mode", "ReGIRCellSize", "ReGIRBuildSamples"], "formats": ["<u4", "<f4", "<u4"], "offsets": [0, 4, 8], "itemsize": 16})
+
+DI_PRESAMPLED_LIGHT = np.dtype({  # PtDIPresampledLight: a Power_RIS tile entry or a ReGIR cell slot; LightIndex 0xFFFFFFFF = empty
+    "names": ["LightIndex", "InvSourcePdf"], "formats": ["<u4", "<f4"], "offsets": [0, 4], "itemsize": 8})
+
+
+def di_light_sampling_settings(mode="regir", cell_size=1.0, build_samples=8):
+    """PtDILightSamplingSettings with the reference's defaults (Source/MyAppData.h:200-215): ReGIR_RIS, cell size 1, 8 build samples.
+    mode: "cdf" (this library's default), "uniform", "power_ris", "regir", or a DI_LOCAL_LIGHT_* value."""
+    s = np.zeros((), DI_LIGHT_SAMPLING_SETTINGS)
+    s["Mode"] = DI_LOCAL_LIGHT_MODES[mode] if isinstance(mode, str) else mode
+    s["ReGIRCellSize"] = cell_size
+    s["ReGIRBuildSamples"] = build_samples
+    return s
+
+
 DI_PREVIOUS_TEXTURES = ["PreviousGeometricNormal", "PreviousLinearDepth", "PreviousBaseColorMetalness", "PreviousNormalRoughness",
                         "PreviousIOR", "PreviousTransmission"]   # PtDIPreviousTextures member order
 

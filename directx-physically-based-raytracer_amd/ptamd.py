@@ -27,6 +27,7 @@ EXPORTS = [
     "pt_raytrace_set_constants", "pt_raytrace_render", "pt_trace_visibility", "pt_bsdf_evaluate", "pt_bsdf_sample", "pt_reset_counters", "pt_get_counters",
     "pt_di_set_constants", "pt_di_render", "pt_di_light_count", "pt_di_download_lights",
     "pt_di_set_resampling", "pt_di_render_with_history", "pt_di_reset_history", "pt_di_download_reservoirs",
+    "pt_di_set_light_sampling", "pt_di_download_presampled",
     "pt_set_debug_flags", "pt_debug_read_mismatch", "pt_debug_download_blob", "pt_debug_trace_ray", "pt_enable_kernel_timing", "pt_get_kernel_timing", "pt_get_round_timing",
 ]
 
@@ -168,6 +169,8 @@ def load_library():
         lib.pt_di_render_with_history.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pt_di_reset_history.argtypes = [C.c_void_p]
         lib.pt_di_download_reservoirs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.pt_di_set_light_sampling.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_di_download_presampled.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.pt_set_debug_flags.argtypes = [C.c_void_p, C.c_uint32]
         lib.pt_debug_read_mismatch.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_debug_download_blob.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -603,6 +606,24 @@ class DirectLighting:
     def ResetHistory(self):
         self.ctx.check(self.ctx.lib.pt_di_reset_history(self.ctx.handle))
 
+    def SetLightSampling(self, settings):
+        """PtDILightSamplingSettings (layouts.di_light_sampling_settings), or None: the power CDF. A changed value resets the history."""
+        if settings is None:
+            self.ctx.check(self.ctx.lib.pt_di_set_light_sampling(self.ctx.handle, None))
+            return
+        self._light_sampling = np.array(settings).reshape(())
+        self.ctx.check(self.ctx.lib.pt_di_set_light_sampling(self.ctx.handle, C.c_void_p(self._light_sampling.ctypes.data)))
+
+    def download_presampled(self, which):
+        """which = 0: the Power_RIS tiles (128 x 1024, tile-major), 1: the ReGIR cells (4096 x 512, cell-major, x fastest) of the last
+        Render (numpy layouts.DI_PRESAMPLED_LIGHT; empty when that render did not fill them)."""
+        n = C.c_uint32(0)
+        self.ctx.check(self.ctx.lib.pt_di_download_presampled(self.ctx.handle, which, None, 0, C.byref(n)))
+        out = np.zeros(n.value, L.DI_PRESAMPLED_LIGHT)
+        if n.value:
+            self.ctx.check(self.ctx.lib.pt_di_download_presampled(self.ctx.handle, which, C.c_void_p(out.ctypes.data), n.value, C.byref(n)))
+        return out
+
     def download_reservoirs(self):
         """The final reservoirs of the last Render (numpy layouts.DI_RESERVOIR, row-major pixels; empty without reuse)."""
         n = C.c_uint32(0)
@@ -651,12 +672,13 @@ class Renderer:
         self.constants["RenderSize"] = (width, height)
         self.constants["Flags"] = L.GBufferFlags.DefaultNoDenoiser        # App.cpp:1224 with Denoiser::None
 
-    def render(self, settings, di_samples=0, di_reuse=None):
+    def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None):
         """di_samples > 0: run the DI pass with that many candidates per pixel; set settings["IsDIEnabled"] to have the path tracer
         consume it (the textures need Diffuse / Specular: with_denoiser_outputs=True). di_reuse: PtDIResamplingSettings
         (layouts.di_resampling_settings) for reservoir reuse; temporal reuse needs di_history=True. With di_history the current and
         Previous* G-buffer textures are swapped before each frame after the first, so that after render() the current ones hold this
-        frame's G-buffer and the Previous* ones the last frame's."""
+        frame's G-buffer and the Previous* ones the last frame's. di_light_sampling: PtDILightSamplingSettings
+        (layouts.di_light_sampling_settings), or None: the power CDF."""
         tlas = self.scene.GetTopLevelAccelerationStructure()
         if self.di_history and self._rendered:
             for n in L.DI_PREVIOUS_TEXTURES:
@@ -670,6 +692,7 @@ class Renderer:
             self.direct_lighting.SetConstants(L.di_settings(self.width, self.height, int(s["FrameIndex"]), di_samples, denoiser,
                                                             last_pass=int(s["Bounces"]) == 0, ext_flags=int(s["ExtFlags"])))
             self.direct_lighting.SetResampling(di_reuse)
+            self.direct_lighting.SetLightSampling(di_light_sampling)
             self.direct_lighting.Render(tlas)
         if int(np.array(settings).reshape(())["Bounces"]) > 0:            # App.cpp:1277
             self.raytracing.SetConstants(settings)

@@ -600,6 +600,34 @@ def instanced_grid(n=100, seed=42, aspect=16 / 9, subdiv=2):
     return Scene(nodes, objects, cam, make_scene_data((0, 0, 0, -1)), name="instanced_grid").finalize()
 
 
+def emitter_field(n=64, seed=11, aspect=16 / 9, height=3.5, span=8.0, power_range=100.0, strength=None):
+    """A floor and n x n small down-facing emissive quads (2 n^2 lights: 8 k for n = 64, 131 k for n = 256) at `height` over it, on a
+    jittered grid over span x span. The quad sides spread over sqrt(power_range), so the light powers spread over ~power_range. The
+    camera is below the emitters (none in view) and looks down at the floor. With the default ReGIR cell size 1 the emitters are 3+ cells
+    above the floor."""
+    rng = np.random.default_rng(seed)
+    pitch = span / n
+    side = pitch * 0.8 * np.sqrt(power_range) ** (rng.random((n, n)) - 1.0)     # in [0.8 pitch / sqrt(range), 0.8 pitch]
+    pos = []
+    for iz in range(n):
+        for ix in range(n):
+            cx = (ix + 0.5) * pitch - span / 2 + (rng.random() - 0.5) * 0.1 * pitch
+            cz = (iz + 0.5) * pitch - span / 2 + (rng.random() - 0.5) * 0.1 * pitch
+            h = side[iz, ix] / 2
+            y = height + rng.random() * 0.25
+            pos += [(cx - h, y, cz - h), (cx + h, y, cz - h), (cx + h, y, cz + h), (cx - h, y, cz + h)]
+    pos = np.array(pos, np.float32)
+    idx = (np.arange(n * n, dtype=np.int64)[:, None] * 4 + np.array([0, 1, 2, 0, 2, 3])).reshape(-1)
+    strength = (4.0 * n * n / 64.0) / float((side ** 2).sum()) * 16.0 if strength is None else strength
+    lights = Mesh(make_vertices(pos, np.tile(np.float32([0, -1, 0]), (len(pos), 1))), make_indices(idx.tolist()), True,
+                  material((0.5, 0.5, 0.5), emissive=(1.0, 0.9, 0.8), strength=strength))
+    floor = quad_mesh((-span, 0, -span), (-span, 0, span), (span, 0, span), (span, 0, -span), (0, 1, 0), material((0.7, 0.7, 0.7), roughness=0.8))
+    nodes = [MeshNode([floor]), MeshNode([lights])]
+    objects = [RenderObject(0, trs()), RenderObject(1, trs())]
+    cam = make_camera((0, 2.0, -3.5), forward=(0, -0.6, 1), hfov_deg=70.0, aspect=aspect)
+    return Scene(nodes, objects, cam, make_scene_data((0, 0, 0, 1)), name=f"emitter_field{n}").finalize()
+
+
 def dynamic_instanced(n=32, aspect=16 / 9, segments=256):
     """n*n static instances + ground + light (instanced_grid) and one skinned column in front of the camera: the per-frame work of a
     dynamic scene -- skinning, bottom-level update of the skinned mesh node, top-level rebuild over ~1 k instances (bench.py

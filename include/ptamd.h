@@ -442,6 +442,35 @@ int  pt_di_reset_history(PtContext* ctx);                                   /* A
 int  pt_di_download_reservoirs(PtContext* ctx, PtDIReservoir* host_dst, uint32_t capacity, uint32_t* out_count);
 
 /* ------------------------------------------------------------------------------------------
+ * how the initial candidates of the DI pass are drawn (ReSTIRDI.InitialSampling.LocalLight.Mode, Source/MyAppData.h:35-39, 212;
+ * ReGIR.Cell.Size / BuildSamples). DESIGN.md section 1, "Local-light sampling", is the arithmetic spec; the RTXDI SDK's static
+ * parameters (128 tiles x 1024 lights, 16-pixel screen tiles, a 16 x 16 x 16 grid of 512 lights per cell, jitter 1) are unpinned.
+ * POWER_CDF is this library's default and keeps the plain and reuse passes exactly as without this call. POWER_RIS presamples
+ * 1 MB of light tiles per render; REGIR_RIS also builds 16 MB of grid cells around the camera Position of the render (points
+ * outside the grid fall back to POWER_RIS). Each context owns its own presampling buffers.
+ * ------------------------------------------------------------------------------------------ */
+enum { PT_DI_LOCAL_LIGHT_POWER_CDF = 0,   /* this library's default: draw from the power prefix sum */
+       PT_DI_LOCAL_LIGHT_UNIFORM   = 1,   /* ReSTIRDI_LocalLightSamplingMode::Uniform */
+       PT_DI_LOCAL_LIGHT_POWER_RIS = 2,   /* ::Power_RIS (presampled light tiles) */
+       PT_DI_LOCAL_LIGHT_REGIR_RIS = 3 }; /* ::ReGIR_RIS (world-space grid, Power_RIS fallback) */
+typedef struct PtDILightSamplingSettings {
+    uint32_t Mode;                        /* PT_DI_LOCAL_LIGHT_* (reference default REGIR_RIS) */
+    float    ReGIRCellSize;               /* ReGIR.Cell.Size, [0.1, 10], default 1 */
+    uint32_t ReGIRBuildSamples;           /* ReGIR.BuildSamples, 1..32, default 8 */
+    uint32_t _pad;
+} PtDILightSamplingSettings;              /* 16 B */
+typedef struct PtDIPresampledLight {
+    uint32_t LightIndex;                  /* into the light list; 0xFFFFFFFF = empty */
+    float    InvSourcePdf;                /* tiles: total / Power; cells: the ReGIR build's contribution weight */
+} PtDIPresampledLight;                    /* 8 B */
+
+/* NULL: POWER_CDF. Out-of-range values are refused and leave the previous setting active; a changed value resets the history. */
+int  pt_di_set_light_sampling(PtContext* ctx, const PtDILightSamplingSettings* settings);
+/* which = 0: the Power_RIS tiles (tile-major, 128 x 1024), 1: the ReGIR cells (cell-major, x fastest, 4096 x 512) of the last
+ * pt_di_render; out_count = 0 when that render did not fill them; synchronises */
+int  pt_di_download_presampled(PtContext* ctx, uint32_t which, PtDIPresampledLight* host_dst, uint32_t capacity, uint32_t* out_count);
+
+/* ------------------------------------------------------------------------------------------
  * building blocks the reference's direct-lighting bridge calls on the same data
  * ------------------------------------------------------------------------------------------ */
 typedef struct PtRayDesc { float Origin[3]; float TMin; float Direction[3]; float TMax; } PtRayDesc;   /* HLSL RayDesc, 32 B */

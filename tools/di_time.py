@@ -1,20 +1,26 @@
 """Developer helper: time the direct-lighting pass (HIP events around N back-to-back pt_di_render calls) and one DI-on frame (G-buffer + DI +
 path tracer with IsDIEnabled) against the DI-off frame, per workload. Each workload runs in a child process of its own. --reuse also times
 the pass with temporal + spatial reservoir reuse at the reference's defaults (layouts.di_resampling_settings), history carried over.
-usage: tools/di_time.py [--workloads c2,c3,c5] [--samples 8] [--n 20] [--reuse]"""
+--light-sampling times each listed local-light sampling mode (cdf, uniform, power_ris, regir; one JSON line per mode). The workload
+emitter_field is scenes.emitter_field(256) (131 k emissive triangles) at 1920 x 1080, 1 spp, 1 bounce.
+usage: tools/di_time.py [--workloads c2,c3,c5,emitter_field] [--samples 8] [--n 20] [--reuse] [--light-sampling cdf,regir]"""
 import argparse, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def child(w, samples, n, reuse):
+def child(w, samples, n, reuse, modes):
     sys.path.insert(0, ROOT)
     import torch
     import __graft_entry__ as ge
     ge.load_package()
     import dxpbrt_amd.layouts as L, dxpbrt_amd.ptamd as P, dxpbrt_amd.scenes as S
     import bench
-    kind, W, H, spp, bounces, desc = bench.WORKLOADS[w]
-    scene, ext = bench.make_scene(kind, W / H, S)
+    if w == "emitter_field":
+        W, H, spp, bounces, ext = 1920, 1080, 1, 1, 0
+        scene = S.emitter_field(256, aspect=W / H)
+    else:
+        kind, W, H, spp, bounces, desc = bench.WORKLOADS[w]
+        scene, ext = bench.make_scene(kind, W / H, S)
     ctx = P.DeviceContext(0)
     ctx.set_frames_in_flight(1)
     g = P.Scene(ctx, scene)
@@ -33,17 +39,25 @@ def child(w, samples, n, reuse):
 
     r.render(gs)                                               # G-buffer + warm-up
     ctx.sync()
-    r.direct_lighting.SetConstants(L.di_settings(W, H, 0, samples, ext_flags=ext))
-    lights = r.direct_lighting.light_count()
-    for _ in range(3):
-        r.direct_lighting.Render(tlas)
-    ctx.sync()
-    di_ms = timed(lambda i: r.direct_lighting.Render(tlas), n)
     off_ms = timed(lambda i: r.render(gs), max(3, n // 4))
-    gs_on = gs.copy(); gs_on["IsDIEnabled"] = 1
-    r.render(gs_on, di_samples=samples); ctx.sync()
-    on_ms = timed(lambda i: r.render(gs_on, di_samples=samples), max(3, n // 4))
-    out = {"workload": w, "size": [W, H], "lights": lights, "samples": samples, "di_ms": di_ms, "frame_di_off_ms": off_ms, "frame_di_on_ms": on_ms}
+    for mode in modes:
+        ls = None if mode == "cdf" else L.di_light_sampling_settings(mode)
+        r.render(gs)
+        ctx.sync()
+        r.direct_lighting.SetConstants(L.di_settings(W, H, 0, samples, ext_flags=ext))
+        r.direct_lighting.SetLightSampling(ls)
+        lights = r.direct_lighting.light_count()
+        for _ in range(3):
+            r.direct_lighting.Render(tlas)
+        ctx.sync()
+        di_ms = timed(lambda i: r.direct_lighting.Render(tlas), n)
+        gs_on = gs.copy(); gs_on["IsDIEnabled"] = 1
+        r.render(gs_on, di_samples=samples, di_light_sampling=ls); ctx.sync()
+        on_ms = timed(lambda i: r.render(gs_on, di_samples=samples, di_light_sampling=ls), max(3, n // 4))
+        out = {"workload": w, "size": [W, H], "lights": lights, "samples": samples, "light_sampling": mode, "di_ms": di_ms,
+               "frame_di_off_ms": off_ms, "frame_di_on_ms": on_ms}
+        if mode != modes[-1]:
+            print(json.dumps(out), flush=True)
     if reuse:
         r.render(gs, di_samples=samples, di_reuse=L.di_resampling_settings()); ctx.sync()     # Previous* G-buffer, first history
         r.direct_lighting.Render(tlas); ctx.sync()
@@ -57,13 +71,15 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", default=None); ap.add_argument("--workloads", default="c2,c3,c5")
     ap.add_argument("--samples", type=int, default=8); ap.add_argument("--n", type=int, default=20); ap.add_argument("--reuse", action="store_true")
+    ap.add_argument("--light-sampling", default="cdf")
     a = ap.parse_args()
     if a.child:
-        child(a.child, a.samples, a.n, a.reuse); sys.exit(0)
+        child(a.child, a.samples, a.n, a.reuse, a.light_sampling.split(",")); sys.exit(0)
     for w in a.workloads.split(","):
-        p = subprocess.run([sys.executable, __file__, "--child", w, "--samples", str(a.samples), "--n", str(a.n)] + (["--reuse"] if a.reuse else []), stdout=subprocess.PIPE,
+        p = subprocess.run([sys.executable, __file__, "--child", w, "--samples", str(a.samples), "--n", str(a.n),
+                            "--light-sampling", a.light_sampling] + (["--reuse"] if a.reuse else []), stdout=subprocess.PIPE,
                            stderr=subprocess.PIPE, text=True, timeout=600)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]
-        print(line[0] if line else "%s FAILED (exit %d) %s" % (w, p.returncode, p.stderr[-400:]), flush=True)
+        print("\n".join(line) if line else "%s FAILED (exit %d) %s" % (w, p.returncode, p.stderr[-400:]), flush=True)
         if p.returncode < 0:                                    # a child killed by a signal: start nothing more on the GPU
             sys.exit(1)
