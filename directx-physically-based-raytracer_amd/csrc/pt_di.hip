@@ -5,16 +5,19 @@
 //   k_light_records                <- LightPreparation.hlsl main: TriangleLight::Initialize (Light.hlsli) on the world-space
 //                                     vertices, CalculatePower; run at every render (moving instances, refits)
 //   k_cdf_*                        <- the local-light pdf texture of the reference's Power_RIS mode, as a fixed-order prefix sum
-//   k_di                           <- DIInitialSampling (local lights only, streaming RIS) + DIFinalShading, no temporal /
+//   k_di_presample_tiles           <- LocalLightPresampling.hlsl: the Power_RIS light tiles (POWER_RIS, REGIR_RIS)
+//   k_di_regir_build               <- ReGIRPresampling.hlsl, Grid mode: the ReGIR cells (REGIR_RIS)
+//   k_di<Source>                   <- DIInitialSampling (local lights only, streaming RIS) + DIFinalShading, no temporal /
 //                                     spatial reuse (RTXDIAppBridge.hlsli RAB_GetGBufferSurface, RAB_Surface::Shade, GetFinalVisibility)
-//   k_di_initial_temporal          <- DIInitialSampling + DITemporalResampling (boiling filter), with reservoir reuse on
+//   k_di_initial_temporal<..., Source> <- DIInitialSampling + DITemporalResampling (boiling filter), with reservoir reuse on
 //   k_di_spatial_shade             <- DISpatialResampling + DIFinalShading
+// Source is where initial sampling draws its candidates from: DIPowerCDF (the prefix sum, the default) or DISampling (Uniform,
+// Power_RIS, ReGIR). Every kernel reads its surfaces with di_surface, draws with di_initial and shades with di_final.
 // DESIGN.md section 1 ("Direct lighting") is the arithmetic spec: seeding, draw order, triangle mapping.
 #include "pt_internal.hpp"
 
 #include <cmath>
 #include <cstring>
-#include <type_traits>
 
 #include "pt_shade.hpp"
 
@@ -179,9 +182,12 @@ __global__ __launch_bounds__(256) void k_cdf_add(float* __restrict__ cdf, uint32
 }
 
 // ---- the DI pass ----------------------------------------------------------------------------------------------------------
-struct DICamera { float position[3], jitter[2]; float projectionToView[16], viewToWorld[16]; };
+// G-buffer planes a surface is read from (the current frame's, or the Previous* textures)
+struct DIGBuffer { const void *depth, *normalRoughness, *geometricNormal, *baseColorMetalness, *ior, *transmission; };
+// what names a frame: its G-buffer and camera (the current one, or PreviousProjectionToView / PreviousViewToWorld / PreviousPosition)
+struct DIView { DIGBuffer g; float position[3], projectionToView[16], viewToWorld[16]; };
 struct DIArgs {
-    FrameView fv; DICamera cam; PtTextures tx;
+    FrameView fv; PtTextures tx; DIView view; float jitter[2];
     const float4* lights; const float* cdf; const float* total; uint32_t count;
     uint32_t frameIndex, samples, denoiser, lastPass, ext;
 };
@@ -212,27 +218,25 @@ PT_DEV void shade_sample(const BSDFSample& bs, const SurfaceVectors& svec, const
     spc = V3(spc.x * Le.x * inv, spc.y * Le.y * inv, spc.z * Le.z * inv);
 }
 
-// G-buffer planes a surface is read from (the current frame's, or the Previous* textures)
-struct DIGBuffer { const void *depth, *normalRoughness, *geometricNormal, *baseColorMetalness, *ior, *transmission; };
 struct DISurface { v3 P, V; SurfaceVectors svec; BSDFSample bs; float w[3]; float depth; };
 
-// RAB_GetGBufferSurface (RTXDIAppBridge.hlsli:293-345) at pixel (x, y); false: the empty surface. The camera is the current one or,
-// for the previous frame, PreviousProjectionToView / PreviousViewToWorld / PreviousPosition -- with the current Jitter (:332).
-PT_DEV bool di_surface(const DIGBuffer& g, size_t pi, uint32_t x, uint32_t y, const FrameView& fv, const float jitter[2], const float* projectionToView,
-                       const float* viewToWorld, const float* position, uint32_t ext, DISurface& s)
+// RAB_GetGBufferSurface (RTXDIAppBridge.hlsli:293-345) of a view at pixel (x, y); false: the empty surface. The jitter is the current
+// frame's whichever the view (:332).
+PT_DEV bool di_surface(const DIArgs& a, const DIView& view, size_t pi, uint32_t x, uint32_t y, DISurface& s)
 {
+    const DIGBuffer& g = view.g;
     const float depth = ((const float*)g.depth)[pi];
     if (!isfinite(depth)) return false;
     const short4 nr = ((const short4*)g.normalRoughness)[pi];
     const float roughness = snorm16_to_f32(nr.w);
     if (roughness < 0.05f) return false;                                 // MinRoughness
-    const float u = ((float)x + 0.5f + jitter[0]) / (float)fv.width, v = ((float)y + 0.5f + jitter[1]) / (float)fv.height;
+    const float u = ((float)x + 0.5f + a.jitter[0]) / (float)a.fv.width, v = ((float)y + 0.5f + a.jitter[1]) / (float)a.fv.height;
     float q[4];
-    xform4(projectionToView, V3(u * 2.0f + -1.0f, v * -2.0f + 1.0f, 0.5f), q);          // Camera::ReconstructWorldPosition
+    xform4(view.projectionToView, V3(u * 2.0f + -1.0f, v * -2.0f + 1.0f, 0.5f), q);     // Camera::ReconstructWorldPosition
     const v3 vp = V3(q[0] / q[2] * depth, q[1] / q[2] * depth, depth);
-    xform4(viewToWorld, vp, q);
+    xform4(view.viewToWorld, vp, q);
     s.P = V3(q[0], q[1], q[2]);
-    s.V = normalize(V3(position[0] - s.P.x, position[1] - s.P.y, position[2] - s.P.z));
+    s.V = normalize(V3(view.position[0] - s.P.x, view.position[1] - s.P.y, view.position[2] - s.P.z));
     const short2 ge = ((const short2*)g.geometricNormal)[pi];
     const v3 gn = oct_decode(snorm16_to_f32(ge.x), snorm16_to_f32(ge.y));
     const bool front = dot(gn, s.V) > 0.0f;
@@ -241,14 +245,14 @@ PT_DEV bool di_surface(const DIGBuffer& g, size_t pi, uint32_t x, uint32_t y, co
     const float metal = unorm8_to_f32(bcm.w);
     const float tr = metal < 1.0f ? unorm8_to_f32(((const uint8_t*)g.transmission)[pi]) : 0.0f;
     s.bs.Initialize(V3(unorm8_to_f32(bcm.x), unorm8_to_f32(bcm.y), unorm8_to_f32(bcm.z)), metal, roughness, f16_to_f32(((const uint16_t*)g.ior)[pi]), tr, front);
-    s.bs.ComputeLobeWeights(s.svec, s.V, ext, s.w);
+    s.bs.ComputeLobeWeights(s.svec, s.V, a.ext, s.w);
     s.depth = depth;
     return true;
 }
 
 // p-hat of light sample (li, U, V) at surface s (RAB_GetLightSampleTargetPdfForSurface): the luminance of the all-lobe Shade. The
-// sample's point is re-derived from the light record: Math::SampleTriangle with r1 = U, r2 = V.
-PT_DEV float di_target(const DIArgs& a, const DISurface& s, uint32_t li, float U, float V, v3& pos, v3& dif, v3& spc)
+// sample's point is re-derived from the light record: Math::SampleTriangle with r1 = U, r2 = V. power: the record's Power.
+PT_DEV float di_target(const DIArgs& a, const DISurface& s, uint32_t li, float U, float V, v3& pos, v3& dif, v3& spc, float& power)
 {
     const float4* L = a.lights + kLightRec16 * (size_t)li;
     const float4 l0 = L[0], l1 = L[1], l2 = L[2], l3 = L[3], l4 = L[4];
@@ -261,26 +265,8 @@ PT_DEV float di_target(const DIArgs& a, const DISurface& s, uint32_t li, float U
     const float cosL = fabsf(dot(dn, -V3(l3.x, l3.y, l3.z)));
     const float pdfSA = (1.0f / l0.w) * len * len / cosL;              // CalculateSolidAnglePDF
     shade_sample(s.bs, s.svec, s.w, a.ext, s.P, s.V, pos, V3(l4.x, l4.y, l4.z), pdfSA, dif, spc);
+    power = l1.w;
     return ml_luminance(dif + spc);
-}
-
-// initial sampling: LocalLightSamples power-proportional candidates, streaming RIS (RTXDI_StreamSample); the selected sample's
-// shaded terms stay in registers
-struct DIInitial { float wsum, p; v3 dif, spc, pos; float u, v; uint32_t li; };
-PT_DEV void di_initial(const DIArgs& a, const DISurface& s, uint32_t x, uint32_t y, float total, DIInitial& o)
-{
-    uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDISalt);
-    o.wsum = 0.0f; o.p = 0.0f; o.u = 0.0f; o.v = 0.0f; o.li = ~0u;
-    o.dif = V3(0, 0, 0); o.spc = V3(0, 0, 0); o.pos = V3(0, 0, 0);
-    for (uint32_t k = 0; k < a.samples; k++) {
-        const float r0 = rng_float(rng), r1 = rng_float(rng), r2 = rng_float(rng), r3 = rng_float(rng);
-        const uint32_t li = select_light(a.cdf, a.count, r0 * total, total);
-        v3 pos, dif, spc;
-        const float p = di_target(a, s, li, r1, r2, pos, dif, spc);
-        const float ris = p > 0.0f ? p / (a.lights[kLightRec16 * (size_t)li + 1].w / total) : 0.0f;   // target / source pdf (light selection; the point is uniform in uv)
-        o.wsum += ris;
-        if (r3 * o.wsum < ris) { o.p = p; o.dif = dif; o.spc = spc; o.pos = pos; o.u = r1; o.v = r2; o.li = li; }
-    }
 }
 
 // ---- local-light sampling (pt_di_set_light_sampling; DESIGN.md section 1, "Local-light sampling") ------------------------------------
@@ -292,8 +278,6 @@ constexpr float kDIJitterScale = 2.0f;                             // max(0, 2 *
 constexpr uint32_t kDITileEntries = kDITileCount * kDITileSize, kDICellEntries = kDIGrid * kDIGrid * kDIGrid * kDICellLights;
 constexpr uint32_t kDIPresampleSalt = 0x44490004u, kDIReGIRSalt = 0x44490005u, kDIReGIRCoherentSalt = 0x44490006u, kDIScreenTileSalt = 0x44490007u;
 static_assert(sizeof(PtDILightSamplingSettings) == 16 && sizeof(PtDIPresampledLight) == 8, "layout");
-
-struct DISampling { uint32_t mode; const uint2* tiles; const uint2* cells; float centre[3], cellSize; };
 
 // Power_RIS presampling (LocalLightPresampling.hlsl): one entry per thread, a power-proportional light from the prefix sum and its
 // inverse selection pdf. Seeded as ReGIRPresampling.hlsl splits its index: (g & 0xfff, g >> 12).
@@ -354,44 +338,75 @@ __global__ __launch_bounds__(256) void k_di_regir_build(const float4* __restrict
     cells[g] = pSel > 0.0f ? make_uint2(sel, __float_as_uint(wsum / (pSel * (float)buildSamples))) : make_uint2(~0u, 0u);
 }
 
-// initial sampling with the Uniform, Power_RIS or ReGIR candidates: di_initial with another source of (light, source pdf). Power_RIS: the
-// pixel's screen tile picks a light tile. ReGIR: three jitter draws from the pixel stream pick the cell; outside the grid, Power_RIS.
-PT_DEV void di_initial_ls(const DIArgs& a, const DISampling& ls, const DISurface& s, uint32_t x, uint32_t y, float total, DIInitial& o)
-{
-    uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDISalt);
-    o.wsum = 0.0f; o.p = 0.0f; o.u = 0.0f; o.v = 0.0f; o.li = ~0u;
-    o.dif = V3(0, 0, 0); o.spc = V3(0, 0, 0); o.pos = V3(0, 0, 0);
-    const uint2* src = nullptr;
-    uint32_t span = 0;
-    if (ls.mode != PT_DI_LOCAL_LIGHT_UNIFORM) {
-        uint32_t ts = ml_hash(rng_init(x / kDIScreenTile, y / kDIScreenTile, a.frameIndex) ^ kDIScreenTileSalt);
-        src = ls.tiles + min((uint32_t)(rng_float(ts) * (float)kDITileCount), kDITileCount - 1u) * kDITileSize;
-        span = kDITileSize;
-    }
-    if (ls.mode == PT_DI_LOCAL_LIGHT_REGIR_RIS) {
-        const float jx = (rng_float(rng) - 0.5f) * kDIJitterScale, jy = (rng_float(rng) - 0.5f) * kDIJitterScale, jz = (rng_float(rng) - 0.5f) * kDIJitterScale;
-        const float fx = floorf((s.P.x + jx * ls.cellSize - ls.centre[0]) / ls.cellSize), fy = floorf((s.P.y + jy * ls.cellSize - ls.centre[1]) / ls.cellSize),
-                    fz = floorf((s.P.z + jz * ls.cellSize - ls.centre[2]) / ls.cellSize);
-        const float lim = (float)(kDIGrid / 2u);
-        if (fx >= -lim && fx < lim && fy >= -lim && fy < lim && fz >= -lim && fz < lim) {
-            const uint32_t cell = (((uint32_t)((int)fz + (int)(kDIGrid / 2u)) * kDIGrid) + (uint32_t)((int)fy + (int)(kDIGrid / 2u))) * kDIGrid + (uint32_t)((int)fx + (int)(kDIGrid / 2u));
-            src = ls.cells + (size_t)cell * kDICellLights;
-            span = kDICellLights;
+// ---- initial sampling -------------------------------------------------------------------------------------------------------
+// Candidate sources. begin(): the pixel's presampled entries (it may draw from the pixel's stream). pick(): a candidate's first draw r0 ->
+// light li (false: an empty slot) and a value pv; pdf(pv, power, total): the light's source pdf, taken after the target, which reads the
+// light's record and hands back its power.
+struct DIEntries { const uint2* e; uint32_t n; };          // a Power_RIS tile or a ReGIR cell; none: no presampled entries
+
+// the power CDF (PT_DI_LOCAL_LIGHT_POWER_CDF): select_light on the prefix sum, source pdf power / total
+struct DIPowerCDF {
+    PT_DEV DIEntries begin(const DIArgs&, const DISurface&, uint32_t, uint32_t, uint32_t&) const { return DIEntries{ nullptr, 0u }; }
+    PT_DEV bool pick(const DIArgs& a, DIEntries, float r0, float total, uint32_t& li, float&) const { li = select_light(a.cdf, a.count, r0 * total, total); return true; }
+    PT_DEV float pdf(float, float power, float total) const { return power / total; }
+};
+
+// Uniform, Power_RIS or ReGIR (the mode is uniform over the grid). Power_RIS: the pixel's screen tile picks a light tile. ReGIR: three
+// jitter draws from the pixel stream pick the cell; outside the grid, Power_RIS. Uniform: 1 / count; an entry: 1 / its inverse pdf.
+struct DISampling {
+    uint32_t mode; const uint2* tiles; const uint2* cells; float centre[3], cellSize;
+    PT_DEV DIEntries begin(const DIArgs& a, const DISurface& s, uint32_t x, uint32_t y, uint32_t& rng) const
+    {
+        DIEntries src{ nullptr, 0u };
+        if (mode != PT_DI_LOCAL_LIGHT_UNIFORM) {
+            uint32_t ts = ml_hash(rng_init(x / kDIScreenTile, y / kDIScreenTile, a.frameIndex) ^ kDIScreenTileSalt);
+            src.e = tiles + min((uint32_t)(rng_float(ts) * (float)kDITileCount), kDITileCount - 1u) * kDITileSize;
+            src.n = kDITileSize;
         }
+        if (mode == PT_DI_LOCAL_LIGHT_REGIR_RIS) {
+            const float jx = (rng_float(rng) - 0.5f) * kDIJitterScale, jy = (rng_float(rng) - 0.5f) * kDIJitterScale, jz = (rng_float(rng) - 0.5f) * kDIJitterScale;
+            const float fx = floorf((s.P.x + jx * cellSize - centre[0]) / cellSize), fy = floorf((s.P.y + jy * cellSize - centre[1]) / cellSize),
+                        fz = floorf((s.P.z + jz * cellSize - centre[2]) / cellSize);
+            const float lim = (float)(kDIGrid / 2u);
+            if (fx >= -lim && fx < lim && fy >= -lim && fy < lim && fz >= -lim && fz < lim) {
+                const uint32_t cell = (((uint32_t)((int)fz + (int)(kDIGrid / 2u)) * kDIGrid) + (uint32_t)((int)fy + (int)(kDIGrid / 2u))) * kDIGrid + (uint32_t)((int)fx + (int)(kDIGrid / 2u));
+                src.e = cells + (size_t)cell * kDICellLights;
+                src.n = kDICellLights;
+            }
+        }
+        return src;
     }
-    for (uint32_t k = 0; k < a.samples; k++) {
-        const float r0 = rng_float(rng), r1 = rng_float(rng), r2 = rng_float(rng), r3 = rng_float(rng);
-        uint32_t li;
-        float pdf;                                                          // source pdf of the light
-        if (src) {
-            const uint2 e = src[min((uint32_t)(r0 * (float)span), span - 1u)];
+    PT_DEV bool pick(const DIArgs& a, DIEntries src, float r0, float, uint32_t& li, float& pdf) const
+    {
+        if (src.e) {
+            const uint2 e = src.e[min((uint32_t)(r0 * (float)src.n), src.n - 1u)];
             li = e.x; pdf = 1.0f / __uint_as_float(e.y);
         } else {
             li = min((uint32_t)(r0 * (float)a.count), a.count - 1u); pdf = 1.0f / (float)a.count;
         }
+        return li < a.count;
+    }
+    PT_DEV float pdf(float pv, float, float) const { return pv; }
+};
+
+// LocalLightSamples candidates from a source, streaming RIS (RTXDI_StreamSample); the selected sample's shaded terms stay in registers
+struct DIInitial { float wsum, p; v3 dif, spc, pos; float u, v; uint32_t li; };
+template <typename Source>
+PT_DEV void di_initial(const DIArgs& a, const Source& source, const DISurface& s, uint32_t x, uint32_t y, float total, DIInitial& o)
+{
+    uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDISalt);
+    o.wsum = 0.0f; o.p = 0.0f; o.u = 0.0f; o.v = 0.0f; o.li = ~0u;
+    o.dif = V3(0, 0, 0); o.spc = V3(0, 0, 0); o.pos = V3(0, 0, 0);
+    const DIEntries src = source.begin(a, s, x, y, rng);
+    for (uint32_t k = 0; k < a.samples; k++) {
+        const float r0 = rng_float(rng), r1 = rng_float(rng), r2 = rng_float(rng), r3 = rng_float(rng);
+        uint32_t li;
+        float pv;
+        const bool some = source.pick(a, src, r0, total, li, pv);
         v3 pos = V3(0, 0, 0), dif = V3(0, 0, 0), spc = V3(0, 0, 0);
-        const float p = li < a.count ? di_target(a, s, li, r1, r2, pos, dif, spc) : 0.0f;    // an empty slot: weight 0, still counted in M
-        const float ris = p > 0.0f ? p / pdf : 0.0f;
+        float power = 0.0f;
+        const float p = some ? di_target(a, s, li, r1, r2, pos, dif, spc, power) : 0.0f;    // an empty slot: weight 0, still counted in M
+        const float ris = p > 0.0f ? p / source.pdf(pv, power, total) : 0.0f;  // target / source pdf (light selection; the point is uniform in uv)
         o.wsum += ris;
         if (r3 * o.wsum < ris) { o.p = p; o.dif = dif; o.spc = spc; o.pos = pos; o.u = r1; o.v = r2; o.li = li; }
     }
@@ -432,122 +447,30 @@ PT_DEV void di_final(const DIArgs& a, BlobView bv, const AlphaContext& ac, Devic
     ((ushort4*)tx.Specular)[pi] = make_ushort4(f32_to_f16(spc.x), f32_to_f16(spc.y), f32_to_f16(spc.z), f32_to_f16(dist));
 }
 
-PT_DEV DIGBuffer current_gbuffer(const PtTextures& tx) { return DIGBuffer{ tx.LinearDepth, tx.NormalRoughness, tx.GeometricNormal, tx.BaseColorMetalness, tx.IOR, tx.Transmission }; }
-
-// One thread per local pixel; a wave covers an 8 x 8 square (as k_gbuffer), so the visibility rays of a wave stay together.
-__global__ __launch_bounds__(256) void k_di(DIArgs a, BlobView bv, AlphaContext ac, DeviceCounters* counters)
+// The pixel of a thread (x, local row): a wave covers an 8 x 8 square of the block's 16 x 16 (as k_gbuffer), so the rays of a wave stay together.
+PT_DEV void di_pixel(uint32_t& x, uint32_t& ly)
 {
     const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63u;
-    const uint32_t x = blockIdx.x * 16 + (wv & 1u) * 8u + (ln & 7u), ly = blockIdx.y * 16 + (wv >> 1) * 8u + (ln >> 3);
-    if (x >= a.fv.width || ly >= a.fv.localRows) return;                 // no barrier below
-    const uint32_t y = global_row(a.fv, ly);
-    const size_t pi = (size_t)ly * a.fv.width + x;
-    const PtTextures& tx = a.tx;
-
-    // RAB_GetGBufferSurface (RTXDIAppBridge.hlsli:293-345)
-    const float depth = ((const float*)tx.LinearDepth)[pi];
-    if (!isfinite(depth)) return;
-    const short4 nr = ((const short4*)tx.NormalRoughness)[pi];
-    const float roughness = snorm16_to_f32(nr.w);
-    if (roughness < 0.05f) return;                                       // MinRoughness
-    const float u = ((float)x + 0.5f + a.cam.jitter[0]) / (float)a.fv.width, v = ((float)y + 0.5f + a.cam.jitter[1]) / (float)a.fv.height;
-    float q[4];
-    xform4(a.cam.projectionToView, V3(u * 2.0f + -1.0f, v * -2.0f + 1.0f, 0.5f), q);      // Camera::ReconstructWorldPosition
-    const v3 vp = V3(q[0] / q[2] * depth, q[1] / q[2] * depth, depth);
-    xform4(a.cam.viewToWorld, vp, q);
-    const v3 P = V3(q[0], q[1], q[2]);
-    const v3 V = normalize(V3(a.cam.position[0] - P.x, a.cam.position[1] - P.y, a.cam.position[2] - P.z));
-    const short2 ge = ((const short2*)tx.GeometricNormal)[pi];
-    const v3 gn = oct_decode(snorm16_to_f32(ge.x), snorm16_to_f32(ge.y));
-    const bool front = dot(gn, V) > 0.0f;
-    const SurfaceVectors svec = surface_vectors(front, gn, V3(snorm16_to_f32(nr.x), snorm16_to_f32(nr.y), snorm16_to_f32(nr.z)));
-    const uchar4 bcm = ((const uchar4*)tx.BaseColorMetalness)[pi];
-    const float metal = unorm8_to_f32(bcm.w);
-    const float tr = metal < 1.0f ? unorm8_to_f32(((const uint8_t*)tx.Transmission)[pi]) : 0.0f;
-    BSDFSample bs;
-    bs.Initialize(V3(unorm8_to_f32(bcm.x), unorm8_to_f32(bcm.y), unorm8_to_f32(bcm.z)), metal, roughness, f16_to_f32(((const uint16_t*)tx.IOR)[pi]), tr, front);
-    float w[3]; bs.ComputeLobeWeights(svec, V, a.ext, w);
-
-    // initial sampling: LocalLightSamples power-proportional candidates, streaming RIS (RTXDI_StreamSample); the selected sample's
-    // shaded terms stay in registers
-    const float total = *a.total;
-    if (!(total > 0.0f) || !isfinite(total)) return;
-    uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDISalt);
-    float wsum = 0.0f, pSel = 0.0f;
-    v3 difSel = V3(0, 0, 0), spcSel = V3(0, 0, 0), posSel = V3(0, 0, 0);
-    for (uint32_t k = 0; k < a.samples; k++) {
-        const float r0 = rng_float(rng), r1 = rng_float(rng), r2 = rng_float(rng), r3 = rng_float(rng);
-        const uint32_t li = select_light(a.cdf, a.count, r0 * total, total);
-        const float4* L = a.lights + kLightRec16 * (size_t)li;
-        const float4 l0 = L[0], l1 = L[1], l2 = L[2], l3 = L[3], l4 = L[4];
-        const float s = sqrtf(r1);                                          // Math::SampleTriangle
-        const float b0 = s * (1.0f - r2), b1 = s * r2;
-        const v3 pos = V3(l0.x + l1.x * b0 + l2.x * b1, l0.y + l1.y * b0 + l2.y * b1, l0.z + l1.z * b0 + l2.z * b1);
-        const v3 d = pos - P;
-        const float len = sqrtf(dot(d, d));
-        const v3 dn = V3(d.x / len, d.y / len, d.z / len);
-        const float cosL = fabsf(dot(dn, -V3(l3.x, l3.y, l3.z)));
-        const float pdfSA = (1.0f / l0.w) * len * len / cosL;              // CalculateSolidAnglePDF
-        v3 dif, spc;
-        shade_sample(bs, svec, w, a.ext, P, V, pos, V3(l4.x, l4.y, l4.z), pdfSA, dif, spc);
-        const float p = ml_luminance(dif + spc);                            // RAB_GetLightSampleTargetPdfForSurface
-        const float ris = p > 0.0f ? p / (l1.w / total) : 0.0f;          // target / source pdf (light selection; the point is uniform in uv)
-        wsum += ris;
-        if (r3 * wsum < ris) { pSel = p; difSel = dif; spcSel = spc; posSel = pos; }
-    }
-    if (!(pSel > 0.0f)) return;
-    const float W = wsum / (float)a.samples / pSel;                        // (sum w / M) / target(y)
-
-    // final shading (DIFinalShading.hlsl): one coloured visibility ray, CreateVisibilityRay with offset 1e-3
-    const v3 d = posSel - P;
-    const float dist = sqrtf(dot(d, d));
-    const v3 dir = V3(d.x / dist, d.y / dist, d.z / dist);
-    __shared__ uint2 ldsStack[kLdsStackDepth * 256];
-    uint2 spill[kStackSize - kLdsStackDepth];
-    GroupStack<kLdsStackDepth> stack; stack.init((PT_LDS_AS void*)ldsStack, spill);
-    BlobReader<false> blob; blob.p = bv.base;
-    TraceStats st; st.nodes = 0; st.tris = 0; st.overflow = 0;
-    v3 vis;
-    trace_single<false, false, true>(blob, bv, ac, P, dir, 1e-3f, fmaxf(0.0f, dist - 2e-3f), stack, &st, &vis);
-    if (st.overflow) atomicAdd(&counters->stackOverflows, st.overflow);
-    if (vis.x == 0.0f && vis.y == 0.0f && vis.z == 0.0f) return;
-    const v3 dif = V3(difSel.x * vis.x * W, difSel.y * vis.y * W, difSel.z * vis.z * W);
-    const v3 spc = V3(spcSel.x * vis.x * W, spcSel.y * vis.y * W, spcSel.z * vis.z * W);
-    const v3 rad = dif + spc;
-    if ((rad.x == 0.0f && rad.y == 0.0f && rad.z == 0.0f) || !finite3(rad)) return;
-
-    // outputs, DIFinalShading.hlsl:78-103
-    if (a.lastPass && a.denoiser <= PT_DENOISER_DLSS_RAY_RECONSTRUCTION) {
-        ushort4* R = (ushort4*)tx.Radiance;
-        const ushort4 o = R[pi];
-        const v3 sum = V3(f16_to_f32(o.x) + rad.x, f16_to_f32(o.y) + rad.y, f16_to_f32(o.z) + rad.z);
-        R[pi] = make_ushort4(f32_to_f16(sum.x), f32_to_f16(sum.y), f32_to_f16(sum.z), o.w);
-        if (tx.RadianceF32) ((float4*)tx.RadianceF32)[pi] = make_float4(sum.x, sum.y, sum.z, 0.0f);
-        if (a.denoiser == PT_DENOISER_DLSS_RAY_RECONSTRUCTION && tx.SpecularHitDistance && (spc.x > 0.0f || spc.y > 0.0f || spc.z > 0.0f))
-            ((uint16_t*)tx.SpecularHitDistance)[pi] = f32_to_f16(dist);
-        return;
-    }
-    ((ushort4*)tx.Diffuse)[pi] = make_ushort4(f32_to_f16(dif.x), f32_to_f16(dif.y), f32_to_f16(dif.z), f32_to_f16(dist));
-    ((ushort4*)tx.Specular)[pi] = make_ushort4(f32_to_f16(spc.x), f32_to_f16(spc.y), f32_to_f16(spc.z), f32_to_f16(dist));
+    x = blockIdx.x * 16 + (wv & 1u) * 8u + (ln & 7u); ly = blockIdx.y * 16 + (wv >> 1) * 8u + (ln >> 3);
 }
 
-// k_di with the Uniform, Power_RIS or ReGIR candidates (the mode is uniform over the grid); the same pixel mapping, surface and final shading.
-__global__ __launch_bounds__(256) void k_di_ls(DIArgs a, DISampling ls, BlobView bv, AlphaContext ac, DeviceCounters* counters)
+// The plain pass, no reuse: initial sampling from a candidate source, then final shading. One thread per local pixel.
+template <typename Source>
+__global__ __launch_bounds__(256) void k_di(DIArgs a, Source source, BlobView bv, AlphaContext ac, DeviceCounters* counters)
 {
-    const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63u;
-    const uint32_t x = blockIdx.x * 16 + (wv & 1u) * 8u + (ln & 7u), ly = blockIdx.y * 16 + (wv >> 1) * 8u + (ln >> 3);
+    uint32_t x, ly; di_pixel(x, ly);
     if (x >= a.fv.width || ly >= a.fv.localRows) return;                 // no barrier below
     const uint32_t y = global_row(a.fv, ly);
     const size_t pi = (size_t)ly * a.fv.width + x;
     DISurface s;
-    if (!di_surface(current_gbuffer(a.tx), pi, x, y, a.fv, a.cam.jitter, a.cam.projectionToView, a.cam.viewToWorld, a.cam.position, a.ext, s)) return;
+    if (!di_surface(a, a.view, pi, x, y, s)) return;
     const float total = *a.total;
     if (!(total > 0.0f) || !isfinite(total)) return;
     DIInitial i0;
-    di_initial_ls(a, ls, s, x, y, total, i0);
+    di_initial(a, source, s, x, y, total, i0);
     if (!(i0.p > 0.0f)) return;
     __shared__ uint2 ldsStack[kLdsStackDepth * 256];
-    di_final(a, bv, ac, counters, ldsStack, pi, s.P, i0.pos, i0.dif, i0.spc, i0.wsum / (float)a.samples / i0.p);
+    di_final(a, bv, ac, counters, ldsStack, pi, s.P, i0.pos, i0.dif, i0.spc, i0.wsum / (float)a.samples / i0.p);   // W = (sum w / M) / target(y)
 }
 
 // ---- reservoir reuse (DITemporalResampling / DISpatialResampling; DESIGN.md section 1, "Reservoir reuse") --------------------------------
@@ -557,13 +480,12 @@ static_assert(sizeof(PtDIReservoir) == 32 && sizeof(PtDIResamplingSettings) == 6
 
 struct DIReuseArgs {
     DIArgs d;
-    DIGBuffer prev; float prevPosition[3]; float prevProjectionToView[16], prevViewToWorld[16];
+    DIView prev;                                    // the previous frame's G-buffer and camera (temporal reuse)
     const PtDIReservoir* in; PtDIReservoir* out;  // temporal: last frame's final reservoirs -> A; spatial: A -> B
     const char2* offsets;
     uint32_t haveHistory, maxHistory, boiling, spatialSamples, boostSamples;
     float boilingMul, tDepth, tNormal, radius, sDepth, sNormal;
 };
-struct DIReuseLSArgs : DIReuseArgs { DISampling ls; };   // k_di_initial_temporal with the candidates of di_initial_ls
 
 PT_DEV PtDIReservoir di_empty(uint32_t M)
 {
@@ -590,6 +512,15 @@ PT_DEV void di_reflect(int& x, int& y, int w, int h)
     if (x >= w) x = 2 * w - x - 1;
     if (y >= h) y = 2 * h - y - 1;
 }
+// spatial sample i's neighbour (qx, qy) of pixel (x, y): offset-table entry start + i scaled by the radius, reflected; false: outside the view
+PT_DEV bool di_neighbour(const DIReuseArgs& r, uint32_t x, uint32_t y, uint32_t start, uint32_t i, int& qx, int& qy)
+{
+    const int w = (int)r.d.fv.width, h = (int)r.d.fv.height;
+    const char2 e = r.offsets[(start + i) & (kDIOffsetCount - 1u)];
+    qx = (int)x + (int)((float)e.x / 127.0f * r.radius); qy = (int)y + (int)((float)e.y / 127.0f * r.radius);
+    di_reflect(qx, qy, w, h);
+    return qx >= 0 && qy >= 0 && qx < w && qy < h;
+}
 // the neighbour test: shading normals, relative depth (RTXDI_CompareRelativeDifference) and RAB_AreMaterialsSimilar
 PT_DEV bool di_similar(const DISurface& a, const DISurface& b, float depthA, float normalThreshold, float depthThreshold)
 {
@@ -602,30 +533,29 @@ PT_DEV float di_target_of(const DIArgs& a, const DISurface& s, uint32_t li, floa
 {
     if (li >= a.count) return 0.0f;
     v3 pos, dif, spc;
-    return di_target(a, s, li, U, V, pos, dif, spc);
+    float power;
+    return di_target(a, s, li, U, V, pos, dif, spc, power);
 }
 
-// Initial sampling fused with temporal reuse: the temporal step at a pixel reads only that pixel's fresh reservoir and last frame's data.
-// TEMPORAL = false writes the initial reservoirs (the spatial pass's input). The boiling filter is a 64-lane butterfly over the wave's
-// 8 x 8 tile, so every lane stays to the end. ARGS = DIReuseLSArgs: the candidates of di_initial_ls instead of di_initial.
-template <bool TEMPORAL, bool BASIC, typename ARGS = DIReuseArgs>
-__global__ __launch_bounds__(256) void k_di_initial_temporal(ARGS r)
+// Initial sampling from a candidate source fused with temporal reuse: the temporal step at a pixel reads only that pixel's fresh reservoir
+// and last frame's data. TEMPORAL = false writes the initial reservoirs (the spatial pass's input). The boiling filter is a 64-lane
+// butterfly over the wave's 8 x 8 tile, so every lane stays to the end.
+template <bool TEMPORAL, bool BASIC, typename Source>
+__global__ __launch_bounds__(256) void k_di_initial_temporal(DIReuseArgs r, Source source)
 {
     const DIArgs& a = r.d;
-    const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63u;
-    const uint32_t x = blockIdx.x * 16 + (wv & 1u) * 8u + (ln & 7u), y = blockIdx.y * 16 + (wv >> 1) * 8u + (ln >> 3);
+    uint32_t x, y; di_pixel(x, y);
     const bool inside = x < a.fv.width && y < a.fv.localRows;             // unsharded: local row = global row
     const size_t pi = (size_t)y * a.fv.width + x;
     PtDIReservoir res = di_empty(0u);
     DISurface s;
-    const bool valid = inside && di_surface(current_gbuffer(a.tx), pi, x, y, a.fv, a.cam.jitter, a.cam.projectionToView, a.cam.viewToWorld, a.cam.position, a.ext, s);
+    const bool valid = inside && di_surface(a, a.view, pi, x, y, s);
     if (valid) {
         res.M = a.samples;
         const float total = *a.total;
         if (total > 0.0f && isfinite(total)) {
             DIInitial i0;
-            if constexpr (std::is_same<ARGS, DIReuseLSArgs>::value) di_initial_ls(a, r.ls, s, x, y, total, i0);
-            else di_initial(a, s, x, y, total, i0);
+            di_initial(a, source, s, x, y, total, i0);
             if (i0.p > 0.0f) { res.LightIndex = i0.li; res.U = i0.u; res.V = i0.v; res.W = i0.wsum / (float)a.samples / i0.p; res.TargetPdf = i0.p; }
         }
         if (TEMPORAL) {
@@ -643,7 +573,7 @@ __global__ __launch_bounds__(256) void k_di_initial_temporal(ARGS r)
                     if (i) { const float rx = rng_float(rng), ry = rng_float(rng); qx += (int)((rx - 0.5f) * 6.0f); qy += (int)((ry - 0.5f) * 6.0f); }
                     di_reflect(qx, qy, w, h);
                     if (qx < 0 || qy < 0 || qx >= w || qy >= h) continue;
-                    if (!di_surface(r.prev, (size_t)qy * w + qx, qx, qy, a.fv, a.cam.jitter, r.prevProjectionToView, r.prevViewToWorld, r.prevPosition, a.ext, sp)) continue;
+                    if (!di_surface(a, r.prev, (size_t)qy * w + qx, qx, qy, sp)) continue;
                     if (!di_similar(s, sp, expected, r.tNormal, r.tDepth)) continue;
                     hx = qx; hy = qy;
                     break;
@@ -690,16 +620,14 @@ template <bool SPATIAL, bool BASIC>
 __global__ __launch_bounds__(256) void k_di_spatial_shade(DIReuseArgs r, BlobView bv, AlphaContext ac, DeviceCounters* counters)
 {
     const DIArgs& a = r.d;
-    const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63u;
-    const uint32_t x = blockIdx.x * 16 + (wv & 1u) * 8u + (ln & 7u), y = blockIdx.y * 16 + (wv >> 1) * 8u + (ln >> 3);
+    uint32_t x, y; di_pixel(x, y);
     if (x >= a.fv.width || y >= a.fv.localRows) return;                 // no barrier below
     const size_t pi = (size_t)y * a.fv.width + x;
-    const DIGBuffer g = current_gbuffer(a.tx);
     PtDIReservoir c = di_load(r.in, pi);
     DISurface s;
-    if (!di_surface(g, pi, x, y, a.fv, a.cam.jitter, a.cam.projectionToView, a.cam.viewToWorld, a.cam.position, a.ext, s)) { di_store(r.out, pi, c); return; }
+    if (!di_surface(a, a.view, pi, x, y, s)) { di_store(r.out, pi, c); return; }
     if (SPATIAL) {
-        const int w = (int)a.fv.width, h = (int)a.fv.height;
+        const int w = (int)a.fv.width;
         uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDISpatialSalt);
         const uint32_t start = (uint32_t)(rng_float(rng) * 8191.0f);
         const uint32_t n = c.M < r.maxHistory ? max(r.spatialSamples, r.boostSamples) : r.spatialSamples;
@@ -708,12 +636,10 @@ __global__ __launch_bounds__(256) void k_di_spatial_shade(DIReuseArgs r, BlobVie
         int sel = -1;
         PtDIReservoir o = c;
         for (uint32_t i = 0; i < n; i++) {
-            const char2 e = r.offsets[(start + i) & (kDIOffsetCount - 1u)];
-            int qx = (int)x + (int)((float)e.x / 127.0f * r.radius), qy = (int)y + (int)((float)e.y / 127.0f * r.radius);
-            di_reflect(qx, qy, w, h);
-            if (qx < 0 || qy < 0 || qx >= w || qy >= h) continue;
+            int qx, qy;
+            if (!di_neighbour(r, x, y, start, i, qx, qy)) continue;
             DISurface sn;
-            if (!di_surface(g, (size_t)qy * w + qx, qx, qy, a.fv, a.cam.jitter, a.cam.projectionToView, a.cam.viewToWorld, a.cam.position, a.ext, sn)) continue;
+            if (!di_surface(a, a.view, (size_t)qy * w + qx, qx, qy, sn)) continue;
             if (!di_similar(s, sn, s.depth, r.sNormal, r.sDepth)) continue;
             mask |= 1u << i;
             const PtDIReservoir rn = di_load(r.in, (size_t)qy * w + qx);
@@ -730,11 +656,10 @@ __global__ __launch_bounds__(256) void k_di_spatial_shade(DIReuseArgs r, BlobVie
                 float den = (float)c.M * p, pSrc = p;
                 for (uint32_t i = 0; i < n; i++) {
                     if (!(mask & (1u << i))) continue;
-                    const char2 e = r.offsets[(start + i) & (kDIOffsetCount - 1u)];
-                    int qx = (int)x + (int)((float)e.x / 127.0f * r.radius), qy = (int)y + (int)((float)e.y / 127.0f * r.radius);
-                    di_reflect(qx, qy, w, h);
+                    int qx, qy;
+                    di_neighbour(r, x, y, start, i, qx, qy);                 // inside: the first loop took it
                     DISurface sn;
-                    di_surface(g, (size_t)qy * w + qx, qx, qy, a.fv, a.cam.jitter, a.cam.projectionToView, a.cam.viewToWorld, a.cam.position, a.ext, sn);
+                    di_surface(a, a.view, (size_t)qy * w + qx, qx, qy, sn);
                     const float pn = di_target_of(a, sn, o.LightIndex, o.U, o.V);
                     den += (float)r.in[(size_t)qy * w + qx].M * pn;
                     if ((int)i == sel) pSrc = pn;
@@ -752,7 +677,8 @@ __global__ __launch_bounds__(256) void k_di_spatial_shade(DIReuseArgs r, BlobVie
     di_store(r.out, pi, c);
     if (c.LightIndex >= a.count || !(c.W > 0.0f)) return;
     v3 pos, dif, spc;
-    di_target(a, s, c.LightIndex, c.U, c.V, pos, dif, spc);
+    float power;
+    di_target(a, s, c.LightIndex, c.U, c.V, pos, dif, spc, power);
     __shared__ uint2 ldsStack[kLdsStackDepth * 256];
     di_final(a, bv, ac, counters, ldsStack, pi, s.P, pos, dif, spc, c.W);
 }
@@ -819,25 +745,10 @@ static int di_fail_hip(Context& c, hipError_t e, const char* what)
 #define DI_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return di_fail_hip(c, e_, #expr); } while (0)
 #define DI_ARG(cond, msg) do { if (!(cond)) return di_fail(c, PT_ERROR_INVALID_ARGUMENT, msg); } while (0)
 
-namespace pt { int di_views(Context& c, uint32_t width, uint32_t height, SceneView& sv, FrameView& fv, bool needFrameInputs); }   // pt_api.hip make_views
-
-extern "C" {
-
-int pt_di_set_constants(PtContext* ctx, const PtDISettings* s)
+// ---- pt_di_render_with_history, in stages ----------------------------------------------------------------------------------
+// the arguments, checked in this order
+static int di_check_args(Context& c, const PtTextures* tx, const PtDIPreviousTextures* prev)
 {
-    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
-    Context& c = ctx->c;
-    DI_ARG(s, "settings is NULL");
-    DI_ARG(s->LocalLightSamples >= 1 && s->LocalLightSamples <= 32, "LocalLightSamples must be 1..32");
-    DI_ARG(s->Denoiser <= PT_DENOISER_NRD_RELAX, "unknown Denoiser value");
-    c.diSettings = *s; c.haveDISettings = true;
-    return PT_OK;
-}
-
-int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPreviousTextures* prev)
-{
-    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
-    Context& c = ctx->c;
     DI_ARG(tx, "textures is NULL");
     if (!c.haveDISettings) return di_fail(c, PT_ERROR_NOT_READY, "call pt_di_set_constants first");
     const PtDISettings& s = c.diSettings;
@@ -846,27 +757,16 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
     const bool toRadiance = s.IsLastRenderPass && s.Denoiser <= PT_DENOISER_DLSS_RAY_RECONSTRUCTION;
     DI_ARG(toRadiance ? tx->Radiance != nullptr : (tx->Diffuse && tx->Specular),
            toRadiance ? "IsLastRenderPass with Denoiser None / DLSS-RR adds to Textures.Radiance: not bound" : "the DI pass writes Textures.Diffuse / Textures.Specular: not bound");
-    const PtDIResamplingSettings& rs = c.diReuse;
-    const bool reuse = c.diReuseOn, temporal = reuse && rs.TemporalResampling, spatial = reuse && rs.SpatialSamples > 0;
-    if (temporal)
+    if (c.diReuseOn && c.diReuse.TemporalResampling)
         DI_ARG(prev && prev->PreviousGeometricNormal && prev->PreviousLinearDepth && prev->PreviousBaseColorMetalness && prev->PreviousNormalRoughness &&
                prev->PreviousIOR && prev->PreviousTransmission && tx->MotionVector,
                "temporal resampling reads Textures.MotionVector and the six Previous* textures: not bound");
-    DI_HIP(hipSetDevice(c.device));
-    SceneView sv; FrameView fv; memset(&sv, 0, sizeof sv); memset(&fv, 0, sizeof fv);
-    int st = di_views(c, s.RenderSize[0], s.RenderSize[1], sv, fv, true);
-    if (st != PT_OK) return st;
-    DI_ARG(!reuse || fv.rankCount == 1, "reservoir reuse needs an unsharded context (RankCount 1)");
-    const size_t npix = (size_t)fv.width * fv.localRows;
-    if (tx->Diffuse) DI_HIP(hipMemsetAsync(tx->Diffuse, 0, npix * 8u, c.stream));                // App.cpp:1238-1239
-    if (tx->Specular) DI_HIP(hipMemsetAsync(tx->Specular, 0, npix * 8u, c.stream));
-    DI_HIP(ensure_light_list(c, sv));
-    const uint32_t n = c.lightCount;
-    c.lightRecordCount = n;
-    c.diTileCount = 0; c.diCellCount = 0;
-    if (!reuse || n == 0 || npix == 0) { c.diHistoryValid = false; c.diResCount = 0; }
-    if (n == 0 || npix == 0) return PT_OK;
-    const uint32_t nb = (n + kScanBlock - 1u) / kScanBlock;
+    return PT_OK;
+}
+
+// the n light records and the prefix sum of their powers (nb scan blocks); the total lands in lightBlockSums[nb]
+static int di_light_records(Context& c, const SceneView& sv, uint32_t n, uint32_t nb)
+{
     if (n > c.lightRecords.capacity()) {
         DI_HIP(hipStreamSynchronize(c.stream));
         c.lightRecords.reset(); c.lightCdf.reset(); c.lightBlockSums.reset();
@@ -879,48 +779,62 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
     k_cdf_local<<<nb, 256, 0, c.stream>>>(power, n, c.lightCdf.data(), c.lightBlockSums.data());
     k_cdf_blocks<<<1, 1, 0, c.stream>>>(c.lightBlockSums.data(), nb);
     k_cdf_add<<<(n + 255u) / 256u, 256, 0, c.stream>>>(c.lightCdf.data(), n, c.lightBlockSums.data(), nb);
-    // local-light sampling: Power_RIS tiles (POWER_RIS, REGIR_RIS), then the ReGIR cells around this render's camera (REGIR_RIS)
-    const PtDILightSamplingSettings& lss = c.diSampling;
-    DISampling ls; memset(&ls, 0, sizeof ls);
-    ls.mode = lss.Mode;
-    if (lss.Mode == PT_DI_LOCAL_LIGHT_POWER_RIS || lss.Mode == PT_DI_LOCAL_LIGHT_REGIR_RIS) {
-        const bool regir = lss.Mode == PT_DI_LOCAL_LIGHT_REGIR_RIS;
-        if (c.diTiles.capacity() < kDITileEntries || (regir && c.diCells.capacity() < kDICellEntries)) {
-            DI_HIP(hipStreamSynchronize(c.stream));
-            DI_HIP(c.diTiles.reserve(kDITileEntries));
-            if (regir) DI_HIP(c.diCells.reserve(kDICellEntries));    // 16 MB, only in ReGIR mode
-        }
-        k_di_presample_tiles<<<kDITileEntries / 256u, 256, 0, c.stream>>>((const float4*)c.lightRecords.data(), c.lightCdf.data(), c.lightBlockSums.data() + nb, n,
-                                                                         s.FrameIndex, (uint2*)c.diTiles.data());
-        DI_HIP(hipGetLastError());
-        c.diTileCount = kDITileEntries;
-        ls.tiles = (const uint2*)c.diTiles.data();
-        if (regir) {
-            memcpy(ls.centre, c.camera.Position, sizeof ls.centre);
-            ls.cellSize = lss.ReGIRCellSize;
-            k_di_regir_build<<<kDICellEntries / 256u, 256, 0, c.stream>>>((const float4*)c.lightRecords.data(), n, ls.tiles, ls.centre[0], ls.centre[1], ls.centre[2],
-                                                                          ls.cellSize, lss.ReGIRBuildSamples, s.FrameIndex, (uint2*)c.diCells.data());
-            DI_HIP(hipGetLastError());
-            c.diCellCount = kDICellEntries;
-            ls.cells = (const uint2*)c.diCells.data();
-        }
-    }
-    DIArgs a; memset(&a, 0, sizeof a);
-    a.fv = fv; a.tx = *tx;
-    memcpy(a.cam.position, c.camera.Position, sizeof a.cam.position); memcpy(a.cam.jitter, c.camera.Jitter, sizeof a.cam.jitter);
-    memcpy(a.cam.projectionToView, c.camera.ProjectionToView, sizeof a.cam.projectionToView); memcpy(a.cam.viewToWorld, c.camera.ViewToWorld, sizeof a.cam.viewToWorld);
-    a.lights = (const float4*)c.lightRecords.data(); a.cdf = c.lightCdf.data(); a.total = c.lightBlockSums.data() + nb; a.count = n;
-    a.frameIndex = s.FrameIndex; a.samples = s.LocalLightSamples; a.denoiser = s.Denoiser; a.lastPass = s.IsLastRenderPass; a.ext = s.ExtFlags;
-    AlphaContext ac; ac.objects = sv.objects; ac.heap = sv.heap; ac.srgbLut = sv.srgbLut; ac.instances = sv.accel.instances; ac.shadeTex = sv.shadeTex;
-    const dim3 grid((fv.width + 15u) / 16u, (fv.localRows + 15u) / 16u);
-    if (!reuse) {
-        if (lss.Mode == PT_DI_LOCAL_LIGHT_POWER_CDF) k_di<<<grid, 256, 0, c.stream>>>(a, c.scene.blob, ac, c.counters.data());
-        else k_di_ls<<<grid, 256, 0, c.stream>>>(a, ls, c.scene.blob, ac, c.counters.data());
-        DI_HIP(hipGetLastError());
-        return PT_OK;
-    }
+    return PT_OK;
+}
 
-    // reservoir reuse: k_di_initial_temporal (last frame's B -> A), k_di_spatial_shade (A -> B); B is next frame's history
+// local-light sampling: Power_RIS tiles (POWER_RIS, REGIR_RIS), then the ReGIR cells around this render's camera (REGIR_RIS); ls is
+// the candidate source of every mode but POWER_CDF
+static int di_presample(Context& c, uint32_t n, uint32_t nb, DISampling& ls)
+{
+    const PtDILightSamplingSettings& lss = c.diSampling;
+    memset(&ls, 0, sizeof ls);
+    ls.mode = lss.Mode;
+    if (lss.Mode != PT_DI_LOCAL_LIGHT_POWER_RIS && lss.Mode != PT_DI_LOCAL_LIGHT_REGIR_RIS) return PT_OK;
+    const bool regir = lss.Mode == PT_DI_LOCAL_LIGHT_REGIR_RIS;
+    if (c.diTiles.capacity() < kDITileEntries || (regir && c.diCells.capacity() < kDICellEntries)) {
+        DI_HIP(hipStreamSynchronize(c.stream));
+        DI_HIP(c.diTiles.reserve(kDITileEntries));
+        if (regir) DI_HIP(c.diCells.reserve(kDICellEntries));    // 16 MB, only in ReGIR mode
+    }
+    k_di_presample_tiles<<<kDITileEntries / 256u, 256, 0, c.stream>>>((const float4*)c.lightRecords.data(), c.lightCdf.data(), c.lightBlockSums.data() + nb, n,
+                                                                     c.diSettings.FrameIndex, (uint2*)c.diTiles.data());
+    DI_HIP(hipGetLastError());
+    c.diTileCount = kDITileEntries;
+    ls.tiles = (const uint2*)c.diTiles.data();
+    if (regir) {
+        memcpy(ls.centre, c.camera.Position, sizeof ls.centre);
+        ls.cellSize = lss.ReGIRCellSize;
+        k_di_regir_build<<<kDICellEntries / 256u, 256, 0, c.stream>>>((const float4*)c.lightRecords.data(), n, ls.tiles, ls.centre[0], ls.centre[1], ls.centre[2],
+                                                                      ls.cellSize, lss.ReGIRBuildSamples, c.diSettings.FrameIndex, (uint2*)c.diCells.data());
+        DI_HIP(hipGetLastError());
+        c.diCellCount = kDICellEntries;
+        ls.cells = (const uint2*)c.diCells.data();
+    }
+    return PT_OK;
+}
+
+static DIView di_view(const DIGBuffer& g, const float* projectionToView, const float* viewToWorld, const float* position)
+{
+    DIView v; v.g = g;
+    memcpy(v.projectionToView, projectionToView, sizeof v.projectionToView); memcpy(v.viewToWorld, viewToWorld, sizeof v.viewToWorld);
+    memcpy(v.position, position, sizeof v.position);
+    return v;
+}
+
+// calls f with the candidate source of the light-sampling mode: the kernels that draw candidates are instantiated for each source
+template <typename F> static void di_with_source(const DISampling& ls, F&& f)
+{
+    if (ls.mode == PT_DI_LOCAL_LIGHT_POWER_CDF) f(DIPowerCDF{});
+    else f(ls);
+}
+
+// reservoir reuse: k_di_initial_temporal (last frame's B -> A), k_di_spatial_shade (A -> B); B is next frame's history
+static int di_launch_reuse(Context& c, const DIArgs& a, const DISampling& ls, const PtDIPreviousTextures* prev, dim3 grid, const AlphaContext& ac)
+{
+    const PtDIResamplingSettings& rs = c.diReuse;
+    const bool temporal = rs.TemporalResampling, spatial = rs.SpatialSamples > 0;
+    const FrameView& fv = a.fv;
+    const size_t npix = (size_t)fv.width * fv.localRows;
     if (npix > c.diResB.capacity() || !c.diOffsets) {
         DI_HIP(hipStreamSynchronize(c.stream));
         if (npix > c.diResB.capacity()) {
@@ -940,13 +854,10 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
     if (c.diHistorySize[0] != fv.width || c.diHistorySize[1] != fv.height || c.diHistoryLightKey != c.lightListKey) c.diHistoryValid = false;
     DIReuseArgs r; memset(&r, 0, sizeof r);
     r.d = a;
-    if (temporal) {
-        r.prev = DIGBuffer{ prev->PreviousLinearDepth, prev->PreviousNormalRoughness, prev->PreviousGeometricNormal, prev->PreviousBaseColorMetalness,
-                            prev->PreviousIOR, prev->PreviousTransmission };
-        memcpy(r.prevPosition, c.camera.PreviousPosition, sizeof r.prevPosition);
-        memcpy(r.prevProjectionToView, c.camera.PreviousProjectionToView, sizeof r.prevProjectionToView);
-        memcpy(r.prevViewToWorld, c.camera.PreviousViewToWorld, sizeof r.prevViewToWorld);
-    }
+    if (temporal)
+        r.prev = di_view(DIGBuffer{ prev->PreviousLinearDepth, prev->PreviousNormalRoughness, prev->PreviousGeometricNormal, prev->PreviousBaseColorMetalness,
+                                    prev->PreviousIOR, prev->PreviousTransmission },
+                         c.camera.PreviousProjectionToView, c.camera.PreviousViewToWorld, c.camera.PreviousPosition);
     r.offsets = (const char2*)c.diOffsets.data();
     r.haveHistory = c.diHistoryValid ? 1u : 0u;
     r.maxHistory = rs.MaxHistoryLength; r.boiling = rs.BoilingFilter; r.spatialSamples = rs.SpatialSamples; r.boostSamples = rs.DisocclusionBoostSamples;
@@ -955,16 +866,12 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
     r.radius = rs.SpatialSamplingRadius; r.sDepth = rs.SpatialDepthThreshold; r.sNormal = rs.SpatialNormalThreshold;
     r.in = c.diResB.data(); r.out = c.diResA.data();
     const bool tb = rs.TemporalBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC, sb = rs.SpatialBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC;
-    if (lss.Mode != PT_DI_LOCAL_LIGHT_POWER_CDF) {
-        DIReuseLSArgs rl; memset(&rl, 0, sizeof rl);
-        static_cast<DIReuseArgs&>(rl) = r; rl.ls = ls;
-        if (!temporal) k_di_initial_temporal<false, false, DIReuseLSArgs><<<grid, 256, 0, c.stream>>>(rl);
-        else if (tb) k_di_initial_temporal<true, true, DIReuseLSArgs><<<grid, 256, 0, c.stream>>>(rl);
-        else k_di_initial_temporal<true, false, DIReuseLSArgs><<<grid, 256, 0, c.stream>>>(rl);
-    }
-    else if (!temporal) k_di_initial_temporal<false, false><<<grid, 256, 0, c.stream>>>(r);
-    else if (tb) k_di_initial_temporal<true, true><<<grid, 256, 0, c.stream>>>(r);
-    else k_di_initial_temporal<true, false><<<grid, 256, 0, c.stream>>>(r);
+    di_with_source(ls, [&](auto source) {
+        using S = decltype(source);
+        if (!temporal) k_di_initial_temporal<false, false, S><<<grid, 256, 0, c.stream>>>(r, source);
+        else if (tb) k_di_initial_temporal<true, true, S><<<grid, 256, 0, c.stream>>>(r, source);
+        else k_di_initial_temporal<true, false, S><<<grid, 256, 0, c.stream>>>(r, source);
+    });
     DI_HIP(hipGetLastError());
     r.in = c.diResA.data(); r.out = c.diResB.data();
     if (!spatial) k_di_spatial_shade<false, false><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data());
@@ -973,6 +880,61 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
     DI_HIP(hipGetLastError());
     c.diHistoryValid = true; c.diHistorySize[0] = fv.width; c.diHistorySize[1] = fv.height; c.diHistoryLightKey = c.lightListKey;
     c.diResCount = (uint32_t)npix;
+    return PT_OK;
+}
+
+namespace pt { int di_views(Context& c, uint32_t width, uint32_t height, SceneView& sv, FrameView& fv, bool needFrameInputs); }   // pt_api.hip make_views
+
+extern "C" {
+
+int pt_di_set_constants(PtContext* ctx, const PtDISettings* s)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    DI_ARG(s, "settings is NULL");
+    DI_ARG(s->LocalLightSamples >= 1 && s->LocalLightSamples <= 32, "LocalLightSamples must be 1..32");
+    DI_ARG(s->Denoiser <= PT_DENOISER_NRD_RELAX, "unknown Denoiser value");
+    c.diSettings = *s; c.haveDISettings = true;
+    return PT_OK;
+}
+
+int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPreviousTextures* prev)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    int st = di_check_args(c, tx, prev);
+    if (st != PT_OK) return st;
+    const PtDISettings& s = c.diSettings;
+    const bool reuse = c.diReuseOn;
+    DI_HIP(hipSetDevice(c.device));
+    SceneView sv; FrameView fv; memset(&sv, 0, sizeof sv); memset(&fv, 0, sizeof fv);
+    if ((st = di_views(c, s.RenderSize[0], s.RenderSize[1], sv, fv, true)) != PT_OK) return st;
+    DI_ARG(!reuse || fv.rankCount == 1, "reservoir reuse needs an unsharded context (RankCount 1)");
+    const size_t npix = (size_t)fv.width * fv.localRows;
+    if (tx->Diffuse) DI_HIP(hipMemsetAsync(tx->Diffuse, 0, npix * 8u, c.stream));                // App.cpp:1238-1239
+    if (tx->Specular) DI_HIP(hipMemsetAsync(tx->Specular, 0, npix * 8u, c.stream));
+    DI_HIP(ensure_light_list(c, sv));
+    const uint32_t n = c.lightCount;
+    c.lightRecordCount = n;
+    c.diTileCount = 0; c.diCellCount = 0;
+    if (!reuse || n == 0 || npix == 0) { c.diHistoryValid = false; c.diResCount = 0; }
+    if (n == 0 || npix == 0) return PT_OK;
+    const uint32_t nb = (n + kScanBlock - 1u) / kScanBlock;
+    if ((st = di_light_records(c, sv, n, nb)) != PT_OK) return st;
+    DISampling ls;
+    if ((st = di_presample(c, n, nb, ls)) != PT_OK) return st;
+    DIArgs a; memset(&a, 0, sizeof a);
+    a.fv = fv; a.tx = *tx;
+    a.view = di_view(DIGBuffer{ tx->LinearDepth, tx->NormalRoughness, tx->GeometricNormal, tx->BaseColorMetalness, tx->IOR, tx->Transmission },
+                     c.camera.ProjectionToView, c.camera.ViewToWorld, c.camera.Position);
+    memcpy(a.jitter, c.camera.Jitter, sizeof a.jitter);
+    a.lights = (const float4*)c.lightRecords.data(); a.cdf = c.lightCdf.data(); a.total = c.lightBlockSums.data() + nb; a.count = n;
+    a.frameIndex = s.FrameIndex; a.samples = s.LocalLightSamples; a.denoiser = s.Denoiser; a.lastPass = s.IsLastRenderPass; a.ext = s.ExtFlags;
+    AlphaContext ac; ac.objects = sv.objects; ac.heap = sv.heap; ac.srgbLut = sv.srgbLut; ac.instances = sv.accel.instances; ac.shadeTex = sv.shadeTex;
+    const dim3 grid((fv.width + 15u) / 16u, (fv.localRows + 15u) / 16u);
+    if (reuse) return di_launch_reuse(c, a, ls, prev, grid, ac);
+    di_with_source(ls, [&](auto source) { k_di<decltype(source)><<<grid, 256, 0, c.stream>>>(a, source, c.scene.blob, ac, c.counters.data()); });   // the plain pass
+    DI_HIP(hipGetLastError());
     return PT_OK;
 }
 
