@@ -208,6 +208,12 @@ struct Context {
     PtDILightSamplingSettings diSampling{};
     DeviceBuffer<PtDIPresampledLight> diTiles, diCells;
     uint32_t diTileCount = 0, diCellCount = 0;        // entries the last render filled (0: not filled)
+
+    // post-processing (pt_post.hip): one slot per bloom stage, each the size of the level it writes (the bytes of the reference's two pyramids)
+    PtPostProcessSettings post{}; bool havePost = false;
+    DeviceBuffer<ushort4> postLevels;
+    uint32_t postDims[9][2] = {};                     // what each stage wrote in the last render with bloom on; 0 x 0: not written
+    size_t postOffset[9] = {};                        // texel offset of each stage's slot in postLevels
 };
 
 std::string& create_error();             // pt_api.hip: the message pt_last_error(NULL) returns (errors of the context-free entry points)

@@ -4,6 +4,9 @@
 //
 //   pt_demo [--width W] [--height H] [--spp S] [--bounces B] [--frames N] [--out file.bin] [--ranks R] [--di] [--di-samples N] [--restir]
 //           [--light-sampling cdf|uniform|power_ris|regir]
+//           [--post] [--no-bloom] [--bloom-strength S] [--tone-map saturate|reinhard|aces] [--exposure E]
+//           [--hdr [--paper-white N] [--color-rotation hdtv_to_uhdtv|dci_p3_d65_to_uhdtv|hdtv_to_dci_p3_d65]]
+//           [--png file.png] [--out-display file.bin]
 //
 // --di: the direct-lighting pass between the G-buffer and the path tracer (App.cpp:1234-1308), LocalLightSamples = --di-samples (default 8);
 // the path tracer then runs with IsDIEnabled (with Bounces 0 the DI pass is the last render pass and adds to Radiance).
@@ -11,6 +14,11 @@
 // frame after the first (App.cpp:629-634). Unsharded only.
 // --light-sampling (with --di): how the DI pass draws its candidates (ReSTIRDI.InitialSampling.LocalLight.Mode; default cdf, the power
 // prefix sum); ReGIR at MyAppData's cell size 1 and 8 build samples.
+//
+// --post: the post-processing chain after every frame (App::PostProcessGraphics, App.cpp:1506-1571: Bloom + Merge, ToneMap, CopyTexture)
+// at MyAppData's defaults (bloom 0.05, ACES filmic, exposure 0, SDR) unless the flags above change them; --png writes the last frame's
+// Display8 as an RGB PNG (SDR only), --out-display its BackBuffer (R10G10B10A2_UNORM words). Both imply --post. With --ranks the chain
+// runs on rank 0, on the gathered frame.
 //
 // --ranks R: one process per GPU. The parent (which never touches a GPU) starts R children `--rank r --world R --id-file F`; rank 0
 // makes the RCCL unique id and leaves it in F, the others pick it up; every rank renders its 16-row bands (BandSharding) and rank 0
@@ -39,6 +47,7 @@
 #include <vector>
 
 #include "ptamd.hpp"
+#include "pt_png.hpp"
 #include "pt_ingest.hpp"
 
 using namespace ptamd;
@@ -343,10 +352,15 @@ int main(int argc, char** argv)
     uint32_t W = 1920, H = 1080, spp = 4, bounces = 8, frames = 10, ranks = 0, rank = 0, world = 1;
     uint32_t diSamples = 8; bool di = false, restir = false;
     std::string out, idFile, scenePath, dumpPath, lightSampling = "cdf";
+    bool post = false, bloom = true, hdr = false; float bloomStrength = 0.05f, exposure = 0.0f, paperWhite = 200.0f;
+    std::string toneMap = "aces", colorRotation = "hdtv_to_uhdtv", pngPath, displayPath;
     for (int i = 1; i < argc; i++) {
         std::string k = argv[i];
         if (k == "--di") { di = true; continue; }                  // the flags without a value
         if (k == "--restir") { restir = true; continue; }
+        if (k == "--post") { post = true; continue; }
+        if (k == "--no-bloom") { bloom = false; continue; }
+        if (k == "--hdr") { hdr = true; continue; }
         if (i + 1 >= argc) break;
         const char* v = argv[++i];
         if (k == "--width") W = atoi(v); else if (k == "--height") H = atoi(v);
@@ -357,7 +371,12 @@ int main(int argc, char** argv)
         else if (k == "--di-samples") diSamples = atoi(v);
         else if (k == "--light-sampling") lightSampling = v;
         else if (k == "--scene") scenePath = v; else if (k == "--dump-scene") dumpPath = v;
+        else if (k == "--bloom-strength") bloomStrength = (float)atof(v); else if (k == "--tone-map") toneMap = v;
+        else if (k == "--exposure") exposure = (float)atof(v); else if (k == "--paper-white") paperWhite = (float)atof(v);
+        else if (k == "--color-rotation") colorRotation = v; else if (k == "--png") pngPath = v;
+        else if (k == "--out-display") displayPath = v;
     }
+    post = post || !pngPath.empty() || !displayPath.empty();
     const bool sharded = !idFile.empty();
     if (!dumpPath.empty()) {                                        // no GPU call on this path
         try { return dump_scene(scenePath.empty() ? cornell_scene() : ingested_scene(scenePath), dumpPath); }
@@ -462,6 +481,31 @@ int main(int argc, char** argv)
         tx.RadianceF32 = radianceF32 = (float*)alloc(px_ * 16);
         if (di) { tx.Diffuse = alloc(px_ * 8); tx.Specular = alloc(px_ * 8); }   // Raytracing::Textures Diffuse / Specular (App.cpp:475-482)
         void* fullRadiance = sharded && rank == 0 ? alloc(fullPx * 8) : nullptr;      // the assembled frame (R16G16B16A16_FLOAT), root only
+        // ---- App::PostProcessGraphics (Denoiser::None): on the whole frame, rank 0 of a sharded run after the gather
+        PostProcessing postProcessing(commandList);
+        const bool runPost = post && rank == 0;
+        if (post) {
+            if (hdr && !pngPath.empty()) throw std::invalid_argument("--png writes an SDR image: drop --hdr");
+            PostProcessing::Settings ps; ps.RenderSize[0] = W; ps.RenderSize[1] = H;
+            ps.Bloom.IsEnabled = bloom; ps.Bloom.Strength = bloomStrength; ps.IsHDREnabled = hdr;
+            using Op = PostProcessing::ToneMapOperator; using Rot = PostProcessing::ColorRotation;
+            if (toneMap == "saturate") ps.ToneMapping.NonHDR.Operator = Op::Saturate;
+            else if (toneMap == "reinhard") ps.ToneMapping.NonHDR.Operator = Op::Reinhard;
+            else if (toneMap == "aces") ps.ToneMapping.NonHDR.Operator = Op::ACESFilmic;
+            else throw std::invalid_argument("--tone-map: saturate, reinhard or aces");
+            ps.ToneMapping.NonHDR.Exposure = exposure; ps.ToneMapping.HDR.PaperWhiteNits = paperWhite;
+            if (colorRotation == "hdtv_to_uhdtv") ps.ToneMapping.HDR.ColorPrimaryRotation = Rot::HDTVtoUHDTV;
+            else if (colorRotation == "dci_p3_d65_to_uhdtv") ps.ToneMapping.HDR.ColorPrimaryRotation = Rot::DCI_P3_D65toUHDTV;
+            else if (colorRotation == "hdtv_to_dci_p3_d65") ps.ToneMapping.HDR.ColorPrimaryRotation = Rot::HDTVtoDCI_P3_D65;
+            else throw std::invalid_argument("--color-rotation: hdtv_to_uhdtv, dci_p3_d65_to_uhdtv or hdtv_to_dci_p3_d65");
+            postProcessing.SetConstants(ps);
+            if (runPost) {
+                postProcessing.Textures.Radiance = sharded ? fullRadiance : tx.Radiance;
+                postProcessing.Textures.Color = alloc(fullPx * 8);
+                postProcessing.Textures.BackBuffer = alloc(fullPx * 4);
+                postProcessing.Textures.Display8 = alloc(fullPx * 4);
+            }
+        }
         float* fullRadianceF32 = sharded && rank == 0 && !out.empty() ? (float*)alloc(fullPx * 16) : nullptr;
 
         // ---- App::RenderScene
@@ -517,6 +561,7 @@ int main(int argc, char** argv)
             raytracing.SetConstants(gs);
             raytracing.Render(commandList, tlas);
             if (sharded) sharding.GatherBands(commandList, tx.Radiance, fullRadiance, W, H, 8);
+            if (runPost) postProcessing.Render(commandList);
         };
         renderFrame(12345);                                         // warm-up
         commandList.End();
@@ -552,6 +597,18 @@ int main(int argc, char** argv)
             FILE* fp = fopen(out.c_str(), "wb");
             if (!fp) { fprintf(stderr, "cannot open %s\n", out.c_str()); return 3; }
             fwrite(host.data(), 16, fullPx, fp); fclose(fp);
+        }
+        if (runPost && !displayPath.empty()) {                      // the presented back buffer of the last frame
+            std::vector<uint32_t> words(fullPx);
+            HIP_OK(hipMemcpy(words.data(), postProcessing.Textures.BackBuffer, fullPx * 4, hipMemcpyDeviceToHost));
+            FILE* fp = fopen(displayPath.c_str(), "wb");
+            if (!fp || fwrite(words.data(), 4, fullPx, fp) != fullPx) { fprintf(stderr, "cannot write %s\n", displayPath.c_str()); if (fp) fclose(fp); return 3; }
+            fclose(fp);
+        }
+        if (runPost && !pngPath.empty()) {
+            std::vector<uint8_t> rgba(fullPx * 4);
+            HIP_OK(hipMemcpy(rgba.data(), postProcessing.Textures.Display8, fullPx * 4, hipMemcpyDeviceToHost));
+            if (!ptpng::write_rgb(pngPath, rgba.data(), W, H)) { fprintf(stderr, "cannot write %s\n", pngPath.c_str()); return 3; }
         }
     } catch (const std::exception& e) {
         fprintf(stderr, "pt_demo: %s\n", e.what());

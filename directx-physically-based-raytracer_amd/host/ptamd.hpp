@@ -6,6 +6,7 @@
 //     struct Raytracing          Source/Raytracing.ixx:29-250      (DEFAULT permutation; SHARC overload absent)
 //     BuildTopLevelAccelerationStructure / CreateGeometryDesc       Source/RaytracingHelpers.ixx:28-105
 //     struct SkeletalMeshSkinning Source/SkeletalMeshSkinning.ixx:20-66
+//     struct PostProcessing      App::PostProcessGraphics with Denoiser::None (Source/App.cpp:1506-1571): Bloom, Merge, ToneMap, CopyTexture
 // Error behaviour: a failing status becomes the exception type the reference throws at the same place
 // (std::invalid_argument for argument checks, std::system_error otherwise: Source/ErrorHelpers.ixx:16-32).
 // Header-only, plain C++20 (std::span), no HIP headers needed by the including translation unit.
@@ -363,6 +364,47 @@ struct Raytracing {
 private:
     PtContext* m_context;
     PtGraphicsSettings m_graphicsSettings{};
+};
+
+// App::PostProcessGraphics with Denoiser::None (Source/App.cpp:1506-1571): Bloom + Merge (ProcessBloom :1769-1775), DirectXTK's
+// ToneMapPostProcess (ToneMap :1777-1803) and the copy into the R10G10B10A2_UNORM back buffer (CopyTexture :1805-1812), enqueued after
+// Raytracing::Render. The settings carry the names of MyAppData::Settings::Graphics::PostProcessing (Source/MyAppData.h:305-333). Runs on
+// the full frame: a sharded host calls it on rank 0 after the gather.
+struct PostProcessing {
+    enum class ToneMapOperator : uint32_t { Saturate = PT_TONE_MAP_SATURATE, Reinhard = PT_TONE_MAP_REINHARD, ACESFilmic = PT_TONE_MAP_ACES_FILMIC };
+    enum class ColorRotation : uint32_t {
+        HDTVtoUHDTV = PT_COLOR_ROTATION_HDTV_TO_UHDTV, DCI_P3_D65toUHDTV = PT_COLOR_ROTATION_DCI_P3_D65_TO_UHDTV,
+        HDTVtoDCI_P3_D65 = PT_COLOR_ROTATION_HDTV_TO_DCI_P3_D65
+    };
+    struct Settings {
+        uint32_t RenderSize[2]{};
+        struct { bool IsEnabled = true; float Strength = 0.05f; } Bloom;                               // [0, 1]
+        struct {
+            struct { float PaperWhiteNits = 200; ColorRotation ColorPrimaryRotation = ColorRotation::HDTVtoUHDTV; } HDR;   // [50, 10000]
+            struct { ToneMapOperator Operator = ToneMapOperator::ACESFilmic; float Exposure = 0; } NonHDR;                   // [-10, 10]
+        } ToneMapping;
+        bool IsHDREnabled = false;                                     // the reference asks the display; this library has none
+    };
+
+    PtPostTextures Textures{};                              // Radiance in; Color, BackBuffer, Display8 out (NULL: not written)
+
+    explicit PostProcessing(CommandList& commandList) : m_context(commandList.Context) {}
+
+    void SetConstants(const Settings& settings)
+    {
+        PtPostProcessSettings s{};
+        s.RenderSize[0] = settings.RenderSize[0]; s.RenderSize[1] = settings.RenderSize[1];
+        s.IsBloomEnabled = settings.Bloom.IsEnabled; s.BloomStrength = settings.Bloom.Strength;
+        s.IsHDREnabled = settings.IsHDREnabled;
+        s.ToneMappingOperator = (uint32_t)settings.ToneMapping.NonHDR.Operator; s.Exposure = settings.ToneMapping.NonHDR.Exposure;
+        s.PaperWhiteNits = settings.ToneMapping.HDR.PaperWhiteNits; s.ColorPrimaryRotation = (uint32_t)settings.ToneMapping.HDR.ColorPrimaryRotation;
+        ThrowIfFailed(m_context, pt_post_set_constants(m_context, &s));
+    }
+
+    void Render(CommandList& commandList) { ThrowIfFailed(commandList.Context, pt_post_render(commandList.Context, &Textures)); }
+
+private:
+    PtContext* m_context;
 };
 
 } // namespace ptamd

@@ -159,6 +159,68 @@ def di_resampling_settings(temporal=True, spatial_samples=1, temporal_bias=DI_BI
     return s
 
 
+POST_PROCESS_SETTINGS = np.dtype({  # PtPostProcessSettings: PostProcessing.{Bloom, ToneMapping} (Source/MyAppData.h:305-333)
+    "names": ["RenderSize", "IsBloomEnabled", "BloomStrength", "IsHDREnabled", "ToneMappingOperator", "Exposure", "PaperWhiteNits",
+              "ColorPrimaryRotation"],
+    "formats": [("<u4", 2), "<u4", "<f4", "<u4", "<u4", "<f4", "<f4", "<u4"],
+    "offsets": [0, 8, 12, 16, 20, 24, 28, 32], "itemsize": 48})
+
+TONE_MAP_SATURATE, TONE_MAP_REINHARD, TONE_MAP_ACES_FILMIC = 1, 2, 3          # ToneMapPostProcess::Operator
+TONE_MAP_OPERATORS = {"saturate": TONE_MAP_SATURATE, "reinhard": TONE_MAP_REINHARD, "aces_filmic": TONE_MAP_ACES_FILMIC}
+COLOR_ROTATION_HDTV_TO_UHDTV, COLOR_ROTATION_DCI_P3_D65_TO_UHDTV, COLOR_ROTATION_HDTV_TO_DCI_P3_D65 = 0, 1, 2   # ::ColorPrimaryRotation
+COLOR_ROTATIONS = {"hdtv_to_uhdtv": COLOR_ROTATION_HDTV_TO_UHDTV, "dci_p3_d65_to_uhdtv": COLOR_ROTATION_DCI_P3_D65_TO_UHDTV,
+                   "hdtv_to_dci_p3_d65": COLOR_ROTATION_HDTV_TO_DCI_P3_D65}
+POST_MAX_SIZE = 16384
+POST_STAGES = 9
+# outputs of pt_post_render (PtPostTextures): name -> (numpy dtype, channels)
+POST_FORMATS = {"Color": ("<u2", 4), "BackBuffer": ("<u4", 1), "Display8": ("u1", 4)}
+
+
+def check_post_processing_settings(s):
+    """The range checks of pt_post_set_constants, on the float32 values the library receives: ValueError where it answers
+    PT_ERROR_INVALID_ARGUMENT."""
+    s = np.asarray(s).reshape(())
+    w, h = (int(v) for v in s["RenderSize"])
+    f = {k: float(np.float32(s[k])) for k in ("BloomStrength", "Exposure", "PaperWhiteNits")}
+    if not (1 <= w <= POST_MAX_SIZE and 1 <= h <= POST_MAX_SIZE):
+        raise ValueError(f"RenderSize must be 1..{POST_MAX_SIZE} on both axes")
+    if int(s["IsBloomEnabled"]) > 1 or int(s["IsHDREnabled"]) > 1:
+        raise ValueError("IsBloomEnabled / IsHDREnabled must be 0 or 1")
+    if not 0.0 <= f["BloomStrength"] <= 1.0:
+        raise ValueError("BloomStrength must be in [0, 1]")
+    if int(s["ToneMappingOperator"]) not in TONE_MAP_OPERATORS.values():
+        raise ValueError("unknown ToneMappingOperator")
+    if not -10.0 <= f["Exposure"] <= 10.0:
+        raise ValueError("Exposure must be in [-10, 10]")
+    if not 50.0 <= f["PaperWhiteNits"] <= 10000.0:
+        raise ValueError("PaperWhiteNits must be in [50, 10000]")
+    if int(s["ColorPrimaryRotation"]) not in COLOR_ROTATIONS.values():
+        raise ValueError("unknown ColorPrimaryRotation")
+    return s
+
+
+def post_bloom_size_ok(width, height):
+    """pt_post_render's bloom-on size rule: five mips of the (W/2, H/2) pyramid need max(W/2, H/2) >= 16, and W, H >= 2."""
+    return width >= 2 and height >= 2 and max(width, height) >= 32
+
+
+def post_processing_settings(width, height, bloom=True, strength=0.05, operator="aces_filmic", exposure=0.0, hdr=False,
+                             paper_white_nits=200.0, rotation="hdtv_to_uhdtv"):
+    """PtPostProcessSettings with the reference's defaults (Source/MyAppData.h:305-333): bloom on at strength 0.05, ACES filmic at
+    exposure 0, paper white 200 nits, Rec.709 -> Rec.2020. HDR is off by default here (the library has no display to ask).
+    operator / rotation: a name of TONE_MAP_OPERATORS / COLOR_ROTATIONS or the enum value. Refuses what pt_post_set_constants refuses."""
+    s = np.zeros((), POST_PROCESS_SETTINGS)
+    s["RenderSize"] = (width, height)
+    s["IsBloomEnabled"] = 1 if bloom else 0
+    s["BloomStrength"] = strength
+    s["IsHDREnabled"] = 1 if hdr else 0
+    s["ToneMappingOperator"] = TONE_MAP_OPERATORS[operator] if isinstance(operator, str) else operator
+    s["Exposure"] = exposure
+    s["PaperWhiteNits"] = paper_white_nits
+    s["ColorPrimaryRotation"] = COLOR_ROTATIONS[rotation] if isinstance(rotation, str) else rotation
+    return check_post_processing_settings(s)
+
+
 GBUFFER_CONSTANTS = np.dtype({
     "names": ["RenderSize", "Flags"], "formats": [("<u4", 2), "<u4"], "offsets": [0, 8], "itemsize": 12})
 

@@ -28,6 +28,7 @@ EXPORTS = [
     "pt_di_set_constants", "pt_di_render", "pt_di_light_count", "pt_di_download_lights",
     "pt_di_set_resampling", "pt_di_render_with_history", "pt_di_reset_history", "pt_di_download_reservoirs",
     "pt_di_set_light_sampling", "pt_di_download_presampled",
+    "pt_post_set_constants", "pt_post_render", "pt_post_download_bloom",
     "pt_set_debug_flags", "pt_debug_read_mismatch", "pt_debug_download_blob", "pt_debug_trace_ray", "pt_enable_kernel_timing", "pt_get_kernel_timing", "pt_get_round_timing",
 ]
 
@@ -60,6 +61,10 @@ class Textures(C.Structure):
 
 class PreviousTextures(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in L.DI_PREVIOUS_TEXTURES]
+
+
+class PostTextures(C.Structure):
+    _fields_ = [("Radiance", C.c_void_p), ("Color", C.c_void_p), ("BackBuffer", C.c_void_p), ("Display8", C.c_void_p)]
 
 
 class Sharding(C.Structure):
@@ -171,6 +176,9 @@ def load_library():
         lib.pt_di_download_reservoirs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.pt_di_set_light_sampling.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_di_download_presampled.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.pt_post_set_constants.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_post_render.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_post_download_bloom.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.pt_set_debug_flags.argtypes = [C.c_void_p, C.c_uint32]
         lib.pt_debug_read_mismatch.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_debug_download_blob.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -497,6 +505,15 @@ def alloc_textures(width, local_rows_, device, with_f32=False, with_denoiser_out
     return out
 
 
+def alloc_post_textures(width, height, device):
+    """The outputs of the post-processing chain as linear CUDA tensors: Color (R16G16B16A16_FLOAT), BackBuffer (R10G10B10A2_UNORM,
+    one 32-bit word per pixel), Display8 (R8G8B8A8_UNORM)."""
+    torch = _torch()
+    tmap = {"<u2": torch.int16, "<u4": torch.int32, "u1": torch.uint8}
+    return {name: torch.zeros((height, width, ch) if ch > 1 else (height, width), dtype=tmap[dt], device=device)
+            for name, (dt, ch) in L.POST_FORMATS.items()}
+
+
 def _ptr(t):
     return t.data_ptr() if t is not None else None
 
@@ -518,6 +535,8 @@ def textures_to_numpy(tex):
             a = a.view(np.dtype(L.GBUFFER_FORMATS[base][0]))
         elif name in L.DENOISER_FORMATS:
             a = a.view(np.dtype(L.DENOISER_FORMATS[name][0]))
+        elif name in L.POST_FORMATS:
+            a = a.view(np.dtype(L.POST_FORMATS[name][0]))
         out[name] = a
     return out
 
@@ -648,6 +667,37 @@ class DirectLighting:
         return out
 
 
+class PostProcessing:
+    """App::PostProcessGraphics with Denoiser::None (Source/App.cpp:1506-1571): Bloom + Merge, ToneMap, CopyTexture. SetConstants takes
+    PtPostProcessSettings (layouts.post_processing_settings); Render reads Textures["Radiance"] and writes whichever of Color / BackBuffer /
+    Display8 are bound. Runs on the full frame: a sharded host calls it on the gathered frame. No scene is needed."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.Textures = {}
+        self._settings = None
+
+    def SetConstants(self, settings):
+        self._settings = np.array(settings).reshape(())
+        self.ctx.check(self.ctx.lib.pt_post_set_constants(self.ctx.handle, C.c_void_p(self._settings.ctypes.data)))
+
+    def Render(self, textures=None):
+        tex = self.Textures if textures is None else textures
+        t = PostTextures(*[_ptr(tex.get(n)) for n in ("Radiance", "Color", "BackBuffer", "Display8")])
+        self.ctx.check(self.ctx.lib.pt_post_render(self.ctx.handle, C.addressof(t)))
+
+    def download_bloom(self, stage):
+        """The image bloom stage `stage` (0..8, DESIGN.md section 1) wrote in the last Render with bloom on: uint16 fp16 bits (h, w, 4);
+        empty (0, 0, 4) when there was none. Synchronises."""
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        self.ctx.check(self.ctx.lib.pt_post_download_bloom(self.ctx.handle, stage, None, 0, C.byref(w), C.byref(h)))
+        out = np.zeros((h.value, w.value, 4), np.uint16)
+        if out.size:
+            self.ctx.check(self.ctx.lib.pt_post_download_bloom(self.ctx.handle, stage, C.c_void_p(out.ctypes.data), w.value * h.value,
+                                                               C.byref(w), C.byref(h)))
+        return out
+
+
 class Renderer:
     """App::RenderScene for this path (Source/App.cpp:1157-1329): G-buffer pass, then the path tracer."""
 
@@ -663,6 +713,7 @@ class Renderer:
         self.gbuffer = GBufferGeneration(ctx)
         self.raytracing = Raytracing(ctx)
         self.direct_lighting = DirectLighting(ctx)
+        self.post = PostProcessing(ctx)
         d = scene_gpu.desc
         for op in (self.gbuffer, self.raytracing, self.direct_lighting):
             op.GPUBuffers["Camera"] = d.camera
@@ -672,14 +723,22 @@ class Renderer:
         self.constants["RenderSize"] = (width, height)
         self.constants["Flags"] = L.GBufferFlags.DefaultNoDenoiser        # App.cpp:1224 with Denoiser::None
 
-    def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None):
+    def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None, post=None):
         """di_samples > 0: run the DI pass with that many candidates per pixel; set settings["IsDIEnabled"] to have the path tracer
         consume it (the textures need Diffuse / Specular: with_denoiser_outputs=True). di_reuse: PtDIResamplingSettings
         (layouts.di_resampling_settings) for reservoir reuse; temporal reuse needs di_history=True. With di_history the current and
         Previous* G-buffer textures are swapped before each frame after the first, so that after render() the current ones hold this
         frame's G-buffer and the Previous* ones the last frame's. di_light_sampling: PtDILightSamplingSettings
-        (layouts.di_light_sampling_settings), or None: the power CDF."""
+        (layouts.di_light_sampling_settings), or None: the power CDF. post: PtPostProcessSettings (layouts.post_processing_settings) to run
+        the post-processing chain on the frame's Radiance; it writes textures["Color"], ["BackBuffer"] and ["Display8"]. Unsharded
+        contexts only: a sharded host gathers Radiance and runs PostProcessing on the full frame."""
         tlas = self.scene.GetTopLevelAccelerationStructure()
+        if post is not None:
+            p = np.array(post).reshape(())
+            if getattr(self.ctx, "sharding", (0, 1, 16))[1] > 1:
+                raise PtInvalidArgument("post-processing needs the whole frame: run PostProcessing on the gathered Radiance of a sharded render")
+            if tuple(int(v) for v in p["RenderSize"]) != (self.width, self.height):
+                raise PtInvalidArgument("post-processing RenderSize differs from the renderer's size")
         if self.di_history and self._rendered:
             for n in L.DI_PREVIOUS_TEXTURES:
                 c = n[len("Previous"):]
@@ -697,4 +756,9 @@ class Renderer:
         if int(np.array(settings).reshape(())["Bounces"]) > 0:            # App.cpp:1277
             self.raytracing.SetConstants(settings)
             self.raytracing.Render(tlas)
+        if post is not None:                                              # App.cpp:1506-1571, after Raytracing::Render
+            if "Color" not in self.textures:
+                self.textures.update(alloc_post_textures(self.width, self.height, self.scene.device))
+            self.post.SetConstants(post)
+            self.post.Render(self.textures)
         self._rendered = True

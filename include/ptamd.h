@@ -499,6 +499,40 @@ typedef struct PtBsdfSampleQuery {
 typedef struct PtBsdfSampleResult { float L[3], PDF, F[3], Weights[3]; uint32_t Lobe, Ok; } PtBsdfSampleResult;   /* 48 B */
 int  pt_bsdf_sample(PtContext* ctx, const PtBsdfSampleQuery* device_queries, uint32_t count, PtBsdfSampleResult* device_results);
 
+/* ------------------------------------------------------------------------------------------
+ * the post-processing chain after the frame (App::PostProcessGraphics with Denoiser::None, Source/App.cpp:1506-1571):
+ * Bloom (Source/Bloom.ixx, Shaders/Bloom.hlsl) + Merge (Shaders/Merge.hlsl), DirectXTK's ToneMapPostProcess (App.cpp:1777-1803)
+ * and CopyTexture into the R10G10B10A2_UNORM back buffer (App.cpp:1805-1812). DESIGN.md section 1, "Post-processing", is the
+ * arithmetic spec; DirectXTK's formulas and Color::ToSrgb are the build's own, unpinned.
+ * ------------------------------------------------------------------------------------------ */
+enum { PT_TONE_MAP_SATURATE = 1, PT_TONE_MAP_REINHARD = 2, PT_TONE_MAP_ACES_FILMIC = 3 };        /* ToneMapPostProcess::Operator */
+enum { PT_COLOR_ROTATION_HDTV_TO_UHDTV = 0, PT_COLOR_ROTATION_DCI_P3_D65_TO_UHDTV = 1,
+       PT_COLOR_ROTATION_HDTV_TO_DCI_P3_D65 = 2 };                                                 /* ::ColorPrimaryRotation */
+typedef struct PtPostProcessSettings {      /* MyAppData::Settings::Graphics::PostProcessing::{Bloom, ToneMapping} */
+    uint32_t RenderSize[2];                 /* 1..16384 each */
+    uint32_t IsBloomEnabled;  float BloomStrength;          /* default 1, 0.05; [0, 1] */
+    uint32_t IsHDREnabled;                                  /* 0: operator + sRGB estimate (library default); 1: HDR10 */
+    uint32_t ToneMappingOperator;  float Exposure;          /* default ACES_FILMIC, 0; [-10, 10] */
+    float    PaperWhiteNits;  uint32_t ColorPrimaryRotation;/* default 200 [50, 10000], HDTV_TO_UHDTV */
+    uint32_t _pad[3];
+} PtPostProcessSettings;                    /* 48 B */
+typedef struct PtPostTextures {             /* full-frame, row-major, RenderSize pixels; NULL = not written */
+    const void* Radiance;                   /* R16G16B16A16_FLOAT in (required) */
+    void* Color;                            /* R16G16B16A16_FLOAT: the tone-mapped texture ToneMap writes */
+    void* BackBuffer;                       /* R10G10B10A2_UNORM: what CopyTexture presents */
+    void* Display8;                         /* build-side extra: R8G8B8A8_UNORM of Color, for image files */
+} PtPostTextures;
+/* Out-of-range values and unknown enums are refused (PT_ERROR_INVALID_ARGUMENT) and leave the previous settings active. */
+int pt_post_set_constants(PtContext* ctx, const PtPostProcessSettings* settings);
+/* Enqueued on the context's stream. Needs no acceleration structure and ignores the sharding (bloom is not local: a sharded host
+ * runs it on the gathered frame). Refuses a NULL Radiance, no output bound, and with bloom on a RenderSize below W, H >= 2 and
+ * max(W, H) >= 32 (five mips of the half-size pyramid). The pyramid is context-owned and grow-only; a failed allocation returns
+ * PT_ERROR_OUT_OF_MEMORY and keeps the previous one. */
+int pt_post_render(PtContext* ctx, const PtPostTextures* textures);
+/* the image stage s (0..8 of the table) wrote in the last pt_post_render with bloom on; *w = *h = 0 if none; synchronises */
+int pt_post_download_bloom(PtContext* ctx, uint32_t stage, uint16_t* host_rgba16f, uint64_t capacity_texels,
+                           uint32_t* out_width, uint32_t* out_height);
+
 /* Measurement (no reference counterpart). Counters cover the work enqueued since the last reset;
  * reading them synchronises the stream. */
 typedef struct PtCounters {
