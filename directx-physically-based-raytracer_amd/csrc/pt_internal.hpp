@@ -9,6 +9,7 @@
 #include "../../include/ptamd.h"
 #include "pt_memory.hpp"
 #include "pt_trace2.hpp"
+#include "pt_sharc.hpp"
 
 namespace pt {
 
@@ -214,6 +215,18 @@ struct Context {
     DeviceBuffer<ushort4> postLevels;
     uint32_t postDims[9][2] = {};                     // what each stage wrote in the last render with bloom on; 0 x 0: not written
     size_t postOffset[9] = {};                        // texel offset of each stage's slot in postLevels
+
+    // SHARC radiance cache (pt_sharc.hip): per context, also for a context that views another's scene. sharcVoxels[sharcParity] is VoxelData (this
+    // frame's deposits, then the resolved cache), the other one PreviousVoxelData; they swap after the query.
+    PtSHARCSettings sharcSettings{}; bool haveSharcSettings = false;
+    uint32_t sharcCapacity = 0, sharcParity = 0;      // capacity 0: not configured
+    DeviceBuffer<unsigned long long> sharcKeys;       // HashEntries
+    DeviceBuffer<uint4> sharcVoxels[2];
+    DeviceBuffer<SharcView> sharcView;                // what the query kernels read, rewritten per render in stream order
+    DeviceBuffer<float> sharcRough[2];                // previousRoughness of the two path queues' entries (allocated by the first SHARC render)
+    bool sharcQuery = false;                          // set around launch_raytrace by pt_raytrace_render_sharc: the SHARC instantiations
+    DeviceBuffer<PtSHARCPathScatter> sharcLogScatter;
+    DeviceBuffer<PtSHARCPathVertex> sharcLog; uint32_t sharcLogPaths = 0, sharcLogBounces = 0;   // PT_DEBUG_SHARC_LOG_PATHS: the last update pass's vertices
 };
 
 std::string& create_error();             // pt_api.hip: the message pt_last_error(NULL) returns (errors of the context-free entry points)

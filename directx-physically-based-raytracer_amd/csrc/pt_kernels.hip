@@ -219,9 +219,11 @@ __global__ __launch_bounds__(256) void k_pt_init(FrameView fv, const FrameConsta
 // wrote them -- so the block that gathers a tile of pixels into primary-surface records shades their first bounce right away, out of
 // the registers that hold the record, and emits the survivors as round 0 would have. The fresh state (48 B written, 48 B read), the record
 // read-back (48 B) and one launch per frame go away; values and draws are those of k_pt_init + shade_fresh.
-template <bool DI>
+// SHARC (the query pass of pt_raytrace_render_sharc): the survivors' previousRoughness goes to the side array roughOut.
+template <bool DI, bool SHARC = false>
 __global__ __launch_bounds__(256) void k_pt_first(FrameView fv, const FrameConstants* __restrict__ fc, PtTextures tx, PathQueue qout, float2* aux,
-                                                                                             uint32_t segCap, uint32_t* countOut, uint4* __restrict__ primary, uint32_t sqShift)
+                                                                                             uint32_t segCap, uint32_t* countOut, uint4* __restrict__ primary, uint32_t sqShift,
+                                                                                             float* roughOut = nullptr)
 {
     __shared__ uint32_t lds[32];
     uint32_t emits = 0;
@@ -236,6 +238,7 @@ __global__ __launch_bounds__(256) void k_pt_first(FrameView fv, const FrameConst
         bool toTraced = false, toFresh = false;
         PathRegs p; p.thr = V3(1.0f, 1.0f, 1.0f); p.srad = V3(0, 0, 0); p.rsum = V3(0, 0, 0); p.pixel = pix; p.rng = 0; p.sample = 0; p.bounce = 0;
         v3 newO = V3(0, 0, 0), newD = V3(0, 0, 1);
+        float pr = 0.0f;
         if (alive) {
             const uint32_t x = pix % fv.width, y = global_row(fv, pix / fv.width);
             p.rng = rng_init(x, y, gs.FrameIndex);
@@ -246,9 +249,9 @@ __global__ __launch_bounds__(256) void k_pt_first(FrameView fv, const FrameConst
             const uint4 r2 = make_uint4(((const uint32_t*)tx.BaseColorMetalness)[pix], rad.x, rad.y,
                                         (uint32_t)((const uint16_t*)tx.IOR)[pix] | ((uint32_t)((const uint8_t*)tx.Transmission)[pix] << 16));
             primary[3 * (size_t)pix] = r0; primary[3 * (size_t)pix + 1] = r1; primary[3 * (size_t)pix + 2] = r2;
-            shade_fresh_record<DI>(fv, cam, gs, tx, aux, r0, r1, r2, p, toTraced, toFresh, newO, newD);
+            shade_fresh_record<DI, SHARC>(fv, cam, gs, tx, aux, r0, r1, r2, p, toTraced, toFresh, newO, newD, &pr);
         }
-        emit_tile(qout, seg, segCap, &countOut[sq], &countOut[nsq + sq], lds + ((emits++ & 1u) << 4), toTraced, toFresh, p, newO, newD);
+        emit_tile<SHARC>(qout, seg, segCap, &countOut[sq], &countOut[nsq + sq], lds + ((emits++ & 1u) << 4), toTraced, toFresh, p, newO, newD, roughOut, pr);
     }
 }
 
@@ -361,9 +364,10 @@ struct RoundArgs {
     const uint4* recA; const uint32_t* recB; // the frame's normal records (null: none)
     uint32_t recordsInLds, sqShift;          // ... and how many of them are staged behind the object table (all or none); log2 of the number of sub-queues
     const uint4* primary;
+    const SharcView* sharc; const float* roughIn; float* roughOut;   // the SHARC instantiations only: the resolved cache, previousRoughness of qin / qout's entries
 };
 
-template <bool TEXTURED, bool LDS, bool FLAT, bool DI>
+template <bool TEXTURED, bool LDS, bool FLAT, bool DI, bool SHARC = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_round(const RoundArgs* __restrict__ A, uint32_t sqBase, uint32_t sqCount)
 {
     const SceneView& sv = A->sv; const FrameView& fv = A->fv; const PtTextures& tx = A->tx; const BlobView& bv = A->bv;
@@ -425,6 +429,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             float4 o = qin.r0[i], d = qin.r1[i];
             PathRegs p = load_path(qin, i);                       // issued before the traversal: its latency hides behind it (registers are
                                                                   // plentiful here, the kernel's budget is set by the shading half)
+            float pr = 0.0f;
+            if constexpr (SHARC) pr = A->roughIn[i];
             if (!valid) { o.w = 1.0f; d.w = 0.0f; }               // empty interval: hits nothing, but the lane still serves work items
             PT_PROF_MARK(prof, 0);
             Hit h;
@@ -439,11 +445,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             bool toTraced = false, toFresh = false;
             v3 newO = V3(0, 0, 0), newD = V3(0, 0, 1);
             if (valid) {
-                shade_traced<TEXTURED, DI>(sv, GeometryFromBlob<LDS>{ blob, bv, tables }, sd, gs, tx, aux, p, make_uint4(h.inst, h.slot, __float_as_uint(h.u), __float_as_uint(h.v)), h.t,
-                                       V3(d.x, d.y, d.z), toTraced, toFresh, newO, newD, prof);
+                shade_traced<TEXTURED, DI, SHARC>(sv, GeometryFromBlob<LDS>{ blob, bv, tables }, sd, gs, tx, aux, p, make_uint4(h.inst, h.slot, __float_as_uint(h.u), __float_as_uint(h.v)), h.t,
+                                       V3(d.x, d.y, d.z), toTraced, toFresh, newO, newD, prof, A->sharc, &pr);
             }
             PT_PROF_MARK(prof, 6);
-            emit_tile(qout, seg, segCap, &countOut[sq], &countOut[nsq + sq], lds + ((emits++ & 1u) << 4), toTraced, toFresh, p, newO, newD);
+            emit_tile<SHARC>(qout, seg, segCap, &countOut[sq], &countOut[nsq + sq], lds + ((emits++ & 1u) << 4), toTraced, toFresh, p, newO, newD, A->roughOut, pr);
             PT_PROF_MARK(prof, 7);
 #ifdef PT_ROUND_PROF
             prof->acc[11] += 1u;
@@ -455,13 +461,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         const uint32_t local = tile * 256u + threadIdx.x;
         bool toTraced = false, toFresh = false;
         PathRegs p; v3 newO = V3(0, 0, 0), newD = V3(0, 0, 1);
+        float pr = 0.0f;
         if (local < nF) {
             p = load_path(qin, seg + (segCap - 1u - local));
             PT_PROF_WAIT(); PT_PROF_MARK(prof, 12);
-            shade_fresh<DI>(fv, cam, gs, tx, aux, primary, p, toTraced, toFresh, newO, newD, prof);
+            shade_fresh<DI, SHARC>(fv, cam, gs, tx, aux, primary, p, toTraced, toFresh, newO, newD, prof, &pr);
         }
         PT_PROF_MARK(prof, 14);
-        emit_tile(qout, seg, segCap, &countOut[sq], &countOut[nsq + sq], lds + ((emits++ & 1u) << 4), toTraced, toFresh, p, newO, newD);
+        emit_tile<SHARC>(qout, seg, segCap, &countOut[sq], &countOut[nsq + sq], lds + ((emits++ & 1u) << 4), toTraced, toFresh, p, newO, newD, A->roughOut, pr);
         PT_PROF_MARK(prof, 15);
     }
 #ifdef PT_ROUND_PROF
@@ -823,8 +830,10 @@ static hipError_t enqueue_preamble(Context& c, const SceneView& sv, const FrameV
     if (normal_records_usable(c))                          // the frame's normal records, from the vertex buffers as they are now
         k_capture_normals<<<dim3(std::min((c.scene.blasTableMaxTris + 255u) / 256u, 64u), c.scene.blasTableCount), 256, 0, c.stream>>>(c.scene.blasTable, sv.shadeGeom, c.shadeRecA.data(), c.shadeRecB.data());
     if (frame_form(c).first) {
-        if (c.settings.IsDIEnabled) k_pt_first<true><<<grid, 256, 0, c.stream>>>(fv, c.frameConstants.data(), tx, c.queue[1], aux, segCap, &c.queueCounts.data()[cstride], c.primaryRecords.data(), c.sqShift);
-        else k_pt_first<false><<<grid, 256, 0, c.stream>>>(fv, c.frameConstants.data(), tx, c.queue[1], aux, segCap, &c.queueCounts.data()[cstride], c.primaryRecords.data(), c.sqShift);
+        #define PT_FIRST(D, S) k_pt_first<D, S><<<grid, 256, 0, c.stream>>>(fv, c.frameConstants.data(), tx, c.queue[1], aux, segCap, &c.queueCounts.data()[cstride], c.primaryRecords.data(), c.sqShift, c.sharcRough[1].data())
+        if (c.sharcQuery) { if (c.settings.IsDIEnabled) PT_FIRST(true, true); else PT_FIRST(false, true); }
+        else { if (c.settings.IsDIEnabled) PT_FIRST(true, false); else PT_FIRST(false, false); }
+        #undef PT_FIRST
     }
     else k_pt_init<<<grid, 256, 0, c.stream>>>(fv, c.frameConstants.data(), tx, c.queue[0], aux, segCap, &c.queueCounts.data()[nsq], c.primaryRecords.data(), c.sqShift);
     return hipGetLastError();
@@ -842,7 +851,7 @@ static hipError_t enqueue_chain(Context& c, const SceneView& sv, const FrameView
     const uint32_t perSq = std::max(1u, grid / nsq);                           // blocks per sub-queue
     const uint32_t sqBase = (uint32_t)((uint64_t)nsq * g / chains), sqCount = (uint32_t)((uint64_t)nsq * (g + 1) / chains) - sqBase;
     if (form.streaming) {                                                      // round 0's shading half ran inside k_pt_first
-        const bool wt = aux != nullptr;
+        const bool wt = aux != nullptr || c.sharcQuery;                        // the cache query needs the hit distance too
         for (uint32_t r = 0; r <= rounds; r++) {
             PathQueue& qin = c.queue[r & 1]; PathQueue& qout = c.queue[(r + 1) & 1];
             uint32_t* cin = &c.queueCounts.data()[r * cstride]; uint32_t* cout = &c.queueCounts.data()[(r + 1) * cstride];
@@ -863,14 +872,16 @@ static hipError_t enqueue_chain(Context& c, const SceneView& sv, const FrameView
     const uint32_t smem = (flat ? kFlatLdsFixed : kExtendLdsFixed) + (lds ? c.scene.blob.bytes : 0u) + round_objects_in_lds(c, sv) * kObjLds16 * 16u + lds_bytes_of_records(round_records_in_lds(c, sv));
     for (uint32_t r = 1; r <= rounds; r++) {                        // queues and counters of round r: in its argument block (launch_raytrace); round 0 ran inside k_pt_first
         timing_begin(c, c.evRound, c.nRound);
-        #define PT_ROUND(T, L, F) do { if (c.settings.IsDIEnabled) k_round<T, L, F, true><<<perSq * sqCount, 256, smem, s>>>(c.roundArgs.data() + r, sqBase, sqCount); \
-                                       else k_round<T, L, F, false><<<perSq * sqCount, 256, smem, s>>>(c.roundArgs.data() + r, sqBase, sqCount); } while (0)
+        #define PT_ROUND_S(T, L, F, D) do { if (c.sharcQuery) k_round<T, L, F, D, true><<<perSq * sqCount, 256, smem, s>>>(c.roundArgs.data() + r, sqBase, sqCount); \
+                                            else k_round<T, L, F, D, false><<<perSq * sqCount, 256, smem, s>>>(c.roundArgs.data() + r, sqBase, sqCount); } while (0)
+        #define PT_ROUND(T, L, F) do { if (c.settings.IsDIEnabled) PT_ROUND_S(T, L, F, true); else PT_ROUND_S(T, L, F, false); } while (0)
         #define PT_ROUND_F(T, L) do { if (flat) PT_ROUND(T, L, true); else PT_ROUND(T, L, false); } while (0)
         #define PT_ROUND_L(T) do { if (lds) PT_ROUND_F(T, true); else PT_ROUND_F(T, false); } while (0)
         if (c.heapHasTextures) PT_ROUND_L(true); else PT_ROUND_L(false);
         #undef PT_ROUND_L
         #undef PT_ROUND_F
         #undef PT_ROUND
+        #undef PT_ROUND_S
         timing_end(c, c.evRound, c.nRound); c.nRound++;
     }
     return hipGetLastError();
@@ -899,7 +910,7 @@ static hipError_t enqueue_validation_rounds(Context& c, const SceneView& sv, con
             if (stats) k_extend<true><<<grid, 256, 0, c.stream>>>(c.scene.blob, ac, qout, segCap, cout, c.counters.data(), c.sqShift);
             else k_extend<false><<<grid, 256, 0, c.stream>>>(c.scene.blob, ac, qout, segCap, cout, c.counters.data(), c.sqShift);
         } else {
-            const bool wt = aux != nullptr;                            // denoiser modes need CommittedRayT
+            const bool wt = aux != nullptr || c.sharcQuery;            // denoiser modes and the cache query need CommittedRayT
             #define PT_EXT2(S, L, W, F) k_extend2<S, L, W, F><<<grid, 256, smem, c.stream>>>(c.scene.blob, ac, qout, segCap, cout, c.counters.data(), c.sqShift)
             #define PT_EXT2_F(S, L, W) do { if (flat) PT_EXT2(S, L, W, true); else PT_EXT2(S, L, W, false); } while (0)
             #define PT_EXT2_W(S, L) do { if (wt) PT_EXT2_F(S, L, true); else PT_EXT2_F(S, L, false); } while (0)
@@ -951,6 +962,7 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
     if (e != hipSuccess) return e;
     if ((e = c.frameConstants.reserve(1)) != hipSuccess) return e;
     if (gs.Denoiser != PT_DENOISER_NONE && (e = c.pixelAux.reserve(npix)) != hipSuccess) return e;
+    if (c.sharcQuery) for (auto& a : c.sharcRough) if ((e = a.reserve((size_t)segCap * nsq)) != hipSuccess) return e;   // previousRoughness, indexed like the path queues
     FrameConstants fc; fc.cam = c.camera; fc.sd = c.sceneData; fc.gs = c.settings;
     k_set_constants<<<1, 256, 0, c.stream>>>(fc, c.frameConstants.data(), c.queueCounts.data(), (rounds + 2u) * cstride);
     // persistent grid, but never more blocks than the queue has tiles: surplus blocks only cost dispatch slots and LDS that
@@ -964,6 +976,7 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
     key_add(key, c.queue[0]); key_add(key, c.queue[1]); key_add(key, c.queueCounts.data()); key_add(key, c.scene.blob); key_add(key, c.heapHasTextures);
     key_add(key, c.frameConstants.data()); key_add(key, c.primaryRecords.data()); key_add(key, c.stream); key_add(key, c.pixelAux.data()); key_add(key, gs.Denoiser); key_add(key, c.debugFlags); key_add(key, gs.IsDIEnabled != 0u);
     key_add(key, c.framesInFlight); key_add(key, c.sqShift); key_add(key, c.chains);
+    key_add(key, c.sharcQuery); key_add(key, c.sharcView.data()); key_add(key, c.sharcRough[0].data()); key_add(key, c.sharcRough[1].data());
     key_add(key, c.shadeRecA.data()); key_add(key, c.scene.blasTable); key_add(key, c.scene.blasTableCount); key_add(key, c.scene.blasTableMaxTris); key_add(key, normal_records_usable(c));
     if (key != c.roundArgsKey || !c.roundArgs.data()) {                              // k_round's argument blocks, one per round (device memory)
         if ((e = c.roundArgs.reserve(rounds + 1)) != hipSuccess) return e;
@@ -976,6 +989,7 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
             a.fc = c.frameConstants.data(); a.aux = aux; a.countIn = &c.queueCounts.data()[r * cstride]; a.countOut = &c.queueCounts.data()[(r + 1) * cstride]; a.sqShift = c.sqShift;
             a.counters = c.counters.data(); a.segCap = segCap; a.primary = c.primaryRecords.data(); a.objectsInLds = round_objects_in_lds(c, sv);
             if (normal_records_usable(c)) { a.recA = c.shadeRecA.data(); a.recB = c.shadeRecB.data(); a.recordsInLds = round_records_in_lds(c, sv); }
+            if (c.sharcQuery) { a.sharc = c.sharcView.data(); a.roughIn = c.sharcRough[r & 1].data(); a.roughOut = c.sharcRough[(r + 1) & 1].data(); }
         }
         if ((e = hipMemcpyAsync(c.roundArgs.data(), host.data(), sizeof(RoundArgs) * (rounds + 1), hipMemcpyHostToDevice, c.stream)) != hipSuccess) return e;
         if ((e = hipStreamSynchronize(c.stream)) != hipSuccess) return e;    // once per change of the scene / frame geometry, never per frame
@@ -984,7 +998,7 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
 
     // hipGraph replay: launch-bound frames (small shards, tail rounds) cost ~75 launches; a replay is one submission.
     const bool graphable = c.stream != nullptr && !c.timing && !c.disableGraphs &&
-                           (c.debugFlags & ~(PT_DEBUG_UNFUSED_ROUNDS | PT_DEBUG_TRAVERSAL_PHASED | PT_DEBUG_LOCKSTEP | PT_DEBUG_GATHER_LOCAL_ONLY | PT_DEBUG_GATHER_SELF_EXCHANGE)) == 0;   // counters / validation variants launch directly
+                           (c.debugFlags & ~(PT_DEBUG_UNFUSED_ROUNDS | PT_DEBUG_TRAVERSAL_PHASED | PT_DEBUG_LOCKSTEP | PT_DEBUG_GATHER_LOCAL_ONLY | PT_DEBUG_GATHER_SELF_EXCHANGE | PT_DEBUG_SHARC_LOG_PATHS | PT_DEBUG_SHARC_SKIP_UPDATE)) == 0;   // counters / validation variants launch directly
     auto capture = [&](hipStream_t s, GraphExec& exec, auto&& body) -> hipError_t {               // one linear graph from what `body` enqueues on s
         if (exec) { hipStreamSynchronize(c.stream); exec.reset(); }                                 // its last replay may still be running (once per change of scene / frame geometry)
         hipGraph_t graph = nullptr;

@@ -4,6 +4,7 @@
 // (Shaders/Raytracing.hlsl:219-364), end of a sample (:372-413), bounce 0 from the primary-surface record (:118-148,193-198).
 #pragma once
 #include "pt_internal.hpp"
+#include "pt_sharc.hpp"
 
 namespace pt {
 
@@ -312,7 +313,38 @@ PT_DEV void store_path(const PathQueue& q, uint32_t i, const PathRegs& p)
 // weights, BSDF sample, throughput update, Russian roulette, luminance cut-off. Returns true when the path goes on
 // with the ray (newO, newD); false ends the sample. RNG draws happen exactly as in the reference, also on the last
 // iteration (bounce == Bounces), which samples but never traces (:213).
-PT_DEV bool scatter(const PtGraphicsSettings& gs, PathRegs& p, const SurfaceHit& h, const BSDFSample& bs, v3 emission, v3 rayDir, v3& newO, v3& newD, int& lobe)
+// The BSDF step of a bounce (Raytracing.hlsl:323-356) for the radiance cache's update pass (pt_sharc.hip): lobe weights, GetFloat4, sample,
+// single-lobe evaluate, throughput update, Russian roulette; false ends the path; rndOut: the four draws, for a log. The same statements as
+// in scatter() below, which keeps its own copy: routing scatter() through this function moved spills in the plain k_round / k_pt_first
+// (62 -> 64 spilled SGPRs, 8 -> 10 spilled VGPRs in one variant), and those kernels stay the code they were. A change to one is a change to
+// both; tests/test_sharc_gpu.py::test_log_validity holds this one to pt_bsdf_sample, and k_bsdf_sample to scatter()'s statements.
+PT_DEV bool scatter_step(const PtGraphicsSettings& gs, uint32_t bounce, uint32_t& rng, v3& thr, const SurfaceHit& h, const BSDFSample& bs, v3 rayDir, v3& L, int& lobe,
+                         float* rndOut = nullptr)
+{
+    const SurfaceVectors svec = surface_vectors(h.IsFrontFace, h.GeometricNormal, h.ShadingNormal);
+    const v3 V = -rayDir;
+    float w[3]; bs.ComputeLobeWeights(svec, V, gs.ExtFlags, w);
+    float rnd[4];
+    rnd[0] = rng_float(rng); rnd[1] = rng_float(rng); rnd[2] = rng_float(rng); rnd[3] = rng_float(rng);   // GetFloat4, :330
+    if (rndOut) { rndOut[0] = rnd[0]; rndOut[1] = rnd[1]; rndOut[2] = rnd[2]; rndOut[3] = rnd[3]; }
+    if (!bs.Sample(svec, V, w, rnd, L, lobe)) return false;
+    float pdf; v3 f;
+    bs.EvaluateLobe(svec, L, V, w, lobe, gs.ExtFlags, pdf, f);
+    if (pdf == 0.0f || (f.x == 0.0f && f.y == 0.0f && f.z == 0.0f)) return false;             // :336,342
+    { const float ipdf = 1.0f / pdf; thr = thr * V3(f.x * ipdf, f.y * ipdf, f.z * ipdf); }     // :346 (float3 / float = the vector times ONE reciprocal: arithmetic spec)
+    if (gs.IsRussianRouletteEnabled && bounce > 3) {                                          // :348-356
+        const float prob = fmaxf(thr.x, fmaxf(thr.y, thr.z));
+        if (rng_float(rng) >= prob) return false;
+        { const float iprob = 1.0f / prob; thr = V3(thr.x * iprob, thr.y * iprob, thr.z * iprob); }
+    }
+    return true;
+}
+
+// SHARC (the query pass of the radiance cache, pt_raytrace_render_sharc): previousRoughness, the blur the path has gathered so far, grows by
+// the sampled lobe's width after every scatter (:366).
+template <bool SHARC = false>
+PT_DEV bool scatter(const PtGraphicsSettings& gs, PathRegs& p, const SurfaceHit& h, const BSDFSample& bs, v3 emission, v3 rayDir, v3& newO, v3& newD, int& lobe,
+                    float* previousRoughness = nullptr)
 {
     p.srad = madd(p.thr, emission, p.srad);                       // :320
     const SurfaceVectors svec = surface_vectors(h.IsFrontFace, h.GeometricNormal, h.ShadingNormal);
@@ -332,6 +364,7 @@ PT_DEV bool scatter(const PtGraphicsSettings& gs, PathRegs& p, const SurfaceHit&
         { const float iprob = 1.0f / prob; p.thr = V3(p.thr.x * iprob, p.thr.y * iprob, p.thr.z * iprob); }
     }
     if (ml_luminance(p.thr) <= gs.ThroughputThreshold) return false;                          // :361
+    if constexpr (SHARC) *previousRoughness += lobe == LOBE_DIFFUSE ? 1.0f : bs.Roughness;
     if (!(p.bounce < gs.Bounces)) return false;                                               // loop bound, :213
     newO = safe_world_ray_origin(h.Position, h.FlatNormal, h.PositionOffset, L);              // :221
     newD = L;
@@ -355,7 +388,7 @@ PT_DEV bool direct_valid(const PtTextures& tx, uint32_t pixel)        // isDIVal
 }
 
 // sample ended: accumulate, start the next sample of the pixel or finish the pixel (Raytracing.hlsl:372-413)
-template <bool DI = false>
+template <bool DI = false, bool SHARC = false>
 PT_DEV bool end_sample(const PtGraphicsSettings& gs, const PtTextures& tx, const float2* aux, PathRegs& p)
 {
     p.rsum = p.rsum + p.srad;                                    // :372
@@ -382,7 +415,7 @@ PT_DEV bool end_sample(const PtGraphicsSettings& gs, const PtTextures& tx, const
         if (tx.Specular) ((ushort4*)tx.Specular)[p.pixel] = isDiffuse ? zero : packed;
         return false;
     }
-    if constexpr (DI) { v3 dd, ds; load_direct(tx, p.pixel, dd, ds); out = out + (dd + ds); }   // radiance += DI, after the division (:382, :390)
+    if constexpr (DI && !SHARC) { v3 dd, ds; load_direct(tx, p.pixel, dd, ds); out = out + (dd + ds); }   // radiance += DI, after the division (:382, :390); the query pass added it per sample (:318)
     if (gs.Denoiser == PT_DENOISER_DLSS_RAY_RECONSTRUCTION && tx.SpecularHitDistance) {      // :395-398
         const float2 a = aux[p.pixel];
         if (a.y == 0.0f && isfinite(a.x)) ((uint16_t*)tx.SpecularHitDistance)[p.pixel] = f32_to_f16(a.x);
@@ -399,9 +432,11 @@ template <bool LDS> struct GeometryFromBlob {                // ... out of the s
     PT_DEV HitGeometry load(uint32_t inst, uint32_t slot) const { return load_hit_geometry<LDS>(blob, bv, inst, slot); }
 };
 
-template <bool TEXTURED, bool DI = false, typename GEOMETRY>
+// SHARC: `sharc` is the resolved cache, previousRoughness the path's entry of the side array; hitT is the hit's distance along the ray.
+template <bool TEXTURED, bool DI = false, bool SHARC = false, typename GEOMETRY>
 PT_DEV void shade_traced(const SceneView& sv, const GEOMETRY& geometry, const PtSceneData& sd, const PtGraphicsSettings& gs, const PtTextures& tx, float2* aux,
-                         PathRegs& p, uint4 hr, float hitT, v3 rayDir, bool& toTraced, bool& toFresh, v3& newO, v3& newD, RoundProf* prof = nullptr)
+                         PathRegs& p, uint4 hr, float hitT, v3 rayDir, bool& toTraced, bool& toFresh, v3& newO, v3& newD, RoundProf* prof = nullptr,
+                         const SharcView* sharc = nullptr, float* previousRoughness = nullptr)
 {
     bool goes = false; int lobe = 0;
     if (aux && p.sample == 0 && p.bounce == 1) aux[p.pixel].x = hr.x == ~0u ? INFINITY : hitT;        // hitDistance, :235-239
@@ -411,22 +446,30 @@ PT_DEV void shade_traced(const SceneView& sv, const GEOMETRY& geometry, const Pt
         SurfaceHit h;
         reconstruct_hit<TEXTURED>(sv, geometry.load(hr.x, hr.y), hr.x, __uint_as_float(hr.z), __uint_as_float(hr.w), rayDir, h, geometry.tables);
         PT_PROF_MARK(prof, 5);
-        const PtMaterial m = surface_material<TEXTURED>(sv, h, geometry.tables.objects);
-        BSDFSample bs;
-        bs.Initialize(V3(m.BaseColor), m.Metallic, m.Roughness, m.IOR, m.Transmission, h.IsFrontFace);
-        v3 emission = material_emission(m);
-        if constexpr (DI) if (p.bounce == 1u && direct_valid(tx, p.pixel)) emission = V3(0, 0, 0);   // the DI pass lit this path's first hit, :302
-        goes = scatter(gs, p, h, bs, emission, rayDir, newO, newD, lobe);
+        bool cached = false;
+        if constexpr (SHARC) {                               // :262-289: a valid cache hit ends the sample before the material is evaluated
+            v3 radiance;
+            cached = sharc_query(*sharc, h.Position, dot(h.FlatNormal, rayDir) < 0.0f ? h.FlatNormal : -h.FlatNormal, hitT, *previousRoughness, radiance);
+            if (cached) p.srad = madd(p.thr, radiance, p.srad);
+        }
+        if (!cached) {
+            const PtMaterial m = surface_material<TEXTURED>(sv, h, geometry.tables.objects);
+            BSDFSample bs;
+            bs.Initialize(V3(m.BaseColor), m.Metallic, m.Roughness, m.IOR, m.Transmission, h.IsFrontFace);
+            v3 emission = material_emission(m);
+            if constexpr (DI) if (p.bounce == 1u && direct_valid(tx, p.pixel)) emission = V3(0, 0, 0);   // the DI pass lit this path's first hit, :302
+            goes = scatter<SHARC>(gs, p, h, bs, emission, rayDir, newO, newD, lobe, previousRoughness);
+        }
     }
     if (goes) toTraced = true;
-    else toFresh = end_sample<DI>(gs, tx, aux, p);
+    else toFresh = end_sample<DI, SHARC>(gs, tx, aux, p);
 }
 
 // A fresh path: bounce 0 on the primary surface rebuilt from the G-buffer, Raytracing.hlsl:118-148,193-198
 // (r0, r1, r2: the pixel's primary-surface record)
-template <bool DI = false>
+template <bool DI = false, bool SHARC = false>
 PT_DEV void shade_fresh_record(const FrameView& fv, const PtCamera& cam, const PtGraphicsSettings& gs, const PtTextures& tx, float2* aux, uint4 r0, uint4 r1, uint4 r2,
-                               PathRegs& p, bool& toTraced, bool& toFresh, v3& newO, v3& newD)
+                               PathRegs& p, bool& toTraced, bool& toFresh, v3& newO, v3& newD, float* previousRoughness = nullptr)
 {
     const uint32_t pixel = p.pixel;
     const uint32_t px = pixel % fv.width, py = global_row(fv, pixel / fv.width);
@@ -452,20 +495,24 @@ PT_DEV void shade_fresh_record(const FrameView& fv, const PtCamera& cam, const P
     bs.Initialize(V3(unorm8_to_f32(bcm.x), unorm8_to_f32(bcm.y), unorm8_to_f32(bcm.z)), metal, snorm16_to_f32(nr.w), ior, tr, h.IsFrontFace);
     int lobe = 0;
     const bool first = p.sample == 0;
-    if (scatter(gs, p, h, bs, emission, rayDir, newO, newD, lobe)) {
+    if constexpr (SHARC) {                                                           // a sample starts: no blur yet (:209); the footprint is 0, so bounce 0 never queries
+        *previousRoughness = 0.0f;
+        if constexpr (DI) { v3 dd, ds; load_direct(tx, p.pixel, dd, ds); p.srad = p.srad + (dd + ds); }   // the DI term once per sample, unscaled (:318)
+    }
+    if (scatter<SHARC>(gs, p, h, bs, emission, rayDir, newO, newD, lobe, previousRoughness)) {
         toTraced = true;
         if (aux && first) aux[p.pixel].y = lobe == LOBE_DIFFUSE ? 1.0f : 0.0f;       // isDiffuse of the lobe sampled at bounce 0, :237
-    } else toFresh = end_sample<DI>(gs, tx, aux, p);
+    } else toFresh = end_sample<DI, SHARC>(gs, tx, aux, p);
 }
 
-template <bool DI = false>
+template <bool DI = false, bool SHARC = false>
 PT_DEV void shade_fresh(const FrameView& fv, const PtCamera& cam, const PtGraphicsSettings& gs, const PtTextures& tx, float2* aux, const uint4* __restrict__ primary,
-                        PathRegs& p, bool& toTraced, bool& toFresh, v3& newO, v3& newD, RoundProf* prof = nullptr)
+                        PathRegs& p, bool& toTraced, bool& toFresh, v3& newO, v3& newD, RoundProf* prof = nullptr, float* previousRoughness = nullptr)
 {
     const uint32_t pixel = p.pixel;
     const uint4 r0 = primary[3 * (size_t)pixel], r1 = primary[3 * (size_t)pixel + 1], r2 = primary[3 * (size_t)pixel + 2];
     PT_PROF_WAIT(); PT_PROF_MARK(prof, 13);
-    shade_fresh_record<DI>(fv, cam, gs, tx, aux, r0, r1, r2, p, toTraced, toFresh, newO, newD);
+    shade_fresh_record<DI, SHARC>(fv, cam, gs, tx, aux, r0, r1, r2, p, toTraced, toFresh, newO, newD, previousRoughness);
 }
 
 // compaction + stores of one tile: survivors to the traced region (state + ray), restarts to the fresh region (state).
@@ -473,8 +520,10 @@ PT_DEV void shade_fresh(const FrameView& fv, const PtCamera& cam, const PtGraphi
 // runs 20 % SLOWER -- 8.6 against 10.8 Grays/s. A block appends the survivors of 256 neighbouring pixels as one run, so a tile of the
 // next round is made of two or three such runs; with 64-entry runs appended in arrival order the neighbourhoods dissolve four times as
 // fast, and coherent tiles are what keeps the item lists of the traversal balanced and the loads of the shading half on few cache lines.
+// SHARC: the survivor's previousRoughness goes to the side array at its slot (a restart begins at 0: nothing to keep).
+template <bool SHARC = false>
 PT_DEV void emit_tile(const PathQueue& qout, uint32_t seg, uint32_t segCap, uint32_t* countTraced, uint32_t* countFresh, uint32_t* lds,
-                      bool toTraced, bool toFresh, const PathRegs& p, v3 newO, v3 newD)
+                      bool toTraced, bool toFresh, const PathRegs& p, v3 newO, v3 newD, float* roughnessOut = nullptr, float previousRoughness = 0.0f)
 {
     uint32_t st, sf;
     block_reserve2(toTraced, toFresh, countTraced, countFresh, lds, st, sf);
@@ -482,6 +531,7 @@ PT_DEV void emit_tile(const PathQueue& qout, uint32_t seg, uint32_t segCap, uint
         store_path(qout, seg + st, p);
         qout.r0[seg + st] = make_float4(newO.x, newO.y, newO.z, 0.0f);                    // TMin = 0, :223
         qout.r1[seg + st] = make_float4(newD.x, newD.y, newD.z, INFINITY);                // TMax = inf, :224
+        if constexpr (SHARC) roughnessOut[seg + st] = previousRoughness;
     }
     if (toFresh) store_path(qout, seg + (segCap - 1u - sf), p);
 }

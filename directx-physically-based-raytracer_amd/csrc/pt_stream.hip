@@ -9,11 +9,11 @@ namespace pt {
 // counts: [0..nsq) traced, [nsq..2*nsq) fresh (nsq = 1 << sqShift sub-queues)
 // k_shade<false> wants 132 VGPRs, one more than four waves per SIMD allow; held to 128 it spills nothing and the fourth wave is worth
 // +1.8 % on C3 and +0.7 % on C5 (the kernel waits on its 268 B per ray, not on issue slots)
-template <bool TEXTURED, bool DI>
+template <bool TEXTURED, bool DI, bool SHARC = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_shade(SceneView sv, FrameView fv, const FrameConstants* __restrict__ fc, PtTextures tx,
                                                PathQueue qin, PathQueue qout, float2* aux, uint32_t segCap, const uint32_t* countIn, uint32_t* countOut,
                                                const uint4* __restrict__ primary, BlobView bv, const uint4* __restrict__ recA, const uint32_t* __restrict__ recB, uint32_t sqShift,
-                                               uint32_t sqBase, uint32_t sqCount)
+                                               uint32_t sqBase, uint32_t sqCount, const SharcView* sharc = nullptr, const float* roughIn = nullptr, float* roughOut = nullptr)
 {
     BlobReader<false> blob; blob.p = bv.base;
     ShadeTables tables; tables.recA = recA; tables.recB = recB;            // the frame's normal records (null: vertices are fetched at the hit)
@@ -29,23 +29,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         const uint32_t i = seg + local;
         bool toTraced = false, toFresh = false;
         PathRegs p; v3 newO = V3(0, 0, 0), newD = V3(0, 0, 1);
+        float pr = 0.0f;
         if (local < nT) {
             p = load_path(qin, i);
             const uint4 hr = qin.hit[i];
-            const float4 rd = qin.r1[i];                                     // k_extend left t in r1.w (denoiser modes)
-            shade_traced<TEXTURED, DI>(sv, GeometryFromBlob<false>{ blob, bv, tables }, sd, gs, tx, aux, p, hr, rd.w, V3(rd.x, rd.y, rd.z), toTraced, toFresh, newO, newD);
+            const float4 rd = qin.r1[i];                                     // k_extend left t in r1.w (denoiser modes, cache query)
+            if constexpr (SHARC) pr = roughIn[i];
+            shade_traced<TEXTURED, DI, SHARC>(sv, GeometryFromBlob<false>{ blob, bv, tables }, sd, gs, tx, aux, p, hr, rd.w, V3(rd.x, rd.y, rd.z), toTraced, toFresh, newO, newD, nullptr, sharc, &pr);
         }
-        emit_tile(qout, seg, segCap, &countOut[sq], &countOut[nsq + sq], lds + ((emits++ & 1u) << 4), toTraced, toFresh, p, newO, newD);
+        emit_tile<SHARC>(qout, seg, segCap, &countOut[sq], &countOut[nsq + sq], lds + ((emits++ & 1u) << 4), toTraced, toFresh, p, newO, newD, roughOut, pr);
     }
     for (uint32_t tile = bq; tile * 256u < nF; tile += nbq) {                // fresh entries
         const uint32_t local = tile * 256u + threadIdx.x;
         bool toTraced = false, toFresh = false;
         PathRegs p; v3 newO = V3(0, 0, 0), newD = V3(0, 0, 1);
+        float pr = 0.0f;
         if (local < nF) {
             p = load_path(qin, seg + (segCap - 1u - local));
-            shade_fresh<DI>(fv, cam, gs, tx, aux, primary, p, toTraced, toFresh, newO, newD);
+            shade_fresh<DI, SHARC>(fv, cam, gs, tx, aux, primary, p, toTraced, toFresh, newO, newD, nullptr, &pr);
         }
-        emit_tile(qout, seg, segCap, &countOut[sq], &countOut[nsq + sq], lds + ((emits++ & 1u) << 4), toTraced, toFresh, p, newO, newD);
+        emit_tile<SHARC>(qout, seg, segCap, &countOut[sq], &countOut[nsq + sq], lds + ((emits++ & 1u) << 4), toTraced, toFresh, p, newO, newD, roughOut, pr);
     }
 }
 
@@ -266,7 +269,10 @@ hipError_t launch_shade(Context& c, const SceneView& sv, const FrameView& fv, co
 {
     const bool rec = normal_records_usable(c);
     const uint4* recA = rec ? c.shadeRecA.data() : nullptr; const uint32_t* recB = rec ? c.shadeRecB.data() : nullptr;
-    #define PT_SHADE(T, D) k_shade<T, D><<<grid, 256, 0, stream>>>(sv, fv, c.frameConstants.data(), tx, qin, qout, aux, segCap, countIn, countOut, c.primaryRecords.data(), c.scene.blob, recA, recB, c.sqShift, sqBase, sqCount)
+    // the queues alternate with the rounds, and so do their previousRoughness arrays (SHARC query)
+    const int qi = qin.s0 == c.queue[0].s0 ? 0 : 1;
+    #define PT_SHADE(T, D) do { if (c.sharcQuery) k_shade<T, D, true><<<grid, 256, 0, stream>>>(sv, fv, c.frameConstants.data(), tx, qin, qout, aux, segCap, countIn, countOut, c.primaryRecords.data(), c.scene.blob, recA, recB, c.sqShift, sqBase, sqCount, c.sharcView.data(), c.sharcRough[qi].data(), c.sharcRough[qi ^ 1].data()); \
+                                  else k_shade<T, D, false><<<grid, 256, 0, stream>>>(sv, fv, c.frameConstants.data(), tx, qin, qout, aux, segCap, countIn, countOut, c.primaryRecords.data(), c.scene.blob, recA, recB, c.sqShift, sqBase, sqCount); } while (0)
     if (c.settings.IsDIEnabled) { if (c.heapHasTextures) PT_SHADE(true, true); else PT_SHADE(false, true); }
     else { if (c.heapHasTextures) PT_SHADE(true, false); else PT_SHADE(false, false); }
     #undef PT_SHADE

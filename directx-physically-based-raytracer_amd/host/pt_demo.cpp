@@ -2,7 +2,7 @@
 // reference-shaped operators of ptamd.hpp (GBufferGeneration / Raytracing / RaytracingHelpers), times it and
 // optionally dumps the radiance for the parity test (tests/test_host_cpp.py compares it with the oracle).
 //
-//   pt_demo [--width W] [--height H] [--spp S] [--bounces B] [--frames N] [--out file.bin] [--ranks R] [--di] [--di-samples N] [--restir]
+//   pt_demo [--width W] [--height H] [--spp S] [--bounces B] [--frames N] [--out file.bin] [--ranks R] [--di] [--di-samples N] [--restir] [--sharc]
 //           [--light-sampling cdf|uniform|power_ris|regir]
 //           [--post] [--no-bloom] [--bloom-strength S] [--tone-map saturate|reinhard|aces] [--exposure E]
 //           [--hdr [--paper-white N] [--color-rotation hdtv_to_uhdtv|dci_p3_d65_to_uhdtv|hdtv_to_dci_p3_d65]]
@@ -351,6 +351,7 @@ int main(int argc, char** argv)
 {
     uint32_t W = 1920, H = 1080, spp = 4, bounces = 8, frames = 10, ranks = 0, rank = 0, world = 1;
     uint32_t diSamples = 8; bool di = false, restir = false;
+    bool useSharc = false; uint32_t sharcDownscale = 4; float sceneScale = 50.0f;   // --sharc [--sharc-downscale N --scene-scale S]: frames through the radiance cache
     std::string out, idFile, scenePath, dumpPath, lightSampling = "cdf";
     bool post = false, bloom = true, hdr = false; float bloomStrength = 0.05f, exposure = 0.0f, paperWhite = 200.0f;
     std::string toneMap = "aces", colorRotation = "hdtv_to_uhdtv", pngPath, displayPath;
@@ -358,6 +359,7 @@ int main(int argc, char** argv)
         std::string k = argv[i];
         if (k == "--di") { di = true; continue; }                  // the flags without a value
         if (k == "--restir") { restir = true; continue; }
+        if (k == "--sharc") { useSharc = true; continue; }
         if (k == "--post") { post = true; continue; }
         if (k == "--no-bloom") { bloom = false; continue; }
         if (k == "--hdr") { hdr = true; continue; }
@@ -369,6 +371,7 @@ int main(int argc, char** argv)
         else if (k == "--ranks") ranks = atoi(v); else if (k == "--rank") rank = atoi(v);
         else if (k == "--world") world = atoi(v); else if (k == "--id-file") idFile = v;
         else if (k == "--di-samples") diSamples = atoi(v);
+        else if (k == "--sharc-downscale") sharcDownscale = atoi(v); else if (k == "--scene-scale") sceneScale = (float)atof(v);
         else if (k == "--light-sampling") lightSampling = v;
         else if (k == "--scene") scenePath = v; else if (k == "--dump-scene") dumpPath = v;
         else if (k == "--bloom-strength") bloomStrength = (float)atof(v); else if (k == "--tone-map") toneMap = v;
@@ -519,6 +522,10 @@ int main(int argc, char** argv)
         directLighting.GPUBuffers = { &sd, &cam, dObjects, n };
         directLighting.Textures = tx;
         if (restir && (!di || sharded)) throw std::invalid_argument("--restir needs --di and one unsharded process");
+        if (useSharc && sharded) throw std::invalid_argument("--sharc needs one unsharded process");
+        SHARC sharc(commandList);
+        Raytracing::SHARCSettings sharcSettings; sharcSettings.DownscaleFactor = sharcDownscale;
+        if (useSharc) { sharc.Constants.SceneScale = sceneScale; sharc.Configure(); }
         if (lightSampling != "cdf") {
             using Mode = DirectLighting::ReSTIRDILocalLightSamplingMode;
             DirectLighting::LightSampling l;
@@ -559,7 +566,8 @@ int main(int argc, char** argv)
             gs.FrameIndex = frameIndex; gs.Bounces = bounces; gs.SamplesPerPixel = spp; gs.IsRussianRouletteEnabled = true;
             gs.IsDIEnabled = di;
             raytracing.SetConstants(gs);
-            raytracing.Render(commandList, tlas);
+            if (useSharc) raytracing.Render(commandList, tlas, sharc, sharcSettings);
+            else raytracing.Render(commandList, tlas);
             if (sharded) sharding.GatherBands(commandList, tx.Radiance, fullRadiance, W, H, 8);
             if (runPost) postProcessing.Render(commandList);
         };
@@ -578,7 +586,10 @@ int main(int argc, char** argv)
             ThrowIfFailed(commandList.Context, pt_di_light_count(commandList.Context, &lights));
             fprintf(stderr, "pt_demo: direct lighting over %u emissive triangles, %u candidates per pixel\n", lights, diSamples);
         }
-        if (!sharded)
+        if (useSharc)        // rays count the update pass's too
+            printf("{\"host\": \"c++\", \"sharc\": true, \"width\": %u, \"height\": %u, \"spp\": %u, \"bounces\": %u, \"frames\": %u, \"sharc_entries\": %u, \"secondary_rays\": %.0f, \"rays\": %.0f, \"ms_per_frame\": %.4f}\n",
+                   W, H, spp, bounces, frames, sharc.LiveEntries(), (double)counters.SecondaryRays, rays, ms / frames);
+        else if (!sharded)
             printf("{\"host\": \"c++\", \"width\": %u, \"height\": %u, \"spp\": %u, \"bounces\": %u, \"frames\": %u, \"rays\": %.0f, \"ms_per_frame\": %.4f, \"mrays_per_s\": %.1f}\n",
                    W, H, spp, bounces, frames, rays, ms / frames, rays / ms / 1e3);
         else       // rays are this rank's; rank 0's time includes every peer's bands arriving

@@ -3,7 +3,7 @@
 // Same names, members and call order as the reference structs this path replaces, so that
 // App::RenderScene (Source/App.cpp:1157-1329) keeps its shape when it is pointed at the MI355X path:
 //     struct GBufferGeneration   Source/GBufferGeneration.ixx:27-122
-//     struct Raytracing          Source/Raytracing.ixx:29-250      (DEFAULT permutation; SHARC overload absent)
+//     struct Raytracing          Source/Raytracing.ixx:29-250      (DEFAULT permutation, and the SHARC overload with struct SHARC)
 //     BuildTopLevelAccelerationStructure / CreateGeometryDesc       Source/RaytracingHelpers.ixx:28-105
 //     struct SkeletalMeshSkinning Source/SkeletalMeshSkinning.ixx:20-66
 //     struct PostProcessing      App::PostProcessGraphics with Denoiser::None (Source/App.cpp:1506-1571): Bloom, Merge, ToneMap, CopyTexture
@@ -321,7 +321,22 @@ private:
     PtContext* m_context;
 };
 
+// struct SHARC, Source/SHARC.ixx: the radiance cache's buffers (context-owned here) and its constants
+struct SHARC {
+    struct ConstantsData { uint32_t AccumulationFrames = 10, MaxStaleFrames = 64; float SceneScale = 50; bool IsAntiFireflyEnabled = true; };
+
+    explicit SHARC(CommandList& commandList) : m_context(commandList.Context) {}
+    void Configure(uint32_t capacity = 1u << 22) { ThrowIfFailed(m_context, pt_sharc_configure(m_context, capacity)); }   // a multiple of 32; empties the cache
+    void Reset() { ThrowIfFailed(m_context, pt_sharc_reset(m_context)); }                                                   // App.cpp:682-685
+    uint32_t LiveEntries() { uint32_t n = 0; ThrowIfFailed(m_context, pt_sharc_download(m_context, nullptr, 0, &n)); return n; }
+    ConstantsData Constants{};
+
+private:
+    PtContext* m_context;
+};
+
 struct Raytracing {
+    struct SHARCSettings { uint32_t DownscaleFactor = 4; float RoughnessThreshold = 0.4f; bool IsHashGridVisualizationEnabled = false; };   // Source/Raytracing.ixx, MyAppData.h:250-262
     struct GraphicsSettings {                               // Source/Raytracing.ixx:30-36
         uint32_t RenderSize[2]{};
         uint32_t FrameIndex{}, Bounces{}, SamplesPerPixel{};
@@ -359,6 +374,23 @@ struct Raytracing {
         ThrowIfFailed(c, pt_set_object_data(c, GPUBuffers.ObjectData, GPUBuffers.ObjectCount));
         ThrowIfFailed(c, pt_raytrace_set_constants(c, &m_graphicsSettings));
         ThrowIfFailed(c, pt_raytrace_render(c, &Textures));
+    }
+
+    // the overload with RTXGITechnique::SHARC (:114-148): clear, update, resolve, query, swap
+    void Render(CommandList& commandList, const RaytracingHelpers::TopLevelAccelerationStructure& topLevelAccelerationStructure, SHARC& sharc, const SHARCSettings& sharcSettings)
+    {
+        if (!topLevelAccelerationStructure.Valid) throw std::invalid_argument("top-level acceleration structure has not been built");
+        PtContext* c = commandList.Context;
+        PtSHARCSettings s{};
+        s.AccumulationFrames = sharc.Constants.AccumulationFrames; s.MaxStaleFrames = sharc.Constants.MaxStaleFrames; s.SceneScale = sharc.Constants.SceneScale;
+        s.IsAntiFireflyEnabled = sharc.Constants.IsAntiFireflyEnabled; s.DownscaleFactor = sharcSettings.DownscaleFactor;
+        s.RoughnessThreshold = sharcSettings.RoughnessThreshold; s.IsHashGridVisualizationEnabled = sharcSettings.IsHashGridVisualizationEnabled;
+        ThrowIfFailed(c, pt_set_scene_data(c, GPUBuffers.SceneData));
+        ThrowIfFailed(c, pt_set_camera(c, GPUBuffers.Camera));
+        ThrowIfFailed(c, pt_set_object_data(c, GPUBuffers.ObjectData, GPUBuffers.ObjectCount));
+        ThrowIfFailed(c, pt_raytrace_set_constants(c, &m_graphicsSettings));
+        ThrowIfFailed(c, pt_sharc_set_constants(c, &s));
+        ThrowIfFailed(c, pt_raytrace_render_sharc(c, &Textures));
     }
 
 private:

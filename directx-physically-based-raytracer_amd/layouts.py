@@ -221,6 +221,62 @@ def post_processing_settings(width, height, bloom=True, strength=0.05, operator=
     return check_post_processing_settings(s)
 
 
+SHARC_SETTINGS = np.dtype({  # PtSHARCSettings: SHARC::Constants + Raytracing::SHARCSettings (Source/MyAppData.h:250-262)
+    "names": ["AccumulationFrames", "MaxStaleFrames", "SceneScale", "IsAntiFireflyEnabled", "DownscaleFactor", "RoughnessThreshold",
+              "IsHashGridVisualizationEnabled"],
+    "formats": ["<u4", "<u4", "<f4", "<u4", "<u4", "<f4", "<u4"], "offsets": [0, 4, 8, 12, 16, 20, 24], "itemsize": 28})
+SHARC_DEFAULT_CAPACITY = 1 << 22
+SHARC_ENTRY = np.dtype({  # PtSHARCEntry: a live entry of the resolved buffer
+    "names": ["Key", "Voxel"], "formats": ["<u8", ("<u4", 4)], "offsets": [0, 8], "itemsize": 32})
+SHARC_QUERY_RESULT = np.dtype({"names": ["Valid", "Radiance"], "formats": ["<u4", ("<f4", 3)], "offsets": [0, 4], "itemsize": 16})
+SHARC_PATH_VERTEX = np.dtype({  # PtSHARCPathVertex: one bounce of one update path
+    "names": ["Position", "Flags", "Normal", "Random", "Radiance", "KeyLo", "Throughput", "KeyHi"],
+    "formats": [("<f4", 3), "<u4", ("<f4", 3), "<f4", ("<f4", 3), "<u4", ("<f4", 3), "<u4"],
+    "offsets": [0, 12, 16, 28, 32, 44, 48, 60], "itemsize": 64})
+SHARC_PATH_SCATTER = np.dtype({  # PtSHARCPathScatter: the BSDF step of the same bounce; the first 96 bytes are a PtBsdfSampleQuery
+    "names": ["Query", "Origin", "Sampled", "L", "Goes"], "formats": [("u1", 96), ("<f4", 3), "<u4", ("<f4", 3), "<u4"],
+    "offsets": [0, 96, 108, 112, 124], "itemsize": 128})
+SHARC_VERTEX_HIT, SHARC_VERTEX_MISS, SHARC_VERTEX_ENDED, SHARC_VERTEX_RESAMPLED = 1, 2, 4, 8
+DEBUG_SHARC_LOG_PATHS, DEBUG_SHARC_SKIP_UPDATE = 0x100, 0x200
+
+
+def check_sharc_settings(s):
+    """The range checks of pt_sharc_set_constants, on the float32 values the library receives: ValueError where it answers
+    PT_ERROR_INVALID_ARGUMENT."""
+    s = np.asarray(s).reshape(())
+    if not 1 <= int(s["DownscaleFactor"]) <= 4:
+        raise ValueError("DownscaleFactor must be 1..4")
+    if not 1 <= int(s["AccumulationFrames"]) <= 63:
+        raise ValueError("AccumulationFrames must be 1..63")
+    if not 1 <= int(s["MaxStaleFrames"]) <= 255:
+        raise ValueError("MaxStaleFrames must be 1..255")
+    if not 5.0 <= float(np.float32(s["SceneScale"])) <= 100.0:
+        raise ValueError("SceneScale must be in [5, 100]")
+    if not 0.0 <= float(np.float32(s["RoughnessThreshold"])) <= 1.0:
+        raise ValueError("RoughnessThreshold must be in [0, 1]")
+    if int(s["IsAntiFireflyEnabled"]) > 1:
+        raise ValueError("IsAntiFireflyEnabled must be 0 or 1")
+    if int(s["IsHashGridVisualizationEnabled"]) != 0:
+        raise ValueError("hash-grid visualisation is not served")
+    return s
+
+
+def sharc_settings(downscale=4, scene_scale=50.0, roughness_threshold=0.4, accumulation_frames=10, max_stale_frames=64,
+                   anti_firefly=True, visualization=False):
+    """PtSHARCSettings with the reference's defaults (Source/MyAppData.h:250-262, Source/SHARC.ixx): DownscaleFactor 4, SceneScale 50,
+    RoughnessThreshold 0.4, 10 accumulation frames, 64 stale frames, anti-firefly on (the reference passes true). Refuses what
+    pt_sharc_set_constants refuses."""
+    s = np.zeros((), SHARC_SETTINGS)
+    s["AccumulationFrames"] = accumulation_frames
+    s["MaxStaleFrames"] = max_stale_frames
+    s["SceneScale"] = scene_scale
+    s["IsAntiFireflyEnabled"] = 1 if anti_firefly else 0
+    s["DownscaleFactor"] = downscale
+    s["RoughnessThreshold"] = roughness_threshold
+    s["IsHashGridVisualizationEnabled"] = 1 if visualization else 0
+    return check_sharc_settings(s)
+
+
 GBUFFER_CONSTANTS = np.dtype({
     "names": ["RenderSize", "Flags"], "formats": [("<u4", 2), "<u4"], "offsets": [0, 8], "itemsize": 12})
 

@@ -29,6 +29,8 @@ EXPORTS = [
     "pt_di_set_resampling", "pt_di_render_with_history", "pt_di_reset_history", "pt_di_download_reservoirs",
     "pt_di_set_light_sampling", "pt_di_download_presampled",
     "pt_post_set_constants", "pt_post_render", "pt_post_download_bloom",
+    "pt_sharc_configure", "pt_sharc_set_constants", "pt_raytrace_render_sharc", "pt_sharc_reset", "pt_sharc_download",
+    "pt_sharc_debug_keys", "pt_sharc_debug_query", "pt_sharc_download_update_paths", "pt_sharc_download_update_scatter",
     "pt_set_debug_flags", "pt_debug_read_mismatch", "pt_debug_download_blob", "pt_debug_trace_ray", "pt_enable_kernel_timing", "pt_get_kernel_timing", "pt_get_round_timing",
 ]
 
@@ -179,6 +181,15 @@ def load_library():
         lib.pt_post_set_constants.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_post_render.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_post_download_bloom.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.pt_sharc_configure.argtypes = [C.c_void_p, C.c_uint32]
+        lib.pt_sharc_set_constants.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_raytrace_render_sharc.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_sharc_reset.argtypes = [C.c_void_p]
+        lib.pt_sharc_download.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.pt_sharc_debug_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pt_sharc_debug_query.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.pt_sharc_download_update_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.pt_sharc_download_update_scatter.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.pt_set_debug_flags.argtypes = [C.c_void_p, C.c_uint32]
         lib.pt_debug_read_mismatch.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_debug_download_blob.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -698,6 +709,82 @@ class PostProcessing:
         return out
 
 
+class SHARC:
+    """Mirror of `struct SHARC` (Source/SHARC.ixx) and of the Raytracing::Render overload that takes it: Configure allocates the context's
+    cache, SetConstants takes PtSHARCSettings (layouts.sharc_settings), Render runs clear, update, resolve, query and the swap with the
+    GraphicsSettings of raytracing.SetConstants. One cache per context, also for a context that views a shared scene."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self._settings = None
+
+    def Configure(self, capacity=0):
+        """capacity 0 = 1 << 22 entries; a multiple of 32. Empties the cache."""
+        self.ctx.check(self.ctx.lib.pt_sharc_configure(self.ctx.handle, capacity))
+
+    def SetConstants(self, settings):
+        self._settings = np.array(settings).reshape(())
+        self.ctx.check(self.ctx.lib.pt_sharc_set_constants(self.ctx.handle, C.c_void_p(self._settings.ctypes.data)))
+
+    def Render(self, raytracing, topLevelAccelerationStructure=None):
+        """raytracing: the Raytracing operator whose GPUBuffers / Textures the frame uses."""
+        ctx, lib = self.ctx, self.ctx.lib
+        cam = np.array(raytracing.GPUBuffers["Camera"]); sd = np.array(raytracing.GPUBuffers["SceneData"])
+        ctx.check(lib.pt_set_camera(ctx.handle, C.c_void_p(cam.ctypes.data)))
+        ctx.check(lib.pt_set_scene_data(ctx.handle, C.c_void_p(sd.ctypes.data)))
+        t = _pack_textures(raytracing.Textures)
+        ctx.check(lib.pt_raytrace_render_sharc(ctx.handle, C.addressof(t)))
+
+    def Reset(self):
+        self.ctx.check(self.ctx.lib.pt_sharc_reset(self.ctx.handle))
+
+    def download(self):
+        """The live entries of the resolved buffer (numpy layouts.SHARC_ENTRY). Synchronises."""
+        n = C.c_uint32(0)
+        self.ctx.check(self.ctx.lib.pt_sharc_download(self.ctx.handle, None, 0, C.byref(n)))
+        out = np.zeros(n.value, L.SHARC_ENTRY)
+        if n.value:
+            self.ctx.check(self.ctx.lib.pt_sharc_download(self.ctx.handle, C.c_void_p(out.ctypes.data), n.value, C.byref(n)))
+        return out
+
+    def debug_keys(self, positions, normals):
+        """(keys uint64, levels uint32, voxel sizes float32) of points with normals, under the context's camera and SceneScale."""
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3); nn = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        n = len(p)
+        keys, levels, sizes = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.float32)
+        self.ctx.check(self.ctx.lib.pt_sharc_debug_keys(self.ctx.handle, C.c_void_p(p.ctypes.data), C.c_void_p(nn.ctypes.data), n,
+                                                         C.c_void_p(keys.ctypes.data), C.c_void_p(levels.ctypes.data), C.c_void_p(sizes.ctypes.data)))
+        return keys, levels, sizes
+
+    def debug_query(self, positions, normals, distances, previous_roughness):
+        """The query decision against the resolved buffer (numpy layouts.SHARC_QUERY_RESULT)."""
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3); nn = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(distances, np.float32).reshape(-1); r = np.ascontiguousarray(previous_roughness, np.float32).reshape(-1)
+        out = np.zeros(len(p), L.SHARC_QUERY_RESULT)
+        self.ctx.check(self.ctx.lib.pt_sharc_debug_query(self.ctx.handle, C.c_void_p(p.ctypes.data), C.c_void_p(nn.ctypes.data), C.c_void_p(d.ctypes.data),
+                                                          C.c_void_p(r.ctypes.data), len(p), C.c_void_p(out.ctypes.data)))
+        return out
+
+    def download_update_paths(self):
+        """The vertex log of the last update pass rendered with DEBUG_SHARC_LOG_PATHS: (paths, bounces) of layouts.SHARC_PATH_VERTEX."""
+        n, b = C.c_uint32(0), C.c_uint32(0)
+        self.ctx.check(self.ctx.lib.pt_sharc_download_update_paths(self.ctx.handle, None, 0, C.byref(n), C.byref(b)))
+        out = np.zeros((n.value, b.value), L.SHARC_PATH_VERTEX)
+        if out.size:
+            self.ctx.check(self.ctx.lib.pt_sharc_download_update_paths(self.ctx.handle, C.c_void_p(out.ctypes.data), out.size, C.byref(n), C.byref(b)))
+        return out
+
+
+    def download_update_scatter(self):
+        """The BSDF steps of the same log: (paths, bounces) of layouts.SHARC_PATH_SCATTER."""
+        n, b = C.c_uint32(0), C.c_uint32(0)
+        self.ctx.check(self.ctx.lib.pt_sharc_download_update_scatter(self.ctx.handle, None, 0, C.byref(n), C.byref(b)))
+        out = np.zeros((n.value, b.value), L.SHARC_PATH_SCATTER)
+        if out.size:
+            self.ctx.check(self.ctx.lib.pt_sharc_download_update_scatter(self.ctx.handle, C.c_void_p(out.ctypes.data), out.size, C.byref(n), C.byref(b)))
+        return out
+
+
 class Renderer:
     """App::RenderScene for this path (Source/App.cpp:1157-1329): G-buffer pass, then the path tracer."""
 
@@ -714,6 +801,7 @@ class Renderer:
         self.raytracing = Raytracing(ctx)
         self.direct_lighting = DirectLighting(ctx)
         self.post = PostProcessing(ctx)
+        self.sharc = SHARC(ctx)
         d = scene_gpu.desc
         for op in (self.gbuffer, self.raytracing, self.direct_lighting):
             op.GPUBuffers["Camera"] = d.camera
@@ -723,7 +811,7 @@ class Renderer:
         self.constants["RenderSize"] = (width, height)
         self.constants["Flags"] = L.GBufferFlags.DefaultNoDenoiser        # App.cpp:1224 with Denoiser::None
 
-    def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None, post=None):
+    def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None, post=None, sharc=None):
         """di_samples > 0: run the DI pass with that many candidates per pixel; set settings["IsDIEnabled"] to have the path tracer
         consume it (the textures need Diffuse / Specular: with_denoiser_outputs=True). di_reuse: PtDIResamplingSettings
         (layouts.di_resampling_settings) for reservoir reuse; temporal reuse needs di_history=True. With di_history the current and
@@ -731,7 +819,8 @@ class Renderer:
         frame's G-buffer and the Previous* ones the last frame's. di_light_sampling: PtDILightSamplingSettings
         (layouts.di_light_sampling_settings), or None: the power CDF. post: PtPostProcessSettings (layouts.post_processing_settings) to run
         the post-processing chain on the frame's Radiance; it writes textures["Color"], ["BackBuffer"] and ["Display8"]. Unsharded
-        contexts only: a sharded host gathers Radiance and runs PostProcessing on the full frame."""
+        contexts only: a sharded host gathers Radiance and runs PostProcessing on the full frame. sharc: PtSHARCSettings
+        (layouts.sharc_settings) to render the frame through the radiance cache (self.sharc.Configure first); None: the plain path tracer."""
         tlas = self.scene.GetTopLevelAccelerationStructure()
         if post is not None:
             p = np.array(post).reshape(())
@@ -755,7 +844,11 @@ class Renderer:
             self.direct_lighting.Render(tlas)
         if int(np.array(settings).reshape(())["Bounces"]) > 0:            # App.cpp:1277
             self.raytracing.SetConstants(settings)
-            self.raytracing.Render(tlas)
+            if sharc is not None:                                         # the Render overload with RTXGITechnique::SHARC
+                self.sharc.SetConstants(sharc)
+                self.sharc.Render(self.raytracing, tlas)
+            else:
+                self.raytracing.Render(tlas)
         if post is not None:                                              # App.cpp:1506-1571, after Raytracing::Render
             if "Color" not in self.textures:
                 self.textures.update(alloc_post_textures(self.width, self.height, self.scene.device))

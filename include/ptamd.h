@@ -106,7 +106,7 @@ typedef struct PtGraphicsSettings {       /* Raytracing::GraphicsSettings, Sourc
     uint32_t Denoiser;                    /* PtDenoiser: selects which outputs Raytracing writes (Raytracing.hlsl:379-413) */
     uint32_t ExtFlags;                    /* reference: first padding word. PT_EXT_* build-side switches */
     uint32_t _pad;
-    uint32_t SHARC[8];                    /* out of scope, ignored */
+    uint32_t SHARC[8];                    /* ignored: the radiance cache has calls of its own (pt_sharc_*, below) */
 } PtGraphicsSettings;
 
 /* enum class Denoiser, Source/Denoiser.ixx:8. The denoisers themselves (NRD, DLSS-RR) are out of scope; these values only
@@ -533,6 +533,65 @@ int pt_post_render(PtContext* ctx, const PtPostTextures* textures);
 int pt_post_download_bloom(PtContext* ctx, uint32_t stage, uint16_t* host_rgba16f, uint64_t capacity_texels,
                            uint32_t* out_width, uint32_t* out_height);
 
+/* ------------------------------------------------------------------------------------------
+ * the SHARC radiance cache: the Raytracing::Render overload with RTXGITechnique::SHARC (Source/Raytracing.ixx:114-148, Source/SHARC.ixx,
+ * the SHARC_UPDATE / SHARC_QUERY permutations of Shaders/Raytracing.hlsl). A world-space hash grid of radiance: an update pass walks one
+ * path per DownscaleFactor^2 pixels and deposits what it finds, a resolve pass blends the frame into the history, and the query pass -- the
+ * plain estimator -- ends a sample at its first far-and-blurred-enough hit on a voxel that holds samples. The SDK's headers are not part of
+ * the reference tree: grid, map, voxel word, resolve and anti-firefly rules are this library's own ("Radiance cache";
+ * tests/sharcref.py restates them), unpinned. PtGraphicsSettings.SHARC stays ignored: the cache is switched on by these calls alone.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct PtSHARCSettings {            /* SHARC::Constants + Raytracing::SHARCSettings */
+    uint32_t AccumulationFrames;            /* default 10; 1..63 */
+    uint32_t MaxStaleFrames;                /* default 64; 1..255 (a voxel is dropped after max(this, 8) frames without a sample) */
+    float    SceneScale;                    /* default 50; [5, 100] */
+    uint32_t IsAntiFireflyEnabled;          /* the reference passes 1; 0 or 1 */
+    uint32_t DownscaleFactor;               /* 1..4, default 4: the update pass covers (W / f) x (H / f) pixels */
+    float    RoughnessThreshold;            /* default 0.4; [0, 1] */
+    uint32_t IsHashGridVisualizationEnabled;/* must be 0 */
+} PtSHARCSettings;                          /* 28 B */
+typedef struct PtSHARCEntry { uint64_t Key; uint32_t Voxel[4]; uint32_t _pad[2]; } PtSHARCEntry;   /* 32 B: a live entry: radiance sums x 1e3 | samples, frames << 18, stale << 24 */
+typedef struct PtSHARCQueryResult { uint32_t Valid; float Radiance[3]; } PtSHARCQueryResult;       /* 16 B */
+typedef struct PtSHARCPathVertex {          /* one bounce of one update path (pt_sharc_download_update_paths) */
+    float Position[3]; uint32_t Flags;      /* PT_SHARC_VERTEX_*; 0: the path never got here */
+    float Normal[3];   float Random;        /* the front flat normal | the random number of the hit update */
+    float Radiance[3]; uint32_t KeyLo;      /* the radiance term handed to the hit / miss update | the device's key of the vertex */
+    float Throughput[3]; uint32_t KeyHi;    /* the bounce's throughput handed to SetThroughput (when not ENDED) */
+} PtSHARCPathVertex;                        /* 64 B */
+typedef struct PtSHARCPathScatter {         /* the BSDF step of the same bounce (pt_sharc_download_update_scatter) */
+    PtBsdfSampleQuery Query;                /* what pt_bsdf_sample needs to repeat it: the material as BSDFSample::Initialize took it, Roughness
+                                               after the RoughnessThreshold floor, the frame, V, the four draws, ExtFlags */
+    float Origin[3]; uint32_t Sampled;      /* the origin of the ray that follows (GetSafeWorldRayOrigin) | 1: the step ran (0: the path ended before it) */
+    float L[3];      uint32_t Goes;         /* the sampled direction | 1: the path went on after the step */
+} PtSHARCPathScatter;                       /* 128 B */
+#define PT_SHARC_VERTEX_HIT       0x1u
+#define PT_SHARC_VERTEX_MISS      0x2u
+#define PT_SHARC_VERTEX_ENDED     0x4u      /* the path ended at this vertex: SetThroughput was not reached */
+#define PT_SHARC_VERTEX_RESAMPLED 0x8u      /* ... because the hit update took the voxel's history instead of going on */
+/* SHARC::Configure: allocates HashEntries (8 B), VoxelData and PreviousVoxelData (16 B each) per entry, context-owned, and empties them.
+ * capacity 0 = 1 << 22; it must be a multiple of 32 (the bucket). Synchronises when it replaces a cache. */
+int pt_sharc_configure(PtContext* ctx, uint32_t capacity);
+/* Out-of-range fields are refused (PT_ERROR_INVALID_ARGUMENT) and leave the previous settings active. */
+int pt_sharc_set_constants(PtContext* ctx, const PtSHARCSettings* settings);
+/* The Render overload: clear VoxelData, update, resolve, query (the frame, with pt_raytrace_set_constants' GraphicsSettings), swap.
+ * PT_ERROR_NOT_READY before pt_sharc_configure / pt_sharc_set_constants. Refuses a sharded context (the cache is world-space and global, a
+ * band holds only its own G-buffer rows), the NRD denoisers (None and DLSS-RR are served) and the PT_DEBUG_BRUTE_FORCE / _TRAVERSAL_V1
+ * traversals (they keep no hit distance). The cached and the plain frame have launch sequences of their own: a context that alternates
+ * pt_raytrace_render and pt_raytrace_render_sharc rebuilds its per-round argument blocks and its captured frame graph at every switch (one
+ * small upload, one stream synchronisation, one capture) -- meant for A/B comparison, not for a frame loop; give each form a context. */
+int pt_raytrace_render_sharc(PtContext* ctx, const PtTextures* textures);
+int pt_sharc_reset(PtContext* ctx);         /* empties the cache (App.cpp:682-685) */
+/* the live entries of the resolved buffer, in slot order; *out_count = how many there are. Synchronises. */
+int pt_sharc_download(PtContext* ctx, PtSHARCEntry* host_dst, uint32_t capacity, uint32_t* out_count);
+/* Test aids (host arrays; they synchronise). Keys: key, level and voxel size of n points (xyz) with normals, camera = the context's.
+ * Query: the query decision against the resolved buffer. Update paths: the vertex log of the last update pass rendered with
+ * PT_DEBUG_SHARC_LOG_PATHS, path-major, *out_bounces entries per path ((W / f) * (H / f) paths, row-major). */
+int pt_sharc_debug_keys(PtContext* ctx, const float* positions, const float* normals, uint32_t n, uint64_t* keys, uint32_t* levels, float* voxel_sizes);
+int pt_sharc_debug_query(PtContext* ctx, const float* positions, const float* normals, const float* distances, const float* previous_roughness,
+                         uint32_t n, PtSHARCQueryResult* results);
+int pt_sharc_download_update_paths(PtContext* ctx, PtSHARCPathVertex* host_dst, uint32_t capacity, uint32_t* out_paths, uint32_t* out_bounces);
+int pt_sharc_download_update_scatter(PtContext* ctx, PtSHARCPathScatter* host_dst, uint32_t capacity, uint32_t* out_paths, uint32_t* out_bounces);
+
 /* Measurement (no reference counterpart). Counters cover the work enqueued since the last reset;
  * reading them synchronises the stream. */
 typedef struct PtCounters {
@@ -556,6 +615,8 @@ int  pt_get_counters(PtContext* ctx, PtCounters* out);
 #define PT_DEBUG_BRUTE_FORCE     0x2u     /* bounce rays test every triangle of every instance (validates the LBVH) */
 #define PT_DEBUG_GATHER_SELF_EXCHANGE 0x80u /* pt_gather_bands with a world-size-1 communicator: the rank's own bands travel by ncclSend to itself + ncclRecv from
                                              itself (one pair per band, one group) into the full frame -- the grouped p2p path of a real gather on ONE GPU (tests, bench --rehearse-collective) */
+#define PT_DEBUG_SHARC_LOG_PATHS 0x100u   /* pt_raytrace_render_sharc keeps the update pass's vertex log (pt_sharc_download_update_paths) */
+#define PT_DEBUG_SHARC_SKIP_UPDATE 0x200u /* pt_raytrace_render_sharc skips the update and resolve passes: the query sees the cache as it is */
 int  pt_set_debug_flags(PtContext* ctx, uint32_t flags);
 /* first mismatching ray under PT_DEBUG_BRUTE_FORCE: o.xyz tmin d.xyz tmax | bvh inst slot t - | brute inst slot t - */
 int  pt_debug_read_mismatch(PtContext* ctx, float* out16);
