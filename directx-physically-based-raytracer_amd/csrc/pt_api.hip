@@ -11,17 +11,15 @@ using namespace pt;
 static thread_local std::string g_createError;
 namespace pt { std::string& create_error() { return g_createError; } }
 
-static int fail(Context* c, int status, const std::string& msg)
+int pt::fail(Context* c, int status, const std::string& msg)
 {
     if (c) c->lastError = msg; else g_createError = msg;
     return status;
 }
-static int fail_hip(Context* c, hipError_t e, const char* what)
+int pt::fail_hip(Context* c, hipError_t e, const char* what)
 {
     return fail(c, e == hipErrorOutOfMemory ? PT_ERROR_OUT_OF_MEMORY : PT_ERROR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
-#define API_HIP(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail_hip(ctx, e_, #expr); } while (0)
-#define API_ARG(ctx, cond, msg) do { if (!(cond)) return fail(ctx, PT_ERROR_INVALID_ARGUMENT, msg); } while (0)
 
 static int poll_tlas_header(Context& c, bool wait);
 
@@ -665,6 +663,8 @@ int pt_deinterleave_bands(PtContext* ctx, void* dst_full, const void* gathered, 
     return PT_OK;
 }
 
+} // extern "C"
+
 // ---- operators ------------------------------------------------------------------------------
 // Scene inputs the kernels will index with: checked once per change of (TLAS, ObjectData binding, heap), never per frame.
 // The reference gets these guarantees from D3D12's descriptor heap; here a wrong index would be a wild device read.
@@ -707,7 +707,7 @@ static int validate_scene(Context& c)
     return PT_OK;
 }
 
-static int make_views(Context& c, uint32_t width, uint32_t height, SceneView& sv, FrameView& fv, bool needFrameInputs = true)
+int pt::make_views(Context& c, uint32_t width, uint32_t height, SceneView& sv, FrameView& fv, bool needFrameInputs)
 {
     // A top level whose build has not reported back yet is never rendered: its depth / error word decides whether the traversal stack can
     // walk it at all. One wait per BUILD (for the build's own kernels, ~0.3 ms of stream work that the frame needs anyway), none per frame
@@ -738,6 +738,20 @@ static int make_views(Context& c, uint32_t width, uint32_t height, SceneView& sv
     return PT_OK;
 }
 
+// (the SHARC entry point has narrowed Denoiser to None / DLSS-RR before it comes here: the two Denoiser checks cannot fire for it)
+int pt::check_raytrace_args(Context& c, const PtTextures* tx)
+{
+    API_ARG(&c, c.settings.Denoiser <= PT_DENOISER_NRD_RELAX, "unknown Denoiser value");
+    API_ARG(&c, !c.settings.IsDIEnabled || (tx->Diffuse && tx->Specular), "IsDIEnabled reads the direct lighting from Textures.Diffuse / Textures.Specular (pt_di_render): not bound");
+    API_ARG(&c, !(c.settings.Denoiser >= PT_DENOISER_NRD_REBLUR) || (tx->Diffuse && tx->Specular), "NRD modes write Textures.Diffuse / Textures.Specular: not bound");
+    API_ARG(&c, c.settings.SamplesPerPixel < 65536 && c.settings.Bounces < 32768, "SamplesPerPixel / Bounces out of range");
+    API_ARG(&c, tx->Position && tx->FlatNormal && tx->GeometricNormal && tx->BaseColorMetalness && tx->NormalRoughness && tx->IOR
+                 && tx->Transmission && tx->Radiance, "a G-buffer texture the path tracer reads is not bound (Raytracing::Textures)");
+    return PT_OK;
+}
+
+extern "C" {
+
 int pt_gbuffer_render(PtContext* ctx, const PtGBufferConstants* constants, const PtTextures* textures)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
@@ -765,18 +779,14 @@ int pt_raytrace_render(PtContext* ctx, const PtTextures* tx)
     Context& c = ctx->c;
     API_ARG(&c, tx, "textures is NULL");
     if (!c.haveSettings) return fail(&c, PT_ERROR_NOT_READY, "call pt_raytrace_set_constants first");
-    API_ARG(&c, c.settings.Denoiser <= PT_DENOISER_NRD_RELAX, "unknown Denoiser value");
-    API_ARG(&c, !c.settings.IsDIEnabled || (tx->Diffuse && tx->Specular), "IsDIEnabled reads the direct lighting from Textures.Diffuse / Textures.Specular (pt_di_render): not bound");
-    API_ARG(&c, !(c.settings.Denoiser >= PT_DENOISER_NRD_REBLUR) || (tx->Diffuse && tx->Specular), "NRD modes write Textures.Diffuse / Textures.Specular: not bound");
-    API_ARG(&c, c.settings.SamplesPerPixel < 65536 && c.settings.Bounces < 32768, "SamplesPerPixel / Bounces out of range");
-    API_ARG(&c, tx->Position && tx->FlatNormal && tx->GeometricNormal && tx->BaseColorMetalness && tx->NormalRoughness && tx->IOR
-                 && tx->Transmission && tx->Radiance, "a G-buffer texture the path tracer reads is not bound (Raytracing::Textures)");
+    int s = check_raytrace_args(c, tx);
+    if (s != PT_OK) return s;
     API_HIP(&c, hipSetDevice(c.device));
     SceneView sv; FrameView fv; memset(&sv, 0, sizeof sv); memset(&fv, 0, sizeof fv);
-    int s = make_views(c, c.settings.RenderSize[0], c.settings.RenderSize[1], sv, fv);
+    s = make_views(c, c.settings.RenderSize[0], c.settings.RenderSize[1], sv, fv);
     if (s != PT_OK) return s;
     if (c.settings.Bounces == 0) return PT_OK;          // reference: the pass is not dispatched, Source/App.cpp:1277-1279
-    API_HIP(&c, launch_raytrace(c, sv, fv, *tx));
+    API_HIP(&c, launch_raytrace(c, sv, fv, *tx, false));
     return PT_OK;
 }
 
@@ -936,6 +946,3 @@ int pt_get_round_timing(PtContext* ctx, float* round_ms, uint32_t* round_launche
 }
 
 } // extern "C"
-
-// the view set-up of the render operators, for the DI pass (pt_di.hip)
-namespace pt { int di_views(Context& c, uint32_t width, uint32_t height, SceneView& sv, FrameView& fv, bool needFrameInputs) { return make_views(c, width, height, sv, fv, needFrameInputs); } }

@@ -51,8 +51,6 @@ void load_rccl()
     #undef PT_SYM
 }
 
-int fail(Context* c, int status, const std::string& msg) { if (c) c->lastError = msg; else create_error() = msg; return status; }
-
 const Rccl* rccl(Context* c, int& status)
 {
     std::call_once(g_rcclOnce, load_rccl);

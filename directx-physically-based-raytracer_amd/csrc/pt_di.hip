@@ -737,28 +737,20 @@ hipError_t ensure_light_list(Context& c, const SceneView& sv)
 
 using namespace pt;
 
-static int di_fail(Context& c, int status, const std::string& msg) { c.lastError = msg; return status; }
-static int di_fail_hip(Context& c, hipError_t e, const char* what)
-{
-    return di_fail(c, e == hipErrorOutOfMemory ? PT_ERROR_OUT_OF_MEMORY : PT_ERROR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-#define DI_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return di_fail_hip(c, e_, #expr); } while (0)
-#define DI_ARG(cond, msg) do { if (!(cond)) return di_fail(c, PT_ERROR_INVALID_ARGUMENT, msg); } while (0)
-
 // ---- pt_di_render_with_history, in stages ----------------------------------------------------------------------------------
 // the arguments, checked in this order
 static int di_check_args(Context& c, const PtTextures* tx, const PtDIPreviousTextures* prev)
 {
-    DI_ARG(tx, "textures is NULL");
-    if (!c.haveDISettings) return di_fail(c, PT_ERROR_NOT_READY, "call pt_di_set_constants first");
+    API_ARG(&c, tx, "textures is NULL");
+    if (!c.haveDISettings) return fail(&c, PT_ERROR_NOT_READY, "call pt_di_set_constants first");
     const PtDISettings& s = c.diSettings;
-    DI_ARG(tx->LinearDepth && tx->GeometricNormal && tx->NormalRoughness && tx->BaseColorMetalness && tx->IOR && tx->Transmission,
+    API_ARG(&c, tx->LinearDepth && tx->GeometricNormal && tx->NormalRoughness && tx->BaseColorMetalness && tx->IOR && tx->Transmission,
            "a G-buffer texture the DI pass reads is not bound (LinearDepth, GeometricNormal, NormalRoughness, BaseColorMetalness, IOR, Transmission)");
     const bool toRadiance = s.IsLastRenderPass && s.Denoiser <= PT_DENOISER_DLSS_RAY_RECONSTRUCTION;
-    DI_ARG(toRadiance ? tx->Radiance != nullptr : (tx->Diffuse && tx->Specular),
+    API_ARG(&c, toRadiance ? tx->Radiance != nullptr : (tx->Diffuse && tx->Specular),
            toRadiance ? "IsLastRenderPass with Denoiser None / DLSS-RR adds to Textures.Radiance: not bound" : "the DI pass writes Textures.Diffuse / Textures.Specular: not bound");
     if (c.diReuseOn && c.diReuse.TemporalResampling)
-        DI_ARG(prev && prev->PreviousGeometricNormal && prev->PreviousLinearDepth && prev->PreviousBaseColorMetalness && prev->PreviousNormalRoughness &&
+        API_ARG(&c, prev && prev->PreviousGeometricNormal && prev->PreviousLinearDepth && prev->PreviousBaseColorMetalness && prev->PreviousNormalRoughness &&
                prev->PreviousIOR && prev->PreviousTransmission && tx->MotionVector,
                "temporal resampling reads Textures.MotionVector and the six Previous* textures: not bound");
     return PT_OK;
@@ -768,11 +760,11 @@ static int di_check_args(Context& c, const PtTextures* tx, const PtDIPreviousTex
 static int di_light_records(Context& c, const SceneView& sv, uint32_t n, uint32_t nb)
 {
     if (n > c.lightRecords.capacity()) {
-        DI_HIP(hipStreamSynchronize(c.stream));
+        API_HIP(&c, hipStreamSynchronize(c.stream));
         c.lightRecords.reset(); c.lightCdf.reset(); c.lightBlockSums.reset();
-        DI_HIP(c.lightCdf.reserve((size_t)n * 2u));                  // cdf | powers
-        DI_HIP(c.lightBlockSums.reserve(nb + 1u));
-        DI_HIP(c.lightRecords.reserve(n));   // last: the grow decision reads its capacity
+        API_HIP(&c, c.lightCdf.reserve((size_t)n * 2u));                  // cdf | powers
+        API_HIP(&c, c.lightBlockSums.reserve(nb + 1u));
+        API_HIP(&c, c.lightRecords.reserve(n));   // last: the grow decision reads its capacity
     }
     float* power = c.lightCdf.data() + c.lightRecords.capacity();
     k_light_records<<<(n + 255u) / 256u, 256, 0, c.stream>>>(c.lightList.data(), n, c.scene.instSource, sv.objects, sv.heap, sv.shadeTex, sv.srgbLut, (float4*)c.lightRecords.data(), power);
@@ -792,13 +784,13 @@ static int di_presample(Context& c, uint32_t n, uint32_t nb, DISampling& ls)
     if (lss.Mode != PT_DI_LOCAL_LIGHT_POWER_RIS && lss.Mode != PT_DI_LOCAL_LIGHT_REGIR_RIS) return PT_OK;
     const bool regir = lss.Mode == PT_DI_LOCAL_LIGHT_REGIR_RIS;
     if (c.diTiles.capacity() < kDITileEntries || (regir && c.diCells.capacity() < kDICellEntries)) {
-        DI_HIP(hipStreamSynchronize(c.stream));
-        DI_HIP(c.diTiles.reserve(kDITileEntries));
-        if (regir) DI_HIP(c.diCells.reserve(kDICellEntries));    // 16 MB, only in ReGIR mode
+        API_HIP(&c, hipStreamSynchronize(c.stream));
+        API_HIP(&c, c.diTiles.reserve(kDITileEntries));
+        if (regir) API_HIP(&c, c.diCells.reserve(kDICellEntries));    // 16 MB, only in ReGIR mode
     }
     k_di_presample_tiles<<<kDITileEntries / 256u, 256, 0, c.stream>>>((const float4*)c.lightRecords.data(), c.lightCdf.data(), c.lightBlockSums.data() + nb, n,
                                                                      c.diSettings.FrameIndex, (uint2*)c.diTiles.data());
-    DI_HIP(hipGetLastError());
+    API_HIP(&c, hipGetLastError());
     c.diTileCount = kDITileEntries;
     ls.tiles = (const uint2*)c.diTiles.data();
     if (regir) {
@@ -806,7 +798,7 @@ static int di_presample(Context& c, uint32_t n, uint32_t nb, DISampling& ls)
         ls.cellSize = lss.ReGIRCellSize;
         k_di_regir_build<<<kDICellEntries / 256u, 256, 0, c.stream>>>((const float4*)c.lightRecords.data(), n, ls.tiles, ls.centre[0], ls.centre[1], ls.centre[2],
                                                                       ls.cellSize, lss.ReGIRBuildSamples, c.diSettings.FrameIndex, (uint2*)c.diCells.data());
-        DI_HIP(hipGetLastError());
+        API_HIP(&c, hipGetLastError());
         c.diCellCount = kDICellEntries;
         ls.cells = (const uint2*)c.diCells.data();
     }
@@ -836,18 +828,18 @@ static int di_launch_reuse(Context& c, const DIArgs& a, const DISampling& ls, co
     const FrameView& fv = a.fv;
     const size_t npix = (size_t)fv.width * fv.localRows;
     if (npix > c.diResB.capacity() || !c.diOffsets) {
-        DI_HIP(hipStreamSynchronize(c.stream));
+        API_HIP(&c, hipStreamSynchronize(c.stream));
         if (npix > c.diResB.capacity()) {
             c.diResA.reset(); c.diResB.reset(); c.diHistoryValid = false;
-            DI_HIP(c.diResA.reserve(npix));
-            DI_HIP(c.diResB.reserve(npix));                          // last: the grow decision reads its capacity
+            API_HIP(&c, c.diResA.reserve(npix));
+            API_HIP(&c, c.diResB.reserve(npix));                          // last: the grow decision reads its capacity
         }
         if (!c.diOffsets) {
             int8_t host[2 * kDIOffsetCount];
             build_di_offsets(host);
             DeviceBuffer<int8_t> dev;
-            DI_HIP(dev.reserve(sizeof host));
-            DI_HIP(hipMemcpy(dev.data(), host, sizeof host, hipMemcpyHostToDevice));
+            API_HIP(&c, dev.reserve(sizeof host));
+            API_HIP(&c, hipMemcpy(dev.data(), host, sizeof host, hipMemcpyHostToDevice));
             c.diOffsets = std::move(dev);
         }
     }
@@ -872,18 +864,16 @@ static int di_launch_reuse(Context& c, const DIArgs& a, const DISampling& ls, co
         else if (tb) k_di_initial_temporal<true, true, S><<<grid, 256, 0, c.stream>>>(r, source);
         else k_di_initial_temporal<true, false, S><<<grid, 256, 0, c.stream>>>(r, source);
     });
-    DI_HIP(hipGetLastError());
+    API_HIP(&c, hipGetLastError());
     r.in = c.diResA.data(); r.out = c.diResB.data();
     if (!spatial) k_di_spatial_shade<false, false><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data());
     else if (sb) k_di_spatial_shade<true, true><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data());
     else k_di_spatial_shade<true, false><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data());
-    DI_HIP(hipGetLastError());
+    API_HIP(&c, hipGetLastError());
     c.diHistoryValid = true; c.diHistorySize[0] = fv.width; c.diHistorySize[1] = fv.height; c.diHistoryLightKey = c.lightListKey;
     c.diResCount = (uint32_t)npix;
     return PT_OK;
 }
-
-namespace pt { int di_views(Context& c, uint32_t width, uint32_t height, SceneView& sv, FrameView& fv, bool needFrameInputs); }   // pt_api.hip make_views
 
 extern "C" {
 
@@ -891,9 +881,9 @@ int pt_di_set_constants(PtContext* ctx, const PtDISettings* s)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
-    DI_ARG(s, "settings is NULL");
-    DI_ARG(s->LocalLightSamples >= 1 && s->LocalLightSamples <= 32, "LocalLightSamples must be 1..32");
-    DI_ARG(s->Denoiser <= PT_DENOISER_NRD_RELAX, "unknown Denoiser value");
+    API_ARG(&c, s, "settings is NULL");
+    API_ARG(&c, s->LocalLightSamples >= 1 && s->LocalLightSamples <= 32, "LocalLightSamples must be 1..32");
+    API_ARG(&c, s->Denoiser <= PT_DENOISER_NRD_RELAX, "unknown Denoiser value");
     c.diSettings = *s; c.haveDISettings = true;
     return PT_OK;
 }
@@ -906,14 +896,14 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
     if (st != PT_OK) return st;
     const PtDISettings& s = c.diSettings;
     const bool reuse = c.diReuseOn;
-    DI_HIP(hipSetDevice(c.device));
+    API_HIP(&c, hipSetDevice(c.device));
     SceneView sv; FrameView fv; memset(&sv, 0, sizeof sv); memset(&fv, 0, sizeof fv);
-    if ((st = di_views(c, s.RenderSize[0], s.RenderSize[1], sv, fv, true)) != PT_OK) return st;
-    DI_ARG(!reuse || fv.rankCount == 1, "reservoir reuse needs an unsharded context (RankCount 1)");
+    if ((st = make_views(c, s.RenderSize[0], s.RenderSize[1], sv, fv, true)) != PT_OK) return st;
+    API_ARG(&c, !reuse || fv.rankCount == 1, "reservoir reuse needs an unsharded context (RankCount 1)");
     const size_t npix = (size_t)fv.width * fv.localRows;
-    if (tx->Diffuse) DI_HIP(hipMemsetAsync(tx->Diffuse, 0, npix * 8u, c.stream));                // App.cpp:1238-1239
-    if (tx->Specular) DI_HIP(hipMemsetAsync(tx->Specular, 0, npix * 8u, c.stream));
-    DI_HIP(ensure_light_list(c, sv));
+    if (tx->Diffuse) API_HIP(&c, hipMemsetAsync(tx->Diffuse, 0, npix * 8u, c.stream));                // App.cpp:1238-1239
+    if (tx->Specular) API_HIP(&c, hipMemsetAsync(tx->Specular, 0, npix * 8u, c.stream));
+    API_HIP(&c, ensure_light_list(c, sv));
     const uint32_t n = c.lightCount;
     c.lightRecordCount = n;
     c.diTileCount = 0; c.diCellCount = 0;
@@ -930,11 +920,11 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
     memcpy(a.jitter, c.camera.Jitter, sizeof a.jitter);
     a.lights = (const float4*)c.lightRecords.data(); a.cdf = c.lightCdf.data(); a.total = c.lightBlockSums.data() + nb; a.count = n;
     a.frameIndex = s.FrameIndex; a.samples = s.LocalLightSamples; a.denoiser = s.Denoiser; a.lastPass = s.IsLastRenderPass; a.ext = s.ExtFlags;
-    AlphaContext ac; ac.objects = sv.objects; ac.heap = sv.heap; ac.srgbLut = sv.srgbLut; ac.instances = sv.accel.instances; ac.shadeTex = sv.shadeTex;
+    const AlphaContext ac = alpha_context(sv);
     const dim3 grid((fv.width + 15u) / 16u, (fv.localRows + 15u) / 16u);
     if (reuse) return di_launch_reuse(c, a, ls, prev, grid, ac);
     di_with_source(ls, [&](auto source) { k_di<decltype(source)><<<grid, 256, 0, c.stream>>>(a, source, c.scene.blob, ac, c.counters.data()); });   // the plain pass
-    DI_HIP(hipGetLastError());
+    API_HIP(&c, hipGetLastError());
     return PT_OK;
 }
 
@@ -946,18 +936,18 @@ int pt_di_set_resampling(PtContext* ctx, const PtDIResamplingSettings* s)
     Context& c = ctx->c;
     PtDIResamplingSettings v; memset(&v, 0, sizeof v);
     if (s) {
-        DI_ARG(s->TemporalResampling <= 1u && s->BoilingFilter <= 1u, "TemporalResampling / BoilingFilter must be 0 or 1");
-        DI_ARG(s->TemporalBiasCorrection != 2u && s->TemporalBiasCorrection != 3u && s->SpatialBiasCorrection != 2u && s->SpatialBiasCorrection != 3u,
+        API_ARG(&c, s->TemporalResampling <= 1u && s->BoilingFilter <= 1u, "TemporalResampling / BoilingFilter must be 0 or 1");
+        API_ARG(&c, s->TemporalBiasCorrection != 2u && s->TemporalBiasCorrection != 3u && s->SpatialBiasCorrection != 2u && s->SpatialBiasCorrection != 3u,
                "Pairwise and Raytraced bias correction are not supported (use PT_DI_BIAS_CORRECTION_OFF or _BASIC)");
-        DI_ARG(s->TemporalBiasCorrection <= 1u && s->SpatialBiasCorrection <= 1u, "unknown bias-correction mode");
-        DI_ARG(s->MaxHistoryLength >= 1u && s->MaxHistoryLength <= 64u, "MaxHistoryLength must be 1..64");
-        DI_ARG(s->BoilingFilterStrength >= 0.0f && s->BoilingFilterStrength <= 1.0f, "BoilingFilterStrength must be in [0, 1]");
-        DI_ARG(s->SpatialSamples <= 32u, "SpatialSamples must be 0..32");
-        DI_ARG(s->DisocclusionBoostSamples <= 32u, "DisocclusionBoostSamples must be 0..32");
-        DI_ARG(s->SpatialSamplingRadius > 0.0f && s->SpatialSamplingRadius <= 64.0f, "SpatialSamplingRadius must be in (0, 64]");
-        DI_ARG(s->TemporalDepthThreshold >= 0.0f && s->SpatialDepthThreshold >= 0.0f && std::isfinite(s->TemporalDepthThreshold) && std::isfinite(s->SpatialDepthThreshold),
+        API_ARG(&c, s->TemporalBiasCorrection <= 1u && s->SpatialBiasCorrection <= 1u, "unknown bias-correction mode");
+        API_ARG(&c, s->MaxHistoryLength >= 1u && s->MaxHistoryLength <= 64u, "MaxHistoryLength must be 1..64");
+        API_ARG(&c, s->BoilingFilterStrength >= 0.0f && s->BoilingFilterStrength <= 1.0f, "BoilingFilterStrength must be in [0, 1]");
+        API_ARG(&c, s->SpatialSamples <= 32u, "SpatialSamples must be 0..32");
+        API_ARG(&c, s->DisocclusionBoostSamples <= 32u, "DisocclusionBoostSamples must be 0..32");
+        API_ARG(&c, s->SpatialSamplingRadius > 0.0f && s->SpatialSamplingRadius <= 64.0f, "SpatialSamplingRadius must be in (0, 64]");
+        API_ARG(&c, s->TemporalDepthThreshold >= 0.0f && s->SpatialDepthThreshold >= 0.0f && std::isfinite(s->TemporalDepthThreshold) && std::isfinite(s->SpatialDepthThreshold),
                "depth thresholds must be finite and >= 0");
-        DI_ARG(s->TemporalNormalThreshold >= -1.0f && s->TemporalNormalThreshold <= 1.0f && s->SpatialNormalThreshold >= -1.0f && s->SpatialNormalThreshold <= 1.0f,
+        API_ARG(&c, s->TemporalNormalThreshold >= -1.0f && s->TemporalNormalThreshold <= 1.0f && s->SpatialNormalThreshold >= -1.0f && s->SpatialNormalThreshold <= 1.0f,
                "normal thresholds must be in [-1, 1]");
         v = *s;
         memset(v._pad, 0, sizeof v._pad);
@@ -974,9 +964,9 @@ int pt_di_set_light_sampling(PtContext* ctx, const PtDILightSamplingSettings* s)
     Context& c = ctx->c;
     PtDILightSamplingSettings v; memset(&v, 0, sizeof v);
     if (s) {
-        DI_ARG(s->Mode <= PT_DI_LOCAL_LIGHT_REGIR_RIS, "unknown local-light sampling Mode");
-        DI_ARG(std::isfinite(s->ReGIRCellSize) && s->ReGIRCellSize >= 0.1f && s->ReGIRCellSize <= 10.0f, "ReGIRCellSize must be finite and in [0.1, 10]");
-        DI_ARG(s->ReGIRBuildSamples >= 1u && s->ReGIRBuildSamples <= 32u, "ReGIRBuildSamples must be 1..32");
+        API_ARG(&c, s->Mode <= PT_DI_LOCAL_LIGHT_REGIR_RIS, "unknown local-light sampling Mode");
+        API_ARG(&c, std::isfinite(s->ReGIRCellSize) && s->ReGIRCellSize >= 0.1f && s->ReGIRCellSize <= 10.0f, "ReGIRCellSize must be finite and in [0.1, 10]");
+        API_ARG(&c, s->ReGIRBuildSamples >= 1u && s->ReGIRBuildSamples <= 32u, "ReGIRBuildSamples must be 1..32");
         v = *s;
         v._pad = 0;
     }
@@ -989,15 +979,9 @@ int pt_di_download_presampled(PtContext* ctx, uint32_t which, PtDIPresampledLigh
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
-    DI_ARG(out_count && (host_dst || capacity == 0), "out_count / host_dst is NULL");
-    DI_ARG(which <= 1u, "which must be 0 (Power_RIS tiles) or 1 (ReGIR cells)");
-    DI_HIP(hipSetDevice(c.device));
-    DI_HIP(hipStreamSynchronize(c.stream));
-    const uint32_t n = which ? c.diCellCount : c.diTileCount;
-    *out_count = n;
-    const uint32_t k = std::min(capacity, n);
-    if (k) DI_HIP(hipMemcpy(host_dst, which ? c.diCells.data() : c.diTiles.data(), sizeof(PtDIPresampledLight) * (size_t)k, hipMemcpyDeviceToHost));
-    return PT_OK;
+    API_ARG(&c, out_count && (host_dst || capacity == 0), "out_count / host_dst is NULL");
+    API_ARG(&c, which <= 1u, "which must be 0 (Power_RIS tiles) or 1 (ReGIR cells)");
+    return download_counted(c, which ? c.diCells.data() : c.diTiles.data(), which ? c.diCellCount : c.diTileCount, 1u, host_dst, capacity, out_count);
 }
 
 int pt_di_reset_history(PtContext* ctx)
@@ -1011,13 +995,8 @@ int pt_di_download_reservoirs(PtContext* ctx, PtDIReservoir* host_dst, uint32_t 
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
-    DI_ARG(out_count && (host_dst || capacity == 0), "out_count / host_dst is NULL");
-    DI_HIP(hipSetDevice(c.device));
-    DI_HIP(hipStreamSynchronize(c.stream));
-    *out_count = c.diResCount;
-    const uint32_t k = std::min(capacity, c.diResCount);
-    if (k) DI_HIP(hipMemcpy(host_dst, c.diResB.data(), sizeof(PtDIReservoir) * (size_t)k, hipMemcpyDeviceToHost));
-    return PT_OK;
+    API_ARG(&c, out_count && (host_dst || capacity == 0), "out_count / host_dst is NULL");
+    return download_counted(c, c.diResB.data(), c.diResCount, 1u, host_dst, capacity, out_count);
 }
 
 
@@ -1025,12 +1004,12 @@ int pt_di_light_count(PtContext* ctx, uint32_t* out_count)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
-    DI_ARG(out_count, "out_count is NULL");
-    DI_HIP(hipSetDevice(c.device));
+    API_ARG(&c, out_count, "out_count is NULL");
+    API_HIP(&c, hipSetDevice(c.device));
     SceneView sv; FrameView fv; memset(&sv, 0, sizeof sv); memset(&fv, 0, sizeof fv);
-    int st = di_views(c, 1, 1, sv, fv, false);
+    int st = make_views(c, 1, 1, sv, fv, false);
     if (st != PT_OK) return st;
-    DI_HIP(ensure_light_list(c, sv));
+    API_HIP(&c, ensure_light_list(c, sv));
     *out_count = c.lightCount;
     return PT_OK;
 }
@@ -1039,13 +1018,8 @@ int pt_di_download_lights(PtContext* ctx, PtTriangleLight* host_dst, uint32_t ca
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
-    DI_ARG(out_count && (host_dst || capacity == 0), "out_count / host_dst is NULL");
-    DI_HIP(hipSetDevice(c.device));
-    DI_HIP(hipStreamSynchronize(c.stream));
-    *out_count = c.lightRecordCount;
-    const uint32_t k = std::min(capacity, c.lightRecordCount);
-    if (k) DI_HIP(hipMemcpy(host_dst, c.lightRecords.data(), sizeof(PtTriangleLight) * (size_t)k, hipMemcpyDeviceToHost));
-    return PT_OK;
+    API_ARG(&c, out_count && (host_dst || capacity == 0), "out_count / host_dst is NULL");
+    return download_counted(c, c.lightRecords.data(), c.lightRecordCount, 1u, host_dst, capacity, out_count);
 }
 
 } // extern "C"

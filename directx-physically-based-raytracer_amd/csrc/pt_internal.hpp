@@ -2,8 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ptamd.h"
@@ -108,7 +110,7 @@ struct PathQueue {
 };
 
 // Queue geometry (pt_kernels.hip "wavefront path tracer"): the path queue is cut into independent sub-queues
-// How many: a power of two chosen per frame by the form that renders it (Context::sqShift = its log2). The fused round kernel likes 32 (C2: 64 -0.4 %,
+// How many: a power of two chosen per frame by the form that renders it (FramePlan::sqShift = its log2). The fused round kernel likes 32 (C2: 64 -0.4 %,
 // 128 -0.9 %), the streaming form 128 (C5 +3 %, C3 +0.5 % over 32; 256 the same, 512 less): a sub-queue is then shared by 16 waves instead of 64,
 // cursors are less contended and run dry at a finer grain. Per round the counters are: entries traced | fresh | cursor of the streaming form,
 // one word per sub-queue each (3 << sqShift words).
@@ -151,7 +153,6 @@ struct Context {
     uint32_t tlasValidatedCount = ~0u, persistentGrid = 0;
     uint64_t tlasBindingHash = 0;                     // over (InstanceID, bottom-level id) of the instances, in order: what the shared-geometry check depends on
     uint64_t tlasObjectEnd = 0;                       // max over instances of InstanceID + geometry count: ObjectData must reach that far
-    uint32_t sqShift = kSubQueueShiftFused;   // log2 of the number of sub-queues of the frame being enqueued (launch_raytrace)
     DeviceBuffer<ShadeGeom> shadeGeomDev;             // per object
     DeviceBuffer<HeapEntry> shadeTexDev;              // 7 resolved texture slots per object
     // per-frame copy of the vertex normals, one record per triangle packet of the traversal copy (pt_shade.hpp ShadeTables)
@@ -224,12 +225,43 @@ struct Context {
     DeviceBuffer<uint4> sharcVoxels[2];
     DeviceBuffer<SharcView> sharcView;                // what the query kernels read, rewritten per render in stream order
     DeviceBuffer<float> sharcRough[2];                // previousRoughness of the two path queues' entries (allocated by the first SHARC render)
-    bool sharcQuery = false;                          // set around launch_raytrace by pt_raytrace_render_sharc: the SHARC instantiations
     DeviceBuffer<PtSHARCPathScatter> sharcLogScatter;
     DeviceBuffer<PtSHARCPathVertex> sharcLog; uint32_t sharcLogPaths = 0, sharcLogBounces = 0;   // PT_DEBUG_SHARC_LOG_PATHS: the last update pass's vertices
 };
 
-std::string& create_error();             // pt_api.hip: the message pt_last_error(NULL) returns (errors of the context-free entry points)
+// ---- API plumbing shared by the files of the C ABI (defined in pt_api.hip) ------------------------------------------------------------
+std::string& create_error();             // the message pt_last_error(NULL) returns (errors of the context-free entry points)
+int fail(Context* c, int status, const std::string& msg);       // records msg in the context (null: in create_error()) and returns status
+int fail_hip(Context* c, hipError_t e, const char* what);
+#define API_HIP(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return pt::fail_hip(ctx, e_, #expr); } while (0)
+#define API_ARG(ctx, cond, msg) do { if (!(cond)) return pt::fail(ctx, PT_ERROR_INVALID_ARGUMENT, msg); } while (0)
+// the view set-up of every render operator: waits for the top-level build's verdict, uploads the heap, validates the scene inputs
+int make_views(Context& c, uint32_t width, uint32_t height, SceneView& sv, FrameView& fv, bool needFrameInputs = true);
+// what pt_raytrace_render and pt_raytrace_render_sharc check alike, behind their own checks: settings ranges and texture bindings
+int check_raytrace_args(Context& c, const PtTextures* tx);
+
+// The tail of a counted download (pt_*_download_*): the counts of what the last render left go out -- `count` rows of `row` records -- then
+// min(capacity, count * row) records. Synchronises.
+template <typename T>
+int download_counted(Context& c, const T* src, uint32_t count, uint32_t row, T* host_dst, uint32_t capacity, uint32_t* out_count, uint32_t* out_row = nullptr)
+{
+    API_HIP(&c, hipSetDevice(c.device));
+    API_HIP(&c, hipStreamSynchronize(c.stream));
+    *out_count = count;
+    if (out_row) *out_row = row;
+    const size_t n = std::min((size_t)capacity, (size_t)count * row);
+    if (n) API_HIP(&c, hipMemcpy(host_dst, src, sizeof(T) * n, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// Run-time flags -> template arguments: with_flags(f, a, b, ...) calls the generic lambda f with one std::bool_constant per flag, so a
+// kernel launch is written once and instantiated for every combination of its switches.
+template <typename F> void with_flags(F&& f) { f(); }
+template <typename F, typename... Rest> void with_flags(F&& f, bool first, Rest... rest)
+{
+    if (first) with_flags([&](auto... bs) { f(std::true_type{}, bs...); }, rest...);
+    else with_flags([&](auto... bs) { f(std::false_type{}, bs...); }, rest...);
+}
 
 // pt_bvh.hip
 hipError_t build_blas_device(const PtGeometryDesc* geoms, uint32_t ngeoms, bool allowUpdate, hipStream_t stream, Blas& out);
@@ -244,15 +276,29 @@ __host__ __device__ void invert_3x4(const float m[12], float out[12]);
 // pt_skin.hip
 hipError_t launch_skin(hipStream_t stream, const void* skeletal, const float* transforms, void* vertices, void* motion, uint32_t count);
 
+// Everything the launches of one path-traced frame depend on, decided once per frame by plan_frame (pt_kernels.hip): the launchers read the
+// plan and the context's buffers, and re-derive nothing. Zero-initialised before it is filled: its bytes are part of the graph key.
+struct FramePlan {
+    uint32_t rounds, segCap, grid, sqShift;          // rounds of the frame | entries per sub-queue segment | persistent grid | log2 of the sub-queues
+    bool streaming, fused, first;                    // the form: streaming rounds | fused rounds | k_pt_first (either product form) or k_pt_init + round 0
+    bool flat, lds;                                  // lock-step traversal: flat instance scan or phased walk | traversal copy staged in LDS
+    uint32_t ldsFixed, roundLds, extend2Lds;         // fixed LDS bytes of the schedule | dynamic LDS bytes of k_round | of k_extend2
+    uint32_t objectsInLds, recordsInLds;             // what k_round stages behind the traversal copy
+    bool recordsUsable;                              // the frame has normal records (k_capture_normals runs)
+    bool writeT, stats, di, textured, sharc;         // the kernel variants' switches
+    float2* aux;                                     // denoiser modes: the per-pixel auxiliary record, else null
+    uint32_t nsq() const { return 1u << sqShift; }
+    uint32_t cstride() const { return 3u * nsq(); }  // traced + fresh counters + the streaming form's cursor, per round
+};
+
 // pt_stream.hip
-hipError_t launch_shade(Context& c, const SceneView& sv, const FrameView& fv, const PtTextures& tx, const PathQueue& qin, const PathQueue& qout, float2* aux,
-                        uint32_t segCap, const uint32_t* countIn, uint32_t* countOut, uint32_t grid, hipStream_t stream, uint32_t sqBase, uint32_t sqCount);
-hipError_t launch_extend_stream(Context& c, const AlphaContext& ac, const PathQueue& q, uint32_t segCap, const uint32_t* count, uint32_t* cursor,
-                                uint32_t grid, bool stats, bool writeT, hipStream_t stream, uint32_t sqBase, uint32_t sqCount);
+hipError_t launch_shade(Context& c, const FramePlan& p, const SceneView& sv, const FrameView& fv, const PtTextures& tx, uint32_t round, uint32_t grid, hipStream_t stream,
+                        uint32_t sqBase, uint32_t sqCount);
+hipError_t launch_extend_stream(Context& c, const FramePlan& p, const AlphaContext& ac, uint32_t round, hipStream_t stream, uint32_t sqBase, uint32_t sqCount);
 
 // pt_kernels.hip
 hipError_t launch_gbuffer(Context& c, const SceneView& sv, const FrameView& fv, uint32_t flags, const PtTextures& tx);
-hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv, const PtTextures& tx);
+hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv, const PtTextures& tx, bool sharcQuery);
 hipError_t launch_visibility(Context& c, const SceneView& sv, const void* rays, uint32_t count, void* out);
 hipError_t launch_bsdf_evaluate(hipStream_t stream, const float* q, uint32_t count, float* r);
 hipError_t launch_bsdf_sample(hipStream_t stream, const float* q, uint32_t count, float* r);

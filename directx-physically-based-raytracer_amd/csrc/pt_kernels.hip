@@ -420,7 +420,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         } else {
             blob.p = bv.base;
         }
-        AlphaContext ac; ac.objects = sv.objects; ac.heap = sv.heap; ac.srgbLut = sv.srgbLut; ac.instances = sv.accel.instances; ac.shadeTex = sv.shadeTex;
+        const AlphaContext ac = alpha_context(sv);
         TraceStats st; st.nodes = 0; st.tris = 0; st.overflow = 0;
         for (uint32_t base = bq * 256u; base < nT; base += nbq * 256u) {
             const uint32_t local = base + threadIdx.x;
@@ -536,8 +536,7 @@ __global__ __launch_bounds__(256) void k_debug_trace(BlobView bv, AlphaContext a
 
 hipError_t launch_debug_trace(Context& c, const SceneView& sv, const float* ray8, uint32_t* devLog, uint32_t logCap)
 {
-    AlphaContext ac; ac.objects = sv.objects; ac.heap = sv.heap; ac.srgbLut = sv.srgbLut; ac.instances = sv.accel.instances; ac.shadeTex = sv.shadeTex;
-    k_debug_trace<<<1, 256, 0, c.stream>>>(c.scene.blob, ac, make_float4(ray8[0], ray8[1], ray8[2], ray8[3]), make_float4(ray8[4], ray8[5], ray8[6], ray8[7]), devLog, logCap);
+    k_debug_trace<<<1, 256, 0, c.stream>>>(c.scene.blob, alpha_context(sv), make_float4(ray8[0], ray8[1], ray8[2], ray8[3]), make_float4(ray8[4], ray8[5], ray8[6], ray8[7]), devLog, logCap);
     return hipGetLastError();
 }
 
@@ -672,8 +671,7 @@ __global__ __launch_bounds__(256) void k_bsdf_sample(const float* __restrict__ q
 hipError_t launch_visibility(Context& c, const SceneView& sv, const void* rays, uint32_t count, void* out)
 {
     if (!count) return hipSuccess;
-    AlphaContext ac; ac.objects = sv.objects; ac.heap = sv.heap; ac.srgbLut = sv.srgbLut; ac.instances = sv.accel.instances; ac.shadeTex = sv.shadeTex;
-    k_visibility<<<persistent_grid(c), 256, 0, c.stream>>>(c.scene.blob, ac, (const float4*)rays, count, (float4*)out, c.counters.data());
+    k_visibility<<<persistent_grid(c), 256, 0, c.stream>>>(c.scene.blob, alpha_context(sv), (const float4*)rays, count, (float4*)out, c.counters.data());
     return hipGetLastError();
 }
 
@@ -720,22 +718,23 @@ static uint32_t persistent_grid(Context& c)
     return c.persistentGrid;
 }
 
+// The G-buffer pass's own flat rule: unlike a round's (lockstep_flat), its other schedule is the interleaved walk itself, so _TRAVERSAL_V1 / _BRUTE_FORCE turn the flat scan off too, and it asks for the traversal copy.
+static bool gbuffer_flat(const Context& c)
+{
+    return c.scene.blob.base && c.scene.blob.instCount <= kFlatInstances &&
+           !(c.debugFlags & (PT_DEBUG_TRAVERSAL_V1 | PT_DEBUG_TRAVERSAL_PHASED | PT_DEBUG_BRUTE_FORCE));
+}
+
 hipError_t launch_gbuffer(Context& c, const SceneView& sv, const FrameView& fv, uint32_t flags, const PtTextures& tx)
 {
     if (fv.localRows == 0 || fv.width == 0) return hipSuccess;
     dim3 grid((fv.width + 15) / 16, (fv.localRows + 15) / 16);
-    const bool stats = (c.debugFlags & PT_DEBUG_TRAVERSAL_STATS) != 0;
-    const bool flat = c.scene.blob.base && c.scene.blob.instCount <= kFlatInstances &&
-                      !(c.debugFlags & (PT_DEBUG_TRAVERSAL_V1 | PT_DEBUG_TRAVERSAL_PHASED | PT_DEBUG_BRUTE_FORCE));
-    const int mode = !flat ? 0 : (c.scene.blob.bytes <= kBlobLdsMax ? 1 : 2);
+    const int mode = !gbuffer_flat(c) ? 0 : (c.scene.blob.bytes <= kBlobLdsMax ? 1 : 2);
     const uint32_t smem = mode == 0 ? 0u : kFlatLdsFixed + (mode == 1 ? c.scene.blob.bytes : 0u);
-    #define PT_GB(S, T, M) k_gbuffer<S, T, M><<<grid, 256, smem, c.stream>>>(sv, fv, c.camera, c.sceneData, flags, tx, c.scene.blob, c.counters.data())
-    #define PT_GB_M(S, T) do { if (mode == 0) PT_GB(S, T, 0); else if (mode == 1) PT_GB(S, T, 1); else PT_GB(S, T, 2); } while (0)
-    #define PT_GB_T(S) do { if (c.heapHasTextures) PT_GB_M(S, true); else PT_GB_M(S, false); } while (0)
-    if (stats) PT_GB_T(true); else PT_GB_T(false);
-    #undef PT_GB_T
-    #undef PT_GB_M
-    #undef PT_GB
+    with_flags([&](auto S, auto T) {
+        auto launch = [&](auto M) { k_gbuffer<S(), T(), M()><<<grid, 256, smem, c.stream>>>(sv, fv, c.camera, c.sceneData, flags, tx, c.scene.blob, c.counters.data()); };
+        if (mode == 0) launch(std::integral_constant<int, 0>{}); else if (mode == 1) launch(std::integral_constant<int, 1>{}); else launch(std::integral_constant<int, 2>{});
+    }, (c.debugFlags & PT_DEBUG_TRAVERSAL_STATS) != 0, c.heapHasTextures);
     return hipGetLastError();
 }
 
@@ -760,27 +759,66 @@ static void timing_begin(Context& c, std::vector<Event>& ev, uint32_t k)
 }
 static void timing_end(Context& c, std::vector<Event>& ev, uint32_t k) { if (c.timing) hipEventRecord(ev[2 * k + 1].get(), c.stream); }
 
-// Objects whose resolved geometry + material k_round stages in LDS behind the blob: all of them, if that does not cost the kernel its fourth
-// workgroup per CU (160 KB / 4, the kernel's static words and the 512-byte allocation granule counted); otherwise none.
+// ---- the LDS layout of a lock-step round, decided here and nowhere else -------------------------------------------------------------------
+// Dynamic LDS of k_round / k_extend2: the schedule's fixed part, the traversal copy when it is staged, and behind it what k_round alone stages:
+// the objects' resolved geometry + material, then the frame's normal records (20 B each).
 static uint32_t lds_bytes_of_records(uint32_t n) { return (n * 20u + 15u) / 16u * 16u; }
+static uint32_t round_lds_bytes(bool flat, uint32_t blobBytes, uint32_t objects, uint32_t records)
+{
+    return (flat ? kFlatLdsFixed : kExtendLdsFixed) + blobBytes + objects * kObjLds16 * 16u + lds_bytes_of_records(records);
+}
+// ... which must not cost the kernel its fourth workgroup per CU (160 KB / 4, the kernel's static words and the 512-byte allocation granule counted)
+static bool round_lds_fits(uint32_t bytes) { return (bytes + 128u + 511u) / 512u * 512u <= 160u * 1024u / 4u; }
+static bool lockstep_flat(const Context& c) { return c.scene.blob.instCount <= kFlatInstances && !(c.debugFlags & PT_DEBUG_TRAVERSAL_PHASED); }
+
+// Objects whose resolved geometry + material k_round stages in LDS behind the blob: all of them if that fits, otherwise none.
 uint32_t round_objects_in_lds(const Context& c, uint32_t objectCount, bool haveShadeGeom)
 {
     if (c.scene.blob.bytes > kBlobLdsMax || !objectCount || !haveShadeGeom) return 0u;
-    const bool flat = c.scene.blob.instCount <= kFlatInstances && !(c.debugFlags & PT_DEBUG_TRAVERSAL_PHASED);
-    const uint32_t bytes = (flat ? kFlatLdsFixed : kExtendLdsFixed) + c.scene.blob.bytes + objectCount * kObjLds16 * 16u + 128u;
-    return (bytes + 511u) / 512u * 512u <= 160u * 1024u / 4u ? objectCount : 0u;
+    return round_lds_fits(round_lds_bytes(lockstep_flat(c), c.scene.blob.bytes, objectCount, 0u)) ? objectCount : 0u;
 }
-static uint32_t round_objects_in_lds(const Context& c, const SceneView& sv) { return round_objects_in_lds(c, sv.objectCount, sv.shadeGeom != nullptr); }
 // ... and the frame's normal records behind them, under the same rule
 uint32_t round_records_in_lds(const Context& c, uint32_t objectCount, bool haveShadeGeom)
 {
     const uint32_t nobj = round_objects_in_lds(c, objectCount, haveShadeGeom);
     if (!nobj || !normal_records_usable(c)) return 0u;
-    const bool flat = c.scene.blob.instCount <= kFlatInstances && !(c.debugFlags & PT_DEBUG_TRAVERSAL_PHASED);
-    const uint32_t bytes = (flat ? kFlatLdsFixed : kExtendLdsFixed) + c.scene.blob.bytes + nobj * kObjLds16 * 16u + lds_bytes_of_records(c.scene.blob.triCount) + 128u;
-    return (bytes + 511u) / 512u * 512u <= 160u * 1024u / 4u ? c.scene.blob.triCount : 0u;
+    return round_lds_fits(round_lds_bytes(lockstep_flat(c), c.scene.blob.bytes, nobj, c.scene.blob.triCount)) ? c.scene.blob.triCount : 0u;
 }
-static uint32_t round_records_in_lds(const Context& c, const SceneView& sv) { return round_records_in_lds(c, sv.objectCount, sv.shadeGeom != nullptr); }
+
+// ---- the plan of a frame (pt_internal.hpp FramePlan): called by launch_raytrace once its grow-only buffers stand ---------------------------------
+static void plan_frame(FramePlan& p, Context& c, const SceneView& sv, const FrameView& fv, bool sharcQuery)
+{
+    std::memset(&p, 0, sizeof p);
+    const PtGraphicsSettings& gs = c.settings;
+    const uint32_t tiles = (fv.width * fv.localRows + 255u) / 256u;
+    // a round = one k_shade + one k_extend. Per sample a path spends one round as "fresh" (bounce 0, no ray) and at
+    // most Bounces rounds as "traced": spp * (Bounces + 1) rounds empty every queue.
+    p.rounds = gs.SamplesPerPixel * (gs.Bounces + 1u);
+    p.lds = c.scene.blob.bytes <= kBlobLdsMax;
+    p.sqShift = p.lds ? kSubQueueShiftFused : kSubQueueShiftStream;           // (pt_internal.hpp: who likes how many sub-queues)
+    p.segCap = (tiles + p.nsq() - 1) / p.nsq() * 256u;
+    // persistent grid, but never more blocks than the queue has tiles: surplus blocks only cost dispatch slots and LDS that
+    // a concurrent frame's kernels (other streams) could use -- this matters for small shards (1/8 of a 1080p frame = 1013 tiles)
+    p.grid = std::min(persistent_grid(c), (tiles + p.nsq() - 1) / p.nsq() * p.nsq());
+    const uint32_t lockStepFlags = PT_DEBUG_LOCKSTEP | PT_DEBUG_TRAVERSAL_PHASED | PT_DEBUG_BRUTE_FORCE | PT_DEBUG_TRAVERSAL_V1 | PT_DEBUG_UNFUSED_ROUNDS;
+    const uint32_t pairOnlyFlags = PT_DEBUG_TRAVERSAL_STATS | PT_DEBUG_BRUTE_FORCE | PT_DEBUG_TRAVERSAL_V1 | PT_DEBUG_UNFUSED_ROUNDS;
+    p.streaming = !p.lds && !(c.debugFlags & lockStepFlags);                  // a scene that does not fit LDS: persistent traversal lanes with ray replacement
+    p.fused = !p.streaming && !(c.debugFlags & pairOnlyFlags);                // fused rounds: everything except the validation / statistics variants
+    p.first = p.streaming || p.fused;                                         // the product paths start with k_pt_first; the validation variants keep k_pt_init and round 0 apart
+    p.flat = lockstep_flat(c);
+    p.ldsFixed = p.flat ? kFlatLdsFixed : kExtendLdsFixed;
+    p.recordsUsable = normal_records_usable(c);
+    p.objectsInLds = round_objects_in_lds(c, sv.objectCount, sv.shadeGeom != nullptr);
+    p.recordsInLds = round_records_in_lds(c, sv.objectCount, sv.shadeGeom != nullptr);
+    p.extend2Lds = round_lds_bytes(p.flat, p.lds ? c.scene.blob.bytes : 0u, 0u, 0u);
+    p.roundLds = round_lds_bytes(p.flat, p.lds ? c.scene.blob.bytes : 0u, p.objectsInLds, p.recordsInLds);
+    p.aux = gs.Denoiser != PT_DENOISER_NONE ? c.pixelAux.data() : nullptr;
+    p.sharc = sharcQuery;
+    p.writeT = p.aux != nullptr || p.sharc;                                   // denoiser modes and the cache query need CommittedRayT
+    p.stats = (c.debugFlags & PT_DEBUG_TRAVERSAL_STATS) != 0;
+    p.di = gs.IsDIEnabled != 0u;
+    p.textured = c.heapHasTextures;
+}
 
 // ---- the launch sequence of one frame after k_set_constants (which also zeroes the queue counters) ----------------------------------
 // preamble: the frame's normal records and k_pt_first (= k_pt_init + round 0), on the context's stream;
@@ -793,152 +831,99 @@ static uint32_t round_records_in_lds(const Context& c, const SceneView& sv) { re
 // their launches start and drain together -- every chain still pays (rounds x the longest walk of a round), which is the critical path of a
 // frame; frames in flight hide it because their phases differ. Plain streams and events, as frames in flight use them (parallel branches inside
 // ONE captured graph were measured too: the same times on C2).
-#ifndef PT_AB_CHAINS
-#define PT_AB_CHAINS 3
-#endif
-struct FrameForm { bool streaming, fused, first; };
-static FrameForm frame_form(const Context& c)
+// The library's choice, from the A/B runs in profiles/r04_ab/frame_chains.jsonl: three chains for the streaming form when the frame has the GPU
+// to itself (C3 +2 %, C5 +7.5 %, c3t +2 % per frame), one otherwise -- the fused round kernel gains nothing (C2 -1 %), and with other frames
+// in flight the extra streams only crowd the three hardware queues the runtime exposes (C3 -40 %; four chains: -35 % even alone).
+constexpr uint32_t kStreamingChains = 3;
+static uint32_t frame_chains(const Context& c, const FramePlan& p, bool ownStreams)
 {
-    const uint32_t lockStepFlags = PT_DEBUG_LOCKSTEP | PT_DEBUG_TRAVERSAL_PHASED | PT_DEBUG_BRUTE_FORCE | PT_DEBUG_TRAVERSAL_V1 | PT_DEBUG_UNFUSED_ROUNDS;
-    const uint32_t pairOnlyFlags = PT_DEBUG_TRAVERSAL_STATS | PT_DEBUG_BRUTE_FORCE | PT_DEBUG_TRAVERSAL_V1 | PT_DEBUG_UNFUSED_ROUNDS;
-    FrameForm f;
-    f.streaming = c.scene.blob.bytes > kBlobLdsMax && !(c.debugFlags & lockStepFlags);   // a scene that does not fit LDS: persistent traversal lanes with ray replacement
-    f.fused = !f.streaming && !(c.debugFlags & pairOnlyFlags);                     // fused rounds: everything except the validation / statistics variants
-    f.first = f.streaming || f.fused;                                              // the product paths start with k_pt_first; the validation variants keep k_pt_init and round 0 apart
-    return f;
-}
-static uint32_t frame_chains(const Context& c, bool ownStreams)
-{
+    if (!p.first) return 1u;
     // on streams of their own: the library's choice unless the caller made one; direct launches (per-launch events, the default stream): only
     // what the caller asked for, one chain after the other on the context's stream
-    // The library's choice, from the A/B runs in profiles/r04_ab/frame_chains.jsonl: three chains for the streaming form when the frame has the GPU
-    // to itself (C3 +2 %, C5 +7.5 %, c3t +2 % per frame), one otherwise -- the fused round kernel gains nothing (C2 -1 %), and with other frames
-    // in flight the extra streams only crowd the three hardware queues the runtime exposes (C3 -40 %; four chains: -35 % even alone).
-#ifdef PT_AB_CHAINS_FORCE
-    const uint32_t choice = PT_AB_CHAINS_FORCE;                   // A/B builds: this many chains whatever the form
-#else
-    const uint32_t choice = (frame_form(c).streaming && c.framesInFlight <= 1) ? (uint32_t)PT_AB_CHAINS : 1u;
-#endif
+    const uint32_t choice = (p.streaming && c.framesInFlight <= 1) ? kStreamingChains : 1u;
     const uint32_t want = c.chains ? c.chains : (ownStreams ? choice : 1u);
-    return std::max(1u, std::min({ want, Context::kMaxChains, 1u << c.sqShift }));
+    return std::max(1u, std::min({ want, Context::kMaxChains, p.nsq() }));
 }
 
-static hipError_t enqueue_preamble(Context& c, const SceneView& sv, const FrameView& fv, const PtTextures& tx, uint32_t segCap, uint32_t grid)
+static hipError_t enqueue_preamble(Context& c, const FramePlan& p, const SceneView& sv, const FrameView& fv, const PtTextures& tx)
 {
-    const uint32_t nsq = 1u << c.sqShift, cstride = 3u * nsq;                  // traced + fresh counters + the streaming form's cursor, per round
-    float2* aux = c.settings.Denoiser != PT_DENOISER_NONE ? c.pixelAux.data() : nullptr;
-    if (normal_records_usable(c))                          // the frame's normal records, from the vertex buffers as they are now
+    if (p.recordsUsable)                                   // the frame's normal records, from the vertex buffers as they are now
         k_capture_normals<<<dim3(std::min((c.scene.blasTableMaxTris + 255u) / 256u, 64u), c.scene.blasTableCount), 256, 0, c.stream>>>(c.scene.blasTable, sv.shadeGeom, c.shadeRecA.data(), c.shadeRecB.data());
-    if (frame_form(c).first) {
-        #define PT_FIRST(D, S) k_pt_first<D, S><<<grid, 256, 0, c.stream>>>(fv, c.frameConstants.data(), tx, c.queue[1], aux, segCap, &c.queueCounts.data()[cstride], c.primaryRecords.data(), c.sqShift, c.sharcRough[1].data())
-        if (c.sharcQuery) { if (c.settings.IsDIEnabled) PT_FIRST(true, true); else PT_FIRST(false, true); }
-        else { if (c.settings.IsDIEnabled) PT_FIRST(true, false); else PT_FIRST(false, false); }
-        #undef PT_FIRST
-    }
-    else k_pt_init<<<grid, 256, 0, c.stream>>>(fv, c.frameConstants.data(), tx, c.queue[0], aux, segCap, &c.queueCounts.data()[nsq], c.primaryRecords.data(), c.sqShift);
+    if (p.first)
+        with_flags([&](auto S, auto D) {
+            k_pt_first<D(), S()><<<p.grid, 256, 0, c.stream>>>(fv, c.frameConstants.data(), tx, c.queue[1], p.aux, p.segCap, &c.queueCounts.data()[p.cstride()], c.primaryRecords.data(), p.sqShift, c.sharcRough[1].data());
+        }, p.sharc, p.di);
+    else k_pt_init<<<p.grid, 256, 0, c.stream>>>(fv, c.frameConstants.data(), tx, c.queue[0], p.aux, p.segCap, &c.queueCounts.data()[p.nsq()], c.primaryRecords.data(), p.sqShift);
     return hipGetLastError();
 }
 
-// chain g of `chains`: the rounds of its sub-queues, on stream s (product forms only: frame_form(c).first)
-static hipError_t enqueue_chain(Context& c, const SceneView& sv, const FrameView& fv, const PtTextures& tx, uint32_t rounds, uint32_t segCap, uint32_t grid,
-                                uint32_t g, uint32_t chains, hipStream_t s)
+// chain g of `chains`: the rounds of its sub-queues, on stream s (product forms only: p.first)
+static hipError_t enqueue_chain(Context& c, const FramePlan& p, const SceneView& sv, const FrameView& fv, const PtTextures& tx, uint32_t g, uint32_t chains, hipStream_t s)
 {
-    const uint32_t nsq = 1u << c.sqShift, cstride = 3u * nsq;
-    float2* aux = c.settings.Denoiser != PT_DENOISER_NONE ? c.pixelAux.data() : nullptr;
-    const FrameForm form = frame_form(c);
-    const bool stats = (c.debugFlags & PT_DEBUG_TRAVERSAL_STATS) != 0;
-    AlphaContext ac; ac.objects = sv.objects; ac.heap = sv.heap; ac.srgbLut = sv.srgbLut; ac.instances = sv.accel.instances; ac.shadeTex = sv.shadeTex;
-    const uint32_t perSq = std::max(1u, grid / nsq);                           // blocks per sub-queue
+    const uint32_t nsq = p.nsq(), perSq = std::max(1u, p.grid / nsq);          // blocks per sub-queue
     const uint32_t sqBase = (uint32_t)((uint64_t)nsq * g / chains), sqCount = (uint32_t)((uint64_t)nsq * (g + 1) / chains) - sqBase;
-    if (form.streaming) {                                                      // round 0's shading half ran inside k_pt_first
-        const bool wt = aux != nullptr || c.sharcQuery;                        // the cache query needs the hit distance too
-        for (uint32_t r = 0; r <= rounds; r++) {
-            PathQueue& qin = c.queue[r & 1]; PathQueue& qout = c.queue[(r + 1) & 1];
-            uint32_t* cin = &c.queueCounts.data()[r * cstride]; uint32_t* cout = &c.queueCounts.data()[(r + 1) * cstride];
+    if (p.streaming) {                                                         // round 0's shading half ran inside k_pt_first
+        const AlphaContext ac = alpha_context(sv);
+        for (uint32_t r = 0; r <= p.rounds; r++) {
             if (r > 0) {
                 timing_begin(c, c.evShade, c.nShade);
-                launch_shade(c, sv, fv, tx, qin, qout, aux, segCap, cin, cout, perSq * sqCount, s, sqBase, sqCount);
+                launch_shade(c, p, sv, fv, tx, r, perSq * sqCount, s, sqBase, sqCount);
                 timing_end(c, c.evShade, c.nShade); c.nShade++;
             }
-            if (r == rounds) break;
+            if (r == p.rounds) break;
             timing_begin(c, c.evExtend, c.nExtend);
-            launch_extend_stream(c, ac, qout, segCap, cout, cout + 2u * nsq, grid, stats, wt, s, sqBase, sqCount);
+            launch_extend_stream(c, p, ac, r, s, sqBase, sqCount);
             timing_end(c, c.evExtend, c.nExtend); c.nExtend++;
         }
         return hipGetLastError();
     }
-    const bool lds = c.scene.blob.bytes <= kBlobLdsMax;
-    const bool flat = c.scene.blob.instCount <= kFlatInstances && !(c.debugFlags & PT_DEBUG_TRAVERSAL_PHASED);
-    const uint32_t smem = (flat ? kFlatLdsFixed : kExtendLdsFixed) + (lds ? c.scene.blob.bytes : 0u) + round_objects_in_lds(c, sv) * kObjLds16 * 16u + lds_bytes_of_records(round_records_in_lds(c, sv));
-    for (uint32_t r = 1; r <= rounds; r++) {                        // queues and counters of round r: in its argument block (launch_raytrace); round 0 ran inside k_pt_first
+    for (uint32_t r = 1; r <= p.rounds; r++) {                      // queues and counters of round r: in its argument block (launch_raytrace); round 0 ran inside k_pt_first
         timing_begin(c, c.evRound, c.nRound);
-        #define PT_ROUND_S(T, L, F, D) do { if (c.sharcQuery) k_round<T, L, F, D, true><<<perSq * sqCount, 256, smem, s>>>(c.roundArgs.data() + r, sqBase, sqCount); \
-                                            else k_round<T, L, F, D, false><<<perSq * sqCount, 256, smem, s>>>(c.roundArgs.data() + r, sqBase, sqCount); } while (0)
-        #define PT_ROUND(T, L, F) do { if (c.settings.IsDIEnabled) PT_ROUND_S(T, L, F, true); else PT_ROUND_S(T, L, F, false); } while (0)
-        #define PT_ROUND_F(T, L) do { if (flat) PT_ROUND(T, L, true); else PT_ROUND(T, L, false); } while (0)
-        #define PT_ROUND_L(T) do { if (lds) PT_ROUND_F(T, true); else PT_ROUND_F(T, false); } while (0)
-        if (c.heapHasTextures) PT_ROUND_L(true); else PT_ROUND_L(false);
-        #undef PT_ROUND_L
-        #undef PT_ROUND_F
-        #undef PT_ROUND
-        #undef PT_ROUND_S
+        with_flags([&](auto T, auto L, auto F, auto D, auto S) {
+            k_round<T(), L(), F(), D(), S()><<<perSq * sqCount, 256, p.roundLds, s>>>(c.roundArgs.data() + r, sqBase, sqCount);
+        }, p.textured, p.lds, p.flat, p.di, p.sharc);
         timing_end(c, c.evRound, c.nRound); c.nRound++;
     }
     return hipGetLastError();
 }
 
 // the validation / statistics variants: two kernels per round over all sub-queues, on the context's stream
-static hipError_t enqueue_validation_rounds(Context& c, const SceneView& sv, const FrameView& fv, const PtTextures& tx, uint32_t rounds, uint32_t segCap, uint32_t grid)
+static hipError_t enqueue_validation_rounds(Context& c, const FramePlan& p, const SceneView& sv, const FrameView& fv, const PtTextures& tx)
 {
-    const uint32_t nsq = 1u << c.sqShift, cstride = 3u * nsq;
-    float2* aux = c.settings.Denoiser != PT_DENOISER_NONE ? c.pixelAux.data() : nullptr;
-    const bool stats = (c.debugFlags & PT_DEBUG_TRAVERSAL_STATS) != 0;
-    AlphaContext ac; ac.objects = sv.objects; ac.heap = sv.heap; ac.srgbLut = sv.srgbLut; ac.instances = sv.accel.instances; ac.shadeTex = sv.shadeTex;
-    for (uint32_t r = 0; r <= rounds; r++) {
-        PathQueue& qin = c.queue[r & 1]; PathQueue& qout = c.queue[(r + 1) & 1];
-        uint32_t* cin = &c.queueCounts.data()[r * cstride]; uint32_t* cout = &c.queueCounts.data()[(r + 1) * cstride];
+    const AlphaContext ac = alpha_context(sv);
+    for (uint32_t r = 0; r <= p.rounds; r++) {
+        PathQueue& qout = c.queue[(r + 1) & 1];
+        uint32_t* cout = &c.queueCounts.data()[(r + 1) * p.cstride()];
         timing_begin(c, c.evShade, c.nShade);
-        launch_shade(c, sv, fv, tx, qin, qout, aux, segCap, cin, cout, grid, c.stream, 0u, nsq);
+        launch_shade(c, p, sv, fv, tx, r, p.grid, c.stream, 0u, p.nsq());
         timing_end(c, c.evShade, c.nShade); c.nShade++;
-        if (r == rounds) break;
+        if (r == p.rounds) break;
         timing_begin(c, c.evExtend, c.nExtend);
-        const bool lds = c.scene.blob.bytes <= kBlobLdsMax;
-        const bool flat = c.scene.blob.instCount <= kFlatInstances && !(c.debugFlags & PT_DEBUG_TRAVERSAL_PHASED);
-        const uint32_t smem = (flat ? kFlatLdsFixed : kExtendLdsFixed) + (lds ? c.scene.blob.bytes : 0u);
-        if (c.debugFlags & PT_DEBUG_BRUTE_FORCE) k_extend_brute<<<grid, 256, 0, c.stream>>>(sv.accel, c.scene.blob, ac, qout, segCap, cout, c.counters.data(), c.sqShift);
-        else if (c.debugFlags & PT_DEBUG_TRAVERSAL_V1) {
-            if (stats) k_extend<true><<<grid, 256, 0, c.stream>>>(c.scene.blob, ac, qout, segCap, cout, c.counters.data(), c.sqShift);
-            else k_extend<false><<<grid, 256, 0, c.stream>>>(c.scene.blob, ac, qout, segCap, cout, c.counters.data(), c.sqShift);
-        } else {
-            const bool wt = aux != nullptr || c.sharcQuery;            // denoiser modes and the cache query need CommittedRayT
-            #define PT_EXT2(S, L, W, F) k_extend2<S, L, W, F><<<grid, 256, smem, c.stream>>>(c.scene.blob, ac, qout, segCap, cout, c.counters.data(), c.sqShift)
-            #define PT_EXT2_F(S, L, W) do { if (flat) PT_EXT2(S, L, W, true); else PT_EXT2(S, L, W, false); } while (0)
-            #define PT_EXT2_W(S, L) do { if (wt) PT_EXT2_F(S, L, true); else PT_EXT2_F(S, L, false); } while (0)
-            #define PT_EXT2_L(S) do { if (lds) PT_EXT2_W(S, true); else PT_EXT2_W(S, false); } while (0)
-            if (stats) PT_EXT2_L(true); else PT_EXT2_L(false);
-            #undef PT_EXT2_L
-            #undef PT_EXT2_W
-            #undef PT_EXT2_F
-            #undef PT_EXT2
-        }
+        if (c.debugFlags & PT_DEBUG_BRUTE_FORCE) k_extend_brute<<<p.grid, 256, 0, c.stream>>>(sv.accel, c.scene.blob, ac, qout, p.segCap, cout, c.counters.data(), p.sqShift);
+        else if (c.debugFlags & PT_DEBUG_TRAVERSAL_V1)
+            with_flags([&](auto S) { k_extend<S()><<<p.grid, 256, 0, c.stream>>>(c.scene.blob, ac, qout, p.segCap, cout, c.counters.data(), p.sqShift); }, p.stats);
+        else
+            with_flags([&](auto S, auto L, auto W, auto F) {
+                k_extend2<S(), L(), W(), F()><<<p.grid, 256, p.extend2Lds, c.stream>>>(c.scene.blob, ac, qout, p.segCap, cout, c.counters.data(), p.sqShift);
+            }, p.stats, p.lds, p.writeT, p.flat);
         timing_end(c, c.evExtend, c.nExtend); c.nExtend++;
     }
     return hipGetLastError();
 }
 
 // the whole frame on the context's stream: preamble, then the chains one after the other (or the validation rounds)
-static hipError_t enqueue_frame(Context& c, const SceneView& sv, const FrameView& fv, const PtTextures& tx, uint32_t rounds, uint32_t segCap, uint32_t grid, uint32_t chains)
+static hipError_t enqueue_frame(Context& c, const FramePlan& p, const SceneView& sv, const FrameView& fv, const PtTextures& tx, uint32_t chains)
 {
-    hipError_t e = enqueue_preamble(c, sv, fv, tx, segCap, grid);
+    hipError_t e = enqueue_preamble(c, p, sv, fv, tx);
     if (e != hipSuccess) return e;
-    if (!frame_form(c).first) return enqueue_validation_rounds(c, sv, fv, tx, rounds, segCap, grid);
-    for (uint32_t g = 0; g < chains && e == hipSuccess; g++) e = enqueue_chain(c, sv, fv, tx, rounds, segCap, grid, g, chains, c.stream);
+    if (!p.first) return enqueue_validation_rounds(c, p, sv, fv, tx);
+    for (uint32_t g = 0; g < chains && e == hipSuccess; g++) e = enqueue_chain(c, p, sv, fv, tx, g, chains, c.stream);
     return e;
 }
 
 template <typename T> static void key_add(std::string& k, const T& v) { k.append((const char*)&v, sizeof v); }
 
-hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv, const PtTextures& tx)
+hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv, const PtTextures& tx, bool sharcQuery)
 {
     const PtGraphicsSettings& gs = c.settings;
     const uint32_t npix = fv.width * fv.localRows;
@@ -951,45 +936,37 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
         if ((ea = c.shadeRecB.reserve(c.scene.blob.triCount)) != hipSuccess) return ea;   // last: the grow decision reads its capacity
     }
     if (npix == 0 || gs.SamplesPerPixel == 0) return hipSuccess;
-    // a round = one k_shade + one k_extend. Per sample a path spends one round as "fresh" (bounce 0, no ray) and at
-    // most Bounces rounds as "traced": spp * (Bounces + 1) rounds empty every queue.
-    const uint32_t rounds = gs.SamplesPerPixel * (gs.Bounces + 1u);
-    const uint32_t tiles = (npix + 255u) / 256u;
-    c.sqShift = c.scene.blob.bytes <= kBlobLdsMax ? kSubQueueShiftFused : kSubQueueShiftStream;          // (pt_internal.hpp: who likes how many sub-queues)
-    const uint32_t nsq = 1u << c.sqShift, cstride = 3u * nsq;
-    const uint32_t segCap = (tiles + nsq - 1) / nsq * 256u;                   // entries per sub-queue segment
-    hipError_t e = ensure_queues(c, segCap * nsq, (rounds + 2) * cstride);
-    if (e != hipSuccess) return e;
-    if ((e = c.frameConstants.reserve(1)) != hipSuccess) return e;
+    hipError_t e;
     if (gs.Denoiser != PT_DENOISER_NONE && (e = c.pixelAux.reserve(npix)) != hipSuccess) return e;
-    if (c.sharcQuery) for (auto& a : c.sharcRough) if ((e = a.reserve((size_t)segCap * nsq)) != hipSuccess) return e;   // previousRoughness, indexed like the path queues
+    FramePlan plan; plan_frame(plan, c, sv, fv, sharcQuery);
+    const FramePlan& p = plan;
+    const uint32_t rounds = p.rounds, nsq = p.nsq(), cstride = p.cstride();
+    if ((e = ensure_queues(c, p.segCap * nsq, (rounds + 2) * cstride)) != hipSuccess) return e;
+    if ((e = c.frameConstants.reserve(1)) != hipSuccess) return e;
+    if (p.sharc) for (auto& a : c.sharcRough) if ((e = a.reserve((size_t)p.segCap * nsq)) != hipSuccess) return e;   // previousRoughness, indexed like the path queues
     FrameConstants fc; fc.cam = c.camera; fc.sd = c.sceneData; fc.gs = c.settings;
     k_set_constants<<<1, 256, 0, c.stream>>>(fc, c.frameConstants.data(), c.queueCounts.data(), (rounds + 2u) * cstride);
-    // persistent grid, but never more blocks than the queue has tiles: surplus blocks only cost dispatch slots and LDS that
-    // a concurrent frame's kernels (other streams) could use -- this matters for small shards (1/8 of a 1080p frame = 1013 tiles)
-    const uint32_t grid = std::min(persistent_grid(c), (tiles + nsq - 1) / nsq * nsq);
     c.lastIterations = rounds + 1;
 
     // everything the launch sequence depends on: the key of the per-round argument blocks and of the captured graph
     std::string key;
-    key_add(key, sv); key_add(key, fv); key_add(key, tx); key_add(key, rounds); key_add(key, segCap); key_add(key, grid);
-    key_add(key, c.queue[0]); key_add(key, c.queue[1]); key_add(key, c.queueCounts.data()); key_add(key, c.scene.blob); key_add(key, c.heapHasTextures);
-    key_add(key, c.frameConstants.data()); key_add(key, c.primaryRecords.data()); key_add(key, c.stream); key_add(key, c.pixelAux.data()); key_add(key, gs.Denoiser); key_add(key, c.debugFlags); key_add(key, gs.IsDIEnabled != 0u);
-    key_add(key, c.framesInFlight); key_add(key, c.sqShift); key_add(key, c.chains);
-    key_add(key, c.sharcQuery); key_add(key, c.sharcView.data()); key_add(key, c.sharcRough[0].data()); key_add(key, c.sharcRough[1].data());
-    key_add(key, c.shadeRecA.data()); key_add(key, c.scene.blasTable); key_add(key, c.scene.blasTableCount); key_add(key, c.scene.blasTableMaxTris); key_add(key, normal_records_usable(c));
+    key_add(key, sv); key_add(key, fv); key_add(key, tx); key_add(key, plan);
+    key_add(key, c.queue[0]); key_add(key, c.queue[1]); key_add(key, c.queueCounts.data()); key_add(key, c.scene.blob);
+    key_add(key, c.frameConstants.data()); key_add(key, c.primaryRecords.data()); key_add(key, c.stream); key_add(key, c.pixelAux.data()); key_add(key, gs.Denoiser); key_add(key, c.debugFlags);
+    key_add(key, c.framesInFlight); key_add(key, c.chains);
+    key_add(key, c.sharcView.data()); key_add(key, c.sharcRough[0].data()); key_add(key, c.sharcRough[1].data());
+    key_add(key, c.shadeRecA.data()); key_add(key, c.scene.blasTable); key_add(key, c.scene.blasTableCount); key_add(key, c.scene.blasTableMaxTris);
     if (key != c.roundArgsKey || !c.roundArgs.data()) {                              // k_round's argument blocks, one per round (device memory)
         if ((e = c.roundArgs.reserve(rounds + 1)) != hipSuccess) return e;
         std::vector<RoundArgs> host(rounds + 1);
-        float2* aux = gs.Denoiser != PT_DENOISER_NONE ? c.pixelAux.data() : nullptr;
         for (uint32_t r = 0; r <= rounds; r++) {
             RoundArgs& a = host[r];
             std::memset(&a, 0, sizeof a);
             a.sv = sv; a.fv = fv; a.tx = tx; a.bv = c.scene.blob; a.qin = c.queue[r & 1]; a.qout = c.queue[(r + 1) & 1];
-            a.fc = c.frameConstants.data(); a.aux = aux; a.countIn = &c.queueCounts.data()[r * cstride]; a.countOut = &c.queueCounts.data()[(r + 1) * cstride]; a.sqShift = c.sqShift;
-            a.counters = c.counters.data(); a.segCap = segCap; a.primary = c.primaryRecords.data(); a.objectsInLds = round_objects_in_lds(c, sv);
-            if (normal_records_usable(c)) { a.recA = c.shadeRecA.data(); a.recB = c.shadeRecB.data(); a.recordsInLds = round_records_in_lds(c, sv); }
-            if (c.sharcQuery) { a.sharc = c.sharcView.data(); a.roughIn = c.sharcRough[r & 1].data(); a.roughOut = c.sharcRough[(r + 1) & 1].data(); }
+            a.fc = c.frameConstants.data(); a.aux = p.aux; a.countIn = &c.queueCounts.data()[r * cstride]; a.countOut = &c.queueCounts.data()[(r + 1) * cstride]; a.sqShift = p.sqShift;
+            a.counters = c.counters.data(); a.segCap = p.segCap; a.primary = c.primaryRecords.data(); a.objectsInLds = p.objectsInLds;
+            if (p.recordsUsable) { a.recA = c.shadeRecA.data(); a.recB = c.shadeRecB.data(); a.recordsInLds = p.recordsInLds; }
+            if (p.sharc) { a.sharc = c.sharcView.data(); a.roughIn = c.sharcRough[r & 1].data(); a.roughOut = c.sharcRough[(r + 1) & 1].data(); }
         }
         if ((e = hipMemcpyAsync(c.roundArgs.data(), host.data(), sizeof(RoundArgs) * (rounds + 1), hipMemcpyHostToDevice, c.stream)) != hipSuccess) return e;
         if ((e = hipStreamSynchronize(c.stream)) != hipSuccess) return e;    // once per change of the scene / frame geometry, never per frame
@@ -1014,7 +991,7 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
         if (ce == hipSuccess) exec.reset(ge); else (void)hipGetLastError();
         return ce;
     };
-    const uint32_t chains = frame_form(c).first ? frame_chains(c, graphable) : 1u;
+    const uint32_t chains = frame_chains(c, p, graphable);
     if (graphable && chains > 1) {
         // every chain a linear graph on a stream of its own; the preamble is launched directly (two kernels)
         if (!c.chainFork && (e = create_event(c.chainFork, hipEventDisableTiming)) != hipSuccess) return e;
@@ -1026,12 +1003,12 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
             c.chainGraphKey.clear();
             for (uint32_t g = 0; g < chains; g++) {
                 hipStream_t s = g == 0 ? c.stream : c.chainStream[g - 1].get();
-                if (capture(s, c.chainGraph[g], [&] { return enqueue_chain(c, sv, fv, tx, rounds, segCap, grid, g, chains, s); }) != hipSuccess) { c.disableGraphs = true; break; }
+                if (capture(s, c.chainGraph[g], [&] { return enqueue_chain(c, p, sv, fv, tx, g, chains, s); }) != hipSuccess) { c.disableGraphs = true; break; }
             }
             if (!c.disableGraphs) c.chainGraphKey = key;
         }
         if (!c.disableGraphs) {
-            if ((e = enqueue_preamble(c, sv, fv, tx, segCap, grid)) != hipSuccess) return e;
+            if ((e = enqueue_preamble(c, p, sv, fv, tx)) != hipSuccess) return e;
             if ((e = hipEventRecord(c.chainFork.get(), c.stream)) != hipSuccess) return e;
             for (uint32_t g = 1; g < chains; g++) {
                 hipStream_t s = c.chainStream[g - 1].get();
@@ -1046,12 +1023,12 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
     } else if (graphable) {
         if (key != c.graphKey || !c.graphExec) {
             c.graphKey.clear();
-            if (capture(c.stream, c.graphExec, [&] { return enqueue_frame(c, sv, fv, tx, rounds, segCap, grid, 1u); }) != hipSuccess) c.disableGraphs = true;
+            if (capture(c.stream, c.graphExec, [&] { return enqueue_frame(c, p, sv, fv, tx, 1u); }) != hipSuccess) c.disableGraphs = true;
             else c.graphKey = key;
         }
         if (c.graphExec) return hipGraphLaunch(c.graphExec.get(), c.stream);
     }
-    return enqueue_frame(c, sv, fv, tx, rounds, segCap, grid, frame_form(c).first ? frame_chains(c, false) : 1u);
+    return enqueue_frame(c, p, sv, fv, tx, frame_chains(c, p, false));
 }
 
 hipError_t launch_deinterleave(hipStream_t stream, void* dst, const void* src, const uint64_t* rankOffsetsHost, uint32_t rankCount,

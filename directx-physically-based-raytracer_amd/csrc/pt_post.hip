@@ -184,28 +184,19 @@ __global__ __launch_bounds__(256) void k_post_resolve(PostResolve a)
 
 using namespace pt;
 
-static int post_fail(Context& c, int status, const std::string& msg) { c.lastError = msg; return status; }
-static int post_fail_hip(Context& c, hipError_t e, const char* what)
-{
-    return post_fail(c, e == hipErrorOutOfMemory ? PT_ERROR_OUT_OF_MEMORY : PT_ERROR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-#define POST_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return post_fail_hip(c, e_, #expr); } while (0)
-#define POST_ARG(cond, msg) do { if (!(cond)) return post_fail(c, PT_ERROR_INVALID_ARGUMENT, msg); } while (0)
-
 static dim3 post_grid(uint32_t w, uint32_t h) { return dim3((w + 63u) / 64u, (h + 3u) / 4u); }
 
-template <bool BLOOM, int OP, bool HDR>
-static void launch_resolve(const PostResolve& a, hipStream_t stream)
+// the resolve kernel's variants: bloom on or off; HDR (no operator), or one of the three tone-mapping operators
+static void launch_resolve(const PostResolve& a, bool bloom, uint32_t op, bool hdr, hipStream_t stream)
 {
-    k_post_resolve<BLOOM, OP, HDR><<<post_grid((uint32_t)a.w, (uint32_t)a.h), 256, 0, stream>>>(a);
-}
-template <bool BLOOM>
-static void launch_resolve(const PostResolve& a, uint32_t op, bool hdr, hipStream_t stream)
-{
-    if (hdr) launch_resolve<BLOOM, 0, true>(a, stream);
-    else if (op == PT_TONE_MAP_SATURATE) launch_resolve<BLOOM, PT_TONE_MAP_SATURATE, false>(a, stream);
-    else if (op == PT_TONE_MAP_REINHARD) launch_resolve<BLOOM, PT_TONE_MAP_REINHARD, false>(a, stream);
-    else launch_resolve<BLOOM, PT_TONE_MAP_ACES_FILMIC, false>(a, stream);
+    auto variants = [&](auto BLOOM) {
+        auto launch = [&](auto OP, auto HDR) { k_post_resolve<BLOOM(), OP(), HDR()><<<post_grid((uint32_t)a.w, (uint32_t)a.h), 256, 0, stream>>>(a); };
+        if (hdr) launch(std::integral_constant<int, 0>{}, std::true_type{});
+        else if (op == PT_TONE_MAP_SATURATE) launch(std::integral_constant<int, PT_TONE_MAP_SATURATE>{}, std::false_type{});
+        else if (op == PT_TONE_MAP_REINHARD) launch(std::integral_constant<int, PT_TONE_MAP_REINHARD>{}, std::false_type{});
+        else launch(std::integral_constant<int, PT_TONE_MAP_ACES_FILMIC>{}, std::false_type{});
+    };
+    if (!bloom) variants(std::false_type{}); else variants(std::true_type{});
 }
 
 // DirectXTK's colour-primary rotations (ToneMapPostProcess.cpp), rows for column vectors
@@ -221,15 +212,15 @@ int pt_post_set_constants(PtContext* ctx, const PtPostProcessSettings* s)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
-    POST_ARG(s, "settings is NULL");
-    POST_ARG(s->RenderSize[0] >= 1u && s->RenderSize[0] <= kPostMaxSize && s->RenderSize[1] >= 1u && s->RenderSize[1] <= kPostMaxSize,
+    API_ARG(&c, s, "settings is NULL");
+    API_ARG(&c, s->RenderSize[0] >= 1u && s->RenderSize[0] <= kPostMaxSize && s->RenderSize[1] >= 1u && s->RenderSize[1] <= kPostMaxSize,
              "RenderSize must be 1..16384 on both axes");
-    POST_ARG(s->IsBloomEnabled <= 1u && s->IsHDREnabled <= 1u, "IsBloomEnabled / IsHDREnabled must be 0 or 1");
-    POST_ARG(s->BloomStrength >= 0.0f && s->BloomStrength <= 1.0f, "BloomStrength must be in [0, 1]");
-    POST_ARG(s->ToneMappingOperator >= PT_TONE_MAP_SATURATE && s->ToneMappingOperator <= PT_TONE_MAP_ACES_FILMIC, "unknown ToneMappingOperator");
-    POST_ARG(s->Exposure >= -10.0f && s->Exposure <= 10.0f, "Exposure must be in [-10, 10]");
-    POST_ARG(s->PaperWhiteNits >= 50.0f && s->PaperWhiteNits <= 10000.0f, "PaperWhiteNits must be in [50, 10000]");
-    POST_ARG(s->ColorPrimaryRotation <= PT_COLOR_ROTATION_HDTV_TO_DCI_P3_D65, "unknown ColorPrimaryRotation");
+    API_ARG(&c, s->IsBloomEnabled <= 1u && s->IsHDREnabled <= 1u, "IsBloomEnabled / IsHDREnabled must be 0 or 1");
+    API_ARG(&c, s->BloomStrength >= 0.0f && s->BloomStrength <= 1.0f, "BloomStrength must be in [0, 1]");
+    API_ARG(&c, s->ToneMappingOperator >= PT_TONE_MAP_SATURATE && s->ToneMappingOperator <= PT_TONE_MAP_ACES_FILMIC, "unknown ToneMappingOperator");
+    API_ARG(&c, s->Exposure >= -10.0f && s->Exposure <= 10.0f, "Exposure must be in [-10, 10]");
+    API_ARG(&c, s->PaperWhiteNits >= 50.0f && s->PaperWhiteNits <= 10000.0f, "PaperWhiteNits must be in [50, 10000]");
+    API_ARG(&c, s->ColorPrimaryRotation <= PT_COLOR_ROTATION_HDTV_TO_DCI_P3_D65, "unknown ColorPrimaryRotation");
     c.post = *s;
     memset(c.post._pad, 0, sizeof c.post._pad);
     c.havePost = true;
@@ -240,18 +231,18 @@ int pt_post_render(PtContext* ctx, const PtPostTextures* t)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
-    POST_ARG(t, "textures is NULL");
-    if (!c.havePost) return post_fail(c, PT_ERROR_NOT_READY, "call pt_post_set_constants first");
+    API_ARG(&c, t, "textures is NULL");
+    if (!c.havePost) return fail(&c, PT_ERROR_NOT_READY, "call pt_post_set_constants first");
     const PtPostProcessSettings& s = c.post;
     const uint32_t W = s.RenderSize[0], H = s.RenderSize[1];
     const bool bloom = s.IsBloomEnabled != 0;
-    POST_ARG(t->Radiance, "Radiance is NULL");
-    POST_ARG(t->Color || t->BackBuffer || t->Display8, "no output bound (Color, BackBuffer, Display8)");
-    POST_ARG(((uintptr_t)t->Radiance & 7u) == 0 && ((uintptr_t)t->Color & 7u) == 0 && ((uintptr_t)t->BackBuffer & 3u) == 0 &&
+    API_ARG(&c, t->Radiance, "Radiance is NULL");
+    API_ARG(&c, t->Color || t->BackBuffer || t->Display8, "no output bound (Color, BackBuffer, Display8)");
+    API_ARG(&c, ((uintptr_t)t->Radiance & 7u) == 0 && ((uintptr_t)t->Color & 7u) == 0 && ((uintptr_t)t->BackBuffer & 3u) == 0 &&
              ((uintptr_t)t->Display8 & 3u) == 0, "textures must be aligned to their texel size");
-    POST_ARG(!bloom || (W >= 2u && H >= 2u && std::max(W, H) >= 32u),
+    API_ARG(&c, !bloom || (W >= 2u && H >= 2u && std::max(W, H) >= 32u),
              "bloom needs RenderSize W, H >= 2 and max(W, H) >= 32 (five mips of the half-size pyramid)");
-    POST_HIP(hipSetDevice(c.device));
+    API_HIP(&c, hipSetDevice(c.device));
 
     PostResolve r; memset(&r, 0, sizeof r);
     r.radiance = (const ushort4*)t->Radiance; r.color = (ushort4*)t->Color; r.back = (uint32_t*)t->BackBuffer; r.disp8 = (uint32_t*)t->Display8;
@@ -263,8 +254,8 @@ int pt_post_render(PtContext* ctx, const PtPostTextures* t)
         r.scale = (float)std::exp2((double)s.Exposure);
     }
     if (!bloom) {
-        launch_resolve<false>(r, s.ToneMappingOperator, s.IsHDREnabled != 0, c.stream);
-        POST_HIP(hipGetLastError());
+        launch_resolve(r, false, s.ToneMappingOperator, s.IsHDREnabled != 0, c.stream);
+        API_HIP(&c, hipGetLastError());
         return PT_OK;
     }
 
@@ -277,8 +268,8 @@ int pt_post_render(PtContext* ctx, const PtPostTextures* t)
     }
     if (c.postLevels.capacity() < total) {                 // transactional: the old pyramid stays until the new one exists
         DeviceBuffer<ushort4> fresh;
-        POST_HIP(fresh.reserve(total));
-        POST_HIP(hipStreamSynchronize(c.stream));          // earlier renders may still read the old one
+        API_HIP(&c, fresh.reserve(total));
+        API_HIP(&c, hipStreamSynchronize(c.stream));          // earlier renders may still read the old one
         c.postLevels = std::move(fresh);
     }
     memset(c.postDims, 0, sizeof c.postDims);
@@ -292,12 +283,12 @@ int pt_post_render(PtContext* ctx, const PtPostTextures* t)
         if (st < 2) k_post_down<true><<<g, 256, 0, c.stream>>>(a);          // InputMipLevel 0 on both: the Karis branch
         else if (st < kPostMips) k_post_down<false><<<g, 256, 0, c.stream>>>(a);
         else k_post_up<<<g, 256, 0, c.stream>>>(a);
-        POST_HIP(hipGetLastError());
+        API_HIP(&c, hipGetLastError());
     }
     r.blur = base + off[kPostStages - 1]; r.bw = (int)dims[kPostStages - 1][0]; r.bh = (int)dims[kPostStages - 1][1];
     r.w1 = 1.0f - s.BloomStrength; r.w2 = s.BloomStrength;
-    launch_resolve<true>(r, s.ToneMappingOperator, s.IsHDREnabled != 0, c.stream);
-    POST_HIP(hipGetLastError());
+    launch_resolve(r, true, s.ToneMappingOperator, s.IsHDREnabled != 0, c.stream);
+    API_HIP(&c, hipGetLastError());
     memcpy(c.postDims, dims, sizeof dims); memcpy(c.postOffset, off, sizeof off);
     return PT_OK;
 }
@@ -306,13 +297,13 @@ int pt_post_download_bloom(PtContext* ctx, uint32_t stage, uint16_t* host, uint6
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
-    POST_ARG(out_width && out_height && (host || capacity == 0), "out_width / out_height / host_rgba16f is NULL");
-    POST_ARG(stage < (uint32_t)kPostStages, "stage must be 0..8");
-    POST_HIP(hipSetDevice(c.device));
-    POST_HIP(hipStreamSynchronize(c.stream));
+    API_ARG(&c, out_width && out_height && (host || capacity == 0), "out_width / out_height / host_rgba16f is NULL");
+    API_ARG(&c, stage < (uint32_t)kPostStages, "stage must be 0..8");
+    API_HIP(&c, hipSetDevice(c.device));
+    API_HIP(&c, hipStreamSynchronize(c.stream));
     *out_width = c.postDims[stage][0]; *out_height = c.postDims[stage][1];
     const uint64_t n = std::min<uint64_t>(capacity, (uint64_t)c.postDims[stage][0] * c.postDims[stage][1]);
-    if (n) POST_HIP(hipMemcpy(host, c.postLevels.data() + c.postOffset[stage], n * sizeof(ushort4), hipMemcpyDeviceToHost));
+    if (n) API_HIP(&c, hipMemcpy(host, c.postLevels.data() + c.postOffset[stage], n * sizeof(ushort4), hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

@@ -285,16 +285,6 @@ __global__ void k_sharc_debug_query(SharcView view, const float* __restrict__ po
     out[i] = q;
 }
 
-int di_views(Context& c, uint32_t width, uint32_t height, SceneView& sv, FrameView& fv, bool needFrameInputs);   // pt_api.hip make_views
-
-static int sharc_fail(Context& c, int status, const std::string& msg) { c.lastError = msg; return status; }
-static int sharc_fail_hip(Context& c, hipError_t e, const char* what)
-{
-    return sharc_fail(c, e == hipErrorOutOfMemory ? PT_ERROR_OUT_OF_MEMORY : PT_ERROR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-#define SHARC_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return sharc_fail_hip(c, e_, #expr); } while (0)
-#define SHARC_ARG(cond, msg) do { if (!(cond)) return sharc_fail(c, PT_ERROR_INVALID_ARGUMENT, msg); } while (0)
-
 static SharcView sharc_view(const Context& c, uint32_t resolvedParity)
 {
     SharcView v; std::memset(&v, 0, sizeof v);
@@ -322,18 +312,18 @@ int pt_sharc_configure(PtContext* ctx, uint32_t capacity)
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
     if (capacity == 0u) capacity = 1u << 22;
-    SHARC_ARG(capacity % kSharcBucket == 0u, "SHARC capacity must be a multiple of 32 (the bucket of the hash map)");
-    SHARC_HIP(hipSetDevice(c.device));
+    API_ARG(&c, capacity % kSharcBucket == 0u, "SHARC capacity must be a multiple of 32 (the bucket of the hash map)");
+    API_HIP(&c, hipSetDevice(c.device));
     if (capacity > c.sharcKeys.capacity()) {                 // kernels in flight may read the old buffers
-        SHARC_HIP(hipStreamSynchronize(c.stream));
+        API_HIP(&c, hipStreamSynchronize(c.stream));
         c.sharcCapacity = 0;
         c.sharcKeys.reset(); for (auto& v : c.sharcVoxels) v.reset();
-        for (auto& v : c.sharcVoxels) SHARC_HIP(v.reserve(capacity));
-        SHARC_HIP(c.sharcView.reserve(1));
-        SHARC_HIP(c.sharcKeys.reserve(capacity));            // last: the grow decision reads its capacity
+        for (auto& v : c.sharcVoxels) API_HIP(&c, v.reserve(capacity));
+        API_HIP(&c, c.sharcView.reserve(1));
+        API_HIP(&c, c.sharcKeys.reserve(capacity));            // last: the grow decision reads its capacity
     }
     c.sharcCapacity = capacity; c.sharcParity = 0;
-    SHARC_HIP(sharc_clear(c));
+    API_HIP(&c, sharc_clear(c));
     return PT_OK;
 }
 
@@ -341,14 +331,14 @@ int pt_sharc_set_constants(PtContext* ctx, const PtSHARCSettings* s)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
-    SHARC_ARG(s, "settings is NULL");
-    SHARC_ARG(s->DownscaleFactor >= 1u && s->DownscaleFactor <= 4u, "SHARC DownscaleFactor must be 1..4");
-    SHARC_ARG(s->AccumulationFrames >= 1u && s->AccumulationFrames <= kSharcFrameMask, "SHARC AccumulationFrames must be 1..63");
-    SHARC_ARG(s->MaxStaleFrames >= 1u && s->MaxStaleFrames <= 255u, "SHARC MaxStaleFrames must be 1..255");
-    SHARC_ARG(s->SceneScale >= 5.0f && s->SceneScale <= 100.0f, "SHARC SceneScale must be in [5, 100]");
-    SHARC_ARG(s->RoughnessThreshold >= 0.0f && s->RoughnessThreshold <= 1.0f, "SHARC RoughnessThreshold must be in [0, 1]");
-    SHARC_ARG(s->IsAntiFireflyEnabled <= 1u, "SHARC IsAntiFireflyEnabled must be 0 or 1");
-    SHARC_ARG(s->IsHashGridVisualizationEnabled == 0u, "SHARC hash-grid visualisation is not served");
+    API_ARG(&c, s, "settings is NULL");
+    API_ARG(&c, s->DownscaleFactor >= 1u && s->DownscaleFactor <= 4u, "SHARC DownscaleFactor must be 1..4");
+    API_ARG(&c, s->AccumulationFrames >= 1u && s->AccumulationFrames <= kSharcFrameMask, "SHARC AccumulationFrames must be 1..63");
+    API_ARG(&c, s->MaxStaleFrames >= 1u && s->MaxStaleFrames <= 255u, "SHARC MaxStaleFrames must be 1..255");
+    API_ARG(&c, s->SceneScale >= 5.0f && s->SceneScale <= 100.0f, "SHARC SceneScale must be in [5, 100]");
+    API_ARG(&c, s->RoughnessThreshold >= 0.0f && s->RoughnessThreshold <= 1.0f, "SHARC RoughnessThreshold must be in [0, 1]");
+    API_ARG(&c, s->IsAntiFireflyEnabled <= 1u, "SHARC IsAntiFireflyEnabled must be 0 or 1");
+    API_ARG(&c, s->IsHashGridVisualizationEnabled == 0u, "SHARC hash-grid visualisation is not served");
     c.sharcSettings = *s; c.haveSharcSettings = true;
     return PT_OK;
 }
@@ -357,9 +347,9 @@ int pt_sharc_reset(PtContext* ctx)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
-    if (!c.sharcCapacity) return sharc_fail(c, PT_ERROR_NOT_READY, "no SHARC cache: call pt_sharc_configure first");
-    SHARC_HIP(hipSetDevice(c.device));
-    SHARC_HIP(sharc_clear(c));
+    if (!c.sharcCapacity) return fail(&c, PT_ERROR_NOT_READY, "no SHARC cache: call pt_sharc_configure first");
+    API_HIP(&c, hipSetDevice(c.device));
+    API_HIP(&c, sharc_clear(c));
     return PT_OK;
 }
 
@@ -367,21 +357,19 @@ int pt_raytrace_render_sharc(PtContext* ctx, const PtTextures* tx)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
-    SHARC_ARG(tx, "textures is NULL");
-    if (!c.sharcCapacity) return sharc_fail(c, PT_ERROR_NOT_READY, "no SHARC cache: call pt_sharc_configure first");
-    if (!c.haveSharcSettings) return sharc_fail(c, PT_ERROR_NOT_READY, "call pt_sharc_set_constants first");
-    if (!c.haveSettings) return sharc_fail(c, PT_ERROR_NOT_READY, "call pt_raytrace_set_constants first");
+    API_ARG(&c, tx, "textures is NULL");
+    if (!c.sharcCapacity) return fail(&c, PT_ERROR_NOT_READY, "no SHARC cache: call pt_sharc_configure first");
+    if (!c.haveSharcSettings) return fail(&c, PT_ERROR_NOT_READY, "call pt_sharc_set_constants first");
+    if (!c.haveSettings) return fail(&c, PT_ERROR_NOT_READY, "call pt_raytrace_set_constants first");
     const PtGraphicsSettings& gs = c.settings;
-    SHARC_ARG(c.sharding.RankCount == 1u, "the SHARC cache needs an unsharded context (RankCount 1): it is world-space and global, a band holds only its own G-buffer rows");
-    SHARC_ARG(gs.Denoiser == PT_DENOISER_NONE || gs.Denoiser == PT_DENOISER_DLSS_RAY_RECONSTRUCTION, "the SHARC query serves Denoiser None and DLSS-RR, not the NRD packing");
-    SHARC_ARG(!(c.debugFlags & (PT_DEBUG_BRUTE_FORCE | PT_DEBUG_TRAVERSAL_V1)), "the SHARC query needs the hit distance: not with PT_DEBUG_BRUTE_FORCE / PT_DEBUG_TRAVERSAL_V1");
-    SHARC_ARG(!gs.IsDIEnabled || (tx->Diffuse && tx->Specular), "IsDIEnabled reads the direct lighting from Textures.Diffuse / Textures.Specular (pt_di_render): not bound");
-    SHARC_ARG(gs.SamplesPerPixel < 65536 && gs.Bounces < 32768, "SamplesPerPixel / Bounces out of range");
-    SHARC_ARG(tx->Position && tx->FlatNormal && tx->GeometricNormal && tx->BaseColorMetalness && tx->NormalRoughness && tx->IOR
-              && tx->Transmission && tx->Radiance, "a G-buffer texture the path tracer reads is not bound (Raytracing::Textures)");
-    SHARC_HIP(hipSetDevice(c.device));
+    API_ARG(&c, c.sharding.RankCount == 1u, "the SHARC cache needs an unsharded context (RankCount 1): it is world-space and global, a band holds only its own G-buffer rows");
+    API_ARG(&c, gs.Denoiser == PT_DENOISER_NONE || gs.Denoiser == PT_DENOISER_DLSS_RAY_RECONSTRUCTION, "the SHARC query serves Denoiser None and DLSS-RR, not the NRD packing");
+    API_ARG(&c, !(c.debugFlags & (PT_DEBUG_BRUTE_FORCE | PT_DEBUG_TRAVERSAL_V1)), "the SHARC query needs the hit distance: not with PT_DEBUG_BRUTE_FORCE / PT_DEBUG_TRAVERSAL_V1");
+    int st = check_raytrace_args(c, tx);
+    if (st != PT_OK) return st;
+    API_HIP(&c, hipSetDevice(c.device));
     SceneView sv; FrameView fv; memset(&sv, 0, sizeof sv); memset(&fv, 0, sizeof fv);
-    int st = di_views(c, gs.RenderSize[0], gs.RenderSize[1], sv, fv, true);
+    st = make_views(c, gs.RenderSize[0], gs.RenderSize[1], sv, fv, true);
     if (st != PT_OK) return st;
     if (gs.Bounces == 0) return PT_OK;                       // the pass is not dispatched, Source/App.cpp:1277-1279
     const PtSHARCSettings& ss = c.sharcSettings;
@@ -390,8 +378,8 @@ int pt_raytrace_render_sharc(PtContext* ctx, const PtTextures* tx)
     const uint32_t uw = fv.width / ss.DownscaleFactor, uh = fv.height / ss.DownscaleFactor;
     uint32_t resolved = prev;                                // skipping: the query sees the cache as the last frame left it
     if (!skip) {
-        SHARC_HIP(c.frameConstants.reserve(1));
-        SHARC_HIP(hipMemsetAsync(c.sharcVoxels[cur].data(), 0, sizeof(uint4) * (size_t)c.sharcCapacity, c.stream));
+        API_HIP(&c, c.frameConstants.reserve(1));
+        API_HIP(&c, hipMemsetAsync(c.sharcVoxels[cur].data(), 0, sizeof(uint4) * (size_t)c.sharcCapacity, c.stream));
         if (uw && uh) {
             SharcUpdateArgs a; memset(&a, 0, sizeof a);
             a.keys = c.sharcKeys.data(); a.current = c.sharcVoxels[cur].data(); a.previous = c.sharcVoxels[prev].data();
@@ -400,10 +388,10 @@ int pt_raytrace_render_sharc(PtContext* ctx, const PtTextures* tx)
             c.sharcLogPaths = 0; c.sharcLogBounces = 0;
             if (log) {
                 const size_t n = (size_t)uw * uh * (gs.Bounces + 1u);
-                SHARC_HIP(c.sharcLogScatter.reserve(n));
-                SHARC_HIP(c.sharcLog.reserve(n));
-                SHARC_HIP(hipMemsetAsync(c.sharcLog.data(), 0, sizeof(PtSHARCPathVertex) * n, c.stream));
-                SHARC_HIP(hipMemsetAsync(c.sharcLogScatter.data(), 0, sizeof(PtSHARCPathScatter) * n, c.stream));
+                API_HIP(&c, c.sharcLogScatter.reserve(n));
+                API_HIP(&c, c.sharcLog.reserve(n));
+                API_HIP(&c, hipMemsetAsync(c.sharcLog.data(), 0, sizeof(PtSHARCPathVertex) * n, c.stream));
+                API_HIP(&c, hipMemsetAsync(c.sharcLogScatter.data(), 0, sizeof(PtSHARCPathScatter) * n, c.stream));
                 a.log = c.sharcLog.data(); a.logScatter = c.sharcLogScatter.data(); a.logBounces = gs.Bounces + 1u;
                 c.sharcLogPaths = uw * uh; c.sharcLogBounces = gs.Bounces + 1u;
             }
@@ -411,23 +399,20 @@ int pt_raytrace_render_sharc(PtContext* ctx, const PtTextures* tx)
             FrameConstants fc; fc.cam = c.camera; fc.sd = c.sceneData; fc.gs = c.settings;
             k_sharc_set_constants<<<1, 256, 0, c.stream>>>(fc, c.frameConstants.data());
             const dim3 grid((uw + 15u) / 16u, (uh + 15u) / 16u);
-            #define PT_SU(T, L) k_sharc_update<T, L><<<grid, 256, 0, c.stream>>>(sv, fv, c.frameConstants.data(), *tx, c.scene.blob, a, c.counters.data())
-            if (c.heapHasTextures) { if (log) PT_SU(true, true); else PT_SU(true, false); }
-            else { if (log) PT_SU(false, true); else PT_SU(false, false); }
-            #undef PT_SU
-            SHARC_HIP(hipGetLastError());
+            with_flags([&](auto T, auto L) {
+                k_sharc_update<T(), L()><<<grid, 256, 0, c.stream>>>(sv, fv, c.frameConstants.data(), *tx, c.scene.blob, a, c.counters.data());
+            }, c.heapHasTextures, log);
+            API_HIP(&c, hipGetLastError());
         }
         k_sharc_resolve<<<(c.sharcCapacity + 255u) / 256u, 256, 0, c.stream>>>(c.sharcKeys.data(), c.sharcVoxels[cur].data(), c.sharcVoxels[prev].data(), c.sharcCapacity,
                                                                                  ss.AccumulationFrames, std::min(std::max(ss.MaxStaleFrames, 8u), 255u), ss.IsAntiFireflyEnabled);
-        SHARC_HIP(hipGetLastError());
+        API_HIP(&c, hipGetLastError());
         resolved = cur;
     }
     k_sharc_set_view<<<1, 64, 0, c.stream>>>(sharc_view(c, resolved), c.sharcView.data());
-    SHARC_HIP(hipGetLastError());
-    c.sharcQuery = true;
-    const hipError_t e = launch_raytrace(c, sv, fv, *tx);
-    c.sharcQuery = false;
-    if (e != hipSuccess) return sharc_fail_hip(c, e, "SHARC query frame");
+    API_HIP(&c, hipGetLastError());
+    const hipError_t e = launch_raytrace(c, sv, fv, *tx, true);
+    if (e != hipSuccess) return fail_hip(&c, e, "SHARC query frame");
     if (!skip) c.sharcParity = prev;                         // the buffers swap: this frame's resolved cache is the next frame's history
     return PT_OK;
 }
@@ -436,13 +421,13 @@ int pt_sharc_download(PtContext* ctx, PtSHARCEntry* host_dst, uint32_t capacity,
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
-    SHARC_ARG(out_count && (host_dst || capacity == 0), "out_count / host_dst is NULL");
-    if (!c.sharcCapacity) return sharc_fail(c, PT_ERROR_NOT_READY, "no SHARC cache: call pt_sharc_configure first");
-    SHARC_HIP(hipSetDevice(c.device));
-    SHARC_HIP(hipStreamSynchronize(c.stream));
+    API_ARG(&c, out_count && (host_dst || capacity == 0), "out_count / host_dst is NULL");
+    if (!c.sharcCapacity) return fail(&c, PT_ERROR_NOT_READY, "no SHARC cache: call pt_sharc_configure first");
+    API_HIP(&c, hipSetDevice(c.device));
+    API_HIP(&c, hipStreamSynchronize(c.stream));
     std::vector<unsigned long long> keys(c.sharcCapacity); std::vector<uint4> vox(c.sharcCapacity);
-    SHARC_HIP(hipMemcpy(keys.data(), c.sharcKeys.data(), sizeof(unsigned long long) * keys.size(), hipMemcpyDeviceToHost));
-    SHARC_HIP(hipMemcpy(vox.data(), c.sharcVoxels[c.sharcParity ^ 1u].data(), sizeof(uint4) * vox.size(), hipMemcpyDeviceToHost));   // the resolved buffer: the last render's, now the history
+    API_HIP(&c, hipMemcpy(keys.data(), c.sharcKeys.data(), sizeof(unsigned long long) * keys.size(), hipMemcpyDeviceToHost));
+    API_HIP(&c, hipMemcpy(vox.data(), c.sharcVoxels[c.sharcParity ^ 1u].data(), sizeof(uint4) * vox.size(), hipMemcpyDeviceToHost));   // the resolved buffer: the last render's, now the history
     uint32_t n = 0;
     for (uint32_t i = 0; i < c.sharcCapacity; i++) {
         if (!keys[i]) continue;
@@ -457,21 +442,21 @@ int pt_sharc_debug_keys(PtContext* ctx, const float* positions, const float* nor
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
-    SHARC_ARG(n == 0 || (positions && normals && keys && levels && voxel_sizes), "an array is NULL");
-    if (!c.haveSharcSettings) return sharc_fail(c, PT_ERROR_NOT_READY, "call pt_sharc_set_constants first");
-    if (!c.haveCamera) return sharc_fail(c, PT_ERROR_NOT_READY, "camera not set");
+    API_ARG(&c, n == 0 || (positions && normals && keys && levels && voxel_sizes), "an array is NULL");
+    if (!c.haveSharcSettings) return fail(&c, PT_ERROR_NOT_READY, "call pt_sharc_set_constants first");
+    if (!c.haveCamera) return fail(&c, PT_ERROR_NOT_READY, "camera not set");
     if (!n) return PT_OK;
-    SHARC_HIP(hipSetDevice(c.device));
+    API_HIP(&c, hipSetDevice(c.device));
     DeviceBuffer<float> in; DeviceBuffer<unsigned long long> dk; DeviceBuffer<uint32_t> dl; DeviceBuffer<float> dv;
-    SHARC_HIP(in.reserve(6 * (size_t)n)); SHARC_HIP(dk.reserve(n)); SHARC_HIP(dl.reserve(n)); SHARC_HIP(dv.reserve(n));
-    SHARC_HIP(hipMemcpyAsync(in.data(), positions, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c.stream));
-    SHARC_HIP(hipMemcpyAsync(in.data() + 3 * (size_t)n, normals, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c.stream));
+    API_HIP(&c, in.reserve(6 * (size_t)n)); API_HIP(&c, dk.reserve(n)); API_HIP(&c, dl.reserve(n)); API_HIP(&c, dv.reserve(n));
+    API_HIP(&c, hipMemcpyAsync(in.data(), positions, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c.stream));
+    API_HIP(&c, hipMemcpyAsync(in.data() + 3 * (size_t)n, normals, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c.stream));
     k_sharc_debug_keys<<<(n + 255u) / 256u, 256, 0, c.stream>>>(c.camera, c.sharcSettings.SceneScale, in.data(), in.data() + 3 * (size_t)n, n, dk.data(), dl.data(), dv.data());
-    SHARC_HIP(hipGetLastError());
-    SHARC_HIP(hipMemcpyAsync(keys, dk.data(), sizeof(uint64_t) * n, hipMemcpyDeviceToHost, c.stream));
-    SHARC_HIP(hipMemcpyAsync(levels, dl.data(), sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c.stream));
-    SHARC_HIP(hipMemcpyAsync(voxel_sizes, dv.data(), sizeof(float) * n, hipMemcpyDeviceToHost, c.stream));
-    SHARC_HIP(hipStreamSynchronize(c.stream));
+    API_HIP(&c, hipGetLastError());
+    API_HIP(&c, hipMemcpyAsync(keys, dk.data(), sizeof(uint64_t) * n, hipMemcpyDeviceToHost, c.stream));
+    API_HIP(&c, hipMemcpyAsync(levels, dl.data(), sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c.stream));
+    API_HIP(&c, hipMemcpyAsync(voxel_sizes, dv.data(), sizeof(float) * n, hipMemcpyDeviceToHost, c.stream));
+    API_HIP(&c, hipStreamSynchronize(c.stream));
     return PT_OK;
 }
 
@@ -480,23 +465,23 @@ int pt_sharc_debug_query(PtContext* ctx, const float* positions, const float* no
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
-    SHARC_ARG(n == 0 || (positions && normals && distances && previous_roughness && results), "an array is NULL");
-    if (!c.sharcCapacity) return sharc_fail(c, PT_ERROR_NOT_READY, "no SHARC cache: call pt_sharc_configure first");
-    if (!c.haveSharcSettings) return sharc_fail(c, PT_ERROR_NOT_READY, "call pt_sharc_set_constants first");
-    if (!c.haveCamera) return sharc_fail(c, PT_ERROR_NOT_READY, "camera not set");
+    API_ARG(&c, n == 0 || (positions && normals && distances && previous_roughness && results), "an array is NULL");
+    if (!c.sharcCapacity) return fail(&c, PT_ERROR_NOT_READY, "no SHARC cache: call pt_sharc_configure first");
+    if (!c.haveSharcSettings) return fail(&c, PT_ERROR_NOT_READY, "call pt_sharc_set_constants first");
+    if (!c.haveCamera) return fail(&c, PT_ERROR_NOT_READY, "camera not set");
     if (!n) return PT_OK;
-    SHARC_HIP(hipSetDevice(c.device));
+    API_HIP(&c, hipSetDevice(c.device));
     DeviceBuffer<float> in; DeviceBuffer<PtSHARCQueryResult> out;
-    SHARC_HIP(in.reserve(8 * (size_t)n)); SHARC_HIP(out.reserve(n));
+    API_HIP(&c, in.reserve(8 * (size_t)n)); API_HIP(&c, out.reserve(n));
     float* d = in.data();
-    SHARC_HIP(hipMemcpyAsync(d, positions, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c.stream));
-    SHARC_HIP(hipMemcpyAsync(d + 3 * (size_t)n, normals, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c.stream));
-    SHARC_HIP(hipMemcpyAsync(d + 6 * (size_t)n, distances, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c.stream));
-    SHARC_HIP(hipMemcpyAsync(d + 7 * (size_t)n, previous_roughness, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c.stream));
+    API_HIP(&c, hipMemcpyAsync(d, positions, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c.stream));
+    API_HIP(&c, hipMemcpyAsync(d + 3 * (size_t)n, normals, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c.stream));
+    API_HIP(&c, hipMemcpyAsync(d + 6 * (size_t)n, distances, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c.stream));
+    API_HIP(&c, hipMemcpyAsync(d + 7 * (size_t)n, previous_roughness, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c.stream));
     k_sharc_debug_query<<<(n + 255u) / 256u, 256, 0, c.stream>>>(sharc_view(c, c.sharcParity ^ 1u), d, d + 3 * (size_t)n, d + 6 * (size_t)n, d + 7 * (size_t)n, n, out.data());
-    SHARC_HIP(hipGetLastError());
-    SHARC_HIP(hipMemcpyAsync(results, out.data(), sizeof(PtSHARCQueryResult) * (size_t)n, hipMemcpyDeviceToHost, c.stream));
-    SHARC_HIP(hipStreamSynchronize(c.stream));
+    API_HIP(&c, hipGetLastError());
+    API_HIP(&c, hipMemcpyAsync(results, out.data(), sizeof(PtSHARCQueryResult) * (size_t)n, hipMemcpyDeviceToHost, c.stream));
+    API_HIP(&c, hipStreamSynchronize(c.stream));
     return PT_OK;
 }
 
@@ -504,26 +489,16 @@ int pt_sharc_download_update_paths(PtContext* ctx, PtSHARCPathVertex* host_dst, 
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
-    SHARC_ARG(out_paths && out_bounces && (host_dst || capacity == 0), "out_paths / out_bounces / host_dst is NULL");
-    SHARC_HIP(hipSetDevice(c.device));
-    SHARC_HIP(hipStreamSynchronize(c.stream));
-    *out_paths = c.sharcLogPaths; *out_bounces = c.sharcLogBounces;
-    const size_t n = std::min((size_t)capacity, (size_t)c.sharcLogPaths * c.sharcLogBounces);
-    if (n) SHARC_HIP(hipMemcpy(host_dst, c.sharcLog.data(), sizeof(PtSHARCPathVertex) * n, hipMemcpyDeviceToHost));
-    return PT_OK;
+    API_ARG(&c, out_paths && out_bounces && (host_dst || capacity == 0), "out_paths / out_bounces / host_dst is NULL");
+    return download_counted(c, c.sharcLog.data(), c.sharcLogPaths, c.sharcLogBounces, host_dst, capacity, out_paths, out_bounces);
 }
 
 int pt_sharc_download_update_scatter(PtContext* ctx, PtSHARCPathScatter* host_dst, uint32_t capacity, uint32_t* out_paths, uint32_t* out_bounces)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
-    SHARC_ARG(out_paths && out_bounces && (host_dst || capacity == 0), "out_paths / out_bounces / host_dst is NULL");
-    SHARC_HIP(hipSetDevice(c.device));
-    SHARC_HIP(hipStreamSynchronize(c.stream));
-    *out_paths = c.sharcLogPaths; *out_bounces = c.sharcLogBounces;
-    const size_t n = std::min((size_t)capacity, (size_t)c.sharcLogPaths * c.sharcLogBounces);
-    if (n) SHARC_HIP(hipMemcpy(host_dst, c.sharcLogScatter.data(), sizeof(PtSHARCPathScatter) * n, hipMemcpyDeviceToHost));
-    return PT_OK;
+    API_ARG(&c, out_paths && out_bounces && (host_dst || capacity == 0), "out_paths / out_bounces / host_dst is NULL");
+    return download_counted(c, c.sharcLogScatter.data(), c.sharcLogPaths, c.sharcLogBounces, host_dst, capacity, out_paths, out_bounces);
 }
 
 } // extern "C"

@@ -264,35 +264,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 }
 
 
-hipError_t launch_shade(Context& c, const SceneView& sv, const FrameView& fv, const PtTextures& tx, const PathQueue& qin, const PathQueue& qout, float2* aux,
-                        uint32_t segCap, const uint32_t* countIn, uint32_t* countOut, uint32_t grid, hipStream_t stream, uint32_t sqBase, uint32_t sqCount)
+// the shading half of round `round`: reads queue round & 1 and its counters, writes the other queue and the next round's counters
+hipError_t launch_shade(Context& c, const FramePlan& p, const SceneView& sv, const FrameView& fv, const PtTextures& tx, uint32_t round, uint32_t grid, hipStream_t stream,
+                        uint32_t sqBase, uint32_t sqCount)
 {
-    const bool rec = normal_records_usable(c);
-    const uint4* recA = rec ? c.shadeRecA.data() : nullptr; const uint32_t* recB = rec ? c.shadeRecB.data() : nullptr;
-    // the queues alternate with the rounds, and so do their previousRoughness arrays (SHARC query)
-    const int qi = qin.s0 == c.queue[0].s0 ? 0 : 1;
-    #define PT_SHADE(T, D) do { if (c.sharcQuery) k_shade<T, D, true><<<grid, 256, 0, stream>>>(sv, fv, c.frameConstants.data(), tx, qin, qout, aux, segCap, countIn, countOut, c.primaryRecords.data(), c.scene.blob, recA, recB, c.sqShift, sqBase, sqCount, c.sharcView.data(), c.sharcRough[qi].data(), c.sharcRough[qi ^ 1].data()); \
-                                  else k_shade<T, D, false><<<grid, 256, 0, stream>>>(sv, fv, c.frameConstants.data(), tx, qin, qout, aux, segCap, countIn, countOut, c.primaryRecords.data(), c.scene.blob, recA, recB, c.sqShift, sqBase, sqCount); } while (0)
-    if (c.settings.IsDIEnabled) { if (c.heapHasTextures) PT_SHADE(true, true); else PT_SHADE(false, true); }
-    else { if (c.heapHasTextures) PT_SHADE(true, false); else PT_SHADE(false, false); }
-    #undef PT_SHADE
+    const uint4* recA = p.recordsUsable ? c.shadeRecA.data() : nullptr; const uint32_t* recB = p.recordsUsable ? c.shadeRecB.data() : nullptr;
+    const uint32_t qi = round & 1u;                             // the queues alternate with the rounds, and so do their previousRoughness arrays (SHARC query)
+    const uint32_t* countIn = &c.queueCounts.data()[round * p.cstride()]; uint32_t* countOut = &c.queueCounts.data()[(round + 1u) * p.cstride()];
+    with_flags([&](auto D, auto T, auto S) {
+        k_shade<T(), D(), S()><<<grid, 256, 0, stream>>>(sv, fv, c.frameConstants.data(), tx, c.queue[qi], c.queue[qi ^ 1u], p.aux, p.segCap, countIn, countOut, c.primaryRecords.data(), c.scene.blob,
+                                                       recA, recB, p.sqShift, sqBase, sqCount, S() ? c.sharcView.data() : nullptr, S() ? c.sharcRough[qi].data() : nullptr, S() ? c.sharcRough[qi ^ 1u].data() : nullptr);
+    }, p.di, p.textured, p.sharc);
     return hipGetLastError();
 }
 
-hipError_t launch_extend_stream(Context& c, const AlphaContext& ac, const PathQueue& q, uint32_t segCap, const uint32_t* count, uint32_t* cursor,
-                                uint32_t grid, bool stats, bool writeT, hipStream_t stream, uint32_t sqBase, uint32_t sqCount)
+// the streaming traversal of the rays round `round` emitted (queue (round + 1) & 1, the next round's counters and cursor)
+hipError_t launch_extend_stream(Context& c, const FramePlan& p, const AlphaContext& ac, uint32_t round, hipStream_t stream, uint32_t sqBase, uint32_t sqCount)
 {
     // Fewer, longer-lived waves than the other kernels: a wave only keeps its lanes busy if it refills them many times, and with
     // 8192 waves a 600 k-ray round gives each wave one batch of 64 (lane use then is mean / longest walk of the batch). Alone on
     // the GPU 1024 blocks are best (C3 1.42 -> 1.44 Grays/s); with other frames in flight on other streams, which fill the SIMD
     // slots a small grid leaves, 512 (C3 2.06 -> 2.22, C5 1.62 -> 1.89; 256: 2.02 / 1.80).
     // (a chain of the frame gets its share of that grid: whole blocks per sub-queue)
-    const uint32_t nsq = 1u << c.sqShift;
-    const uint32_t whole = std::max(nsq, std::min(grid, c.framesInFlight > 1 ? kStreamGridShared : kStreamGridAlone));
+    const uint32_t nsq = p.nsq();
+    const uint32_t whole = std::max(nsq, std::min(p.grid, c.framesInFlight > 1 ? kStreamGridShared : kStreamGridAlone));
     const uint32_t sgrid = std::max(1u, whole / nsq) * sqCount;
-    #define PT_XS(S, W) k_extend_stream<S, W><<<sgrid, 256, kStreamLdsStack, stream>>>(c.scene.blob, ac, q, segCap, count, cursor, c.counters.data(), sqBase, sqCount)
-    if (stats) { if (writeT) PT_XS(true, true); else PT_XS(true, false); } else { if (writeT) PT_XS(false, true); else PT_XS(false, false); }
-    #undef PT_XS
+    uint32_t* count = &c.queueCounts.data()[(round + 1u) * p.cstride()];
+    with_flags([&](auto S, auto W) {
+        k_extend_stream<S(), W()><<<sgrid, 256, kStreamLdsStack, stream>>>(c.scene.blob, ac, c.queue[(round + 1u) & 1u], p.segCap, count, count + 2u * nsq, c.counters.data(), sqBase, sqCount);
+    }, p.stats, p.writeT);
     return hipGetLastError();
 }
 

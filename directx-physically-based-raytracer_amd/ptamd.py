@@ -348,6 +348,18 @@ def to_device(arr, device):
     return torch.from_numpy(raw.copy()).to(device)
 
 
+def _download_counted(ctx, fn, dtype, *lead, counts=1):
+    """The two calls of a counted download (pt_*_download_*): ask for the counts, then fetch that many records. The result has one axis
+    per count. lead: the arguments between the context and the destination."""
+    n = [C.c_uint32(0) for _ in range(counts)]
+    refs = [C.byref(v) for v in n]
+    ctx.check(fn(ctx.handle, *lead, None, 0, *refs))
+    out = np.zeros(tuple(v.value for v in n), dtype)
+    if out.size:
+        ctx.check(fn(ctx.handle, *lead, C.c_void_p(out.ctypes.data), out.size, *refs))
+    return out
+
+
 class SharedScene:
     """A second context's view of a Scene built on another context of the same GPU (pt_share_scene): frames in flight on separate
     streams render one copy of the scene. Holds a reference to the owning Scene so that it outlives the view."""
@@ -647,21 +659,11 @@ class DirectLighting:
     def download_presampled(self, which):
         """which = 0: the Power_RIS tiles (128 x 1024, tile-major), 1: the ReGIR cells (4096 x 512, cell-major, x fastest) of the last
         Render (numpy layouts.DI_PRESAMPLED_LIGHT; empty when that render did not fill them)."""
-        n = C.c_uint32(0)
-        self.ctx.check(self.ctx.lib.pt_di_download_presampled(self.ctx.handle, which, None, 0, C.byref(n)))
-        out = np.zeros(n.value, L.DI_PRESAMPLED_LIGHT)
-        if n.value:
-            self.ctx.check(self.ctx.lib.pt_di_download_presampled(self.ctx.handle, which, C.c_void_p(out.ctypes.data), n.value, C.byref(n)))
-        return out
+        return _download_counted(self.ctx, self.ctx.lib.pt_di_download_presampled, L.DI_PRESAMPLED_LIGHT, which)
 
     def download_reservoirs(self):
         """The final reservoirs of the last Render (numpy layouts.DI_RESERVOIR, row-major pixels; empty without reuse)."""
-        n = C.c_uint32(0)
-        self.ctx.check(self.ctx.lib.pt_di_download_reservoirs(self.ctx.handle, None, 0, C.byref(n)))
-        out = np.zeros(n.value, L.DI_RESERVOIR)
-        if n.value:
-            self.ctx.check(self.ctx.lib.pt_di_download_reservoirs(self.ctx.handle, C.c_void_p(out.ctypes.data), n.value, C.byref(n)))
-        return out
+        return _download_counted(self.ctx, self.ctx.lib.pt_di_download_reservoirs, L.DI_RESERVOIR)
 
     def light_count(self):
         n = C.c_uint32(0)
@@ -670,12 +672,7 @@ class DirectLighting:
 
     def download_lights(self):
         """The light records of the last Render (numpy layouts.TRIANGLE_LIGHT, list order)."""
-        n = C.c_uint32(0)
-        self.ctx.check(self.ctx.lib.pt_di_download_lights(self.ctx.handle, None, 0, C.byref(n)))
-        out = np.zeros(n.value, L.TRIANGLE_LIGHT)
-        if n.value:
-            self.ctx.check(self.ctx.lib.pt_di_download_lights(self.ctx.handle, C.c_void_p(out.ctypes.data), n.value, C.byref(n)))
-        return out
+        return _download_counted(self.ctx, self.ctx.lib.pt_di_download_lights, L.TRIANGLE_LIGHT)
 
 
 class PostProcessing:
@@ -767,22 +764,11 @@ class SHARC:
 
     def download_update_paths(self):
         """The vertex log of the last update pass rendered with DEBUG_SHARC_LOG_PATHS: (paths, bounces) of layouts.SHARC_PATH_VERTEX."""
-        n, b = C.c_uint32(0), C.c_uint32(0)
-        self.ctx.check(self.ctx.lib.pt_sharc_download_update_paths(self.ctx.handle, None, 0, C.byref(n), C.byref(b)))
-        out = np.zeros((n.value, b.value), L.SHARC_PATH_VERTEX)
-        if out.size:
-            self.ctx.check(self.ctx.lib.pt_sharc_download_update_paths(self.ctx.handle, C.c_void_p(out.ctypes.data), out.size, C.byref(n), C.byref(b)))
-        return out
-
+        return _download_counted(self.ctx, self.ctx.lib.pt_sharc_download_update_paths, L.SHARC_PATH_VERTEX, counts=2)
 
     def download_update_scatter(self):
         """The BSDF steps of the same log: (paths, bounces) of layouts.SHARC_PATH_SCATTER."""
-        n, b = C.c_uint32(0), C.c_uint32(0)
-        self.ctx.check(self.ctx.lib.pt_sharc_download_update_scatter(self.ctx.handle, None, 0, C.byref(n), C.byref(b)))
-        out = np.zeros((n.value, b.value), L.SHARC_PATH_SCATTER)
-        if out.size:
-            self.ctx.check(self.ctx.lib.pt_sharc_download_update_scatter(self.ctx.handle, C.c_void_p(out.ctypes.data), out.size, C.byref(n), C.byref(b)))
-        return out
+        return _download_counted(self.ctx, self.ctx.lib.pt_sharc_download_update_scatter, L.SHARC_PATH_SCATTER, counts=2)
 
 
 class Renderer:
