@@ -103,6 +103,13 @@ PT_DEV float rng_float(uint32_t& st)
 // ---- packing (DXGI typed-store conversion rules, D3D11.3 functional spec 3.2.3) -----------
 PT_DEV uint16_t f32_to_f16(float f)          // round-to-nearest-even, overflow -> inf, NaN kept
 {
+    // The conversion takes the fp32 value AS ROUNDED. Left to itself the compiler folds a multiply (or a mad()) whose result comes
+    // straight here into v_fma_mixlo_f16, which rounds the exact product ONCE, to half: where the fp32 rounding lands on a half-way
+    // point of the half grid the two differ by one half ulp (a G-buffer motion vector against the oracle, one pixel in some ten
+    // thousand). The empty statement pins the value to a register first; it emits nothing.
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(f));
+#endif
     _Float16 h = (_Float16)f;                // v_cvt_f16_f32, RNE
     return __builtin_bit_cast(uint16_t, h);
 }

@@ -476,15 +476,14 @@ def bar_pose(angle_deg, lift=0.0):
     return np.stack([j0, j1]).astype(np.float32)
 
 
-def dynamic_scene(aspect=16 / 9):
+def dynamic_scene(aspect=16 / 9, meshes=None):
     """floor + light + a skinned bar: the smallest scene that exercises skinning, BLAS update, TLAS rebuild and
-    per-vertex motion vectors (SceneData.IsStatic = 0)."""
+    per-vertex motion vectors (SceneData.IsStatic = 0). meshes: the skinned meshes of the third mesh node instead of the bar."""
     white = (0.73, 0.73, 0.73)
-    bar = skinned_bar()
     nodes = [MeshNode([quad_mesh((-2, 0, -2), (-2, 0, 2), (2, 0, 2), (2, 0, -2), (0, 1, 0), material(white))]),
              MeshNode([quad_mesh((-0.5, 0, -0.5), (0.5, 0, -0.5), (0.5, 0, 0.5), (-0.5, 0, 0.5), (0, -1, 0),
                                  material((0.8, 0.8, 0.8), emissive=(1, 1, 1), strength=10.0))]),
-             MeshNode([bar])]
+             MeshNode(list(meshes) if meshes is not None else [skinned_bar()])]
     objects = [RenderObject(0, trs()), RenderObject(1, trs((0, 2.2, 0))), RenderObject(2, trs((0.1, 0, 0.2), 20.0, (1, 1.2, 1)))]
     cam = make_camera((0, 0.9, -2.2), forward=(0, -0.1, 1), hfov_deg=70.0, aspect=aspect)
     return Scene(nodes, objects, cam, make_scene_data((0.05, 0.06, 0.08, 1), is_static=False), name="dynamic").finalize()

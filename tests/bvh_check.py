@@ -203,3 +203,94 @@ def reach(layout, buf, o, d, tmin=0.0, tmax=np.inf, leaf_tris_rule=lambda n: 2 i
         tc = int(it["triCount"])
         res.append((x, items(int(it["nodeBase"]), tc <= leaf_tris_rule(tc), tc, ro, rd)))
     return res
+
+
+# ---------------------------------------------------------------------------------------------
+# Triangle packets against the vertex data they were made from (what a refit rewrites besides the boxes), and a form of a
+# bottom level that does not depend on where the builder happened to put its nodes.
+# ---------------------------------------------------------------------------------------------
+def check_packets(layout, buf, geometries):
+    """geometries[i]: the geometries of instance i's bottom level as a list of (positions [nv, 3] float32, indices) in API order, as they
+    are on the device now -- or None to leave that instance out. Every packet (geom, prim) of the instance must hold exactly the three
+    positions positions[indices[3 prim + k]] of that geometry, bit for bit, and every (geom, prim) must occur exactly once; the packet's
+    row of vertex indices (the section behind the packets, in the same order: what a hit fetches its vertex attributes through) must be
+    indices[3 prim + k]. Raises AssertionError listing the problems found."""
+    inst, nodes, tris, order = split(layout, buf)
+    rows = buf[layout.TriangleOffset16 * 16 + layout.TriangleCount * 48:][:layout.TriangleCount * 16].view("<u4").reshape(-1, 4)
+    problems = []
+    assert len(geometries) == len(inst), f"{len(geometries)} geometry lists for {len(inst)} instances"
+    for i, geoms in enumerate(geometries):
+        if geoms is None:
+            continue
+        tb, tc = int(inst[i]["triBase"]), int(inst[i]["triCount"])
+        counts = [np.asarray(ix).size // 3 for _, ix in geoms]
+        if tc != sum(counts):
+            problems.append(f"instance {i}: {tc} packets for {sum(counts)} triangles"); continue
+        t = tris[tb:tb + tc]
+        g, p = t["geom"].astype(np.int64), t["prim"].astype(np.int64)
+        if (g >= len(geoms)).any():
+            problems.append(f"instance {i}: a packet names geometry {int(g.max())} of {len(geoms)}"); continue
+        if (p >= np.asarray(counts)[g]).any():
+            problems.append(f"instance {i}: a packet names a primitive beyond its geometry's count"); continue
+        if len(np.unique(np.stack([g, p], -1), axis=0)) != tc:
+            problems.append(f"instance {i}: a (geometry, primitive) pair occurs more than once (so another is missing)")
+        got = np.stack([t["v0"], t["v1"], t["v2"]], 1).view(np.uint32)                     # [tc, 3, 3]
+        for k, (pos, ix) in enumerate(geoms):
+            sel = np.nonzero(g == k)[0]
+            if not len(sel):
+                continue
+            vi = np.asarray(ix).reshape(-1).astype(np.int64)[:3 * counts[k]].reshape(-1, 3)[p[sel]]
+            want = np.ascontiguousarray(np.asarray(pos, np.float32)[vi]).view(np.uint32)   # [n, 3, 3]
+            stale = np.nonzero((rows[tb:tb + tc][sel][:, :3] != vi).any(1))[0]
+            for b in stale[:3]:
+                problems.append(f"instance {i}: packet {int(sel[b])} (geometry {k}, primitive {int(p[sel[b]])}) carries the vertex indices {rows[tb + sel[b]][:3].tolist()}, not {vi[b].tolist()}")
+            bad = np.nonzero((got[sel] != want).any((1, 2)))[0]
+            for b in bad[:3]:
+                problems.append(f"instance {i}: packet {int(sel[b])} (geometry {k}, primitive {int(p[sel[b]])}) does not hold that triangle's vertices")
+            if len(bad) > 3:
+                problems.append(f"instance {i}: ... and {len(bad) - 3} more packets of geometry {k}")
+    assert not problems, "\n".join(problems[:20])
+
+
+def canonical_blas(layout, buf, instance, leaf_tris_rule):
+    """(node records, packets) of the bottom level of `instance` in depth-first slot order, with the two fields that say where the builder
+    put a node's children and items (childBase, triBase: allocation order, not structure) zeroed. Two bottom levels are the same tree
+    over the same triangles exactly when these are equal field for field."""
+    inst, nodes, tris, order = split(layout, buf)
+    it = inst[instance]
+    nb, tb, tc = int(it["nodeBase"]), int(it["triBase"]), int(it["triCount"])
+    if tc <= leaf_tris_rule(tc):
+        return nodes[:0].copy(), tris[tb:tb + tc].copy()
+    node_order, tri_order, stack = [], [], [0]
+    while stack:
+        idx = stack.pop()
+        assert len(node_order) < layout.NodeCount, "the node references do not form a tree"
+        n = nodes[nb + idx]
+        node_order.append(nb + idx)
+        rank, kids = 0, []
+        for s in range(8):
+            m = int(n["meta"][s])
+            if m == 0:
+                continue
+            if (m & 0x1F) >= 24:
+                kids.append(int(n["childBase"]) + rank); rank += 1
+            else:
+                cnt = {1: 1, 3: 2, 7: 3}[m >> 5]
+                first = tb + int(n["triBase"]) + (m & 0x1F)
+                tri_order.extend(range(first, first + cnt))
+        stack.extend(reversed(kids))
+    cn = nodes[node_order].copy()
+    cn["childBase"] = 0; cn["triBase"] = 0
+    return cn, tris[tri_order].copy()
+
+
+def assert_records_equal(a, b, what):
+    """field-for-field equality of two structured arrays (bit patterns: -0.0 and NaN payloads count)"""
+    assert a.dtype == b.dtype and a.shape == b.shape, f"{what}: {a.shape} records against {b.shape}"
+    for name in a.dtype.names:
+        x, y = np.ascontiguousarray(a[name]), np.ascontiguousarray(b[name])
+        if x.dtype.kind == "f":
+            x, y = x.view(np.uint32), y.view(np.uint32)
+        if not np.array_equal(x, y):
+            rows = np.nonzero((x != y).reshape(len(x), -1).any(1))[0]
+            raise AssertionError(f"{what}: field {name} differs in {len(rows)} of {len(x)} records, first at {int(rows[0])}: {a[name][rows[0]]} against {b[name][rows[0]]}")
