@@ -898,6 +898,19 @@ int pt_debug_trace_ray(PtContext* ctx, const PtRayDesc* host_ray, uint32_t* host
     return PT_OK;
 }
 
+int pt_debug_trace_closest(PtContext* ctx, const PtRayDesc* device_rays, uint32_t count, PtClosestHit* device_hits)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    API_ARG(&c, count == 0 || (device_rays && device_hits), "ray / hit buffer is NULL");
+    API_HIP(&c, hipSetDevice(c.device));
+    SceneView sv; FrameView fv; memset(&sv, 0, sizeof sv); memset(&fv, 0, sizeof fv);
+    int s = make_views(c, 1, 1, sv, fv, false);                    // only the scene half of the views is needed
+    if (s != PT_OK) return s;
+    API_HIP(&c, launch_debug_closest(c, sv, device_rays, count, device_hits));
+    return PT_OK;
+}
+
 int pt_set_debug_flags(PtContext* ctx, uint32_t flags)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;

@@ -218,7 +218,7 @@ __device__ __forceinline__ void grow_by_transformed_box(const float* M, const fl
 constexpr uint32_t kExactBoxTriangles = 1024;
 // The 64 lanes of a wave work on ONE instance: the triangles of the exact path are dealt to the lanes and the result reduced; the
 // node path is evaluated by every lane alike (a handful of boxes). All lanes return the same box.
-__device__ void instance_world_box(const InstanceRecord& ir, const float* b, float lo[3], float hi[3])
+__device__ void instance_world_bound(const InstanceRecord& ir, const float* b, float lo[3], float hi[3])
 {
     for (int a = 0; a < 3; a++) { lo[a] = INFINITY; hi[a] = -INFINITY; }
     if (!(b[0] <= b[3])) return;                                             // empty BLAS
@@ -270,6 +270,32 @@ __device__ void instance_world_box(const InstanceRecord& ir, const float* b, flo
     }
     for (int a = 0; a < 3; a++) { lo[a] = fmaxf(lo[a], tlo[a]); hi[a] = fminf(hi[a], thi[a]); }
     if (!(lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2])) for (int a = 0; a < 3; a++) { lo[a] = INFINITY; hi[a] = -INFINITY; }
+}
+
+// Every bound above is M x + M y + M z + t evaluated in fp32, and a ray meets the instance through worldToObject, evaluated in fp32 as well.
+// Both round by a few 2^-24 of their LARGEST term, not of their result: where the translation is large against the object (geometry
+// far from its own origin under a large scale: |t| = 4e6 for a mesh at 4096 scaled by 1e3) a transformed vertex lands up to |t| 2^-22
+// away from where the exact transform puts it, and the object-space ray as far from the world-space one -- more than the relative
+// padding of the top-level leaves (1e-5 of the WORLD coordinate) covers. So the box moves outward, per axis a, by
+//     2^-21 (sum_j |M[a][j]| (max |p_j| + |W[j][3]|) + |M[a][3]|)        p: the root box of the bottom level, W: worldToObject
+// = 8 roundings' worth: at most 4 on the way of a term of the forward sum, and 3 of the fused affine row of W on each of |W[j][3]| and
+// the ray's own term that cancels against it (brought back to world space through |M|). The part of W's error that grows with the ray's
+// origin is the box tests' own business (their slack is relative to the ray). For a transform near the identity this is 5e-7 of the
+// coordinates: nothing next to the leaves' padding.
+__device__ void instance_world_box(const InstanceRecord& ir, const float* b, float lo[3], float hi[3])
+{
+    instance_world_bound(ir, b, lo, hi);
+    if (!(lo[0] <= hi[0])) return;
+    const float* M = ir.objectToWorld; const float* W = ir.worldToObject;
+    for (int a = 0; a < 3; a++) {
+        float s = fabsf(M[4 * a + 3]);
+        for (int j = 0; j < 3; j++) {
+            const float w = fabsf(W[4 * j + 3]);                               // a singular transform has no inverse: W is inf / NaN, and no
+            s += fabsf(M[4 * a + j]) * (fmaxf(fabsf(b[j]), fabsf(b[3 + j])) + (w < INFINITY ? w : 0.0f));   // ray comes back through it
+        }
+        const float e = s * 4.76837158e-7f;
+        if (e < INFINITY) { lo[a] -= e; hi[a] += e; }                           // (NaN fails the comparison too): the flat box stays as it was
+    }
 }
 
 // TLAS items: the world box of each instance. A wave works on one instance at a time and strides over the array; the scene bounds are

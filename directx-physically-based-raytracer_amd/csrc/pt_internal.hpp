@@ -303,6 +303,7 @@ hipError_t launch_visibility(Context& c, const SceneView& sv, const void* rays, 
 hipError_t launch_bsdf_evaluate(hipStream_t stream, const float* q, uint32_t count, float* r);
 hipError_t launch_bsdf_sample(hipStream_t stream, const float* q, uint32_t count, float* r);
 hipError_t launch_debug_trace(Context& c, const SceneView& sv, const float* ray8, uint32_t* devLog, uint32_t logCap);
+hipError_t launch_debug_closest(Context& c, const SceneView& sv, const void* rays, uint32_t count, void* hits);
 uint32_t round_objects_in_lds(const Context& c, uint32_t objectCount, bool haveShadeGeom);   // the fused round kernel's LDS tables (PtAccelStats)
 uint32_t round_records_in_lds(const Context& c, uint32_t objectCount, bool haveShadeGeom);
 inline bool normal_records_usable(const Context& c) { return c.normalsShared && c.scene.blasTable && c.scene.blasTableCount <= 65535u /* grid.y of k_capture_normals */ && c.shadeRecB && c.scene.blob.triCount && c.scene.blob.triCount <= c.shadeRecB.capacity(); }

@@ -540,6 +540,27 @@ hipError_t launch_debug_trace(Context& c, const SceneView& sv, const float* ray8
     return hipGetLastError();
 }
 
+// test / developer aid (pt_debug_trace_closest): the closest hit of each ray of a batch as a PtClosestHit record (two 16-byte halves);
+// BRUTE: every triangle of every instance instead of the walk
+template <bool BRUTE>
+__global__ __launch_bounds__(256) void k_debug_closest(AccelView av, BlobView bv, AlphaContext ac, const float4* __restrict__ rays, uint32_t count, uint4* __restrict__ out,
+                                                       DeviceCounters* counters)
+{
+    __shared__ uint2 ldsStack[kLdsStackDepth * 256];
+    uint2 spill[kStackSize - kLdsStackDepth];
+    GroupStack<kLdsStackDepth> stack; stack.init((PT_LDS_AS void*)ldsStack, spill);
+    BlobReader<false> blob; blob.p = bv.base;
+    TraceStats st; st.nodes = 0; st.tris = 0; st.overflow = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+        const float4 o = rays[2 * (size_t)i], d = rays[2 * (size_t)i + 1];
+        const Hit h = BRUTE ? trace_brute_force(av, ac, V3(o.x, o.y, o.z), V3(d.x, d.y, d.z), o.w, d.w)
+                            : trace_single<false, false, false>(blob, bv, ac, V3(o.x, o.y, o.z), V3(d.x, d.y, d.z), o.w, d.w, stack, &st, nullptr);
+        out[2 * (size_t)i] = make_uint4(__float_as_uint(h.t), __float_as_uint(h.u), __float_as_uint(h.v), h.inst);
+        out[2 * (size_t)i + 1] = make_uint4(h.geom, h.prim, h.slot, 0u);
+    }
+    if (st.overflow) atomicAdd(&counters->stackOverflows, st.overflow);
+}
+
 // scene-input validation (pt_api.hip validate_scene): every descriptor index ObjectData carries must name a heap entry of the
 // right kind. out: error member (1 Vertices, 2 Indices, 3 MotionVectors, 4 TextureMapInfo) | object | descriptor | 1 = wrong kind
 __global__ void k_validate_objects(const PtObjectData* __restrict__ objects, uint32_t count, const HeapEntry* __restrict__ heap, uint32_t heapCount, uint32_t* out,
@@ -672,6 +693,16 @@ hipError_t launch_visibility(Context& c, const SceneView& sv, const void* rays, 
 {
     if (!count) return hipSuccess;
     k_visibility<<<persistent_grid(c), 256, 0, c.stream>>>(c.scene.blob, alpha_context(sv), (const float4*)rays, count, (float4*)out, c.counters.data());
+    return hipGetLastError();
+}
+
+hipError_t launch_debug_closest(Context& c, const SceneView& sv, const void* rays, uint32_t count, void* hits)
+{
+    if (!count) return hipSuccess;
+    if (c.debugFlags & PT_DEBUG_BRUTE_FORCE)
+        k_debug_closest<true><<<persistent_grid(c), 256, 0, c.stream>>>(sv.accel, c.scene.blob, alpha_context(sv), (const float4*)rays, count, (uint4*)hits, c.counters.data());
+    else
+        k_debug_closest<false><<<persistent_grid(c), 256, 0, c.stream>>>(sv.accel, c.scene.blob, alpha_context(sv), (const float4*)rays, count, (uint4*)hits, c.counters.data());
     return hipGetLastError();
 }
 

@@ -188,8 +188,9 @@ PT_DEV uint32_t wide_node_hits(f4v n0, f4v n1, f4v n2, f4v n3, f4v n4, const Box
 // Per-ray constants of the watertight test. kz = dominant axis of the direction (c2: z, else c1: y, else x),
 // kx = kz + 1, ky = kz + 2 (mod 3). The paper additionally swaps kx and ky when d[kz] < 0 to keep the winding; that swap
 // negates U, V, W, det and T exactly (IEEE negation commutes with every operation used) and therefore changes neither the
-// hit decision nor t = T/det, u = V/det, v = W/det: it is omitted here, the results stay bit-identical to the oracle's,
-// which keeps the swap.
+// hit decision nor t = T * rcp, nor any non-zero u = V * rcp, v = W * rcp. It is omitted here. The one thing it would change is
+// the SIGN of a u or v that is exactly zero (a ray through an edge: V = x - x = +0 with or without the swap, rcp negated), so
+// the oracle omits it too (tests/test_intersection_reference.py holds both forms against each other).
 struct RaySetup { bool c1, c2; float Sx, Sy, Sz; };
 PT_DEV float sel_kz(v3 v, const RaySetup& r) { return r.c2 ? v.z : (r.c1 ? v.y : v.x); }
 PT_DEV float sel_kx(v3 v, const RaySetup& r) { return r.c2 ? v.x : (r.c1 ? v.z : v.y); }

@@ -31,7 +31,7 @@ EXPORTS = [
     "pt_post_set_constants", "pt_post_render", "pt_post_download_bloom",
     "pt_sharc_configure", "pt_sharc_set_constants", "pt_raytrace_render_sharc", "pt_sharc_reset", "pt_sharc_download",
     "pt_sharc_debug_keys", "pt_sharc_debug_query", "pt_sharc_download_update_paths", "pt_sharc_download_update_scatter",
-    "pt_set_debug_flags", "pt_debug_read_mismatch", "pt_debug_download_blob", "pt_debug_trace_ray", "pt_enable_kernel_timing", "pt_get_kernel_timing", "pt_get_round_timing",
+    "pt_set_debug_flags", "pt_debug_read_mismatch", "pt_debug_download_blob", "pt_debug_trace_ray", "pt_debug_trace_closest", "pt_enable_kernel_timing", "pt_get_kernel_timing", "pt_get_round_timing",
 ]
 
 
@@ -119,6 +119,10 @@ class BsdfSampleResult(C.Structure):
                 ("Lobe", C.c_uint32), ("Ok", C.c_uint32)]
 
 
+CLOSEST_HIT = np.dtype([("T", "<f4"), ("U", "<f4"), ("V", "<f4"), ("Instance", "<u4"), ("Geometry", "<u4"), ("Primitive", "<u4"),
+                        ("Slot", "<u4"), ("_pad", "<u4")])          # PtClosestHit, 32 B
+
+
 def load_library():
     """Load libptamd.so; fail loudly when the HIP extension has not been built."""
     global _LIB
@@ -194,6 +198,7 @@ def load_library():
         lib.pt_debug_read_mismatch.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_debug_download_blob.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         lib.pt_debug_trace_ray.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        lib.pt_debug_trace_closest.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.pt_enable_kernel_timing.argtypes = [C.c_void_p, C.c_int]
         lib.pt_get_round_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
         lib.pt_get_kernel_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
@@ -277,6 +282,7 @@ class DeviceContext:
 
     def set_debug_flags(self, flags):
         self.check(self.lib.pt_set_debug_flags(self.handle, flags))
+        self.debug_flags = flags
 
     def invalidate_object_data(self):
         """VertexDesc / MeshDescriptors of the bound ObjectData were rewritten in place: resolve and check them again at the next render."""
@@ -300,6 +306,23 @@ class DeviceContext:
         buf = np.zeros(lay.Bytes, np.uint8)
         self.check(self.lib.pt_debug_download_blob(self.handle, C.c_void_p(buf.ctypes.data), buf.nbytes, C.byref(lay)))
         return lay, buf
+
+    def trace_closest(self, rays, brute_force=False):
+        """pt_debug_trace_closest over host rays [n, 8] float32 (origin, tmin, direction, tmax): CLOSEST_HIT records. brute_force: with
+        PT_DEBUG_BRUTE_FORCE set for the call (every triangle of every instance, no box test); the flags set through set_debug_flags are
+        back in place afterwards."""
+        torch = _torch()
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        dr = torch.from_numpy(rays).to(torch.device("cuda", self.device_ordinal))
+        dh = torch.zeros(max(1, len(rays)) * 32, dtype=torch.uint8, device=dr.device)
+        before = getattr(self, "debug_flags", 0)
+        self.set_debug_flags((before | 0x2) if brute_force else (before & ~0x2))
+        try:
+            self.check(self.lib.pt_debug_trace_closest(self.handle, C.c_void_p(dr.data_ptr()), len(rays), C.c_void_p(dh.data_ptr())))
+            self.sync()
+        finally:
+            self.set_debug_flags(before)
+        return dh.cpu().numpy()[:len(rays) * 32].view(CLOSEST_HIT).copy()
 
     def accel_stats(self):
         s = AccelStats()

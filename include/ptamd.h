@@ -634,6 +634,13 @@ int  pt_debug_download_blob(PtContext* ctx, void* host_dst, uint64_t capacity_by
  * 1 enter instance a | 2 triangle b of instance a | 3 node group (a, b) about to be visited | 4 groups after the visit |
  * 5 popped (a, b) | 6 top-level state restored | 7 result (instance, triangle slot). Synchronises. */
 int  pt_debug_trace_ray(PtContext* ctx, const PtRayDesc* host_ray, uint32_t* host_log, uint32_t log_words);
+/* Test / developer aid: the closest hit of every ray of a batch, through the one-lane two-level walk -- or, while PT_DEBUG_BRUTE_FORCE is set,
+ * through every triangle of every instance with no box test in front of the triangle test. The closest-hit rule of the renderer: t in
+ * (TMin, TMax) exclusive, no face culling, ties on t to the lowest (instance, geometry, primitive). A miss has Instance = ~0u and T = TMax.
+ * U weights vertex 1, V vertex 2; Slot is the triangle packet inside its bottom level. Refused pushes are counted in StackOverflows.
+ * Enqueued on the context's stream like pt_trace_visibility. */
+typedef struct PtClosestHit { float T, U, V; uint32_t Instance, Geometry, Primitive, Slot, _pad; } PtClosestHit;   /* 32 B */
+int  pt_debug_trace_closest(PtContext* ctx, const PtRayDesc* device_rays, uint32_t count, PtClosestHit* device_hits);
 
 /* Per-kernel timing with HIP events recorded on the context stream around every extend / shade launch
  * issued after pt_enable_kernel_timing(ctx, 1); the getter synchronises and returns the sums since then. */

@@ -82,6 +82,7 @@ def lib():
         L.or_bsdf_evaluate.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.or_bsdf_sample_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.or_trace_visibility.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.or_trace_closest.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.or_skin_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.or_texture_sample.argtypes = [C.c_void_p, C.c_float, C.c_float, fp]
         L.or_cube_sample.argtypes = [C.c_void_p, fp, fp]

@@ -910,7 +910,10 @@ static void ray_setup(RayObj* r, f3 o, f3 d)
     if (fabsf(d.z) > m) { kz = 2; }
     int kx = kz + 1; if (kx == 3) kx = 0;
     int ky = kx + 1; if (ky == 3) ky = 0;
-    if (get3(d, kz) < 0.0f) { int t = kx; kx = ky; ky = t; }
+    /* The paper swaps kx and ky when d[kz] < 0 to keep the winding. The swap negates U, V, W, det and T exactly, so the hit decision,
+     * t and every non-zero u, v are the same bits with and without it -- but an edge value that is exactly 0 stays +0 (x - x = +0
+     * either way) while rcp changes sign, so u = V * rcp or v = W * rcp came out as -0 on one side and +0 on the other for a ray
+     * through an edge. The kernels never had the swap (pt_trace.hpp ray_setup); the oracle follows them, as the rule is theirs. */
     r->kx = kx; r->ky = ky; r->kz = kz;
     r->Sz = 1.0f / get3(d, kz);          /* one IEEE division; Sx, Sy by multiplication (spec) */
     r->Sx = get3(d, kx) * r->Sz;
@@ -1259,6 +1262,23 @@ void or_trace_visibility(const OrScene* s, const float* rays, uint32_t count, fl
             }
         }
         out[4 * ii] = vis[0]; out[4 * ii + 1] = vis[1]; out[4 * ii + 2] = vis[2]; out[4 * ii + 3] = committed ? 0.0f : 1.0f;
+    }
+}
+
+void or_trace_closest(const OrScene* s, const float* rays, uint32_t count, void* out)
+{
+    #pragma omp parallel for schedule(dynamic, 64)
+    for (int64_t ii = 0; ii < (int64_t)count; ii++) {
+        const float* r = rays + 8 * ii;
+        Committed c = trace_ray(s, ld3(r), ld3(r + 4), r[3], r[7]);
+        uint32_t slot = 0;
+        if (c.hit) {
+            const Blas* B = &s->blas[s->inst[c.inst].Blas];
+            for (uint32_t k = 0; k < B->n_tris; k++) if (B->tris[k].geom == c.geom && B->tris[k].prim == c.prim) { slot = k; break; }
+        }
+        float f[3] = { c.hit ? c.t : r[7], c.hit ? c.u : 0.0f, c.hit ? c.v : 0.0f };
+        uint32_t w[5] = { c.hit ? c.inst : ~0u, c.hit ? c.geom : 0u, c.hit ? c.prim : 0u, slot, 0u };
+        memcpy((uint8_t*)out + 32 * ii, f, 12); memcpy((uint8_t*)out + 32 * ii + 12, w, 20);
     }
 }
 

@@ -227,6 +227,10 @@ void     or_bsdf_sample_batch(const float* q, uint32_t count, float* r);
  * (RaytracingHelpers.hlsli:7-55, ShadingHelpers.hlsli:117-159, RTXDIAppBridge.hlsli:418-439).
  * rays: 8 floats per ray = origin.xyz tmin dir.xyz tmax; out: 4 floats = visibility.rgb, 1 if nothing was committed else 0 */
 void     or_trace_visibility(const OrScene* scene, const float* rays, uint32_t count, float* out);
+/* The closest hit of each ray (8 floats as above) by trace_ray, in the scene's accel_mode: 32 B per ray = float t, u, v; uint32 instance,
+ * geometry, primitive, slot, pad. A miss has instance = ~0u and t = tmax. slot is the triangle's position in the oracle's own list of the
+ * bottom level (submission order in accel_mode 0), not the device's packet order. */
+void     or_trace_closest(const OrScene* scene, const float* rays, uint32_t count, void* out);
 /* SkeletalMeshSkinning.hlsl:28-62. skeletal: VertexPositionNormalTangentSkin (48 B: pos f32x3, normal i16x3, tangent i16x3,
  * joints u16x4, weights f32x4); transforms: row-major 3x4 per joint; vertices: 32-B vertex (in/out); motion: half4 per vertex */
 void     or_skin_mesh(const void* skeletal, const float* transforms, void* vertices, uint16_t* motion, uint32_t count);
