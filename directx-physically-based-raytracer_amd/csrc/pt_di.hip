@@ -10,7 +10,11 @@
 //   k_di<Source>                   <- DIInitialSampling (local lights only, streaming RIS) + DIFinalShading, no temporal /
 //                                     spatial reuse (RTXDIAppBridge.hlsli RAB_GetGBufferSurface, RAB_Surface::Shade, GetFinalVisibility)
 //   k_di_initial_temporal<..., Source> <- DIInitialSampling + DITemporalResampling (boiling filter), with reservoir reuse on
-//   k_di_spatial_shade             <- DISpatialResampling + DIFinalShading
+//   k_di_spatial_shade<..., VIS>   <- DISpatialResampling + DIFinalShading
+//   k_di_initial_temporal_vis, k_di_spatial_shade<..., VIS != 0> <- the same with visibility in the reservoirs (pt_di_set_visibility):
+//                                     initial visibility (DIInitialSampling.hlsl:49-54), Raytraced bias correction
+//                                     (RAB_GetConservativeVisibility / RAB_GetTemporalConservativeVisibility), the final-visibility store and
+//                                     reuse and discardInvisibleSamples (DIFinalShading.hlsl:32-56)
 // Source is where initial sampling draws its candidates from: DIPowerCDF (the prefix sum, the default) or DISampling (Uniform,
 // Power_RIS, ReGIR). Every kernel reads its surfaces with di_surface, draws with di_initial and shades with di_final.
 // DESIGN.md section 1 ("Direct lighting") is the arithmetic spec: seeding, draw order, triangle mapping.
@@ -412,6 +416,46 @@ PT_DEV void di_initial(const DIArgs& a, const Source& source, const DISurface& s
     }
 }
 
+// the visibility ray every DI pass traces (CreateVisibilityRay with offset 1e-3): from P to pos, tmin 1e-3, tmax = max(0, dist - 2e-3).
+// vis: the coloured visibility; returns whether the any-hit walk committed something (GetConservativeVisibility: blocked)
+PT_DEV bool di_shadow_ray(BlobView bv, const AlphaContext& ac, DeviceCounters* counters, uint2* ldsStack, v3 P, v3 pos, float& dist, v3& vis)
+{
+    const v3 d = pos - P;
+    dist = sqrtf(dot(d, d));
+    const v3 dir = V3(d.x / dist, d.y / dist, d.z / dist);
+    uint2 spill[kStackSize - kLdsStackDepth];
+    GroupStack<kLdsStackDepth> stack; stack.init((PT_LDS_AS void*)ldsStack, spill);
+    BlobReader<false> blob; blob.p = bv.base;
+    TraceStats st; st.nodes = 0; st.tris = 0; st.overflow = 0;
+    const Hit h = trace_single<false, false, true>(blob, bv, ac, P, dir, 1e-3f, fmaxf(0.0f, dist - 2e-3f), stack, &st, &vis);
+    if (st.overflow) atomicAdd(&counters->stackOverflows, st.overflow);
+    return h.inst != ~0u;
+}
+
+// the outputs of final shading (DIFinalShading.hlsl:78-103) for a sample of visibility vis at distance dist
+PT_DEV void di_final_write(const DIArgs& a, size_t pi, float dist, v3 vis, v3 difSel, v3 spcSel, float W)
+{
+    const PtTextures& tx = a.tx;
+    if (vis.x == 0.0f && vis.y == 0.0f && vis.z == 0.0f) return;
+    const v3 dif = V3(difSel.x * vis.x * W, difSel.y * vis.y * W, difSel.z * vis.z * W);
+    const v3 spc = V3(spcSel.x * vis.x * W, spcSel.y * vis.y * W, spcSel.z * vis.z * W);
+    const v3 rad = dif + spc;
+    if ((rad.x == 0.0f && rad.y == 0.0f && rad.z == 0.0f) || !finite3(rad)) return;
+
+    if (a.lastPass && a.denoiser <= PT_DENOISER_DLSS_RAY_RECONSTRUCTION) {
+        ushort4* R = (ushort4*)tx.Radiance;
+        const ushort4 o = R[pi];
+        const v3 sum = V3(f16_to_f32(o.x) + rad.x, f16_to_f32(o.y) + rad.y, f16_to_f32(o.z) + rad.z);
+        R[pi] = make_ushort4(f32_to_f16(sum.x), f32_to_f16(sum.y), f32_to_f16(sum.z), o.w);
+        if (tx.RadianceF32) ((float4*)tx.RadianceF32)[pi] = make_float4(sum.x, sum.y, sum.z, 0.0f);
+        if (a.denoiser == PT_DENOISER_DLSS_RAY_RECONSTRUCTION && tx.SpecularHitDistance && (spc.x > 0.0f || spc.y > 0.0f || spc.z > 0.0f))
+            ((uint16_t*)tx.SpecularHitDistance)[pi] = f32_to_f16(dist);
+        return;
+    }
+    ((ushort4*)tx.Diffuse)[pi] = make_ushort4(f32_to_f16(dif.x), f32_to_f16(dif.y), f32_to_f16(dif.z), f32_to_f16(dist));
+    ((ushort4*)tx.Specular)[pi] = make_ushort4(f32_to_f16(spc.x), f32_to_f16(spc.y), f32_to_f16(spc.z), f32_to_f16(dist));
+}
+
 // final shading (DIFinalShading.hlsl): one coloured visibility ray, CreateVisibilityRay with offset 1e-3; outputs :78-103
 PT_DEV void di_final(const DIArgs& a, BlobView bv, const AlphaContext& ac, DeviceCounters* counters, uint2* ldsStack, size_t pi, v3 P, v3 posSel,
                      v3 difSel, v3 spcSel, float W)
@@ -476,7 +520,7 @@ __global__ __launch_bounds__(256) void k_di(DIArgs a, Source source, BlobView bv
 // ---- reservoir reuse (DITemporalResampling / DISpatialResampling; DESIGN.md section 1, "Reservoir reuse") --------------------------------
 constexpr uint32_t kDITemporalSalt = 0x44490002u, kDISpatialSalt = 0x44490003u;
 constexpr uint32_t kDIOffsetCount = 8192u;          // neighbour-offset table entries (int8 x, y)
-static_assert(sizeof(PtDIReservoir) == 32 && sizeof(PtDIResamplingSettings) == 64 && sizeof(PtDIPreviousTextures) == 48, "layout");
+static_assert(sizeof(PtDIReservoir) == 32 && sizeof(PtDIResamplingSettings) == 64 && sizeof(PtDIPreviousTextures) == 48 && sizeof(PtDIVisibilitySettings) == 32, "layout");
 
 struct DIReuseArgs {
     DIArgs d;
@@ -489,20 +533,63 @@ struct DIReuseArgs {
 
 PT_DEV PtDIReservoir di_empty(uint32_t M)
 {
-    PtDIReservoir r; r.LightIndex = ~0u; r.U = 0.0f; r.V = 0.0f; r.W = 0.0f; r.M = M; r.TargetPdf = 0.0f; r.Age = 0u; r._pad = 0u;
+    PtDIReservoir r; r.LightIndex = ~0u; r.U = 0.0f; r.V = 0.0f; r.W = 0.0f; r.M = M; r.TargetPdf = 0.0f; r.Age = 0u; r.Visibility = 0u;
     return r;
 }
+// VIS: the reservoirs carry the Visibility word (pt_di_set_visibility); without it the word is read and written as 0
+template <bool VIS = false>
 PT_DEV PtDIReservoir di_load(const PtDIReservoir* p, size_t i)
 {
     const uint4 a = ((const uint4*)p)[2 * i], b = ((const uint4*)p)[2 * i + 1];
     PtDIReservoir r; r.LightIndex = a.x; r.U = __uint_as_float(a.y); r.V = __uint_as_float(a.z); r.W = __uint_as_float(a.w);
-    r.M = b.x; r.TargetPdf = __uint_as_float(b.y); r.Age = b.z; r._pad = 0u;
+    r.M = b.x; r.TargetPdf = __uint_as_float(b.y); r.Age = b.z; r.Visibility = VIS ? b.w : 0u;
     return r;
 }
+template <bool VIS = false>
 PT_DEV void di_store(PtDIReservoir* p, size_t i, const PtDIReservoir& r)
 {
     ((uint4*)p)[2 * i] = make_uint4(r.LightIndex, __float_as_uint(r.U), __float_as_uint(r.V), __float_as_uint(r.W));
-    ((uint4*)p)[2 * i + 1] = make_uint4(r.M, __float_as_uint(r.TargetPdf), r.Age, 0u);
+    ((uint4*)p)[2 * i + 1] = make_uint4(r.M, __float_as_uint(r.TargetPdf), r.Age, VIS ? r.Visibility : 0u);
+}
+
+// ---- reservoir visibility (pt_di_set_visibility; DESIGN.md section 1, "Reservoir visibility") ------------------------------------------
+// What the visibility-enabled instantiations take on top of DIReuseArgs: the traversal's inputs and the settings.
+struct DIVisArgs {
+    BlobView bv; AlphaContext ac; DeviceCounters* counters;
+    uint32_t initial, maxAge, discard;              // maxAge 0: no final-visibility reuse
+    float maxDistance;
+};
+// PtDIReservoir.Visibility: rgb 5 bits each | dx, dy 6-bit two's complement clamped to +-31 | age 4 bits saturating
+PT_DEV uint32_t di_vis_pack(v3 vis)
+{
+    const uint32_t r = (uint32_t)(fminf(fmaxf(vis.x, 0.0f), 1.0f) * 31.0f), g = (uint32_t)(fminf(fmaxf(vis.y, 0.0f), 1.0f) * 31.0f),
+                   b = (uint32_t)(fminf(fmaxf(vis.z, 0.0f), 1.0f) * 31.0f);
+    return r | (g << 5) | (b << 10);
+}
+PT_DEV v3 di_vis_colour(uint32_t w) { return V3((float)(w & 31u) / 31.0f, (float)((w >> 5) & 31u) / 31.0f, (float)((w >> 10) & 31u) / 31.0f); }
+PT_DEV int di_vis_delta(uint32_t w, uint32_t shift) { return (int)((w >> shift) & 63u) - (int)((w >> shift) & 32u) * 2; }
+// the word of a sample taken from pixel (x + ddx, y + ddy), dAge frames later
+PT_DEV uint32_t di_vis_carry(uint32_t w, int ddx, int ddy, uint32_t dAge)
+{
+    const int dx = min(max(di_vis_delta(w, 15u) + ddx, -31), 31), dy = min(max(di_vis_delta(w, 21u) + ddy, -31), 31);
+    const uint32_t age = min(((w >> 27) & 15u) + dAge, 15u);
+    return (w & 0x7FFFu) | (((uint32_t)dx & 63u) << 15) | (((uint32_t)dy & 63u) << 21) | (age << 27);
+}
+// final shading may use the stored visibility: 1 <= age <= maxAge and |d| < maxDistance (a d clamped to 31 never is: maxDistance <= 31)
+PT_DEV bool di_vis_reusable(uint32_t w, uint32_t maxAge, float maxDistance)
+{
+    const uint32_t age = (w >> 27) & 15u;
+    const int dx = di_vis_delta(w, 15u), dy = di_vis_delta(w, 21u);
+    return age >= 1u && age <= maxAge && sqrtf((float)(dx * dx + dy * dy)) < maxDistance;
+}
+// the point of sample (li, U, V): the arithmetic of di_target
+PT_DEV v3 di_sample_point(const DIArgs& a, uint32_t li, float U, float V)
+{
+    const float4* L = a.lights + kLightRec16 * (size_t)li;
+    const float4 l0 = L[0], l1 = L[1], l2 = L[2];
+    const float sq = sqrtf(U);
+    const float b0 = sq * (1.0f - V), b1 = sq * V;
+    return V3(l0.x + l1.x * b0 + l2.x * b1, l0.y + l1.y * b0 + l2.y * b1, l0.z + l1.z * b0 + l2.z * b1);
 }
 // RAB_ClampSamplePositionIntoView: reflect across the screen edges (one reflection; a position still outside reads the empty surface)
 PT_DEV void di_reflect(int& x, int& y, int w, int h)
@@ -535,6 +622,36 @@ PT_DEV float di_target_of(const DIArgs& a, const DISurface& s, uint32_t li, floa
     v3 pos, dif, spc;
     float power;
     return di_target(a, s, li, U, V, pos, dif, spc, power);
+}
+
+// the temporal pass's history search: the motion-vector position, then eight jittered ones (draws from the temporal stream); (hx, hy) is
+// the first whose previous surface sp passes the neighbour test against the expected depth, or stays (-1, -1)
+PT_DEV void di_find_history(const DIReuseArgs& r, const DISurface& s, uint32_t x, uint32_t y, size_t pi, uint32_t& rng, DISurface& sp, int& hx, int& hy)
+{
+    const DIArgs& a = r.d;
+    const int w = (int)a.fv.width, h = (int)a.fv.height;
+    const ushort4 mv = ((const ushort4*)a.tx.MotionVector)[pi];
+    const float expected = s.depth + f16_to_f32(mv.z);
+    const float fx = fminf(fmaxf((float)x + f16_to_f32(mv.x), -65536.0f), 65536.0f), fy = fminf(fmaxf((float)y + f16_to_f32(mv.y), -65536.0f), 65536.0f);
+    const int px = (int)rintf(fx), py = (int)rintf(fy);            // HLSL round: to nearest even
+    for (int i = 0; i < 9; i++) {
+        int qx = px, qy = py;
+        if (i) { const float rx = rng_float(rng), ry = rng_float(rng); qx += (int)((rx - 0.5f) * 6.0f); qy += (int)((ry - 0.5f) * 6.0f); }
+        di_reflect(qx, qy, w, h);
+        if (qx < 0 || qy < 0 || qx >= w || qy >= h) continue;
+        if (!di_surface(a, r.prev, (size_t)qy * w + qx, qx, qy, sp)) continue;
+        if (!di_similar(s, sp, expected, r.tNormal, r.tDepth)) continue;
+        hx = qx; hy = qy;
+        break;
+    }
+}
+// boiling filter: the tile's mean of the nonzero weights, a 64-lane butterfly (every lane of the wave takes part)
+PT_DEV void di_boiling(const DIReuseArgs& r, bool valid, PtDIReservoir& res)
+{
+    const bool nz = valid && res.W > 0.0f;
+    float sum = nz ? res.W : 0.0f, cnt = nz ? 1.0f : 0.0f;
+    for (int m = 1; m < 64; m <<= 1) { sum += __shfl_xor(sum, m); cnt += __shfl_xor(cnt, m); }
+    if (cnt > 0.0f && res.W > sum / cnt * r.boilingMul) res = di_empty(0u);
 }
 
 // Initial sampling from a candidate source fused with temporal reuse: the temporal step at a pixel reads only that pixel's fresh reservoir
@@ -615,17 +732,112 @@ __global__ __launch_bounds__(256) void k_di_initial_temporal(DIReuseArgs r, Sour
     if (inside) di_store(r.out, pi, res);
 }
 
-// Spatial reuse, then final shading in the same thread. SPATIAL = false: the final reservoir is the input (temporal-only).
-template <bool SPATIAL, bool BASIC>
-__global__ __launch_bounds__(256) void k_di_spatial_shade(DIReuseArgs r, BlobView bv, AlphaContext ac, DeviceCounters* counters)
+// k_di_initial_temporal with reservoir visibility on (pt_di_set_visibility). Initial visibility: the selected initial sample's ray; blocked
+// empties the reservoir. RAYTRACED (with BASIC): p at the previous surface counts as 0 when the ray from the current surface to the
+// selected sample is blocked. The two rays of a lane depend on each other (the second sample is chosen after the first ray), so they are
+// the two trips of one loop that all lanes walk together: lanes without a ray on a trip trace nothing, and every lane reaches the boiling
+// filter's butterfly. The loop is unrolled, i.e. two inlined walks: kept rolled around one trace site the kernel needs 185 VGPRs (2 waves
+// per SIMD), unrolled 137 (3 waves), scratch 464 B / lane either way. A selected history sample brings its Visibility
+// word along, moved by the pixel offset and one frame older.
+template <bool TEMPORAL, bool BASIC, bool RAYTRACED, typename Source>
+__global__ __launch_bounds__(256) void k_di_initial_temporal_vis(DIReuseArgs r, Source source, DIVisArgs va)
 {
+    __shared__ uint2 ldsStack[kLdsStackDepth * 256];
+    const DIArgs& a = r.d;
+    uint32_t x, y; di_pixel(x, y);
+    const bool inside = x < a.fv.width && y < a.fv.localRows;
+    const size_t pi = (size_t)y * a.fv.width + x;
+    PtDIReservoir res = di_empty(0u);
+    DISurface s;
+    const bool valid = inside && di_surface(a, a.view, pi, x, y, s);
+    v3 target = V3(0.0f, 0.0f, 0.0f);                                      // where this trip's ray goes
+    bool want = false;
+    if (valid) {
+        res.M = a.samples;
+        const float total = *a.total;
+        if (total > 0.0f && isfinite(total)) {
+            DIInitial i0;
+            di_initial(a, source, s, x, y, total, i0);
+            if (i0.p > 0.0f) {
+                res.LightIndex = i0.li; res.U = i0.u; res.V = i0.v; res.W = i0.wsum / (float)a.samples / i0.p; res.TargetPdf = i0.p;
+                target = i0.pos; want = va.initial != 0u;
+            }
+        }
+    }
+    constexpr int kTrips = TEMPORAL && BASIC && RAYTRACED ? 2 : 1;
+    uint32_t Mcur = 0, MH = 0;
+    float wsum = 0.0f, pPrev = 0.0f;
+    bool fromH = false, basicPending = false;
+    #pragma unroll
+    for (int trip = 0; trip < kTrips; trip++) {
+        bool blocked = false;
+        if (want) { float dist; v3 vis; blocked = di_shadow_ray(va.bv, va.ac, va.counters, ldsStack, s.P, target, dist, vis); }
+        want = false;
+        if (trip == 1) { if (blocked) pPrev = 0.0f; continue; }
+        if (blocked) res = di_empty(a.samples);                               // initial visibility
+        if (TEMPORAL && valid) {
+            const int w = (int)a.fv.width;
+            uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDITemporalSalt);
+            DISurface sp;
+            int hx = -1, hy = -1;
+            if (r.haveHistory) di_find_history(r, s, x, y, pi, rng, sp, hx, hy);
+            Mcur = res.M;
+            wsum = res.TargetPdf * res.W * (float)res.M;
+            if (hx >= 0) {
+                PtDIReservoir H = di_load<true>(r.in, (size_t)hy * w + hx);
+                H.M = min(H.M, r.maxHistory * Mcur);
+                const float pH = di_target_of(a, s, H.LightIndex, H.U, H.V);
+                const float rc = rng_float(rng);
+                const float wH = pH * H.W * (float)H.M;
+                wsum += wH;
+                if (rc * wsum < wH) {
+                    res.LightIndex = H.LightIndex; res.U = H.U; res.V = H.V; res.TargetPdf = pH; res.Age = H.Age == ~0u ? ~0u : H.Age + 1u; fromH = true;
+                    res.Visibility = di_vis_carry(H.Visibility, hx - (int)x, hy - (int)y, 1u);
+                }
+                MH = H.M;
+                res.M = Mcur + H.M;
+            }
+            const float p = res.TargetPdf;
+            if (!(p > 0.0f)) {
+                res = di_empty(res.M);
+            } else if (BASIC) {
+                pPrev = hx >= 0 ? di_target_of(a, sp, res.LightIndex, res.U, res.V) : 0.0f;
+                basicPending = true;
+                if (RAYTRACED && hx >= 0 && pPrev > 0.0f) { want = true; target = di_sample_point(a, res.LightIndex, res.U, res.V); }
+            } else {
+                res.W = wsum / (p * (float)res.M);
+            }
+        }
+    }
+    if (basicPending) {
+        const float p = res.TargetPdf;
+        const float den = p * ((float)Mcur * p + (float)MH * pPrev);
+        res.W = den > 0.0f ? wsum * (fromH ? pPrev : p) / den : 0.0f;
+    }
+    if (TEMPORAL && r.boiling) di_boiling(r, valid, res);
+    if (inside) di_store<true>(r.out, pi, res);
+}
+
+// Spatial reuse, then final shading in the same thread. SPATIAL = false: the final reservoir is the input (temporal-only).
+// VIS (pt_di_set_visibility): 0 off; kDIVisOn: the reservoirs carry the Visibility word and final shading may reuse it; | kDIVisRaytraced
+// (with BASIC): in the normalisation a neighbour's p counts as 0 when the ray from that neighbour's surface to the selected sample is
+// blocked -- one trace site inside that loop.
+constexpr uint32_t kDIVisOn = 1u, kDIVisRaytraced = 2u;
+// The settings reach the visibility-enabled instantiations as one trailing DIVisArgs; without VIS the kernel's arguments are the four.
+PT_DEV const DIVisArgs* di_vis_args() { return nullptr; }
+PT_DEV const DIVisArgs* di_vis_args(const DIVisArgs& va) { return &va; }
+template <bool SPATIAL, bool BASIC, uint32_t VIS, typename... Extra>
+__global__ __launch_bounds__(256) void k_di_spatial_shade(DIReuseArgs r, BlobView bv, AlphaContext ac, DeviceCounters* counters, Extra... extra)
+{
+    constexpr bool CARRY = VIS != 0u;
+    __shared__ uint2 ldsStack[kLdsStackDepth * 256];
     const DIArgs& a = r.d;
     uint32_t x, y; di_pixel(x, y);
     if (x >= a.fv.width || y >= a.fv.localRows) return;                 // no barrier below
     const size_t pi = (size_t)y * a.fv.width + x;
-    PtDIReservoir c = di_load(r.in, pi);
+    PtDIReservoir c = di_load<CARRY>(r.in, pi);
     DISurface s;
-    if (!di_surface(a, a.view, pi, x, y, s)) { di_store(r.out, pi, c); return; }
+    if (!di_surface(a, a.view, pi, x, y, s)) { di_store<CARRY>(r.out, pi, c); return; }
     if (SPATIAL) {
         const int w = (int)a.fv.width;
         uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDISpatialSalt);
@@ -642,25 +854,33 @@ __global__ __launch_bounds__(256) void k_di_spatial_shade(DIReuseArgs r, BlobVie
             if (!di_surface(a, a.view, (size_t)qy * w + qx, qx, qy, sn)) continue;
             if (!di_similar(s, sn, s.depth, r.sNormal, r.sDepth)) continue;
             mask |= 1u << i;
-            const PtDIReservoir rn = di_load(r.in, (size_t)qy * w + qx);
+            const PtDIReservoir rn = di_load<CARRY>(r.in, (size_t)qy * w + qx);
             const float pn = di_target_of(a, s, rn.LightIndex, rn.U, rn.V);
             const float rc = rng_float(rng);
             const float wn = pn * rn.W * (float)rn.M;
             wsum += wn; M += rn.M;
-            if (rc * wsum < wn) { o.LightIndex = rn.LightIndex; o.U = rn.U; o.V = rn.V; o.TargetPdf = pn; o.Age = rn.Age; sel = (int)i; }
+            if (rc * wsum < wn) { o.LightIndex = rn.LightIndex; o.U = rn.U; o.V = rn.V; o.TargetPdf = pn; o.Age = rn.Age; sel = (int)i;
+                if (CARRY) o.Visibility = di_vis_carry(rn.Visibility, qx - (int)x, qy - (int)y, 0u);
+            }
         }
         const float p = o.TargetPdf;
         o.M = M;
         if (p > 0.0f) {
             if (BASIC) {                                                     // sum over the centre and the contributing neighbours
                 float den = (float)c.M * p, pSrc = p;
+                v3 posSel = V3(0.0f, 0.0f, 0.0f);
+                if constexpr ((VIS & kDIVisRaytraced) != 0u) posSel = di_sample_point(a, o.LightIndex, o.U, o.V);
                 for (uint32_t i = 0; i < n; i++) {
                     if (!(mask & (1u << i))) continue;
                     int qx, qy;
                     di_neighbour(r, x, y, start, i, qx, qy);                 // inside: the first loop took it
                     DISurface sn;
                     di_surface(a, a.view, (size_t)qy * w + qx, qx, qy, sn);
-                    const float pn = di_target_of(a, sn, o.LightIndex, o.U, o.V);
+                    float pn = di_target_of(a, sn, o.LightIndex, o.U, o.V);
+                    if constexpr ((VIS & kDIVisRaytraced) != 0u) {
+                        float dist; v3 vis;
+                        if (pn > 0.0f && di_shadow_ray(bv, ac, counters, ldsStack, sn.P, posSel, dist, vis)) pn = 0.0f;
+                    }
                     den += (float)r.in[(size_t)qy * w + qx].M * pn;
                     if ((int)i == sel) pSrc = pn;
                 }
@@ -674,13 +894,34 @@ __global__ __launch_bounds__(256) void k_di_spatial_shade(DIReuseArgs r, BlobVie
         }
         c = o;
     }
-    di_store(r.out, pi, c);
-    if (c.LightIndex >= a.count || !(c.W > 0.0f)) return;
-    v3 pos, dif, spc;
-    float power;
-    di_target(a, s, c.LightIndex, c.U, c.V, pos, dif, spc, power);
-    __shared__ uint2 ldsStack[kLdsStackDepth * 256];
-    di_final(a, bv, ac, counters, ldsStack, pi, s.P, pos, dif, spc, c.W);
+    if constexpr (!CARRY) {
+        di_store(r.out, pi, c);
+        if (c.LightIndex >= a.count || !(c.W > 0.0f)) return;
+        v3 pos, dif, spc;
+        float power;
+        di_target(a, s, c.LightIndex, c.U, c.V, pos, dif, spc, power);
+        di_final(a, bv, ac, counters, ldsStack, pi, s.P, pos, dif, spc, c.W);
+    } else {
+        // final shading with the visibility word: a young, nearby one stands in for the ray and the reservoir is stored as it is; otherwise the
+        // traced visibility is stored (d = 0, age 0). The stored reservoir is the final one: next frame's history.
+        const DIVisArgs* va = di_vis_args(extra...);
+        if (c.LightIndex >= a.count || !(c.W > 0.0f)) { di_store<true>(r.out, pi, c); return; }
+        v3 pos, dif, spc, vis;
+        float power, dist;
+        const float W = c.W;
+        di_target(a, s, c.LightIndex, c.U, c.V, pos, dif, spc, power);
+        if (va->maxAge != 0u && di_vis_reusable(c.Visibility, va->maxAge, va->maxDistance)) {
+            const v3 d = pos - s.P;
+            dist = sqrtf(dot(d, d));
+            vis = di_vis_colour(c.Visibility);
+        } else {
+            di_shadow_ray(bv, ac, counters, ldsStack, s.P, pos, dist, vis);
+            c.Visibility = di_vis_pack(vis);
+            if (va->discard != 0u && vis.x == 0.0f && vis.y == 0.0f && vis.z == 0.0f) c = di_empty(c.M);
+        }
+        di_store<true>(r.out, pi, c);
+        di_final_write(a, pi, dist, vis, dif, spc, W);
+    }
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
@@ -753,6 +994,12 @@ static int di_check_args(Context& c, const PtTextures* tx, const PtDIPreviousTex
         API_ARG(&c, prev && prev->PreviousGeometricNormal && prev->PreviousLinearDepth && prev->PreviousBaseColorMetalness && prev->PreviousNormalRoughness &&
                prev->PreviousIOR && prev->PreviousTransmission && tx->MotionVector,
                "temporal resampling reads Textures.MotionVector and the six Previous* textures: not bound");
+    if (c.diReuseOn && c.diVisibilityOn) {
+        API_ARG(&c, !(c.diVisibility.TemporalRaytraced && c.diReuse.TemporalResampling) || c.diReuse.TemporalBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC,
+               "TemporalRaytraced needs TemporalBiasCorrection = PT_DI_BIAS_CORRECTION_BASIC");
+        API_ARG(&c, !(c.diVisibility.SpatialRaytraced && c.diReuse.SpatialSamples) || c.diReuse.SpatialBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC,
+               "SpatialRaytraced needs SpatialBiasCorrection = PT_DI_BIAS_CORRECTION_BASIC");
+    }
     return PT_OK;
 }
 
@@ -858,17 +1105,35 @@ static int di_launch_reuse(Context& c, const DIArgs& a, const DISampling& ls, co
     r.radius = rs.SpatialSamplingRadius; r.sDepth = rs.SpatialDepthThreshold; r.sNormal = rs.SpatialNormalThreshold;
     r.in = c.diResB.data(); r.out = c.diResA.data();
     const bool tb = rs.TemporalBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC, sb = rs.SpatialBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC;
+    const PtDIVisibilitySettings& vs = c.diVisibility;
+    const bool vis = c.diVisibilityOn, tr = vis && temporal && vs.TemporalRaytraced, sr = vis && spatial && vs.SpatialRaytraced;
+    DIVisArgs va; memset(&va, 0, sizeof va);
+    va.bv = c.scene.blob; va.ac = ac; va.counters = c.counters.data();
+    va.initial = vs.InitialVisibility; va.maxAge = vs.FinalVisibilityReuse ? vs.FinalVisibilityMaxAge : 0u; va.discard = vs.DiscardInvisibleSamples;
+    va.maxDistance = vs.FinalVisibilityMaxDistance;
     di_with_source(ls, [&](auto source) {
         using S = decltype(source);
-        if (!temporal) k_di_initial_temporal<false, false, S><<<grid, 256, 0, c.stream>>>(r, source);
+        if (vis) {
+            if (!temporal) k_di_initial_temporal_vis<false, false, false, S><<<grid, 256, 0, c.stream>>>(r, source, va);
+            else if (tr) k_di_initial_temporal_vis<true, true, true, S><<<grid, 256, 0, c.stream>>>(r, source, va);
+            else if (tb) k_di_initial_temporal_vis<true, true, false, S><<<grid, 256, 0, c.stream>>>(r, source, va);
+            else k_di_initial_temporal_vis<true, false, false, S><<<grid, 256, 0, c.stream>>>(r, source, va);
+        }
+        else if (!temporal) k_di_initial_temporal<false, false, S><<<grid, 256, 0, c.stream>>>(r, source);
         else if (tb) k_di_initial_temporal<true, true, S><<<grid, 256, 0, c.stream>>>(r, source);
         else k_di_initial_temporal<true, false, S><<<grid, 256, 0, c.stream>>>(r, source);
     });
     API_HIP(&c, hipGetLastError());
     r.in = c.diResA.data(); r.out = c.diResB.data();
-    if (!spatial) k_di_spatial_shade<false, false><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data());
-    else if (sb) k_di_spatial_shade<true, true><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data());
-    else k_di_spatial_shade<true, false><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data());
+    if (vis) {
+        if (!spatial) k_di_spatial_shade<false, false, kDIVisOn><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data(), va);
+        else if (sr) k_di_spatial_shade<true, true, kDIVisOn | kDIVisRaytraced><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data(), va);
+        else if (sb) k_di_spatial_shade<true, true, kDIVisOn><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data(), va);
+        else k_di_spatial_shade<true, false, kDIVisOn><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data(), va);
+    }
+    else if (!spatial) k_di_spatial_shade<false, false, 0u><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data());
+    else if (sb) k_di_spatial_shade<true, true, 0u><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data());
+    else k_di_spatial_shade<true, false, 0u><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data());
     API_HIP(&c, hipGetLastError());
     c.diHistoryValid = true; c.diHistorySize[0] = fv.width; c.diHistorySize[1] = fv.height; c.diHistoryLightKey = c.lightListKey;
     c.diResCount = (uint32_t)npix;
@@ -955,6 +1220,31 @@ int pt_di_set_resampling(PtContext* ctx, const PtDIResamplingSettings* s)
     const bool on = v.TemporalResampling || v.SpatialSamples;
     if (on != c.diReuseOn || memcmp(&v, &c.diReuse, sizeof v) != 0) c.diHistoryValid = false;
     c.diReuse = v; c.diReuseOn = on;
+    return PT_OK;
+}
+
+int pt_di_set_visibility(PtContext* ctx, const PtDIVisibilitySettings* s)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    PtDIVisibilitySettings v; memset(&v, 0, sizeof v);
+    if (s) {
+        API_ARG(&c, s->InitialVisibility <= 1u, "InitialVisibility must be 0 or 1");
+        API_ARG(&c, s->FinalVisibilityReuse <= 1u, "FinalVisibilityReuse must be 0 or 1");
+        API_ARG(&c, s->DiscardInvisibleSamples <= 1u, "DiscardInvisibleSamples must be 0 or 1");
+        API_ARG(&c, s->TemporalRaytraced <= 1u, "TemporalRaytraced must be 0 or 1");
+        API_ARG(&c, s->SpatialRaytraced <= 1u, "SpatialRaytraced must be 0 or 1");
+        const bool on = s->InitialVisibility || s->FinalVisibilityReuse || s->DiscardInvisibleSamples || s->TemporalRaytraced || s->SpatialRaytraced;
+        if (on) {                                                             // all flags 0: the struct is today's behaviour whatever else it holds
+            API_ARG(&c, s->FinalVisibilityMaxAge >= 1u && s->FinalVisibilityMaxAge <= 14u, "FinalVisibilityMaxAge must be 1..14");
+            API_ARG(&c, s->FinalVisibilityMaxDistance > 0.0f && s->FinalVisibilityMaxDistance <= 31.0f, "FinalVisibilityMaxDistance must be in (0, 31]");
+            v = *s;
+            v._pad = 0;
+        }
+    }
+    const bool on = v.InitialVisibility || v.FinalVisibilityReuse || v.DiscardInvisibleSamples || v.TemporalRaytraced || v.SpatialRaytraced;
+    if (memcmp(&v, &c.diVisibility, sizeof v) != 0) c.diHistoryValid = false;
+    c.diVisibility = v; c.diVisibilityOn = on;
     return PT_OK;
 }
 

@@ -2,7 +2,7 @@
 // reference-shaped operators of ptamd.hpp (GBufferGeneration / Raytracing / RaytracingHelpers), times it and
 // optionally dumps the radiance for the parity test (tests/test_host_cpp.py compares it with the oracle).
 //
-//   pt_demo [--width W] [--height H] [--spp S] [--bounces B] [--frames N] [--out file.bin] [--ranks R] [--di] [--di-samples N] [--restir] [--sharc]
+//   pt_demo [--width W] [--height H] [--spp S] [--bounces B] [--frames N] [--out file.bin] [--ranks R] [--di] [--di-samples N] [--restir [--restir-visibility [--restir-raytraced]]] [--sharc]
 //           [--light-sampling cdf|uniform|power_ris|regir]
 //           [--post] [--no-bloom] [--bloom-strength S] [--tone-map saturate|reinhard|aces] [--exposure E]
 //           [--hdr [--paper-white N] [--color-rotation hdtv_to_uhdtv|dci_p3_d65_to_uhdtv|hdtv_to_dci_p3_d65]]
@@ -12,6 +12,8 @@
 // the path tracer then runs with IsDIEnabled (with Bounces 0 the DI pass is the last render pass and adds to Radiance).
 // --restir (with --di): temporal + spatial reservoir reuse at MyAppData's defaults; the Previous* G-buffer is swapped in before every
 // frame after the first (App.cpp:629-634). Unsharded only.
+// --restir-visibility (with --restir): visibility in the reservoirs at the RTXDI SDK's defaults (initial visibility, final-visibility reuse
+// over 4 frames / 16 pixels); --restir-raytraced (with it): Raytraced bias correction in both passes.
 // --light-sampling (with --di): how the DI pass draws its candidates (ReSTIRDI.InitialSampling.LocalLight.Mode; default cdf, the power
 // prefix sum); ReGIR at MyAppData's cell size 1 and 8 build samples.
 //
@@ -350,7 +352,7 @@ static std::vector<uint8_t> exchange_unique_id(uint32_t rank, const std::string&
 int main(int argc, char** argv)
 {
     uint32_t W = 1920, H = 1080, spp = 4, bounces = 8, frames = 10, ranks = 0, rank = 0, world = 1;
-    uint32_t diSamples = 8; bool di = false, restir = false;
+    uint32_t diSamples = 8; bool di = false, restir = false, restirVisibility = false, restirRaytraced = false;
     bool useSharc = false; uint32_t sharcDownscale = 4; float sceneScale = 50.0f;   // --sharc [--sharc-downscale N --scene-scale S]: frames through the radiance cache
     std::string out, idFile, scenePath, dumpPath, lightSampling = "cdf";
     bool post = false, bloom = true, hdr = false; float bloomStrength = 0.05f, exposure = 0.0f, paperWhite = 200.0f;
@@ -359,6 +361,8 @@ int main(int argc, char** argv)
         std::string k = argv[i];
         if (k == "--di") { di = true; continue; }                  // the flags without a value
         if (k == "--restir") { restir = true; continue; }
+        if (k == "--restir-visibility") { restirVisibility = true; continue; }
+        if (k == "--restir-raytraced") { restirRaytraced = true; continue; }
         if (k == "--sharc") { useSharc = true; continue; }
         if (k == "--post") { post = true; continue; }
         if (k == "--no-bloom") { bloom = false; continue; }
@@ -522,6 +526,8 @@ int main(int argc, char** argv)
         directLighting.GPUBuffers = { &sd, &cam, dObjects, n };
         directLighting.Textures = tx;
         if (restir && (!di || sharded)) throw std::invalid_argument("--restir needs --di and one unsharded process");
+        if (restirVisibility && !restir) throw std::invalid_argument("--restir-visibility needs --restir");
+        if (restirRaytraced && !restirVisibility) throw std::invalid_argument("--restir-raytraced needs --restir-visibility");
         if (useSharc && sharded) throw std::invalid_argument("--sharc needs one unsharded process");
         SHARC sharc(commandList);
         Raytracing::SHARCSettings sharcSettings; sharcSettings.DownscaleFactor = sharcDownscale;
@@ -543,6 +549,11 @@ int main(int argc, char** argv)
             DirectLighting::ReSTIRDI r;
             r.TemporalResampling.IsEnabled = true; r.SpatialResampling.IsEnabled = true;
             directLighting.SetResampling(r);
+            if (restirVisibility) {
+                DirectLighting::Visibility v;
+                v.TemporalRaytraced = v.SpatialRaytraced = restirRaytraced;
+                directLighting.SetVisibility(v);
+            }
         }
         bool firstFrame = true;
         PtCounters counters{};

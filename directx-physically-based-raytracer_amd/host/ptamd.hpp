@@ -245,6 +245,24 @@ struct DirectLighting {
 
     void ResetHistory() { ThrowIfFailed(m_context, pt_di_reset_history(m_context)); }     // App::ResetHistory
 
+    // Visibility in the reservoirs (pt_di_set_visibility): the RTXDI SDK's defaults, unpinned; it acts only with reuse on. The Raytraced
+    // flags turn the Basic normalisation of a pass into ReSTIRDI_BiasCorrectionMode::Raytraced.
+    struct Visibility {
+        bool EnableInitialVisibility = true, ReuseFinalVisibility = true, DiscardInvisibleSamples = false;
+        uint32_t FinalVisibilityMaxAge = 4;
+        float FinalVisibilityMaxDistance = 16.0f;
+        bool TemporalRaytraced = false, SpatialRaytraced = false;
+    };
+    void SetVisibility(const Visibility& v)
+    {
+        PtDIVisibilitySettings s{};
+        s.InitialVisibility = v.EnableInitialVisibility ? 1u : 0u; s.FinalVisibilityReuse = v.ReuseFinalVisibility ? 1u : 0u;
+        s.FinalVisibilityMaxAge = v.FinalVisibilityMaxAge; s.FinalVisibilityMaxDistance = v.FinalVisibilityMaxDistance;
+        s.DiscardInvisibleSamples = v.DiscardInvisibleSamples ? 1u : 0u;
+        s.TemporalRaytraced = v.TemporalRaytraced ? 1u : 0u; s.SpatialRaytraced = v.SpatialRaytraced ? 1u : 0u;
+        ThrowIfFailed(m_context, pt_di_set_visibility(m_context, &s));
+    }
+
     void SetLightSampling(const LightSampling& l)
     {
         PtDILightSamplingSettings s{};

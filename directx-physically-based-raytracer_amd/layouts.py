@@ -106,10 +106,46 @@ DI_RESAMPLING_SETTINGS = np.dtype({  # PtDIResamplingSettings: ReSTIRDI.Temporal
     "formats": ["<u4", "<u4", "<u4", "<u4", "<f4", "<f4", "<f4", "<u4", "<u4", "<u4", "<f4", "<f4", "<f4"],
     "offsets": [0, 4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 44, 48], "itemsize": 64})
 
-DI_RESERVOIR = np.dtype({  # PtDIReservoir: one per pixel, row-major
-    "names": ["LightIndex", "U", "V", "W", "M", "TargetPdf", "Age"],
-    "formats": ["<u4", "<f4", "<f4", "<f4", "<u4", "<f4", "<u4"],
-    "offsets": [0, 4, 8, 12, 16, 20, 24], "itemsize": 32})
+DI_RESERVOIR = np.dtype({  # PtDIReservoir: one per pixel, row-major; Visibility: di_unpack_visibility (0 unless di_visibility is on)
+    "names": ["LightIndex", "U", "V", "W", "M", "TargetPdf", "Age", "Visibility"],
+    "formats": ["<u4", "<f4", "<f4", "<f4", "<u4", "<f4", "<u4", "<u4"],
+    "offsets": [0, 4, 8, 12, 16, 20, 24, 28], "itemsize": 32})
+
+PT_DI_VISIBILITY_SETTINGS = np.dtype({  # PtDIVisibilitySettings: visibility in the reservoirs (pt_di_set_visibility)
+    "names": ["InitialVisibility", "FinalVisibilityReuse", "FinalVisibilityMaxAge", "FinalVisibilityMaxDistance", "DiscardInvisibleSamples",
+              "TemporalRaytraced", "SpatialRaytraced"],
+    "formats": ["<u4", "<u4", "<u4", "<f4", "<u4", "<u4", "<u4"], "offsets": [0, 4, 8, 12, 16, 20, 24], "itemsize": 32})
+
+
+def di_visibility_settings(initial=True, final_reuse=True, max_age=4, max_distance=16.0, discard_invisible=False,
+                           temporal_raytraced=False, spatial_raytraced=False):
+    """PtDIVisibilitySettings. The defaults are the RTXDI SDK's from memory (not in the reference tree, unpinned): initial visibility and
+    final-visibility reuse on, 4 frames, 16 pixels, invisible samples kept. *_raytraced turn a pass's Basic normalisation into Raytraced."""
+    s = np.zeros((), PT_DI_VISIBILITY_SETTINGS)
+    s["InitialVisibility"] = 1 if initial else 0
+    s["FinalVisibilityReuse"] = 1 if final_reuse else 0
+    s["FinalVisibilityMaxAge"] = max_age
+    s["FinalVisibilityMaxDistance"] = max_distance
+    s["DiscardInvisibleSamples"] = 1 if discard_invisible else 0
+    s["TemporalRaytraced"] = 1 if temporal_raytraced else 0
+    s["SpatialRaytraced"] = 1 if spatial_raytraced else 0
+    return s
+
+
+def di_unpack_visibility(word):
+    """PtDIReservoir.Visibility (array or scalar) -> (rgb visibility [..., 3] in [0, 1], dx, dy, age): 5 bits per channel decoded / 31,
+    two 6-bit two's-complement pixel offsets, a 4-bit age."""
+    w = np.asarray(word, np.uint32).astype(np.int64)
+    rgb = np.stack([w & 31, (w >> 5) & 31, (w >> 10) & 31], -1) / 31.0
+    dx, dy = (w >> 15) & 63, (w >> 21) & 63
+    return rgb, dx - 2 * (dx & 32), dy - 2 * (dy & 32), (w >> 27) & 15
+
+
+def di_pack_visibility(rgb, dx=0, dy=0, age=0):
+    """the inverse of di_unpack_visibility, with the device's clamps: uint(clamp(v, 0, 1) * 31) in float32, d to +-31, age to 15"""
+    c = (np.clip(np.asarray(rgb, np.float32), np.float32(0), np.float32(1)) * np.float32(31)).astype(np.uint32)
+    dx, dy = int(np.clip(dx, -31, 31)) & 63, int(np.clip(dy, -31, 31)) & 63
+    return int(c[0]) | int(c[1]) << 5 | int(c[2]) << 10 | dx << 15 | dy << 21 | min(int(age), 15) << 27
 
 DI_LOCAL_LIGHT_POWER_CDF, DI_LOCAL_LIGHT_UNIFORM, DI_LOCAL_LIGHT_POWER_RIS, DI_LOCAL_LIGHT_REGIR_RIS = 0, 1, 2, 3
 DI_LOCAL_LIGHT_MODES = {"cdf": DI_LOCAL_LIGHT_POWER_CDF, "uniform": DI_LOCAL_LIGHT_UNIFORM, "power_ris": DI_LOCAL_LIGHT_POWER_RIS,

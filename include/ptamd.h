@@ -399,7 +399,8 @@ int  pt_di_download_lights(PtContext* ctx, PtTriangleLight* host_dst, uint32_t c
  * Off by default: pt_di_render is pt_di_render_with_history(ctx, tx, NULL) and, with both passes off, runs the plain pass.
  * Unsharded contexts only. Each context keeps two reservoir buffers of RenderSize pixels x 32 B (ping-ponged per render).
  * ------------------------------------------------------------------------------------------ */
-enum { PT_DI_BIAS_CORRECTION_OFF = 0, PT_DI_BIAS_CORRECTION_BASIC = 1 };   /* 2 Pairwise, 3 Raytraced: rejected */
+enum { PT_DI_BIAS_CORRECTION_OFF = 0, PT_DI_BIAS_CORRECTION_BASIC = 1 };   /* 2 Pairwise, 3 Raytraced: rejected here; Raytraced is
+                                                                             BASIC + pt_di_set_visibility's *Raytraced flags */
 typedef struct PtDIResamplingSettings {
     uint32_t TemporalResampling;          /* 0 / 1 */
     uint32_t TemporalBiasCorrection;      /* OFF | BASIC (reference default BASIC) */
@@ -424,7 +425,10 @@ typedef struct PtDIReservoir {            /* one per local pixel, row-major */
     uint32_t M;                           /* confidence */
     float    TargetPdf;                   /* p-hat of the sample at this pixel's surface */
     uint32_t Age;                         /* frames since drawn, saturating; informational */
-    uint32_t _pad;
+    uint32_t Visibility;                  /* 0 unless pt_di_set_visibility turned a flag on. bits 0-14: rgb visibility, 5 bits per channel,
+                                             uint(clamp(v, 0, 1) * 31), decoded / 31; 15-20: dx, 21-26: dy (6-bit two's complement, clamped
+                                             to +-31): pixels from where the visibility was traced to this pixel's sample; 27-30: frames
+                                             since it was traced, saturating at 15; 31: 0 */
 } PtDIReservoir;                          /* 32 B */
 
 typedef struct PtDIPreviousTextures {     /* RTXDI::Textures Previous* members, Source/RTXDI.ixx:37-50: last frame's G-buffer, same formats */
@@ -440,6 +444,27 @@ int  pt_di_render_with_history(PtContext* ctx, const PtTextures* textures, const
 int  pt_di_reset_history(PtContext* ctx);                                   /* App::ResetHistory */
 /* the final reservoirs of the last render (next frame's history), RenderSize pixels row-major; synchronises */
 int  pt_di_download_reservoirs(PtContext* ctx, PtDIReservoir* host_dst, uint32_t capacity, uint32_t* out_count);
+
+/* ------------------------------------------------------------------------------------------
+ * visibility in the reservoirs (DIInitialSampling.hlsl:49-54, DIFinalShading.hlsl:32-56, RAB_GetConservativeVisibility /
+ * RAB_GetTemporalConservativeVisibility, RTXDIAppBridge.hlsli:433-459). DESIGN.md section 1, "Reservoir visibility", is the spec; the
+ * defaults are the RTXDI SDK's from memory, unpinned. Takes effect only with reservoir reuse on (the plain pass keeps no reservoir).
+ * Every ray is the final-shading ray: surface to sample point, tmin 1e-3, tmax = max(0, distance - 2e-3).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct PtDIVisibilitySettings {
+    uint32_t InitialVisibility;           /* 0 / 1 (SDK default 1): an occluded initial sample empties the reservoir */
+    uint32_t FinalVisibilityReuse;        /* 0 / 1 (SDK default 1): final shading reuses a stored visibility instead of tracing */
+    uint32_t FinalVisibilityMaxAge;       /* 1..14 frames, default 4 */
+    float    FinalVisibilityMaxDistance;  /* pixels, (0, 31], default 16 */
+    uint32_t DiscardInvisibleSamples;     /* 0 / 1 (SDK default 0): a sample whose traced final visibility is zero leaves the reservoir */
+    uint32_t TemporalRaytraced;           /* 0 / 1: the temporal pass's BASIC normalisation becomes Raytraced */
+    uint32_t SpatialRaytraced;            /* 0 / 1: the spatial pass's BASIC normalisation becomes Raytraced */
+    uint32_t _pad;
+} PtDIVisibilitySettings;                 /* 32 B */
+/* NULL or all flags 0: reservoirs carry no visibility (PtDIReservoir.Visibility stays 0). Out-of-range values are refused and leave the
+ * previous setting active; a changed value resets the history. A *Raytraced flag whose pass is on with a bias correction other than
+ * BASIC is refused by pt_di_render_with_history. */
+int  pt_di_set_visibility(PtContext* ctx, const PtDIVisibilitySettings* settings);
 
 /* ------------------------------------------------------------------------------------------
  * how the initial candidates of the DI pass are drawn (ReSTIRDI.InitialSampling.LocalLight.Mode, Source/MyAppData.h:35-39, 212;

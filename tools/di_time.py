@@ -1,14 +1,16 @@
 """Developer helper: time the direct-lighting pass (HIP events around N back-to-back pt_di_render calls) and one DI-on frame (G-buffer + DI +
 path tracer with IsDIEnabled) against the DI-off frame, per workload. Each workload runs in a child process of its own. --reuse also times
 the pass with temporal + spatial reservoir reuse at the reference's defaults (layouts.di_resampling_settings), history carried over.
---light-sampling times each listed local-light sampling mode (cdf, uniform, power_ris, regir; one JSON line per mode). The workload
+--visibility (with --reuse) adds the pass with visibility in the reservoirs (layouts.di_visibility_settings): initial visibility, + Raytraced in both
+passes, + final-visibility reuse, each with the final shadow rays per pixel counted from the downloaded reservoirs (a shaded reservoir
+whose visibility has age 0 was traced this frame, an older one was reused). --light-sampling times each listed local-light sampling mode (cdf, uniform, power_ris, regir; one JSON line per mode). The workload
 emitter_field is scenes.emitter_field(256) (131 k emissive triangles) at 1920 x 1080, 1 spp, 1 bounce.
-usage: tools/di_time.py [--workloads c2,c3,c5,emitter_field] [--samples 8] [--n 20] [--reuse] [--light-sampling cdf,regir]"""
+usage: tools/di_time.py [--workloads c2,c3,c5,emitter_field] [--samples 8] [--n 20] [--reuse [--visibility]] [--light-sampling cdf,regir]"""
 import argparse, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def child(w, samples, n, reuse, modes):
+def child(w, samples, n, reuse, modes, visibility=False):
     sys.path.insert(0, ROOT)
     import torch
     import __graft_entry__ as ge
@@ -62,6 +64,25 @@ def child(w, samples, n, reuse, modes):
         r.render(gs, di_samples=samples, di_reuse=L.di_resampling_settings()); ctx.sync()     # Previous* G-buffer, first history
         r.direct_lighting.Render(tlas); ctx.sync()
         out["di_reuse_ms"] = timed(lambda i: r.direct_lighting.Render(tlas), n)
+
+        def final_rays():
+            res = r.direct_lighting.download_reservoirs()
+            shaded = (res["LightIndex"] != 0xFFFFFFFF) & (res["W"] > 0)
+            age = L.di_unpack_visibility(res["Visibility"])[3]
+            return float((shaded & (age == 0)).sum()) / (W * H), float((shaded & (age > 0)).sum()) / (W * H)
+        out["final_rays_per_pixel"] = final_rays()[0]
+        rows = [("initial", L.di_visibility_settings(final_reuse=False)),
+                ("initial_raytraced", L.di_visibility_settings(final_reuse=False, temporal_raytraced=True, spatial_raytraced=True)),
+                ("initial_raytraced_final_reuse", L.di_visibility_settings(temporal_raytraced=True, spatial_raytraced=True))] if visibility else []
+        for label, vs in rows:
+            r.direct_lighting.SetVisibility(vs)
+            for _ in range(6):                                 # the history refills; stored visibilities reach every age up to MaxAge
+                r.direct_lighting.Render(tlas)
+            ctx.sync()
+            ms = timed(lambda i: r.direct_lighting.Render(tlas), n)
+            traced, reused = final_rays()
+            out["visibility_" + label] = {"di_reuse_ms": ms, "final_rays_per_pixel": traced, "final_reused_per_pixel": reused}
+        r.direct_lighting.SetVisibility(None)
         r.direct_lighting.SetResampling(None)
     print(json.dumps(out))
     ctx.close()
@@ -71,13 +92,13 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", default=None); ap.add_argument("--workloads", default="c2,c3,c5")
     ap.add_argument("--samples", type=int, default=8); ap.add_argument("--n", type=int, default=20); ap.add_argument("--reuse", action="store_true")
-    ap.add_argument("--light-sampling", default="cdf")
+    ap.add_argument("--light-sampling", default="cdf"); ap.add_argument("--visibility", action="store_true")
     a = ap.parse_args()
     if a.child:
-        child(a.child, a.samples, a.n, a.reuse, a.light_sampling.split(",")); sys.exit(0)
+        child(a.child, a.samples, a.n, a.reuse, a.light_sampling.split(","), a.visibility); sys.exit(0)
     for w in a.workloads.split(","):
         p = subprocess.run([sys.executable, __file__, "--child", w, "--samples", str(a.samples), "--n", str(a.n),
-                            "--light-sampling", a.light_sampling] + (["--reuse"] if a.reuse else []), stdout=subprocess.PIPE,
+                            "--light-sampling", a.light_sampling] + (["--reuse"] if a.reuse else []) + (["--visibility"] if a.visibility else []), stdout=subprocess.PIPE,
                            stderr=subprocess.PIPE, text=True, timeout=600)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]
         print("\n".join(line) if line else "%s FAILED (exit %d) %s" % (w, p.returncode, p.stderr[-400:]), flush=True)
