@@ -9,19 +9,21 @@
 //   k_di_regir_build               <- ReGIRPresampling.hlsl, Grid mode: the ReGIR cells (REGIR_RIS)
 //   k_di<Source>                   <- DIInitialSampling (local lights only, streaming RIS) + DIFinalShading, no temporal /
 //                                     spatial reuse (RTXDIAppBridge.hlsli RAB_GetGBufferSurface, RAB_Surface::Shade, GetFinalVisibility)
-//   k_di_initial_temporal<..., Source> <- DIInitialSampling + DITemporalResampling (boiling filter), with reservoir reuse on
+//   k_di_initial_temporal<..., VIS, Source> <- DIInitialSampling + DITemporalResampling (boiling filter), with reservoir reuse on
 //   k_di_spatial_shade<..., VIS>   <- DISpatialResampling + DIFinalShading
-//   k_di_initial_temporal_vis, k_di_spatial_shade<..., VIS != 0> <- the same with visibility in the reservoirs (pt_di_set_visibility):
+//   both with VIS != 0             <- the same with visibility in the reservoirs (pt_di_set_visibility):
 //                                     initial visibility (DIInitialSampling.hlsl:49-54), Raytraced bias correction
 //                                     (RAB_GetConservativeVisibility / RAB_GetTemporalConservativeVisibility), the final-visibility store and
 //                                     reuse and discardInvisibleSamples (DIFinalShading.hlsl:32-56)
 // Source is where initial sampling draws its candidates from: DIPowerCDF (the prefix sum, the default) or DISampling (Uniform,
-// Power_RIS, ReGIR). Every kernel reads its surfaces with di_surface, draws with di_initial and shades with di_final.
+// Power_RIS, ReGIR). Every kernel reads its surfaces with di_surface, draws with di_initial and shades with di_shadow_ray +
+// di_final_write.
 // DESIGN.md section 1 ("Direct lighting") is the arithmetic spec: seeding, draw order, triangle mapping.
 #include "pt_internal.hpp"
 
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "pt_shade.hpp"
 
@@ -456,41 +458,6 @@ PT_DEV void di_final_write(const DIArgs& a, size_t pi, float dist, v3 vis, v3 di
     ((ushort4*)tx.Specular)[pi] = make_ushort4(f32_to_f16(spc.x), f32_to_f16(spc.y), f32_to_f16(spc.z), f32_to_f16(dist));
 }
 
-// final shading (DIFinalShading.hlsl): one coloured visibility ray, CreateVisibilityRay with offset 1e-3; outputs :78-103
-PT_DEV void di_final(const DIArgs& a, BlobView bv, const AlphaContext& ac, DeviceCounters* counters, uint2* ldsStack, size_t pi, v3 P, v3 posSel,
-                     v3 difSel, v3 spcSel, float W)
-{
-    const PtTextures& tx = a.tx;
-    const v3 d = posSel - P;
-    const float dist = sqrtf(dot(d, d));
-    const v3 dir = V3(d.x / dist, d.y / dist, d.z / dist);
-    uint2 spill[kStackSize - kLdsStackDepth];
-    GroupStack<kLdsStackDepth> stack; stack.init((PT_LDS_AS void*)ldsStack, spill);
-    BlobReader<false> blob; blob.p = bv.base;
-    TraceStats st; st.nodes = 0; st.tris = 0; st.overflow = 0;
-    v3 vis;
-    trace_single<false, false, true>(blob, bv, ac, P, dir, 1e-3f, fmaxf(0.0f, dist - 2e-3f), stack, &st, &vis);
-    if (st.overflow) atomicAdd(&counters->stackOverflows, st.overflow);
-    if (vis.x == 0.0f && vis.y == 0.0f && vis.z == 0.0f) return;
-    const v3 dif = V3(difSel.x * vis.x * W, difSel.y * vis.y * W, difSel.z * vis.z * W);
-    const v3 spc = V3(spcSel.x * vis.x * W, spcSel.y * vis.y * W, spcSel.z * vis.z * W);
-    const v3 rad = dif + spc;
-    if ((rad.x == 0.0f && rad.y == 0.0f && rad.z == 0.0f) || !finite3(rad)) return;
-
-    if (a.lastPass && a.denoiser <= PT_DENOISER_DLSS_RAY_RECONSTRUCTION) {
-        ushort4* R = (ushort4*)tx.Radiance;
-        const ushort4 o = R[pi];
-        const v3 sum = V3(f16_to_f32(o.x) + rad.x, f16_to_f32(o.y) + rad.y, f16_to_f32(o.z) + rad.z);
-        R[pi] = make_ushort4(f32_to_f16(sum.x), f32_to_f16(sum.y), f32_to_f16(sum.z), o.w);
-        if (tx.RadianceF32) ((float4*)tx.RadianceF32)[pi] = make_float4(sum.x, sum.y, sum.z, 0.0f);
-        if (a.denoiser == PT_DENOISER_DLSS_RAY_RECONSTRUCTION && tx.SpecularHitDistance && (spc.x > 0.0f || spc.y > 0.0f || spc.z > 0.0f))
-            ((uint16_t*)tx.SpecularHitDistance)[pi] = f32_to_f16(dist);
-        return;
-    }
-    ((ushort4*)tx.Diffuse)[pi] = make_ushort4(f32_to_f16(dif.x), f32_to_f16(dif.y), f32_to_f16(dif.z), f32_to_f16(dist));
-    ((ushort4*)tx.Specular)[pi] = make_ushort4(f32_to_f16(spc.x), f32_to_f16(spc.y), f32_to_f16(spc.z), f32_to_f16(dist));
-}
-
 // The pixel of a thread (x, local row): a wave covers an 8 x 8 square of the block's 16 x 16 (as k_gbuffer), so the rays of a wave stay together.
 PT_DEV void di_pixel(uint32_t& x, uint32_t& ly)
 {
@@ -514,7 +481,9 @@ __global__ __launch_bounds__(256) void k_di(DIArgs a, Source source, BlobView bv
     di_initial(a, source, s, x, y, total, i0);
     if (!(i0.p > 0.0f)) return;
     __shared__ uint2 ldsStack[kLdsStackDepth * 256];
-    di_final(a, bv, ac, counters, ldsStack, pi, s.P, i0.pos, i0.dif, i0.spc, i0.wsum / (float)a.samples / i0.p);   // W = (sum w / M) / target(y)
+    float dist; v3 vis;
+    di_shadow_ray(bv, ac, counters, ldsStack, s.P, i0.pos, dist, vis);
+    di_final_write(a, pi, dist, vis, i0.dif, i0.spc, i0.wsum / (float)a.samples / i0.p);   // W = (sum w / M) / target(y)
 }
 
 // ---- reservoir reuse (DITemporalResampling / DISpatialResampling; DESIGN.md section 1, "Reservoir reuse") --------------------------------
@@ -559,6 +528,11 @@ struct DIVisArgs {
     uint32_t initial, maxAge, discard;              // maxAge 0: no final-visibility reuse
     float maxDistance;
 };
+// VIS of the reuse kernels: 0 off; kDIVisOn: the reservoirs carry the Visibility word; | kDIVisRaytraced: Basic bias correction traces
+constexpr uint32_t kDIVisOn = 1u, kDIVisRaytraced = 2u;
+// The settings reach the visibility-enabled instantiations as one trailing DIVisArgs; without VIS a kernel's arguments end before it.
+PT_DEV const DIVisArgs* di_vis_args() { return nullptr; }
+PT_DEV const DIVisArgs* di_vis_args(const DIVisArgs& va) { return &va; }
 // PtDIReservoir.Visibility: rgb 5 bits each | dx, dy 6-bit two's complement clamped to +-31 | age 4 bits saturating
 PT_DEV uint32_t di_vis_pack(v3 vis)
 {
@@ -624,12 +598,12 @@ PT_DEV float di_target_of(const DIArgs& a, const DISurface& s, uint32_t li, floa
     return di_target(a, s, li, U, V, pos, dif, spc, power);
 }
 
-// the temporal pass's history search: the motion-vector position, then eight jittered ones (draws from the temporal stream); (hx, hy) is
-// the first whose previous surface sp passes the neighbour test against the expected depth, or stays (-1, -1)
-PT_DEV void di_find_history(const DIReuseArgs& r, const DISurface& s, uint32_t x, uint32_t y, size_t pi, uint32_t& rng, DISurface& sp, int& hx, int& hy)
+// the temporal pass's history search: the motion-vector position, then eight jittered ones (draws from the temporal stream); returns the
+// pixel index in the w x h previous frame of the first whose previous surface sp passes the neighbour test against the expected depth, or -1.
+// The position comes back in one int: as two by-reference outputs it cost the Basic instantiations a wave per SIMD.
+PT_DEV int di_find_history(const DIReuseArgs& r, const DISurface& s, int w, int h, uint32_t x, uint32_t y, size_t pi, uint32_t& rng, DISurface& sp)
 {
     const DIArgs& a = r.d;
-    const int w = (int)a.fv.width, h = (int)a.fv.height;
     const ushort4 mv = ((const ushort4*)a.tx.MotionVector)[pi];
     const float expected = s.depth + f16_to_f32(mv.z);
     const float fx = fminf(fmaxf((float)x + f16_to_f32(mv.x), -65536.0f), 65536.0f), fy = fminf(fmaxf((float)y + f16_to_f32(mv.y), -65536.0f), 65536.0f);
@@ -641,9 +615,9 @@ PT_DEV void di_find_history(const DIReuseArgs& r, const DISurface& s, uint32_t x
         if (qx < 0 || qy < 0 || qx >= w || qy >= h) continue;
         if (!di_surface(a, r.prev, (size_t)qy * w + qx, qx, qy, sp)) continue;
         if (!di_similar(s, sp, expected, r.tNormal, r.tDepth)) continue;
-        hx = qx; hy = qy;
-        break;
+        return qy * w + qx;
     }
+    return -1;
 }
 // boiling filter: the tile's mean of the nonzero weights, a 64-lane butterfly (every lane of the wave takes part)
 PT_DEV void di_boiling(const DIReuseArgs& r, bool valid, PtDIReservoir& res)
@@ -657,9 +631,18 @@ PT_DEV void di_boiling(const DIReuseArgs& r, bool valid, PtDIReservoir& res)
 // Initial sampling from a candidate source fused with temporal reuse: the temporal step at a pixel reads only that pixel's fresh reservoir
 // and last frame's data. TEMPORAL = false writes the initial reservoirs (the spatial pass's input). The boiling filter is a 64-lane
 // butterfly over the wave's 8 x 8 tile, so every lane stays to the end.
-template <bool TEMPORAL, bool BASIC, typename Source>
-__global__ __launch_bounds__(256) void k_di_initial_temporal(DIReuseArgs r, Source source)
+// VIS != 0 (pt_di_set_visibility, encoded as above): initial visibility traces the selected initial sample's ray, and blocked empties the
+// reservoir; a selected history sample brings its Visibility word along, moved by the pixel offset and one frame older. kDIVisRaytraced
+// (with BASIC): p at the previous surface counts as 0 when the ray from the current surface to the selected sample is blocked. The two
+// rays of a lane depend on each other (the second sample is chosen after the first ray), so they are the two trips of one loop that all
+// lanes walk together: lanes without a ray on a trip trace nothing, and every lane reaches the boiling filter's butterfly. The loop is
+// unrolled, i.e. two inlined walks: kept rolled around one trace site the kernel needs 185 VGPRs (2 waves per SIMD), unrolled 137
+// (3 waves), scratch 464 B / lane either way. Without VIS there is no loop, no ray and no group stack in LDS.
+template <bool TEMPORAL, bool BASIC, uint32_t VIS, typename Source, typename... Extra>
+__global__ __launch_bounds__(256) void k_di_initial_temporal(DIReuseArgs r, Source source, Extra... extra)
 {
+    constexpr bool CARRY = VIS != 0u, RAYTRACED = (VIS & kDIVisRaytraced) != 0u;
+    static_assert(!RAYTRACED || (TEMPORAL && BASIC), "the raytraced normalisation is Basic bias correction's");
     const DIArgs& a = r.d;
     uint32_t x, y; di_pixel(x, y);
     const bool inside = x < a.fv.width && y < a.fv.localRows;             // unsharded: local row = global row
@@ -667,91 +650,46 @@ __global__ __launch_bounds__(256) void k_di_initial_temporal(DIReuseArgs r, Sour
     PtDIReservoir res = di_empty(0u);
     DISurface s;
     const bool valid = inside && di_surface(a, a.view, pi, x, y, s);
-    if (valid) {
-        res.M = a.samples;
-        const float total = *a.total;
-        if (total > 0.0f && isfinite(total)) {
-            DIInitial i0;
-            di_initial(a, source, s, x, y, total, i0);
-            if (i0.p > 0.0f) { res.LightIndex = i0.li; res.U = i0.u; res.V = i0.v; res.W = i0.wsum / (float)a.samples / i0.p; res.TargetPdf = i0.p; }
-        }
-        if (TEMPORAL) {
-            const int w = (int)a.fv.width, h = (int)a.fv.height;
-            uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDITemporalSalt);
-            DISurface sp;
-            int hx = -1, hy = -1;
-            if (r.haveHistory) {
-                const ushort4 mv = ((const ushort4*)a.tx.MotionVector)[pi];
-                const float expected = s.depth + f16_to_f32(mv.z);
-                const float fx = fminf(fmaxf((float)x + f16_to_f32(mv.x), -65536.0f), 65536.0f), fy = fminf(fmaxf((float)y + f16_to_f32(mv.y), -65536.0f), 65536.0f);
-                const int px = (int)rintf(fx), py = (int)rintf(fy);            // HLSL round: to nearest even
-                for (int i = 0; i < 9; i++) {
-                    int qx = px, qy = py;
-                    if (i) { const float rx = rng_float(rng), ry = rng_float(rng); qx += (int)((rx - 0.5f) * 6.0f); qy += (int)((ry - 0.5f) * 6.0f); }
-                    di_reflect(qx, qy, w, h);
-                    if (qx < 0 || qy < 0 || qx >= w || qy >= h) continue;
-                    if (!di_surface(a, r.prev, (size_t)qy * w + qx, qx, qy, sp)) continue;
-                    if (!di_similar(s, sp, expected, r.tNormal, r.tDepth)) continue;
-                    hx = qx; hy = qy;
-                    break;
-                }
-            }
-            // combine(s, R0, 0.5, p(y0)) selects R0; then combine(s, H, rc, p(yH)) with the draw after every search draw
-            const uint32_t Mcur = res.M;
-            float wsum = res.TargetPdf * res.W * (float)res.M;
-            PtDIReservoir H = di_empty(0u);
-            bool fromH = false;
-            if (hx >= 0) {
-                H = di_load(r.in, (size_t)hy * w + hx);
-                H.M = min(H.M, r.maxHistory * Mcur);
-                const float pH = di_target_of(a, s, H.LightIndex, H.U, H.V);
-                const float rc = rng_float(rng);
-                const float wH = pH * H.W * (float)H.M;
-                wsum += wH;
-                if (rc * wsum < wH) { res.LightIndex = H.LightIndex; res.U = H.U; res.V = H.V; res.TargetPdf = pH; res.Age = H.Age == ~0u ? ~0u : H.Age + 1u; fromH = true; }
-                res.M = Mcur + H.M;
-            }
-            const float p = res.TargetPdf;
-            if (!(p > 0.0f)) {
-                res = di_empty(res.M);
-            } else if (BASIC) {                                             // p at the previous surface: no visibility
-                const float pPrev = hx >= 0 ? di_target_of(a, sp, res.LightIndex, res.U, res.V) : 0.0f;
-                const float den = p * ((float)Mcur * p + (float)H.M * pPrev);
-                res.W = den > 0.0f ? wsum * (fromH ? pPrev : p) / den : 0.0f;
-            } else {
-                res.W = wsum / (p * (float)res.M);
-            }
-        }
-    }
-    if (TEMPORAL && r.boiling) {                                           // boiling filter: the tile's mean of the nonzero weights
-        const bool nz = valid && res.W > 0.0f;
-        float sum = nz ? res.W : 0.0f, cnt = nz ? 1.0f : 0.0f;
-        for (int m = 1; m < 64; m <<= 1) { sum += __shfl_xor(sum, m); cnt += __shfl_xor(cnt, m); }
-        if (cnt > 0.0f && res.W > sum / cnt * r.boilingMul) res = di_empty(0u);
-    }
-    if (inside) di_store(r.out, pi, res);
-}
-
-// k_di_initial_temporal with reservoir visibility on (pt_di_set_visibility). Initial visibility: the selected initial sample's ray; blocked
-// empties the reservoir. RAYTRACED (with BASIC): p at the previous surface counts as 0 when the ray from the current surface to the
-// selected sample is blocked. The two rays of a lane depend on each other (the second sample is chosen after the first ray), so they are
-// the two trips of one loop that all lanes walk together: lanes without a ray on a trip trace nothing, and every lane reaches the boiling
-// filter's butterfly. The loop is unrolled, i.e. two inlined walks: kept rolled around one trace site the kernel needs 185 VGPRs (2 waves
-// per SIMD), unrolled 137 (3 waves), scratch 464 B / lane either way. A selected history sample brings its Visibility
-// word along, moved by the pixel offset and one frame older.
-template <bool TEMPORAL, bool BASIC, bool RAYTRACED, typename Source>
-__global__ __launch_bounds__(256) void k_di_initial_temporal_vis(DIReuseArgs r, Source source, DIVisArgs va)
-{
-    __shared__ uint2 ldsStack[kLdsStackDepth * 256];
-    const DIArgs& a = r.d;
-    uint32_t x, y; di_pixel(x, y);
-    const bool inside = x < a.fv.width && y < a.fv.localRows;
-    const size_t pi = (size_t)y * a.fv.width + x;
-    PtDIReservoir res = di_empty(0u);
-    DISurface s;
-    const bool valid = inside && di_surface(a, a.view, pi, x, y, s);
     v3 target = V3(0.0f, 0.0f, 0.0f);                                      // where this trip's ray goes
     bool want = false;
+    uint32_t Mcur = 0, MH = 0;                                            // Basic's normalisation waits for the second ray
+    float wsum = 0.0f, pPrev = 0.0f;
+    bool fromH = false, basicPending = false;
+    // the temporal step of a valid pixel. Without VIS it runs inside the block of the initial sampling: behind the block, as with VIS, it
+    // took three of those instantiations one VGPR more
+    auto temporal = [&]() {
+        const int w = (int)a.fv.width, h = (int)a.fv.height;
+        uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDITemporalSalt);
+        DISurface sp;
+        const int hi = r.haveHistory ? di_find_history(r, s, w, h, x, y, pi, rng, sp) : -1;
+        // combine(s, R0, 0.5, p(y0)) selects R0; then combine(s, H, rc, p(yH)) with the draw after every search draw
+        Mcur = res.M;
+        wsum = res.TargetPdf * res.W * (float)res.M;
+        if (hi >= 0) {
+            PtDIReservoir H = di_load<CARRY>(r.in, (size_t)hi);
+            H.M = min(H.M, r.maxHistory * Mcur);
+            const float pH = di_target_of(a, s, H.LightIndex, H.U, H.V);
+            const float rc = rng_float(rng);
+            const float wH = pH * H.W * (float)H.M;
+            wsum += wH;
+            if (rc * wsum < wH) {
+                res.LightIndex = H.LightIndex; res.U = H.U; res.V = H.V; res.TargetPdf = pH; res.Age = H.Age == ~0u ? ~0u : H.Age + 1u; fromH = true;
+                if constexpr (CARRY) res.Visibility = di_vis_carry(H.Visibility, hi % w - (int)x, hi / w - (int)y, 1u);
+            }
+            MH = H.M;
+            res.M = Mcur + H.M;
+        }
+        const float p = res.TargetPdf;
+        if (!(p > 0.0f)) {
+            res = di_empty(res.M);
+        } else if (BASIC) {                                             // p at the previous surface: no visibility but RAYTRACED's
+            pPrev = hi >= 0 ? di_target_of(a, sp, res.LightIndex, res.U, res.V) : 0.0f;
+            basicPending = true;
+            if (RAYTRACED && hi >= 0 && pPrev > 0.0f) { want = true; target = di_sample_point(a, res.LightIndex, res.U, res.V); }
+        } else {
+            res.W = wsum / (p * (float)res.M);
+        }
+    };
     if (valid) {
         res.M = a.samples;
         const float total = *a.total;
@@ -760,53 +698,22 @@ __global__ __launch_bounds__(256) void k_di_initial_temporal_vis(DIReuseArgs r, 
             di_initial(a, source, s, x, y, total, i0);
             if (i0.p > 0.0f) {
                 res.LightIndex = i0.li; res.U = i0.u; res.V = i0.v; res.W = i0.wsum / (float)a.samples / i0.p; res.TargetPdf = i0.p;
-                target = i0.pos; want = va.initial != 0u;
+                if constexpr (CARRY) { target = i0.pos; want = di_vis_args(extra...)->initial != 0u; }
             }
         }
+        if constexpr (TEMPORAL && !CARRY) temporal();
     }
-    constexpr int kTrips = TEMPORAL && BASIC && RAYTRACED ? 2 : 1;
-    uint32_t Mcur = 0, MH = 0;
-    float wsum = 0.0f, pPrev = 0.0f;
-    bool fromH = false, basicPending = false;
-    #pragma unroll
-    for (int trip = 0; trip < kTrips; trip++) {
-        bool blocked = false;
-        if (want) { float dist; v3 vis; blocked = di_shadow_ray(va.bv, va.ac, va.counters, ldsStack, s.P, target, dist, vis); }
-        want = false;
-        if (trip == 1) { if (blocked) pPrev = 0.0f; continue; }
-        if (blocked) res = di_empty(a.samples);                               // initial visibility
-        if (TEMPORAL && valid) {
-            const int w = (int)a.fv.width;
-            uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDITemporalSalt);
-            DISurface sp;
-            int hx = -1, hy = -1;
-            if (r.haveHistory) di_find_history(r, s, x, y, pi, rng, sp, hx, hy);
-            Mcur = res.M;
-            wsum = res.TargetPdf * res.W * (float)res.M;
-            if (hx >= 0) {
-                PtDIReservoir H = di_load<true>(r.in, (size_t)hy * w + hx);
-                H.M = min(H.M, r.maxHistory * Mcur);
-                const float pH = di_target_of(a, s, H.LightIndex, H.U, H.V);
-                const float rc = rng_float(rng);
-                const float wH = pH * H.W * (float)H.M;
-                wsum += wH;
-                if (rc * wsum < wH) {
-                    res.LightIndex = H.LightIndex; res.U = H.U; res.V = H.V; res.TargetPdf = pH; res.Age = H.Age == ~0u ? ~0u : H.Age + 1u; fromH = true;
-                    res.Visibility = di_vis_carry(H.Visibility, hx - (int)x, hy - (int)y, 1u);
-                }
-                MH = H.M;
-                res.M = Mcur + H.M;
-            }
-            const float p = res.TargetPdf;
-            if (!(p > 0.0f)) {
-                res = di_empty(res.M);
-            } else if (BASIC) {
-                pPrev = hx >= 0 ? di_target_of(a, sp, res.LightIndex, res.U, res.V) : 0.0f;
-                basicPending = true;
-                if (RAYTRACED && hx >= 0 && pPrev > 0.0f) { want = true; target = di_sample_point(a, res.LightIndex, res.U, res.V); }
-            } else {
-                res.W = wsum / (p * (float)res.M);
-            }
+    if constexpr (CARRY) {
+        __shared__ uint2 ldsStack[kLdsStackDepth * 256];
+        const DIVisArgs* va = di_vis_args(extra...);
+        #pragma unroll
+        for (int trip = 0; trip < (RAYTRACED ? 2 : 1); trip++) {
+            bool blocked = false;
+            if (want) { float dist; v3 vis; blocked = di_shadow_ray(va->bv, va->ac, va->counters, ldsStack, s.P, target, dist, vis); }
+            want = false;
+            if (trip == 1) { if (blocked) pPrev = 0.0f; continue; }
+            if (blocked) res = di_empty(a.samples);                               // initial visibility
+            if (TEMPORAL && valid) temporal();
         }
     }
     if (basicPending) {
@@ -815,17 +722,12 @@ __global__ __launch_bounds__(256) void k_di_initial_temporal_vis(DIReuseArgs r, 
         res.W = den > 0.0f ? wsum * (fromH ? pPrev : p) / den : 0.0f;
     }
     if (TEMPORAL && r.boiling) di_boiling(r, valid, res);
-    if (inside) di_store<true>(r.out, pi, res);
+    if (inside) di_store<CARRY>(r.out, pi, res);
 }
 
 // Spatial reuse, then final shading in the same thread. SPATIAL = false: the final reservoir is the input (temporal-only).
-// VIS (pt_di_set_visibility): 0 off; kDIVisOn: the reservoirs carry the Visibility word and final shading may reuse it; | kDIVisRaytraced
-// (with BASIC): in the normalisation a neighbour's p counts as 0 when the ray from that neighbour's surface to the selected sample is
-// blocked -- one trace site inside that loop.
-constexpr uint32_t kDIVisOn = 1u, kDIVisRaytraced = 2u;
-// The settings reach the visibility-enabled instantiations as one trailing DIVisArgs; without VIS the kernel's arguments are the four.
-PT_DEV const DIVisArgs* di_vis_args() { return nullptr; }
-PT_DEV const DIVisArgs* di_vis_args(const DIVisArgs& va) { return &va; }
+// VIS & kDIVisRaytraced (with BASIC): in the normalisation a neighbour's p counts as 0 when the ray from that neighbour's surface to the
+// selected sample is blocked -- one trace site inside that loop.
 template <bool SPATIAL, bool BASIC, uint32_t VIS, typename... Extra>
 __global__ __launch_bounds__(256) void k_di_spatial_shade(DIReuseArgs r, BlobView bv, AlphaContext ac, DeviceCounters* counters, Extra... extra)
 {
@@ -894,34 +796,31 @@ __global__ __launch_bounds__(256) void k_di_spatial_shade(DIReuseArgs r, BlobVie
         }
         c = o;
     }
-    if constexpr (!CARRY) {
-        di_store(r.out, pi, c);
-        if (c.LightIndex >= a.count || !(c.W > 0.0f)) return;
-        v3 pos, dif, spc;
-        float power;
-        di_target(a, s, c.LightIndex, c.U, c.V, pos, dif, spc, power);
-        di_final(a, bv, ac, counters, ldsStack, pi, s.P, pos, dif, spc, c.W);
+    // final shading. The stored reservoir is the final one: next frame's history. With the visibility word a young, nearby one stands in
+    // for the ray and the reservoir is stored as it is; otherwise the traced visibility is stored (d = 0, age 0). Without the word the
+    // ray changes nothing in the reservoir, which is stored ahead of it.
+    const bool lit = c.LightIndex < a.count && c.W > 0.0f;
+    if (!CARRY || !lit) di_store<CARRY>(r.out, pi, c);
+    if (!lit) return;
+    v3 pos, dif, spc, vis;
+    float power, dist;
+    const float W = c.W;
+    di_target(a, s, c.LightIndex, c.U, c.V, pos, dif, spc, power);
+    bool reuse = false;
+    if constexpr (CARRY) { const DIVisArgs* va = di_vis_args(extra...); reuse = va->maxAge != 0u && di_vis_reusable(c.Visibility, va->maxAge, va->maxDistance); }
+    if (reuse) {
+        const v3 d = pos - s.P;
+        dist = sqrtf(dot(d, d));
+        vis = di_vis_colour(c.Visibility);
     } else {
-        // final shading with the visibility word: a young, nearby one stands in for the ray and the reservoir is stored as it is; otherwise the
-        // traced visibility is stored (d = 0, age 0). The stored reservoir is the final one: next frame's history.
-        const DIVisArgs* va = di_vis_args(extra...);
-        if (c.LightIndex >= a.count || !(c.W > 0.0f)) { di_store<true>(r.out, pi, c); return; }
-        v3 pos, dif, spc, vis;
-        float power, dist;
-        const float W = c.W;
-        di_target(a, s, c.LightIndex, c.U, c.V, pos, dif, spc, power);
-        if (va->maxAge != 0u && di_vis_reusable(c.Visibility, va->maxAge, va->maxDistance)) {
-            const v3 d = pos - s.P;
-            dist = sqrtf(dot(d, d));
-            vis = di_vis_colour(c.Visibility);
-        } else {
-            di_shadow_ray(bv, ac, counters, ldsStack, s.P, pos, dist, vis);
+        di_shadow_ray(bv, ac, counters, ldsStack, s.P, pos, dist, vis);
+        if constexpr (CARRY) {
             c.Visibility = di_vis_pack(vis);
-            if (va->discard != 0u && vis.x == 0.0f && vis.y == 0.0f && vis.z == 0.0f) c = di_empty(c.M);
+            if (di_vis_args(extra...)->discard != 0u && vis.x == 0.0f && vis.y == 0.0f && vis.z == 0.0f) c = di_empty(c.M);
         }
-        di_store<true>(r.out, pi, c);
-        di_final_write(a, pi, dist, vis, dif, spc, W);
     }
+    if constexpr (CARRY) di_store<true>(r.out, pi, c);
+    di_final_write(a, pi, dist, vis, dif, spc, W);
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
@@ -1067,6 +966,21 @@ template <typename F> static void di_with_source(const DISampling& ls, F&& f)
     else f(ls);
 }
 
+// calls f with the compile-time form of a reuse pass, (pass on, Basic bias correction, VIS), and with va behind it when VIS != 0. The
+// forms are {(0, 0), (1, 0), (1, 1)} x {0, kDIVisOn} and (1, 1, kDIVisOn | kDIVisRaytraced): di_check_args refuses raytraced without Basic.
+template <typename F> static void di_with_form(bool on, bool basic, bool vis, bool raytraced, const DIVisArgs& va, F&& f)
+{
+    using std::integral_constant;
+    auto with_vis = [&](auto ON, auto BASIC) {
+        if (vis) f(ON, BASIC, integral_constant<uint32_t, kDIVisOn>{}, va);
+        else f(ON, BASIC, integral_constant<uint32_t, 0u>{});
+    };
+    if (!on) with_vis(std::false_type{}, std::false_type{});
+    else if (raytraced) f(std::true_type{}, std::true_type{}, integral_constant<uint32_t, kDIVisOn | kDIVisRaytraced>{}, va);
+    else if (basic) with_vis(std::true_type{}, std::true_type{});
+    else with_vis(std::true_type{}, std::false_type{});
+}
+
 // reservoir reuse: k_di_initial_temporal (last frame's B -> A), k_di_spatial_shade (A -> B); B is next frame's history
 static int di_launch_reuse(Context& c, const DIArgs& a, const DISampling& ls, const PtDIPreviousTextures* prev, dim3 grid, const AlphaContext& ac)
 {
@@ -1112,28 +1026,15 @@ static int di_launch_reuse(Context& c, const DIArgs& a, const DISampling& ls, co
     va.initial = vs.InitialVisibility; va.maxAge = vs.FinalVisibilityReuse ? vs.FinalVisibilityMaxAge : 0u; va.discard = vs.DiscardInvisibleSamples;
     va.maxDistance = vs.FinalVisibilityMaxDistance;
     di_with_source(ls, [&](auto source) {
-        using S = decltype(source);
-        if (vis) {
-            if (!temporal) k_di_initial_temporal_vis<false, false, false, S><<<grid, 256, 0, c.stream>>>(r, source, va);
-            else if (tr) k_di_initial_temporal_vis<true, true, true, S><<<grid, 256, 0, c.stream>>>(r, source, va);
-            else if (tb) k_di_initial_temporal_vis<true, true, false, S><<<grid, 256, 0, c.stream>>>(r, source, va);
-            else k_di_initial_temporal_vis<true, false, false, S><<<grid, 256, 0, c.stream>>>(r, source, va);
-        }
-        else if (!temporal) k_di_initial_temporal<false, false, S><<<grid, 256, 0, c.stream>>>(r, source);
-        else if (tb) k_di_initial_temporal<true, true, S><<<grid, 256, 0, c.stream>>>(r, source);
-        else k_di_initial_temporal<true, false, S><<<grid, 256, 0, c.stream>>>(r, source);
+        di_with_form(temporal, tb, vis, tr, va, [&](auto T, auto B, auto V, auto... extra) {
+            k_di_initial_temporal<T(), B(), V(), decltype(source)><<<grid, 256, 0, c.stream>>>(r, source, extra...);
+        });
     });
     API_HIP(&c, hipGetLastError());
     r.in = c.diResA.data(); r.out = c.diResB.data();
-    if (vis) {
-        if (!spatial) k_di_spatial_shade<false, false, kDIVisOn><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data(), va);
-        else if (sr) k_di_spatial_shade<true, true, kDIVisOn | kDIVisRaytraced><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data(), va);
-        else if (sb) k_di_spatial_shade<true, true, kDIVisOn><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data(), va);
-        else k_di_spatial_shade<true, false, kDIVisOn><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data(), va);
-    }
-    else if (!spatial) k_di_spatial_shade<false, false, 0u><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data());
-    else if (sb) k_di_spatial_shade<true, true, 0u><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data());
-    else k_di_spatial_shade<true, false, 0u><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data());
+    di_with_form(spatial, sb, vis, sr, va, [&](auto S, auto B, auto V, auto... extra) {
+        k_di_spatial_shade<S(), B(), V()><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data(), extra...);
+    });
     API_HIP(&c, hipGetLastError());
     c.diHistoryValid = true; c.diHistorySize[0] = fv.width; c.diHistorySize[1] = fv.height; c.diHistoryLightKey = c.lightListKey;
     c.diResCount = (uint32_t)npix;

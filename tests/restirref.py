@@ -1,7 +1,9 @@
 """Float64 restatement of the reservoir-reuse rules of the DI pass ("Reservoir reuse"): the RNG streams, the
 neighbour-offset table, view reflection, surface position reconstruction, the neighbour and material tests, combine and the two
-normalisations, and the boiling filter. Each rule that the device computes in float32 with a discrete outcome (pixel positions, the
-offset table, the boiling sum) is restated with the same float32 steps."""
+normalisations, and the boiling filter; the temporal and spatial passes over whole frames, which also carry the reservoirs' Visibility
+word ("Reservoir visibility") and take the Raytraced normalisation's occluders (the ray itself, initial visibility and final shading:
+tests/restirvisref.py). Each rule that the device computes in float32 with a discrete outcome (pixel positions, the offset table, the
+boiling sum) is restated with the same float32 steps."""
 import numpy as np
 
 M32 = 0xFFFFFFFF
@@ -288,24 +290,86 @@ def _margin(a, b):
     return abs(a - b) / max(abs(a), abs(b), 1e-30)
 
 
-def temporal_pass(cur, prev, mv, fresh, history, lights, st, frame, bsdf, max_history, basic, boiling, strength,
-                  depth_thr=0.1, normal_thr=0.5):
-    """k_di_initial_temporal over a frame. fresh / history: DI_RESERVOIR arrays [H, W] (the initial reservoirs of this frame and last
-    frame's final ones, or None: no history). Returns (reservoirs as dict arrays, margin [H, W])."""
+# ---- the Visibility word of a reservoir ("Reservoir visibility") ------------------------------------------------
+def pack(rgb, dx=0, dy=0, age=0):
+    """bits 0-14: uint(clamp(v, 0, 1) * 31) per channel (float32, as stored); 15-20 / 21-26: dx, dy as 6-bit two's complement clamped to
+    +-31; 27-30: age saturating at 15; bit 31: 0"""
+    c = [int(np.float32(min(max(np.float32(v), np.float32(0)), np.float32(1))) * np.float32(31)) for v in rgb]
+    dx, dy = max(-31, min(31, int(dx))), max(-31, min(31, int(dy)))
+    return c[0] | c[1] << 5 | c[2] << 10 | (dx & 63) << 15 | (dy & 63) << 21 | min(int(age), 15) << 27
+
+
+def unpack(word):
+    """-> (rgb in [0, 1], dx, dy, age)"""
+    w = int(word)
+    s6 = lambda v: v - 64 if v & 32 else v
+    return (np.array([w & 31, (w >> 5) & 31, (w >> 10) & 31]) / 31.0, s6((w >> 15) & 63), s6((w >> 21) & 63), (w >> 27) & 15)
+
+
+def carry(word, ddx, ddy, dage):
+    """the word of a sample taken from the pixel at offset (ddx, ddy), dage frames later: the colour stays, d and age move and saturate"""
+    _, dx, dy, age = unpack(word)
+    w = int(word)
+    dx, dy = max(-31, min(31, dx + ddx)), max(-31, min(31, dy + ddy))
+    return (w & 0x7FFF) | (dx & 63) << 15 | (dy & 63) << 21 | min(age + dage, 15) << 27
+
+
+def reusable(word, max_age, max_distance):
+    """final shading may use the stored visibility: 1 <= age <= max_age and sqrt(dx^2 + dy^2) < max_distance (float32, as compared)"""
+    _, dx, dy, age = unpack(word)
+    return 1 <= age <= max_age and bool(np.sqrt(np.float32(dx * dx + dy * dy)) < np.float32(max_distance))
+
+
+def reuse_margin(word, max_distance):
+    """relative distance of the distance test from its boundary (the age test is on integers)"""
+    _, dx, dy, _ = unpack(word)
+    return _margin(float(np.sqrt(float(dx * dx + dy * dy))), float(max_distance))
+
+
+def sample_points(lights, li, U, V):
+    """Math::SampleTriangle(r1 = U, r2 = V) on light records li: base + e0 * sqrt(U) (1 - V) + e1 * sqrt(U) V"""
+    lt = lights[np.asarray(li, np.int64)]
+    s = np.sqrt(np.asarray(U, np.float64))[:, None]
+    v = np.asarray(V, np.float64)[:, None]
+    return lt["Base"].astype(np.float64) + lt["Edge0"].astype(np.float64) * (s * (1 - v)) + lt["Edge1"].astype(np.float64) * (s * v)
+
+
+# ---- reservoir frames: dicts of [H, W] arrays, LightIndex -1 = empty ---------------------------------------------------------------
+FIELDS = ("LightIndex", "U", "V", "W", "M", "TargetPdf", "Age", "Visibility")
+
+
+def as_frame(res, H, W):
+    """a downloaded DI_RESERVOIR array -> dict of [H, W] arrays (float64 / int64), LightIndex -1 = empty"""
+    out = {k: res[k].reshape(H, W).astype(np.float64 if res.dtype[k].kind == "f" else np.int64) for k in res.dtype.names}
+    out["LightIndex"] = np.where(res["LightIndex"].reshape(H, W) == 0xFFFFFFFF, -1, out["LightIndex"])
+    return out
+
+
+def empty(out, c, M):
+    for k in FIELDS:
+        out[k][c] = 0
+    out["LightIndex"][c], out["M"][c] = -1, M
+
+
+def temporal_pass(cur, prev, mv, fresh, history, lights, frame, bsdf, max_history, basic, boiling, strength, depth_thr=0.1, normal_thr=0.5,
+                  in_margin=None, occ=None, raytraced=False, stats=None):
+    """k_di_initial_temporal's reuse over a frame. fresh / history: frames (the initial reservoirs of this frame, after initial visibility
+    if that is on, with their margin in_margin, and last frame's final ones, or None: no history). A selected history sample takes the
+    history pixel's Visibility moved by (hx - x, hy - y) and one frame older. raytraced (with basic): p at the previous surface := 0 when
+    the ray from the current surface to the selected sample is blocked by occ (restirvisref.Occluders), traced only when a history pixel
+    was found and that p > 0; stats["zeroed"] counts the zeroed terms. Returns (frame, margin [H, W])."""
     H, W = cur.H, cur.W
-    out = {k: np.zeros((H, W), t) for k, t in (("LightIndex", np.int64), ("U", np.float64), ("V", np.float64), ("W", np.float64),
-                                                ("M", np.int64), ("TargetPdf", np.float64), ("Age", np.int64))}
+    out = {k: np.zeros((H, W), np.float64 if k in ("U", "V", "W", "TargetPdf") else np.int64) for k in FIELDS}
     out["LightIndex"][:] = -1
-    margin = np.full((H, W), np.inf)
+    margin = np.full((H, W), np.inf) if in_margin is None else np.array(in_margin, np.float64)
     found = {}
     for y in range(H):
         for x in range(W):
             if not cur.valid[y, x]:
+                margin[y, x] = np.inf
                 continue
             for k in ("LightIndex", "U", "V", "W", "M", "TargetPdf"):
                 out[k][y, x] = fresh[k][y, x]
-            if fresh["LightIndex"][y, x] == 0xFFFFFFFF:
-                out["LightIndex"][y, x] = -1
             if history is None:
                 continue
             rng = Rng(x, y, frame, SALT_TEMPORAL)
@@ -327,10 +391,9 @@ def temporal_pass(cur, prev, mv, fresh, history, lights, st, frame, bsdf, max_hi
                     found[(y, x)] = (qy, qx, rng.next())
                     break
     keys = list(found)
-    Hs = [history[qy, qx] for (qy, qx, _) in found.values()]
+    Hs = [{k: history[k][qy, qx] for k in FIELDS} for (qy, qx, _) in found.values()]
     mH = []
-    pH = target_pdfs(cur, keys, lights, [h["LightIndex"] if h["LightIndex"] != 0xFFFFFFFF else -1 for h in Hs],
-                     [h["U"] for h in Hs], [h["V"] for h in Hs], bsdf, mH)
+    pH = target_pdfs(cur, keys, lights, [h["LightIndex"] for h in Hs], [h["U"] for h in Hs], [h["V"] for h in Hs], bsdf, mH)
     for k, m in zip(keys, mH):
         margin[k] = min(margin[k], m)
     sel_from_h = {}
@@ -344,25 +407,37 @@ def temporal_pass(cur, prev, mv, fresh, history, lights, st, frame, bsdf, max_hi
         margin[y, x] = min(margin[y, x], _margin(rc * wsum, wH) if wH > 0 else np.inf)
         fromH = rc * wsum < wH
         if fromH:
+            qy, qx = found[(y, x)][:2]
             out["LightIndex"][y, x], out["U"][y, x], out["V"][y, x] = int(h["LightIndex"]), float(h["U"]), float(h["V"])
             out["TargetPdf"][y, x], out["Age"][y, x] = ph, int(h["Age"]) + 1
+            out["Visibility"][y, x] = carry(int(h["Visibility"]), qx - x, qy - y, 1)
         out["M"][y, x] = mcur + mh
         sel_from_h[(y, x)] = (fromH, mh, wsum, mcur)
-    # normalisation (every valid pixel: no history found is the same formula with M_H = 0)
     need = [(y, x) for (y, x) in sel_from_h if out["TargetPdf"][y, x] > 0]
     mP = []
     pprev = target_pdfs(prev, [(found[k][0], found[k][1]) for k in need], lights, [out["LightIndex"][k] for k in need],
-                        [out["U"][k] for k in need], [out["V"][k] for k in need], bsdf, mP) if basic else []
+                          [out["U"][k] for k in need], [out["V"][k] for k in need], bsdf, mP) if basic else []
     for k, m in zip(need, mP):
         margin[k] = min(margin[k], m)
     pprev = dict(zip(need, pprev))
+    if basic and raytraced:
+        rays = [k for k in need if pprev[k] > 0]
+        if rays:
+            ys, xs = np.array(rays).T
+            blocked, _, m = occ.trace(cur.P[ys, xs], sample_points(lights, out["LightIndex"][ys, xs], out["U"][ys, xs], out["V"][ys, xs]))
+            for k, b, mm in zip(rays, blocked, m):
+                margin[k] = min(margin[k], mm)
+                if b:
+                    pprev[k] = 0.0
+                    if stats is not None:
+                        stats["zeroed"] = stats.get("zeroed", 0) + 1
     for y in range(H):
         for x in range(W):
             if not cur.valid[y, x] or history is None:
                 continue
             p = out["TargetPdf"][y, x]
             if not p > 0:
-                out["LightIndex"][y, x], out["U"][y, x], out["V"][y, x], out["W"][y, x], out["TargetPdf"][y, x], out["Age"][y, x] = -1, 0, 0, 0, 0, 0
+                empty(out, (y, x), out["M"][y, x])
                 continue
             fromH, mh, wsum, mcur = sel_from_h.get((y, x), (False, 0, None, int(out["M"][y, x])))
             if wsum is None:
@@ -373,8 +448,6 @@ def temporal_pass(cur, prev, mv, fresh, history, lights, st, frame, bsdf, max_hi
                 out["W"][y, x] = wsum * (pp if fromH else p) / den if den > 0 else 0.0
             else:
                 out["W"][y, x] = wsum / (p * out["M"][y, x])
-    if history is None:                                                  # no history: the fresh reservoir renormalised (same value)
-        pass
     if boiling:
         for ty in range(0, H, 8):
             for tx in range(0, W, 8):
@@ -394,10 +467,7 @@ def temporal_pass(cur, prev, mv, fresh, history, lights, st, frame, bsdf, max_hi
                     if nz[ln]:
                         margin[y, x] = min(margin[y, x], _margin(float(Wt[ln]), thr))
                         if Wt[ln] > thr:
-                            for k in out:
-                                out[k][y, x] = 0
-                            out["LightIndex"][y, x] = -1
-                # the tile's sum moves with every lane's W: a lane near the cut makes the whole tile uncertain
+                            empty(out, (y, x), 0)
                 tmin = min((margin[y, x] for _, y, x in idx), default=np.inf)
                 if tmin < 1e-5:
                     for _, y, x in idx:
@@ -405,12 +475,15 @@ def temporal_pass(cur, prev, mv, fresh, history, lights, st, frame, bsdf, max_hi
     return out, margin
 
 
-def spatial_pass(cur, inp, in_margin, lights, table, frame, bsdf, samples, boost, max_history, radius, basic,
-                 depth_thr=0.1, normal_thr=0.5):
-    """k_di_spatial_shade's reuse over a frame: inp = the temporal output (dict arrays, LightIndex -1 = empty)"""
+def spatial_pass(cur, inp, in_margin, lights, table, frame, bsdf, samples, boost, max_history, radius, basic, depth_thr=0.1, normal_thr=0.5,
+                 occ=None, raytraced=False, stats=None):
+    """k_di_spatial_shade's reuse over a frame: inp = the temporal output. A selected neighbour's sample takes its Visibility moved by
+    (qx - x, qy - y). raytraced (with basic): in the normalisation a contributing neighbour's p := 0 when the ray from that neighbour's
+    surface to the selected sample is blocked by occ (traced only when that p > 0; the centre's own term is not tested). Returns
+    (frame, margin)."""
     H, W = cur.H, cur.W
-    out = {k: v.copy() for k, v in inp.items()}
-    margin = in_margin.copy()
+    out = {k: np.array(inp[k]).copy() for k in FIELDS}
+    margin = np.array(in_margin, np.float64).copy()
     plan = {}
     for y in range(H):
         for x in range(W):
@@ -430,7 +503,8 @@ def spatial_pass(cur, inp, in_margin, lights, table, frame, bsdf, samples, boost
                 margin[y, x] = min(margin[y, x], _margin(np.dot(a["Normal"], b["Normal"]), normal_thr),
                                    _margin(abs(a["Depth"] - b["Depth"]), depth_thr * max(a["Depth"], b["Depth"])),
                                    _margin(abs(a["Roughness"] - b["Roughness"]), 0.5 * max(a["Roughness"], b["Roughness"])),
-                                   _margin(abs(LUMA @ a["F0"] - LUMA @ b["F0"]), 0.25), _margin(abs(LUMA @ a["Albedo"] - LUMA @ b["Albedo"]), 0.25))
+                                   _margin(abs(LUMA @ a["F0"] - LUMA @ b["F0"]), 0.25),
+                                   _margin(abs(LUMA @ a["Albedo"] - LUMA @ b["Albedo"]), 0.25))
                 if neighbour_ok(a, b, a["Depth"], normal_thr, depth_thr):
                     nb.append((qy, qx, rng.next()))
                     margin[y, x] = min(margin[y, x], in_margin[qy, qx])
@@ -438,7 +512,7 @@ def spatial_pass(cur, inp, in_margin, lights, table, frame, bsdf, samples, boost
     pairs = [((y, x), (qy, qx)) for (y, x), nb in plan.items() for (qy, qx, _) in nb]
     mN = []
     pn = target_pdfs(cur, [c for c, _ in pairs], lights, [inp["LightIndex"][q] for _, q in pairs], [inp["U"][q] for _, q in pairs],
-                     [inp["V"][q] for _, q in pairs], bsdf, mN)
+                       [inp["V"][q] for _, q in pairs], bsdf, mN)
     for (c, _), m in zip(pairs, mN):
         margin[c] = min(margin[c], m)
     pn = iter(pn)
@@ -458,29 +532,44 @@ def spatial_pass(cur, inp, in_margin, lights, table, frame, bsdf, samples, boost
                 for k in ("LightIndex", "U", "V", "Age"):
                     out[k][c] = inp[k][qy, qx]
                 out["TargetPdf"][c] = p
+                out["Visibility"][c] = carry(int(inp["Visibility"][qy, qx]), qx - x, qy - y, 0)
         out["M"][c] = M
         sel[c] = (s, wsum)
+    pc = {}
     if basic:
         q = [((y, x), (qy, qx)) for (y, x), nb in plan.items() if out["TargetPdf"][y, x] > 0 for (qy, qx, _) in nb]
         mC = []
-        pc = iter(target_pdfs(cur, [n for _, n in q], lights, [out["LightIndex"][c] for c, _ in q], [out["U"][c] for c, _ in q],
-                              [out["V"][c] for c, _ in q], bsdf, mC))
+        vals = target_pdfs(cur, [n for _, n in q], lights, [out["LightIndex"][c] for c, _ in q], [out["U"][c] for c, _ in q],
+                             [out["V"][c] for c, _ in q], bsdf, mC)
         for (c, _), m in zip(q, mC):
             margin[c] = min(margin[c], m)
+        vals = list(vals)
+        if raytraced:
+            rays = [j for j, v in enumerate(vals) if v > 0]
+            if rays:
+                cs = np.array([q[j][0] for j in rays]); ns = np.array([q[j][1] for j in rays])
+                blocked, _, m = occ.trace(cur.P[ns[:, 0], ns[:, 1]],
+                                          sample_points(lights, out["LightIndex"][cs[:, 0], cs[:, 1]], out["U"][cs[:, 0], cs[:, 1]], out["V"][cs[:, 0], cs[:, 1]]))
+                for j, b, mm in zip(rays, blocked, m):
+                    margin[q[j][0]] = min(margin[q[j][0]], mm)
+                    if b:
+                        vals[j] = 0.0
+                        if stats is not None:
+                            stats["zeroed"] = stats.get("zeroed", 0) + 1
+        vals = iter(vals)
+        for (y, x), nb in plan.items():
+            if out["TargetPdf"][y, x] > 0:
+                pc[(y, x)] = [next(vals) for _ in nb]
     for (y, x), nb in plan.items():
         c = (y, x)
         p = out["TargetPdf"][c]
         s, wsum = sel[c]
         if not p > 0:
-            M = out["M"][c]
-            for k in out:
-                out[k][c] = 0
-            out["LightIndex"][c], out["M"][c] = -1, M
+            empty(out, c, out["M"][c])
             continue
         if basic:
             den, psrc = inp["M"][c] * p, p
-            for i, (qy, qx, _) in enumerate(nb):
-                pq = next(pc)
+            for i, ((qy, qx, _), pq) in enumerate(zip(nb, pc[c])):
                 den += inp["M"][qy, qx] * pq
                 if i == s:
                     psrc = pq
@@ -489,3 +578,5 @@ def spatial_pass(cur, inp, in_margin, lights, table, frame, bsdf, samples, boost
         else:
             out["W"][c] = wsum / (p * out["M"][c])
     return out, margin
+
+

@@ -9,48 +9,9 @@ import pytest
 import __graft_entry__ as ge
 import bsdfref
 import restirref as R
+import visscene
 
 NEAR = 1e-5
-
-
-def _pin_scene(S, aspect):
-    """a GGX-ish floor, an opaque bar over it (parallax disocclusion as the camera moves), five emissive triangles on two instances"""
-    floor = S.quad_mesh((-2, 0, -2), (-2, 0, 2), (2, 0, 2), (2, 0, -2), (0, 1, 0), S.material((0.6, 0.5, 0.4), roughness=0.4, metallic=0.3))
-    bar = S.quad_mesh((-1.5, 0.7, -0.1), (1.5, 0.7, -0.1), (1.5, 0.7, 0.15), (-1.5, 0.7, 0.15), (0, -1, 0), S.material((0.9, 0.9, 0.9), roughness=0.8))
-
-    def tris(pts, strength, color):
-        pos = np.array(pts, np.float32)
-        return S.Mesh(S.make_vertices(pos, np.tile(np.float32([0, -1, 0]), (len(pos), 1))), S.make_indices(list(range(len(pos)))), True,
-                      S.material((0.5, 0.5, 0.5), emissive=color, strength=strength))
-    a = tris([(-0.6, 1.5, -0.3), (0.7, 1.6, 0.1), (0.0, 1.4, 0.8), (-1.5, 1.3, 0.5), (-1.2, 1.3, 0.6), (-1.3, 1.35, 0.9),
-              (1.0, 1.2, -0.8), (1.3, 1.2, -0.7), (1.1, 1.25, -0.4)], 6.0, (1.0, 0.8, 0.6))
-    b = tris([(0.2, 1.1, 1.2), (0.5, 1.1, 1.3), (0.3, 1.15, 1.6), (-0.9, 1.0, -1.2), (-0.6, 1.0, -1.1), (-0.8, 1.05, -0.8)], 20.0, (0.6, 0.8, 1.0))
-    nodes = [S.MeshNode([floor]), S.MeshNode([a]), S.MeshNode([bar]), S.MeshNode([b])]
-    objects = [S.RenderObject(i, S.trs()) for i in range(4)]
-    cam = S.make_camera((0, 2.2, -2.6), forward=(0, -0.6, 1), hfov_deg=70.0, aspect=aspect)
-    return S.Scene(nodes, objects, cam, S.make_scene_data((0, 0, 0, 1)), name="di_reuse_pin").finalize()
-
-
-def _move(S, cam, prev, dx):
-    """the camera shifted by dx along x, with Previous* from the last frame's camera (static geometry: IsStatic)"""
-    c = S.make_camera(cam["Position"].astype(np.float64) + (dx, 0, 0), forward=cam["ForwardDirection"].astype(np.float64), hfov_deg=70.0,
-                      aspect=float(np.linalg.norm(cam["RightDirection"]) / np.linalg.norm(cam["UpDirection"])))
-    c["PreviousPosition"] = prev["Position"]
-    for k in ("WorldToProjection", "ProjectionToView", "ViewToWorld"):
-        c["Previous" + k] = prev[k]
-    c["PreviousWorldToView"], c["PreviousViewToProjection"] = prev["PreviousWorldToView"], prev["PreviousViewToProjection"]
-    return c
-
-
-def _set_camera(r, cam):
-    for op in (r.gbuffer, r.raytracing, r.direct_lighting):
-        op.GPUBuffers["Camera"] = cam
-
-
-def _as_ref(res, H, W):
-    out = {k: res[k].reshape(H, W).astype(np.float64 if res.dtype[k].kind == "f" else np.int64) for k in res.dtype.names}
-    out["LightIndex"] = np.where(res["LightIndex"].reshape(H, W) == 0xFFFFFFFF, -1, out["LightIndex"])
-    return out
 
 
 CONFIGS = [  # (name, temporal, spatial samples, basic, boiling)
@@ -80,7 +41,7 @@ def test_gpu_reuse_pinned_per_pixel(gpu, ptamd, pkg, name, temporal, spatial, ba
     # the initial reservoirs of each frame come from a second context: temporal-only, Off, no boiling, history reset before every frame
     init = L.di_resampling_settings(temporal=True, spatial_samples=0, temporal_bias=L.DI_BIAS_CORRECTION_OFF, boiling_filter=False)
     gpu.set_sharding(0, 1, 16)
-    scene = _pin_scene(S, W / H)
+    scene = visscene.pin_scene(S, W / H)
     g = ptamd.Scene(gpu, scene)
     ctx2 = ptamd.DeviceContext(0)
     g2 = ptamd.Scene(ctx2, scene)
@@ -90,25 +51,25 @@ def test_gpu_reuse_pinned_per_pixel(gpu, ptamd, pkg, name, temporal, spatial, ba
     history, excluded, compared, disoccluded = None, 0, 0, 0
     for f in range(3):
         if f:
-            cam = _move(S, cam, cam, 0.17)
-        _set_camera(r, cam); _set_camera(r2, cam)
+            cam = visscene.move(S, cam, cam, 0.17)
+        visscene.set_camera(r, cam); visscene.set_camera(r2, cam)
         gs = S.graphics_settings(W, H, spp=1, bounces=1, frame_index=40 + f)
         r.render(gs, di_samples=n, di_reuse=reuse); gpu.sync()
         r2.direct_lighting.ResetHistory()
         r2.render(gs, di_samples=n, di_reuse=init); ctx2.sync()
         out = ptamd.textures_to_numpy(r.textures)
-        got = _as_ref(r.direct_lighting.download_reservoirs(), H, W)
-        fresh = r2.direct_lighting.download_reservoirs().reshape(H, W)
+        got = R.as_frame(r.direct_lighting.download_reservoirs(), H, W)
+        fresh = R.as_frame(r2.direct_lighting.download_reservoirs(), H, W)
         lights = r.direct_lighting.download_lights()
         cur = R.Surfaces(out, cam)
         mv = out["MotionVector"].view(np.float16).astype(np.float32)
         if temporal:
             prev = R.Surfaces(out, cam, previous=True) if f else None
-            exp, margin = R.temporal_pass(cur, prev, mv, fresh, history if f else None, lights, None, 40 + f, bsdf, 20, basic, boiling, 0.2)
+            exp, margin = R.temporal_pass(cur, prev, mv, fresh, history if f else None, lights, 40 + f, bsdf, 20, basic, boiling, 0.2)
             if f:
                 disoccluded += int((cur.valid & (exp["M"] == n)).sum())
         else:
-            exp = _as_ref(fresh.reshape(-1), H, W)
+            exp = fresh
             exp["Age"][:] = 0
             margin = np.full((H, W), np.inf)
         if spatial:
@@ -127,7 +88,7 @@ def test_gpu_reuse_pinned_per_pixel(gpu, ptamd, pkg, name, temporal, spatial, ba
         worst = np.argwhere(sel)[np.argmax(rel)]
         assert rel.max() <= 2e-5, (name, f, rel.max(), worst.tolist(), margin[tuple(worst)], got["W"][tuple(worst)], exp["W"][tuple(worst)],
                                    got["M"][tuple(worst)])
-        history = r.direct_lighting.download_reservoirs().reshape(H, W)
+        history = got
     print(f"{name}: {compared} pixels compared, {excluded} within {NEAR} of a decision ({excluded / max(1, compared + excluded):.3%}), "
           f"{disoccluded} without history after motion")
     assert compared > 0.3 * 3 * W * H
@@ -207,7 +168,7 @@ def test_gpu_hidden_emitter_resets_history(gpu, ptamd, pkg):
     """hiding an emitter instance rebuilds the light list (the top level's instance hash): the next temporal frame has no history"""
     S, L = pkg.scenes, pkg.layouts
     W, H, n = 48, 32, 8
-    scene = _pin_scene(S, W / H)
+    scene = visscene.pin_scene(S, W / H)
     gpu.set_sharding(0, 1, 16)
     g = ptamd.Scene(gpu, scene)
     r = ptamd.Renderer(gpu, g, W, H, with_denoiser_outputs=True, di_history=True)

@@ -1,5 +1,5 @@
 """Visibility in the DI reservoirs on the GPU (pt_di_set_visibility): off is the parent's output bit for bit; every rule pinned per pixel
-against the float64 restatement (tests/restirvisref.py) on a moving camera; final-visibility reuse exact where it must be; Raytraced
+against the float64 restatement (tests/restirref.py, tests/restirvisref.py) on a moving camera; final-visibility reuse exact where it must be; Raytraced
 unbiased in a penumbra where Basic is not; the setter's and the render's refusals; pt_demo --restir-visibility."""
 import os
 import subprocess
@@ -69,7 +69,7 @@ CONFIGS = [  # (name, temporal, spatial samples, boiling, visibility settings)
 @pytest.mark.parametrize("name,temporal,spatial,boiling,vis", CONFIGS, ids=[c[0] for c in CONFIGS])
 def test_gpu_visibility_pinned_per_pixel(gpu, ptamd, pkg, name, temporal, spatial, boiling, vis):
     """4 frames of 48 x 32 on the pin scene with the camera moving 0.17 per frame, 8 candidates, initial visibility on. Each frame's final
-    reservoirs match restirvisref, fed the downloaded G-buffers, motion vectors, light records, last frame's final reservoirs and the
+    reservoirs match the restatement, fed the downloaded G-buffers, motion vectors, light records, last frame's final reservoirs and the
     frame's initial reservoirs (from a second context without visibility; the restatement applies initial visibility itself):
     LightIndex, M, Age, U, V and the Visibility word exactly, W to 2e-5 relative (the new arithmetic only zeroes terms; measured up to 1.5e-5,
     as without visibility). Pixels within 1e-5 of a
@@ -105,8 +105,8 @@ def test_gpu_visibility_pinned_per_pixel(gpu, ptamd, pkg, name, temporal, spatia
         r2.direct_lighting.ResetHistory()
         r2.render(gs, di_samples=n, di_reuse=init); ctx2.sync()
         out = ptamd.textures_to_numpy(r.textures)
-        got = V.as_frame(r.direct_lighting.download_reservoirs(), H, W)
-        fresh = V.as_frame(r2.direct_lighting.download_reservoirs(), H, W)
+        got = R.as_frame(r.direct_lighting.download_reservoirs(), H, W)
+        fresh = R.as_frame(r2.direct_lighting.download_reservoirs(), H, W)
         fresh["Age"][:] = 0
         lights = r.direct_lighting.download_lights()
         cur = R.Surfaces(out, cam)
@@ -116,10 +116,10 @@ def test_gpu_visibility_pinned_per_pixel(gpu, ptamd, pkg, name, temporal, spatia
         seen["emptied"] += int(emptied.sum())
         if temporal:
             prev = R.Surfaces(out, cam, previous=True) if f else None
-            exp, margin = V.temporal_pass(cur, prev, mv, exp, margin, history if f else None, lights, F0 + f, bsdf, 20, True, boiling, 0.2,
-                                          occ=occ, raytraced=tr, stats=st)
+            exp, margin = R.temporal_pass(cur, prev, mv, exp, history if f else None, lights, F0 + f, bsdf, 20, True, boiling, 0.2,
+                                          in_margin=margin, occ=occ, raytraced=tr, stats=st)
         if spatial:
-            exp, margin = V.spatial_pass(cur, exp, margin, lights, table, F0 + f, bsdf, spatial, 8, 20, 32.0, True, occ=occ, raytraced=sr, stats=st)
+            exp, margin = R.spatial_pass(cur, exp, margin, lights, table, F0 + f, bsdf, spatial, 8, 20, 32.0, True, occ=occ, raytraced=sr, stats=st)
         age_in = (exp["Visibility"] >> 27) & 15
         exp, margin, info = V.final_pass(cur, exp, margin, lights, occ, reuse=vis["final_reuse"], max_age=vis.get("max_age", 4),
                                          max_distance=16.0, discard=vis.get("discard_invisible", False))

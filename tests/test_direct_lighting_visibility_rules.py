@@ -1,5 +1,5 @@
 """CPU checks of visibility in the DI reservoirs: the settings struct and the Visibility word against the header, the float64 restatement
-(tests/restirvisref.py) against restirref with every flag off, Raytraced against Basic, an enumerated two-pixel case that tells the two
+(tests/restirref.py's passes, tests/restirvisref.py) with every flag off, Raytraced against Basic, an enumerated two-pixel case that tells the two
 apart, the final-visibility reuse boundaries, and the share of pixels the per-pixel GPU pins may have to leave out."""
 import os
 import re
@@ -141,30 +141,31 @@ def frame(pkg, oracle):
                 table=R.offset_table(), W=W, H=H)
 
 
-def _structured(f, L):
-    a = np.zeros(f["M"].shape, L.DI_RESERVOIR)
-    for k in a.dtype.names:
-        a[k] = np.where(f[k] < 0, 0xFFFFFFFF, f[k]) if k == "LightIndex" else f[k]
-    return a
-
-
 def test_flags_off_is_restirref(frame, pkg):
-    """with no visibility the passes here are restirref's, value for value"""
+    """the passes without the visibility arguments are the passes given occluders and a margin with Raytraced off, field for field and
+    margin for margin. The history's words are zero, so no output carries a colour: after the temporal pass a word is 0 on a fresh
+    sample and the carried offset and age of a zero word on a sample from the history (the device without visibility stores 0 there;
+    the word is not read)."""
     f = frame
     inf = np.full((f["H"], f["W"]), np.inf)
+    assert not f["history"]["Visibility"].any() and not f["fresh"]["Visibility"].any()
     for basic, boiling in ((True, True), (False, False)):
-        want, wm = R.temporal_pass(f["cur"], f["prev"], f["mv"], _structured(f["fresh"], pkg.layouts), _structured(f["history"], pkg.layouts),
-                                   f["lights"], None, 7, f["bsdf"], 20, basic, boiling, 0.2)
-        got, gm = V.temporal_pass(f["cur"], f["prev"], f["mv"], f["fresh"], inf, f["history"], f["lights"], 7, f["bsdf"], 20, basic, boiling, 0.2)
+        want, wm = R.temporal_pass(f["cur"], f["prev"], f["mv"], f["fresh"], f["history"], f["lights"], 7, f["bsdf"], 20, basic, boiling, 0.2)
+        got, gm = R.temporal_pass(f["cur"], f["prev"], f["mv"], f["fresh"], f["history"], f["lights"], 7, f["bsdf"], 20, basic, boiling, 0.2,
+                                  in_margin=inf, occ=f["occ"], raytraced=False, stats={})
+        assert set(want) == set(got) == set(R.FIELDS)
         for k in want:
             assert np.array_equal(want[k], got[k]), ("temporal", basic, k)
         assert np.array_equal(wm, gm)
         assert (got["M"] > 8).any() and ((got["Age"] > 0).any())
         want2, wm2 = R.spatial_pass(f["cur"], want, wm, f["lights"], f["table"], 7, f["bsdf"], 2, 8, 20, 32.0, basic)
-        got2, gm2 = V.spatial_pass(f["cur"], got, gm, f["lights"], f["table"], 7, f["bsdf"], 2, 8, 20, 32.0, basic)
+        got2, gm2 = R.spatial_pass(f["cur"], got, gm, f["lights"], f["table"], 7, f["bsdf"], 2, 8, 20, 32.0, basic, occ=f["occ"], raytraced=False,
+                                   stats={})
         for k in want2:
             assert np.array_equal(want2[k], got2[k]), ("spatial", basic, k)
         assert np.array_equal(wm2, gm2)
+        assert not (want["Visibility"] & 0x7FFF).any() and not (want2["Visibility"] & 0x7FFF).any(), basic
+        assert not want["Visibility"][want["Age"] == 0].any(), basic
 
 
 def test_raytraced_equals_basic_when_nothing_is_blocked(frame, pkg):
@@ -175,22 +176,22 @@ def test_raytraced_equals_basic_when_nothing_is_blocked(frame, pkg):
     scene.instance_masks[2] = 0                                           # no bar: nothing between the floor and the lights
     occ = V.Occluders(scene)
     st = {}
-    b, _ = V.temporal_pass(f["cur"], f["prev"], f["mv"], f["fresh"], inf, f["history"], f["lights"], 7, f["bsdf"], 20, True, False, 0.2)
-    r, _ = V.temporal_pass(f["cur"], f["prev"], f["mv"], f["fresh"], inf, f["history"], f["lights"], 7, f["bsdf"], 20, True, False, 0.2,
+    b, _ = R.temporal_pass(f["cur"], f["prev"], f["mv"], f["fresh"], f["history"], f["lights"], 7, f["bsdf"], 20, True, False, 0.2)
+    r, _ = R.temporal_pass(f["cur"], f["prev"], f["mv"], f["fresh"], f["history"], f["lights"], 7, f["bsdf"], 20, True, False, 0.2,
                            occ=occ, raytraced=True, stats=st)
     floor = f["cur"].valid & (np.abs(f["cur"].P[..., 1]) < 1e-3)
     assert floor.sum() > 0.3 * f["W"] * f["H"]
     for k in b:
         assert np.array_equal(b[k][floor], r[k][floor]), k
-    b2, _ = V.spatial_pass(f["cur"], b, inf, f["lights"], f["table"], 7, f["bsdf"], 2, 8, 20, 32.0, True)
-    r2, _ = V.spatial_pass(f["cur"], b, inf, f["lights"], f["table"], 7, f["bsdf"], 2, 8, 20, 32.0, True, occ=occ, raytraced=True, stats=st)
+    b2, _ = R.spatial_pass(f["cur"], b, inf, f["lights"], f["table"], 7, f["bsdf"], 2, 8, 20, 32.0, True)
+    r2, _ = R.spatial_pass(f["cur"], b, inf, f["lights"], f["table"], 7, f["bsdf"], 2, 8, 20, 32.0, True, occ=occ, raytraced=True, stats=st)
     on_floor = floor.copy()                                               # pixels all of whose neighbours lie on the floor too
     for k in b2:
         same = b2[k] == r2[k]
         assert same[on_floor].mean() > 0.98, k                            # (a neighbour on an emitter or the bar's top may be blocked by its own mesh)
     # and with the bar back, Raytraced zeroes terms
     st = {}
-    V.temporal_pass(f["cur"], f["prev"], f["mv"], f["fresh"], inf, f["history"], f["lights"], 7, f["bsdf"], 20, True, False, 0.2,
+    R.temporal_pass(f["cur"], f["prev"], f["mv"], f["fresh"], f["history"], f["lights"], 7, f["bsdf"], 20, True, False, 0.2,
                     occ=f["occ"], raytraced=True, stats=st)
     assert st.get("zeroed", 0) > 0
 
@@ -204,8 +205,8 @@ def test_pins_leave_enough_pixels(frame):
     st = {}
     iv, m0, emptied = V.initial_visibility(f["cur"], f["fresh"], f["lights"], f["occ"], 8)
     # (no boiling filter here: its cut depends on the tile's real weights, which the synthetic frame does not have)
-    t, m1 = V.temporal_pass(f["cur"], None, f["mv"], iv, m0, None, f["lights"], 7, f["bsdf"], 20, True, False, 0.2, occ=f["occ"], raytraced=True)
-    s, m2 = V.spatial_pass(f["cur"], t, m1, f["lights"], f["table"], 7, f["bsdf"], 2, 8, 20, 32.0, True, occ=f["occ"], raytraced=True, stats=st)
+    t, m1 = R.temporal_pass(f["cur"], None, f["mv"], iv, None, f["lights"], 7, f["bsdf"], 20, True, False, 0.2, in_margin=m0, occ=f["occ"], raytraced=True)
+    s, m2 = R.spatial_pass(f["cur"], t, m1, f["lights"], f["table"], 7, f["bsdf"], 2, 8, 20, 32.0, True, occ=f["occ"], raytraced=True, stats=st)
     out, m3, info = V.final_pass(f["cur"], s, m2, f["lights"], f["occ"], reuse=True, max_age=2, max_distance=16.0)
     valid = f["cur"].valid
     excluded, compared = int((valid & (m3 < NEAR)).sum()), int((valid & (m3 >= NEAR)).sum())
@@ -217,11 +218,11 @@ def test_pins_leave_enough_pixels(frame):
     assert (info["vis"][info["traced"]] == 0).all(-1).any() and (info["vis"][info["traced"]] == 1).all(-1).any()   # the bar's shadow is there
     assert ((out["Visibility"][info["traced"]] >> 15) == 0).all()         # traced: d = 0, age 0
     st = {}
-    t, m1 = V.temporal_pass(f["cur"], f["prev"], f["mv"], iv, m0, f["history"], f["lights"], 7, f["bsdf"], 20, True, False, 0.2, occ=f["occ"],
-                            raytraced=True, stats=st)
+    t, m1 = R.temporal_pass(f["cur"], f["prev"], f["mv"], iv, f["history"], f["lights"], 7, f["bsdf"], 20, True, False, 0.2, in_margin=m0,
+                            occ=f["occ"], raytraced=True, stats=st)
     assert st.get("zeroed", 0) > 0
     assert ((t["Visibility"] >> 27) >= 1)[t["Age"] > 0].all()             # a history sample's visibility is one frame older
-    s, m2 = V.spatial_pass(f["cur"], t, m1, f["lights"], f["table"], 7, f["bsdf"], 2, 8, 20, 32.0, True, occ=f["occ"], raytraced=True)
+    s, m2 = R.spatial_pass(f["cur"], t, m1, f["lights"], f["table"], 7, f["bsdf"], 2, 8, 20, 32.0, True, occ=f["occ"], raytraced=True)
     out, m3, info = V.final_pass(f["cur"], s, m2, f["lights"], f["occ"], reuse=True, max_age=2, max_distance=16.0)
     assert info["reused"].any() and info["traced"].any()
     assert np.array_equal(out["Visibility"][info["reused"]], s["Visibility"][info["reused"]])      # reused: stored unchanged

@@ -1,5 +1,5 @@
-"""What the reservoir-visibility tests share: the pin scene (a copy of tests/test_direct_lighting_reuse_pins.py's: a floor, an opaque bar over
-it, five emissive triangles), camera motion, the light records of a scene computed on the host, and a synthetic reservoir frame."""
+"""What the reservoir-reuse and reservoir-visibility tests share: the pin scene (a floor, an opaque bar over it, five emissive triangles),
+camera motion, the light records of a scene computed on the host, and a synthetic reservoir frame."""
 import numpy as np
 
 import restirref as R
@@ -25,7 +25,7 @@ def pin_scene(S, aspect, bar=BAR):
     nodes = [S.MeshNode([floor]), S.MeshNode([a]), S.MeshNode([bar]), S.MeshNode([b])]
     objects = [S.RenderObject(i, S.trs()) for i in range(4)]
     cam = S.make_camera((0, 2.2, -2.6), forward=(0, -0.6, 1), hfov_deg=70.0, aspect=aspect)
-    return S.Scene(nodes, objects, cam, S.make_scene_data((0, 0, 0, 1)), name="di_visibility_pin").finalize()
+    return S.Scene(nodes, objects, cam, S.make_scene_data((0, 0, 0, 1)), name="di_reuse_pin").finalize()
 
 
 def move(S, cam, prev, dx):
