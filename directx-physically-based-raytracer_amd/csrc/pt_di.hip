@@ -11,6 +11,7 @@
 //                                     spatial reuse (RTXDIAppBridge.hlsli RAB_GetGBufferSurface, RAB_Surface::Shade, GetFinalVisibility)
 //   k_di_initial_temporal<..., VIS, Source> <- DIInitialSampling + DITemporalResampling (boiling filter), with reservoir reuse on
 //   k_di_spatial_shade<..., VIS>   <- DISpatialResampling + DIFinalShading
+//   both with BIAS = kDIBiasPairwise <- pairwise-MIS bias correction (pt_di_set_pairwise): one pass over the neighbours, no rays
 //   both with VIS != 0             <- the same with visibility in the reservoirs (pt_di_set_visibility):
 //                                     initial visibility (DIInitialSampling.hlsl:49-54), Raytraced bias correction
 //                                     (RAB_GetConservativeVisibility / RAB_GetTemporalConservativeVisibility), the final-visibility store and
@@ -490,6 +491,9 @@ __global__ __launch_bounds__(256) void k_di(DIArgs a, Source source, BlobView bv
 constexpr uint32_t kDITemporalSalt = 0x44490002u, kDISpatialSalt = 0x44490003u;
 constexpr uint32_t kDIOffsetCount = 8192u;          // neighbour-offset table entries (int8 x, y)
 static_assert(sizeof(PtDIReservoir) == 32 && sizeof(PtDIResamplingSettings) == 64 && sizeof(PtDIPreviousTextures) == 48 && sizeof(PtDIVisibilitySettings) == 32, "layout");
+static_assert(sizeof(PtDIPairwiseSettings) == 16, "layout");
+// BIAS of the reuse kernels, the normalisation of a pass: Off (1 / M), Basic, or Pairwise (BASIC + pt_di_set_pairwise's flag)
+constexpr uint32_t kDIBiasOff = 0u, kDIBiasBasic = 1u, kDIBiasPairwise = 2u;
 
 struct DIReuseArgs {
     DIArgs d;
@@ -598,6 +602,15 @@ PT_DEV float di_target_of(const DIArgs& a, const DISurface& s, uint32_t li, floa
     return di_target(a, s, li, U, V, pos, dif, spc, power);
 }
 
+// ---- pairwise MIS (pt_di_set_pairwise; DESIGN.md section 1, "Pairwise bias correction") ----------------------------------------------
+// One pair (canonical c, neighbour i) of n attempted slots at a sample y: a = (n * M_i) * p_i(y), b = M_c * p_c(y), D = a + b. The
+// neighbour's share of y is a / D and the canonical's b / D; D = 0 gives 0. The caller scales by 1 / (n + 1).
+PT_DEV float di_pair_share(float mine, float other)
+{
+    const float D = mine + other;
+    return D > 0.0f ? mine / D : 0.0f;
+}
+
 // the temporal pass's history search: the motion-vector position, then eight jittered ones (draws from the temporal stream); returns the
 // pixel index in the w x h previous frame of the first whose previous surface sp passes the neighbour test against the expected depth, or -1.
 // The position comes back in one int: as two by-reference outputs it cost the Basic instantiations a wave per SIMD.
@@ -638,10 +651,14 @@ PT_DEV void di_boiling(const DIReuseArgs& r, bool valid, PtDIReservoir& res)
 // lanes walk together: lanes without a ray on a trip trace nothing, and every lane reaches the boiling filter's butterfly. The loop is
 // unrolled, i.e. two inlined walks: kept rolled around one trace site the kernel needs 185 VGPRs (2 waves per SIMD), unrolled 137
 // (3 waves), scratch 464 B / lane either way. Without VIS there is no loop, no ray and no group stack in LDS.
-template <bool TEMPORAL, bool BASIC, uint32_t VIS, typename Source, typename... Extra>
+// BIAS = kDIBiasPairwise: the fresh reservoir is the canonical domain and the history the one neighbour (n = 1); p at the previous surface
+// is taken for both samples, the weights and W come from the temporal step itself and nothing waits for a ray.
+template <bool TEMPORAL, uint32_t BIAS, uint32_t VIS, typename Source, typename... Extra>
 __global__ __launch_bounds__(256) void k_di_initial_temporal(DIReuseArgs r, Source source, Extra... extra)
 {
+    constexpr bool BASIC = BIAS == kDIBiasBasic, PAIRWISE = BIAS == kDIBiasPairwise;
     constexpr bool CARRY = VIS != 0u, RAYTRACED = (VIS & kDIVisRaytraced) != 0u;
+    static_assert(!PAIRWISE || TEMPORAL, "a normalisation belongs to a pass that is on");
     static_assert(!RAYTRACED || (TEMPORAL && BASIC), "the raytraced normalisation is Basic bias correction's");
     const DIArgs& a = r.d;
     uint32_t x, y; di_pixel(x, y);
@@ -664,6 +681,27 @@ __global__ __launch_bounds__(256) void k_di_initial_temporal(DIReuseArgs r, Sour
         const int hi = r.haveHistory ? di_find_history(r, s, w, h, x, y, pi, rng, sp) : -1;
         // combine(s, R0, 0.5, p(y0)) selects R0; then combine(s, H, rc, p(yH)) with the draw after every search draw
         Mcur = res.M;
+        if constexpr (PAIRWISE) {                                       // no history pixel: the fresh reservoir as it is. (The return below
+                                                                        // leaves this lambda; the lane goes on to the boiling filter.)
+            if (hi >= 0) {
+                PtDIReservoir H = di_load<CARRY>(r.in, (size_t)hi);
+                H.M = min(H.M, r.maxHistory * Mcur);
+                const float pH = di_target_of(a, s, H.LightIndex, H.U, H.V);
+                const float rc = rng_float(rng);
+                const float pc = res.TargetPdf;
+                const float mH = di_pair_share((float)H.M * di_target_of(a, sp, H.LightIndex, H.U, H.V), (float)Mcur * pH) * 0.5f;    // n = 1
+                const float mc = (1.0f + di_pair_share((float)Mcur * pc, (float)H.M * di_target_of(a, sp, res.LightIndex, res.U, res.V))) * 0.5f;
+                const float wH = mH * pH * H.W;
+                wsum = mc * pc * res.W + wH;
+                if (rc * wsum < wH) {
+                    res.LightIndex = H.LightIndex; res.U = H.U; res.V = H.V; res.TargetPdf = pH; res.Age = H.Age == ~0u ? ~0u : H.Age + 1u;
+                    if constexpr (CARRY) res.Visibility = di_vis_carry(H.Visibility, hi % w - (int)x, hi / w - (int)y, 1u);
+                }
+                res.M = Mcur + H.M;
+                if (res.TargetPdf > 0.0f) res.W = wsum / res.TargetPdf; else res = di_empty(res.M);
+            }
+            return;
+        }
         wsum = res.TargetPdf * res.W * (float)res.M;
         if (hi >= 0) {
             PtDIReservoir H = di_load<CARRY>(r.in, (size_t)hi);
@@ -728,10 +766,14 @@ __global__ __launch_bounds__(256) void k_di_initial_temporal(DIReuseArgs r, Sour
 // Spatial reuse, then final shading in the same thread. SPATIAL = false: the final reservoir is the input (temporal-only).
 // VIS & kDIVisRaytraced (with BASIC): in the normalisation a neighbour's p counts as 0 when the ray from that neighbour's surface to the
 // selected sample is blocked -- one trace site inside that loop.
-template <bool SPATIAL, bool BASIC, uint32_t VIS, typename... Extra>
+// BIAS = kDIBiasPairwise: the neighbours stream through one loop with their pairwise weights, the centre (the canonical domain) is merged
+// last with the share the slots left it, and there is no second loop.
+template <bool SPATIAL, uint32_t BIAS, uint32_t VIS, typename... Extra>
 __global__ __launch_bounds__(256) void k_di_spatial_shade(DIReuseArgs r, BlobView bv, AlphaContext ac, DeviceCounters* counters, Extra... extra)
 {
+    constexpr bool BASIC = BIAS == kDIBiasBasic, PAIRWISE = BIAS == kDIBiasPairwise;
     constexpr bool CARRY = VIS != 0u;
+    static_assert(!PAIRWISE || (SPATIAL && !(VIS & kDIVisRaytraced)), "pairwise traces nothing and belongs to a pass that is on");
     __shared__ uint2 ldsStack[kLdsStackDepth * 256];
     const DIArgs& a = r.d;
     uint32_t x, y; di_pixel(x, y);
@@ -740,7 +782,46 @@ __global__ __launch_bounds__(256) void k_di_spatial_shade(DIReuseArgs r, BlobVie
     PtDIReservoir c = di_load<CARRY>(r.in, pi);
     DISurface s;
     if (!di_surface(a, a.view, pi, x, y, s)) { di_store<CARRY>(r.out, pi, c); return; }
-    if (SPATIAL) {
+    if constexpr (PAIRWISE) {
+        const int w = (int)a.fv.width;
+        uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDISpatialSalt);
+        const uint32_t start = (uint32_t)(rng_float(rng) * 8191.0f);
+        const uint32_t n = c.M < r.maxHistory ? max(r.spatialSamples, r.boostSamples) : r.spatialSamples;
+        const float nf = (float)n, inv = 1.0f / (nf + 1.0f);
+        float wsum = 0.0f, own = 0.0f, pSel = 0.0f;
+        uint32_t M = c.M, k = 0u;
+        int sel = -1;                                                     // the selected neighbour's pixel: its reservoir is loaded again after
+                                                                          // the loop. Kept in registers through the loop the selected sample
+                                                                          // costs the kernel a wave per SIMD (138 VGPRs against 127)
+        for (uint32_t i = 0; i < n; i++) {
+            int qx, qy;
+            if (!di_neighbour(r, x, y, start, i, qx, qy)) continue;
+            DISurface sn;
+            if (!di_surface(a, a.view, (size_t)qy * w + qx, qx, qy, sn)) continue;
+            if (!di_similar(s, sn, s.depth, r.sNormal, r.sDepth)) continue;
+            k++;
+            const float pic = di_target_of(a, sn, c.LightIndex, c.U, c.V);       // the centre's sample at the neighbour: sn's last use
+            const PtDIReservoir rn = di_load<CARRY>(r.in, (size_t)qy * w + qx);
+            const float pn = di_target_of(a, s, rn.LightIndex, rn.U, rn.V);
+            const float rc = rng_float(rng);
+            const float nM = nf * (float)rn.M;
+            const float wn = di_pair_share(nM * rn.TargetPdf, (float)c.M * pn) * inv * pn * rn.W;
+            own += di_pair_share((float)c.M * c.TargetPdf, nM * pic);
+            wsum += wn; M += rn.M;
+            if (rc * wsum < wn) { sel = qy * w + qx; pSel = pn; }
+        }
+        if (k) {                                                         // no contributing slot: the centre as it is
+            const float wc = (1.0f + (float)(n - k) + own) * inv * c.TargetPdf * c.W;
+            wsum += wc;
+            if (rng_float(rng) * wsum < wc) { sel = -1; pSel = c.TargetPdf; }
+            if (sel >= 0) {
+                const PtDIReservoir rn = di_load<CARRY>(r.in, (size_t)sel);
+                c.LightIndex = rn.LightIndex; c.U = rn.U; c.V = rn.V; c.Age = rn.Age;
+                if (CARRY) c.Visibility = di_vis_carry(rn.Visibility, sel % w - (int)x, sel / w - (int)y, 0u);
+            }
+            if (pSel > 0.0f) { c.M = M; c.TargetPdf = pSel; c.W = wsum / pSel; } else c = di_empty(M);
+        }
+    } else if (SPATIAL) {
         const int w = (int)a.fv.width;
         uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDISpatialSalt);
         const uint32_t start = (uint32_t)(rng_float(rng) * 8191.0f);
@@ -899,6 +980,13 @@ static int di_check_args(Context& c, const PtTextures* tx, const PtDIPreviousTex
         API_ARG(&c, !(c.diVisibility.SpatialRaytraced && c.diReuse.SpatialSamples) || c.diReuse.SpatialBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC,
                "SpatialRaytraced needs SpatialBiasCorrection = PT_DI_BIAS_CORRECTION_BASIC");
     }
+    if (c.diReuseOn) {                                                         // a flag on a pass that is off is ignored
+        const bool tp = c.diPairwise.TemporalPairwise && c.diReuse.TemporalResampling, sp = c.diPairwise.SpatialPairwise && c.diReuse.SpatialSamples;
+        API_ARG(&c, !tp || c.diReuse.TemporalBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC, "TemporalPairwise needs TemporalBiasCorrection = PT_DI_BIAS_CORRECTION_BASIC");
+        API_ARG(&c, !sp || c.diReuse.SpatialBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC, "SpatialPairwise needs SpatialBiasCorrection = PT_DI_BIAS_CORRECTION_BASIC");
+        API_ARG(&c, !(tp && c.diVisibilityOn && c.diVisibility.TemporalRaytraced), "TemporalPairwise and TemporalRaytraced are two corrections of one pass: set one");
+        API_ARG(&c, !(sp && c.diVisibilityOn && c.diVisibility.SpatialRaytraced), "SpatialPairwise and SpatialRaytraced are two corrections of one pass: set one");
+    }
     return PT_OK;
 }
 
@@ -966,19 +1054,22 @@ template <typename F> static void di_with_source(const DISampling& ls, F&& f)
     else f(ls);
 }
 
-// calls f with the compile-time form of a reuse pass, (pass on, Basic bias correction, VIS), and with va behind it when VIS != 0. The
-// forms are {(0, 0), (1, 0), (1, 1)} x {0, kDIVisOn} and (1, 1, kDIVisOn | kDIVisRaytraced): di_check_args refuses raytraced without Basic.
-template <typename F> static void di_with_form(bool on, bool basic, bool vis, bool raytraced, const DIVisArgs& va, F&& f)
+// calls f with the compile-time form of a reuse pass, (pass on, BIAS, VIS), and with va behind it when VIS != 0. The forms are
+// {(0, Off), (1, Off), (1, Basic), (1, Pairwise)} x {0, kDIVisOn} and (1, Basic, kDIVisOn | kDIVisRaytraced): di_check_args refuses raytraced
+// and pairwise without Basic, and the two together.
+template <typename F> static void di_with_form(bool on, bool basic, bool pairwise, bool vis, bool raytraced, const DIVisArgs& va, F&& f)
 {
     using std::integral_constant;
-    auto with_vis = [&](auto ON, auto BASIC) {
-        if (vis) f(ON, BASIC, integral_constant<uint32_t, kDIVisOn>{}, va);
-        else f(ON, BASIC, integral_constant<uint32_t, 0u>{});
+    auto with_vis = [&](auto ON, auto BIAS) {
+        if (vis) f(ON, BIAS, integral_constant<uint32_t, kDIVisOn>{}, va);
+        else f(ON, BIAS, integral_constant<uint32_t, 0u>{});
     };
-    if (!on) with_vis(std::false_type{}, std::false_type{});
-    else if (raytraced) f(std::true_type{}, std::true_type{}, integral_constant<uint32_t, kDIVisOn | kDIVisRaytraced>{}, va);
-    else if (basic) with_vis(std::true_type{}, std::true_type{});
-    else with_vis(std::true_type{}, std::false_type{});
+    using Off = integral_constant<uint32_t, kDIBiasOff>; using Basic = integral_constant<uint32_t, kDIBiasBasic>;
+    if (!on) with_vis(std::false_type{}, Off{});
+    else if (raytraced) f(std::true_type{}, Basic{}, integral_constant<uint32_t, kDIVisOn | kDIVisRaytraced>{}, va);
+    else if (pairwise) with_vis(std::true_type{}, integral_constant<uint32_t, kDIBiasPairwise>{});
+    else if (basic) with_vis(std::true_type{}, Basic{});
+    else with_vis(std::true_type{}, Off{});
 }
 
 // reservoir reuse: k_di_initial_temporal (last frame's B -> A), k_di_spatial_shade (A -> B); B is next frame's history
@@ -1021,18 +1112,19 @@ static int di_launch_reuse(Context& c, const DIArgs& a, const DISampling& ls, co
     const bool tb = rs.TemporalBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC, sb = rs.SpatialBiasCorrection == PT_DI_BIAS_CORRECTION_BASIC;
     const PtDIVisibilitySettings& vs = c.diVisibility;
     const bool vis = c.diVisibilityOn, tr = vis && temporal && vs.TemporalRaytraced, sr = vis && spatial && vs.SpatialRaytraced;
+    const bool tp = temporal && c.diPairwise.TemporalPairwise, sp = spatial && c.diPairwise.SpatialPairwise;
     DIVisArgs va; memset(&va, 0, sizeof va);
     va.bv = c.scene.blob; va.ac = ac; va.counters = c.counters.data();
     va.initial = vs.InitialVisibility; va.maxAge = vs.FinalVisibilityReuse ? vs.FinalVisibilityMaxAge : 0u; va.discard = vs.DiscardInvisibleSamples;
     va.maxDistance = vs.FinalVisibilityMaxDistance;
     di_with_source(ls, [&](auto source) {
-        di_with_form(temporal, tb, vis, tr, va, [&](auto T, auto B, auto V, auto... extra) {
+        di_with_form(temporal, tb, tp, vis, tr, va, [&](auto T, auto B, auto V, auto... extra) {
             k_di_initial_temporal<T(), B(), V(), decltype(source)><<<grid, 256, 0, c.stream>>>(r, source, extra...);
         });
     });
     API_HIP(&c, hipGetLastError());
     r.in = c.diResA.data(); r.out = c.diResB.data();
-    di_with_form(spatial, sb, vis, sr, va, [&](auto S, auto B, auto V, auto... extra) {
+    di_with_form(spatial, sb, sp, vis, sr, va, [&](auto S, auto B, auto V, auto... extra) {
         k_di_spatial_shade<S(), B(), V()><<<grid, 256, 0, c.stream>>>(r, c.scene.blob, ac, c.counters.data(), extra...);
     });
     API_HIP(&c, hipGetLastError());
@@ -1146,6 +1238,22 @@ int pt_di_set_visibility(PtContext* ctx, const PtDIVisibilitySettings* s)
     const bool on = v.InitialVisibility || v.FinalVisibilityReuse || v.DiscardInvisibleSamples || v.TemporalRaytraced || v.SpatialRaytraced;
     if (memcmp(&v, &c.diVisibility, sizeof v) != 0) c.diHistoryValid = false;
     c.diVisibility = v; c.diVisibilityOn = on;
+    return PT_OK;
+}
+
+int pt_di_set_pairwise(PtContext* ctx, const PtDIPairwiseSettings* s)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    PtDIPairwiseSettings v; memset(&v, 0, sizeof v);
+    if (s) {
+        API_ARG(&c, s->TemporalPairwise <= 1u, "TemporalPairwise must be 0 or 1");
+        API_ARG(&c, s->SpatialPairwise <= 1u, "SpatialPairwise must be 0 or 1");
+        API_ARG(&c, s->Reserved[0] == 0u && s->Reserved[1] == 0u, "Reserved must be 0");
+        v = *s;
+    }
+    if (memcmp(&v, &c.diPairwise, sizeof v) != 0) c.diHistoryValid = false;
+    c.diPairwise = v;
     return PT_OK;
 }
 

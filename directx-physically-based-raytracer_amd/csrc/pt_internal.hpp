@@ -208,6 +208,7 @@ struct Context {
     bool diHistoryValid = false; uint32_t diHistorySize[2] = {0, 0}; uint64_t diHistoryLightKey = 0; uint32_t diResCount = 0;
     // local-light sampling (pt_di_set_light_sampling): the Power_RIS tiles and the ReGIR cells of the last render, per context
     PtDIVisibilitySettings diVisibility{}; bool diVisibilityOn = false;   // pt_di_set_visibility: any flag set
+    PtDIPairwiseSettings diPairwise{};                                      // pt_di_set_pairwise
     PtDILightSamplingSettings diSampling{};
     DeviceBuffer<PtDIPresampledLight> diTiles, diCells;
     uint32_t diTileCount = 0, diCellCount = 0;        // entries the last render filled (0: not filled)

@@ -2,7 +2,7 @@
 // reference-shaped operators of ptamd.hpp (GBufferGeneration / Raytracing / RaytracingHelpers), times it and
 // optionally dumps the radiance for the parity test (tests/test_host_cpp.py compares it with the oracle).
 //
-//   pt_demo [--width W] [--height H] [--spp S] [--bounces B] [--frames N] [--out file.bin] [--ranks R] [--di] [--di-samples N] [--restir [--restir-visibility [--restir-raytraced]]] [--sharc]
+//   pt_demo [--width W] [--height H] [--spp S] [--bounces B] [--frames N] [--out file.bin] [--ranks R] [--di] [--di-samples N] [--restir [--restir-pairwise] [--restir-visibility [--restir-raytraced]]] [--sharc]
 //           [--light-sampling cdf|uniform|power_ris|regir]
 //           [--post] [--no-bloom] [--bloom-strength S] [--tone-map saturate|reinhard|aces] [--exposure E]
 //           [--hdr [--paper-white N] [--color-rotation hdtv_to_uhdtv|dci_p3_d65_to_uhdtv|hdtv_to_dci_p3_d65]]
@@ -14,6 +14,8 @@
 // frame after the first (App.cpp:629-634). Unsharded only.
 // --restir-visibility (with --restir): visibility in the reservoirs at the RTXDI SDK's defaults (initial visibility, final-visibility reuse
 // over 4 frames / 16 pixels); --restir-raytraced (with it): Raytraced bias correction in both passes.
+// --restir-pairwise (with --restir): Pairwise bias correction in both passes (BiasCorrectionMode::Pairwise) instead of Basic; not
+// together with --restir-raytraced.
 // --light-sampling (with --di): how the DI pass draws its candidates (ReSTIRDI.InitialSampling.LocalLight.Mode; default cdf, the power
 // prefix sum); ReGIR at MyAppData's cell size 1 and 8 build samples.
 //
@@ -352,7 +354,7 @@ static std::vector<uint8_t> exchange_unique_id(uint32_t rank, const std::string&
 int main(int argc, char** argv)
 {
     uint32_t W = 1920, H = 1080, spp = 4, bounces = 8, frames = 10, ranks = 0, rank = 0, world = 1;
-    uint32_t diSamples = 8; bool di = false, restir = false, restirVisibility = false, restirRaytraced = false;
+    uint32_t diSamples = 8; bool di = false, restir = false, restirVisibility = false, restirRaytraced = false, restirPairwise = false;
     bool useSharc = false; uint32_t sharcDownscale = 4; float sceneScale = 50.0f;   // --sharc [--sharc-downscale N --scene-scale S]: frames through the radiance cache
     std::string out, idFile, scenePath, dumpPath, lightSampling = "cdf";
     bool post = false, bloom = true, hdr = false; float bloomStrength = 0.05f, exposure = 0.0f, paperWhite = 200.0f;
@@ -363,6 +365,7 @@ int main(int argc, char** argv)
         if (k == "--restir") { restir = true; continue; }
         if (k == "--restir-visibility") { restirVisibility = true; continue; }
         if (k == "--restir-raytraced") { restirRaytraced = true; continue; }
+        if (k == "--restir-pairwise") { restirPairwise = true; continue; }
         if (k == "--sharc") { useSharc = true; continue; }
         if (k == "--post") { post = true; continue; }
         if (k == "--no-bloom") { bloom = false; continue; }
@@ -528,6 +531,8 @@ int main(int argc, char** argv)
         if (restir && (!di || sharded)) throw std::invalid_argument("--restir needs --di and one unsharded process");
         if (restirVisibility && !restir) throw std::invalid_argument("--restir-visibility needs --restir");
         if (restirRaytraced && !restirVisibility) throw std::invalid_argument("--restir-raytraced needs --restir-visibility");
+        if (restirPairwise && !restir) throw std::invalid_argument("--restir-pairwise needs --restir");
+        if (restirPairwise && restirRaytraced) throw std::invalid_argument("--restir-pairwise and --restir-raytraced are two bias corrections: give one");
         if (useSharc && sharded) throw std::invalid_argument("--sharc needs one unsharded process");
         SHARC sharc(commandList);
         Raytracing::SHARCSettings sharcSettings; sharcSettings.DownscaleFactor = sharcDownscale;
@@ -548,6 +553,7 @@ int main(int argc, char** argv)
             prev.PreviousNormalRoughness = alloc(px_ * 8); prev.PreviousIOR = alloc(px_ * 2); prev.PreviousTransmission = alloc(px_);
             DirectLighting::ReSTIRDI r;
             r.TemporalResampling.IsEnabled = true; r.SpatialResampling.IsEnabled = true;
+            if (restirPairwise) r.TemporalResampling.BiasCorrectionMode = r.SpatialResampling.BiasCorrectionMode = DirectLighting::ReSTIRDIBiasCorrectionMode::Pairwise;
             directLighting.SetResampling(r);
             if (restirVisibility) {
                 DirectLighting::Visibility v;

@@ -189,8 +189,9 @@ struct DirectLighting {
     };
 
     // MyAppData ReSTIRDI.TemporalResampling / SpatialResampling (Source/MyAppData.h:226-247); the thresholds, history length, radius and
-    // disocclusion boost are the RTXDI SDK's documented defaults. Both passes off by default: the plain pass.
-    enum class ReSTIRDIBiasCorrectionMode : uint32_t { Off = PT_DI_BIAS_CORRECTION_OFF, Basic = PT_DI_BIAS_CORRECTION_BASIC };
+    // disocclusion boost are the RTXDI SDK's documented defaults. Both passes off by default: the plain pass. Pairwise and Raytraced
+    // (the reference's values 2 and 3) reach the library as BASIC plus pt_di_set_pairwise's / pt_di_set_visibility's flag of the pass.
+    enum class ReSTIRDIBiasCorrectionMode : uint32_t { Off = PT_DI_BIAS_CORRECTION_OFF, Basic = PT_DI_BIAS_CORRECTION_BASIC, Pairwise = 2, Raytraced = 3 };
     struct ReSTIRDI {
         struct TemporalResampling {
             bool IsEnabled{};
@@ -230,17 +231,24 @@ struct DirectLighting {
     {
         PtDIResamplingSettings s{};
         s.TemporalResampling = r.TemporalResampling.IsEnabled ? 1u : 0u;
-        s.TemporalBiasCorrection = (uint32_t)r.TemporalResampling.BiasCorrectionMode;
+        s.TemporalBiasCorrection = LibraryBiasCorrection(r.TemporalResampling.BiasCorrectionMode);
         s.MaxHistoryLength = r.TemporalResampling.MaxHistoryLength;
         s.BoilingFilter = r.TemporalResampling.BoilingFilter.IsEnabled ? 1u : 0u;
         s.BoilingFilterStrength = r.TemporalResampling.BoilingFilter.Strength;
         s.TemporalDepthThreshold = r.TemporalResampling.DepthThreshold; s.TemporalNormalThreshold = r.TemporalResampling.NormalThreshold;
         s.SpatialSamples = r.SpatialResampling.IsEnabled ? r.SpatialResampling.Samples : 0u;
-        s.SpatialBiasCorrection = (uint32_t)r.SpatialResampling.BiasCorrectionMode;
+        s.SpatialBiasCorrection = LibraryBiasCorrection(r.SpatialResampling.BiasCorrectionMode);
         s.DisocclusionBoostSamples = r.SpatialResampling.DisocclusionBoostSamples;
         s.SpatialSamplingRadius = r.SpatialResampling.SamplingRadius;
         s.SpatialDepthThreshold = r.SpatialResampling.DepthThreshold; s.SpatialNormalThreshold = r.SpatialResampling.NormalThreshold;
         ThrowIfFailed(m_context, pt_di_set_resampling(m_context, &s));
+        PtDIPairwiseSettings p{};
+        p.TemporalPairwise = r.TemporalResampling.BiasCorrectionMode == ReSTIRDIBiasCorrectionMode::Pairwise ? 1u : 0u;
+        p.SpatialPairwise = r.SpatialResampling.BiasCorrectionMode == ReSTIRDIBiasCorrectionMode::Pairwise ? 1u : 0u;
+        ThrowIfFailed(m_context, pt_di_set_pairwise(m_context, &p));
+        m_temporalRaytraced = r.TemporalResampling.BiasCorrectionMode == ReSTIRDIBiasCorrectionMode::Raytraced;
+        m_spatialRaytraced = r.SpatialResampling.BiasCorrectionMode == ReSTIRDIBiasCorrectionMode::Raytraced;
+        ApplyVisibility();
     }
 
     void ResetHistory() { ThrowIfFailed(m_context, pt_di_reset_history(m_context)); }     // App::ResetHistory
@@ -253,15 +261,7 @@ struct DirectLighting {
         float FinalVisibilityMaxDistance = 16.0f;
         bool TemporalRaytraced = false, SpatialRaytraced = false;
     };
-    void SetVisibility(const Visibility& v)
-    {
-        PtDIVisibilitySettings s{};
-        s.InitialVisibility = v.EnableInitialVisibility ? 1u : 0u; s.FinalVisibilityReuse = v.ReuseFinalVisibility ? 1u : 0u;
-        s.FinalVisibilityMaxAge = v.FinalVisibilityMaxAge; s.FinalVisibilityMaxDistance = v.FinalVisibilityMaxDistance;
-        s.DiscardInvisibleSamples = v.DiscardInvisibleSamples ? 1u : 0u;
-        s.TemporalRaytraced = v.TemporalRaytraced ? 1u : 0u; s.SpatialRaytraced = v.SpatialRaytraced ? 1u : 0u;
-        ThrowIfFailed(m_context, pt_di_set_visibility(m_context, &s));
-    }
+    void SetVisibility(const Visibility& v) { m_visibility = v; ApplyVisibility(); }
 
     void SetLightSampling(const LightSampling& l)
     {
@@ -301,6 +301,21 @@ struct DirectLighting {
 
 private:
     PtContext* m_context;
+    static uint32_t LibraryBiasCorrection(ReSTIRDIBiasCorrectionMode m) { return m == ReSTIRDIBiasCorrectionMode::Off ? PT_DI_BIAS_CORRECTION_OFF : PT_DI_BIAS_CORRECTION_BASIC; }
+    static Visibility NoVisibility() { Visibility v; v.EnableInitialVisibility = v.ReuseFinalVisibility = false; return v; }
+    // the Visibility last set (none: every flag off) with the Raytraced modes of the last SetResampling on top
+    void ApplyVisibility()
+    {
+        const Visibility& v = m_visibility;
+        PtDIVisibilitySettings s{};
+        s.InitialVisibility = v.EnableInitialVisibility ? 1u : 0u; s.FinalVisibilityReuse = v.ReuseFinalVisibility ? 1u : 0u;
+        s.FinalVisibilityMaxAge = v.FinalVisibilityMaxAge; s.FinalVisibilityMaxDistance = v.FinalVisibilityMaxDistance;
+        s.DiscardInvisibleSamples = v.DiscardInvisibleSamples ? 1u : 0u;
+        s.TemporalRaytraced = v.TemporalRaytraced || m_temporalRaytraced ? 1u : 0u; s.SpatialRaytraced = v.SpatialRaytraced || m_spatialRaytraced ? 1u : 0u;
+        ThrowIfFailed(m_context, pt_di_set_visibility(m_context, &s));
+    }
+    Visibility m_visibility = NoVisibility();
+    bool m_temporalRaytraced = false, m_spatialRaytraced = false;
 };
 
 struct GBufferGeneration {

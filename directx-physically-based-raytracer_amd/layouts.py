@@ -132,6 +132,19 @@ def di_visibility_settings(initial=True, final_reuse=True, max_age=4, max_distan
     return s
 
 
+PT_DI_PAIRWISE_SETTINGS = np.dtype({  # PtDIPairwiseSettings: pairwise-MIS bias correction of the reuse passes (pt_di_set_pairwise)
+    "names": ["TemporalPairwise", "SpatialPairwise", "Reserved"], "formats": ["<u4", "<u4", ("<u4", 2)], "offsets": [0, 4, 8], "itemsize": 16})
+
+
+def di_pairwise_settings(temporal=False, spatial=False):
+    """PtDIPairwiseSettings: a flag turns the Basic normalisation of its pass (di_resampling_settings' *_bias = DI_BIAS_CORRECTION_BASIC)
+    into ReSTIRDI's Pairwise bias correction. Both off by default."""
+    s = np.zeros((), PT_DI_PAIRWISE_SETTINGS)
+    s["TemporalPairwise"] = 1 if temporal else 0
+    s["SpatialPairwise"] = 1 if spatial else 0
+    return s
+
+
 def di_unpack_visibility(word):
     """PtDIReservoir.Visibility (array or scalar) -> (rgb visibility [..., 3] in [0, 1], dx, dy, age): 5 bits per channel decoded / 31,
     two 6-bit two's-complement pixel offsets, a 4-bit age."""

@@ -27,7 +27,7 @@ EXPORTS = [
     "pt_raytrace_set_constants", "pt_raytrace_render", "pt_trace_visibility", "pt_bsdf_evaluate", "pt_bsdf_sample", "pt_reset_counters", "pt_get_counters",
     "pt_di_set_constants", "pt_di_render", "pt_di_light_count", "pt_di_download_lights",
     "pt_di_set_resampling", "pt_di_render_with_history", "pt_di_reset_history", "pt_di_download_reservoirs",
-    "pt_di_set_light_sampling", "pt_di_download_presampled", "pt_di_set_visibility",
+    "pt_di_set_light_sampling", "pt_di_download_presampled", "pt_di_set_visibility", "pt_di_set_pairwise",
     "pt_post_set_constants", "pt_post_render", "pt_post_download_bloom",
     "pt_sharc_configure", "pt_sharc_set_constants", "pt_raytrace_render_sharc", "pt_sharc_reset", "pt_sharc_download",
     "pt_sharc_debug_keys", "pt_sharc_debug_query", "pt_sharc_download_update_paths", "pt_sharc_download_update_scatter",
@@ -182,6 +182,7 @@ def load_library():
         lib.pt_di_download_reservoirs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.pt_di_set_light_sampling.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_di_set_visibility.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_di_set_pairwise.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_di_download_presampled.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.pt_post_set_constants.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_post_render.argtypes = [C.c_void_p, C.c_void_p]
@@ -689,6 +690,15 @@ class DirectLighting:
         self._visibility = np.array(settings).reshape(())
         self.ctx.check(self.ctx.lib.pt_di_set_visibility(self.ctx.handle, C.c_void_p(self._visibility.ctypes.data)))
 
+    def SetPairwise(self, settings):
+        """PtDIPairwiseSettings (layouts.di_pairwise_settings), or None: off. A flag turns the Basic bias correction of its pass into
+        Pairwise. A changed value resets the history."""
+        if settings is None:
+            self.ctx.check(self.ctx.lib.pt_di_set_pairwise(self.ctx.handle, None))
+            return
+        self._pairwise = np.array(settings).reshape(())
+        self.ctx.check(self.ctx.lib.pt_di_set_pairwise(self.ctx.handle, C.c_void_p(self._pairwise.ctypes.data)))
+
     def download_presampled(self, which):
         """which = 0: the Power_RIS tiles (128 x 1024, tile-major), 1: the ReGIR cells (4096 x 512, cell-major, x fastest) of the last
         Render (numpy layouts.DI_PRESAMPLED_LIGHT; empty when that render did not fill them)."""
@@ -830,14 +840,15 @@ class Renderer:
         self.constants["RenderSize"] = (width, height)
         self.constants["Flags"] = L.GBufferFlags.DefaultNoDenoiser        # App.cpp:1224 with Denoiser::None
 
-    def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None, post=None, sharc=None, di_visibility=None):
+    def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None, post=None, sharc=None, di_visibility=None, di_pairwise=None):
         """di_samples > 0: run the DI pass with that many candidates per pixel; set settings["IsDIEnabled"] to have the path tracer
         consume it (the textures need Diffuse / Specular: with_denoiser_outputs=True). di_reuse: PtDIResamplingSettings
         (layouts.di_resampling_settings) for reservoir reuse; temporal reuse needs di_history=True. With di_history the current and
         Previous* G-buffer textures are swapped before each frame after the first, so that after render() the current ones hold this
         frame's G-buffer and the Previous* ones the last frame's. di_light_sampling: PtDILightSamplingSettings
         (layouts.di_light_sampling_settings), or None: the power CDF. di_visibility: PtDIVisibilitySettings (layouts.di_visibility_settings)
-        for visibility in the reservoirs (initial visibility, Raytraced bias correction, final-visibility reuse), or None: none. post: PtPostProcessSettings (layouts.post_processing_settings) to run
+        for visibility in the reservoirs (initial visibility, Raytraced bias correction, final-visibility reuse), or None: none. di_pairwise: PtDIPairwiseSettings
+        (layouts.di_pairwise_settings) to turn a pass's Basic bias correction into Pairwise, or None: off. post: PtPostProcessSettings (layouts.post_processing_settings) to run
         the post-processing chain on the frame's Radiance; it writes textures["Color"], ["BackBuffer"] and ["Display8"]. Unsharded
         contexts only: a sharded host gathers Radiance and runs PostProcessing on the full frame. sharc: PtSHARCSettings
         (layouts.sharc_settings) to render the frame through the radiance cache (self.sharc.Configure first); None: the plain path tracer."""
@@ -862,6 +873,7 @@ class Renderer:
             self.direct_lighting.SetResampling(di_reuse)
             self.direct_lighting.SetLightSampling(di_light_sampling)
             self.direct_lighting.SetVisibility(di_visibility)
+            self.direct_lighting.SetPairwise(di_pairwise)
             self.direct_lighting.Render(tlas)
         if int(np.array(settings).reshape(())["Bounces"]) > 0:            # App.cpp:1277
             self.raytracing.SetConstants(settings)

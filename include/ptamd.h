@@ -399,7 +399,8 @@ int  pt_di_download_lights(PtContext* ctx, PtTriangleLight* host_dst, uint32_t c
  * Off by default: pt_di_render is pt_di_render_with_history(ctx, tx, NULL) and, with both passes off, runs the plain pass.
  * Unsharded contexts only. Each context keeps two reservoir buffers of RenderSize pixels x 32 B (ping-ponged per render).
  * ------------------------------------------------------------------------------------------ */
-enum { PT_DI_BIAS_CORRECTION_OFF = 0, PT_DI_BIAS_CORRECTION_BASIC = 1 };   /* 2 Pairwise, 3 Raytraced: rejected here; Raytraced is
+enum { PT_DI_BIAS_CORRECTION_OFF = 0, PT_DI_BIAS_CORRECTION_BASIC = 1 };   /* 2 Pairwise, 3 Raytraced: rejected here; Pairwise is
+                                                                             BASIC + pt_di_set_pairwise's *Pairwise flags, Raytraced
                                                                              BASIC + pt_di_set_visibility's *Raytraced flags */
 typedef struct PtDIResamplingSettings {
     uint32_t TemporalResampling;          /* 0 / 1 */
@@ -465,6 +466,22 @@ typedef struct PtDIVisibilitySettings {
  * previous setting active; a changed value resets the history. A *Raytraced flag whose pass is on with a bias correction other than
  * BASIC is refused by pt_di_render_with_history. */
 int  pt_di_set_visibility(PtContext* ctx, const PtDIVisibilitySettings* settings);
+
+/* ------------------------------------------------------------------------------------------
+ * pairwise-MIS bias correction of the reuse passes (ReSTIRDI_*BiasCorrectionMode::Pairwise, Source/MyAppData.h:44-59). DESIGN.md
+ * section 1, "Pairwise bias correction", is the spec (this library's own; parity with the RTXDI SDK is unpinned). A flag turns the BASIC
+ * normalisation of its pass into the pairwise one: one pass over the neighbours, no rays, the pixel's own sample keeps a guaranteed
+ * share. It works with pt_di_set_visibility's Visibility word; like BASIC it is biased in penumbrae under initial visibility.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct PtDIPairwiseSettings {
+    uint32_t TemporalPairwise;            /* 0 / 1: the temporal pass's BASIC normalisation becomes Pairwise */
+    uint32_t SpatialPairwise;             /* 0 / 1: the spatial pass's BASIC normalisation becomes Pairwise */
+    uint32_t Reserved[2];                 /* 0 */
+} PtDIPairwiseSettings;                   /* 16 B */
+/* NULL or all 0: off. A flag above 1 or a non-zero Reserved is refused and leaves the previous setting active; a changed value resets
+ * the history. A flag on a pass that is off is ignored. pt_di_render_with_history refuses a *Pairwise flag whose pass is on with a bias
+ * correction other than BASIC, and *Pairwise together with *Raytraced on one pass. */
+int  pt_di_set_pairwise(PtContext* ctx, const PtDIPairwiseSettings* settings);
 
 /* ------------------------------------------------------------------------------------------
  * how the initial candidates of the DI pass are drawn (ReSTIRDI.InitialSampling.LocalLight.Mode, Source/MyAppData.h:35-39, 212;

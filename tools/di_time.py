@@ -3,14 +3,15 @@ path tracer with IsDIEnabled) against the DI-off frame, per workload. Each workl
 the pass with temporal + spatial reservoir reuse at the reference's defaults (layouts.di_resampling_settings), history carried over.
 --visibility (with --reuse) adds the pass with visibility in the reservoirs (layouts.di_visibility_settings): initial visibility, + Raytraced in both
 passes, + final-visibility reuse, each with the final shadow rays per pixel counted from the downloaded reservoirs (a shaded reservoir
-whose visibility has age 0 was traced this frame, an older one was reused). --light-sampling times each listed local-light sampling mode (cdf, uniform, power_ris, regir; one JSON line per mode). The workload
+whose visibility has age 0 was traced this frame, an older one was reused). --pairwise (with --reuse) times Basic and Pairwise bias
+correction (layouts.di_pairwise_settings, both passes) side by side at SpatialSamples 1 and 4, three alternating rounds each. --light-sampling times each listed local-light sampling mode (cdf, uniform, power_ris, regir; one JSON line per mode). The workload
 emitter_field is scenes.emitter_field(256) (131 k emissive triangles) at 1920 x 1080, 1 spp, 1 bounce.
-usage: tools/di_time.py [--workloads c2,c3,c5,emitter_field] [--samples 8] [--n 20] [--reuse [--visibility]] [--light-sampling cdf,regir]"""
+usage: tools/di_time.py [--workloads c2,c3,c5,emitter_field] [--samples 8] [--n 20] [--reuse [--visibility] [--pairwise]] [--light-sampling cdf,regir]"""
 import argparse, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def child(w, samples, n, reuse, modes, visibility=False):
+def child(w, samples, n, reuse, modes, visibility=False, pairwise=False):
     sys.path.insert(0, ROOT)
     import torch
     import __graft_entry__ as ge
@@ -83,6 +84,19 @@ def child(w, samples, n, reuse, modes, visibility=False):
             traced, reused = final_rays()
             out["visibility_" + label] = {"di_reuse_ms": ms, "final_rays_per_pixel": traced, "final_reused_per_pixel": reused}
         r.direct_lighting.SetVisibility(None)
+        if pairwise:                                           # Basic against Pairwise, alternating: the spread between rounds is the noise
+            rows = {}
+            for spatial in (1, 4):
+                r.direct_lighting.SetResampling(L.di_resampling_settings(spatial_samples=spatial))
+                for rnd in range(3):
+                    for label, pw in (("basic", None), ("pairwise", L.di_pairwise_settings(temporal=True, spatial=True))):
+                        r.direct_lighting.SetPairwise(pw)
+                        for _ in range(6):                     # the history refills up to MaxHistoryLength: no disocclusion boost in the window
+                            r.direct_lighting.Render(tlas)
+                        ctx.sync()
+                        rows.setdefault("%s_spatial%d_ms" % (label, spatial), []).append(timed(lambda i: r.direct_lighting.Render(tlas), n))
+            out["pairwise"] = rows
+            r.direct_lighting.SetPairwise(None)
         r.direct_lighting.SetResampling(None)
     print(json.dumps(out))
     ctx.close()
@@ -93,12 +107,14 @@ if __name__ == "__main__":
     ap.add_argument("--child", default=None); ap.add_argument("--workloads", default="c2,c3,c5")
     ap.add_argument("--samples", type=int, default=8); ap.add_argument("--n", type=int, default=20); ap.add_argument("--reuse", action="store_true")
     ap.add_argument("--light-sampling", default="cdf"); ap.add_argument("--visibility", action="store_true")
+    ap.add_argument("--pairwise", action="store_true")
     a = ap.parse_args()
     if a.child:
-        child(a.child, a.samples, a.n, a.reuse, a.light_sampling.split(","), a.visibility); sys.exit(0)
+        child(a.child, a.samples, a.n, a.reuse, a.light_sampling.split(","), a.visibility, a.pairwise); sys.exit(0)
     for w in a.workloads.split(","):
         p = subprocess.run([sys.executable, __file__, "--child", w, "--samples", str(a.samples), "--n", str(a.n),
-                            "--light-sampling", a.light_sampling] + (["--reuse"] if a.reuse else []) + (["--visibility"] if a.visibility else []), stdout=subprocess.PIPE,
+                            "--light-sampling", a.light_sampling] + (["--reuse"] if a.reuse else []) + (["--visibility"] if a.visibility else []) +
+                           (["--pairwise"] if a.pairwise else []), stdout=subprocess.PIPE,
                            stderr=subprocess.PIPE, text=True, timeout=600)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]
         print("\n".join(line) if line else "%s FAILED (exit %d) %s" % (w, p.returncode, p.stderr[-400:]), flush=True)
