@@ -7,6 +7,7 @@
 //   k_cdf_*                        <- the local-light pdf texture of the reference's Power_RIS mode, as a fixed-order prefix sum
 //   k_di_presample_tiles           <- LocalLightPresampling.hlsl: the Power_RIS light tiles (POWER_RIS, REGIR_RIS)
 //   k_di_regir_build               <- ReGIRPresampling.hlsl, Grid mode: the ReGIR cells (REGIR_RIS)
+//   k_di_regir_build_onion         <- the same over the Onion layout's cells (pt_di_set_regir_layout; the reference's compiled mode)
 //   k_di<Source>                   <- DIInitialSampling (local lights only, streaming RIS) + DIFinalShading, no temporal /
 //                                     spatial reuse (RTXDIAppBridge.hlsli RAB_GetGBufferSurface, RAB_Surface::Shade, GetFinalVisibility)
 //   k_di_initial_temporal<..., VIS, Source> <- DIInitialSampling + DITemporalResampling (boiling filter), with reservoir reuse on
@@ -22,6 +23,7 @@
 // DESIGN.md section 1 ("Direct lighting") is the arithmetic spec: seeding, draw order, triangle mapping.
 #include "pt_internal.hpp"
 
+#include <cassert>
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -316,19 +318,12 @@ PT_DEV float di_volume_weight(const float4* L, v3 c, float radius)
     return fminf(l0.w / (dist * dist), 2.0f * kPi) * ml_luminance(V3(l4.x, l4.y, l4.z));
 }
 
-// ReGIR build (ReGIRPresampling.hlsl, Grid mode): one thread per slot, BuildSamples candidates from one Power_RIS tile (chosen by a
-// stream shared by 256 slots), streaming RIS against the cell's sphere (the cell centre, half its diagonal); the slot keeps the light and
-// its contribution weight sum(w) / (p(sel) * BuildSamples), or is empty.
-__global__ __launch_bounds__(256) void k_di_regir_build(const float4* __restrict__ lights, uint32_t count, const uint2* __restrict__ tiles, float cx0, float cy0, float cz0,
-                                                        float cellSize, uint32_t buildSamples, uint32_t frameIndex, uint2* __restrict__ cells)
+// One slot of a ReGIR cell (ReGIRPresampling.hlsl): BuildSamples candidates from one Power_RIS tile (chosen by a stream shared by 256
+// slots), streaming RIS against the cell's sphere (c, radius); the slot keeps the light and its contribution weight
+// sum(w) / (p(sel) * BuildSamples), or is empty. The layouts differ only in the sphere.
+PT_DEV uint2 di_regir_slot(const float4* __restrict__ lights, uint32_t count, const uint2* __restrict__ tiles, uint32_t g, v3 c, float radius,
+                           uint32_t buildSamples, uint32_t frameIndex)
 {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= kDICellEntries) return;
-    const uint32_t cell = g / kDICellLights;
-    const uint32_t ix = cell % kDIGrid, iy = (cell / kDIGrid) % kDIGrid, iz = cell / (kDIGrid * kDIGrid);
-    const float h = (float)(kDIGrid / 2u) - 0.5f;
-    const v3 c = V3(cx0 + ((float)ix - h) * cellSize, cy0 + ((float)iy - h) * cellSize, cz0 + ((float)iz - h) * cellSize);
-    const float radius = 0.5f * sqrtf(3.0f) * cellSize;
     uint32_t rng = ml_hash(rng_init(g & 0xFFFu, g >> 12, frameIndex) ^ kDIReGIRSalt);
     uint32_t coherent = ml_hash(rng_init(g >> 8, 0u, frameIndex) ^ kDIReGIRCoherentSalt);
     const uint2* tile = tiles + min((uint32_t)(rng_float(coherent) * (float)kDITileCount), kDITileCount - 1u) * kDITileSize;
@@ -342,7 +337,108 @@ __global__ __launch_bounds__(256) void k_di_regir_build(const float4* __restrict
         wsum += w;
         if (r * wsum < w) { sel = e.x; pSel = p; }
     }
-    cells[g] = pSel > 0.0f ? make_uint2(sel, __float_as_uint(wsum / (pSel * (float)buildSamples))) : make_uint2(~0u, 0u);
+    return pSel > 0.0f ? make_uint2(sel, __float_as_uint(wsum / (pSel * (float)buildSamples))) : make_uint2(~0u, 0u);
+}
+
+// ReGIR build, Grid layout: one thread per slot; the cell's sphere is the cell centre and half its diagonal.
+__global__ __launch_bounds__(256) void k_di_regir_build(const float4* __restrict__ lights, uint32_t count, const uint2* __restrict__ tiles, float cx0, float cy0, float cz0,
+                                                        float cellSize, uint32_t buildSamples, uint32_t frameIndex, uint2* __restrict__ cells)
+{
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= kDICellEntries) return;
+    const uint32_t cell = g / kDICellLights;
+    const uint32_t ix = cell % kDIGrid, iy = (cell / kDIGrid) % kDIGrid, iz = cell / (kDIGrid * kDIGrid);
+    const float h = (float)(kDIGrid / 2u) - 0.5f;
+    const v3 c = V3(cx0 + ((float)ix - h) * cellSize, cy0 + ((float)iy - h) * cellSize, cz0 + ((float)iz - h) * cellSize);
+    const float radius = 0.5f * sqrtf(3.0f) * cellSize;
+    cells[g] = di_regir_slot(lights, count, tiles, g, c, radius, buildSamples, frameIndex);
+}
+
+// ---- ReGIR Onion layout (pt_di_set_regir_layout; DESIGN.md section 1, "Local-light sampling") -----------------------------------------
+// Cell 0 is the sphere of radius c = 0.5 * ReGIRCellSize around the camera; 15 layers follow, their boundaries growing by
+// (p + pi) / (p - pi) per layer of a group with p partitions. A layer is cut into latitude rings of 2 pi / p (ring 0 the equatorial band,
+// ring k >= 1 once per hemisphere, the last one a polar cap) and a ring into n cells of equal azimuth. The RTXDI SDK is not in the
+// reference tree: the layout is this library's own after the SDK's structure, unpinned.
+constexpr uint32_t kOnionGroups = 5u, kOnionLayers = 15u, kOnionCells = 2253u, kOnionRings = 20u, kOnionAzimuths = 241u;
+constexpr uint32_t kDIOnionEntries = kOnionCells * kDICellLights;
+static_assert(kDICellLights == 2u * 256u, "two blocks of the build per cell: the cell's sphere is uniform over a block");
+static_assert(sizeof(PtDIReGIRLayoutSettings) == 16, "layout");
+// Group g: p = 8 + 4 g partitions, g + 3 rings (g + 2 thresholds, the first of them at ring[g (g + 3) / 2]). The cells per ring are listed, so
+// that no platform's cos decides a count; what follows from them is written out and checked where the tables are built.
+constexpr uint32_t kOnionRingCells[kOnionGroups][7] = { { 8, 5, 1 }, { 12, 10, 6, 1 }, { 16, 14, 11, 6, 1 }, { 20, 19, 16, 11, 6, 1 }, { 24, 23, 20, 16, 12, 6, 1 } };
+constexpr uint32_t onion_layer_base(uint32_t layer)            // the first cell of a layer: 20, 46, 80, 126 cells, then 180 per layer
+{
+    return layer >= 4u ? 273u + 180u * (layer - 4u) : layer == 0u ? 1u : layer == 1u ? 21u : layer == 2u ? 67u : 147u;
+}
+constexpr uint32_t onion_group_azimuth(uint32_t g) { return g == 0u ? 0u : g == 1u ? 11u : g == 2u ? 36u : g == 3u ? 79u : 146u; }   // a group's first azimuth threshold
+struct OnionTables {
+    float4 cells[kOnionCells];                      // unit scale: centre, radius of the bounding sphere
+    float b2[16];                                   // squared layer boundaries, b2[0] = 1
+    float ring[kOnionRings];                        // sin^2 of the rings' lower elevations, by group
+    uint32_t ringStep[kOnionRings];                 // what passing ring[k] adds: cells before the ring | azimuth thresholds before it << 8 | the ring's cells << 16
+    float azimuth[kOnionAzimuths + 3u];             // the pseudo-angles (di_diamond) between the cells of a ring, by (group, ring)
+};
+static_assert(sizeof(OnionTables) % 16 == 0 && kOnionRings % 4u == 0, "layout");
+// monotone pseudo-angle of (x, z) around +y in [0, 4): one division instead of atan2
+PT_DEV float di_diamond(float x, float z)
+{
+    if (z >= 0.0f) {
+        if (x >= 0.0f) { const float s = x + z; return s > 0.0f ? z / s : 0.0f; }
+        return 1.0f + (-x) / (z - x);
+    }
+    if (x < 0.0f) return 2.0f + (-z) / (-x - z);
+    return 3.0f + x / (x - z);
+}
+
+// the cell of v (relative to the centre) at scale c; ~0u: beyond the last layer (or not a number). Every count is bounded by its
+// table, so a cell index is < kOnionCells whatever v holds.
+PT_DEV uint32_t di_onion_cell(const OnionTables* __restrict__ t, v3 v, float c)
+{
+    const float d2 = dot(v, v);
+    const float q = d2 / (c * c);
+    if (!(q < t->b2[15])) return ~0u;
+    if (q < 1.0f) return 0u;
+    // The layer and ring thresholds are read at uniform addresses, four to a trip: unrolled whole, their 36 SGPRs at once made the
+    // temporal kernels spill. What a lane's ring selects -- the cells and azimuth thresholds before it, its own
+    // cells -- is summed from ringStep as the group's thresholds pass: no per-lane address but the azimuths'.
+    uint32_t layer = ~0u;                                                                     // b2[0] = 1 <= q < b2[15]
+#pragma nounroll
+    for (uint32_t l = 0; l < 16u; l += 4u)
+#pragma unroll
+        for (uint32_t i = 0; i < 4u; i++) layer += t->b2[l + i] <= q ? 1u : 0u;
+    const uint32_t g = min(layer, kOnionGroups - 1u);
+    uint32_t cell = onion_layer_base(layer);
+    const float e = (v.y * v.y) / d2;
+    uint32_t n = 8u + 4u * g, first = onion_group_azimuth(g);                                 // ring 0 of the group
+    const uint32_t lo = g * (g + 3u) / 2u, cnt = g + 2u;                                      // the group's thresholds
+    bool hemispheres = false;
+#pragma nounroll
+    for (uint32_t k = 0; k < kOnionRings; k += 4u) {
+#pragma unroll
+        for (uint32_t i = 0; i < 4u; i++) {                                                   // past a threshold: the next ring or beyond
+            const bool in = k + i - lo < cnt && t->ring[k + i] <= e;
+            const uint32_t step = t->ringStep[k + i];
+            cell += in ? step & 0xFFu : 0u;
+            first += in ? (step >> 8) & 0xFFu : 0u;
+            n = in ? step >> 16 : n;
+            hemispheres = hemispheres || in;
+        }
+    }
+    cell += (hemispheres && v.y < 0.0f) ? n : 0u;                                             // ring k >= 1: north, then south
+    const float A = di_diamond(v.x, v.z);
+    for (uint32_t j = 0; j + 1u < n; j++) cell += t->azimuth[first + j] <= A ? 1u : 0u;       // per lane, at most 23
+    return cell;
+}
+
+// ReGIR build, Onion layout: one thread per slot, two blocks per cell, so the cell's sphere is read through a uniform index.
+__global__ __launch_bounds__(256) void k_di_regir_build_onion(const float4* __restrict__ lights, uint32_t count, const uint2* __restrict__ tiles,
+                                                              const OnionTables* __restrict__ onion, float cx0, float cy0, float cz0, float c, uint32_t buildSamples,
+                                                              uint32_t frameIndex, uint2* __restrict__ cells)
+{
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= kDIOnionEntries) return;
+    const float4 sph = onion->cells[blockIdx.x >> 1];
+    cells[g] = di_regir_slot(lights, count, tiles, g, V3(cx0 + c * sph.x, cy0 + c * sph.y, cz0 + c * sph.z), c * sph.w, buildSamples, frameIndex);
 }
 
 // ---- initial sampling -------------------------------------------------------------------------------------------------------
@@ -359,9 +455,11 @@ struct DIPowerCDF {
 };
 
 // Uniform, Power_RIS or ReGIR (the mode is uniform over the grid). Power_RIS: the pixel's screen tile picks a light tile. ReGIR: three
-// jitter draws from the pixel stream pick the cell; outside the grid, Power_RIS. Uniform: 1 / count; an entry: 1 / its inverse pdf.
+// jitter draws from the pixel stream pick the cell (of the Grid or the Onion layout, uniform over the grid too); outside the cells,
+// Power_RIS. Uniform: 1 / count; an entry: 1 / its inverse pdf.
 struct DISampling {
     uint32_t mode; const uint2* tiles; const uint2* cells; float centre[3], cellSize;
+    uint32_t layout; const OnionTables* onion;          // PT_DI_REGIR_LAYOUT_*; the tables under ONION
     PT_DEV DIEntries begin(const DIArgs& a, const DISurface& s, uint32_t x, uint32_t y, uint32_t& rng) const
     {
         DIEntries src{ nullptr, 0u };
@@ -372,11 +470,20 @@ struct DISampling {
         }
         if (mode == PT_DI_LOCAL_LIGHT_REGIR_RIS) {
             const float jx = (rng_float(rng) - 0.5f) * kDIJitterScale, jy = (rng_float(rng) - 0.5f) * kDIJitterScale, jz = (rng_float(rng) - 0.5f) * kDIJitterScale;
-            const float fx = floorf((s.P.x + jx * cellSize - centre[0]) / cellSize), fy = floorf((s.P.y + jy * cellSize - centre[1]) / cellSize),
-                        fz = floorf((s.P.z + jz * cellSize - centre[2]) / cellSize);
-            const float lim = (float)(kDIGrid / 2u);
-            if (fx >= -lim && fx < lim && fy >= -lim && fy < lim && fz >= -lim && fz < lim) {
-                const uint32_t cell = (((uint32_t)((int)fz + (int)(kDIGrid / 2u)) * kDIGrid) + (uint32_t)((int)fy + (int)(kDIGrid / 2u))) * kDIGrid + (uint32_t)((int)fx + (int)(kDIGrid / 2u));
+            uint32_t cell = ~0u;
+            if (layout == PT_DI_REGIR_LAYOUT_ONION) {                     // the jitter grows with the distance, as the cells do (pi / 12)
+                const float c = 0.5f * cellSize;                           // RTXDI.ixx:92
+                const v3 v0 = V3(s.P.x - centre[0], s.P.y - centre[1], s.P.z - centre[2]);
+                const float sc = fmaxf(c, 0.2617994f * sqrtf(dot(v0, v0)));
+                cell = di_onion_cell(onion, V3(v0.x + jx * sc, v0.y + jy * sc, v0.z + jz * sc), c);
+            } else {
+                const float fx = floorf((s.P.x + jx * cellSize - centre[0]) / cellSize), fy = floorf((s.P.y + jy * cellSize - centre[1]) / cellSize),
+                            fz = floorf((s.P.z + jz * cellSize - centre[2]) / cellSize);
+                const float lim = (float)(kDIGrid / 2u);
+                if (fx >= -lim && fx < lim && fy >= -lim && fy < lim && fz >= -lim && fz < lim)
+                    cell = (((uint32_t)((int)fz + (int)(kDIGrid / 2u)) * kDIGrid) + (uint32_t)((int)fy + (int)(kDIGrid / 2u))) * kDIGrid + (uint32_t)((int)fx + (int)(kDIGrid / 2u));
+            }
+            if (cell != ~0u) {
                 src.e = cells + (size_t)cell * kDICellLights;
                 src.n = kDICellLights;
             }
@@ -1008,19 +1115,89 @@ static int di_light_records(Context& c, const SceneView& sv, uint32_t n, uint32_
     return PT_OK;
 }
 
-// local-light sampling: Power_RIS tiles (POWER_RIS, REGIR_RIS), then the ReGIR cells around this render's camera (REGIR_RIS); ls is
-// the candidate source of every mode but POWER_CDF
+// The Onion layout's tables, built once in double and stored as float.
+static const OnionTables& onion_tables()
+{
+    static const OnionTables tables = [] {
+        static const uint32_t groupLayers[kOnionGroups] = { 1, 1, 1, 1, 11 };
+        const double pi = 3.14159265358979323846;
+        OnionTables t; memset(&t, 0, sizeof t);
+        uint32_t nRing = 0, nAz = 0, cell = 1, layer = 0;
+        double B = 1.0;
+        t.cells[0] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+        t.b2[0] = 1.0f;
+        auto point = [](double r, double E, double A, double* o) { o[0] = r * cos(E) * cos(A); o[1] = r * sin(E); o[2] = r * cos(E) * sin(A); };
+        auto dist = [](const double* a, const double* b) { return sqrt((a[0] - b[0]) * (a[0] - b[0]) + (a[1] - b[1]) * (a[1] - b[1]) + (a[2] - b[2]) * (a[2] - b[2])); };
+        for (uint32_t g = 0; g < kOnionGroups; g++) {
+            const uint32_t p = 8u + 4u * g, rings = p / 4u + 1u;
+            const double eq = 2.0 * pi / p, ratio = (p + pi) / (p - pi);
+            for (uint32_t k = 1; k < rings; k++) {
+                const double sn = sin((k - 0.5) * eq);
+                const uint32_t before = kOnionRingCells[g][k - 1u];
+                t.ringStep[nRing] = (k == 1u ? before : 2u * before) | ((before - 1u) << 8) | (kOnionRingCells[g][k] << 16);
+                t.ring[nRing++] = (float)(sn * sn);
+            }
+            assert(onion_group_azimuth(g) == nAz && kOnionRingCells[g][0] == p);
+            for (uint32_t k = 0; k < rings; k++) {
+                const uint32_t n = kOnionRingCells[g][k];
+                for (uint32_t j = 1; j < n; j++) {                           // diamond(cos a, sin a) in double
+                    const double x = cos(2.0 * pi * j / n), z = sin(2.0 * pi * j / n);
+                    t.azimuth[nAz++] = (float)(z >= 0.0 ? (x >= 0.0 ? z / (x + z) : 1.0 + (-x) / (z - x)) : (x < 0.0 ? 2.0 + (-z) / (-x - z) : 3.0 + x / (x - z)));
+                }
+            }
+            for (uint32_t l = 0; l < groupLayers[g]; l++, layer++) {
+                const double rIn = B, rOut = B * ratio, rMid = 0.5 * (rIn + rOut);
+                assert(onion_layer_base(layer) == cell);
+                for (uint32_t k = 0; k < rings; k++) {
+                    const uint32_t n = kOnionRingCells[g][k];
+                    const double lo = (k - 0.5) * eq, hi = k + 1u == rings ? 0.5 * pi : (k + 0.5) * eq, mid = k ? k * eq : 0.0;
+                    for (uint32_t south = 0; south < (k ? 2u : 1u); south++) {
+                        const double sgn = south ? -1.0 : 1.0;
+                        for (uint32_t i = 0; i < n; i++, cell++) {
+                            double c[3], q[3], radius = 0.0;
+                            if (n == 1u) {                                   // a polar cap
+                                c[0] = 0.0; c[1] = sgn * rMid; c[2] = 0.0;
+                                radius = rOut - rMid;
+                                for (double r : { rIn, rOut }) { point(r, sgn * lo, 0.0, q); radius = std::max(radius, dist(c, q)); }
+                            } else {
+                                const double aLo = i * 2.0 * pi / n, aHi = (i + 1u) * 2.0 * pi / n;
+                                point(rMid, sgn * mid, (i + 0.5) * 2.0 * pi / n, c);
+                                for (double r : { rIn, rOut }) for (double E : { lo, hi }) for (double A : { aLo, aHi }) { point(r, sgn * E, A, q); radius = std::max(radius, dist(c, q)); }
+                            }
+                            t.cells[cell] = make_float4((float)c[0], (float)c[1], (float)c[2], (float)radius);
+                        }
+                    }
+                }
+                B = rOut;
+                t.b2[layer + 1u] = (float)(B * B);
+            }
+        }
+        assert(nRing == kOnionRings && nAz == kOnionAzimuths && cell == kOnionCells && layer == kOnionLayers);
+        return t;
+    }();
+    return tables;
+}
+
+// local-light sampling: Power_RIS tiles (POWER_RIS, REGIR_RIS), then the ReGIR cells around this render's camera (REGIR_RIS) in the
+// context's layout; ls is the candidate source of every mode but POWER_CDF
 static int di_presample(Context& c, uint32_t n, uint32_t nb, DISampling& ls)
 {
     const PtDILightSamplingSettings& lss = c.diSampling;
     memset(&ls, 0, sizeof ls);
     ls.mode = lss.Mode;
     if (lss.Mode != PT_DI_LOCAL_LIGHT_POWER_RIS && lss.Mode != PT_DI_LOCAL_LIGHT_REGIR_RIS) return PT_OK;
-    const bool regir = lss.Mode == PT_DI_LOCAL_LIGHT_REGIR_RIS;
-    if (c.diTiles.capacity() < kDITileEntries || (regir && c.diCells.capacity() < kDICellEntries)) {
+    const bool regir = lss.Mode == PT_DI_LOCAL_LIGHT_REGIR_RIS, onion = regir && c.diReGIRLayout == PT_DI_REGIR_LAYOUT_ONION;
+    const uint32_t cellEntries = onion ? kDIOnionEntries : kDICellEntries;                    // 9.2 MB or 16 MB, only in ReGIR mode
+    if (c.diTiles.capacity() < kDITileEntries || (regir && c.diCells.capacity() < cellEntries) || (onion && !c.diOnion)) {
         API_HIP(&c, hipStreamSynchronize(c.stream));
         API_HIP(&c, c.diTiles.reserve(kDITileEntries));
-        if (regir) API_HIP(&c, c.diCells.reserve(kDICellEntries));    // 16 MB, only in ReGIR mode
+        if (regir && c.diCells.capacity() < cellEntries) API_HIP(&c, c.diCells.reserve(cellEntries));
+        if (onion && !c.diOnion) {
+            DeviceBuffer<float> dev;
+            API_HIP(&c, dev.reserve(sizeof(OnionTables) / sizeof(float)));
+            API_HIP(&c, hipMemcpy(dev.data(), &onion_tables(), sizeof(OnionTables), hipMemcpyHostToDevice));
+            c.diOnion = std::move(dev);
+        }
     }
     k_di_presample_tiles<<<kDITileEntries / 256u, 256, 0, c.stream>>>((const float4*)c.lightRecords.data(), c.lightCdf.data(), c.lightBlockSums.data() + nb, n,
                                                                      c.diSettings.FrameIndex, (uint2*)c.diTiles.data());
@@ -1030,10 +1207,17 @@ static int di_presample(Context& c, uint32_t n, uint32_t nb, DISampling& ls)
     if (regir) {
         memcpy(ls.centre, c.camera.Position, sizeof ls.centre);
         ls.cellSize = lss.ReGIRCellSize;
-        k_di_regir_build<<<kDICellEntries / 256u, 256, 0, c.stream>>>((const float4*)c.lightRecords.data(), n, ls.tiles, ls.centre[0], ls.centre[1], ls.centre[2],
-                                                                      ls.cellSize, lss.ReGIRBuildSamples, c.diSettings.FrameIndex, (uint2*)c.diCells.data());
+        if (onion) {
+            ls.layout = PT_DI_REGIR_LAYOUT_ONION;
+            ls.onion = (const OnionTables*)c.diOnion.data();
+            k_di_regir_build_onion<<<kDIOnionEntries / 256u, 256, 0, c.stream>>>((const float4*)c.lightRecords.data(), n, ls.tiles, ls.onion, ls.centre[0], ls.centre[1],
+                                                                                ls.centre[2], 0.5f * ls.cellSize, lss.ReGIRBuildSamples, c.diSettings.FrameIndex,
+                                                                                (uint2*)c.diCells.data());
+        } else
+            k_di_regir_build<<<kDICellEntries / 256u, 256, 0, c.stream>>>((const float4*)c.lightRecords.data(), n, ls.tiles, ls.centre[0], ls.centre[1], ls.centre[2],
+                                                                          ls.cellSize, lss.ReGIRBuildSamples, c.diSettings.FrameIndex, (uint2*)c.diCells.data());
         API_HIP(&c, hipGetLastError());
-        c.diCellCount = kDICellEntries;
+        c.diCellCount = cellEntries;
         ls.cells = (const uint2*)c.diCells.data();
     }
     return PT_OK;
@@ -1271,6 +1455,28 @@ int pt_di_set_light_sampling(PtContext* ctx, const PtDILightSamplingSettings* s)
     }
     if (memcmp(&v, &c.diSampling, sizeof v) != 0) c.diHistoryValid = false;
     c.diSampling = v;
+    return PT_OK;
+}
+
+int pt_di_set_regir_layout(PtContext* ctx, const PtDIReGIRLayoutSettings* s)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    const uint32_t layout = s ? s->Layout : (uint32_t)PT_DI_REGIR_LAYOUT_GRID;
+    API_ARG(&c, layout <= PT_DI_REGIR_LAYOUT_ONION, "unknown ReGIR Layout");
+    if (layout != c.diReGIRLayout) c.diHistoryValid = false;
+    c.diReGIRLayout = layout;
+    return PT_OK;
+}
+
+int pt_di_regir_onion_table(uint32_t which, float* host_dst, uint32_t capacity, uint32_t* out_count)
+{
+    if (!out_count || (!host_dst && capacity) || which > 3u) return PT_ERROR_INVALID_ARGUMENT;
+    const OnionTables& t = onion_tables();
+    const float* src[4] = { t.b2, t.ring, t.azimuth, &t.cells[0].x };
+    const uint32_t count[4] = { 16u, kOnionRings, kOnionAzimuths, 4u * kOnionCells };
+    *out_count = count[which];
+    if (capacity) memcpy(host_dst, src[which], sizeof(float) * std::min(capacity, count[which]));
     return PT_OK;
 }
 

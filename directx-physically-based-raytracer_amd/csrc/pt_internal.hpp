@@ -212,6 +212,8 @@ struct Context {
     PtDILightSamplingSettings diSampling{};
     DeviceBuffer<PtDIPresampledLight> diTiles, diCells;
     uint32_t diTileCount = 0, diCellCount = 0;        // entries the last render filled (0: not filled)
+    uint32_t diReGIRLayout = 0;                       // pt_di_set_regir_layout: PT_DI_REGIR_LAYOUT_*
+    DeviceBuffer<float> diOnion;                      // the Onion layout's tables (OnionTables), uploaded by the first Onion render
 
     // post-processing (pt_post.hip): one slot per bloom stage, each the size of the level it writes (the bytes of the reference's two pyramids)
     PtPostProcessSettings post{}; bool havePost = false;

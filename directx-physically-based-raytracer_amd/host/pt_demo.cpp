@@ -3,7 +3,7 @@
 // optionally dumps the radiance for the parity test (tests/test_host_cpp.py compares it with the oracle).
 //
 //   pt_demo [--width W] [--height H] [--spp S] [--bounces B] [--frames N] [--out file.bin] [--ranks R] [--di] [--di-samples N] [--restir [--restir-pairwise] [--restir-visibility [--restir-raytraced]]] [--sharc]
-//           [--light-sampling cdf|uniform|power_ris|regir]
+//           [--light-sampling cdf|uniform|power_ris|regir [--regir-layout grid|onion]]
 //           [--post] [--no-bloom] [--bloom-strength S] [--tone-map saturate|reinhard|aces] [--exposure E]
 //           [--hdr [--paper-white N] [--color-rotation hdtv_to_uhdtv|dci_p3_d65_to_uhdtv|hdtv_to_dci_p3_d65]]
 //           [--png file.png] [--out-display file.bin]
@@ -17,7 +17,8 @@
 // --restir-pairwise (with --restir): Pairwise bias correction in both passes (BiasCorrectionMode::Pairwise) instead of Basic; not
 // together with --restir-raytraced.
 // --light-sampling (with --di): how the DI pass draws its candidates (ReSTIRDI.InitialSampling.LocalLight.Mode; default cdf, the power
-// prefix sum); ReGIR at MyAppData's cell size 1 and 8 build samples.
+// prefix sum); ReGIR at MyAppData's cell size 1 and 8 build samples. --regir-layout (with --light-sampling regir): the layout of the
+// ReGIR cells, the Grid (default) or the Onion the reference compiles.
 //
 // --post: the post-processing chain after every frame (App::PostProcessGraphics, App.cpp:1506-1571: Bloom + Merge, ToneMap, CopyTexture)
 // at MyAppData's defaults (bloom 0.05, ACES filmic, exposure 0, SDR) unless the flags above change them; --png writes the last frame's
@@ -356,7 +357,7 @@ int main(int argc, char** argv)
     uint32_t W = 1920, H = 1080, spp = 4, bounces = 8, frames = 10, ranks = 0, rank = 0, world = 1;
     uint32_t diSamples = 8; bool di = false, restir = false, restirVisibility = false, restirRaytraced = false, restirPairwise = false;
     bool useSharc = false; uint32_t sharcDownscale = 4; float sceneScale = 50.0f;   // --sharc [--sharc-downscale N --scene-scale S]: frames through the radiance cache
-    std::string out, idFile, scenePath, dumpPath, lightSampling = "cdf";
+    std::string out, idFile, scenePath, dumpPath, lightSampling = "cdf", regirLayout = "grid";
     bool post = false, bloom = true, hdr = false; float bloomStrength = 0.05f, exposure = 0.0f, paperWhite = 200.0f;
     std::string toneMap = "aces", colorRotation = "hdtv_to_uhdtv", pngPath, displayPath;
     for (int i = 1; i < argc; i++) {
@@ -379,7 +380,7 @@ int main(int argc, char** argv)
         else if (k == "--world") world = atoi(v); else if (k == "--id-file") idFile = v;
         else if (k == "--di-samples") diSamples = atoi(v);
         else if (k == "--sharc-downscale") sharcDownscale = atoi(v); else if (k == "--scene-scale") sceneScale = (float)atof(v);
-        else if (k == "--light-sampling") lightSampling = v;
+        else if (k == "--light-sampling") lightSampling = v; else if (k == "--regir-layout") regirLayout = v;
         else if (k == "--scene") scenePath = v; else if (k == "--dump-scene") dumpPath = v;
         else if (k == "--bloom-strength") bloomStrength = (float)atof(v); else if (k == "--tone-map") toneMap = v;
         else if (k == "--exposure") exposure = (float)atof(v); else if (k == "--paper-white") paperWhite = (float)atof(v);
@@ -545,8 +546,11 @@ int main(int argc, char** argv)
             else if (lightSampling == "regir") l.InitialSampling.LocalLight.Mode = Mode::ReGIR_RIS;
             else throw std::invalid_argument("--light-sampling: cdf, uniform, power_ris or regir");
             if (!di) throw std::invalid_argument("--light-sampling needs --di");
+            if (regirLayout == "onion") l.ReGIR.Layout = DirectLighting::ReGIRLayout::Onion;
+            else if (regirLayout != "grid") throw std::invalid_argument("--regir-layout: grid or onion");
+            if (regirLayout != "grid" && lightSampling != "regir") throw std::invalid_argument("--regir-layout needs --light-sampling regir");
             directLighting.SetLightSampling(l);
-        }
+        } else if (regirLayout != "grid") throw std::invalid_argument("--regir-layout needs --light-sampling regir");
         PtDIPreviousTextures& prev = directLighting.PreviousTextures;
         if (restir) {
             prev.PreviousGeometricNormal = alloc(px_ * 4); prev.PreviousLinearDepth = alloc(px_ * 4); prev.PreviousBaseColorMetalness = alloc(px_ * 4);

@@ -213,11 +213,15 @@ struct DirectLighting {
     enum class ReSTIRDILocalLightSamplingMode : uint32_t {
         PowerCDF = PT_DI_LOCAL_LIGHT_POWER_CDF, Uniform = PT_DI_LOCAL_LIGHT_UNIFORM, Power_RIS = PT_DI_LOCAL_LIGHT_POWER_RIS, ReGIR_RIS = PT_DI_LOCAL_LIGHT_REGIR_RIS
     };
+    // ReGIRLayout: the cells' layout (pt_di_set_regir_layout). The reference compiles the Onion (Shaders/RTXDIAppBridge.hlsli:6); the Grid is
+    // this library's default.
+    enum class ReGIRLayout : uint32_t { Grid = PT_DI_REGIR_LAYOUT_GRID, Onion = PT_DI_REGIR_LAYOUT_ONION };
     struct LightSampling {
         struct InitialSampling { struct LocalLight { ReSTIRDILocalLightSamplingMode Mode = ReSTIRDILocalLightSamplingMode::ReGIR_RIS; } LocalLight; } InitialSampling;
         struct ReGIR {
             struct Cell { float Size = 1.0f; } Cell;       // [0.1, 10]
             uint32_t BuildSamples = 8;                      // 1..32
+            ReGIRLayout Layout = ReGIRLayout::Grid;
         } ReGIR;
     };
 
@@ -269,6 +273,9 @@ struct DirectLighting {
         s.Mode = (uint32_t)l.InitialSampling.LocalLight.Mode;
         s.ReGIRCellSize = l.ReGIR.Cell.Size; s.ReGIRBuildSamples = l.ReGIR.BuildSamples;
         ThrowIfFailed(m_context, pt_di_set_light_sampling(m_context, &s));
+        PtDIReGIRLayoutSettings layout{};
+        layout.Layout = (uint32_t)l.ReGIR.Layout;
+        ThrowIfFailed(m_context, pt_di_set_regir_layout(m_context, &layout));
     }
 
     void SetConstants(const Settings& settings)

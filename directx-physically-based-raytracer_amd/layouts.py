@@ -181,6 +181,21 @@ def di_light_sampling_settings(mode="regir", cell_size=1.0, build_samples=8):
     return s
 
 
+DI_REGIR_LAYOUT_GRID, DI_REGIR_LAYOUT_ONION = 0, 1
+DI_REGIR_LAYOUTS = {"grid": DI_REGIR_LAYOUT_GRID, "onion": DI_REGIR_LAYOUT_ONION}
+
+DI_REGIR_LAYOUT_SETTINGS = np.dtype({  # PtDIReGIRLayoutSettings: the layout of the ReGIR cells (pt_di_set_regir_layout)
+    "names": ["Layout", "_pad"], "formats": ["<u4", ("<u4", 3)], "offsets": [0, 4], "itemsize": 16})
+
+
+def di_regir_layout_settings(layout="grid"):
+    """PtDIReGIRLayoutSettings. layout: "grid" (this library's default: 16 x 16 x 16 cubes), "onion" (the reference's compiled
+    RTXDI_REGIR_ONION: 2253 cells in concentric shells around the camera), or a DI_REGIR_LAYOUT_* value. It acts only in ReGIR mode."""
+    s = np.zeros((), DI_REGIR_LAYOUT_SETTINGS)
+    s["Layout"] = DI_REGIR_LAYOUTS[layout] if isinstance(layout, str) else layout
+    return s
+
+
 DI_PREVIOUS_TEXTURES = ["PreviousGeometricNormal", "PreviousLinearDepth", "PreviousBaseColorMetalness", "PreviousNormalRoughness",
                         "PreviousIOR", "PreviousTransmission"]   # PtDIPreviousTextures member order
 

@@ -28,6 +28,7 @@ EXPORTS = [
     "pt_di_set_constants", "pt_di_render", "pt_di_light_count", "pt_di_download_lights",
     "pt_di_set_resampling", "pt_di_render_with_history", "pt_di_reset_history", "pt_di_download_reservoirs",
     "pt_di_set_light_sampling", "pt_di_download_presampled", "pt_di_set_visibility", "pt_di_set_pairwise",
+    "pt_di_set_regir_layout", "pt_di_regir_onion_table",
     "pt_post_set_constants", "pt_post_render", "pt_post_download_bloom",
     "pt_sharc_configure", "pt_sharc_set_constants", "pt_raytrace_render_sharc", "pt_sharc_reset", "pt_sharc_download",
     "pt_sharc_debug_keys", "pt_sharc_debug_query", "pt_sharc_download_update_paths", "pt_sharc_download_update_scatter",
@@ -183,6 +184,8 @@ def load_library():
         lib.pt_di_set_light_sampling.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_di_set_visibility.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_di_set_pairwise.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_di_set_regir_layout.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_di_regir_onion_table.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.pt_di_download_presampled.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.pt_post_set_constants.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_post_render.argtypes = [C.c_void_p, C.c_void_p]
@@ -632,6 +635,20 @@ class Raytracing:
         ctx.check(lib.pt_raytrace_render(ctx.handle, C.addressof(t)))
 
 
+def onion_table(which):
+    """The static tables of the ReGIR Onion layout at unit scale (pt_di_regir_onion_table; host only, no context, no GPU), float32.
+    which = 0: the 16 squared layer boundaries; 1: the 20 ring thresholds, by group; 2: the 241 azimuth thresholds, by (group, ring);
+    3: the cell spheres [2253, 4] (centre xyz, radius)."""
+    lib = load_library()
+    n = C.c_uint32(0)
+    if lib.pt_di_regir_onion_table(which, None, 0, C.byref(n)) != 0:
+        raise PtInvalidArgument("pt_di_regir_onion_table: which must be 0..3")
+    out = np.empty(n.value, np.float32)
+    if lib.pt_di_regir_onion_table(which, C.c_void_p(out.ctypes.data), n.value, C.byref(n)) != 0:
+        raise PtInvalidArgument("pt_di_regir_onion_table failed")
+    return out.reshape(-1, 4) if which == 3 else out
+
+
 class DirectLighting:
     """Mirror of the reference's RTXDI operator (Source/RTXDI.ixx: SetConstants + Render) for this library's DI pass: emissive-triangle
     lights, LocalLightSamples power-proportional candidates, streaming RIS, one visibility ray. Writes Textures["Diffuse"] /
@@ -699,9 +716,19 @@ class DirectLighting:
         self._pairwise = np.array(settings).reshape(())
         self.ctx.check(self.ctx.lib.pt_di_set_pairwise(self.ctx.handle, C.c_void_p(self._pairwise.ctypes.data)))
 
+    def SetReGIRLayout(self, settings):
+        """PtDIReGIRLayoutSettings (layouts.di_regir_layout_settings), or None: the Grid. It acts only in ReGIR mode. A changed value
+        resets the history."""
+        if settings is None:
+            self.ctx.check(self.ctx.lib.pt_di_set_regir_layout(self.ctx.handle, None))
+            return
+        self._regir_layout = np.array(settings).reshape(())
+        self.ctx.check(self.ctx.lib.pt_di_set_regir_layout(self.ctx.handle, C.c_void_p(self._regir_layout.ctypes.data)))
+
     def download_presampled(self, which):
-        """which = 0: the Power_RIS tiles (128 x 1024, tile-major), 1: the ReGIR cells (4096 x 512, cell-major, x fastest) of the last
-        Render (numpy layouts.DI_PRESAMPLED_LIGHT; empty when that render did not fill them)."""
+        """which = 0: the Power_RIS tiles (128 x 1024, tile-major), 1: the ReGIR cells (cell-major; Grid: 4096 x 512, x fastest; Onion:
+        2253 x 512 in the layout's cell order) of the last Render (numpy layouts.DI_PRESAMPLED_LIGHT; empty when that render did not
+        fill them)."""
         return _download_counted(self.ctx, self.ctx.lib.pt_di_download_presampled, L.DI_PRESAMPLED_LIGHT, which)
 
     def download_reservoirs(self):
@@ -840,7 +867,8 @@ class Renderer:
         self.constants["RenderSize"] = (width, height)
         self.constants["Flags"] = L.GBufferFlags.DefaultNoDenoiser        # App.cpp:1224 with Denoiser::None
 
-    def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None, post=None, sharc=None, di_visibility=None, di_pairwise=None):
+    def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None, post=None, sharc=None, di_visibility=None, di_pairwise=None,
+               di_regir_layout=None):
         """di_samples > 0: run the DI pass with that many candidates per pixel; set settings["IsDIEnabled"] to have the path tracer
         consume it (the textures need Diffuse / Specular: with_denoiser_outputs=True). di_reuse: PtDIResamplingSettings
         (layouts.di_resampling_settings) for reservoir reuse; temporal reuse needs di_history=True. With di_history the current and
@@ -848,7 +876,8 @@ class Renderer:
         frame's G-buffer and the Previous* ones the last frame's. di_light_sampling: PtDILightSamplingSettings
         (layouts.di_light_sampling_settings), or None: the power CDF. di_visibility: PtDIVisibilitySettings (layouts.di_visibility_settings)
         for visibility in the reservoirs (initial visibility, Raytraced bias correction, final-visibility reuse), or None: none. di_pairwise: PtDIPairwiseSettings
-        (layouts.di_pairwise_settings) to turn a pass's Basic bias correction into Pairwise, or None: off. post: PtPostProcessSettings (layouts.post_processing_settings) to run
+        (layouts.di_pairwise_settings) to turn a pass's Basic bias correction into Pairwise, or None: off. di_regir_layout: PtDIReGIRLayoutSettings
+        (layouts.di_regir_layout_settings) for the layout of the ReGIR cells, or None: the Grid. post: PtPostProcessSettings (layouts.post_processing_settings) to run
         the post-processing chain on the frame's Radiance; it writes textures["Color"], ["BackBuffer"] and ["Display8"]. Unsharded
         contexts only: a sharded host gathers Radiance and runs PostProcessing on the full frame. sharc: PtSHARCSettings
         (layouts.sharc_settings) to render the frame through the radiance cache (self.sharc.Configure first); None: the plain path tracer."""
@@ -874,6 +903,7 @@ class Renderer:
             self.direct_lighting.SetLightSampling(di_light_sampling)
             self.direct_lighting.SetVisibility(di_visibility)
             self.direct_lighting.SetPairwise(di_pairwise)
+            self.direct_lighting.SetReGIRLayout(di_regir_layout)
             self.direct_lighting.Render(tlas)
         if int(np.array(settings).reshape(())["Bounces"]) > 0:            # App.cpp:1277
             self.raytracing.SetConstants(settings)

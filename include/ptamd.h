@@ -489,7 +489,8 @@ int  pt_di_set_pairwise(PtContext* ctx, const PtDIPairwiseSettings* settings);
  * parameters (128 tiles x 1024 lights, 16-pixel screen tiles, a 16 x 16 x 16 grid of 512 lights per cell, jitter 1) are unpinned.
  * POWER_CDF is this library's default and keeps the plain and reuse passes exactly as without this call. POWER_RIS presamples
  * 1 MB of light tiles per render; REGIR_RIS also builds 16 MB of grid cells around the camera Position of the render (points
- * outside the grid fall back to POWER_RIS). Each context owns its own presampling buffers.
+ * outside the grid fall back to POWER_RIS), or 9.2 MB of Onion cells under pt_di_set_regir_layout. Each context owns its own
+ * presampling buffers.
  * ------------------------------------------------------------------------------------------ */
 enum { PT_DI_LOCAL_LIGHT_POWER_CDF = 0,   /* this library's default: draw from the power prefix sum */
        PT_DI_LOCAL_LIGHT_UNIFORM   = 1,   /* ReSTIRDI_LocalLightSamplingMode::Uniform */
@@ -508,9 +509,30 @@ typedef struct PtDIPresampledLight {
 
 /* NULL: POWER_CDF. Out-of-range values are refused and leave the previous setting active; a changed value resets the history. */
 int  pt_di_set_light_sampling(PtContext* ctx, const PtDILightSamplingSettings* settings);
-/* which = 0: the Power_RIS tiles (tile-major, 128 x 1024), 1: the ReGIR cells (cell-major, x fastest, 4096 x 512) of the last
- * pt_di_render; out_count = 0 when that render did not fill them; synchronises */
+/* which = 0: the Power_RIS tiles (tile-major, 128 x 1024), 1: the ReGIR cells (cell-major; Grid: x fastest, 4096 x 512; Onion:
+ * 2253 x 512 in the layout's cell order) of the last pt_di_render; out_count = 0 when that render did not fill them; synchronises */
 int  pt_di_download_presampled(PtContext* ctx, uint32_t which, PtDIPresampledLight* host_dst, uint32_t capacity, uint32_t* out_count);
+
+/* ------------------------------------------------------------------------------------------
+ * the layout of the ReGIR cells (the reference compiles RTXDI_REGIR_MODE RTXDI_REGIR_ONION, Shaders/RTXDIAppBridge.hlsli:6, and
+ * fills onionParams in Source/RTXDI.ixx:83-113). GRID, the default: 16 x 16 x 16 cubes of ReGIRCellSize. ONION: 2253 cells around
+ * the camera Position -- the sphere of radius c = 0.5 * ReGIRCellSize, then 15 concentric shells out to 145.055 c, each cut into
+ * latitude rings and longitude cells (5 layer groups of 8, 12, 16, 20, 24 partitions with 1, 1, 1, 1, 11 layers). The RTXDI SDK is
+ * not in the reference tree: the layout is this library's own, after the SDK's structure, unpinned. DESIGN.md section 1,
+ * "Local-light sampling", is the spec. The setting acts only in PT_DI_LOCAL_LIGHT_REGIR_RIS; ONION builds 9.2 MB of cells.
+ * ------------------------------------------------------------------------------------------ */
+enum { PT_DI_REGIR_LAYOUT_GRID = 0, PT_DI_REGIR_LAYOUT_ONION = 1 };
+typedef struct PtDIReGIRLayoutSettings {
+    uint32_t Layout;                      /* PT_DI_REGIR_LAYOUT_* (reference: ONION) */
+    uint32_t _pad[3];
+} PtDIReGIRLayoutSettings;                /* 16 B */
+/* NULL: GRID. An unknown Layout is refused and leaves the previous setting active; a changed value resets the history. */
+int  pt_di_set_regir_layout(PtContext* ctx, const PtDIReGIRLayoutSettings* settings);
+/* The Onion layout's static tables at unit scale (host only: no context, no GPU). which = 0: the 16 squared layer boundaries;
+ * 1: the ring thresholds sin^2, concatenated by group (20); 2: the azimuth thresholds (pseudo-angles in [0, 4)), concatenated in
+ * (group, ring) order (241); 3: the cell spheres, (centre xyz, radius) x 2253. out_count = the number of floats; min(capacity,
+ * out_count) floats are copied. */
+int  pt_di_regir_onion_table(uint32_t which, float* host_dst, uint32_t capacity, uint32_t* out_count);
 
 /* ------------------------------------------------------------------------------------------
  * building blocks the reference's direct-lighting bridge calls on the same data

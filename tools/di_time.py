@@ -4,7 +4,7 @@ the pass with temporal + spatial reservoir reuse at the reference's defaults (la
 --visibility (with --reuse) adds the pass with visibility in the reservoirs (layouts.di_visibility_settings): initial visibility, + Raytraced in both
 passes, + final-visibility reuse, each with the final shadow rays per pixel counted from the downloaded reservoirs (a shaded reservoir
 whose visibility has age 0 was traced this frame, an older one was reused). --pairwise (with --reuse) times Basic and Pairwise bias
-correction (layouts.di_pairwise_settings, both passes) side by side at SpatialSamples 1 and 4, three alternating rounds each. --light-sampling times each listed local-light sampling mode (cdf, uniform, power_ris, regir; one JSON line per mode). The workload
+correction (layouts.di_pairwise_settings, both passes) side by side at SpatialSamples 1 and 4, three alternating rounds each. --light-sampling times each listed local-light sampling mode (cdf, uniform, power_ris, regir, regir_onion: ReGIR over the Onion layout; one JSON line per mode). The workload
 emitter_field is scenes.emitter_field(256) (131 k emissive triangles) at 1920 x 1080, 1 spp, 1 bounce.
 usage: tools/di_time.py [--workloads c2,c3,c5,emitter_field] [--samples 8] [--n 20] [--reuse [--visibility] [--pairwise]] [--light-sampling cdf,regir]"""
 import argparse, json, os, subprocess, sys
@@ -44,19 +44,21 @@ def child(w, samples, n, reuse, modes, visibility=False, pairwise=False):
     ctx.sync()
     off_ms = timed(lambda i: r.render(gs), max(3, n // 4))
     for mode in modes:
-        ls = None if mode == "cdf" else L.di_light_sampling_settings(mode)
+        ls = None if mode == "cdf" else L.di_light_sampling_settings("regir" if mode == "regir_onion" else mode)
+        layout = L.di_regir_layout_settings("onion") if mode == "regir_onion" else None
         r.render(gs)
         ctx.sync()
         r.direct_lighting.SetConstants(L.di_settings(W, H, 0, samples, ext_flags=ext))
         r.direct_lighting.SetLightSampling(ls)
+        r.direct_lighting.SetReGIRLayout(layout)
         lights = r.direct_lighting.light_count()
         for _ in range(3):
             r.direct_lighting.Render(tlas)
         ctx.sync()
         di_ms = timed(lambda i: r.direct_lighting.Render(tlas), n)
         gs_on = gs.copy(); gs_on["IsDIEnabled"] = 1
-        r.render(gs_on, di_samples=samples, di_light_sampling=ls); ctx.sync()
-        on_ms = timed(lambda i: r.render(gs_on, di_samples=samples, di_light_sampling=ls), max(3, n // 4))
+        r.render(gs_on, di_samples=samples, di_light_sampling=ls, di_regir_layout=layout); ctx.sync()
+        on_ms = timed(lambda i: r.render(gs_on, di_samples=samples, di_light_sampling=ls, di_regir_layout=layout), max(3, n // 4))
         out = {"workload": w, "size": [W, H], "lights": lights, "samples": samples, "light_sampling": mode, "di_ms": di_ms,
                "frame_di_off_ms": off_ms, "frame_di_on_ms": on_ms}
         if mode != modes[-1]:
