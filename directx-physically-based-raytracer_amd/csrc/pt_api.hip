@@ -206,6 +206,12 @@ static int check_geometries(Context& c, const PtGeometryDesc* geometries, uint32
 
 // the traversal stack holds at most two entries per level of both trees (a node group and, in the streaming form, a postponed
 // leaf group) plus the three of an instance transition (pt_trace.hpp)
+static bool any_non_opaque(const PtGeometryDesc* geometries, uint32_t geometry_count)
+{
+    for (uint32_t g = 0; g < geometry_count; g++) if (!(geometries[g].Flags & PT_GEOMETRY_FLAG_OPAQUE)) return true;
+    return false;
+}
+
 static int check_depth(Context& c, uint32_t tlasDepth)
 {
     if (2u * (tlasDepth + c.maxBlasDepth) + 4u > (uint32_t)kStackSize)
@@ -245,6 +251,7 @@ int pt_build_bottom_level(PtContext* ctx, const PtGeometryDesc* geometries, uint
     if (e != hipSuccess) return fail_hip(&c, e, "bottom-level build");
     if (b.buildError || 2u * b.depth + 4u > (uint32_t)kStackSize) return fail(&c, PT_ERROR_INVALID_ARGUMENT, "bottom-level build failed: tree too deep for the traversal stack");
     b.geometryCount = geometry_count;
+    b.hasNonOpaque = any_non_opaque(geometries, geometry_count);
     uint64_t id = c.nextBlasId++;
     c.maxBlasDepth = std::max(c.maxBlasDepth, b.depth);
     c.blas[id] = std::move(b);
@@ -271,6 +278,7 @@ int pt_update_bottom_level(PtContext* ctx, uint64_t blas_id, const PtGeometryDes
     if (b.updatable && ntris == b.triCount && geometry_count == b.geometryCount) {
         hipError_t e = refit_blas_device(geometries, geometry_count, c.stream, b);
         if (e != hipSuccess) return fail_hip(&c, e, "bottom-level update");
+        b.hasNonOpaque = any_non_opaque(geometries, geometry_count);   // the refit rewrites the packets' flags from these descriptors
         drop_tlas(c);                                    // instance boxes are stale until the top level is rebuilt
         return PT_OK;
     }
@@ -284,6 +292,7 @@ int pt_update_bottom_level(PtContext* ctx, uint64_t blas_id, const PtGeometryDes
     if (e != hipSuccess) return fail_hip(&c, e, "bottom-level update");
     if (nb.buildError || 2u * nb.depth + 4u > (uint32_t)kStackSize) return fail(&c, PT_ERROR_INVALID_ARGUMENT, "bottom-level update failed: tree too deep for the traversal stack");
     nb.geometryCount = geometry_count;
+    nb.hasNonOpaque = any_non_opaque(geometries, geometry_count);
     c.maxBlasDepth = std::max(c.maxBlasDepth, nb.depth);
     b = std::move(nb);
     drop_tlas(c);                                        // instance records point at the freed arrays
@@ -529,6 +538,8 @@ int pt_build_top_level(PtContext* ctx, const PtInstanceDesc* descs, uint32_t cou
     r.blob.instCount = count; r.blob.nodeCount = P.blobNodes; r.blob.triCount = P.blobTris; r.blob.bytes = (uint32_t)P.total;
     r.blasTable = dTable; r.blasTableCount = (uint32_t)P.table.size(); r.instSource = dSrc; r.blasTableMaxTris = 0;
     for (const BlasEntry& te : P.table) r.blasTableMaxTris = std::max(r.blasTableMaxTris, te.triCount);
+    r.hasNonOpaque = false;                                         // over the bottom levels this top level refers to (those that only ride along are never entered)
+    for (const auto& p : P.pieces) if (p.referenced && p.b->hasNonOpaque) r.hasNonOpaque = true;
     c.tlasBlasIds = P.pieceIds;
     if (P.objectEnd != c.tlasObjectEnd || count != c.tlasValidatedCount || P.bindingHash != c.tlasBindingHash) c.validated = false;     // same instances of the same bottom levels over the same objects: nothing new to check
     c.tlasObjectEnd = P.objectEnd; c.tlasValidatedCount = count; c.tlasBindingHash = P.bindingHash;
@@ -563,6 +574,7 @@ int pt_share_scene(PtContext* ctx, PtContext* source)
     c.objects = s.objects; c.objectCount = s.objectCount; c.instanceData = s.instanceData; c.instanceDataCount = s.instanceDataCount;
     c.sceneOwner = &s; s.viewers.push_back(&c);
     c.tlasHeaderPending = false; c.validated = false;
+    c.hasTransmission = c.gbufferTransmission = true;                       // unknown until this context has resolved the object data itself
     c.haveTlas = true;
     return PT_OK;
 }
@@ -619,7 +631,9 @@ int pt_invalidate_object_data(PtContext* ctx)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     ctx->c.validated = false; ctx->c.normalsShared = false; ctx->c.sharedVerdict = false;   // the next render resolves VertexDesc / MeshDescriptors again (validate_scene)
+    ctx->c.hasTransmission = true;                                                            // ... and looks for transmissive materials again: unknown until then
     ctx->c.objectDataGen++;                                                                   // ... and pt_di_render lists the emissive triangles again
+    for (pt::Context* v : ctx->c.viewers) { v->validated = false; v->hasTransmission = true; }   // the contexts that view this scene read the same array
     return PT_OK;
 }
 int pt_set_instance_data(PtContext* ctx, const PtInstanceData* device_instances, uint32_t count)
@@ -672,12 +686,14 @@ static int validate_scene(Context& c)
 {
     if (c.validated && c.validatedObjects == c.objects && c.validatedObjectCount == c.objectCount) return PT_OK;
     const uint32_t heapCount = (uint32_t)c.heapHost.size();
+    c.hasTransmission = true;                               // unknown until the kernel below has looked (every failure leaves it so)
     if (c.tlasObjectEnd > c.objectCount)
         return fail(&c, PT_ERROR_INVALID_ARGUMENT, "InstanceID + geometry count of an instance reaches ObjectData[" + std::to_string(c.tlasObjectEnd - 1)
                     + "] but only " + std::to_string(c.objectCount) + " objects are bound (pt_set_object_data)");
     if (c.instanceData && c.instanceDataCount < c.scene.instanceCount)
         return fail(&c, PT_ERROR_INVALID_ARGUMENT, "InstanceData holds fewer records than the top level has instances");
     uint32_t sharedMismatch = 0;
+    bool transmission = false;                              // no objects: nothing to hit
     if (c.objectCount) {
         API_HIP(&c, c.validateDev.reserve(8));
         if (c.objectCount > c.shadeGeomDev.capacity()) {    // the resolved-geometry table the same kernel fills (grow-only; kernels in flight may read the old one)
@@ -695,6 +711,7 @@ static int validate_scene(Context& c)
         API_HIP(&c, hipMemcpyAsync(r, c.validateDev.data(), sizeof r, hipMemcpyDeviceToHost, c.stream));
         API_HIP(&c, hipStreamSynchronize(c.stream));
         sharedMismatch = r[4];
+        transmission = r[5] != 0u;
         if (r[0]) {
             static const char* what[] = { "", "MeshDescriptors.Vertices", "MeshDescriptors.Indices", "MeshDescriptors.MotionVectors", "TextureMapInfo.Descriptor" };
             return fail(&c, PT_ERROR_INVALID_ARGUMENT, std::string("ObjectData[") + std::to_string(r[1]) + "]." + what[r[0] < 5 ? r[0] : 0] + " = " + std::to_string(r[2])
@@ -704,6 +721,7 @@ static int validate_scene(Context& c)
     c.validated = true; c.validatedObjects = c.objects; c.validatedObjectCount = c.objectCount;
     c.sharedVerdict = c.objectCount != 0 && c.scene.blasTable != nullptr && sharedMismatch == 0;
     c.normalsShared = c.sharedVerdict;
+    c.hasTransmission = transmission;
     return PT_OK;
 }
 

@@ -43,6 +43,7 @@ struct Blas {
     DeviceBuffer<float> rootBounds;          // lo.xyz hi.xyz
     uint32_t triCount = 0, leafCount = 0, nodeCount = 0, depth = 0, geometryCount = 0;
     bool buildError = false, updatable = false;
+    bool hasNonOpaque = true;                // a geometry of the last build / update lacks PT_GEOMETRY_FLAG_OPAQUE
     // a static bottom level lives in the context's traversal copy only, once a top-level build has seen it (pt_api.hip pt_build_top_level):
     // nodes / tris / idx above are empty then, and these are the byte offsets of its three pieces in that copy
     bool inBlob = false; uint64_t blobNodeAt = 0, blobTriAt = 0, blobIdxAt = 0;
@@ -73,6 +74,9 @@ struct SceneRefs {
     BlobView blob{};                         // compact traversal copy of TLAS + instances + every referenced BLAS
     const BlasEntry* blasTable = nullptr; uint32_t blasTableCount = 0, blasTableMaxTris = 0;   // the top-level build's table of bottom levels
     const InstanceSource* instSource = nullptr;
+    // A candidate can be non-opaque: some geometry of a bottom level this top level refers to lacks PT_GEOMETRY_FLAG_OPAQUE (the only source
+    // include/ptamd.h has: no instance flags, no ray flags on closest-hit rays). Unknown -- no top level -- is "has".
+    bool hasNonOpaque = true;
 };
 
 // What hit reconstruction needs of an object's geometry, resolved once per change of (ObjectData, heap) by the validation kernel: the
@@ -161,6 +165,10 @@ struct Context {
     bool sharedVerdict = false;              // what the last shared-geometry check said (normalsShared is put aside while there is no top level)
     bool validated = false; DeviceBuffer<uint32_t> validateDev;   // descriptor / index validation of the scene inputs (pt_api.hip make_views)
     const void* validatedObjects = nullptr; uint32_t validatedObjectCount = 0;
+    // Scene facts behind the kernels' ALPHA / TRANSMISSION switches (plan_frame); unknown is "has". hasTransmission: some object has Material.Transmission != 0
+    // or a Transmission texture (k_validate_objects, with the validation: per change of ObjectData / heap / top level, and after pt_invalidate_object_data).
+    // gbufferTransmission: the same fact when this context last rendered a G-buffer -- bounce 0 reads Transmission from there, not from ObjectData.
+    bool hasTransmission = true, gbufferTransmission = true;
 
     PtCamera camera{}; PtSceneData sceneData{}; PtGraphicsSettings settings{};
     bool haveCamera = false, haveSceneData = false, haveSettings = false;
@@ -267,6 +275,24 @@ template <typename F, typename... Rest> void with_flags(F&& f, bool first, Rest.
     else with_flags([&](auto... bs) { f(std::false_type{}, bs...); }, rest...);
 }
 
+// Developer builds (tools/ab.sh): -DPT_SPEC_FORCE_ALPHA / -DPT_SPEC_FORCE_TRANSMISSION hold one of the two scene switches at "has" whatever the scene,
+// and -DPT_SPEC_SPLIT gives k_round the two switches apart, so that each can be timed alone. The product defines none of them.
+#ifdef PT_SPEC_FORCE_ALPHA
+constexpr bool kSpecForceAlpha = true;
+#else
+constexpr bool kSpecForceAlpha = false;
+#endif
+#ifdef PT_SPEC_FORCE_TRANSMISSION
+constexpr bool kSpecForceTransmission = true;
+#else
+constexpr bool kSpecForceTransmission = false;
+#endif
+#ifdef PT_SPEC_SPLIT
+constexpr bool kSpecSplit = true;
+#else
+constexpr bool kSpecSplit = false;
+#endif
+
 // pt_bvh.hip
 hipError_t build_blas_device(const PtGeometryDesc* geoms, uint32_t ngeoms, bool allowUpdate, hipStream_t stream, Blas& out);
 hipError_t refit_blas_device(const PtGeometryDesc* geoms, uint32_t ngeoms, hipStream_t stream, Blas& b);
@@ -290,6 +316,7 @@ struct FramePlan {
     uint32_t objectsInLds, recordsInLds;             // what k_round stages behind the traversal copy
     bool recordsUsable;                              // the frame has normal records (k_capture_normals runs)
     bool writeT, stats, di, textured, sharc;         // the kernel variants' switches
+    bool alpha, transmission;                        // ... and the scene's: non-opaque geometry / transmissive materials may exist (both false: compiled out of k_round)
     float2* aux;                                     // denoiser modes: the per-pixel auxiliary record, else null
     uint32_t nsq() const { return 1u << sqShift; }
     uint32_t cstride() const { return 3u * nsq(); }  // traced + fresh counters + the streaming form's cursor, per round

@@ -367,7 +367,10 @@ struct RoundArgs {
     const SharcView* sharc; const float* roughIn; float* roughOut;   // the SHARC instantiations only: the resolved cache, previousRoughness of qin / qout's entries
 };
 
-template <bool TEXTURED, bool LDS, bool FLAT, bool DI, bool SHARC = false>
+// ALPHA / TRANSMISSION = false: the scene has no non-opaque geometry / no transmissive material (FramePlan::alpha, ::transmission): the alpha-test
+// call and the third lobe are compiled out. The product instantiates the pair as ONE switch (neither / generic, enqueue_chain). This is the only
+// kernel that takes the switches: in k_gbuffer, k_pt_first, k_shade and k_extend_stream they measured as nothing or as a loss.
+template <bool TEXTURED, bool LDS, bool FLAT, bool DI, bool SHARC = false, bool ALPHA = true, bool TRANSMISSION = true>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_round(const RoundArgs* __restrict__ A, uint32_t sqBase, uint32_t sqCount)
 {
     const SceneView& sv = A->sv; const FrameView& fv = A->fv; const PtTextures& tx = A->tx; const BlobView& bv = A->bv;
@@ -436,16 +439,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             Hit h;
             if constexpr (FLAT) {
                 unsigned char* ldsWave = smem + (uint32_t)kStackLdsFlat * 256u * 8u + (threadIdx.x >> 6) * kFlatWaveLds;
-                h = trace_closest_flat<false, LDS>(blob, bv, ac, V3(o.x, o.y, o.z), V3(d.x, d.y, d.z), o.w, d.w, ldsStack, ldsWave, &st, prof);
+                h = trace_closest_flat<false, LDS, ALPHA>(blob, bv, ac, V3(o.x, o.y, o.z), V3(d.x, d.y, d.z), o.w, d.w, ldsStack, ldsWave, &st, prof);
             } else {
                 uint32_t* ldsCand = (uint32_t*)(smem + kStackLds2Bytes);
                 unsigned char* ldsWave = smem + kStackLds2Bytes + (uint32_t)kCandidates * 256u * 4u + (threadIdx.x >> 6) * kPhasedWaveLds;
-                h = trace_closest_v2<false, LDS, kStackLds2>(blob, bv, ac, V3(o.x, o.y, o.z), V3(d.x, d.y, d.z), o.w, d.w, ldsStack, ldsCand, ldsWave, &st);
+                h = trace_closest_v2<false, LDS, kStackLds2, ALPHA>(blob, bv, ac, V3(o.x, o.y, o.z), V3(d.x, d.y, d.z), o.w, d.w, ldsStack, ldsCand, ldsWave, &st);
             }
             bool toTraced = false, toFresh = false;
             v3 newO = V3(0, 0, 0), newD = V3(0, 0, 1);
             if (valid) {
-                shade_traced<TEXTURED, DI, SHARC>(sv, GeometryFromBlob<LDS>{ blob, bv, tables }, sd, gs, tx, aux, p, make_uint4(h.inst, h.slot, __float_as_uint(h.u), __float_as_uint(h.v)), h.t,
+                shade_traced<TEXTURED, DI, SHARC, TRANSMISSION>(sv, GeometryFromBlob<LDS>{ blob, bv, tables }, sd, gs, tx, aux, p, make_uint4(h.inst, h.slot, __float_as_uint(h.u), __float_as_uint(h.v)), h.t,
                                        V3(d.x, d.y, d.z), toTraced, toFresh, newO, newD, prof, A->sharc, &pr);
             }
             PT_PROF_MARK(prof, 6);
@@ -465,7 +468,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         if (local < nF) {
             p = load_path(qin, seg + (segCap - 1u - local));
             PT_PROF_WAIT(); PT_PROF_MARK(prof, 12);
-            shade_fresh<DI, SHARC>(fv, cam, gs, tx, aux, primary, p, toTraced, toFresh, newO, newD, prof, &pr);
+            shade_fresh<DI, SHARC, TRANSMISSION>(fv, cam, gs, tx, aux, primary, p, toTraced, toFresh, newO, newD, prof, &pr);
         }
         PT_PROF_MARK(prof, 14);
         emit_tile<SHARC>(qout, seg, segCap, &countOut[sq], &countOut[nsq + sq], lds + ((emits++ & 1u) << 4), toTraced, toFresh, p, newO, newD, A->roughOut, pr);
@@ -589,6 +592,17 @@ __global__ void k_validate_objects(const PtObjectData* __restrict__ objects, uin
         shadeTex[(size_t)i * kTextureSlots + k] = e;
     }
     if (err && atomicCAS(&out[0], 0u, err) == 0u) { out[1] = i; out[2] = desc; out[3] = kind; }
+    // out[5]: the scene may transmit (Context::hasTransmission). Transmission != 0 also holds for a NaN; a Transmission texture counts whatever the
+    // factor; and a Metallic that is not finite, or comes out of a float texture, could turn 0 * (1 - Metallic) into a NaN: all "has".
+    {
+        bool has = od->Material.Transmission != 0.0f || od->TextureMapInfoArray[TEX_Transmission].Descriptor != ~0u || !isfinite(od->Material.Metallic);
+        for (int k = TEX_Metallic; k <= TEX_MetallicRoughness; k++) {
+            if (k == TEX_Roughness) continue;
+            const uint32_t d = od->TextureMapInfoArray[k].Descriptor;
+            if (d != ~0u && d < heapCount && heap[d].stride == kFmtRGBA32F) has = true;
+        }
+        if (has) out[5] = 1u;
+    }
     // the resolved geometry of the object (ShadeGeom): an object without vertex / index buffers has no vertex attributes to fetch
     ShadeGeom sg; sg.vb = nullptr; sg.stride = 0; sg.nOff = ~0u; sg.tOff = ~0u; sg.uvOff[0] = sg.uvOff[1] = ~0u; sg._pad = 0;
     if (!err && md[0] != ~0u && md[1] != ~0u) {
@@ -766,6 +780,7 @@ hipError_t launch_gbuffer(Context& c, const SceneView& sv, const FrameView& fv, 
         auto launch = [&](auto M) { k_gbuffer<S(), T(), M()><<<grid, 256, smem, c.stream>>>(sv, fv, c.camera, c.sceneData, flags, tx, c.scene.blob, c.counters.data()); };
         if (mode == 0) launch(std::integral_constant<int, 0>{}); else if (mode == 1) launch(std::integral_constant<int, 1>{}); else launch(std::integral_constant<int, 2>{});
     }, (c.debugFlags & PT_DEBUG_TRAVERSAL_STATS) != 0, c.heapHasTextures);
+    c.gbufferTransmission = c.hasTransmission;                           // what bounce 0 of the path tracer will read from these textures
     return hipGetLastError();
 }
 
@@ -849,6 +864,11 @@ static void plan_frame(FramePlan& p, Context& c, const SceneView& sv, const Fram
     p.stats = (c.debugFlags & PT_DEBUG_TRAVERSAL_STATS) != 0;
     p.di = gs.IsDIEnabled != 0u;
     p.textured = c.heapHasTextures;
+    // The scene's switches: "has" unless the facts say otherwise, and always for the validation / statistics / brute-force variants and under
+    // PT_DEBUG_GENERIC_SCENE. The plan's bytes are part of the graph key: a changed fact captures the frame again.
+    const bool generic = (c.debugFlags & (PT_DEBUG_GENERIC_SCENE | PT_DEBUG_TRAVERSAL_STATS | PT_DEBUG_BRUTE_FORCE | PT_DEBUG_TRAVERSAL_V1)) != 0;
+    p.alpha = generic || c.scene.hasNonOpaque || kSpecForceAlpha;
+    p.transmission = generic || c.hasTransmission || c.gbufferTransmission || kSpecForceTransmission;
 }
 
 // ---- the launch sequence of one frame after k_set_constants (which also zeroes the queue counters) ----------------------------------
@@ -910,9 +930,12 @@ static hipError_t enqueue_chain(Context& c, const FramePlan& p, const SceneView&
     }
     for (uint32_t r = 1; r <= p.rounds; r++) {                      // queues and counters of round r: in its argument block (launch_raytrace); round 0 ran inside k_pt_first
         timing_begin(c, c.evRound, c.nRound);
-        with_flags([&](auto T, auto L, auto F, auto D, auto S) {
-            k_round<T(), L(), F(), D(), S()><<<perSq * sqCount, 256, p.roundLds, s>>>(c.roundArgs.data() + r, sqBase, sqCount);
-        }, p.textured, p.lds, p.flat, p.di, p.sharc);
+        with_flags([&](auto T, auto L, auto F, auto D, auto S, auto A, auto X) {
+            // ONE switch for this kernel, neither / generic: 64 instantiations instead of 32, and 1.8 times the compile time of this file; with the
+            // two apart there would be 128. A developer build (-DPT_SPEC_SPLIT, tools/ab.sh) takes them apart to time each alone
+            constexpr bool generic = A() || X();
+            k_round<T(), L(), F(), D(), S(), kSpecSplit ? A() : generic, kSpecSplit ? X() : generic><<<perSq * sqCount, 256, p.roundLds, s>>>(c.roundArgs.data() + r, sqBase, sqCount);
+        }, p.textured, p.lds, p.flat, p.di, p.sharc, p.alpha, p.transmission);
         timing_end(c, c.evRound, c.nRound); c.nRound++;
     }
     return hipGetLastError();
@@ -1006,7 +1029,7 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
 
     // hipGraph replay: launch-bound frames (small shards, tail rounds) cost ~75 launches; a replay is one submission.
     const bool graphable = c.stream != nullptr && !c.timing && !c.disableGraphs &&
-                           (c.debugFlags & ~(PT_DEBUG_UNFUSED_ROUNDS | PT_DEBUG_TRAVERSAL_PHASED | PT_DEBUG_LOCKSTEP | PT_DEBUG_GATHER_LOCAL_ONLY | PT_DEBUG_GATHER_SELF_EXCHANGE | PT_DEBUG_SHARC_LOG_PATHS | PT_DEBUG_SHARC_SKIP_UPDATE)) == 0;   // counters / validation variants launch directly
+                           (c.debugFlags & ~(PT_DEBUG_UNFUSED_ROUNDS | PT_DEBUG_TRAVERSAL_PHASED | PT_DEBUG_LOCKSTEP | PT_DEBUG_GATHER_LOCAL_ONLY | PT_DEBUG_GATHER_SELF_EXCHANGE | PT_DEBUG_SHARC_LOG_PATHS | PT_DEBUG_SHARC_SKIP_UPDATE | PT_DEBUG_GENERIC_SCENE)) == 0;   // counters / validation variants launch directly
     auto capture = [&](hipStream_t s, GraphExec& exec, auto&& body) -> hipError_t {               // one linear graph from what `body` enqueues on s
         if (exec) { hipStreamSynchronize(c.stream); exec.reset(); }                                 // its last replay may still be running (once per change of scene / frame geometry)
         hipGraph_t graph = nullptr;

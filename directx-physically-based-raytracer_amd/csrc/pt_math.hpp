@@ -323,17 +323,27 @@ struct BSDFSample {                           // BxDF.hlsli:36-44
         return p;
     }
 
+    // TRANSMISSION = false (template parameter of the sampling functions below): the scene has no transmissive material at all
+    // (FramePlan::transmission), so tw is the literal 0, rw the literal 1 and the third lobe is compiled out. On such a scene the generic
+    // form computes tw = +-0 and multiplies by rw = 1: the same values (DESIGN.md "Arithmetic spec").
+    template <bool TRANSMISSION = true>
     PT_DEV void ComputeLobeWeights(const SurfaceVectors& sv, v3 V, uint32_t ext, float w[3]) const   // BxDF.hlsli:184-196
     {
         if (ext & kExtLambertianOnly) { w[0] = 1.0f; w[1] = 0.0f; w[2] = 0.0f; return; }
         float NoV = fabsf(dot(sv.ShadingNormal, V));
-        float tw = Transmission * (1.0f - Metallic);
-        float rw = 1.0f - tw;
         float dw = EstimateDiffuseProbability(NoV);
         float sw = 1.0f - dw;
-        w[LOBE_DIFFUSE] = dw * rw;
-        w[LOBE_SPECULAR] = sw * rw;
-        w[LOBE_TRANSMISSION] = tw;
+        if constexpr (TRANSMISSION) {
+            float tw = Transmission * (1.0f - Metallic);
+            float rw = 1.0f - tw;
+            w[LOBE_DIFFUSE] = dw * rw;
+            w[LOBE_SPECULAR] = sw * rw;
+            w[LOBE_TRANSMISSION] = tw;
+        } else {
+            w[LOBE_DIFFUSE] = dw;
+            w[LOBE_SPECULAR] = sw;
+            w[LOBE_TRANSMISSION] = 0.0f;
+        }
     }
 
     PT_DEV static v3 reflect(v3 i, v3 n) { float d = dot(n, i); return madd(n, -(2.0f * d), i); }
@@ -347,13 +357,16 @@ struct BSDFSample {                           // BxDF.hlsli:36-44
     }
 
     // FindLobe :198-212 + Sample :214-226 (+ :81-86, :110-118, :148-168)
+    template <bool TRANSMISSION = true>
     PT_DEV bool Sample(const SurfaceVectors& sv, v3 V, const float w[3], const float rnd[4], v3& L, int& lobe) const
     {
         lobe = 0;
-        {
+        if constexpr (TRANSMISSION) {
             float weight = w[2];
             if (rnd[0] < weight) lobe = 2;
             else { weight += w[1]; if (rnd[0] < weight) lobe = 1; }
+        } else {
+            if (rnd[0] < w[1]) lobe = 1;                   // w[2] = 0: never below rnd[0] >= 0, and 0 + w[1] = w[1]
         }
         if (lobe == LOBE_DIFFUSE) {
             L = rotate_vector_inv(sv.ShadingBasis, ml_cosine_get_ray(rnd[1], rnd[2]));
@@ -361,7 +374,7 @@ struct BSDFSample {                           // BxDF.hlsli:36-44
         }
         v3 Vlocal = rotate_vector(sv.ShadingBasis, V);
         v3 H = rotate_vector_inv(sv.ShadingBasis, ml_vndf_get_ray(rnd[1], rnd[2], Roughness, Vlocal));
-        if (lobe == LOBE_SPECULAR) {
+        if (!TRANSMISSION || lobe == LOBE_SPECULAR) {
             L = reflect(-V, H);
             return dot(sv.FrontGeometricNormal, L) > 0.0f;
         }
@@ -375,10 +388,11 @@ struct BSDFSample {                           // BxDF.hlsli:36-44
         return true;
     }
 
+    template <bool TRANSMISSION = true>
     PT_DEV v3 ComputeHalfVector(const SurfaceVectors& sv, v3 L, v3 V, bool isTransmissive) const   // :228-245
     {
         v3 N = sv.FrontGeometricNormal, H;
-        if (isTransmissive && dot(N, L) < 0.0f) {
+        if (TRANSMISSION && isTransmissive && dot(N, L) < 0.0f) {
             H = normalize(L * IORo + V * IORi);
             if (dot(N, H) < 0.0f) H = -H;
         } else {
@@ -406,20 +420,21 @@ struct BSDFSample {                           // BxDF.hlsli:36-44
     }
 
     // single-lobe EvaluatePDF :287-299 and Evaluate :301-315, fused (they share H and the dots)
+    template <bool TRANSMISSION = true>
     PT_DEV void EvaluateLobe(const SurfaceVectors& sv, v3 L, v3 V, const float w[3], int lobe, uint32_t ext,
                              float& pdf, v3& f) const
     {
-        const float tw = w[LOBE_TRANSMISSION];
-        const v3 H = ComputeHalfVector(sv, L, V, tw > 0.0f);
+        const float tw = TRANSMISSION ? w[LOBE_TRANSMISSION] : 0.0f;
+        const v3 H = ComputeHalfVector<TRANSMISSION>(sv, L, V, tw > 0.0f);
         const v3 N = sv.ShadingNormal;
         const float lw = w[lobe];
         const float NoL = fabsf(dot(N, L));
-        if (lobe == LOBE_TRANSMISSION) {
+        if (TRANSMISSION && lobe == LOBE_TRANSMISSION) {
             pdf = NoL * lw;
             f = (BaseColor * NoL) * tw;
             return;
         }
-        const float rw = 1.0f - tw;
+        const float rw = TRANSMISSION ? 1.0f - tw : 1.0f;
         pdf = 0.0f; f = V3(0.0f, 0.0f, 0.0f);
         if (!(dot(sv.FrontGeometricNormal, L) > 0.0f)) return;
         const float NoV = fabsf(dot(N, V)), VoH = fabsf(dot(V, H));

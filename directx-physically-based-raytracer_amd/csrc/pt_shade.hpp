@@ -335,20 +335,20 @@ PT_DEV bool scatter_step(const PtGraphicsSettings& gs, uint32_t bounce, uint32_t
 
 // SHARC (the query pass of the radiance cache, pt_raytrace_render_sharc): previousRoughness, the blur the path has gathered so far, grows by
 // the sampled lobe's width after every scatter (:366).
-template <bool SHARC = false>
+template <bool SHARC = false, bool TRANSMISSION = true>
 PT_DEV bool scatter(const PtGraphicsSettings& gs, PathRegs& p, const SurfaceHit& h, const BSDFSample& bs, v3 emission, v3 rayDir, v3& newO, v3& newD, int& lobe,
                     float* previousRoughness = nullptr)
 {
     p.srad = madd(p.thr, emission, p.srad);                       // :320
     const SurfaceVectors svec = surface_vectors(h.IsFrontFace, h.GeometricNormal, h.ShadingNormal);
     const v3 V = -rayDir;
-    float w[3]; bs.ComputeLobeWeights(svec, V, gs.ExtFlags, w);
+    float w[3]; bs.ComputeLobeWeights<TRANSMISSION>(svec, V, gs.ExtFlags, w);
     float rnd[4];
     rnd[0] = rng_float(p.rng); rnd[1] = rng_float(p.rng); rnd[2] = rng_float(p.rng); rnd[3] = rng_float(p.rng);   // GetFloat4, :330
     v3 L;
-    if (!bs.Sample(svec, V, w, rnd, L, lobe)) return false;
+    if (!bs.Sample<TRANSMISSION>(svec, V, w, rnd, L, lobe)) return false;
     float pdf; v3 f;
-    bs.EvaluateLobe(svec, L, V, w, lobe, gs.ExtFlags, pdf, f);
+    bs.EvaluateLobe<TRANSMISSION>(svec, L, V, w, lobe, gs.ExtFlags, pdf, f);
     if (pdf == 0.0f || (f.x == 0.0f && f.y == 0.0f && f.z == 0.0f)) return false;             // :336,342
     { const float ipdf = 1.0f / pdf; p.thr = p.thr * V3(f.x * ipdf, f.y * ipdf, f.z * ipdf); }   // :346 (float3 / float = the vector times ONE reciprocal: arithmetic spec)
     if (gs.IsRussianRouletteEnabled && p.bounce > 3) {                                        // :348-356
@@ -426,7 +426,7 @@ template <bool LDS> struct GeometryFromBlob {                // ... out of the s
 };
 
 // SHARC: `sharc` is the resolved cache, previousRoughness the path's entry of the side array; hitT is the hit's distance along the ray.
-template <bool TEXTURED, bool DI = false, bool SHARC = false, typename GEOMETRY>
+template <bool TEXTURED, bool DI = false, bool SHARC = false, bool TRANSMISSION = true, typename GEOMETRY>
 PT_DEV void shade_traced(const SceneView& sv, const GEOMETRY& geometry, const PtSceneData& sd, const PtGraphicsSettings& gs, const PtTextures& tx, float2* aux,
                          PathRegs& p, uint4 hr, float hitT, v3 rayDir, bool& toTraced, bool& toFresh, v3& newO, v3& newD, RoundProf* prof = nullptr,
                          const SharcView* sharc = nullptr, float* previousRoughness = nullptr)
@@ -451,7 +451,7 @@ PT_DEV void shade_traced(const SceneView& sv, const GEOMETRY& geometry, const Pt
             bs.Initialize(V3(m.BaseColor), m.Metallic, m.Roughness, m.IOR, m.Transmission, h.IsFrontFace);
             v3 emission = material_emission(m);
             if constexpr (DI) if (p.bounce == 1u && direct_valid(tx, p.pixel)) emission = V3(0, 0, 0);   // the DI pass lit this path's first hit, :302
-            goes = scatter<SHARC>(gs, p, h, bs, emission, rayDir, newO, newD, lobe, previousRoughness);
+            goes = scatter<SHARC, TRANSMISSION>(gs, p, h, bs, emission, rayDir, newO, newD, lobe, previousRoughness);
         }
     }
     if (goes) toTraced = true;
@@ -460,7 +460,7 @@ PT_DEV void shade_traced(const SceneView& sv, const GEOMETRY& geometry, const Pt
 
 // A fresh path: bounce 0 on the primary surface rebuilt from the G-buffer, Raytracing.hlsl:118-148,193-198
 // (r0, r1, r2: the pixel's primary-surface record)
-template <bool DI = false, bool SHARC = false>
+template <bool DI = false, bool SHARC = false, bool TRANSMISSION = true>
 PT_DEV void shade_fresh_record(const FrameView& fv, const PtCamera& cam, const PtGraphicsSettings& gs, const PtTextures& tx, float2* aux, uint4 r0, uint4 r1, uint4 r2,
                                PathRegs& p, bool& toTraced, bool& toFresh, v3& newO, v3& newD, float* previousRoughness = nullptr)
 {
@@ -492,20 +492,20 @@ PT_DEV void shade_fresh_record(const FrameView& fv, const PtCamera& cam, const P
         *previousRoughness = 0.0f;
         if constexpr (DI) { v3 dd, ds; load_direct(tx, p.pixel, dd, ds); p.srad = p.srad + (dd + ds); }   // the DI term once per sample, unscaled (:318)
     }
-    if (scatter<SHARC>(gs, p, h, bs, emission, rayDir, newO, newD, lobe, previousRoughness)) {
+    if (scatter<SHARC, TRANSMISSION>(gs, p, h, bs, emission, rayDir, newO, newD, lobe, previousRoughness)) {
         toTraced = true;
         if (aux && first) aux[p.pixel].y = lobe == LOBE_DIFFUSE ? 1.0f : 0.0f;       // isDiffuse of the lobe sampled at bounce 0, :237
     } else toFresh = end_sample<DI, SHARC>(gs, tx, aux, p);
 }
 
-template <bool DI = false, bool SHARC = false>
+template <bool DI = false, bool SHARC = false, bool TRANSMISSION = true>
 PT_DEV void shade_fresh(const FrameView& fv, const PtCamera& cam, const PtGraphicsSettings& gs, const PtTextures& tx, float2* aux, const uint4* __restrict__ primary,
                         PathRegs& p, bool& toTraced, bool& toFresh, v3& newO, v3& newD, RoundProf* prof = nullptr, float* previousRoughness = nullptr)
 {
     const uint32_t pixel = p.pixel;
     const uint4 r0 = primary[3 * (size_t)pixel], r1 = primary[3 * (size_t)pixel + 1], r2 = primary[3 * (size_t)pixel + 2];
     PT_PROF_WAIT(); PT_PROF_MARK(prof, 13);
-    shade_fresh_record<DI, SHARC>(fv, cam, gs, tx, aux, r0, r1, r2, p, toTraced, toFresh, newO, newD, previousRoughness);
+    shade_fresh_record<DI, SHARC, TRANSMISSION>(fv, cam, gs, tx, aux, r0, r1, r2, p, toTraced, toFresh, newO, newD, previousRoughness);
 }
 
 // compaction + stores of one tile: survivors to the traced region (state + ray), restarts to the fresh region (state).

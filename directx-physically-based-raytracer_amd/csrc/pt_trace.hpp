@@ -280,11 +280,14 @@ __device__ __attribute__((noinline)) bool candidate_is_opaque(const AlphaContext
 
 // commit() for a candidate of a geometry without D3D12_RAYTRACING_GEOMETRY_FLAG_OPAQUE: the alpha test runs only
 // for candidates that would otherwise be committed (DXR reports candidates inside the current ray interval).
+// ALPHA = false (template parameter of the product traversals): no geometry of the scene is without the OPAQUE flag (SceneRefs::hasNonOpaque),
+// so the callback is never reached and is compiled out -- and with it the call's register traffic.
+template <bool ALPHA = true>
 PT_DEV void commit_candidate(const AlphaContext& ac, uint32_t flags, Hit& h, float tmin, float t, float u, float v,
                              uint32_t inst, uint32_t geom, uint32_t prim, uint32_t slot)
 {
     if (!is_better(h, tmin, t, inst, geom, prim)) return;
-    if (!(flags & PT_GEOMETRY_FLAG_OPAQUE) && !candidate_is_opaque(ac, inst, geom, prim, u, v)) return;
+    if constexpr (ALPHA) if (!(flags & PT_GEOMETRY_FLAG_OPAQUE) && !candidate_is_opaque(ac, inst, geom, prim, u, v)) return;
     h.t = t; h.u = u; h.v = v; h.inst = inst; h.geom = geom; h.prim = prim; h.slot = slot;
 }
 

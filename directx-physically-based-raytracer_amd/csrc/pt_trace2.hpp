@@ -91,7 +91,7 @@ PT_DEV void visit_node(const BlobReader<LDS>& blob, uint32_t nodeBase16, const B
 // hit inside the instance goes back as (t, u, v, slot); slot == ~0u: nothing closer than the ray's best t.
 // The item-local best starts at the ray's best t with an id that loses every tie, so a candidate at exactly that t is kept
 // and the ray's own lane applies the instance order when it merges.
-template <bool STATS, bool LDS, bool CULL, typename STACK>
+template <bool STATS, bool LDS, bool CULL, bool ALPHA = true, typename STACK>
 PT_DEV f4v trace_item(const BlobReader<LDS>& blob, const BlobView& bv, const AlphaContext& ac, const f4v* rays, uint32_t src, uint32_t x,
                       STACK& stack, TraceStats* stats)
 {
@@ -133,7 +133,7 @@ PT_DEV f4v trace_item(const BlobReader<LDS>& blob, const BlobView& bv, const Alp
                 if (STATS) stats->tris++;
                 float t, u, v;
                 if (tri_test(rs, ro, V3(pa.x, pa.y, pa.z), V3(pb.x, pb.y, pb.z), V3(pc.x, pc.y, pc.z), t, u, v))
-                    commit_candidate(ac, __float_as_uint(pc.w), hi, itmin, t, u, v, x, __float_as_uint(pa.w), __float_as_uint(pb.w), i);
+                    commit_candidate<ALPHA>(ac, __float_as_uint(pc.w), hi, itmin, t, u, v, x, __float_as_uint(pa.w), __float_as_uint(pb.w), i);
             }
             if (G.y <= 0x00FFFFFFu) {
                 if (stack.sp == floor) break;
@@ -161,7 +161,7 @@ PT_DEV void merge_item(Hit& h, float tmin, f4v q, uint32_t x)
 constexpr uint32_t kPhasedItems = 128;                                       // items per batch and wave
 constexpr uint32_t kPhasedWaveLds = 64u * 32u + kPhasedItems * 16u + kPhasedItems * 4u;
 
-template <bool STATS, bool LDS, int STACK_DEPTH>
+template <bool STATS, bool LDS, int STACK_DEPTH, bool ALPHA = true>
 PT_DEV Hit trace_closest_v2(const BlobReader<LDS>& blob, const BlobView& bv, const AlphaContext& ac, v3 o, v3 d, float tmin, float tmax,
                             PT_LDS_AS void* ldsStack, uint32_t* ldsCand, unsigned char* ldsWave, TraceStats* stats)
 {
@@ -212,7 +212,7 @@ PT_DEV Hit trace_closest_v2(const BlobReader<LDS>& blob, const BlobView& bv, con
             __builtin_amdgcn_wave_barrier();
             for (uint32_t j = lane; j < total; j += 64u) {
                 const uint32_t it = items[j];
-                results[j] = trace_item<STATS, LDS, true>(blob, bv, ac, rays, it & 0xFFu, it >> 8, stack, stats);   // on top of this lane's TLAS stack
+                results[j] = trace_item<STATS, LDS, true, ALPHA>(blob, bv, ac, rays, it & 0xFFu, it >> 8, stack, stats);   // on top of this lane's TLAS stack
             }
             __builtin_amdgcn_wave_barrier();
             uint32_t off = 0;
@@ -252,7 +252,7 @@ constexpr uint32_t kFlatItems = 192;                                         // 
 constexpr uint32_t kFlatWaveLds = 64u * 32u + kFlatItems * 16u + kFlatItems * 4u;
 constexpr uint32_t kFlatLdsFixed = (uint32_t)kStackLdsFlat * 256u * 8u + 4u * kFlatWaveLds;
 
-template <bool STATS, bool LDS>
+template <bool STATS, bool LDS, bool ALPHA = true>
 PT_DEV Hit trace_closest_flat(const BlobReader<LDS>& blob, const BlobView& bv, const AlphaContext& ac, v3 o, v3 d, float tmin, float tmax,
                               PT_LDS_AS void* ldsStack, unsigned char* ldsWave, TraceStats* stats, RoundProf* prof = nullptr)
 {
@@ -330,8 +330,8 @@ PT_DEV Hit trace_closest_flat(const BlobReader<LDS>& blob, const BlobView& bv, c
         for (uint32_t j = lane; j < total; j += 64u) {
             const uint32_t it = items[j];
             stack.sp = 0;
-            results[j] = firstBatch ? trace_item<STATS, LDS, false>(blob, bv, ac, rays, it & 0xFFu, it >> 8, stack, stats)      // first batch: the scan's verdict stands
-                                    : trace_item<STATS, LDS, true>(blob, bv, ac, rays, it & 0xFFu, it >> 8, stack, stats);
+            results[j] = firstBatch ? trace_item<STATS, LDS, false, ALPHA>(blob, bv, ac, rays, it & 0xFFu, it >> 8, stack, stats)      // first batch: the scan's verdict stands
+                                    : trace_item<STATS, LDS, true, ALPHA>(blob, bv, ac, rays, it & 0xFFu, it >> 8, stack, stats);
         }
         __builtin_amdgcn_wave_barrier();
         PT_PROF_MARK(prof, 3);

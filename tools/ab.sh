@@ -14,7 +14,7 @@ while [ $# -gt 1 ]; do
     /opt/rocm/bin/hipcc $FLAGS $defs -c $CSRC/pt_stream.hip -o $OUT/pt_stream_$name.o &&
     /opt/rocm/bin/hipcc $FLAGS $defs -c $CSRC/pt_bvh.hip -o $OUT/pt_bvh_$name.o &&
     /opt/rocm/bin/hipcc $FLAGS $defs -c $CSRC/pt_api.hip -o $OUT/pt_api_$name.o &&
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $OUT/libptamd_$name.so $OUT/pt_api_$name.o $OUT/pt_bvh_$name.o $OUT/pt_kernels_$name.o $OUT/pt_stream_$name.o $CSRC/pt_skin.o $CSRC/pt_comm.o -ldl &&
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $OUT/libptamd_$name.so $OUT/pt_api_$name.o $OUT/pt_bvh_$name.o $OUT/pt_kernels_$name.o $OUT/pt_stream_$name.o $CSRC/pt_skin.o $CSRC/pt_comm.o $CSRC/pt_di.o $CSRC/pt_post.o $CSRC/pt_sharc.o -ldl &&
     echo built $name ) &
   if (( $(jobs -r | wc -l) >= 4 )); then wait -n; fi
 done
