@@ -837,7 +837,7 @@ int pt_bsdf_sample(PtContext* ctx, const PtBsdfSampleQuery* device_queries, uint
     Context& c = ctx->c;
     API_ARG(&c, count == 0 || (device_queries && device_results), "query / result buffer is NULL");
     API_HIP(&c, hipSetDevice(c.device));
-    API_HIP(&c, launch_bsdf_sample(c.stream, (const float*)device_queries, count, (float*)device_results));
+    API_HIP(&c, launch_bsdf_sample(c.stream, (const float*)device_queries, count, (float*)device_results, !(c.debugFlags & PT_DEBUG_GENERIC_SCENE)));
     return PT_OK;
 }
 

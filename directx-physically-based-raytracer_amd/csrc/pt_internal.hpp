@@ -293,6 +293,14 @@ constexpr bool kSpecSplit = true;
 constexpr bool kSpecSplit = false;
 #endif
 
+// Developer builds (tools/ab.sh): -DPT_PLAIN_NO_MERGED gives the untextured plain form of k_round (no alpha test, no third lobe) the two-branch
+// BSDFSample::Sample back, so that the merged form can be timed against it. The product does not define it.
+#ifdef PT_PLAIN_NO_MERGED
+constexpr bool kPlainMerged = false;
+#else
+constexpr bool kPlainMerged = true;
+#endif
+
 // pt_bvh.hip
 hipError_t build_blas_device(const PtGeometryDesc* geoms, uint32_t ngeoms, bool allowUpdate, hipStream_t stream, Blas& out);
 hipError_t refit_blas_device(const PtGeometryDesc* geoms, uint32_t ngeoms, hipStream_t stream, Blas& b);
@@ -332,7 +340,7 @@ hipError_t launch_gbuffer(Context& c, const SceneView& sv, const FrameView& fv, 
 hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv, const PtTextures& tx, bool sharcQuery);
 hipError_t launch_visibility(Context& c, const SceneView& sv, const void* rays, uint32_t count, void* out);
 hipError_t launch_bsdf_evaluate(hipStream_t stream, const float* q, uint32_t count, float* r);
-hipError_t launch_bsdf_sample(hipStream_t stream, const float* q, uint32_t count, float* r);
+hipError_t launch_bsdf_sample(hipStream_t stream, const float* q, uint32_t count, float* r, bool merged);   // merged: Sample as the plain k_round runs it
 hipError_t launch_debug_trace(Context& c, const SceneView& sv, const float* ray8, uint32_t* devLog, uint32_t logCap);
 hipError_t launch_debug_closest(Context& c, const SceneView& sv, const void* rays, uint32_t count, void* hits);
 uint32_t round_objects_in_lds(const Context& c, uint32_t objectCount, bool haveShadeGeom);   // the fused round kernel's LDS tables (PtAccelStats)

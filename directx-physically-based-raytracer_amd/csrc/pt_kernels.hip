@@ -370,9 +370,12 @@ struct RoundArgs {
 // ALPHA / TRANSMISSION = false: the scene has no non-opaque geometry / no transmissive material (FramePlan::alpha, ::transmission): the alpha-test
 // call and the third lobe are compiled out. The product instantiates the pair as ONE switch (neither / generic, enqueue_chain). This is the only
 // kernel that takes the switches: in k_gbuffer, k_pt_first, k_shade and k_extend_stream they measured as nothing or as a loss.
+// Both false is the plain form; untextured -- what C2 runs -- it also takes the merged BSDFSample::Sample (pt_math.hpp). The textured plain forms
+// keep the two-branch Sample: merged, two of them (LDS, FLAT, SHARC) would spill three VGPRs where they spill none.
 template <bool TEXTURED, bool LDS, bool FLAT, bool DI, bool SHARC = false, bool ALPHA = true, bool TRANSMISSION = true>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_round(const RoundArgs* __restrict__ A, uint32_t sqBase, uint32_t sqCount)
 {
+    constexpr bool MERGED = !TEXTURED && !ALPHA && !TRANSMISSION && kPlainMerged;
     const SceneView& sv = A->sv; const FrameView& fv = A->fv; const PtTextures& tx = A->tx; const BlobView& bv = A->bv;
     const PathQueue& qin = A->qin; const PathQueue& qout = A->qout;
     const FrameConstants* __restrict__ fc = A->fc; float2* aux = A->aux; const uint32_t segCap = A->segCap;
@@ -448,7 +451,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             bool toTraced = false, toFresh = false;
             v3 newO = V3(0, 0, 0), newD = V3(0, 0, 1);
             if (valid) {
-                shade_traced<TEXTURED, DI, SHARC, TRANSMISSION>(sv, GeometryFromBlob<LDS>{ blob, bv, tables }, sd, gs, tx, aux, p, make_uint4(h.inst, h.slot, __float_as_uint(h.u), __float_as_uint(h.v)), h.t,
+                shade_traced<TEXTURED, DI, SHARC, TRANSMISSION, MERGED>(sv, GeometryFromBlob<LDS>{ blob, bv, tables }, sd, gs, tx, aux, p, make_uint4(h.inst, h.slot, __float_as_uint(h.u), __float_as_uint(h.v)), h.t,
                                        V3(d.x, d.y, d.z), toTraced, toFresh, newO, newD, prof, A->sharc, &pr);
             }
             PT_PROF_MARK(prof, 6);
@@ -681,6 +684,9 @@ __global__ __launch_bounds__(256) void k_bsdf_evaluate(const float* __restrict__
 }
 
 // one bounce's BSDF step as scatter() takes it: Initialize, ComputeLobeWeights, Sample, single-lobe EvaluateLobe (PtBsdfSampleQuery / Result)
+// MERGED: a query without a third-lobe weight goes through the merged Sample of the plain k_round (the weights are those of the generic
+// form: tw = +-0, rw = 1); every other query, and everything around Sample, is the same code in both instantiations
+template <bool MERGED>
 __global__ __launch_bounds__(256) void k_bsdf_sample(const float* __restrict__ q, uint32_t count, float* __restrict__ r)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -695,7 +701,9 @@ __global__ __launch_bounds__(256) void k_bsdf_sample(const float* __restrict__ q
     const uint32_t ext = __float_as_uint(a[21]);
     float w[3]; b.ComputeLobeWeights(sv, V, ext, w);
     v3 L = V3(0.0f, 0.0f, 0.0f); int lobe = 0;
-    const bool ok = b.Sample(sv, V, w, rnd, L, lobe);
+    bool ok;
+    if (MERGED && w[2] == 0.0f) ok = b.Sample<false, true>(sv, V, w, rnd, L, lobe);
+    else ok = b.Sample(sv, V, w, rnd, L, lobe);
     float pdf = 0.0f; v3 f = V3(0.0f, 0.0f, 0.0f);
     if (ok) b.EvaluateLobe(sv, L, V, w, lobe, ext, pdf, f);
     float* o = r + 12 * (size_t)i;
@@ -727,10 +735,11 @@ hipError_t launch_bsdf_evaluate(hipStream_t stream, const float* q, uint32_t cou
     return hipGetLastError();
 }
 
-hipError_t launch_bsdf_sample(hipStream_t stream, const float* q, uint32_t count, float* r)
+hipError_t launch_bsdf_sample(hipStream_t stream, const float* q, uint32_t count, float* r, bool merged)
 {
     if (!count) return hipSuccess;
-    k_bsdf_sample<<<(count + 255) / 256, 256, 0, stream>>>(q, count, r);
+    if (merged) k_bsdf_sample<true><<<(count + 255) / 256, 256, 0, stream>>>(q, count, r);
+    else k_bsdf_sample<false><<<(count + 255) / 256, 256, 0, stream>>>(q, count, r);
     return hipGetLastError();
 }
 

@@ -189,6 +189,13 @@ PT_DEV v3 ml_cosine_get_ray(float u0, float u1)
     float sinT = ml_sqrt01(mad(-cosT, cosT, 1.0f));
     return V3(sinT * c, sinT * s, cosT);
 }
+// ... with sin / cos (2 pi u0) handed in: the statements of ml_cosine_get_ray behind its sincos_2pi (the merged BSDFSample::Sample)
+PT_DEV v3 ml_cosine_get_ray_sc(float s, float c, float u1)
+{
+    float cosT = ml_sqrt01(u1);
+    float sinT = ml_sqrt01(mad(-cosT, cosT, 1.0f));
+    return V3(sinT * c, sinT * s, cosT);
+}
 PT_DEV float ml_cosine_pdf(float NoL) { return PT_DIV_CONST(NoL, kPi); }
 
 PT_DEV float ml_distribution_ggx(float roughness, float NoH)
@@ -255,6 +262,16 @@ PT_DEV v3 ml_vndf_get_ray(float u0, float u1, float roughness, v3 Vl)     // Dup
     float m = roughness * roughness;
     v3 Vh = normalize(V3(m * Vl.x, m * Vl.y, Vl.z));
     float s, c; sincos_2pi(u0, s, c);
+    float z = mad(1.0f - u1, 1.0f + Vh.z, -Vh.z);
+    float sinT = ml_sqrt01(mad(-z, z, 1.0f));
+    v3 h = V3(mad(sinT, c, Vh.x), mad(sinT, s, Vh.y), z + Vh.z);
+    return normalize(V3(m * h.x, m * h.y, fmaxf(h.z, 0.0f)));
+}
+// ... with sin / cos (2 pi u0) handed in: the statements of ml_vndf_get_ray around its sincos_2pi, which depends on none of them
+PT_DEV v3 ml_vndf_get_ray_sc(float s, float c, float u1, float roughness, v3 Vl)
+{
+    float m = roughness * roughness;
+    v3 Vh = normalize(V3(m * Vl.x, m * Vl.y, Vl.z));
     float z = mad(1.0f - u1, 1.0f + Vh.z, -Vh.z);
     float sinT = ml_sqrt01(mad(-z, z, 1.0f));
     v3 h = V3(mad(sinT, c, Vh.x), mad(sinT, s, Vh.y), z + Vh.z);
@@ -357,9 +374,25 @@ struct BSDFSample {                           // BxDF.hlsli:36-44
     }
 
     // FindLobe :198-212 + Sample :214-226 (+ :81-86, :110-118, :148-168)
-    template <bool TRANSMISSION = true>
+    // MERGED (two lobes only; the plain form of k_round): what both lobes' branches contain is executed once by a wave that holds lanes of both
+    // -- sincos_2pi(rnd[1]) before the branch, the lobe's local vector chosen per lane, ONE rotate_vector_inv, ONE test against the geometric
+    // normal. Every lane executes the operations it executes in the plain form, on the same operands and in the same order (sincos_2pi depends
+    // on rnd[1] alone, so where it stands changes no value): the same bits (DESIGN.md "Arithmetic spec").
+    template <bool TRANSMISSION = true, bool MERGED = false>
     PT_DEV bool Sample(const SurfaceVectors& sv, v3 V, const float w[3], const float rnd[4], v3& L, int& lobe) const
     {
+        static_assert(!(MERGED && TRANSMISSION), "the merged form has two lobes");
+        if constexpr (MERGED) {
+            lobe = rnd[0] < w[1] ? 1 : 0;
+            float s, c; sincos_2pi(rnd[1], s, c);
+            v3 local;
+            if (lobe == LOBE_DIFFUSE) local = ml_cosine_get_ray_sc(s, c, rnd[2]);
+            else local = ml_vndf_get_ray_sc(s, c, rnd[2], Roughness, rotate_vector(sv.ShadingBasis, V));
+            const v3 R = rotate_vector_inv(sv.ShadingBasis, local);      // diffuse: L itself; specular: the half vector
+            L = R;
+            if (lobe != LOBE_DIFFUSE) L = reflect(-V, R);
+            return dot(sv.FrontGeometricNormal, L) > 0.0f;
+        }
         lobe = 0;
         if constexpr (TRANSMISSION) {
             float weight = w[2];

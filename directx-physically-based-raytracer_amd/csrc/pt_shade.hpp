@@ -335,7 +335,7 @@ PT_DEV bool scatter_step(const PtGraphicsSettings& gs, uint32_t bounce, uint32_t
 
 // SHARC (the query pass of the radiance cache, pt_raytrace_render_sharc): previousRoughness, the blur the path has gathered so far, grows by
 // the sampled lobe's width after every scatter (:366).
-template <bool SHARC = false, bool TRANSMISSION = true>
+template <bool SHARC = false, bool TRANSMISSION = true, bool MERGED = false>
 PT_DEV bool scatter(const PtGraphicsSettings& gs, PathRegs& p, const SurfaceHit& h, const BSDFSample& bs, v3 emission, v3 rayDir, v3& newO, v3& newD, int& lobe,
                     float* previousRoughness = nullptr)
 {
@@ -346,7 +346,7 @@ PT_DEV bool scatter(const PtGraphicsSettings& gs, PathRegs& p, const SurfaceHit&
     float rnd[4];
     rnd[0] = rng_float(p.rng); rnd[1] = rng_float(p.rng); rnd[2] = rng_float(p.rng); rnd[3] = rng_float(p.rng);   // GetFloat4, :330
     v3 L;
-    if (!bs.Sample<TRANSMISSION>(svec, V, w, rnd, L, lobe)) return false;
+    if (!bs.Sample<TRANSMISSION, MERGED>(svec, V, w, rnd, L, lobe)) return false;
     float pdf; v3 f;
     bs.EvaluateLobe<TRANSMISSION>(svec, L, V, w, lobe, gs.ExtFlags, pdf, f);
     if (pdf == 0.0f || (f.x == 0.0f && f.y == 0.0f && f.z == 0.0f)) return false;             // :336,342
@@ -426,7 +426,8 @@ template <bool LDS> struct GeometryFromBlob {                // ... out of the s
 };
 
 // SHARC: `sharc` is the resolved cache, previousRoughness the path's entry of the side array; hitT is the hit's distance along the ray.
-template <bool TEXTURED, bool DI = false, bool SHARC = false, bool TRANSMISSION = true, typename GEOMETRY>
+// MERGED: the merged form of BSDFSample::Sample (pt_math.hpp; two lobes only): the untextured plain form of k_round, unless -DPT_PLAIN_NO_MERGED.
+template <bool TEXTURED, bool DI = false, bool SHARC = false, bool TRANSMISSION = true, bool MERGED = false, typename GEOMETRY>
 PT_DEV void shade_traced(const SceneView& sv, const GEOMETRY& geometry, const PtSceneData& sd, const PtGraphicsSettings& gs, const PtTextures& tx, float2* aux,
                          PathRegs& p, uint4 hr, float hitT, v3 rayDir, bool& toTraced, bool& toFresh, v3& newO, v3& newD, RoundProf* prof = nullptr,
                          const SharcView* sharc = nullptr, float* previousRoughness = nullptr)
@@ -451,7 +452,7 @@ PT_DEV void shade_traced(const SceneView& sv, const GEOMETRY& geometry, const Pt
             bs.Initialize(V3(m.BaseColor), m.Metallic, m.Roughness, m.IOR, m.Transmission, h.IsFrontFace);
             v3 emission = material_emission(m);
             if constexpr (DI) if (p.bounce == 1u && direct_valid(tx, p.pixel)) emission = V3(0, 0, 0);   // the DI pass lit this path's first hit, :302
-            goes = scatter<SHARC, TRANSMISSION>(gs, p, h, bs, emission, rayDir, newO, newD, lobe, previousRoughness);
+            goes = scatter<SHARC, TRANSMISSION, MERGED>(gs, p, h, bs, emission, rayDir, newO, newD, lobe, previousRoughness);
         }
     }
     if (goes) toTraced = true;

@@ -682,7 +682,8 @@ int  pt_get_counters(PtContext* ctx, PtCounters* out);
 #define PT_DEBUG_SHARC_LOG_PATHS 0x100u   /* pt_raytrace_render_sharc keeps the update pass's vertex log (pt_sharc_download_update_paths) */
 #define PT_DEBUG_SHARC_SKIP_UPDATE 0x200u /* pt_raytrace_render_sharc skips the update and resolve passes: the query sees the cache as it is */
 #define PT_DEBUG_GENERIC_SCENE  0x400u   /* the kernels keep the alpha test and the transmission lobe even when the scene has no non-opaque geometry / no transmissive
-                                            material (the library compiles both out of such a scene's frames; the image is the same either way: A/B runs, tests) */
+                                            material (the library compiles both out of such a scene's frames; the image is the same either way: A/B runs, tests).
+                                            pt_bsdf_sample runs the two-branch BSDFSample::Sample under it instead of the merged one of such frames: the same results */
 int  pt_set_debug_flags(PtContext* ctx, uint32_t flags);
 /* first mismatching ray under PT_DEBUG_BRUTE_FORCE: o.xyz tmin d.xyz tmax | bvh inst slot t - | brute inst slot t - */
 int  pt_debug_read_mismatch(PtContext* ctx, float* out16);
