@@ -162,8 +162,13 @@ int pt_heap_set_texture(PtContext* ctx, uint32_t descriptor, const void* device_
     Context& c = ctx->c;
     API_ARG(&c, descriptor < c.heapHost.size(), "descriptor index beyond pt_heap_resize");
     API_ARG(&c, device_ptr && width && height, "texture pointer / size is null");
-    API_ARG(&c, format <= PT_FORMAT_R32G32B32A32_FLOAT, "unsupported texture format");
+    API_ARG(&c, format <= PT_FORMAT_BC5_UNORM, "unsupported texture format");
     API_ARG(&c, !is_cube || width == height, "cube faces must be square");
+    if (format >= PT_FORMAT_BC1_UNORM) {                  // 4x4 blocks, ceil(w / 4) * ceil(h / 4) of them, each read with one aligned vector load
+        const bool wide = format == PT_FORMAT_BC3_UNORM || format == PT_FORMAT_BC3_UNORM_SRGB || format == PT_FORMAT_BC5_UNORM;
+        API_ARG(&c, !is_cube, "block-compressed cube maps are not supported");
+        API_ARG(&c, ((uintptr_t)device_ptr & (wide ? 15u : 7u)) == 0, "block-compressed texture memory must be aligned to its block size (8 bytes for BC1 / BC4, 16 for BC3 / BC5)");
+    }
     c.heapHost[descriptor] = HeapEntry{ device_ptr, (uint64_t)width | ((uint64_t)height << 32), format, is_cube ? kKindTextureCube : kKindTexture2D };
     c.heapDirty = true;
     return PT_OK;

@@ -8,13 +8,15 @@
 // texel through a 256-entry table built on the host in double precision (DESIGN.md "Arithmetic spec").
 #pragma once
 #include "pt_math.hpp"
+#include "pt_bc.hpp"
 #include "../../include/ptamd.h"
 
 namespace pt {
 
 struct HeapEntry { const void* ptr; uint64_t bytes; uint32_t stride; uint32_t kind; };   // textures: bytes = w | h << 32, stride = format
 enum : uint32_t { kKindBuffer = 0, kKindTexture2D = 1, kKindTextureCube = 2 };
-enum : uint32_t { kFmtRGBA8 = 0, kFmtRGBA8Srgb = 1, kFmtRGBA32F = 2 };
+enum : uint32_t { kFmtRGBA8 = 0, kFmtRGBA8Srgb = 1, kFmtRGBA32F = 2,                      // PtFormat
+                  kFmtBC1 = 3, kFmtBC1Srgb = 4, kFmtBC3 = 5, kFmtBC3Srgb = 6, kFmtBC4 = 7, kFmtBC5 = 8 };   // block-compressed: bytes = texels w | h << 32, the memory holds 4x4 blocks
 
 struct f4 { float x, y, z, w; };
 
@@ -23,23 +25,46 @@ struct f4 { float x, y, z, w; };
 // the contract of pt_heap_set_*: say so.
 #define PT_GLOBAL_AS __attribute__((address_space(1)))
 template <typename T> PT_DEV const PT_GLOBAL_AS T* gptr(const void* p) { return (const PT_GLOBAL_AS T*)p; }
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));     // one 8-byte / 16-byte load of a BC block
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// An RGBA8 code (r | g << 8 | b << 16 | a << 24) as floats: rgb through the sRGB table or linear, alpha linear
+PT_DEV f4 rgba8_to_f4(uint32_t pw, bool srgb, const float* srgbLut)
+{
+    const uchar4 p = make_uchar4((uint8_t)(pw & 0xFFu), (uint8_t)((pw >> 8) & 0xFFu), (uint8_t)((pw >> 16) & 0xFFu), (uint8_t)(pw >> 24));
+    f4 o;
+    if (srgb) { o.x = srgbLut[p.x]; o.y = srgbLut[p.y]; o.z = srgbLut[p.z]; }
+    else { o.x = unorm8_to_f32(p.x); o.y = unorm8_to_f32(p.y); o.z = unorm8_to_f32(p.z); }
+    o.w = unorm8_to_f32(p.w);
+    return o;
+}
+
+// A texel of a block-compressed texture: one aligned vector load of the block it lies in -- 8 bytes (BC1, BC4) or 16 (BC3: alpha block,
+// then the colour half; BC5: red, then green) -- then the block arithmetic of pt_bc.hpp. A BC1 / BC3 texel is an RGBA8 code and goes on
+// through the RGBA8 step; BC4 / BC5 give (r, 0, 0, 1) / (r, g, 0, 1) with the interpolants at fp32 precision.
+PT_DEV f4 texel_fetch_bc(const void* ptr, uint32_t W, uint32_t H, uint32_t fmt, const float* srgbLut, uint32_t face, uint32_t x, uint32_t y)
+{
+    const uint64_t block = bc::block_index(W, H, face, x, y);
+    const uint32_t i = bc::texel_in_block(x, y);
+    if (fmt == kFmtBC4) { const u32x2 b = gptr<u32x2>(ptr)[block]; return f4{ bc::bc4_value(b.x, b.y, i), 0.0f, 0.0f, 1.0f }; }
+    if (fmt == kFmtBC5) { const u32x4 b = gptr<u32x4>(ptr)[block]; return f4{ bc::bc4_value(b.x, b.y, i), bc::bc4_value(b.z, b.w, i), 0.0f, 1.0f }; }
+    if (fmt <= kFmtBC1Srgb) { const u32x2 b = gptr<u32x2>(ptr)[block]; return rgba8_to_f4(bc::color_code(b.x, b.y, i, true), fmt == kFmtBC1Srgb, srgbLut); }
+    const u32x4 b = gptr<u32x4>(ptr)[block];
+    return rgba8_to_f4((bc::color_code(b.z, b.w, i, false) & 0x00FFFFFFu) | (bc::alpha_code(b.x, b.y, i) << 24), fmt == kFmtBC3Srgb, srgbLut);
+}
 
 PT_DEV f4 texel_fetch(const HeapEntry& t, const float* srgbLut, uint32_t face, uint32_t x, uint32_t y)
 {
     const uint32_t W = (uint32_t)(t.bytes & 0xFFFFFFFFu), H = (uint32_t)(t.bytes >> 32);
+    if (__builtin_expect(t.stride >= kFmtBC1, 0)) return texel_fetch_bc(t.ptr, W, H, t.stride, srgbLut, face, x, y);
     const size_t idx = ((size_t)face * H + y) * W + x;
-    f4 o;
     if (t.stride == kFmtRGBA32F) {
         const PT_GLOBAL_AS float* v = gptr<float>(t.ptr) + 4 * idx;
+        f4 o;
         o.x = v[0]; o.y = v[1]; o.z = v[2]; o.w = v[3];
         return o;
     }
-    const uint32_t pw = gptr<uint32_t>(t.ptr)[idx];
-    const uchar4 p = make_uchar4((uint8_t)(pw & 0xFFu), (uint8_t)((pw >> 8) & 0xFFu), (uint8_t)((pw >> 16) & 0xFFu), (uint8_t)(pw >> 24));
-    if (t.stride == kFmtRGBA8Srgb) { o.x = srgbLut[p.x]; o.y = srgbLut[p.y]; o.z = srgbLut[p.z]; }
-    else { o.x = unorm8_to_f32(p.x); o.y = unorm8_to_f32(p.y); o.z = unorm8_to_f32(p.z); }
-    o.w = unorm8_to_f32(p.w);
-    return o;
+    return rgba8_to_f4(gptr<uint32_t>(t.ptr)[idx], t.stride == kFmtRGBA8Srgb, srgbLut);
 }
 
 PT_DEV f4 bilinear(const HeapEntry& t, const float* srgbLut, uint32_t face, float fx, float fy, bool wrap)
@@ -54,8 +79,16 @@ PT_DEV f4 bilinear(const HeapEntry& t, const float* srgbLut, uint32_t face, floa
         x0 = x0 < 0 ? 0 : (x0 >= W ? W - 1 : x0); x1 = x1 < 0 ? 0 : (x1 >= W ? W - 1 : x1);
         y0 = y0 < 0 ? 0 : (y0 >= H ? H - 1 : y0); y1 = y1 < 0 ? 0 : (y1 >= H ? H - 1 : y1);
     }
-    const f4 c00 = texel_fetch(t, srgbLut, face, (uint32_t)x0, (uint32_t)y0), c10 = texel_fetch(t, srgbLut, face, (uint32_t)x1, (uint32_t)y0);
-    const f4 c01 = texel_fetch(t, srgbLut, face, (uint32_t)x0, (uint32_t)y1), c11 = texel_fetch(t, srgbLut, face, (uint32_t)x1, (uint32_t)y1);
+    // The four taps of a block-compressed texture stand in one branch of their own (texel_fetch would take each of them there by itself):
+    // with the decode inside every tap, the kernels that sample textures paid for it in registers on the RGBA8 path too.
+    f4 c00, c10, c01, c11;
+    if (__builtin_expect(t.stride >= kFmtBC1, 0)) {
+        c00 = texel_fetch_bc(t.ptr, (uint32_t)W, (uint32_t)H, t.stride, srgbLut, face, (uint32_t)x0, (uint32_t)y0); c10 = texel_fetch_bc(t.ptr, (uint32_t)W, (uint32_t)H, t.stride, srgbLut, face, (uint32_t)x1, (uint32_t)y0);
+        c01 = texel_fetch_bc(t.ptr, (uint32_t)W, (uint32_t)H, t.stride, srgbLut, face, (uint32_t)x0, (uint32_t)y1); c11 = texel_fetch_bc(t.ptr, (uint32_t)W, (uint32_t)H, t.stride, srgbLut, face, (uint32_t)x1, (uint32_t)y1);
+    } else {
+        c00 = texel_fetch(t, srgbLut, face, (uint32_t)x0, (uint32_t)y0); c10 = texel_fetch(t, srgbLut, face, (uint32_t)x1, (uint32_t)y0);
+        c01 = texel_fetch(t, srgbLut, face, (uint32_t)x0, (uint32_t)y1); c11 = texel_fetch(t, srgbLut, face, (uint32_t)x1, (uint32_t)y1);
+    }
     f4 o;
     { float top = mad(c10.x, wx, c00.x * (1.0f - wx)), bot = mad(c11.x, wx, c01.x * (1.0f - wx)); o.x = mad(bot, wy, top * (1.0f - wy)); }
     { float top = mad(c10.y, wx, c00.y * (1.0f - wx)), bot = mad(c11.y, wx, c01.y * (1.0f - wx)); o.y = mad(bot, wy, top * (1.0f - wy)); }

@@ -201,7 +201,7 @@ static HostScene ingested_scene(const std::string& path)
             g.hasNormals = md.HasNormals; g.hasTangents = md.HasTangents; g.hasUV[0] = md.HasUV[0]; g.hasUV[1] = md.HasUV[1];
             g.material = md.HasMaterial ? md.Material : ingest::default_material();            // App.cpp:1044: Material() when a mesh names none
             for (int k = 0; k < 7; k++) { g.textures[k] = md.Textures[k]; g.texCoord[k] = md.TextureCoordinateIndex[k]; }
-            for (const std::string& slot : md.SkippedTextures) fprintf(stderr, "pt_demo: %s texture of a material not loaded (this host decodes 8-bit PNG only)\n", slot.c_str());
+            for (const std::string& slot : md.SkippedTextures) fprintf(stderr, "pt_demo: %s texture of a material not loaded (this host decodes 8-bit PNG and reads BC1 / BC3 / BC4 / BC5 or RGBA8 DDS only)\n", slot.c_str());
             n.meshes.push_back(std::move(g));
         }
         sc.nodes.push_back(std::move(n));
@@ -269,8 +269,11 @@ static int dump_scene(const HostScene& sc, const std::string& path)
             fwrite(g.vertices.data(), 1, g.vertices.size(), fp); fwrite(g.indices.data(), 1, g.indices.size(), fp); fwrite(&g.material, sizeof(PtMaterial), 1, fp);
             bool firstTex = true;
             for (int k = 0; k < 7; k++) if (g.textures[k]) {              // slot, size, sRGB, coordinate set; the texels follow the material in the file
-                printf("%s[%d, %u, %u, %d, %u]", firstTex ? "" : ", ", k, g.textures[k]->Texels.Width, g.textures[k]->Texels.Height, g.textures[k]->SRGB ? 1 : 0, g.texCoord[k]);
-                fwrite(g.textures[k]->Texels.RGBA.data(), 1, g.textures[k]->Texels.RGBA.size(), fp); firstTex = false;
+                const ingest::Texture& t = *g.textures[k];                // a block-compressed texture: a sixth entry, its PtFormat, and the block bytes in the file
+                printf("%s[%d, %u, %u, %d, %u", firstTex ? "" : ", ", k, t.Texels.Width, t.Texels.Height, t.SRGB ? 1 : 0, g.texCoord[k]);
+                if (t.IsBlockCompressed()) { printf(", %u]", (unsigned)t.Format()); fwrite(t.Blocks.data(), 1, t.Blocks.size(), fp); }
+                else { printf("]"); fwrite(t.Texels.RGBA.data(), 1, t.Texels.RGBA.size(), fp); }
+                firstTex = false;
             }
             printf("]}");
         }
@@ -422,10 +425,9 @@ int main(int argc, char** argv)
             uint32_t next = firstTextureDescriptor;
             for (auto& kv : textureDescriptor) {                             // texel arrays as pt_heap_set_texture takes them (App.cpp:1052-1063 fills the descriptor indices)
                 kv.second = next++;
-                const ingest::Image& im = kv.first->Texels;
-                uint8_t* dt = upload(im.RGBA);
-                ThrowIfFailed(commandList.Context, pt_heap_set_texture(commandList.Context, kv.second, dt, im.Width, im.Height,
-                                                                       kv.first->SRGB ? PT_FORMAT_R8G8B8A8_UNORM_SRGB : PT_FORMAT_R8G8B8A8_UNORM, 0));
+                const ingest::Image& im = kv.first->Texels;                 // a DDS texture goes up as the blocks of its file, under its block format
+                uint8_t* dt = upload(kv.first->IsBlockCompressed() ? kv.first->Blocks : im.RGBA);
+                ThrowIfFailed(commandList.Context, pt_heap_set_texture(commandList.Context, kv.second, dt, im.Width, im.Height, kv.first->Format(), 0));
             }
         }
         struct GeometryOnDevice { uint32_t heapVertices, heapIndices; };

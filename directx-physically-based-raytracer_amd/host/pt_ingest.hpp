@@ -12,12 +12,15 @@
 // Same conventions, same arithmetic order as the test harness's ingest.py, so that both hosts hand the library the same bytes
 // (tests/test_host_cpp.py compares vertex / index buffers, transforms and materials of the committed fixture, and the rendered frame).
 // Textures: 8-bit PNG images (embedded or referenced) are decoded here (a small inflate + the PNG filters, checked against PIL); the reference
-// decodes files with DirectXTex / stb behind TextureHelpers.ixx, this image has neither, so JPEG / DDS / 16-bit references are listed in
+// decodes files with DirectXTex / stb behind TextureHelpers.ixx, this image has neither, so JPEG / 16-bit references are listed in
 // MeshData::SkippedTextures and the material keeps its factors (a host with a codec fills those slots through pt_heap_set_texture).
+// DDS images -- a texture's MSFT_texture_dds source wins over its PNG, as in the reference -- need no codec: the header is parsed here
+// and the BC1 / BC3 / BC4 / BC5 blocks go to the library as they are (read_dds below); a DDS outside those formats is listed and skipped too.
 // [DirectXMesh spec] ComputeTangentFrame is an un-vendored dependency: restated as Lengyel's per-vertex accumulation with Gram-Schmidt
 // against the normal (as in ingest.py). Header-only, C++20, no dependency beyond the standard library and include/ptamd.h.
 #pragma once
 #include <array>
+#include <cctype>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -140,7 +143,7 @@ inline std::string base64_decode(const std::string& in)
 }
 
 // ------------------------------------------------------------------------------------------------
-// PNG (the lossless half of what glTF embeds; JPEG / DDS need a codec this image does not have: such textures are listed and skipped)
+// PNG (the lossless half of what glTF embeds; JPEG needs a codec this image does not have: such textures are listed and skipped)
 // ------------------------------------------------------------------------------------------------
 // RFC 1951 inflate (stored, fixed and dynamic Huffman blocks) behind the RFC 1950 zlib header; canonical-code decoding by counts per length.
 class Inflate {
@@ -306,6 +309,73 @@ inline Image decode_png(const std::string& d)
 }
 
 // ------------------------------------------------------------------------------------------------
+// DDS (mip 0 of a 2D texture): header parsing only, the blocks are passed through as they are (the reference hands them to the GPU the
+// same way, TextureHelpers.ixx:65-78). The same acceptance as the harness's bc.read_dds: the DX10 header with DXGI 28, 29, 71, 72, 77, 78,
+// 80, 83, the FourCCs DXT1, DXT5, ATI1 / BC4U, ATI2 / BC5U, and 32-bit RGBA masks; everything else throws. Every size the file states is
+// checked against the buffer before a byte is read.
+// ------------------------------------------------------------------------------------------------
+inline bool is_dds(const std::string& d) { return d.size() >= 4 && !std::memcmp(d.data(), "DDS ", 4); }
+
+struct DdsImage { uint32_t Width = 0, Height = 0, Format = 0; std::vector<uint8_t> Data; };   // Format: PtFormat; Data: blocks, or RGBA8 texels
+
+inline DdsImage read_dds(const std::string& d)
+{
+    if (!is_dds(d)) throw std::runtime_error("DDS: no 'DDS ' magic");
+    if (d.size() < 128) throw std::runtime_error("DDS: the file is shorter than its header");
+    auto u32 = [&](size_t o) { uint32_t v; std::memcpy(&v, d.data() + o, 4); return v; };     // o + 4 <= 128 <= size (148 for the DX10 fields, checked below)
+    const uint32_t size = u32(4), flags = u32(8), height = u32(12), width = u32(16), depth = u32(24), pfSize = u32(76), pfFlags = u32(80), caps2 = u32(112);
+    uint32_t mips = u32(28);
+    if (size != 124 || pfSize != 32) throw std::runtime_error("DDS: bad header size");
+    if (!width || !height) throw std::runtime_error("DDS: zero width or height");
+    if (width > 65536u || height > 65536u) throw std::runtime_error("DDS: texture larger than 65536 texels a side");   // (D3D12's limit is 16384) sizes below stay far from 2^64
+    if ((caps2 & 0x200000u) || ((flags & 0x800000u) && depth > 1)) throw std::runtime_error("DDS: volume textures are not supported");
+    if (caps2 & 0x200u) throw std::runtime_error("DDS: cube maps are not supported");
+    DdsImage im; im.Width = width; im.Height = height;
+    size_t off = 128;
+    const bool fourcc = (pfFlags & 0x4u) != 0;
+    const std::string cc = d.substr(84, 4);
+    if (fourcc && cc == "DX10") {
+        if (d.size() < 148) throw std::runtime_error("DDS: the file is shorter than its DX10 header");
+        const uint32_t dxgi = u32(128), dimension = u32(132), misc = u32(136), arraySize = u32(140);
+        off = 148;
+        if (dimension == 4) throw std::runtime_error("DDS: volume textures are not supported");
+        if (dimension != 3) throw std::runtime_error("DDS: only 2D textures are supported");
+        if (misc & 0x4u) throw std::runtime_error("DDS: cube maps are not supported");
+        if (arraySize > 1) throw std::runtime_error("DDS: texture arrays are not supported");
+        switch (dxgi) {
+        case 28: im.Format = PT_FORMAT_R8G8B8A8_UNORM; break; case 29: im.Format = PT_FORMAT_R8G8B8A8_UNORM_SRGB; break;
+        case 71: im.Format = PT_FORMAT_BC1_UNORM; break; case 72: im.Format = PT_FORMAT_BC1_UNORM_SRGB; break;
+        case 77: im.Format = PT_FORMAT_BC3_UNORM; break; case 78: im.Format = PT_FORMAT_BC3_UNORM_SRGB; break;
+        case 80: im.Format = PT_FORMAT_BC4_UNORM; break; case 83: im.Format = PT_FORMAT_BC5_UNORM; break;
+        default: throw std::runtime_error("DDS: unsupported DXGI format " + std::to_string(dxgi));
+        }
+    } else if (fourcc) {
+        if (cc == "DXT1") im.Format = PT_FORMAT_BC1_UNORM; else if (cc == "DXT5") im.Format = PT_FORMAT_BC3_UNORM;
+        else if (cc == "ATI1" || cc == "BC4U") im.Format = PT_FORMAT_BC4_UNORM; else if (cc == "ATI2" || cc == "BC5U") im.Format = PT_FORMAT_BC5_UNORM;
+        else throw std::runtime_error("DDS: unsupported FourCC");
+    } else if ((pfFlags & 0x40u) && (pfFlags & 0x1u) && u32(88) == 32 && u32(92) == 0xFFu && u32(96) == 0xFF00u && u32(100) == 0xFF0000u && u32(104) == 0xFF000000u)
+        im.Format = PT_FORMAT_R8G8B8A8_UNORM;
+    else throw std::runtime_error("DDS: unsupported pixel format");
+    const bool block = im.Format >= PT_FORMAT_BC1_UNORM;
+    const uint64_t blockBytes = (im.Format == PT_FORMAT_BC3_UNORM || im.Format == PT_FORMAT_BC3_UNORM_SRGB || im.Format == PT_FORMAT_BC5_UNORM) ? 16 : 8;
+    auto mip_bytes = [&](uint64_t w, uint64_t h) { return block ? ((w + 3) / 4) * ((h + 3) / 4) * blockBytes : w * h * 4; };
+    if (!((flags & 0x20000u) && mips > 0)) mips = 1;
+    uint32_t maxMips = 0;
+    for (uint32_t s = width > height ? width : height; s; s >>= 1) maxMips++;
+    if (mips > maxMips) throw std::runtime_error("DDS: more mips than the texture size allows");
+    uint64_t total = 0;
+    const uint64_t room = d.size() - off;
+    for (uint32_t m = 0; m < mips; m++) {
+        const uint64_t w = (width >> m) ? (width >> m) : 1, h = (height >> m) ? (height >> m) : 1;
+        total += mip_bytes(w, h);
+        if (total > room) throw std::runtime_error("DDS: the header asks for more texels than the file holds");
+    }
+    const uint64_t n = mip_bytes(width, height);                            // the further mips are skipped
+    im.Data.assign((const uint8_t*)d.data() + off, (const uint8_t*)d.data() + off + (size_t)n);
+    return im;
+}
+
+// ------------------------------------------------------------------------------------------------
 // SimpleMath / DirectXMath conventions (row vectors: v' = v M), in double like ingest.py
 // ------------------------------------------------------------------------------------------------
 struct M4 { double m[4][4]; };
@@ -401,9 +471,16 @@ struct MeshData {
     // texture slots in the order of Material.ixx:22-33 (BaseColor, EmissiveColor, Metallic, Roughness, MetallicRoughness, Transmission, Normal);
     // textures are shared between the meshes of a model by (image, sRGB) like the reference's and the harness's loaders share them
     std::shared_ptr<struct Texture> Textures[7]; uint32_t TextureCoordinateIndex[7] = { 0, 0, 0, 0, 0, 0, 0 };
-    std::vector<std::string> SkippedTextures;                               // slots whose image this host cannot decode (anything but 8-bit PNG)
+    std::vector<std::string> SkippedTextures;                               // slots whose image this host cannot load (anything but 8-bit PNG and BC1 / BC3 / BC4 / BC5 / RGBA8 DDS)
 };
-struct Texture { Image Texels; bool SRGB = false; };                        // base-colour / emissive textures are created as *_UNORM_SRGB (GLTFHelpers.ixx:375-391)
+// base-colour / emissive textures are created as *_UNORM_SRGB (GLTFHelpers.ixx:375-391). A block-compressed DDS texture keeps the blocks
+// of its file (Blocks; Texels then carries the size only) and BlockFormat names its PtFormat: the library samples them in place.
+struct Texture {
+    Image Texels; bool SRGB = false;
+    std::vector<uint8_t> Blocks; uint32_t BlockFormat = 0;
+    bool IsBlockCompressed() const { return BlockFormat != 0; }
+    uint32_t Format() const { return IsBlockCompressed() ? BlockFormat : SRGB ? (uint32_t)PT_FORMAT_R8G8B8A8_UNORM_SRGB : (uint32_t)PT_FORMAT_R8G8B8A8_UNORM; }
+};
 enum TextureSlot { BaseColor = 0, EmissiveColor, Metallic, Roughness, MetallicRoughness, Transmission, Normal };
 struct MeshNode { std::vector<MeshData> Meshes; M4 GlobalTransform; };        // GlobalTransform reinterpreted as a row-vector matrix (LoadModel)
 
@@ -499,6 +576,22 @@ public:
         return b.substr(off, len);
     }
 
+    // a DDS image by its mime type, its file name or its first four bytes
+    bool image_is_dds(size_t ii, const std::string& bytes)
+    {
+        const Json& im = j.at("images").at(ii);
+        if (im.has("mimeType") && im.at("mimeType").str == "image/vnd-ms.dds") return true;
+        if (im.has("uri")) {
+            std::string uri = im.at("uri").str;
+            if (uri.compare(0, 5, "data:") && uri.size() >= 4) {
+                std::string tail = uri.substr(uri.size() - 4);
+                for (char& c : tail) c = (char)std::tolower((unsigned char)c);
+                if (tail == ".dds") return true;
+            }
+        }
+        return is_dds(bytes);
+    }
+
 private:
     std::string dir, jsonText, binChunk; bool haveBin = false;
     std::map<size_t, std::string> buffers;
@@ -550,13 +643,26 @@ inline std::vector<std::shared_ptr<MeshNode>> load_model(const std::string& path
     const Json& j = asset.j;
     std::map<std::pair<size_t, bool>, std::shared_ptr<Texture>> textureCache;          // (image, forced sRGB) -> texture; nullptr: not decodable here
     auto texture_for = [&](const Json& info, bool forceSrgb) -> std::shared_ptr<Texture> {
-        const size_t src = (size_t)j.at("textures").at((size_t)info.at("index").num).at("source").num;
+        const Json& tex = j.at("textures").at((size_t)info.at("index").num);
+        const Json* ext = tex.find("extensions");
+        const Json* msft = ext ? ext->find("MSFT_texture_dds") : nullptr;                // the DDS image wins over the PNG (GLTFHelpers.ixx:87-90,103,451)
+        const size_t src = (size_t)(msft && msft->has("source") ? msft->at("source") : tex.at("source")).num;
         const auto key = std::make_pair(src, forceSrgb);
         auto it = textureCache.find(key);
         if (it != textureCache.end()) return it->second;
         std::shared_ptr<Texture> t;
         const std::string bytes = asset.image_bytes(src);
-        if (is_png(bytes)) { try { t = std::make_shared<Texture>(); t->Texels = decode_png(bytes); t->SRGB = forceSrgb; } catch (const std::exception&) { t.reset(); } }
+        if (asset.image_is_dds(src, bytes)) {                              // forceSRGB: a UNORM DDS in these slots gets the _SRGB format (TextureHelpers.ixx:68)
+            try {
+                DdsImage dds = read_dds(bytes);
+                if (forceSrgb) dds.Format = dds.Format == PT_FORMAT_R8G8B8A8_UNORM ? (uint32_t)PT_FORMAT_R8G8B8A8_UNORM_SRGB : dds.Format == PT_FORMAT_BC1_UNORM ? (uint32_t)PT_FORMAT_BC1_UNORM_SRGB
+                                       : dds.Format == PT_FORMAT_BC3_UNORM ? (uint32_t)PT_FORMAT_BC3_UNORM_SRGB : dds.Format;
+                t = std::make_shared<Texture>(); t->Texels.Width = dds.Width; t->Texels.Height = dds.Height;
+                if (dds.Format >= PT_FORMAT_BC1_UNORM) { t->Blocks = std::move(dds.Data); t->BlockFormat = dds.Format; }
+                else { t->Texels.RGBA = std::move(dds.Data); }
+                t->SRGB = dds.Format == PT_FORMAT_R8G8B8A8_UNORM_SRGB || dds.Format == PT_FORMAT_BC1_UNORM_SRGB || dds.Format == PT_FORMAT_BC3_UNORM_SRGB;
+            } catch (const std::exception&) { t.reset(); }
+        } else if (is_png(bytes)) { try { t = std::make_shared<Texture>(); t->Texels = decode_png(bytes); t->SRGB = forceSrgb; } catch (const std::exception&) { t.reset(); } }
         return textureCache[key] = t;
     };
     auto process_primitive = [&](const Json& prim, MeshData& mesh) -> bool {

@@ -148,7 +148,9 @@ struct DescriptorHeap {
     {
         ThrowIfFailed(m_context, pt_heap_set_buffer(m_context, descriptor, buffer.DevicePointer, buffer.Capacity * buffer.Stride, buffer.Stride));
     }
-    // Texture::CreateSRV for a material map or the environment map (App.cpp:1021-1024,1052-1063); mip 0 texels, cube = 6 faces
+    // Texture::CreateSRV for a material map or the environment map (App.cpp:1021-1024,1052-1063); mip 0 texels, cube = 6 faces.
+    // format is a PtFormat: RGBA8 / RGBA8_SRGB / RGBA32F texel arrays, or PT_FORMAT_BC1 / BC3 / BC4 / BC5_*: the tightly packed 4x4 blocks of a
+    // DDS file's mip 0 as they are (2D only, 8- / 16-byte aligned), sampled in place
     void SetTexture(uint32_t descriptor, const void* texels, uint32_t width, uint32_t height, PtFormat format, bool isCubeMap = false)
     {
         ThrowIfFailed(m_context, pt_heap_set_texture(m_context, descriptor, texels, width, height, (uint32_t)format, isCubeMap ? 1u : 0u));

@@ -11,7 +11,9 @@ What it mirrors (host side of the path, upstream of the acceleration-structure b
                      transmission, base colour + emissive textures forced to sRGB, normal texture only with tangents
   instance transform Source/Scene.ixx:195-231: world = GlobalTransform * Scale(1,1,-1) * RenderObject.Transform()
                      (SimpleMath row-vector convention), AffineTransform = Scale * Rotation * Translation (Math.ixx:17-19)
-Texture *files* are decoded with PIL (PNG/JPEG); DDS/EXR/HDR codecs stay out of scope (TextureHelpers.ixx).
+Texture *files* are decoded with PIL (PNG/JPEG); a DDS image -- a texture's MSFT_texture_dds source wins over its PNG, as in the
+reference (GLTFHelpers.ixx:87-90,103,451) -- is read by bc.read_dds and its BC1 / BC3 / BC4 / BC5 blocks are handed on as they are; a DDS
+outside those formats is listed in Mesh.skipped_textures and the material keeps its factors. EXR/HDR stay out of scope (TextureHelpers.ixx).
 [DirectXMesh spec] ComputeTangentFrame is an un-vendored dependency: restated as Lengyel's per-vertex accumulation with
 Gram-Schmidt against the normal.
 """
@@ -24,6 +26,7 @@ import struct
 
 import numpy as np
 
+from . import bc
 from . import layouts as L
 from . import scenes as S
 
@@ -177,15 +180,37 @@ class _Asset:
             arr = arr.astype(np.float32) / float(np.iinfo(dt).max)
         return arr
 
-    def image(self, ii):
-        from PIL import Image
+    def image_bytes(self, ii):
         im = self.j["images"][ii]
         if "uri" in im:
             uri = im["uri"]
-            data = base64.b64decode(uri.split(",", 1)[1]) if uri.startswith("data:") else open(os.path.join(self.dir, uri), "rb").read()
-        else:
-            data, _ = self.view_bytes(im["bufferView"])
-        return np.ascontiguousarray(np.asarray(Image.open(io.BytesIO(data)).convert("RGBA"), np.uint8))
+            return base64.b64decode(uri.split(",", 1)[1]) if uri.startswith("data:") else open(os.path.join(self.dir, uri), "rb").read()
+        return self.view_bytes(im["bufferView"])[0]
+
+    def image_is_dds(self, ii, data):
+        im = self.j["images"][ii]
+        uri = im.get("uri", "")
+        return im.get("mimeType") == "image/vnd-ms.dds" or (not uri.startswith("data:") and uri.lower().endswith(".dds")) or bc.is_dds(data)
+
+    def image(self, ii):
+        from PIL import Image
+        return np.ascontiguousarray(np.asarray(Image.open(io.BytesIO(self.image_bytes(ii))).convert("RGBA"), np.uint8))
+
+    def texture(self, ii, force_srgb):
+        """Image ii as a scenes.Texture, or -- a DDS file, whose blocks go to the device as they are (TextureHelpers.ixx:65-78) -- a
+        scenes.BlockTexture. forceSRGB (base colour, emissive): a UNORM DDS gets the _SRGB format (TextureHelpers.ixx:68).
+        None: a DDS this host does not load (bc.read_dds says which)."""
+        data = self.image_bytes(ii)
+        if not self.image_is_dds(ii, data):
+            return S.Texture(self.image(ii), srgb=force_srgb)
+        try:
+            dds = bc.read_dds(data)
+        except ValueError:
+            return None
+        fmt = bc.SRGB_OF.get(dds.fmt, dds.fmt) if force_srgb else dds.fmt
+        if fmt in S.FMT_BLOCK_BYTES:
+            return S.BlockTexture(dds.data, dds.width, dds.height, fmt)
+        return S.Texture(dds.data, srgb=(fmt == S.FMT_RGBA8_UNORM_SRGB))
 
 
 def compute_tangents(positions, normals, uvs, indices):
@@ -232,10 +257,11 @@ def load_model(path, flip_winding_order=True):
 
     def texture_for(info, force_srgb):
         tex = j["textures"][info["index"]]
-        src = tex.get("source")
+        dds = (tex.get("extensions") or {}).get("MSFT_texture_dds") or {}
+        src = dds.get("source", tex.get("source"))                        # the DDS image wins over the PNG (GLTFHelpers.ixx:87-90,103,451)
         key = (src, force_srgb)
         if key not in tex_cache:
-            tex_cache[key] = S.Texture(asset.image(src), srgb=force_srgb)
+            tex_cache[key] = asset.texture(src, force_srgb)
         return tex_cache[key]
 
     def process_primitive(prim):
@@ -283,7 +309,11 @@ def load_model(path, flip_winding_order=True):
                 textures = {}
                 for slot, (info, srgb) in slots.items():
                     if info is not None and info.get("texCoord", 0) < 2 and has_uv[info.get("texCoord", 0)]:
-                        textures[slot] = (texture_for(info, srgb), info.get("texCoord", 0))
+                        t = texture_for(info, srgb)
+                        if t is None:                                     # listed and skipped: the material keeps its factors
+                            mesh.skipped_textures = (mesh.skipped_textures or []) + [slot]
+                        else:
+                            textures[slot] = (t, info.get("texCoord", 0))
                 mesh.textures = textures or None
         return mesh
 

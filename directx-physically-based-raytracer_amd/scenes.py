@@ -45,6 +45,8 @@ def make_indices(idx):
 
 
 FMT_RGBA8_UNORM, FMT_RGBA8_UNORM_SRGB, FMT_RGBA32_FLOAT = 0, 1, 2
+FMT_BC1_UNORM, FMT_BC1_UNORM_SRGB, FMT_BC3_UNORM, FMT_BC3_UNORM_SRGB, FMT_BC4_UNORM, FMT_BC5_UNORM = 3, 4, 5, 6, 7, 8   # PtFormat, include/ptamd.h
+FMT_BLOCK_BYTES = {FMT_BC1_UNORM: 8, FMT_BC1_UNORM_SRGB: 8, FMT_BC3_UNORM: 16, FMT_BC3_UNORM_SRGB: 16, FMT_BC4_UNORM: 8, FMT_BC5_UNORM: 16}
 KIND_BUFFER, KIND_TEXTURE2D, KIND_TEXTURECUBE = 0, 1, 2
 TEX_SLOTS = ["BaseColor", "EmissiveColor", "Metallic", "Roughness", "MetallicRoughness", "Transmission", "Normal"]   # Material.ixx:22-33
 
@@ -61,6 +63,16 @@ class Texture:
         if self.data.dtype == np.float32:
             return FMT_RGBA32_FLOAT
         return FMT_RGBA8_UNORM_SRGB if self.srgb else FMT_RGBA8_UNORM
+
+
+@dataclass
+class BlockTexture:
+    """Mip 0 of a block-compressed 2D texture (PtFormat BC1 / BC3 / BC4 / BC5), sampled in place. data: the block stream, uint8
+    [ceil(width / 4) * ceil(height / 4), 8 | 16], row-major; width, height: texels; fmt: one of FMT_BC* (bc.py decodes / encodes)."""
+    data: np.ndarray
+    width: int
+    height: int
+    fmt: int
 
 
 @dataclass
@@ -81,9 +93,10 @@ class Mesh:                      # Source/Model.ixx:26-47
     material: np.ndarray = None  # L.MATERIAL scalar, None => Material() (App.cpp:1044)
     has_tangents: bool = False
     has_uv: tuple = (False, False)
-    textures: dict = None        # slot name (TEX_SLOTS) -> (Texture, TextureCoordinateIndex)
+    textures: dict = None        # slot name (TEX_SLOTS) -> (Texture | BlockTexture, TextureCoordinateIndex)
     motion_vectors: np.ndarray = None   # skinned meshes: [n,4] half bits, written by the skinning pass (Model.ixx:33)
     skeletal_vertices: np.ndarray = None  # L.SKELETAL_VERTEX, Mesh::SkeletalVertices
+    skipped_textures: list = None  # slot names whose image the ingest could not load (ingest.py)
 
 
 @dataclass
@@ -135,6 +148,12 @@ class Scene:
         self._motion_heap = {}
 
         def tex_descriptor(tex):
+            if id(tex) not in tex_heap and isinstance(tex, BlockTexture):
+                blocks = np.ascontiguousarray(tex.data, np.uint8).reshape(-1, FMT_BLOCK_BYTES[tex.fmt])
+                if len(blocks) != ((tex.width + 3) // 4) * ((tex.height + 3) // 4):
+                    raise ValueError(f"block texture {tex.width}x{tex.height}: {len(blocks)} blocks")
+                tex_heap[id(tex)] = len(self.heap)
+                self.heap.append(HeapItem(blocks, 0, KIND_TEXTURE2D, tex.width, tex.height, tex.fmt))
             if id(tex) not in tex_heap:
                 cube = tex.data.ndim == 4 and tex.data.shape[0] == 6 and tex.data.shape[-1] == 4 and tex.data.shape[1] == tex.data.shape[2]
                 h, w = tex.data.shape[-3], tex.data.shape[-2]

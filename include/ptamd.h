@@ -191,11 +191,23 @@ int  pt_heap_set_buffer(PtContext* ctx, uint32_t descriptor, const void* device_
 /* Texture2D / TextureCube SRV (reference: Texture::GetSRVDescriptor, indices stored in TextureMapInfo.Descriptor
  * at Source/App.cpp:1052-1063 and in SceneData.EnvironmentLightTextureDescriptor at :1021-1024). Mip 0 only: the
  * path samples with SampleLevel(sampler, uv, 0) (Shaders/ShadingHelpers.hlsli:58). Linear row-major texels;
- * a cube is 6 faces +X,-X,+Y,-Y,+Z,-Z back to back. */
+ * a cube is 6 faces +X,-X,+Y,-Y,+Z,-Z back to back.
+ * Block-compressed formats (the DDS assets the reference loads through DirectXTex, Source/TextureHelpers.ixx:65-78) are
+ * sampled in place: width / height are texels (any value >= 1), the memory holds ceil(w/4) * ceil(h/4) blocks of 4x4
+ * texels, row-major and tightly packed (D3D's mip 0 without row padding); texels of an edge block beyond the image are
+ * never read. device_ptr must be aligned to the block size (8 / 16 bytes). 2D only: is_cube != 0 is refused. The decode
+ * rules are DESIGN.md's ("Arithmetic spec"): a BC1 / BC3 texture samples to the bits of its RGBA8(_SRGB) expansion,
+ * a BC4 / BC5 texture to the bits of its R32G32B32A32_FLOAT expansion. Values only grow; pt_abi_version() is unchanged. */
 typedef enum PtFormat {
     PT_FORMAT_R8G8B8A8_UNORM = 0,
     PT_FORMAT_R8G8B8A8_UNORM_SRGB = 1,     /* base colour / emissive textures (Source/GLTFHelpers.ixx:375-391) */
-    PT_FORMAT_R32G32B32A32_FLOAT = 2       /* HDR environment maps */
+    PT_FORMAT_R32G32B32A32_FLOAT = 2,      /* HDR environment maps */
+    PT_FORMAT_BC1_UNORM = 3,               /*  8-byte blocks: rgb, a in {0, 1} (three-colour mode, index 3) */
+    PT_FORMAT_BC1_UNORM_SRGB = 4,          /*  ... rgb through the sRGB table, a linear */
+    PT_FORMAT_BC3_UNORM = 5,               /* 16-byte blocks: interpolated 8-bit alpha, then the BC1 colour half: rgba */
+    PT_FORMAT_BC3_UNORM_SRGB = 6,          /*  ... rgb through the sRGB table, a linear */
+    PT_FORMAT_BC4_UNORM = 7,               /*  8-byte blocks: (r, 0, 0, 1), the interpolants at fp32 precision */
+    PT_FORMAT_BC5_UNORM = 8                /* 16-byte blocks: (r, g, 0, 1): two BC4 halves (normal maps) */
 } PtFormat;
 int  pt_heap_set_texture(PtContext* ctx, uint32_t descriptor, const void* device_ptr, uint32_t width, uint32_t height,
                          uint32_t format, uint32_t is_cube);
