@@ -18,6 +18,12 @@
 // and the BC1 / BC3 / BC4 / BC5 blocks go to the library as they are (read_dds below); a DDS outside those formats is listed and skipped too.
 // [DirectXMesh spec] ComputeTangentFrame is an un-vendored dependency: restated as Lengyel's per-vertex accumulation with Gram-Schmidt
 // against the normal (as in ingest.py). Header-only, C++20, no dependency beyond the standard library and include/ptamd.h.
+//
+// These are the only files the project reads that it did not write, so every size, offset and index a file states passes one of the checked
+// primitives at the top before it is used: Bytes (a view that refuses a read outside itself), Json::uint / index / string / real (a value of
+// the right kind and range, or a refusal) and add / mul (size arithmetic that refuses to wrap). Below them nothing touches a raw file byte or
+// turns a JSON number into an integer, with one exception: Asset::element reads inside a range that Asset::accessor has validated, once per
+// vertex component. What the hosts accept is stated in DESIGN.md section 2; every refusal is a std::runtime_error.
 #pragma once
 #include <array>
 #include <cctype>
@@ -26,8 +32,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <fstream>
-#include <functional>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -39,8 +45,39 @@
 namespace ptamd::ingest {
 
 // ------------------------------------------------------------------------------------------------
-// a small JSON reader (objects, arrays, strings, numbers, true / false / null)
+// checked primitives: size arithmetic, a byte view, JSON values
 // ------------------------------------------------------------------------------------------------
+inline size_t add(size_t a, size_t b) { if (b > SIZE_MAX - a) throw std::runtime_error("a size stated by the file overflows"); return a + b; }
+inline size_t mul(size_t a, size_t b) { if (b && a > SIZE_MAX / b) throw std::runtime_error("a size stated by the file overflows"); return a * b; }
+
+// a non-owning view of file bytes; every read names an offset and a length and throws unless both lie inside the view
+struct Bytes {
+    const uint8_t* data = nullptr; size_t size = 0;
+    Bytes() = default;
+    Bytes(const uint8_t* p, size_t n) : data(p), size(n) {}
+    Bytes(const std::string& s) : data(reinterpret_cast<const uint8_t*>(s.data())), size(s.size()) {}
+    Bytes(const std::vector<uint8_t>& v) : data(v.data()), size(v.size()) {}
+
+    Bytes sub(size_t off, size_t len, const char* what = "a read") const
+    {
+        if (len > size || off > size - len)                                // never off + len: it may wrap
+            throw std::runtime_error(std::string(what) + " of " + std::to_string(len) + " bytes at offset " + std::to_string(off) + " reaches beyond the " + std::to_string(size) + " bytes there are");
+        return Bytes(data + off, len);
+    }
+    Bytes from(size_t off) const { return sub(off, off <= size ? size - off : 0); }
+    uint8_t u8(size_t off) const { return sub(off, 1).data[0]; }
+    uint16_t le16(size_t off) const { const uint8_t* p = sub(off, 2).data; return (uint16_t)(p[0] | (p[1] << 8)); }
+    uint32_t le32(size_t off) const { const uint8_t* p = sub(off, 4).data; return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+    uint32_t be32(size_t off) const { const uint8_t* p = sub(off, 4).data; return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3]; }
+    bool is(const char* s) const { return size == std::strlen(s) && !std::memcmp(data, s, size); }
+    bool starts_with(const char* s, size_t n) const { return size >= n && !std::memcmp(data, s, n); }
+    const uint8_t* begin() const { return data; }
+    const uint8_t* end() const { return data + size; }
+    void append_to(std::vector<uint8_t>& v) const { v.insert(v.end(), begin(), end()); }
+};
+
+// objects, arrays, strings, numbers, true / false / null. The public members are what JsonParser fills; file content is read through the
+// accessors, which throw on a value of the wrong kind (a bare .num / .str would silently give 0 / "").
 struct Json {
     enum Kind { Null, Bool, Number, String, Array, Object } kind = Null;
     bool b = false; double num = 0.0; std::string str;
@@ -55,66 +92,105 @@ struct Json {
     bool has(const std::string& key) const { const Json* j = find(key); return j && j->kind != Null; }
     const Json& at(const std::string& key) const { const Json* j = find(key); if (!j) throw std::runtime_error("JSON: missing key " + key); return *j; }
     const Json& at(size_t i) const { if (kind != Array || i >= arr.size()) throw std::runtime_error("JSON: index out of range"); return arr[i]; }
-    double number(const std::string& key, double def) const { const Json* j = find(key); return j && j->kind == Number ? j->num : def; }
+    const std::vector<Json>& items() const { if (kind != Array) throw std::runtime_error("JSON: an array is expected"); return arr; }
     size_t size() const { return kind == Array ? arr.size() : obj.size(); }
+
+    double real() const { if (kind != Number) throw std::runtime_error("JSON: a number is expected"); return num; }
+    double number(const std::string& key, double def) const { const Json* j = find(key); return j && j->kind == Number ? j->num : def; }
+    float f32() const { return (float)real(); }
+    float f32(const std::string& key, double def) const { return (float)number(key, def); }
+    const std::string& string() const { if (kind != String) throw std::runtime_error("JSON: a string is expected"); return str; }
+    // the one place a JSON number becomes an integer: finite, integral, 0 <= value <= max (and <= 2^53: up to there a double holds every integer)
+    size_t uint(size_t max) const
+    {
+        if (kind != Number || !(num >= 0.0) || !(num <= (double)(max < kMaxUint ? max : kMaxUint)) || num != std::floor(num))
+            throw std::runtime_error("JSON: " + (kind == Number ? std::to_string(num) : std::string("a value that is no number")) + " where an integer from 0 to " + std::to_string(max) + " is expected");
+        return (size_t)num;
+    }
+    size_t uint(const std::string& key, size_t def, size_t max) const { const Json* j = find(key); return j ? j->uint(max) : def; }   // an optional member
+    size_t index(size_t limit) const { if (!limit) throw std::runtime_error("JSON: an index into an empty list"); return uint(limit - 1); }
+    const Json& pick(const Json& i) const { return items()[i.index(arr.size())]; }   // the element of this list that the file value i names
+    static constexpr size_t kMaxUint = (size_t)1 << 53;
 };
+
+// Nesting limit of the reader, which recurses once per level. Measured: the deepest nesting in tests/golden/ingest/* and in what
+// ingest.export_scene writes is 6 (document -> materials -> material -> extensions -> extension -> texture info); the reader without a limit,
+// built with -O1 under AddressSanitizer, overflows the default 8 MiB stack at a nesting of 9688. A power of two that is at least 4 x 6 and
+// at most 9688 / 4; ingest.py has the same limit (MAX_JSON_DEPTH).
+constexpr int kMaxJsonDepth = 128;
 
 class JsonParser {
 public:
-    explicit JsonParser(const std::string& text) : s(text) {}
-    Json parse() { Json v = value(); ws(); if (p != s.size()) fail("trailing characters"); return v; }
+    explicit JsonParser(Bytes text) : s(text) {}
+    Json parse() { Json v = value(1); ws(); if (p != s.size) fail("trailing characters"); return v; }
 
 private:
-    const std::string& s; size_t p = 0;
-    [[noreturn]] void fail(const char* what) const { throw std::runtime_error(std::string("JSON: ") + what + " at byte " + std::to_string(p)); }
-    void ws() { while (p < s.size() && (s[p] == ' ' || s[p] == '\n' || s[p] == '\t' || s[p] == '\r')) p++; }
-    bool eat(char c) { ws(); if (p < s.size() && s[p] == c) { p++; return true; } return false; }
-    Json value()
+    const Bytes s; size_t p = 0; std::string token;
+    [[noreturn]] void fail(const std::string& what) const { throw std::runtime_error("JSON: " + what + " at byte " + std::to_string(p)); }
+    int peek() const { return p < s.size ? s.u8(p) : -1; }                 // -1: the end of the text
+    void ws() { for (int c = peek(); c == ' ' || c == '\n' || c == '\t' || c == '\r'; c = peek()) p++; }
+    bool eat(char c) { ws(); if (peek() == c) { p++; return true; } return false; }
+    bool word(const char* w, size_t n) { if (n > s.size - p || !s.sub(p, n).is(w)) return false; p += n; return true; }
+    unsigned hex4()
+    {
+        unsigned cp = 0;
+        for (int k = 0; k < 4; k++, p++) {
+            const int c = peek(), d = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
+            if (d < 0) fail("bad \\u escape");
+            cp = cp * 16 + (unsigned)d;
+        }
+        return cp;
+    }
+    Json value(int depth)
     {
         ws();
-        if (p >= s.size()) fail("unexpected end");
         Json v;
-        const char c = s[p];
+        const int c = peek();
+        if (c < 0) fail("unexpected end");
+        if ((c == '{' || c == '[') && depth > kMaxJsonDepth) fail("arrays and objects nested deeper than " + std::to_string(kMaxJsonDepth));
         if (c == '{') {
             p++; v.kind = Json::Object;
             if (eat('}')) return v;
-            do { ws(); Json k = value(); if (k.kind != Json::String) fail("object key is not a string"); if (!eat(':')) fail("':' expected"); v.obj.emplace_back(k.str, value()); } while (eat(','));
+            do { ws(); Json k = value(depth + 1); if (k.kind != Json::String) fail("object key is not a string"); if (!eat(':')) fail("':' expected"); v.obj.emplace_back(std::move(k.str), value(depth + 1)); } while (eat(','));
             if (!eat('}')) fail("'}' expected");
         } else if (c == '[') {
             p++; v.kind = Json::Array;
             if (eat(']')) return v;
-            do v.arr.push_back(value()); while (eat(','));
+            do v.arr.push_back(value(depth + 1)); while (eat(','));
             if (!eat(']')) fail("']' expected");
         } else if (c == '"') {
             p++; v.kind = Json::String;
-            while (p < s.size() && s[p] != '"') {
-                if (s[p] == '\\') {
-                    if (++p >= s.size()) fail("bad escape");
-                    switch (s[p]) {
-                    case 'n': v.str += '\n'; break; case 't': v.str += '\t'; break; case 'r': v.str += '\r'; break;
-                    case 'b': v.str += '\b'; break; case 'f': v.str += '\f'; break;
-                    case 'u': {                                            // BMP code point -> UTF-8 (names and paths only)
-                        if (p + 4 >= s.size()) fail("bad \\u escape");
-                        const unsigned cp = (unsigned)std::stoul(s.substr(p + 1, 4), nullptr, 16); p += 4;
-                        if (cp < 0x80) v.str += (char)cp;
-                        else if (cp < 0x800) { v.str += (char)(0xC0 | (cp >> 6)); v.str += (char)(0x80 | (cp & 0x3F)); }
-                        else { v.str += (char)(0xE0 | (cp >> 12)); v.str += (char)(0x80 | ((cp >> 6) & 0x3F)); v.str += (char)(0x80 | (cp & 0x3F)); }
-                        break; }
-                    default: v.str += s[p];
-                    }
-                    p++;
-                } else v.str += s[p++];
+            for (int ch = peek(); ch != '"'; ch = peek()) {
+                if (ch < 0) fail("unterminated string");
+                p++;
+                if (ch != '\\') { v.str += (char)ch; continue; }
+                const int e = peek();
+                if (e < 0) fail("bad escape");
+                p++;
+                switch (e) {
+                case 'n': v.str += '\n'; break; case 't': v.str += '\t'; break; case 'r': v.str += '\r'; break;
+                case 'b': v.str += '\b'; break; case 'f': v.str += '\f'; break;
+                case 'u': {                                                // BMP code point -> UTF-8 (names and paths only)
+                    const unsigned cp = hex4();
+                    if (cp < 0x80) v.str += (char)cp;
+                    else if (cp < 0x800) { v.str += (char)(0xC0 | (cp >> 6)); v.str += (char)(0x80 | (cp & 0x3F)); }
+                    else { v.str += (char)(0xE0 | (cp >> 12)); v.str += (char)(0x80 | ((cp >> 6) & 0x3F)); v.str += (char)(0x80 | (cp & 0x3F)); }
+                    break; }
+                default: v.str += (char)e;
+                }
             }
-            if (p >= s.size()) fail("unterminated string");
             p++;
-        } else if (!s.compare(p, 4, "true")) { p += 4; v.kind = Json::Bool; v.b = true; }
-        else if (!s.compare(p, 5, "false")) { p += 5; v.kind = Json::Bool; v.b = false; }
-        else if (!s.compare(p, 4, "null")) { p += 4; v.kind = Json::Null; }
-        else {
+        } else if (word("true", 4)) { v.kind = Json::Bool; v.b = true; }
+        else if (word("false", 5)) { v.kind = Json::Bool; v.b = false; }
+        else if (word("null", 4)) { v.kind = Json::Null; }
+        else {                                                             // a number: the JSON token, then strtod on a copy of it alone (so no "nan", "inf" or hex,
+            token.clear();                                                 // and nothing read past the end of a view that no NUL ends)
+            for (int ch = c; (ch >= '0' && ch <= '9') || ch == '-' || ch == '+' || ch == '.' || ch == 'e' || ch == 'E'; ch = peek()) { token += (char)ch; p++; }
+            if (c != '-' && !(c >= '0' && c <= '9')) fail("value expected");
             char* end = nullptr;
-            v.num = std::strtod(s.c_str() + p, &end);                     // correctly rounded, like Python's float()
-            if (end == s.c_str() + p) fail("value expected");
-            p = (size_t)(end - s.c_str()); v.kind = Json::Number;
+            v.num = std::strtod(token.c_str(), &end);                      // correctly rounded, like Python's float()
+            if (token.empty() || end != token.c_str() + token.size()) fail("bad number");
+            v.kind = Json::Number;
         }
         return v;
     }
@@ -129,7 +205,7 @@ inline std::string read_file(const std::string& path)
 inline std::string dir_of(const std::string& path) { const size_t k = path.find_last_of('/'); return k == std::string::npos ? std::string(".") : path.substr(0, k); }
 inline std::string resolve(const std::string& base, const std::string& p) { return (p.empty() || p[0] == '/') ? p : base + "/" + p; }
 
-inline std::string base64_decode(const std::string& in)
+inline std::string base64_decode(Bytes in)
 {
     std::string out; unsigned acc = 0; int bits = 0;
     for (unsigned char c : in) {
@@ -141,6 +217,13 @@ inline std::string base64_decode(const std::string& in)
     }
     return out;
 }
+// what a buffer's or an image's uri names: the payload of a data: uri, or the file beside the model
+inline std::string read_uri(const std::string& dir, const std::string& uri)
+{
+    if (uri.compare(0, 5, "data:")) return read_file(resolve(dir, uri));
+    const size_t comma = uri.find(',');
+    return base64_decode(Bytes(uri).from(comma == std::string::npos ? 0 : comma + 1));
+}
 
 // ------------------------------------------------------------------------------------------------
 // PNG (the lossless half of what glTF embeds; JPEG needs a codec this image does not have: such textures are listed and skipped)
@@ -148,24 +231,27 @@ inline std::string base64_decode(const std::string& in)
 // RFC 1951 inflate (stored, fixed and dynamic Huffman blocks) behind the RFC 1950 zlib header; canonical-code decoding by counts per length.
 class Inflate {
 public:
-    static std::vector<uint8_t> zlib(const uint8_t* src, size_t n)
+    // expected: the size the caller knows the stream must inflate to; one that produces more is refused as soon as it does, so the output
+    // is bounded by what the image header and the file's own bytes justify
+    static std::vector<uint8_t> zlib(Bytes src, size_t expected)
     {
-        if (n < 6 || (src[0] & 0x0F) != 8 || ((src[0] << 8) | src[1]) % 31 != 0 || (src[1] & 0x20)) throw std::runtime_error("PNG: bad zlib header");
-        Inflate z(src + 2, n - 2);
+        if (src.size < 6 || (src.u8(0) & 0x0F) != 8 || ((src.u8(0) << 8) | src.u8(1)) % 31 != 0 || (src.u8(1) & 0x20)) throw std::runtime_error("PNG: bad zlib header");
+        Inflate z(src.from(2), expected);
         z.run();
         return std::move(z.out);
     }
 
 private:
-    Inflate(const uint8_t* s, size_t n) : in(s), size(n) {}
-    const uint8_t* in; size_t size, pos = 0; uint32_t bitbuf = 0; int bitcnt = 0;
+    Inflate(Bytes s, size_t expected) : in(s), limit(expected) {}
+    const Bytes in; const size_t limit; size_t pos = 0; uint32_t bitbuf = 0; int bitcnt = 0;
     std::vector<uint8_t> out;
+    void room(size_t n) const { if (n > limit - out.size()) throw std::runtime_error("PNG: the deflate stream holds more than the image needs"); }
     struct Huffman { uint16_t count[16]; uint16_t symbol[288]; };
 
     uint32_t bits(int need)
     {
         uint32_t v = bitbuf;
-        while (bitcnt < need) { if (pos >= size) throw std::runtime_error("PNG: deflate stream ends early"); v |= (uint32_t)in[pos++] << bitcnt; bitcnt += 8; }
+        while (bitcnt < need) { v |= (uint32_t)in.u8(pos++) << bitcnt; bitcnt += 8; }         // (the view refuses a read past the end of the stream)
         bitbuf = need < 32 ? v >> need : 0; bitcnt -= need;
         return need < 32 ? v & ((1u << need) - 1u) : v;
     }
@@ -197,7 +283,7 @@ private:
         static const uint16_t dext[30] = { 0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13 };
         for (;;) {
             int sym = decode(lencode);
-            if (sym < 256) out.push_back((uint8_t)sym);
+            if (sym < 256) { room(1); out.push_back((uint8_t)sym); }
             else if (sym == 256) return;
             else {
                 sym -= 257;
@@ -207,6 +293,7 @@ private:
                 if (ds >= 30) throw std::runtime_error("PNG: bad distance symbol");
                 const size_t dist = dbase[ds] + bits(dext[ds]);
                 if (dist > out.size()) throw std::runtime_error("PNG: distance beyond the window");
+                room((size_t)len);
                 for (int k = 0; k < len; k++) out.push_back(out[out.size() - dist]);
             }
         }
@@ -218,11 +305,11 @@ private:
             const uint32_t type = bits(2);
             if (type == 0) {
                 bitbuf = 0; bitcnt = 0;
-                if (pos + 4 > size) throw std::runtime_error("PNG: stored block ends early");
-                const uint32_t len = in[pos] | (in[pos + 1] << 8), nlen = in[pos + 2] | (in[pos + 3] << 8);
+                const uint32_t len = in.le16(pos), nlen = in.le16(pos + 2);  // pos <= in.size: no wrap
                 pos += 4;
-                if ((len ^ 0xFFFFu) != nlen || pos + len > size) throw std::runtime_error("PNG: bad stored block");
-                out.insert(out.end(), in + pos, in + pos + len); pos += len;
+                if ((len ^ 0xFFFFu) != nlen) throw std::runtime_error("PNG: bad stored block");
+                room(len);
+                in.sub(pos, len, "PNG: a stored block").append_to(out); pos += len;
             } else if (type == 1) {
                 uint8_t l[288];
                 for (int i = 0; i < 288; i++) l[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8;
@@ -258,31 +345,34 @@ private:
 
 struct Image { uint32_t Width = 0, Height = 0; std::vector<uint8_t> RGBA; };       // 8 bits per channel, rows top to bottom
 
-inline bool is_png(const std::string& d) { return d.size() >= 8 && !std::memcmp(d.data(), "\x89PNG\r\n\x1a\n", 8); }
+inline bool is_png(Bytes d) { return d.starts_with("\x89PNG\r\n\x1a\n", 8); }
+constexpr uint32_t kMaxImageSide = 65536;                                  // of a PNG and of a DDS alike (D3D12's limit is 16384)
 
 // 8-bit grey / grey+alpha / RGB / RGBA / palette PNG without interlacing -> RGBA8, as PIL's Image.open(...).convert("RGBA") delivers it
-inline Image decode_png(const std::string& d)
+inline Image decode_png(Bytes d)
 {
     if (!is_png(d)) throw std::runtime_error("not a PNG");
-    auto be32 = [&](size_t o) { return ((uint32_t)(uint8_t)d[o] << 24) | ((uint32_t)(uint8_t)d[o + 1] << 16) | ((uint32_t)(uint8_t)d[o + 2] << 8) | (uint32_t)(uint8_t)d[o + 3]; };
     Image im; int depth = 0, ctype = 0, interlace = 0;
-    std::string idat; std::vector<uint8_t> palette, trns;
-    for (size_t o = 8; o + 12 <= d.size();) {
-        const uint32_t len = be32(o); const std::string type = d.substr(o + 4, 4);
-        if (o + 12 + (size_t)len > d.size()) throw std::runtime_error("PNG: chunk reaches beyond the file");
-        if (type == "IHDR") { im.Width = be32(o + 8); im.Height = be32(o + 12); depth = (uint8_t)d[o + 16]; ctype = (uint8_t)d[o + 17]; interlace = (uint8_t)d[o + 20]; }
-        else if (type == "PLTE") palette.assign(d.begin() + (long)o + 8, d.begin() + (long)o + 8 + len);
-        else if (type == "tRNS") trns.assign(d.begin() + (long)o + 8, d.begin() + (long)o + 8 + len);
-        else if (type == "IDAT") idat.append(d, o + 8, len);
-        else if (type == "IEND") break;
-        o += 12 + (size_t)len;
+    std::vector<uint8_t> idat; Bytes palette, trns;
+    for (size_t o = 8; d.size - o >= 12;) {                                 // length, type, body, CRC
+        const Bytes chunk = d.sub(o, add(12, d.be32(o)), "PNG: a chunk"), type = chunk.sub(4, 4), body = chunk.sub(8, chunk.size - 12);
+        if (type.is("IHDR")) {
+            if (body.size != 13) throw std::runtime_error("PNG: IHDR is not 13 bytes");
+            im.Width = body.be32(0); im.Height = body.be32(4); depth = body.u8(8); ctype = body.u8(9); interlace = body.u8(12);
+        }
+        else if (type.is("PLTE")) palette = body;
+        else if (type.is("tRNS")) trns = body;
+        else if (type.is("IDAT")) body.append_to(idat);
+        else if (type.is("IEND")) break;
+        o += chunk.size;
     }
     const int channels = ctype == 0 ? 1 : ctype == 2 ? 3 : ctype == 3 ? 1 : ctype == 4 ? 2 : ctype == 6 ? 4 : 0;
     if (!channels || depth != 8 || interlace || !im.Width || !im.Height) throw std::runtime_error("PNG: only 8-bit non-interlaced images are decoded here");
-    const std::vector<uint8_t> raw = Inflate::zlib((const uint8_t*)idat.data(), idat.size());
-    const size_t bpp = (size_t)channels, stride = (size_t)im.Width * bpp;
-    if (raw.size() < (stride + 1) * im.Height) throw std::runtime_error("PNG: image data too short");
-    std::vector<uint8_t> px(stride * im.Height);
+    if (im.Width > kMaxImageSide || im.Height > kMaxImageSide) throw std::runtime_error("PNG: image larger than 65536 texels a side");
+    const size_t bpp = (size_t)channels, stride = mul(im.Width, bpp), texels = mul(im.Width, im.Height);
+    const std::vector<uint8_t> raw = Inflate::zlib(idat, mul(add(stride, 1), im.Height));     // no more than this; every buffer below is sized
+    if (raw.size() < mul(add(stride, 1), im.Height)) throw std::runtime_error("PNG: image data too short");   // once that much data exists
+    std::vector<uint8_t> px(mul(stride, im.Height));
     for (uint32_t y = 0; y < im.Height; y++) {                                      // undo the scanline filters (PNG spec 9.2)
         const uint8_t* src = raw.data() + (stride + 1) * y; const int f = src[0]; src++;
         uint8_t* cur = px.data() + stride * y; const uint8_t* up = y ? cur - stride : nullptr;
@@ -295,15 +385,15 @@ inline Image decode_png(const std::string& d)
             cur[x] = (uint8_t)v;
         }
     }
-    im.RGBA.resize((size_t)im.Width * im.Height * 4);
-    for (size_t i = 0; i < (size_t)im.Width * im.Height; i++) {
+    im.RGBA.resize(mul(texels, 4));
+    for (size_t i = 0; i < texels; i++) {
         uint8_t* o = im.RGBA.data() + 4 * i; const uint8_t* s = px.data() + bpp * i;
         if (ctype == 6) { o[0] = s[0]; o[1] = s[1]; o[2] = s[2]; o[3] = s[3]; }
         else if (ctype == 2) { o[0] = s[0]; o[1] = s[1]; o[2] = s[2]; o[3] = 255; }
         else if (ctype == 0) { o[0] = o[1] = o[2] = s[0]; o[3] = 255; }
         else if (ctype == 4) { o[0] = o[1] = o[2] = s[0]; o[3] = s[1]; }
-        else { const size_t k = s[0]; if (3 * k + 3 > palette.size()) throw std::runtime_error("PNG: palette index out of range");
-               o[0] = palette[3 * k]; o[1] = palette[3 * k + 1]; o[2] = palette[3 * k + 2]; o[3] = k < trns.size() ? trns[k] : 255; }
+        else { const size_t k = s[0]; const Bytes rgb = palette.sub(3 * k, 3, "PNG: a palette entry");
+               o[0] = rgb.u8(0); o[1] = rgb.u8(1); o[2] = rgb.u8(2); o[3] = k < trns.size ? trns.u8(k) : 255; }
     }
     return im;
 }
@@ -314,29 +404,28 @@ inline Image decode_png(const std::string& d)
 // 80, 83, the FourCCs DXT1, DXT5, ATI1 / BC4U, ATI2 / BC5U, and 32-bit RGBA masks; everything else throws. Every size the file states is
 // checked against the buffer before a byte is read.
 // ------------------------------------------------------------------------------------------------
-inline bool is_dds(const std::string& d) { return d.size() >= 4 && !std::memcmp(d.data(), "DDS ", 4); }
+inline bool is_dds(Bytes d) { return d.starts_with("DDS ", 4); }
 
 struct DdsImage { uint32_t Width = 0, Height = 0, Format = 0; std::vector<uint8_t> Data; };   // Format: PtFormat; Data: blocks, or RGBA8 texels
 
-inline DdsImage read_dds(const std::string& d)
+inline DdsImage read_dds(Bytes d)
 {
     if (!is_dds(d)) throw std::runtime_error("DDS: no 'DDS ' magic");
-    if (d.size() < 128) throw std::runtime_error("DDS: the file is shorter than its header");
-    auto u32 = [&](size_t o) { uint32_t v; std::memcpy(&v, d.data() + o, 4); return v; };     // o + 4 <= 128 <= size (148 for the DX10 fields, checked below)
-    const uint32_t size = u32(4), flags = u32(8), height = u32(12), width = u32(16), depth = u32(24), pfSize = u32(76), pfFlags = u32(80), caps2 = u32(112);
-    uint32_t mips = u32(28);
+    if (d.size < 128) throw std::runtime_error("DDS: the file is shorter than its header");
+    const uint32_t size = d.le32(4), flags = d.le32(8), height = d.le32(12), width = d.le32(16), depth = d.le32(24), pfSize = d.le32(76), pfFlags = d.le32(80), caps2 = d.le32(112);
+    uint32_t mips = d.le32(28);
     if (size != 124 || pfSize != 32) throw std::runtime_error("DDS: bad header size");
     if (!width || !height) throw std::runtime_error("DDS: zero width or height");
-    if (width > 65536u || height > 65536u) throw std::runtime_error("DDS: texture larger than 65536 texels a side");   // (D3D12's limit is 16384) sizes below stay far from 2^64
+    if (width > kMaxImageSide || height > kMaxImageSide) throw std::runtime_error("DDS: texture larger than 65536 texels a side");
     if ((caps2 & 0x200000u) || ((flags & 0x800000u) && depth > 1)) throw std::runtime_error("DDS: volume textures are not supported");
     if (caps2 & 0x200u) throw std::runtime_error("DDS: cube maps are not supported");
     DdsImage im; im.Width = width; im.Height = height;
     size_t off = 128;
     const bool fourcc = (pfFlags & 0x4u) != 0;
-    const std::string cc = d.substr(84, 4);
-    if (fourcc && cc == "DX10") {
-        if (d.size() < 148) throw std::runtime_error("DDS: the file is shorter than its DX10 header");
-        const uint32_t dxgi = u32(128), dimension = u32(132), misc = u32(136), arraySize = u32(140);
+    const Bytes cc = d.sub(84, 4);
+    if (fourcc && cc.is("DX10")) {
+        if (d.size < 148) throw std::runtime_error("DDS: the file is shorter than its DX10 header");
+        const uint32_t dxgi = d.le32(128), dimension = d.le32(132), misc = d.le32(136), arraySize = d.le32(140);
         off = 148;
         if (dimension == 4) throw std::runtime_error("DDS: volume textures are not supported");
         if (dimension != 3) throw std::runtime_error("DDS: only 2D textures are supported");
@@ -350,28 +439,27 @@ inline DdsImage read_dds(const std::string& d)
         default: throw std::runtime_error("DDS: unsupported DXGI format " + std::to_string(dxgi));
         }
     } else if (fourcc) {
-        if (cc == "DXT1") im.Format = PT_FORMAT_BC1_UNORM; else if (cc == "DXT5") im.Format = PT_FORMAT_BC3_UNORM;
-        else if (cc == "ATI1" || cc == "BC4U") im.Format = PT_FORMAT_BC4_UNORM; else if (cc == "ATI2" || cc == "BC5U") im.Format = PT_FORMAT_BC5_UNORM;
+        if (cc.is("DXT1")) im.Format = PT_FORMAT_BC1_UNORM; else if (cc.is("DXT5")) im.Format = PT_FORMAT_BC3_UNORM;
+        else if (cc.is("ATI1") || cc.is("BC4U")) im.Format = PT_FORMAT_BC4_UNORM; else if (cc.is("ATI2") || cc.is("BC5U")) im.Format = PT_FORMAT_BC5_UNORM;
         else throw std::runtime_error("DDS: unsupported FourCC");
-    } else if ((pfFlags & 0x40u) && (pfFlags & 0x1u) && u32(88) == 32 && u32(92) == 0xFFu && u32(96) == 0xFF00u && u32(100) == 0xFF0000u && u32(104) == 0xFF000000u)
+    } else if ((pfFlags & 0x40u) && (pfFlags & 0x1u) && d.le32(88) == 32 && d.le32(92) == 0xFFu && d.le32(96) == 0xFF00u && d.le32(100) == 0xFF0000u && d.le32(104) == 0xFF000000u)
         im.Format = PT_FORMAT_R8G8B8A8_UNORM;
     else throw std::runtime_error("DDS: unsupported pixel format");
     const bool block = im.Format >= PT_FORMAT_BC1_UNORM;
-    const uint64_t blockBytes = (im.Format == PT_FORMAT_BC3_UNORM || im.Format == PT_FORMAT_BC3_UNORM_SRGB || im.Format == PT_FORMAT_BC5_UNORM) ? 16 : 8;
-    auto mip_bytes = [&](uint64_t w, uint64_t h) { return block ? ((w + 3) / 4) * ((h + 3) / 4) * blockBytes : w * h * 4; };
+    const size_t blockBytes = (im.Format == PT_FORMAT_BC3_UNORM || im.Format == PT_FORMAT_BC3_UNORM_SRGB || im.Format == PT_FORMAT_BC5_UNORM) ? 16 : 8;
+    auto mip_bytes = [&](size_t w, size_t h) { return block ? mul(mul((w + 3) / 4, (h + 3) / 4), blockBytes) : mul(mul(w, h), 4); };
     if (!((flags & 0x20000u) && mips > 0)) mips = 1;
     uint32_t maxMips = 0;
     for (uint32_t s = width > height ? width : height; s; s >>= 1) maxMips++;
     if (mips > maxMips) throw std::runtime_error("DDS: more mips than the texture size allows");
-    uint64_t total = 0;
-    const uint64_t room = d.size() - off;
+    const Bytes texels = d.from(off);
+    size_t total = 0;
     for (uint32_t m = 0; m < mips; m++) {
-        const uint64_t w = (width >> m) ? (width >> m) : 1, h = (height >> m) ? (height >> m) : 1;
-        total += mip_bytes(w, h);
-        if (total > room) throw std::runtime_error("DDS: the header asks for more texels than the file holds");
+        const size_t w = (width >> m) ? (width >> m) : 1, h = (height >> m) ? (height >> m) : 1;
+        total = add(total, mip_bytes(w, h));
+        if (total > texels.size) throw std::runtime_error("DDS: the header asks for more texels than the file holds");
     }
-    const uint64_t n = mip_bytes(width, height);                            // the further mips are skipped
-    im.Data.assign((const uint8_t*)d.data() + off, (const uint8_t*)d.data() + off + (size_t)n);
+    texels.sub(0, mip_bytes(width, height)).append_to(im.Data);            // the further mips are skipped
     return im;
 }
 
@@ -493,50 +581,54 @@ inline PtMaterial default_material()
 
 class Asset {
 public:
-    explicit Asset(const std::string& path) : dir(dir_of(path))
+    explicit Asset(const std::string& path) : dir(dir_of(path)), raw(read_file(path))
     {
-        const std::string raw = read_file(path);
-        if (raw.size() >= 12 && !raw.compare(0, 4, "glTF")) {
-            uint32_t length; std::memcpy(&length, raw.data() + 8, 4);
-            size_t off = 12;
-            while (off + 8 <= length && off + 8 <= raw.size()) {
-                uint32_t clen, ctype; std::memcpy(&clen, raw.data() + off, 4); std::memcpy(&ctype, raw.data() + off + 4, 4);
-                if (ctype == 0x4E4F534Au) j = JsonParser(jsonText = raw.substr(off + 8, clen)).parse();
-                else if (ctype == 0x004E4942u) { binChunk = raw.substr(off + 8, clen); haveBin = true; }
-                off += 8 + (size_t)clen;
-            }
-        } else j = JsonParser(jsonText = raw).parse();
+        const Bytes file(raw);
+        if (file.size < 12 || !file.starts_with("glTF", 4)) { j = JsonParser(file).parse(); return; }
+        const Bytes glb = file.sub(0, file.le32(8), "GLB: the length in the header");
+        if (glb.size < 12) throw std::runtime_error("GLB: the length in the header is shorter than the header");
+        for (size_t off = 12; off < glb.size;) {                            // chunk length, chunk type, chunk
+            const Bytes chunk = glb.from(off + 8).sub(0, glb.le32(off), "GLB: a chunk");
+            const uint32_t ctype = glb.le32(off + 4);
+            if (ctype == 0x4E4F534Au) j = JsonParser(chunk).parse();
+            else if (ctype == 0x004E4942u) { binChunk = chunk; haveBin = true; }
+            off += 8 + chunk.size;
+        }
     }
     Json j;
 
-    const std::string& buffer(size_t i)
+    Bytes buffer(size_t i)
     {
         auto it = buffers.find(i);
         if (it != buffers.end()) return it->second;
         const Json& b = j.at("buffers").at(i);
         if (!b.has("uri")) { if (!haveBin) throw std::runtime_error("glTF: buffer without uri and no BIN chunk"); return buffers[i] = binChunk; }
-        const std::string& uri = b.at("uri").str;
-        if (!uri.compare(0, 5, "data:")) return buffers[i] = base64_decode(uri.substr(uri.find(',') + 1));
-        return buffers[i] = read_file(resolve(dir, uri));
+        return buffers[i] = owned.emplace_back(read_uri(dir, b.at("uri").string()));
+    }
+    // the bytes of a bufferView: inside its buffer
+    Bytes view(const Json& v, const char* what)
+    {
+        const Bytes b = buffer(v.at("buffer").index(j.at("buffers").size()));
+        return b.sub(v.uint("byteOffset", 0, b.size), v.at("byteLength").uint(b.size), what);
     }
     // element (i, c) of an accessor as double (integers as they are; normalised integers divided by their maximum, in float like ingest.py)
     struct Accessor { const uint8_t* data; size_t stride, count; int ncomp, ctype; bool normalized; };
-    Accessor accessor(size_t ai)
+    // validated here, once: [data, data + (count - 1) * stride + element size) lies inside the accessor's bufferView
+    Accessor accessor(const Json& index)
     {
-        const Json& a = j.at("accessors").at(ai);
-        const Json& v = j.at("bufferViews").at((size_t)a.at("bufferView").num);
-        const std::string& b = buffer((size_t)v.at("buffer").num);
+        const Json& a = j.at("accessors").pick(index);
+        const Json& v = j.at("bufferViews").pick(a.at("bufferView"));
+        const Bytes b = view(v, "glTF: the bufferView of an accessor");
         Accessor r;
-        r.ctype = (int)a.at("componentType").num;
-        const std::string& t = a.at("type").str;
+        r.ctype = (int)a.at("componentType").uint(0xFFFF);
+        const std::string& t = a.at("type").string();
         r.ncomp = t == "SCALAR" ? 1 : t == "VEC2" ? 2 : t == "VEC3" ? 3 : t == "VEC4" ? 4 : t == "MAT4" ? 16 : 0;
         if (!r.ncomp) throw std::runtime_error("glTF: accessor type " + t);
-        const size_t elem = (size_t)component_size(r.ctype) * r.ncomp, vstride = (size_t)v.number("byteStride", 0);
+        const size_t elem = (size_t)component_size(r.ctype) * r.ncomp, vstride = v.uint("byteStride", 0, 252);     // (252: glTF's limit)
         r.stride = (vstride == 0 || vstride == elem) ? elem : vstride;
-        r.count = (size_t)a.at("count").num;
-        const size_t off = (size_t)v.number("byteOffset", 0) + (size_t)a.number("byteOffset", 0);
-        if (off + (r.count ? (r.count - 1) * r.stride + elem : 0) > b.size()) throw std::runtime_error("glTF: accessor reaches beyond its buffer");
-        r.data = (const uint8_t*)b.data() + off;
+        r.count = a.at("count").uint(b.size);                             // (an element has at least one byte)
+        const size_t extent = r.count ? add(mul(r.count - 1, r.stride), elem) : 0;
+        r.data = b.sub(a.uint("byteOffset", 0, b.size), extent, "glTF: an accessor in its bufferView").data;
         const Json* n = a.find("normalized");
         r.normalized = n && n->kind == Json::Bool && n->b;
         return r;
@@ -561,30 +653,22 @@ public:
         return a.normalized ? (double)((float)v / maxv) : v;
     }
 
-    // the encoded bytes of image ii (data: / file uri, or a buffer view)
-    std::string image_bytes(size_t ii)
+    const Json& image(const Json& index) const { return j.at("images").pick(index); }
+    // the encoded bytes of an image: a view of its bufferView, or of hold, which receives what a data: / file uri names
+    Bytes image_bytes(const Json& im, std::string& hold)
     {
-        const Json& im = j.at("images").at(ii);
-        if (im.has("uri")) {
-            const std::string& uri = im.at("uri").str;
-            return !uri.compare(0, 5, "data:") ? base64_decode(uri.substr(uri.find(',') + 1)) : read_file(resolve(dir, uri));
-        }
-        const Json& v = j.at("bufferViews").at((size_t)im.at("bufferView").num);
-        const std::string& b = buffer((size_t)v.at("buffer").num);
-        const size_t off = (size_t)v.number("byteOffset", 0), len = (size_t)v.at("byteLength").num;
-        if (off + len > b.size()) throw std::runtime_error("glTF: image reaches beyond its buffer");
-        return b.substr(off, len);
+        if (im.has("uri")) return hold = read_uri(dir, im.at("uri").string());
+        return view(j.at("bufferViews").pick(im.at("bufferView")), "glTF: the bufferView of an image");
     }
 
     // a DDS image by its mime type, its file name or its first four bytes
-    bool image_is_dds(size_t ii, const std::string& bytes)
+    static bool image_is_dds(const Json& im, Bytes bytes)
     {
-        const Json& im = j.at("images").at(ii);
-        if (im.has("mimeType") && im.at("mimeType").str == "image/vnd-ms.dds") return true;
+        if (im.has("mimeType") && im.at("mimeType").string() == "image/vnd-ms.dds") return true;
         if (im.has("uri")) {
-            std::string uri = im.at("uri").str;
+            const std::string& uri = im.at("uri").string();
             if (uri.compare(0, 5, "data:") && uri.size() >= 4) {
-                std::string tail = uri.substr(uri.size() - 4);
+                std::string tail(uri.end() - 4, uri.end());
                 for (char& c : tail) c = (char)std::tolower((unsigned char)c);
                 if (tail == ".dds") return true;
             }
@@ -593,8 +677,9 @@ public:
     }
 
 private:
-    std::string dir, jsonText, binChunk; bool haveBin = false;
-    std::map<size_t, std::string> buffers;
+    const std::string dir, raw;                                             // raw: the file; the BIN chunk and the views into it point here
+    Bytes binChunk; bool haveBin = false;
+    std::map<size_t, Bytes> buffers; std::deque<std::string> owned;         // owned: buffers that a uri names (a deque never moves them)
 };
 
 // [DirectXMesh spec] ComputeTangentFrame (tangent output only): same operations in the same order as ingest.py's compute_tangents
@@ -628,11 +713,11 @@ inline std::vector<std::array<double, 3>> compute_tangents(const std::vector<std
 // glTF column-vector local matrix of a node
 inline M4 node_matrix(const Json& node)
 {
-    if (node.has("matrix")) { M4 c{}; const Json& m = node.at("matrix"); for (int i = 0; i < 16; i++) c.m[i / 4][i % 4] = m.at((size_t)i).num; return transpose(c); }   // column-major list
+    if (node.has("matrix")) { M4 c{}; const Json& m = node.at("matrix"); for (int i = 0; i < 16; i++) c.m[i / 4][i % 4] = m.at((size_t)i).real(); return transpose(c); }   // column-major list
     M4 t = identity(), r = identity(), s = identity();
-    if (node.has("translation")) for (int k = 0; k < 3; k++) t.m[k][3] = node.at("translation").at((size_t)k).num;
-    if (node.has("rotation")) { const Json& q = node.at("rotation"); r = transpose(matrix_from_quaternion(q.at(0).num, q.at(1).num, q.at(2).num, q.at(3).num)); }
-    if (node.has("scale")) for (int k = 0; k < 3; k++) s.m[k][k] = node.at("scale").at((size_t)k).num;
+    if (node.has("translation")) for (int k = 0; k < 3; k++) t.m[k][3] = node.at("translation").at((size_t)k).real();
+    if (node.has("rotation")) { const Json& q = node.at("rotation"); r = transpose(matrix_from_quaternion(q.at(0).real(), q.at(1).real(), q.at(2).real(), q.at(3).real())); }
+    if (node.has("scale")) for (int k = 0; k < 3; k++) s.m[k][k] = node.at("scale").at((size_t)k).real();
     return mul(mul(t, r), s);
 }
 
@@ -641,18 +726,19 @@ inline std::vector<std::shared_ptr<MeshNode>> load_model(const std::string& path
 {
     Asset asset(path);
     const Json& j = asset.j;
-    std::map<std::pair<size_t, bool>, std::shared_ptr<Texture>> textureCache;          // (image, forced sRGB) -> texture; nullptr: not decodable here
+    std::map<std::pair<const Json*, bool>, std::shared_ptr<Texture>> textureCache;          // (image, forced sRGB) -> texture; nullptr: not decodable here
     auto texture_for = [&](const Json& info, bool forceSrgb) -> std::shared_ptr<Texture> {
-        const Json& tex = j.at("textures").at((size_t)info.at("index").num);
+        const Json& tex = j.at("textures").pick(info.at("index"));
         const Json* ext = tex.find("extensions");
         const Json* msft = ext ? ext->find("MSFT_texture_dds") : nullptr;                // the DDS image wins over the PNG (GLTFHelpers.ixx:87-90,103,451)
-        const size_t src = (size_t)(msft && msft->has("source") ? msft->at("source") : tex.at("source")).num;
-        const auto key = std::make_pair(src, forceSrgb);
+        const Json& im = asset.image(msft && msft->has("source") ? msft->at("source") : tex.at("source"));
+        const auto key = std::make_pair(&im, forceSrgb);
         auto it = textureCache.find(key);
         if (it != textureCache.end()) return it->second;
         std::shared_ptr<Texture> t;
-        const std::string bytes = asset.image_bytes(src);
-        if (asset.image_is_dds(src, bytes)) {                              // forceSRGB: a UNORM DDS in these slots gets the _SRGB format (TextureHelpers.ixx:68)
+        std::string hold;
+        const Bytes bytes = asset.image_bytes(im, hold);
+        if (Asset::image_is_dds(im, bytes)) {                              // forceSRGB: a UNORM DDS in these slots gets the _SRGB format (TextureHelpers.ixx:68)
             try {
                 DdsImage dds = read_dds(bytes);
                 if (forceSrgb) dds.Format = dds.Format == PT_FORMAT_R8G8B8A8_UNORM ? (uint32_t)PT_FORMAT_R8G8B8A8_UNORM_SRGB : dds.Format == PT_FORMAT_BC1_UNORM ? (uint32_t)PT_FORMAT_BC1_UNORM_SRGB
@@ -666,13 +752,14 @@ inline std::vector<std::shared_ptr<MeshNode>> load_model(const std::string& path
         return textureCache[key] = t;
     };
     auto process_primitive = [&](const Json& prim, MeshData& mesh) -> bool {
-        if ((int)prim.number("mode", 4) != 4 || !prim.has("attributes") || !prim.at("attributes").has("POSITION") || !prim.has("indices")) return false;   // :150-152,169-171,191-193
+        if (prim.uint("mode", 4, 0xFFFF) != 4 || !prim.has("attributes") || !prim.at("attributes").has("POSITION") || !prim.has("indices")) return false;   // :150-152,169-171,191-193
         const Json& attrs = prim.at("attributes");
-        const Asset::Accessor pa = asset.accessor((size_t)attrs.at("POSITION").num);
+        const Asset::Accessor pa = asset.accessor(attrs.at("POSITION"));
         if (pa.ncomp < 3) throw std::runtime_error("glTF: POSITION is not a VEC3");
         std::vector<std::array<float, 3>> pos(pa.count);
         for (size_t i = 0; i < pa.count; i++) for (int k = 0; k < 3; k++) pos[i][k] = (float)Asset::element(pa, i, k);
-        const Asset::Accessor ia = asset.accessor((size_t)prim.at("indices").num);
+        const Asset::Accessor ia = asset.accessor(prim.at("indices"));
+        if (ia.ctype != 5121 && ia.ctype != 5123 && ia.ctype != 5125) throw std::runtime_error("glTF: indices are not unsigned integers");   // (so the conversion below is exact)
         std::vector<uint32_t> idx(ia.count);
         for (size_t i = 0; i < ia.count; i++) { idx[i] = (uint32_t)Asset::element(ia, i, 0); if (idx[i] >= pa.count) throw std::runtime_error("glTF: vertex index beyond the POSITION accessor"); }
         if (flipWindingOrder) for (size_t i = 0; i < idx.size() / 2; i++) std::swap(idx[i], idx[idx.size() - 1 - i]);        // slot count-1-i <- index i (:179)
@@ -680,7 +767,7 @@ inline std::vector<std::shared_ptr<MeshNode>> load_model(const std::string& path
         for (int s = 0; s < 2; s++) {
             const std::string name = "TEXCOORD_" + std::to_string(s);
             if (!attrs.has(name)) continue;
-            const Asset::Accessor ua = asset.accessor((size_t)attrs.at(name).num);
+            const Asset::Accessor ua = asset.accessor(attrs.at(name));
             if (ua.count != pa.count || ua.ncomp < 2) throw std::runtime_error("glTF: " + name + " does not match POSITION");
             uv[s].resize(ua.count);
             for (size_t i = 0; i < ua.count; i++) for (int k = 0; k < 2; k++) uv[s][i][k] = (float)Asset::element(ua, i, k);
@@ -688,7 +775,7 @@ inline std::vector<std::shared_ptr<MeshNode>> load_model(const std::string& path
         }
         std::vector<std::array<float, 3>> nrm; std::vector<std::array<double, 3>> tan;
         if (attrs.has("NORMAL")) {
-            const Asset::Accessor na = asset.accessor((size_t)attrs.at("NORMAL").num);
+            const Asset::Accessor na = asset.accessor(attrs.at("NORMAL"));
             if (na.count != pa.count || na.ncomp < 3) throw std::runtime_error("glTF: NORMAL does not match POSITION");
             nrm.resize(na.count);
             for (size_t i = 0; i < na.count; i++) for (int k = 0; k < 3; k++) nrm[i][k] = (float)Asset::element(na, i, k);
@@ -712,28 +799,28 @@ inline std::vector<std::shared_ptr<MeshNode>> load_model(const std::string& path
             else std::memcpy(mesh.Indices.data() + 4 * i, &idx[i], 4);
         }
         if (prim.has("material")) {
-            const Json& m = j.at("materials").at((size_t)prim.at("material").num);
+            const Json& m = j.at("materials").pick(prim.at("material"));
             static const Json empty = [] { Json e; e.kind = Json::Object; return e; }();
             const Json& pbr = m.has("pbrMetallicRoughness") ? m.at("pbrMetallicRoughness") : empty;
             const Json& ext = m.has("extensions") ? m.at("extensions") : empty;
             PtMaterial mat = default_material();
-            if (pbr.has("baseColorFactor")) for (int k = 0; k < 4; k++) mat.BaseColor[k] = (float)pbr.at("baseColorFactor").at((size_t)k).num;
+            if (pbr.has("baseColorFactor")) for (int k = 0; k < 4; k++) mat.BaseColor[k] = pbr.at("baseColorFactor").at((size_t)k).f32();
             else for (int k = 0; k < 4; k++) mat.BaseColor[k] = 1.0f;
-            mat.EmissiveStrength = ext.has("KHR_materials_emissive_strength") ? (float)ext.at("KHR_materials_emissive_strength").number("emissiveStrength", 1.0) : 1.0f;
-            for (int k = 0; k < 3; k++) mat.EmissiveColor[k] = m.has("emissiveFactor") ? (float)m.at("emissiveFactor").at((size_t)k).num : 0.0f;
-            mat.Metallic = (float)pbr.number("metallicFactor", 1.0);
-            mat.Roughness = (float)pbr.number("roughnessFactor", 1.0);
-            mat.IOR = ext.has("KHR_materials_ior") ? (float)ext.at("KHR_materials_ior").number("ior", 1.5) : 1.5f;
-            const std::string am = m.has("alphaMode") ? m.at("alphaMode").str : "OPAQUE";
+            mat.EmissiveStrength = ext.has("KHR_materials_emissive_strength") ? ext.at("KHR_materials_emissive_strength").f32("emissiveStrength", 1.0) : 1.0f;
+            for (int k = 0; k < 3; k++) mat.EmissiveColor[k] = m.has("emissiveFactor") ? m.at("emissiveFactor").at((size_t)k).f32() : 0.0f;
+            mat.Metallic = pbr.f32("metallicFactor", 1.0);
+            mat.Roughness = pbr.f32("roughnessFactor", 1.0);
+            mat.IOR = ext.has("KHR_materials_ior") ? ext.at("KHR_materials_ior").f32("ior", 1.5) : 1.5f;
+            const std::string am = m.has("alphaMode") ? m.at("alphaMode").string() : "OPAQUE";
             mat.AlphaMode = am == "MASK" ? 1u : am == "BLEND" ? 2u : 0u;
-            mat.AlphaCutoff = (float)m.number("alphaCutoff", 0.5);
+            mat.AlphaCutoff = m.f32("alphaCutoff", 0.5);
             const Json* tr = ext.find("KHR_materials_transmission");
-            if (tr && tr->kind == Json::Object) mat.Transmission = (float)tr->number("transmissionFactor", 0.0);
+            if (tr && tr->kind == Json::Object) mat.Transmission = tr->f32("transmissionFactor", 0.0);
             mesh.Material = mat; mesh.HasMaterial = true;
             if (mesh.HasUV[0] || mesh.HasUV[1]) {                          // :370-428
                 auto slot = [&](TextureSlot k, const char* name, const Json* info, bool srgb) {
                     if (!info || info->kind != Json::Object) return;
-                    const int tc = (int)info->number("texCoord", 0);
+                    const size_t tc = info->uint("texCoord", 0, UINT32_MAX);   // any set is valid glTF; this host keeps two
                     if (tc >= 2 || !mesh.HasUV[tc]) return;
                     if (auto t = texture_for(*info, srgb)) { mesh.Textures[k] = t; mesh.TextureCoordinateIndex[k] = (uint32_t)tc; }
                     else mesh.SkippedTextures.push_back(name);
@@ -748,22 +835,35 @@ inline std::vector<std::shared_ptr<MeshNode>> load_model(const std::string& path
     };
 
     std::vector<std::shared_ptr<MeshNode>> out;
-    const Json& scene = j.at("scenes").at((size_t)j.number("scene", 0));
-    std::function<void(size_t, const M4&)> visit = [&](size_t ni, const M4& parent) {
-        const Json& node = j.at("nodes").at(ni);
+    const Json& scene = j.at("scenes").at(j.uint("scene", 0, Json::kMaxUint));
+    // depth first, children in file order, on an explicit stack (a chain of nodes may be as long as the file allows). glTF wants a strict
+    // tree: a node reached a second time, through a cycle or through a second parent, is refused -- shared children could repeat a subtree
+    // exponentially often.
+    static const std::vector<Json> none;
+    const std::vector<Json>& nodes = j.has("nodes") ? j.at("nodes").items() : none;
+    std::vector<bool> visited(nodes.size(), false);
+    std::vector<std::pair<size_t, M4>> pending;                            // (node, its parent's global matrix)
+    auto push = [&](const Json& list, const M4& parent) {
+        for (size_t k = list.items().size(); k--;) pending.emplace_back(list.items()[k].index(nodes.size()), parent);
+    };
+    if (scene.has("nodes")) push(scene.at("nodes"), identity());
+    while (!pending.empty()) {
+        const auto [ni, parent] = pending.back(); pending.pop_back();
+        if (visited[ni]) throw std::runtime_error("glTF: node " + std::to_string(ni) + " is reached twice (a cycle, or a second parent)");
+        visited[ni] = true;
+        const Json& node = nodes[ni];
         const M4 m = mul(parent, node_matrix(node));
         if (node.has("mesh")) {
-            const Json& mj = j.at("meshes").at((size_t)node.at("mesh").num);
+            const Json& mj = j.at("meshes").pick(node.at("mesh"));
             if (mj.has("primitives") && mj.at("primitives").size()) {
                 auto mn = std::make_shared<MeshNode>();
-                for (const Json& p : mj.at("primitives").arr) { MeshData md; if (process_primitive(p, md)) mn->Meshes.push_back(std::move(md)); }
+                for (const Json& p : mj.at("primitives").items()) { MeshData md; if (process_primitive(p, md)) mn->Meshes.push_back(std::move(md)); }
                 mn->GlobalTransform = transpose(m);                       // the column-vector global matrix reinterpreted as a row-vector Matrix
                 out.push_back(mn);
             }
         }
-        if (node.has("children")) for (const Json& c : node.at("children").arr) visit((size_t)c.num, m);
-    };
-    if (scene.has("nodes")) for (const Json& n : scene.at("nodes").arr) visit((size_t)n.num, identity());
+        if (node.has("children")) push(node.at("children"), m);
+    }
     return out;
 }
 
@@ -791,19 +891,19 @@ inline Scene load_scene(const std::string& path)
     const Json* env = j.find("EnvironmentLight");
     if (env && env->kind == Json::Object) {
         if (const Json* col = env->find("Color"); col && col->kind == Json::Object) {
-            sc.EnvironmentLightColor[0] = (float)col->number("R", 0); sc.EnvironmentLightColor[1] = (float)col->number("G", 0);
-            sc.EnvironmentLightColor[2] = (float)col->number("B", 0); sc.EnvironmentLightColor[3] = (float)col->number("A", -1);
+            sc.EnvironmentLightColor[0] = col->f32("R", 0); sc.EnvironmentLightColor[1] = col->f32("G", 0);
+            sc.EnvironmentLightColor[2] = col->f32("B", 0); sc.EnvironmentLightColor[3] = col->f32("A", -1);
         } else sc.EnvironmentLightColor[3] = -1;
         store_float3x4(rotation_from_json(env->find("Rotation")), sc.EnvironmentLightTransform);     // App.cpp:1019
-        if (env->has("Texture")) sc.EnvironmentLightTexture = resolve(base, env->at("Texture").str);
+        if (env->has("Texture")) sc.EnvironmentLightTexture = resolve(base, env->at("Texture").string());
     }
     std::map<std::string, std::string> models;
-    if (const Json* m = j.find("Models"); m && m->kind == Json::Object) for (auto& kv : m->obj) models[kv.first] = resolve(base, kv.second.str);
+    if (const Json* m = j.find("Models"); m && m->kind == Json::Object) for (auto& kv : m->obj) models[kv.first] = resolve(base, kv.second.string());
     std::map<std::string, std::vector<std::shared_ptr<MeshNode>>> loaded;
     M4 zflip = identity(); zflip.m[2][2] = -1.0;
     if (const Json* ros = j.find("RenderObjects"); ros && ros->kind == Json::Array)
         for (const Json& ro : ros->arr) {
-            const std::string model = ro.has("Model") ? ro.at("Model").str : "", name = ro.has("Name") ? ro.at("Name").str : "";
+            const std::string model = ro.has("Model") ? ro.at("Model").string() : "", name = ro.has("Name") ? ro.at("Name").string() : "";
             if (!model.empty() && !models.count(model))                    // MyScene.ixx:57-70
                 throw std::runtime_error(path + ": " + (name.empty() ? std::string("Unnamed RenderObject") : "RenderObject " + name) + ": Models " + model + " not found");
             if (model.empty()) continue;

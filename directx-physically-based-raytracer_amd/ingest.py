@@ -16,12 +16,14 @@ reference (GLTFHelpers.ixx:87-90,103,451) -- is read by bc.read_dds and its BC1 
 outside those formats is listed in Mesh.skipped_textures and the material keeps its factors. EXR/HDR stay out of scope (TextureHelpers.ixx).
 [DirectXMesh spec] ComputeTangentFrame is an un-vendored dependency: restated as Lengyel's per-vertex accumulation with
 Gram-Schmidt against the normal.
+What both hosts accept of a file is stated in DESIGN.md section 2 ("what the hosts accept"); host/pt_ingest.hpp refuses the same files.
 """
 import base64
 import io
 import json
 import math
 import os
+import re
 import struct
 
 import numpy as np
@@ -32,6 +34,27 @@ from . import scenes as S
 
 _COMPONENT = {5120: np.int8, 5121: np.uint8, 5122: np.int16, 5123: np.uint16, 5125: np.uint32, 5126: np.float32}
 _NCOMP = {"SCALAR": 1, "VEC2": 2, "VEC3": 3, "VEC4": 4, "MAT4": 16}
+MAX_JSON_DEPTH = 128                                                      # kMaxJsonDepth of host/pt_ingest.hpp
+_JSON_STRING_OR_BRACKET = re.compile(rb'"(?:[^"\\]|\\.)*"|[\[{\]}]')
+
+
+def _index(v, n):
+    """A file value that indexes a list of n entries (or states a size below n): a non-negative int below n, nothing else. Python
+    itself would take -1 for the last entry, True for 1 and a float wherever it only slices."""
+    if type(v) is not int or not 0 <= v < n:
+        raise ValueError(f"{v!r} where an integer from 0 to {n - 1} is expected")
+    return v
+
+
+def _loads(text):
+    """json.loads of a file's text, refusing arrays and objects nested deeper than MAX_JSON_DEPTH (the C++ reader recurses per level)."""
+    depth = 0
+    for m in _JSON_STRING_OR_BRACKET.finditer(text):
+        c = m.group()[:1]
+        depth += 1 if c in b"[{" else -1 if c in b"]}" else 0
+        if depth > MAX_JSON_DEPTH:
+            raise ValueError(f"JSON: arrays and objects nested deeper than {MAX_JSON_DEPTH}")
+    return json.loads(text.decode("utf-8"))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -134,22 +157,28 @@ class _Asset:
         self.bin_chunk = None
         if raw[:4] == b"glTF":
             _, _, length = struct.unpack_from("<III", raw, 0)
+            if not 12 <= length <= len(raw):
+                raise ValueError("GLB: the length in the header does not lie inside the file")
             off = 12
             while off < length:
+                if length - off < 8:
+                    raise ValueError("GLB: a chunk header reaches beyond the file")
                 clen, ctype = struct.unpack_from("<II", raw, off)
+                if clen > length - off - 8:
+                    raise ValueError("GLB: a chunk reaches beyond the file")
                 data = raw[off + 8: off + 8 + clen]
                 if ctype == 0x4E4F534A:
-                    self.j = json.loads(data.decode("utf-8"))
+                    self.j = _loads(data)
                 elif ctype == 0x004E4942:
                     self.bin_chunk = data
                 off += 8 + clen
         else:
-            self.j = json.loads(raw.decode("utf-8"))
+            self.j = _loads(raw)
         self.buffers = {}
 
     def buffer(self, i):
         if i not in self.buffers:
-            b = self.j["buffers"][i]
+            b = self.j["buffers"][_index(i, len(self.j["buffers"]))]
             uri = b.get("uri")
             if uri is None:
                 self.buffers[i] = self.bin_chunk
@@ -160,17 +189,17 @@ class _Asset:
         return self.buffers[i]
 
     def view_bytes(self, vi):
-        v = self.j["bufferViews"][vi]
+        v = self.j["bufferViews"][_index(vi, len(self.j["bufferViews"]))]
         b = self.buffer(v["buffer"])
-        off = v.get("byteOffset", 0)
-        return b[off: off + v["byteLength"]], v.get("byteStride", 0)
+        off = _index(v.get("byteOffset", 0), len(b) + 1)
+        return b[off: off + _index(v["byteLength"], len(b) - off + 1)], _index(v.get("byteStride", 0), 253)     # inside its buffer
 
     def accessor(self, ai):
-        a = self.j["accessors"][ai]
+        a = self.j["accessors"][_index(ai, len(self.j["accessors"]))]
         dt = np.dtype(_COMPONENT[a["componentType"]]); nc = _NCOMP[a["type"]]
-        count = a["count"]
         data, stride = self.view_bytes(a["bufferView"])
-        off = a.get("byteOffset", 0)
+        count = _index(a["count"], len(data) + 1)                         # frombuffer keeps the accessor inside its view
+        off = _index(a.get("byteOffset", 0), len(data) + 1)
         elem = dt.itemsize * nc
         if stride in (0, elem):
             arr = np.frombuffer(data, dt, count * nc, off).reshape(count, nc)
@@ -181,7 +210,7 @@ class _Asset:
         return arr
 
     def image_bytes(self, ii):
-        im = self.j["images"][ii]
+        im = self.j["images"][_index(ii, len(self.j["images"]))]
         if "uri" in im:
             uri = im["uri"]
             return base64.b64decode(uri.split(",", 1)[1]) if uri.startswith("data:") else open(os.path.join(self.dir, uri), "rb").read()
@@ -256,7 +285,7 @@ def load_model(path, flip_winding_order=True):
     tex_cache = {}
 
     def texture_for(info, force_srgb):
-        tex = j["textures"][info["index"]]
+        tex = j["textures"][_index(info["index"], len(j["textures"]))]
         dds = (tex.get("extensions") or {}).get("MSFT_texture_dds") or {}
         src = dds.get("source", tex.get("source"))                        # the DDS image wins over the PNG (GLTFHelpers.ixx:87-90,103,451)
         key = (src, force_srgb)
@@ -265,11 +294,16 @@ def load_model(path, flip_winding_order=True):
         return tex_cache[key]
 
     def process_primitive(prim):
-        if prim.get("mode", 4) != 4 or "POSITION" not in prim["attributes"] or "indices" not in prim:
+        if _index(prim.get("mode", 4), 65536) != 4 or "POSITION" not in prim["attributes"] or "indices" not in prim:
             return None                                                   # :150-152,169-171,191-193
         attrs = prim["attributes"]
         pos = asset.accessor(attrs["POSITION"]).astype(np.float32)
-        idx = asset.accessor(prim["indices"]).reshape(-1).astype(np.int64)
+        idx = asset.accessor(prim["indices"])
+        if idx.dtype.kind != "u":
+            raise ValueError("glTF: indices are not unsigned integers")
+        idx = idx.reshape(-1).astype(np.int64)
+        if idx.size and idx.max() >= len(pos):
+            raise ValueError("glTF: vertex index beyond the POSITION accessor")
         if flip_winding_order:
             idx = idx[::-1].copy()                                        # slot count-1-i <- index i (:179)
         indices = idx.astype(np.uint16 if idx.size <= 65535 else np.uint32)
@@ -285,7 +319,7 @@ def load_model(path, flip_winding_order=True):
         vb = S.make_vertices(pos, nrm, uvs[0], tan, uvs[1])
         mesh = S.Mesh(vb, indices, has_normals=nrm is not None, material=None, has_tangents=tan is not None, has_uv=tuple(has_uv))
         if "material" in prim:
-            m = j["materials"][prim["material"]]
+            m = j["materials"][_index(prim["material"], len(j["materials"]))]
             pbr = m.get("pbrMetallicRoughness", {})
             ext = m.get("extensions", {})
             mat = L.default_material()
@@ -308,7 +342,7 @@ def load_model(path, flip_winding_order=True):
                          "Normal": (m.get("normalTexture") if tan is not None else None, False)}
                 textures = {}
                 for slot, (info, srgb) in slots.items():
-                    if info is not None and info.get("texCoord", 0) < 2 and has_uv[info.get("texCoord", 0)]:
+                    if info is not None and _index(info.get("texCoord", 0), 2 ** 32) < 2 and has_uv[info.get("texCoord", 0)]:
                         t = texture_for(info, srgb)
                         if t is None:                                     # listed and skipped: the material keeps its factors
                             mesh.skipped_textures = (mesh.skipped_textures or []) + [slot]
@@ -318,21 +352,23 @@ def load_model(path, flip_winding_order=True):
         return mesh
 
     out = []
-    scene = j["scenes"][j.get("scene", 0)]
-
-    def visit(ni, parent):
-        node = j["nodes"][ni]
+    scene = j["scenes"][_index(j.get("scene", 0), len(j["scenes"]))]
+    nodes = j.get("nodes", [])
+    visited = set()
+    pending = [(ni, np.eye(4)) for ni in reversed(scene.get("nodes", []))]   # depth first, children in file order, without recursion
+    while pending:
+        ni, parent = pending.pop()
+        if _index(ni, len(nodes)) in visited:                             # glTF wants a strict tree
+            raise ValueError(f"glTF: node {ni} is reached twice (a cycle, or a second parent)")
+        visited.add(ni)
+        node = nodes[ni]
         m = parent @ _node_matrix(node)
         if "mesh" in node:
-            prims = j["meshes"][node["mesh"]].get("primitives", [])
+            prims = j["meshes"][_index(node["mesh"], len(j["meshes"]))].get("primitives", [])
             if prims:
                 meshes = [x for x in (process_primitive(p) for p in prims) if x is not None]
                 out.append((S.MeshNode(meshes), m.T.copy()))            # GlobalTransform reinterpreted as a row-vector Matrix
-        for c in node.get("children", []):
-            visit(c, m)
-
-    for ni in scene.get("nodes", []):
-        visit(ni, np.eye(4))
+        pending.extend((c, m) for c in reversed(node.get("children", [])))
     return out
 
 
