@@ -2,6 +2,13 @@
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this.
 PARITY STATUS: parity unpinned (no reference golden vectors exist; MathLib absent) -- see pt_oracle.h.
+
+The oracle and the kernels are one reading of the shaders written twice, so a mistake in that reading is shared. Stages pinned besides by
+an independent float64 restatement (numpy, tests/*ref.py), which the oracle itself must agree with: ray/triangle and traversal (isectref),
+BSDF (bsdfref), textures / materials / environment (texref), skinning (skinref), post-processing (postref), SHARC (sharcref), the DI
+passes (restirref and its siblings), the primary surface (surfaceref: or_gbuffer_render) and the untextured path estimator
+(pathref: or_raytrace_render; its IsDIEnabled half exists on the device only and is replayed there). Oracle-only remain: the BVH
+builder's choice of tree, the comm kernels, the textured estimator.
 """
 import ctypes as C
 import os
