@@ -17,6 +17,9 @@
 //                                     initial visibility (DIInitialSampling.hlsl:49-54), Raytraced bias correction
 //                                     (RAB_GetConservativeVisibility / RAB_GetTemporalConservativeVisibility), the final-visibility store and
 //                                     reuse and discardInvisibleSamples (DIFinalShading.hlsl:32-56)
+//   k_di_brdf_rays                 <- the BRDF candidates of initial sampling (pt_di_set_brdf_sampling): one all-lobe BSDF sample and one
+//                                     closest-hit walk per pixel and candidate, a 16-byte record each; k_di and k_di_initial_temporal with
+//                                     BRDF = true read the records and weight light and BRDF candidates by MIS
 // Source is where initial sampling draws its candidates from: DIPowerCDF (the prefix sum, the default) or DISampling (Uniform,
 // Power_RIS, ReGIR). Every kernel reads its surfaces with di_surface, draws with di_initial and shades with di_shadow_ray +
 // di_final_write.
@@ -76,9 +79,11 @@ __global__ __launch_bounds__(1024) void k_light_count(const InstanceSource* __re
     if (threadIdx.x == 0) start[n] = carry;
 }
 
-// one block per instance: its emissive triangles in (geometry, triangle) order
+// one block per instance: its emissive triangles in (geometry, triangle) order. first[object]: the list entry of the object's triangle 0
+// (the table is ~0u before the pass; instances that share an InstanceID leave the smallest entry)
 __global__ __launch_bounds__(256) void k_light_fill(const InstanceSource* __restrict__ src, const BlasEntry* __restrict__ table, const PtObjectData* __restrict__ objects,
-                                                    const HeapEntry* __restrict__ heap, const uint32_t* __restrict__ start, uint4* __restrict__ list)
+                                                    const HeapEntry* __restrict__ heap, const uint32_t* __restrict__ start, uint4* __restrict__ list,
+                                                    uint32_t* __restrict__ first, uint32_t objectCount)
 {
     const uint32_t i = blockIdx.x;
     if (src[i].mask == 0u) return;
@@ -89,6 +94,7 @@ __global__ __launch_bounds__(256) void k_light_fill(const InstanceSource* __rest
         if (!emissive(objects[o].Material)) continue;
         const uint32_t nt = geometry_triangles(objects[o], heap);
         for (uint32_t t = threadIdx.x; t < nt; t += 256u) list[at + t] = make_uint4(i, g, t, o);
+        if (threadIdx.x == 0 && o < objectCount) atomicMin(&first[o], at);
         at += nt;
     }
 }
@@ -199,6 +205,8 @@ struct DIArgs {
     FrameView fv; PtTextures tx; DIView view; float jitter[2];
     const float4* lights; const float* cdf; const float* total; uint32_t count;
     uint32_t frameIndex, samples, denoiser, lastPass, ext;
+    // BRDF candidates (pt_di_set_brdf_sampling); read only by the BRDF instantiations
+    const uint4* brdfRecords; const uint32_t* firstLight; uint32_t brdfSamples, objectCount; float brdfCutoff;   // firstLight[objectCount]
 };
 
 // first light whose inclusive prefix exceeds x: a light of zero power never qualifies. x >= total (rounding of u * total): the
@@ -216,11 +224,11 @@ PT_DEV uint32_t select_light(const float* __restrict__ cdf, uint32_t n, float x,
 }
 
 // Shade(lightSample) of RAB_Surface, RTXDIAppBridge.hlsli: all-lobe Evaluate times radiance / solid-angle pdf
-PT_DEV void shade_sample(const BSDFSample& bs, const SurfaceVectors& svec, const float w[3], uint32_t ext, v3 P, v3 V, v3 pos, v3 Le, float pdfSA, v3& dif, v3& spc)
+// pdf: the all-lobe EvaluatePDF of the direction (the BRDF candidates' MIS weight reads it; 0 where nothing is evaluated)
+PT_DEV void shade_sample(const BSDFSample& bs, const SurfaceVectors& svec, const float w[3], uint32_t ext, v3 P, v3 V, v3 pos, v3 Le, float pdfSA, v3& dif, v3& spc, float& pdf)
 {
-    dif = V3(0.0f, 0.0f, 0.0f); spc = V3(0.0f, 0.0f, 0.0f);
+    dif = V3(0.0f, 0.0f, 0.0f); spc = V3(0.0f, 0.0f, 0.0f); pdf = 0.0f;
     if (!(pdfSA > 0.0f)) return;
-    float pdf;
     bs.EvaluateAll(svec, normalize(pos - P), V, w, pdf, dif, spc, ext);
     const float inv = 1.0f / pdfSA;
     dif = V3(dif.x * Le.x * inv, dif.y * Le.y * inv, dif.z * Le.z * inv);
@@ -261,7 +269,9 @@ PT_DEV bool di_surface(const DIArgs& a, const DIView& view, size_t pi, uint32_t 
 
 // p-hat of light sample (li, U, V) at surface s (RAB_GetLightSampleTargetPdfForSurface): the luminance of the all-lobe Shade. The
 // sample's point is re-derived from the light record: Math::SampleTriangle with r1 = U, r2 = V. power: the record's Power.
-PT_DEV float di_target(const DIArgs& a, const DISurface& s, uint32_t li, float U, float V, v3& pos, v3& dif, v3& spc, float& power)
+// mis (BRDF candidates): the sample's solid-angle pdf, its all-lobe BSDF pdf and its distance.
+struct DIMisTerms { float pdfSA, pdfBrdf, dist; };
+PT_DEV float di_target(const DIArgs& a, const DISurface& s, uint32_t li, float U, float V, v3& pos, v3& dif, v3& spc, float& power, DIMisTerms* mis = nullptr)
 {
     const float4* L = a.lights + kLightRec16 * (size_t)li;
     const float4 l0 = L[0], l1 = L[1], l2 = L[2], l3 = L[3], l4 = L[4];
@@ -273,8 +283,10 @@ PT_DEV float di_target(const DIArgs& a, const DISurface& s, uint32_t li, float U
     const v3 dn = V3(d.x / len, d.y / len, d.z / len);
     const float cosL = fabsf(dot(dn, -V3(l3.x, l3.y, l3.z)));
     const float pdfSA = (1.0f / l0.w) * len * len / cosL;              // CalculateSolidAnglePDF
-    shade_sample(s.bs, s.svec, s.w, a.ext, s.P, s.V, pos, V3(l4.x, l4.y, l4.z), pdfSA, dif, spc);
+    float pdfBrdf;
+    shade_sample(s.bs, s.svec, s.w, a.ext, s.P, s.V, pos, V3(l4.x, l4.y, l4.z), pdfSA, dif, spc, pdfBrdf);
     power = l1.w;
+    if (mis) { mis->pdfSA = pdfSA; mis->pdfBrdf = pdfBrdf; mis->dist = len; }
     return ml_luminance(dif + spc);
 }
 
@@ -452,6 +464,7 @@ struct DIPowerCDF {
     PT_DEV DIEntries begin(const DIArgs&, const DISurface&, uint32_t, uint32_t, uint32_t&) const { return DIEntries{ nullptr, 0u }; }
     PT_DEV bool pick(const DIArgs& a, DIEntries, float r0, float total, uint32_t& li, float&) const { li = select_light(a.cdf, a.count, r0 * total, total); return true; }
     PT_DEV float pdf(float, float power, float total) const { return power / total; }
+    PT_DEV float light_pdf(const DIArgs&, float power, float total) const { return power / total; }     // of a light no draw of the source produced
 };
 
 // Uniform, Power_RIS or ReGIR (the mode is uniform over the grid). Power_RIS: the pixel's screen tile picks a light tile. ReGIR: three
@@ -501,12 +514,35 @@ struct DISampling {
         return li < a.count;
     }
     PT_DEV float pdf(float pv, float, float) const { return pv; }
+    // RAB_EvaluateLocalLightSourcePdf of a light that came out of no tile or cell: Uniform 1 / count, else power / total
+    PT_DEV float light_pdf(const DIArgs& a, float power, float total) const { return mode == PT_DI_LOCAL_LIGHT_UNIFORM ? 1.0f / (float)a.count : power / total; }
 };
 
 // LocalLightSamples candidates from a source, streaming RIS (RTXDI_StreamSample); the selected sample's shaded terms stay in registers
 struct DIInitial { float wsum, p; v3 dif, spc, pos; float u, v; uint32_t li; };
-template <typename Source>
-PT_DEV void di_initial(const DIArgs& a, const Source& source, const DISurface& s, uint32_t x, uint32_t y, float total, DIInitial& o)
+
+// ---- BRDF candidates (pt_di_set_brdf_sampling; DESIGN.md section 1, "BRDF candidates") -------------------------------------------------
+constexpr uint32_t kDIBrdfSalt = 0x44490008u;        // the BRDF candidates' stream: five draws per candidate, r0..r3 (Sample), r4 (the RIS coin)
+static_assert(sizeof(uint4) == 4u * PT_DI_BRDF_CANDIDATE_WORDS, "layout");
+// candidates of a pixel, the reservoir's M: light samples plus, in the BRDF instantiations, BRDF samples
+template <bool BRDF> PT_DEV uint32_t di_candidates(const DIArgs& a) { if constexpr (BRDF) return a.samples + a.brdfSamples; else return a.samples; }
+// how far a BRDF ray of pdf q reaches under BrdfCutoff c > 0
+PT_DEV float di_brdf_range(float cutoff, float q) { return sqrtf((1.0f / cutoff - 1.0f) * q); }
+// the pdf a sample of light-source pdf qL is weighted against with both techniques on: (N_L qL + N_B qB / pdfSA) / N, the BRDF pdf
+// counting as 0 beyond the cutoff range. (Never taken with N_B = 0: (N_L x) / N_L is not x.)
+PT_DEV float di_blended_pdf(const DIArgs& a, float qL, const DIMisTerms& m)
+{
+    const float nl = (float)a.samples, nb = (float)a.brdfSamples, n = (float)(a.samples + a.brdfSamples);
+    if (!(m.pdfSA > 0.0f) || !isfinite(m.pdfSA)) return nl * qL / n;
+    float qB = m.pdfBrdf;
+    if (a.brdfCutoff > 0.0f && m.dist > di_brdf_range(a.brdfCutoff, qB)) qB = 0.0f;
+    return (nl * qL + nb * qB / m.pdfSA) / n;
+}
+
+// BRDF = true: the RIS weight of a light candidate is target / blended pdf, and the pixel's BRDF records follow the light candidates into
+// the same reservoir, each a light sample (li, U, V) of source pdf light_pdf with the stream's fifth draw as its coin.
+template <bool BRDF = false, typename Source>
+PT_DEV void di_initial(const DIArgs& a, const Source& source, const DISurface& s, uint32_t x, uint32_t y, size_t pi, float total, DIInitial& o)
 {
     uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDISalt);
     o.wsum = 0.0f; o.p = 0.0f; o.u = 0.0f; o.v = 0.0f; o.li = ~0u;
@@ -519,11 +555,37 @@ PT_DEV void di_initial(const DIArgs& a, const Source& source, const DISurface& s
         const bool some = source.pick(a, src, r0, total, li, pv);
         v3 pos = V3(0, 0, 0), dif = V3(0, 0, 0), spc = V3(0, 0, 0);
         float power = 0.0f;
-        const float p = some ? di_target(a, s, li, r1, r2, pos, dif, spc, power) : 0.0f;    // an empty slot: weight 0, still counted in M
-        const float ris = p > 0.0f ? p / source.pdf(pv, power, total) : 0.0f;  // target / source pdf (light selection; the point is uniform in uv)
+        DIMisTerms mis;
+        const float p = some ? di_target(a, s, li, r1, r2, pos, dif, spc, power, BRDF ? &mis : nullptr) : 0.0f;    // an empty slot: weight 0, still counted in M
+        float ris;
+        if constexpr (BRDF) ris = p > 0.0f ? p / di_blended_pdf(a, source.pdf(pv, power, total), mis) : 0.0f;
+        else ris = p > 0.0f ? p / source.pdf(pv, power, total) : 0.0f;  // target / source pdf (light selection; the point is uniform in uv)
         o.wsum += ris;
         if (r3 * o.wsum < ris) { o.p = p; o.dif = dif; o.spc = spc; o.pos = pos; o.u = r1; o.v = r2; o.li = li; }
     }
+    if constexpr (BRDF) {
+        uint32_t brng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDIBrdfSalt);
+        for (uint32_t j = 0; j < a.brdfSamples; j++) {
+            rng_float(brng); rng_float(brng); rng_float(brng); rng_float(brng);
+            const float r4 = rng_float(brng);
+            const uint4 rec = a.brdfRecords[pi * a.brdfSamples + j];
+            if (rec.x >= a.count) continue;                                 // no light at the end of the ray: weight 0, counted in M
+            const float U = __uint_as_float(rec.y), V = __uint_as_float(rec.z);
+            v3 pos = V3(0, 0, 0), dif = V3(0, 0, 0), spc = V3(0, 0, 0);
+            float power = 0.0f;
+            DIMisTerms mis;
+            const float p = di_target(a, s, rec.x, U, V, pos, dif, spc, power, &mis);
+            const float ris = p > 0.0f ? p / di_blended_pdf(a, source.light_pdf(a, power, total), mis) : 0.0f;
+            o.wsum += ris;
+            if (r4 * o.wsum < ris) { o.p = p; o.dif = dif; o.spc = spc; o.pos = pos; o.u = U; o.v = V; o.li = rec.x; }
+        }
+    }
+}
+// W of the initial reservoir: (sum w / M) / target(y); with BRDF candidates sum w / (M target(y))
+template <bool BRDF> PT_DEV float di_initial_weight(const DIArgs& a, const DIInitial& i0)
+{
+    if constexpr (BRDF) return i0.wsum / ((float)(a.samples + a.brdfSamples) * i0.p);
+    else return i0.wsum / (float)a.samples / i0.p;
 }
 
 // the visibility ray every DI pass traces (CreateVisibilityRay with offset 1e-3): from P to pos, tmin 1e-3, tmax = max(0, dist - 2e-3).
@@ -574,7 +636,7 @@ PT_DEV void di_pixel(uint32_t& x, uint32_t& ly)
 }
 
 // The plain pass, no reuse: initial sampling from a candidate source, then final shading. One thread per local pixel.
-template <typename Source>
+template <typename Source, bool BRDF = false>
 __global__ __launch_bounds__(256) void k_di(DIArgs a, Source source, BlobView bv, AlphaContext ac, DeviceCounters* counters)
 {
     uint32_t x, ly; di_pixel(x, ly);
@@ -586,12 +648,61 @@ __global__ __launch_bounds__(256) void k_di(DIArgs a, Source source, BlobView bv
     const float total = *a.total;
     if (!(total > 0.0f) || !isfinite(total)) return;
     DIInitial i0;
-    di_initial(a, source, s, x, y, total, i0);
+    di_initial<BRDF>(a, source, s, x, y, pi, total, i0);
     if (!(i0.p > 0.0f)) return;
     __shared__ uint2 ldsStack[kLdsStackDepth * 256];
     float dist; v3 vis;
     di_shadow_ray(bv, ac, counters, ldsStack, s.P, i0.pos, dist, vis);
-    di_final_write(a, pi, dist, vis, i0.dif, i0.spc, i0.wsum / (float)a.samples / i0.p);   // W = (sum w / M) / target(y)
+    di_final_write(a, pi, dist, vis, i0.dif, i0.spc, di_initial_weight<BRDF>(a, i0));   // W = (sum w / M) / target(y)
+}
+
+// The BRDF candidates' rays, ahead of initial sampling: one thread per local pixel, a wave on an 8 x 8 square. Per candidate the five draws
+// of the stream, an all-lobe Sample as RAB_Surface::Sample takes it, the all-lobe pdf of the direction, and -- when there is a direction of
+// positive pdf -- one closest-hit walk (the renderer's rule: alpha test on non-opaque geometry) from (P, 1e-3) out to the cutoff range.
+// A hit on an emissive object becomes the light sample (first[object] + primitive, U, V) that Math::SampleTriangle maps back to the hit point:
+// with hit barycentrics (b1, b2), sqrt(U) = b1 + b2 and V = b2 / (b1 + b2). Every local pixel writes its records, the empty surface empty ones.
+// The walk's stack is di_shadow_ray's: kLdsStackDepth entries per lane in LDS, the rest spilled, overflows counted.
+__global__ __launch_bounds__(256) void k_di_brdf_rays(DIArgs a, uint4* __restrict__ records, BlobView bv, AlphaContext ac, DeviceCounters* counters)
+{
+    uint32_t x, ly; di_pixel(x, ly);
+    if (x >= a.fv.width || ly >= a.fv.localRows) return;                 // no barrier below
+    const uint32_t y = global_row(a.fv, ly);
+    const size_t pi = (size_t)ly * a.fv.width + x;
+    DISurface s;
+    const bool valid = di_surface(a, a.view, pi, x, y, s);
+    __shared__ uint2 ldsStack[kLdsStackDepth * 256];
+    uint2 spill[kStackSize - kLdsStackDepth];
+    GroupStack<kLdsStackDepth> stack; stack.init((PT_LDS_AS void*)ldsStack, spill);
+    BlobReader<false> blob; blob.p = bv.base;
+    TraceStats st; st.nodes = 0; st.tris = 0; st.overflow = 0;
+    uint32_t rng = ml_hash(rng_init(x, y, a.frameIndex) ^ kDIBrdfSalt);
+    for (uint32_t j = 0; j < a.brdfSamples; j++) {
+        float rnd[4];
+        rnd[0] = rng_float(rng); rnd[1] = rng_float(rng); rnd[2] = rng_float(rng); rnd[3] = rng_float(rng);   // GetFloat4
+        rng_float(rng);                                                   // r4: the coin, di_initial's
+        uint4 rec = make_uint4(~0u, 0u, 0u, 0u);
+        v3 L = V3(0.0f, 0.0f, 0.0f); int lobe = 0;
+        if (valid && s.bs.Sample(s.svec, s.V, s.w, rnd, L, lobe)) {
+            float q; v3 dif, spc;
+            s.bs.EvaluateAll(s.svec, L, s.V, s.w, q, dif, spc, a.ext);
+            if (q > 0.0f) {
+                rec.w = __float_as_uint(q);
+                const float tmax = a.brdfCutoff > 0.0f ? di_brdf_range(a.brdfCutoff, q) : 3.402823466e+38f;
+                const Hit h = trace_single<false, false, false>(blob, bv, ac, s.P, L, 1e-3f, tmax, stack, &st, nullptr);
+                if (h.inst != ~0u) {
+                    const uint32_t object = ac.instances[h.inst].instanceID + h.geom;
+                    const uint32_t first = object < a.objectCount ? a.firstLight[object] : ~0u;
+                    if (first != ~0u) {
+                        const float t = h.u + h.v;
+                        rec.x = first + h.prim;
+                        if (t != 0.0f) { rec.y = __float_as_uint(t * t); rec.z = __float_as_uint(h.v / t); }
+                    }
+                }
+            }
+        }
+        records[pi * a.brdfSamples + j] = rec;
+    }
+    if (st.overflow) atomicAdd(&counters->stackOverflows, st.overflow);
 }
 
 // ---- reservoir reuse (DITemporalResampling / DISpatialResampling; DESIGN.md section 1, "Reservoir reuse") --------------------------------
@@ -760,7 +871,7 @@ PT_DEV void di_boiling(const DIReuseArgs& r, bool valid, PtDIReservoir& res)
 // (3 waves), scratch 464 B / lane either way. Without VIS there is no loop, no ray and no group stack in LDS.
 // BIAS = kDIBiasPairwise: the fresh reservoir is the canonical domain and the history the one neighbour (n = 1); p at the previous surface
 // is taken for both samples, the weights and W come from the temporal step itself and nothing waits for a ray.
-template <bool TEMPORAL, uint32_t BIAS, uint32_t VIS, typename Source, typename... Extra>
+template <bool TEMPORAL, uint32_t BIAS, uint32_t VIS, bool BRDF, typename Source, typename... Extra>
 __global__ __launch_bounds__(256) void k_di_initial_temporal(DIReuseArgs r, Source source, Extra... extra)
 {
     constexpr bool BASIC = BIAS == kDIBiasBasic, PAIRWISE = BIAS == kDIBiasPairwise;
@@ -836,13 +947,13 @@ __global__ __launch_bounds__(256) void k_di_initial_temporal(DIReuseArgs r, Sour
         }
     };
     if (valid) {
-        res.M = a.samples;
+        res.M = di_candidates<BRDF>(a);
         const float total = *a.total;
         if (total > 0.0f && isfinite(total)) {
             DIInitial i0;
-            di_initial(a, source, s, x, y, total, i0);
+            di_initial<BRDF>(a, source, s, x, y, pi, total, i0);
             if (i0.p > 0.0f) {
-                res.LightIndex = i0.li; res.U = i0.u; res.V = i0.v; res.W = i0.wsum / (float)a.samples / i0.p; res.TargetPdf = i0.p;
+                res.LightIndex = i0.li; res.U = i0.u; res.V = i0.v; res.W = di_initial_weight<BRDF>(a, i0); res.TargetPdf = i0.p;
                 if constexpr (CARRY) { target = i0.pos; want = di_vis_args(extra...)->initial != 0u; }
             }
         }
@@ -857,7 +968,7 @@ __global__ __launch_bounds__(256) void k_di_initial_temporal(DIReuseArgs r, Sour
             if (want) { float dist; v3 vis; blocked = di_shadow_ray(va->bv, va->ac, va->counters, ldsStack, s.P, target, dist, vis); }
             want = false;
             if (trip == 1) { if (blocked) pPrev = 0.0f; continue; }
-            if (blocked) res = di_empty(a.samples);                               // initial visibility
+            if (blocked) res = di_empty(di_candidates<BRDF>(a));                               // initial visibility
             if (TEMPORAL && valid) temporal();
         }
     }
@@ -1053,7 +1164,10 @@ hipError_t ensure_light_list(Context& c, const SceneView& sv)
         if ((e = hipMemcpyAsync(&total, c.lightInstStart.data() + n, sizeof total, hipMemcpyDeviceToHost, c.stream)) != hipSuccess) return e;
         if ((e = hipStreamSynchronize(c.stream)) != hipSuccess) return e;
         if ((e = c.lightList.reserve(total)) != hipSuccess) return e;
-        if (total) k_light_fill<<<n, 256, 0, c.stream>>>(c.scene.instSource, c.scene.blasTable, sv.objects, sv.heap, c.lightInstStart.data(), c.lightList.data());
+        if ((e = c.lightFirst.reserve(c.objectCount)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(c.lightFirst.data(), 0xFF, sizeof(uint32_t) * c.objectCount, c.stream)) != hipSuccess) return e;
+        if (total) k_light_fill<<<n, 256, 0, c.stream>>>(c.scene.instSource, c.scene.blasTable, sv.objects, sv.heap, c.lightInstStart.data(), c.lightList.data(),
+                                                         c.lightFirst.data(), c.objectCount);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         c.lightCount = total;
     }
@@ -1303,7 +1417,8 @@ static int di_launch_reuse(Context& c, const DIArgs& a, const DISampling& ls, co
     va.maxDistance = vs.FinalVisibilityMaxDistance;
     di_with_source(ls, [&](auto source) {
         di_with_form(temporal, tb, tp, vis, tr, va, [&](auto T, auto B, auto V, auto... extra) {
-            k_di_initial_temporal<T(), B(), V(), decltype(source)><<<grid, 256, 0, c.stream>>>(r, source, extra...);
+            if (a.brdfSamples) k_di_initial_temporal<T(), B(), V(), true, decltype(source)><<<grid, 256, 0, c.stream>>>(r, source, extra...);
+            else k_di_initial_temporal<T(), B(), V(), false, decltype(source)><<<grid, 256, 0, c.stream>>>(r, source, extra...);
         });
     });
     API_HIP(&c, hipGetLastError());
@@ -1348,7 +1463,7 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
     API_HIP(&c, ensure_light_list(c, sv));
     const uint32_t n = c.lightCount;
     c.lightRecordCount = n;
-    c.diTileCount = 0; c.diCellCount = 0;
+    c.diTileCount = 0; c.diCellCount = 0; c.diBrdfCount = 0;
     if (!reuse || n == 0 || npix == 0) { c.diHistoryValid = false; c.diResCount = 0; }
     if (n == 0 || npix == 0) return PT_OK;
     const uint32_t nb = (n + kScanBlock - 1u) / kScanBlock;
@@ -1364,8 +1479,23 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
     a.frameIndex = s.FrameIndex; a.samples = s.LocalLightSamples; a.denoiser = s.Denoiser; a.lastPass = s.IsLastRenderPass; a.ext = s.ExtFlags;
     const AlphaContext ac = alpha_context(sv);
     const dim3 grid((fv.width + 15u) / 16u, (fv.localRows + 15u) / 16u);
+    if (c.diBrdf.BrdfSamples) {                                               // the BRDF candidates' rays, ahead of whichever pass draws the candidates
+        const size_t nrec = npix * c.diBrdf.BrdfSamples;
+        if (nrec > c.diBrdfRecords.capacity()) {
+            API_HIP(&c, hipStreamSynchronize(c.stream));
+            API_HIP(&c, c.diBrdfRecords.reserve(nrec));
+        }
+        a.brdfSamples = c.diBrdf.BrdfSamples; a.brdfCutoff = c.diBrdf.BrdfCutoff;
+        a.brdfRecords = c.diBrdfRecords.data(); a.firstLight = c.lightFirst.data(); a.objectCount = c.objectCount;
+        k_di_brdf_rays<<<grid, 256, 0, c.stream>>>(a, c.diBrdfRecords.data(), c.scene.blob, ac, c.counters.data());
+        API_HIP(&c, hipGetLastError());
+        c.diBrdfCount = (uint32_t)nrec;
+    }
     if (reuse) return di_launch_reuse(c, a, ls, prev, grid, ac);
-    di_with_source(ls, [&](auto source) { k_di<decltype(source)><<<grid, 256, 0, c.stream>>>(a, source, c.scene.blob, ac, c.counters.data()); });   // the plain pass
+    di_with_source(ls, [&](auto source) {                                     // the plain pass
+        if (a.brdfSamples) k_di<decltype(source), true><<<grid, 256, 0, c.stream>>>(a, source, c.scene.blob, ac, c.counters.data());
+        else k_di<decltype(source), false><<<grid, 256, 0, c.stream>>>(a, source, c.scene.blob, ac, c.counters.data());
+    });
     API_HIP(&c, hipGetLastError());
     return PT_OK;
 }
@@ -1467,6 +1597,27 @@ int pt_di_set_regir_layout(PtContext* ctx, const PtDIReGIRLayoutSettings* s)
     if (layout != c.diReGIRLayout) c.diHistoryValid = false;
     c.diReGIRLayout = layout;
     return PT_OK;
+}
+
+int pt_di_set_brdf_sampling(PtContext* ctx, uint32_t brdf_samples, float brdf_cutoff)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    API_ARG(&c, brdf_samples <= 8u, "brdf_samples must be 0..8");
+    API_ARG(&c, std::isfinite(brdf_cutoff) && brdf_cutoff >= 0.0f && brdf_cutoff < 1.0f, "brdf_cutoff must be finite and in [0, 1)");
+    Context::DIBrdfSettings v;
+    if (brdf_samples) { v.BrdfSamples = brdf_samples; v.BrdfCutoff = brdf_cutoff + 0.0f; }      // 0 samples: off whatever the cutoff; -0 is 0
+    if (v.BrdfSamples != c.diBrdf.BrdfSamples || v.BrdfCutoff != c.diBrdf.BrdfCutoff) c.diHistoryValid = false;
+    c.diBrdf = v;
+    return PT_OK;
+}
+
+int pt_di_download_brdf_candidates(PtContext* ctx, uint32_t* host_dst, uint32_t capacity, uint32_t* out_count)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    API_ARG(&c, out_count && (host_dst || capacity == 0), "out_count / host_dst is NULL");
+    return download_counted(c, c.diBrdfRecords.data(), c.diBrdfCount, 1u, (uint4*)host_dst, capacity, out_count);
 }
 
 int pt_di_regir_onion_table(uint32_t which, float* host_dst, uint32_t capacity, uint32_t* out_count)

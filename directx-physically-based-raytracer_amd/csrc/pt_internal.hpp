@@ -220,8 +220,14 @@ struct Context {
     PtDILightSamplingSettings diSampling{};
     DeviceBuffer<PtDIPresampledLight> diTiles, diCells;
     uint32_t diTileCount = 0, diCellCount = 0;        // entries the last render filled (0: not filled)
+    uint32_t diBrdfCount = 0;                         // ... and BRDF candidate records (diBrdfRecords below)
     uint32_t diReGIRLayout = 0;                       // pt_di_set_regir_layout: PT_DI_REGIR_LAYOUT_*
     DeviceBuffer<float> diOnion;                      // the Onion layout's tables (OnionTables), uploaded by the first Onion render
+    // BRDF candidates (pt_di_set_brdf_sampling): lightFirst[object] = the first list entry of an emissive object (~0u: not emissive), built with
+    // the light list; diBrdfRecords: the last render's candidates, BrdfSamples per local pixel
+    struct DIBrdfSettings { uint32_t BrdfSamples = 0; float BrdfCutoff = 0.0f; } diBrdf;
+    DeviceBuffer<uint32_t> lightFirst;
+    DeviceBuffer<uint4> diBrdfRecords;                // (li | ~0u, U, V, pdf of the ray)
 
     // post-processing (pt_post.hip): one slot per bloom stage, each the size of the level it writes (the bytes of the reference's two pyramids)
     PtPostProcessSettings post{}; bool havePost = false;

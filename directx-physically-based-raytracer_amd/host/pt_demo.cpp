@@ -2,13 +2,14 @@
 // reference-shaped operators of ptamd.hpp (GBufferGeneration / Raytracing / RaytracingHelpers), times it and
 // optionally dumps the radiance for the parity test (tests/test_host_cpp.py compares it with the oracle).
 //
-//   pt_demo [--width W] [--height H] [--spp S] [--bounces B] [--frames N] [--out file.bin] [--ranks R] [--di] [--di-samples N] [--restir [--restir-pairwise] [--restir-visibility [--restir-raytraced]]] [--sharc]
+//   pt_demo [--width W] [--height H] [--spp S] [--bounces B] [--frames N] [--out file.bin] [--ranks R] [--di] [--di-samples N] [--di-brdf-samples N [--di-brdf-cutoff C]] [--restir [--restir-pairwise] [--restir-visibility [--restir-raytraced]]] [--sharc]
 //           [--light-sampling cdf|uniform|power_ris|regir [--regir-layout grid|onion]]
 //           [--post] [--no-bloom] [--bloom-strength S] [--tone-map saturate|reinhard|aces] [--exposure E]
 //           [--hdr [--paper-white N] [--color-rotation hdtv_to_uhdtv|dci_p3_d65_to_uhdtv|hdtv_to_dci_p3_d65]]
 //           [--png file.png] [--out-display file.bin]
 //
 // --di: the direct-lighting pass between the G-buffer and the path tracer (App.cpp:1234-1308), LocalLightSamples = --di-samples (default 8);
+// --di-brdf-samples N adds N BRDF-sampled candidates per pixel, weighted by MIS against the light candidates (--di-brdf-cutoff C bounds their rays);
 // the path tracer then runs with IsDIEnabled (with Bounces 0 the DI pass is the last render pass and adds to Radiance).
 // --restir (with --di): temporal + spatial reservoir reuse at MyAppData's defaults; the Previous* G-buffer is swapped in before every
 // frame after the first (App.cpp:629-634). Unsharded only.
@@ -358,7 +359,7 @@ static std::vector<uint8_t> exchange_unique_id(uint32_t rank, const std::string&
 int main(int argc, char** argv)
 {
     uint32_t W = 1920, H = 1080, spp = 4, bounces = 8, frames = 10, ranks = 0, rank = 0, world = 1;
-    uint32_t diSamples = 8; bool di = false, restir = false, restirVisibility = false, restirRaytraced = false, restirPairwise = false;
+    uint32_t diSamples = 8, diBrdfSamples = 0; float diBrdfCutoff = 0.0f; bool di = false, restir = false, restirVisibility = false, restirRaytraced = false, restirPairwise = false;
     bool useSharc = false; uint32_t sharcDownscale = 4; float sceneScale = 50.0f;   // --sharc [--sharc-downscale N --scene-scale S]: frames through the radiance cache
     std::string out, idFile, scenePath, dumpPath, lightSampling = "cdf", regirLayout = "grid";
     bool post = false, bloom = true, hdr = false; float bloomStrength = 0.05f, exposure = 0.0f, paperWhite = 200.0f;
@@ -382,6 +383,7 @@ int main(int argc, char** argv)
         else if (k == "--ranks") ranks = atoi(v); else if (k == "--rank") rank = atoi(v);
         else if (k == "--world") world = atoi(v); else if (k == "--id-file") idFile = v;
         else if (k == "--di-samples") diSamples = atoi(v);
+        else if (k == "--di-brdf-samples") diBrdfSamples = atoi(v); else if (k == "--di-brdf-cutoff") diBrdfCutoff = (float)atof(v);
         else if (k == "--sharc-downscale") sharcDownscale = atoi(v); else if (k == "--scene-scale") sceneScale = (float)atof(v);
         else if (k == "--light-sampling") lightSampling = v; else if (k == "--regir-layout") regirLayout = v;
         else if (k == "--scene") scenePath = v; else if (k == "--dump-scene") dumpPath = v;
@@ -553,6 +555,12 @@ int main(int argc, char** argv)
             if (regirLayout != "grid" && lightSampling != "regir") throw std::invalid_argument("--regir-layout needs --light-sampling regir");
             directLighting.SetLightSampling(l);
         } else if (regirLayout != "grid") throw std::invalid_argument("--regir-layout needs --light-sampling regir");
+        if (diBrdfSamples || diBrdfCutoff != 0.0f) {                              // BRDF candidates in initial sampling (MyAppData BRDFSamples)
+            if (!di) throw std::invalid_argument("--di-brdf-samples needs --di");
+            if (!diBrdfSamples) throw std::invalid_argument("--di-brdf-cutoff needs --di-brdf-samples");
+            DirectLighting::BrdfSampling b; b.Samples = diBrdfSamples; b.Cutoff = diBrdfCutoff;
+            directLighting.SetBrdfSampling(b);
+        }
         PtDIPreviousTextures& prev = directLighting.PreviousTextures;
         if (restir) {
             prev.PreviousGeometricNormal = alloc(px_ * 4); prev.PreviousLinearDepth = alloc(px_ * 4); prev.PreviousBaseColorMetalness = alloc(px_ * 4);

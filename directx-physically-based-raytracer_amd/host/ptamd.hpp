@@ -280,6 +280,14 @@ struct DirectLighting {
         ThrowIfFailed(m_context, pt_di_set_regir_layout(m_context, &layout));
     }
 
+    // MyAppData ReSTIRDI.InitialSampling.BRDFSamples (Source/MyAppData.h:220-221; reference default 1) and the BRDF ray cutoff
+    // (pt_di_set_brdf_sampling). Samples 0, this library's default: no BRDF candidates.
+    struct BrdfSampling { uint32_t Samples = 0; float Cutoff = 0.0f; };
+    void SetBrdfSampling(const BrdfSampling& b)
+    {
+        ThrowIfFailed(m_context, pt_di_set_brdf_sampling(m_context, b.Samples, b.Cutoff));
+    }
+
     void SetConstants(const Settings& settings)
     {
         PtDISettings s{};

@@ -196,6 +196,23 @@ def di_regir_layout_settings(layout="grid"):
     return s
 
 
+DI_BRDF_SETTINGS = np.dtype({  # the arguments of pt_di_set_brdf_sampling (BRDF candidates of initial sampling) as one record
+    "names": ["BrdfSamples", "BrdfCutoff", "_pad"], "formats": ["<u4", "<f4", ("<u4", 2)], "offsets": [0, 4, 8], "itemsize": 16})
+
+DI_BRDF_CANDIDATE = np.dtype({  # the four words of a record of pt_di_download_brdf_candidates: one per pixel and BRDF candidate, pixel-major; LightIndex 0xFFFFFFFF = no light at the end of the ray
+    "names": ["LightIndex", "U", "V", "BrdfPdf"], "formats": ["<u4", "<f4", "<f4", "<f4"], "offsets": [0, 4, 8, 12], "itemsize": 16})
+
+
+def di_brdf_settings(samples=1, cutoff=0.0):
+    """pt_di_set_brdf_sampling's arguments with the reference's default (Source/MyAppData.h:220-221): BRDFSamples 1. cutoff in [0, 1): a BRDF ray ends at
+    sqrt((1 / cutoff - 1) * pdf); 0, this library's default, leaves the rays unbounded. The RTXDI SDK's own cutoff default is 1e-4 from
+    memory (the SDK is not in the reference tree, unpinned)."""
+    s = np.zeros((), DI_BRDF_SETTINGS)
+    s["BrdfSamples"] = samples
+    s["BrdfCutoff"] = cutoff
+    return s
+
+
 DI_PREVIOUS_TEXTURES = ["PreviousGeometricNormal", "PreviousLinearDepth", "PreviousBaseColorMetalness", "PreviousNormalRoughness",
                         "PreviousIOR", "PreviousTransmission"]   # PtDIPreviousTextures member order
 

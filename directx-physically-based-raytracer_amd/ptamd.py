@@ -28,7 +28,7 @@ EXPORTS = [
     "pt_di_set_constants", "pt_di_render", "pt_di_light_count", "pt_di_download_lights",
     "pt_di_set_resampling", "pt_di_render_with_history", "pt_di_reset_history", "pt_di_download_reservoirs",
     "pt_di_set_light_sampling", "pt_di_download_presampled", "pt_di_set_visibility", "pt_di_set_pairwise",
-    "pt_di_set_regir_layout", "pt_di_regir_onion_table",
+    "pt_di_set_regir_layout", "pt_di_regir_onion_table", "pt_di_set_brdf_sampling", "pt_di_download_brdf_candidates",
     "pt_post_set_constants", "pt_post_render", "pt_post_download_bloom",
     "pt_sharc_configure", "pt_sharc_set_constants", "pt_raytrace_render_sharc", "pt_sharc_reset", "pt_sharc_download",
     "pt_sharc_debug_keys", "pt_sharc_debug_query", "pt_sharc_download_update_paths", "pt_sharc_download_update_scatter",
@@ -187,6 +187,8 @@ def load_library():
         lib.pt_di_set_regir_layout.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_di_regir_onion_table.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.pt_di_download_presampled.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.pt_di_set_brdf_sampling.argtypes = [C.c_void_p, C.c_uint32, C.c_float]
+        lib.pt_di_download_brdf_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.pt_post_set_constants.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_post_render.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_post_download_bloom.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -725,6 +727,20 @@ class DirectLighting:
         self._regir_layout = np.array(settings).reshape(())
         self.ctx.check(self.ctx.lib.pt_di_set_regir_layout(self.ctx.handle, C.c_void_p(self._regir_layout.ctypes.data)))
 
+    def SetBrdfSampling(self, settings):
+        """layouts.di_brdf_settings (BrdfSamples, BrdfCutoff), or None: no BRDF candidates in initial sampling (0 samples). A changed
+        value resets the history; a refused one leaves the previous setting active."""
+        if settings is None:
+            self.ctx.check(self.ctx.lib.pt_di_set_brdf_sampling(self.ctx.handle, 0, 0.0))
+            return
+        s = np.array(settings).reshape(())
+        self.ctx.check(self.ctx.lib.pt_di_set_brdf_sampling(self.ctx.handle, int(s["BrdfSamples"]), float(s["BrdfCutoff"])))
+
+    def download_brdf_candidates(self):
+        """The BRDF candidates of the last Render (numpy layouts.DI_BRDF_CANDIDATE, [local pixels * BrdfSamples], pixel-major; empty
+        when that render drew none)."""
+        return _download_counted(self.ctx, self.ctx.lib.pt_di_download_brdf_candidates, L.DI_BRDF_CANDIDATE)
+
     def download_presampled(self, which):
         """which = 0: the Power_RIS tiles (128 x 1024, tile-major), 1: the ReGIR cells (cell-major; Grid: 4096 x 512, x fastest; Onion:
         2253 x 512 in the layout's cell order) of the last Render (numpy layouts.DI_PRESAMPLED_LIGHT; empty when that render did not
@@ -849,7 +865,7 @@ class Renderer:
         rank, world, band = getattr(ctx, "sharding", (0, 1, 16))
         self.local_rows = local_rows(height, rank, world, band)
         self.textures = alloc_textures(width, self.local_rows, scene_gpu.device, with_f32, with_denoiser_outputs)
-        self.di_history, self._rendered = di_history, False
+        self.di_history, self._rendered, self._di_brdf_set = di_history, False, False
         if di_history:                                                    # App.cpp:629-634: the DI pass's Previous* G-buffer
             for n in L.DI_PREVIOUS_TEXTURES:
                 self.textures[n] = self.textures[n[len("Previous"):]].clone()
@@ -868,8 +884,10 @@ class Renderer:
         self.constants["Flags"] = L.GBufferFlags.DefaultNoDenoiser        # App.cpp:1224 with Denoiser::None
 
     def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None, post=None, sharc=None, di_visibility=None, di_pairwise=None,
-               di_regir_layout=None):
-        """di_samples > 0: run the DI pass with that many candidates per pixel; set settings["IsDIEnabled"] to have the path tracer
+               di_regir_layout=None, di_brdf=None):
+        """di_brdf: layouts.di_brdf_settings for BRDF candidates in the DI pass's initial sampling, or None: none (the
+        setter is then called only to turn off what an earlier frame of this renderer turned on).
+        di_samples > 0: run the DI pass with that many candidates per pixel; set settings["IsDIEnabled"] to have the path tracer
         consume it (the textures need Diffuse / Specular: with_denoiser_outputs=True). di_reuse: PtDIResamplingSettings
         (layouts.di_resampling_settings) for reservoir reuse; temporal reuse needs di_history=True. With di_history the current and
         Previous* G-buffer textures are swapped before each frame after the first, so that after render() the current ones hold this
@@ -904,6 +922,9 @@ class Renderer:
             self.direct_lighting.SetVisibility(di_visibility)
             self.direct_lighting.SetPairwise(di_pairwise)
             self.direct_lighting.SetReGIRLayout(di_regir_layout)
+            if di_brdf is not None or self._di_brdf_set:
+                self.direct_lighting.SetBrdfSampling(di_brdf)
+                self._di_brdf_set = di_brdf is not None
             self.direct_lighting.Render(tlas)
         if int(np.array(settings).reshape(())["Bounces"]) > 0:            # App.cpp:1277
             self.raytracing.SetConstants(settings)

@@ -547,6 +547,30 @@ int  pt_di_set_regir_layout(PtContext* ctx, const PtDIReGIRLayoutSettings* setti
 int  pt_di_regir_onion_table(uint32_t which, float* host_dst, uint32_t capacity, uint32_t* out_count);
 
 /* ------------------------------------------------------------------------------------------
+ * BRDF candidates in initial sampling (the reference's BRDFSamples, Source/MyAppData.h:220-221; DESIGN.md section 1, "BRDF
+ * candidates", is the spec). On top of the LocalLightSamples light candidates a pixel draws BrdfSamples directions from its all-lobe
+ * BSDF (a stream of its own), traces one closest-hit ray each, and a ray that lands on an emissive triangle becomes a light sample of
+ * that triangle at the hit point. Light and BRDF candidates are weighted against each other by MIS and stream into one reservoir
+ * with M = LocalLightSamples + BrdfSamples; everything behind initial sampling is unchanged. Off by default, and with it off every
+ * output is what it was. The RTXDI SDK is not in the reference tree: the arithmetic is this library's own after the structure of
+ * RTXDI_SampleBrdf / RTXDI_LightBrdfMisWeight, unpinned.
+ * ------------------------------------------------------------------------------------------ */
+/* The entry points take plain values and words: the C ABI's list of structs stays the one it was (the ABI tests pin it).
+ * brdf_samples: BRDF candidates per pixel, 0..8 (reference default 1); 0: off, whatever brdf_cutoff holds within its range.
+ * brdf_cutoff: in [0, 1). > 0: a BRDF ray ends at sqrt((1 / brdf_cutoff - 1) * pdf), and the BRDF pdf of a sample beyond that distance
+ * counts as 0 in the MIS weight; 0: rays are unbounded.
+ * brdf_samples > 8 and a brdf_cutoff that is negative, not finite or >= 1 are refused and leave the previous setting active; a changed
+ * value resets the history. */
+int  pt_di_set_brdf_sampling(PtContext* ctx, uint32_t brdf_samples, float brdf_cutoff);
+/* The BRDF candidates of the last pt_di_render: local pixels x brdf_samples records, pixel-major, PT_DI_BRDF_CANDIDATE_WORDS 32-bit
+ * words each: [0] the light the ray landed on (0xFFFFFFFF: no direction, a miss, or not a light); [1], [2] the float bits of U, V, the
+ * hit point as a light sample, U = (b1 + b2)^2, V = b2 / (b1 + b2) (0 without a light); [3] the float bits of the all-lobe pdf of the
+ * drawn direction (0 when no direction was drawn). capacity and out_count are in records; out_count = 0 when that render drew none;
+ * synchronises. */
+#define PT_DI_BRDF_CANDIDATE_WORDS 4u
+int  pt_di_download_brdf_candidates(PtContext* ctx, uint32_t* host_dst, uint32_t capacity, uint32_t* out_count);
+
+/* ------------------------------------------------------------------------------------------
  * building blocks the reference's direct-lighting bridge calls on the same data
  * ------------------------------------------------------------------------------------------ */
 typedef struct PtRayDesc { float Origin[3]; float TMin; float Direction[3]; float TMax; } PtRayDesc;   /* HLSL RayDesc, 32 B */

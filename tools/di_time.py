@@ -5,13 +5,15 @@ the pass with temporal + spatial reservoir reuse at the reference's defaults (la
 passes, + final-visibility reuse, each with the final shadow rays per pixel counted from the downloaded reservoirs (a shaded reservoir
 whose visibility has age 0 was traced this frame, an older one was reused). --pairwise (with --reuse) times Basic and Pairwise bias
 correction (layouts.di_pairwise_settings, both passes) side by side at SpatialSamples 1 and 4, three alternating rounds each. --light-sampling times each listed local-light sampling mode (cdf, uniform, power_ris, regir, regir_onion: ReGIR over the Onion layout; one JSON line per mode). The workload
+--brdf-samples 0,1,2 times the plain pass with that many BRDF candidates per pixel (layouts.di_brdf_settings; 0 is the pass as it was): "brdf": {N_B: pass ms}; the BRDF-ray kernel's own share is the
+difference to N_B = 0 less what the candidates add to initial sampling, and `rocprofv3 --kernel-trace --stats -- python tools/di_time.py --child W --brdf-samples 1` names it (k_di_brdf_rays). The workload
 emitter_field is scenes.emitter_field(256) (131 k emissive triangles) at 1920 x 1080, 1 spp, 1 bounce.
-usage: tools/di_time.py [--workloads c2,c3,c5,emitter_field] [--samples 8] [--n 20] [--reuse [--visibility] [--pairwise]] [--light-sampling cdf,regir]"""
+usage: tools/di_time.py [--workloads c2,c3,c5,emitter_field] [--samples 8] [--n 20] [--reuse [--visibility] [--pairwise]] [--light-sampling cdf,regir] [--brdf-samples 0,1,2]"""
 import argparse, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def child(w, samples, n, reuse, modes, visibility=False, pairwise=False):
+def child(w, samples, n, reuse, modes, visibility=False, pairwise=False, brdf=()):
     sys.path.insert(0, ROOT)
     import torch
     import __graft_entry__ as ge
@@ -63,6 +65,17 @@ def child(w, samples, n, reuse, modes, visibility=False, pairwise=False):
                "frame_di_off_ms": off_ms, "frame_di_on_ms": on_ms}
         if mode != modes[-1]:
             print(json.dumps(out), flush=True)
+    if brdf:                                                   # the plain pass of the last mode with N_B BRDF candidates, alternating twice
+        rows = {}
+        for rnd in range(2):
+            for nb in brdf:
+                r.direct_lighting.SetBrdfSampling(L.di_brdf_settings(nb) if nb else None)
+                for _ in range(3):
+                    r.direct_lighting.Render(tlas)
+                ctx.sync()
+                rows.setdefault(str(nb), []).append(timed(lambda i: r.direct_lighting.Render(tlas), n))
+        r.direct_lighting.SetBrdfSampling(None)
+        out["brdf"] = rows
     if reuse:
         r.render(gs, di_samples=samples, di_reuse=L.di_resampling_settings()); ctx.sync()     # Previous* G-buffer, first history
         r.direct_lighting.Render(tlas); ctx.sync()
@@ -109,14 +122,15 @@ if __name__ == "__main__":
     ap.add_argument("--child", default=None); ap.add_argument("--workloads", default="c2,c3,c5")
     ap.add_argument("--samples", type=int, default=8); ap.add_argument("--n", type=int, default=20); ap.add_argument("--reuse", action="store_true")
     ap.add_argument("--light-sampling", default="cdf"); ap.add_argument("--visibility", action="store_true")
-    ap.add_argument("--pairwise", action="store_true")
+    ap.add_argument("--pairwise", action="store_true"); ap.add_argument("--brdf-samples", default="")
     a = ap.parse_args()
     if a.child:
-        child(a.child, a.samples, a.n, a.reuse, a.light_sampling.split(","), a.visibility, a.pairwise); sys.exit(0)
+        child(a.child, a.samples, a.n, a.reuse, a.light_sampling.split(","), a.visibility, a.pairwise,
+              [int(v) for v in a.brdf_samples.split(",") if v]); sys.exit(0)
     for w in a.workloads.split(","):
         p = subprocess.run([sys.executable, __file__, "--child", w, "--samples", str(a.samples), "--n", str(a.n),
                             "--light-sampling", a.light_sampling] + (["--reuse"] if a.reuse else []) + (["--visibility"] if a.visibility else []) +
-                           (["--pairwise"] if a.pairwise else []), stdout=subprocess.PIPE,
+                           (["--pairwise"] if a.pairwise else []) + (["--brdf-samples", a.brdf_samples] if a.brdf_samples else []), stdout=subprocess.PIPE,
                            stderr=subprocess.PIPE, text=True, timeout=600)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]
         print("\n".join(line) if line else "%s FAILED (exit %d) %s" % (w, p.returncode, p.stderr[-400:]), flush=True)
