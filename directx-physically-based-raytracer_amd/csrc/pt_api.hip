@@ -363,7 +363,9 @@ struct TopLevelPlan {
 }
 
 // host only: resolve the ids, lay the copy out, write the instance sources into c.tlasUploadHost
-static int plan_top_level(Context& c, const PtInstanceDesc* descs, uint32_t count, TopLevelPlan& P)
+// fromDevice (null: none): instances whose transform the device patches in from the posed InstanceData (pt_build_top_level_posed); the
+// source's pad word says so to the patch kernel. Nothing else of the plan depends on a transform.
+static int plan_top_level(Context& c, const PtInstanceDesc* descs, uint32_t count, const uint8_t* fromDevice, TopLevelPlan& P)
 {
     P.tlasNodeExact = wide_node_capacity(count);
     P.tlasNodeCap = P.tlasNodeExact;
@@ -389,7 +391,7 @@ static int plan_top_level(Context& c, const PtInstanceDesc* descs, uint32_t coun
         }
         InstanceSource src;
         memcpy(src.transform, descs[i].Transform, sizeof(float) * 12);
-        src.instanceID = descs[i].InstanceID & 0xFFFFFFu; src.mask = descs[i].InstanceMask & 0xFFu; src.blasSlot = pb->second; src._pad = 0;
+        src.instanceID = descs[i].InstanceID & 0xFFFFFFu; src.mask = descs[i].InstanceMask & 0xFFu; src.blasSlot = pb->second; src._pad = fromDevice && fromDevice[i] ? 1u : 0u;
         memcpy(up.data() + sizeof(InstanceSource) * (size_t)i, &src, sizeof src);
         P.tris += b.triCount;
         P.objectEnd = std::max<uint64_t>(P.objectEnd, (uint64_t)src.instanceID + b.geometryCount);
@@ -410,19 +412,26 @@ static int plan_top_level(Context& c, const PtInstanceDesc* descs, uint32_t coun
     return PT_OK;
 }
 
-int pt_build_top_level(PtContext* ctx, const PtInstanceDesc* descs, uint32_t count, uint32_t build_flags)
+// The one top-level build behind pt_build_top_level (posed == null) and pt_build_top_level_posed.
+static int build_top_level(PtContext* ctx, const PtInstanceDesc* descs, uint32_t count, const PtInstanceData* posed, const uint8_t* fromDevice)
 {
-    (void)build_flags;
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
     API_ARG(&c, descs || count == 0, "descs is NULL");
+    bool patch = false;
+    uint32_t lastPosed = 0;
+    for (uint32_t i = 0; fromDevice && i < count; i++) if (fromDevice[i]) { patch = true; lastPosed = i; }
+    if (!patch) fromDevice = nullptr;
+    API_ARG(&c, !patch || posed, "from_device names instances but device_instances is NULL");
+    // the patch kernel reads device_instances[i]: its extent is known only for the array the context has bound
+    API_ARG(&c, !patch || (posed == c.instanceData && lastPosed < c.instanceDataCount), "device_instances must be the array bound with pt_set_instance_data and reach every instance from_device names");
     API_ARG(&c, c.viewers.empty(), "other contexts view this context's scene (pt_share_scene): destroy or re-point them before rebuilding");
     API_HIP(&c, hipSetDevice(c.device));
     if (c.sceneOwner) { detach_from_owner(c); drop_tlas(c); }
     int st = poll_tlas_header(c, false);
     if (st != PT_OK) return st;
     TopLevelPlan P;
-    st = plan_top_level(c, descs, count, P);
+    st = plan_top_level(c, descs, count, fromDevice, P);
     if (st != PT_OK) return st;
 
     // ---- allocate: everything is grow-only, so the rebuild of an unchanged scene layout (a dynamic frame) allocates nothing and waits for
@@ -512,6 +521,7 @@ int pt_build_top_level(PtContext* ctx, const PtInstanceDesc* descs, uint32_t cou
 
     // ---- launch, all in stream order
     if (!preJobs.empty()) e = launch_blob_assembly(nullptr, c.tlas, nullptr, 0, nullptr, nullptr, dPre, (uint32_t)preJobs.size(), nullptr, c.stream);   // static pieces into place first: the table points there
+    if (e == hipSuccess && patch) e = launch_patch_instance_sources(c.stream, (InstanceSource*)c.tlasUploadDev.data(), posed, count);
     if (e == hipSuccess) e = launch_instance_records(dSrc, dTable, count, c.tlas.instances.data(), c.tlas.blasBounds.data(), c.tlas.tree.bounds.data(), c.stream);
     if (e == hipSuccess) e = build_tlas_device(c.tlas.instances.data(), c.tlas.blasBounds.data(), count, c.stream, c.tlas);
     if (e == hipSuccess) e = launch_blob_assembly(c.tlas.instances.data(), c.tlas, dTable, count, (InstanceT*)(blob + P.instAt), (InstanceT*)(blob + P.leafAt),
@@ -555,6 +565,19 @@ int pt_build_top_level(PtContext* ctx, const PtInstanceDesc* descs, uint32_t cou
     c.normalsShared = c.validated && c.sharedVerdict;
     c.haveTlas = true;
     return PT_OK;
+}
+
+int pt_build_top_level(PtContext* ctx, const PtInstanceDesc* descs, uint32_t count, uint32_t build_flags)
+{
+    (void)build_flags;
+    return build_top_level(ctx, descs, count, nullptr, nullptr);
+}
+
+int pt_build_top_level_posed(PtContext* ctx, const PtInstanceDesc* descs, uint32_t count, uint32_t build_flags, const PtInstanceData* device_instances,
+                             const uint8_t* from_device)
+{
+    (void)build_flags;
+    return build_top_level(ctx, descs, count, device_instances, from_device);
 }
 
 int pt_share_scene(PtContext* ctx, PtContext* source)

@@ -123,6 +123,38 @@ constexpr uint32_t kSubQueueShiftFused = 5, kSubQueueShiftStream = 7, kSubQueues
 struct FrameConstants { PtCamera cam; PtSceneData sd; PtGraphicsSettings gs; };
 struct RoundArgs;
 
+// ---- animation (pt_anim.hip). What the posing kernel reads of a rig and of an animated object: device pointers into the one device buffer
+// each of them owns. Written once, at creation.
+struct AnimRigView {
+    const int* parents; const float* rest;           // [nodes] | [nodes * 10]: T3 R4 S3
+    const uint32_t* levelNodes; const uint32_t* levelStart;   // the nodes ordered by depth | [levels + 1] into levelNodes
+    const uint2* channels;                           // [clips * nodes * 3] {FirstKey, KeyCount}
+    const float* keyTimes; const float4* keyValues;
+    uint32_t nodeCount, levelCount, clipCount, _pad;
+};
+struct AnimObjectView {
+    AnimRigView rig;
+    float transform[16];                             // RenderObject.Transform()
+    float* globals;                                  // [nodes * 16]
+    float* skeletal;                                 // [joints of all skins * 12]
+    float* skinInverse;                              // [skins * 16]: Global(meshNode)^-1 of this evaluation
+    const uint32_t* bindingNodes; const uint32_t* bindingInstances; const float* bindingGlobals;
+    const uint32_t* skinMeshNodes;                   // [skins]: the rig node of each skinned mesh node
+    const uint32_t* jointNodes; const uint32_t* jointSkin; const float* inverseBinds;   // [joints of all skins]: rig node | skin | InverseBind
+    uint32_t bindingCount, skinCount, jointCount, _pad;
+};
+struct AnimStateDev { const AnimObjectView* object; uint32_t clip, first; double time; };   // one per state of pt_anim_evaluate
+struct AnimRig { DeviceBuffer<uint8_t> dev; AnimRigView view{}; std::vector<double> durations; uint32_t users = 0; };
+struct AnimObject {
+    uint64_t rig = 0;
+    DeviceBuffer<uint8_t> dev; const AnimObjectView* viewDev = nullptr;
+    float* globals = nullptr; float* skeletal = nullptr;
+    uint32_t nodeCount = 0, maxInstance = 0; bool hasBindings = false;
+    std::vector<uint32_t> skinFirstJoint;
+    bool evaluated = false;                          // PreviousObjectToWorld of the first evaluation = its ObjectToWorld
+    uint64_t stamp = 0;                              // the evaluate call that last named it (an object twice in one call is refused)
+};
+
 struct DeviceCounters {
     unsigned long long primaryRays, secondaryRays, nodesVisited, trianglesTested;
     unsigned int mismatchCount, stackOverflows;   // PT_DEBUG_BRUTE_FORCE: rays whose BVH result differs from brute force | refused stack pushes (must be 0)
@@ -229,6 +261,12 @@ struct Context {
     DeviceBuffer<uint32_t> lightFirst;
     DeviceBuffer<uint4> diBrdfRecords;                // (li | ~0u, U, V, pdf of the ray)
 
+    // animation (pt_anim.hip): rigs, animated objects, and the staging of pt_anim_evaluate's states (a pinned ring guarded by events, like
+    // tlasStage; the device array is grow-only)
+    std::map<uint64_t, AnimRig> animRigs; std::map<uint64_t, AnimObject> animObjects; uint64_t nextAnimId = 1, animStamp = 0;
+    UploadStage animStage[2]; uint32_t animStageNext = 0;
+    DeviceBuffer<AnimStateDev> animStatesDev;
+
     // post-processing (pt_post.hip): one slot per bloom stage, each the size of the level it writes (the bytes of the reference's two pyramids)
     PtPostProcessSettings post{}; bool havePost = false;
     DeviceBuffer<ushort4> postLevels;
@@ -316,6 +354,9 @@ hipError_t launch_instance_records(const InstanceSource* src, const BlasEntry* t
 hipError_t launch_blob_assembly(const InstanceRecord* inst, const Tlas& tlas, const BlasEntry* table, uint32_t n, InstanceT* outInst,
                                 InstanceT* outLeafInst, const BlobCopy* jobs, uint32_t njobs, f4v* outEnter, hipStream_t stream);
 __host__ __device__ void invert_3x4(const float m[12], float out[12]);
+
+// pt_anim.hip: src[i].transform <- instances[i].ObjectToWorld for every i whose src[i]._pad is set (pt_build_top_level_posed)
+hipError_t launch_patch_instance_sources(hipStream_t stream, InstanceSource* src, const PtInstanceData* instances, uint32_t n);
 
 // pt_skin.hip
 hipError_t launch_skin(hipStream_t stream, const void* skeletal, const float* transforms, void* vertices, void* motion, uint32_t count);

@@ -3,7 +3,8 @@
 // What it mirrors (host side of the path, upstream of the acceleration-structure build):
 //   scene descriptor   Source/MyScene.ixx:33-90, Source/JSONConverters.ixx:12-33, Source/Scene.ixx:33-73
 //                      {Camera{Position,Rotation}, EnvironmentLight{Color,Rotation,Texture}, Models{name:path},
-//                       RenderObjects[{Name,Transform{Translation,Rotation,Scale},IsVisible,Model}]}
+//                       RenderObjects[{Name,Transform{Translation,Rotation,Scale},IsVisible,Model,Animation}], Animations{name:path}}
+//   animations         Source/GLTFHelpers.ixx:278-345, 463-520 (JOINTS_0 / WEIGHTS_0, skins) and :539-663 (LoadAnimation): load_animation below
 //   glTF loader        Source/GLTFHelpers.ixx:142-537 (ProcessPrimitive, LoadModel): triangles only, the index array written BACKWARDS
 //                      (flipWindingOrder is always set, Scene.ixx:90), u16 indices iff count <= 65535, tangents ALWAYS recomputed when
 //                      NORMAL + TEXCOORD_0 exist, material factors incl. KHR_materials_emissive_strength / ior / transmission
@@ -551,7 +552,13 @@ inline uint16_t f32_to_f16(float f)                                      // roun
 // ------------------------------------------------------------------------------------------------
 // model: glTF 2.0 (.gltf with data: / external buffers, .glb)
 // ------------------------------------------------------------------------------------------------
+struct SkeletalVertex { float Position[3]; int16_t Normal[3], Tangent[3]; uint16_t Joints[4]; float Weights[4]; };   // VertexPositionNormalTangentSkin, Source/Vertex.ixx:52-57
+static_assert(sizeof(SkeletalVertex) == 48, "layout");
+// the joints of a skin: the names of their nodes and their inverse bind matrices (Model.ixx SkinJoint), shared by the mesh nodes that name the skin
+struct SkinJoints { std::vector<std::string> Names; std::vector<std::array<float, 16>> InverseBindMatrices; };
+
 struct MeshData {
+    std::vector<SkeletalVertex> SkeletalVertices;                           // JOINTS_0 + WEIGHTS_0: Mesh::SkeletalVertices, with a motion-vector buffer of as many entries
     std::vector<Vertex> Vertices;
     std::vector<uint8_t> Indices; uint32_t IndexStride = 2, IndexCount = 0;      // u16 iff count <= 65535 (GLTFHelpers.ixx:183-188)
     bool HasNormals = false, HasTangents = false, HasUV[2] = { false, false };
@@ -570,7 +577,8 @@ struct Texture {
     uint32_t Format() const { return IsBlockCompressed() ? BlockFormat : SRGB ? (uint32_t)PT_FORMAT_R8G8B8A8_UNORM_SRGB : (uint32_t)PT_FORMAT_R8G8B8A8_UNORM; }
 };
 enum TextureSlot { BaseColor = 0, EmissiveColor, Metallic, Roughness, MetallicRoughness, Transmission, Normal };
-struct MeshNode { std::vector<MeshData> Meshes; M4 GlobalTransform; };        // GlobalTransform reinterpreted as a row-vector matrix (LoadModel)
+struct MeshNode { std::vector<MeshData> Meshes; M4 GlobalTransform;           // GlobalTransform reinterpreted as a row-vector matrix (LoadModel)
+                  std::string NodeName; std::shared_ptr<SkinJoints> Skin; };  // NodeName: what an animation's transforms are looked up by; Skin: null without one
 
 inline PtMaterial default_material()
 {
@@ -798,6 +806,19 @@ inline std::vector<std::shared_ptr<MeshNode>> load_model(const std::string& path
             if (mesh.IndexStride == 2) { const uint16_t x = (uint16_t)idx[i]; std::memcpy(mesh.Indices.data() + 2 * i, &x, 2); }
             else std::memcpy(mesh.Indices.data() + 4 * i, &idx[i], 4);
         }
+        if (attrs.has("JOINTS_0") && attrs.has("WEIGHTS_0")) {           // :278-304: u8 / u16 joints become XMUSHORT4, normalised-integer weights are converted
+            const Asset::Accessor ja = asset.accessor(attrs.at("JOINTS_0"));
+            Asset::Accessor wa = asset.accessor(attrs.at("WEIGHTS_0"));
+            if ((ja.ctype != 5121 && ja.ctype != 5123) || ja.ncomp != 4) throw std::runtime_error("glTF: JOINTS_0 is not a VEC4 of unsigned bytes or shorts");
+            if (wa.ncomp != 4 || ja.count != pa.count || wa.count != pa.count) throw std::runtime_error("glTF: JOINTS_0 / WEIGHTS_0 do not match the POSITION accessor");
+            if (wa.ctype != 5126) wa.normalized = true;                    // integer weights are normalised ones, flagged or not (as ingest.py)
+            mesh.SkeletalVertices.assign(pos.size(), SkeletalVertex{});
+            for (size_t i = 0; i < pos.size(); i++) {
+                SkeletalVertex& sv = mesh.SkeletalVertices[i]; const Vertex& v = mesh.Vertices[i];
+                for (int k = 0; k < 3; k++) { sv.Position[k] = v.Position[k]; sv.Normal[k] = v.Normal[k]; sv.Tangent[k] = v.Tangent[k]; }
+                for (int k = 0; k < 4; k++) { sv.Joints[k] = (uint16_t)Asset::element(ja, i, k); sv.Weights[k] = (float)Asset::element(wa, i, k); }
+            }
+        }
         if (prim.has("material")) {
             const Json& m = j.at("materials").pick(prim.at("material"));
             static const Json empty = [] { Json e; e.kind = Json::Object; return e; }();
@@ -835,6 +856,7 @@ inline std::vector<std::shared_ptr<MeshNode>> load_model(const std::string& path
     };
 
     std::vector<std::shared_ptr<MeshNode>> out;
+    std::map<size_t, std::shared_ptr<SkinJoints>> skins;
     const Json& scene = j.at("scenes").at(j.uint("scene", 0, Json::kMaxUint));
     // depth first, children in file order, on an explicit stack (a chain of nodes may be as long as the file allows). glTF wants a strict
     // tree: a node reached a second time, through a cycle or through a second parent, is refused -- shared children could repeat a subtree
@@ -859,6 +881,26 @@ inline std::vector<std::shared_ptr<MeshNode>> load_model(const std::string& path
                 auto mn = std::make_shared<MeshNode>();
                 for (const Json& p : mj.at("primitives").items()) { MeshData md; if (process_primitive(p, md)) mn->Meshes.push_back(std::move(md)); }
                 mn->GlobalTransform = transpose(m);                       // the column-vector global matrix reinterpreted as a row-vector Matrix
+                if (node.has("name")) mn->NodeName = node.at("name").string();
+                if (node.has("skin")) {                                    // :477-512: joint names + inverse bind matrices, shared per skin index
+                    const size_t si = node.at("skin").index(j.has("skins") ? j.at("skins").size() : 0);
+                    if (!skins.count(si)) {
+                        skins[si] = nullptr;
+                        const Json& skin = j.at("skins").at(si);
+                        if (skin.has("inverseBindMatrices")) {             // a skin without them is ignored (:484)
+                            const Asset::Accessor ia = asset.accessor(skin.at("inverseBindMatrices"));
+                            if (ia.ctype != 5126 || ia.ncomp != 16) throw std::runtime_error("glTF: inverseBindMatrices is not a MAT4 of floats");
+                            auto sj = std::make_shared<SkinJoints>();
+                            if (skin.has("joints")) for (const Json& jn : skin.at("joints").items()) { const Json& n = nodes[jn.index(nodes.size())]; sj->Names.push_back(n.has("name") ? n.at("name").string() : std::string()); }
+                            if (ia.count > sj->Names.size()) throw std::runtime_error("glTF: more inverse bind matrices than joints");
+                            sj->Names.resize(ia.count);
+                            // glTF's column-major column-vector matrix, reinterpreted as a row-vector Matrix (:492): the floats as they lie
+                            for (size_t k = 0; k < ia.count; k++) { std::array<float, 16> mtx; for (int e = 0; e < 16; e++) mtx[e] = (float)Asset::element(ia, k, e); sj->InverseBindMatrices.push_back(mtx); }
+                            skins[si] = sj;
+                        }
+                    }
+                    mn->Skin = skins[si];
+                }
                 out.push_back(mn);
             }
         }
@@ -868,8 +910,132 @@ inline std::vector<std::shared_ptr<MeshNode>> load_model(const std::string& path
 }
 
 // ------------------------------------------------------------------------------------------------
+// animations: GLTFHelpers::LoadAnimation (GLTFHelpers.ixx:539-663) -> a rig as pt_anim_create_rig takes it
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t kNoNode = PT_ANIM_NO_NODE;
+struct Rig {
+    std::vector<int32_t> Parents;                                           // depth first, parent < own index, -1 for a root
+    std::vector<float> Rest;                                                // 10 per node: Translation, Rotation (x, y, z, w), Scale
+    std::vector<std::string> Names, ClipNames;
+    std::vector<double> Durations;                                          // per clip
+    std::vector<uint32_t> Channels;                                         // [clip][node][T, R, S][FirstKey, KeyCount]
+    std::vector<float> KeyTimes, KeyValues;                                 // KeyValues: 4 per key
+    // m_globalTransforms.find(name): the LAST node of that name in traversal order (the reference's map entry is overwritten), or kNoNode
+    uint32_t FindNode(const std::string& name) const { for (size_t n = Names.size(); n--;) if (Names[n] == name) return (uint32_t)n; return kNoNode; }
+};
+
+// fastgltf's DecomposeNodeMatrices on a column-vector matrix, the operations of ingest.py's decompose in the same order
+inline void decompose(const M4& m, double t[3], double q[4], double sc[3])
+{
+    for (int k = 0; k < 3; k++) { t[k] = m.m[k][3]; sc[k] = std::sqrt((m.m[0][k] * m.m[0][k] + m.m[1][k] * m.m[1][k]) + m.m[2][k] * m.m[2][k]); }
+    const double det = m.m[0][0] * (m.m[1][1] * m.m[2][2] - m.m[1][2] * m.m[2][1]) - m.m[0][1] * (m.m[1][0] * m.m[2][2] - m.m[1][2] * m.m[2][0])
+                     + m.m[0][2] * (m.m[1][0] * m.m[2][1] - m.m[1][1] * m.m[2][0]);
+    if (det < 0) sc[0] = -sc[0];
+    double r[3][3];
+    for (int i = 0; i < 3; i++) for (int k = 0; k < 3; k++) r[i][k] = m.m[i][k] / (sc[k] == 0 ? 1.0 : sc[k]);
+    const double tr = r[0][0] + r[1][1] + r[2][2];
+    if (tr > 0) { const double k = std::sqrt(tr + 1.0) * 2; q[0] = (r[2][1] - r[1][2]) / k; q[1] = (r[0][2] - r[2][0]) / k; q[2] = (r[1][0] - r[0][1]) / k; q[3] = 0.25 * k; }
+    else if (r[0][0] > r[1][1] && r[0][0] > r[2][2]) { const double k = std::sqrt(1.0 + r[0][0] - r[1][1] - r[2][2]) * 2; q[0] = 0.25 * k; q[1] = (r[0][1] + r[1][0]) / k; q[2] = (r[0][2] + r[2][0]) / k; q[3] = (r[2][1] - r[1][2]) / k; }
+    else if (r[1][1] > r[2][2]) { const double k = std::sqrt(1.0 + r[1][1] - r[0][0] - r[2][2]) * 2; q[0] = (r[0][1] + r[1][0]) / k; q[1] = 0.25 * k; q[2] = (r[1][2] + r[2][1]) / k; q[3] = (r[0][2] - r[2][0]) / k; }
+    else { const double k = std::sqrt(1.0 + r[2][2] - r[0][0] - r[1][1]) * 2; q[0] = (r[0][2] + r[2][0]) / k; q[1] = (r[1][2] + r[2][1]) / k; q[2] = 0.25 * k; q[3] = (r[1][0] - r[0][1]) / k; }
+}
+
+// The default scene's node forest, flattened depth first with its decomposed TRS, and one clip per glTF animation. LINEAR samplers only (STEP and
+// CUBICSPLINE channels are skipped, :582-584), channels without a target node are skipped, and per node NAME and path the first channel wins
+// (:593, :616, :639); a clip's duration is the largest key time of the channels it accepted.
+// The reference keeps keyframes and global transforms in maps keyed by node name. Names are resolved to indices HERE, with the maps' semantics:
+// the keyframes of a name apply to every node of the forest that carries it (Animation.ixx:123), and a lookup BY name (Rig::FindNode: a mesh
+// node, a joint) finds the LAST node of that name in traversal order, because m_globalTransforms[name] is overwritten (:138).
+inline std::shared_ptr<Rig> load_animation(const std::string& path)
+{
+    Asset asset(path);
+    const Json& j = asset.j;
+    auto rig = std::make_shared<Rig>();
+    static const std::vector<Json> none;
+    const std::vector<Json>& nodes = j.has("nodes") ? j.at("nodes").items() : none;
+    const Json& scene = j.at("scenes").at(j.uint("scene", 0, Json::kMaxUint));
+    auto name_of = [&](const Json& n) { return n.has("name") ? n.at("name").string() : std::string(); };
+    std::vector<bool> visited(nodes.size(), false);
+    std::vector<std::pair<size_t, int32_t>> pending;                       // (node, its parent's index in the rig)
+    auto push = [&](const Json& list, int32_t parent) { for (size_t k = list.items().size(); k--;) pending.emplace_back(list.items()[k].index(nodes.size()), parent); };
+    if (scene.has("nodes")) push(scene.at("nodes"), -1);
+    while (!pending.empty()) {
+        const auto [ni, parent] = pending.back(); pending.pop_back();
+        if (visited[ni]) throw std::runtime_error("glTF: node " + std::to_string(ni) + " is reached twice (a cycle, or a second parent)");
+        visited[ni] = true;
+        const Json& node = nodes[ni];
+        double t[3] = { 0, 0, 0 }, q[4] = { 0, 0, 0, 1 }, sc[3] = { 1, 1, 1 };
+        if (node.has("matrix")) decompose(node_matrix(node), t, q, sc);
+        else {
+            auto read = [&](const char* key, double* dst, size_t n) { if (!node.has(key)) return; if (node.at(key).items().size() != n) throw std::runtime_error(std::string("glTF: a node's ") + key + " of the wrong length"); for (size_t k = 0; k < n; k++) dst[k] = node.at(key).at(k).real(); };
+            read("translation", t, 3); read("rotation", q, 4); read("scale", sc, 3);
+        }
+        const int32_t me = (int32_t)rig->Parents.size();
+        rig->Parents.push_back(parent); rig->Names.push_back(name_of(node));
+        for (double v : t) rig->Rest.push_back((float)v);
+        for (double v : q) rig->Rest.push_back((float)v);
+        for (double v : sc) rig->Rest.push_back((float)v);
+        if (node.has("children")) push(node.at("children"), me);
+    }
+    const size_t n = rig->Parents.size();
+    if (!j.has("animations") || !j.at("animations").size()) throw std::runtime_error(path + ": the file holds no animation");
+    const std::vector<Json>& anims = j.at("animations").items();
+    rig->Channels.assign(mul(mul(anims.size(), n), 6), 0u);
+    for (size_t ci = 0; ci < anims.size(); ci++) {
+        const Json& anim = anims[ci];
+        float duration = 0.0f;
+        std::map<std::pair<std::string, int>, std::pair<uint32_t, uint32_t>> taken;      // (node name, path) -> (FirstKey, KeyCount): the first channel wins
+        if (anim.has("channels")) for (const Json& ch : anim.at("channels").items()) {
+            const Json* target = ch.find("target");
+            if (!target || !target->has("node")) continue;
+            const Json& sampler = anim.at("samplers").pick(ch.at("sampler"));
+            if (sampler.has("interpolation") && sampler.at("interpolation").string() != "LINEAR") continue;
+            const std::string pathName = target->has("path") ? target->at("path").string() : std::string();
+            const int slot = pathName == "translation" ? 0 : pathName == "rotation" ? 1 : pathName == "scale" ? 2 : -1;
+            if (slot < 0) continue;                                        // weights: morph targets are out of scope
+            const size_t ncomp = slot == 1 ? 4 : 3;
+            const std::string name = name_of(nodes[target->at("node").index(nodes.size())]);
+            if (taken.count({ name, slot })) continue;
+            const Asset::Accessor ta = asset.accessor(sampler.at("input")), va = asset.accessor(sampler.at("output"));
+            if (ta.ctype != 5126 || ta.ncomp != 1) throw std::runtime_error("glTF: an animation sampler's input is not a SCALAR of floats");
+            if ((size_t)va.ncomp != ncomp || va.ctype != 5126) throw std::runtime_error("glTF: an animation sampler's output does not fit the " + pathName + " path");
+            if (ta.count != va.count) throw std::runtime_error("glTF: an animation sampler's input and output counts differ");
+            if (!ta.count) continue;                                       // an empty channel leaves the slot empty: a later one may take it
+            if (add(rig->KeyTimes.size(), ta.count) > UINT32_MAX) throw std::runtime_error("glTF: more than 2^32 keys");
+            const uint32_t first = (uint32_t)rig->KeyTimes.size();
+            for (size_t k = 0; k < ta.count; k++) {
+                const float time = (float)Asset::element(ta, k, 0);
+                bool ok = std::isfinite(time) && (k == 0 || time > rig->KeyTimes.back());
+                rig->KeyTimes.push_back(time);
+                for (size_t c = 0; c < 4; c++) { const float v = c < ncomp ? (float)Asset::element(va, k, (int)c) : 0.0f; ok = ok && std::isfinite(v); rig->KeyValues.push_back(v); }
+                if (!ok) throw std::runtime_error("glTF: key times must be finite and strictly ascending, key values finite");
+                duration = std::fmax(duration, time);
+            }
+            taken[{ name, slot }] = { first, (uint32_t)ta.count };
+        }
+        for (size_t ni = 0; ni < n; ni++) for (int slot = 0; slot < 3; slot++) {       // the keyframes of a name apply to every node that carries it
+            auto it = taken.find({ rig->Names[ni], slot });
+            if (it == taken.end()) continue;
+            uint32_t* c = rig->Channels.data() + ((ci * n + ni) * 3 + (size_t)slot) * 2;
+            c[0] = it->second.first; c[1] = it->second.second;
+        }
+        rig->Durations.push_back((double)duration);
+        rig->ClipNames.push_back(anim.has("name") ? anim.at("name").string() : std::string());
+    }
+    return rig;
+}
+
+// ------------------------------------------------------------------------------------------------
 // scene descriptor + Scene::Load / Refresh
 // ------------------------------------------------------------------------------------------------
+// a render object with an animation bound (Scene.ixx:165-168), as pt_anim_create_object takes it
+struct AnimatedObject {
+    std::shared_ptr<Rig> Animation;
+    float Transform[16];                                                    // RenderObject.Transform(), row-vector convention
+    std::vector<uint32_t> BindingNodes, BindingInstances; std::vector<float> BindingGlobals;   // per mesh node: rig node (or kNoNode), instance, GlobalTransform
+    struct Skin { uint32_t MeshNode; std::vector<uint32_t> JointNodes; std::vector<float> InverseBinds; uint32_t SceneNode; };
+    std::vector<Skin> Skins;                                                // per skinned mesh node; SceneNode: index into Scene::Nodes
+};
 struct RenderObject { uint32_t Node; float Transform[12]; bool IsVisible; std::string Name; };   // Transform: column-vector [R|t], as InstanceData.ObjectToWorld wants it
 struct Scene {
     double CameraPosition[3] = { 0, 0, 0 }; M4 CameraRotation = identity();
@@ -877,6 +1043,7 @@ struct Scene {
     std::string EnvironmentLightTexture;                                    // path, not decoded here
     std::vector<std::shared_ptr<MeshNode>> Nodes;                           // one bottom level each
     std::vector<RenderObject> Objects;                                      // one instance each
+    std::vector<AnimatedObject> Animations;                                 // one per render object that names an animation
 };
 
 inline Scene load_scene(const std::string& path)
@@ -899,6 +1066,9 @@ inline Scene load_scene(const std::string& path)
     }
     std::map<std::string, std::string> models;
     if (const Json* m = j.find("Models"); m && m->kind == Json::Object) for (auto& kv : m->obj) models[kv.first] = resolve(base, kv.second.string());
+    std::map<std::string, std::string> animations;
+    if (const Json* m = j.find("Animations"); m && m->kind == Json::Object) for (auto& kv : m->obj) animations[kv.first] = resolve(base, kv.second.string());
+    std::map<std::string, std::shared_ptr<Rig>> rigs;
     std::map<std::string, std::vector<std::shared_ptr<MeshNode>>> loaded;
     M4 zflip = identity(); zflip.m[2][2] = -1.0;
     if (const Json* ros = j.find("RenderObjects"); ros && ros->kind == Json::Array)
@@ -906,18 +1076,44 @@ inline Scene load_scene(const std::string& path)
             const std::string model = ro.has("Model") ? ro.at("Model").string() : "", name = ro.has("Name") ? ro.at("Name").string() : "";
             if (!model.empty() && !models.count(model))                    // MyScene.ixx:57-70
                 throw std::runtime_error(path + ": " + (name.empty() ? std::string("Unnamed RenderObject") : "RenderObject " + name) + ": Models " + model + " not found");
+            const std::string animation = ro.has("Animation") ? ro.at("Animation").string() : "";
+            if (!animation.empty() && !animations.count(animation))        // MyScene.ixx:69
+                throw std::runtime_error(path + ": " + (name.empty() ? std::string("Unnamed RenderObject") : "RenderObject " + name) + ": Animations " + animation + " not found");
             if (model.empty()) continue;
             if (!loaded.count(model)) loaded[model] = load_model(models[model], true);      // Scene.ixx:90
             const M4 transform = affine_from_json(ro.find("Transform"));
             const Json* vis = ro.find("IsVisible");
-            for (auto& mn : loaded[model]) {
+            std::shared_ptr<Rig> rig;
+            if (!animation.empty()) { if (!rigs.count(animation)) rigs[animation] = load_animation(animations[animation]); rig = rigs[animation]; }
+            AnimatedObject ao; ao.Animation = rig;
+            for (int e = 0; e < 16; e++) ao.Transform[e] = (float)transform.m[e / 4][e % 4];
+            // Model.SkinJoints is a dictionary keyed by the mesh node's name: the last skin stored under a name serves every mesh node of that name
+            std::map<std::string, std::shared_ptr<SkinJoints>> skinOf;
+            for (auto& mn : loaded[model]) if (mn->Skin) skinOf[mn->NodeName] = mn->Skin;
+            for (auto mn : loaded[model]) {
+                bool skinned = false;
+                for (const MeshData& md : mn->Meshes) skinned = skinned || !md.SkeletalVertices.empty();
+                // the skinning pass rewrites the vertex buffer in place: a skinned mesh node is instanced once per animated render object
+                if (rig && skinned) mn = std::make_shared<MeshNode>(*mn);
                 uint32_t ni = 0;
                 for (; ni < sc.Nodes.size(); ni++) if (sc.Nodes[ni] == mn) break;
                 if (ni == sc.Nodes.size()) sc.Nodes.push_back(mn);
                 RenderObject o; o.Node = ni; o.Name = name; o.IsVisible = !(vis && vis->kind == Json::Bool && !vis->b);
                 store_float3x4(mul(mul(mn->GlobalTransform, zflip), transform), o.Transform);     // Scene.ixx:199-214
+                if (rig) {
+                    ao.BindingNodes.push_back(rig->FindNode(mn->NodeName)); ao.BindingInstances.push_back((uint32_t)sc.Objects.size());
+                    for (int e = 0; e < 16; e++) ao.BindingGlobals.push_back((float)mn->GlobalTransform.m[e / 4][e % 4]);
+                    auto sk = skinOf.find(mn->NodeName);
+                    if (sk != skinOf.end()) {
+                        AnimatedObject::Skin s; s.MeshNode = rig->FindNode(mn->NodeName); s.SceneNode = ni;
+                        for (const std::string& jn : sk->second->Names) s.JointNodes.push_back(rig->FindNode(jn));
+                        for (const auto& mtx : sk->second->InverseBindMatrices) s.InverseBinds.insert(s.InverseBinds.end(), mtx.begin(), mtx.end());
+                        ao.Skins.push_back(std::move(s));
+                    }
+                }
                 sc.Objects.push_back(o);
             }
+            if (rig) sc.Animations.push_back(std::move(ao));
         }
     return sc;
 }

@@ -6,12 +6,16 @@
 //     struct Raytracing          Source/Raytracing.ixx:29-250      (DEFAULT permutation, and the SHARC overload with struct SHARC)
 //     BuildTopLevelAccelerationStructure / CreateGeometryDesc       Source/RaytracingHelpers.ixx:28-105
 //     struct SkeletalMeshSkinning Source/SkeletalMeshSkinning.ixx:20-66
+//     struct Animation / AnimationCollection   Source/Animation.ixx:78-197 (the clock and the selection; the transforms are computed on the device)
 //     struct PostProcessing      App::PostProcessGraphics with Denoiser::None (Source/App.cpp:1506-1571): Bloom, Merge, ToneMap, CopyTexture
 // Error behaviour: a failing status becomes the exception type the reference throws at the same place
 // (std::invalid_argument for argument checks, std::system_error otherwise: Source/ErrorHelpers.ixx:16-32).
 // Header-only, plain C++20 (std::span), no HIP headers needed by the including translation unit.
 #pragma once
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <memory>
 #include <span>
 #include <stdexcept>
 #include <string>
@@ -176,6 +180,93 @@ struct SkeletalMeshSkinning {
                                                         (uint32_t)GPUBuffers.Vertices->Capacity));
     }
 };
+
+// ---- animation (Source/Animation.ixx). The reference's Animation computes its transforms on the CPU in Tick; here Tick and SetTime keep the clock
+// only, and AnimationCollection::Evaluate hands the selected clips and their times to the device (pt_anim_evaluate), which leaves the global
+// transforms, the skeletal transforms of every skin and the posed InstanceData where skinning and the top-level build read them.
+struct AnimationRig {                   // one animation file on the device: node forest, clips and keys, names resolved to indices by the loader
+    struct Desc {                       // the arrays of pt_anim_create_rig
+        std::span<const int32_t> Parents; std::span<const float> RestTRS; std::span<const double> Durations; std::span<const uint32_t> Channels;
+        std::span<const float> KeyTimes, KeyValues;
+    };
+    uint64_t ID = 0; std::vector<double> Durations;
+    AnimationRig(CommandList& commandList, const Desc& d) : Durations(d.Durations.begin(), d.Durations.end()), m_context(commandList.Context)
+    {
+        ThrowIfFailed(m_context, pt_anim_create_rig(m_context, (uint32_t)d.Parents.size(), d.Parents.data(), d.RestTRS.data(), (uint32_t)d.Durations.size(), d.Durations.data(),
+                                                    d.Channels.data(), d.KeyTimes.data(), d.KeyValues.data(), (uint32_t)d.KeyTimes.size(), &ID));
+    }
+    AnimationRig(const AnimationRig&) = delete;
+    AnimationRig& operator=(const AnimationRig&) = delete;
+    ~AnimationRig() { pt_anim_release_rig(m_context, ID); }
+private:
+    PtContext* m_context;
+};
+
+struct Animation {                      // one clip: Source/Animation.ixx:78-175
+    std::string Name;
+    explicit Animation(double duration) : m_duration(duration) {}
+    auto GetDuration() const { return m_duration; }
+    auto GetTime() const { return m_time; }
+    void SetTime(double seconds = 0) { m_time = std::clamp(seconds, 0.0, m_duration); }                       // :107
+    void Tick(double elapsedSeconds) { m_time = m_duration > 0 ? std::fmod(m_time + elapsedSeconds, m_duration) : 0.0; }   // :109-113; Duration 0 stays at 0 (the reference: NaN)
+private:
+    double m_duration, m_time{};
+};
+
+struct AnimationCollection : std::vector<Animation> {     // Source/Animation.ixx:177-197, bound to ONE render object (Scene.ixx:165-168)
+    struct Bindings {                   // the arrays of pt_anim_create_object
+        std::span<const float> Transform;                 // RenderObject.Transform(), 16 floats
+        std::span<const uint32_t> Nodes, Instances; std::span<const float> GlobalTransforms;
+        std::span<const uint32_t> SkinMeshNodes, SkinJointCounts, JointNodes; std::span<const float> InverseBindMatrices;
+    };
+    std::string Name;
+    uint64_t Object = 0;
+
+    AnimationCollection(CommandList& commandList, std::shared_ptr<AnimationRig> rig, const Bindings& b) : m_context(commandList.Context), m_rig(std::move(rig)), m_isSkinned(!b.SkinMeshNodes.empty())
+    {
+        for (double d : m_rig->Durations) emplace_back(d);
+        ThrowIfFailed(m_context, pt_anim_create_object(m_context, m_rig->ID, b.Transform.data(), (uint32_t)b.Nodes.size(), b.Nodes.data(), b.Instances.data(), b.GlobalTransforms.data(),
+                                                       (uint32_t)b.SkinMeshNodes.size(), b.SkinMeshNodes.data(), b.SkinJointCounts.data(), b.JointNodes.data(), b.InverseBindMatrices.data(), &Object));
+    }
+    AnimationCollection(const AnimationCollection&) = delete;
+    AnimationCollection& operator=(const AnimationCollection&) = delete;
+    ~AnimationCollection() { pt_anim_release_object(m_context, Object); }
+
+    auto GetSelectedIndex() const { return std::min(m_selectedIndex, size() - 1); }
+    void SetSelectedIndex(size_t index) { m_selectedIndex = std::min(index, size() - 1); }
+    auto IsSkinned() const { return m_isSkinned; }
+    // Animation::GetSkeletalTransforms for one skinned mesh node: the device array SkeletalMeshSkinning::GPUBuffers.SkeletalTransforms takes
+    GPUBuffer GetSkeletalTransforms(uint32_t skin) const
+    {
+        const float* p = nullptr; uint32_t joints = 0;
+        ThrowIfFailed(m_context, pt_anim_skeletal_transforms(m_context, Object, skin, &p, &joints));
+        return GPUBuffer{ p, joints, 48 };
+    }
+    // Animation::ComputeTransforms + Scene::Refresh for every collection of a scene in ONE launch, at each one's selected clip and time
+    static void Evaluate(CommandList& commandList, std::span<AnimationCollection* const> collections, PtInstanceData* deviceInstances)
+    {
+        std::vector<PtAnimState> states;
+        for (const AnimationCollection* c : collections) states.push_back(PtAnimState{ c->Object, (uint32_t)c->GetSelectedIndex(), 0, (*c)[c->GetSelectedIndex()].GetTime() });
+        ThrowIfFailed(commandList.Context, pt_anim_evaluate(commandList.Context, states.data(), (uint32_t)states.size(), deviceInstances));
+    }
+private:
+    PtContext* m_context;
+    std::shared_ptr<AnimationRig> m_rig;
+    size_t m_selectedIndex{};
+    bool m_isSkinned{};
+};
+
+namespace RaytracingHelpers {
+// BuildTopLevelAccelerationStructure over posed instances: where fromDevice[i] is set, instance i's transform is InstanceData[i].ObjectToWorld as
+// AnimationCollection::Evaluate left it on the device
+inline void BuildTopLevelAccelerationStructure(CommandList& commandList, uint32_t flags, std::span<const PtInstanceDesc> descs, const PtInstanceData* deviceInstances,
+                                               std::span<const uint8_t> fromDevice, TopLevelAccelerationStructure& accelerationStructure)
+{
+    if (fromDevice.size() != descs.size()) throw std::invalid_argument("fromDevice must name every instance");
+    ThrowIfFailed(commandList.Context, pt_build_top_level_posed(commandList.Context, descs.data(), (uint32_t)descs.size(), flags, deviceInstances, fromDevice.data()));
+    accelerationStructure.Valid = true;
+}
+}
 
 // The RTXDI operator of the reference (Source/RTXDI.ixx: SetConstants + Render) as this library restates it: direct lighting from the
 // scene's emissive triangles, written to Textures.Diffuse / Specular for the path tracer (GraphicsSettings.IsDIEnabled), or added to

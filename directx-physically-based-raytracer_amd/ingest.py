@@ -135,6 +135,7 @@ def load_scene_desc(path):
         "EnvironmentLight": {"Color": (float(col.get("R", 0)), float(col.get("G", 0)), float(col.get("B", 0)), float(col.get("A", -1))),
                              "Rotation": rotation_from_json(env.get("Rotation")), "Texture": resolve(env.get("Texture", ""))},
         "Models": {k: resolve(v) for k, v in (j.get("Models") or {}).items()},
+        "Animations": {k: resolve(v) for k, v in (j.get("Animations") or {}).items()},
         "RenderObjects": [],
     }
     for ro in j.get("RenderObjects") or []:
@@ -142,8 +143,12 @@ def load_scene_desc(path):
         if model and model not in desc["Models"]:                      # MyScene.ixx:57-70
             name = ("RenderObject " + ro["Name"]) if ro.get("Name") else "Unnamed RenderObject"
             raise RuntimeError(f"{path}: {name}: Models {model} not found")
+        anim = ro.get("Animation", "")
+        if anim and anim not in desc["Animations"]:                    # MyScene.ixx:69
+            name = ("RenderObject " + ro["Name"]) if ro.get("Name") else "Unnamed RenderObject"
+            raise RuntimeError(f"{path}: {name}: Animations {anim} not found")
         desc["RenderObjects"].append({"Name": ro.get("Name", ""), "Transform": affine_from_json(ro.get("Transform")),
-                                      "IsVisible": bool(ro.get("IsVisible", True)), "Model": model})
+                                      "IsVisible": bool(ro.get("IsVisible", True)), "Model": model, "Animation": anim})
     return desc
 
 
@@ -318,6 +323,20 @@ def load_model(path, flip_winding_order=True):
                 tan = compute_tangents(pos, nrm, uvs[0], indices)
         vb = S.make_vertices(pos, nrm, uvs[0], tan, uvs[1])
         mesh = S.Mesh(vb, indices, has_normals=nrm is not None, material=None, has_tangents=tan is not None, has_uv=tuple(has_uv))
+        if "JOINTS_0" in attrs and "WEIGHTS_0" in attrs:                  # :278-304: the 48-byte skeletal vertex + a motion-vector buffer
+            joints = asset.accessor(attrs["JOINTS_0"]); weights = asset.accessor(attrs["WEIGHTS_0"])
+            if joints.dtype not in (np.uint8, np.uint16) or joints.shape[1] != 4:
+                raise ValueError("glTF: JOINTS_0 is not a VEC4 of unsigned bytes or shorts")
+            if weights.shape[1] != 4 or len(joints) != len(pos) or len(weights) != len(pos):
+                raise ValueError("glTF: JOINTS_0 / WEIGHTS_0 do not match the POSITION accessor")
+            if weights.dtype.kind in "iu":                                # normalised integers (accessor() converts the flagged ones)
+                weights = weights.astype(np.float32) / float(np.iinfo(weights.dtype).max)
+            sk = np.zeros(len(pos), L.SKELETAL_VERTEX)
+            sk["Position"] = vb["Position"]; sk["Normal"] = vb["Normal"]; sk["Tangent"] = vb["Tangent"]
+            sk["Joints"] = joints.astype(np.uint16)                       # u8 and u16 components both become XMUSHORT4
+            sk["Weights"] = weights.astype(np.float32)
+            mesh.skeletal_vertices = sk
+            mesh.motion_vectors = np.zeros((len(pos), 4), np.uint16)
         if "material" in prim:
             m = j["materials"][_index(prim["material"], len(j["materials"]))]
             pbr = m.get("pbrMetallicRoughness", {})
@@ -352,6 +371,7 @@ def load_model(path, flip_winding_order=True):
         return mesh
 
     out = []
+    skins = {}
     scene = j["scenes"][_index(j.get("scene", 0), len(j["scenes"]))]
     nodes = j.get("nodes", [])
     visited = set()
@@ -367,9 +387,144 @@ def load_model(path, flip_winding_order=True):
             prims = j["meshes"][_index(node["mesh"], len(j["meshes"]))].get("primitives", [])
             if prims:
                 meshes = [x for x in (process_primitive(p) for p in prims) if x is not None]
-                out.append((S.MeshNode(meshes), m.T.copy()))            # GlobalTransform reinterpreted as a row-vector Matrix
+                mesh_node = S.MeshNode(meshes)
+                mesh_node.name = node.get("name", "")
+                if "skin" in node:                                        # :477-512: joint names + inverse bind matrices, shared per skin index
+                    si = _index(node["skin"], len(j.get("skins", [])))
+                    if si not in skins:
+                        skin = j["skins"][si]
+                        skins[si] = None
+                        if "inverseBindMatrices" in skin:                 # a skin without them is ignored (:484)
+                            ibm = asset.accessor(skin["inverseBindMatrices"])
+                            if ibm.dtype != np.float32 or ibm.shape[1] != 16:
+                                raise ValueError("glTF: inverseBindMatrices is not a MAT4 of floats")
+                            names = [nodes[_index(jn, len(nodes))].get("name", "") for jn in skin.get("joints", [])]
+                            if len(ibm) > len(names):
+                                raise ValueError("glTF: more inverse bind matrices than joints")
+                            # glTF's column-major column-vector matrix, reinterpreted as a row-vector Matrix (:492): the floats as they lie
+                            skins[si] = (names[:len(ibm)], np.ascontiguousarray(ibm, np.float32).reshape(-1, 4, 4))
+                    mesh_node.skin = skins[si]
+                out.append((mesh_node, m.T.copy()))                     # GlobalTransform reinterpreted as a row-vector Matrix
         pending.extend((c, m) for c in reversed(node.get("children", [])))
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# animations
+# ----------------------------------------------------------------------------------------------
+def decompose(m_col):
+    """fastgltf's DecomposeNodeMatrices on a column-vector matrix: translation, rotation (x, y, z, w), scale. The scale is the length of
+    each basis column (the first negated when the basis is left-handed), the rotation what remains."""
+    m = np.asarray(m_col, np.float64)
+    t = m[:3, 3].copy()
+    sc = np.linalg.norm(m[:3, :3], axis=0)
+    if np.linalg.det(m[:3, :3]) < 0:
+        sc[0] = -sc[0]
+    r = m[:3, :3] / np.where(sc == 0, 1.0, sc)
+    tr = r[0, 0] + r[1, 1] + r[2, 2]
+    if tr > 0:
+        k = math.sqrt(tr + 1.0) * 2
+        q = ((r[2, 1] - r[1, 2]) / k, (r[0, 2] - r[2, 0]) / k, (r[1, 0] - r[0, 1]) / k, 0.25 * k)
+    elif r[0, 0] > r[1, 1] and r[0, 0] > r[2, 2]:
+        k = math.sqrt(1.0 + r[0, 0] - r[1, 1] - r[2, 2]) * 2
+        q = (0.25 * k, (r[0, 1] + r[1, 0]) / k, (r[0, 2] + r[2, 0]) / k, (r[2, 1] - r[1, 2]) / k)
+    elif r[1, 1] > r[2, 2]:
+        k = math.sqrt(1.0 + r[1, 1] - r[0, 0] - r[2, 2]) * 2
+        q = ((r[0, 1] + r[1, 0]) / k, 0.25 * k, (r[1, 2] + r[2, 1]) / k, (r[0, 2] - r[2, 0]) / k)
+    else:
+        k = math.sqrt(1.0 + r[2, 2] - r[0, 0] - r[1, 1]) * 2
+        q = ((r[0, 2] + r[2, 0]) / k, (r[1, 2] + r[2, 1]) / k, 0.25 * k, (r[1, 0] - r[0, 1]) / k)
+    return t, np.array(q), sc
+
+
+_PATHS = {"translation": (0, 3), "rotation": (1, 4), "scale": (2, 3)}
+
+
+def load_animation(path):
+    """GLTFHelpers::LoadAnimation (GLTFHelpers.ixx:539-663) -> scenes.Rig: the default scene's node forest flattened depth first with its
+    decomposed TRS, one clip per glTF animation. LINEAR samplers only (STEP and CUBICSPLINE channels are skipped, :582-584), channels
+    without a target node are skipped, and per node NAME and path the first channel wins (:593, :616, :639); a clip's duration is the
+    largest key time of the channels it accepted.
+
+    The reference keeps keyframes and global transforms in maps keyed by node name. Names are resolved to indices HERE, with the maps'
+    semantics: the keyframes of a name apply to every node of the forest that carries it (ComputeTransforms looks them up per node,
+    Animation.ixx:123), and a lookup BY name (a mesh node, a joint: find_node) finds the LAST node of that name in traversal order,
+    because m_globalTransforms[name] is overwritten (:138)."""
+    asset = _Asset(path)
+    j = asset.j
+    nodes = j.get("nodes", [])
+    scene = j["scenes"][_index(j.get("scene", 0), len(j["scenes"]))]
+    parents, rest, names, visited = [], [], [], set()
+    pending = [(ni, -1) for ni in reversed(scene.get("nodes", []))]
+    while pending:
+        ni, parent = pending.pop()
+        if _index(ni, len(nodes)) in visited:
+            raise ValueError(f"glTF: node {ni} is reached twice (a cycle, or a second parent)")
+        visited.add(ni)
+        node = nodes[ni]
+        if "matrix" in node:
+            t, q, sc = decompose(np.array(node["matrix"], np.float64).reshape(4, 4).T)
+        else:
+            t, q, sc = (np.array(node.get(k, d), np.float64) for k, d in (("translation", (0, 0, 0)), ("rotation", (0, 0, 0, 1)), ("scale", (1, 1, 1))))
+        if t.shape != (3,) or q.shape != (4,) or sc.shape != (3,):
+            raise ValueError(f"glTF: node {ni}: translation / rotation / scale of the wrong length")
+        me = len(parents)
+        parents.append(parent); rest.append(np.concatenate([t, q, sc])); names.append(node.get("name", ""))
+        pending.extend((c, me) for c in reversed(node.get("children", [])))
+    n = len(parents)
+    anims = j.get("animations", [])
+    channels = np.zeros((len(anims), n, 3, 2), np.uint32)
+    key_times, key_values, durations, clip_names = [], [], [], []
+    for ci, anim in enumerate(anims):
+        duration = np.float32(0)
+        taken = {}                                                        # (node name, path) -> (FirstKey, KeyCount): the first channel wins
+        samplers = anim.get("samplers", [])
+        for ch in anim.get("channels", []):
+            target = ch.get("target") or {}
+            if "node" not in target:
+                continue
+            sampler = samplers[_index(ch["sampler"], len(samplers))]
+            if sampler.get("interpolation", "LINEAR") != "LINEAR":
+                continue
+            if target.get("path") not in _PATHS:                          # weights: morph targets are out of scope
+                continue
+            slot, ncomp = _PATHS[target["path"]]
+            name = nodes[_index(target["node"], len(nodes))].get("name", "")
+            if (name, slot) in taken:
+                continue
+            times = asset.accessor(sampler["input"]); values = asset.accessor(sampler["output"])
+            if times.dtype != np.float32 or times.shape[1] != 1:
+                raise ValueError("glTF: an animation sampler's input is not a SCALAR of floats")
+            if values.shape[1] != ncomp or values.dtype.kind != "f":
+                raise ValueError(f"glTF: an animation sampler's output does not fit the {target['path']} path")
+            if len(times) != len(values):
+                raise ValueError("glTF: an animation sampler's input and output counts differ")
+            if len(times) == 0:
+                continue                                                  # an empty channel leaves the slot empty: a later one may take it
+            times = times.reshape(-1)
+            if not np.all(np.isfinite(times)) or not np.all(np.isfinite(values)) or np.any(np.diff(times) <= 0):
+                raise ValueError("glTF: key times must be finite and strictly ascending, key values finite")
+            taken[(name, slot)] = (len(key_times), len(times))
+            key_times += times.tolist()
+            key_values += np.pad(values.astype(np.float32), ((0, 0), (0, 4 - ncomp))).tolist()
+            duration = max(duration, np.float32(times.max()))
+        for ni in range(n):                                               # the keyframes of a name apply to every node that carries it
+            for slot in range(3):
+                if (names[ni], slot) in taken:
+                    channels[ci, ni, slot] = taken[(names[ni], slot)]
+        durations.append(float(duration)); clip_names.append(anim.get("name", ""))
+    if not anims:
+        raise ValueError(f"{path}: the file holds no animation")
+    return S.Rig(np.asarray(parents, np.int32), np.asarray(rest, np.float32).reshape(n, 10), np.asarray(durations, np.float64), channels,
+                 np.asarray(key_times, np.float32), np.asarray(key_values, np.float32).reshape(-1, 4), names=names, clip_names=clip_names)
+
+
+def find_node(rig, name):
+    """m_globalTransforms.find(name): the LAST node of that name in traversal order (the map entry is overwritten), or NO_NODE."""
+    for ni in range(len(rig.names) - 1, -1, -1):
+        if rig.names[ni] == name:
+            return ni
+    return S.NO_NODE
 
 
 # ----------------------------------------------------------------------------------------------
@@ -384,25 +539,55 @@ def camera_from_desc(desc, aspect, hfov_deg=90.0, near=0.01):
     return S.make_camera(desc["Camera"]["Position"], forward=fwd[:3], up=up, hfov_deg=hfov_deg, aspect=aspect, near=near)
 
 
+def _copy_mesh(m):
+    import copy
+    c = copy.copy(m)
+    c.vertices = m.vertices.copy(); c.motion_vectors = m.motion_vectors.copy() if m.motion_vectors is not None else None
+    return c
+
+
 def load_scene(path, aspect=16 / 9):
     desc = load_scene_desc(path)
-    models = {}
-    nodes, objects = [], []
+    models, rigs = {}, {}
+    nodes, objects, animations = [], [], []
     zflip = np.diag([1.0, 1.0, -1.0, 1.0])
     for ro in desc["RenderObjects"]:
         if not ro["Model"]:
             continue
         if ro["Model"] not in models:
             models[ro["Model"]] = load_model(desc["Models"][ro["Model"]], flip_winding_order=True)    # Scene.ixx:90
+        rig = None
+        if ro["Animation"]:                                               # Scene.ixx:165-168: a copy of the collection, bound to the model's skins
+            if ro["Animation"] not in rigs:
+                rigs[ro["Animation"]] = load_animation(desc["Animations"][ro["Animation"]])
+            rig = rigs[ro["Animation"]]
+        binding_nodes, binding_instances, binding_globals, skins = [], [], [], []
+        # Model.SkinJoints is a dictionary keyed by the mesh node's name: the last skin stored under a name serves every mesh node of that name
+        skin_of = {mn.name: mn.skin for mn, _ in models[ro["Model"]] if getattr(mn, "skin", None) is not None}
         for mesh_node, g in models[ro["Model"]]:
+            if rig is not None and any(m.skeletal_vertices is not None for m in mesh_node.meshes):
+                # the skinning pass rewrites the vertex buffer in place: a skinned mesh node is instanced once per animated render object
+                mesh_node = S.MeshNode([_copy_mesh(m) for m in mesh_node.meshes], name=mesh_node.name, skin=mesh_node.skin)
             key = id(mesh_node)
             if key not in [id(n) for n in nodes]:
                 nodes.append(mesh_node)
             world = g @ zflip @ ro["Transform"]                           # Scene.ixx:199-214
+            if rig is not None:
+                binding_nodes.append(find_node(rig, mesh_node.name)); binding_instances.append(len(objects)); binding_globals.append(g)
+                skin = skin_of.get(mesh_node.name)
+                if skin is not None:
+                    skins.append(S.Skin(find_node(rig, mesh_node.name), np.array([find_node(rig, nm) for nm in skin[0]], np.uint32), skin[1],
+                                        scene_node=[id(n) for n in nodes].index(key)))
             objects.append(S.RenderObject([id(n) for n in nodes].index(key), store_float3x4(world), ro["IsVisible"]))
+        if rig is not None:
+            animations.append(S.AnimatedObject(rig, ro["Transform"].astype(np.float32), np.array(binding_nodes, np.uint32),
+                                               np.array(binding_instances, np.uint32), np.array(binding_globals, np.float32).reshape(-1, 4, 4), skins))
     sd = S.make_scene_data(desc["EnvironmentLight"]["Color"])
     sd["EnvironmentLightTransform"] = store_float3x4(desc["EnvironmentLight"]["Rotation"])     # App.cpp:1019
+    if animations:
+        sd["IsStatic"] = 0
     sc = S.Scene(nodes, objects, camera_from_desc(desc, aspect), sd, name=os.path.basename(path))
+    sc.animations = animations
     tex = desc["EnvironmentLight"]["Texture"]
     if tex:
         from PIL import Image

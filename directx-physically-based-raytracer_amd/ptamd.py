@@ -21,7 +21,7 @@ _LIB = None
 EXPORTS = [
     "pt_abi_version", "pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_sync", "pt_set_frames_in_flight", "pt_set_round_chains",
     "pt_heap_resize", "pt_heap_set_buffer", "pt_heap_set_texture", "pt_build_bottom_level", "pt_update_bottom_level", "pt_release_bottom_level", "pt_skin_mesh",
-    "pt_build_top_level", "pt_get_accel_stats", "pt_share_scene", "pt_set_camera", "pt_set_scene_data", "pt_set_object_data", "pt_invalidate_object_data",
+    "pt_build_top_level", "pt_build_top_level_posed", "pt_get_accel_stats", "pt_share_scene", "pt_set_camera", "pt_set_scene_data", "pt_set_object_data", "pt_invalidate_object_data",
     "pt_set_instance_data", "pt_set_sharding", "pt_local_rows", "pt_deinterleave_bands", "pt_gbuffer_render",
     "pt_comm_get_unique_id", "pt_comm_init", "pt_comm_adopt", "pt_comm_destroy", "pt_gather_bands", "pt_gather_plan",
     "pt_raytrace_set_constants", "pt_raytrace_render", "pt_trace_visibility", "pt_bsdf_evaluate", "pt_bsdf_sample", "pt_reset_counters", "pt_get_counters",
@@ -30,6 +30,8 @@ EXPORTS = [
     "pt_di_set_light_sampling", "pt_di_download_presampled", "pt_di_set_visibility", "pt_di_set_pairwise",
     "pt_di_set_regir_layout", "pt_di_regir_onion_table", "pt_di_set_brdf_sampling", "pt_di_download_brdf_candidates",
     "pt_post_set_constants", "pt_post_render", "pt_post_download_bloom",
+    "pt_anim_create_rig", "pt_anim_release_rig", "pt_anim_create_object", "pt_anim_release_object", "pt_anim_evaluate",
+    "pt_anim_skeletal_transforms", "pt_anim_download_globals", "pt_anim_download_skeletal", "pt_anim_debug_slerp",
     "pt_sharc_configure", "pt_sharc_set_constants", "pt_raytrace_render_sharc", "pt_sharc_reset", "pt_sharc_download",
     "pt_sharc_debug_keys", "pt_sharc_debug_query", "pt_sharc_download_update_paths", "pt_sharc_download_update_scatter",
     "pt_set_debug_flags", "pt_debug_read_mismatch", "pt_debug_download_blob", "pt_debug_trace_ray", "pt_debug_trace_closest", "pt_enable_kernel_timing", "pt_get_kernel_timing", "pt_get_round_timing",
@@ -120,6 +122,10 @@ class BsdfSampleResult(C.Structure):
                 ("Lobe", C.c_uint32), ("Ok", C.c_uint32)]
 
 
+class AnimState(C.Structure):               # struct PtAnimState, 24 B
+    _fields_ = [("Object", C.c_uint64), ("Clip", C.c_uint32), ("_pad", C.c_uint32), ("Time", C.c_double)]
+
+
 CLOSEST_HIT = np.dtype([("T", "<f4"), ("U", "<f4"), ("V", "<f4"), ("Instance", "<u4"), ("Geometry", "<u4"), ("Primitive", "<u4"),
                         ("Slot", "<u4"), ("_pad", "<u4")])          # PtClosestHit, 32 B
 
@@ -151,6 +157,18 @@ def load_library():
         lib.pt_update_bottom_level.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32]
         lib.pt_skin_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         lib.pt_build_top_level.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        lib.pt_build_top_level_posed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.pt_anim_create_rig.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_uint32, C.POINTER(C.c_uint64)]
+        lib.pt_anim_release_rig.argtypes = [C.c_void_p, C.c_uint64]
+        lib.pt_anim_create_object.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.pt_anim_release_object.argtypes = [C.c_void_p, C.c_uint64]
+        lib.pt_anim_evaluate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.pt_anim_skeletal_transforms.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+        lib.pt_anim_download_globals.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.pt_anim_download_skeletal.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.pt_anim_debug_slerp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.pt_get_accel_stats.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_share_scene.argtypes = [C.c_void_p, C.c_void_p]
         for f in (lib.pt_set_camera, lib.pt_set_scene_data, lib.pt_set_sharding, lib.pt_raytrace_set_constants,
@@ -434,6 +452,7 @@ class Scene:
         self._heap_dev = heap_dev
         self.blas_ids = []
         self._skin_cache = {}
+        self._skeletal_dev = {}           # Animate: the skeletal vertices of a skinned mesh, uploaded once
         self.CreateAccelerationStructures()
 
     def close(self):
@@ -522,8 +541,8 @@ class Scene:
             self.blas_ids.append(bid.value)
         self._build_top_level()
 
-    def _build_top_level(self):
-        """instance descs as Scene::CreateAccelerationStructures fills them (Scene.ixx:365-377). The array is kept: a dynamic frame
+    def _build_top_level(self, posed=None):
+        """posed: the from_device bytes of pt_build_top_level_posed (Animate), or None: pt_build_top_level. instance descs as Scene::CreateAccelerationStructures fills them (Scene.ixx:365-377). The array is kept: a dynamic frame
         re-submits it as it is (transforms of the static instances do not move; update_instance_transform() for those that do)."""
         ctx, scene, lib = self.ctx, self.desc, self.ctx.lib
         n = len(scene.objects)
@@ -536,10 +555,164 @@ class Scene:
                 descs[i].InstanceMask = int(scene.instance_masks[i])
                 descs[i].AccelerationStructure = self.blas_ids[int(scene.instance_blas[i])]
             self._descs, self._descs_ids = descs, list(self.blas_ids)
+        if posed is not None:
+            ctx.check(lib.pt_build_top_level_posed(ctx.handle, C.addressof(self._descs), n, 0x4, C.c_void_p(self.instance_data.data_ptr()),
+                                                   C.c_void_p(posed.ctypes.data)))
+            return
         ctx.check(lib.pt_build_top_level(ctx.handle, C.addressof(self._descs), n, 0x4))
 
     def GetTopLevelAccelerationStructure(self):
         return self.ctx.handle        # the context owns the single TLAS
+
+    def Animate(self, animation):
+        """One dynamic frame's update in the reference's order (Scene::Tick -> Refresh -> SkinSkeletalMeshes -> CreateAccelerationStructures,
+        Source/Scene.ixx:174-188, 195-380), all of it enqueued on the stream, nothing computed or copied by the host but the few bytes of
+        the states: pt_anim_evaluate poses every animated object at its current time (joint matrices and InstanceData on the device),
+        pt_skin_mesh reads the joint matrices where the pose left them, the skinned mesh nodes are refitted, and the top level takes the
+        posed instances' transforms from the device."""
+        ctx, lib = self.ctx, self.ctx.lib
+        animation.Evaluate(self.instance_data)
+        for obj, handle in zip(animation.objects, animation.handles):
+            for k, skin in enumerate(obj.skins):
+                if skin.scene_node is None:
+                    continue
+                ptr, count = animation.skeletal_transforms(handle, k)
+                for mesh in self.desc.nodes[skin.scene_node].meshes:
+                    if mesh.skeletal_vertices is None:
+                        continue
+                    if id(mesh) not in self._skeletal_dev:
+                        self._skeletal_dev[id(mesh)] = to_device(mesh.skeletal_vertices, self.device)
+                    hv = next(h for m, h, _ in self.desc.geometry if m is mesh)
+                    hm = int(self.desc._motion_heap[id(mesh)])
+                    ctx.check(lib.pt_skin_mesh(ctx.handle, C.c_void_p(self._skeletal_dev[id(mesh)].data_ptr()), C.c_void_p(ptr),
+                                               C.c_void_p(self._heap_dev[hv].data_ptr()), C.c_void_p(self._heap_dev[hm].data_ptr()), len(mesh.vertices)))
+        for node_index in animation.skinned_nodes:
+            geoms, count, flags = self._geometry_descs(node_index)
+            ctx.check(lib.pt_update_bottom_level(ctx.handle, self.blas_ids[node_index], C.addressof(geoms), count, flags))
+        self._build_top_level(posed=animation.from_device(len(self.desc.objects)))
+
+
+def _vp(a):
+    return C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+
+
+class Animation:
+    """The animated render objects of a scene (scenes.AnimatedObject) on the device: one rig per animation file (shared by the objects
+    that name it), one animated object per render object -- the reference binds a copy of the AnimationCollection to every render
+    object (Source/Scene.ixx:165-168) --, and per object the selected clip and its time, as Animation::m_time
+    (Source/Animation.ixx:104-113). Nothing here computes a matrix: Scene.Animate hands the times to the device."""
+
+    def __init__(self, ctx, objects):
+        """ctx None: the clock alone (clips and times), nothing on a device."""
+        self.ctx, self.objects = ctx, list(objects)
+        lib = ctx.lib if ctx is not None else None
+        self.rigs, self.handles = {}, []
+        for o in (self.objects if ctx is not None else []):
+            r = o.rig
+            if id(r) not in self.rigs:
+                n = len(r.parents)
+                arrays = (np.ascontiguousarray(r.parents, np.int32), np.ascontiguousarray(r.rest, np.float32).reshape(n, 10),
+                          np.ascontiguousarray(r.durations, np.float64), np.ascontiguousarray(r.channels, np.uint32).reshape(len(r.durations), n, 3, 2),
+                          np.ascontiguousarray(r.key_times, np.float32), np.ascontiguousarray(r.key_values, np.float32).reshape(-1, 4))
+                h = C.c_uint64(0)
+                ctx.check(lib.pt_anim_create_rig(ctx.handle, n, _vp(arrays[0]), _vp(arrays[1]), len(arrays[2]), _vp(arrays[2]), _vp(arrays[3]),
+                                                 _vp(arrays[4]), _vp(arrays[5]), len(arrays[4]), C.byref(h)))
+                self.rigs[id(r)] = h.value
+            bn = np.ascontiguousarray(o.binding_nodes, np.uint32); bi = np.ascontiguousarray(o.binding_instances, np.uint32)
+            bg = np.ascontiguousarray(o.binding_globals, np.float32).reshape(len(bn), 16)
+            sn = np.array([s.mesh_node for s in o.skins], np.uint32); sc = np.array([len(s.joint_nodes) for s in o.skins], np.uint32)
+            jn = np.concatenate([np.asarray(s.joint_nodes, np.uint32) for s in o.skins]) if o.skins else np.zeros(0, np.uint32)
+            ib = (np.concatenate([np.asarray(s.inverse_binds, np.float32).reshape(-1, 16) for s in o.skins]) if o.skins else np.zeros((0, 16), np.float32))
+            tr = np.ascontiguousarray(o.transform, np.float32).reshape(16)
+            h = C.c_uint64(0)
+            ctx.check(lib.pt_anim_create_object(ctx.handle, self.rigs[id(o.rig)], _vp(tr), len(bn), _vp(bn), _vp(bi), _vp(bg), len(sn), _vp(sn), _vp(sc),
+                                                _vp(jn), _vp(np.ascontiguousarray(ib)), C.byref(h)))
+            self.handles.append(h.value)
+        self.clips = [min(int(o.clip), len(o.rig.durations) - 1) for o in self.objects]      # AnimationCollection::GetSelectedIndex
+        self.times = [0.0] * len(self.objects)
+        self.skinned_nodes = sorted({s.scene_node for o in self.objects for s in o.skins if s.scene_node is not None})
+        self._states = (AnimState * max(1, len(self.objects)))()
+        self._from_device = None
+
+    def duration(self, i):
+        return float(self.objects[i].rig.durations[self.clips[i]])
+
+    def SetSelectedIndex(self, i, clip):
+        self.clips[i] = min(int(clip), len(self.objects[i].rig.durations) - 1)
+
+    def SetTime(self, seconds=0.0, index=None):
+        """Animation::SetTime: clamp(seconds, 0, duration), for one object or for all."""
+        for i in (range(len(self.objects)) if index is None else [index]):
+            self.times[i] = min(max(float(seconds), 0.0), self.duration(i))
+
+    def Tick(self, elapsed_seconds, index=None):
+        """Animation::Tick: time = fmod(time + elapsed, duration). A clip of duration 0 stays at time 0 (the reference's fmod yields NaN)."""
+        import math
+        for i in (range(len(self.objects)) if index is None else [index]):
+            d = self.duration(i)
+            self.times[i] = math.fmod(self.times[i] + float(elapsed_seconds), d) if d > 0.0 else 0.0
+
+    def Evaluate(self, device_instances=None):
+        """pt_anim_evaluate of every object at its clip and time. device_instances: the scene's InstanceData tensor, or None."""
+        for i, h in enumerate(self.handles):
+            self._states[i].Object, self._states[i].Clip, self._states[i].Time = h, self.clips[i], self.times[i]
+        self.ctx.check(self.ctx.lib.pt_anim_evaluate(self.ctx.handle, C.addressof(self._states), len(self.handles),
+                                                     C.c_void_p(device_instances.data_ptr()) if device_instances is not None else None))
+
+    def from_device(self, instance_count):
+        """The from_device bytes of pt_build_top_level_posed: 1 for every instance an object's bindings pose."""
+        if self._from_device is None or len(self._from_device) != max(1, instance_count):
+            m = np.zeros(max(1, instance_count), np.uint8)
+            for o in self.objects:
+                m[np.asarray(o.binding_instances, np.int64)] = 1
+            self._from_device = m
+        return self._from_device
+
+    def skeletal_transforms(self, handle, skin):
+        """(device pointer, joint count) of a skin's float3x4 matrices: what pt_skin_mesh takes."""
+        p, n = C.c_void_p(), C.c_uint32(0)
+        self.ctx.check(self.ctx.lib.pt_anim_skeletal_transforms(self.ctx.handle, handle, skin, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def _download(self, fn, shape, *lead):
+        n = C.c_uint32(0)
+        self.ctx.check(fn(self.ctx.handle, *lead, None, 0, C.byref(n)))
+        out = np.zeros((n.value,) + shape, np.float32)
+        if n.value:
+            self.ctx.check(fn(self.ctx.handle, *lead, C.c_void_p(out.ctypes.data), n.value, C.byref(n)))
+        return out
+
+    def download_globals(self, i):
+        """The global transforms of object i's last evaluation, [nodes, 4, 4] float32 (row-vector convention). Synchronises."""
+        return self._download(self.ctx.lib.pt_anim_download_globals, (4, 4), self.handles[i])
+
+    def download_skeletal(self, i, skin):
+        """A skin's float3x4 matrices as the last evaluation left them, [joints, 3, 4] float32. Synchronises."""
+        return self._download(self.ctx.lib.pt_anim_download_skeletal, (3, 4), self.handles[i], skin)
+
+    def close(self):
+        ctx = self.ctx
+        if getattr(ctx, "handle", None):
+            for h in self.handles:
+                ctx.lib.pt_anim_release_object(ctx.handle, h)
+            for h in self.rigs.values():
+                ctx.lib.pt_anim_release_rig(ctx.handle, h)
+        self.handles, self.rigs = [], {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def debug_slerp(ctx, q0, q1, t):
+    """pt_anim_debug_slerp: the device's slerp on host cases; [n, 12] float32 (result, then c, x, s, w, a0, a1, sin a0, sin a1)."""
+    q0 = np.ascontiguousarray(q0, np.float32).reshape(-1, 4); q1 = np.ascontiguousarray(q1, np.float32).reshape(-1, 4)
+    t = np.ascontiguousarray(t, np.float32).reshape(-1)
+    out = np.zeros((len(t), 12), np.float32)
+    ctx.check(ctx.lib.pt_anim_debug_slerp(ctx.handle, _vp(q0), _vp(q1), _vp(t), len(t), _vp(out)))
+    return out
 
 
 def alloc_textures(width, local_rows_, device, with_f32=False, with_denoiser_outputs=False):

@@ -102,6 +102,8 @@ class Mesh:                      # Source/Model.ixx:26-47
 @dataclass
 class MeshNode:                  # Source/Model.ixx:58-70: one BLAS per mesh node
     meshes: list
+    name: str = ""               # MeshNode::NodeName: what an animation's global transforms are looked up by
+    skin: tuple = None           # (joint node names, inverse bind matrices [joints, 4, 4] row-vector) of the node's skin (Model.SkinJoints)
 
 
 @dataclass
@@ -109,6 +111,40 @@ class RenderObject:              # one instance of a mesh node with its world tr
     node: int
     transform: np.ndarray
     visible: bool = True
+
+
+NO_NODE = 0xFFFFFFFF             # PT_ANIM_NO_NODE: a name the animation file has no node for
+
+
+@dataclass
+class Rig:                       # one animation file, names resolved to indices (ingest.load_animation; include/ptamd.h pt_anim_create_rig)
+    parents: np.ndarray          # int32 [nodes]: depth-first, parent < own index, -1 for a root
+    rest: np.ndarray             # float32 [nodes, 10]: Translation, Rotation (x, y, z, w), Scale
+    durations: np.ndarray        # float64 [clips]
+    channels: np.ndarray         # uint32 [clips, nodes, 3 (T, R, S), 2 (FirstKey, KeyCount)]
+    key_times: np.ndarray        # float32 [keys]
+    key_values: np.ndarray       # float32 [keys, 4]
+    names: list = None           # node names, clip names (informational)
+    clip_names: list = None
+
+
+@dataclass
+class Skin:                      # one skinned mesh node of a render object
+    mesh_node: int               # rig node of the mesh node, or NO_NODE
+    joint_nodes: np.ndarray      # uint32 [joints]: rig node per joint, or NO_NODE
+    inverse_binds: np.ndarray    # float32 [joints, 4, 4], row-vector convention
+    scene_node: int = None       # index into Scene.nodes: the meshes to skin and the bottom level to refit
+
+
+@dataclass
+class AnimatedObject:            # a render object with an animation bound (Scene.ixx:165-168)
+    rig: Rig
+    transform: np.ndarray        # float32 [4, 4]: RenderObject.Transform(), row-vector convention
+    binding_nodes: np.ndarray    # uint32 [mesh nodes]: rig node per mesh node, or NO_NODE
+    binding_instances: np.ndarray  # uint32: the instance each mesh node became
+    binding_globals: np.ndarray  # float32 [mesh nodes, 4, 4]: MeshNode::GlobalTransform, used where the node is NO_NODE
+    skins: list = field(default_factory=list)
+    clip: int = 0                # AnimationCollection's selected index
 
 
 def trs(translation=(0, 0, 0), yaw_deg=0.0, scale=(1, 1, 1), pitch_deg=0.0):
@@ -140,6 +176,7 @@ class Scene:
     instance_ids: np.ndarray = None
     instance_masks: np.ndarray = None
     instance_blas: np.ndarray = None
+    animations: list = field(default_factory=list)    # AnimatedObject per animated render object (ptamd.Animation plays them)
 
     def finalize(self):
         """Scene::Refresh + App::UpdateScene: InstanceData / ObjectData / descriptor heap."""
@@ -508,6 +545,64 @@ def dynamic_scene(aspect=16 / 9, meshes=None):
     return Scene(nodes, objects, cam, make_scene_data((0.05, 0.06, 0.08, 1), is_static=False), name="dynamic").finalize()
 
 
+def quat_z(deg):
+    """unit quaternion (x, y, z, w) of a rotation about Z"""
+    a = math.radians(deg) / 2
+    return (0.0, 0.0, math.sin(a), math.cos(a))
+
+
+def rig_from_channels(parents, rest, clips, names=None):
+    """A Rig from per-clip dictionaries {(node, path): (times, values)}, path 0 T, 1 R, 2 S; a clip's duration is its largest key time."""
+    n = len(parents)
+    channels = np.zeros((len(clips), n, 3, 2), np.uint32)
+    times, values, durations = [], [], []
+    for ci, clip in enumerate(clips):
+        d = 0.0
+        for (node, path), (kt, kv) in clip.items():
+            kv = np.asarray(kv, np.float32).reshape(len(kt), -1)
+            channels[ci, node, path] = (len(times), len(kt))
+            times += [float(t) for t in kt]
+            values += [tuple(v) + (0.0,) * (4 - len(v)) for v in kv.tolist()]
+            d = max(d, float(np.float32(max(kt))))
+        durations.append(d)
+    return Rig(np.asarray(parents, np.int32), np.asarray(rest, np.float32).reshape(n, 10), np.asarray(durations, np.float64), channels,
+               np.asarray(times, np.float32), np.asarray(values, np.float32).reshape(-1, 4), names=names)
+
+
+def animated_scene(aspect=16 / 9, segments=8):
+    """dynamic_scene's floor, light and two-joint column, plus a small rigid box, moved by a rig instead of a hand-written pose: the smallest
+    scene through which keyframes reach skinning, the refit, the top level and the motion vectors. Rig (depth-first): 0 root, 1 column (the
+    skinned mesh node), 2 joint0, 3 joint1 (child of joint0, at half height), 4 box (rigid). Two clips: 0 bends the column and slides the box,
+    1 twists joint0 and lifts the box. The posed instances carry the reference's Scale(1, 1, -1) (Scene.ixx:199-214)."""
+    white = (0.73, 0.73, 0.73)
+    box = box_mesh(material((0.2, 0.5, 0.8), roughness=0.6))
+    nodes = [MeshNode([quad_mesh((-2, 0, -2), (-2, 0, 2), (2, 0, 2), (2, 0, -2), (0, 1, 0), material(white))]),
+             MeshNode([quad_mesh((-0.5, 0, -0.5), (0.5, 0, -0.5), (0.5, 0, 0.5), (-0.5, 0, 0.5), (0, -1, 0),
+                                 material((0.8, 0.8, 0.8), emissive=(1, 1, 1), strength=10.0))]),
+             MeshNode([skinned_bar(segments)]), MeshNode([box])]
+    objects = [RenderObject(0, trs()), RenderObject(1, trs((0, 2.2, 0))), RenderObject(2, trs((0.1, 0, 0.2), 20.0, (1, 1.2, 1))),
+               RenderObject(3, trs((-0.8, 0.2, 0.1), 0.0, (0.2, 0.2, 0.2)))]
+    cam = make_camera((0, 0.9, -2.2), forward=(0, -0.1, 1), hfov_deg=70.0, aspect=aspect)
+    sc = Scene(nodes, objects, cam, make_scene_data((0.05, 0.06, 0.08, 1), is_static=False), name="animated")
+    ident = (0, 0, 0, 1)
+    rest = [(0.1, 0, 0.2) + quat_z(0) + (1, 1.2, 1), (0, 0, 0) + ident + (1, 1, 1), (0, 0, 0) + ident + (1, 1, 1),
+            (0, 0.5, 0) + ident + (1, 1, 1), (-0.9, 0.2, -0.1) + ident + (0.2, 0.2, 0.2)]
+    clips = [{(3, 1): ([0.0, 0.5, 1.0], [quat_z(0), quat_z(40), quat_z(-25)]), (3, 0): ([0.0, 1.0], [(0, 0.5, 0), (0, 0.6, 0)]),
+              (4, 0): ([0.25, 0.75], [(-0.9, 0.2, -0.1), (-0.5, 0.2, -0.1)]),
+              (4, 1): ([0.0, 1.0], [quat_z(0), tuple(-v for v in quat_z(100))])},      # the same rotation, the other sign: a negative dot
+             {(2, 1): ([0.0, 2.0], [quat_z(0), quat_z(30)]), (4, 0): ([0.0, 1.0, 2.0], [(-0.9, 0.2, -0.1), (-0.9, 0.6, -0.1), (-0.9, 0.2, -0.1)]),
+              (4, 2): ([0.0, 2.0], [(0.2, 0.2, 0.2), (0.3, 0.2, 0.2)])}]
+    rig = rig_from_channels([-1, 0, 0, 2, 0], rest, clips, names=["root", "column", "joint0", "joint1", "box"])
+    # inverse binds: at rest the skeletal transforms are the identity, InverseBind = Global(column) . Global(joint)^-1 (both under the same
+    # root, which cancels): joint0 sits on the column's node, joint1 half way up
+    ib = np.stack([np.eye(4), np.eye(4)]).astype(np.float32)
+    ib[1, 3, 1] = -0.5
+    eye = np.eye(4, dtype=np.float32)
+    sc.animations = [AnimatedObject(rig, eye, np.array([1, 4], np.uint32), np.array([2, 3], np.uint32), np.stack([eye, eye]),
+                                    [Skin(1, np.array([2, 3], np.uint32), ib, scene_node=2)])]
+    return sc.finalize()
+
+
 def _material_textures(rng, size, masked):
     """Procedural RGBA8 texture set of one glTF-style material (Source/GLTFHelpers.ixx:370-428): base colour (sRGB; alpha is a lattice with
     a quarter of its cells cut out when the material is alpha-masked), tangent-space normal map, packed metallic-roughness (G = roughness,
@@ -657,6 +752,24 @@ def dynamic_instanced(n=32, aspect=16 / 9, segments=256):
     sc.scene_data = make_scene_data((0.05, 0.06, 0.08, 1), is_static=False)
     sc.name = "dynamic_instanced"
     return sc.finalize()
+
+
+def animate_bar(scene, swing_deg=30.0, period=4.0, keys=9):
+    """Binds a two-joint rig to the skinned column that is the LAST mesh node / render object of `scene` (dynamic_scene, dynamic_instanced):
+    the keyframed counterpart of bar_pose -- joint 1 swings about Z around the bar's base and lifts. Rig: 0 column (the mesh node, at the
+    object's place), 1 joint0, 2 joint1. The posed instance carries the reference's Scale(1, 1, -1)."""
+    ro = scene.objects[-1]
+    m = np.asarray(ro.transform, np.float64)                    # column-vector [R|t] -> the row-vector RenderObject.Transform()
+    transform = np.eye(4); transform[:3, :3] = m[:, :3].T; transform[3, :3] = m[:, 3]
+    times = [period * k / (keys - 1) for k in range(keys)]
+    clip = {(2, 1): (times, [quat_z(swing_deg * math.sin(2 * math.pi * t / period)) for t in times]),
+            (2, 0): (times, [(0.0, 0.05 * (k % 3), 0.0) for k in range(keys)])}
+    ident = (0.0, 0.0, 0.0) + (0.0, 0.0, 0.0, 1.0) + (1.0, 1.0, 1.0)
+    rig = rig_from_channels([-1, 0, 1], [ident, ident, ident], [clip], names=["column", "joint0", "joint1"])
+    eye = np.eye(4, dtype=np.float32)
+    scene.animations = [AnimatedObject(rig, transform.astype(np.float32), np.array([0], np.uint32), np.array([len(scene.objects) - 1], np.uint32), eye[None],
+                                       [Skin(0, np.array([1, 2], np.uint32), np.stack([eye, eye]), scene_node=len(scene.nodes) - 1)])]
+    return scene
 
 
 def graphics_settings(width, height, spp=1, bounces=8, frame_index=0, russian_roulette=True, ext_flags=0,

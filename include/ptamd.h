@@ -267,6 +267,69 @@ typedef struct PtInstanceDesc {           /* D3D12_RAYTRACING_INSTANCE_DESC as f
  * boxes and the traversal copy are made by kernels; a rebuild that needs no more room than the last one allocates nothing and
  * waits for nothing. A tree too deep for the traversal stack is reported by the next pt_sync / render call. */
 int  pt_build_top_level(PtContext* ctx, const PtInstanceDesc* descs, uint32_t count, uint32_t build_flags);
+/* pt_build_top_level with one addition: for every i with from_device[i] != 0 the instance's transform is read ON THE DEVICE from
+ * device_instances[i].ObjectToWorld (what pt_anim_evaluate wrote there, in stream order), not from descs[i].Transform: one small kernel
+ * patches the uploaded instance sources in front of the instance-record kernel. from_device is HOST memory, count bytes; device_instances
+ * must be the array bound with pt_set_instance_data and reach every instance from_device names (refused otherwise). With
+ * from_device NULL or all zero the call IS pt_build_top_level (same launches); device_instances may then be NULL. */
+int  pt_build_top_level_posed(PtContext* ctx, const PtInstanceDesc* descs, uint32_t count, uint32_t build_flags,
+                              const PtInstanceData* device_instances, const uint8_t* from_device);
+
+/* ------------------------------------------------------------------------------------------
+ * animation playback on the device (Source/Animation.ixx: KeyframeCollection::Interpolate :45-75, Animation::ComputeTransforms :119-162;
+ * Scene::Refresh, Source/Scene.ixx:195-231). A rig holds the node forest, the clips and the keys of one animation file; an animated
+ * object binds a rig to one render object (the reference copies the collection per render object, Scene.ixx:165-168) and owns the
+ * device buffers of its results; pt_anim_evaluate poses any number of objects in ONE launch on the context's stream, with no allocation
+ * and no wait in the steady state. DESIGN.md section 1, "Animation", is the arithmetic spec (DirectXMath is not part of the reference
+ * tree: parity with it is unpinned). Matrices are row-major 4x4 in the reference's row-vector convention unless stated otherwise. The
+ * reference matches nodes by NAME; names are resolved to indices by the host (ingest) with the reference's map semantics.
+ * All arrays of the create calls are HOST memory, copied during the call.
+ * ------------------------------------------------------------------------------------------ */
+#define PT_ANIM_NO_NODE 0xFFFFFFFFu
+/* One state of pt_anim_evaluate: which object, which clip of its rig, at what time in seconds. 24 B. (Tagged, not a typedef: C callers
+ * write `struct PtAnimState`.) */
+struct PtAnimState { uint64_t Object; uint32_t Clip; uint32_t _pad; double Time; };
+/* parents[node_count]: index of the parent, < the node's own index (depth-first order), -1 for a root.
+ * rest_trs[node_count * 10]: Translation[3], Rotation[4] (x, y, z, w), Scale[3] of the node's rest transform.
+ * durations[clip_count]; channels[clip_count * node_count * 3 * 2]: per clip, node and path (0 T, 1 R, 2 S) {FirstKey, KeyCount}
+ * into key_times[key_count] / key_values[key_count * 4] (T / S keys use xyz); KeyCount 0: the path keeps the rest value.
+ * Refused: a parent >= its node, key times of a channel not strictly ascending or not finite, non-finite key values or rest TRS, a
+ * channel that runs beyond key_count, a duration that is negative or not finite. */
+int  pt_anim_create_rig(PtContext* ctx, uint32_t node_count, const int32_t* parents, const float* rest_trs,
+                        uint32_t clip_count, const double* durations, const uint32_t* channels,
+                        const float* key_times, const float* key_values, uint32_t key_count, uint64_t* out_rig);
+int  pt_anim_release_rig(PtContext* ctx, uint64_t rig);       /* refused while an object refers to it; synchronises */
+/* transform16: RenderObject.Transform(). Bindings (one per mesh node of the render object): binding_nodes[i] = the rig node whose
+ * global transform moves instance binding_instances[i], or PT_ANIM_NO_NODE: binding_globals16[16 * i] (MeshNode::GlobalTransform) is
+ * used instead (Scene.ixx:213). Skins (one per skinned mesh node): skin_mesh_nodes[s] = the rig node of the mesh node (PT_ANIM_NO_NODE:
+ * the skin's matrices are never written), skin_joint_counts[s] joints, whose rig nodes (PT_ANIM_NO_NODE: that joint's matrix is never
+ * written) and inverse bind matrices follow one another in joint_nodes / inverse_binds16. Matrices never written stay zero. */
+int  pt_anim_create_object(PtContext* ctx, uint64_t rig, const float* transform16,
+                           uint32_t binding_count, const uint32_t* binding_nodes, const uint32_t* binding_instances, const float* binding_globals16,
+                           uint32_t skin_count, const uint32_t* skin_mesh_nodes, const uint32_t* skin_joint_counts,
+                           const uint32_t* joint_nodes, const float* inverse_binds16, uint64_t* out_object);
+int  pt_anim_release_object(PtContext* ctx, uint64_t object); /* synchronises */
+/* Poses states[0 .. count) (HOST memory, staged through a pinned ring like pt_build_top_level's upload): per object the global
+ * transform of every node, the skeletal transforms InverseBind . Global(joint) . Global(meshNode)^-1 of every skin (float3x4, the layout
+ * pt_skin_mesh reads), and -- when device_instances is not NULL -- for every binding
+ *   ObjectToWorld = To3x4(Global(meshNode) . Scale(1, 1, -1) . transform16),  PreviousObjectToWorld = the ObjectToWorld it replaces
+ * (on an object's first evaluation: the new ObjectToWorld). device_instances must be the array bound with pt_set_instance_data (its
+ * count bounds the bindings' instance indices). A clip with Duration 0 is posed at time 0; a Time beyond the keys clamps per channel.
+ * Refused, with nothing modified: an unknown object, an object named twice in one call, a clip out of range, a Time that is not
+ * finite, a binding beyond the bound instance data. */
+int  pt_anim_evaluate(PtContext* ctx, const struct PtAnimState* states, uint32_t count, PtInstanceData* device_instances);
+/* the device array of skin `skin`'s float3x4 matrices (owned by the object, rewritten by every pt_anim_evaluate): goes straight into
+ * pt_skin_mesh */
+int  pt_anim_skeletal_transforms(PtContext* ctx, uint64_t object, uint32_t skin, const float** device_ptr, uint32_t* joint_count);
+/* test aid: the global transforms of the last evaluation, 16 floats per node; out_count = nodes; min(capacity, nodes) matrices are
+ * copied. Synchronises. */
+int  pt_anim_download_globals(PtContext* ctx, uint64_t object, float* host_dst16, uint32_t capacity, uint32_t* out_count);
+/* test aid: skin `skin`'s float3x4 matrices as the last evaluation left them, 12 floats per joint; out_count = joints. Synchronises. */
+int  pt_anim_download_skeletal(PtContext* ctx, uint64_t object, uint32_t skin, float* host_dst12, uint32_t capacity, uint32_t* out_count);
+/* test aid: the device's slerp on n host cases (q0[4n], q1[4n], t[n]); out[12n]: the result (4), then the intermediates c = dot (after
+ * the sign flip), x = 1 - c c, s = sqrtf(x), w = atan2f(s, c), a0 = (1 - t) w, a1 = t w, sinf(a0), sinf(a1) (the last six are 0 on the
+ * lerp branch). tests/ measure the error of the device's sqrtf / atan2f / sinf on them. Synchronises. */
+int  pt_anim_debug_slerp(PtContext* ctx, const float* q0, const float* q1, const float* t, uint32_t n, float* out);
 
 typedef struct PtAccelStats {
     uint32_t InstanceCount, BottomLevelCount;
