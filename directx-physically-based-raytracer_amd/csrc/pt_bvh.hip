@@ -490,7 +490,8 @@ __device__ __forceinline__ void ref_box(int r, const float4* leafLo, const float
     if (r < 0) { lo = leafLo[~r]; hi = leafHi[~r]; } else { lo = nodeLo[r]; hi = nodeHi[r]; }
 }
 
-// Origin, per-axis power-of-two scale and the 8-bit child boxes of a node (paper, section 3.3): e = ceil(log2(extent / 255)),
+// Origin, per-axis power-of-two scale and the 8-bit child boxes of a node (paper, section 3.3): e = ceil(log2(extent / 255)), the least
+// exponent at which the children fit 0..255 (tests/bvhref.py part d),
 // q_lo = floor((lo - p) / 2^e), q_hi = ceil((hi - p) / 2^e), each checked against its decoded value so that the stored box
 // contains the child box whatever the roundings were. Slots with refs[s] == kEmptyRef (or an empty child box) get lo > hi.
 __device__ void quantise_node(WideNode& n, float4 nlo, float4 nhi, const float4* clo, const float4* chi, const int* refs)
@@ -504,6 +505,7 @@ __device__ void quantise_node(WideNode& n, float4 nlo, float4 nhi, const float4*
         const float ext = valid ? ph[a] - p[a] : 0.0f;
         int e;
         (void)frexpf(ext * (1.0f / 255.0f), &e);             // ext / 255 = m * 2^e with m in [0.5, 1): 2^e covers it
+        if (255.0f * ldexpf(1.0f, e - 1) >= ext) e--;        // ext = 255 * 2^(e - 1) has m = 0.5: the finer grid holds it (the loop below goes back up if not)
         if (!(ext > 0.0f)) e = -126;
         while (true) {
             if (e < -126) e = -126;
@@ -715,6 +717,7 @@ __device__ void collapse_node(const CollapseArgs& A, uint32_t w, bool active, ui
         const float ext = valid ? ph[a] - p[a] : 0.0f;
         int e;
         (void)frexpf(ext * (1.0f / 255.0f), &e);
+        if (255.0f * ldexpf(1.0f, e - 1) >= ext) e--;        // as in quantise_node
         if (!(ext > 0.0f)) e = -126;
         const bool boxed = valid && occupied && cl3[a] <= ch3[a];
         bool done = false;
