@@ -6,6 +6,7 @@
 //           [--light-sampling cdf|uniform|power_ris|regir [--regir-layout grid|onion]]
 //           [--post] [--no-bloom] [--bloom-strength S] [--tone-map saturate|reinhard|aces] [--exposure E]
 //           [--hdr [--paper-white N] [--color-rotation hdtv_to_uhdtv|dci_p3_d65_to_uhdtv|hdtv_to_dci_p3_d65]]
+//           [--nrd relax|reblur] [--out-radiance file.bin]
 //           [--png file.png] [--out-display file.bin] [--scene descriptor.json [--anim-time T [--anim-step DT]]] [--dump-scene file.bin]
 //
 // --anim-time T (with --scene): the animated render objects of the descriptor (RenderObjects[].Animation) are posed at T seconds of their selected
@@ -30,6 +31,11 @@
 // at MyAppData's defaults (bloom 0.05, ACES filmic, exposure 0, SDR) unless the flags above change them; --png writes the last frame's
 // Display8 as an RGB PNG (SDR only), --out-display its BackBuffer (R10G10B10A2_UNORM words). Both imply --post. With --ranks the chain
 // runs on rank 0, on the gathered frame.
+//
+// --nrd relax|reblur: the frame is rendered with that Denoiser value (the G-buffer pass then writes the albedos, App.cpp:1223, and the path tracer the
+// NRD-facing Diffuse / Specular), and App::ProcessNRD (App.cpp:1595-1688) runs after it and before --post: the NRD composition pass packs the pair,
+// the denoiser -- here the identity: this library has none -- leaves it as it is, and the pass composes it into Radiance. With --ranks every rank
+// runs the two passes on its own rows, before the gather. --out-radiance writes the last frame's Radiance (R16G16B16A16_FLOAT, the whole frame).
 //
 // --ranks R: one process per GPU. The parent (which never touches a GPU) starts R children `--rank r --world R --id-file F`; rank 0
 // makes the RCCL unique id and leaves it in F, the others pick it up; every rank renders its 16-row bands (BandSharding) and rank 0
@@ -400,6 +406,7 @@ int main(int argc, char** argv)
     bool post = false, bloom = true, hdr = false; float bloomStrength = 0.05f, exposure = 0.0f, paperWhite = 200.0f;
     std::string toneMap = "aces", colorRotation = "hdtv_to_uhdtv", pngPath, displayPath;
     bool animate = false; double animTime = 0.0, animStep = 0.0;
+    std::string nrd, radiancePath;
     for (int i = 1; i < argc; i++) {
         std::string k = argv[i];
         if (k == "--di") { di = true; continue; }                  // the flags without a value
@@ -427,6 +434,7 @@ int main(int argc, char** argv)
         else if (k == "--exposure") exposure = (float)atof(v); else if (k == "--paper-white") paperWhite = (float)atof(v);
         else if (k == "--color-rotation") colorRotation = v; else if (k == "--png") pngPath = v;
         else if (k == "--out-display") displayPath = v;
+        else if (k == "--nrd") nrd = v; else if (k == "--out-radiance") radiancePath = v;
         else if (k == "--anim-time") { animate = true; animTime = atof(v); } else if (k == "--anim-step") animStep = atof(v);
     }
     post = post || !pngPath.empty() || !displayPath.empty();
@@ -542,7 +550,12 @@ int main(int argc, char** argv)
         tx.NormalizedDepth = alloc(px_ * 4); tx.MotionVector = alloc(px_ * 8); tx.BaseColorMetalness = alloc(px_ * 4); tx.NormalRoughness = alloc(px_ * 8);
         tx.IOR = alloc(px_ * 2); tx.Transmission = alloc(px_); tx.Radiance = alloc(px_ * 8);
         tx.RadianceF32 = radianceF32 = (float*)alloc(px_ * 16);
-        if (di) { tx.Diffuse = alloc(px_ * 8); tx.Specular = alloc(px_ * 8); }   // Raytracing::Textures Diffuse / Specular (App.cpp:475-482)
+        uint32_t nrdDenoiser = PT_DENOISER_NONE;
+        if (nrd == "relax") nrdDenoiser = PT_DENOISER_NRD_RELAX;
+        else if (nrd == "reblur") nrdDenoiser = PT_DENOISER_NRD_REBLUR;
+        else if (!nrd.empty()) throw std::invalid_argument("--nrd: relax or reblur");
+        if (di || nrdDenoiser) { tx.Diffuse = alloc(px_ * 8); tx.Specular = alloc(px_ * 8); }   // Raytracing::Textures Diffuse / Specular (App.cpp:475-482)
+        if (nrdDenoiser) { tx.DiffuseAlbedo = alloc(px_ * 8); tx.SpecularAlbedo = alloc(px_ * 8); }   // App.cpp:1223: the albedos exist for the denoiser
         void* fullRadiance = sharded && rank == 0 ? alloc(fullPx * 8) : nullptr;      // the assembled frame (R16G16B16A16_FLOAT), root only
         // ---- App::PostProcessGraphics (Denoiser::None): on the whole frame, rank 0 of a sharded run after the gather
         PostProcessing postProcessing(commandList);
@@ -587,6 +600,9 @@ int main(int argc, char** argv)
         if (restirPairwise && !restir) throw std::invalid_argument("--restir-pairwise needs --restir");
         if (restirPairwise && restirRaytraced) throw std::invalid_argument("--restir-pairwise and --restir-raytraced are two bias corrections: give one");
         if (useSharc && sharded) throw std::invalid_argument("--sharc needs one unsharded process");
+        if (useSharc && nrdDenoiser) throw std::invalid_argument("--nrd: the radiance-cache query does not serve the NRD packing, drop --sharc");
+        NRDComposition nrdComposition(commandList);
+        if (nrdDenoiser) fprintf(stderr, "pt_demo: --nrd %s: the denoiser between the pack and the compose is the identity\n", nrd.c_str());
         SHARC sharc(commandList);
         Raytracing::SHARCSettings sharcSettings; sharcSettings.DownscaleFactor = sharcDownscale;
         if (useSharc) { sharc.Constants.SceneScale = sceneScale; sharc.Configure(); }
@@ -675,19 +691,26 @@ int main(int argc, char** argv)
                 gbuffer.Textures = tx; raytracing.Textures = tx; directLighting.Textures = tx;
             }
             firstFrame = false;
-            gbuffer.Render(commandList, tlas, { { W, H }, ~0u & ~(uint32_t)GBufferGeneration::Flags::Albedo });     // App.cpp:1224
+            gbuffer.Render(commandList, tlas, { { W, H }, nrdDenoiser ? ~0u : ~0u & ~(uint32_t)GBufferGeneration::Flags::Albedo });     // App.cpp:1223-1224
             if (di) {                                               // App.cpp:1234-1308: RTXDI between the G-buffer and the path tracer
                 DirectLighting::Settings ds; ds.RenderSize[0] = W; ds.RenderSize[1] = H; ds.FrameIndex = frameIndex;
-                ds.LocalLightSamples = diSamples; ds.IsLastRenderPass = bounces == 0;
+                ds.LocalLightSamples = diSamples; ds.IsLastRenderPass = bounces == 0; ds.Denoiser = nrdDenoiser;
                 directLighting.SetConstants(ds);
                 directLighting.Render(commandList, tlas);
             }
             Raytracing::GraphicsSettings gs; gs.RenderSize[0] = W; gs.RenderSize[1] = H;
             gs.FrameIndex = frameIndex; gs.Bounces = bounces; gs.SamplesPerPixel = spp; gs.IsRussianRouletteEnabled = true;
-            gs.IsDIEnabled = di;
+            gs.IsDIEnabled = di; gs.Denoiser = nrdDenoiser;
             raytracing.SetConstants(gs);
             if (useSharc) raytracing.Render(commandList, tlas, sharc, sharcSettings);
             else raytracing.Render(commandList, tlas);
+            if (nrdDenoiser) {                                      // App::ProcessNRD (App.cpp:1595-1688): pack, the denoiser (the identity), compose
+                NRDComposition::Constants nc; nc.RenderSize[0] = W; nc.RenderSize[1] = std::max(localRows, 1u); nc.Denoiser = nrdDenoiser;
+                nrdComposition.Textures = { tx.LinearDepth, tx.DiffuseAlbedo, tx.SpecularAlbedo, tx.NormalRoughness, tx.Diffuse, tx.Specular,
+                                            tx.Diffuse, tx.Specular, tx.Radiance };
+                nc.IsPack = true; nrdComposition.Process(commandList, nc);
+                nc.IsPack = false; nrdComposition.Process(commandList, nc);
+            }
             if (sharded) sharding.GatherBands(commandList, tx.Radiance, fullRadiance, W, H, 8);
             if (runPost) postProcessing.Render(commandList);
         };
@@ -733,6 +756,13 @@ int main(int argc, char** argv)
             FILE* fp = fopen(out.c_str(), "wb");
             if (!fp) { fprintf(stderr, "cannot open %s\n", out.c_str()); return 3; }
             fwrite(host.data(), 16, fullPx, fp); fclose(fp);
+        }
+        if (!radiancePath.empty() && rank == 0) {                   // the fp16 Radiance of the last frame, whole frame
+            std::vector<uint16_t> host(fullPx * 4);
+            HIP_OK(hipMemcpy(host.data(), sharded ? fullRadiance : tx.Radiance, fullPx * 8, hipMemcpyDeviceToHost));
+            FILE* fp = fopen(radiancePath.c_str(), "wb");
+            if (!fp || fwrite(host.data(), 8, fullPx, fp) != fullPx) { fprintf(stderr, "cannot write %s\n", radiancePath.c_str()); if (fp) fclose(fp); return 3; }
+            fclose(fp);
         }
         if (runPost && !displayPath.empty()) {                      // the presented back buffer of the last frame
             std::vector<uint32_t> words(fullPx);

@@ -8,6 +8,7 @@
 //     struct SkeletalMeshSkinning Source/SkeletalMeshSkinning.ixx:20-66
 //     struct Animation / AnimationCollection   Source/Animation.ixx:78-197 (the clock and the selection; the transforms are computed on the device)
 //     struct PostProcessing      App::PostProcessGraphics with Denoiser::None (Source/App.cpp:1506-1571): Bloom, Merge, ToneMap, CopyTexture
+//     struct NRDComposition      Source/NRDComposition.ixx (the pack and compose passes of App::ProcessNRD, Source/App.cpp:1595-1688)
 // Error behaviour: a failing status becomes the exception type the reference throws at the same place
 // (std::invalid_argument for argument checks, std::system_error otherwise: Source/ErrorHelpers.ixx:16-32).
 // Header-only, plain C++20 (std::span), no HIP headers needed by the including translation unit.
@@ -578,6 +579,34 @@ struct PostProcessing {
 
 private:
     PtContext* m_context;
+};
+
+// struct NRDComposition (Source/NRDComposition.ixx -> Shaders/NRDComposition.hlsl:36-88): the pass App::ProcessNRD (Source/App.cpp:1595-1688)
+// runs in front of the denoiser (IsPack: Diffuse / Specular become its input encoding, in place) and behind it (the denoised pair is unpacked,
+// multiplied by the albedos and added to Radiance). The denoiser between the two calls is the host's. Element-wise: a sharded host passes its
+// own rows and their size. DenoisedDiffuse / DenoisedSpecular may be NoisyDiffuse / NoisySpecular themselves (the identity denoiser).
+struct NRDComposition {
+    struct Constants {
+        uint32_t RenderSize[2]{};
+        bool IsPack{};
+        uint32_t Denoiser{};                                  // PtDenoiser
+        float ReBLURHitDistance[4]{};                         // nrd::ReblurSettings().hitDistanceParameters
+
+        Constants() { pt_nrd_reblur_hit_distance_defaults(ReBLURHitDistance); }
+    };
+
+    PtNRDCompositionTextures Textures{};
+
+    explicit NRDComposition(CommandList&) {}
+
+    void Process(CommandList& commandList, const Constants& constants)
+    {
+        PtNRDCompositionConstants k{};
+        k.RenderSize[0] = constants.RenderSize[0]; k.RenderSize[1] = constants.RenderSize[1];
+        k.IsPack = constants.IsPack; k.Denoiser = constants.Denoiser;
+        for (int i = 0; i < 4; i++) k.ReBLURHitDistance[i] = constants.ReBLURHitDistance[i];
+        ThrowIfFailed(commandList.Context, pt_nrd_composition_process(commandList.Context, &k, &Textures));
+    }
 };
 
 } // namespace ptamd

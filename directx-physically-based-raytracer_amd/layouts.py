@@ -302,6 +302,45 @@ def post_processing_settings(width, height, bloom=True, strength=0.05, operator=
     return check_post_processing_settings(s)
 
 
+NRD_COMPOSITION_CONSTANTS = np.dtype({  # PtNRDCompositionConstants: NRDComposition::Constants (Shaders/NRDComposition.hlsl:3-9), 8 root constants
+    "names": ["RenderSize", "IsPack", "Denoiser", "ReBLURHitDistance"], "formats": [("<u4", 2), "<u4", "<u4", ("<f4", 4)],
+    "offsets": [0, 8, 12, 16], "itemsize": 32})
+# PtNRDCompositionTextures member order (NRDComposition::Textures): nine pointers
+NRD_COMPOSITION_TEXTURES = ["LinearDepth", "DiffuseAlbedo", "SpecularAlbedo", "NormalRoughness", "NoisyDiffuse", "NoisySpecular",
+                            "DenoisedDiffuse", "DenoisedSpecular", "Radiance"]
+NRD_REBLUR_HIT_DISTANCE_DEFAULTS = (3.0, 0.1, 20.0, -25.0)   # nrd::ReblurSettings().hitDistanceParameters, from memory (unpinned)
+NRD_MAX_SIZE = 16384
+
+
+def check_nrd_composition_constants(k):
+    """The checks pt_nrd_composition_process makes on its constants: ValueError where it answers PT_ERROR_INVALID_ARGUMENT."""
+    k = np.asarray(k).reshape(())
+    w, h = (int(v) for v in k["RenderSize"])
+    if not (1 <= w <= NRD_MAX_SIZE and 1 <= h <= NRD_MAX_SIZE):
+        raise ValueError(f"RenderSize must be 1..{NRD_MAX_SIZE} on both axes")
+    if int(k["IsPack"]) > 1:
+        raise ValueError("IsPack must be 0 or 1")
+    if int(k["Denoiser"]) > DENOISER_NRD_RELAX:
+        raise ValueError("unknown Denoiser value")
+    if not np.all(np.isfinite(k["ReBLURHitDistance"])):
+        raise ValueError("ReBLURHitDistance must be finite")
+    return k
+
+
+def nrd_composition_constants(width, height, denoiser, is_pack, hit_distance=None):
+    """PtNRDCompositionConstants. width, height: the size of the arrays passed (a sharded context: its band). hit_distance: the four
+    ReBLUR hit-distance parameters, None: NRD_REBLUR_HIT_DISTANCE_DEFAULTS. Refuses what pt_nrd_composition_process refuses."""
+    for name, v in (("RenderSize", width), ("RenderSize", height), ("Denoiser", denoiser), ("IsPack", int(is_pack))):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{name} is not a 32-bit unsigned value")
+    k = np.zeros((), NRD_COMPOSITION_CONSTANTS)
+    k["RenderSize"] = (width, height)
+    k["IsPack"] = int(is_pack)
+    k["Denoiser"] = denoiser
+    k["ReBLURHitDistance"] = NRD_REBLUR_HIT_DISTANCE_DEFAULTS if hit_distance is None else hit_distance
+    return check_nrd_composition_constants(k)
+
+
 SHARC_SETTINGS = np.dtype({  # PtSHARCSettings: SHARC::Constants + Raytracing::SHARCSettings (Source/MyAppData.h:250-262)
     "names": ["AccumulationFrames", "MaxStaleFrames", "SceneScale", "IsAntiFireflyEnabled", "DownscaleFactor", "RoughnessThreshold",
               "IsHashGridVisualizationEnabled"],

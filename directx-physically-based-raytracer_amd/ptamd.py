@@ -30,6 +30,7 @@ EXPORTS = [
     "pt_di_set_light_sampling", "pt_di_download_presampled", "pt_di_set_visibility", "pt_di_set_pairwise",
     "pt_di_set_regir_layout", "pt_di_regir_onion_table", "pt_di_set_brdf_sampling", "pt_di_download_brdf_candidates",
     "pt_post_set_constants", "pt_post_render", "pt_post_download_bloom",
+    "pt_nrd_composition_process", "pt_nrd_composition_pixels_per_lane", "pt_nrd_reblur_hit_distance_defaults",
     "pt_anim_create_rig", "pt_anim_release_rig", "pt_anim_create_object", "pt_anim_release_object", "pt_anim_evaluate",
     "pt_anim_skeletal_transforms", "pt_anim_download_globals", "pt_anim_download_skeletal", "pt_anim_debug_slerp",
     "pt_sharc_configure", "pt_sharc_set_constants", "pt_raytrace_render_sharc", "pt_sharc_reset", "pt_sharc_download",
@@ -70,6 +71,10 @@ class PreviousTextures(C.Structure):
 
 class PostTextures(C.Structure):
     _fields_ = [("Radiance", C.c_void_p), ("Color", C.c_void_p), ("BackBuffer", C.c_void_p), ("Display8", C.c_void_p)]
+
+
+class NRDCompositionTextures(C.Structure):   # PtNRDCompositionTextures: nine pointers, NRDComposition::Textures' member order
+    _fields_ = [(n, C.c_void_p) for n in L.NRD_COMPOSITION_TEXTURES]
 
 
 class Sharding(C.Structure):
@@ -210,6 +215,9 @@ def load_library():
         lib.pt_post_set_constants.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_post_render.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_post_download_bloom.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.pt_nrd_composition_process.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pt_nrd_composition_pixels_per_lane.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_nrd_reblur_hit_distance_defaults.argtypes = [C.c_void_p]; lib.pt_nrd_reblur_hit_distance_defaults.restype = None
         lib.pt_sharc_configure.argtypes = [C.c_void_p, C.c_uint32]
         lib.pt_sharc_set_constants.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_raytrace_render_sharc.argtypes = [C.c_void_p, C.c_void_p]
@@ -965,6 +973,48 @@ class PostProcessing:
         return out
 
 
+def nrd_reblur_hit_distance_defaults():
+    """pt_nrd_reblur_hit_distance_defaults: nrd::ReblurSettings().hitDistanceParameters as the library states them. No GPU."""
+    out = np.zeros(4, np.float32)
+    load_library().pt_nrd_reblur_hit_distance_defaults(C.c_void_p(out.ctypes.data))
+    return out
+
+
+class NRDComposition:
+    """Mirror of `struct NRDComposition` (Source/NRDComposition.ixx -> Shaders/NRDComposition.hlsl:36-88), the pass App::ProcessNRD
+    (Source/App.cpp:1595-1688) runs in front of the denoiser (IsPack = 1) and behind it (IsPack = 0). Process takes the textures by the
+    names of layouts.NRD_COMPOSITION_TEXTURES (a missing name is an unbound texture) and PtNRDCompositionConstants
+    (layouts.nrd_composition_constants). Element-wise: a sharded context passes its own rows and their size. No scene is needed."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.Textures = {}
+
+    def Process(self, textures, constants):
+        """textures: the dict of bound textures, None: self.Textures. constants: one record of layouts.NRD_COMPOSITION_CONSTANTS."""
+        tex = self.Textures if textures is None else textures
+        k = _nrd_constants(constants)
+        t = NRDCompositionTextures(*[_ptr(tex.get(n)) for n in L.NRD_COMPOSITION_TEXTURES])
+        self.ctx.check(self.ctx.lib.pt_nrd_composition_process(self.ctx.handle, C.c_void_p(k.ctypes.data), C.addressof(t)))
+
+
+def _nrd_constants(constants):
+    """the 32 bytes the library reads: anything but one record of the mirror's dtype is refused here (its values are the library's to check)"""
+    k = np.array(constants)
+    if k.dtype != L.NRD_COMPOSITION_CONSTANTS or k.size != 1:
+        raise PtInvalidArgument("constants must be one PtNRDCompositionConstants record (layouts.nrd_composition_constants)")
+    return np.ascontiguousarray(k).reshape(())
+
+
+def nrd_composition_pixels_per_lane(pointers, constants):
+    """pt_nrd_composition_pixels_per_lane: 2 or 1, the form pt_nrd_composition_process would launch for textures at these addresses
+    (pointers: name of layouts.NRD_COMPOSITION_TEXTURES -> device address as an int, a missing name is unbound), 0 if it would refuse
+    the call. Host arithmetic: no GPU, nothing is dereferenced."""
+    k = _nrd_constants(constants)
+    t = NRDCompositionTextures(*[pointers.get(n) for n in L.NRD_COMPOSITION_TEXTURES])
+    return load_library().pt_nrd_composition_pixels_per_lane(C.c_void_p(k.ctypes.data), C.addressof(t))
+
+
 class SHARC:
     """Mirror of `struct SHARC` (Source/SHARC.ixx) and of the Raytracing::Render overload that takes it: Configure allocates the context's
     cache, SetConstants takes PtSHARCSettings (layouts.sharc_settings), Render runs clear, update, resolve, query and the swap with the
@@ -1047,6 +1097,7 @@ class Renderer:
         self.direct_lighting = DirectLighting(ctx)
         self.post = PostProcessing(ctx)
         self.sharc = SHARC(ctx)
+        self.nrd = NRDComposition(ctx)
         d = scene_gpu.desc
         for op in (self.gbuffer, self.raytracing, self.direct_lighting):
             op.GPUBuffers["Camera"] = d.camera
@@ -1057,8 +1108,14 @@ class Renderer:
         self.constants["Flags"] = L.GBufferFlags.DefaultNoDenoiser        # App.cpp:1224 with Denoiser::None
 
     def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None, post=None, sharc=None, di_visibility=None, di_pairwise=None,
-               di_regir_layout=None, di_brdf=None):
-        """di_brdf: layouts.di_brdf_settings for BRDF candidates in the DI pass's initial sampling, or None: none (the
+               di_regir_layout=None, di_brdf=None, nrd=None, denoise=None, nrd_hit_distance=None):
+        """nrd: layouts.DENOISER_NRD_REBLUR / _RELAX (it must be settings' Denoiser) to run App::ProcessNRD (App.cpp:1595-1688) after the
+        frame and before post: the NRD composition pass packs textures["Diffuse"] / ["Specular"] in place, denoise(noisy_diffuse,
+        noisy_specular) -> (denoised_diffuse, denoised_specular) takes and returns device tensors of their shape (None: the identity,
+        the denoised textures alias the noisy ones), and the pass composes the result into textures["Radiance"]. It needs a renderer with
+        with_denoiser_outputs=True; the G-buffer call then carries the albedo flags. nrd_hit_distance: the four ReBLUR hit-distance
+        parameters, None: the defaults. Works on a sharded context (on its own rows).
+        di_brdf: layouts.di_brdf_settings for BRDF candidates in the DI pass's initial sampling, or None: none (the
         setter is then called only to turn off what an earlier frame of this renderer turned on).
         di_samples > 0: run the DI pass with that many candidates per pixel; set settings["IsDIEnabled"] to have the path tracer
         consume it (the textures need Diffuse / Specular: with_denoiser_outputs=True). di_reuse: PtDIResamplingSettings
@@ -1084,7 +1141,20 @@ class Renderer:
                 c = n[len("Previous"):]
                 self.textures[n], self.textures[c] = self.textures[c], self.textures[n]
         denoiser = int(np.array(settings).reshape(())["Denoiser"])
+        if nrd is None and denoise is not None:
+            raise PtInvalidArgument("denoise is given without nrd: name the NRD denoiser value whose packing it reads")
+        if nrd is not None:
+            if int(nrd) not in (L.DENOISER_NRD_REBLUR, L.DENOISER_NRD_RELAX):
+                raise PtInvalidArgument("nrd must be DENOISER_NRD_REBLUR or DENOISER_NRD_RELAX")
+            if denoiser != int(nrd):
+                raise PtInvalidArgument("nrd differs from the settings' Denoiser: the frame must write the NRD-facing outputs the pass packs")
+            if "Diffuse" not in self.textures or "Specular" not in self.textures:
+                raise PtInvalidArgument("nrd needs the Diffuse / Specular textures: create the Renderer with with_denoiser_outputs=True")
+            nrd_pack = L.nrd_composition_constants(self.width, self.local_rows, int(nrd), True, nrd_hit_distance)
+            nrd_compose = L.nrd_composition_constants(self.width, self.local_rows, int(nrd), False, nrd_hit_distance)
         self.constants["Flags"] = 0xFFFFFFFF if denoiser != L.DENOISER_NONE else L.GBufferFlags.DefaultNoDenoiser   # App.cpp:1223
+        if nrd is not None and int(self.constants["Flags"]) & L.GBufferFlags.Albedo != L.GBufferFlags.Albedo:
+            raise PtInvalidArgument("nrd needs DiffuseAlbedo / SpecularAlbedo: the G-buffer call lacks the albedo flags")
         self.gbuffer.Render(tlas, self.constants)
         if di_samples:                                                    # App.cpp:1234-1308: the DI pass between the two
             s = np.array(settings).reshape(())
@@ -1106,6 +1176,18 @@ class Renderer:
                 self.sharc.Render(self.raytracing, tlas)
             else:
                 self.raytracing.Render(tlas)
+        if nrd is not None:                                               # App::ProcessNRD, App.cpp:1595-1688: pack, the denoiser, compose
+            t = self.textures
+            tex = {n: t[n] for n in ("LinearDepth", "DiffuseAlbedo", "SpecularAlbedo", "NormalRoughness", "Radiance")}
+            tex["NoisyDiffuse"], tex["NoisySpecular"] = t["Diffuse"], t["Specular"]
+            self.nrd.Process(tex, nrd_pack)
+            dd, ds = (t["Diffuse"], t["Specular"]) if denoise is None else denoise(t["Diffuse"], t["Specular"])
+            for name, got, like in (("diffuse", dd, t["Diffuse"]), ("specular", ds, t["Specular"])):
+                if got is None or got.dtype != like.dtype or tuple(got.shape) != tuple(like.shape) or got.device != like.device or not got.is_contiguous():
+                    raise PtInvalidArgument(f"denoise returned a {name} texture that is not a contiguous device tensor of the noisy one's shape and dtype")
+            tex["DenoisedDiffuse"], tex["DenoisedSpecular"] = dd, ds
+            self.nrd.Process(tex, nrd_compose)
+            self._nrd_keep = (dd, ds)                                     # the compose is enqueued: its inputs live until the next frame
         if post is not None:                                              # App.cpp:1506-1571, after Raytracing::Render
             if "Color" not in self.textures:
                 self.textures.update(alloc_post_textures(self.width, self.height, self.scene.device))

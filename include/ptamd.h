@@ -697,6 +697,42 @@ int pt_post_download_bloom(PtContext* ctx, uint32_t stage, uint16_t* host_rgba16
                            uint32_t* out_width, uint32_t* out_height);
 
 /* ------------------------------------------------------------------------------------------
+ * the NRD composition pass (NRDComposition::Process, Source/NRDComposition.ixx -> Shaders/NRDComposition.hlsl:36-88), which
+ * App::ProcessNRD (Source/App.cpp:1595-1688) runs twice around the denoiser: IsPack = 1 turns the path tracer's Diffuse / Specular
+ * into the denoiser's input encoding (demodulation by the albedos, hit-distance normalisation, front-end packing), IsPack = 0 unpacks
+ * the denoised pair, multiplies the albedos back and adds the result to Radiance. The denoiser itself stays out of scope: a host
+ * brings its own between the two calls, which sit between pt_raytrace_render and pt_post_render. NRD.hlsli is not part of the
+ * reference tree: DESIGN.md section 1, "NRD composition", is the arithmetic spec (this library's own after the SDK; parity with the
+ * SDK is unpinned; tests/nrdref.py restates it).
+ * ------------------------------------------------------------------------------------------ */
+struct PtNRDCompositionConstants {          /* NRDComposition::Constants, 8 root constants. (The two structs of this pass are tagged, not
+                                               typedefs, like PtAnimState: C callers write `struct PtNRDCompositionConstants`.) */
+    uint32_t RenderSize[2];                 /* size of the arrays passed: 1..16384 each */
+    uint32_t IsPack;                        /* 0 / 1 */
+    uint32_t Denoiser;                      /* PtDenoiser */
+    float    ReBLURHitDistance[4];          /* nrd::ReblurSettings().hitDistanceParameters; finite */
+};                                          /* 32 B */
+struct PtNRDCompositionTextures {           /* NRDComposition::Textures, the same member order; row-major, RenderSize pixels */
+    const void *LinearDepth, *DiffuseAlbedo, *SpecularAlbedo, *NormalRoughness;   /* as pt_gbuffer_render writes them */
+    void *NoisyDiffuse, *NoisySpecular;     /* R16G16B16A16_FLOAT, rewritten in place by the pack */
+    const void *DenoisedDiffuse, *DenoisedSpecular;
+    void *Radiance;                         /* R16G16B16A16_FLOAT, += by the compose (its alpha keeps its bits) */
+};
+/* Enqueued on the context's stream. Needs no acceleration structure. One lane moves two pixels with 16-byte accesses when every texture
+ * of the call is aligned to two texels (16 bytes; LinearDepth 8), else one pixel with 8-byte accesses: the same bytes either way.
+ * The pass is element-wise and ignores the sharding: a sharded context passes its own rows and their size. The pack needs
+ * LinearDepth, both albedos and both Noisy*, plus NormalRoughness when Denoiser is ReBLUR; the compose needs LinearDepth, both
+ * albedos, both Denoised* and Radiance. Denoised* may point at Noisy* (the identity denoiser, no copy). A pixel whose LinearDepth
+ * is not finite is left untouched in every texture. Refused with PT_ERROR_INVALID_ARGUMENT and a message that names the field,
+ * nothing written: a missing binding, a texture not aligned to its texel (8 bytes; LinearDepth 4), an unknown Denoiser,
+ * IsPack > 1, a RenderSize out of range, a ReBLURHitDistance that is not finite. */
+int  pt_nrd_composition_process(PtContext* ctx, const struct PtNRDCompositionConstants* constants, const struct PtNRDCompositionTextures* textures);
+/* The pixels per lane of the kernel that call would launch: 2 or 1; 0 when the call would be refused. Host arithmetic on the pointer
+ * values (nothing is dereferenced, no GPU): the decision pt_nrd_composition_process itself takes. */
+int  pt_nrd_composition_pixels_per_lane(const struct PtNRDCompositionConstants* constants, const struct PtNRDCompositionTextures* textures);
+void pt_nrd_reblur_hit_distance_defaults(float out[4]);    /* {3, 0.1, 20, -25}; needs no GPU */
+
+/* ------------------------------------------------------------------------------------------
  * the SHARC radiance cache: the Raytracing::Render overload with RTXGITechnique::SHARC (Source/Raytracing.ixx:114-148, Source/SHARC.ixx,
  * the SHARC_UPDATE / SHARC_QUERY permutations of Shaders/Raytracing.hlsl). A world-space hash grid of radiance: an update pass walks one
  * path per DownscaleFactor^2 pixels and deposits what it finds, a resolve pass blends the frame into the history, and the query pass -- the
