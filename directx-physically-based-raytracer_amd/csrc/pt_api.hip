@@ -209,14 +209,14 @@ static int check_geometries(Context& c, const PtGeometryDesc* geometries, uint32
     return PT_OK;
 }
 
-// the traversal stack holds at most two entries per level of both trees (a node group and, in the streaming form, a postponed
-// leaf group) plus the three of an instance transition (pt_trace.hpp)
 static bool any_non_opaque(const PtGeometryDesc* geometries, uint32_t geometry_count)
 {
     for (uint32_t g = 0; g < geometry_count; g++) if (!(geometries[g].Flags & PT_GEOMETRY_FLAG_OPAQUE)) return true;
     return false;
 }
 
+// the traversal stack holds at most two entries per level of both trees (the rest of a node group and, in the streaming form only, a
+// postponed leaf group) plus the three of an instance transition (pt_trace.hpp GroupStack)
 static int check_depth(Context& c, uint32_t tlasDepth)
 {
     if (2u * (tlasDepth + c.maxBlasDepth) + 4u > (uint32_t)kStackSize)
@@ -296,10 +296,26 @@ int pt_update_bottom_level(PtContext* ctx, uint64_t blas_id, const PtGeometryDes
     if (!updatable) std::swap(nb.tree, c.buildScratch);
     if (e != hipSuccess) return fail_hip(&c, e, "bottom-level update");
     if (nb.buildError || 2u * nb.depth + 4u > (uint32_t)kStackSize) return fail(&c, PT_ERROR_INVALID_ARGUMENT, "bottom-level update failed: tree too deep for the traversal stack");
+    // The live top level was accepted over the old tree. A new tree that would take it past the bound is refused here, while the old one
+    // is still in place and keeps rendering -- not at the next top-level build, when it is gone. (Without a live top level the update
+    // goes through and that build decides.)
+    if (c.haveTlas) {
+        s = poll_tlas_header(c, true);
+        if (s != PT_OK) return s;
+    }
+    if (c.haveTlas) {
+        uint32_t deepest = nb.depth;
+        for (auto& kv : c.blas) if (kv.first != blas_id) deepest = std::max(deepest, kv.second.depth);
+        const uint32_t tlasDepth = c.tlasHeaderHost.data()->depth;
+        if (2u * (tlasDepth + deepest) + 4u > (uint32_t)kStackSize)
+            return fail(&c, PT_ERROR_INVALID_ARGUMENT, "bottom-level update failed: the structure would be too deep for the traversal stack (top level " + std::to_string(tlasDepth)
+                        + " + bottom level " + std::to_string(deepest) + " levels)");
+    }
     nb.geometryCount = geometry_count;
     nb.hasNonOpaque = any_non_opaque(geometries, geometry_count);
-    c.maxBlasDepth = std::max(c.maxBlasDepth, nb.depth);
     b = std::move(nb);
+    c.maxBlasDepth = 0;                                  // over the live bottom levels: the tree that was replaced may have been the deepest
+    for (auto& kv : c.blas) c.maxBlasDepth = std::max(c.maxBlasDepth, kv.second.depth);
     drop_tlas(c);                                        // instance records point at the freed arrays
     return PT_OK;
 }

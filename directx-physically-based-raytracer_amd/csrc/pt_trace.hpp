@@ -65,9 +65,14 @@ struct Hit {
 
 struct TraceStats { uint32_t nodes, tris, overflow; };
 
-// Traversal stack of node groups (8 B each: child base | hits << 24 | imask). One entry at most per level of the wide
-// tree, so kStackSize bounds TLAS depth + BLAS depth + the three entries of an instance transition; the builders refuse
-// a structure that does not fit (pt_api.hip), and a push that would still overflow is counted, never silent.
+// Traversal stack of node groups (8 B each: child base | hits << 24 | imask). The one-lane walk (trace_single) and the work-item
+// walk (trace_item) push ONE entry at most per level of a wide tree: the rest of a node group, and only at a level where two or
+// more internal children were hit (none at the last level: its children are leaves). The streaming walk (pt_stream.hip) also
+// postpones the rest of a leaf group next to it: TWO per level. An instance transition parks three entries. check_depth
+// (pt_api.hip) budgets for the larger, 2 * (TLAS depth + BLAS depth) + 4 <= kStackSize; the builders refuse a structure beyond
+// that, and a push that would still overflow is counted, never silent. What the step logs of trace_single show on the deepest
+// trees the builder is known to make (tests/test_deep_trees_gpu.py): sp up to 19 on a bottom level of 19 levels, 25 on one of 25,
+// 27 on 13 top + 17 bottom levels (2 * 30 + 4 = 64, the last structure accepted) -- always within depth - 1 per tree + 3.
 constexpr int kStackSize = 64;
 constexpr uint32_t kMaxLeafTris = 3;                      // the unary count of a leaf slot has 3 bits
 // Triangles per BLAS leaf, a function of the BLAS size so that builder and traversal agree without storing it.

@@ -357,6 +357,19 @@ class DeviceContext:
             self.set_debug_flags(before)
         return dh.cpu().numpy()[:len(rays) * 32].view(CLOSEST_HIT).copy()
 
+    def trace_ray(self, ray8, log_words=4 * 4096):
+        """pt_debug_trace_ray: one host ray (origin, tmin, direction, tmax) through the one-lane two-level walk with its step log. Returns
+        the steps written as an [n, 4] uint32 array of (code, a, b, sp) (csrc/pt_trace2.hpp trace_single names the codes; 7 ends a walk).
+        A log that fills log_words ends without its code 7: the walk itself still ran to its end. Refuses like the C call does: without
+        a top level, PtError; a ray that is not eight floats, PtInvalidArgument."""
+        ray = np.ascontiguousarray(ray8, np.float32).reshape(-1)
+        if ray.size != 8 or log_words < 4:
+            raise PtInvalidArgument("trace_ray takes one ray of eight floats and room for at least one step")
+        log = np.zeros(int(log_words), np.uint32)
+        self.check(self.lib.pt_debug_trace_ray(self.handle, C.c_void_p(ray.ctypes.data), C.c_void_p(log.ctypes.data), int(log_words)))
+        steps = log[:4 * (int(log_words) // 4)].reshape(-1, 4)
+        return steps[:int(np.count_nonzero(steps[:, 0]))].copy()
+
     def accel_stats(self):
         s = AccelStats()
         self.check(self.lib.pt_get_accel_stats(self.handle, C.byref(s)))

@@ -241,7 +241,9 @@ int  pt_build_bottom_level(PtContext* ctx, const PtGeometryDesc* geometries, uin
  * CommandList::UpdateAccelerationStructures, Source/CommandList.ixx:235-241): same id, geometry re-read from the (moved)
  * vertex buffers. A structure built with PT_BUILD_FLAG_ALLOW_UPDATE and given the same triangle counts is REFITTED in place
  * (asynchronous: no allocation, no wait); any other is rebuilt under its id. Until pt_build_top_level has been called again
- * (Scene::CreateAccelerationStructures does so every dynamic frame) renders answer PT_ERROR_NOT_READY. */
+ * (Scene::CreateAccelerationStructures does so every dynamic frame) renders answer PT_ERROR_NOT_READY. A rebuild whose tree would
+ * take the live top level past the traversal stack's bound (2 * (top-level + deepest bottom-level depth) + 4 <= 64) is
+ * PT_ERROR_INVALID_ARGUMENT and changes nothing: the old tree and the top level over it keep rendering. */
 int  pt_update_bottom_level(PtContext* ctx, uint64_t blas_id, const PtGeometryDesc* geometries, uint32_t geometry_count, uint32_t build_flags);
 /* Frees a bottom level. If the live top level refers to it, that top level is dropped with it (renders answer
  * PT_ERROR_NOT_READY until the next pt_build_top_level). */

@@ -370,7 +370,9 @@ def test_pathological_mesh_coincident_centroids_and_diagonal_slivers(gpu, ptamd,
     """What a Morton-ordered builder likes least: thousands of triangles whose centroids coincide (one Morton cell: the
     split falls back to the primitive's position in the sorted order) and a long diagonal strip of slivers (boxes that overlap
     everything along the diagonal). The structure must stay within the traversal stack (StackOverflows 0, depth reported), agree
-    with the device's brute-force loop on every bounce ray, and the image must be the oracle's brute-force image bit for bit."""
+    with the device's brute-force loop on every bounce ray, and the image must be the oracle's brute-force image bit for bit.
+    This mesh is hard on the builder, not on the stack: its tree is balanced, and no lane's stack leaves its LDS part here. The trees
+    that do that are those of tests/test_deep_trees_gpu.py."""
     S, L = pkg.scenes, pkg.layouts
     W, H = 64, 48
     rng = np.random.default_rng(99)
