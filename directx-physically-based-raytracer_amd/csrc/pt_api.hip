@@ -804,12 +804,22 @@ int pt::make_views(Context& c, uint32_t width, uint32_t height, SceneView& sv, F
 int pt::check_raytrace_args(Context& c, const PtTextures* tx)
 {
     API_ARG(&c, c.settings.Denoiser <= PT_DENOISER_NRD_RELAX, "unknown Denoiser value");
-    API_ARG(&c, !c.settings.IsDIEnabled || (tx->Diffuse && tx->Specular), "IsDIEnabled reads the direct lighting from Textures.Diffuse / Textures.Specular (pt_di_render): not bound");
-    API_ARG(&c, !(c.settings.Denoiser >= PT_DENOISER_NRD_REBLUR) || (tx->Diffuse && tx->Specular), "NRD modes write Textures.Diffuse / Textures.Specular: not bound");
+    const bool empty = !rank_holds_pixels(c, c.settings.RenderSize[0], c.settings.RenderSize[1]);   // nothing to bind: the pass launches nothing
+    API_ARG(&c, empty || !c.settings.IsDIEnabled || (tx->Diffuse && tx->Specular), "IsDIEnabled reads the direct lighting from Textures.Diffuse / Textures.Specular (pt_di_render): not bound");
+    API_ARG(&c, empty || !(c.settings.Denoiser >= PT_DENOISER_NRD_REBLUR) || (tx->Diffuse && tx->Specular), "NRD modes write Textures.Diffuse / Textures.Specular: not bound");
     API_ARG(&c, c.settings.SamplesPerPixel < 65536 && c.settings.Bounces < 32768, "SamplesPerPixel / Bounces out of range");
-    API_ARG(&c, tx->Position && tx->FlatNormal && tx->GeometricNormal && tx->BaseColorMetalness && tx->NormalRoughness && tx->IOR
-                 && tx->Transmission && tx->Radiance, "a G-buffer texture the path tracer reads is not bound (Raytracing::Textures)");
+    API_ARG(&c, empty || (tx->Position && tx->FlatNormal && tx->GeometricNormal && tx->BaseColorMetalness && tx->NormalRoughness && tx->IOR
+                          && tx->Transmission && tx->Radiance), "a G-buffer texture the path tracer reads is not bound (Raytracing::Textures)");
     return PT_OK;
+}
+
+// A rank whose bands all lie below the frame holds no rows (a 5-row frame in bands of 16 over three ranks leaves two of them empty). Its textures
+// are allocations of zero bytes, which may well be NULL: the render operators ask for no binding there and launch nothing.
+bool pt::rank_holds_pixels(const Context& c, uint32_t width, uint32_t height)
+{
+    uint32_t rows = 0;
+    pt_local_rows(&c.sharding, height, &rows);
+    return width != 0u && rows != 0u;
 }
 
 extern "C" {

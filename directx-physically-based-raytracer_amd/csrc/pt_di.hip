@@ -1186,12 +1186,13 @@ static int di_check_args(Context& c, const PtTextures* tx, const PtDIPreviousTex
     API_ARG(&c, tx, "textures is NULL");
     if (!c.haveDISettings) return fail(&c, PT_ERROR_NOT_READY, "call pt_di_set_constants first");
     const PtDISettings& s = c.diSettings;
-    API_ARG(&c, tx->LinearDepth && tx->GeometricNormal && tx->NormalRoughness && tx->BaseColorMetalness && tx->IOR && tx->Transmission,
+    const bool empty = !rank_holds_pixels(c, s.RenderSize[0], s.RenderSize[1]);            // a rank without rows: nothing to bind, nothing is launched
+    API_ARG(&c, empty || (tx->LinearDepth && tx->GeometricNormal && tx->NormalRoughness && tx->BaseColorMetalness && tx->IOR && tx->Transmission),
            "a G-buffer texture the DI pass reads is not bound (LinearDepth, GeometricNormal, NormalRoughness, BaseColorMetalness, IOR, Transmission)");
     const bool toRadiance = s.IsLastRenderPass && s.Denoiser <= PT_DENOISER_DLSS_RAY_RECONSTRUCTION;
-    API_ARG(&c, toRadiance ? tx->Radiance != nullptr : (tx->Diffuse && tx->Specular),
+    API_ARG(&c, empty || (toRadiance ? tx->Radiance != nullptr : (tx->Diffuse && tx->Specular)),
            toRadiance ? "IsLastRenderPass with Denoiser None / DLSS-RR adds to Textures.Radiance: not bound" : "the DI pass writes Textures.Diffuse / Textures.Specular: not bound");
-    if (c.diReuseOn && c.diReuse.TemporalResampling)
+    if (!empty && c.diReuseOn && c.diReuse.TemporalResampling)
         API_ARG(&c, prev && prev->PreviousGeometricNormal && prev->PreviousLinearDepth && prev->PreviousBaseColorMetalness && prev->PreviousNormalRoughness &&
                prev->PreviousIOR && prev->PreviousTransmission && tx->MotionVector,
                "temporal resampling reads Textures.MotionVector and the six Previous* textures: not bound");

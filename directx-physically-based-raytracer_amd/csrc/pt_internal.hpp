@@ -295,6 +295,8 @@ int fail_hip(Context* c, hipError_t e, const char* what);
 int make_views(Context& c, uint32_t width, uint32_t height, SceneView& sv, FrameView& fv, bool needFrameInputs = true);
 // what pt_raytrace_render and pt_raytrace_render_sharc check alike, behind their own checks: settings ranges and texture bindings
 int check_raytrace_args(Context& c, const PtTextures* tx);
+// false for a rank of the sharding that holds no row of a width x height frame (or for an empty frame): no texture binding is asked of it
+bool rank_holds_pixels(const Context& c, uint32_t width, uint32_t height);
 
 // The tail of a counted download (pt_*_download_*): the counts of what the last render left go out -- `count` rows of `row` records -- then
 // min(capacity, count * row) records. Synchronises.

@@ -96,7 +96,7 @@ def spatial_resample(n, canon, pc_c, neighbours, draws):
 def _search_margins(a, b, depth_a, normal_thr, depth_thr):
     return min(_margin(np.dot(a["Normal"], b["Normal"]), normal_thr),
                _margin(abs(depth_a - b["Depth"]), depth_thr * max(depth_a, b["Depth"])),
-               _margin(abs(a["Roughness"] - b["Roughness"]), 0.5 * max(a["Roughness"], b["Roughness"])),
+               R.roughness_margin(a["Roughness"], b["Roughness"]),
                _margin(abs(LUMA @ a["F0"] - LUMA @ b["F0"]), 0.25), _margin(abs(LUMA @ a["Albedo"] - LUMA @ b["Albedo"]), 0.25))
 
 
@@ -124,7 +124,7 @@ def temporal_pass(cur, prev, mv, fresh, history, lights, frame, bsdf, max_histor
             for c in (np.float32(x) + mvx, np.float32(y) + mvy):
                 margin[y, x] = min(margin[y, x], abs(abs(float(c) - np.floor(float(c))) - 0.5))
             a = cur.material(y, x)
-            for qx, qy in R.temporal_candidates(x, y, (mvx, mvy), W, H, rng):
+            for qx, qy in R.temporal_candidates(x, y, (mvx, mvy), W, H, rng, stats=stats):
                 if not (0 <= qx < W and 0 <= qy < H) or not prev.valid[qy, qx]:
                     continue
                 b = prev.material(qy, qx)
@@ -165,12 +165,12 @@ def temporal_pass(cur, prev, mv, fresh, history, lights, frame, bsdf, max_histor
         else:
             empty(out, k, M)
     if boiling:
-        _boil(cur, out, margin, strength)
+        _boil(cur, out, margin, strength, stats)
     return out, margin
 
 
-def _boil(cur, out, margin, strength):
-    """the boiling filter over the frame's 8 x 8 tiles, as restirref.temporal_pass applies it"""
+def _boil(cur, out, margin, strength, stats=None):
+    """the boiling filter over the frame's 8 x 8 tiles, as restirref.temporal_pass applies it (and counts it: restirref.note_boiling_tile)"""
     H, W = cur.H, cur.W
     for ty in range(0, H, 8):
         for tx in range(0, W, 8):
@@ -184,6 +184,7 @@ def _boil(cur, out, margin, strength):
             total, count = R.butterfly_sum(np.where(nz, Wt, 0)), R.butterfly_sum(nz.astype(np.float32))
             if not count > 0:
                 continue
+            R.note_boiling_tile(stats, len(idx), count)
             mul = np.float32(np.float32(10.0) / np.float32(min(max(strength, 1e-6), 1.0))) - np.float32(9.0)
             thr = float(np.float32(total / count) * mul)
             for ln, y, x in idx:
@@ -191,6 +192,7 @@ def _boil(cur, out, margin, strength):
                     margin[y, x] = min(margin[y, x], _margin(float(Wt[ln]), thr))
                     if Wt[ln] > thr:
                         empty(out, (y, x), 0)
+                        R.note(stats, "boiling_emptied" if len(idx) == 64 else "boiling_cut_emptied")
             tmin = min((margin[y, x] for _, y, x in idx), default=np.inf)
             if tmin < 1e-5:
                 for _, y, x in idx:
@@ -216,7 +218,7 @@ def spatial_pass(cur, inp, in_margin, lights, table, frame, bsdf, samples, boost
             nb = []
             for i in range(n):
                 e = table[(start + i) & 8191]
-                qx, qy = R.reflect(x + R.spatial_offset(int(e[0]), radius), y + R.spatial_offset(int(e[1]), radius), W, H)
+                qx, qy = R.reflect(x + R.spatial_offset(int(e[0]), radius), y + R.spatial_offset(int(e[1]), radius), W, H, stats, "spatial")
                 if not (0 <= qx < W and 0 <= qy < H) or not cur.valid[qy, qx]:
                     continue
                 b = cur.material(qy, qx)

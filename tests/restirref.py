@@ -55,16 +55,29 @@ def spatial_offset(q, radius):
     return int(np.float32(np.float32(q) / np.float32(127.0)) * np.float32(radius))
 
 
-def reflect(x, y, w, h):
-    """RAB_ClampSamplePositionIntoView (one reflection)"""
+def note(stats, key, n=1):
+    """bookkeeping of what a pass met (the edge witnesses of the per-pixel pins): counts, never part of a result"""
+    if stats is not None:
+        stats[key] = stats.get(key, 0) + n
+
+
+def reflect(x, y, w, h, stats=None, what="reflect"):
+    """RAB_ClampSamplePositionIntoView (one reflection). stats[what + "_left" / "_top" / "_right" / "_bottom"] count the reflections by
+    edge, stats[what + "_outside"] the positions one reflection leaves outside the view."""
     if x < 0:
         x = -x
+        note(stats, what + "_left")
     if y < 0:
         y = -y
+        note(stats, what + "_top")
     if x >= w:
         x = 2 * w - x - 1
+        note(stats, what + "_right")
     if y >= h:
         y = 2 * h - y - 1
+        note(stats, what + "_bottom")
+    if not (0 <= x < w and 0 <= y < h):
+        note(stats, what + "_outside")
     return x, y
 
 
@@ -73,15 +86,16 @@ def hlsl_round(v):
     return int(np.rint(np.float32(v)))
 
 
-def temporal_candidates(x, y, mv, w, h, rng, rounding=hlsl_round):
-    """the up-to-9 positions of the history search, reflected into view, with the draws they consume (attempts >= 1 draw x, then y)"""
+def temporal_candidates(x, y, mv, w, h, rng, rounding=hlsl_round, stats=None):
+    """the up-to-9 positions of the history search, reflected into view, with the draws they consume (attempts >= 1 draw x, then y).
+    stats: reflect's counters under "temporal_*" (positions the search reached before it found its history pixel)"""
     px, py = rounding(np.float32(x) + np.float32(mv[0])), rounding(np.float32(y) + np.float32(mv[1]))
     for i in range(9):
         qx, qy = px, py
         if i:
             rx, ry = rng.next(), rng.next()
             qx += int(np.float32(rx - np.float32(0.5)) * np.float32(6.0)); qy += int(np.float32(ry - np.float32(0.5)) * np.float32(6.0))
-        yield reflect(qx, qy, w, h)
+        yield reflect(qx, qy, w, h, stats, "temporal")
 
 
 def reconstruct_position(x, y, w, h, jitter, depth, projection_to_view, view_to_world):
@@ -178,6 +192,15 @@ def butterfly_sum(values):
         v = (v + v[lanes ^ m]).astype(np.float32)
         m <<= 1
     return v[0]
+
+
+def note_boiling_tile(stats, pixels_in_frame, count):
+    """a tile in which the boiling filter decided (count > 0 reservoirs averaged): stats["boiling_tiles"], and for a tile the frame's
+    right or bottom edge cuts (fewer than 64 pixels in the frame) stats["boiling_cut_tiles"] and its count in ["boiling_cut_count"]"""
+    note(stats, "boiling_tiles")
+    if pixels_in_frame < 64:
+        note(stats, "boiling_cut_tiles")
+        note(stats, "boiling_cut_count", int(count))
 
 
 def boiling_filter(W, valid, strength):
@@ -290,6 +313,17 @@ def _margin(a, b):
     return abs(a - b) / max(abs(a), abs(b), 1e-30)
 
 
+def roughness_margin(ra, rb):
+    """the margin of RAB_AreMaterialsSimilar's roughness test, |ra - rb| <= 0.5 max(ra, rb). One roughness exactly twice the other -- the
+    pin scene's floor and bar: snorm16 codes 13107 and 26214 -- is a tie, not a decision at risk: doubling is exact in binary floating
+    point, so the decoded values keep the ratio in float32 as in float64, |ra - rb| is the smaller one and 0.5 max the same bits without
+    a rounding anywhere, and `<=` holds in every arithmetic."""
+    lo, hi = min(ra, rb), max(ra, rb)
+    if hi == 2.0 * lo and np.float32(hi) == np.float32(2.0) * np.float32(lo):
+        return np.inf
+    return _margin(abs(ra - rb), 0.5 * hi)
+
+
 # ---- the Visibility word of a reservoir (DESIGN.md section 1, "Reservoir visibility") ------------------------------------------------
 def pack(rgb, dx=0, dy=0, age=0):
     """bits 0-14: uint(clamp(v, 0, 1) * 31) per channel (float32, as stored); 15-20 / 21-26: dx, dy as 6-bit two's complement clamped to
@@ -378,13 +412,13 @@ def temporal_pass(cur, prev, mv, fresh, history, lights, frame, bsdf, max_histor
             for c in (np.float32(x) + mvx, np.float32(y) + mvy):
                 margin[y, x] = min(margin[y, x], abs(abs(float(c) - np.floor(float(c))) - 0.5))
             a = cur.material(y, x)
-            for qx, qy in temporal_candidates(x, y, (mvx, mvy), W, H, rng):
+            for qx, qy in temporal_candidates(x, y, (mvx, mvy), W, H, rng, stats=stats):
                 if not (0 <= qx < W and 0 <= qy < H) or not prev.valid[qy, qx]:
                     continue
                 b = prev.material(qy, qx)
                 margin[y, x] = min(margin[y, x], _margin(np.dot(a["Normal"], b["Normal"]), normal_thr),
                                    _margin(abs(float(expected) - b["Depth"]), depth_thr * max(float(expected), b["Depth"])),
-                                   _margin(abs(a["Roughness"] - b["Roughness"]), 0.5 * max(a["Roughness"], b["Roughness"])),
+                                   roughness_margin(a["Roughness"], b["Roughness"]),
                                    _margin(abs(LUMA @ a["F0"] - LUMA @ b["F0"]), 0.25),
                                    _margin(abs(LUMA @ a["Albedo"] - LUMA @ b["Albedo"]), 0.25))
                 if neighbour_ok(a, b, float(expected), normal_thr, depth_thr):
@@ -461,6 +495,7 @@ def temporal_pass(cur, prev, mv, fresh, history, lights, frame, bsdf, max_histor
                 total, count = butterfly_sum(np.where(nz, Wt, 0)), butterfly_sum(nz.astype(np.float32))
                 if not count > 0:
                     continue
+                note_boiling_tile(stats, len(idx), count)
                 mul = np.float32(np.float32(10.0) / np.float32(min(max(strength, 1e-6), 1.0))) - np.float32(9.0)
                 thr = float(np.float32(total / count) * mul)
                 for ln, y, x in idx:
@@ -468,6 +503,7 @@ def temporal_pass(cur, prev, mv, fresh, history, lights, frame, bsdf, max_histor
                         margin[y, x] = min(margin[y, x], _margin(float(Wt[ln]), thr))
                         if Wt[ln] > thr:
                             empty(out, (y, x), 0)
+                            note(stats, "boiling_emptied" if len(idx) == 64 else "boiling_cut_emptied")
                 tmin = min((margin[y, x] for _, y, x in idx), default=np.inf)
                 if tmin < 1e-5:
                     for _, y, x in idx:
@@ -496,13 +532,13 @@ def spatial_pass(cur, inp, in_margin, lights, table, frame, bsdf, samples, boost
             nb = []
             for i in range(n):
                 e = table[(start + i) & 8191]
-                qx, qy = reflect(x + spatial_offset(int(e[0]), radius), y + spatial_offset(int(e[1]), radius), W, H)
+                qx, qy = reflect(x + spatial_offset(int(e[0]), radius), y + spatial_offset(int(e[1]), radius), W, H, stats, "spatial")
                 if not (0 <= qx < W and 0 <= qy < H) or not cur.valid[qy, qx]:
                     continue
                 b = cur.material(qy, qx)
                 margin[y, x] = min(margin[y, x], _margin(np.dot(a["Normal"], b["Normal"]), normal_thr),
                                    _margin(abs(a["Depth"] - b["Depth"]), depth_thr * max(a["Depth"], b["Depth"])),
-                                   _margin(abs(a["Roughness"] - b["Roughness"]), 0.5 * max(a["Roughness"], b["Roughness"])),
+                                   roughness_margin(a["Roughness"], b["Roughness"]),
                                    _margin(abs(LUMA @ a["F0"] - LUMA @ b["F0"]), 0.25),
                                    _margin(abs(LUMA @ a["Albedo"] - LUMA @ b["Albedo"]), 0.25))
                 if neighbour_ok(a, b, a["Depth"], normal_thr, depth_thr):

@@ -9,6 +9,7 @@ import pytest
 
 import __graft_entry__ as ge
 import bsdfref
+import dipins
 import onionref as O
 import presamplingref as P
 import restirref as R
@@ -96,14 +97,15 @@ def test_gpu_onion_cells_pinned(gpu, ptamd, pkg, tables):
     assert rel[same].max() <= 2e-5
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("cell_size", [1.0, 0.3])
-def test_gpu_onion_initial_reservoirs_pinned(gpu, ptamd, pkg, tables, cell_size):
+def _onion_initial_pin(gpu, ptamd, pkg, tables, cell_size, W, H):
     """Temporal on, Off, no boiling, frame 0 after a reset: the reservoirs are the initial ones. LightIndex, M, U, V exact, W within 2e-5;
     pixels within 1e-5 of a coin, or within 1e-6 relative of a layer, ring or azimuth threshold, are left out and counted. At cell size
-    0.3 the Grid would send most of the frame to its Power_RIS fallback, the Onion none of it."""
+    0.3 the Grid would send most of the frame to its Power_RIS fallback, the Onion none of it. Returns how many of the compared pixels lie
+    in a screen tile that the frame's right or bottom edge cuts. Left out, measured: none at 37 x 23 (814 valid pixels) and 21 x 13 (252)."""
     S, L = pkg.scenes, pkg.layouts
-    W, H, n, frame = 40, 24, 8, 3
+    n, frame = 8, 3
+    cut_x, cut_y = (W // P.SCREEN_TILE if W % P.SCREEN_TILE else -1), (H // P.SCREEN_TILE if H % P.SCREEN_TILE else -1)
+    in_cut = 0
     gpu.set_sharding(0, 1, 16)
     scene = S.emitter_field(64, aspect=W / H)
     g = ptamd.Scene(gpu, scene)
@@ -139,6 +141,7 @@ def test_gpu_onion_initial_reservoirs_pinned(gpu, ptamd, pkg, tables, cell_size)
                 near_threshold += m[0] < NEAR_THRESHOLD
                 continue
             compared += 1
+            in_cut += int(x // P.SCREEN_TILE == cut_x or y // P.SCREEN_TILE == cut_y)
             gr = got[y, x]
             gli = -1 if gr["LightIndex"] == 0xFFFFFFFF else int(gr["LightIndex"])
             assert (gli, int(gr["M"])) == (li, M), (x, y, gli, li, int(gr["M"]), cell)
@@ -147,11 +150,30 @@ def test_gpu_onion_initial_reservoirs_pinned(gpu, ptamd, pkg, tables, cell_size)
                 assert abs(float(gr["W"]) - Wt) <= 2e-5 * Wt, (x, y, float(gr["W"]), Wt)
             else:
                 assert float(gr["W"]) == 0.0
-    print(f"cell size {cell_size}: {compared} pixels compared, {excluded} left out ({near_threshold} near a cell threshold), "
-          f"fallbacks: Onion {onion_fallback}, Grid {grid_fallback} of {valid}")
+    print(f"cell size {cell_size} at {W} x {H}: {compared} pixels compared ({in_cut} in cut screen tiles), {excluded} left out "
+          f"({excluded / max(1, compared + excluded):.3%}; {near_threshold} near a cell threshold), fallbacks: Onion {onion_fallback}, Grid {grid_fallback} of {valid}")
     assert compared > 0.5 * W * H and excluded < 0.05 * (compared + excluded)
     if cell_size == 0.3:
         assert grid_fallback > 0.5 * valid and onion_fallback == 0
+    return in_cut
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cell_size", [1.0, 0.3])
+def test_gpu_onion_initial_reservoirs_pinned(gpu, ptamd, pkg, tables, cell_size):
+    """_onion_initial_pin at 40 x 24"""
+    _onion_initial_pin(gpu, ptamd, pkg, tables, cell_size, 40, 24)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", dipins.RAGGED, ids=dipins.size_id)
+@pytest.mark.parametrize("cell_size", [1.0, 0.3])
+def test_gpu_onion_initial_reservoirs_pinned_ragged(gpu, ptamd, pkg, tables, cell_size, size):
+    """_onion_initial_pin at the sizes that cut the 16 x 16 block, the 8 x 8 wave tile and the 16-pixel screen tile on both axes: same
+    scene, settings, tolerances and caps; pixels of the cut screen tiles must be among the compared ones. (No pixel of this scene leaves
+    the Onion, so none draws from its screen tile's light tile: that witness is test_direct_lighting_presampling.py's, under Power_RIS.)"""
+    W, H = size
+    assert _onion_initial_pin(gpu, ptamd, pkg, tables, cell_size, W, H) > 0
 
 
 def _means(ptamd, S, L, ctx, g, W, H, ls, layout, frames, base, samples=8, reuse=None):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as ge
+import dipins
 
 M32 = 0xFFFFFFFF
 
@@ -68,10 +69,13 @@ def _oct_decode(e):
     return v / np.linalg.norm(v, axis=-1, keepdims=True)
 
 
-@pytest.mark.gpu
-def test_gpu_one_sample_pin(gpu, ptamd, pkg, oracle):
+def _one_sample_pin(gpu, ptamd, pkg, oracle, W, H):
+    """The plain pass with one candidate on a scene with one emissive triangle, restated per pixel from the downloaded G-buffer and light
+    record: the sample point from the documented draws, the BSDF from the oracle's evaluate, the shadow ray from the oracle's brute-force
+    visibility. The floors on what the frame must show (shadowed and lit floor pixels) are stated for 80 x 60 and taken as the same
+    share of another size (dipins.more_than)."""
     S, L = pkg.scenes, pkg.layouts
-    W, H, frame = 80, 60, 11
+    frame = 11
     scene = _pin_scene(S, L, W / H)
     gpu.set_sharding(0, 1, 16)
     g = ptamd.Scene(gpu, scene)
@@ -135,7 +139,8 @@ def test_gpu_one_sample_pin(gpu, ptamd, pkg, oracle):
 
     occluded = vis[:, 3] == 0
     lit = ~occluded & ((exp_d + exp_s).max(1) > 0)
-    assert occluded.sum() > 20 and lit.sum() > 200                 # both the shadow and the lit floor are in view
+    print(f"one-sample pin at {W} x {H}: {len(pix)} pixels restated, {int(occluded.sum())} occluded, {int(lit.sum())} lit")
+    assert dipins.more_than(occluded.sum(), 20, W, H, 80, 60) and dipins.more_than(lit.sum(), 200, W, H, 80, 60)   # both the shadow and the lit floor are in view
     # occluded: exactly 0 -- except where the float32 surface point of the pass and this float64 one fall on either side of the bar's edge
     flip = occluded & ((got_d[:, :3] != 0).any(1) | (got_s[:, :3] != 0).any(1))
     assert flip.sum() <= max(2, 0.01 * occluded.sum()), flip.sum()
@@ -148,6 +153,21 @@ def test_gpu_one_sample_pin(gpu, ptamd, pkg, oracle):
         err = np.abs(got[sel, :3] - exp[sel]) / np.maximum(np.abs(exp[sel]), 1e-6)
         assert np.quantile(err, 0.99) < 2e-3 and np.all(err[exp[sel] > 1e-4] < 1e-2), (np.quantile(err, 0.99), err.max())
     g.close()
+
+
+@pytest.mark.gpu
+def test_gpu_one_sample_pin(gpu, ptamd, pkg, oracle):
+    """_one_sample_pin at 80 x 60"""
+    _one_sample_pin(gpu, ptamd, pkg, oracle, 80, 60)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", dipins.RAGGED + [(17, 5)], ids=dipins.size_id)
+def test_gpu_one_sample_pin_ragged(gpu, ptamd, pkg, oracle, size):
+    """_one_sample_pin where k_di's 16 x 16 block and 8 x 8 wave tile are cut on both axes, and at 17 x 5: 85 pixels, less than one
+    workgroup, the second block column one pixel wide. The lanes outside the frame leave before the shadow ray's walk, whose stack is the
+    group's in LDS."""
+    _one_sample_pin(gpu, ptamd, pkg, oracle, *size)
 
 
 @pytest.mark.gpu

@@ -9,6 +9,7 @@ import pytest
 
 import __graft_entry__ as ge
 import bsdfref
+import dipins
 import presamplingref as P
 import restirref as R
 
@@ -87,13 +88,17 @@ def _pin_initial(ptamd, S, L, gpu, scene, mode, W, H, frame, n=8):
     return out, got, lights, tiles, cells
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("mode", MODES)
-def test_gpu_initial_reservoirs_pinned(gpu, ptamd, pkg, mode):
+def _initial_pin(gpu, ptamd, pkg, mode, W, H):
     """Temporal on, Off, no boiling, frame 0 after a reset: the reservoirs are the initial ones. LightIndex, M, U, V exact, W within 2e-5
-    (float32 against float64 p-hat); pixels within 1e-5 of a coin or an ill-conditioned cosine are left out and counted."""
+    (float32 against float64 p-hat); pixels within 1e-5 of a coin or an ill-conditioned cosine are left out and counted. Returns the
+    compared pixels of the screen tiles that the frame's right or bottom edge cuts: how many there were, and how many of them drew their
+    candidates from their screen tile's light tile (Power_RIS: all of them; ReGIR: those outside the grid, its fallback). Left out,
+    measured: none of the 814 valid pixels at 37 x 23 and none of the 252 at 21 x 13, in any mode; there 334 and 252 compared pixels lie in
+    cut screen tiles, of which ReGIR's fallback serves 11 and 21."""
     S, L = pkg.scenes, pkg.layouts
-    W, H, n, frame = 40, 24, 8, 3
+    n, frame = 8, 3
+    cut_x, cut_y = (W // P.SCREEN_TILE if W % P.SCREEN_TILE else -1), (H // P.SCREEN_TILE if H % P.SCREEN_TILE else -1)
+    in_cut = from_tile = 0
     gpu.set_sharding(0, 1, 16)
     scene = S.emitter_field(64, aspect=W / H)
     out, got, lights, tiles, cells = _pin_initial(ptamd, S, L, gpu, scene, mode, W, H, frame, n)
@@ -113,16 +118,20 @@ def test_gpu_initial_reservoirs_pinned(gpu, ptamd, pkg, mode):
             c = P.candidates(mode, x, y, frame, n, Pw, len(lights), tl, tiles["InvSourcePdf"], cl,
                              cells["InvSourcePdf"] if len(cells) else None, centre, 1.0)
             li, U, V, Wt, M, margin = P.initial_reservoir(cur, (y, x), c, lights, bsdf, n)
+            tile = mode == "power_ris"
             if mode == "regir":
                 st = P.rng_states(np.uint64(x), np.uint64(y), frame, R.SALT_INITIAL)
                 j = []
                 for _ in range(3):
                     st, rr = P.rng_next(st); j.append(rr)
-                fallback += int(P.regir_cell(Pw, np.array(j, np.float32), centre, 1.0) < 0)
+                tile = bool(P.regir_cell(Pw, np.array(j, np.float32), centre, 1.0) < 0)
+                fallback += int(tile)
             if margin < NEAR:
                 excluded += 1
                 continue
             compared += 1
+            if x // P.SCREEN_TILE == cut_x or y // P.SCREEN_TILE == cut_y:
+                in_cut += 1; from_tile += int(tile)
             gr = got[y, x]
             gli = -1 if gr["LightIndex"] == 0xFFFFFFFF else int(gr["LightIndex"])
             assert (gli, int(gr["M"])) == (li, M), (mode, x, y, gli, li, int(gr["M"]))
@@ -131,8 +140,31 @@ def test_gpu_initial_reservoirs_pinned(gpu, ptamd, pkg, mode):
                 assert abs(float(gr["W"]) - Wt) <= 2e-5 * Wt, (mode, x, y, float(gr["W"]), Wt)
             else:
                 assert float(gr["W"]) == 0.0
-    print(f"{mode}: {compared} pixels compared, {excluded} within {NEAR} of a decision, {fallback} ReGIR fallbacks")
+    print(f"{mode} at {W} x {H}: {compared} pixels compared, {excluded} within {NEAR} of a decision ({excluded / max(1, compared + excluded):.3%}), "
+          f"{fallback} ReGIR fallbacks; in cut screen tiles {in_cut} compared, {from_tile} of them drawing from the light tile")
     assert compared > 0.5 * W * H and excluded < 0.05 * (compared + excluded)
+    return in_cut, from_tile
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES)
+def test_gpu_initial_reservoirs_pinned(gpu, ptamd, pkg, mode):
+    """_initial_pin at 40 x 24"""
+    _initial_pin(gpu, ptamd, pkg, mode, 40, 24)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", dipins.RAGGED, ids=dipins.size_id)
+@pytest.mark.parametrize("mode", MODES)
+def test_gpu_initial_reservoirs_pinned_ragged(gpu, ptamd, pkg, mode, size):
+    """_initial_pin at the sizes that cut the 16-pixel screen tile on both axes (37 wide: the last tile is 5 pixels wide; 23 and 13 high:
+    7 and 13 rows in the last one), the 16 x 16 block and the 8 x 8 wave tile: same scene, settings, tolerances and caps. Pixels of the cut
+    screen tiles must be among the compared ones, and under Power_RIS every one of them draws from its tile's light tile."""
+    W, H = size
+    in_cut, from_tile = _initial_pin(gpu, ptamd, pkg, mode, W, H)
+    assert in_cut > 0
+    if mode == "power_ris":
+        assert from_tile == in_cut
 
 
 def _means(ptamd, S, L, ctx, g, W, H, mode, frames, base, samples=8, reuse=None):

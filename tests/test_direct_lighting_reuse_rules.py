@@ -160,3 +160,49 @@ def test_boiling_filter():
     assert not R.boiling_filter(np.zeros(64, np.float32), valid, 0.2).any()
     v = np.random.default_rng(1).random(64).astype(np.float32)
     assert R.butterfly_sum(v) == R.butterfly_sum(v[np.arange(64) ^ 1])  # order-independent across lanes
+
+
+# ---- what counts as "near a decision" ---------------------------------------------------------------------------------------------
+def test_exact_roughness_tie_is_not_a_decision_at_risk():
+    """The pin scene's floor (roughness 0.4, snorm16 code 13107) and bar (0.8, code 26214) meet the similarity test |ra - rb| <= 0.5 max
+    exactly on its boundary. For codes q and 2 q the decoded values are in the ratio 2 in float32 as in float64, and both sides of the
+    test are then the same bits: no arithmetic can take it the other way. roughness_margin says so; everywhere else it is the relative
+    margin the pins always used."""
+    q = np.arange(66, 16384)                                             # decoded >= the 2e-3 floor, 2 q still a code
+    lo32, hi32 = q.astype(np.float32) / np.float32(32767.0), (2 * q).astype(np.float32) / np.float32(32767.0)
+    assert np.array_equal(hi32, np.float32(2.0) * lo32)
+    assert np.array_equal(np.abs(lo32 - hi32), np.float32(0.5) * np.maximum(lo32, hi32))
+    lo, hi = 13107 / 32767.0, 26214 / 32767.0
+    assert R._margin(abs(lo - hi), 0.5 * max(lo, hi)) == 0.0             # what the pins saw: a decision with no margin at all
+    assert R.roughness_margin(lo, hi) == np.inf and R.roughness_margin(hi, lo) == np.inf
+    a = {"Normal": np.array([0, 1.0, 0]), "Depth": 2.0, "Roughness": lo, "F0": np.full(3, 0.04), "Albedo": np.full(3, 0.8)}
+    assert R.neighbour_ok(a, dict(a, Roughness=hi), 2.0, 0.5, 0.1)       # the tie is on the accepting side
+    for ra, rb in ((lo, 26215 / 32767.0), (lo, 26213 / 32767.0), (0.4, 0.8000001), (0.5, 0.5), (0.2, 0.9), (2e-3, 4e-3 + 1e-12)):
+        assert R.roughness_margin(ra, rb) == R._margin(abs(ra - rb), 0.5 * max(ra, rb)), (ra, rb)
+    assert R.roughness_margin(lo, 26215 / 32767.0) < 1e-4                # one code off the tie is near, and is still left out
+
+
+def test_tie_rule_changes_what_is_left_out_and_nothing_else(pkg, oracle, monkeypatch):
+    """The spatial pass over the oracle's G-buffer of the pin scene at 37 x 23 and a synthetic fresh frame: with the tie taken for a
+    decision at risk (the margin as it was) every floor pixel that drew a bar pixel among its eight neighbours is left out -- over a
+    quarter of the valid pixels, the per-pixel pins' cap -- and with the tie rule a few per cent are; the reservoirs are the same."""
+    import bsdfref
+    import visscene
+    S, L = pkg.scenes, pkg.layouts
+    W, H = 37, 23
+    scene = visscene.pin_scene(S, W / H)
+    gb, _, _ = oracle.render(scene, S.graphics_settings(W, H, spp=1, bounces=0), layouts=L)
+    cur = R.Surfaces(gb, scene.camera)
+    lights, bsdf, table = visscene.host_lights(scene, L), bsdfref.Reference(), R.offset_table()
+    fresh = visscene.synthetic_frame(cur, lights, bsdf, 1)
+
+    def left_out():
+        out, margin = R.spatial_pass(cur, fresh, np.full((H, W), np.inf), lights, table, 40, bsdf, 1, 8, 20, 32.0, True)
+        return out, float((cur.valid & (margin < 1e-5)).sum()) / cur.valid.sum()
+    new, share = left_out()
+    monkeypatch.setattr(R, "roughness_margin", lambda ra, rb: R._margin(abs(ra - rb), 0.5 * max(ra, rb)))
+    old, old_share = left_out()
+    print(f"left out at {W} x {H}: {old_share:.1%} with the tie at risk, {share:.1%} with the tie rule")
+    assert old_share > 0.25 and share < 0.05
+    for k in R.FIELDS:
+        assert np.array_equal(new[k], old[k]), k

@@ -9,6 +9,7 @@ import pytest
 
 import __graft_entry__ as ge
 import bsdfref
+import dipins
 import restirref as R
 import restirvisref as V
 import visscene
@@ -65,18 +66,19 @@ CONFIGS = [  # (name, temporal, spatial samples, boiling, visibility settings)
 ]
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("name,temporal,spatial,boiling,vis", CONFIGS, ids=[c[0] for c in CONFIGS])
-def test_gpu_visibility_pinned_per_pixel(gpu, ptamd, pkg, name, temporal, spatial, boiling, vis):
-    """4 frames of 48 x 32 on the pin scene with the camera moving 0.17 per frame, 8 candidates, initial visibility on. Each frame's final
+def _visibility_pin(gpu, ptamd, pkg, name, temporal, spatial, boiling, vis, W, H):
+    """4 frames of W x H on the pin scene with the camera moving 0.17 per frame, 8 candidates, initial visibility on. Each frame's final
     reservoirs match the restatement, fed the downloaded G-buffers, motion vectors, light records, last frame's final reservoirs and the
     frame's initial reservoirs (from a second context without visibility; the restatement applies initial visibility itself):
     LightIndex, M, Age, U, V and the Visibility word exactly, W to 2e-5 relative (the new arithmetic only zeroes terms; measured up to 1.5e-5,
     as without visibility). Pixels within 1e-5 of a
     decision -- restirref's, and every ray's edge values and tmin / tmax -- are left out and counted, and so is every pixel that reused
-    one (measured: 0.9 % of the valid pixels temporal-only, 10 to 22 % with a spatial pass). Each configuration must have exercised its rule."""
+    one (measured, of the valid pixels: 48 x 32 0.8 to 1.5 %, 37 x 23 1.8 to 2.3 %, 21 x 13 0.2 to 0.5 %; 10 to 22 % at 48 x 32 with a
+    spatial pass while the pin scene's roughness tie counted as a decision at risk, restirref.roughness_margin). Each configuration must
+    have exercised its rule. Returns what the restatement counted on the way."""
     S, L = pkg.scenes, pkg.layouts
-    W, H, n, F0 = 48, 32, 8, 40
+    n, F0 = 8, 40
+    edges = {}
     bsdf = bsdfref.Reference()
     table = R.offset_table()
     basic = L.DI_BIAS_CORRECTION_BASIC
@@ -111,7 +113,8 @@ def test_gpu_visibility_pinned_per_pixel(gpu, ptamd, pkg, name, temporal, spatia
         lights = r.direct_lighting.download_lights()
         cur = R.Surfaces(out, cam)
         mv = out["MotionVector"].view(np.float16).astype(np.float32)
-        st = {}
+        st = edges                                                         # the edge counters run over the frames; "zeroed" is per frame
+        st["zeroed"] = 0
         exp, margin, emptied = V.initial_visibility(cur, fresh, lights, occ, n)
         seen["emptied"] += int(emptied.sum())
         if temporal:
@@ -154,6 +157,30 @@ def test_gpu_visibility_pinned_per_pixel(gpu, ptamd, pkg, name, temporal, spatia
         assert seen["discarded"] > 0
     del r, r2
     g2.close(); ctx2.close(); g.close()
+    return edges
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,temporal,spatial,boiling,vis", CONFIGS, ids=[c[0] for c in CONFIGS])
+def test_gpu_visibility_pinned_per_pixel(gpu, ptamd, pkg, name, temporal, spatial, boiling, vis):
+    """_visibility_pin at 48 x 32"""
+    _visibility_pin(gpu, ptamd, pkg, name, temporal, spatial, boiling, vis, 48, 32)
+
+
+RAGGED_CONFIGS = [c for c in CONFIGS if c[0] in ("initial-spatial-basic", "both-raytraced-boiling", "both-raytraced-reuse")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", dipins.RAGGED, ids=dipins.size_id)
+@pytest.mark.parametrize("name,temporal,spatial,boiling,vis", RAGGED_CONFIGS, ids=[c[0] for c in RAGGED_CONFIGS])
+def test_gpu_visibility_pinned_per_pixel_ragged(gpu, ptamd, pkg, name, temporal, spatial, boiling, vis, size):
+    """_visibility_pin at the sizes that cut every tile of the DI kernels on both axes (tests/dipins.py), for a Basic row, a Raytraced row
+    with the boiling filter and a Raytraced row with final-visibility reuse on -- the carried pixel offset of a reused visibility goes
+    through `history index % width`, with an odd width here. Same scene, camera path, settings, tolerances and caps; the run must have
+    reached the edges."""
+    W, H = size
+    seen = _visibility_pin(gpu, ptamd, pkg, name, temporal, spatial, boiling, vis, W, H)
+    dipins.assert_edge_witnesses(seen, W, H, name, temporal=temporal, spatial=spatial > 0, boiling=temporal and boiling)
 
 
 @pytest.mark.gpu

@@ -25,10 +25,21 @@ SCENES = {
 CHAINED = ("fused_flat", "streaming_flat")             # the direct-lighting + SHARC cell again with pt_set_round_chains(3)
 
 
-@pytest.mark.parametrize("name", list(SCENES))
-def test_frame_forms_agree(ptamd, pkg, name):
+# Frames that do not fill a tile (tests/test_frame_edges.py): 37 x 23 cuts the 16 x 16 block and the 8 x 8 wave tile on both axes and leaves 83 pixels
+# in the last 256-pixel queue tile; 17 x 5 is less than one workgroup -- one queue tile, a wave of 21 lanes and two empty ones, and more sub-queues
+# than tiles in every form.
+RAGGED_SIZES = [(37, 23), (17, 5)]
+RAGGED_SCENES = ("fused_flat", "fused_phased", "streaming_flat", "streaming_phased")
+
+
+def _forms_agree(ptamd, pkg, name, size=None):
+    """size: None, the scene's own; or a frame size, at which every texture and the primary rays are compared too, not RadianceF32 and the
+    secondary rays alone"""
     S, L = pkg.scenes, pkg.layouts
     make, (W, H), streaming, phased = SCENES[name]
+    every_texture = size is not None
+    if size is not None:
+        W, H = size
     ctx = ptamd.DeviceContext(0)                        # a context of its own: debug flags, chains and the cache do not leak into other tests
     try:
         g = ptamd.Scene(ctx, make(S, W / H))
@@ -49,6 +60,9 @@ def test_frame_forms_agree(ptamd, pkg, name):
                 ctx.set_debug_flags(0)
             c = ctx.counters()
             assert c.StackOverflows == 0
+            if every_texture:
+                assert c.PrimaryRays == W * H
+                return np.concatenate([a.reshape(-1).view(np.uint8) for _, a in sorted(ptamd.textures_to_numpy(r.textures).items())]), c.SecondaryRays
             return ptamd.textures_to_numpy({"RadianceF32": r.textures["RadianceF32"]})["RadianceF32"].view(np.uint32).copy(), c.SecondaryRays
 
         cells = {}
@@ -75,3 +89,16 @@ def test_frame_forms_agree(ptamd, pkg, name):
             assert rays == cells[True, True][1] and np.array_equal(img, cells[True, True][0])
     finally:
         ctx.close()
+
+
+@pytest.mark.parametrize("name", list(SCENES))
+def test_frame_forms_agree(ptamd, pkg, name):
+    _forms_agree(ptamd, pkg, name)
+
+
+@pytest.mark.parametrize("size", RAGGED_SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("name", RAGGED_SCENES)
+def test_frame_forms_agree_at_ragged_sizes(ptamd, pkg, name, size):
+    """the same matrix -- the class assertion through accel_stats() included, so the small frame really takes the form its scene claims --
+    with every output texture compared byte for byte"""
+    _forms_agree(ptamd, pkg, name, size)

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as ge
+import dipins
 import sharcref as R
 
 pytestmark = pytest.mark.gpu
@@ -141,20 +142,48 @@ def test_empty_cache_is_the_plain_render(ptamd, pkg, rigs, name, flags):
     assert len(rig.map()) == 0
 
 
+def test_no_update_pixel_leaves_the_plain_render(ptamd, pkg, rigs):
+    """5 x 3 with DownscaleFactor 4: the update grid is 1 x 0, so no update pass runs (the resolve and the query do, on an empty map).
+    The map stays empty and the frame is the plain render bit for bit, ray counters included -- with no debug flag to keep the cache empty."""
+    S = pkg.scenes
+    W, H = 5, 3
+    rig = Rig(ptamd, S.cornell_box(aspect=W / H, variant="ggx", glass_sphere=True), W, H); rigs.append(rig)
+    for f in range(2):
+        gs = settings(pkg, W, H, spp=8, bounces=5, frame=3 + f)
+        plain = rig.frame(gs)
+        cached = rig.frame(gs, sharc=pkg.layouts.sharc_settings(downscale=4))
+        assert plain[2] == (W * H, plain[2][1]) and plain[2][1] > 0
+        assert np.array_equal(plain[0], cached[0]) and np.array_equal(plain[1].view(np.uint32), cached[1].view(np.uint32))
+        assert plain[2] == cached[2]
+        assert len(rig.map()) == 0 and rig.r.sharc.download_update_paths().size == 0
+
+
 # ---- 3, 4, 5 -----------------------------------------------------------------------------------------------------------------------
-def _pinned_frames(ptamd, pkg, rigs, frames=3):
+# The update pass runs one path per update pixel, (W / DownscaleFactor) x (H / DownscaleFactor) of them, truncated. 64 x 36 halves evenly; 37 x 23 gives
+# 18 x 11 (factor 2) and 12 x 7 (factor 3): both axes truncated, both grids cut the 16 x 16 block and the 8 x 8 wave tile, and the G-buffer texel of a
+# path is min(int(u * W), W - 1) with an odd W.
+# At 37 x 23 the camera is jittered by a fraction of a pixel (test_estimator_reference.py's jitter): unjittered, pixel centres of this raster lie on
+# the seams between the walls, where a path starts inside the next wall's plane, meets it at t = 0 and can stay in the corner for several bounces --
+# six of the 574 segments of the first frame, all too short for test_log_validity's probe, which allows 1 %.
+PINNED = [((64, 36), 2), ((37, 23), 2), ((37, 23), 3)]
+RAGGED_PINNED = PINNED[1:]
+RAGGED_JITTER = (0.2, -0.35)
+_pinned_id = lambda p: f"{p[0][0]}x{p[0][1]}-downscale{p[1]}"
+
+
+def _pinned_frames(ptamd, pkg, rigs, frames=3, size=(64, 36), downscale=2):
     S, L = pkg.scenes, pkg.layouts
-    W, H = 64, 36
-    scene = S.cornell_box(aspect=W / H, variant="diffuse")
+    W, H = size
+    scene = S.cornell_box(aspect=W / H, variant="diffuse", jitter=(0.0, 0.0) if size == (64, 36) else RAGGED_JITTER)
     rig = Rig(ptamd, scene, W, H, capacity=1 << 16, flags=LOG_PATHS); rigs.append(rig)
-    ss = L.sharc_settings(downscale=2, accumulation_frames=2)          # frame 2 is the third: the resolve's rescale is in the comparison
+    ss = L.sharc_settings(downscale=downscale, accumulation_frames=2)  # frame 2 is the third: the resolve's rescale is in the comparison
     ref = R.Cache(1 << 16)
     cam = np.array(scene.camera)["Position"]
     out = []
     for f in range(frames):
         rig.frame(settings(pkg, W, H, frame=f), sharc=ss)
         log = rig.r.sharc.download_update_paths()
-        assert log.shape == ((W // 2) * (H // 2), 9)
+        assert log.shape == ((W // downscale) * (H // downscale), 9)
         resampled = wrong_keys = vertices = 0
         for path in log:
             hit = (path["Flags"] & R.HIT) != 0
@@ -184,19 +213,32 @@ def test_update_and_resolve_pinned(ptamd, pkg, rigs):
     assert any(R.unpack(v[3])[1] == 2 and R.unpack(v[3])[2] == 0 for v in ref.resolved.values())   # ... and voxels went through the AccumulationFrames rescale
 
 
-def test_log_validity(ptamd, pkg, rigs):
+@pytest.mark.parametrize("pinned", RAGGED_PINNED, ids=_pinned_id)
+def test_update_and_resolve_pinned_ragged(ptamd, pkg, rigs, pinned):
+    """the same three frames where the update grid is truncated on both axes and cut by its blocks: keys, the resampled count and the
+    {key -> voxel} map exact, as _pinned_frames asserts frame by frame (the floor on live entries is 64 x 36's share of the paths)"""
+    (W, H), downscale = pinned
+    rig, ref, scene, ss, out = _pinned_frames(ptamd, pkg, rigs, size=(W, H), downscale=downscale)
+    assert dipins.more_than(len(ref.resolved), 500, W // downscale, H // downscale, 32, 18)
+    assert out[2][1] >= 1
+    assert any(R.unpack(v[3])[1] == 2 and R.unpack(v[3])[2] == 0 for v in ref.resolved.values())
+
+
+def _log_validity(ptamd, pkg, rigs, pinned):
     """Vertex 0 is the G-buffer texel under the LOAD rule; the first two draws are the jitter and the hit update's random number;
     pt_bsdf_sample with the logged inputs (Roughness after the RoughnessThreshold floor) reproduces the next direction and, up to bounce 3
-    (before Russian roulette), the throughput handed to SetThroughput; and every vertex sees the next one along the logged ray."""
+    (before Russian roulette), the throughput handed to SetThroughput; and every vertex sees the next one along the logged ray.
+    The floors on segments and throughputs (500 at 64 x 36 / 2) are taken as the same share of the paths at the other sizes."""
     import torch
-    rig, ref, scene, ss, out = _pinned_frames(ptamd, pkg, rigs, frames=1)
+    (W, H), f = pinned
+    rig, ref, scene, ss, out = _pinned_frames(ptamd, pkg, rigs, frames=1, size=(W, H), downscale=f)
     log = out[0][0]
     scatter = rig.r.sharc.download_update_scatter()
     assert scatter.shape == log.shape
-    W, H, f = rig.W, rig.H, 2
     uw, uh = W // f, H // f
+    more = lambda value, count: dipins.more_than(value, count, uw, uh, 32, 18)
     position = ptamd.textures_to_numpy({"Position": rig.r.textures["Position"]})["Position"]
-    rays, steps, too_close = [], [], 0
+    rays, steps, too_close, short = [], [], 0, []
     PROBE_CLEARANCE = 1e-4                                                # the probe ends this far above the next vertex's face
     for path_index, path in enumerate(log):
         ux, uy = path_index % uw, path_index // uw
@@ -233,9 +275,10 @@ def test_log_validity(ptamd, pkg, rigs):
                 tmax = t_plane - PROBE_CLEARANCE / cos
                 if tmax <= 0:
                     too_close += 1
+                    short.append((path_index, b, float(t_plane), float(cos)))
                     continue
                 rays.append(np.concatenate([o, [0.0], d, [tmax]]))
-    assert len(rays) > 500 and len(steps) > len(rays)
+    assert more(len(rays), 500) and len(steps) > len(rays)
     dev = torch.device("cuda", rig.ctx.device_ordinal)
     ctx, lib = rig.ctx, rig.ctx.lib
     # the BSDF step again, through pt_bsdf_sample
@@ -264,14 +307,23 @@ def test_log_validity(ptamd, pkg, rigs):
     # Nothing lies before a closest hit, so every probe is free. Cutting by a share of the distance to the logged position instead is not
     # sound at grazing incidence: the barycentrics of a sliver-projected triangle move the position along the face by more than that share.
     # A segment too short for the clearance (the next face closer than 1e-4 / cos) is left out and counted: at most 1 %.
-    assert too_close <= 0.01 * len(rays)
+    assert too_close <= 0.01 * len(rays), short                          # (path, bounce, distance along the ray to the next face, cosine there)
     rays = np.asarray(rays, np.float32)
     dr = torch.from_numpy(rays.copy()).to(dev); dv = torch.zeros((len(rays), 4), dtype=torch.float32, device=dev)
     ctx.check(lib.pt_trace_visibility(ctx.handle, C.c_void_p(dr.data_ptr()), len(rays), C.c_void_p(dv.data_ptr())))
     ctx.sync()
     vis = dv.cpu().numpy()
     print(f"log: {len(steps)} BSDF steps, {throughputs} throughputs, {len(rays)} segments, {too_close} too short, {int((vis[:, 3] != 1).sum())} occluded")
-    assert throughputs > 500 and (vis[:, 3] == 1).all()
+    assert more(throughputs, 500) and (vis[:, 3] == 1).all()
+
+
+def test_log_validity(ptamd, pkg, rigs):
+    _log_validity(ptamd, pkg, rigs, PINNED[0])
+
+
+@pytest.mark.parametrize("pinned", RAGGED_PINNED, ids=_pinned_id)
+def test_log_validity_ragged(ptamd, pkg, rigs, pinned):
+    _log_validity(ptamd, pkg, rigs, pinned)
 
 
 def test_query_decision(ptamd, pkg, rigs):
