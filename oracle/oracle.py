@@ -6,9 +6,10 @@ PARITY STATUS: parity unpinned (no reference golden vectors exist; MathLib absen
 The oracle and the kernels are one reading of the shaders written twice, so a mistake in that reading is shared. Stages pinned besides by
 an independent float64 restatement (numpy, tests/*ref.py), which the oracle itself must agree with: ray/triangle and traversal (isectref),
 BSDF (bsdfref), textures / materials / environment (texref), skinning (skinref), post-processing (postref), SHARC (sharcref), the DI
-passes (restirref and its siblings), the primary surface (surfaceref: or_gbuffer_render) and the untextured path estimator
-(pathref: or_raytrace_render; its IsDIEnabled half exists on the device only and is replayed there). Oracle-only remain: the BVH
-builder's choice of tree, the comm kernels, the textured estimator.
+passes (restirref and its siblings), the primary surface (surfaceref: or_gbuffer_render) and the path estimator, textured or
+not (pathref: or_raytrace_render, with surfaceref's alpha-aware closest hit and textured materials and environment; its IsDIEnabled half
+exists on the device only and is replayed there), the BVH builder's choice of tree (bvhref). Oracle-only remain: the comm kernels, which
+have their exact-copy tests.
 """
 import ctypes as C
 import os

@@ -1,5 +1,6 @@
-"""Float64 replay of the path estimator: RayGeneration of Shaders/Raytracing.hlsl:103-415 (default permutation, untextured scenes,
-constant environment colour or the procedural sky), numpy only, vectorised over pixels with a loop over samples and bounces.
+"""Float64 replay of the path estimator: RayGeneration of Shaders/Raytracing.hlsl:103-415 (default permutation; untextured or textured
+scenes -- RGBA8, RGBA8 sRGB and RGBA32F textures, not block-compressed ones; constant environment colour, the procedural sky, or a lat-long
+or cube environment texture under EnvironmentLightTransform), numpy only, vectorised over pixels with a loop over samples and bounces.
 
 Restated from the shader, not from csrc/pt_shade.hpp or oracle/pt_oracle.c. It starts where the shader starts: from the G-buffer textures it
 is handed (Position, FlatNormal / GeometricNormal octahedral, NormalRoughness, BaseColorMetalness, IOR, Transmission, Radiance), decoded
@@ -34,6 +35,30 @@ Largest error / tolerance seen on kept pixels of the CPU oracle (tests/test_esti
 `ggx_s2_b6_no_roulette` (at most 0.013 on the other rows; p99 below 0.0025 and the median relative error below 1e-7 on every row). Loose
 by design; the mutations show that it is tight enough.
 
+Textured vertices (Raytracing.hlsl:289-301 EvaluateMaterial with hitInfo.ShadingNormal, GetFrontTangent() and the hit's TextureCoordinates;
+RaytracingHelpers.hlsli:19-44 the alpha test of every CANDIDATE_NON_OPAQUE_TRIANGLE; ShadingHelpers.hlsli:11-30 the environment): at every
+bounce hit surfaceref.Surface.material evaluates the textured material, on every miss Surface.environment the textured environment, and
+bounce rays take surfaceref's alpha-aware closest hit. A candidate the alpha rule turns down draws no random number: the stream of a pixel
+advances at BSDF samples and roulette only. An untextured scene takes none of these branches, and its figures are bit for bit what they
+were. What a texture adds to the tolerance is `texture_slack`, absolute, next to REL * budget:
+  a tap's value      differs in fp32 because its position does: (the largest difference between neighbouring texels around the footprint)
+                     x (texture size x the triangle's UV extent x the barycentric uncertainty of the hit -- surfaceref's edge margin of
+                     that (ray, triangle) pair: EDGE_B, the transform term, and the ray's drift over the triangle's world altitude), plus
+                     texref's own position and value tolerance (test_texture_reference.py's), which covers the fp32 interpolation of the
+                     f16 corners (surfaceref.Surface.tap_bound)
+  emission, environment   enter linearly: |throughput| x the bound
+  base colour, metallic, roughness, transmission, the perturbed normal   finite differences (textured_vertex): the vertex evaluated once
+                     more per quantity moved by its bound -- lobe weights, sampled direction, single-lobe f / pdf; the relative change of
+                     f / pdf accumulates along the path and scales every later contribution; the change of the lobe weights widens
+                     near_lobe; the change of the sampled direction widens the next ray's drift
+  decisions          `risky` within their bound: Metallic < 1 ahead of the Transmission tap, the rim of the normal map where
+                     sqrt(saturate(1 - x^2 - y^2)) clamps, a candidate's alpha against AlphaCutoff (unless the tap is constant 0 or 1 over
+                     the whole box its position can lie in: then fp32 samples it exactly, also AT the cutoff), the lat-long poles
+                     (atan2 / acos, and the NaN-coordinate rule at |w.y| = 1) within surfaceref.POLE
+Largest error / tolerance on kept pixels of the CPU oracle on the textured rows (tests/test_textured_estimator.py prints it per row): 0.045 on
+`textured_s1_b1`, 0.041 on `plain_s2_b6` and `plain_masked_s2_b6`, at most 0.0085 on the other rows (textured_s2_b6 with and without
+roulette, DLSS-RR, latlong_s2_b6 0.0079, cube_s2_b6 0.0076, plain_transmissive_s2_b6, large_s2_b6); p99 below 0.0024 on every row.
+
 MUTATIONS: switches that each break one rule; the tests show that the comparison notices each.
 """
 import numpy as np
@@ -48,8 +73,10 @@ FLT_MAX = float(np.finfo(np.float32).max)
 DENOISER_NONE, DENOISER_DLSS_RR, DENOISER_NRD_REBLUR, DENOISER_NRD_RELAX = 0, 1, 2, 3
 MUTATIONS = ("roulette_from_3", "roulette_no_divide", "threshold_before_roulette", "bounce_exclusive", "emission_after_throughput",
              "divide_before_finite", "rng_per_sample", "hit_distance_bounce0", "is_diffuse_last_sample",
-             "di_suppress_bounce2", "di_before_divide", "di_swapped", "di_valid_all")
+             "di_suppress_bounce2", "di_before_divide", "di_swapped", "di_valid_all",
+             "alpha_skip_bounce", "material_at_primary_uv", "rejected_draws_random")
 DI_MUTATIONS = tuple(m for m in MUTATIONS if m.startswith("di_"))
+TEXTURE_MUTATIONS = ("alpha_skip_bounce", "material_at_primary_uv", "rejected_draws_random")
 
 f64 = np.float64
 M32 = np.uint64(0xFFFFFFFF)
@@ -140,11 +167,18 @@ def replay(scene, settings, textures, camera, scene_data, di=None, mutations=(),
     radiance = np.zeros((n, 3)); budget = np.zeros((n, 3))
     risky = np.zeros(n, bool)
     segments = np.zeros(n, np.int64)
+    rejected = np.zeros(n, np.int64)                                        # candidates of bounce rays the alpha rule turned down
     is_diffuse = np.ones(n, bool); hit_distance = np.full(n, np.inf)
     emissive_at_bounce_1 = np.zeros(n, bool)
     primary_front = R.dot(prim["geometric"], d0) < 0
     risky |= hitp & (np.abs(R.dot(prim["geometric"], d0)) < FRONT)
-    materials = surface.scene.object_data["Material"]
+    alpha = surface.alpha_rule if len(surface.alpha_rule.tested) else None
+    slack = np.zeros((n, 3))                                                # what the textures' fp32 tap positions may move the sum by
+    primary_uv = None
+    if mut["material_at_primary_uv"]:
+        _, _, tmin0, tmax0 = R.pinhole(cam, uv)
+        c0 = surface.tris.closest(o0, d0, tmin0, tmax0, alpha=alpha)
+        primary_uv = surface.uv_of(c0["tri"], c0["u"], c0["v"])
 
     for sample in range(spp):
         if mut["rng_per_sample"]:
@@ -157,6 +191,7 @@ def replay(scene, settings, textures, camera, scene_data, di=None, mutations=(),
                "roughness": prim["roughness"][act], "ior": prim["ior"][act], "transmission": prim["transmission"][act],
                "emission": prim["radiance"][act], "direction": d0[act], "distance": np.linalg.norm(prim["position"][act] - o0[act], axis=1)}
         throughput = np.ones((k, 3)); sample_radiance = np.zeros((k, 3)); sample_budget = np.zeros((k, 3))
+        sample_slack = np.zeros((k, 3)); drifted = np.zeros((k, 3))           # drifted: the throughput's relative error from textured vertices
         L = np.zeros((k, 3)); lobe = np.zeros(k, np.int64); angle = np.zeros(k)
         last = bounces - 1 if mut["bounce_exclusive"] else bounces
         for bounce in range(last + 1):
@@ -165,8 +200,11 @@ def replay(scene, settings, textures, camera, scene_data, di=None, mutations=(),
             if bounce:
                 sgn = np.where(R.dot(L, cur["flat"]) >= 0, 1.0, -1.0)       # Math::Sign: never 0
                 origin = cur["position"] + (cur["offset"] * sgn)[:, None] * cur["flat"]
-                c = closest_with_drift(surface.tris, origin, L, angle)
+                c = closest_with_drift(surface.tris, origin, L, angle, None if mut["alpha_skip_bounce"] else alpha)
+                if mut["rejected_draws_random"] and c["rejected"].any():
+                    rng_float(state, act[c["rejected"] > 0])
                 segments[act] += 1
+                rejected[act] += c["rejected"]
                 risky[act] |= c["unsafe"]
                 h = surface.reconstruct(c["tri"], c["u"], c["v"], L)
                 hit = c["hit"]
@@ -182,29 +220,46 @@ def replay(scene, settings, textures, camera, scene_data, di=None, mutations=(),
                 env = surface.environment(sd, L)
                 contrib = throughput * env
                 sample_radiance[miss] += contrib[miss]; sample_budget[miss] += (bounce + 1) * np.abs(contrib[miss])
+                env_bound, env_undecided = surface.environment_bound(sd, L, angle)
+                if env_bound.any() or drifted.any():
+                    sample_slack[miss] += (np.abs(throughput) * env_bound[:, None] + np.abs(contrib) * drifted)[miss]
+                risky[act[miss]] |= env_undecided[miss]
                 # the paths that go on: compact every per-path array
                 keep = hit
-                radiance[act[miss]] += sample_radiance[miss]; budget[act[miss]] += sample_budget[miss]
+                radiance[act[miss]] += sample_radiance[miss]; budget[act[miss]] += sample_budget[miss]; slack[act[miss]] += sample_slack[miss]
                 act, throughput, sample_radiance, sample_budget, L = act[keep], throughput[keep], sample_radiance[keep], sample_budget[keep], L[keep]
+                sample_slack, drifted = sample_slack[keep], drifted[keep]
                 hk = {kk: v[keep] for kk, v in h.items()}
-                mat = materials[hk["object"]]
-                emission = np.asarray(mat["EmissiveStrength"], f64)[:, None] * np.asarray(mat["EmissiveColor"], f64)
+                if primary_uv is not None:
+                    hk["uv"] = primary_uv[act]
+                mat = surface.material(hk["object"], hk, c["bary"][keep])       # EvaluateMaterial at the hit: its UVs, shading normal, front tangent
+                emission = mat["EmissiveStrength"][:, None] * mat["EmissiveColor"]
+                bound = mat.get("bound")
+                if bound is not None:
+                    risky[act] |= mat["undecided"]
                 if bounce == 1:
                     emissive_at_bounce_1[act] |= (emission > 0).any(1)
                 suppressed = 2 if mut["di_suppress_bounce2"] else 1
                 if bounce == suppressed:
                     emission = np.where(di_valid[act][:, None], 0.0, emission)
                 risky[act] |= hk["perp"] < FRONT
-                cur = {"position": hk["position"], "offset": hk["offset"], "flat": hk["flat"], "geometric": hk["geometric"], "shading": hk["shading"],
+                cur = {"position": hk["position"], "offset": hk["offset"], "flat": hk["flat"], "geometric": hk["geometric"],
+                       "shading": mat.get("Normal", hk["shading"]),
                        "front": hk["front"], "base": np.asarray(mat["BaseColor"], f64)[:, :3], "metal": np.asarray(mat["Metallic"], f64),
                        "roughness": np.asarray(mat["Roughness"], f64), "ior": np.asarray(mat["IOR"], f64),
                        "transmission": np.asarray(mat["Transmission"], f64), "emission": emission, "direction": L, "distance": cur["distance"][keep]}
+                if bound is not None:
+                    cur.update({"d_" + kk: v for kk, v in bound.items()})
                 if not len(act):
                     break
             m = len(act)
             if not mut["emission_after_throughput"]:
                 contrib = throughput * cur["emission"]
                 sample_radiance += contrib; sample_budget += (bounce + 1) * np.abs(contrib)
+                if drifted.any():
+                    sample_slack += np.abs(contrib) * drifted
+                if "d_emission" in cur:
+                    sample_slack += np.abs(throughput) * cur["d_emission"][:, None]
             # BSDFSample: weights, lobe, direction, pdf, f
             rnd = np.stack([rng_float(state, act) for _ in range(4)], -1)
             q = np.zeros((m, 24))
@@ -215,10 +270,13 @@ def replay(scene, settings, textures, camera, scene_data, di=None, mutations=(),
             s = ref.initialize(q)
             w = ref.weights(s, extv)
             lobe = ref.find_lobe(w, rnd[:, 0])
-            near_lobe = (ref.find_lobe(w, rnd[:, 0] - B.NEAR) != lobe) | (ref.find_lobe(w, rnd[:, 0] + B.NEAR) != lobe)
             with np.errstate(invalid="ignore", divide="ignore"):
                 L, ok, side = ref.sample_lobe(s, rnd, lobe)
-                angle = np.minimum(B.ANGLE + side["cond"], 1.0)
+            moved = textured_vertex(ref, cur, q, s, w, rnd, lobe, L, extv) if "d_base" in cur else None
+            margin = B.NEAR if moved is None else B.NEAR + moved["weights"]
+            near_lobe = (ref.find_lobe(w, rnd[:, 0] - margin) != lobe) | (ref.find_lobe(w, rnd[:, 0] + margin) != lobe)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                angle = np.minimum(B.ANGLE + side["cond"], 1.0) if moved is None else np.minimum(B.ANGLE + side["cond"] + moved["angle"], 1.0)
                 horizon = (lobe != B.TRANSMISSION) & ~(np.abs(R.dot(s["Ng"], L)) > B.NEAR + np.sin(angle))
                 branch = (lobe == B.TRANSMISSION) & ((np.abs(side["tir_margin"]) <= B.NEAR) | (np.abs(side["coin_margin"]) <= B.NEAR))
                 p_all, f_all, _, _ = ref.eval_lobes(s, w, np.where(np.isfinite(L).all(1, keepdims=True), L, s["Ns"]), extv)
@@ -233,6 +291,10 @@ def replay(scene, settings, textures, camera, scene_data, di=None, mutations=(),
                 sample_radiance += contrib; sample_budget += (bounce + 1) * np.abs(contrib)
             throughput = np.where(go[:, None], new_tp, throughput)
             rel = DECISION_REL * (bounce + 1)
+            if moved is not None:
+                drifted = drifted + moved["ratio"]
+            if drifted.any():
+                rel = rel + drifted.max(1)
 
             def threshold_test(tp):
                 lum = B.luminance(tp)
@@ -253,13 +315,15 @@ def replay(scene, settings, textures, camera, scene_data, di=None, mutations=(),
             if not mut["threshold_before_roulette"]:
                 go &= ~threshold_test(throughput)
             ended = ~go
-            radiance[act[ended]] += sample_radiance[ended]; budget[act[ended]] += sample_budget[ended]
+            radiance[act[ended]] += sample_radiance[ended]; budget[act[ended]] += sample_budget[ended]; slack[act[ended]] += sample_slack[ended]
             act, throughput, sample_radiance, sample_budget = act[go], throughput[go], sample_radiance[go], sample_budget[go]
+            sample_slack, drifted = sample_slack[go], drifted[go]
             L, lobe, angle = L[go], lobe[go], angle[go]
             cur = {kk: v[go] for kk, v in cur.items()}
         radiance[act] += sample_radiance; budget[act] += sample_budget        # paths the bounce limit ended
+        slack[act] += sample_slack
 
-    tolerance = REL * budget / max(spp, 1)
+    tolerance = REL * budget / max(spp, 1) + slack / max(spp, 1)
     if mut["di_before_divide"]:
         radiance = radiance + DI
     if mut["divide_before_finite"]:
@@ -273,7 +337,7 @@ def replay(scene, settings, textures, camera, scene_data, di=None, mutations=(),
             risky |= (np.isfinite(radiance) & (np.abs(np.abs(radiance) - FLT_MAX) <= tolerance * spp + ulp32(radiance))).any(1)
         radiance = np.where(finite[:, None], radiance / spp, 0.0)
     tolerance = np.where(finite[:, None], tolerance, 0.0)
-    out = {"primary_hit": hitp, "is_diffuse": is_diffuse, "hit_distance": hit_distance, "segments": segments, "budget": budget, "risky": risky & hitp,
+    out = {"primary_hit": hitp, "is_diffuse": is_diffuse, "hit_distance": hit_distance, "segments": segments, "rejected": rejected, "budget": budget, "texture_slack": slack, "risky": risky & hitp,
            "di_valid": di_valid, "sampled": radiance.copy(), "emissive_at_bounce_1": emissive_at_bounce_1}
     final = radiance + (0.0 if mut["di_before_divide"] else DI)
     out["radiance"] = np.where(hitp[:, None], final, prim["radiance"])
@@ -288,10 +352,50 @@ def replay(scene, settings, textures, camera, scene_data, di=None, mutations=(),
     return out
 
 
-def closest_with_drift(tris, origin, direction, angle):
+def closest_with_drift(tris, origin, direction, angle, alpha=None):
     """surfaceref's closest hit of bounce rays whose fp32 twins may drift sideways by angle * t + 1e-6 (1 + |origin|): the edge margin of
-    every (ray, triangle) pair is widened by that drift over the triangle's smallest world-space altitude."""
-    return tris.closest(origin, direction, 0.0, np.inf, drift=(angle, 1e-6 * (1.0 + np.linalg.norm(origin, axis=1))))
+    every (ray, triangle) pair is widened by that drift over the triangle's smallest world-space altitude. alpha: surfaceref's alpha
+    rule, put to every candidate; the margin is also the barycentric uncertainty the rule and the material's taps are bounded with."""
+    return tris.closest(origin, direction, 0.0, np.inf, drift=(angle, 1e-6 * (1.0 + np.linalg.norm(origin, axis=1))), alpha=alpha)
+
+
+def textured_vertex(ref, cur, q, s, w, rnd, lobe, L, extv):
+    """What the bounds of a textured vertex's material (cur["d_*"], surfaceref.Surface.material) are worth downstream, by finite
+    differences: one more evaluation of the whole vertex -- state, lobe weights, sampled direction, single-lobe f / pdf -- per quantity,
+    moved by its bound (base colour: all channels at once, it enters linearly; the normal: tilted along the basis tangent). Returns
+    `ratio` [m, 3] the relative change of f / pdf, `weights` [m] the change of the lobe weights (widens the lobe decision on rnd.x),
+    `angle` [m] the change of the sampled direction (radians; widens the next ray's drift)."""
+    m = len(lobe)
+    rows = np.arange(m)
+    out = {"ratio": np.zeros((m, 3)), "weights": np.zeros(m), "angle": np.zeros(m)}
+
+    def evaluate(qq, ss=None, ww=None, LL=None):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            if ss is None:
+                ss = ref.initialize(qq); ww = ref.weights(ss, extv)
+                LL = ref.sample_lobe(ss, rnd, lobe)[0]
+            p, f, _, _ = ref.eval_lobes(ss, ww, np.where(np.isfinite(LL).all(1, keepdims=True), LL, ss["Ns"]), extv)
+            return ww, LL, f[rows, lobe] / p[rows, lobe][:, None]
+    _, _, ratio0 = evaluate(q, s, w, L)
+    for key, col in (("base", B.Q_BASE), ("metal", B.Q_METAL), ("rough", B.Q_ROUGH), ("trans", B.Q_TRANS), ("normal", B.Q_NS)):
+        dv = cur["d_" + key]
+        if not dv.any():
+            continue
+        q2 = q.copy()
+        if key == "normal":
+            q2[:, col] = R.normalize(q[:, col] + dv[:, None] * s["basis"][0])
+        elif key == "base":
+            q2[:, col] = q[:, col] + dv[:, None]
+        else:
+            q2[:, col] = np.where(q[:, col] + dv > 1.0, q[:, col] - dv, q[:, col] + dv)      # stay inside [0, 1]
+        w2, L2, ratio2 = evaluate(q2)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            rel = np.abs(ratio2 - ratio0) / np.abs(ratio0)
+        out["ratio"] += np.where(np.isfinite(rel), rel, 0.0)
+        out["weights"] += np.abs(w2 - w).sum(1)
+        with np.errstate(invalid="ignore"):
+            out["angle"] += np.nan_to_num(np.linalg.norm(L2 - L, axis=1), nan=0.0, posinf=0.0)
+    return out
 
 
 # ----------------------------------------------------------------------------------------------

@@ -39,7 +39,19 @@ Tolerances, from the formats (never from an implementation):
                     length), 9.4 on `transformed` and `moved`, 0.8 / 1.9 on the two `scale` cameras. The factor leaves room for another
                     evaluation order on the device, not for another algorithm: at distance 7 the limit is 4e-5.
 
-Every switch of `MUTATIONS` breaks one rule; tests/test_gbuffer_reference.py shows that the comparison notices each.
+Textured hits (RaytracingHelpers.hlsli:19-44 and :113-130, ShadingHelpers.hlsli:32-51 and :105-235, HitInfo.hlsli:85-88, sampled through
+tests/texref.py): Triangles carries both UV sets per corner, decoded from f16 (an absent set reads 0); reconstruct() interpolates them and
+hands the tangent on negated on a back face; closest() puts EVERY candidate of a geometry without the OPAQUE flag to the closest-hit
+IsOpaque (BaseColor.a x the texture's alpha >= AlphaCutoff) at the candidate's own UVs; Surface.material() is EvaluateMaterial with the
+perturbed shading normal, Surface.environment() the lat-long or cube lookup under EnvironmentLightTransform. render() uses them all. The
+bound of a tap (Surface.tap_bound) and what decisions count as undecided are stated in tests/pathref.py's docstring; in the G-buffer
+comparison the bound of each stored quantity is added to its format's step (the albedos: by finite differences of the rational fit).
+
+Every switch of `MUTATIONS` breaks one rule; tests/test_gbuffer_reference.py and, for TEXTURE_MUTATIONS, tests/test_textured_estimator.py
+show that the comparison notices each. `transmission_gate_on_factor` stands for "the Transmission texture applied at Metallic == 1": taken
+literally that mistake leaves no trace (GBufferGeneration.hlsl:191-195 stores Transmission only where Metallic < 1, and the transmission
+lobe's weight is Transmission (1 - Metallic)), so the switch breaks the observable half of the same rule -- the gate reads the Metallic
+FACTOR instead of the textured value (ShadingHelpers.hlsli:213-220 tests it after the Metallic tap).
 """
 import numpy as np
 
@@ -54,9 +66,13 @@ MV_ROUNDINGS = 8.0
 OFFSET_ROUNDINGS = 32.0
 K_POSITION = 100.0
 SNORM16, UNORM8 = 1.0 / 32767.0, 1.0 / 255.0
-MUTATIONS = ("normal_by_matrix", "no_front_flip", "mv_current_camera", "mv_no_vertex_term", "v_not_flipped")
+TEXTURE_MUTATIONS = ("uv_corner0", "alpha_ignores_opaque_flag", "alpha_geometry0", "tangent_no_back_flip", "normal_map_ignored",
+                     "normal_map_without_tangents", "emissive_texture_ignored", "transmission_gate_on_factor", "env_no_transform", "env_transposed")
+MUTATIONS = ("normal_by_matrix", "no_front_flip", "mv_current_camera", "mv_no_vertex_term", "v_not_flipped") + TEXTURE_MUTATIONS
+POLE = 1e-4                                          # sin of the angle to the lat-long poles below which atan2 / the NaN rule decide
 
 f64 = np.float64
+_TRUE = texref.Reference()                           # tolerances come from the unmutated sampler
 
 
 def dot(a, b):
@@ -143,7 +159,8 @@ class Triangles:
             inv = np.linalg.inv(self.o2w[i, :, :3])
             self.w2o[i, :, :3] = inv
             self.w2o[i, :, 3] = -inv @ self.o2w[i, :, 3]
-        cols = {k: [] for k in ("obj", "nrm", "tan", "mot", "has_n", "has_t", "inst", "geom", "prim", "object")}
+        cols = {k: [] for k in ("obj", "nrm", "tan", "mot", "has_n", "has_t", "inst", "geom", "prim", "object", "uv0", "uv1", "has_uv0", "has_uv1",
+                                "opaque", "object0")}
         for i in range(n_inst):
             if not int(scene.instance_masks[i]):
                 continue                                                   # InstanceMask 0: no ray sees it
@@ -161,6 +178,13 @@ class Triangles:
                 cols["has_t"].append(np.full(n, bool(mesh.has_tangents)))
                 cols["inst"].append(np.full(n, i)); cols["geom"].append(np.full(n, g)); cols["prim"].append(np.arange(n))
                 cols["object"].append(np.full(n, int(scene.instance_data[i]["FirstGeometryIndex"]) + g))
+                cols["object0"].append(np.full(n, int(scene.instance_data[i]["FirstGeometryIndex"])))
+                for k, key in enumerate(("TexCoord0", "TexCoord1")):                 # f16 storage; an absent set reads as 0
+                    has = bool(mesh.has_uv[k])
+                    cols[f"uv{k}"].append(np.asarray(mesh.vertices[key]).astype(f64)[idx] if has else np.zeros((n, 3, 2)))
+                    cols[f"has_uv{k}"].append(np.full(n, has))
+                # the bottom level's geometry flag (Scene.ixx:320-324): OPAQUE iff the mesh has no material or AlphaMode::Opaque
+                cols["opaque"].append(np.full(n, mesh.material is None or int(mesh.material["AlphaMode"]) == 0))
         for k, v in cols.items():
             setattr(self, k, np.concatenate(v))
         M = self.o2w[self.inst]
@@ -173,15 +197,27 @@ class Triangles:
         longest = np.maximum(np.maximum(np.linalg.norm(w1, axis=1), np.linalg.norm(w2, axis=1)), np.linalg.norm(w2 - w1, axis=1))
         with np.errstate(invalid="ignore", divide="ignore"):
             self.altitude_world = np.linalg.norm(np.cross(w1, w2), axis=1) / longest
+        self.uv = np.stack([self.uv0, self.uv1], 1)                                         # [T, set, corner, 2]
+        self.uv_extent = np.abs(self.uv[:, :, 1:] - self.uv[:, :, :1]).sum(2).max(-1)       # [T, set]: |uv1 - uv0| + |uv2 - uv0|, larger axis
+        self.uv_magnitude = np.abs(self.uv).max((2, 3))                                     # [T, set]
 
-    def closest(self, o, d, tmin, tmax, chunk=1 << 19, drift=None):
+    def interpolate_uv(self, tri, u, v):
+        """Vertex::Interpolate of both sets at hits (tri, u, v): [n, set, 2]"""
+        c = self.uv[tri]
+        return c[:, :, 0] + u[:, None, None] * (c[:, :, 1] - c[:, :, 0]) + v[:, None, None] * (c[:, :, 2] - c[:, :, 0])
+
+    def closest(self, o, d, tmin, tmax, chunk=1 << 19, drift=None, alpha=None):
         """The exact closest hit of rays (float64 [n, 3], TMin / TMax [n] or scalars, both exclusive): hit, tri, u, v, t and `unsafe`
         (edge / depth of the module docstring). drift = (angle [n], shift [n]): the fp32 ray may lie that far off this one (radians about
-        its origin, world units sideways); the edge margin of a pair widens by (angle |t| + shift) over the triangle's world altitude."""
+        its origin, world units sideways); the edge margin of a pair widens by (angle |t| + shift) over the triangle's world altitude.
+        alpha: the closest-hit alpha rule of RaytracingHelpers.hlsli:19-44 (Surface.alpha_rule): an object with `tested` (the triangles
+        whose candidates are CANDIDATE_NON_OPAQUE_TRIANGLE) and __call__(tri, u, v, barycentric uncertainty) -> (commit, near the cutoff).
+        EVERY candidate inside its triangle and the ray's interval is put to it, not the closest one alone; a candidate the rule cannot
+        decide in fp32 that lies no further than the committed hit makes the ray unsafe."""
         n, T = len(o), len(self.world)
         tmin = np.broadcast_to(np.asarray(tmin, f64), (n,)); tmax = np.broadcast_to(np.asarray(tmax, f64), (n,))
         out = {"hit": np.zeros(n, bool), "tri": np.zeros(n, np.int64), "u": np.zeros(n), "v": np.zeros(n), "t": np.full(n, np.inf),
-               "unsafe": np.zeros(n, bool)}
+               "unsafe": np.zeros(n, bool), "bary": np.zeros(n), "rejected": np.zeros(n, np.int64)}
         V0, E1, E2 = self.world[:, 0], self.world[:, 1] - self.world[:, 0], self.world[:, 2] - self.world[:, 0]
         step = max(1, chunk // max(T, 1))
         W = self.w2o
@@ -204,8 +240,16 @@ class Triangles:
                     thr = thr + (drift[0][sl, None] * np.abs(t) + drift[1][sl, None]) / self.altitude_world[None]
                 lo, hi = tmin[sl, None], tmax[sl, None]
                 inside = (b >= 0) & (t > lo) & (t < hi)
+                undecided, geometric = None, inside
+                if alpha is not None and len(alpha.tested):
+                    ri, ci = np.nonzero(inside[:, alpha.tested])
+                    tj = alpha.tested[ci]
+                    commit, close = alpha(tj, u[ri, tj], v[ri, tj], thr[ri, tj])
+                    inside = inside.copy(); inside[ri[~commit], tj[~commit]] = False
+                    np.add.at(out["rejected"], r0 + ri[~commit], 1)
+                    undecided = (ri[close], tj[close])
                 gap = DEPTH_GAP * np.abs(t)
-                near = (b > -thr) & (t > lo - gap) & (t < hi + gap) & ~inside
+                near = (b > -thr) & (t > lo - gap) & (t < hi + gap) & ~geometric
                 tt = np.where(inside, t, np.inf)
                 j = tt.argmin(1)
                 rows = np.arange(len(oo))
@@ -217,21 +261,110 @@ class Triangles:
                 tie = (others & (t < limit)).any(1)
                 edge = hit & (b[rows, j] < thr[rows, j])
                 rng = hit & ((t1 - tmin[sl] < DEPTH_GAP * t1) | (tmax[sl] - t1 < DEPTH_GAP * t1))
+                if undecided is not None and len(undecided[0]):
+                    ri, tj = undecided
+                    ri = ri[t[ri, tj] < limit[ri, 0]]
+                    edge[ri] = True
             out["hit"][sl] = hit; out["tri"][sl] = j; out["t"][sl] = t1
             out["u"][sl] = np.where(hit, u[rows, j], 0.0); out["v"][sl] = np.where(hit, v[rows, j], 0.0)
             out["unsafe"][sl] = steal | tie | edge | rng
+            out["bary"][sl] = thr[rows, j]
         return out
 
 
-class Surface:
-    """The reference of one scene; the keyword switches (MUTATIONS) each break one rule."""
+def object_textures(scene):
+    """Per ObjectData record: (Material, slot -> (texel array, format, TextureCoordinateIndex)), read the way the shaders read them: the
+    TextureMapInfoArray's descriptors into the heap. Block-compressed textures are not this reference's business (test_bc_*)."""
+    out = []
+    for od in scene.object_data:
+        slots = {}
+        for k, slot in enumerate(texref.SLOTS):
+            info = od["TextureMapInfoArray"][k]
+            if int(info["Descriptor"]) != 0xFFFFFFFF:
+                item = scene.heap[int(info["Descriptor"])]
+                assert item.fmt in (texref.FMT_RGBA8, texref.FMT_RGBA8_SRGB, texref.FMT_RGBA32F), item.fmt
+                slots[slot] = (item.array, item.fmt, int(info["TextureCoordinateIndex"]))
+        out.append((od["Material"], slots))
+    return out
 
-    def __init__(self, scene, **mutations):
+
+class AlphaRule:
+    """The closest-hit alpha rule as Triangles.closest consumes it (RaytracingHelpers.hlsli:19-44, ShadingHelpers.hlsli:105-116): a candidate
+    of a geometry without the OPAQUE flag commits only if BaseColor.a (factor times the texture's alpha at the candidate's own UVs) >=
+    AlphaCutoff."""
+
+    def __init__(self, surface):
+        self.s = surface
+        T = surface.tris
+        self.tested = np.arange(len(T.opaque)) if surface.m["alpha_ignores_opaque_flag"] else np.nonzero(~T.opaque)[0]
+
+    def __call__(self, tri, u, v, uncertainty):
+        S, T = self.s, self.s.tris
+        uvs = S.uv_of(tri, u, v)
+        objects = T.object0[tri] if S.m["alpha_geometry0"] else T.object[tri]
+        commit, close = np.ones(len(tri), bool), np.zeros(len(tri), bool)
+        shift = T.uv_extent[tri] * (uncertainty + EPS)[:, None]
+        for ob in np.unique(objects):
+            sel = objects == ob
+            mat, slots = S.objects[ob]
+            uv = [[uvs[sel, k, 0], uvs[sel, k, 1]] for k in range(2)]
+            commit[sel], alpha = S.tex.is_opaque(mat, slots, uv)
+            if "BaseColor" in slots and (np.asarray(mat["BaseColor"]) > 0).any():
+                bound = S.tap_bound(slots["BaseColor"], uvs[sel], shift[sel]) * float(mat["BaseColor"][3])
+                close[sel] = (np.abs(alpha - float(mat["AlphaCutoff"])) <= bound) & ~S.tap_is_constant(slots["BaseColor"], uvs[sel], shift[sel], 3)
+        return commit, close
+
+
+class Surface:
+    """The reference of one scene; the keyword switches (MUTATIONS) each break one rule. tex: the texref.Reference that samples (one with
+    a switch of texref.MUTATIONS set carries that mistake through the frame)."""
+
+    def __init__(self, scene, tex=None, **mutations):
         unknown = set(mutations) - set(MUTATIONS)
         assert not unknown, unknown
         self.m = {k: bool(mutations.get(k, False)) for k in MUTATIONS}
         self.scene = scene
         self.tris = Triangles(scene)
+        self.tex = tex if tex is not None else texref.Reference()
+        self.objects = object_textures(scene)
+        self.textured = any(slots for _, slots in self.objects)
+        self.alpha_rule = AlphaRule(self)
+
+    # ------------------------------------------------------------------ textures
+    def uv_of(self, tri, u, v):
+        """both UV sets of hits: [n, set, 2]"""
+        if self.m["uv_corner0"]:
+            return self.tris.uv[tri][:, :, 0].copy()
+        return self.tris.interpolate_uv(tri, u, v)
+
+    def tap_bound(self, entry, uvs, shift):
+        """|fp32 sample - float64 sample| of one tap (per hit, over channels, before the material's factor). The tap position differs by
+        shift[n, set] in UV units -- the triangle's UV extent times the barycentric uncertainty of the hit -- plus texref's own position
+        error (the fp32 interpolation of the f16 corners and the sampler's address arithmetic), in texels of the larger side; the value
+        moves by that times the largest difference between neighbouring texels around the footprint, plus the sampler's roundings."""
+        data, fmt, index = entry
+        dec = _TRUE.decode(data, fmt)
+        size = max(dec.shape[0], dec.shape[1])
+        diff, mag = _TRUE.footprint2d(dec, uvs[:, index, 0], uvs[:, index, 1])
+        pos = size * shift[:, index] + texref.texel_position_error(size, np.abs(uvs[:, index]).max(-1))
+        return texref.value_tolerance(pos, diff, mag)
+
+    def tap_is_constant(self, entry, uvs, shift, channel):
+        """The tap is decided exactly: the channel samples to the same 0 or 1 at the hit and at the four corners of the box its fp32
+        position can lie in, so every texel any such footprint touches holds that value, and a bilinear blend of equal texels 0 or 1 is
+        exact in fp32 (c (1 - w) + c w; test_texture_reference.py's alpha case rests on the same fact). This is what lets a mask's solid
+        cells stand exactly AT AlphaCutoff = 1 and still be decided."""
+        data, fmt, index = entry
+        dec = _TRUE.decode(data, fmt)
+        size = max(dec.shape[0], dec.shape[1])
+        e = (size * shift[:, index] + texref.texel_position_error(size, np.abs(uvs[:, index]).max(-1))) / min(dec.shape[0], dec.shape[1])
+        u, v = uvs[:, index, 0], uvs[:, index, 1]
+        at = _TRUE.sample2d(dec, u, v)[..., channel]
+        same = np.isin(at, (0.0, 1.0))
+        for su in (-1.0, 1.0):
+            for sv in (-1.0, 1.0):
+                same &= _TRUE.sample2d(dec, u + su * e, v + sv * e)[..., channel] == at
+        return same
 
     # ------------------------------------------------------------------ HitInfo::Initialize, SelfIntersectionAvoidance
     def reconstruct(self, tri, u, v, d):
@@ -268,19 +401,133 @@ class Surface:
         motion = mot[:, 0] + u[:, None] * (mot[:, 1] - mot[:, 0]) + v[:, None] * (mot[:, 2] - mot[:, 0])
         return {"position": pos, "object_position": obj_pos, "offset": offset, "flat": flat, "geometric": geo, "front": front,
                 "shading": shading, "tangent": tangent, "motion": motion, "instance": inst, "geometry": T.geom[tri],
-                "primitive": T.prim[tri], "object": T.object[tri], "perp": np.abs(dot(geo, d))}
+                "primitive": T.prim[tri], "object": T.object[tri], "perp": np.abs(dot(geo, d)), "uv": self.uv_of(tri, u, v), "tri": tri,
+                "front_tangent": tangent if self.m["tangent_no_back_flip"] else np.where(front[:, None], tangent, -tangent)}
 
     def environment(self, scene_data, d):
-        """GetEnvironmentLightColor without a texture: the constant colour, or the procedural sky when its alpha is negative"""
+        """GetEnvironmentLightColor (ShadingHelpers.hlsli:11-30): the texture (lat-long or cube) looked up along the direction turned by
+        EnvironmentLightTransform; else the constant colour, or the procedural sky when its alpha is negative"""
+        descriptor = int(scene_data["EnvironmentLightTextureDescriptor"])
+        if descriptor != 0xFFFFFFFF:
+            sd = np.array(scene_data).reshape(()).copy()
+            M = np.asarray(sd["EnvironmentLightTransform"], f64).reshape(3, 4).copy()
+            if self.m["env_no_transform"]:
+                M[:, :3] = np.eye(3)
+            if self.m["env_transposed"]:
+                M[:, :3] = M[:, :3].T.copy()
+            sd["EnvironmentLightTransform"] = M.reshape(np.shape(sd["EnvironmentLightTransform"]))
+            item = self.scene.heap[descriptor]
+            return self.tex.environment(sd, item.array, item.fmt, d)
         c = np.asarray(scene_data["EnvironmentLightColor"], f64)
         if c[3] >= 0:
             return np.broadcast_to(c[:3], d.shape).copy()
         t = (d[:, 1:2] + 1.0) * 0.5
         return texref.srgb_to_linear(1.0 + t * (np.array([0.5, 0.7, 1.0]) - 1.0))
 
-    def material(self, objects):
+    def environment_bound(self, scene_data, d, angle):
+        """(|fp32 environment - float64 environment| per direction, undecided). Zero without a texture. The direction may be off by `angle`
+        radians. Lat-long: v = acos(w.y) / pi moves by angle / pi, u = atan2 / 2 pi by angle / (2 pi r), r = |w.xz|, and the fp32 acos /
+        atan2 of arguments rounded at 2^-24 add 2^-24 / r each (test_texture_reference's pole term); within POLE of a pole nothing is
+        decided (atan2 of two roundings; the NaN-coordinate rule at |w.y| = 1). Cube: (sc, tc) / ma has slope <= 2 on a face, so the
+        position moves by 2 angle of the face's half-width; the contrast is the texture's whole range (texref.cube_footprint), which also
+        covers a face chosen differently: seamless filtering is continuous across edges."""
+        n = len(d)
+        descriptor = int(scene_data["EnvironmentLightTextureDescriptor"])
+        if descriptor == 0xFFFFFFFF:
+            return np.zeros(n), np.zeros(n, bool)
+        item = self.scene.heap[descriptor]
+        dec = _TRUE.decode(item.array, item.fmt)
+        M = np.asarray(scene_data["EnvironmentLightTransform"], f64).reshape(3, 4)[:, :3]
+        w = normalize(d @ M.T)
+        angle = np.broadcast_to(np.asarray(angle, f64), (n,))
+        if int(scene_data["IsEnvironmentLightTextureCubeMap"]):
+            size = dec.shape[1]
+            diff, mag = _TRUE.cube_footprint(dec, w)
+            return texref.value_tolerance(texref.texel_position_error(size, 1.0) + size * 2.0 * angle, diff, mag), np.zeros(n, bool)
+        size = max(dec.shape[0], dec.shape[1])
+        r = np.hypot(w[:, 0], w[:, 2])
+        uu = (1.0 + np.arctan2(w[:, 0], w[:, 2]) / np.pi) / 2.0
+        vv = np.arccos(np.clip(w[:, 1], -1.0, 1.0)) / np.pi
+        diff, mag = _TRUE.footprint2d(dec, uu, vv)
+        with np.errstate(divide="ignore"):
+            pos = texref.texel_position_error(size, 1.0) + size * (angle / np.pi + (angle / (2.0 * np.pi) + 2.0 * EPS) / np.maximum(r, 1e-30))
+        return texref.value_tolerance(pos, diff, mag), r < POLE
+
+    MATERIAL_KEYS = ("BaseColor", "EmissiveStrength", "EmissiveColor", "Metallic", "Roughness", "IOR", "Transmission")
+
+    def material(self, objects, hit=None, uncertainty=None):
+        """The Material of hits. Without `hit`, or in a scene without material textures: the record as it stands (EvaluateMaterial of an
+        untextured object returns it unchanged). With `hit` (reconstruct's dictionary): EvaluateMaterial (ShadingHelpers.hlsli:161-235) through
+        texref at the hit's UV sets, with its shading normal and FRONT tangent (HitInfo.hlsli:85-88). Adds
+          Normal      the shading normal, perturbed where the object has a Normal texture AND the mesh has tangents (any(T != 0))
+          bound       per quantity (base, emission, metal, rough, trans, normal) what fp32 may differ by: tap_bound at `uncertainty`
+                      (the barycentric uncertainty of each hit; EDGE_B by default) times the material's factor
+          undecided   a decision inside the material lies within its bound: Metallic < 1 ahead of the Transmission tap, or the normal
+                      map's x^2 + y^2 at the rim where sqrt(saturate(1 - x^2 - y^2)) clamps"""
         m = self.scene.object_data["Material"][objects]
-        return {k: np.asarray(m[k], f64) for k in ("BaseColor", "EmissiveStrength", "EmissiveColor", "Metallic", "Roughness", "IOR", "Transmission")}
+        out = {k: np.asarray(m[k], f64) for k in self.MATERIAL_KEYS}
+        if hit is None or not self.textured:
+            return out
+        n = len(objects)
+        out = {k: v.copy() for k, v in out.items()}
+        out["Normal"] = hit["shading"].copy()
+        bound = {k: np.zeros(n) for k in ("base", "emission", "metal", "rough", "trans", "normal")}
+        undecided = np.zeros(n, bool)
+        unc = np.full(n, EDGE_B) if uncertainty is None else np.asarray(uncertainty, f64)
+        shift_all = self.tris.uv_extent[hit["tri"]] * (unc + EPS)[:, None]
+        for ob in np.unique(objects):
+            mat, slots = self.objects[ob]
+            if not slots:
+                continue
+            sel = np.nonzero(objects == ob)[0]
+            slots = dict(slots)
+            if self.m["normal_map_ignored"]:
+                slots.pop("Normal", None)
+            if self.m["emissive_texture_ignored"]:
+                slots.pop("EmissiveColor", None)
+            uvs, shift = hit["uv"][sel], shift_all[sel]
+            uv = [[uvs[:, k, 0], uvs[:, k, 1]] for k in range(2)]
+            Ns = hit["shading"][sel]
+            T = hit["front_tangent"][sel] if self.tris.has_t[hit["tri"][sel]].all() else None
+            if T is None and self.m["normal_map_without_tangents"]:
+                T = B.get_basis(Ns)[0]
+            e = self.tex.evaluate_material(mat, slots, uv, Ns, T)
+            strength = float(mat["EmissiveStrength"])
+            out["BaseColor"][sel] = e["BaseColor"]; out["Metallic"][sel] = e["Metallic"]; out["Roughness"][sel] = e["Roughness"]
+            out["Transmission"][sel] = e["Transmission"]; out["Normal"][sel] = e["Normal"]
+            if strength != 0:
+                out["EmissiveColor"][sel] = e["Emission"] / strength
+            if self.m["transmission_gate_on_factor"] and float(mat["Metallic"]) >= 1:
+                out["Transmission"][sel] = float(mat["Transmission"])
+
+            def tb(slot):
+                return self.tap_bound(slots[slot], uvs, shift)
+            if "BaseColor" in slots and (np.asarray(mat["BaseColor"]) > 0).any():
+                bound["base"][sel] = tb("BaseColor") * float(np.max(mat["BaseColor"][:3]))
+            if "EmissiveColor" in slots and (np.asarray(mat["EmissiveColor"], f64) * strength > 0).any():
+                bound["emission"][sel] = tb("EmissiveColor") * strength * float(np.max(mat["EmissiveColor"]))
+            if "MetallicRoughness" in slots:
+                if mat["Metallic"] > 0 or mat["Roughness"] > 0:
+                    t = tb("MetallicRoughness")
+                    bound["metal"][sel] = t * float(mat["Metallic"]); bound["rough"][sel] = t * float(mat["Roughness"])
+            else:
+                if "Metallic" in slots and mat["Metallic"] > 0:
+                    bound["metal"][sel] = tb("Metallic") * float(mat["Metallic"])
+                if "Roughness" in slots and mat["Roughness"] > 0:
+                    bound["rough"][sel] = tb("Roughness") * float(mat["Roughness"])
+            if "Transmission" in slots and mat["Transmission"] > 0:
+                bound["trans"][sel] = tb("Transmission") * float(mat["Transmission"])
+                undecided[sel] |= (bound["metal"][sel] > 0) & (np.abs(e["Metallic"] - 1.0) <= bound["metal"][sel])
+            if "Normal" in slots and T is not None:
+                t = tb("Normal")
+                xy = _TRUE._tap(slots, "Normal", uv)[..., :2] * 2.0 - 1.0
+                r2 = (xy * xy).sum(-1)
+                nz = np.sqrt(np.clip(1.0 - r2, 0.0, 1.0))
+                # n = (x, y, sqrt(1 - x^2 - y^2)), x = 2 tap - 1: |dn| <= 2 t (sqrt 2 + |xy| / nz) before the normalisation, which only shrinks it
+                bound["normal"][sel] = 2.0 * t * (np.sqrt(2.0) + np.sqrt(r2) / np.maximum(nz, 1e-3))
+                undecided[sel] |= (1.0 - r2) <= 8.0 * t
+        out["bound"], out["undecided"] = bound, undecided
+        return out
 
     # ------------------------------------------------------------------ GBufferGeneration.hlsl main
     def render(self, camera, W, H, scene_data=None, rows=None):
@@ -289,7 +536,7 @@ class Surface:
         sd = np.asarray(scene_data if scene_data is not None else self.scene.scene_data).reshape(())
         uv, pix = pixel_uv(W, H, cam["Jitter"], rows)
         o, d, tmin, tmax = pinhole(cam, uv)
-        c = self.tris.closest(o, d, tmin, tmax)
+        c = self.tris.closest(o, d, tmin, tmax, alpha=self.alpha_rule if len(self.alpha_rule.tested) else None)
         hit = c["hit"]
         h = self.reconstruct(c["tri"], c["u"], c["v"], d)
         r = {"uv": uv, "pixel": pix, "origin": o, "direction": d, "tmin": tmin, "tmax": tmax, "hit": hit, "t": c["t"], "u": c["u"], "v": c["v"],
@@ -340,21 +587,41 @@ class Surface:
         r["motion"] = np.concatenate([(suv - uv) * dims, (pview[:, 2] - lin_all)[:, None]], -1)
         r["motion_error"] = np.concatenate([(MV_ROUNDINGS * EPS * (1.0 + A) + through) * dims,
                                             (4.0 * EPS * (vmag[:, 2] + mag[:, 3]) + pos_err * (np.linalg.norm(pw2v[:3, 2]) + col[3]))[:, None]], -1)
-        # material words (untextured: EvaluateMaterial returns the material as it stands)
-        mat = self.material(h["object"])
+        # material words: EvaluateMaterial at the hit (an untextured object's material as it stands)
+        mat = self.material(h["object"], h, c["bary"])
         base, metal = mat["BaseColor"][:, :3], mat["Metallic"]
         r["base_color_metalness"] = np.concatenate([base, metal[:, None]], -1)
         r["roughness"] = np.maximum(B.MIN_ROUGHNESS, mat["Roughness"])
         r["ior"], r["transmission"] = mat["IOR"], mat["Transmission"]
         emission = mat["EmissiveStrength"][:, None] * mat["EmissiveColor"]
         r["radiance"] = np.where(hit[:, None], emission, self.environment(sd, d))
+        env_bound, env_undecided = self.environment_bound(sd, d, 8.0 * EPS)
+        r["unsafe"] = r["unsafe"] | (~hit & env_undecided)
+        r["radiance_error"] = np.where(hit, 0.0, env_bound)
+        if "bound" in mat:                                                            # a textured scene: the perturbed normal and every tap's bound
+            bd = mat["bound"]
+            r["shading"] = mat["Normal"]
+            r["unsafe"] = r["unsafe"] | (hit & mat["undecided"])
+            r["radiance_error"] = np.where(hit, bd["emission"], env_bound)
+            r["base_color_metalness_error"] = np.stack([bd["base"]] * 3 + [bd["metal"]], -1)
+            r["roughness_error"], r["transmission_error"], r["shading_error"] = bd["rough"], bd["trans"], bd["normal"]
         # EstimateDemodulationFactors (NRD's material factors): Fenv from EnvironmentTerm_Rtg; (1 - Fenv) albedo 0.99 + 0.01, Fenv 0.99 + 0.01
         ior_i = np.where(h["front"], 1.0, mat["IOR"]); ior_o = np.where(h["front"], mat["IOR"], 1.0)
         r2 = ((ior_i - ior_o) / (ior_i + ior_o)) ** 2
-        F0 = r2[:, None] + (base - r2[:, None]) * metal[:, None]
-        Fenv = B.env_term_rtg(F0, np.abs(dot(h["shading"], -d)), r["roughness"])
-        r["diffuse_albedo"] = (1.0 - Fenv) * (base * (1.0 - metal[:, None])) * 0.99 + 0.01
-        r["specular_albedo"] = Fenv * 0.99 + 0.01
+
+        def albedos(base, metal, rough, nov):
+            F0 = r2[:, None] + (base - r2[:, None]) * metal[:, None]
+            Fenv = B.env_term_rtg(F0, nov, rough)
+            return (1.0 - Fenv) * (base * (1.0 - metal[:, None])) * 0.99 + 0.01, Fenv * 0.99 + 0.01
+        nov = np.abs(dot(r["shading"], -d))
+        r["diffuse_albedo"], r["specular_albedo"] = albedos(base, metal, r["roughness"], nov)
+        if "bound" in mat:                                                            # one more evaluation per textured quantity, moved by its bound
+            bd = mat["bound"]
+            moved = (albedos(base + bd["base"][:, None], metal, r["roughness"], nov), albedos(base, np.clip(metal + bd["metal"], 0, 1), r["roughness"], nov),
+                     albedos(base, metal, r["roughness"] + bd["rough"], nov), albedos(base, metal, r["roughness"], np.clip(nov + bd["normal"], 0, 1)))
+            with np.errstate(invalid="ignore"):
+                r["diffuse_albedo_error"] = sum(np.abs(mv[0] - r["diffuse_albedo"]) for mv in moved)
+                r["specular_albedo_error"] = sum(np.abs(mv[1] - r["specular_albedo"]) for mv in moved)
         return r
 
 
@@ -397,8 +664,10 @@ def compare(gb, ref, surface, flags=0xFFFFFFFF):
         e = flat[name].astype(f64) * SNORM16
         fail(name, ~(np.abs(e - oct_encode(ref[key])) <= SNORM16).all(1), k_hit)
     nr = flat["NormalRoughness"].astype(f64) * SNORM16
-    fail("NormalRoughness.xyz", ~(np.abs(nr[:, :3] - ref["shading"]) <= SNORM16).all(1), k_hit)
-    fail("NormalRoughness.w", ~(np.abs(nr[:, 3] - ref["roughness"]) <= SNORM16), k_hit)
+    zero = np.zeros(n)
+    extra = lambda key, shape=None: ref.get(key, zero if shape is None else np.zeros((n, shape)))   # the texture bounds of a textured scene
+    fail("NormalRoughness.xyz", ~(np.abs(nr[:, :3] - ref["shading"]) <= SNORM16 + extra("shading_error")[:, None]).all(1), k_hit)
+    fail("NormalRoughness.w", ~(np.abs(nr[:, 3] - ref["roughness"]) <= SNORM16 + extra("roughness_error")), k_hit)
     ld, ndp = flat["LinearDepth"][:, 0].astype(f64), flat["NormalizedDepth"][:, 0].astype(f64)
     with np.errstate(invalid="ignore"):
         fail("LinearDepth", ~(np.abs(ld - ref["linear_depth"]) <= ref["linear_depth_error"]), k_hit)
@@ -408,14 +677,15 @@ def compare(gb, ref, surface, flags=0xFFFFFFFF):
     fail("MotionVector", ~f16_close(mv[:, :3], ref["motion"], ref["motion_error"]).all(1), k_hit | k_miss)
     fail("MotionVector.w", mv[:, 3] != 0, k_hit | k_miss)
     bcm = flat["BaseColorMetalness"].astype(f64) * UNORM8
-    fail("BaseColorMetalness", ~(np.abs(bcm - np.clip(ref["base_color_metalness"], 0, 1)) <= UNORM8).all(1), k_hit)
+    fail("BaseColorMetalness", ~(np.abs(bcm - np.clip(ref["base_color_metalness"], 0, 1)) <= UNORM8 + extra("base_color_metalness_error", 4)).all(1), k_hit)
     fail("IOR", ~f16_close(flat["IOR"][:, 0], ref["ior"]), k_hit)
-    fail("Transmission", ~(np.abs(flat["Transmission"][:, 0].astype(f64) * UNORM8 - ref["transmission"]) <= UNORM8), k_hit & (ref["base_color_metalness"][:, 3] < 1))
-    fail("Radiance", ~f16_close(flat["Radiance"][:, :3], ref["radiance"]).all(1), k_hit | k_miss)
+    fail("Transmission", ~(np.abs(flat["Transmission"][:, 0].astype(f64) * UNORM8 - ref["transmission"]) <= UNORM8 + extra("transmission_error")),
+         k_hit & (ref["base_color_metalness"][:, 3] < 1))
+    fail("Radiance", ~f16_close(flat["Radiance"][:, :3], ref["radiance"], extra("radiance_error")[:, None]).all(1), k_hit | k_miss)
     fail("Radiance.w", flat["Radiance"][:, 3] != 0, k_hit | k_miss)
     if flags & 0xC0 == 0xC0:
         for name, key in (("DiffuseAlbedo", "diffuse_albedo"), ("SpecularAlbedo", "specular_albedo")):
-            fail(name, ~f16_close(flat[name][:, :3], ref[key], B.REL * ref[key]).all(1), k_hit)
+            fail(name, ~f16_close(flat[name][:, :3], ref[key], B.REL * ref[key] + extra(key + "_error", 3)).all(1), k_hit)
     return fails, fig
 
 

@@ -163,7 +163,7 @@ MUTATION_ROW = {
 }
 
 
-assert set(MUTATION_ROW) == set(P.MUTATIONS) - set(P.DI_MUTATIONS)
+assert set(MUTATION_ROW) == set(P.MUTATIONS) - set(P.DI_MUTATIONS) - set(P.TEXTURE_MUTATIONS)      # those: tests/test_textured_estimator.py
 
 
 @pytest.mark.parametrize("mutation,row", list(MUTATION_ROW.items()), ids=[f"{m}-{r}" for m, r in MUTATION_ROW.items()])

@@ -92,7 +92,10 @@ MUTATION_SCENE = {"normal_by_matrix": "transformed", "no_front_flip": "transform
                   "mv_no_vertex_term": "moved", "v_not_flipped": "moved"}
 
 
-@pytest.mark.parametrize("mutation", R.MUTATIONS)
+assert set(MUTATION_SCENE) == set(R.MUTATIONS) - set(R.TEXTURE_MUTATIONS)                              # those: tests/test_textured_estimator.py
+
+
+@pytest.mark.parametrize("mutation", list(MUTATION_SCENE))
 def test_mutated_surface_is_caught(mutation, oracle, pkg):
     name = MUTATION_SCENE[mutation]
     scene, surface, ref = reference(pkg, name)
