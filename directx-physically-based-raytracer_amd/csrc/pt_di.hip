@@ -6,6 +6,8 @@
 //                                     vertices, CalculatePower; run at every render (moving instances, refits)
 //   k_cdf_*                        <- the local-light pdf texture of the reference's Power_RIS mode, as a fixed-order prefix sum
 //   k_di_presample_tiles           <- LocalLightPresampling.hlsl: the Power_RIS light tiles (POWER_RIS, REGIR_RIS)
+//   k_pdf_level0 / k_pdf_denominator / k_di_presample_tiles_mip <- the LocalLightPDF texture of App::PrepareReSTIRDI (pt_di_set_pdf_mipmap): level 0 on
+//                                     the Z-curve, its chain by pt_mip.hip, and the tiles by a descent of the chain instead of the prefix sum
 //   k_di_regir_build               <- ReGIRPresampling.hlsl, Grid mode: the ReGIR cells (REGIR_RIS)
 //   k_di_regir_build_onion         <- the same over the Onion layout's cells (pt_di_set_regir_layout; the reference's compiled mode)
 //   k_di<Source>                   <- DIInitialSampling (local lights only, streaming RIS) + DIFinalShading, no temporal /
@@ -317,6 +319,65 @@ __global__ __launch_bounds__(256) void k_di_presample_tiles(const float4* __rest
     tiles[g] = e;
 }
 
+// ---- the local-light PDF texture (pt_di_set_pdf_mipmap; DESIGN.md section 1, "Local-light PDF texture") ------------------------------
+// the inverse of RTXDI_LinearIndexToZCurve: x gives the even bits of the index, y the odd ones
+PT_DEV uint32_t di_z_spread(uint32_t v)
+{
+    v &= 0x0000FFFFu; v = (v | (v << 8)) & 0x00FF00FFu; v = (v | (v << 4)) & 0x0F0F0F0Fu; v = (v | (v << 2)) & 0x33333333u; v = (v | (v << 1)) & 0x55555555u;
+    return v;
+}
+PT_DEV uint32_t di_z_index(uint32_t x, uint32_t y) { return di_z_spread(x) | (di_z_spread(y) << 1); }
+
+// Level 0, one thread per texel: Power of the light whose Z-curve position the texel is, 0 where there is none (the reference clears the
+// texture and LightPreparation.hlsl:133 scatters; a gather needs no clear)
+__global__ __launch_bounds__(256) void k_pdf_level0(const float* __restrict__ power, uint32_t count, uint32_t width, uint32_t texels, float* __restrict__ level0)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= texels) return;
+    const uint32_t li = di_z_index(i & (width - 1u), i / width);           // the width is a power of two
+    level0[i] = li < count ? power[li] : 0.0f;
+}
+// one thread: what the source pdf of a light divides its Power by, top * M * M (RAB_EvaluateLocalLightSourcePdf); M is a power of two
+__global__ void k_pdf_denominator(const float* __restrict__ top, float M, float* __restrict__ out) { *out = (*top * M) * M; }
+
+// Power_RIS presampling by a descent of the chain (RTXDI_PresampleLocalLights over RTXDI_SamplePdfMipmap): the entry's stream is the one of
+// k_di_presample_tiles, one draw per level. pdf: the levels back to back, level 0 first, `texels` floats in all.
+__global__ __launch_bounds__(256) void k_di_presample_tiles_mip(const float* __restrict__ pdf, uint32_t width, uint32_t height, uint32_t mips, uint32_t texels,
+                                                                uint32_t count, uint32_t frameIndex, uint2* __restrict__ tiles)
+{
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= kDITileEntries) return;
+    uint32_t rng = ml_hash(rng_init(g & 0xFFFu, g >> 12, frameIndex) ^ kDIPresampleSalt);
+    uint32_t px = 0, py = 0;
+    float p = 1.0f;
+    bool empty = false;
+    uint32_t at = mips >= 2u ? texels - 1u : texels;                       // where the level above the first one read starts
+    for (int level = mips >= 2u ? (int)mips - 2 : 0; level >= 0; level--) {
+        const uint32_t lw = max(1u, width >> level), lh = max(1u, height >> level);
+        at -= lw * lh;
+        px *= 2u; py *= 2u;
+        const float* L = pdf + at;
+        auto texel = [&](uint32_t x, uint32_t y) { const float t = x < lw && y < lh ? L[(size_t)y * lw + x] : 0.0f; return t > 0.0f ? t : 0.0f; };   // max(0, NaN) = 0
+        const float s0 = texel(px, py), s1 = texel(px, py + 1u), s2 = texel(px + 1u, py), s3 = texel(px + 1u, py + 1u);
+        const float sum = ((s0 + s1) + s2) + s3;
+        if (!(sum > 0.0f && isfinite(sum))) { empty = true; break; }
+        const float p0 = s0 / sum, p1 = s1 / sum, p2 = s2 / sum, p3 = s3 / sum;
+        float r = rng_float(rng);
+        if (r < p0) p *= p0;
+        else {
+            r -= p0;
+            if (r < p1) { py += 1u; p *= p1; }
+            else {
+                r -= p1;
+                if (r < p2) { px += 1u; p *= p2; }
+                else { px += 1u; py += 1u; p *= p3; }
+            }
+        }
+    }
+    const uint32_t li = di_z_index(px, py);
+    tiles[g] = !empty && p > 0.0f && li < count ? make_uint2(li, __float_as_uint(1.0f / p)) : make_uint2(~0u, 0u);
+}
+
 // TriangleLight::CalculateWeightForVolume with CalculateAverageDistanceToVolume (Light.hlsli:16-24, 84-95)
 PT_DEV float di_volume_weight(const float4* L, v3 c, float radius)
 {
@@ -514,7 +575,8 @@ struct DISampling {
         return li < a.count;
     }
     PT_DEV float pdf(float pv, float, float) const { return pv; }
-    // RAB_EvaluateLocalLightSourcePdf of a light that came out of no tile or cell: Uniform 1 / count, else power / total
+    // RAB_EvaluateLocalLightSourcePdf of a light that came out of no tile or cell: Uniform 1 / count, else power / total (with the PDF texture
+    // acting, a.total holds top * M * M in place of the prefix sum's total)
     PT_DEV float light_pdf(const DIArgs& a, float power, float total) const { return mode == PT_DI_LOCAL_LIGHT_UNIFORM ? 1.0f / (float)a.count : power / total; }
 };
 
@@ -1212,7 +1274,31 @@ static int di_check_args(Context& c, const PtTextures* tx, const PtDIPreviousTex
     return PT_OK;
 }
 
-// the n light records and the prefix sum of their powers (nb scan blocks); the total lands in lightBlockSums[nb]
+// (width, height, mips) of the PDF texture of n lights: ComputePdfTextureSize (Source/RTXDIResources.ixx:43-52) in integers
+static void di_pdf_size(uint32_t n, uint32_t size[3])
+{
+    n = std::max(n, 1u);
+    uint32_t w = 1, h = 1, mips = 1;
+    while ((uint64_t)w * w < n) w <<= 1;                                   // the smallest power of two >= ceil(sqrt(n))
+    while ((uint64_t)h * w < n) h <<= 1;                                   // ... >= ceil(n / width)
+    for (uint32_t e = std::max(w, h); e > 1u; e >>= 1) mips++;
+    size[0] = w; size[1] = h; size[2] = mips;
+}
+static uint32_t di_pdf_level_texels(const uint32_t size[3], uint32_t k) { return std::max(1u, size[0] >> k) * std::max(1u, size[1] >> k); }
+static uint32_t di_pdf_texels(const uint32_t size[3])
+{
+    uint32_t t = 0;
+    for (uint32_t k = 0; k < size[2]; k++) t += di_pdf_level_texels(size, k);
+    return t;
+}
+// whether the descent of the PDF texture replaces the prefix sum in this render's candidates (and a.total becomes top * M * M)
+static bool di_pdf_acts(const Context& c)
+{
+    return c.diPdfMipmap && (c.diSampling.Mode == PT_DI_LOCAL_LIGHT_POWER_RIS || c.diSampling.Mode == PT_DI_LOCAL_LIGHT_REGIR_RIS);
+}
+
+// the n light records and the prefix sum of their powers (nb scan blocks); the total lands in lightBlockSums[nb]. With pt_di_set_pdf_mipmap on,
+// the PDF texture and its chain too; where it acts nothing of the render reads the prefix sum, and its three launches are skipped.
 static int di_light_records(Context& c, const SceneView& sv, uint32_t n, uint32_t nb)
 {
     if (n > c.lightRecords.capacity()) {
@@ -1224,9 +1310,30 @@ static int di_light_records(Context& c, const SceneView& sv, uint32_t n, uint32_
     }
     float* power = c.lightCdf.data() + c.lightRecords.capacity();
     k_light_records<<<(n + 255u) / 256u, 256, 0, c.stream>>>(c.lightList.data(), n, c.scene.instSource, sv.objects, sv.heap, sv.shadeTex, sv.srgbLut, (float4*)c.lightRecords.data(), power);
-    k_cdf_local<<<nb, 256, 0, c.stream>>>(power, n, c.lightCdf.data(), c.lightBlockSums.data());
-    k_cdf_blocks<<<1, 1, 0, c.stream>>>(c.lightBlockSums.data(), nb);
-    k_cdf_add<<<(n + 255u) / 256u, 256, 0, c.stream>>>(c.lightCdf.data(), n, c.lightBlockSums.data(), nb);
+    if (!di_pdf_acts(c)) {
+        k_cdf_local<<<nb, 256, 0, c.stream>>>(power, n, c.lightCdf.data(), c.lightBlockSums.data());
+        k_cdf_blocks<<<1, 1, 0, c.stream>>>(c.lightBlockSums.data(), nb);
+        k_cdf_add<<<(n + 255u) / 256u, 256, 0, c.stream>>>(c.lightCdf.data(), n, c.lightBlockSums.data(), nb);
+    }
+    if (!c.diPdfMipmap) return PT_OK;
+    API_ARG(&c, n <= (1u << 24), "the PDF texture holds at most 2^24 lights");
+    uint32_t size[3];
+    di_pdf_size(n, size);
+    const uint32_t texels = di_pdf_texels(size);
+    if ((size_t)texels + 1u > c.diPdfTexture.capacity()) {
+        API_HIP(&c, hipStreamSynchronize(c.stream));
+        API_HIP(&c, c.diPdfTexture.reserve((size_t)texels + 1u));
+    }
+    float* levels[16];
+    uint32_t at = 0;
+    for (uint32_t k = 0; k < size[2]; k++) { levels[k] = c.diPdfTexture.data() + at; at += di_pdf_level_texels(size, k); }
+    k_pdf_level0<<<(size[0] * size[1] + 255u) / 256u, 256, 0, c.stream>>>(power, n, size[0], size[0] * size[1], levels[0]);
+    API_HIP(&c, hipGetLastError());
+    const int st = mip_generate(c, levels, size[0], size[1], size[2]);
+    if (st != PT_OK) return st;
+    k_pdf_denominator<<<1, 1, 0, c.stream>>>(levels[size[2] - 1u], (float)std::max(size[0], size[1]), c.diPdfTexture.data() + texels);
+    API_HIP(&c, hipGetLastError());
+    memcpy(c.diPdfSize, size, sizeof size);
     return PT_OK;
 }
 
@@ -1314,8 +1421,12 @@ static int di_presample(Context& c, uint32_t n, uint32_t nb, DISampling& ls)
             c.diOnion = std::move(dev);
         }
     }
-    k_di_presample_tiles<<<kDITileEntries / 256u, 256, 0, c.stream>>>((const float4*)c.lightRecords.data(), c.lightCdf.data(), c.lightBlockSums.data() + nb, n,
-                                                                     c.diSettings.FrameIndex, (uint2*)c.diTiles.data());
+    if (di_pdf_acts(c))
+        k_di_presample_tiles_mip<<<kDITileEntries / 256u, 256, 0, c.stream>>>(c.diPdfTexture.data(), c.diPdfSize[0], c.diPdfSize[1], c.diPdfSize[2], di_pdf_texels(c.diPdfSize),
+                                                                             n, c.diSettings.FrameIndex, (uint2*)c.diTiles.data());
+    else
+        k_di_presample_tiles<<<kDITileEntries / 256u, 256, 0, c.stream>>>((const float4*)c.lightRecords.data(), c.lightCdf.data(), c.lightBlockSums.data() + nb, n,
+                                                                         c.diSettings.FrameIndex, (uint2*)c.diTiles.data());
     API_HIP(&c, hipGetLastError());
     c.diTileCount = kDITileEntries;
     ls.tiles = (const uint2*)c.diTiles.data();
@@ -1464,7 +1575,7 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
     API_HIP(&c, ensure_light_list(c, sv));
     const uint32_t n = c.lightCount;
     c.lightRecordCount = n;
-    c.diTileCount = 0; c.diCellCount = 0; c.diBrdfCount = 0;
+    c.diTileCount = 0; c.diCellCount = 0; c.diBrdfCount = 0; memset(c.diPdfSize, 0, sizeof c.diPdfSize);
     if (!reuse || n == 0 || npix == 0) { c.diHistoryValid = false; c.diResCount = 0; }
     if (n == 0 || npix == 0) return PT_OK;
     const uint32_t nb = (n + kScanBlock - 1u) / kScanBlock;
@@ -1477,6 +1588,7 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
                      c.camera.ProjectionToView, c.camera.ViewToWorld, c.camera.Position);
     memcpy(a.jitter, c.camera.Jitter, sizeof a.jitter);
     a.lights = (const float4*)c.lightRecords.data(); a.cdf = c.lightCdf.data(); a.total = c.lightBlockSums.data() + nb; a.count = n;
+    if (di_pdf_acts(c)) a.total = c.diPdfTexture.data() + di_pdf_texels(c.diPdfSize);       // top * M * M: the gate of the pass and the denominator of light_pdf
     a.frameIndex = s.FrameIndex; a.samples = s.LocalLightSamples; a.denoiser = s.Denoiser; a.lastPass = s.IsLastRenderPass; a.ext = s.ExtFlags;
     const AlphaContext ac = alpha_context(sv);
     const dim3 grid((fv.width + 15u) / 16u, (fv.localRows + 15u) / 16u);
@@ -1610,6 +1722,43 @@ int pt_di_set_brdf_sampling(PtContext* ctx, uint32_t brdf_samples, float brdf_cu
     if (brdf_samples) { v.BrdfSamples = brdf_samples; v.BrdfCutoff = brdf_cutoff + 0.0f; }      // 0 samples: off whatever the cutoff; -0 is 0
     if (v.BrdfSamples != c.diBrdf.BrdfSamples || v.BrdfCutoff != c.diBrdf.BrdfCutoff) c.diHistoryValid = false;
     c.diBrdf = v;
+    return PT_OK;
+}
+
+int pt_di_pdf_texture_size(uint32_t light_count, uint32_t* width, uint32_t* height, uint32_t* mip_levels)
+{
+    if (!width || !height || !mip_levels || light_count > (1u << 24)) return PT_ERROR_INVALID_ARGUMENT;
+    uint32_t size[3];
+    di_pdf_size(light_count, size);
+    *width = size[0]; *height = size[1]; *mip_levels = size[2];
+    return PT_OK;
+}
+
+int pt_di_set_pdf_mipmap(PtContext* ctx, uint32_t enabled)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    API_ARG(&c, enabled <= 1u, "enabled must be 0 or 1");
+    if (enabled != c.diPdfMipmap) c.diHistoryValid = false;
+    c.diPdfMipmap = enabled;
+    return PT_OK;
+}
+
+int pt_di_download_pdf_texture(PtContext* ctx, uint32_t level, float* host_dst, uint32_t capacity, uint32_t* out_width, uint32_t* out_height)
+{
+    if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
+    Context& c = ctx->c;
+    API_ARG(&c, out_width && out_height && (host_dst || capacity == 0), "out_width / out_height / host_dst is NULL");
+    API_ARG(&c, level < 16u, "level must be below 16");
+    API_HIP(&c, hipSetDevice(c.device));
+    API_HIP(&c, hipStreamSynchronize(c.stream));
+    *out_width = 0; *out_height = 0;
+    if (level >= c.diPdfSize[2]) return PT_OK;                               // no texture, or no such level of it
+    uint32_t at = 0;
+    for (uint32_t k = 0; k < level; k++) at += di_pdf_level_texels(c.diPdfSize, k);
+    *out_width = std::max(1u, c.diPdfSize[0] >> level); *out_height = std::max(1u, c.diPdfSize[1] >> level);
+    const size_t n = std::min((size_t)capacity, (size_t)*out_width * *out_height);
+    if (n) API_HIP(&c, hipMemcpy(host_dst, c.diPdfTexture.data() + at, sizeof(float) * n, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

@@ -260,6 +260,11 @@ struct Context {
     struct DIBrdfSettings { uint32_t BrdfSamples = 0; float BrdfCutoff = 0.0f; } diBrdf;
     DeviceBuffer<uint32_t> lightFirst;
     DeviceBuffer<uint4> diBrdfRecords;                // (li | ~0u, U, V, pdf of the ray)
+    // the local-light PDF texture (pt_di_set_pdf_mipmap): every level of the chain in one grow-only allocation, level 0 first, and behind the
+    // last level one float, top * M * M (what a.total points at while the setting acts). diPdfSize: the last render's (width, height, mips); 0: none
+    uint32_t diPdfMipmap = 0;
+    DeviceBuffer<float> diPdfTexture;
+    uint32_t diPdfSize[3] = {0, 0, 0};
 
     // animation (pt_anim.hip): rigs, animated objects, and the staging of pt_anim_evaluate's states (a pinned ring guarded by events, like
     // tlasStage; the device array is grow-only)
@@ -295,6 +300,8 @@ int fail_hip(Context* c, hipError_t e, const char* what);
 int make_views(Context& c, uint32_t width, uint32_t height, SceneView& sv, FrameView& fv, bool needFrameInputs = true);
 // what pt_raytrace_render and pt_raytrace_render_sharc check alike, behind their own checks: settings ranges and texture bindings
 int check_raytrace_args(Context& c, const PtTextures* tx);
+// pt_mipmap_generate behind its context checks (pt_mip.hip): levels is a host array of device pointers; the DI pass builds its PDF texture's chain with it
+int mip_generate(Context& c, float* const* levels, uint32_t width, uint32_t height, uint32_t mips);
 // false for a rank of the sharding that holds no row of a width x height frame (or for an empty frame): no texture binding is asked of it
 bool rank_holds_pixels(const Context& c, uint32_t width, uint32_t height);
 

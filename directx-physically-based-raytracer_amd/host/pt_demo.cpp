@@ -3,7 +3,7 @@
 // optionally dumps the radiance for the parity test (tests/test_host_cpp.py compares it with the oracle).
 //
 //   pt_demo [--width W] [--height H] [--spp S] [--bounces B] [--frames N] [--out file.bin] [--ranks R] [--di] [--di-samples N] [--di-brdf-samples N [--di-brdf-cutoff C]] [--restir [--restir-pairwise] [--restir-visibility [--restir-raytraced]]] [--sharc]
-//           [--light-sampling cdf|uniform|power_ris|regir [--regir-layout grid|onion]]
+//           [--light-sampling cdf|uniform|power_ris|regir [--regir-layout grid|onion]] [--di-pdf-mipmap]
 //           [--post] [--no-bloom] [--bloom-strength S] [--tone-map saturate|reinhard|aces] [--exposure E]
 //           [--hdr [--paper-white N] [--color-rotation hdtv_to_uhdtv|dci_p3_d65_to_uhdtv|hdtv_to_dci_p3_d65]]
 //           [--nrd relax|reblur] [--out-radiance file.bin]
@@ -26,6 +26,8 @@
 // --light-sampling (with --di): how the DI pass draws its candidates (ReSTIRDI.InitialSampling.LocalLight.Mode; default cdf, the power
 // prefix sum); ReGIR at MyAppData's cell size 1 and 8 build samples. --regir-layout (with --light-sampling regir): the layout of the
 // ReGIR cells, the Grid (default) or the Onion the reference compiles.
+// --di-pdf-mipmap (with --di): the DI pass builds the local-light PDF texture and its mip chain every frame (App::PrepareReSTIRDI), and
+// power_ris / regir descend the chain for their light tiles instead of the power prefix sum; the JSON line then carries "di_pdf_mipmap": true.
 //
 // --post: the post-processing chain after every frame (App::PostProcessGraphics, App.cpp:1506-1571: Bloom + Merge, ToneMap, CopyTexture)
 // at MyAppData's defaults (bloom 0.05, ACES filmic, exposure 0, SDR) unless the flags above change them; --png writes the last frame's
@@ -400,7 +402,7 @@ static std::vector<uint8_t> exchange_unique_id(uint32_t rank, const std::string&
 int main(int argc, char** argv)
 {
     uint32_t W = 1920, H = 1080, spp = 4, bounces = 8, frames = 10, ranks = 0, rank = 0, world = 1;
-    uint32_t diSamples = 8, diBrdfSamples = 0; float diBrdfCutoff = 0.0f; bool di = false, restir = false, restirVisibility = false, restirRaytraced = false, restirPairwise = false;
+    uint32_t diSamples = 8, diBrdfSamples = 0; float diBrdfCutoff = 0.0f; bool di = false, diPdfMipmap = false, restir = false, restirVisibility = false, restirRaytraced = false, restirPairwise = false;
     bool useSharc = false; uint32_t sharcDownscale = 4; float sceneScale = 50.0f;   // --sharc [--sharc-downscale N --scene-scale S]: frames through the radiance cache
     std::string out, idFile, scenePath, dumpPath, lightSampling = "cdf", regirLayout = "grid";
     bool post = false, bloom = true, hdr = false; float bloomStrength = 0.05f, exposure = 0.0f, paperWhite = 200.0f;
@@ -410,6 +412,7 @@ int main(int argc, char** argv)
     for (int i = 1; i < argc; i++) {
         std::string k = argv[i];
         if (k == "--di") { di = true; continue; }                  // the flags without a value
+        if (k == "--di-pdf-mipmap") { diPdfMipmap = true; continue; }
         if (k == "--restir") { restir = true; continue; }
         if (k == "--restir-visibility") { restirVisibility = true; continue; }
         if (k == "--restir-raytraced") { restirRaytraced = true; continue; }
@@ -619,6 +622,10 @@ int main(int argc, char** argv)
             if (regirLayout != "grid" && lightSampling != "regir") throw std::invalid_argument("--regir-layout needs --light-sampling regir");
             directLighting.SetLightSampling(l);
         } else if (regirLayout != "grid") throw std::invalid_argument("--regir-layout needs --light-sampling regir");
+        if (diPdfMipmap) {                                                        // the LocalLightPDF texture and its chain (App::PrepareReSTIRDI)
+            if (!di) throw std::invalid_argument("--di-pdf-mipmap needs --di");
+            directLighting.SetPdfMipmap(true);
+        }
         if (diBrdfSamples || diBrdfCutoff != 0.0f) {                              // BRDF candidates in initial sampling (MyAppData BRDFSamples)
             if (!di) throw std::invalid_argument("--di-brdf-samples needs --di");
             if (!diBrdfSamples) throw std::invalid_argument("--di-brdf-cutoff needs --di-brdf-samples");
@@ -734,15 +741,16 @@ int main(int argc, char** argv)
             ThrowIfFailed(commandList.Context, pt_di_light_count(commandList.Context, &lights));
             fprintf(stderr, "pt_demo: direct lighting over %u emissive triangles, %u candidates per pixel\n", lights, diSamples);
         }
+        const char* pdfField = diPdfMipmap ? ", \"di_pdf_mipmap\": true" : "";
         if (useSharc)        // rays count the update pass's too
-            printf("{\"host\": \"c++\", \"sharc\": true, \"width\": %u, \"height\": %u, \"spp\": %u, \"bounces\": %u, \"frames\": %u, \"sharc_entries\": %u, \"secondary_rays\": %.0f, \"rays\": %.0f, \"ms_per_frame\": %.4f}\n",
-                   W, H, spp, bounces, frames, sharc.LiveEntries(), (double)counters.SecondaryRays, rays, ms / frames);
+            printf("{\"host\": \"c++\", \"sharc\": true, \"width\": %u, \"height\": %u, \"spp\": %u, \"bounces\": %u, \"frames\": %u, \"sharc_entries\": %u, \"secondary_rays\": %.0f, \"rays\": %.0f, \"ms_per_frame\": %.4f%s}\n",
+                   W, H, spp, bounces, frames, sharc.LiveEntries(), (double)counters.SecondaryRays, rays, ms / frames, pdfField);
         else if (!sharded)
-            printf("{\"host\": \"c++\", \"width\": %u, \"height\": %u, \"spp\": %u, \"bounces\": %u, \"frames\": %u, \"rays\": %.0f, \"ms_per_frame\": %.4f, \"mrays_per_s\": %.1f}\n",
-                   W, H, spp, bounces, frames, rays, ms / frames, rays / ms / 1e3);
+            printf("{\"host\": \"c++\", \"width\": %u, \"height\": %u, \"spp\": %u, \"bounces\": %u, \"frames\": %u, \"rays\": %.0f, \"ms_per_frame\": %.4f, \"mrays_per_s\": %.1f%s}\n",
+                   W, H, spp, bounces, frames, rays, ms / frames, rays / ms / 1e3, pdfField);
         else       // rays are this rank's; rank 0's time includes every peer's bands arriving
-            printf("{\"host\": \"c++\", \"rank\": %u, \"world\": %u, \"local_rows\": %u, \"width\": %u, \"height\": %u, \"spp\": %u, \"bounces\": %u, \"frames\": %u, \"rays_this_rank\": %.0f, \"ms_per_frame\": %.4f}\n",
-                   rank, world, localRows, W, H, spp, bounces, frames, rays, ms / frames);
+            printf("{\"host\": \"c++\", \"rank\": %u, \"world\": %u, \"local_rows\": %u, \"width\": %u, \"height\": %u, \"spp\": %u, \"bounces\": %u, \"frames\": %u, \"rays_this_rank\": %.0f, \"ms_per_frame\": %.4f%s}\n",
+                   rank, world, localRows, W, H, spp, bounces, frames, rays, ms / frames, pdfField);
         if (sharded && fullRadianceF32) {                          // parity dump of a sharded run: the fp32 copy, assembled the same way
             sharding.GatherBands(commandList, radianceF32, fullRadianceF32, W, H, 16);
             commandList.End();

@@ -380,6 +380,10 @@ struct DirectLighting {
         ThrowIfFailed(m_context, pt_di_set_brdf_sampling(m_context, b.Samples, b.Cutoff));
     }
 
+    // The LocalLightPDF texture of App::PrepareReSTIRDI (pt_di_set_pdf_mipmap): with it on every Render builds the texture and its mip
+    // chain, and the Power_RIS / ReGIR modes descend the chain for their light tiles. Off, this library's default: the power prefix sum.
+    void SetPdfMipmap(bool enabled) { ThrowIfFailed(m_context, pt_di_set_pdf_mipmap(m_context, enabled ? 1u : 0u)); }
+
     void SetConstants(const Settings& settings)
     {
         PtDISettings s{};
@@ -607,6 +611,28 @@ struct NRDComposition {
         for (int i = 0; i < 4; i++) k.ReBLURHitDistance[i] = constants.ReBLURHitDistance[i];
         ThrowIfFailed(commandList.Context, pt_nrd_composition_process(commandList.Context, &k, &Textures));
     }
+};
+
+// struct MipmapGeneration (Source/MipmapGeneration.ixx: SetTexture + Process) for an R32_FLOAT texture: Process reads level 0 and writes the
+// other levels of the chain (pt_mipmap_generate). App::PrepareReSTIRDI (Source/App.cpp:1095-1116) runs it on the LocalLightPDF texture; the DI
+// pass here does that itself (DirectLighting::SetPdfMipmap), so a host needs this operator only for a texture of its own.
+struct MipmapGeneration {
+    explicit MipmapGeneration(CommandList&) {}
+
+    // levels[k]: the device memory of level k, row-major, max(1, width >> k) x max(1, height >> k) floats
+    void SetTexture(std::vector<float*> levels, uint32_t width, uint32_t height)
+    {
+        m_levels = std::move(levels); m_width = width; m_height = height;
+    }
+
+    void Process(CommandList& commandList)
+    {
+        ThrowIfFailed(commandList.Context, pt_mipmap_generate(commandList.Context, m_levels.empty() ? nullptr : m_levels.data(), m_width, m_height, (uint32_t)m_levels.size()));
+    }
+
+private:
+    std::vector<float*> m_levels;
+    uint32_t m_width = 0, m_height = 0;
 };
 
 } // namespace ptamd

@@ -29,6 +29,7 @@ EXPORTS = [
     "pt_di_set_resampling", "pt_di_render_with_history", "pt_di_reset_history", "pt_di_download_reservoirs",
     "pt_di_set_light_sampling", "pt_di_download_presampled", "pt_di_set_visibility", "pt_di_set_pairwise",
     "pt_di_set_regir_layout", "pt_di_regir_onion_table", "pt_di_set_brdf_sampling", "pt_di_download_brdf_candidates",
+    "pt_di_pdf_texture_size", "pt_di_set_pdf_mipmap", "pt_di_download_pdf_texture", "pt_mipmap_generate",
     "pt_post_set_constants", "pt_post_render", "pt_post_download_bloom",
     "pt_nrd_composition_process", "pt_nrd_composition_pixels_per_lane", "pt_nrd_reblur_hit_distance_defaults",
     "pt_anim_create_rig", "pt_anim_release_rig", "pt_anim_create_object", "pt_anim_release_object", "pt_anim_evaluate",
@@ -212,6 +213,10 @@ def load_library():
         lib.pt_di_download_presampled.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.pt_di_set_brdf_sampling.argtypes = [C.c_void_p, C.c_uint32, C.c_float]
         lib.pt_di_download_brdf_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.pt_di_pdf_texture_size.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.pt_di_set_pdf_mipmap.argtypes = [C.c_void_p, C.c_uint32]
+        lib.pt_di_download_pdf_texture.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.pt_mipmap_generate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.pt_post_set_constants.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_post_render.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_post_download_bloom.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -930,6 +935,27 @@ class DirectLighting:
         s = np.array(settings).reshape(())
         self.ctx.check(self.ctx.lib.pt_di_set_brdf_sampling(self.ctx.handle, int(s["BrdfSamples"]), float(s["BrdfCutoff"])))
 
+    def SetPdfMipmap(self, enabled):
+        """True: every Render builds the local-light PDF texture and its mip chain, and in the Power_RIS / ReGIR modes the light tiles
+        come from a descent of the chain (pt_di_set_pdf_mipmap). False, the default: the power prefix sum. A changed value resets the
+        history."""
+        self.ctx.check(self.ctx.lib.pt_di_set_pdf_mipmap(self.ctx.handle, 1 if enabled else 0))
+
+    def download_pdf_texture(self):
+        """The levels of the PDF texture of the last Render: a list of float32 arrays [height, width], level 0 first; empty when that
+        render built none. Synchronises."""
+        ctx, fn = self.ctx, self.ctx.lib.pt_di_download_pdf_texture
+        levels = []
+        while len(levels) < 16:
+            w, h = C.c_uint32(0), C.c_uint32(0)
+            ctx.check(fn(ctx.handle, len(levels), None, 0, C.byref(w), C.byref(h)))
+            if w.value == 0 or h.value == 0:
+                break
+            out = np.zeros((h.value, w.value), np.float32)
+            ctx.check(fn(ctx.handle, len(levels), C.c_void_p(out.ctypes.data), out.size, C.byref(w), C.byref(h)))
+            levels.append(out)
+        return levels
+
     def download_brdf_candidates(self):
         """The BRDF candidates of the last Render (numpy layouts.DI_BRDF_CANDIDATE, [local pixels * BrdfSamples], pixel-major; empty
         when that render drew none)."""
@@ -953,6 +979,34 @@ class DirectLighting:
     def download_lights(self):
         """The light records of the last Render (numpy layouts.TRIANGLE_LIGHT, list order)."""
         return _download_counted(self.ctx, self.ctx.lib.pt_di_download_lights, L.TRIANGLE_LIGHT)
+
+
+def pdf_texture_size(n):
+    """(width, height, mip_levels) of the local-light PDF texture of n lights (pt_di_pdf_texture_size; host only, no context, no GPU)."""
+    w, h, m = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    if not 0 <= int(n) <= 0xFFFFFFFF or load_library().pt_di_pdf_texture_size(int(n), C.byref(w), C.byref(h), C.byref(m)) != 0:
+        raise PtInvalidArgument("pt_di_pdf_texture_size: the light count must be 0..2^24")
+    return w.value, h.value, m.value
+
+
+class MipmapGeneration:
+    """Mirror of `struct MipmapGeneration` (Source/MipmapGeneration.ixx: SetTexture + Process) for an R32_FLOAT texture. SetTexture takes
+    the levels, level 0 first, as float32 device tensors or device addresses (level k: max(1, width >> k) x max(1, height >> k), row-major);
+    Process reads level 0 and writes the others on the context's stream. No scene is needed."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self._levels, self._size = None, (0, 0)
+
+    def SetTexture(self, levels, width, height):
+        self._levels, self._size = list(levels), (int(width), int(height))
+
+    def Process(self):
+        if self._levels is None:
+            raise PtInvalidArgument("MipmapGeneration.Process: call SetTexture first")
+        addresses = [v if isinstance(v, int) else (_ptr(v) or 0) for v in self._levels]
+        table = (C.c_void_p * max(len(addresses), 1))(*addresses)
+        self.ctx.check(self.ctx.lib.pt_mipmap_generate(self.ctx.handle, C.cast(table, C.c_void_p), self._size[0], self._size[1], len(addresses)))
 
 
 class PostProcessing:
@@ -1121,8 +1175,9 @@ class Renderer:
         self.constants["Flags"] = L.GBufferFlags.DefaultNoDenoiser        # App.cpp:1224 with Denoiser::None
 
     def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None, post=None, sharc=None, di_visibility=None, di_pairwise=None,
-               di_regir_layout=None, di_brdf=None, nrd=None, denoise=None, nrd_hit_distance=None):
-        """nrd: layouts.DENOISER_NRD_REBLUR / _RELAX (it must be settings' Denoiser) to run App::ProcessNRD (App.cpp:1595-1688) after the
+               di_regir_layout=None, di_brdf=None, nrd=None, denoise=None, nrd_hit_distance=None, di_pdf_mipmap=None):
+        """di_pdf_mipmap: True / False for DirectLighting.SetPdfMipmap ahead of the DI pass, or None: the context's setting is left alone.
+        nrd: layouts.DENOISER_NRD_REBLUR / _RELAX (it must be settings' Denoiser) to run App::ProcessNRD (App.cpp:1595-1688) after the
         frame and before post: the NRD composition pass packs textures["Diffuse"] / ["Specular"] in place, denoise(noisy_diffuse,
         noisy_specular) -> (denoised_diffuse, denoised_specular) takes and returns device tensors of their shape (None: the identity,
         the denoised textures alias the noisy ones), and the pass composes the result into textures["Radiance"]. It needs a renderer with
@@ -1181,6 +1236,8 @@ class Renderer:
             if di_brdf is not None or self._di_brdf_set:
                 self.direct_lighting.SetBrdfSampling(di_brdf)
                 self._di_brdf_set = di_brdf is not None
+            if di_pdf_mipmap is not None:
+                self.direct_lighting.SetPdfMipmap(di_pdf_mipmap)
             self.direct_lighting.Render(tlas)
         if int(np.array(settings).reshape(())["Bounces"]) > 0:            # App.cpp:1277
             self.raytracing.SetConstants(settings)

@@ -636,6 +636,31 @@ int  pt_di_set_brdf_sampling(PtContext* ctx, uint32_t brdf_samples, float brdf_c
 int  pt_di_download_brdf_candidates(PtContext* ctx, uint32_t* host_dst, uint32_t capacity, uint32_t* out_count);
 
 /* ------------------------------------------------------------------------------------------
+ * the local-light PDF texture (App::PrepareReSTIRDI, Source/App.cpp:1095-1116: the LocalLightPDF texture is cleared,
+ * LightPreparation writes TriangleLight::CalculatePower() at RTXDI_LinearIndexToZCurve(lightIndex), Shaders/LightPreparation.hlsl:133,
+ * and MipmapGeneration::Process builds its chain). With the setting on, every pt_di_render of a scene with emitters builds the texture
+ * and its chain, and in PT_DI_LOCAL_LIGHT_POWER_RIS / _REGIR_RIS the Power_RIS tiles come from a descent of the chain
+ * (RTXDI_PresampleLocalLights) instead of the power prefix sum, and the source pdf of a light no tile produced
+ * (RAB_EvaluateLocalLightSourcePdf, Shaders/RTXDIAppBridge.hlsli:488-501) is Power / (top * M * M), top the chain's last texel and
+ * M = max(width, height). POWER_CDF and UNIFORM keep their bits. Off by default, and with it off every launch and output is what it
+ * was. The RTXDI SDK is not in the reference tree: size rule and descent are this library's own after the SDK's structure, unpinned;
+ * DESIGN.md section 1, "Local-light PDF texture", is the spec (tests/pdfmipref.py restates it). The entry points take plain values and
+ * pointers: the C ABI's list of structs stays the one it was.
+ * ------------------------------------------------------------------------------------------ */
+/* ComputePdfTextureSize (Source/RTXDIResources.ixx:43-52) in integers: width = the smallest power of two >= ceil(sqrt(n)), height = the
+ * smallest power of two >= ceil(n / width), mip_levels = log2(max(width, height)) + 1; n = 0 counts as 1; square or 2:1. Host
+ * arithmetic, no context, no GPU. light_count above 2^24 and a NULL pointer are refused. */
+int  pt_di_pdf_texture_size(uint32_t light_count, uint32_t* width, uint32_t* height, uint32_t* mip_levels);
+/* enabled: 0 (the default) or 1; anything else is refused and leaves the previous setting active; a changed value resets the history.
+ * The texture is per context (a context viewing a shared scene builds its own), grow-only, 5.6 MB at 2^20 lights. */
+int  pt_di_set_pdf_mipmap(PtContext* ctx, uint32_t enabled);
+/* One level of the PDF texture of the last pt_di_render, row-major: level k is max(1, width >> k) x max(1, height >> k); level 0
+ * holds Power at (x, y) = (even bits, odd bits) of the light index and 0 elsewhere. out_width x out_height = 0 x 0 when that render
+ * built none (the setting off, no emitters) or the texture has no such level; min(capacity, out_width * out_height) floats are
+ * copied; synchronises. level >= 16 and a NULL out pointer (or a NULL host_dst with capacity > 0) are refused. */
+int  pt_di_download_pdf_texture(PtContext* ctx, uint32_t level, float* host_dst, uint32_t capacity, uint32_t* out_width, uint32_t* out_height);
+
+/* ------------------------------------------------------------------------------------------
  * building blocks the reference's direct-lighting bridge calls on the same data
  * ------------------------------------------------------------------------------------------ */
 typedef struct PtRayDesc { float Origin[3]; float TMin; float Direction[3]; float TMax; } PtRayDesc;   /* HLSL RayDesc, 32 B */
@@ -733,6 +758,20 @@ int  pt_nrd_composition_process(PtContext* ctx, const struct PtNRDCompositionCon
  * values (nothing is dereferenced, no GPU): the decision pt_nrd_composition_process itself takes. */
 int  pt_nrd_composition_pixels_per_lane(const struct PtNRDCompositionConstants* constants, const struct PtNRDCompositionTextures* textures);
 void pt_nrd_reblur_hit_distance_defaults(float out[4]);    /* {3, 0.1, 20, -25}; needs no GPU */
+
+/* ------------------------------------------------------------------------------------------
+ * the mip chain of an R32_FLOAT texture (MipmapGeneration::SetTexture + Process, Source/MipmapGeneration.ixx ->
+ * Shaders/MipmapGeneration.hlsl), which App::PrepareReSTIRDI (Source/App.cpp:1095-1116) runs on the LocalLightPDF texture. The
+ * shader is not restated: DESIGN.md section 1, "Local-light PDF texture", is the arithmetic spec (tests/pdfmipref.py restates it).
+ * ------------------------------------------------------------------------------------------ */
+/* levels: a host array of mip_levels device pointers; levels[k] is level k, row-major and tightly packed, max(1, width >> k) x
+ * max(1, height >> k) texels. Level 0 is read, levels 1 .. mip_levels - 1 are written: a texel is a quarter of the sum of the four
+ * under it, a texel outside its level counting as 0 (the levels of a 2:1 texture stay zero-padded to a square). Unlike the reference's
+ * Process, which under-dispatches its second pass for textures wider than 1024, every level is covered fully. Enqueued on the
+ * context's stream, ceil((mip_levels - 1) / 5) launches; mip_levels = 1 enqueues nothing. Needs no scene. Refused with
+ * PT_ERROR_INVALID_ARGUMENT and a message, nothing enqueued: a NULL array or level, a level not aligned to 4 bytes, a width or height
+ * that is 0, not a power of two or above 16384, mip_levels of 0, above 16 or above log2(max(width, height)) + 1. */
+int  pt_mipmap_generate(PtContext* ctx, float* const* levels, uint32_t width, uint32_t height, uint32_t mip_levels);
 
 /* ------------------------------------------------------------------------------------------
  * the SHARC radiance cache: the Raytracing::Render overload with RTXGITechnique::SHARC (Source/Raytracing.ixx:114-148, Source/SHARC.ixx,

@@ -7,13 +7,15 @@ whose visibility has age 0 was traced this frame, an older one was reused). --pa
 correction (layouts.di_pairwise_settings, both passes) side by side at SpatialSamples 1 and 4, three alternating rounds each. --light-sampling times each listed local-light sampling mode (cdf, uniform, power_ris, regir, regir_onion: ReGIR over the Onion layout; one JSON line per mode). The workload
 --brdf-samples 0,1,2 times the plain pass with that many BRDF candidates per pixel (layouts.di_brdf_settings; 0 is the pass as it was): "brdf": {N_B: pass ms}; the BRDF-ray kernel's own share is the
 difference to N_B = 0 less what the candidates add to initial sampling, and `rocprofv3 --kernel-trace --stats -- python tools/di_time.py --child W --brdf-samples 1` names it (k_di_brdf_rays). The workload
-emitter_field is scenes.emitter_field(256) (131 k emissive triangles) at 1920 x 1080, 1 spp, 1 bounce.
-usage: tools/di_time.py [--workloads c2,c3,c5,emitter_field] [--samples 8] [--n 20] [--reuse [--visibility] [--pairwise]] [--light-sampling cdf,regir] [--brdf-samples 0,1,2]"""
+emitter_field is scenes.emitter_field(256) (131 k emissive triangles) at 1920 x 1080, 1 spp, 1 bounce. --pdf-mipmap times every listed
+--light-sampling mode twice, with the local-light PDF texture off and on (DirectLighting.SetPdfMipmap; "pdf_mipmap" in the JSON line): the
+texture and its chain are built in every mode, the descent replaces the prefix sum in power_ris, regir and regir_onion.
+usage: tools/di_time.py [--workloads c2,c3,c5,emitter_field] [--samples 8] [--n 20] [--reuse [--visibility] [--pairwise]] [--light-sampling cdf,regir] [--brdf-samples 0,1,2] [--pdf-mipmap]"""
 import argparse, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def child(w, samples, n, reuse, modes, visibility=False, pairwise=False, brdf=()):
+def child(w, samples, n, reuse, modes, visibility=False, pairwise=False, brdf=(), pdf_mipmap=False):
     sys.path.insert(0, ROOT)
     import torch
     import __graft_entry__ as ge
@@ -45,7 +47,8 @@ def child(w, samples, n, reuse, modes, visibility=False, pairwise=False, brdf=()
     r.render(gs)                                               # G-buffer + warm-up
     ctx.sync()
     off_ms = timed(lambda i: r.render(gs), max(3, n // 4))
-    for mode in modes:
+    cases = [(mode, pdf) for mode in modes for pdf in ((False, True) if pdf_mipmap else (None,))]
+    for mode, pdf in cases:
         ls = None if mode == "cdf" else L.di_light_sampling_settings("regir" if mode == "regir_onion" else mode)
         layout = L.di_regir_layout_settings("onion") if mode == "regir_onion" else None
         r.render(gs)
@@ -53,6 +56,8 @@ def child(w, samples, n, reuse, modes, visibility=False, pairwise=False, brdf=()
         r.direct_lighting.SetConstants(L.di_settings(W, H, 0, samples, ext_flags=ext))
         r.direct_lighting.SetLightSampling(ls)
         r.direct_lighting.SetReGIRLayout(layout)
+        if pdf is not None:
+            r.direct_lighting.SetPdfMipmap(pdf)
         lights = r.direct_lighting.light_count()
         for _ in range(3):
             r.direct_lighting.Render(tlas)
@@ -63,8 +68,12 @@ def child(w, samples, n, reuse, modes, visibility=False, pairwise=False, brdf=()
         on_ms = timed(lambda i: r.render(gs_on, di_samples=samples, di_light_sampling=ls, di_regir_layout=layout), max(3, n // 4))
         out = {"workload": w, "size": [W, H], "lights": lights, "samples": samples, "light_sampling": mode, "di_ms": di_ms,
                "frame_di_off_ms": off_ms, "frame_di_on_ms": on_ms}
-        if mode != modes[-1]:
+        if pdf is not None:
+            out["pdf_mipmap"] = pdf
+        if (mode, pdf) != cases[-1]:
             print(json.dumps(out), flush=True)
+    if pdf_mipmap:
+        r.direct_lighting.SetPdfMipmap(False)
     if brdf:                                                   # the plain pass of the last mode with N_B BRDF candidates, alternating twice
         rows = {}
         for rnd in range(2):
@@ -123,14 +132,15 @@ if __name__ == "__main__":
     ap.add_argument("--samples", type=int, default=8); ap.add_argument("--n", type=int, default=20); ap.add_argument("--reuse", action="store_true")
     ap.add_argument("--light-sampling", default="cdf"); ap.add_argument("--visibility", action="store_true")
     ap.add_argument("--pairwise", action="store_true"); ap.add_argument("--brdf-samples", default="")
+    ap.add_argument("--pdf-mipmap", action="store_true")
     a = ap.parse_args()
     if a.child:
         child(a.child, a.samples, a.n, a.reuse, a.light_sampling.split(","), a.visibility, a.pairwise,
-              [int(v) for v in a.brdf_samples.split(",") if v]); sys.exit(0)
+              [int(v) for v in a.brdf_samples.split(",") if v], a.pdf_mipmap); sys.exit(0)
     for w in a.workloads.split(","):
         p = subprocess.run([sys.executable, __file__, "--child", w, "--samples", str(a.samples), "--n", str(a.n),
                             "--light-sampling", a.light_sampling] + (["--reuse"] if a.reuse else []) + (["--visibility"] if a.visibility else []) +
-                           (["--pairwise"] if a.pairwise else []) + (["--brdf-samples", a.brdf_samples] if a.brdf_samples else []), stdout=subprocess.PIPE,
+                           (["--pairwise"] if a.pairwise else []) + (["--brdf-samples", a.brdf_samples] if a.brdf_samples else []) + (["--pdf-mipmap"] if a.pdf_mipmap else []), stdout=subprocess.PIPE,
                            stderr=subprocess.PIPE, text=True, timeout=600)
         line = [l for l in p.stdout.splitlines() if l.startswith("{")]
         print("\n".join(line) if line else "%s FAILED (exit %d) %s" % (w, p.returncode, p.stderr[-400:]), flush=True)
