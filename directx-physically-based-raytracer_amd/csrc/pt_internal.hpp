@@ -278,6 +278,14 @@ struct Context {
     uint32_t postDims[9][2] = {};                     // what each stage wrote in the last render with bloom on; 0 x 0: not written
     size_t postOffset[9] = {};                        // texel offset of each stage's slot in postLevels
 
+    // denoiser (pt_denoise.hip): every per-pixel array of the history in one grow-only allocation, 17 float4 per pixel of the frame (the
+    // ping-pong pairs of the accumulated colours, moments and guide records, the a-trous work buffers, the lengths and variances)
+    PtDenoiserSettings dn{}; bool haveDn = false;
+    DeviceBuffer<float4> dnHistory;
+    uint32_t dnSize[2] = {0, 0};                      // the frame the history was laid out for by the last pt_denoiser_process
+    uint32_t dnParity = 0;                            // which half of each pair the last call wrote
+    uint64_t dnFrames = 0;                            // calls since the history was last reset; 0: the next call finds none
+
     // SHARC radiance cache (pt_sharc.hip): per context, also for a context that views another's scene. sharcVoxels[sharcParity] is VoxelData (this
     // frame's deposits, then the resolved cache), the other one PreviousVoxelData; they swap after the query.
     PtSHARCSettings sharcSettings{}; bool haveSharcSettings = false;

@@ -6,7 +6,7 @@
 //           [--light-sampling cdf|uniform|power_ris|regir [--regir-layout grid|onion]] [--di-pdf-mipmap]
 //           [--post] [--no-bloom] [--bloom-strength S] [--tone-map saturate|reinhard|aces] [--exposure E]
 //           [--hdr [--paper-white N] [--color-rotation hdtv_to_uhdtv|dci_p3_d65_to_uhdtv|hdtv_to_dci_p3_d65]]
-//           [--nrd relax|reblur] [--out-radiance file.bin]
+//           [--nrd relax|reblur [--denoise [--denoise-frames-max N] [--denoise-iterations K]]] [--out-radiance file.bin]
 //           [--png file.png] [--out-display file.bin] [--scene descriptor.json [--anim-time T [--anim-step DT]]] [--dump-scene file.bin]
 //
 // --anim-time T (with --scene): the animated render objects of the descriptor (RenderObjects[].Animation) are posed at T seconds of their selected
@@ -36,8 +36,12 @@
 //
 // --nrd relax|reblur: the frame is rendered with that Denoiser value (the G-buffer pass then writes the albedos, App.cpp:1223, and the path tracer the
 // NRD-facing Diffuse / Specular), and App::ProcessNRD (App.cpp:1595-1688) runs after it and before --post: the NRD composition pass packs the pair,
-// the denoiser -- here the identity: this library has none -- leaves it as it is, and the pass composes it into Radiance. With --ranks every rank
+// the denoiser -- the identity unless --denoise is given -- leaves it as it is, and the pass composes it into Radiance. With --ranks every rank
 // runs the two passes on its own rows, before the gather. --out-radiance writes the last frame's Radiance (R16G16B16A16_FLOAT, the whole frame).
+// --denoise (with --nrd relax, one unsharded process): the library's own denoiser (ptamd.hpp Denoiser: temporal accumulation, variance,
+// a-trous) runs between the pack and the compose instead of the identity, at its defaults unless --denoise-frames-max (MaxAccumulatedFrames)
+// or --denoise-iterations (AtrousIterations) change them. The timed frames are then one temporal sequence: they carry FrameIndex 0 .. N - 1
+// in that order, and the history starts empty behind the warm-up frame. ReBLUR's packing is refused.
 //
 // --ranks R: one process per GPU. The parent (which never touches a GPU) starts R children `--rank r --world R --id-file F`; rank 0
 // makes the RCCL unique id and leaves it in F, the others pick it up; every rank renders its 16-row bands (BandSharding) and rank 0
@@ -409,6 +413,7 @@ int main(int argc, char** argv)
     std::string toneMap = "aces", colorRotation = "hdtv_to_uhdtv", pngPath, displayPath;
     bool animate = false; double animTime = 0.0, animStep = 0.0;
     std::string nrd, radiancePath;
+    bool denoise = false; uint32_t denoiseFramesMax = 30, denoiseIterations = 5;
     for (int i = 1; i < argc; i++) {
         std::string k = argv[i];
         if (k == "--di") { di = true; continue; }                  // the flags without a value
@@ -421,6 +426,7 @@ int main(int argc, char** argv)
         if (k == "--post") { post = true; continue; }
         if (k == "--no-bloom") { bloom = false; continue; }
         if (k == "--hdr") { hdr = true; continue; }
+        if (k == "--denoise") { denoise = true; continue; }
         if (i + 1 >= argc) break;
         const char* v = argv[++i];
         if (k == "--width") W = atoi(v); else if (k == "--height") H = atoi(v);
@@ -437,6 +443,7 @@ int main(int argc, char** argv)
         else if (k == "--exposure") exposure = (float)atof(v); else if (k == "--paper-white") paperWhite = (float)atof(v);
         else if (k == "--color-rotation") colorRotation = v; else if (k == "--png") pngPath = v;
         else if (k == "--out-display") displayPath = v;
+        else if (k == "--denoise-frames-max") denoiseFramesMax = atoi(v); else if (k == "--denoise-iterations") denoiseIterations = atoi(v);
         else if (k == "--nrd") nrd = v; else if (k == "--out-radiance") radiancePath = v;
         else if (k == "--anim-time") { animate = true; animTime = atof(v); } else if (k == "--anim-step") animStep = atof(v);
     }
@@ -605,7 +612,13 @@ int main(int argc, char** argv)
         if (useSharc && sharded) throw std::invalid_argument("--sharc needs one unsharded process");
         if (useSharc && nrdDenoiser) throw std::invalid_argument("--nrd: the radiance-cache query does not serve the NRD packing, drop --sharc");
         NRDComposition nrdComposition(commandList);
-        if (nrdDenoiser) fprintf(stderr, "pt_demo: --nrd %s: the denoiser between the pack and the compose is the identity\n", nrd.c_str());
+        if (denoise && (!nrdDenoiser || sharded)) throw std::invalid_argument("--denoise needs --nrd relax and one unsharded process");
+        Denoiser denoiser(commandList);
+        if (denoise) {                                              // refuses ReBLUR's packing
+            Denoiser::Settings s; s.RenderSize[0] = W; s.RenderSize[1] = H; s.Denoiser = nrdDenoiser;
+            s.MaxAccumulatedFrames = denoiseFramesMax; s.AtrousIterations = denoiseIterations;
+            denoiser.SetConstants(s);
+        } else if (nrdDenoiser) fprintf(stderr, "pt_demo: --nrd %s: the denoiser between the pack and the compose is the identity\n", nrd.c_str());
         SHARC sharc(commandList);
         Raytracing::SHARCSettings sharcSettings; sharcSettings.DownscaleFactor = sharcDownscale;
         if (useSharc) { sharc.Constants.SceneScale = sceneScale; sharc.Configure(); }
@@ -716,6 +729,10 @@ int main(int argc, char** argv)
                 nrdComposition.Textures = { tx.LinearDepth, tx.DiffuseAlbedo, tx.SpecularAlbedo, tx.NormalRoughness, tx.Diffuse, tx.Specular,
                                             tx.Diffuse, tx.Specular, tx.Radiance };
                 nc.IsPack = true; nrdComposition.Process(commandList, nc);
+                if (denoise) {                                      // in place: the Denoised pair is the Noisy pair
+                    denoiser.Textures = { tx.Position, tx.LinearDepth, tx.NormalRoughness, tx.MotionVector, tx.Diffuse, tx.Specular, tx.Diffuse, tx.Specular };
+                    denoiser.Process(commandList);
+                }
                 nc.IsPack = false; nrdComposition.Process(commandList, nc);
             }
             if (sharded) sharding.GatherBands(commandList, tx.Radiance, fullRadiance, W, H, 8);
@@ -724,13 +741,14 @@ int main(int argc, char** argv)
         animateFrame();
         renderFrame(12345);                                         // warm-up
         commandList.End();
+        if (denoise) denoiser.ResetHistory();                       // the warm-up frame is not part of the sequence
         // timed run: frames 1..N back to back
         ThrowIfFailed(commandList.Context, pt_reset_counters(commandList.Context));
         const auto t0 = std::chrono::steady_clock::now();
         for (uint32_t f = 0; f < frames; f++) {                    // the last frame has FrameIndex 0 (dumped below)
             if (f) for (AnimationCollection* c : collectionList) (*c)[c->GetSelectedIndex()].Tick(animStep);
             animateFrame();
-            renderFrame(frames - 1 - f);
+            renderFrame(denoise ? f : frames - 1 - f);              // a denoised run is a temporal sequence: FrameIndex counts up
         }
         commandList.End();
         ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

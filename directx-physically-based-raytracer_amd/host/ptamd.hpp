@@ -9,6 +9,7 @@
 //     struct Animation / AnimationCollection   Source/Animation.ixx:78-197 (the clock and the selection; the transforms are computed on the device)
 //     struct PostProcessing      App::PostProcessGraphics with Denoiser::None (Source/App.cpp:1506-1571): Bloom, Merge, ToneMap, CopyTexture
 //     struct NRDComposition      Source/NRDComposition.ixx (the pack and compose passes of App::ProcessNRD, Source/App.cpp:1595-1688)
+//     struct Denoiser            the library's own filter for the ReLAX slot between them (where the reference calls NRD::Denoise)
 // Error behaviour: a failing status becomes the exception type the reference throws at the same place
 // (std::invalid_argument for argument checks, std::system_error otherwise: Source/ErrorHelpers.ixx:16-32).
 // Header-only, plain C++20 (std::span), no HIP headers needed by the including translation unit.
@@ -611,6 +612,54 @@ struct NRDComposition {
         for (int i = 0; i < 4; i++) k.ReBLURHitDistance[i] = constants.ReBLURHitDistance[i];
         ThrowIfFailed(commandList.Context, pt_nrd_composition_process(commandList.Context, &k, &Textures));
     }
+};
+
+// The library's own denoiser for the ReLAX slot between the two calls of NRDComposition (pt_denoiser_*; DESIGN.md section 1, "Denoiser"):
+// temporal accumulation with reprojection, a variance estimate, an edge-stopping a-trous wavelet. Not NRD's ReLAX, and ReLAX's packing
+// only: SetConstants refuses Settings::Denoiser = PT_DENOISER_NRD_REBLUR. In App::ProcessNRD it stands where NRD::Denoise does. The
+// Denoised pair may be the Noisy pair. Runs on the full frame: a sharded host calls it on the gathered textures.
+struct Denoiser {
+    struct Settings {
+        uint32_t RenderSize[2]{};
+        uint32_t MaxAccumulatedFrames = 30, AtrousIterations = 5;           // 1..255 | 0..8
+        float DepthThreshold = 0.01f, NormalCosine = 0.8f;                  // (0, 1] | [0, 1)
+        float DiffuseLuminanceSigma = 2, SpecularLuminanceSigma = 1, RoughnessFraction = 0.15f;   // > 0
+        uint32_t Denoiser = PT_DENOISER_NRD_RELAX;                          // the packing of the pair it will be handed
+    };
+
+    PtDenoiserTextures Textures{};
+
+    explicit Denoiser(CommandList& commandList) : m_context(commandList.Context) {}
+
+    void SetConstants(const Settings& settings)
+    {
+        if (settings.Denoiser != PT_DENOISER_NRD_RELAX)
+            throw std::invalid_argument("the denoiser reads ReLAX's packing (radiance, hit distance) only: ReBLUR's (YCoCg, normalised hit distance) "
+                                        "and the other Denoiser values are not served");
+        PtDenoiserSettings s{};
+        s.RenderSize[0] = settings.RenderSize[0]; s.RenderSize[1] = settings.RenderSize[1];
+        s.MaxAccumulatedFrames = settings.MaxAccumulatedFrames; s.AtrousIterations = settings.AtrousIterations;
+        s.DepthThreshold = settings.DepthThreshold; s.NormalCosine = settings.NormalCosine;
+        s.DiffuseLuminanceSigma = settings.DiffuseLuminanceSigma; s.SpecularLuminanceSigma = settings.SpecularLuminanceSigma;
+        s.RoughnessFraction = settings.RoughnessFraction;
+        ThrowIfFailed(m_context, pt_denoiser_set_constants(m_context, &s));
+    }
+
+    void Process(CommandList& commandList) { ThrowIfFailed(commandList.Context, pt_denoiser_process(commandList.Context, &Textures)); }
+
+    void ResetHistory() { ThrowIfFailed(m_context, pt_denoiser_reset_history(m_context)); }
+
+    // the accumulated length of the diffuse channel per pixel after the last Process, row-major; empty when there is no history. Synchronises.
+    std::vector<float> DownloadHistory(uint32_t& width, uint32_t& height)
+    {
+        ThrowIfFailed(m_context, pt_denoiser_download_history(m_context, nullptr, 0, &width, &height));
+        std::vector<float> out((size_t)width * height);
+        if (!out.empty()) ThrowIfFailed(m_context, pt_denoiser_download_history(m_context, out.data(), out.size(), &width, &height));
+        return out;
+    }
+
+private:
+    PtContext* m_context;
 };
 
 // struct MipmapGeneration (Source/MipmapGeneration.ixx: SetTexture + Process) for an R32_FLOAT texture: Process reads level 0 and writes the

@@ -341,6 +341,60 @@ def nrd_composition_constants(width, height, denoiser, is_pack, hit_distance=Non
     return check_nrd_composition_constants(k)
 
 
+DENOISER_SETTINGS = np.dtype({  # PtDenoiserSettings, 48 B
+    "names": ["RenderSize", "MaxAccumulatedFrames", "AtrousIterations", "DepthThreshold", "NormalCosine", "DiffuseLuminanceSigma",
+              "SpecularLuminanceSigma", "RoughnessFraction", "_pad"],
+    "formats": [("<u4", 2), "<u4", "<u4", "<f4", "<f4", "<f4", "<f4", "<f4", ("<u4", 3)],
+    "offsets": [0, 8, 12, 16, 20, 24, 28, 32, 36], "itemsize": 48})
+# PtDenoiserTextures member order: eight pointers
+DENOISER_TEXTURES = ["Position", "LinearDepth", "NormalRoughness", "MotionVector", "NoisyDiffuse", "NoisySpecular",
+                     "DenoisedDiffuse", "DenoisedSpecular"]
+DENOISER_DEFAULTS = {"MaxAccumulatedFrames": 30, "AtrousIterations": 5, "DepthThreshold": 0.01, "NormalCosine": 0.8,
+                     "DiffuseLuminanceSigma": 2.0, "SpecularLuminanceSigma": 1.0, "RoughnessFraction": 0.15}
+DENOISER_MAX_SIZE = 16384
+
+
+def check_denoiser_settings(s):
+    """The range checks of pt_denoiser_set_constants, on the float32 values the library receives: ValueError where it answers
+    PT_ERROR_INVALID_ARGUMENT."""
+    s = np.asarray(s).reshape(())
+    w, h = (int(v) for v in s["RenderSize"])
+    f = {k: float(np.float32(s[k])) for k in ("DepthThreshold", "NormalCosine", "DiffuseLuminanceSigma", "SpecularLuminanceSigma", "RoughnessFraction")}
+    if not (1 <= w <= DENOISER_MAX_SIZE and 1 <= h <= DENOISER_MAX_SIZE):
+        raise ValueError(f"RenderSize must be 1..{DENOISER_MAX_SIZE} on both axes")
+    if not 1 <= int(s["MaxAccumulatedFrames"]) <= 255:
+        raise ValueError("MaxAccumulatedFrames must be 1..255")
+    if int(s["AtrousIterations"]) > 8:
+        raise ValueError("AtrousIterations must be 0..8")
+    if not 0.0 < f["DepthThreshold"] <= 1.0:
+        raise ValueError("DepthThreshold must be in (0, 1]")
+    if not 0.0 <= f["NormalCosine"] < 1.0:
+        raise ValueError("NormalCosine must be in [0, 1)")
+    for k in ("DiffuseLuminanceSigma", "SpecularLuminanceSigma", "RoughnessFraction"):
+        if not (f[k] > 0.0 and np.isfinite(f[k])):
+            raise ValueError(f"{k} must be positive and finite")
+    return s
+
+
+def denoiser_settings(width, height, **overrides):
+    """PtDenoiserSettings with the defaults of DENOISER_DEFAULTS; overrides by field name. Refuses what pt_denoiser_set_constants refuses."""
+    s = np.zeros((), DENOISER_SETTINGS)
+    for name, v in (("RenderSize", width), ("RenderSize", height)):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{name} is not a 32-bit unsigned value")
+    s["RenderSize"] = (width, height)
+    values = dict(DENOISER_DEFAULTS)
+    for k, v in overrides.items():
+        if k not in values:
+            raise ValueError(f"PtDenoiserSettings has no field {k}")
+        values[k] = v
+    for k, v in values.items():
+        if s.dtype[k].kind == "u" and not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{k} is not a 32-bit unsigned value")
+        s[k] = v
+    return check_denoiser_settings(s)
+
+
 SHARC_SETTINGS = np.dtype({  # PtSHARCSettings: SHARC::Constants + Raytracing::SHARCSettings (Source/MyAppData.h:250-262)
     "names": ["AccumulationFrames", "MaxStaleFrames", "SceneScale", "IsAntiFireflyEnabled", "DownscaleFactor", "RoughnessThreshold",
               "IsHashGridVisualizationEnabled"],

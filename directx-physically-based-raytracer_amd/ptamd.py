@@ -32,6 +32,7 @@ EXPORTS = [
     "pt_di_pdf_texture_size", "pt_di_set_pdf_mipmap", "pt_di_download_pdf_texture", "pt_mipmap_generate",
     "pt_post_set_constants", "pt_post_render", "pt_post_download_bloom",
     "pt_nrd_composition_process", "pt_nrd_composition_pixels_per_lane", "pt_nrd_reblur_hit_distance_defaults",
+    "pt_denoiser_set_constants", "pt_denoiser_process", "pt_denoiser_reset_history", "pt_denoiser_download_history",
     "pt_anim_create_rig", "pt_anim_release_rig", "pt_anim_create_object", "pt_anim_release_object", "pt_anim_evaluate",
     "pt_anim_skeletal_transforms", "pt_anim_download_globals", "pt_anim_download_skeletal", "pt_anim_debug_slerp",
     "pt_sharc_configure", "pt_sharc_set_constants", "pt_raytrace_render_sharc", "pt_sharc_reset", "pt_sharc_download",
@@ -76,6 +77,10 @@ class PostTextures(C.Structure):
 
 class NRDCompositionTextures(C.Structure):   # PtNRDCompositionTextures: nine pointers, NRDComposition::Textures' member order
     _fields_ = [(n, C.c_void_p) for n in L.NRD_COMPOSITION_TEXTURES]
+
+
+class DenoiserTextures(C.Structure):         # PtDenoiserTextures: eight pointers
+    _fields_ = [(n, C.c_void_p) for n in L.DENOISER_TEXTURES]
 
 
 class Sharding(C.Structure):
@@ -223,6 +228,10 @@ def load_library():
         lib.pt_nrd_composition_process.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pt_nrd_composition_pixels_per_lane.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_nrd_reblur_hit_distance_defaults.argtypes = [C.c_void_p]; lib.pt_nrd_reblur_hit_distance_defaults.restype = None
+        lib.pt_denoiser_set_constants.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_denoiser_process.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_denoiser_reset_history.argtypes = [C.c_void_p]
+        lib.pt_denoiser_download_history.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.pt_sharc_configure.argtypes = [C.c_void_p, C.c_uint32]
         lib.pt_sharc_set_constants.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_raytrace_render_sharc.argtypes = [C.c_void_p, C.c_void_p]
@@ -1082,6 +1091,59 @@ def nrd_composition_pixels_per_lane(pointers, constants):
     return load_library().pt_nrd_composition_pixels_per_lane(C.c_void_p(k.ctypes.data), C.addressof(t))
 
 
+class Denoiser:
+    """The library's own denoiser for the ReLAX slot between the two calls of the NRD composition pass (pt_denoiser_*; DESIGN.md section
+    1, "Denoiser"): temporal accumulation with reprojection, a variance estimate, an edge-stopping a-trous wavelet. Not NRD's ReLAX, and
+    ReLAX's packing only: SetConstants refuses denoiser=DENOISER_NRD_REBLUR. Process takes the textures by the names of
+    layouts.DENOISER_TEXTURES (a missing name is an unbound texture); the Denoised pair may be the Noisy pair. Runs on the full frame: a
+    sharded host calls it on the gathered frame. No scene is needed.
+
+    An instance is callable as denoise(noisy_diffuse, noisy_specular) -> (denoised_diffuse, denoised_specular), in place, on the guide
+    textures of self.Textures: what Renderer.render(..., nrd=DENOISER_NRD_RELAX, denoise=...) asks for."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.Textures = {}
+        self._settings = None
+
+    def SetConstants(self, settings, denoiser=L.DENOISER_NRD_RELAX):
+        """settings: PtDenoiserSettings (layouts.denoiser_settings). denoiser: the packing of the pair it will be handed."""
+        if int(denoiser) != L.DENOISER_NRD_RELAX:
+            raise PtInvalidArgument("the denoiser reads ReLAX's packing (radiance, hit distance) only: ReBLUR's (YCoCg, normalised hit "
+                                    "distance) and the other Denoiser values are not served")
+        k = np.array(settings)
+        if k.dtype != L.DENOISER_SETTINGS or k.size != 1:
+            raise PtInvalidArgument("settings must be one PtDenoiserSettings record (layouts.denoiser_settings)")
+        k = np.ascontiguousarray(k).reshape(())
+        self.ctx.check(self.ctx.lib.pt_denoiser_set_constants(self.ctx.handle, C.c_void_p(k.ctypes.data)))
+        self._settings = k
+
+    def Process(self, textures=None):
+        tex = self.Textures if textures is None else textures
+        t = DenoiserTextures(*[_ptr(tex.get(n)) for n in L.DENOISER_TEXTURES])
+        self.ctx.check(self.ctx.lib.pt_denoiser_process(self.ctx.handle, C.addressof(t)))
+
+    def ResetHistory(self):
+        self.ctx.check(self.ctx.lib.pt_denoiser_reset_history(self.ctx.handle))
+
+    def DownloadHistory(self):
+        """The accumulated length of the diffuse channel per pixel after the last Process: float32 (h, w), 0 where the G-buffer missed;
+        empty (0, 0) when there is no history. Synchronises."""
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        self.ctx.check(self.ctx.lib.pt_denoiser_download_history(self.ctx.handle, None, 0, C.byref(w), C.byref(h)))
+        out = np.zeros((h.value, w.value), np.float32)
+        if out.size:
+            self.ctx.check(self.ctx.lib.pt_denoiser_download_history(self.ctx.handle, C.c_void_p(out.ctypes.data), out.size, C.byref(w), C.byref(h)))
+        return out
+
+    def __call__(self, noisy_diffuse, noisy_specular):
+        if self._settings is None:
+            raise PtInvalidArgument("Denoiser: call SetConstants first")
+        self.Process(dict(self.Textures, NoisyDiffuse=noisy_diffuse, NoisySpecular=noisy_specular,
+                          DenoisedDiffuse=noisy_diffuse, DenoisedSpecular=noisy_specular))
+        return noisy_diffuse, noisy_specular
+
+
 class SHARC:
     """Mirror of `struct SHARC` (Source/SHARC.ixx) and of the Raytracing::Render overload that takes it: Configure allocates the context's
     cache, SetConstants takes PtSHARCSettings (layouts.sharc_settings), Render runs clear, update, resolve, query and the swap with the
@@ -1165,6 +1227,7 @@ class Renderer:
         self.post = PostProcessing(ctx)
         self.sharc = SHARC(ctx)
         self.nrd = NRDComposition(ctx)
+        self._denoiser = None
         d = scene_gpu.desc
         for op in (self.gbuffer, self.raytracing, self.direct_lighting):
             op.GPUBuffers["Camera"] = d.camera
@@ -1174,13 +1237,28 @@ class Renderer:
         self.constants["RenderSize"] = (width, height)
         self.constants["Flags"] = L.GBufferFlags.DefaultNoDenoiser        # App.cpp:1224 with Denoiser::None
 
+    @property
+    def denoiser(self):
+        """The library's denoiser (Denoiser) bound to this renderer's guide textures, with layouts.denoiser_settings' defaults at the
+        renderer's size, created at first use: render(..., nrd=layouts.DENOISER_NRD_RELAX, denoise=renderer.denoiser). Other settings:
+        renderer.denoiser.SetConstants. Unsharded contexts only: the filter needs the whole frame."""
+        if self._denoiser is None:
+            if getattr(self.ctx, "sharding", (0, 1, 16))[1] > 1:
+                raise PtInvalidArgument("the denoiser needs the whole frame: run Denoiser on the gathered textures of a sharded render")
+            d = Denoiser(self.ctx)
+            d.Textures = self.textures                                    # Position, LinearDepth, NormalRoughness, MotionVector
+            d.SetConstants(L.denoiser_settings(self.width, self.height))
+            self._denoiser = d
+        return self._denoiser
+
     def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None, post=None, sharc=None, di_visibility=None, di_pairwise=None,
                di_regir_layout=None, di_brdf=None, nrd=None, denoise=None, nrd_hit_distance=None, di_pdf_mipmap=None):
         """di_pdf_mipmap: True / False for DirectLighting.SetPdfMipmap ahead of the DI pass, or None: the context's setting is left alone.
         nrd: layouts.DENOISER_NRD_REBLUR / _RELAX (it must be settings' Denoiser) to run App::ProcessNRD (App.cpp:1595-1688) after the
         frame and before post: the NRD composition pass packs textures["Diffuse"] / ["Specular"] in place, denoise(noisy_diffuse,
         noisy_specular) -> (denoised_diffuse, denoised_specular) takes and returns device tensors of their shape (None: the identity,
-        the denoised textures alias the noisy ones), and the pass composes the result into textures["Radiance"]. It needs a renderer with
+        the denoised textures alias the noisy ones; self.denoiser: the library's own filter, ReLAX only), and the pass composes the result
+        into textures["Radiance"]. It needs a renderer with
         with_denoiser_outputs=True; the G-buffer call then carries the albedo flags. nrd_hit_distance: the four ReBLUR hit-distance
         parameters, None: the defaults. Works on a sharded context (on its own rows).
         di_brdf: layouts.di_brdf_settings for BRDF candidates in the DI pass's initial sampling, or None: none (the
@@ -1216,6 +1294,8 @@ class Renderer:
                 raise PtInvalidArgument("nrd must be DENOISER_NRD_REBLUR or DENOISER_NRD_RELAX")
             if denoiser != int(nrd):
                 raise PtInvalidArgument("nrd differs from the settings' Denoiser: the frame must write the NRD-facing outputs the pass packs")
+            if isinstance(denoise, Denoiser) and int(nrd) != L.DENOISER_NRD_RELAX:
+                raise PtInvalidArgument("the library's Denoiser reads ReLAX's packing only: ReBLUR's (YCoCg, normalised hit distance) is not served")
             if "Diffuse" not in self.textures or "Specular" not in self.textures:
                 raise PtInvalidArgument("nrd needs the Diffuse / Specular textures: create the Renderer with with_denoiser_outputs=True")
             nrd_pack = L.nrd_composition_constants(self.width, self.local_rows, int(nrd), True, nrd_hit_distance)

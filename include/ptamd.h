@@ -727,8 +727,9 @@ int pt_post_download_bloom(PtContext* ctx, uint32_t stage, uint16_t* host_rgba16
  * the NRD composition pass (NRDComposition::Process, Source/NRDComposition.ixx -> Shaders/NRDComposition.hlsl:36-88), which
  * App::ProcessNRD (Source/App.cpp:1595-1688) runs twice around the denoiser: IsPack = 1 turns the path tracer's Diffuse / Specular
  * into the denoiser's input encoding (demodulation by the albedos, hit-distance normalisation, front-end packing), IsPack = 0 unpacks
- * the denoised pair, multiplies the albedos back and adds the result to Radiance. The denoiser itself stays out of scope: a host
- * brings its own between the two calls, which sit between pt_raytrace_render and pt_post_render. NRD.hlsli is not part of the
+ * the denoised pair, multiplies the albedos back and adds the result to Radiance. NRD itself stays out of scope: a host brings its
+ * own denoiser between the two calls, which sit between pt_raytrace_render and pt_post_render, or runs the library's own filter for
+ * the ReLAX packing there (pt_denoiser_process, below). NRD.hlsli is not part of the
  * reference tree: DESIGN.md section 1, "NRD composition", is the arithmetic spec (this library's own after the SDK; parity with the
  * SDK is unpinned; tests/nrdref.py restates it).
  * ------------------------------------------------------------------------------------------ */
@@ -758,6 +759,51 @@ int  pt_nrd_composition_process(PtContext* ctx, const struct PtNRDCompositionCon
  * values (nothing is dereferenced, no GPU): the decision pt_nrd_composition_process itself takes. */
 int  pt_nrd_composition_pixels_per_lane(const struct PtNRDCompositionConstants* constants, const struct PtNRDCompositionTextures* textures);
 void pt_nrd_reblur_hit_distance_defaults(float out[4]);    /* {3, 0.1, 20, -25}; needs no GPU */
+
+/* ------------------------------------------------------------------------------------------
+ * the denoiser for the ReLAX slot between the two calls of the composition pass: this library's own filter in ReLAX's shape (temporal
+ * accumulation with reprojection, a variance estimate, an edge-stopping a-trous wavelet), NOT a port of NRD's ReLAX, whose source is
+ * not part of the reference tree. DESIGN.md section 1, "Denoiser", is the arithmetic spec (unpinned against the SDK; tests/denoiseref.py
+ * restates it bit for bit). It reads the ReLAX-packed pair (radiance, hit distance) and the G-buffer guides and writes a pair in the
+ * same encoding. ReBLUR's packing (YCoCg, normalised hit distance) is not served.
+ * ------------------------------------------------------------------------------------------ */
+struct PtDenoiserSettings {           /* (tagged, not a typedef, like the structs of the composition pass: C callers write `struct PtDenoiserSettings`) */
+    uint32_t RenderSize[2];            /* 1..16384 each */
+    uint32_t MaxAccumulatedFrames;     /* default 30; 1..255 (1 = no temporal reuse) */
+    uint32_t AtrousIterations;         /* default 5; 0..8 (0 = temporal stage only) */
+    float    DepthThreshold;           /* default 0.01; (0, 1]: relative, both for reprojection and for the plane distance */
+    float    NormalCosine;             /* default 0.8; [0, 1): taps whose normals agree less weigh 0 */
+    float    DiffuseLuminanceSigma;    /* default 2;  > 0 */
+    float    SpecularLuminanceSigma;   /* default 1;  > 0 */
+    float    RoughnessFraction;        /* default 0.15; > 0: specular taps, relative roughness difference that weighs 0 */
+    uint32_t _pad[3];
+};                                     /* 48 B */
+struct PtDenoiserTextures {            /* full frame, row-major, RenderSize pixels */
+    const void *Position, *LinearDepth, *NormalRoughness, *MotionVector;   /* as pt_gbuffer_render writes them */
+    const void *NoisyDiffuse, *NoisySpecular;                              /* R16G16B16A16_FLOAT, ReLAX-packed (radiance, hit distance) */
+    void *DenoisedDiffuse, *DenoisedSpecular;                              /* same format; may alias the Noisy pair */
+};
+/* Out-of-range values are refused (PT_ERROR_INVALID_ARGUMENT, the message names the field) and leave the previous settings active.
+ * Settings that differ from the active ones (RenderSize among them) restart the history. */
+int pt_denoiser_set_constants(PtContext* ctx, const struct PtDenoiserSettings* settings);
+/* One frame: 2 + AtrousIterations launches enqueued on the context's stream (1 when AtrousIterations is 0). Needs no scene and ignores
+ * the sharding (the filter is not local: a sharded host runs it on the gathered frame). A pixel whose LinearDepth is not finite is
+ * copied from Noisy* to Denoised* bit for bit. The history (fp32 accumulated colours and hit distances, luminance moments, lengths, the
+ * previous frame's guides, the a-trous ping-pong: 272 B per pixel) is context-owned and grow-only; a failed allocation returns
+ * PT_ERROR_OUT_OF_MEMORY and keeps what was there. It restarts on the first call, after pt_denoiser_reset_history and after a change
+ * of settings. Refused with PT_ERROR_INVALID_ARGUMENT and a message that names the field, nothing written and the history untouched:
+ * a NULL binding, a texture not aligned to its texel (Position 16 bytes, LinearDepth 4, the others 8), a call before
+ * pt_denoiser_set_constants. */
+int pt_denoiser_process(PtContext* ctx, const struct PtDenoiserTextures* textures);
+int pt_denoiser_reset_history(PtContext* ctx);
+/* Test aid: the accumulated length of the diffuse channel per pixel after the last pt_denoiser_process (0: the G-buffer missed), the
+ * first min(capacity_pixels, w * h) of them; *out_w = *out_h = 0 when there is no history. Synchronises. */
+int pt_denoiser_download_history(PtContext* ctx, float* host_length, uint64_t capacity_pixels, uint32_t* out_w, uint32_t* out_h);
+
+/* Two more bits of pt_set_debug_flags, for tests and A/B runs: which form of the a-trous kernel pt_denoiser_process launches. */
+#define PT_DENOISER_FORM_DIRECT 0x800u   /* every a-trous step takes the direct form (each tap a global load) */
+#define PT_DENOISER_FORM_STAGED 0x1000u  /* the staged form (tile + halo through LDS) at every step whose halo fits (1, 2, 4): what the library chooses
+                                            unasked, since it is the faster one there. The same bytes either way */
 
 /* ------------------------------------------------------------------------------------------
  * the mip chain of an R32_FLOAT texture (MipmapGeneration::SetTexture + Process, Source/MipmapGeneration.ixx ->
