@@ -286,6 +286,14 @@ struct Context {
     uint32_t dnParity = 0;                            // which half of each pair the last call wrote
     uint64_t dnFrames = 0;                            // calls since the history was last reset; 0: the next call finds none
 
+    // upscaler (pt_upscale.hip): the history in one grow-only allocation, per output pixel two parities of a float4 (the colour in the
+    // tone-mapped space and the accumulated weight n) and, behind them, two parities of the depth: 40 B
+    PtUpscalerSettings up{}; bool haveUp = false;
+    DeviceBuffer<float4> upHistory;
+    uint32_t upSize[2] = {0, 0};                      // the output frame the history was laid out for by the last pt_upscaler_process
+    uint32_t upParity = 0;                            // which parity the last call wrote
+    uint64_t upFrames = 0;                            // calls since the history was last reset; 0: the next call finds none
+
     // SHARC radiance cache (pt_sharc.hip): per context, also for a context that views another's scene. sharcVoxels[sharcParity] is VoxelData (this
     // frame's deposits, then the resolved cache), the other one PreviousVoxelData; they swap after the query.
     PtSHARCSettings sharcSettings{}; bool haveSharcSettings = false;

@@ -7,6 +7,7 @@
 //           [--post] [--no-bloom] [--bloom-strength S] [--tone-map saturate|reinhard|aces] [--exposure E]
 //           [--hdr [--paper-white N] [--color-rotation hdtv_to_uhdtv|dci_p3_d65_to_uhdtv|hdtv_to_dci_p3_d65]]
 //           [--nrd relax|reblur [--denoise [--denoise-frames-max N] [--denoise-iterations K]]] [--out-radiance file.bin]
+//           [--upscale native|quality|balanced|performance|ultra [--output-size WxH] [--out-upscaled file.bin]]
 //           [--png file.png] [--out-display file.bin] [--scene descriptor.json [--anim-time T [--anim-step DT]]] [--dump-scene file.bin]
 //
 // --anim-time T (with --scene): the animated render objects of the descriptor (RenderObjects[].Animation) are posed at T seconds of their selected
@@ -42,6 +43,13 @@
 // a-trous) runs between the pack and the compose instead of the identity, at its defaults unless --denoise-frames-max (MaxAccumulatedFrames)
 // or --denoise-iterations (AtrousIterations) change them. The timed frames are then one temporal sequence: they carry FrameIndex 0 .. N - 1
 // in that order, and the history starts empty behind the warm-up frame. ReBLUR's packing is refused.
+//
+// --upscale MODE (one unsharded process): the frame is rendered at the render size of that super-resolution mode for the output size
+// (--output-size WxH, else --width x --height; Upscaler::RenderSize) and the library's temporal upscaler (ptamd.hpp Upscaler) brings it to the
+// output size after the NRD block and before --post, which then runs at the output size on the upscaled frame (--png / --out-display are
+// output-size images). The camera keeps the output's aspect and carries the Halton jitter of the frame (Upscaler::Jitter). The timed
+// frames are one temporal sequence: FrameIndex and the jitter index count 0 .. N - 1, and the history starts empty behind the warm-up
+// frame. --out-upscaled writes the last frame's upscaled colour (R16G16B16A16_FLOAT at the output size). Composes with --nrd relax --denoise.
 //
 // --ranks R: one process per GPU. The parent (which never touches a GPU) starts R children `--rank r --world R --id-file F`; rank 0
 // makes the RCCL unique id and leaves it in F, the others pick it up; every rank renders its 16-row bands (BandSharding) and rank 0
@@ -414,6 +422,7 @@ int main(int argc, char** argv)
     bool animate = false; double animTime = 0.0, animStep = 0.0;
     std::string nrd, radiancePath;
     bool denoise = false; uint32_t denoiseFramesMax = 30, denoiseIterations = 5;
+    std::string upscale, outputSize, upscaledPath;
     for (int i = 1; i < argc; i++) {
         std::string k = argv[i];
         if (k == "--di") { di = true; continue; }                  // the flags without a value
@@ -445,6 +454,7 @@ int main(int argc, char** argv)
         else if (k == "--out-display") displayPath = v;
         else if (k == "--denoise-frames-max") denoiseFramesMax = atoi(v); else if (k == "--denoise-iterations") denoiseIterations = atoi(v);
         else if (k == "--nrd") nrd = v; else if (k == "--out-radiance") radiancePath = v;
+        else if (k == "--upscale") upscale = v; else if (k == "--output-size") outputSize = v; else if (k == "--out-upscaled") upscaledPath = v;
         else if (k == "--anim-time") { animate = true; animTime = atof(v); } else if (k == "--anim-step") animStep = atof(v);
     }
     post = post || !pngPath.empty() || !displayPath.empty();
@@ -455,6 +465,21 @@ int main(int argc, char** argv)
     }
     if (ranks && !sharded) return launch_ranks(argc, argv, ranks);
     try {
+        // ---- --upscale: W x H becomes the render size of the mode for the output size
+        const bool upscaling = !upscale.empty();
+        uint32_t outW = W, outH = H;
+        if (upscaling) {
+            if (sharded) throw std::invalid_argument("--upscale needs one unsharded process");
+            Upscaler::SuperResolutionMode mode;
+            if (upscale == "native") mode = PT_SUPER_RESOLUTION_NATIVE; else if (upscale == "quality") mode = PT_SUPER_RESOLUTION_QUALITY;
+            else if (upscale == "balanced") mode = PT_SUPER_RESOLUTION_BALANCED; else if (upscale == "performance") mode = PT_SUPER_RESOLUTION_PERFORMANCE;
+            else if (upscale == "ultra") mode = PT_SUPER_RESOLUTION_ULTRA_PERFORMANCE;
+            else throw std::invalid_argument("--upscale: native, quality, balanced, performance or ultra");
+            if (!outputSize.empty() && sscanf(outputSize.c_str(), "%ux%u", &outW, &outH) != 2) throw std::invalid_argument("--output-size: WxH");
+            const uint32_t output[2] = { outW, outH }; uint32_t render[2];
+            Upscaler::RenderSize(mode, output, render);
+            W = render[0]; H = render[1];
+        } else if (!outputSize.empty() || !upscaledPath.empty()) throw std::invalid_argument("--output-size and --out-upscaled need --upscale");
         int deviceCount = 0;
         HIP_OK(hipGetDeviceCount(&deviceCount));
         if ((int)world > deviceCount) { fprintf(stderr, "pt_demo: %u ranks need %u GPUs, %d visible\n", world, world, deviceCount); return 4; }
@@ -548,12 +573,13 @@ int main(int argc, char** argv)
         PtObjectData* dObjects = upload(objectData); PtInstanceData* dInstances = upload(instanceData);
 
         // ---- camera (scenes.py:make_camera: hfov 90, near 0.01, far inf) and scene data
-        PtCamera cam = make_camera(scene, (double)W / (double)H);
+        PtCamera cam = make_camera(scene, (double)outW / (double)outH);
         PtSceneData sd{}; sd.IsStatic = scene.animations.empty() ? 1 : 0; sd.EnvironmentLightTextureDescriptor = ~0u;
         memcpy(sd.EnvironmentLightColor, scene.envColor, 16); memcpy(sd.EnvironmentLightTransform, scene.envTransform, 48);
 
         // ---- textures (Source/App.cpp:438-455 formats)
         const size_t px_ = (size_t)W * std::max(localRows, 1u), fullPx = (size_t)W * H;     // a rank's textures hold its own rows
+        const size_t outPx = (size_t)outW * outH;                  // the frame the post chain sees: the upscaler's output, else the render size
         PtTextures tx{}; float* radianceF32 = nullptr;
         auto alloc = [&](size_t bytes) { void* p = nullptr; HIP_OK(hipMalloc(&p, bytes)); HIP_OK(hipMemset(p, 0, bytes)); return p; };
         tx.Position = alloc(px_ * 16); tx.FlatNormal = alloc(px_ * 4); tx.GeometricNormal = alloc(px_ * 4); tx.LinearDepth = alloc(px_ * 4);
@@ -572,7 +598,7 @@ int main(int argc, char** argv)
         const bool runPost = post && rank == 0;
         if (post) {
             if (hdr && !pngPath.empty()) throw std::invalid_argument("--png writes an SDR image: drop --hdr");
-            PostProcessing::Settings ps; ps.RenderSize[0] = W; ps.RenderSize[1] = H;
+            PostProcessing::Settings ps; ps.RenderSize[0] = outW; ps.RenderSize[1] = outH;
             ps.Bloom.IsEnabled = bloom; ps.Bloom.Strength = bloomStrength; ps.IsHDREnabled = hdr;
             using Op = PostProcessing::ToneMapOperator; using Rot = PostProcessing::ColorRotation;
             if (toneMap == "saturate") ps.ToneMapping.NonHDR.Operator = Op::Saturate;
@@ -587,9 +613,9 @@ int main(int argc, char** argv)
             postProcessing.SetConstants(ps);
             if (runPost) {
                 postProcessing.Textures.Radiance = sharded ? fullRadiance : tx.Radiance;
-                postProcessing.Textures.Color = alloc(fullPx * 8);
-                postProcessing.Textures.BackBuffer = alloc(fullPx * 4);
-                postProcessing.Textures.Display8 = alloc(fullPx * 4);
+                postProcessing.Textures.Color = alloc(outPx * 8);
+                postProcessing.Textures.BackBuffer = alloc(outPx * 4);
+                postProcessing.Textures.Display8 = alloc(outPx * 4);
             }
         }
         float* fullRadianceF32 = sharded && rank == 0 && !out.empty() ? (float*)alloc(fullPx * 16) : nullptr;
@@ -619,6 +645,13 @@ int main(int argc, char** argv)
             s.MaxAccumulatedFrames = denoiseFramesMax; s.AtrousIterations = denoiseIterations;
             denoiser.SetConstants(s);
         } else if (nrdDenoiser) fprintf(stderr, "pt_demo: --nrd %s: the denoiser between the pack and the compose is the identity\n", nrd.c_str());
+        Upscaler upscaler(commandList);
+        if (upscaling) {                                            // App.cpp:1532-1541: the super-resolution step, ahead of Bloom / ToneMap
+            Upscaler::Settings s; s.RenderSize[0] = W; s.RenderSize[1] = H; s.OutputSize[0] = outW; s.OutputSize[1] = outH;
+            upscaler.SetConstants(s);
+            upscaler.Textures = { tx.Radiance, tx.LinearDepth, tx.MotionVector, alloc(outPx * 8) };
+            if (runPost) postProcessing.Textures.Radiance = upscaler.Textures.Color;
+        }
         SHARC sharc(commandList);
         Raytracing::SHARCSettings sharcSettings; sharcSettings.DownscaleFactor = sharcDownscale;
         if (useSharc) { sharc.Constants.SceneScale = sceneScale; sharc.Configure(); }
@@ -704,6 +737,12 @@ int main(int argc, char** argv)
         PtCounters counters{};
         double ms = 0;
         auto renderFrame = [&](uint32_t frameIndex) {
+            float jitter[2] = { 0.0f, 0.0f };
+            if (upscaling) {                                        // App.cpp:556: the frame's Halton jitter, in the camera every pass reads
+                const uint32_t render[2] = { W, H }, output[2] = { outW, outH };
+                Upscaler::Jitter(frameIndex, render, output, jitter);
+                cam.Jitter[0] = jitter[0]; cam.Jitter[1] = jitter[1];
+            }
             if (restir && !firstFrame) {                            // App.cpp:629-634: this frame's G-buffer goes where last frame's was
                 std::swap(tx.GeometricNormal, prev.PreviousGeometricNormal); std::swap(tx.LinearDepth, prev.PreviousLinearDepth);
                 std::swap(tx.BaseColorMetalness, prev.PreviousBaseColorMetalness); std::swap(tx.NormalRoughness, prev.PreviousNormalRoughness);
@@ -736,19 +775,21 @@ int main(int argc, char** argv)
                 nc.IsPack = false; nrdComposition.Process(commandList, nc);
             }
             if (sharded) sharding.GatherBands(commandList, tx.Radiance, fullRadiance, W, H, 8);
+            if (upscaling) upscaler.Process(commandList, jitter);
             if (runPost) postProcessing.Render(commandList);
         };
         animateFrame();
         renderFrame(12345);                                         // warm-up
         commandList.End();
         if (denoise) denoiser.ResetHistory();                       // the warm-up frame is not part of the sequence
+        if (upscaling) upscaler.ResetHistory();
         // timed run: frames 1..N back to back
         ThrowIfFailed(commandList.Context, pt_reset_counters(commandList.Context));
         const auto t0 = std::chrono::steady_clock::now();
         for (uint32_t f = 0; f < frames; f++) {                    // the last frame has FrameIndex 0 (dumped below)
             if (f) for (AnimationCollection* c : collectionList) (*c)[c->GetSelectedIndex()].Tick(animStep);
             animateFrame();
-            renderFrame(denoise ? f : frames - 1 - f);              // a denoised run is a temporal sequence: FrameIndex counts up
+            renderFrame(denoise || upscaling ? f : frames - 1 - f); // a denoised or upscaled run is a temporal sequence: FrameIndex counts up
         }
         commandList.End();
         ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -790,17 +831,24 @@ int main(int argc, char** argv)
             if (!fp || fwrite(host.data(), 8, fullPx, fp) != fullPx) { fprintf(stderr, "cannot write %s\n", radiancePath.c_str()); if (fp) fclose(fp); return 3; }
             fclose(fp);
         }
+        if (upscaling && !upscaledPath.empty()) {                   // the upscaler's Color of the last frame
+            std::vector<uint16_t> host(outPx * 4);
+            HIP_OK(hipMemcpy(host.data(), upscaler.Textures.Color, outPx * 8, hipMemcpyDeviceToHost));
+            FILE* fp = fopen(upscaledPath.c_str(), "wb");
+            if (!fp || fwrite(host.data(), 8, outPx, fp) != outPx) { fprintf(stderr, "cannot write %s\n", upscaledPath.c_str()); if (fp) fclose(fp); return 3; }
+            fclose(fp);
+        }
         if (runPost && !displayPath.empty()) {                      // the presented back buffer of the last frame
-            std::vector<uint32_t> words(fullPx);
-            HIP_OK(hipMemcpy(words.data(), postProcessing.Textures.BackBuffer, fullPx * 4, hipMemcpyDeviceToHost));
+            std::vector<uint32_t> words(outPx);
+            HIP_OK(hipMemcpy(words.data(), postProcessing.Textures.BackBuffer, outPx * 4, hipMemcpyDeviceToHost));
             FILE* fp = fopen(displayPath.c_str(), "wb");
-            if (!fp || fwrite(words.data(), 4, fullPx, fp) != fullPx) { fprintf(stderr, "cannot write %s\n", displayPath.c_str()); if (fp) fclose(fp); return 3; }
+            if (!fp || fwrite(words.data(), 4, outPx, fp) != outPx) { fprintf(stderr, "cannot write %s\n", displayPath.c_str()); if (fp) fclose(fp); return 3; }
             fclose(fp);
         }
         if (runPost && !pngPath.empty()) {
-            std::vector<uint8_t> rgba(fullPx * 4);
-            HIP_OK(hipMemcpy(rgba.data(), postProcessing.Textures.Display8, fullPx * 4, hipMemcpyDeviceToHost));
-            if (!ptpng::write_rgb(pngPath, rgba.data(), W, H)) { fprintf(stderr, "cannot write %s\n", pngPath.c_str()); return 3; }
+            std::vector<uint8_t> rgba(outPx * 4);
+            HIP_OK(hipMemcpy(rgba.data(), postProcessing.Textures.Display8, outPx * 4, hipMemcpyDeviceToHost));
+            if (!ptpng::write_rgb(pngPath, rgba.data(), outW, outH)) { fprintf(stderr, "cannot write %s\n", pngPath.c_str()); return 3; }
         }
     } catch (const std::exception& e) {
         fprintf(stderr, "pt_demo: %s\n", e.what());

@@ -10,6 +10,7 @@
 //     struct PostProcessing      App::PostProcessGraphics with Denoiser::None (Source/App.cpp:1506-1571): Bloom, Merge, ToneMap, CopyTexture
 //     struct NRDComposition      Source/NRDComposition.ixx (the pack and compose passes of App::ProcessNRD, Source/App.cpp:1595-1688)
 //     struct Denoiser            the library's own filter for the ReLAX slot between them (where the reference calls NRD::Denoise)
+//     struct Upscaler            the library's own temporal upscaler for the super-resolution step (where the reference calls DLSS or XeSS)
 // Error behaviour: a failing status becomes the exception type the reference throws at the same place
 // (std::invalid_argument for argument checks, std::system_error otherwise: Source/ErrorHelpers.ixx:16-32).
 // Header-only, plain C++20 (std::span), no HIP headers needed by the including translation unit.
@@ -656,6 +657,59 @@ struct Denoiser {
         std::vector<float> out((size_t)width * height);
         if (!out.empty()) ThrowIfFailed(m_context, pt_denoiser_download_history(m_context, out.data(), out.size(), &width, &height));
         return out;
+    }
+
+private:
+    PtContext* m_context;
+};
+
+// The library's own temporal upscaler for the super-resolution step of App::PostProcessGraphics (Source/App.cpp:1532-1541), between the
+// denoiser and Bloom / ToneMap, where the reference calls DLSS or XeSS (pt_upscaler_*; DESIGN.md section 1, "Upscaler"): a temporal
+// accumulating upscaler from RenderSize to OutputSize. Not a port of either SDK. Process takes the Camera.Jitter the frame was rendered
+// with (as it stands in PtCamera); Color then is the post chain's Radiance. Runs on the full frame of an unsharded context.
+struct Upscaler {
+    using SuperResolutionMode = PtSuperResolutionMode;                     // Source/Upscaler.ixx
+
+    struct Settings {
+        uint32_t RenderSize[2]{}, OutputSize[2]{};                          // RenderSize <= OutputSize <= 4 RenderSize per axis
+        uint32_t MaxAccumulatedFrames = 16;                                 // 1..255
+        float KernelRadius = 1, DepthThreshold = 0.01f;                     // [0.75, 2] | (0, 1]
+    };
+
+    PtUpscalerTextures Textures{};
+
+    explicit Upscaler(CommandList& commandList) : m_context(commandList.Context) {}
+
+    void SetConstants(const Settings& settings)
+    {
+        PtUpscalerSettings s{};
+        s.RenderSize[0] = settings.RenderSize[0]; s.RenderSize[1] = settings.RenderSize[1];
+        s.OutputSize[0] = settings.OutputSize[0]; s.OutputSize[1] = settings.OutputSize[1];
+        s.MaxAccumulatedFrames = settings.MaxAccumulatedFrames; s.KernelRadius = settings.KernelRadius; s.DepthThreshold = settings.DepthThreshold;
+        ThrowIfFailed(m_context, pt_upscaler_set_constants(m_context, &s));
+    }
+
+    void Process(CommandList& commandList, const float (&jitter)[2]) { ThrowIfFailed(commandList.Context, pt_upscaler_process(commandList.Context, &Textures, jitter)); }
+
+    void ResetHistory() { ThrowIfFailed(m_context, pt_upscaler_reset_history(m_context)); }
+
+    // the accumulated weight n per output pixel after the last Process, row-major; empty when there is no history. Synchronises.
+    std::vector<float> DownloadHistory(uint32_t& width, uint32_t& height)
+    {
+        ThrowIfFailed(m_context, pt_upscaler_download_history(m_context, nullptr, 0, &width, &height));
+        std::vector<float> out((size_t)width * height);
+        if (!out.empty()) ThrowIfFailed(m_context, pt_upscaler_download_history(m_context, out.data(), out.size(), &width, &height));
+        return out;
+    }
+
+    // host only: the render size of a mode for an output size, and the Camera.Jitter of a frame
+    static void RenderSize(SuperResolutionMode mode, const uint32_t (&output)[2], uint32_t (&render)[2])
+    {
+        if (pt_upscaler_render_size((uint32_t)mode, output, render) != PT_OK) throw std::invalid_argument("Upscaler::RenderSize: a mode or an output size out of range");
+    }
+    static void Jitter(uint64_t frameIndex, const uint32_t (&render)[2], const uint32_t (&output)[2], float (&jitter)[2])
+    {
+        if (pt_upscaler_jitter(frameIndex, render, output, jitter) != PT_OK) throw std::invalid_argument("Upscaler::Jitter: a size out of range");
     }
 
 private:

@@ -395,6 +395,97 @@ def denoiser_settings(width, height, **overrides):
     return check_denoiser_settings(s)
 
 
+UPSCALER_SETTINGS = np.dtype({  # PtUpscalerSettings, 48 B
+    "names": ["RenderSize", "OutputSize", "MaxAccumulatedFrames", "KernelRadius", "DepthThreshold", "_pad"],
+    "formats": [("<u4", 2), ("<u4", 2), "<u4", "<f4", "<f4", ("<u4", 5)],
+    "offsets": [0, 8, 16, 20, 24, 28], "itemsize": 48})
+# PtUpscalerTextures member order: four pointers
+UPSCALER_TEXTURES = ["Radiance", "LinearDepth", "MotionVector", "Color"]
+UPSCALER_DEFAULTS = {"MaxAccumulatedFrames": 16, "KernelRadius": 1.0, "DepthThreshold": 0.01}
+UPSCALER_MAX_SIZE = 16384
+# PtSuperResolutionMode, SuperResolutionMode of Source/Upscaler.ixx in its order
+SUPER_RESOLUTION_AUTO, SUPER_RESOLUTION_NATIVE, SUPER_RESOLUTION_QUALITY, SUPER_RESOLUTION_BALANCED = 0, 1, 2, 3
+SUPER_RESOLUTION_PERFORMANCE, SUPER_RESOLUTION_ULTRA_PERFORMANCE = 4, 5
+SUPER_RESOLUTION_RATIO10 = {SUPER_RESOLUTION_NATIVE: 10, SUPER_RESOLUTION_QUALITY: 15, SUPER_RESOLUTION_BALANCED: 17,
+                            SUPER_RESOLUTION_PERFORMANCE: 20, SUPER_RESOLUTION_ULTRA_PERFORMANCE: 30}
+
+
+def check_upscaler_settings(s):
+    """The range checks of pt_upscaler_set_constants, on the float32 values the library receives: ValueError where it answers
+    PT_ERROR_INVALID_ARGUMENT."""
+    s = np.asarray(s).reshape(())
+    render, output = [int(v) for v in s["RenderSize"]], [int(v) for v in s["OutputSize"]]
+    for name, size in (("RenderSize", render), ("OutputSize", output)):
+        if not all(1 <= v <= UPSCALER_MAX_SIZE for v in size):
+            raise ValueError(f"{name} must be 1..{UPSCALER_MAX_SIZE} on both axes")
+    if not all(r <= o <= 4 * r for r, o in zip(render, output)):
+        raise ValueError("OutputSize must be RenderSize..4 RenderSize on both axes")
+    if not 1 <= int(s["MaxAccumulatedFrames"]) <= 255:
+        raise ValueError("MaxAccumulatedFrames must be 1..255")
+    if not 0.75 <= float(np.float32(s["KernelRadius"])) <= 2.0:
+        raise ValueError("KernelRadius must be in [0.75, 2]")
+    if not 0.0 < float(np.float32(s["DepthThreshold"])) <= 1.0:
+        raise ValueError("DepthThreshold must be in (0, 1]")
+    return s
+
+
+def upscaler_settings(render_size, output_size, **overrides):
+    """PtUpscalerSettings with the defaults of UPSCALER_DEFAULTS; overrides by field name. Refuses what pt_upscaler_set_constants refuses."""
+    s = np.zeros((), UPSCALER_SETTINGS)
+    for name, size in (("RenderSize", render_size), ("OutputSize", output_size)):
+        if len(size) != 2 or not all(0 <= int(v) <= 0xFFFFFFFF for v in size):
+            raise ValueError(f"{name} is not a pair of 32-bit unsigned values")
+        s[name] = tuple(int(v) for v in size)
+    values = dict(UPSCALER_DEFAULTS)
+    for k, v in overrides.items():
+        if k not in values:
+            raise ValueError(f"PtUpscalerSettings has no field {k}")
+        values[k] = v
+    for k, v in values.items():
+        if s.dtype[k].kind == "u" and not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{k} is not a 32-bit unsigned value")
+        s[k] = v
+    return check_upscaler_settings(s)
+
+
+def upscaler_render_size(mode, output_size):
+    """pt_upscaler_render_size restated: the render size of a PtSuperResolutionMode for an output size, in integers. No GPU."""
+    mode, output = int(mode), [int(v) for v in output_size]
+    if not SUPER_RESOLUTION_AUTO <= mode <= SUPER_RESOLUTION_ULTRA_PERFORMANCE:
+        raise ValueError("mode must be a PtSuperResolutionMode value")
+    if len(output) != 2 or not all(1 <= v <= UPSCALER_MAX_SIZE for v in output):
+        raise ValueError(f"output must be 1..{UPSCALER_MAX_SIZE} on both axes")
+    if mode == SUPER_RESOLUTION_AUTO:                  # by the pixel count of the output (App.cpp:1427-1440)
+        pixels = output[0] * output[1]
+        mode = (SUPER_RESOLUTION_NATIVE if pixels <= 1280 * 800 else SUPER_RESOLUTION_QUALITY if pixels <= 1920 * 1200
+                else SUPER_RESOLUTION_BALANCED if pixels <= 2560 * 1600 else SUPER_RESOLUTION_PERFORMANCE if pixels <= 3840 * 2400
+                else SUPER_RESOLUTION_ULTRA_PERFORMANCE)
+    r10 = SUPER_RESOLUTION_RATIO10[mode]
+    return tuple(max(1, (v * 10 + r10 // 2) // r10) for v in output)
+
+
+def upscaler_jitter(frame_index, render_size, output_size):
+    """pt_upscaler_jitter restated bit for bit: the Halton point (bases 2 and 3) of index frame_index % count + 1 minus 0.5, as two
+    float32; count = ceil(8 (ow / rw) (oh / rh)) in float32. No GPU."""
+    f32 = np.float32
+    render, output = [int(v) for v in render_size], [int(v) for v in output_size]
+    if len(render) != 2 or len(output) != 2 or not all(1 <= v <= UPSCALER_MAX_SIZE for v in render + output):
+        raise ValueError(f"render and output must be 1..{UPSCALER_MAX_SIZE} on both axes")
+    scaled = f32(f32(8) * f32(f32(output[0]) / f32(render[0])))
+    count = int(np.ceil(f32(scaled * f32(f32(output[1]) / f32(render[1])))))
+    index = int(frame_index) % count + 1
+    out = []
+    for base in (2, 3):
+        inv = f32(1) / f32(base)
+        weight, value, i = inv, f32(0), index
+        while i > 0:
+            value = f32(value + f32(f32(i % base) * weight))
+            weight = f32(weight * inv)
+            i //= base
+        out.append(f32(value - f32(0.5)))
+    return tuple(out)
+
+
 SHARC_SETTINGS = np.dtype({  # PtSHARCSettings: SHARC::Constants + Raytracing::SHARCSettings (Source/MyAppData.h:250-262)
     "names": ["AccumulationFrames", "MaxStaleFrames", "SceneScale", "IsAntiFireflyEnabled", "DownscaleFactor", "RoughnessThreshold",
               "IsHashGridVisualizationEnabled"],

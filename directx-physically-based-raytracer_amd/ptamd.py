@@ -33,6 +33,8 @@ EXPORTS = [
     "pt_post_set_constants", "pt_post_render", "pt_post_download_bloom",
     "pt_nrd_composition_process", "pt_nrd_composition_pixels_per_lane", "pt_nrd_reblur_hit_distance_defaults",
     "pt_denoiser_set_constants", "pt_denoiser_process", "pt_denoiser_reset_history", "pt_denoiser_download_history",
+    "pt_upscaler_set_constants", "pt_upscaler_process", "pt_upscaler_reset_history", "pt_upscaler_download_history",
+    "pt_upscaler_render_size", "pt_upscaler_jitter",
     "pt_anim_create_rig", "pt_anim_release_rig", "pt_anim_create_object", "pt_anim_release_object", "pt_anim_evaluate",
     "pt_anim_skeletal_transforms", "pt_anim_download_globals", "pt_anim_download_skeletal", "pt_anim_debug_slerp",
     "pt_sharc_configure", "pt_sharc_set_constants", "pt_raytrace_render_sharc", "pt_sharc_reset", "pt_sharc_download",
@@ -81,6 +83,10 @@ class NRDCompositionTextures(C.Structure):   # PtNRDCompositionTextures: nine po
 
 class DenoiserTextures(C.Structure):         # PtDenoiserTextures: eight pointers
     _fields_ = [(n, C.c_void_p) for n in L.DENOISER_TEXTURES]
+
+
+class UpscalerTextures(C.Structure):         # PtUpscalerTextures: four pointers
+    _fields_ = [(n, C.c_void_p) for n in L.UPSCALER_TEXTURES]
 
 
 class Sharding(C.Structure):
@@ -232,6 +238,12 @@ def load_library():
         lib.pt_denoiser_process.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_denoiser_reset_history.argtypes = [C.c_void_p]
         lib.pt_denoiser_download_history.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.pt_upscaler_set_constants.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_upscaler_process.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        lib.pt_upscaler_reset_history.argtypes = [C.c_void_p]
+        lib.pt_upscaler_download_history.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.pt_upscaler_render_size.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.pt_upscaler_jitter.argtypes = [C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
         lib.pt_sharc_configure.argtypes = [C.c_void_p, C.c_uint32]
         lib.pt_sharc_set_constants.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_raytrace_render_sharc.argtypes = [C.c_void_p, C.c_void_p]
@@ -1144,6 +1156,68 @@ class Denoiser:
         return noisy_diffuse, noisy_specular
 
 
+def upscaler_render_size(mode, output_size):
+    """pt_upscaler_render_size: the render size (w, h) of a PtSuperResolutionMode (layouts.SUPER_RESOLUTION_*) for an output size. No GPU."""
+    out, size = (C.c_uint32 * 2)(), (C.c_uint32 * 2)(*[int(v) for v in output_size])
+    if not 0 <= int(mode) <= 0xFFFFFFFF or load_library().pt_upscaler_render_size(int(mode), size, out) != 0:
+        raise PtInvalidArgument("mode must be a PtSuperResolutionMode value and output 1..16384 on both axes")
+    return out[0], out[1]
+
+
+def upscaler_jitter(frame_index, render_size, output_size):
+    """pt_upscaler_jitter: the Camera.Jitter of frame `frame_index` as two float32, in [-0.5, 0.5). No GPU."""
+    out = (C.c_float * 2)()
+    render, output = (C.c_uint32 * 2)(*[int(v) for v in render_size]), (C.c_uint32 * 2)(*[int(v) for v in output_size])
+    if load_library().pt_upscaler_jitter(int(frame_index), render, output, out) != 0:
+        raise PtInvalidArgument("render and output must be 1..16384 on both axes")
+    return np.float32(out[0]), np.float32(out[1])
+
+
+class Upscaler:
+    """The library's own temporal upscaler for the super-resolution slot between the denoiser and the post chain (pt_upscaler_*;
+    DESIGN.md section 1, "Upscaler"): a temporal accumulating upscaler from RenderSize to OutputSize, where the reference loads DLSS or
+    XeSS. Not a port of either. Process takes the textures by the names of layouts.UPSCALER_TEXTURES (a missing name is an unbound
+    texture) and the Camera.Jitter the frame was rendered with. Runs on the full frame of an unsharded context. No scene is needed."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.Textures = {}
+        self._settings = None
+
+    @property
+    def settings(self):
+        """the PtUpscalerSettings record last accepted, or None"""
+        return self._settings
+
+    def SetConstants(self, settings):
+        """settings: PtUpscalerSettings (layouts.upscaler_settings)."""
+        k = np.array(settings)
+        if k.dtype != L.UPSCALER_SETTINGS or k.size != 1:
+            raise PtInvalidArgument("settings must be one PtUpscalerSettings record (layouts.upscaler_settings)")
+        k = np.ascontiguousarray(k).reshape(())
+        self.ctx.check(self.ctx.lib.pt_upscaler_set_constants(self.ctx.handle, C.c_void_p(k.ctypes.data)))
+        self._settings = k
+
+    def Process(self, jitter, textures=None):
+        tex = self.Textures if textures is None else textures
+        t = UpscalerTextures(*[_ptr(tex.get(n)) for n in L.UPSCALER_TEXTURES])
+        j = (C.c_float * 2)(float(jitter[0]), float(jitter[1]))
+        self.ctx.check(self.ctx.lib.pt_upscaler_process(self.ctx.handle, C.addressof(t), j))
+
+    def ResetHistory(self):
+        self.ctx.check(self.ctx.lib.pt_upscaler_reset_history(self.ctx.handle))
+
+    def DownloadHistory(self):
+        """The accumulated weight n per output pixel after the last Process: float32 (h, w); empty (0, 0) when there is no history.
+        Synchronises."""
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        self.ctx.check(self.ctx.lib.pt_upscaler_download_history(self.ctx.handle, None, 0, C.byref(w), C.byref(h)))
+        out = np.zeros((h.value, w.value), np.float32)
+        if out.size:
+            self.ctx.check(self.ctx.lib.pt_upscaler_download_history(self.ctx.handle, C.c_void_p(out.ctypes.data), out.size, C.byref(w), C.byref(h)))
+        return out
+
+
 class SHARC:
     """Mirror of `struct SHARC` (Source/SHARC.ixx) and of the Raytracing::Render overload that takes it: Configure allocates the context's
     cache, SetConstants takes PtSHARCSettings (layouts.sharc_settings), Render runs clear, update, resolve, query and the swap with the
@@ -1251,9 +1325,24 @@ class Renderer:
             self._denoiser = d
         return self._denoiser
 
+    def upscaler(self, output_w, output_h, **overrides):
+        """A new Upscaler from this renderer's size to output_w x output_h, bound to the renderer's Radiance, LinearDepth and
+        MotionVector, with layouts.upscaler_settings' defaults (overrides by field name): render(..., upscale=that). It writes
+        textures["Upscaled"]. Unsharded contexts only: the pass needs the whole frame."""
+        if getattr(self.ctx, "sharding", (0, 1, 16))[1] > 1:
+            raise PtInvalidArgument("the upscaler needs the whole frame: the context is sharded (run Upscaler on the gathered textures)")
+        u = Upscaler(self.ctx)
+        u.Textures = self.textures
+        u.SetConstants(L.upscaler_settings((self.width, self.height), (output_w, output_h), **overrides))
+        return u
+
     def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None, post=None, sharc=None, di_visibility=None, di_pairwise=None,
-               di_regir_layout=None, di_brdf=None, nrd=None, denoise=None, nrd_hit_distance=None, di_pdf_mipmap=None):
-        """di_pdf_mipmap: True / False for DirectLighting.SetPdfMipmap ahead of the DI pass, or None: the context's setting is left alone.
+               di_regir_layout=None, di_brdf=None, nrd=None, denoise=None, nrd_hit_distance=None, di_pdf_mipmap=None, upscale=None):
+        """upscale: an Upscaler (self.upscaler(output_w, output_h)) to run the super-resolution step of App::PostProcessGraphics
+        (App.cpp:1532-1541) after the NRD block and before post: it reads the frame's Radiance, LinearDepth and MotionVector and the
+        camera's Jitter and writes textures["Upscaled"] at its OutputSize; post's RenderSize must then be that OutputSize and the post
+        chain reads Upscaled as its Radiance. None: no such step, the frame as it was.
+        di_pdf_mipmap: True / False for DirectLighting.SetPdfMipmap ahead of the DI pass, or None: the context's setting is left alone.
         nrd: layouts.DENOISER_NRD_REBLUR / _RELAX (it must be settings' Denoiser) to run App::ProcessNRD (App.cpp:1595-1688) after the
         frame and before post: the NRD composition pass packs textures["Diffuse"] / ["Specular"] in place, denoise(noisy_diffuse,
         noisy_specular) -> (denoised_diffuse, denoised_specular) takes and returns device tensors of their shape (None: the identity,
@@ -1280,8 +1369,19 @@ class Renderer:
             p = np.array(post).reshape(())
             if getattr(self.ctx, "sharding", (0, 1, 16))[1] > 1:
                 raise PtInvalidArgument("post-processing needs the whole frame: run PostProcessing on the gathered Radiance of a sharded render")
-            if tuple(int(v) for v in p["RenderSize"]) != (self.width, self.height):
+            if upscale is None and tuple(int(v) for v in p["RenderSize"]) != (self.width, self.height):
                 raise PtInvalidArgument("post-processing RenderSize differs from the renderer's size")
+        out_w = out_h = None
+        if upscale is not None:
+            if not isinstance(upscale, Upscaler) or upscale.settings is None:
+                raise PtInvalidArgument("upscale must be an Upscaler whose constants are set (Renderer.upscaler)")
+            if getattr(self.ctx, "sharding", (0, 1, 16))[1] > 1:
+                raise PtInvalidArgument("the upscaler needs the whole frame: the context is sharded")
+            if tuple(int(v) for v in upscale.settings["RenderSize"]) != (self.width, self.height):
+                raise PtInvalidArgument("the upscaler's RenderSize differs from the renderer's size")
+            out_w, out_h = (int(v) for v in upscale.settings["OutputSize"])
+            if post is not None and tuple(int(v) for v in p["RenderSize"]) != (out_w, out_h):
+                raise PtInvalidArgument("post-processing RenderSize differs from the upscaler's OutputSize")
         if self.di_history and self._rendered:
             for n in L.DI_PREVIOUS_TEXTURES:
                 c = n[len("Previous"):]
@@ -1338,9 +1438,19 @@ class Renderer:
             tex["DenoisedDiffuse"], tex["DenoisedSpecular"] = dd, ds
             self.nrd.Process(tex, nrd_compose)
             self._nrd_keep = (dd, ds)                                     # the compose is enqueued: its inputs live until the next frame
+        if upscale is not None:                                           # App.cpp:1532-1541: between the denoiser and Bloom / ToneMap
+            t = self.textures
+            if "Upscaled" not in t or tuple(t["Upscaled"].shape) != (out_h, out_w, 4):
+                t["Upscaled"] = _torch().zeros((out_h, out_w, 4), dtype=t["Radiance"].dtype, device=self.scene.device)
+            jitter = np.array(self.gbuffer.GPUBuffers["Camera"]).reshape(())["Jitter"]
+            # the context's settings are this upscaler's (the same again keep the history): they size what the call writes
+            upscale.SetConstants(upscale.settings)
+            upscale.Process(jitter, {"Radiance": t["Radiance"], "LinearDepth": t["LinearDepth"], "MotionVector": t["MotionVector"],
+                                     "Color": t["Upscaled"]})
         if post is not None:                                              # App.cpp:1506-1571, after Raytracing::Render
-            if "Color" not in self.textures:
-                self.textures.update(alloc_post_textures(self.width, self.height, self.scene.device))
+            pw, ph = (out_w, out_h) if upscale is not None else (self.width, self.height)
+            if "Color" not in self.textures or tuple(self.textures["Color"].shape[:2]) != (ph, pw):
+                self.textures.update(alloc_post_textures(pw, ph, self.scene.device))
             self.post.SetConstants(post)
-            self.post.Render(self.textures)
+            self.post.Render(self.textures if upscale is None else dict(self.textures, Radiance=self.textures["Upscaled"]))
         self._rendered = True

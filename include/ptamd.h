@@ -806,6 +806,58 @@ int pt_denoiser_download_history(PtContext* ctx, float* host_length, uint64_t ca
                                             unasked, since it is the faster one there. The same bytes either way */
 
 /* ------------------------------------------------------------------------------------------
+ * the temporal upscaler for the super-resolution slot of App::PostProcessGraphics (Source/App.cpp:1532-1541), between the denoiser and
+ * Bloom / ToneMap: this library's own temporal accumulating upscaler (TAAU) from RenderSize to OutputSize, NOT a port of DLSS or XeSS,
+ * which the reference loads there (closed SDKs, not part of its tree). DESIGN.md section 1, "Upscaler", is the arithmetic spec (unpinned
+ * against either SDK; tests/upscaleref.py restates it bit for bit). It reads what the reference hands its upscaler: Radiance,
+ * MotionVector and LinearDepth at RenderSize and the frame's Camera.Jitter (as it stands in PtCamera: not negated), and writes Color at
+ * OutputSize, which then is the post chain's Radiance.
+ * ------------------------------------------------------------------------------------------ */
+struct PtUpscalerSettings {            /* (tagged, not a typedef, like PtDenoiserSettings: C callers write `struct PtUpscalerSettings`) */
+    uint32_t RenderSize[2];            /* 1..16384 each */
+    uint32_t OutputSize[2];            /* 1..16384 each; RenderSize <= OutputSize <= 4 RenderSize per axis */
+    uint32_t MaxAccumulatedFrames;     /* default 16; 1..255 (1 = no temporal reuse) */
+    float    KernelRadius;             /* default 1; [0.75, 2]: the radius of the reconstruction kernel, in render pixels */
+    float    DepthThreshold;           /* default 0.01; (0, 1]: relative depth difference beyond which a history tap is rejected */
+    uint32_t _pad[5];
+};                                     /* 48 B */
+struct PtUpscalerTextures {            /* full frames, row-major */
+    const void *Radiance, *LinearDepth, *MotionVector;   /* RenderSize: R16G16B16A16_FLOAT (alpha ignored), R32_FLOAT, R16G16B16A16_FLOAT, as the frame wrote them */
+    void *Color;                                         /* OutputSize: R16G16B16A16_FLOAT, alpha 1; must not overlap the inputs */
+};
+enum PtSuperResolutionMode {           /* SuperResolutionMode of Source/Upscaler.ixx, in its order */
+    PT_SUPER_RESOLUTION_AUTO = 0, PT_SUPER_RESOLUTION_NATIVE = 1, PT_SUPER_RESOLUTION_QUALITY = 2, PT_SUPER_RESOLUTION_BALANCED = 3,
+    PT_SUPER_RESOLUTION_PERFORMANCE = 4, PT_SUPER_RESOLUTION_ULTRA_PERFORMANCE = 5
+};
+/* Out-of-range values are refused (PT_ERROR_INVALID_ARGUMENT, the message names the field) and leave the previous settings active.
+ * Settings that differ from the active ones (a size among them) restart the history. */
+int pt_upscaler_set_constants(PtContext* ctx, const struct PtUpscalerSettings* settings);
+/* One frame: one launch enqueued on the context's stream. jitter is the Camera.Jitter the frame was rendered with. Needs no scene. The
+ * history (fp32 colour in the tone-mapped space, accumulated weight n and depth, two parities: 40 B per output pixel) is context-owned
+ * and grow-only; a failed allocation returns PT_ERROR_OUT_OF_MEMORY and keeps what was there. It restarts on the first call, after
+ * pt_upscaler_reset_history and after a change of settings. Refused with PT_ERROR_INVALID_ARGUMENT and a message that names the field,
+ * nothing written and the history untouched: a NULL binding, a texture not aligned to its texel (LinearDepth 4 bytes, the others 8), a
+ * jitter that is not finite or outside [-0.5, 0.5], a call before pt_upscaler_set_constants, a sharded context (the pass is not local:
+ * a sharded host runs it on the gathered frame of an unsharded context). */
+int pt_upscaler_process(PtContext* ctx, const struct PtUpscalerTextures* textures, const float jitter[2]);
+int pt_upscaler_reset_history(PtContext* ctx);
+/* Test aid: the accumulated weight n per output pixel after the last pt_upscaler_process, the first min(capacity_pixels, w * h) of
+ * them; *out_w = *out_h = 0 when there is no history. Synchronises. */
+int pt_upscaler_download_history(PtContext* ctx, float* host_length, uint64_t capacity_pixels, uint32_t* out_w, uint32_t* out_h);
+/* Host only, no GPU and no context. The render size of a mode for an output size, max(1, (output * 10 + r10 / 2) / r10) per axis in
+ * integers with r10 = 10, 15, 17, 20, 30 for NATIVE .. ULTRA_PERFORMANCE (the ratios the SDKs publish: unpinned); AUTO resolves by
+ * the output's pixel count (App.cpp:1427-1440). */
+int pt_upscaler_render_size(uint32_t mode, const uint32_t output[2], uint32_t render_out[2]);
+/* Host only. The Camera.Jitter of a frame: the Halton point (bases 2 and 3) of index frame_index % count + 1, minus 0.5 per axis, in
+ * [-0.5, 0.5); count = ceil(8 (ow / rw) (oh / rh)) in fp32 (App.cpp:661). The radical inverse is this library's own fp32 loop. */
+int pt_upscaler_jitter(uint64_t frame_index, const uint32_t render[2], const uint32_t output[2], float jitter_out[2]);
+
+/* Two more bits of pt_set_debug_flags, for tests and A/B runs: which form of the kernel pt_upscaler_process launches. */
+#define PT_UPSCALER_FORM_DIRECT 0x2000u  /* the direct form (each tap a global load) */
+#define PT_UPSCALER_FORM_STAGED 0x4000u  /* the staged form (the tile's render footprint and halo through LDS): what the library chooses unasked, since it
+                                            is the faster one at a 4K output and level at 1080p. The same bytes either way */
+
+/* ------------------------------------------------------------------------------------------
  * the mip chain of an R32_FLOAT texture (MipmapGeneration::SetTexture + Process, Source/MipmapGeneration.ixx ->
  * Shaders/MipmapGeneration.hlsl), which App::PrepareReSTIRDI (Source/App.cpp:1095-1116) runs on the LocalLightPDF texture. The
  * shader is not restated: DESIGN.md section 1, "Local-light PDF texture", is the arithmetic spec (tests/pdfmipref.py restates it).
