@@ -294,6 +294,16 @@ struct Context {
     uint32_t upParity = 0;                            // which parity the last call wrote
     uint64_t upFrames = 0;                            // calls since the history was last reset; 0: the next call finds none
 
+    // ray reconstruction (pt_reconstruct.hip): two grow-only allocations. rrHistory, per render pixel ten float4 (two parities of the
+    // signal with its length and of the two guide records, the albedo, the a-trous ping-pong, two parities of the moments): 160 B.
+    // rrOutput, per output pixel two parities of a float4 (tone-mapped colour, n) and of the depth: 40 B. It shares nothing with the upscaler.
+    PtReconstructionSettings rr{}; bool haveRr = false;
+    DeviceBuffer<float4> rrHistory, rrOutput;
+    uint32_t rrSize[4] = {0, 0, 0, 0};                // render w, h and output w, h the history was laid out for by the last pt_reconstruction_process
+    uint32_t rrParity = 0;                            // which parity the last call wrote
+    uint32_t rrFinal = 0;                             // which a-trous work buffer holds the last call's filtered signal
+    uint64_t rrFrames = 0;                            // calls since the history was last reset; 0: the next call finds none
+
     // SHARC radiance cache (pt_sharc.hip): per context, also for a context that views another's scene. sharcVoxels[sharcParity] is VoxelData (this
     // frame's deposits, then the resolved cache), the other one PreviousVoxelData; they swap after the query.
     PtSHARCSettings sharcSettings{}; bool haveSharcSettings = false;

@@ -8,6 +8,7 @@
 //           [--hdr [--paper-white N] [--color-rotation hdtv_to_uhdtv|dci_p3_d65_to_uhdtv|hdtv_to_dci_p3_d65]]
 //           [--nrd relax|reblur [--denoise [--denoise-frames-max N] [--denoise-iterations K]]] [--out-radiance file.bin]
 //           [--upscale native|quality|balanced|performance|ultra [--output-size WxH] [--out-upscaled file.bin]]
+//           [--reconstruct native|quality|balanced|performance|ultra --output-size WxH [--reconstruct-iterations K] [--out-reconstructed file.bin]]
 //           [--png file.png] [--out-display file.bin] [--scene descriptor.json [--anim-time T [--anim-step DT]]] [--dump-scene file.bin]
 //
 // --anim-time T (with --scene): the animated render objects of the descriptor (RenderObjects[].Animation) are posed at T seconds of their selected
@@ -50,6 +51,13 @@
 // output-size images). The camera keeps the output's aspect and carries the Halton jitter of the frame (Upscaler::Jitter). The timed
 // frames are one temporal sequence: FrameIndex and the jitter index count 0 .. N - 1, and the history starts empty behind the warm-up
 // frame. --out-upscaled writes the last frame's upscaled colour (R16G16B16A16_FLOAT at the output size). Composes with --nrd relax --denoise.
+//
+// --reconstruct MODE --output-size WxH (one unsharded process): the reference's default chain. The frame is rendered with Denoiser =
+// DLSSRayReconstruction (the G-buffer pass then writes the albedos, Radiance stays the noisy sum) at the render size of that mode, jittered
+// like --upscale, and the library's denoising upscaler (ptamd.hpp Reconstruction) brings it to the output size where the reference calls
+// ProcessDLSSRayReconstruction (App.cpp:1513-1523), ahead of --post. --reconstruct-iterations K: its a-trous iterations (0..8, default 5).
+// --out-reconstructed writes the last frame's Color (R16G16B16A16_FLOAT at the output size). Refused together with --upscale or --nrd (the
+// pass is both steps); composes with --sharc, --di --restir, --post, --frames.
 //
 // --ranks R: one process per GPU. The parent (which never touches a GPU) starts R children `--rank r --world R --id-file F`; rank 0
 // makes the RCCL unique id and leaves it in F, the others pick it up; every rank renders its 16-row bands (BandSharding) and rank 0
@@ -423,6 +431,7 @@ int main(int argc, char** argv)
     std::string nrd, radiancePath;
     bool denoise = false; uint32_t denoiseFramesMax = 30, denoiseIterations = 5;
     std::string upscale, outputSize, upscaledPath;
+    std::string reconstruct, reconstructedPath; int reconstructIterations = -1;
     for (int i = 1; i < argc; i++) {
         std::string k = argv[i];
         if (k == "--di") { di = true; continue; }                  // the flags without a value
@@ -455,6 +464,8 @@ int main(int argc, char** argv)
         else if (k == "--denoise-frames-max") denoiseFramesMax = atoi(v); else if (k == "--denoise-iterations") denoiseIterations = atoi(v);
         else if (k == "--nrd") nrd = v; else if (k == "--out-radiance") radiancePath = v;
         else if (k == "--upscale") upscale = v; else if (k == "--output-size") outputSize = v; else if (k == "--out-upscaled") upscaledPath = v;
+        else if (k == "--reconstruct") reconstruct = v; else if (k == "--out-reconstructed") reconstructedPath = v;
+        else if (k == "--reconstruct-iterations") reconstructIterations = atoi(v);
         else if (k == "--anim-time") { animate = true; animTime = atof(v); } else if (k == "--anim-step") animStep = atof(v);
     }
     post = post || !pngPath.empty() || !displayPath.empty();
@@ -466,9 +477,21 @@ int main(int argc, char** argv)
     if (ranks && !sharded) return launch_ranks(argc, argv, ranks);
     try {
         // ---- --upscale: W x H becomes the render size of the mode for the output size
-        const bool upscaling = !upscale.empty();
+        // ---- --reconstruct: the same sizes and jitter, with the denoising upscaler in the upscaler's place and no NRD block
+        const bool upscaling = !upscale.empty(), reconstructing = !reconstruct.empty(), resizing = upscaling || reconstructing;
         uint32_t outW = W, outH = H;
-        if (upscaling) {
+        if (reconstructing) {
+            if (upscaling) throw std::invalid_argument("--reconstruct is the denoiser and the upscaler of its frame: drop --upscale");
+            if (!nrd.empty() || denoise) throw std::invalid_argument("--reconstruct is the denoiser and the upscaler of its frame: drop --nrd / --denoise");
+            if (sharded) throw std::invalid_argument("--reconstruct needs one unsharded process");
+            if (outputSize.empty()) throw std::invalid_argument("--reconstruct needs --output-size WxH");
+            if (reconstructIterations != -1 && (reconstructIterations < 0 || reconstructIterations > 8)) throw std::invalid_argument("--reconstruct-iterations: 0..8");
+            if (reconstruct != "native" && reconstruct != "quality" && reconstruct != "balanced" && reconstruct != "performance" && reconstruct != "ultra")
+                throw std::invalid_argument("--reconstruct: native, quality, balanced, performance or ultra");
+            upscale = reconstruct;                                  // the mode names and the render sizes are the upscaler's
+        } else if (reconstructIterations != -1 || !reconstructedPath.empty())
+            throw std::invalid_argument("--reconstruct-iterations and --out-reconstructed need --reconstruct");
+        if (resizing) {
             if (sharded) throw std::invalid_argument("--upscale needs one unsharded process");
             Upscaler::SuperResolutionMode mode;
             if (upscale == "native") mode = PT_SUPER_RESOLUTION_NATIVE; else if (upscale == "quality") mode = PT_SUPER_RESOLUTION_QUALITY;
@@ -591,7 +614,9 @@ int main(int argc, char** argv)
         else if (nrd == "reblur") nrdDenoiser = PT_DENOISER_NRD_REBLUR;
         else if (!nrd.empty()) throw std::invalid_argument("--nrd: relax or reblur");
         if (di || nrdDenoiser) { tx.Diffuse = alloc(px_ * 8); tx.Specular = alloc(px_ * 8); }   // Raytracing::Textures Diffuse / Specular (App.cpp:475-482)
-        if (nrdDenoiser) { tx.DiffuseAlbedo = alloc(px_ * 8); tx.SpecularAlbedo = alloc(px_ * 8); }   // App.cpp:1223: the albedos exist for the denoiser
+        // the Denoiser value of the frame: the NRD one, or DLSS-RR under --reconstruct (the guides the same, Radiance the noisy sum)
+        const uint32_t frameDenoiser = reconstructing ? (uint32_t)PT_DENOISER_DLSS_RAY_RECONSTRUCTION : nrdDenoiser;
+        if (frameDenoiser) { tx.DiffuseAlbedo = alloc(px_ * 8); tx.SpecularAlbedo = alloc(px_ * 8); }   // App.cpp:1223: the albedos exist for the denoiser
         void* fullRadiance = sharded && rank == 0 ? alloc(fullPx * 8) : nullptr;      // the assembled frame (R16G16B16A16_FLOAT), root only
         // ---- App::PostProcessGraphics (Denoiser::None): on the whole frame, rank 0 of a sharded run after the gather
         PostProcessing postProcessing(commandList);
@@ -651,6 +676,15 @@ int main(int argc, char** argv)
             upscaler.SetConstants(s);
             upscaler.Textures = { tx.Radiance, tx.LinearDepth, tx.MotionVector, alloc(outPx * 8) };
             if (runPost) postProcessing.Textures.Radiance = upscaler.Textures.Color;
+        }
+        Reconstruction reconstruction(commandList);
+        if (reconstructing) {                                       // App.cpp:1513-1523: ProcessDLSSRayReconstruction's place, ahead of Bloom / ToneMap
+            Reconstruction::Settings s; s.RenderSize[0] = W; s.RenderSize[1] = H; s.OutputSize[0] = outW; s.OutputSize[1] = outH;
+            if (reconstructIterations != -1) s.AtrousIterations = (uint32_t)reconstructIterations;
+            reconstruction.SetConstants(s);
+            reconstruction.Textures = { tx.Radiance, tx.DiffuseAlbedo, tx.SpecularAlbedo, tx.NormalRoughness, tx.Position, tx.LinearDepth, tx.MotionVector,
+                                        alloc(outPx * 8) };
+            if (runPost) postProcessing.Textures.Radiance = reconstruction.Textures.Color;
         }
         SHARC sharc(commandList);
         Raytracing::SHARCSettings sharcSettings; sharcSettings.DownscaleFactor = sharcDownscale;
@@ -738,7 +772,7 @@ int main(int argc, char** argv)
         double ms = 0;
         auto renderFrame = [&](uint32_t frameIndex) {
             float jitter[2] = { 0.0f, 0.0f };
-            if (upscaling) {                                        // App.cpp:556: the frame's Halton jitter, in the camera every pass reads
+            if (resizing) {                                         // App.cpp:556: the frame's Halton jitter, in the camera every pass reads
                 const uint32_t render[2] = { W, H }, output[2] = { outW, outH };
                 Upscaler::Jitter(frameIndex, render, output, jitter);
                 cam.Jitter[0] = jitter[0]; cam.Jitter[1] = jitter[1];
@@ -750,16 +784,16 @@ int main(int argc, char** argv)
                 gbuffer.Textures = tx; raytracing.Textures = tx; directLighting.Textures = tx;
             }
             firstFrame = false;
-            gbuffer.Render(commandList, tlas, { { W, H }, nrdDenoiser ? ~0u : ~0u & ~(uint32_t)GBufferGeneration::Flags::Albedo });     // App.cpp:1223-1224
+            gbuffer.Render(commandList, tlas, { { W, H }, frameDenoiser ? ~0u : ~0u & ~(uint32_t)GBufferGeneration::Flags::Albedo });     // App.cpp:1223-1224
             if (di) {                                               // App.cpp:1234-1308: RTXDI between the G-buffer and the path tracer
                 DirectLighting::Settings ds; ds.RenderSize[0] = W; ds.RenderSize[1] = H; ds.FrameIndex = frameIndex;
-                ds.LocalLightSamples = diSamples; ds.IsLastRenderPass = bounces == 0; ds.Denoiser = nrdDenoiser;
+                ds.LocalLightSamples = diSamples; ds.IsLastRenderPass = bounces == 0; ds.Denoiser = frameDenoiser;
                 directLighting.SetConstants(ds);
                 directLighting.Render(commandList, tlas);
             }
             Raytracing::GraphicsSettings gs; gs.RenderSize[0] = W; gs.RenderSize[1] = H;
             gs.FrameIndex = frameIndex; gs.Bounces = bounces; gs.SamplesPerPixel = spp; gs.IsRussianRouletteEnabled = true;
-            gs.IsDIEnabled = di; gs.Denoiser = nrdDenoiser;
+            gs.IsDIEnabled = di; gs.Denoiser = frameDenoiser;
             raytracing.SetConstants(gs);
             if (useSharc) raytracing.Render(commandList, tlas, sharc, sharcSettings);
             else raytracing.Render(commandList, tlas);
@@ -776,6 +810,10 @@ int main(int argc, char** argv)
             }
             if (sharded) sharding.GatherBands(commandList, tx.Radiance, fullRadiance, W, H, 8);
             if (upscaling) upscaler.Process(commandList, jitter);
+            if (reconstructing) {                                   // the restir swap may have moved the G-buffer textures
+                reconstruction.Textures.NormalRoughness = tx.NormalRoughness; reconstruction.Textures.LinearDepth = tx.LinearDepth;
+                reconstruction.Process(commandList, jitter);
+            }
             if (runPost) postProcessing.Render(commandList);
         };
         animateFrame();
@@ -783,13 +821,14 @@ int main(int argc, char** argv)
         commandList.End();
         if (denoise) denoiser.ResetHistory();                       // the warm-up frame is not part of the sequence
         if (upscaling) upscaler.ResetHistory();
+        if (reconstructing) reconstruction.ResetHistory();
         // timed run: frames 1..N back to back
         ThrowIfFailed(commandList.Context, pt_reset_counters(commandList.Context));
         const auto t0 = std::chrono::steady_clock::now();
         for (uint32_t f = 0; f < frames; f++) {                    // the last frame has FrameIndex 0 (dumped below)
             if (f) for (AnimationCollection* c : collectionList) (*c)[c->GetSelectedIndex()].Tick(animStep);
             animateFrame();
-            renderFrame(denoise || upscaling ? f : frames - 1 - f); // a denoised or upscaled run is a temporal sequence: FrameIndex counts up
+            renderFrame(denoise || resizing ? f : frames - 1 - f);  // a denoised or upscaled run is a temporal sequence: FrameIndex counts up
         }
         commandList.End();
         ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -836,6 +875,13 @@ int main(int argc, char** argv)
             HIP_OK(hipMemcpy(host.data(), upscaler.Textures.Color, outPx * 8, hipMemcpyDeviceToHost));
             FILE* fp = fopen(upscaledPath.c_str(), "wb");
             if (!fp || fwrite(host.data(), 8, outPx, fp) != outPx) { fprintf(stderr, "cannot write %s\n", upscaledPath.c_str()); if (fp) fclose(fp); return 3; }
+            fclose(fp);
+        }
+        if (reconstructing && !reconstructedPath.empty()) {         // the reconstruction's Color of the last frame
+            std::vector<uint16_t> host(outPx * 4);
+            HIP_OK(hipMemcpy(host.data(), reconstruction.Textures.Color, outPx * 8, hipMemcpyDeviceToHost));
+            FILE* fp = fopen(reconstructedPath.c_str(), "wb");
+            if (!fp || fwrite(host.data(), 8, outPx, fp) != outPx) { fprintf(stderr, "cannot write %s\n", reconstructedPath.c_str()); if (fp) fclose(fp); return 3; }
             fclose(fp);
         }
         if (runPost && !displayPath.empty()) {                      // the presented back buffer of the last frame

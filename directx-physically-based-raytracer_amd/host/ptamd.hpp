@@ -11,6 +11,7 @@
 //     struct NRDComposition      Source/NRDComposition.ixx (the pack and compose passes of App::ProcessNRD, Source/App.cpp:1595-1688)
 //     struct Denoiser            the library's own filter for the ReLAX slot between them (where the reference calls NRD::Denoise)
 //     struct Upscaler            the library's own temporal upscaler for the super-resolution step (where the reference calls DLSS or XeSS)
+//     struct Reconstruction      the library's own denoising upscaler for the ray-reconstruction step (where the reference calls DLSS-RR)
 // Error behaviour: a failing status becomes the exception type the reference throws at the same place
 // (std::invalid_argument for argument checks, std::system_error otherwise: Source/ErrorHelpers.ixx:16-32).
 // Header-only, plain C++20 (std::span), no HIP headers needed by the including translation unit.
@@ -710,6 +711,53 @@ struct Upscaler {
     static void Jitter(uint64_t frameIndex, const uint32_t (&render)[2], const uint32_t (&output)[2], float (&jitter)[2])
     {
         if (pt_upscaler_jitter(frameIndex, render, output, jitter) != PT_OK) throw std::invalid_argument("Upscaler::Jitter: a size out of range");
+    }
+
+private:
+    PtContext* m_context;
+};
+
+// The library's own denoising upscaler for the ray-reconstruction step of App::PostProcessGraphics (Source/App.cpp:1513-1523), where the
+// reference's default settings call ProcessDLSSRayReconstruction (pt_reconstruction_*; DESIGN.md section 1, "Ray reconstruction"): from
+// the noisy Radiance of a Denoiser = DLSSRayReconstruction frame, the two albedos and the G-buffer guides at RenderSize to the denoised
+// Color at OutputSize. Not a port of the SDK. Process takes the Camera.Jitter the frame was rendered with (Upscaler::RenderSize and
+// Upscaler::Jitter serve this pass too); Color then is the post chain's Radiance. Runs on the full frame of an unsharded context.
+struct Reconstruction {
+    struct Settings {
+        uint32_t RenderSize[2]{}, OutputSize[2]{};                          // RenderSize <= OutputSize <= 4 RenderSize per axis
+        uint32_t MaxAccumulatedFrames = 30, MaxOutputFrames = 16;           // 1..255: the history at RenderSize | at OutputSize
+        uint32_t AtrousIterations = 5;                                      // 0..8
+        float DepthThreshold = 0.01f, NormalCosine = 0.8f;                  // (0, 1] | [0, 1)
+        float LuminanceSigma = 2, RoughnessFraction = 0.15f, KernelRadius = 1;   // > 0 | > 0 | [0.75, 2]
+    };
+
+    PtReconstructionTextures Textures{};
+
+    explicit Reconstruction(CommandList& commandList) : m_context(commandList.Context) {}
+
+    void SetConstants(const Settings& settings)
+    {
+        PtReconstructionSettings s{};
+        s.RenderSize[0] = settings.RenderSize[0]; s.RenderSize[1] = settings.RenderSize[1];
+        s.OutputSize[0] = settings.OutputSize[0]; s.OutputSize[1] = settings.OutputSize[1];
+        s.MaxAccumulatedFrames = settings.MaxAccumulatedFrames; s.MaxOutputFrames = settings.MaxOutputFrames; s.AtrousIterations = settings.AtrousIterations;
+        s.DepthThreshold = settings.DepthThreshold; s.NormalCosine = settings.NormalCosine; s.LuminanceSigma = settings.LuminanceSigma;
+        s.RoughnessFraction = settings.RoughnessFraction; s.KernelRadius = settings.KernelRadius;
+        ThrowIfFailed(m_context, pt_reconstruction_set_constants(m_context, &s));
+    }
+
+    void Process(CommandList& commandList, const float (&jitter)[2]) { ThrowIfFailed(commandList.Context, pt_reconstruction_process(commandList.Context, &Textures, jitter)); }
+
+    void ResetHistory() { ThrowIfFailed(m_context, pt_reconstruction_reset_history(m_context)); }
+
+    // after the last Process, row-major: the history length of the signal per render pixel and the accumulated weight n per output pixel;
+    // both empty when there is no history. Synchronises.
+    void DownloadHistory(std::vector<float>& length, uint32_t (&render)[2], std::vector<float>& n, uint32_t (&output)[2])
+    {
+        ThrowIfFailed(m_context, pt_reconstruction_download_history(m_context, nullptr, nullptr, 0, nullptr, 0, render, output));
+        length.assign((size_t)render[0] * render[1], 0.0f); n.assign((size_t)output[0] * output[1], 0.0f);
+        if (!length.empty())
+            ThrowIfFailed(m_context, pt_reconstruction_download_history(m_context, length.data(), nullptr, length.size(), n.data(), n.size(), render, output));
     }
 
 private:

@@ -486,6 +486,67 @@ def upscaler_jitter(frame_index, render_size, output_size):
     return tuple(out)
 
 
+RECONSTRUCTION_SETTINGS = np.dtype({  # PtReconstructionSettings, 64 B
+    "names": ["RenderSize", "OutputSize", "MaxAccumulatedFrames", "MaxOutputFrames", "AtrousIterations", "DepthThreshold", "NormalCosine",
+              "LuminanceSigma", "RoughnessFraction", "KernelRadius", "_pad"],
+    "formats": [("<u4", 2), ("<u4", 2), "<u4", "<u4", "<u4", "<f4", "<f4", "<f4", "<f4", "<f4", ("<u4", 4)],
+    "offsets": [0, 8, 16, 20, 24, 28, 32, 36, 40, 44, 48], "itemsize": 64})
+# PtReconstructionTextures member order: eight pointers
+RECONSTRUCTION_TEXTURES = ["Radiance", "DiffuseAlbedo", "SpecularAlbedo", "NormalRoughness", "Position", "LinearDepth", "MotionVector", "Color"]
+RECONSTRUCTION_DEFAULTS = {"MaxAccumulatedFrames": 30, "MaxOutputFrames": 16, "AtrousIterations": 5, "DepthThreshold": 0.01,
+                           "NormalCosine": 0.8, "LuminanceSigma": 2.0, "RoughnessFraction": 0.15, "KernelRadius": 1.0}
+RECONSTRUCTION_MAX_SIZE = 16384
+RECONSTRUCTION_FORM_DIRECT, RECONSTRUCTION_FORM_STAGED = 0x8000, 0x10000      # PT_RECONSTRUCTION_FORM_*: bits of pt_set_debug_flags
+
+
+def check_reconstruction_settings(s):
+    """The range checks of pt_reconstruction_set_constants, on the float32 values the library receives: ValueError where it answers
+    PT_ERROR_INVALID_ARGUMENT."""
+    s = np.asarray(s).reshape(())
+    render, output = [int(v) for v in s["RenderSize"]], [int(v) for v in s["OutputSize"]]
+    f = {k: float(np.float32(s[k])) for k in ("DepthThreshold", "NormalCosine", "LuminanceSigma", "RoughnessFraction", "KernelRadius")}
+    for name, size in (("RenderSize", render), ("OutputSize", output)):
+        if not all(1 <= v <= RECONSTRUCTION_MAX_SIZE for v in size):
+            raise ValueError(f"{name} must be 1..{RECONSTRUCTION_MAX_SIZE} on both axes")
+    if not all(r <= o <= 4 * r for r, o in zip(render, output)):
+        raise ValueError("OutputSize must be RenderSize..4 RenderSize on both axes")
+    for k in ("MaxAccumulatedFrames", "MaxOutputFrames"):
+        if not 1 <= int(s[k]) <= 255:
+            raise ValueError(f"{k} must be 1..255")
+    if int(s["AtrousIterations"]) > 8:
+        raise ValueError("AtrousIterations must be 0..8")
+    if not 0.0 < f["DepthThreshold"] <= 1.0:
+        raise ValueError("DepthThreshold must be in (0, 1]")
+    if not 0.0 <= f["NormalCosine"] < 1.0:
+        raise ValueError("NormalCosine must be in [0, 1)")
+    for k in ("LuminanceSigma", "RoughnessFraction"):
+        if not (f[k] > 0.0 and np.isfinite(f[k])):
+            raise ValueError(f"{k} must be positive and finite")
+    if not 0.75 <= f["KernelRadius"] <= 2.0:
+        raise ValueError("KernelRadius must be in [0.75, 2]")
+    return s
+
+
+def reconstruction_settings(render_size, output_size, **overrides):
+    """PtReconstructionSettings with the defaults of RECONSTRUCTION_DEFAULTS; overrides by field name. Refuses what
+    pt_reconstruction_set_constants refuses."""
+    s = np.zeros((), RECONSTRUCTION_SETTINGS)
+    for name, size in (("RenderSize", render_size), ("OutputSize", output_size)):
+        if len(size) != 2 or not all(0 <= int(v) <= 0xFFFFFFFF for v in size):
+            raise ValueError(f"{name} is not a pair of 32-bit unsigned values")
+        s[name] = tuple(int(v) for v in size)
+    values = dict(RECONSTRUCTION_DEFAULTS)
+    for k, v in overrides.items():
+        if k not in values:
+            raise ValueError(f"PtReconstructionSettings has no field {k}")
+        values[k] = v
+    for k, v in values.items():
+        if s.dtype[k].kind == "u" and not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{k} is not a 32-bit unsigned value")
+        s[k] = v
+    return check_reconstruction_settings(s)
+
+
 SHARC_SETTINGS = np.dtype({  # PtSHARCSettings: SHARC::Constants + Raytracing::SHARCSettings (Source/MyAppData.h:250-262)
     "names": ["AccumulationFrames", "MaxStaleFrames", "SceneScale", "IsAntiFireflyEnabled", "DownscaleFactor", "RoughnessThreshold",
               "IsHashGridVisualizationEnabled"],

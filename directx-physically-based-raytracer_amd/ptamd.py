@@ -35,6 +35,7 @@ EXPORTS = [
     "pt_denoiser_set_constants", "pt_denoiser_process", "pt_denoiser_reset_history", "pt_denoiser_download_history",
     "pt_upscaler_set_constants", "pt_upscaler_process", "pt_upscaler_reset_history", "pt_upscaler_download_history",
     "pt_upscaler_render_size", "pt_upscaler_jitter",
+    "pt_reconstruction_set_constants", "pt_reconstruction_process", "pt_reconstruction_reset_history", "pt_reconstruction_download_history",
     "pt_anim_create_rig", "pt_anim_release_rig", "pt_anim_create_object", "pt_anim_release_object", "pt_anim_evaluate",
     "pt_anim_skeletal_transforms", "pt_anim_download_globals", "pt_anim_download_skeletal", "pt_anim_debug_slerp",
     "pt_sharc_configure", "pt_sharc_set_constants", "pt_raytrace_render_sharc", "pt_sharc_reset", "pt_sharc_download",
@@ -87,6 +88,10 @@ class DenoiserTextures(C.Structure):         # PtDenoiserTextures: eight pointer
 
 class UpscalerTextures(C.Structure):         # PtUpscalerTextures: four pointers
     _fields_ = [(n, C.c_void_p) for n in L.UPSCALER_TEXTURES]
+
+
+class ReconstructionTextures(C.Structure):   # PtReconstructionTextures: eight pointers
+    _fields_ = [(n, C.c_void_p) for n in L.RECONSTRUCTION_TEXTURES]
 
 
 class Sharding(C.Structure):
@@ -244,6 +249,11 @@ def load_library():
         lib.pt_upscaler_download_history.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.pt_upscaler_render_size.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.pt_upscaler_jitter.argtypes = [C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+        lib.pt_reconstruction_set_constants.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_reconstruction_process.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        lib.pt_reconstruction_reset_history.argtypes = [C.c_void_p]
+        lib.pt_reconstruction_download_history.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.pt_sharc_configure.argtypes = [C.c_void_p, C.c_uint32]
         lib.pt_sharc_set_constants.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_raytrace_render_sharc.argtypes = [C.c_void_p, C.c_void_p]
@@ -1218,6 +1228,57 @@ class Upscaler:
         return out
 
 
+class Reconstruction:
+    """The library's own denoising upscaler for the ray-reconstruction slot of App::PostProcessGraphics (pt_reconstruction_*; DESIGN.md
+    section 1, "Ray reconstruction"), where the reference's default settings call DLSS Ray Reconstruction. Not a port of it. From the noisy
+    Radiance of a Denoiser = DLSS-RR frame, the two albedos and the G-buffer guides at RenderSize to the denoised Color at OutputSize.
+    Process takes the textures by the names of layouts.RECONSTRUCTION_TEXTURES (a missing name is an unbound texture) and the
+    Camera.Jitter the frame was rendered with. Runs on the full frame of an unsharded context. No scene is needed."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.Textures = {}
+        self._settings = None
+
+    @property
+    def settings(self):
+        """the PtReconstructionSettings record last accepted, or None"""
+        return self._settings
+
+    def SetConstants(self, settings):
+        """settings: PtReconstructionSettings (layouts.reconstruction_settings)."""
+        k = np.array(settings)
+        if k.dtype != L.RECONSTRUCTION_SETTINGS or k.size != 1:
+            raise PtInvalidArgument("settings must be one PtReconstructionSettings record (layouts.reconstruction_settings)")
+        k = np.ascontiguousarray(k).reshape(())
+        self.ctx.check(self.ctx.lib.pt_reconstruction_set_constants(self.ctx.handle, C.c_void_p(k.ctypes.data)))
+        self._settings = k
+
+    def Process(self, jitter, textures=None):
+        tex = self.Textures if textures is None else textures
+        t = ReconstructionTextures(*[_ptr(tex.get(n)) for n in L.RECONSTRUCTION_TEXTURES])
+        j = (C.c_float * 2)(float(jitter[0]), float(jitter[1]))
+        self.ctx.check(self.ctx.lib.pt_reconstruction_process(self.ctx.handle, C.addressof(t), j))
+
+    def ResetHistory(self):
+        self.ctx.check(self.ctx.lib.pt_reconstruction_reset_history(self.ctx.handle))
+
+    def DownloadHistory(self):
+        """After the last Process: (length, filtered, n). length: the history length of the signal per render pixel, float32 (h, w);
+        filtered: what the resolve read, float32 (h, w, 4) (the filtered signal and its variance; the guarded Radiance and 0 where the
+        G-buffer missed); n: the accumulated weight per output pixel, float32 (oh, ow). Empty arrays when there is no history.
+        Synchronises."""
+        render, output = (C.c_uint32 * 2)(), (C.c_uint32 * 2)()
+        call = self.ctx.lib.pt_reconstruction_download_history
+        self.ctx.check(call(self.ctx.handle, None, None, 0, None, 0, render, output))
+        length, filtered = np.zeros((render[1], render[0]), np.float32), np.zeros((render[1], render[0], 4), np.float32)
+        n = np.zeros((output[1], output[0]), np.float32)
+        if length.size:
+            self.ctx.check(call(self.ctx.handle, C.c_void_p(length.ctypes.data), C.c_void_p(filtered.ctypes.data), length.size,
+                                C.c_void_p(n.ctypes.data), n.size, render, output))
+        return length, filtered, n
+
+
 class SHARC:
     """Mirror of `struct SHARC` (Source/SHARC.ixx) and of the Raytracing::Render overload that takes it: Configure allocates the context's
     cache, SetConstants takes PtSHARCSettings (layouts.sharc_settings), Render runs clear, update, resolve, query and the swap with the
@@ -1336,9 +1397,26 @@ class Renderer:
         u.SetConstants(L.upscaler_settings((self.width, self.height), (output_w, output_h), **overrides))
         return u
 
+    def reconstruction(self, output_w, output_h, **overrides):
+        """A new Reconstruction from this renderer's size to output_w x output_h, bound to the renderer's textures, with
+        layouts.reconstruction_settings' defaults (overrides by field name): render(..., reconstruct=that) with settings["Denoiser"] =
+        DENOISER_DLSS_RR. It writes textures["Reconstructed"]. Unsharded contexts only: the pass needs the whole frame."""
+        if getattr(self.ctx, "sharding", (0, 1, 16))[1] > 1:
+            raise PtInvalidArgument("the reconstruction needs the whole frame: the context is sharded (run Reconstruction on the gathered textures)")
+        u = Reconstruction(self.ctx)
+        u.Textures = self.textures
+        u.SetConstants(L.reconstruction_settings((self.width, self.height), (output_w, output_h), **overrides))
+        return u
+
     def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None, post=None, sharc=None, di_visibility=None, di_pairwise=None,
-               di_regir_layout=None, di_brdf=None, nrd=None, denoise=None, nrd_hit_distance=None, di_pdf_mipmap=None, upscale=None):
-        """upscale: an Upscaler (self.upscaler(output_w, output_h)) to run the super-resolution step of App::PostProcessGraphics
+               di_regir_layout=None, di_brdf=None, nrd=None, denoise=None, nrd_hit_distance=None, di_pdf_mipmap=None, upscale=None,
+               reconstruct=None):
+        """reconstruct: a Reconstruction (self.reconstruction(output_w, output_h)) to run the ray-reconstruction step of
+        App::PostProcessGraphics (App.cpp:1513-1523) after the frame and before post, where upscale= runs: it reads the frame's noisy
+        Radiance, the albedos, the guides and the camera's Jitter and writes textures["Reconstructed"] at its OutputSize; post's
+        RenderSize must then be that OutputSize and the post chain reads Reconstructed as its Radiance. settings["Denoiser"] must be
+        DENOISER_DLSS_RR (the frame then writes what the pass reads); not together with upscale or nrd (the pass is both steps).
+        upscale: an Upscaler (self.upscaler(output_w, output_h)) to run the super-resolution step of App::PostProcessGraphics
         (App.cpp:1532-1541) after the NRD block and before post: it reads the frame's Radiance, LinearDepth and MotionVector and the
         camera's Jitter and writes textures["Upscaled"] at its OutputSize; post's RenderSize must then be that OutputSize and the post
         chain reads Upscaled as its Radiance. None: no such step, the frame as it was.
@@ -1369,9 +1447,25 @@ class Renderer:
             p = np.array(post).reshape(())
             if getattr(self.ctx, "sharding", (0, 1, 16))[1] > 1:
                 raise PtInvalidArgument("post-processing needs the whole frame: run PostProcessing on the gathered Radiance of a sharded render")
-            if upscale is None and tuple(int(v) for v in p["RenderSize"]) != (self.width, self.height):
+            if upscale is None and reconstruct is None and tuple(int(v) for v in p["RenderSize"]) != (self.width, self.height):
                 raise PtInvalidArgument("post-processing RenderSize differs from the renderer's size")
         out_w = out_h = None
+        if reconstruct is not None:
+            if not isinstance(reconstruct, Reconstruction) or reconstruct.settings is None:
+                raise PtInvalidArgument("reconstruct must be a Reconstruction whose constants are set (Renderer.reconstruction)")
+            if upscale is not None or nrd is not None:
+                raise PtInvalidArgument("reconstruct cannot be combined with upscale or nrd: ray reconstruction is the denoiser and the upscaler of its frame")
+            if int(np.array(settings).reshape(())["Denoiser"]) != L.DENOISER_DLSS_RR:
+                raise PtInvalidArgument("reconstruct needs settings['Denoiser'] = DENOISER_DLSS_RR: only then the frame writes the noisy Radiance and the albedos the pass reads")
+            if "DiffuseAlbedo" not in self.textures or "SpecularAlbedo" not in self.textures:
+                raise PtInvalidArgument("reconstruct needs the DiffuseAlbedo / SpecularAlbedo textures: the renderer has none")
+            if getattr(self.ctx, "sharding", (0, 1, 16))[1] > 1:
+                raise PtInvalidArgument("the reconstruction needs the whole frame: the context is sharded")
+            if tuple(int(v) for v in reconstruct.settings["RenderSize"]) != (self.width, self.height):
+                raise PtInvalidArgument("the reconstruction's RenderSize differs from the renderer's size")
+            out_w, out_h = (int(v) for v in reconstruct.settings["OutputSize"])
+            if post is not None and tuple(int(v) for v in p["RenderSize"]) != (out_w, out_h):
+                raise PtInvalidArgument("post-processing RenderSize differs from the reconstruction's OutputSize")
         if upscale is not None:
             if not isinstance(upscale, Upscaler) or upscale.settings is None:
                 raise PtInvalidArgument("upscale must be an Upscaler whose constants are set (Renderer.upscaler)")
@@ -1447,10 +1541,19 @@ class Renderer:
             upscale.SetConstants(upscale.settings)
             upscale.Process(jitter, {"Radiance": t["Radiance"], "LinearDepth": t["LinearDepth"], "MotionVector": t["MotionVector"],
                                      "Color": t["Upscaled"]})
+        if reconstruct is not None:                                       # App.cpp:1513-1523: ProcessDLSSRayReconstruction's place
+            t = self.textures
+            if "Reconstructed" not in t or tuple(t["Reconstructed"].shape) != (out_h, out_w, 4):
+                t["Reconstructed"] = _torch().zeros((out_h, out_w, 4), dtype=t["Radiance"].dtype, device=self.scene.device)
+            jitter = np.array(self.gbuffer.GPUBuffers["Camera"]).reshape(())["Jitter"]
+            # the context's settings are this pass's (the same again keep the history): they size what the call writes
+            reconstruct.SetConstants(reconstruct.settings)
+            reconstruct.Process(jitter, dict({n: t[n] for n in L.RECONSTRUCTION_TEXTURES[:-1]}, Color=t["Reconstructed"]))
         if post is not None:                                              # App.cpp:1506-1571, after Raytracing::Render
-            pw, ph = (out_w, out_h) if upscale is not None else (self.width, self.height)
+            pw, ph = (out_w, out_h) if upscale is not None or reconstruct is not None else (self.width, self.height)
             if "Color" not in self.textures or tuple(self.textures["Color"].shape[:2]) != (ph, pw):
                 self.textures.update(alloc_post_textures(pw, ph, self.scene.device))
             self.post.SetConstants(post)
-            self.post.Render(self.textures if upscale is None else dict(self.textures, Radiance=self.textures["Upscaled"]))
+            resized = "Upscaled" if upscale is not None else "Reconstructed" if reconstruct is not None else None
+            self.post.Render(self.textures if resized is None else dict(self.textures, Radiance=self.textures[resized]))
         self._rendered = True

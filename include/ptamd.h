@@ -858,6 +858,64 @@ int pt_upscaler_jitter(uint64_t frame_index, const uint32_t render[2], const uin
                                             is the faster one at a 4K output and level at 1080p. The same bytes either way */
 
 /* ------------------------------------------------------------------------------------------
+ * the denoising upscaler for the ray-reconstruction slot of App::PostProcessGraphics (Source/App.cpp:1513-1523, :1700-1716), which the
+ * reference's default settings (Denoiser = DLSSRayReconstruction) fill with ProcessDLSSRayReconstruction: this library's own filter,
+ * NOT a port of DLSS Ray Reconstruction (a closed SDK, not part of the reference tree). DESIGN.md section 1, "Ray reconstruction", is the
+ * arithmetic spec (unpinned against the SDK; tests/reconstructref.py restates it bit for bit). It reads what the frame wrote for
+ * PT_DENOISER_DLSS_RAY_RECONSTRUCTION at RenderSize -- the noisy Radiance (one signal, direct + indirect), the two albedos,
+ * NormalRoughness, Position, LinearDepth, MotionVector -- and the frame's Camera.Jitter (as it stands in PtCamera: not negated), and
+ * writes the denoised Color at OutputSize, which then is the post chain's Radiance. The signal is Radiance divided by the albedo sum
+ * (floored at 1/64 per channel); it is accumulated over time, filtered by an edge-stopping a-trous wavelet, and multiplied by each
+ * tap's own albedo again inside the temporal resolve to OutputSize. SpecularHitDistance is not read: reprojection follows the surface
+ * motion only (no virtual motion), as in the denoiser.
+ * ------------------------------------------------------------------------------------------ */
+struct PtReconstructionSettings {      /* (tagged, not a typedef, like PtDenoiserSettings: C callers write `struct PtReconstructionSettings`) */
+    uint32_t RenderSize[2];            /* 1..16384 each */
+    uint32_t OutputSize[2];            /* 1..16384 each; RenderSize <= OutputSize <= 4 RenderSize per axis */
+    uint32_t MaxAccumulatedFrames;     /* default 30; 1..255: the history of the signal at RenderSize (1 = no temporal reuse there) */
+    uint32_t MaxOutputFrames;          /* default 16; 1..255: the history of the output at OutputSize */
+    uint32_t AtrousIterations;         /* default 5; 0..8 (0 = no spatial filter) */
+    float    DepthThreshold;           /* default 0.01; (0, 1]: relative, for both reprojections and for the plane distance */
+    float    NormalCosine;             /* default 0.8; [0, 1): taps whose normals agree less weigh 0 */
+    float    LuminanceSigma;           /* default 2;  > 0 */
+    float    RoughnessFraction;        /* default 0.15; > 0: relative roughness difference that weighs 0 */
+    float    KernelRadius;             /* default 1; [0.75, 2]: the radius of the resolve's reconstruction kernel, in render pixels */
+    uint32_t _pad[4];
+};                                     /* 64 B */
+struct PtReconstructionTextures {      /* full frames, row-major */
+    const void *Radiance, *DiffuseAlbedo, *SpecularAlbedo;                 /* RenderSize, R16G16B16A16_FLOAT (alpha ignored), as the frame wrote them */
+    const void *NormalRoughness, *Position, *LinearDepth, *MotionVector;   /* RenderSize, as pt_gbuffer_render writes them */
+    void *Color;                                                           /* OutputSize: R16G16B16A16_FLOAT, alpha 1; must not overlap an input */
+};
+/* Out-of-range values are refused (PT_ERROR_INVALID_ARGUMENT, the message names the field) and leave the previous settings active.
+ * Settings that differ from the active ones (a size among them) restart the history. */
+int pt_reconstruction_set_constants(PtContext* ctx, const struct PtReconstructionSettings* settings);
+/* One frame: 3 + AtrousIterations launches enqueued on the context's stream. jitter is the Camera.Jitter the frame was rendered with
+ * (pt_upscaler_render_size and pt_upscaler_jitter serve this pass too). Needs no scene. A pixel whose LinearDepth is not finite is
+ * never filtered: its Radiance (all three channels 0 when one is not finite) goes to the resolve as it is. The history is context-owned
+ * and grow-only, and apart from the upscaler's (a context may run both): per render pixel 160 B (fp32 signal and length, luminance
+ * moments and guide records in two parities, the albedo, the a-trous ping-pong), per output pixel 40 B (fp32 colour in the tone-mapped
+ * space, accumulated weight n and depth, two parities). A failed allocation returns PT_ERROR_OUT_OF_MEMORY and keeps what was there.
+ * It restarts on the first call, after pt_reconstruction_reset_history and after a change of settings. Refused with
+ * PT_ERROR_INVALID_ARGUMENT and a message that names the field, nothing written and the history untouched: a NULL binding, a texture
+ * not aligned to its texel (Position 16 bytes, LinearDepth 4, the others 8), Color overlapping an input, a jitter that is not finite or
+ * outside [-0.5, 0.5], a call before pt_reconstruction_set_constants, a sharded context (the pass is not local: a sharded host runs it
+ * on the gathered frame of an unsharded context). */
+int pt_reconstruction_process(PtContext* ctx, const struct PtReconstructionTextures* textures, const float jitter[2]);
+int pt_reconstruction_reset_history(PtContext* ctx);
+/* Test aid, after the last pt_reconstruction_process: host_length, the history length of the signal per render pixel (0: the G-buffer
+ * missed); host_filtered, four floats per render pixel, what the resolve read (the filtered signal and its variance; the guarded
+ * Radiance and 0 where the G-buffer missed); host_n, the accumulated weight n per output pixel. The first min(capacity, w * h) pixels
+ * of each; a NULL array is skipped. render_out = output_out = 0 x 0 when there is no history. Synchronises. */
+int pt_reconstruction_download_history(PtContext* ctx, float* host_length, float* host_filtered, uint64_t capacity_render_pixels,
+                                       float* host_n, uint64_t capacity_output_pixels, uint32_t render_out[2], uint32_t output_out[2]);
+
+/* Two more bits of pt_set_debug_flags, for tests and A/B runs: which form of the a-trous kernel pt_reconstruction_process launches. */
+#define PT_RECONSTRUCTION_FORM_DIRECT 0x8000u   /* every a-trous step takes the direct form (each tap a global load) */
+#define PT_RECONSTRUCTION_FORM_STAGED 0x10000u  /* the staged form (tile + halo through LDS) at every step whose halo fits (1, 2, 4): what the library
+                                                   chooses unasked. The same bytes either way */
+
+/* ------------------------------------------------------------------------------------------
  * the mip chain of an R32_FLOAT texture (MipmapGeneration::SetTexture + Process, Source/MipmapGeneration.ixx ->
  * Shaders/MipmapGeneration.hlsl), which App::PrepareReSTIRDI (Source/App.cpp:1095-1116) runs on the LocalLightPDF texture. The
  * shader is not restated: DESIGN.md section 1, "Local-light PDF texture", is the arithmetic spec (tests/pdfmipref.py restates it).
