@@ -7,27 +7,19 @@
 //                          through LDS first, else every tap is a global load. Same taps, same order, same arithmetic: the same bits.
 // Not a port of NRD's ReLAX (its source is not in the reference tree): DESIGN.md section 1, "Denoiser", is the arithmetic spec and
 // tests/denoiseref.py restates it. Plain fp32 operations, one rounding each (-ffp-contract=off); the only fused operations are those
-// of dot() / ml_luminance(); no library transcendental.
-#include "pt_internal.hpp"
-
-#include <cmath>
-#include <cstring>
-#include <vector>
+// of dot() / ml_luminance(); no library transcendental. The small arithmetic, the set-up of the history taps and the host plumbing are
+// pt_filter.hpp's, shared with the upscaler and the reconstruction; the kernels' bodies (two channels, a float2 variance) are this pass's own.
+#include "pt_filter.hpp"
 
 namespace pt {
 
-constexpr uint32_t kDnMaxSize = 16384u;
 constexpr uint16_t kDnNaN16 = 0x7E00u;
-constexpr int kDnTile = 16;                                    // a workgroup is one 16 x 16 tile of pixels
-constexpr uint32_t kDnStagedMaxStep = 4u;                      // 16 + 4 * step pixels a side: 32 x 32 records at step 4
+constexpr int kDnTile = kFlTile;
 constexpr uint32_t kDnStagedBytes = 72u;                       // a staged record: four float4 and the float2 variance
 // per-pixel slots of Context::dnHistory, in float4 units of one frame each: the ping-pong pairs first
 enum { DN_HIST_D = 0, DN_HIST_S = 2, DN_MOMENTS = 4, DN_G0 = 6, DN_G1 = 8, DN_WORK_D = 10, DN_WORK_S = 12, DN_PAIRS = 14, DN_SLOTS = 17 };
 // behind them five float2 arrays (half a slot each): the lengths of both parities, the variance, the two work variances
 enum { DN_LEN = 0, DN_VAR = 2, DN_WORK_VAR = 3 };
-
-typedef uint16_t d4v __attribute__((ext_vector_type(4)));     // one fp16 RGBA texel
-typedef int16_t  ds4v __attribute__((ext_vector_type(4)));
 
 struct DnSettings { float maxFrames, depthThreshold, normalCosine, sigmaD, sigmaS, roughnessFraction; };
 
@@ -54,32 +46,24 @@ struct DnAtrousArgs {
     DnSettings s;
 };
 
-PT_DEV float dn_max0(float x) { return x > 0.0f ? x : 0.0f; }
 PT_DEV uint16_t dn_h(float x) { return x != x ? kDnNaN16 : f32_to_f16(x); }
-PT_DEV d4v dn_store(float4 c) { return d4v{ dn_h(c.x), dn_h(c.y), dn_h(c.z), dn_h(c.w) }; }
-PT_DEV float dn_lum(float4 c) { return ml_luminance(V3(c.x, c.y, c.z)); }
-// the noisy texel as the filter takes it: rgb all 0 when one of them is not finite, a hit distance that is not finite 0 (the ReLAX pack
-// leaves neither; a host that hands over something else cannot poison the history)
+PT_DEV h4v dn_store(float4 c) { return h4v{ dn_h(c.x), dn_h(c.y), dn_h(c.z), dn_h(c.w) }; }
+// the noisy texel as the filter takes it: the guarded rgb, a hit distance that is not finite 0 (the ReLAX pack leaves neither; a host
+// that hands over something else cannot poison the history)
 PT_DEV float4 dn_load(const void* tex, uint32_t i)
 {
-    const d4v q = gptr<d4v>(tex)[i];
-    const float r = f16_to_f32(q.x), g = f16_to_f32(q.y), b = f16_to_f32(q.z), a = f16_to_f32(q.w);
-    const bool ok = isfinite(r) && isfinite(g) && isfinite(b);
-    return float4{ ok ? r : 0.0f, ok ? g : 0.0f, ok ? b : 0.0f, isfinite(a) ? a : 0.0f };
+    const h4v q = gptr<h4v>(tex)[i];
+    const v3 c = fl_guard(fl_rgb16(q));
+    const float a = f16_to_f32(q.w);
+    return float4{ c.x, c.y, c.z, isfinite(a) ? a : 0.0f };
 }
-// wg and wn of stage 3 (stage 2 asks whether both are > 0)
-PT_DEV float dn_wg(v3 Np, v3 Pp, v3 Pq, float planeScale) { return dn_max0(1.0f - fabsf(dot(Np, Pq - Pp)) / planeScale); }
-PT_DEV float dn_wn(v3 Np, v3 Nq, float normalCosine) { return dn_max0((dot(Np, Nq) - normalCosine) / (1.0f - normalCosine)); }
-
-// hist + (cur - hist) * (1 / n)
-PT_DEV float dn_blend(float hist, float cur, float inv) { return hist + (cur - hist) * inv; }
 
 // one channel of stage 1: the validated bilinear read of the history and the accumulation. q[t] = the four taps' colour, m[t] = their two
 // moments, l[t] = their length; a tap with ok[t] false was not read.
 struct DnChannel { float4 colour; float m1, m2, length; };
 PT_DEV DnChannel dn_accumulate(const bool ok[4], const float w[4], const float4 q[4], const float2 m[4], const float l[4], float4 cur, float cap)
 {
-    const float L = dn_lum(cur);
+    const float L = fl_lum(cur);
     DnChannel out{ cur, L, L * L, 1.0f };                      // disoccluded: the input, length 1
     float wsum = 0.0f;
     for (int t = 0; t < 4; ++t) if (ok[t]) wsum = wsum + w[t];
@@ -93,8 +77,8 @@ PT_DEV DnChannel dn_accumulate(const bool ok[4], const float w[4], const float4 
     const float n1 = h[6] + 1.0f;
     const float n = n1 < cap ? n1 : cap;
     const float inv = 1.0f / n;
-    out.colour = float4{ dn_blend(h[0], cur.x, inv), dn_blend(h[1], cur.y, inv), dn_blend(h[2], cur.z, inv), dn_blend(h[3], cur.w, inv) };
-    out.m1 = dn_blend(h[4], out.m1, inv); out.m2 = dn_blend(h[5], out.m2, inv); out.length = n;
+    out.colour = float4{ fl_blend(h[0], cur.x, inv), fl_blend(h[1], cur.y, inv), fl_blend(h[2], cur.z, inv), fl_blend(h[3], cur.w, inv) };
+    out.m1 = fl_blend(h[4], out.m1, inv); out.m2 = fl_blend(h[5], out.m2, inv); out.length = n;
     return out;
 }
 
@@ -108,31 +92,27 @@ __global__ __launch_bounds__(256) void k_dn_temporal(DnTemporalArgs a)
     if (!isfinite(z)) {                                        // the G-buffer missed: Noisy -> Denoised bit for bit, length 0, never a tap
         a.g0[i] = float4{ 0.0f, 0.0f, 0.0f, z }; a.g1[i] = zero4;
         a.histD[i] = zero4; a.histS[i] = zero4; a.moments[i] = zero4; a.len[i] = float2{ 0.0f, 0.0f }; a.var[i] = float2{ 0.0f, 0.0f };
-        const d4v d = gptr<d4v>(a.noisyD)[i], s = gptr<d4v>(a.noisyS)[i];
-        ((PT_GLOBAL_AS d4v*)a.outD)[i] = d; ((PT_GLOBAL_AS d4v*)a.outS)[i] = s;
+        const h4v d = gptr<h4v>(a.noisyD)[i], s = gptr<h4v>(a.noisyS)[i];
+        ((PT_GLOBAL_AS h4v*)a.outD)[i] = d; ((PT_GLOBAL_AS h4v*)a.outS)[i] = s;
         return;
     }
-    const ds4v nr = gptr<ds4v>(a.normalRoughness)[i];
+    const s4v nr = gptr<s4v>(a.normalRoughness)[i];
     const v3 N = V3(snorm16_to_f32(nr.x), snorm16_to_f32(nr.y), snorm16_to_f32(nr.z));
     const float r = snorm16_to_f32(nr.w);
     const float4 P = a.position[i];
-    const d4v mvh = gptr<d4v>(a.motion)[i];
+    const h4v mvh = gptr<h4v>(a.motion)[i];
     const float mvx = f16_to_f32(mvh.x), mvy = f16_to_f32(mvh.y), mvz = f16_to_f32(mvh.z);
     const float4 curD = dn_load(a.noisyD, i), curS = dn_load(a.noisyS, i);
 
     // the previous position and the four taps around it, row-major
-    const float fx = (((float)x + 0.5f) + mvx) - 0.5f, fy = (((float)y + 0.5f) + mvy) - 0.5f;
-    const float x0 = floorf(fx), y0 = floorf(fy);
-    const float tx = fx - x0, ty = fy - y0;
+    const FlTaps taps((((float)x + 0.5f) + mvx) - 0.5f, (((float)y + 0.5f) + mvy) - 0.5f, a.W, a.H);
     const float zp = z + mvz, zTol = a.s.depthThreshold * fabsf(zp);
-    const float wx[2] = { 1.0f - tx, tx }, wy[2] = { 1.0f - ty, ty };
     bool okD[4], okS[4]; float w[4], lD[4], lS[4]; float4 qD[4], qS[4]; float2 mD[4], mS[4];
     for (int t = 0; t < 4; ++t) {
-        const float xf = x0 + (float)(t & 1), yf = y0 + (float)(t >> 1);
-        w[t] = wx[t & 1] * wy[t >> 1];
+        w[t] = taps.weight(t);
         okD[t] = okS[t] = false;
-        if (a.reset || !(xf >= 0.0f && xf <= (float)(a.W - 1u) && yf >= 0.0f && yf <= (float)(a.H - 1u))) continue;
-        const uint32_t j = (uint32_t)yf * a.W + (uint32_t)xf;
+        if (a.reset || !taps.inside(t)) continue;
+        const uint32_t j = taps.index(t);
         const float4 g0 = a.prevG0[j], g1 = a.prevG1[j];
         const bool geometry = fabsf(g0.w - zp) <= zTol && dot(N, V3(g1.x, g1.y, g1.z)) >= a.s.normalCosine;
         const float2 len = a.prevLen[j];
@@ -142,19 +122,12 @@ __global__ __launch_bounds__(256) void k_dn_temporal(DnTemporalArgs a)
         const float4 m = a.prevMoments[j];
         qD[t] = a.prevD[j]; qS[t] = a.prevS[j]; mD[t] = float2{ m.x, m.y }; mS[t] = float2{ m.z, m.w }; lD[t] = len.x; lS[t] = len.y;
     }
-    // the specular history is shorter on smooth surfaces that moved (surface motion only: no virtual motion)
-    float capS = a.s.maxFrames;
-    if (mvx * mvx + mvy * mvy > 0.0625f) {
-        float t = r / 0.5f;
-        t = t < 1.0f ? t : 1.0f;
-        capS = 1.0f + floorf((a.s.maxFrames - 1.0f) * dn_max0(t));
-    }
     const DnChannel D = dn_accumulate(okD, w, qD, mD, lD, curD, a.s.maxFrames);
-    const DnChannel S = dn_accumulate(okS, w, qS, mS, lS, curS, capS);
+    const DnChannel S = dn_accumulate(okS, w, qS, mS, lS, curS, fl_specular_cap(a.s.maxFrames, r, mvx, mvy));
     a.g0[i] = float4{ P.x, P.y, P.z, z }; a.g1[i] = float4{ N.x, N.y, N.z, r };
     a.histD[i] = D.colour; a.histS[i] = S.colour;
     a.moments[i] = float4{ D.m1, D.m2, S.m1, S.m2 }; a.len[i] = float2{ D.length, S.length };
-    if (a.store) { ((PT_GLOBAL_AS d4v*)a.outD)[i] = dn_store(D.colour); ((PT_GLOBAL_AS d4v*)a.outS)[i] = dn_store(S.colour); }
+    if (a.store) { ((PT_GLOBAL_AS h4v*)a.outD)[i] = dn_store(D.colour); ((PT_GLOBAL_AS h4v*)a.outS)[i] = dn_store(S.colour); }
 }
 
 __global__ __launch_bounds__(256) void k_dn_variance(DnVarianceArgs a)
@@ -166,7 +139,7 @@ __global__ __launch_bounds__(256) void k_dn_variance(DnVarianceArgs a)
     if (!isfinite(g0.w)) return;                               // stage 1 wrote 0
     const float4 m = a.moments[i];
     const float2 n = a.len[i];
-    float vD = dn_max0(m.y - m.x * m.x), vS = dn_max0(m.w - m.z * m.z);
+    float vD = fl_max0(m.y - m.x * m.x), vS = fl_max0(m.w - m.z * m.z);
     if (n.x < 4.0f || n.y < 4.0f) {                            // a short history: the moments of the 7 x 7 neighbourhood on the same surface
         const float4 g1 = a.g1[i];
         const v3 Pp = V3(g0.x, g0.y, g0.z), Np = V3(g1.x, g1.y, g1.z);
@@ -180,14 +153,14 @@ __global__ __launch_bounds__(256) void k_dn_variance(DnVarianceArgs a)
                 const float4 q0 = a.g0[j];
                 if (!isfinite(q0.w)) continue;
                 const float4 q1 = a.g1[j];
-                if (!(dn_wg(Np, Pp, V3(q0.x, q0.y, q0.z), planeScale) > 0.0f && dn_wn(Np, V3(q1.x, q1.y, q1.z), a.s.normalCosine) > 0.0f)) continue;
+                if (!(fl_wg(Np, Pp, V3(q0.x, q0.y, q0.z), planeScale) > 0.0f && fl_wn(Np, V3(q1.x, q1.y, q1.z), a.s.normalCosine) > 0.0f)) continue;
             }
-            const float LD = dn_lum(a.histD[j]), LS = dn_lum(a.histS[j]);
+            const float LD = fl_lum(a.histD[j]), LS = fl_lum(a.histS[j]);
             s1D = s1D + LD; s2D = s2D + LD * LD; s1S = s1S + LS; s2S = s2S + LS * LS; count = count + 1.0f;
         }
         const float m1D = s1D / count, m2D = s2D / count, m1S = s1S / count, m2S = s2S / count;
-        if (n.x < 4.0f) vD = dn_max0(m2D - m1D * m1D);
-        if (n.y < 4.0f) vS = dn_max0(m2S - m1S * m1S);
+        if (n.x < 4.0f) vD = fl_max0(m2D - m1D * m1D);
+        if (n.y < 4.0f) vS = fl_max0(m2S - m1S * m1S);
     }
     a.var[i] = float2{ vD, vS };
 }
@@ -240,14 +213,13 @@ __global__ __launch_bounds__(256) void k_dn_atrous(DnAtrousArgs a)
         if (xq < 0 || xq >= W || yq < 0 || yq >= H) continue;
         const DnTap q = fetch(xq, yq, false);
         if (!isfinite(q.g0.w)) continue;
-        const float k = (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f);
+        const float k = fl_blur3(dx, dy);
         bD = bD + k * q.var.x; bS = bS + k * q.var.y; bw = bw + k;
     }
     const float sdD = a.s.sigmaD * sqrtf(bD / bw) + 1e-4f, sdS = a.s.sigmaS * sqrtf(bS / bw) + 1e-4f;
     const v3 Pp = V3(p.g0.x, p.g0.y, p.g0.z), Np = V3(p.g1.x, p.g1.y, p.g1.z);
     const float rp = p.g1.w, planeScale = a.s.depthThreshold * fabsf(p.g0.w);
-    const float LDp = dn_lum(p.cD), LSp = dn_lum(p.cS);
-    const float h[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
+    const float LDp = fl_lum(p.cD), LSp = fl_lum(p.cS);
     float4 sD{ 0.0f, 0.0f, 0.0f, 0.0f }, sS{ 0.0f, 0.0f, 0.0f, 0.0f };
     float wsD = 0.0f, wsS = 0.0f, vD = 0.0f, vS = 0.0f;
     for (int dy = -2; dy <= 2; ++dy) for (int dx = -2; dx <= 2; ++dx) {
@@ -259,11 +231,10 @@ __global__ __launch_bounds__(256) void k_dn_atrous(DnAtrousArgs a)
             if (xq < 0 || xq >= W || yq < 0 || yq >= H) continue;
             q = fetch(xq, yq, true);
             if (!isfinite(q.g0.w)) continue;
-            const float base = ((h[dy + 2] * h[dx + 2]) * dn_wg(Np, Pp, V3(q.g0.x, q.g0.y, q.g0.z), planeScale)) * dn_wn(Np, V3(q.g1.x, q.g1.y, q.g1.z), a.s.normalCosine);
-            const float rq = q.g1.w;
-            const float wr = dn_max0(1.0f - fabsf(rq - rp) / (a.s.roughnessFraction * (rp > rq ? rp : rq) + 1e-6f));
-            wD = base * dn_max0(1.0f - fabsf(dn_lum(q.cD) - LDp) / sdD);
-            wS = (base * dn_max0(1.0f - fabsf(dn_lum(q.cS) - LSp) / sdS)) * wr;
+            const float base = ((fl_h5(dy) * fl_h5(dx)) * fl_wg(Np, Pp, V3(q.g0.x, q.g0.y, q.g0.z), planeScale)) * fl_wn(Np, V3(q.g1.x, q.g1.y, q.g1.z), a.s.normalCosine);
+            const float wr = fl_wr(rp, q.g1.w, a.s.roughnessFraction);
+            wD = base * fl_max0(1.0f - fabsf(fl_lum(q.cD) - LDp) / sdD);
+            wS = (base * fl_max0(1.0f - fabsf(fl_lum(q.cS) - LSp) / sdS)) * wr;
         }
         if (wD > 0.0f) {
             wsD = wsD + wD; vD = vD + (wD * wD) * q.var.x;
@@ -275,7 +246,7 @@ __global__ __launch_bounds__(256) void k_dn_atrous(DnAtrousArgs a)
         }
     }
     const float4 oD{ sD.x / wsD, sD.y / wsD, sD.z / wsD, sD.w / wsD }, oS{ sS.x / wsS, sS.y / wsS, sS.z / wsS, sS.w / wsS };
-    if (a.last) { ((PT_GLOBAL_AS d4v*)a.texD)[i] = dn_store(oD); ((PT_GLOBAL_AS d4v*)a.texS)[i] = dn_store(oS); }
+    if (a.last) { ((PT_GLOBAL_AS h4v*)a.texD)[i] = dn_store(oD); ((PT_GLOBAL_AS h4v*)a.texS)[i] = dn_store(oS); }
     else { a.outD[i] = oD; a.outS[i] = oS; a.outVar[i] = float2{ vD / (wsD * wsD), vS / (wsS * wsS) }; }
 }
 
@@ -283,7 +254,7 @@ __global__ __launch_bounds__(256) void k_dn_atrous(DnAtrousArgs a)
 // by 2.5x, 2.1x and 1.3x ("Denoiser") -- unless PT_DENOISER_FORM_DIRECT pins the direct one
 static bool dn_staged(const Context& c, uint32_t step)
 {
-    return step <= kDnStagedMaxStep && !(c.debugFlags & PT_DENOISER_FORM_DIRECT);
+    return step <= kFlStagedMaxStep && !(c.debugFlags & PT_DENOISER_FORM_DIRECT);
 }
 
 } // namespace pt
@@ -293,8 +264,7 @@ using namespace pt;
 // nullptr when the settings are in range, else the message of the refusal
 static const char* dn_check_settings(const PtDenoiserSettings* s)
 {
-    if (!(s->RenderSize[0] >= 1u && s->RenderSize[0] <= kDnMaxSize && s->RenderSize[1] >= 1u && s->RenderSize[1] <= kDnMaxSize))
-        return "RenderSize must be 1..16384 on both axes";
+    if (const char* refusal = fl_check_sizes(s->RenderSize)) return refusal;
     if (!(s->MaxAccumulatedFrames >= 1u && s->MaxAccumulatedFrames <= 255u)) return "MaxAccumulatedFrames must be 1..255";
     if (s->AtrousIterations > 8u) return "AtrousIterations must be 0..8";
     if (!(s->DepthThreshold > 0.0f && s->DepthThreshold <= 1.0f)) return "DepthThreshold must be in (0, 1]";
@@ -310,21 +280,13 @@ extern "C" {
 int pt_denoiser_set_constants(PtContext* ctx, const PtDenoiserSettings* s)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
-    Context& c = ctx->c;
-    API_ARG(&c, s, "settings is NULL");
-    if (const char* refusal = dn_check_settings(s)) return fail(&c, PT_ERROR_INVALID_ARGUMENT, refusal);
-    PtDenoiserSettings next = *s;
-    memset(next._pad, 0, sizeof next._pad);
-    if (!c.haveDn || memcmp(&next, &c.dn, sizeof next) != 0) c.dnFrames = 0;      // a change of settings (RenderSize among them) restarts the history
-    c.dn = next;
-    c.haveDn = true;
-    return PT_OK;
+    return fl_set_constants(ctx->c, s, dn_check_settings, ctx->c.dn, ctx->c.dnState);
 }
 
 int pt_denoiser_reset_history(PtContext* ctx)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
-    ctx->c.dnFrames = 0;
+    ctx->c.dnState.frames = 0;
     return PT_OK;
 }
 
@@ -333,30 +295,22 @@ int pt_denoiser_process(PtContext* ctx, const struct PtDenoiserTextures* t)
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
     Context& c = ctx->c;
     API_ARG(&c, t, "textures is NULL");
-    if (!c.haveDn) return fail(&c, PT_ERROR_INVALID_ARGUMENT, "call pt_denoiser_set_constants first");
-    const struct { const char* name; const void* p; uint32_t texel; } bound[8] = {
+    if (!c.dnState.have) return fail(&c, PT_ERROR_INVALID_ARGUMENT, "call pt_denoiser_set_constants first");
+    const BoundTexture bound[8] = {
         { "Position", t->Position, 16 }, { "LinearDepth", t->LinearDepth, 4 }, { "NormalRoughness", t->NormalRoughness, 8 },
         { "MotionVector", t->MotionVector, 8 }, { "NoisyDiffuse", t->NoisyDiffuse, 8 }, { "NoisySpecular", t->NoisySpecular, 8 },
         { "DenoisedDiffuse", t->DenoisedDiffuse, 8 }, { "DenoisedSpecular", t->DenoisedSpecular, 8 } };
-    for (const auto& b : bound) if (!b.p) return fail(&c, PT_ERROR_INVALID_ARGUMENT, std::string(b.name) + " is NULL");
-    for (const auto& b : bound) if ((uintptr_t)b.p & (b.texel - 1u))
-        return fail(&c, PT_ERROR_INVALID_ARGUMENT, std::string(b.name) + " is not aligned to its texel (" + std::to_string(b.texel) + " bytes)");
+    if (int refusal = fl_check_bound(c, bound)) return refusal;
     const PtDenoiserSettings& s = c.dn;
     const uint32_t W = s.RenderSize[0], H = s.RenderSize[1];
     const size_t n = (size_t)W * H;
     API_HIP(&c, hipSetDevice(c.device));
-    if (c.dnHistory.capacity() < n * DN_SLOTS) {               // transactional: the old history stays until the new one exists
-        DeviceBuffer<float4> fresh;
-        API_HIP(&c, fresh.reserve(n * DN_SLOTS));
-        API_HIP(&c, hipStreamSynchronize(c.stream));           // an earlier call may still use the old one
-        c.dnHistory = std::move(fresh);
-        c.dnFrames = 0;
-    }
+    if (int e = fl_grow_history(c, c.dnState, { { c.dnHistory, n * DN_SLOTS } })) return e;
     if (s.AtrousIterations >= 3u && dn_staged(c, 4u))           // the staged tile of step 4 is beyond the 64 kB a launch gets unasked
         API_HIP(&c, hipFuncSetAttribute((const void*)k_dn_atrous<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 32 * (int)kDnStagedBytes));
     float4* base = c.dnHistory.data();
     float2* halves = (float2*)(base + n * DN_PAIRS);
-    const uint32_t cur = c.dnParity ^ 1u, prev = c.dnParity;
+    const uint32_t cur = c.dnState.parity ^ 1u, prev = c.dnState.parity;
     auto slot = [&](int first, uint32_t parity) { return base + n * (first + parity); };
 
     const DnSettings ds{ (float)s.MaxAccumulatedFrames, s.DepthThreshold, s.NormalCosine, s.DiffuseLuminanceSigma, s.SpecularLuminanceSigma, s.RoughnessFraction };
@@ -368,7 +322,7 @@ int pt_denoiser_process(PtContext* ctx, const struct PtDenoiserTextures* t)
     ta.len = halves + n * (DN_LEN + cur); ta.var = halves + n * DN_VAR;
     ta.prevD = slot(DN_HIST_D, prev); ta.prevS = slot(DN_HIST_S, prev); ta.prevMoments = slot(DN_MOMENTS, prev); ta.prevG0 = slot(DN_G0, prev);
     ta.prevG1 = slot(DN_G1, prev); ta.prevLen = halves + n * (DN_LEN + prev);
-    ta.W = W; ta.H = H; ta.reset = c.dnFrames == 0 ? 1u : 0u; ta.store = s.AtrousIterations == 0u ? 1u : 0u; ta.s = ds;
+    ta.W = W; ta.H = H; ta.reset = c.dnState.frames == 0 ? 1u : 0u; ta.store = s.AtrousIterations == 0u ? 1u : 0u; ta.s = ds;
     k_dn_temporal<<<grid, block, 0, c.stream>>>(ta);
     if (s.AtrousIterations) {
         DnVarianceArgs va{ ta.histD, ta.histS, ta.moments, ta.g0, ta.g1, ta.len, ta.var, W, H, ds };
@@ -387,9 +341,7 @@ int pt_denoiser_process(PtContext* ctx, const struct PtDenoiserTextures* t)
         }
     }
     API_HIP(&c, hipGetLastError());
-    c.dnParity = cur;
-    c.dnFrames += 1;
-    c.dnSize[0] = W; c.dnSize[1] = H;
+    c.dnState.advance(W, H);
     return PT_OK;
 }
 
@@ -400,13 +352,12 @@ int pt_denoiser_download_history(PtContext* ctx, float* host_length, uint64_t ca
     API_ARG(&c, out_w && out_h && (host_length || capacity_pixels == 0), "out_w / out_h / host_length is NULL");
     API_HIP(&c, hipSetDevice(c.device));
     API_HIP(&c, hipStreamSynchronize(c.stream));
-    const bool have = c.dnFrames != 0;                         // after a reset there is no history to show: 0 x 0
-    *out_w = have ? c.dnSize[0] : 0u; *out_h = have ? c.dnSize[1] : 0u;
+    *out_w = c.dnState.shown(0); *out_h = c.dnState.shown(1);
     const size_t n = (size_t)*out_w * *out_h;
     const size_t count = (size_t)std::min<uint64_t>(capacity_pixels, n);
     if (!count) return PT_OK;
     std::vector<float2> both(count);
-    const float2* len = (const float2*)(c.dnHistory.data() + n * DN_PAIRS) + n * (DN_LEN + c.dnParity);
+    const float2* len = (const float2*)(c.dnHistory.data() + n * DN_PAIRS) + n * (DN_LEN + c.dnState.parity);
     API_HIP(&c, hipMemcpy(both.data(), len, count * sizeof(float2), hipMemcpyDeviceToHost));
     for (size_t k = 0; k < count; ++k) host_length[k] = both[k].x;   // the diffuse length (the specular one differs only where its own tests do)
     return PT_OK;

@@ -162,6 +162,16 @@ struct DeviceCounters {
     unsigned int maxNodesPerRay, _pad2;      // PT_DEBUG_TRAVERSAL_STATS, streaming traversal: the longest walk
 };
 
+// What each of the three screen-space filters (pt_filter.hpp) keeps between calls, beside its settings and its history buffers.
+struct FilterState {
+    bool have = false;                       // pt_*_set_constants has accepted settings
+    uint32_t parity = 0;                     // which half of each ping-pong pair of the history the last call wrote
+    uint64_t frames = 0;                     // calls since the history was last reset; 0: the next call finds none
+    uint32_t size[4] = {0, 0, 0, 0};         // the frame the history was laid out for by the last call: w, h (and the output's w, h)
+    void advance(uint32_t w, uint32_t h, uint32_t ow = 0, uint32_t oh = 0) { parity ^= 1u; frames += 1; size[0] = w; size[1] = h; size[2] = ow; size[3] = oh; }
+    uint32_t shown(int k) const { return frames != 0 ? size[k] : 0u; }   // after a reset there is no history to show: 0 x 0
+};
+
 struct Context {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -280,29 +290,20 @@ struct Context {
 
     // denoiser (pt_denoise.hip): every per-pixel array of the history in one grow-only allocation, 17 float4 per pixel of the frame (the
     // ping-pong pairs of the accumulated colours, moments and guide records, the a-trous work buffers, the lengths and variances)
-    PtDenoiserSettings dn{}; bool haveDn = false;
+    PtDenoiserSettings dn{}; FilterState dnState;     // size: the frame of the last pt_denoiser_process
     DeviceBuffer<float4> dnHistory;
-    uint32_t dnSize[2] = {0, 0};                      // the frame the history was laid out for by the last pt_denoiser_process
-    uint32_t dnParity = 0;                            // which half of each pair the last call wrote
-    uint64_t dnFrames = 0;                            // calls since the history was last reset; 0: the next call finds none
 
     // upscaler (pt_upscale.hip): the history in one grow-only allocation, per output pixel two parities of a float4 (the colour in the
     // tone-mapped space and the accumulated weight n) and, behind them, two parities of the depth: 40 B
-    PtUpscalerSettings up{}; bool haveUp = false;
+    PtUpscalerSettings up{}; FilterState upState;     // size: the output frame of the last pt_upscaler_process
     DeviceBuffer<float4> upHistory;
-    uint32_t upSize[2] = {0, 0};                      // the output frame the history was laid out for by the last pt_upscaler_process
-    uint32_t upParity = 0;                            // which parity the last call wrote
-    uint64_t upFrames = 0;                            // calls since the history was last reset; 0: the next call finds none
 
     // ray reconstruction (pt_reconstruct.hip): two grow-only allocations. rrHistory, per render pixel ten float4 (two parities of the
     // signal with its length and of the two guide records, the albedo, the a-trous ping-pong, two parities of the moments): 160 B.
     // rrOutput, per output pixel two parities of a float4 (tone-mapped colour, n) and of the depth: 40 B. It shares nothing with the upscaler.
-    PtReconstructionSettings rr{}; bool haveRr = false;
+    PtReconstructionSettings rr{}; FilterState rrState;   // size: render w, h and output w, h of the last pt_reconstruction_process
     DeviceBuffer<float4> rrHistory, rrOutput;
-    uint32_t rrSize[4] = {0, 0, 0, 0};                // render w, h and output w, h the history was laid out for by the last pt_reconstruction_process
-    uint32_t rrParity = 0;                            // which parity the last call wrote
     uint32_t rrFinal = 0;                             // which a-trous work buffer holds the last call's filtered signal
-    uint64_t rrFrames = 0;                            // calls since the history was last reset; 0: the next call finds none
 
     // SHARC radiance cache (pt_sharc.hip): per context, also for a context that views another's scene. sharcVoxels[sharcParity] is VoxelData (this
     // frame's deposits, then the resolved cache), the other one PreviousVoxelData; they swap after the query.

@@ -8,10 +8,11 @@
 //   k_rr_variance          stage 2: the variance of the luminance, from the moments (length >= 4) or from the 7 x 7 neighbourhood
 //   k_rr_atrous<STAGED>    stage 3: one 5 x 5 edge-stopping a-trous iteration at step 1, 2, 4, ...; STAGED: the 16 x 16 tile and its halo go
 //                          through LDS first, else every tap is a global load. Same taps, same order, same arithmetic: the same bits.
-//   k_rr_resolve           stage 4, output size: the nearest render sample under the jitter, the 3 x 3 dilation of depth and motion, the
-//                          kernel-weighted current colour (filtered signal x the tap's own albedo) and its clamp box, four validated
-//                          bilinear taps of the previous output, the blend; writes Color and the new output history
-// One signal (Radiance, direct + indirect) where pt_denoise.hip carries two; no pack and no compose pass. Not a port of DLSS Ray
+//   k_rr_resolve           stage 4, output size: the upscaler's steps 1-6 (fl_resolve, pt_filter.hpp; k_upscale runs the same function)
+//                          over taps whose colour is the filtered signal x the tap's own albedo, on this pass's own output history;
+//                          writes Color
+// One signal (Radiance, direct + indirect) where pt_denoise.hip carries two; no pack and no compose pass. Stages 1-3 share their small
+// arithmetic and the set-up of the history taps with the denoiser (pt_filter.hpp); the bodies stay this pass's own. Not a port of DLSS Ray
 // Reconstruction (a closed SDK the reference tree does not carry): DESIGN.md section 1, "Ray reconstruction", is the arithmetic spec and
 // tests/reconstructref.py restates it. Plain fp32 operations, one rounding each (-ffp-contract=off); the only fused operations are those
 // of dot() / ml_luminance(); no library transcendental. SpecularHitDistance is not read: reprojection follows the surface motion only
@@ -20,29 +21,17 @@
 // History, context-owned and grow-only. Per render pixel 160 B: two parities of (signal, length), of the two moments and of the two
 // guide records (112 B), the albedo (16 B), the a-trous ping-pong of (signal, variance) (32 B), the later of which holds the filtered
 // signal. Per output pixel 40 B: two parities of (tone-mapped colour, n) and of the depth.
-#include "pt_internal.hpp"
-
-#include <cmath>
-#include <cstring>
-#include <vector>
+#include "pt_filter.hpp"
 
 namespace pt {
 
-constexpr uint32_t kRrMaxSize = 16384u;
-constexpr int kRrTile = 16;                                    // a workgroup is one 16 x 16 tile of pixels
-constexpr uint32_t kRrStagedMaxStep = 4u;                      // 16 + 4 * step pixels a side: 32 x 32 records at step 4
+constexpr int kRrTile = kFlTile;
 constexpr uint32_t kRrStagedBytes = 48u;                       // a staged record: three float4 (48 kB at step 4: within what a launch gets unasked)
 constexpr float kRrAlbedoFloor = 0.015625f;                    // 1 / 64: the least albedo sum a signal is divided by
 constexpr float kRrAlbedoCeiling = 131008.0f;                  // 2 x 65504: the sum of two finite fp16 values is below it
-constexpr float kRrWeightFloor = 0.015625f;                    // 1 / 64: the least weight of the nearest sample
-constexpr float kRrDenominatorFloor = 7.62939453125e-06f;      // 2^-17: the guard of the inverse tone map
-constexpr float kRrMax16 = 65504.0f;
 constexpr float kRrResetRatio = 16.0f;                         // the luminance reset of stage 1: four stops against the history
 // per-render-pixel slots of Context::rrHistory, in float4 units of one frame each; behind them two float2 arrays (the moments' parities)
 enum { RR_HIST = 0, RR_G0 = 2, RR_G1 = 4, RR_ALBEDO = 6, RR_WORK = 7, RR_SLOTS4 = 9, RR_SLOTS = 10 };
-
-typedef uint16_t r4v __attribute__((ext_vector_type(4)));     // one fp16 RGBA texel
-typedef int16_t  rs4v __attribute__((ext_vector_type(4)));
 
 struct RrSettings { float maxFrames, depthThreshold, normalCosine, sigma, roughnessFraction; };
 
@@ -66,28 +55,9 @@ struct RrAtrousArgs {
     RrSettings s;
 };
 
-struct RrResolveArgs {
-    const float4 *filtered, *albedo; const float* depth; const void* motion; void* color;
-    float4* hist; float* histZ;                                // this frame's parity, written
-    const float4* prevHist; const float* prevZ;                // the last frame's
-    uint32_t Rw, Rh, Ow, Oh, reset;                            // reset: no history
-    float sx, sy, jx, jy, maxFrames, r2, tau;                  // s = RenderSize / OutputSize, r2 = KernelRadius^2
-};
+struct RrResolveArgs { const float4 *filtered, *albedo; const float* depth; const void* motion; FlResolveArgs r; };
 
-PT_DEV float rr_max0(float x) { return x > 0.0f ? x : 0.0f; }
-PT_DEV float rr_max3(float r, float g, float b) { const float m = r > g ? r : g; return m > b ? m : b; }
-PT_DEV float rr_lum(float4 c) { return ml_luminance(V3(c.x, c.y, c.z)); }
-PT_DEV v3 rr_rgb16(const void* tex, uint32_t i)
-{
-    const r4v q = gptr<r4v>(tex)[i];
-    return V3(f16_to_f32(q.x), f16_to_f32(q.y), f16_to_f32(q.z));
-}
-// the Radiance texel as the filter takes it: rgb all 0 when one of them is not finite
-PT_DEV v3 rr_load(const void* tex, uint32_t i)
-{
-    const v3 c = rr_rgb16(tex, i);
-    return isfinite(c.x) && isfinite(c.y) && isfinite(c.z) ? c : V3(0.0f, 0.0f, 0.0f);
-}
+PT_DEV v3 rr_rgb16(const void* tex, uint32_t i) { return fl_rgb16(gptr<h4v>(tex)[i]); }
 // one channel of the albedo sum: floored (a NaN reads as the floor), then kept finite
 PT_DEV float rr_albedo(float d, float s)
 {
@@ -95,22 +65,11 @@ PT_DEV float rr_albedo(float d, float s)
     a = a > kRrAlbedoFloor ? a : kRrAlbedoFloor;
     return a < kRrAlbedoCeiling ? a : kRrAlbedoCeiling;
 }
-// wg and wn of stage 3 (stage 2 asks whether both are > 0)
-PT_DEV float rr_wg(v3 Np, v3 Pp, v3 Pq, float planeScale) { return rr_max0(1.0f - fabsf(dot(Np, Pq - Pp)) / planeScale); }
-PT_DEV float rr_wn(v3 Np, v3 Nq, float normalCosine) { return rr_max0((dot(Np, Nq) - normalCosine) / (1.0f - normalCosine)); }
 // the signal's luminance of a neighbour of stage 1's pixel, this frame's: the same operations as the pixel's own
 PT_DEV float rr_signal_luminance(const RrTemporalArgs& a, uint32_t j)
 {
-    const v3 rad = rr_load(a.radiance, j), Ad = rr_rgb16(a.diffuseAlbedo, j), As = rr_rgb16(a.specularAlbedo, j);
-    return rr_lum(float4{ rad.x / rr_albedo(Ad.x, As.x), rad.y / rr_albedo(Ad.y, As.y), rad.z / rr_albedo(Ad.z, As.z), 0.0f });
-}
-// hist + (cur - hist) * (1 / n)
-PT_DEV float rr_blend(float hist, float cur, float inv) { return hist + (cur - hist) * inv; }
-// floor((o + 0.5) s - jitter) clamped into the frame, as a float: the nearest render sample of an output coordinate
-PT_DEV float rr_nearest(float oc, float s, float j, float last)
-{
-    const float c = floorf(oc * s - j);
-    return c < 0.0f ? 0.0f : (c > last ? last : c);
+    const v3 rad = fl_guard(rr_rgb16(a.radiance, j)), Ad = rr_rgb16(a.diffuseAlbedo, j), As = rr_rgb16(a.specularAlbedo, j);
+    return fl_lum(float4{ rad.x / rr_albedo(Ad.x, As.x), rad.y / rr_albedo(Ad.y, As.y), rad.z / rr_albedo(Ad.z, As.z), 0.0f });
 }
 
 __global__ __launch_bounds__(256) void k_rr_temporal(RrTemporalArgs a)
@@ -119,7 +78,7 @@ __global__ __launch_bounds__(256) void k_rr_temporal(RrTemporalArgs a)
     if (x >= a.W || y >= a.H) return;
     const uint32_t i = y * a.W + x;
     const float z = a.depth[i];
-    const v3 rad = rr_load(a.radiance, i);
+    const v3 rad = fl_guard(rr_rgb16(a.radiance, i));
     const float4 zero4{ 0.0f, 0.0f, 0.0f, 0.0f };
     if (!isfinite(z)) {                                        // the G-buffer missed: the guarded Radiance goes to the resolve, length 0, never a tap
         a.g0[i] = float4{ 0.0f, 0.0f, 0.0f, z }; a.g1[i] = zero4;
@@ -128,36 +87,27 @@ __global__ __launch_bounds__(256) void k_rr_temporal(RrTemporalArgs a)
         a.out[i] = float4{ rad.x, rad.y, rad.z, 0.0f };
         return;
     }
-    const rs4v nr = gptr<rs4v>(a.normalRoughness)[i];
+    const s4v nr = gptr<s4v>(a.normalRoughness)[i];
     const v3 N = V3(snorm16_to_f32(nr.x), snorm16_to_f32(nr.y), snorm16_to_f32(nr.z));
     const float r = snorm16_to_f32(nr.w);
     const float4 P = a.position[i];
-    const r4v mvh = gptr<r4v>(a.motion)[i];
+    const h4v mvh = gptr<h4v>(a.motion)[i];
     const float mvx = f16_to_f32(mvh.x), mvy = f16_to_f32(mvh.y), mvz = f16_to_f32(mvh.z);
     const v3 Ad = rr_rgb16(a.diffuseAlbedo, i), As = rr_rgb16(a.specularAlbedo, i);
     const v3 A = V3(rr_albedo(Ad.x, As.x), rr_albedo(Ad.y, As.y), rr_albedo(Ad.z, As.z));
     const float4 cur{ rad.x / A.x, rad.y / A.y, rad.z / A.z, 0.0f };
-    const float L = rr_lum(cur);
+    const float L = fl_lum(cur);
 
-    // the cap of the history: shorter on smooth specular-dominated surfaces that moved (surface motion only: no virtual motion)
-    float cap = a.s.maxFrames;
-    if (ml_luminance(As) > ml_luminance(Ad) && mvx * mvx + mvy * mvy > 0.0625f) {
-        float t = r / 0.5f;
-        t = t < 1.0f ? t : 1.0f;
-        cap = 1.0f + floorf((a.s.maxFrames - 1.0f) * rr_max0(t));
-    }
+    // the cap of the history: the specular one on specular-dominated surfaces
+    const float cap = ml_luminance(As) > ml_luminance(Ad) ? fl_specular_cap(a.s.maxFrames, r, mvx, mvy) : a.s.maxFrames;
 
     // the previous position and the four taps around it, row-major
-    const float fx = (((float)x + 0.5f) + mvx) - 0.5f, fy = (((float)y + 0.5f) + mvy) - 0.5f;
-    const float x0 = floorf(fx), y0 = floorf(fy);
-    const float tx = fx - x0, ty = fy - y0;
+    const FlTaps taps((((float)x + 0.5f) + mvx) - 0.5f, (((float)y + 0.5f) + mvy) - 0.5f, a.W, a.H);
     const float zp = z + mvz, zTol = a.s.depthThreshold * fabsf(zp), planeScale = a.s.depthThreshold * fabsf(z);
-    const float wx[2] = { 1.0f - tx, tx }, wy[2] = { 1.0f - ty, ty };
     float wsum = 0.0f, h[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
     for (int t = 0; t < 4; ++t) {
-        const float xf = x0 + (float)(t & 1), yf = y0 + (float)(t >> 1);
-        if (a.reset || !(xf >= 0.0f && xf <= (float)(a.W - 1u) && yf >= 0.0f && yf <= (float)(a.H - 1u))) continue;
-        const uint32_t j = (uint32_t)yf * a.W + (uint32_t)xf;
+        if (a.reset || !taps.inside(t)) continue;
+        const uint32_t j = taps.index(t);
         const float4 g0 = a.prevG0[j], g1 = a.prevG1[j];
         const float4 q = a.prevHist[j];
         const bool sameSurface = fabsf(g0.w - zp) <= zTol || fabsf(dot(N, V3(g0.x, g0.y, g0.z) - V3(P.x, P.y, P.z))) <= planeScale;
@@ -165,7 +115,7 @@ __global__ __launch_bounds__(256) void k_rr_temporal(RrTemporalArgs a)
                      && fabsf(r - g1.w) <= a.s.roughnessFraction * (r > g1.w ? r : g1.w);
         if (!ok) continue;
         const float2 m = a.prevMoments[j];
-        const float w = wx[t & 1] * wy[t >> 1];
+        const float w = taps.weight(t);
         wsum = wsum + w;
         h[0] = h[0] + w * q.x; h[1] = h[1] + w * q.y; h[2] = h[2] + w * q.z;
         h[3] = h[3] + w * m.x; h[4] = h[4] + w * m.y; h[5] = h[5] + w * q.w;
@@ -178,7 +128,7 @@ __global__ __launch_bounds__(256) void k_rr_temporal(RrTemporalArgs a)
         // the luminance reset: sixteen times darker than the history less its deviation (a history of sparse outliers has sd >= mean and
         // never asks), or sixteen times brighter than the history plus its deviation with one of the eight neighbours of this frame at
         // least half as bright (a lone outlier keeps its history and is averaged in)
-        const float sd = sqrtf(rr_max0(h[4] - h[3] * h[3]));
+        const float sd = sqrtf(fl_max0(h[4] - h[3] * h[3]));
         if (L * kRrResetRatio < h[3] - sd) feature = 1.0f;
         else if (L > kRrResetRatio * (h[3] + sd)) {
             for (int dy = -1; dy <= 1; ++dy) for (int dx = -1; dx <= 1; ++dx) {
@@ -193,8 +143,8 @@ __global__ __launch_bounds__(256) void k_rr_temporal(RrTemporalArgs a)
         const float n1 = h[5] + 1.0f;
         const float n = n1 < cap ? n1 : cap;
         const float inv = 1.0f / n;
-        out = float4{ rr_blend(h[0], cur.x, inv), rr_blend(h[1], cur.y, inv), rr_blend(h[2], cur.z, inv), n };
-        mom = float2{ rr_blend(h[3], mom.x, inv), rr_blend(h[4], mom.y, inv) };
+        out = float4{ fl_blend(h[0], cur.x, inv), fl_blend(h[1], cur.y, inv), fl_blend(h[2], cur.z, inv), n };
+        mom = float2{ fl_blend(h[3], mom.x, inv), fl_blend(h[4], mom.y, inv) };
     }
     a.g0[i] = float4{ P.x, P.y, P.z, z }; a.g1[i] = float4{ N.x, N.y, N.z, r };
     a.hist[i] = out; a.moments[i] = mom;
@@ -210,7 +160,7 @@ __global__ __launch_bounds__(256) void k_rr_variance(RrVarianceArgs a)
     if (!isfinite(g0.w)) return;                               // stage 1 wrote the texel the resolve reads
     const float2 m = a.moments[i];
     const float4 c = a.hist[i];
-    float v = rr_max0(m.y - m.x * m.x);
+    float v = fl_max0(m.y - m.x * m.x);
     if (a.albedo[i].w != 0.0f) v = 0.0f;                       // the luminance reset took its history: stage 3 does not spread it
     else if (c.w < 4.0f) {                                          // a short history: the moments of the 7 x 7 neighbourhood on the same surface
         const float4 g1 = a.g1[i];
@@ -225,13 +175,13 @@ __global__ __launch_bounds__(256) void k_rr_variance(RrVarianceArgs a)
                 const float4 q0 = a.g0[j];
                 if (!isfinite(q0.w)) continue;
                 const float4 q1 = a.g1[j];
-                if (!(rr_wg(Np, Pp, V3(q0.x, q0.y, q0.z), planeScale) > 0.0f && rr_wn(Np, V3(q1.x, q1.y, q1.z), a.s.normalCosine) > 0.0f)) continue;
+                if (!(fl_wg(Np, Pp, V3(q0.x, q0.y, q0.z), planeScale) > 0.0f && fl_wn(Np, V3(q1.x, q1.y, q1.z), a.s.normalCosine) > 0.0f)) continue;
             }
-            const float Lq = rr_lum(a.hist[j]);
+            const float Lq = fl_lum(a.hist[j]);
             s1 = s1 + Lq; s2 = s2 + Lq * Lq; count = count + 1.0f;
         }
         const float m1 = s1 / count, m2 = s2 / count;
-        v = rr_max0(m2 - m1 * m1);
+        v = fl_max0(m2 - m1 * m1);
     }
     a.out[i] = float4{ c.x, c.y, c.z, v };
 }
@@ -278,14 +228,13 @@ __global__ __launch_bounds__(256) void k_rr_atrous(RrAtrousArgs a)
         if (xq < 0 || xq >= W || yq < 0 || yq >= H) continue;
         const RrTap q = fetch(xq, yq);
         if (!isfinite(q.g0.w)) continue;
-        const float k = (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f);
+        const float k = fl_blur3(dx, dy);
         b = b + k * q.c.w; bw = bw + k;
     }
     const float sd = a.s.sigma * sqrtf(b / bw) + 1e-4f;
     const v3 Pp = V3(p.g0.x, p.g0.y, p.g0.z), Np = V3(p.g1.x, p.g1.y, p.g1.z);
     const float rp = p.g1.w, planeScale = a.s.depthThreshold * fabsf(p.g0.w);
-    const float Lp = rr_lum(p.c);
-    const float h[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
+    const float Lp = fl_lum(p.c);
     float s[3] = { 0.0f, 0.0f, 0.0f }, ws = 0.0f, v = 0.0f;
     for (int dy = -2; dy <= 2; ++dy) for (int dx = -2; dx <= 2; ++dx) {
         const int xq = x + dx * step, yq = y + dy * step;
@@ -296,10 +245,9 @@ __global__ __launch_bounds__(256) void k_rr_atrous(RrAtrousArgs a)
             if (xq < 0 || xq >= W || yq < 0 || yq >= H) continue;
             q = fetch(xq, yq);
             if (!isfinite(q.g0.w)) continue;
-            const float base = ((h[dy + 2] * h[dx + 2]) * rr_wg(Np, Pp, V3(q.g0.x, q.g0.y, q.g0.z), planeScale)) * rr_wn(Np, V3(q.g1.x, q.g1.y, q.g1.z), a.s.normalCosine);
-            const float rq = q.g1.w;
-            const float wr = rr_max0(1.0f - fabsf(rq - rp) / (a.s.roughnessFraction * (rp > rq ? rp : rq) + 1e-6f));
-            w = (base * rr_max0(1.0f - fabsf(rr_lum(q.c) - Lp) / sd)) * wr;
+            const float base = ((fl_h5(dy) * fl_h5(dx)) * fl_wg(Np, Pp, V3(q.g0.x, q.g0.y, q.g0.z), planeScale)) * fl_wn(Np, V3(q.g1.x, q.g1.y, q.g1.z), a.s.normalCosine);
+            const float wr = fl_wr(rp, q.g1.w, a.s.roughnessFraction);
+            w = (base * fl_max0(1.0f - fabsf(fl_lum(q.c) - Lp) / sd)) * wr;
         }
         if (w > 0.0f) {
             ws = ws + w; v = v + (w * w) * q.c.w;
@@ -309,100 +257,27 @@ __global__ __launch_bounds__(256) void k_rr_atrous(RrAtrousArgs a)
     a.out[i] = float4{ s[0] / ws, s[1] / ws, s[2] / ws, v / (ws * ws) };
 }
 
+// A render texel as a tap of fl_resolve sees it: the filtered signal remodulated with the tap's own albedo (1 for a missed tap).
+struct RrSource {
+    const RrResolveArgs& a;
+    PT_DEV uint32_t at(int qx, int qy) const { return (uint32_t)qy * a.r.Rw + (uint32_t)qx; }
+    PT_DEV float depth(uint32_t j) const { return a.depth[j]; }
+    PT_DEV h4v motion(uint32_t j) const { return gptr<h4v>(a.motion)[j]; }
+    PT_DEV v3 colour(uint32_t j) const { const float4 f = a.filtered[j], A = a.albedo[j]; return V3(f.x * A.x, f.y * A.y, f.z * A.z); }
+};
+
 __global__ __launch_bounds__(256) void k_rr_resolve(RrResolveArgs a)
 {
-    const int Rw = (int)a.Rw, Rh = (int)a.Rh;
     const uint32_t ox = blockIdx.x * kRrTile + threadIdx.x, oy = blockIdx.y * kRrTile + threadIdx.y;
-    if (ox >= a.Ow || oy >= a.Oh) return;
-
-    // 1: position
-    const float oxc = (float)ox + 0.5f, oyc = (float)oy + 0.5f;
-    const float ux = oxc * a.sx, uy = oyc * a.sy;
-    const int cx = (int)rr_nearest(oxc, a.sx, a.jx, (float)(Rw - 1)), cy = (int)rr_nearest(oyc, a.sy, a.jy, (float)(Rh - 1));
-
-    // 2 and 3: the dilation and the current colour over the same 3 x 3 taps, row-major
-    float best = INFINITY;
-    uint32_t bj = 0;
-    bool found = false;
-    float wsum = 0.0f, k = 0.0f;
-    float acc[3] = { 0.0f, 0.0f, 0.0f }, lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-    for (int dy = -1; dy <= 1; ++dy) for (int dx = -1; dx <= 1; ++dx) {
-        const int qx = cx + dx, qy = cy + dy;
-        if (qx < 0 || qx >= Rw || qy < 0 || qy >= Rh) continue;
-        const uint32_t j = (uint32_t)qy * a.Rw + (uint32_t)qx;
-        const float zq = a.depth[j];
-        if (isfinite(zq) && zq < best) { best = zq; bj = j; found = true; }
-        const float ddx = (((float)qx + 0.5f) + a.jx) - ux, ddy = (((float)qy + 0.5f) + a.jy) - uy;
-        const float d2 = ddx * ddx + ddy * ddy;
-        float w = rr_max0(1.0f - d2 / a.r2);
-        w = w * w;
-        if (dx == 0 && dy == 0) { w = w < kRrWeightFloor ? kRrWeightFloor : w; k = w; }
-        const float4 f = a.filtered[j], A = a.albedo[j];
-        const float c[3] = { f.x * A.x, f.y * A.y, f.z * A.z };      // remodulated with the tap's own albedo (1 for a missed tap)
-        const float den = 1.0f + rr_max0(rr_max3(c[0], c[1], c[2]));
-        for (int ch = 0; ch < 3; ++ch) {
-            const float t = c[ch] / den;
-            lo[ch] = t < lo[ch] ? t : lo[ch]; hi[ch] = t > hi[ch] ? t : hi[ch];
-            if (w > 0.0f) acc[ch] = acc[ch] + w * t;
-        }
-        if (w > 0.0f) wsum = wsum + w;
-    }
-    const float cur[3] = { acc[0] / wsum, acc[1] / wsum, acc[2] / wsum };
-    const float z = best;
-    float mvx = 0.0f, mvy = 0.0f, mvz = 0.0f;
-    if (found) { const r4v m = gptr<r4v>(a.motion)[bj]; mvx = f16_to_f32(m.x); mvy = f16_to_f32(m.y); mvz = f16_to_f32(m.z); }
-
-    // 4: the previous output at (o + 0.5) + mv / s, four bilinear taps, row-major
-    const float fx = (oxc + mvx / a.sx) - 0.5f, fy = (oyc + mvy / a.sy) - 0.5f;
-    const float hx0 = floorf(fx), hy0 = floorf(fy);
-    const float tx = fx - hx0, ty = fy - hy0;
-    const float wx[2] = { 1.0f - tx, tx }, wy[2] = { 1.0f - ty, ty };
-    const float zp = z + mvz, tol = a.tau * fabsf(zp);
-    float hsum = 0.0f, h[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-    for (int t = 0; t < 4; ++t) {
-        const float xf = hx0 + (float)(t & 1), yf = hy0 + (float)(t >> 1);
-        if (a.reset || !(xf >= 0.0f && xf <= (float)(a.Ow - 1u) && yf >= 0.0f && yf <= (float)(a.Oh - 1u))) continue;
-        const uint32_t j = (uint32_t)yf * a.Ow + (uint32_t)xf;
-        const float zh = a.prevZ[j];
-        if (!(found ? fabsf(zh - zp) <= tol : !isfinite(zh))) continue;
-        const float w = wx[t & 1] * wy[t >> 1];
-        const float4 q = a.prevHist[j];
-        hsum = hsum + w;
-        h[0] = h[0] + w * q.x; h[1] = h[1] + w * q.y; h[2] = h[2] + w * q.z; h[3] = h[3] + w * q.w;
-    }
-
-    // 5: clamp and blend
-    float out[3] = { cur[0], cur[1], cur[2] }, n = k;          // disoccluded
-    if (hsum > 0.0f) {
-        const float n1 = h[3] / hsum + k;
-        n = n1 < a.maxFrames ? n1 : a.maxFrames;
-        const float alpha = k / n;
-        if (!(alpha >= 1.0f)) for (int ch = 0; ch < 3; ++ch) {
-            float hc = h[ch] / hsum;
-            hc = hc < lo[ch] ? lo[ch] : (hc > hi[ch] ? hi[ch] : hc);
-            out[ch] = hc + (cur[ch] - hc) * alpha;
-        }
-    }
-
-    // 6: store
-    const uint32_t i = oy * a.Ow + ox;
-    a.hist[i] = float4{ out[0], out[1], out[2], n };
-    a.histZ[i] = z;
-    float den = 1.0f - rr_max0(rr_max3(out[0], out[1], out[2]));
-    den = den < kRrDenominatorFloor ? kRrDenominatorFloor : den;
-    uint16_t c16[3];
-    for (int ch = 0; ch < 3; ++ch) {
-        const float c = out[ch] / den;
-        c16[ch] = f32_to_f16(c > kRrMax16 ? kRrMax16 : (c < -kRrMax16 ? -kRrMax16 : c));
-    }
-    ((PT_GLOBAL_AS r4v*)a.color)[i] = r4v{ c16[0], c16[1], c16[2], (uint16_t)0x3C00u };
+    if (ox >= a.r.Ow || oy >= a.r.Oh) return;
+    fl_resolve(a.r, ox, oy, RrSource{ a });
 }
 
 // the form pt_reconstruction_process takes for an a-trous step: the staged one wherever the tile's halo fits (steps 1, 2 and 4; DESIGN.md
 // section 4, "Ray reconstruction") unless PT_RECONSTRUCTION_FORM_DIRECT pins the direct one
 static bool rr_staged(const Context& c, uint32_t step)
 {
-    return step <= kRrStagedMaxStep && !(c.debugFlags & PT_RECONSTRUCTION_FORM_DIRECT);
+    return step <= kFlStagedMaxStep && !(c.debugFlags & PT_RECONSTRUCTION_FORM_DIRECT);
 }
 
 // which of the two work buffers holds the filtered signal after `iterations` a-trous launches: stage 2 writes the second one, iteration k
@@ -416,10 +291,7 @@ using namespace pt;
 // nullptr when the settings are in range, else the message of the refusal
 static const char* rr_check_settings(const PtReconstructionSettings* s)
 {
-    for (int k = 0; k < 2; ++k) if (!(s->RenderSize[k] >= 1u && s->RenderSize[k] <= kRrMaxSize)) return "RenderSize must be 1..16384 on both axes";
-    for (int k = 0; k < 2; ++k) if (!(s->OutputSize[k] >= 1u && s->OutputSize[k] <= kRrMaxSize)) return "OutputSize must be 1..16384 on both axes";
-    for (int k = 0; k < 2; ++k) if (!(s->RenderSize[k] <= s->OutputSize[k] && s->OutputSize[k] <= 4u * s->RenderSize[k]))
-        return "OutputSize must be RenderSize..4 RenderSize on both axes";
+    if (const char* refusal = fl_check_sizes(s->RenderSize, s->OutputSize)) return refusal;
     if (!(s->MaxAccumulatedFrames >= 1u && s->MaxAccumulatedFrames <= 255u)) return "MaxAccumulatedFrames must be 1..255";
     if (!(s->MaxOutputFrames >= 1u && s->MaxOutputFrames <= 255u)) return "MaxOutputFrames must be 1..255";
     if (s->AtrousIterations > 8u) return "AtrousIterations must be 0..8";
@@ -436,21 +308,13 @@ extern "C" {
 int pt_reconstruction_set_constants(PtContext* ctx, const PtReconstructionSettings* s)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
-    Context& c = ctx->c;
-    API_ARG(&c, s, "settings is NULL");
-    if (const char* refusal = rr_check_settings(s)) return fail(&c, PT_ERROR_INVALID_ARGUMENT, refusal);
-    PtReconstructionSettings next = *s;
-    memset(next._pad, 0, sizeof next._pad);
-    if (!c.haveRr || memcmp(&next, &c.rr, sizeof next) != 0) c.rrFrames = 0;      // a change of settings (a size among them) restarts the history
-    c.rr = next;
-    c.haveRr = true;
-    return PT_OK;
+    return fl_set_constants(ctx->c, s, rr_check_settings, ctx->c.rr, ctx->c.rrState);
 }
 
 int pt_reconstruction_reset_history(PtContext* ctx)
 {
     if (!ctx) return PT_ERROR_INVALID_ARGUMENT;
-    ctx->c.rrFrames = 0;
+    ctx->c.rrState.frames = 0;
     return PT_OK;
 }
 
@@ -460,43 +324,28 @@ int pt_reconstruction_process(PtContext* ctx, const struct PtReconstructionTextu
     Context& c = ctx->c;
     API_ARG(&c, t, "textures is NULL");
     API_ARG(&c, jitter, "jitter is NULL");
-    if (!c.haveRr) return fail(&c, PT_ERROR_INVALID_ARGUMENT, "call pt_reconstruction_set_constants first");
+    if (!c.rrState.have) return fail(&c, PT_ERROR_INVALID_ARGUMENT, "call pt_reconstruction_set_constants first");
     if (c.sharding.RankCount > 1u)
         return fail(&c, PT_ERROR_INVALID_ARGUMENT, "the reconstruction needs the whole frame: the context is sharded (run it on the gathered textures of an unsharded context)");
     const PtReconstructionSettings& s = c.rr;
     const uint32_t W = s.RenderSize[0], H = s.RenderSize[1], Ow = s.OutputSize[0], Oh = s.OutputSize[1];
     const size_t n = (size_t)W * H, no = (size_t)Ow * Oh;
-    const struct { const char* name; const void* p; uint32_t texel; } bound[8] = {
+    const BoundTexture bound[8] = {
         { "Radiance", t->Radiance, 8 }, { "DiffuseAlbedo", t->DiffuseAlbedo, 8 }, { "SpecularAlbedo", t->SpecularAlbedo, 8 },
         { "NormalRoughness", t->NormalRoughness, 8 }, { "Position", t->Position, 16 }, { "LinearDepth", t->LinearDepth, 4 },
         { "MotionVector", t->MotionVector, 8 }, { "Color", t->Color, 8 } };
-    for (const auto& b : bound) if (!b.p) return fail(&c, PT_ERROR_INVALID_ARGUMENT, std::string(b.name) + " is NULL");
-    for (const auto& b : bound) if ((uintptr_t)b.p & (b.texel - 1u))
-        return fail(&c, PT_ERROR_INVALID_ARGUMENT, std::string(b.name) + " is not aligned to its texel (" + std::to_string(b.texel) + " bytes)");
+    if (int refusal = fl_check_bound(c, bound)) return refusal;
     for (int k = 0; k < 7; ++k) {                              // Color is written while the inputs are still read
         const uintptr_t in0 = (uintptr_t)bound[k].p, in1 = in0 + n * bound[k].texel, out0 = (uintptr_t)t->Color, out1 = out0 + no * 8u;
         if (in0 < out1 && out0 < in1) return fail(&c, PT_ERROR_INVALID_ARGUMENT, std::string("Color overlaps ") + bound[k].name);
     }
-    for (int k = 0; k < 2; ++k) if (!(std::isfinite(jitter[k]) && jitter[k] >= -0.5f && jitter[k] <= 0.5f))
-        return fail(&c, PT_ERROR_INVALID_ARGUMENT, "jitter must be finite and in [-0.5, 0.5] on both axes");
-    const size_t slots = n * RR_SLOTS;
-    const size_t outSlots = 2 * no + (2 * no + 3) / 4;          // float4 units: two parities of (colour, n), then two of z
+    if (int refusal = fl_check_jitter(c, jitter)) return refusal;
     API_HIP(&c, hipSetDevice(c.device));
-    if (c.rrHistory.capacity() < slots || c.rrOutput.capacity() < outSlots) {      // transactional: the old history stays until the new one exists
-        DeviceBuffer<float4> fresh, freshOut;
-        const bool growRender = c.rrHistory.capacity() < slots, growOutput = c.rrOutput.capacity() < outSlots;
-        if (growRender) API_HIP(&c, fresh.reserve(slots));
-        if (growOutput) API_HIP(&c, freshOut.reserve(outSlots));
-        API_HIP(&c, hipStreamSynchronize(c.stream));           // an earlier call may still use the old ones
-        if (growRender) c.rrHistory = std::move(fresh);
-        if (growOutput) c.rrOutput = std::move(freshOut);
-        c.rrFrames = 0;
-    }
+    if (int e = fl_grow_history(c, c.rrState, { { c.rrHistory, n * RR_SLOTS }, { c.rrOutput, fl_output_slots(no) } })) return e;
     float4* base = c.rrHistory.data();
     float2* halves = (float2*)(base + n * RR_SLOTS4);
-    const uint32_t cur = c.rrParity ^ 1u, prev = c.rrParity;
+    const uint32_t cur = c.rrState.parity ^ 1u, prev = c.rrState.parity;
     auto slot = [&](int first, uint32_t parity) { return base + n * (first + parity); };
-    const uint32_t reset = c.rrFrames == 0 ? 1u : 0u;
     float4* filtered = slot(RR_WORK, rr_final_work(s.AtrousIterations));
 
     const RrSettings rs{ (float)s.MaxAccumulatedFrames, s.DepthThreshold, s.NormalCosine, s.LuminanceSigma, s.RoughnessFraction };
@@ -507,7 +356,7 @@ int pt_reconstruction_process(PtContext* ctx, const struct PtReconstructionTextu
     ta.hist = slot(RR_HIST, cur); ta.g0 = slot(RR_G0, cur); ta.g1 = slot(RR_G1, cur); ta.albedo = slot(RR_ALBEDO, 0); ta.out = filtered;
     ta.moments = halves + n * cur;
     ta.prevHist = slot(RR_HIST, prev); ta.prevG0 = slot(RR_G0, prev); ta.prevG1 = slot(RR_G1, prev); ta.prevMoments = halves + n * prev;
-    ta.W = W; ta.H = H; ta.reset = reset; ta.s = rs;
+    ta.W = W; ta.H = H; ta.reset = c.rrState.frames == 0 ? 1u : 0u; ta.s = rs;
     k_rr_temporal<<<grid, block, 0, c.stream>>>(ta);
     const RrVarianceArgs va{ ta.hist, ta.g0, ta.g1, ta.albedo, ta.moments, slot(RR_WORK, 1), W, H, rs };
     k_rr_variance<<<grid, block, 0, c.stream>>>(va);
@@ -521,20 +370,14 @@ int pt_reconstruction_process(PtContext* ctx, const struct PtReconstructionTextu
         } else k_rr_atrous<false><<<grid, block, 0, c.stream>>>(aa);
         aa.in = aa.out;
     }
-    float4* obase = c.rrOutput.data();
-    float* zBase = (float*)(obase + 2 * no);
     RrResolveArgs ra{};
-    ra.filtered = filtered; ra.albedo = ta.albedo; ra.depth = ta.depth; ra.motion = t->MotionVector; ra.color = t->Color;
-    ra.hist = obase + no * cur; ra.histZ = zBase + no * cur; ra.prevHist = obase + no * prev; ra.prevZ = zBase + no * prev;
-    ra.Rw = W; ra.Rh = H; ra.Ow = Ow; ra.Oh = Oh; ra.reset = reset;
-    ra.sx = (float)W / (float)Ow; ra.sy = (float)H / (float)Oh; ra.jx = jitter[0]; ra.jy = jitter[1];
-    ra.maxFrames = (float)s.MaxOutputFrames; ra.r2 = s.KernelRadius * s.KernelRadius; ra.tau = s.DepthThreshold;
+    ra.filtered = filtered; ra.albedo = ta.albedo; ra.depth = ta.depth; ra.motion = t->MotionVector;
+    ra.r = fl_resolve_args(c.rrState, c.rrOutput.data(), t->Color, s.RenderSize, s.OutputSize, jitter, s.MaxOutputFrames, s.KernelRadius, s.DepthThreshold);
     const dim3 ogrid((Ow + kRrTile - 1) / kRrTile, (Oh + kRrTile - 1) / kRrTile);
     k_rr_resolve<<<ogrid, block, 0, c.stream>>>(ra);
     API_HIP(&c, hipGetLastError());
-    c.rrParity = cur;
-    c.rrFrames += 1;
-    c.rrSize[0] = W; c.rrSize[1] = H; c.rrSize[2] = Ow; c.rrSize[3] = Oh; c.rrFinal = rr_final_work(s.AtrousIterations);
+    c.rrState.advance(W, H, Ow, Oh);
+    c.rrFinal = rr_final_work(s.AtrousIterations);
     return PT_OK;
 }
 
@@ -546,22 +389,15 @@ int pt_reconstruction_download_history(PtContext* ctx, float* host_length, float
     API_ARG(&c, render_out && output_out, "render_out / output_out is NULL");
     API_HIP(&c, hipSetDevice(c.device));
     API_HIP(&c, hipStreamSynchronize(c.stream));
-    const bool have = c.rrFrames != 0;                         // after a reset there is no history to show: 0 x 0
-    for (int k = 0; k < 2; ++k) { render_out[k] = have ? c.rrSize[k] : 0u; output_out[k] = have ? c.rrSize[2 + k] : 0u; }
+    for (int k = 0; k < 2; ++k) { render_out[k] = c.rrState.shown(k); output_out[k] = c.rrState.shown(2 + k); }
     const size_t n = (size_t)render_out[0] * render_out[1], no = (size_t)output_out[0] * output_out[1];
     const size_t count = (size_t)std::min<uint64_t>(capacity_render_pixels, n), countOut = (size_t)std::min<uint64_t>(capacity_output_pixels, no);
-    if (count && host_length) {
-        std::vector<float4> texels(count);
-        API_HIP(&c, hipMemcpy(texels.data(), c.rrHistory.data() + n * (RR_HIST + c.rrParity), count * sizeof(float4), hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < count; ++k) host_length[k] = texels[k].w;
-    }
+    if (count && host_length)
+        if (int e = fl_download_w(c, c.rrHistory.data() + n * (RR_HIST + c.rrState.parity), count, host_length)) return e;
     if (count && host_filtered)
         API_HIP(&c, hipMemcpy(host_filtered, c.rrHistory.data() + n * (RR_WORK + c.rrFinal), count * sizeof(float4), hipMemcpyDeviceToHost));
-    if (countOut && host_n) {
-        std::vector<float4> texels(countOut);
-        API_HIP(&c, hipMemcpy(texels.data(), c.rrOutput.data() + no * c.rrParity, countOut * sizeof(float4), hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < countOut; ++k) host_n[k] = texels[k].w;
-    }
+    if (countOut && host_n)
+        if (int e = fl_download_w(c, c.rrOutput.data() + no * c.rrState.parity, countOut, host_n)) return e;
     return PT_OK;
 }
 

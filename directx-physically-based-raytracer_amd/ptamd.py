@@ -1113,7 +1113,29 @@ def nrd_composition_pixels_per_lane(pointers, constants):
     return load_library().pt_nrd_composition_pixels_per_lane(C.c_void_p(k.ctypes.data), C.addressof(t))
 
 
-class Denoiser:
+class _Filter:
+    """What Denoiser, Upscaler and Reconstruction have in common: the textures by name, the settings record last accepted, the history.
+    A subclass names its record (_DTYPE, _RECORD, _LAYOUT for the message) and its two library functions (_SET, _RESET)."""
+    _DTYPE = _RECORD = _LAYOUT = _SET = _RESET = None
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.Textures = {}
+        self._settings = None
+
+    def _set_constants(self, settings):
+        k = np.array(settings)
+        if k.dtype != self._DTYPE or k.size != 1:
+            raise PtInvalidArgument(f"settings must be one {self._RECORD} record (layouts.{self._LAYOUT})")
+        k = np.ascontiguousarray(k).reshape(())
+        self.ctx.check(getattr(self.ctx.lib, self._SET)(self.ctx.handle, C.c_void_p(k.ctypes.data)))
+        self._settings = k
+
+    def ResetHistory(self):
+        self.ctx.check(getattr(self.ctx.lib, self._RESET)(self.ctx.handle))
+
+
+class Denoiser(_Filter):
     """The library's own denoiser for the ReLAX slot between the two calls of the NRD composition pass (pt_denoiser_*; DESIGN.md section
     1, "Denoiser"): temporal accumulation with reprojection, a variance estimate, an edge-stopping a-trous wavelet. Not NRD's ReLAX, and
     ReLAX's packing only: SetConstants refuses denoiser=DENOISER_NRD_REBLUR. Process takes the textures by the names of
@@ -1122,31 +1144,20 @@ class Denoiser:
 
     An instance is callable as denoise(noisy_diffuse, noisy_specular) -> (denoised_diffuse, denoised_specular), in place, on the guide
     textures of self.Textures: what Renderer.render(..., nrd=DENOISER_NRD_RELAX, denoise=...) asks for."""
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self.Textures = {}
-        self._settings = None
+    _DTYPE, _RECORD, _LAYOUT = L.DENOISER_SETTINGS, "PtDenoiserSettings", "denoiser_settings"
+    _SET, _RESET = "pt_denoiser_set_constants", "pt_denoiser_reset_history"
 
     def SetConstants(self, settings, denoiser=L.DENOISER_NRD_RELAX):
         """settings: PtDenoiserSettings (layouts.denoiser_settings). denoiser: the packing of the pair it will be handed."""
         if int(denoiser) != L.DENOISER_NRD_RELAX:
             raise PtInvalidArgument("the denoiser reads ReLAX's packing (radiance, hit distance) only: ReBLUR's (YCoCg, normalised hit "
                                     "distance) and the other Denoiser values are not served")
-        k = np.array(settings)
-        if k.dtype != L.DENOISER_SETTINGS or k.size != 1:
-            raise PtInvalidArgument("settings must be one PtDenoiserSettings record (layouts.denoiser_settings)")
-        k = np.ascontiguousarray(k).reshape(())
-        self.ctx.check(self.ctx.lib.pt_denoiser_set_constants(self.ctx.handle, C.c_void_p(k.ctypes.data)))
-        self._settings = k
+        self._set_constants(settings)
 
     def Process(self, textures=None):
         tex = self.Textures if textures is None else textures
         t = DenoiserTextures(*[_ptr(tex.get(n)) for n in L.DENOISER_TEXTURES])
         self.ctx.check(self.ctx.lib.pt_denoiser_process(self.ctx.handle, C.addressof(t)))
-
-    def ResetHistory(self):
-        self.ctx.check(self.ctx.lib.pt_denoiser_reset_history(self.ctx.handle))
 
     def DownloadHistory(self):
         """The accumulated length of the diffuse channel per pixel after the last Process: float32 (h, w), 0 where the G-buffer missed;
@@ -1183,16 +1194,13 @@ def upscaler_jitter(frame_index, render_size, output_size):
     return np.float32(out[0]), np.float32(out[1])
 
 
-class Upscaler:
+class Upscaler(_Filter):
     """The library's own temporal upscaler for the super-resolution slot between the denoiser and the post chain (pt_upscaler_*;
     DESIGN.md section 1, "Upscaler"): a temporal accumulating upscaler from RenderSize to OutputSize, where the reference loads DLSS or
     XeSS. Not a port of either. Process takes the textures by the names of layouts.UPSCALER_TEXTURES (a missing name is an unbound
     texture) and the Camera.Jitter the frame was rendered with. Runs on the full frame of an unsharded context. No scene is needed."""
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self.Textures = {}
-        self._settings = None
+    _DTYPE, _RECORD, _LAYOUT = L.UPSCALER_SETTINGS, "PtUpscalerSettings", "upscaler_settings"
+    _SET, _RESET = "pt_upscaler_set_constants", "pt_upscaler_reset_history"
 
     @property
     def settings(self):
@@ -1201,21 +1209,13 @@ class Upscaler:
 
     def SetConstants(self, settings):
         """settings: PtUpscalerSettings (layouts.upscaler_settings)."""
-        k = np.array(settings)
-        if k.dtype != L.UPSCALER_SETTINGS or k.size != 1:
-            raise PtInvalidArgument("settings must be one PtUpscalerSettings record (layouts.upscaler_settings)")
-        k = np.ascontiguousarray(k).reshape(())
-        self.ctx.check(self.ctx.lib.pt_upscaler_set_constants(self.ctx.handle, C.c_void_p(k.ctypes.data)))
-        self._settings = k
+        self._set_constants(settings)
 
     def Process(self, jitter, textures=None):
         tex = self.Textures if textures is None else textures
         t = UpscalerTextures(*[_ptr(tex.get(n)) for n in L.UPSCALER_TEXTURES])
         j = (C.c_float * 2)(float(jitter[0]), float(jitter[1]))
         self.ctx.check(self.ctx.lib.pt_upscaler_process(self.ctx.handle, C.addressof(t), j))
-
-    def ResetHistory(self):
-        self.ctx.check(self.ctx.lib.pt_upscaler_reset_history(self.ctx.handle))
 
     def DownloadHistory(self):
         """The accumulated weight n per output pixel after the last Process: float32 (h, w); empty (0, 0) when there is no history.
@@ -1228,17 +1228,14 @@ class Upscaler:
         return out
 
 
-class Reconstruction:
+class Reconstruction(_Filter):
     """The library's own denoising upscaler for the ray-reconstruction slot of App::PostProcessGraphics (pt_reconstruction_*; DESIGN.md
     section 1, "Ray reconstruction"), where the reference's default settings call DLSS Ray Reconstruction. Not a port of it. From the noisy
     Radiance of a Denoiser = DLSS-RR frame, the two albedos and the G-buffer guides at RenderSize to the denoised Color at OutputSize.
     Process takes the textures by the names of layouts.RECONSTRUCTION_TEXTURES (a missing name is an unbound texture) and the
     Camera.Jitter the frame was rendered with. Runs on the full frame of an unsharded context. No scene is needed."""
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self.Textures = {}
-        self._settings = None
+    _DTYPE, _RECORD, _LAYOUT = L.RECONSTRUCTION_SETTINGS, "PtReconstructionSettings", "reconstruction_settings"
+    _SET, _RESET = "pt_reconstruction_set_constants", "pt_reconstruction_reset_history"
 
     @property
     def settings(self):
@@ -1247,21 +1244,13 @@ class Reconstruction:
 
     def SetConstants(self, settings):
         """settings: PtReconstructionSettings (layouts.reconstruction_settings)."""
-        k = np.array(settings)
-        if k.dtype != L.RECONSTRUCTION_SETTINGS or k.size != 1:
-            raise PtInvalidArgument("settings must be one PtReconstructionSettings record (layouts.reconstruction_settings)")
-        k = np.ascontiguousarray(k).reshape(())
-        self.ctx.check(self.ctx.lib.pt_reconstruction_set_constants(self.ctx.handle, C.c_void_p(k.ctypes.data)))
-        self._settings = k
+        self._set_constants(settings)
 
     def Process(self, jitter, textures=None):
         tex = self.Textures if textures is None else textures
         t = ReconstructionTextures(*[_ptr(tex.get(n)) for n in L.RECONSTRUCTION_TEXTURES])
         j = (C.c_float * 2)(float(jitter[0]), float(jitter[1]))
         self.ctx.check(self.ctx.lib.pt_reconstruction_process(self.ctx.handle, C.addressof(t), j))
-
-    def ResetHistory(self):
-        self.ctx.check(self.ctx.lib.pt_reconstruction_reset_history(self.ctx.handle))
 
     def DownloadHistory(self):
         """After the last Process: (length, filtered, n). length: the history length of the signal per render pixel, float32 (h, w);

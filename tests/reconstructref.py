@@ -16,8 +16,8 @@ DEFAULTS = {"MaxAccumulatedFrames": 30, "MaxOutputFrames": 16, "AtrousIterations
 INTEGERS = ("MaxAccumulatedFrames", "MaxOutputFrames", "AtrousIterations")
 ALBEDO_FLOOR, ALBEDO_CEILING = 0.015625, 131008.0
 RESET_RATIO = 16.0
-TAPS, NEIGHBOURS, ONE16 = U.TAPS, U.NEIGHBOURS, U.ONE16
-f16_to_f32, f_to_f16, f16, jitter, ulp16 = U.f16_to_f32, U.f_to_f16, U.f16, U.jitter, U.ulp16
+TAPS, ONE16 = U.TAPS, U.ONE16
+f16_to_f32, f16, jitter, ulp16 = U.f16_to_f32, U.f16, U.jitter, U.ulp16
 _shift = D._shift
 
 
@@ -41,11 +41,20 @@ class Reconstruction:
         self.render, self.output = (int(render[0]), int(render[1])), (int(output[0]), int(output[1]))
         self.A = D.Arith(dtype)
         self.s = settings(**overrides)
+        # stage 4 is the upscaler's resolve with this pass's own output history
+        self.up = U.Upscaler(render, output, dtype, MaxAccumulatedFrames=self.s["MaxOutputFrames"], KernelRadius=self.s["KernelRadius"],
+                             DepthThreshold=self.s["DepthThreshold"])
         self.reset()
 
     def reset(self):
-        self.hist = self.out_hist = None
+        self.hist = None
+        self.up.reset()
         self.length = self.filtered = self.albedo = self.n = self.reused = self.reused_out = self.feature = None
+
+    @property
+    def out_hist(self):
+        """the output history: stage 4's (tone-mapped colour, n, z), None when there is none"""
+        return self.up.hist
 
     def process(self, tex, jitter):
         with np.errstate(all="ignore"):
@@ -150,7 +159,9 @@ class Reconstruction:
         self.filtered, self.albedo = filtered, albedo
 
         # ---- stage 4: resolve
-        return self._resolve((filtered[..., :3] * albedo).astype(T), z, mv[..., :3], jitter)
+        color = self.up.resolve((filtered[..., :3] * albedo).astype(T), z, mv[..., :3], jitter)
+        self.n, self.reused_out = self.up.length, self.up.reused
+        return color
 
     def _spatial_variance(self, signal, P, N, hit, plane):
         A, T = self.A, self.A.T
@@ -209,106 +220,6 @@ class Reconstruction:
                 va = va + np.where(use, (wq * wq) * vq, T(0))
                 acc = acc + np.where(use[..., None], wq[..., None] * cq, T(0))
         return (acc / ws[..., None]).astype(T), (va / (ws * ws)).astype(T)
-
-    def _resolve(self, rgb, depth, motion, jitter):
-        """DESIGN.md section 1, "Upscaler", steps 1-6 on the remodulated taps, with this pass's own output history"""
-        T = self.A.T
-        (Rw, Rh), (Ow, Oh) = self.render, self.output
-        one, zero, half = T(1), T(0), T(0.5)
-        jx, jy = T(np.float32(jitter[0])), T(np.float32(jitter[1]))
-        M, R, tau = T(self.s["MaxOutputFrames"]), T(self.s["KernelRadius"]), T(self.s["DepthThreshold"])
-        R2 = R * R
-        floor_w = T(0.015625)
-        m = np.maximum(np.maximum(rgb[..., 0], rgb[..., 1]), rgb[..., 2])
-        toned = (rgb / (one + np.where(m > 0, m, zero))[..., None]).astype(T)
-
-        sx, sy = T(Rw) / T(Ow), T(Rh) / T(Oh)
-        oy, ox = np.mgrid[0:Oh, 0:Ow]
-        oxc, oyc = ox.astype(T) + half, oy.astype(T) + half
-        ux, uy = oxc * sx, oyc * sy
-        cxf, cyf = np.floor(ux - jx), np.floor(uy - jy)
-        cxf = np.where(cxf < 0, zero, np.where(cxf > T(Rw - 1), T(Rw - 1), cxf))
-        cyf = np.where(cyf < 0, zero, np.where(cyf > T(Rh - 1), T(Rh - 1), cyf))
-        cx, cy = cxf.astype(np.int64), cyf.astype(np.int64)
-
-        best = np.full((Oh, Ow), np.inf, T)
-        bx, by = np.zeros((Oh, Ow), np.int64), np.zeros((Oh, Ow), np.int64)
-        found = np.zeros((Oh, Ow), bool)
-        wsum = np.zeros((Oh, Ow), T)
-        acc = np.zeros((Oh, Ow, 3), T)
-        lo, hi = np.full((Oh, Ow, 3), np.inf, T), np.full((Oh, Ow, 3), -np.inf, T)
-        k = None
-        for dx, dy in NEIGHBOURS:
-            qx, qy = cx + dx, cy + dy
-            inside = (qx >= 0) & (qx < Rw) & (qy >= 0) & (qy < Rh)
-            qxc, qyc = np.clip(qx, 0, Rw - 1), np.clip(qy, 0, Rh - 1)
-            zq = depth[qyc, qxc]
-            better = inside & np.isfinite(zq) & (zq < best)
-            best = np.where(better, zq, best)
-            bx, by = np.where(better, qxc, bx), np.where(better, qyc, by)
-            found |= better
-            ddx = ((qx.astype(T) + half) + jx) - ux
-            ddy = ((qy.astype(T) + half) + jy) - uy
-            d2 = ddx * ddx + ddy * ddy
-            w = one - d2 / R2
-            w = np.where(w > 0, w, zero)
-            w = w * w
-            if dx == 0 and dy == 0:
-                w = np.where(w < floor_w, floor_w, w)
-                k = w
-            use = inside & (w > 0)
-            tq = toned[qyc, qxc]
-            wsum = wsum + np.where(use, w, zero)
-            acc = acc + np.where(use[..., None], w[..., None] * tq, zero)
-            lo = np.where(inside[..., None] & (tq < lo), tq, lo)
-            hi = np.where(inside[..., None] & (tq > hi), tq, hi)
-        cur = (acc / wsum[..., None]).astype(T)
-        z = best
-        mv = np.where(found[..., None], motion[by, bx], zero)
-        background = ~found
-
-        px, py = oxc + mv[..., 0] / sx, oyc + mv[..., 1] / sy
-        fx, fy = px - half, py - half
-        x0, y0 = np.floor(fx), np.floor(fy)
-        tx, ty = fx - x0, fy - y0
-        wx, wy = (one - tx, tx), (one - ty, ty)
-        zp = z + mv[..., 2]
-        tol = tau * np.abs(zp)
-        hsum = np.zeros((Oh, Ow), T)
-        hacc = np.zeros((Oh, Ow, 4), T)
-        if self.out_hist is not None:
-            for dx, dy in TAPS:
-                xf, yf = x0 + T(dx), y0 + T(dy)
-                inside = (xf >= 0) & (xf <= T(Ow - 1)) & (yf >= 0) & (yf <= T(Oh - 1))
-                xi, yi = np.where(inside, xf, 0).astype(np.int64), np.where(inside, yf, 0).astype(np.int64)
-                zh = self.out_hist["z"][yi, xi]
-                ok = inside & np.where(background, ~np.isfinite(zh), np.abs(zh - zp) <= tol)
-                w = wx[dx] * wy[dy]
-                hsum = hsum + np.where(ok, w, zero)
-                hacc = hacc + np.where(ok[..., None], w[..., None] * self.out_hist["colour_n"][yi, xi], zero)
-        have = hsum > 0
-        h = hacc / hsum[..., None]
-
-        hc = h[..., :3]
-        hc = np.where(hc < lo, lo, np.where(hc > hi, hi, hc))
-        n1 = h[..., 3] + k
-        n = np.where(n1 < M, n1, M)
-        a = k / n
-        blend = np.where((a >= one)[..., None], cur, hc + (cur - hc) * a[..., None])
-        out = np.where(have[..., None], blend, cur).astype(T)
-        n = np.where(have, n, k).astype(T)
-
-        self.out_hist = {"colour_n": np.concatenate([out, n[..., None]], -1).astype(T), "z": z.astype(T)}
-        self.n, self.reused_out = n, have
-        mo = np.maximum(np.maximum(out[..., 0], out[..., 1]), out[..., 2])
-        den = one - np.where(mo > 0, mo, zero)
-        den = np.where(den < T(2.0 ** -17), T(2.0 ** -17), den)
-        c = out / den[..., None]
-        c = np.where(c > T(65504), T(65504), np.where(c < T(-65504), T(-65504), c))
-        color = np.empty((Oh, Ow, 4), np.uint16)
-        color[..., :3] = f_to_f16(c)
-        color[..., 3] = ONE16
-        return color
 
 
 # ---------------------------------------------------------------------------------------------- frames

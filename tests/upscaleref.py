@@ -100,6 +100,22 @@ class Upscaler:
             return self._process(tex, jitter)
 
     def _process(self, tex, jitter):
+        """the texture decode: the taps' guarded colour, depth and motion, as `dtype`"""
+        T = self.T
+        Rw, Rh = self.render
+        depth = np.asarray(tex["LinearDepth"], np.float32).reshape(Rh, Rw).astype(T)
+        motion = f16_to_f32(np.asarray(tex["MotionVector"]).reshape(Rh, Rw, 4))[..., :3].astype(T)
+        rgb = f16_to_f32(np.asarray(tex["Radiance"]).reshape(Rh, Rw, 4))[..., :3].astype(T)
+        rgb = np.where(np.isfinite(rgb).all(-1, keepdims=True), rgb, T(0))
+        return self._resolve(rgb, depth, motion, jitter)
+
+    def resolve(self, rgb, depth, motion, jitter):
+        """Steps 1-6 on taps given as arrays of `dtype`: rgb (Rh, Rw, 3) guarded colour, depth (Rh, Rw), motion (Rh, Rw, 3). Owns the
+        output history: process() is the texture decode and this; the reconstruction's stage 4 is this on its remodulated taps."""
+        with np.errstate(all="ignore"):
+            return self._resolve(rgb, depth, motion, jitter)
+
+    def _resolve(self, rgb, depth, motion, jitter):
         T = self.T
         (Rw, Rh), (Ow, Oh) = self.render, self.output
         one, zero, half = T(1), T(0), T(0.5)
@@ -107,11 +123,6 @@ class Upscaler:
         M, R, tau = T(self.s["MaxAccumulatedFrames"]), T(self.s["KernelRadius"]), T(self.s["DepthThreshold"])
         R2 = R * R
         floor_w = T(0.015625)
-
-        depth = np.asarray(tex["LinearDepth"], np.float32).reshape(Rh, Rw).astype(T)
-        motion = f16_to_f32(np.asarray(tex["MotionVector"]).reshape(Rh, Rw, 4))[..., :3].astype(T)
-        rgb = f16_to_f32(np.asarray(tex["Radiance"]).reshape(Rh, Rw, 4))[..., :3].astype(T)
-        rgb = np.where(np.isfinite(rgb).all(-1, keepdims=True), rgb, zero)
         m = np.maximum(np.maximum(rgb[..., 0], rgb[..., 1]), rgb[..., 2])
         toned = (rgb / (one + np.where(m > 0, m, zero))[..., None]).astype(T)        # t(c), the same value at every tap that reads the texel
 
