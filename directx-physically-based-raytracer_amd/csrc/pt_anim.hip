@@ -405,15 +405,16 @@ int pt_anim_evaluate(PtContext* ctx, const struct PtAnimState* states, uint32_t 
         API_ARG(&c, !device_instances || !o.hasBindings || o.maxInstance < c.instanceDataCount, "a binding's instance index is beyond the bound instance data");
     }
     API_HIP(&c, hipSetDevice(c.device));
-    if (count > c.animStatesDev.capacity()) {                      // growth waits for the stream: a kernel in flight may still read the old array
-        API_HIP(&c, hipStreamSynchronize(c.stream));
-        API_HIP(&c, c.animStatesDev.reserve((size_t)count * 2));
-    }
+    API_HIP(&c, grow(c.stream, nullptr, want(c.animStatesDev, count > c.animStatesDev.capacity() ? (size_t)count * 2 : 0)));   // head room
     Context::UploadStage& sg = c.animStage[c.animStageNext];
     if (sg.event) API_HIP(&c, hipEventSynchronize(sg.event.get()));    // the copy that last read this buffer has run
     else API_HIP(&c, create_event(sg.event, hipEventDisableTiming));
     const size_t bytes = sizeof(AnimStateDev) * (size_t)count;
-    if (bytes > sg.host.capacity()) API_HIP(&c, sg.host.reserve(bytes * 2));
+    if (bytes > sg.host.capacity()) {                                  // (the event, not the stream, guards it: a fresh one, moved in)
+        PinnedBuffer<uint8_t> fresh;
+        API_HIP(&c, fresh.reserve(bytes * 2));
+        sg.host = std::move(fresh);
+    }
     AnimStateDev* h = (AnimStateDev*)sg.host.data();
     for (uint32_t i = 0; i < count; i++) {
         const AnimObject& o = c.animObjects.at(states[i].Object);

@@ -179,16 +179,13 @@ static int upload_heap(Context& c)
     if (!c.srgbLutDev) {                                  // sRGB -> linear table, evaluated in double (arithmetic spec)
         float lut[256];
         for (int i = 0; i < 256; i++) { double v = i / 255.0; lut[i] = (float)(v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4)); }
-        DeviceBuffer<float> dev;
-        API_HIP(&c, dev.reserve(256));
-        API_HIP(&c, hipMemcpy(dev.data(), lut, sizeof lut, hipMemcpyHostToDevice));
-        c.srgbLutDev = std::move(dev);
+        API_HIP(&c, upload_once(c.srgbLutDev, lut, sizeof lut));
     }
     if (!c.heapDirty) return PT_OK;
     uint32_t n = (uint32_t)c.heapHost.size();
     c.heapHasTextures = false;
     for (const HeapEntry& e : c.heapHost) if (e.kind != kKindBuffer) c.heapHasTextures = true;
-    API_HIP(&c, c.heapDev.reserve(n));
+    API_HIP(&c, grow(c.stream, nullptr, want(c.heapDev, n)));
     if (n) API_HIP(&c, hipMemcpyAsync(c.heapDev.data(), c.heapHost.data(), sizeof(HeapEntry) * n, hipMemcpyHostToDevice, c.stream));
     API_HIP(&c, hipStreamSynchronize(c.stream));     // heapHost may change right after
     c.heapDirty = false; c.validated = false;
@@ -451,26 +448,18 @@ static int build_top_level(PtContext* ctx, const PtInstanceDesc* descs, uint32_t
     if (st != PT_OK) return st;
 
     // ---- allocate: everything is grow-only, so the rebuild of an unchanged scene layout (a dynamic frame) allocates nothing and waits for
-    // nothing; growth waits for the stream first (kernels in flight may still read the old buffers). A new traversal copy stays local.
+    // nothing. A new traversal copy stays local until the commit: its pieces are copied out of the old one first.
     bool moved = false;                                            // an adopted piece is not where the new layout wants it
     for (const auto& p : P.pieces) if (p.b->inBlob && !P.in_place(p)) moved = true;
     const bool newBlob = P.total > c.blobDev.capacity() || moved;
-    const uint32_t instCap = count ? count : 1;
-    const bool growth = instCap > c.tlas.instances.capacity() || wide_node_capacity(instCap) > c.tlas.nodes.capacity() || newBlob;
-    if (growth) API_HIP(&c, hipStreamSynchronize(c.stream));
     drop_tlas(c);
-    if (instCap > c.tlas.instances.capacity()) {
-        c.tlas.instances.reset(); c.tlas.blasBounds.reset();
-        API_HIP(&c, c.tlas.blasBounds.reserve(instCap));
-        API_HIP(&c, c.tlas.instances.reserve(instCap));            // last: the grow decision reads its capacity
-    }
     DeviceBuffer<uint8_t> newCopy;                                 // pieces move over from the context's copy into it
     if (newBlob) {
         const hipError_t ea = newCopy.reserve(std::max<size_t>(P.total ? P.total : 16, moved ? c.blobDev.capacity() : 0));
         if (ea != hipSuccess) return fail_hip(&c, ea, "hipMalloc(traversal copy)");
     }
     if (!c.tlasHeaderEvent) API_HIP(&c, create_event(c.tlasHeaderEvent, hipEventDisableTiming));
-    API_HIP(&c, c.tlasHeaderHost.reserve(1));
+    if (!c.tlasHeaderHost) API_HIP(&c, c.tlasHeaderHost.reserve(1));
     const uint8_t* oldBlob = c.blobDev.data();
     uint8_t* blob = newBlob ? newCopy.data() : c.blobDev.data();
 
@@ -503,20 +492,22 @@ static int build_top_level(PtContext* ctx, const PtInstanceDesc* descs, uint32_t
         if (p.referenced) { BlasEntry& row = P.table[P.pieceOf[p.id]]; row.nodes = (const WideNode*)sn; row.tris = (const TriPacket*)st_; row.idx = (const uint4*)si; }
     }
     const size_t tableOff = (P.srcBytes + 15) / 16 * 16, tableBytes = sizeof(BlasEntry) * P.table.size();
-    hipError_t e = build_tlas_prepare(c.tlas, count);          // node / order arrays of the TLAS (grow-only), known before the jobs that copy them
-    if (e != hipSuccess) return fail_hip(&c, e, "top-level build");
-    jobs.push_back(BlobCopy{ c.tlas.nodes.data(), blob + P.nodeAt, sizeof(WideNode) * (size_t)P.tlasNodeExact / 16 });
     const size_t preOff = (tableOff + tableBytes + 15) / 16 * 16, preBytes = sizeof(BlobCopy) * preJobs.size();
-    const size_t jobsOff = (preOff + preBytes + 15) / 16 * 16, jobsBytes = sizeof(BlobCopy) * jobs.size();
+    const size_t jobsOff = (preOff + preBytes + 15) / 16 * 16, jobsBytes = sizeof(BlobCopy) * (jobs.size() + 1);   // + the top level's own nodes, below
     std::vector<uint8_t>& up = c.tlasUploadHost;
     up.resize(jobsOff + jobsBytes);
+    // everything of the context that this build writes and a frame in flight may read, as one growth with one wait. The upload gets head room:
+    // a few more instances next frame do not reallocate. (The build buffers of the top level hold as many items as `instances`: they grow,
+    // in build_tlas_prepare, only behind the wait of this growth.)
+    const uint32_t instCap = count ? count : 1;
+    API_HIP(&c, grow(c.stream, nullptr, want(c.tlas.instances, instCap), want(c.tlas.blasBounds, instCap), want(c.tlas.nodes, wide_node_capacity(instCap)),
+                     want(c.tlas.rootBounds, 8), want(c.tlasUploadDev, up.size() > c.tlasUploadDev.capacity() ? up.size() * 2 : 0)));
+    hipError_t e = build_tlas_prepare(c.tlas, count);          // the build buffers of the top level (grow-only)
+    if (e != hipSuccess) return fail_hip(&c, e, "top-level build");
+    jobs.push_back(BlobCopy{ c.tlas.nodes.data(), blob + P.nodeAt, sizeof(WideNode) * (size_t)P.tlasNodeExact / 16 });
     if (tableBytes) memcpy(up.data() + tableOff, P.table.data(), tableBytes);
     if (preBytes) memcpy(up.data() + preOff, preJobs.data(), preBytes);
     memcpy(up.data() + jobsOff, jobs.data(), jobsBytes);
-    if (up.size() > c.tlasUploadDev.capacity()) {
-        if (!growth) API_HIP(&c, hipStreamSynchronize(c.stream));
-        API_HIP(&c, c.tlasUploadDev.reserve(up.size() * 2));          // head room: a few more instances next frame do not reallocate
-    }
     {
         // staged in pinned host memory, two buffers taken in turn, each guarded by an event recorded behind the copy that read it: the host
         // may be a build ahead of the stream (a dynamic frame never synchronises) without rewriting bytes a copy has yet to read
@@ -524,7 +515,11 @@ static int build_top_level(PtContext* ctx, const PtInstanceDesc* descs, uint32_t
         c.tlasStageNext ^= 1u;
         if (sg.event) API_HIP(&c, hipEventSynchronize(sg.event.get()));   // the copy that last read this buffer has run
         else API_HIP(&c, create_event(sg.event, hipEventDisableTiming));
-        if (up.size() > sg.host.capacity()) API_HIP(&c, sg.host.reserve(up.size() * 2));
+        if (up.size() > sg.host.capacity()) {                              // (the event, not the stream, guards it: a fresh one, moved in)
+            PinnedBuffer<uint8_t> fresh;
+            API_HIP(&c, fresh.reserve(up.size() * 2));
+            sg.host = std::move(fresh);
+        }
         memcpy(sg.host.data(), up.data(), up.size());
         API_HIP(&c, hipMemcpyAsync(c.tlasUploadDev.data(), sg.host.data(), up.size(), hipMemcpyHostToDevice, c.stream));
         API_HIP(&c, hipEventRecord(sg.event.get(), c.stream));
@@ -739,13 +734,8 @@ static int validate_scene(Context& c)
     uint32_t sharedMismatch = 0;
     bool transmission = false;                              // no objects: nothing to hit
     if (c.objectCount) {
-        API_HIP(&c, c.validateDev.reserve(8));
-        if (c.objectCount > c.shadeGeomDev.capacity()) {    // the resolved-geometry table the same kernel fills (grow-only; kernels in flight may read the old one)
-            API_HIP(&c, hipStreamSynchronize(c.stream));
-            c.shadeGeomDev.reset(); c.shadeTexDev.reset();
-            API_HIP(&c, c.shadeTexDev.reserve(kTextureSlots * (size_t)c.objectCount));
-            API_HIP(&c, c.shadeGeomDev.reserve(c.objectCount));     // last: the grow decision reads its capacity
-        }
+        // the check's verdict words, and the resolved-geometry tables the same kernel fills (grow-only)
+        API_HIP(&c, grow(c.stream, nullptr, want(c.validateDev, 8), want(c.shadeGeomDev, c.objectCount), want(c.shadeTexDev, kTextureSlots * (size_t)c.objectCount)));
         API_HIP(&c, hipMemsetAsync(c.validateDev.data(), 0, sizeof(uint32_t) * 8, c.stream));
         API_HIP(&c, launch_validate_objects(c.stream, c.objects, c.objectCount, c.heapDev.data(), heapCount, c.validateDev.data(), c.shadeGeomDev.data(), c.shadeTexDev.data()));
         // do all instances of a bottom level name the same vertex data? (the frame's normal records are made from the first one's objects)

@@ -1025,20 +1025,10 @@ hipError_t refit_blas_device(const PtGeometryDesc* geoms, uint32_t ngeoms, hipSt
     return hipGetLastError();
 }
 
-// TLAS over n instances: nodes into out.nodes (the order of the leaf items is tree.indexSorted through tree.leafDst). build_tlas_prepare sizes the arrays (grow-only:
-// a rebuild with no more instances than before allocates nothing); build_tlas_device only enqueues kernels -- no sync, no
-// allocation; the header (node count, depth) stays on the device until the caller reads it.
-hipError_t build_tlas_prepare(Tlas& out, uint32_t n)
-{
-    BVH_CHECK(ensure_tree_buffers(out.tree, n, 1, false));
-    const uint32_t nodes = wide_node_capacity(n ? n : 1);
-    if (nodes > out.nodes.capacity()) {
-        out.nodes.reset(); out.rootBounds.reset();
-        BVH_CHECK(out.rootBounds.reserve(8));
-        BVH_CHECK(out.nodes.reserve(nodes));                // last: the grow decision reads its capacity
-    }
-    return hipSuccess;
-}
+// TLAS over n instances: nodes into out.nodes, which the caller has grown to wide_node_capacity(n) (the order of the leaf items is tree.indexSorted through
+// tree.leafDst). build_tlas_prepare sizes the build buffers (grow-only: a rebuild with no more instances than before allocates nothing);
+// build_tlas_device only enqueues kernels -- no sync, no allocation; the header (node count, depth) stays on the device until the caller reads it.
+hipError_t build_tlas_prepare(Tlas& out, uint32_t n) { return ensure_tree_buffers(out.tree, n, 1, false); }
 
 hipError_t build_tlas_device(const InstanceRecord* dInstances, const float* const* dBlasBounds, uint32_t n, hipStream_t stream, Tlas& out)
 {

@@ -305,7 +305,7 @@ int pt_denoiser_process(PtContext* ctx, const struct PtDenoiserTextures* t)
     const uint32_t W = s.RenderSize[0], H = s.RenderSize[1];
     const size_t n = (size_t)W * H;
     API_HIP(&c, hipSetDevice(c.device));
-    if (int e = fl_grow_history(c, c.dnState, { { c.dnHistory, n * DN_SLOTS } })) return e;
+    if (int e = fl_grow_history(c, c.dnState, want(c.dnHistory, n * DN_SLOTS))) return e;
     if (s.AtrousIterations >= 3u && dn_staged(c, 4u))           // the staged tile of step 4 is beyond the 64 kB a launch gets unasked
         API_HIP(&c, hipFuncSetAttribute((const void*)k_dn_atrous<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 32 * (int)kDnStagedBytes));
     float4* base = c.dnHistory.data();

@@ -1217,16 +1217,12 @@ hipError_t ensure_light_list(Context& c, const SceneView& sv)
     const uint32_t n = c.scene.instanceCount;
     c.lightCount = 0; c.lightListValid = false; c.diHistoryValid = false;       // light indices may move
     if (n && c.scene.instSource && c.scene.blasTable && c.objectCount) {
-        if (n + 1u > c.lightInstStart.capacity()) {
-            if ((e = hipStreamSynchronize(c.stream)) != hipSuccess) return e;
-            if ((e = c.lightInstStart.reserve(n + 1u)) != hipSuccess) return e;
-        }
+        if ((e = grow(c.stream, nullptr, want(c.lightInstStart, n + 1u))) != hipSuccess) return e;
         k_light_count<<<1, 1024, 0, c.stream>>>(c.scene.instSource, c.scene.blasTable, n, sv.objects, sv.heap, c.lightInstStart.data());
         uint32_t total = 0;
         if ((e = hipMemcpyAsync(&total, c.lightInstStart.data() + n, sizeof total, hipMemcpyDeviceToHost, c.stream)) != hipSuccess) return e;
         if ((e = hipStreamSynchronize(c.stream)) != hipSuccess) return e;
-        if ((e = c.lightList.reserve(total)) != hipSuccess) return e;
-        if ((e = c.lightFirst.reserve(c.objectCount)) != hipSuccess) return e;
+        if ((e = grow(c.stream, nullptr, want(c.lightList, total), want(c.lightFirst, c.objectCount))) != hipSuccess) return e;
         if ((e = hipMemsetAsync(c.lightFirst.data(), 0xFF, sizeof(uint32_t) * c.objectCount, c.stream)) != hipSuccess) return e;
         if (total) k_light_fill<<<n, 256, 0, c.stream>>>(c.scene.instSource, c.scene.blasTable, sv.objects, sv.heap, c.lightInstStart.data(), c.lightList.data(),
                                                          c.lightFirst.data(), c.objectCount);
@@ -1301,14 +1297,8 @@ static bool di_pdf_acts(const Context& c)
 // the PDF texture and its chain too; where it acts nothing of the render reads the prefix sum, and its three launches are skipped.
 static int di_light_records(Context& c, const SceneView& sv, uint32_t n, uint32_t nb)
 {
-    if (n > c.lightRecords.capacity()) {
-        API_HIP(&c, hipStreamSynchronize(c.stream));
-        c.lightRecords.reset(); c.lightCdf.reset(); c.lightBlockSums.reset();
-        API_HIP(&c, c.lightCdf.reserve((size_t)n * 2u));                  // cdf | powers
-        API_HIP(&c, c.lightBlockSums.reserve(nb + 1u));
-        API_HIP(&c, c.lightRecords.reserve(n));   // last: the grow decision reads its capacity
-    }
-    float* power = c.lightCdf.data() + c.lightRecords.capacity();
+    API_HIP(&c, grow(c.stream, nullptr, want(c.lightRecords, n), want(c.lightCdf, (size_t)n * 2u), want(c.lightBlockSums, nb + 1u)));
+    float* power = c.lightCdf.data() + c.lightCdf.capacity() / 2u;        // cdf | powers: the halves of the one buffer, whatever else grew with it
     k_light_records<<<(n + 255u) / 256u, 256, 0, c.stream>>>(c.lightList.data(), n, c.scene.instSource, sv.objects, sv.heap, sv.shadeTex, sv.srgbLut, (float4*)c.lightRecords.data(), power);
     if (!di_pdf_acts(c)) {
         k_cdf_local<<<nb, 256, 0, c.stream>>>(power, n, c.lightCdf.data(), c.lightBlockSums.data());
@@ -1320,10 +1310,7 @@ static int di_light_records(Context& c, const SceneView& sv, uint32_t n, uint32_
     uint32_t size[3];
     di_pdf_size(n, size);
     const uint32_t texels = di_pdf_texels(size);
-    if ((size_t)texels + 1u > c.diPdfTexture.capacity()) {
-        API_HIP(&c, hipStreamSynchronize(c.stream));
-        API_HIP(&c, c.diPdfTexture.reserve((size_t)texels + 1u));
-    }
+    API_HIP(&c, grow(c.stream, nullptr, want(c.diPdfTexture, (size_t)texels + 1u)));
     float* levels[16];
     uint32_t at = 0;
     for (uint32_t k = 0; k < size[2]; k++) { levels[k] = c.diPdfTexture.data() + at; at += di_pdf_level_texels(size, k); }
@@ -1410,17 +1397,8 @@ static int di_presample(Context& c, uint32_t n, uint32_t nb, DISampling& ls)
     if (lss.Mode != PT_DI_LOCAL_LIGHT_POWER_RIS && lss.Mode != PT_DI_LOCAL_LIGHT_REGIR_RIS) return PT_OK;
     const bool regir = lss.Mode == PT_DI_LOCAL_LIGHT_REGIR_RIS, onion = regir && c.diReGIRLayout == PT_DI_REGIR_LAYOUT_ONION;
     const uint32_t cellEntries = onion ? kDIOnionEntries : kDICellEntries;                    // 9.2 MB or 16 MB, only in ReGIR mode
-    if (c.diTiles.capacity() < kDITileEntries || (regir && c.diCells.capacity() < cellEntries) || (onion && !c.diOnion)) {
-        API_HIP(&c, hipStreamSynchronize(c.stream));
-        API_HIP(&c, c.diTiles.reserve(kDITileEntries));
-        if (regir && c.diCells.capacity() < cellEntries) API_HIP(&c, c.diCells.reserve(cellEntries));
-        if (onion && !c.diOnion) {
-            DeviceBuffer<float> dev;
-            API_HIP(&c, dev.reserve(sizeof(OnionTables) / sizeof(float)));
-            API_HIP(&c, hipMemcpy(dev.data(), &onion_tables(), sizeof(OnionTables), hipMemcpyHostToDevice));
-            c.diOnion = std::move(dev);
-        }
-    }
+    API_HIP(&c, grow(c.stream, nullptr, want(c.diTiles, kDITileEntries), want(c.diCells, regir ? cellEntries : 0u)));
+    if (onion) API_HIP(&c, upload_once(c.diOnion, &onion_tables(), sizeof(OnionTables)));
     if (di_pdf_acts(c))
         k_di_presample_tiles_mip<<<kDITileEntries / 256u, 256, 0, c.stream>>>(c.diPdfTexture.data(), c.diPdfSize[0], c.diPdfSize[1], c.diPdfSize[2], di_pdf_texels(c.diPdfSize),
                                                                              n, c.diSettings.FrameIndex, (uint2*)c.diTiles.data());
@@ -1489,21 +1467,13 @@ static int di_launch_reuse(Context& c, const DIArgs& a, const DISampling& ls, co
     const bool temporal = rs.TemporalResampling, spatial = rs.SpatialSamples > 0;
     const FrameView& fv = a.fv;
     const size_t npix = (size_t)fv.width * fv.localRows;
-    if (npix > c.diResB.capacity() || !c.diOffsets) {
-        API_HIP(&c, hipStreamSynchronize(c.stream));
-        if (npix > c.diResB.capacity()) {
-            c.diResA.reset(); c.diResB.reset(); c.diHistoryValid = false;
-            API_HIP(&c, c.diResA.reserve(npix));
-            API_HIP(&c, c.diResB.reserve(npix));                          // last: the grow decision reads its capacity
-        }
-        if (!c.diOffsets) {
-            int8_t host[2 * kDIOffsetCount];
-            build_di_offsets(host);
-            DeviceBuffer<int8_t> dev;
-            API_HIP(&c, dev.reserve(sizeof host));
-            API_HIP(&c, hipMemcpy(dev.data(), host, sizeof host, hipMemcpyHostToDevice));
-            c.diOffsets = std::move(dev);
-        }
+    bool grew = false;
+    API_HIP(&c, grow(c.stream, &grew, want(c.diResA, npix), want(c.diResB, npix)));
+    if (grew) c.diHistoryValid = false;
+    if (!c.diOffsets) {
+        int8_t host[2 * kDIOffsetCount];
+        build_di_offsets(host);
+        API_HIP(&c, upload_once(c.diOffsets, host, sizeof host));
     }
     if (c.diHistorySize[0] != fv.width || c.diHistorySize[1] != fv.height || c.diHistoryLightKey != c.lightListKey) c.diHistoryValid = false;
     DIReuseArgs r; memset(&r, 0, sizeof r);
@@ -1594,10 +1564,7 @@ int pt_di_render_with_history(PtContext* ctx, const PtTextures* tx, const PtDIPr
     const dim3 grid((fv.width + 15u) / 16u, (fv.localRows + 15u) / 16u);
     if (c.diBrdf.BrdfSamples) {                                               // the BRDF candidates' rays, ahead of whichever pass draws the candidates
         const size_t nrec = npix * c.diBrdf.BrdfSamples;
-        if (nrec > c.diBrdfRecords.capacity()) {
-            API_HIP(&c, hipStreamSynchronize(c.stream));
-            API_HIP(&c, c.diBrdfRecords.reserve(nrec));
-        }
+        API_HIP(&c, grow(c.stream, nullptr, want(c.diBrdfRecords, nrec)));
         a.brdfSamples = c.diBrdf.BrdfSamples; a.brdfCutoff = c.diBrdf.BrdfCutoff;
         a.brdfRecords = c.diBrdfRecords.data(); a.firstLight = c.lightFirst.data(); a.objectCount = c.objectCount;
         k_di_brdf_rays<<<grid, 256, 0, c.stream>>>(a, c.diBrdfRecords.data(), c.scene.blob, ac, c.counters.data());

@@ -212,20 +212,13 @@ int fl_set_constants(Context& c, const S* s, const char* (*check)(const S*), S& 
     return PT_OK;
 }
 
-// Grows the grow-only histories of a pass to the float4 counts asked for. Transactional: the old ones stay until every new one exists;
-// one wait for the stream, as an earlier call may still use the old ones; a history that grew starts again.
-struct HistoryDemand { DeviceBuffer<float4>& buffer; size_t slots; };
-template <size_t N>
-int fl_grow_history(Context& c, FilterState& state, const HistoryDemand (&demands)[N])
+// Grows the grow-only histories of a pass to the float4 counts asked for (want(), pt_memory.hpp); a history that grew starts again.
+template <typename... D>
+int fl_grow_history(Context& c, FilterState& state, D... demands)
 {
-    DeviceBuffer<float4> fresh[N];
-    bool grow = false;
-    for (size_t k = 0; k < N; ++k)
-        if (demands[k].buffer.capacity() < demands[k].slots) { API_HIP(&c, fresh[k].reserve(demands[k].slots)); grow = true; }
-    if (!grow) return PT_OK;
-    API_HIP(&c, hipStreamSynchronize(c.stream));
-    for (size_t k = 0; k < N; ++k) if (fresh[k]) demands[k].buffer = std::move(fresh[k]);
-    state.frames = 0;
+    bool grew = false;
+    API_HIP(&c, grow(c.stream, &grew, demands...));
+    if (grew) state.frames = 0;
     return PT_OK;
 }
 

@@ -793,17 +793,20 @@ hipError_t launch_gbuffer(Context& c, const SceneView& sv, const FrameView& fv, 
     return hipGetLastError();
 }
 
-static hipError_t ensure_queues(Context& c, uint32_t capacity, uint32_t iterations)
+// what a frame of `capacity` queue entries and `iterations` counters writes besides its textures: one growth, and the queue views made from what stands after it
+static hipError_t ensure_queues(Context& c, uint32_t capacity, uint32_t iterations, bool sharc)
 {
-    hipError_t e = hipSuccess;
-    for (auto& arrays : c.queueArrays) for (auto& a : arrays) if (e == hipSuccess) e = a.reserve(capacity);   // each array freed, then allocated, in turn
+    bool grew = false;
+    const hipError_t e = grow(c.stream, &grew, want(c.queueArrays[0], capacity), want(c.queueArrays[1], capacity),
+                              want(c.primaryRecords, 3 * (size_t)capacity),          // 48 bytes per local pixel (capacity >= pixels)
+                              want(c.queueCounts, iterations), want(c.frameConstants, 1),
+                              want(c.sharcRough, sharc ? capacity : 0u));             // previousRoughness, indexed like the path queues
+    if (e != hipSuccess || !grew) return e;
     for (int k = 0; k < 2; k++) {
         DeviceBuffer<uint4>* a = c.queueArrays[k];
         c.queue[k] = PathQueue{ (float4*)a[0].data(), (float4*)a[1].data(), (float4*)a[2].data(), (float4*)a[3].data(), (float4*)a[4].data(), a[5].data() };
     }
-    if (e != hipSuccess) return e;
-    if ((e = c.primaryRecords.reserve(3 * (size_t)capacity)) != hipSuccess) return e;   // 48 bytes per local pixel (capacity >= pixels)
-    return c.queueCounts.reserve(iterations);
+    return hipSuccess;
 }
 
 static void timing_begin(Context& c, std::vector<Event>& ev, uint32_t k)
@@ -991,22 +994,16 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
     const PtGraphicsSettings& gs = c.settings;
     const uint32_t npix = fv.width * fv.localRows;
     c.lastIterations = 0;
-    if (c.normalsShared && c.scene.blasTable && c.scene.blob.triCount > c.shadeRecB.capacity()) {       // the frame's normal records: 20 B per triangle packet (grow-only)
-        hipError_t ea = hipStreamSynchronize(c.stream);
-        if (ea != hipSuccess) return ea;
-        c.shadeRecA.reset(); c.shadeRecB.reset();
-        if ((ea = c.shadeRecA.reserve(c.scene.blob.triCount)) != hipSuccess) return ea;
-        if ((ea = c.shadeRecB.reserve(c.scene.blob.triCount)) != hipSuccess) return ea;   // last: the grow decision reads its capacity
-    }
-    if (npix == 0 || gs.SamplesPerPixel == 0) return hipSuccess;
-    hipError_t e;
-    if (gs.Denoiser != PT_DENOISER_NONE && (e = c.pixelAux.reserve(npix)) != hipSuccess) return e;
+    const bool renders = npix != 0 && gs.SamplesPerPixel != 0;
+    // what the plan reads: the frame's normal records, 20 B per triangle packet, and the denoiser modes' per-pixel words (grow-only)
+    hipError_t e = grow(c.stream, nullptr, want(c.shadeRecA, c.normalsShared && c.scene.blasTable ? c.scene.blob.triCount : 0u),
+                        want(c.shadeRecB, c.normalsShared && c.scene.blasTable ? c.scene.blob.triCount : 0u),
+                        want(c.pixelAux, renders && gs.Denoiser != PT_DENOISER_NONE ? npix : 0u));
+    if (e != hipSuccess || !renders) return e;
     FramePlan plan; plan_frame(plan, c, sv, fv, sharcQuery);
     const FramePlan& p = plan;
     const uint32_t rounds = p.rounds, nsq = p.nsq(), cstride = p.cstride();
-    if ((e = ensure_queues(c, p.segCap * nsq, (rounds + 2) * cstride)) != hipSuccess) return e;
-    if ((e = c.frameConstants.reserve(1)) != hipSuccess) return e;
-    if (p.sharc) for (auto& a : c.sharcRough) if ((e = a.reserve((size_t)p.segCap * nsq)) != hipSuccess) return e;   // previousRoughness, indexed like the path queues
+    if ((e = ensure_queues(c, p.segCap * nsq, (rounds + 2) * cstride, p.sharc)) != hipSuccess) return e;
     FrameConstants fc; fc.cam = c.camera; fc.sd = c.sceneData; fc.gs = c.settings;
     k_set_constants<<<1, 256, 0, c.stream>>>(fc, c.frameConstants.data(), c.queueCounts.data(), (rounds + 2u) * cstride);
     c.lastIterations = rounds + 1;
@@ -1020,7 +1017,7 @@ hipError_t launch_raytrace(Context& c, const SceneView& sv, const FrameView& fv,
     key_add(key, c.sharcView.data()); key_add(key, c.sharcRough[0].data()); key_add(key, c.sharcRough[1].data());
     key_add(key, c.shadeRecA.data()); key_add(key, c.scene.blasTable); key_add(key, c.scene.blasTableCount); key_add(key, c.scene.blasTableMaxTris);
     if (key != c.roundArgsKey || !c.roundArgs.data()) {                              // k_round's argument blocks, one per round (device memory)
-        if ((e = c.roundArgs.reserve(rounds + 1)) != hipSuccess) return e;
+        if ((e = grow(c.stream, nullptr, want(c.roundArgs, rounds + 1))) != hipSuccess) return e;
         std::vector<RoundArgs> host(rounds + 1);
         for (uint32_t r = 0; r <= rounds; r++) {
             RoundArgs& a = host[r];

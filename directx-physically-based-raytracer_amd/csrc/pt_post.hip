@@ -266,12 +266,7 @@ int pt_post_render(PtContext* ctx, const PtPostTextures* t)
         dims[st][0] = std::max(1u, (W / 2u) >> k); dims[st][1] = std::max(1u, (H / 2u) >> k);
         off[st] = total; total += (size_t)dims[st][0] * dims[st][1];
     }
-    if (c.postLevels.capacity() < total) {                 // transactional: the old pyramid stays until the new one exists
-        DeviceBuffer<ushort4> fresh;
-        API_HIP(&c, fresh.reserve(total));
-        API_HIP(&c, hipStreamSynchronize(c.stream));          // earlier renders may still read the old one
-        c.postLevels = std::move(fresh);
-    }
+    API_HIP(&c, grow(c.stream, nullptr, want(c.postLevels, total)));
     memset(c.postDims, 0, sizeof c.postDims);
     ushort4* base = c.postLevels.data();
     for (int st = 0; st < kPostStages; ++st) {

@@ -341,7 +341,7 @@ int pt_reconstruction_process(PtContext* ctx, const struct PtReconstructionTextu
     }
     if (int refusal = fl_check_jitter(c, jitter)) return refusal;
     API_HIP(&c, hipSetDevice(c.device));
-    if (int e = fl_grow_history(c, c.rrState, { { c.rrHistory, n * RR_SLOTS }, { c.rrOutput, fl_output_slots(no) } })) return e;
+    if (int e = fl_grow_history(c, c.rrState, want(c.rrHistory, n * RR_SLOTS), want(c.rrOutput, fl_output_slots(no)))) return e;
     float4* base = c.rrHistory.data();
     float2* halves = (float2*)(base + n * RR_SLOTS4);
     const uint32_t cur = c.rrState.parity ^ 1u, prev = c.rrState.parity;

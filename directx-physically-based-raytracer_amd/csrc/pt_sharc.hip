@@ -314,14 +314,8 @@ int pt_sharc_configure(PtContext* ctx, uint32_t capacity)
     if (capacity == 0u) capacity = 1u << 22;
     API_ARG(&c, capacity % kSharcBucket == 0u, "SHARC capacity must be a multiple of 32 (the bucket of the hash map)");
     API_HIP(&c, hipSetDevice(c.device));
-    if (capacity > c.sharcKeys.capacity()) {                 // kernels in flight may read the old buffers
-        API_HIP(&c, hipStreamSynchronize(c.stream));
-        c.sharcCapacity = 0;
-        c.sharcKeys.reset(); for (auto& v : c.sharcVoxels) v.reset();
-        for (auto& v : c.sharcVoxels) API_HIP(&c, v.reserve(capacity));
-        API_HIP(&c, c.sharcView.reserve(1));
-        API_HIP(&c, c.sharcKeys.reserve(capacity));            // last: the grow decision reads its capacity
-    }
+    // (a refused growth leaves the previous configuration, and its cache, as they were)
+    API_HIP(&c, grow(c.stream, nullptr, want(c.sharcKeys, capacity), want(c.sharcVoxels, capacity), want(c.sharcView, 1)));
     c.sharcCapacity = capacity; c.sharcParity = 0;
     API_HIP(&c, sharc_clear(c));
     return PT_OK;
@@ -378,7 +372,7 @@ int pt_raytrace_render_sharc(PtContext* ctx, const PtTextures* tx)
     const uint32_t uw = fv.width / ss.DownscaleFactor, uh = fv.height / ss.DownscaleFactor;
     uint32_t resolved = prev;                                // skipping: the query sees the cache as the last frame left it
     if (!skip) {
-        API_HIP(&c, c.frameConstants.reserve(1));
+        API_HIP(&c, grow(c.stream, nullptr, want(c.frameConstants, 1)));
         API_HIP(&c, hipMemsetAsync(c.sharcVoxels[cur].data(), 0, sizeof(uint4) * (size_t)c.sharcCapacity, c.stream));
         if (uw && uh) {
             SharcUpdateArgs a; memset(&a, 0, sizeof a);
@@ -388,8 +382,7 @@ int pt_raytrace_render_sharc(PtContext* ctx, const PtTextures* tx)
             c.sharcLogPaths = 0; c.sharcLogBounces = 0;
             if (log) {
                 const size_t n = (size_t)uw * uh * (gs.Bounces + 1u);
-                API_HIP(&c, c.sharcLogScatter.reserve(n));
-                API_HIP(&c, c.sharcLog.reserve(n));
+                API_HIP(&c, grow(c.stream, nullptr, want(c.sharcLogScatter, n), want(c.sharcLog, n)));
                 API_HIP(&c, hipMemsetAsync(c.sharcLog.data(), 0, sizeof(PtSHARCPathVertex) * n, c.stream));
                 API_HIP(&c, hipMemsetAsync(c.sharcLogScatter.data(), 0, sizeof(PtSHARCPathScatter) * n, c.stream));
                 a.log = c.sharcLog.data(); a.logScatter = c.sharcLogScatter.data(); a.logBounces = gs.Bounces + 1u;

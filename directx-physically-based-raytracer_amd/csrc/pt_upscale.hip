@@ -144,7 +144,7 @@ int pt_upscaler_process(PtContext* ctx, const struct PtUpscalerTextures* t, cons
     const PtUpscalerSettings& s = c.up;
     const size_t n = (size_t)s.OutputSize[0] * s.OutputSize[1];
     API_HIP(&c, hipSetDevice(c.device));
-    if (int e = fl_grow_history(c, c.upState, { { c.upHistory, fl_output_slots(n) } })) return e;
+    if (int e = fl_grow_history(c, c.upState, want(c.upHistory, fl_output_slots(n)))) return e;
     UpArgs a{};
     a.radiance = t->Radiance; a.depth = (const float*)t->LinearDepth; a.motion = t->MotionVector;
     a.r = fl_resolve_args(c.upState, c.upHistory.data(), t->Color, s.RenderSize, s.OutputSize, jitter, s.MaxAccumulatedFrames, s.KernelRadius, s.DepthThreshold);
