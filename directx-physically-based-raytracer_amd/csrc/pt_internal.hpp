@@ -305,6 +305,16 @@ struct Context {
     DeviceBuffer<float4> rrHistory, rrOutput;
     uint32_t rrFinal = 0;                             // which a-trous work buffer holds the last call's filtered signal
 
+    // frame generation (pt_framegen.hip): four grow-only allocations. The previous frame's Color (8 B per output pixel) and LinearDepth (4 B
+    // per render pixel), the midpoint field of the last call (8 B per render pixel), the class bytes of the test aid (1 B per output pixel).
+    // fgState.frames == 0: there is no previous frame; fgState.parity is not used (the previous frame is an explicit copy).
+    PtFrameGenerationSettings fg{}; FilterState fgState;  // size: render w, h and output w, h of the last call that generated a frame
+    DeviceBuffer<uint64_t> fgPrevColor, fgField;
+    DeviceBuffer<float> fgPrevDepth;
+    DeviceBuffer<uint8_t> fgClass;
+    float fgPrevJitter[2] = { 0.0f, 0.0f };           // the Camera.Jitter of the frame in fgPrevDepth
+    bool fgFieldValid = false;                        // the last call generated a frame: field and class bytes are its
+
     // SHARC radiance cache (pt_sharc.hip): per context, also for a context that views another's scene. sharcVoxels[sharcParity] is VoxelData (this
     // frame's deposits, then the resolved cache), the other one PreviousVoxelData; they swap after the query.
     PtSHARCSettings sharcSettings{}; bool haveSharcSettings = false;

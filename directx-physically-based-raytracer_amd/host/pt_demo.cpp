@@ -9,6 +9,7 @@
 //           [--nrd relax|reblur [--denoise [--denoise-frames-max N] [--denoise-iterations K]]] [--out-radiance file.bin]
 //           [--upscale native|quality|balanced|performance|ultra [--output-size WxH] [--out-upscaled file.bin]]
 //           [--reconstruct native|quality|balanced|performance|ultra --output-size WxH [--reconstruct-iterations K] [--out-reconstructed file.bin]]
+//           [--frame-generation [--fg-phase PHI] [--out-generated file.bin] [--png-generated file.png]] [--camera-start X] [--camera-step DX]
 //           [--png file.png] [--out-display file.bin] [--scene descriptor.json [--anim-time T [--anim-step DT]]] [--dump-scene file.bin]
 //
 // --anim-time T (with --scene): the animated render objects of the descriptor (RenderObjects[].Animation) are posed at T seconds of their selected
@@ -58,6 +59,14 @@
 // ProcessDLSSRayReconstruction (App.cpp:1513-1523), ahead of --post. --reconstruct-iterations K: its a-trous iterations (0..8, default 5).
 // --out-reconstructed writes the last frame's Color (R16G16B16A16_FLOAT at the output size). Refused together with --upscale or --nrd (the
 // pass is both steps); composes with --sharc, --di --restir, --post, --frames.
+// --frame-generation (one unsharded process, needs --post and --frames 2 or more): the library's own frame interpolator (ptamd.hpp
+// FrameGeneration; not a port of DLSS-G or FSR 3) runs behind the post chain of every frame, where the reference tags DLSS-G's inputs
+// (App.cpp:1564-1566), on the post chain's Color, the frame's LinearDepth and MotionVector and its jitter. --fg-phase PHI: the phase between
+// the two frames (default 0.5). --out-generated writes the frame generated between the last two rendered ones (R16G16B16A16_FLOAT at the
+// output size), --png-generated its 8-bit form as an RGB PNG. Composes with --upscale, --reconstruct, --nrd ... --denoise. On a sequence
+// that does not move the generated frame is the blend of the two.
+// --camera-start X --camera-step DX (one unsharded process): timed frame f is rendered from the scene's camera moved by X + f DX along world
+// x, with the pose of frame f - 1 in the camera's Previous* members (the motion vectors follow); the warm-up frame stands at X.
 //
 // --ranks R: one process per GPU. The parent (which never touches a GPU) starts R children `--rank r --world R --id-file F`; rank 0
 // makes the RCCL unique id and leaves it in F, the others pick it up; every rank renders its 16-row bands (BandSharding) and rank 0
@@ -254,14 +263,14 @@ static HostScene ingested_scene(const std::string& path)
 }
 
 // scenes.py:make_camera (hfov 90, near 0.01, far inf): XMMatrixLookToLH + SetupByHalfFovxInf, row-vector convention
-static PtCamera make_camera(const HostScene& sc, double aspect)
+static PtCamera make_camera(const HostScene& sc, double aspect, const double* position = nullptr)
 {
     auto norm = [](double v[3]) { const double l = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); v[0] /= l; v[1] /= l; v[2] /= l; };
     auto cross = [](const double a[3], const double b[3], double o[3]) { o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0]; };
     auto dot = [](const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
     double f[3] = { sc.cameraForward[0], sc.cameraForward[1], sc.cameraForward[2] }, r[3], u[3];
     norm(f); cross(sc.cameraUp, f, r); norm(r); cross(f, r, u);
-    const double* pos = sc.cameraPosition;
+    const double* pos = position ? position : sc.cameraPosition;
     const double rightLen = std::tan((90.0 * (M_PI / 180.0)) / 2), upLen = rightLen / aspect, nearD = 0.01;
     PtCamera cam{};
     cam.IsNormalizedDepthReversed = 1;
@@ -289,6 +298,20 @@ static PtCamera make_camera(const HostScene& sc, double aspect)
         cam.ProjectionToView[i] = cam.PreviousProjectionToView[i] = (float)p2v[i / 4][i % 4];
         cam.ViewToWorld[i] = cam.PreviousViewToWorld[i] = (float)v2w[i / 4][i % 4];
     }
+    return cam;
+}
+
+// the camera at `position` whose Previous* members are the camera at `previous`: a frame of a camera that moves (--camera-step)
+static PtCamera make_moved_camera(const HostScene& sc, double aspect, const double* position, const double* previous)
+{
+    PtCamera cam = make_camera(sc, aspect, position);
+    const PtCamera prev = make_camera(sc, aspect, previous);
+    memcpy(cam.PreviousPosition, prev.Position, sizeof cam.PreviousPosition);
+    memcpy(cam.PreviousWorldToProjection, prev.WorldToProjection, sizeof cam.PreviousWorldToProjection);
+    memcpy(cam.PreviousProjectionToView, prev.ProjectionToView, sizeof cam.PreviousProjectionToView);
+    memcpy(cam.PreviousViewToWorld, prev.ViewToWorld, sizeof cam.PreviousViewToWorld);
+    memcpy(cam.PreviousWorldToView, prev.PreviousWorldToView, sizeof cam.PreviousWorldToView);
+    memcpy(cam.PreviousViewToProjection, prev.PreviousViewToProjection, sizeof cam.PreviousViewToProjection);
     return cam;
 }
 
@@ -432,6 +455,8 @@ int main(int argc, char** argv)
     bool denoise = false; uint32_t denoiseFramesMax = 30, denoiseIterations = 5;
     std::string upscale, outputSize, upscaledPath;
     std::string reconstruct, reconstructedPath; int reconstructIterations = -1;
+    bool frameGeneration = false; float fgPhase = 0.5f; std::string generatedPath, generatedPngPath;
+    bool cameraMoves = false; double cameraStart = 0.0, cameraStep = 0.0;
     for (int i = 1; i < argc; i++) {
         std::string k = argv[i];
         if (k == "--di") { di = true; continue; }                  // the flags without a value
@@ -445,6 +470,7 @@ int main(int argc, char** argv)
         if (k == "--no-bloom") { bloom = false; continue; }
         if (k == "--hdr") { hdr = true; continue; }
         if (k == "--denoise") { denoise = true; continue; }
+        if (k == "--frame-generation") { frameGeneration = true; continue; }
         if (i + 1 >= argc) break;
         const char* v = argv[++i];
         if (k == "--width") W = atoi(v); else if (k == "--height") H = atoi(v);
@@ -466,6 +492,8 @@ int main(int argc, char** argv)
         else if (k == "--upscale") upscale = v; else if (k == "--output-size") outputSize = v; else if (k == "--out-upscaled") upscaledPath = v;
         else if (k == "--reconstruct") reconstruct = v; else if (k == "--out-reconstructed") reconstructedPath = v;
         else if (k == "--reconstruct-iterations") reconstructIterations = atoi(v);
+        else if (k == "--fg-phase") fgPhase = (float)atof(v); else if (k == "--out-generated") generatedPath = v; else if (k == "--png-generated") generatedPngPath = v;
+        else if (k == "--camera-start") { cameraMoves = true; cameraStart = atof(v); } else if (k == "--camera-step") { cameraMoves = true; cameraStep = atof(v); }
         else if (k == "--anim-time") { animate = true; animTime = atof(v); } else if (k == "--anim-step") animStep = atof(v);
     }
     post = post || !pngPath.empty() || !displayPath.empty();
@@ -503,6 +531,14 @@ int main(int argc, char** argv)
             Upscaler::RenderSize(mode, output, render);
             W = render[0]; H = render[1];
         } else if (!outputSize.empty() || !upscaledPath.empty()) throw std::invalid_argument("--output-size and --out-upscaled need --upscale");
+        if (frameGeneration) {
+            if (!post) throw std::invalid_argument("--frame-generation interpolates the tone-mapped Color: it needs --post");
+            if (sharded) throw std::invalid_argument("--frame-generation needs one unsharded process");
+            if (frames < 2) throw std::invalid_argument("--frame-generation needs --frames 2 or more: the first frame has no predecessor");
+            if (hdr && !generatedPngPath.empty()) throw std::invalid_argument("--png-generated writes an SDR image: drop --hdr");
+        } else if (fgPhase != 0.5f || !generatedPath.empty() || !generatedPngPath.empty())
+            throw std::invalid_argument("--fg-phase, --out-generated and --png-generated need --frame-generation");
+        if (cameraMoves && sharded) throw std::invalid_argument("--camera-start / --camera-step need one unsharded process");
         int deviceCount = 0;
         HIP_OK(hipGetDeviceCount(&deviceCount));
         if ((int)world > deviceCount) { fprintf(stderr, "pt_demo: %u ranks need %u GPUs, %d visible\n", world, world, deviceCount); return 4; }
@@ -686,6 +722,13 @@ int main(int argc, char** argv)
                                         alloc(outPx * 8) };
             if (runPost) postProcessing.Textures.Radiance = reconstruction.Textures.Color;
         }
+        FrameGeneration generation(commandList);
+        bool generated = false;                                     // the last frame's Generated is an interpolated frame
+        if (frameGeneration) {                                      // App.cpp:1564-1566: behind ToneMap, where the reference tags DLSS-G's inputs
+            FrameGeneration::Settings s; s.RenderSize[0] = W; s.RenderSize[1] = H; s.OutputSize[0] = outW; s.OutputSize[1] = outH; s.Phase = fgPhase;
+            generation.SetConstants(s);
+            generation.Textures = { postProcessing.Textures.Color, tx.LinearDepth, tx.MotionVector, alloc(outPx * 8), alloc(outPx * 4) };
+        }
         SHARC sharc(commandList);
         Raytracing::SHARCSettings sharcSettings; sharcSettings.DownscaleFactor = sharcDownscale;
         if (useSharc) { sharc.Constants.SceneScale = sceneScale; sharc.Configure(); }
@@ -770,8 +813,15 @@ int main(int argc, char** argv)
         bool firstFrame = true;
         PtCounters counters{};
         double ms = 0;
+        uint32_t poseIndex = 0;                                     // --camera-step: which frame of the camera's path renderFrame renders
         auto renderFrame = [&](uint32_t frameIndex) {
             float jitter[2] = { 0.0f, 0.0f };
+            if (cameraMoves) {                                      // sideways along world x; the first pose is its own predecessor
+                const double x = cameraStart + cameraStep * poseIndex;
+                const double now[3] = { scene.cameraPosition[0] + x, scene.cameraPosition[1], scene.cameraPosition[2] };
+                const double before[3] = { scene.cameraPosition[0] + (poseIndex ? x - cameraStep : x), scene.cameraPosition[1], scene.cameraPosition[2] };
+                cam = make_moved_camera(scene, (double)outW / (double)outH, now, before);
+            }
             if (resizing) {                                         // App.cpp:556: the frame's Halton jitter, in the camera every pass reads
                 const uint32_t render[2] = { W, H }, output[2] = { outW, outH };
                 Upscaler::Jitter(frameIndex, render, output, jitter);
@@ -815,6 +865,10 @@ int main(int argc, char** argv)
                 reconstruction.Process(commandList, jitter);
             }
             if (runPost) postProcessing.Render(commandList);
+            if (frameGeneration) {                                  // the restir swap may have moved LinearDepth
+                generation.Textures.LinearDepth = tx.LinearDepth;
+                generated = generation.Process(commandList, jitter);
+            }
         };
         animateFrame();
         renderFrame(12345);                                         // warm-up
@@ -822,12 +876,14 @@ int main(int argc, char** argv)
         if (denoise) denoiser.ResetHistory();                       // the warm-up frame is not part of the sequence
         if (upscaling) upscaler.ResetHistory();
         if (reconstructing) reconstruction.ResetHistory();
+        if (frameGeneration) generation.ResetHistory();
         // timed run: frames 1..N back to back
         ThrowIfFailed(commandList.Context, pt_reset_counters(commandList.Context));
         const auto t0 = std::chrono::steady_clock::now();
         for (uint32_t f = 0; f < frames; f++) {                    // the last frame has FrameIndex 0 (dumped below)
             if (f) for (AnimationCollection* c : collectionList) (*c)[c->GetSelectedIndex()].Tick(animStep);
             animateFrame();
+            poseIndex = f;
             renderFrame(denoise || resizing ? f : frames - 1 - f);  // a denoised or upscaled run is a temporal sequence: FrameIndex counts up
         }
         commandList.End();
@@ -883,6 +939,19 @@ int main(int argc, char** argv)
             FILE* fp = fopen(reconstructedPath.c_str(), "wb");
             if (!fp || fwrite(host.data(), 8, outPx, fp) != outPx) { fprintf(stderr, "cannot write %s\n", reconstructedPath.c_str()); if (fp) fclose(fp); return 3; }
             fclose(fp);
+        }
+        if (frameGeneration && !generated) throw std::runtime_error("--frame-generation: the last frame generated nothing");
+        if (frameGeneration && !generatedPath.empty()) {            // the frame between the last two rendered ones
+            std::vector<uint16_t> host(outPx * 4);
+            HIP_OK(hipMemcpy(host.data(), generation.Textures.Generated, outPx * 8, hipMemcpyDeviceToHost));
+            FILE* fp = fopen(generatedPath.c_str(), "wb");
+            if (!fp || fwrite(host.data(), 8, outPx, fp) != outPx) { fprintf(stderr, "cannot write %s\n", generatedPath.c_str()); if (fp) fclose(fp); return 3; }
+            fclose(fp);
+        }
+        if (frameGeneration && !generatedPngPath.empty()) {
+            std::vector<uint8_t> rgba(outPx * 4);
+            HIP_OK(hipMemcpy(rgba.data(), generation.Textures.Generated8, outPx * 4, hipMemcpyDeviceToHost));
+            if (!ptpng::write_rgb(generatedPngPath, rgba.data(), outW, outH)) { fprintf(stderr, "cannot write %s\n", generatedPngPath.c_str()); return 3; }
         }
         if (runPost && !displayPath.empty()) {                      // the presented back buffer of the last frame
             std::vector<uint32_t> words(outPx);

@@ -12,6 +12,7 @@
 //     struct Denoiser            the library's own filter for the ReLAX slot between them (where the reference calls NRD::Denoise)
 //     struct Upscaler            the library's own temporal upscaler for the super-resolution step (where the reference calls DLSS or XeSS)
 //     struct Reconstruction      the library's own denoising upscaler for the ray-reconstruction step (where the reference calls DLSS-RR)
+//     struct FrameGeneration     the library's own frame interpolator for the frame-generation step (where the reference calls DLSS-G)
 // Error behaviour: a failing status becomes the exception type the reference throws at the same place
 // (std::invalid_argument for argument checks, std::system_error otherwise: Source/ErrorHelpers.ixx:16-32).
 // Header-only, plain C++20 (std::span), no HIP headers needed by the including translation unit.
@@ -758,6 +759,55 @@ struct Reconstruction {
         length.assign((size_t)render[0] * render[1], 0.0f); n.assign((size_t)output[0] * output[1], 0.0f);
         if (!length.empty())
             ThrowIfFailed(m_context, pt_reconstruction_download_history(m_context, length.data(), nullptr, length.size(), n.data(), n.size(), render, output));
+    }
+
+private:
+    PtContext* m_context;
+};
+
+// The library's own frame interpolator for the frame-generation step of App::PostProcessGraphics (Source/App.cpp:1564-1566), behind
+// ToneMap, where the reference's default settings hand DLSS-G the depth, the motion vectors and the HUD-less colour
+// (pt_frame_generation_*; DESIGN.md section 1, "Frame generation"): from the tone-mapped Color of this frame and of the one before it to
+// the frame at Phase between them. Not a port of DLSS-G or FSR 3, and unpinned against both. Process takes the Camera.Jitter the frame
+// was rendered with and returns whether Generated is an interpolated frame (false on the call without a previous frame: Generated is
+// Color). A host displays Generated, then Color. Runs on the full frame of an unsharded context.
+static_assert(sizeof(PtFrameGenerationSettings) == 48, "PtFrameGenerationSettings is 48 B");
+struct FrameGeneration {
+    struct Settings {
+        uint32_t RenderSize[2]{}, OutputSize[2]{};                          // RenderSize <= OutputSize <= 4 RenderSize per axis
+        float Phase = 0.5f, DepthThreshold = 0.01f;                         // (0, 1) | (0, 1]
+    };
+
+    PtFrameGenerationTextures Textures{};
+
+    explicit FrameGeneration(CommandList& commandList) : m_context(commandList.Context) {}
+
+    void SetConstants(const Settings& settings)
+    {
+        PtFrameGenerationSettings s{};
+        s.RenderSize[0] = settings.RenderSize[0]; s.RenderSize[1] = settings.RenderSize[1];
+        s.OutputSize[0] = settings.OutputSize[0]; s.OutputSize[1] = settings.OutputSize[1];
+        s.Phase = settings.Phase; s.DepthThreshold = settings.DepthThreshold;
+        ThrowIfFailed(m_context, pt_frame_generation_set_constants(m_context, &s));
+    }
+
+    bool Process(CommandList& commandList, const float (&jitter)[2])
+    {
+        uint32_t generated = 0;
+        ThrowIfFailed(commandList.Context, pt_frame_generation_process(commandList.Context, &Textures, jitter, &generated));
+        return generated != 0;
+    }
+
+    void ResetHistory() { ThrowIfFailed(m_context, pt_frame_generation_reset_history(m_context)); }
+
+    // after the last Process that generated a frame, row-major: the midpoint field per render pixel and the PtFrameGenerationClass byte per
+    // output pixel; both empty when the last call generated nothing. Synchronises.
+    void DownloadField(std::vector<uint64_t>& field, uint32_t (&render)[2], std::vector<uint8_t>& classes, uint32_t (&output)[2])
+    {
+        ThrowIfFailed(m_context, pt_frame_generation_download_field(m_context, nullptr, 0, nullptr, 0, render, output));
+        field.assign((size_t)render[0] * render[1], 0); classes.assign((size_t)output[0] * output[1], 0);
+        if (!field.empty())
+            ThrowIfFailed(m_context, pt_frame_generation_download_field(m_context, field.data(), field.size(), classes.data(), classes.size(), render, output));
     }
 
 private:

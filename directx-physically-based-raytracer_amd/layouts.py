@@ -547,6 +547,55 @@ def reconstruction_settings(render_size, output_size, **overrides):
     return check_reconstruction_settings(s)
 
 
+FRAME_GENERATION_SETTINGS = np.dtype({  # PtFrameGenerationSettings, 48 B
+    "names": ["RenderSize", "OutputSize", "Phase", "DepthThreshold", "_pad"],
+    "formats": [("<u4", 2), ("<u4", 2), "<f4", "<f4", ("<u4", 6)],
+    "offsets": [0, 8, 16, 20, 24], "itemsize": 48})
+assert FRAME_GENERATION_SETTINGS.itemsize == 48
+# PtFrameGenerationTextures member order: five pointers; Generated8 is optional
+FRAME_GENERATION_TEXTURES = ["Color", "LinearDepth", "MotionVector", "Generated", "Generated8"]
+FRAME_GENERATION_DEFAULTS = {"Phase": 0.5, "DepthThreshold": 0.01}
+FRAME_GENERATION_MAX_SIZE = 16384
+# PtFrameGenerationClass: the class byte of an output pixel
+FRAME_GENERATION_BOTH, FRAME_GENERATION_CURRENT_ONLY, FRAME_GENERATION_PREVIOUS_ONLY, FRAME_GENERATION_FALLBACK = 0, 1, 2, 3
+FRAME_GENERATION_EMPTY = 0xFFFFFFFFFFFFFFFF     # a cell of the midpoint field no surface landed in
+
+
+def check_frame_generation_settings(s):
+    """The range checks of pt_frame_generation_set_constants, on the float32 values the library receives: ValueError where it answers
+    PT_ERROR_INVALID_ARGUMENT."""
+    s = np.asarray(s).reshape(())
+    render, output = [int(v) for v in s["RenderSize"]], [int(v) for v in s["OutputSize"]]
+    for name, size in (("RenderSize", render), ("OutputSize", output)):
+        if not all(1 <= v <= FRAME_GENERATION_MAX_SIZE for v in size):
+            raise ValueError(f"{name} must be 1..{FRAME_GENERATION_MAX_SIZE} on both axes")
+    if not all(r <= o <= 4 * r for r, o in zip(render, output)):
+        raise ValueError("OutputSize must be RenderSize..4 RenderSize on both axes")
+    if not 0.0 < float(np.float32(s["Phase"])) < 1.0:
+        raise ValueError("Phase must be in (0, 1)")
+    if not 0.0 < float(np.float32(s["DepthThreshold"])) <= 1.0:
+        raise ValueError("DepthThreshold must be in (0, 1]")
+    return s
+
+
+def frame_generation_settings(render_size, output_size, **overrides):
+    """PtFrameGenerationSettings with the defaults of FRAME_GENERATION_DEFAULTS; overrides by field name. Refuses what
+    pt_frame_generation_set_constants refuses."""
+    s = np.zeros((), FRAME_GENERATION_SETTINGS)
+    for name, size in (("RenderSize", render_size), ("OutputSize", output_size)):
+        if len(size) != 2 or not all(0 <= int(v) <= 0xFFFFFFFF for v in size):
+            raise ValueError(f"{name} is not a pair of 32-bit unsigned values")
+        s[name] = tuple(int(v) for v in size)
+    values = dict(FRAME_GENERATION_DEFAULTS)
+    for k, v in overrides.items():
+        if k not in values:
+            raise ValueError(f"PtFrameGenerationSettings has no field {k}")
+        values[k] = v
+    for k, v in values.items():
+        s[k] = v
+    return check_frame_generation_settings(s)
+
+
 SHARC_SETTINGS = np.dtype({  # PtSHARCSettings: SHARC::Constants + Raytracing::SHARCSettings (Source/MyAppData.h:250-262)
     "names": ["AccumulationFrames", "MaxStaleFrames", "SceneScale", "IsAntiFireflyEnabled", "DownscaleFactor", "RoughnessThreshold",
               "IsHashGridVisualizationEnabled"],

@@ -36,6 +36,7 @@ EXPORTS = [
     "pt_upscaler_set_constants", "pt_upscaler_process", "pt_upscaler_reset_history", "pt_upscaler_download_history",
     "pt_upscaler_render_size", "pt_upscaler_jitter",
     "pt_reconstruction_set_constants", "pt_reconstruction_process", "pt_reconstruction_reset_history", "pt_reconstruction_download_history",
+    "pt_frame_generation_set_constants", "pt_frame_generation_process", "pt_frame_generation_reset_history", "pt_frame_generation_download_field",
     "pt_anim_create_rig", "pt_anim_release_rig", "pt_anim_create_object", "pt_anim_release_object", "pt_anim_evaluate",
     "pt_anim_skeletal_transforms", "pt_anim_download_globals", "pt_anim_download_skeletal", "pt_anim_debug_slerp",
     "pt_sharc_configure", "pt_sharc_set_constants", "pt_raytrace_render_sharc", "pt_sharc_reset", "pt_sharc_download",
@@ -92,6 +93,10 @@ class UpscalerTextures(C.Structure):         # PtUpscalerTextures: four pointers
 
 class ReconstructionTextures(C.Structure):   # PtReconstructionTextures: eight pointers
     _fields_ = [(n, C.c_void_p) for n in L.RECONSTRUCTION_TEXTURES]
+
+
+class FrameGenerationTextures(C.Structure): # PtFrameGenerationTextures: five pointers
+    _fields_ = [(n, C.c_void_p) for n in L.FRAME_GENERATION_TEXTURES]
 
 
 class Sharding(C.Structure):
@@ -253,6 +258,11 @@ def load_library():
         lib.pt_reconstruction_process.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         lib.pt_reconstruction_reset_history.argtypes = [C.c_void_p]
         lib.pt_reconstruction_download_history.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.pt_frame_generation_set_constants.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_frame_generation_process.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
+        lib.pt_frame_generation_reset_history.argtypes = [C.c_void_p]
+        lib.pt_frame_generation_download_field.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.pt_sharc_configure.argtypes = [C.c_void_p, C.c_uint32]
         lib.pt_sharc_set_constants.argtypes = [C.c_void_p, C.c_void_p]
@@ -1268,6 +1278,48 @@ class Reconstruction(_Filter):
         return length, filtered, n
 
 
+class FrameGeneration(_Filter):
+    """The library's own frame interpolator for the frame-generation slot of App::PostProcessGraphics (pt_frame_generation_*; DESIGN.md
+    section 1, "Frame generation"), where the reference's default settings call DLSS-G after the tone-mapped copy. Not a port of DLSS-G or
+    FSR 3, and unpinned against both. From the tone-mapped Color of this frame and of the one before it, with this frame's LinearDepth and
+    MotionVector, to the frame at Phase between them. Process takes the textures by the names of layouts.FRAME_GENERATION_TEXTURES (a
+    missing name is an unbound texture; Generated8 is optional) and the Camera.Jitter the frame was rendered with. Runs on the full frame
+    of an unsharded context. No scene is needed."""
+    _DTYPE, _RECORD, _LAYOUT = L.FRAME_GENERATION_SETTINGS, "PtFrameGenerationSettings", "frame_generation_settings"
+    _SET, _RESET = "pt_frame_generation_set_constants", "pt_frame_generation_reset_history"
+
+    @property
+    def settings(self):
+        """the PtFrameGenerationSettings record last accepted, or None"""
+        return self._settings
+
+    def SetConstants(self, settings):
+        """settings: PtFrameGenerationSettings (layouts.frame_generation_settings)."""
+        self._set_constants(settings)
+
+    def Process(self, jitter, textures=None):
+        """True when Generated holds an interpolated frame; False on the call that has no previous frame (Generated is then Color)."""
+        tex = self.Textures if textures is None else textures
+        t = FrameGenerationTextures(*[_ptr(tex.get(n)) for n in L.FRAME_GENERATION_TEXTURES])
+        j = (C.c_float * 2)(float(jitter[0]), float(jitter[1]))
+        generated = C.c_uint32(0xFFFFFFFF)
+        self.ctx.check(self.ctx.lib.pt_frame_generation_process(self.ctx.handle, C.addressof(t), j, C.byref(generated)))
+        return bool(generated.value)
+
+    def DownloadField(self):
+        """After the last Process that generated a frame: (field, classes). field: the midpoint field, uint64 (h, w) at RenderSize
+        (depth bits << 32 | index of the render pixel that won the cell; layouts.FRAME_GENERATION_EMPTY: none); classes: one
+        layouts.FRAME_GENERATION_* byte per output pixel, uint8 (oh, ow). Empty arrays when the last call generated nothing. Synchronises."""
+        render, output = (C.c_uint32 * 2)(), (C.c_uint32 * 2)()
+        call = self.ctx.lib.pt_frame_generation_download_field
+        self.ctx.check(call(self.ctx.handle, None, 0, None, 0, render, output))
+        field, classes = np.zeros((render[1], render[0]), np.uint64), np.zeros((output[1], output[0]), np.uint8)
+        if field.size:
+            self.ctx.check(call(self.ctx.handle, C.c_void_p(field.ctypes.data), field.size, C.c_void_p(classes.ctypes.data), classes.size,
+                                render, output))
+        return field, classes
+
+
 class SHARC:
     """Mirror of `struct SHARC` (Source/SHARC.ixx) and of the Raytracing::Render overload that takes it: Configure allocates the context's
     cache, SetConstants takes PtSHARCSettings (layouts.sharc_settings), Render runs clear, update, resolve, query and the swap with the
@@ -1342,6 +1394,7 @@ class Renderer:
         self.local_rows = local_rows(height, rank, world, band)
         self.textures = alloc_textures(width, self.local_rows, scene_gpu.device, with_f32, with_denoiser_outputs)
         self.di_history, self._rendered, self._di_brdf_set = di_history, False, False
+        self.generated = False                                            # render(..., generate=): textures["Generated"] is an interpolated frame
         if di_history:                                                    # App.cpp:629-634: the DI pass's Previous* G-buffer
             for n in L.DI_PREVIOUS_TEXTURES:
                 self.textures[n] = self.textures[n[len("Previous"):]].clone()
@@ -1397,10 +1450,26 @@ class Renderer:
         u.SetConstants(L.reconstruction_settings((self.width, self.height), (output_w, output_h), **overrides))
         return u
 
+    def frame_generation(self, output_w, output_h, **overrides):
+        """A new FrameGeneration from this renderer's size to output_w x output_h (the size post= runs at), with
+        layouts.frame_generation_settings' defaults (overrides by field name): render(..., post=..., generate=that). It writes
+        textures["Generated"] and ["Generated8"]. Unsharded contexts only: the pass needs the whole frame."""
+        if getattr(self.ctx, "sharding", (0, 1, 16))[1] > 1:
+            raise PtInvalidArgument("frame generation needs the whole frame: the context is sharded (run FrameGeneration on the gathered textures)")
+        g = FrameGeneration(self.ctx)
+        g.Textures = self.textures
+        g.SetConstants(L.frame_generation_settings((self.width, self.height), (output_w, output_h), **overrides))
+        return g
+
     def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None, post=None, sharc=None, di_visibility=None, di_pairwise=None,
                di_regir_layout=None, di_brdf=None, nrd=None, denoise=None, nrd_hit_distance=None, di_pdf_mipmap=None, upscale=None,
-               reconstruct=None):
-        """reconstruct: a Reconstruction (self.reconstruction(output_w, output_h)) to run the ray-reconstruction step of
+               reconstruct=None, generate=None):
+        """generate: a FrameGeneration (self.frame_generation(output_w, output_h)) to run the frame-generation step of
+        App::PostProcessGraphics (App.cpp:1564-1566) after the post chain: it reads textures["Color"] (post= is required, at the pass's
+        OutputSize), the frame's LinearDepth and MotionVector and the camera's Jitter and writes textures["Generated"] and
+        ["Generated8"]; self.generated tells whether that is an interpolated frame (False on the frame without a predecessor: a copy of
+        Color). None: no such step, nothing changes.
+        reconstruct: a Reconstruction (self.reconstruction(output_w, output_h)) to run the ray-reconstruction step of
         App::PostProcessGraphics (App.cpp:1513-1523) after the frame and before post, where upscale= runs: it reads the frame's noisy
         Radiance, the albedos, the guides and the camera's Jitter and writes textures["Reconstructed"] at its OutputSize; post's
         RenderSize must then be that OutputSize and the post chain reads Reconstructed as its Radiance. settings["Denoiser"] must be
@@ -1465,6 +1534,15 @@ class Renderer:
             out_w, out_h = (int(v) for v in upscale.settings["OutputSize"])
             if post is not None and tuple(int(v) for v in p["RenderSize"]) != (out_w, out_h):
                 raise PtInvalidArgument("post-processing RenderSize differs from the upscaler's OutputSize")
+        if generate is not None:
+            if post is None:
+                raise PtInvalidArgument("generate needs post: the pass interpolates the tone-mapped Color the post chain writes")
+            if not isinstance(generate, FrameGeneration) or generate.settings is None:
+                raise PtInvalidArgument("generate must be a FrameGeneration whose constants are set (Renderer.frame_generation)")
+            if tuple(int(v) for v in generate.settings["RenderSize"]) != (self.width, self.height):
+                raise PtInvalidArgument("the frame generation's RenderSize differs from the renderer's size")
+            if tuple(int(v) for v in generate.settings["OutputSize"]) != tuple(int(v) for v in p["RenderSize"]):
+                raise PtInvalidArgument("the frame generation's OutputSize differs from the post-processing RenderSize")
         if self.di_history and self._rendered:
             for n in L.DI_PREVIOUS_TEXTURES:
                 c = n[len("Previous"):]
@@ -1545,4 +1623,14 @@ class Renderer:
             self.post.SetConstants(post)
             resized = "Upscaled" if upscale is not None else "Reconstructed" if reconstruct is not None else None
             self.post.Render(self.textures if resized is None else dict(self.textures, Radiance=self.textures[resized]))
+        if generate is not None:                                          # App.cpp:1564-1566: behind ToneMap, where DLSS-G is tagged
+            t = self.textures
+            gw, gh = (int(v) for v in generate.settings["OutputSize"])
+            if "Generated" not in t or tuple(t["Generated"].shape) != (gh, gw, 4):
+                t["Generated"] = _torch().zeros((gh, gw, 4), dtype=t["Color"].dtype, device=self.scene.device)
+                t["Generated8"] = _torch().zeros((gh, gw, 4), dtype=_torch().uint8, device=self.scene.device)   # like Display8: four bytes a pixel
+            jitter = np.array(self.gbuffer.GPUBuffers["Camera"]).reshape(())["Jitter"]
+            # the context's settings are this pass's (the same again keep the previous frame)
+            generate.SetConstants(generate.settings)
+            self.generated = generate.Process(jitter, {n: t[n] for n in L.FRAME_GENERATION_TEXTURES})
         self._rendered = True

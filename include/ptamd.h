@@ -916,6 +916,54 @@ int pt_reconstruction_download_history(PtContext* ctx, float* host_length, float
                                                    chooses unasked. The same bytes either way */
 
 /* ------------------------------------------------------------------------------------------
+ * the frame interpolator for the frame-generation slot of App::PostProcessGraphics (Source/App.cpp:1564-1566, :1719-1726), which the
+ * reference's default settings (IsDLSSFrameGenerationEnabled = true, MyAppData.h:295) fill with DLSS-G after the tone-mapped copy: this
+ * library's own motion-compensated interpolator, NOT a port of DLSS-G or FSR 3 (closed or foreign SDKs, not part of the reference tree)
+ * and unpinned against both. DESIGN.md section 1, "Frame generation", is the arithmetic spec (tests/framegenref.py restates it bit for
+ * bit). It reads what the reference tags for DLSS-G -- the tone-mapped Color at OutputSize, LinearDepth and MotionVector at RenderSize
+ * -- and the frame's Camera.Jitter (as it stands in PtCamera: not negated), keeps the frame before it, and writes the frame at phase
+ * Phase between the two. No optical flow, UI mask, reactive mask or presentation pacing: a host displays Generated, then Color.
+ * ------------------------------------------------------------------------------------------ */
+struct PtFrameGenerationSettings {     /* (tagged, not a typedef, like PtUpscalerSettings: C callers write `struct PtFrameGenerationSettings`) */
+    uint32_t RenderSize[2];            /* 1..16384 each: the size of LinearDepth and MotionVector */
+    uint32_t OutputSize[2];            /* 1..16384 each; RenderSize <= OutputSize <= 4 RenderSize per axis: the size of Color and Generated */
+    float    Phase;                    /* default 0.5; (0, 1): 0 would be the previous frame, 1 the current one */
+    float    DepthThreshold;           /* default 0.01; (0, 1]: relative depth difference beyond which a warped sample is rejected */
+    uint32_t _pad[6];
+};                                     /* 48 B */
+struct PtFrameGenerationTextures {     /* full frames, row-major */
+    const void *Color;                                   /* OutputSize: R16G16B16A16_FLOAT, what pt_post_render writes as Color (taken as unjittered) */
+    const void *LinearDepth, *MotionVector;              /* RenderSize: R32_FLOAT, R16G16B16A16_FLOAT, as pt_gbuffer_render writes them */
+    void *Generated;                                     /* OutputSize: R16G16B16A16_FLOAT, alpha 1; must not overlap an input */
+    void *Generated8;                                    /* optional (NULL: not written): R8G8B8A8_UNORM of Generated, by the rule of PtPostTextures.Display8 */
+};
+enum PtFrameGenerationClass {          /* the class byte of an output pixel (pt_frame_generation_download_field) */
+    PT_FRAME_GENERATION_BOTH = 0, PT_FRAME_GENERATION_CURRENT_ONLY = 1, PT_FRAME_GENERATION_PREVIOUS_ONLY = 2, PT_FRAME_GENERATION_FALLBACK = 3
+};
+/* Out-of-range values are refused (PT_ERROR_INVALID_ARGUMENT, the message names the field) and leave the previous settings active.
+ * Settings that differ from the active ones (a size among them) drop the previous frame. */
+int pt_frame_generation_set_constants(PtContext* ctx, const struct PtFrameGenerationSettings* settings);
+/* One frame, enqueued on the context's stream: the clear of the field, the scatter, the resolve, then the copy of Color and LinearDepth
+ * into the context (the caller may overwrite its textures once the call returned). jitter is the Camera.Jitter the frame was rendered
+ * with. Needs no scene. The first call after creation, after pt_frame_generation_reset_history and after a change of settings has no
+ * previous frame: it copies Color to Generated bit for bit (Generated8 from it), keeps the frame and sets *out_generated = 0; later
+ * calls set it to 1. Context-owned and grow-only: the previous Color (8 B per output pixel), the previous LinearDepth (4 B per render
+ * pixel), the midpoint field (8 B per render pixel), the class bytes of the test aid (1 B per output pixel); the previous jitter is
+ * kept beside them. A failed allocation returns PT_ERROR_OUT_OF_MEMORY and changes nothing. Refused with PT_ERROR_INVALID_ARGUMENT and
+ * a message that names the field, nothing written and the history untouched: a NULL required binding (out_generated among them), a
+ * texture not aligned to its texel (LinearDepth and Generated8 4 bytes, the others 8), Generated or Generated8 overlapping an input or
+ * each other, a jitter that is not finite or outside [-0.5, 0.5], a call before pt_frame_generation_set_constants, a sharded context
+ * (the pass is not local: a sharded host runs it on the gathered frame of an unsharded context). */
+int pt_frame_generation_process(PtContext* ctx, const struct PtFrameGenerationTextures* textures, const float jitter[2], uint32_t* out_generated);
+int pt_frame_generation_reset_history(PtContext* ctx);
+/* Test aid, after the last pt_frame_generation_process that generated a frame: host_field, the midpoint field, one 64-bit word per
+ * render pixel (bits(z) << 32 | index of the render pixel that won the cell; all ones: no surface landed there); host_class, one
+ * PtFrameGenerationClass byte per output pixel. The first min(capacity, w * h) of each; a NULL array is skipped. render_out =
+ * output_out = 0 x 0 when the last call generated nothing. Synchronises. */
+int pt_frame_generation_download_field(PtContext* ctx, uint64_t* host_field, uint64_t capacity_render_pixels, uint8_t* host_class,
+                                       uint64_t capacity_output_pixels, uint32_t render_out[2], uint32_t output_out[2]);
+
+/* ------------------------------------------------------------------------------------------
  * the mip chain of an R32_FLOAT texture (MipmapGeneration::SetTexture + Process, Source/MipmapGeneration.ixx ->
  * Shaders/MipmapGeneration.hlsl), which App::PrepareReSTIRDI (Source/App.cpp:1095-1116) runs on the LocalLightPDF texture. The
  * shader is not restated: DESIGN.md section 1, "Local-light PDF texture", is the arithmetic spec (tests/pdfmipref.py restates it).
