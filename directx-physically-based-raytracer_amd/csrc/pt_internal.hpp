@@ -315,6 +315,9 @@ struct Context {
     float fgPrevJitter[2] = { 0.0f, 0.0f };           // the Camera.Jitter of the frame in fgPrevDepth
     bool fgFieldValid = false;                        // the last call generated a frame: field and class bytes are its
 
+    // sharpening (pt_sharpen.hip): the settings alone; the pass has no history and no memory of its own (shState.have is all it uses)
+    PtSharpenSettings sh{}; FilterState shState;
+
     // SHARC radiance cache (pt_sharc.hip): per context, also for a context that views another's scene. sharcVoxels[sharcParity] is VoxelData (this
     // frame's deposits, then the resolved cache), the other one PreviousVoxelData; they swap after the query.
     PtSHARCSettings sharcSettings{}; bool haveSharcSettings = false;

@@ -10,6 +10,7 @@
 //           [--upscale native|quality|balanced|performance|ultra [--output-size WxH] [--out-upscaled file.bin]]
 //           [--reconstruct native|quality|balanced|performance|ultra --output-size WxH [--reconstruct-iterations K] [--out-reconstructed file.bin]]
 //           [--frame-generation [--fg-phase PHI] [--out-generated file.bin] [--png-generated file.png]] [--camera-start X] [--camera-step DX]
+//           [--sharpen [S] [--out-sharpened file.bin]]
 //           [--png file.png] [--out-display file.bin] [--scene descriptor.json [--anim-time T [--anim-step DT]]] [--dump-scene file.bin]
 //
 // --anim-time T (with --scene): the animated render objects of the descriptor (RenderObjects[].Animation) are posed at T seconds of their selected
@@ -65,6 +66,11 @@
 // the two frames (default 0.5). --out-generated writes the frame generated between the last two rendered ones (R16G16B16A16_FLOAT at the
 // output size), --png-generated its 8-bit form as an RGB PNG. Composes with --upscale, --reconstruct, --nrd ... --denoise. On a sequence
 // that does not move the generated frame is the blend of the two.
+// --sharpen [S]: the library's own adaptive sharpener (ptamd.hpp Sharpening; not a port of NVIDIA Image Scaling) runs where the reference
+// runs ProcessNIS (App.cpp:1544-1548): behind --upscale / --reconstruct when given, else behind the frame (rank 0 of a sharded run, on the
+// gathered frame), at the size --post runs at and ahead of it; --post then reads its output. S: Sharpness in [0, 1], default 0.5 (the
+// reference's NIS.Sharpness). --out-sharpened writes the last frame's Sharpened (R16G16B16A16_FLOAT at that size). Composes with
+// --upscale, --reconstruct, --nrd, --post and --frame-generation.
 // --camera-start X --camera-step DX (one unsharded process): timed frame f is rendered from the scene's camera moved by X + f DX along world
 // x, with the pose of frame f - 1 in the camera's Previous* members (the motion vectors follow); the warm-up frame stands at X.
 //
@@ -457,6 +463,7 @@ int main(int argc, char** argv)
     std::string reconstruct, reconstructedPath; int reconstructIterations = -1;
     bool frameGeneration = false; float fgPhase = 0.5f; std::string generatedPath, generatedPngPath;
     bool cameraMoves = false; double cameraStart = 0.0, cameraStep = 0.0;
+    bool sharpen = false; float sharpness = 0.5f; std::string sharpenedPath;
     for (int i = 1; i < argc; i++) {
         std::string k = argv[i];
         if (k == "--di") { di = true; continue; }                  // the flags without a value
@@ -471,6 +478,11 @@ int main(int argc, char** argv)
         if (k == "--hdr") { hdr = true; continue; }
         if (k == "--denoise") { denoise = true; continue; }
         if (k == "--frame-generation") { frameGeneration = true; continue; }
+        if (k == "--sharpen") {                                    // its value is optional: a following word that is not a flag
+            sharpen = true;
+            if (i + 1 < argc && strncmp(argv[i + 1], "--", 2) != 0) sharpness = (float)atof(argv[++i]);
+            continue;
+        }
         if (i + 1 >= argc) break;
         const char* v = argv[++i];
         if (k == "--width") W = atoi(v); else if (k == "--height") H = atoi(v);
@@ -493,6 +505,7 @@ int main(int argc, char** argv)
         else if (k == "--reconstruct") reconstruct = v; else if (k == "--out-reconstructed") reconstructedPath = v;
         else if (k == "--reconstruct-iterations") reconstructIterations = atoi(v);
         else if (k == "--fg-phase") fgPhase = (float)atof(v); else if (k == "--out-generated") generatedPath = v; else if (k == "--png-generated") generatedPngPath = v;
+        else if (k == "--out-sharpened") sharpenedPath = v;
         else if (k == "--camera-start") { cameraMoves = true; cameraStart = atof(v); } else if (k == "--camera-step") { cameraMoves = true; cameraStep = atof(v); }
         else if (k == "--anim-time") { animate = true; animTime = atof(v); } else if (k == "--anim-step") animStep = atof(v);
     }
@@ -538,6 +551,7 @@ int main(int argc, char** argv)
             if (hdr && !generatedPngPath.empty()) throw std::invalid_argument("--png-generated writes an SDR image: drop --hdr");
         } else if (fgPhase != 0.5f || !generatedPath.empty() || !generatedPngPath.empty())
             throw std::invalid_argument("--fg-phase, --out-generated and --png-generated need --frame-generation");
+        if (!sharpen && !sharpenedPath.empty()) throw std::invalid_argument("--out-sharpened needs --sharpen");
         if (cameraMoves && sharded) throw std::invalid_argument("--camera-start / --camera-step need one unsharded process");
         int deviceCount = 0;
         HIP_OK(hipGetDeviceCount(&deviceCount));
@@ -722,6 +736,15 @@ int main(int argc, char** argv)
                                         alloc(outPx * 8) };
             if (runPost) postProcessing.Textures.Radiance = reconstruction.Textures.Color;
         }
+        Sharpening sharpening(commandList);
+        const bool runSharpen = sharpen && rank == 0;
+        if (runSharpen) {                                           // App.cpp:1544-1548: ProcessNIS's place, between the upscaler and Bloom
+            Sharpening::Settings s; s.Size[0] = outW; s.Size[1] = outH; s.Sharpness = sharpness;
+            sharpening.SetConstants(s);
+            sharpening.Textures = { upscaling ? upscaler.Textures.Color : reconstructing ? reconstruction.Textures.Color : sharded ? fullRadiance : tx.Radiance,
+                                    alloc(outPx * 8) };
+            if (runPost) postProcessing.Textures.Radiance = sharpening.Textures.Sharpened;
+        }
         FrameGeneration generation(commandList);
         bool generated = false;                                     // the last frame's Generated is an interpolated frame
         if (frameGeneration) {                                      // App.cpp:1564-1566: behind ToneMap, where the reference tags DLSS-G's inputs
@@ -864,6 +887,7 @@ int main(int argc, char** argv)
                 reconstruction.Textures.NormalRoughness = tx.NormalRoughness; reconstruction.Textures.LinearDepth = tx.LinearDepth;
                 reconstruction.Process(commandList, jitter);
             }
+            if (runSharpen) sharpening.Process(commandList);
             if (runPost) postProcessing.Render(commandList);
             if (frameGeneration) {                                  // the restir swap may have moved LinearDepth
                 generation.Textures.LinearDepth = tx.LinearDepth;
@@ -938,6 +962,13 @@ int main(int argc, char** argv)
             HIP_OK(hipMemcpy(host.data(), reconstruction.Textures.Color, outPx * 8, hipMemcpyDeviceToHost));
             FILE* fp = fopen(reconstructedPath.c_str(), "wb");
             if (!fp || fwrite(host.data(), 8, outPx, fp) != outPx) { fprintf(stderr, "cannot write %s\n", reconstructedPath.c_str()); if (fp) fclose(fp); return 3; }
+            fclose(fp);
+        }
+        if (runSharpen && !sharpenedPath.empty()) {                 // the sharpener's output of the last frame
+            std::vector<uint16_t> host(outPx * 4);
+            HIP_OK(hipMemcpy(host.data(), sharpening.Textures.Sharpened, outPx * 8, hipMemcpyDeviceToHost));
+            FILE* fp = fopen(sharpenedPath.c_str(), "wb");
+            if (!fp || fwrite(host.data(), 8, outPx, fp) != outPx) { fprintf(stderr, "cannot write %s\n", sharpenedPath.c_str()); if (fp) fclose(fp); return 3; }
             fclose(fp);
         }
         if (frameGeneration && !generated) throw std::runtime_error("--frame-generation: the last frame generated nothing");

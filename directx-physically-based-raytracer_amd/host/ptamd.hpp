@@ -13,6 +13,7 @@
 //     struct Upscaler            the library's own temporal upscaler for the super-resolution step (where the reference calls DLSS or XeSS)
 //     struct Reconstruction      the library's own denoising upscaler for the ray-reconstruction step (where the reference calls DLSS-RR)
 //     struct FrameGeneration     the library's own frame interpolator for the frame-generation step (where the reference calls DLSS-G)
+//     struct Sharpening          the library's own adaptive sharpener for the image-scaling step (where the reference calls NIS)
 // Error behaviour: a failing status becomes the exception type the reference throws at the same place
 // (std::invalid_argument for argument checks, std::system_error otherwise: Source/ErrorHelpers.ixx:16-32).
 // Header-only, plain C++20 (std::span), no HIP headers needed by the including translation unit.
@@ -809,6 +810,36 @@ struct FrameGeneration {
         if (!field.empty())
             ThrowIfFailed(m_context, pt_frame_generation_download_field(m_context, field.data(), field.size(), classes.data(), classes.size(), render, output));
     }
+
+private:
+    PtContext* m_context;
+};
+
+// The library's own edge-adaptive sharpening filter for the image-scaling step of App::PostProcessGraphics (App::ProcessNIS,
+// Source/App.cpp:1544-1548, :1756-1766), between the upscaler and Bloom, where the reference runs NVIDIA Image Scaling in its sharpen mode
+// with NIS.Sharpness (pt_sharpen_*; DESIGN.md section 1, "Sharpening"): from the linear HDR Color the post chain would read to Sharpened,
+// which the post chain then reads. Not a port of NVIDIA Image Scaling, and unpinned against it. No history and no memory of its own; a
+// sharded host runs it on the gathered frame.
+static_assert(sizeof(PtSharpenSettings) == 32, "PtSharpenSettings is 32 B");
+struct Sharpening {
+    struct Settings {
+        uint32_t Size[2]{};                                                 // the size the post chain runs at
+        float Sharpness = 0.5f, ContrastFloor = 0.015625f;                  // [0, 1] (NIS.Sharpness) | [2^-10, 0.5]
+    };
+
+    PtSharpenTextures Textures{};
+
+    explicit Sharpening(CommandList& commandList) : m_context(commandList.Context) {}
+
+    void SetConstants(const Settings& settings)
+    {
+        PtSharpenSettings s{};
+        s.Size[0] = settings.Size[0]; s.Size[1] = settings.Size[1];
+        s.Sharpness = settings.Sharpness; s.ContrastFloor = settings.ContrastFloor;
+        ThrowIfFailed(m_context, pt_sharpen_set_constants(m_context, &s));
+    }
+
+    void Process(CommandList& commandList) { ThrowIfFailed(commandList.Context, pt_sharpen_process(commandList.Context, &Textures)); }
 
 private:
     PtContext* m_context;

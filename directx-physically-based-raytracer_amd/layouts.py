@@ -596,6 +596,46 @@ def frame_generation_settings(render_size, output_size, **overrides):
     return check_frame_generation_settings(s)
 
 
+SHARPEN_SETTINGS = np.dtype({  # PtSharpenSettings, 32 B
+    "names": ["Size", "Sharpness", "ContrastFloor", "_pad"],
+    "formats": [("<u4", 2), "<f4", "<f4", ("<u4", 4)],
+    "offsets": [0, 8, 12, 16], "itemsize": 32})
+assert SHARPEN_SETTINGS.itemsize == 32
+SHARPEN_TEXTURES = ["Color", "Sharpened"]       # PtSharpenTextures member order: two pointers
+SHARPEN_DEFAULTS = {"Sharpness": 0.5, "ContrastFloor": 0.015625}
+SHARPEN_MAX_SIZE = 16384
+SHARPEN_MIN_CONTRAST_FLOOR = 2.0 ** -10
+
+
+def check_sharpen_settings(s):
+    """The range checks of pt_sharpen_set_constants, on the float32 values the library receives: ValueError where it answers
+    PT_ERROR_INVALID_ARGUMENT (a value that is not finite is out of every range)."""
+    s = np.asarray(s).reshape(())
+    if not all(1 <= int(v) <= SHARPEN_MAX_SIZE for v in s["Size"]):
+        raise ValueError(f"Size must be 1..{SHARPEN_MAX_SIZE} on both axes")
+    if not 0.0 <= float(np.float32(s["Sharpness"])) <= 1.0:
+        raise ValueError("Sharpness must be in [0, 1]")
+    if not SHARPEN_MIN_CONTRAST_FLOOR <= float(np.float32(s["ContrastFloor"])) <= 0.5:
+        raise ValueError("ContrastFloor must be in [2^-10, 0.5]")
+    return s
+
+
+def sharpen_settings(size, **overrides):
+    """PtSharpenSettings with the defaults of SHARPEN_DEFAULTS; overrides by field name. Refuses what pt_sharpen_set_constants refuses."""
+    s = np.zeros((), SHARPEN_SETTINGS)
+    if len(size) != 2 or not all(0 <= int(v) <= 0xFFFFFFFF for v in size):
+        raise ValueError("Size is not a pair of 32-bit unsigned values")
+    s["Size"] = tuple(int(v) for v in size)
+    values = dict(SHARPEN_DEFAULTS)
+    for k, v in overrides.items():
+        if k not in values:
+            raise ValueError(f"PtSharpenSettings has no field {k}")
+        values[k] = v
+    for k, v in values.items():
+        s[k] = v
+    return check_sharpen_settings(s)
+
+
 SHARC_SETTINGS = np.dtype({  # PtSHARCSettings: SHARC::Constants + Raytracing::SHARCSettings (Source/MyAppData.h:250-262)
     "names": ["AccumulationFrames", "MaxStaleFrames", "SceneScale", "IsAntiFireflyEnabled", "DownscaleFactor", "RoughnessThreshold",
               "IsHashGridVisualizationEnabled"],

@@ -37,6 +37,7 @@ EXPORTS = [
     "pt_upscaler_render_size", "pt_upscaler_jitter",
     "pt_reconstruction_set_constants", "pt_reconstruction_process", "pt_reconstruction_reset_history", "pt_reconstruction_download_history",
     "pt_frame_generation_set_constants", "pt_frame_generation_process", "pt_frame_generation_reset_history", "pt_frame_generation_download_field",
+    "pt_sharpen_set_constants", "pt_sharpen_process",
     "pt_anim_create_rig", "pt_anim_release_rig", "pt_anim_create_object", "pt_anim_release_object", "pt_anim_evaluate",
     "pt_anim_skeletal_transforms", "pt_anim_download_globals", "pt_anim_download_skeletal", "pt_anim_debug_slerp",
     "pt_sharc_configure", "pt_sharc_set_constants", "pt_raytrace_render_sharc", "pt_sharc_reset", "pt_sharc_download",
@@ -97,6 +98,10 @@ class ReconstructionTextures(C.Structure):   # PtReconstructionTextures: eight p
 
 class FrameGenerationTextures(C.Structure): # PtFrameGenerationTextures: five pointers
     _fields_ = [(n, C.c_void_p) for n in L.FRAME_GENERATION_TEXTURES]
+
+
+class SharpenTextures(C.Structure):         # PtSharpenTextures: two pointers
+    _fields_ = [(n, C.c_void_p) for n in L.SHARPEN_TEXTURES]
 
 
 class Sharding(C.Structure):
@@ -264,6 +269,8 @@ def load_library():
         lib.pt_frame_generation_reset_history.argtypes = [C.c_void_p]
         lib.pt_frame_generation_download_field.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.pt_sharpen_set_constants.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pt_sharpen_process.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_sharc_configure.argtypes = [C.c_void_p, C.c_uint32]
         lib.pt_sharc_set_constants.argtypes = [C.c_void_p, C.c_void_p]
         lib.pt_raytrace_render_sharc.argtypes = [C.c_void_p, C.c_void_p]
@@ -1320,6 +1327,34 @@ class FrameGeneration(_Filter):
         return field, classes
 
 
+class Sharpening(_Filter):
+    """The library's own edge-adaptive sharpening filter for the image-scaling slot of App::PostProcessGraphics (pt_sharpen_*; DESIGN.md
+    section 1, "Sharpening"), where the reference runs App::ProcessNIS (NVIDIA Image Scaling in its sharpen mode) between the upscaler and
+    Bloom. Not a port of NVIDIA Image Scaling, and unpinned against it. From the linear HDR Color the post chain would read to Sharpened,
+    the same format and size: a high-pass across the edges of the 5 x 5's row, column and diagonals, gated by the contrast of the 3 x 3 and
+    limited to its range. Process takes the textures by the names of layouts.SHARPEN_TEXTURES (a missing name is an unbound texture). No
+    history, no context-owned memory; no scene is needed. Runs on the full frame: a sharded host calls it on the gathered one."""
+    _DTYPE, _RECORD, _LAYOUT = L.SHARPEN_SETTINGS, "PtSharpenSettings", "sharpen_settings"
+    _SET = "pt_sharpen_set_constants"
+
+    @property
+    def settings(self):
+        """the PtSharpenSettings record last accepted, or None"""
+        return self._settings
+
+    def SetConstants(self, settings):
+        """settings: PtSharpenSettings (layouts.sharpen_settings)."""
+        self._set_constants(settings)
+
+    def ResetHistory(self):
+        """the pass keeps nothing between calls"""
+
+    def Process(self, textures=None):
+        tex = self.Textures if textures is None else textures
+        t = SharpenTextures(*[_ptr(tex.get(n)) for n in L.SHARPEN_TEXTURES])
+        self.ctx.check(self.ctx.lib.pt_sharpen_process(self.ctx.handle, C.addressof(t)))
+
+
 class SHARC:
     """Mirror of `struct SHARC` (Source/SHARC.ixx) and of the Raytracing::Render overload that takes it: Configure allocates the context's
     cache, SetConstants takes PtSHARCSettings (layouts.sharc_settings), Render runs clear, update, resolve, query and the swap with the
@@ -1461,10 +1496,22 @@ class Renderer:
         g.SetConstants(L.frame_generation_settings((self.width, self.height), (output_w, output_h), **overrides))
         return g
 
+    def sharpening(self, w, h, **overrides):
+        """A new Sharpening at w x h (the size post= runs at: the upscaler's or the reconstruction's OutputSize, else the renderer's), with
+        layouts.sharpen_settings' defaults (overrides by field name): render(..., sharpen=that). It writes textures["Sharpened"]."""
+        s = Sharpening(self.ctx)
+        s.Textures = self.textures
+        s.SetConstants(L.sharpen_settings((w, h), **overrides))
+        return s
+
     def render(self, settings, di_samples=0, di_reuse=None, di_light_sampling=None, post=None, sharc=None, di_visibility=None, di_pairwise=None,
                di_regir_layout=None, di_brdf=None, nrd=None, denoise=None, nrd_hit_distance=None, di_pdf_mipmap=None, upscale=None,
-               reconstruct=None, generate=None):
-        """generate: a FrameGeneration (self.frame_generation(output_w, output_h)) to run the frame-generation step of
+               reconstruct=None, generate=None, sharpen=None):
+        """sharpen: a Sharpening (self.sharpening(w, h)) to run the image-scaling step of App::PostProcessGraphics (ProcessNIS,
+        App.cpp:1544-1548) after upscale= / reconstruct= when given, else after the frame, and before post: it reads the texture post=
+        would have read (Upscaled, Reconstructed, else Radiance) and writes textures["Sharpened"], which post=, when given, then reads
+        as its Radiance. Its Size must be the size post= runs at. None: no such step, nothing changes.
+        generate: a FrameGeneration (self.frame_generation(output_w, output_h)) to run the frame-generation step of
         App::PostProcessGraphics (App.cpp:1564-1566) after the post chain: it reads textures["Color"] (post= is required, at the pass's
         OutputSize), the frame's LinearDepth and MotionVector and the camera's Jitter and writes textures["Generated"] and
         ["Generated8"]; self.generated tells whether that is an interpolated frame (False on the frame without a predecessor: a copy of
@@ -1543,6 +1590,13 @@ class Renderer:
                 raise PtInvalidArgument("the frame generation's RenderSize differs from the renderer's size")
             if tuple(int(v) for v in generate.settings["OutputSize"]) != tuple(int(v) for v in p["RenderSize"]):
                 raise PtInvalidArgument("the frame generation's OutputSize differs from the post-processing RenderSize")
+        if sharpen is not None:
+            if not isinstance(sharpen, Sharpening) or sharpen.settings is None:
+                raise PtInvalidArgument("sharpen must be a Sharpening whose constants are set (Renderer.sharpening)")
+            if getattr(self.ctx, "sharding", (0, 1, 16))[1] > 1:
+                raise PtInvalidArgument("sharpening needs the whole frame: the context is sharded (run Sharpening on the gathered frame)")
+            if tuple(int(v) for v in sharpen.settings["Size"]) != ((self.width, self.height) if out_w is None else (out_w, out_h)):
+                raise PtInvalidArgument("the sharpening's Size differs from the size the post chain runs at")
         if self.di_history and self._rendered:
             for n in L.DI_PREVIOUS_TEXTURES:
                 c = n[len("Previous"):]
@@ -1616,12 +1670,19 @@ class Renderer:
             # the context's settings are this pass's (the same again keep the history): they size what the call writes
             reconstruct.SetConstants(reconstruct.settings)
             reconstruct.Process(jitter, dict({n: t[n] for n in L.RECONSTRUCTION_TEXTURES[:-1]}, Color=t["Reconstructed"]))
+        if sharpen is not None:                                           # App.cpp:1544-1548: ProcessNIS, between the upscaler and Bloom
+            t = self.textures
+            source = "Upscaled" if upscale is not None else "Reconstructed" if reconstruct is not None else "Radiance"
+            if "Sharpened" not in t or tuple(t["Sharpened"].shape) != tuple(t[source].shape):
+                t["Sharpened"] = _torch().zeros(tuple(t[source].shape), dtype=t[source].dtype, device=self.scene.device)
+            sharpen.SetConstants(sharpen.settings)                        # the context's settings are this pass's
+            sharpen.Process({"Color": t[source], "Sharpened": t["Sharpened"]})
         if post is not None:                                              # App.cpp:1506-1571, after Raytracing::Render
             pw, ph = (out_w, out_h) if upscale is not None or reconstruct is not None else (self.width, self.height)
             if "Color" not in self.textures or tuple(self.textures["Color"].shape[:2]) != (ph, pw):
                 self.textures.update(alloc_post_textures(pw, ph, self.scene.device))
             self.post.SetConstants(post)
-            resized = "Upscaled" if upscale is not None else "Reconstructed" if reconstruct is not None else None
+            resized = "Sharpened" if sharpen is not None else "Upscaled" if upscale is not None else "Reconstructed" if reconstruct is not None else None
             self.post.Render(self.textures if resized is None else dict(self.textures, Radiance=self.textures[resized]))
         if generate is not None:                                          # App.cpp:1564-1566: behind ToneMap, where DLSS-G is tagged
             t = self.textures

@@ -964,6 +964,35 @@ int pt_frame_generation_download_field(PtContext* ctx, uint64_t* host_field, uin
                                        uint64_t capacity_output_pixels, uint32_t render_out[2], uint32_t output_out[2]);
 
 /* ------------------------------------------------------------------------------------------
+ * the sharpening filter for the image-scaling slot of App::PostProcessGraphics (App::ProcessNIS, Source/App.cpp:1544-1548, :1756-1766),
+ * which the reference fills with NVIDIA Image Scaling in its sharpen mode (sl::NISMode::eSharpen, NIS.Sharpness, MyAppData.h:297-303)
+ * between the upscaler and Bloom: this library's own edge-adaptive sharpener, NOT a port of NVIDIA Image Scaling (Streamline's NIS
+ * plugin, a binary the reference tree does not carry) and unpinned against it. DESIGN.md section 1, "Sharpening", is the arithmetic
+ * spec (tests/sharpenref.py restates it bit for bit). It works on the linear HDR colour the post chain would otherwise read: a
+ * high-pass along the row, the column and the two diagonals of the 5 x 5, combined by the luminance gradient across each (across the
+ * edge, not along it), gated by the Michelson contrast of the 3 x 3 and limited to the 3 x 3 range of the input (no overshoot). No
+ * scaler mode, no chromatic aberration, no history, no context-owned memory.
+ * ------------------------------------------------------------------------------------------ */
+struct PtSharpenSettings {             /* (tagged, not a typedef, like PtUpscalerSettings: C callers write `struct PtSharpenSettings`) */
+    uint32_t Size[2];                  /* 1..16384 each: the size of Color and Sharpened, the size the post chain runs at */
+    float    Sharpness;                /* default 0.5; [0, 1]: the reference's NIS.Sharpness and its clamp; 0 returns the (guarded) input */
+    float    ContrastFloor;            /* default 0.015625; [2^-10, 0.5]: the 3 x 3's Michelson contrast below which nothing is sharpened; full strength at twice it */
+    uint32_t _pad[4];
+};                                     /* 32 B */
+struct PtSharpenTextures {             /* full frames, row-major */
+    const void *Color;                 /* R16G16B16A16_FLOAT, linear HDR: what pt_post_render would read as Radiance */
+    void *Sharpened;                   /* R16G16B16A16_FLOAT, alpha 1; must not overlap Color */
+};
+/* Out-of-range or non-finite values are refused (PT_ERROR_INVALID_ARGUMENT, the message names the field) and leave the previous settings
+ * active. */
+int pt_sharpen_set_constants(PtContext* ctx, const struct PtSharpenSettings* settings);
+/* One frame, one kernel enqueued on the context's stream. Needs no scene and allocates nothing. Ignores the sharding, as pt_post_render
+ * does: the taps reach two rows beyond a band, so a sharded host runs it on the gathered frame. Refused with PT_ERROR_INVALID_ARGUMENT
+ * and a message, nothing written: NULL textures or a NULL texture, a texture not aligned to its texel (8 bytes), Sharpened overlapping
+ * Color (the taps read neighbours), a call before pt_sharpen_set_constants. */
+int pt_sharpen_process(PtContext* ctx, const struct PtSharpenTextures* textures);
+
+/* ------------------------------------------------------------------------------------------
  * the mip chain of an R32_FLOAT texture (MipmapGeneration::SetTexture + Process, Source/MipmapGeneration.ixx ->
  * Shaders/MipmapGeneration.hlsl), which App::PrepareReSTIRDI (Source/App.cpp:1095-1116) runs on the LocalLightPDF texture. The
  * shader is not restated: DESIGN.md section 1, "Local-light PDF texture", is the arithmetic spec (tests/pdfmipref.py restates it).
